@@ -17,17 +17,26 @@ work fixed: strong scaling).  --config picks another shape (CONFIGS below; c1 = 
 reference's own bench shapes, one point per call: the plumbing).
 
 Prints ONE JSON line on rank 0 (contract in the task statement), including
+  ms_per_step  -- wall time of one timed step (host clock around the steps, ended
+                  by a device synchronise);
   roofline     -- dominant kernel: algorithmic flops (2*N*D per query, SURVEY.md
                   8d) / its average hipEvent duration, against the MFMA peak of
                   the dtype the kernel contracts in (bf16 first tier: 2516.8 TFLOP/s);
                   traffic = HBM bytes per launch from the committed rocprofv3 --pmc
-                  record of the same configuration (profiles/*pmc*.json), else null;
-  verified     -- after the timed region the step's answers are checked (order,
-                  range, duplicates, distances re-derived by the scalar metric, a
-                  sample against the oracle's brute force and 2048 queries against
-                  the exact engine); --no-verify skips it (profiling runs);
+                  record of the same configuration (profiles/*pmc*.json), else null.
+A plain run sets up, warms up, times the steps and prints the line ("verified":
+null).  --full adds, after the timed region:
+  verified     -- the step's answers are checked (order, range, duplicates,
+                  distances re-derived by the scalar metric, a sample against the
+                  oracle's brute force and 2048 queries against the exact engine);
+                  --no-verify skips it (profiling runs);
   cpu_baseline -- the CPU oracle's faithful ball tree ("port": the reference is
-                  Rust and cannot be built here) timed on this host's cores.
+                  Rust and cannot be built here) timed on this host's cores;
+                  --no-cpu-baseline skips it;
+  device_api   -- with --mode radius, the same queries timed again through
+                  pn_query_radius_device_f32.
+--dump-outputs DIR writes the answers of the last timed step as DIR/<name>.npy
+(dump_outputs below), so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -70,6 +79,8 @@ CONFIGS = {
 PEAK_F32_MFMA_TFLOPS = 157.3  # /opt/skills/guides/MI355X_MICROARCH.md, "Peak FP32 (matrix)"
 PEAK_BF16_MFMA_TFLOPS = 2516.8  # same table: dense BF16 MFMA = 16 x the f32 matrix rate ("~2.5 PF dense")
 SEED_P, SEED_Q = 0x5EED0001, 0x5EED0002
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files together, .npy headers included
+DUMP_SAMPLE_SEED = 0x5EED0D0D
 
 
 def usable_cores():
@@ -278,6 +289,46 @@ def committed_kernel_split(config_key):
         return None
 
 
+def dump_outputs(out_dir, nq, per_query, lists=None):
+    """--dump-outputs: what the timed path returned in its last step, as out_dir/<name>.npy in float32 or float64
+    (indices as float64: exact below 2^53).  per_query: {name: array with one row per query}; lists: the radius
+    mode's CSR (offsets, ids), written as offsets.npy and ids.npy.  When everything would exceed DUMP_LIMIT_BYTES, the
+    queries are taken in a fixed seeded order until the limit, sorted, and written as query_rows.npy; the arrays keep
+    those rows only and the CSR is rebuilt over them.  Returns the names written."""
+    os.makedirs(out_dir, exist_ok=True)
+    n_files = len(per_query) + 1 + (2 if lists is not None else 0)  # + query_rows.npy when sampled
+    budget = DUMP_LIMIT_BYTES - 128 * n_files - 8  # np.save's 128-byte headers; the CSR's closing offset
+    arrays = {}
+    for name, a in per_query.items():
+        a = np.asarray(a)
+        arrays[name] = np.ascontiguousarray(a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+        assert arrays[name].shape[0] == nq, (name, arrays[name].shape)
+    cost = np.zeros(nq, dtype=np.int64)  # bytes each query adds to the dump
+    for a in arrays.values():
+        cost += a[0].nbytes if nq else 0
+    if lists is not None:
+        off = np.asarray(lists[0]).astype(np.int64)
+        ids = np.asarray(lists[1]).astype(np.float64)
+        cost += 8 + 8 * np.diff(off)
+    rows = None
+    if int(cost.sum()) > budget:
+        order = np.random.default_rng(DUMP_SAMPLE_SEED).permutation(nq)
+        keep = int(np.searchsorted(np.cumsum(cost[order] + 8), budget, side="right"))  # + 8: its entry in query_rows
+        rows = np.sort(order[:keep])
+        arrays = {name: a[rows] for name, a in arrays.items()}
+        arrays["query_rows"] = rows.astype(np.float64)
+    if lists is not None:
+        if rows is not None:
+            starts, counts = off[rows], off[rows + 1] - off[rows]
+            new_off = np.concatenate([[0], np.cumsum(counts)])
+            ids = ids[np.repeat(starts - new_off[:-1], counts) + np.arange(int(new_off[-1]))]
+            off = new_off
+        arrays["offsets"], arrays["ids"] = off.astype(np.float64), ids
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def bench_f64(args):
     """--dtype f64: the same k-NN step on an f64 index (the reference is generic over A and its own harness is f64,
     benches/ball_tree.rs:9-13): the bf16 MFMA filter over the f64 corpus' tile images, then the f64 re-rank, proof and
@@ -321,8 +372,10 @@ def bench_f64(args):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     st = tree.stats()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, nq, {"indices": out_idx.cpu().numpy(), "distances": out_dst.cpu().numpy()})
     verified = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         verified = {"ok": True, "checks": []}
 
         def chk(name, ok):
@@ -393,7 +446,7 @@ def bench_f64(args):
         "candidates_per_query": round(st["candidates"] / max(st["queries"], 1), 2),
         "exact_evaluations_per_query": round(st["evaluations"] / max(st["queries"], 1), 2),
     }
-    if not args.no_verify:  # the exact scan on the verification sample, for scale (one un-warmed call: an upper bound)
+    if verified is not None:  # the exact scan on the verification sample, for scale (one un-warmed call: an upper bound)
         line["exact_scan_ms_per_query_1024"] = round(exact_ms_per_query, 5)
     emit(line)
 
@@ -493,6 +546,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS) + ["c1"])
     ap.add_argument("--engine", default="auto", choices=["auto", "exact", "mfma", "bf16"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also the parity leg, the CPU baseline and (--mode radius) the device-API "
+                         "leg; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's answers as DIR/<name>.npy (float32/float64, at most 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--segments", type=int, default=0)
     ap.add_argument("--slots", type=int, default=0, help="PN_OPT_FILTER_SLOTS (k' of the MFMA filter); 0 = auto")
@@ -518,6 +576,10 @@ def main():
     ap.add_argument("--comm", default="abi", choices=["abi", "torch"],
                     help="abi: the all-gather is RCCL behind the C ABI (pn_sharded_*); torch: torch.distributed")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.config == "c1":
+        ap.error("--config c1 has no step whose answers --dump-outputs could write")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # Bare `python bench.py --gpus N`: this parent has made NO GPU call (importing torch and parsing flags does
@@ -661,9 +723,14 @@ def main():
         elapsed = float(t.item())
     st = tree.stats() if tree is not None else {"hot_launches": 0, "hot_ms": 0.0, "fallback_queries": 0, "candidates": 0,
                                                  "queries": 0, "evaluations": 0}
+    if args.dump_outputs and rank == 0:  # every rank holds the full answer
+        if args.mode == "radius":
+            dump_outputs(args.dump_outputs, nq, {}, lists=out)
+        else:
+            dump_outputs(args.dump_outputs, nq, {"indices": out[0].cpu().numpy(), "distances": out[1].cpu().numpy()})
 
     radius_device = None
-    if args.mode == "radius":
+    if args.mode == "radius" and args.full:
         # the same queries through pn_query_radius_device_* (queries and CSR in HBM, counts scanned on the device, nothing
         # read back inside the timed region), side by side with the host API's number above
         total = int(out[0][-1])
@@ -685,12 +752,13 @@ def main():
                          "ms_per_step": round(el_d / args.steps * 1e3, 4), "value": round(nq * args.steps / el_d, 1),
                          "unit": "queries/s", "capacity": cap, "equals_host_api": bool(same)}
     verified = None
-    if not args.no_verify and args.mode == "radius":
+    do_verify = args.full and not args.no_verify
+    if do_verify and args.mode == "radius":
         verified = verify_radius(out, q_host, n, dim, nq, radius, tree)
         if radius_device is not None and not radius_device["equals_host_api"]:
             verified["ok"] = False
             verified["checks"].append("device API == host API: FAILED")
-    elif not args.no_verify:
+    elif do_verify:
         verified = verify(out, queries, n, dim, nq, k, rank, world, index, gen)
         if dist:
             v = torch.tensor([1 if verified["ok"] else 0], dtype=torch.int32, device=dev)
@@ -778,7 +846,7 @@ def main():
             "candidates_per_query": round(st["candidates"] / max(st["queries"], 1), 2),
             "exact_evaluations_per_query": round(st["evaluations"] / max(st["queries"], 1), 2),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cb = cpu_baseline(n, dim, k, gpu_out=out if args.mode == "knn" else None)
             line["cpu_baseline"] = cb
             if cb.get("agrees_with_gpu") is False:  # the tree walk and the GPU disagree outside exact ties: not verified

@@ -2,7 +2,8 @@
 query tiles -- against corpora of 120-300 thousand rows, the bf16 tier with the seed model against the exact engine on every
 query, bit for bit.  Test infrastructure."""
 import sys, os, numpy as np
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo")); sys.path.insert(0, os.path.join(os.environ.get("GRAFT_REPO_ROOT", "/root/repo"), "tests"))
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, _ROOT); sys.path.insert(0, os.path.join(_ROOT, "tests"))
 import petal_neighbors_amd as pn
 from conftest import uniform
 bad = 0
