@@ -1,7 +1,10 @@
 //! UNVERIFIED SOURCE (no rustc in the build image).
 //! What `bindgen` emits from `include/petal_mi355x.h` (ABI version 2), trimmed to what `lib.rs` calls.
 #![allow(non_camel_case_types)]
-use std::os::raw::{c_char, c_int, c_void};
+use std::os::raw::{c_char, c_int, c_uint, c_void};
+
+/// `flags` of the radius calls with distances: each list by (distance, index) ascending
+pub const PN_RADIUS_SORTED: c_uint = 1;
 
 #[repr(C)]
 pub struct pn_index {
@@ -39,6 +42,39 @@ extern "C" {
                                q_row_stride: isize, radius: f32, offsets: *mut u64, idx_out: *mut *mut u64) -> c_int;
     pub fn pn_query_radius_f64(index: *const pn_index, queries: *const f64, nq: usize, q_cols: usize,
                                q_row_stride: isize, radius: f64, offsets: *mut u64, idx_out: *mut *mut u64) -> c_int;
+    /// flags: 0 = ascending index, PN_RADIUS_SORTED = by (distance, index); *dist_out released with pn_free
+    pub fn pn_query_radius_with_distance_f32(index: *const pn_index, queries: *const f32, nq: usize, q_cols: usize,
+                                             q_row_stride: isize, radius: f32, flags: c_uint, offsets: *mut u64,
+                                             idx_out: *mut *mut u64, dist_out: *mut *mut f32) -> c_int;
+    pub fn pn_query_radius_with_distance_f64(index: *const pn_index, queries: *const f64, nq: usize, q_cols: usize,
+                                             q_row_stride: isize, radius: f64, flags: c_uint, offsets: *mut u64,
+                                             idx_out: *mut *mut u64, dist_out: *mut *mut f64) -> c_int;
+    pub fn pn_query_radius_with_distance_device_f32(index: *const pn_index, d_queries: *const f32, nq: usize,
+                                                    q_cols: usize, q_row_stride: usize, radius: f32, flags: c_uint,
+                                                    d_offsets: *mut u64, d_idx: *mut u64, d_dist: *mut f32,
+                                                    capacity: usize, d_total: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn pn_query_radius_with_distance_device_f64(index: *const pn_index, d_queries: *const f64, nq: usize,
+                                                    q_cols: usize, q_row_stride: usize, radius: f64, flags: c_uint,
+                                                    d_offsets: *mut u64, d_idx: *mut u64, d_dist: *mut f64,
+                                                    capacity: usize, d_total: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn pn_sharded_query_radius_with_distance_f32(sharded: *const pn_sharded, queries: *const f32, nq: usize,
+                                                     q_cols: usize, q_row_stride: isize, radius: f32, flags: c_uint,
+                                                     offsets: *mut u64, idx_out: *mut *mut u64,
+                                                     dist_out: *mut *mut f32) -> c_int;
+    pub fn pn_sharded_query_radius_with_distance_f64(sharded: *const pn_sharded, queries: *const f64, nq: usize,
+                                                     q_cols: usize, q_row_stride: isize, radius: f64, flags: c_uint,
+                                                     offsets: *mut u64, idx_out: *mut *mut u64,
+                                                     dist_out: *mut *mut f64) -> c_int;
+    pub fn pn_sharded_query_radius_with_distance_device_f32(sharded: *const pn_sharded, d_queries: *const f32, nq: usize,
+                                                            q_cols: usize, q_row_stride: usize, radius: f32,
+                                                            flags: c_uint, d_offsets: *mut u64, d_idx: *mut u64,
+                                                            d_dist: *mut f32, capacity: usize, d_total: *mut u64,
+                                                            stream: *mut c_void) -> c_int;
+    pub fn pn_sharded_query_radius_with_distance_device_f64(sharded: *const pn_sharded, d_queries: *const f64, nq: usize,
+                                                            q_cols: usize, q_row_stride: usize, radius: f64,
+                                                            flags: c_uint, d_offsets: *mut u64, d_idx: *mut u64,
+                                                            d_dist: *mut f64, capacity: usize, d_total: *mut u64,
+                                                            stream: *mut c_void) -> c_int;
 
     pub fn pn_pairwise_f32(x: *const f32, n_rows: usize, n_cols: usize, row_stride: isize, device: c_int,
                            out: *mut f32) -> c_int;

@@ -38,6 +38,9 @@ pub trait Elem: Copy + Default + PartialOrd + 'static {
     #[doc(hidden)]
     unsafe fn radius(ix: *const ffi::pn_index, q: *const Self, qc: usize, r: Self, off: *mut u64, out: *mut *mut u64) -> c_int;
     #[doc(hidden)]
+    unsafe fn radius_wd(ix: *const ffi::pn_index, q: *const Self, qc: usize, r: Self, flags: std::os::raw::c_uint,
+                        off: *mut u64, out: *mut *mut u64, dout: *mut *mut Self) -> c_int;
+    #[doc(hidden)]
     unsafe fn radius_of(ix: *const ffi::pn_index, n: u64, out: *mut Self) -> c_int;
     #[doc(hidden)]
     unsafe fn lower_bound(ix: *const ffi::pn_index, a: u64, b: u64, out: *mut Self) -> c_int;
@@ -49,8 +52,8 @@ pub trait Elem: Copy + Default + PartialOrd + 'static {
     unsafe fn pairwise(x: *const Self, n: usize, d: usize, rs: isize, cosine: bool, out: *mut Self) -> c_int;
 }
 macro_rules! impl_elem {
-    ($t:ty, $create:ident, $create_cos:ident, $query:ident, $radius:ident, $rad_of:ident, $lb:ident, $eu:ident, $reu:ident,
-     $cos:ident, $pw:ident, $pwc:ident) => {
+    ($t:ty, $create:ident, $create_cos:ident, $query:ident, $radius:ident, $radius_wd:ident, $rad_of:ident, $lb:ident,
+     $eu:ident, $reu:ident, $cos:ident, $pw:ident, $pwc:ident) => {
         impl Elem for $t {
             unsafe fn create(p: *const Self, n: usize, d: usize, rs: isize, cs: isize, cosine: bool, out: *mut *mut ffi::pn_index) -> c_int {
                 if cosine { ffi::$create_cos(p, n, d, rs, cs, 0, out) } else { ffi::$create(p, n, d, rs, cs, 0, out) }
@@ -60,6 +63,10 @@ macro_rules! impl_elem {
             }
             unsafe fn radius(ix: *const ffi::pn_index, q: *const Self, qc: usize, r: Self, off: *mut u64, out: *mut *mut u64) -> c_int {
                 ffi::$radius(ix, q, 1, qc, qc as isize, r, off, out)
+            }
+            unsafe fn radius_wd(ix: *const ffi::pn_index, q: *const Self, qc: usize, r: Self, flags: std::os::raw::c_uint,
+                                off: *mut u64, out: *mut *mut u64, dout: *mut *mut Self) -> c_int {
+                ffi::$radius_wd(ix, q, 1, qc, qc as isize, r, flags, off, out, dout)
             }
             unsafe fn radius_of(ix: *const ffi::pn_index, n: u64, out: *mut Self) -> c_int { ffi::$rad_of(ix, n, out) }
             unsafe fn lower_bound(ix: *const ffi::pn_index, a: u64, b: u64, out: *mut Self) -> c_int { ffi::$lb(ix, a, b, out) }
@@ -73,10 +80,12 @@ macro_rules! impl_elem {
         }
     };
 }
-impl_elem!(f32, pn_index_create_f32, pn_index_create_cosine_f32, pn_query_f32, pn_query_radius_f32, pn_tree_radius_of_f32,
+impl_elem!(f32, pn_index_create_f32, pn_index_create_cosine_f32, pn_query_f32, pn_query_radius_f32,
+           pn_query_radius_with_distance_f32, pn_tree_radius_of_f32,
            pn_tree_node_distance_lower_bound_f32, pn_euclidean_f32, pn_reuclidean_f32, pn_cosine_f32, pn_pairwise_f32,
            pn_pairwise_cosine_f32);
-impl_elem!(f64, pn_index_create_f64, pn_index_create_cosine_f64, pn_query_f64, pn_query_radius_f64, pn_tree_radius_of_f64,
+impl_elem!(f64, pn_index_create_f64, pn_index_create_cosine_f64, pn_query_f64, pn_query_radius_f64,
+           pn_query_radius_with_distance_f64, pn_tree_radius_of_f64,
            pn_tree_node_distance_lower_bound_f64, pn_euclidean_f64, pn_reuclidean_f64, pn_cosine_f64, pn_pairwise_f64,
            pn_pairwise_cosine_f64);
 
@@ -188,6 +197,25 @@ impl<'a, A: Elem, M: Metric<A>> BallTree<'a, A, M> {
         let v = unsafe { std::slice::from_raw_parts(out, off[1] as usize) }.iter().map(|&i| i as usize).collect();
         unsafe { ffi::pn_free(out as *mut _) };
         v
+    }
+    /// extension: `query_radius` with each neighbour's distance (bit-identical to the metric's); ascending indices, or
+    /// nearest first by (distance, index) -- the order of `query` -- with `sorted`
+    pub fn query_radius_with_distance<S: Data<Elem = A>>(&self, point: &ArrayBase<S, Ix1>, distance: A,
+                                                         sorted: bool) -> (Vec<usize>, Vec<A>) {
+        let q = point.as_standard_layout();
+        let mut off = [0u64; 2];
+        let mut out: *mut u64 = std::ptr::null_mut();
+        let mut dout: *mut A = std::ptr::null_mut();
+        let flags = if sorted { ffi::PN_RADIUS_SORTED } else { 0 };
+        ok(unsafe { A::radius_wd(self.handle, q.as_ptr(), q.len(), distance, flags, off.as_mut_ptr(), &mut out, &mut dout) });
+        let n = off[1] as usize;
+        let idx = unsafe { std::slice::from_raw_parts(out, n) }.iter().map(|&i| i as usize).collect();
+        let dist = unsafe { std::slice::from_raw_parts(dout, n) }.to_vec();
+        unsafe {
+            ffi::pn_free(out as *mut _);
+            ffi::pn_free(dout as *mut _);
+        }
+        (idx, dist)
     }
     /// extension: the rows of `queries` in ONE call (what the GPU is for); (nq, min(k, n)) indices and distances
     pub fn query_batch(&self, queries: ArrayView2<A>, k: usize) -> (Array2<u64>, Array2<A>) {

@@ -55,7 +55,9 @@ extern "C" {
 
 /* 3 (round 4): + pn_query_radius_device_*, pn_sharded_query_radius_device_*, pn_bf16_selftest,
  * pn_debug_seed_model_feedback, PN_OPT_BF16_WAVES, PN_OPT_SEED_MODEL, pn_info.seed_model (the former reserved word);
- * PN_OPT_MFMA_STRUCTURE = 1 is now PN_ERR_INVALID.  Everything of version 2 is unchanged. */
+ * PN_OPT_MFMA_STRUCTURE = 1 is now PN_ERR_INVALID.  Everything of version 2 is unchanged.
+ * Additive within version 3 (callers detect them by symbol): pn_query_radius_with_distance_{,device_}{f32,f64},
+ * pn_sharded_query_radius_with_distance_{,device_}{f32,f64}, PN_RADIUS_SORTED. */
 #define PN_ABI_VERSION 3
 
 /* ---- error codes.  EMPTY / NOT_CONTIGUOUS are ArrayError (src/lib.rs:9-16). */
@@ -241,6 +243,36 @@ int pn_query_radius_device_f64(const pn_index *index, const double *d_queries, s
                                size_t q_row_stride, double radius, uint64_t *d_offsets, uint64_t *d_idx, size_t capacity,
                                uint64_t *d_total, void *stream);
 
+/* ---- radius with distances: the lists of pn_query_radius_* (same index sets, same edge cases -- r <= 0, NaN, +inf,
+ * Cosine r >= 1 --, index_base, pn_stats.radius_results) and, next to every index, its distance: bit-identical to the
+ * reference's metric.distance(q, p) in the index's element type (Euclidean: the sequential unfused fold over
+ * min(q_cols, dim) coordinates and a correctly rounded sqrt; Cosine: the three sums and 1 - dot / (|a| |b|)).
+ * flags: 0 = each list in ascending index order, as pn_query_radius_*; PN_RADIUS_SORTED = each list nearest-first, by
+ * (distance, index) ascending -- the k-NN answers' order, so the first k entries of a list of at least k equal
+ * pn_query_*'s answer.  Any other bit: PN_ERR_INVALID.
+ * Host entry points: offsets [nq + 1] caller-allocated; *idx_out and *dist_out allocated by the library (pn_free). */
+#define PN_RADIUS_SORTED 1
+int pn_query_radius_with_distance_f32(const pn_index *index, const float *queries, size_t nq, size_t q_cols,
+                                      ptrdiff_t q_row_stride, float radius, unsigned flags, uint64_t *offsets,
+                                      uint64_t **idx_out, float **dist_out);
+int pn_query_radius_with_distance_f64(const pn_index *index, const double *queries, size_t nq, size_t q_cols,
+                                      ptrdiff_t q_row_stride, double radius, unsigned flags, uint64_t *offsets,
+                                      uint64_t **idx_out, double **dist_out);
+/* Device entry points: the contract of pn_query_radius_device_* (complete offsets, entries below `capacity` written,
+ * capacity = 0 only counts), d_dist [capacity] next to d_idx; d_dist must not be NULL when capacity > 0.  With
+ * PN_RADIUS_SORTED and a total above the capacity, every list that lies wholly below the capacity is complete and
+ * sorted; the list that straddles the capacity holds its first entries in ascending index order, unsorted.  A sorted
+ * call that may meet a list longer than 2048 entries reserves scratch for min(capacity, nq * n_points) entries in the
+ * handle's workspace. */
+int pn_query_radius_with_distance_device_f32(const pn_index *index, const float *d_queries, size_t nq, size_t q_cols,
+                                             size_t q_row_stride, float radius, unsigned flags, uint64_t *d_offsets,
+                                             uint64_t *d_idx, float *d_dist, size_t capacity, uint64_t *d_total,
+                                             void *stream);
+int pn_query_radius_with_distance_device_f64(const pn_index *index, const double *d_queries, size_t nq, size_t q_cols,
+                                             size_t q_row_stride, double radius, unsigned flags, uint64_t *d_offsets,
+                                             uint64_t *d_idx, double *d_dist, size_t capacity, uint64_t *d_total,
+                                             void *stream);
+
 /* ---- distance::pairwise(x, &Euclidean) (src/distance.rs:58-74): n x n
  * symmetric matrix, zero diagonal, n < 2 -> zeros. Host in, host out. */
 int pn_pairwise_f32(const float *x, size_t n_rows, size_t n_cols, ptrdiff_t row_stride, int device,
@@ -396,6 +428,24 @@ int pn_sharded_query_radius_device_f32(const pn_sharded *sharded, const float *d
 int pn_sharded_query_radius_device_f64(const pn_sharded *sharded, const double *d_queries, size_t nq, size_t q_cols,
                                        size_t q_row_stride, double radius, uint64_t *d_offsets, uint64_t *d_idx,
                                        size_t capacity, uint64_t *d_total, void *stream);
+/* pn_query_radius_with_distance_* over all shards: the lists of pn_sharded_query_radius_* with their distances (global
+ * rows); PN_RADIUS_SORTED: each query's list by (distance, global row), merged from the shards' sorted lists.  With one
+ * process per GPU the distances travel by a second padded all-gather of the lists' shape. */
+int pn_sharded_query_radius_with_distance_f32(const pn_sharded *sharded, const float *queries, size_t nq, size_t q_cols,
+                                              ptrdiff_t q_row_stride, float radius, unsigned flags, uint64_t *offsets,
+                                              uint64_t **idx_out, float **dist_out);
+int pn_sharded_query_radius_with_distance_f64(const pn_sharded *sharded, const double *queries, size_t nq, size_t q_cols,
+                                              ptrdiff_t q_row_stride, double radius, unsigned flags, uint64_t *offsets,
+                                              uint64_t **idx_out, double **dist_out);
+/* pn_query_radius_with_distance_device_* on a handle with ONE shard; several shards: PN_ERR_UNSUPPORTED */
+int pn_sharded_query_radius_with_distance_device_f32(const pn_sharded *sharded, const float *d_queries, size_t nq,
+                                                     size_t q_cols, size_t q_row_stride, float radius, unsigned flags,
+                                                     uint64_t *d_offsets, uint64_t *d_idx, float *d_dist,
+                                                     size_t capacity, uint64_t *d_total, void *stream);
+int pn_sharded_query_radius_with_distance_device_f64(const pn_sharded *sharded, const double *d_queries, size_t nq,
+                                                     size_t q_cols, size_t q_row_stride, double radius, unsigned flags,
+                                                     uint64_t *d_offsets, uint64_t *d_idx, double *d_dist,
+                                                     size_t capacity, uint64_t *d_total, void *stream);
 
 /* ---- diagnostic: the first-tier filter's lower bounds themselves.  bounds_out[q * n_rows + i] = L'(q, p_i)
  * for the first n_rows corpus rows (clamped to n_points), with L' + qnorm_out[q] <= |q - p_i|^2 in real

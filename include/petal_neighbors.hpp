@@ -199,6 +199,24 @@ class BallTree {
         pn_free(out);
         return v;
     }
+    // extension: query_radius with each neighbour's distance (pn_query_radius_with_distance_*); ascending indices, or
+    // nearest first by (distance, index) with sorted = true
+    std::pair<std::vector<size_t>, std::vector<A>> query_radius_with_distance(const A *point, size_t len, A distance,
+                                                                              bool sorted) const {
+        uint64_t off[2] = {0, 0};
+        uint64_t *out = nullptr;
+        A *dout = nullptr;
+        const unsigned flags = sorted ? PN_RADIUS_SORTED : 0u;
+        if constexpr (std::is_same<A, float>::value)
+            check(pn_query_radius_with_distance_f32(h_, point, 1, len, (ptrdiff_t)len, distance, flags, off, &out, &dout));
+        else
+            check(pn_query_radius_with_distance_f64(h_, point, 1, len, (ptrdiff_t)len, distance, flags, off, &out, &dout));
+        std::pair<std::vector<size_t>, std::vector<A>> r(std::vector<size_t>(out, out + off[1]),
+                                                         std::vector<A>(dout, dout + off[1]));
+        pn_free(out);
+        pn_free(dout);
+        return r;
+    }
     // extension: a batch of points per call (row-major queries), results nq x min(k, n)
     void query_batch(const A *queries, size_t nq, size_t len, size_t k, uint64_t *idx_out, A *dist_out) const {
         if constexpr (std::is_same<A, float>::value)
@@ -248,6 +266,14 @@ inline int sh_radius(const pn_sharded *h, const float *q, size_t len, float r, u
 inline int sh_radius(const pn_sharded *h, const double *q, size_t len, double r, uint64_t *off, uint64_t **out) {
     return pn_sharded_query_radius_f64(h, q, 1, len, (ptrdiff_t)len, r, off, out);
 }
+inline int sh_radius_wd(const pn_sharded *h, const float *q, size_t len, float r, unsigned fl, uint64_t *off, uint64_t **out,
+                        float **dout) {
+    return pn_sharded_query_radius_with_distance_f32(h, q, 1, len, (ptrdiff_t)len, r, fl, off, out, dout);
+}
+inline int sh_radius_wd(const pn_sharded *h, const double *q, size_t len, double r, unsigned fl, uint64_t *off,
+                        uint64_t **out, double **dout) {
+    return pn_sharded_query_radius_with_distance_f64(h, q, 1, len, (ptrdiff_t)len, r, fl, off, out, dout);
+}
 }  // namespace detail
 template <typename A>
 class ShardedBallTreeT {
@@ -281,6 +307,19 @@ class ShardedBallTreeT {
         std::vector<size_t> v(out, out + off[1]);
         pn_free(out);
         return v;
+    }
+    // query_radius_with_distance over all shards (global rows); nearest first by (distance, row) with sorted = true
+    std::pair<std::vector<size_t>, std::vector<A>> query_radius_with_distance(const A *point, size_t len, A distance,
+                                                                              bool sorted) const {
+        uint64_t off[2] = {0, 0};
+        uint64_t *out = nullptr;
+        A *dout = nullptr;
+        check(detail::sh_radius_wd(h_, point, len, distance, sorted ? PN_RADIUS_SORTED : 0u, off, &out, &dout));
+        std::pair<std::vector<size_t>, std::vector<A>> r(std::vector<size_t>(out, out + off[1]),
+                                                         std::vector<A>(dout, dout + off[1]));
+        pn_free(out);
+        pn_free(dout);
+        return r;
     }
 };
 using ShardedBallTree = ShardedBallTreeT<float>;

@@ -22,6 +22,7 @@ PN_OPT_EXCHANGE_ALWAYS = 7
 PN_OPT_SHARED_THRESHOLDS = 8
 PN_OPT_BF16_WAVES = 9
 PN_OPT_SEED_MODEL = 10
+PN_RADIUS_SORTED = 1
 
 
 class PnInfo(C.Structure):
@@ -75,6 +76,14 @@ SIGNATURES = {
     "pn_query_radius_device_f32": (_i, [_vp, _vp, _sz, _sz, _sz, C.c_float, _vp, _vp, _sz, _vp, _vp]),
     "pn_query_radius_device_f64": (_i, [_vp, _vp, _sz, _sz, _sz, C.c_double, _vp, _vp, _sz, _vp, _vp]),
     "pn_query_radius_f64": (_i, [_vp, _vp, _sz, _sz, _ssz, C.c_double, _vp, C.POINTER(_vp)]),
+    "pn_query_radius_with_distance_f32": (_i, [_vp, _vp, _sz, _sz, _ssz, C.c_float, C.c_uint, _vp, C.POINTER(_vp),
+                                               C.POINTER(_vp)]),
+    "pn_query_radius_with_distance_f64": (_i, [_vp, _vp, _sz, _sz, _ssz, C.c_double, C.c_uint, _vp, C.POINTER(_vp),
+                                               C.POINTER(_vp)]),
+    "pn_query_radius_with_distance_device_f32": (_i, [_vp, _vp, _sz, _sz, _sz, C.c_float, C.c_uint, _vp, _vp, _vp, _sz,
+                                                      _vp, _vp]),
+    "pn_query_radius_with_distance_device_f64": (_i, [_vp, _vp, _sz, _sz, _sz, C.c_double, C.c_uint, _vp, _vp, _vp, _sz,
+                                                      _vp, _vp]),
     "pn_free": (None, [_vp]),
     "pn_pairwise_f32": (_i, [_vp, _sz, _sz, _ssz, _i, _vp]),
     "pn_pairwise_f64": (_i, [_vp, _sz, _sz, _ssz, _i, _vp]),
@@ -124,6 +133,14 @@ SIGNATURES = {
     "pn_sharded_query_f64": (_i, [_vp, _vp, _sz, _sz, _ssz, _sz, _vp, _vp]),
     "pn_sharded_query_device_f64": (_i, [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, _vp]),
     "pn_sharded_query_radius_f64": (_i, [_vp, _vp, _sz, _sz, _ssz, C.c_double, _vp, C.POINTER(_vp)]),
+    "pn_sharded_query_radius_with_distance_f32": (_i, [_vp, _vp, _sz, _sz, _ssz, C.c_float, C.c_uint, _vp,
+                                                       C.POINTER(_vp), C.POINTER(_vp)]),
+    "pn_sharded_query_radius_with_distance_f64": (_i, [_vp, _vp, _sz, _sz, _ssz, C.c_double, C.c_uint, _vp,
+                                                       C.POINTER(_vp), C.POINTER(_vp)]),
+    "pn_sharded_query_radius_with_distance_device_f32": (_i, [_vp, _vp, _sz, _sz, _sz, C.c_float, C.c_uint, _vp, _vp,
+                                                              _vp, _sz, _vp, _vp]),
+    "pn_sharded_query_radius_with_distance_device_f64": (_i, [_vp, _vp, _sz, _sz, _sz, C.c_double, C.c_uint, _vp, _vp,
+                                                              _vp, _sz, _vp, _vp]),
 }
 
 _lib = None

@@ -257,6 +257,39 @@ class BallTree:
         _, idx = self.query_radius_batch(self._queries(point, True), distance)
         return idx
 
+    def query_radius_with_distance_batch(self, queries, distance, sort: bool = False):
+        """``query_radius_batch`` plus each neighbour's distance (``pn_query_radius_with_distance_*``):
+        ``(offsets uint64 [nq+1], idx uint64, dist)``.  The lists are ascending by index, or by (distance, index) --
+        nearest first, the k-NN order -- with ``sort=True``."""
+        a = self._queries(queries, False)
+        nq, qc = a.shape
+        offsets = np.zeros(nq + 1, dtype=np.uint64)
+        out_i, out_d = C.c_void_p(0), C.c_void_p(0)
+        r = C.c_float(distance) if self._sfx == "f32" else C.c_double(distance)
+        flags = _lib.PN_RADIUS_SORTED if sort else 0
+        fn = getattr(_lib.lib(), f"pn_query_radius_with_distance_{self._sfx}")
+        try:
+            check(fn(self._h, a.ctypes.data, nq, qc, max(qc, 1), r, flags, offsets.ctypes.data, C.byref(out_i),
+                     C.byref(out_d)))
+            total = int(offsets[-1])
+            idx = np.empty(0, dtype=np.uint64)
+            dist = np.empty(0, dtype=self.dtype)
+            if total:
+                idx = np.frombuffer((C.c_uint64 * total).from_address(out_i.value), dtype=np.uint64).copy()
+                ct = C.c_float if self._sfx == "f32" else C.c_double
+                dist = np.frombuffer((ct * total).from_address(out_d.value), dtype=self.dtype).copy()
+        finally:
+            for p in (out_i, out_d):
+                if p.value:
+                    _lib.lib().pn_free(p)
+        return offsets, idx, dist
+
+    def query_radius_with_distance(self, point, distance, sort: bool = False):
+        """``query_radius(point, distance)`` and the distance of each neighbour: ``(idx, dist)``, ascending by index, or
+        nearest first (by (distance, index)) with ``sort=True``."""
+        _, idx, dist = self.query_radius_with_distance_batch(self._queries(point, True), distance, sort)
+        return idx, dist
+
     # --------------------------------------------------------- device-resident
     def query_radius_device(self, queries, distance, capacity: int, out_offsets=None, out_idx=None, out_total=None,
                             stream=None):
@@ -282,6 +315,37 @@ class BallTree:
         check(fn(self._h, queries.data_ptr() if nq * qc else None, nq, qc, queries.stride(0) if nq > 1 else max(qc, 1), r,
                  offs.data_ptr(), idx.data_ptr(), int(capacity), tot.data_ptr(), C.c_void_p(st)))
         return offs, idx, tot
+
+    def query_radius_with_distance_device(self, queries, distance, capacity: int, sort: bool = False, out_offsets=None,
+                                          out_idx=None, out_dist=None, out_total=None, stream=None):
+        """``query_radius_device`` plus each neighbour's distance (``pn_query_radius_with_distance_device_*``):
+        ``(offsets int64 [nq+1], idx int64 [capacity], dist [capacity], total int64 [1])`` as CUDA tensors.  With
+        ``sort=True`` every list lying wholly below ``capacity`` is ordered by (distance, index); a list straddling the
+        capacity is left unsorted."""
+        import torch
+        tdt = torch.float32 if self._sfx == "f32" else torch.float64
+        if not isinstance(queries, torch.Tensor) or queries.dtype != tdt or queries.dim() != 2 or not queries.is_cuda:
+            raise ValueError("queries must be a 2-D CUDA tensor of the tree's element type")
+        if int(capacity) < 0:
+            raise ValueError("capacity must be >= 0")
+        if queries.shape[1] > 1 and queries.stride(1) != 1:
+            queries = queries.contiguous()
+        nq, qc = queries.shape
+        dev = queries.device
+        cap = max(int(capacity), 1)
+        offs = out_offsets if out_offsets is not None else torch.empty(nq + 1, dtype=torch.int64, device=dev)
+        idx = out_idx if out_idx is not None else torch.empty(cap, dtype=torch.int64, device=dev)
+        dist = out_dist if out_dist is not None else torch.empty(cap, dtype=tdt, device=dev)
+        tot = out_total if out_total is not None else torch.empty(1, dtype=torch.int64, device=dev)
+        if dist.dtype != tdt or idx.numel() < int(capacity) or dist.numel() < int(capacity) or offs.numel() < nq + 1:
+            raise ValueError("output tensors are too small or of the wrong type")
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        r = C.c_float(distance) if self._sfx == "f32" else C.c_double(distance)
+        flags = _lib.PN_RADIUS_SORTED if sort else 0
+        fn = getattr(_lib.lib(), f"pn_query_radius_with_distance_device_{self._sfx}")
+        check(fn(self._h, queries.data_ptr() if nq * qc else None, nq, qc, queries.stride(0) if nq > 1 else max(qc, 1), r,
+                 flags, offs.data_ptr(), idx.data_ptr(), dist.data_ptr(), int(capacity), tot.data_ptr(), C.c_void_p(st)))
+        return offs, idx, dist, tot
 
     def query_device(self, queries, k: int, out_idx=None, out_dist=None, stream=None):
         """k-NN with queries and results in HBM (torch CUDA tensors of the tree's element type; indices as int64)."""

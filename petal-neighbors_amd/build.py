@@ -40,6 +40,7 @@ UNITS = [
     ("bf16_filter.hip", []),
     ("sharded.hip", []),
     ("radius_device.hip", []),
+    ("csr_sort.hip", []),
     ("metric.cpp", ["-ffp-contract=off"]),
     ("tree.cpp", ["-ffp-contract=off"]),
 ]

@@ -324,12 +324,14 @@ hipError_t launch_exact_knn_f64(const double *P, size_t n, int dim, size_t ldp, 
 // into offsets; pass 2 writes indices in row order: within a tile the 16 lanes
 // that share a query scan their per-lane counts with stride-4 shuffles.
 // ---------------------------------------------------------------------------
-template <typename T, bool FILL, bool COS>
+template <typename T, bool FILL, bool COS, bool WD = false>
 __global__ __launch_bounds__(256) void exact_radius_kernel(
     const T *__restrict__ P, size_t n, int dim, size_t ldp, const T *__restrict__ Q, int nq, size_t ldq, T r,
     size_t seg_len, int nseg, uint32_t *__restrict__ counts, const uint64_t *__restrict__ offsets,
     uint64_t *__restrict__ fill, uint64_t index_base, const T *__restrict__ pnorm, const T *__restrict__ qnorm,
-    const uint32_t *__restrict__ qsel, const uint32_t *__restrict__ nq_dev, uint64_t capacity) {
+    const uint32_t *__restrict__ qsel, const uint32_t *__restrict__ nq_dev, uint64_t capacity, T *__restrict__ fill_dist) {
+    // fill_dist (WD: FILL with distances): each written row's distance, the d it was compared by, at the same position
+    // (a template flag: the index-only fill keeps its registers)
     // qsel / nq_dev (nullable; the device-resident entry point, pn_query_radius_device_*): query r of the launch is row
     // qsel[r] of Q and only the first *nq_dev listed queries exist -- the grid is sized for nq and surplus tiles leave at
     // once; counts / offsets are indexed by r.  capacity: positions at or beyond it are counted, not written.
@@ -409,7 +411,11 @@ __global__ __launch_bounds__(256) void exact_radius_kernel(
 #pragma unroll
                 for (int b = 0; b < 4; ++b)
                     if (mask[a] & (1u << b)) {
-                        if (pos < capacity) fill[pos] = index_base + (uint64_t)(p0 + pb + b);
+                        if (pos < capacity) {
+                            fill[pos] = index_base + (uint64_t)(p0 + pb + b);
+                            // (the d compared above: the same expression of the same operands)
+                            if (WD) fill_dist[pos] = COS ? (T)1 - acc[a][b] / (qn4[a] * pn4[b]) : pn_sqrt(acc[a][b]);
+                        }
                         ++pos;
                     }
             }
@@ -429,15 +435,17 @@ static hipError_t launch_exact_radius(const T *P, size_t n, int dim, size_t ldp,
                                       T r, size_t seg_len, int nseg, uint32_t *counts, const uint64_t *offsets,
                                       uint64_t *fill, uint64_t index_base, const T *pnorm, const T *qnorm,
                                       hipStream_t s, const uint32_t *qsel = nullptr, const uint32_t *nq_dev = nullptr,
-                                      uint64_t capacity = ~0ull) {
+                                      uint64_t capacity = ~0ull, T *fill_dist = nullptr) {
     dim3 grid((unsigned)(round_up((size_t)nq, kTileQ) / kTileQ), (unsigned)nseg), block(256);
-#define PN_RAD(FF, CC)                                                                                          \
-    hipLaunchKernelGGL((exact_radius_kernel<T, FF, CC>), grid, block, 0, s, P, n, dim, ldp, Q, nq, ldq, r, seg_len, \
-                       nseg, counts, offsets, fill, index_base, pnorm, qnorm, qsel, nq_dev, capacity)
-    if (fill) {
-        if (pnorm) PN_RAD(true, true); else PN_RAD(true, false);
+#define PN_RAD(FF, CC, WW)                                                                                          \
+    hipLaunchKernelGGL((exact_radius_kernel<T, FF, CC, WW>), grid, block, 0, s, P, n, dim, ldp, Q, nq, ldq, r, seg_len, \
+                       nseg, counts, offsets, fill, index_base, pnorm, qnorm, qsel, nq_dev, capacity, fill_dist)
+    if (fill && fill_dist) {
+        if (pnorm) PN_RAD(true, true, true); else PN_RAD(true, false, true);
+    } else if (fill) {
+        if (pnorm) PN_RAD(true, true, false); else PN_RAD(true, false, false);
     } else {
-        if (pnorm) PN_RAD(false, true); else PN_RAD(false, false);
+        if (pnorm) PN_RAD(false, true, false); else PN_RAD(false, false, false);
     }
 #undef PN_RAD
     return hipGetLastError();
@@ -446,17 +454,17 @@ hipError_t launch_exact_radius_f32(const float *P, size_t n, int dim, size_t ldp
                                    size_t ldq, float r, size_t seg_len, int nseg, uint32_t *counts,
                                    const uint64_t *offsets, uint64_t *fill, uint64_t index_base, const float *pnorm,
                                    const float *qnorm, hipStream_t s, const uint32_t *qsel, const uint32_t *nq_dev,
-                                   uint64_t capacity) {
+                                   uint64_t capacity, float *fill_dist) {
     return launch_exact_radius<float>(P, n, dim, ldp, Q, nq, ldq, r, seg_len, nseg, counts, offsets, fill,
-                                      index_base, pnorm, qnorm, s, qsel, nq_dev, capacity);
+                                      index_base, pnorm, qnorm, s, qsel, nq_dev, capacity, fill_dist);
 }
 hipError_t launch_exact_radius_f64(const double *P, size_t n, int dim, size_t ldp, const double *Q, int nq,
                                    size_t ldq, double r, size_t seg_len, int nseg, uint32_t *counts,
                                    const uint64_t *offsets, uint64_t *fill, uint64_t index_base, const double *pnorm,
                                    const double *qnorm, hipStream_t s, const uint32_t *qsel, const uint32_t *nq_dev,
-                                   uint64_t capacity) {
+                                   uint64_t capacity, double *fill_dist) {
     return launch_exact_radius<double>(P, n, dim, ldp, Q, nq, ldq, r, seg_len, nseg, counts, offsets, fill,
-                                       index_base, pnorm, qnorm, s, qsel, nq_dev, capacity);
+                                       index_base, pnorm, qnorm, s, qsel, nq_dev, capacity, fill_dist);
 }
 
 // ---------------------------------------------------------------------------

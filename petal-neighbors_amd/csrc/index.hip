@@ -140,6 +140,8 @@ struct Workspace {
     DevBuf w_hq, w_hidx, w_hdist;  // staging of the host entry points (queries up, results down)
     DevBuf w_fparts;               // second tier, many-segment path: per-group partial results
     DevBuf w_rpos, w_rfin, w_rcx, w_rox, w_rscan;  // pn_query_radius_device_*: list positions, counts, per-segment counts / offsets, scan scratch
+    DevBuf w_rkd;  // pn_query_radius_with_distance_*: the filter tier's kept rows' distances ([2][nq][kept_stride])
+    DevBuf w_cs_nch, w_cs_off, w_cs_scan, w_cs_idx, w_cs_dist, w_cs_hoff;  // PN_RADIUS_SORTED: csr_sort.hip's scratch
     // small calls (tiny_*): mapped pinned host memory the one kernel of the call reads its queries from and writes its
     // answers to -- no copy commands
     void *pin_in = nullptr, *pin_out = nullptr;
@@ -165,7 +167,7 @@ struct Workspace {
     hipEvent_t done = nullptr;
     hipStream_t last_stream = nullptr;
     bool in_flight = false;
-    DevBuf *all[36] = {&w_gqn, &w_rpos, &w_rfin, &w_rcx, &w_rox, &w_rscan, &w_q, &w_qnorm, &w_qnrm, &w_keys, &w_idx, &w_cnt, &w_tau, &w_flags, &w_sel, &w_misc, &w2_keys, &w2_idx,
+    DevBuf *all[43] = {&w_cs_hoff, &w_rkd, &w_cs_nch, &w_cs_off, &w_cs_scan, &w_cs_idx, &w_cs_dist, &w_gqn, &w_rpos, &w_rfin, &w_rcx, &w_rox, &w_rscan, &w_q, &w_qnorm, &w_qnrm, &w_keys, &w_idx, &w_cnt, &w_tau, &w_flags, &w_sel, &w_misc, &w2_keys, &w2_idx,
                        &w2_cnt, &w2_tau, &w_lo, &w_bq, &w_qn, &w_qbad, &w_gq, &w_gidx, &w_gdist, &w_gsel, &w_seed,
                        &w_qstat, &w_lists, &w_hq, &w_hidx, &w_hdist, &w_fparts, &w_pcnt};
     std::vector<void *> retired;  // outgrown allocations, freed once `done` has passed (DevBuf::ensure)
@@ -2345,15 +2347,17 @@ static int tiny_knn(const pn_index *ix, Workspace &ws, hipStream_t s, const T *q
 }
 template <typename T>
 static int tiny_radius(const pn_index *ix, Workspace &ws, hipStream_t s, const T *q, size_t nq, size_t q_cols,
-                       ptrdiff_t q_stride, T radius, uint64_t *offsets, uint64_t **idx_out) {
+                       ptrdiff_t q_stride, T radius, uint64_t *offsets, uint64_t **idx_out, T **dist_out = nullptr) {
     const size_t dim_eff = q_cols < ix->dim ? q_cols : ix->dim, qc = q_cols ? q_cols : 1;
     const T *Qd = nullptr;
     PNCHK(tiny_stage<T>(ws, q, nq, q_cols, q_stride, &Qd));
-    const size_t os = ix->n + 1;  // per query: count, then up to n rows
-    PNCHK(ws.pin_ensure(&ws.pin_out, &ws.pin_out_bytes, nq * os * sizeof(uint64_t)));
+    const size_t os = ix->n + 1;  // per query: count, then up to n rows (and, behind all of them, their distances)
+    const size_t ib = nq * os * sizeof(uint64_t);
+    PNCHK(ws.pin_ensure(&ws.pin_out, &ws.pin_out_bytes, ib + (dist_out ? nq * os * sizeof(T) : 0)));
     void *od = nullptr;
     HIPCHK(hipHostGetDevicePointer(&od, ws.pin_out, 0));
-    HIPCHK(tiny_launch<T>(ix, dim_eff, Qd, qc, nq, 0, true, radius, (uint64_t *)od, (T *)nullptr, os, s));
+    HIPCHK(tiny_launch<T>(ix, dim_eff, Qd, qc, nq, 0, true, radius, (uint64_t *)od,
+                          dist_out ? (T *)((char *)od + ib) : (T *)nullptr, os, s));
     HIPCHK(hipStreamSynchronize(s));
     const uint64_t *h = (const uint64_t *)ws.pin_out;
     uint64_t total = 0;
@@ -2365,6 +2369,16 @@ static int tiny_radius(const pn_index *ix, Workspace &ws, hipStream_t s, const T
     uint64_t *out = (uint64_t *)malloc((total ? total : 1) * sizeof(uint64_t));
     if (!out) return fail(PN_ERR_NOMEM, "malloc(%llu results) failed", (unsigned long long)total);
     for (size_t a = 0; a < nq; ++a) memcpy(out + offsets[a], h + a * os + 1, (size_t)h[a * os] * sizeof(uint64_t));
+    if (dist_out) {
+        T *dout = (T *)malloc((total ? total : 1) * sizeof(T));
+        if (!dout) {
+            free(out);
+            return fail(PN_ERR_NOMEM, "malloc(%llu distances) failed", (unsigned long long)total);
+        }
+        const T *hd = (const T *)((const char *)ws.pin_out + ib);
+        for (size_t a = 0; a < nq; ++a) memcpy(dout + offsets[a], hd + a * os + 1, (size_t)h[a * os] * sizeof(T));
+        *dist_out = dout;
+    }
     *idx_out = out;
     std::lock_guard<std::mutex> lk(ix->sh.mu);
     ix->sh.stats.radius_results += total;
@@ -2525,32 +2539,84 @@ template <> struct RadOps<float> {
     static hipError_t run(const float *P, size_t n, int dim, size_t ldp, const float *Q, int nq, size_t ldq, float r,
                           size_t seg_len, int nseg, uint32_t *counts, const uint64_t *offs, uint64_t *fill,
                           uint64_t base, const float *pn, const float *qn, hipStream_t s, const uint32_t *qsel = nullptr,
-                          const uint32_t *nq_dev = nullptr, uint64_t capacity = ~0ull) {
+                          const uint32_t *nq_dev = nullptr, uint64_t capacity = ~0ull, float *fill_dist = nullptr) {
         return launch_exact_radius_f32(P, n, dim, ldp, Q, nq, ldq, r, seg_len, nseg, counts, offs, fill, base, pn, qn, s, qsel,
-                                       nq_dev, capacity);
+                                       nq_dev, capacity, fill_dist);
     }
 };
 template <> struct RadOps<double> {
     static hipError_t run(const double *P, size_t n, int dim, size_t ldp, const double *Q, int nq, size_t ldq, double r,
                           size_t seg_len, int nseg, uint32_t *counts, const uint64_t *offs, uint64_t *fill,
                           uint64_t base, const double *pn, const double *qn, hipStream_t s, const uint32_t *qsel = nullptr,
-                          const uint32_t *nq_dev = nullptr, uint64_t capacity = ~0ull) {
+                          const uint32_t *nq_dev = nullptr, uint64_t capacity = ~0ull, double *fill_dist = nullptr) {
         return launch_exact_radius_f64(P, n, dim, ldp, Q, nq, ldq, r, seg_len, nseg, counts, offs, fill, base, pn, qn, s, qsel,
-                                       nq_dev, capacity);
+                                       nq_dev, capacity, fill_dist);
     }
 };
+
+// PN_RADIUS_SORTED: every list of the CSR (d_off [nq + 1], d_idx / d_dist on the device) that ends at or below `limit`
+// ordered by (distance, index) in place, on stream s (csr_sort.hip); scratch from the workspace
+template <typename T>
+static int csr_sort_dev(const pn_index *ix, Workspace &ws, const uint64_t *d_off, size_t nq, uint64_t *d_idx, T *d_dist,
+                        uint64_t limit, hipStream_t s) {
+    if (nq == 0 || limit < 2) return PN_OK;
+    const size_t ent = csr_sort_scratch_entries(nq, ix->n, (size_t)limit);
+    CsrSortScratch w;
+    PNCHK(ws.w_cs_nch.ensure(nq * sizeof(uint32_t)));
+    w.nch = (uint32_t *)ws.w_cs_nch.p;
+    if (ent) {  // some list may be long: chunk offsets and the ping-pong copy
+        PNCHK(ws.w_cs_off.ensure((nq + 1) * sizeof(uint64_t)));
+        PNCHK(ws.w_cs_scan.ensure((nq / 4096 + 2) * sizeof(uint64_t)));
+        PNCHK(ws.w_cs_idx.ensure(ent * sizeof(uint64_t)));
+        PNCHK(ws.w_cs_dist.ensure(ent * sizeof(T)));
+        w.chunk_off = (uint64_t *)ws.w_cs_off.p;
+        w.scan = (uint64_t *)ws.w_cs_scan.p;
+        w.idx = (uint64_t *)ws.w_cs_idx.p;
+        w.dist = ws.w_cs_dist.p;
+    }
+    if constexpr (sizeof(T) == 4)
+        HIPCHK(launch_csr_sort_f32(d_off, (int)nq, d_idx, d_dist, limit, ix->n, w, ix->n_cu, s));
+    else
+        HIPCHK(launch_csr_sort_f64(d_off, (int)nq, d_idx, d_dist, limit, ix->n, w, ix->n_cu, s));
+    return PN_OK;
+}
+// the host entry point's answer (host arrays) sorted on the device: up, csr_sort_dev, down (through the workspace's
+// staging buffers)
+template <typename T>
+static int csr_sort_host(const pn_index *ix, Workspace &ws, const uint64_t *offsets, size_t nq, uint64_t *idx, T *dist,
+                         hipStream_t s) {
+    const uint64_t total = offsets[nq];
+    if (total < 2) return PN_OK;
+    PNCHK(ws.w_cs_hoff.ensure((nq + 1) * sizeof(uint64_t)));
+    PNCHK(ws.w_hidx.ensure(total * sizeof(uint64_t)));
+    PNCHK(ws.w_hdist.ensure(total * sizeof(T)));
+    uint64_t *d_off = (uint64_t *)ws.w_cs_hoff.p, *d_idx = (uint64_t *)ws.w_hidx.p;
+    T *d_dist = (T *)ws.w_hdist.p;
+    HIPCHK(hipMemcpyAsync(d_off, offsets, (nq + 1) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_idx, idx, total * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_dist, dist, total * sizeof(T), hipMemcpyHostToDevice, s));
+    PNCHK(csr_sort_dev<T>(ix, ws, d_off, nq, d_idx, d_dist, total, s));
+    HIPCHK(hipMemcpyAsync(idx, d_idx, total * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(dist, d_dist, total * sizeof(T), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return PN_OK;
+}
 
 // query_radius through the MFMA filter (f32, D <= 128, finite positive r).  *done = false means the
 // caller must run the exact two-pass engine instead (a survivor list overflowed, or a query norm is not
 // finite): correctness never depends on this path being taken.
 // exact radius queries: count pass -> host exclusive scan -> fill pass (exact scan kernel); offs gets nq + 1
-// entries, *out a malloc'ed array of offs[nq] global row numbers, ascending per query
+// entries, *out a malloc'ed array of offs[nq] global row numbers, ascending per query; dout (nullable): *dout a malloc'ed
+// array of their distances
 template <typename T>
 static int radius_exact(const pn_index *ix, Workspace &ws, const T *Qp, size_t nq, size_t nq_pad, size_t dim_eff, T radius,
-                        std::vector<uint64_t> &offs, uint64_t **out, hipStream_t s, const T *qnorm = nullptr) {
+                        std::vector<uint64_t> &offs, uint64_t **out, hipStream_t s, const T *qnorm = nullptr,
+                        T **dout = nullptr) {
     *out = nullptr;
+    if (dout) *dout = nullptr;
     uint32_t *d_counts = nullptr;
     uint64_t *d_offs = nullptr, *d_fill = nullptr;
+    T *d_fill_d = nullptr;
     std::vector<uint32_t> h_counts;
     std::vector<uint64_t> h_offs;
     int rc = PN_OK;
@@ -2596,30 +2662,42 @@ static int radius_exact(const pn_index *ix, Workspace &ws, const T *Qp, size_t n
         uint64_t *h_out = (uint64_t *)malloc((run ? run : 1) * sizeof(uint64_t));
         if (!h_out) { rc = fail(PN_ERR_NOMEM, "malloc(%llu results) failed", (unsigned long long)run); break; }
         *out = h_out;
+        if (dout) {
+            *dout = (T *)malloc((run ? run : 1) * sizeof(T));
+            if (!*dout) { rc = fail(PN_ERR_NOMEM, "malloc(%llu distances) failed", (unsigned long long)run); break; }
+        }
         if (run == 0) break;
-        if (hipMalloc((void **)&d_fill, run * 8) != hipSuccess) { rc = fail(PN_ERR_NOMEM, "hipMalloc radius output failed"); break; }
+        if (hipMalloc((void **)&d_fill, run * 8) != hipSuccess ||
+            (dout && hipMalloc((void **)&d_fill_d, run * sizeof(T)) != hipSuccess)) {
+            rc = fail(PN_ERR_NOMEM, "hipMalloc radius output failed");
+            break;
+        }
         if (hipMemcpyAsync(d_offs, h_offs.data(), cells * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
             RadOps<T>::run((const T *)ix->d_pts, ix->n, (int)dim_eff, ix->ld, Qp, (int)nq, ix->ld, radius, pl.seg_len,
                            pl.nseg, d_counts, d_offs, d_fill, ix->index_base, qnorm ? (const T *)ix->d_cnorm : nullptr, qnorm,
-                           s) != hipSuccess ||
+                           s, nullptr, nullptr, ~0ull, d_fill_d) != hipSuccess ||
             hipMemcpyAsync(h_out, d_fill, run * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            (dout && hipMemcpyAsync(*dout, d_fill_d, run * sizeof(T), hipMemcpyDeviceToHost, s) != hipSuccess) ||
             hipStreamSynchronize(s) != hipSuccess) {
             rc = fail(PN_ERR_DEVICE, "radius fill pass failed: %s", hipGetErrorString(hipGetLastError()));
             break;
         }
     } while (0);
     if (rc != PN_OK && *out) { free(*out); *out = nullptr; }
+    if (rc != PN_OK && dout && *dout) { free(*dout); *dout = nullptr; }
     if (d_counts) (void)hipFree(d_counts);
     if (d_offs) (void)hipFree(d_offs);
     if (d_fill) (void)hipFree(d_fill);
+    if (d_fill_d) (void)hipFree(d_fill_d);
     return rc;
 }
 
-// common tail of the filtered radius paths: kept rows per query (w_keys, ascending) -> CSR on the host
+// common tail of the filtered radius paths: kept rows per query (w_keys, ascending) -> CSR on the host; dist_out
+// (nullable): their distances too (w_rkd's second half, left by the check kernel)
 template <typename T>
 static int radius_finish(const pn_index *ix, Workspace &ws, const T *Qp, size_t nq, size_t kept_stride, uint32_t *d_misc,
                          const uint32_t *d_over, T radius, uint64_t *offsets, uint64_t **idx_out, bool *done,
-                         hipStream_t s, bool cosine = false) {
+                         hipStream_t s, bool cosine = false, T **dist_out = nullptr) {
     uint32_t h_misc[2] = {0, 0};
     std::vector<uint32_t> h_n(nq);
     HIPCHK(hipMemcpyAsync(h_misc, d_misc, sizeof h_misc, hipMemcpyDeviceToHost, s));
@@ -2648,22 +2726,36 @@ static int radius_finish(const pn_index *ix, Workspace &ws, const T *Qp, size_t 
     h_off[nq] = run;
     uint64_t *h_out = (uint64_t *)malloc((run ? run : 1) * sizeof(uint64_t));
     if (!h_out) return fail(PN_ERR_NOMEM, "malloc(%llu results) failed", (unsigned long long)run);
+    T *h_dout = nullptr;
+    if (dist_out) {
+        h_dout = (T *)malloc((run ? run : 1) * sizeof(T));
+        if (!h_dout) {
+            free(h_out);
+            return fail(PN_ERR_NOMEM, "malloc(%llu distances) failed", (unsigned long long)run);
+        }
+    }
     if (run) {
         uint64_t *d_off = nullptr, *d_out = nullptr;
+        T *d_dout = nullptr;
         int rc = PN_OK;
-        if (hipMalloc((void **)&d_off, (nq + 1) * 8) != hipSuccess || hipMalloc((void **)&d_out, run * 8) != hipSuccess)
+        if (hipMalloc((void **)&d_off, (nq + 1) * 8) != hipSuccess || hipMalloc((void **)&d_out, run * 8) != hipSuccess ||
+            (dist_out && hipMalloc((void **)&d_dout, run * sizeof(T)) != hipSuccess))
             rc = fail(PN_ERR_NOMEM, "hipMalloc radius output failed");
+        const T *kd = dist_out ? (const T *)ws.w_rkd.p + nq * kept_stride : nullptr;  // (rank-ordered half)
         if (rc == PN_OK &&
             (hipMemcpyAsync(d_off, h_off.data(), (nq + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
              launch_radius_gather((const uint32_t *)ws.w_keys.p, (const uint32_t *)ws.w_flags.p, d_off, (int)nq,
-                                  kept_stride, ix->index_base, d_out, s) != hipSuccess ||
+                                  kept_stride, ix->index_base, d_out, s, kd, d_dout, (int)sizeof(T)) != hipSuccess ||
              hipMemcpyAsync(h_out, d_out, run * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+             (dist_out && hipMemcpyAsync(h_dout, d_dout, run * sizeof(T), hipMemcpyDeviceToHost, s) != hipSuccess) ||
              hipStreamSynchronize(s) != hipSuccess))
             rc = fail(PN_ERR_DEVICE, "radius gather failed: %s", hipGetErrorString(hipGetLastError()));
         if (d_off) (void)hipFree(d_off);
         if (d_out) (void)hipFree(d_out);
+        if (d_dout) (void)hipFree(d_dout);
         if (rc != PN_OK) {
             free(h_out);
+            free(h_dout);
             return rc;
         }
     }
@@ -2675,6 +2767,7 @@ static int radius_finish(const pn_index *ix, Workspace &ws, const T *Qp, size_t 
         const size_t nf = sel.size(), nf_pad = round_up(nf, (size_t)kTileQ);  // whole query tiles of the exact engine
         std::vector<uint64_t> offs_x;
         uint64_t *out_x = nullptr;
+        T *dout_x = nullptr;
         int rc = PN_OK;
         sel.push_back((uint32_t)nf);  // the gather kernel reads its row count from the device: kept behind the list
         if (ws.w_gsel.ensure((nf + 1) * sizeof(uint32_t)) != PN_OK || ws.w_gq.ensure(nf_pad * ix->ld * sizeof(T)) != PN_OK ||
@@ -2692,17 +2785,24 @@ static int radius_finish(const pn_index *ix, Workspace &ws, const T *Qp, size_t 
             gqnorm = (const T *)ws.w_gqn.p;
         }
         if (rc == PN_OK)
-            rc = radius_exact<T>(ix, ws, (const T *)ws.w_gq.p, nf, nf_pad, ix->dim, radius, offs_x, &out_x, s, gqnorm);
+            rc = radius_exact<T>(ix, ws, (const T *)ws.w_gq.p, nf, nf_pad, ix->dim, radius, offs_x, &out_x, s, gqnorm,
+                                 dist_out ? &dout_x : nullptr);
         if (rc != PN_OK) {
             free(h_out);
+            free(h_dout);
             return rc;
         }
-        // splice: overflowed queries take the exact lists, the others keep the filter's
+        // splice: overflowed queries take the exact lists, the others keep the filter's (distances alongside)
         const uint64_t total = run + offs_x[nf];
         uint64_t *h_all = (uint64_t *)malloc((total ? total : 1) * sizeof(uint64_t));
-        if (!h_all) {
+        T *d_all = dist_out ? (T *)malloc((total ? total : 1) * sizeof(T)) : nullptr;
+        if (!h_all || (dist_out && !d_all)) {
+            free(h_all);
+            free(d_all);
             free(h_out);
+            free(h_dout);
             free(out_x);
+            free(dout_x);
             return fail(PN_ERR_NOMEM, "malloc(%llu results) failed", (unsigned long long)total);
         }
         uint64_t w = 0;
@@ -2712,18 +2812,23 @@ static int radius_finish(const pn_index *ix, Workspace &ws, const T *Qp, size_t 
             if (j < nf && sel[j] == a) {
                 const uint64_t c = offs_x[j + 1] - offs_x[j];
                 memcpy(h_all + w, out_x + offs_x[j], c * sizeof(uint64_t));
+                if (d_all) memcpy(d_all + w, dout_x + offs_x[j], c * sizeof(T));
                 w += c;
                 ++j;
             } else {
                 const uint64_t c = h_off[a + 1] - h_off[a];
                 memcpy(h_all + w, h_out + h_off[a], c * sizeof(uint64_t));
+                if (d_all) memcpy(d_all + w, h_dout + h_off[a], c * sizeof(T));
                 w += c;
             }
         }
         offsets[nq] = w;
         free(h_out);
+        free(h_dout);
         free(out_x);
+        free(dout_x);
         *idx_out = h_all;
+        if (dist_out) *dist_out = d_all;
         {
             std::lock_guard<std::mutex> lk(ix->sh.mu);
             ix->sh.stats.fallback_queries += nf;
@@ -2733,6 +2838,7 @@ static int radius_finish(const pn_index *ix, Workspace &ws, const T *Qp, size_t 
     }
     memcpy(offsets, h_off.data(), (nq + 1) * sizeof(uint64_t));
     *idx_out = h_out;
+    if (dist_out) *dist_out = h_dout;
     *done = true;
     return PN_OK;
 }
@@ -2745,7 +2851,8 @@ static int radius_finish(const pn_index *ix, Workspace &ws, const T *Qp, size_t 
 // queries the filter cannot serve, d_misc[0] / [1] = how many of either.  *enq = false: the radius cannot be served.)
 template <typename T>
 static int radius_bf16_enqueue(const pn_index *ix, Workspace &ws, int level, const T *Qp, size_t nq, size_t nq_pad, T radius,
-                               size_t *kept_stride_out, bool *enq, hipStream_t s, const T *qnorm = nullptr) {
+                               size_t *kept_stride_out, bool *enq, hipStream_t s, const T *qnorm = nullptr,
+                               bool want_dist = false) {
     *enq = false;
     const bool cosine = ix->metric == 1;  // (round 4: the filter over the normalised rows, Cosine::distance check)
     if (cosine && (!qnorm || !ix->d_cnorm || !(radius < (T)1))) return PN_OK;  // (r >= 1: half the sphere -- exact scan)
@@ -2791,6 +2898,7 @@ static int radius_bf16_enqueue(const pn_index *ix, Workspace &ws, int level, con
     PNCHK(ws.w_keys.ensure(nq * kept_stride * sizeof(uint32_t)));    // kept rows per query
     PNCHK(ws.w_flags.ensure(nq_pad * sizeof(uint32_t)));             // kept counts
     PNCHK(ws.w_sel.ensure(nq_pad * sizeof(uint32_t)));            // per-query overflow flags
+    if (want_dist) PNCHK(ws.w_rkd.ensure(2 * nq * kept_stride * sizeof(T)));  // kept rows' distances: by slot, by rank
     uint32_t *d_misc = (uint32_t *)ws.w_misc.p;  // [0] overflow count, [1] queries the filter cannot serve
     HIPCHK(hipMemsetAsync(ws.w_misc.p, 0, 64, s));
     HIPCHK(hipMemsetAsync(ws.w_cnt.p, 0, cells * sizeof(uint32_t), s));
@@ -2829,23 +2937,23 @@ static int radius_bf16_enqueue(const pn_index *ix, Workspace &ws, int level, con
                                   (const T *)ix->d_pts, ix->ld, Qp, (int)nq, (int)ix->dim, radius,
                                   (uint32_t *)ws.w_keys.p, (uint32_t *)ws.w_flags.p, d_misc, 2,
                                   (uint32_t *)ws.w_sel.p, s, cosine ? (const T *)ix->d_cnorm : nullptr,
-                                  cosine ? qnorm : nullptr));
+                                  cosine ? qnorm : nullptr, want_dist ? (T *)ws.w_rkd.p : nullptr));
     *kept_stride_out = kept_stride;
     *enq = true;
     return PN_OK;
 }
 template <typename T>
 static int radius_bf16(const pn_index *ix, Workspace &ws, int level, const T *Qp, size_t nq, size_t nq_pad, T radius, uint64_t *offsets,
-                       uint64_t **idx_out, bool *done, hipStream_t s, const T *qnorm = nullptr) {
+                       uint64_t **idx_out, bool *done, hipStream_t s, const T *qnorm = nullptr, T **dist_out = nullptr) {
     *done = false;
     size_t kept_stride = 0;
     bool enq = false;
-    PNCHK(radius_bf16_enqueue<T>(ix, ws, level, Qp, nq, nq_pad, radius, &kept_stride, &enq, s, qnorm));
+    PNCHK(radius_bf16_enqueue<T>(ix, ws, level, Qp, nq, nq_pad, radius, &kept_stride, &enq, s, qnorm, dist_out != nullptr));
     if (!enq) return PN_OK;
     const bool prof = ix->profile != 0;
     uint32_t *d_misc = (uint32_t *)ws.w_misc.p;
     const int rc = radius_finish<T>(ix, ws, Qp, nq, kept_stride, d_misc, (const uint32_t *)ws.w_sel.p, radius, offsets,
-                                    idx_out, done, s, ix->metric == 1);
+                                    idx_out, done, s, ix->metric == 1, dist_out);
     if (prof && rc == PN_OK) {  // (radius_finish has waited for the stream)
         float ms = 0.0f;
         if (hipEventElapsedTime(&ms, ws.ev_r[0], ws.ev_r[1]) == hipSuccess) {
@@ -2858,7 +2966,7 @@ static int radius_bf16(const pn_index *ix, Workspace &ws, int level, const T *Qp
 }
 
 static int radius_mfma(const pn_index *ix, Workspace &ws, const float *Qp, size_t nq, size_t nq_pad, float radius, uint64_t *offsets,
-                       uint64_t **idx_out, bool *done, hipStream_t s) {
+                       uint64_t **idx_out, bool *done, hipStream_t s, float **dist_out = nullptr) {
     *done = false;
     const uint32_t cap = 32;
     const size_t q_tiles = nq_pad / 128, r_tiles = (ix->n + 63) / 64;
@@ -2884,6 +2992,7 @@ static int radius_mfma(const pn_index *ix, Workspace &ws, const float *Qp, size_
     PNCHK(ws.w_idx.ensure(cells * cap * sizeof(uint32_t)));
     PNCHK(ws.w_keys.ensure(nq * kept_stride * sizeof(uint32_t)));  // kept rows per query
     PNCHK(ws.w_flags.ensure(nq_pad * sizeof(uint32_t)));           // kept counts
+    if (dist_out) PNCHK(ws.w_rkd.ensure(2 * nq * kept_stride * sizeof(float)));
     uint32_t *d_misc = (uint32_t *)ws.w_misc.p;  // [0] overflow count, [1] non-finite query norms
     HIPCHK(hipMemsetAsync(ws.w_misc.p, 0, 64, s));
     HIPCHK(hipMemsetAsync(ws.w_cnt.p, 0, cells * sizeof(uint32_t), s));
@@ -2893,17 +3002,27 @@ static int radius_mfma(const pn_index *ix, Workspace &ws, const float *Qp, size_
                                   nq_pad, tau_excl, cap, (uint32_t *)ws.w_cnt.p, (uint32_t *)ws.w_idx.p, (int)n_wg, s));
     HIPCHK(launch_radius_check_f32((const uint32_t *)ws.w_cnt.p, (const uint32_t *)ws.w_idx.p, nq_pad, nseg, cap,
                                    (const float *)ix->d_pts, ix->ld, Qp, (int)nq, (int)ix->dim, radius,
-                                   (uint32_t *)ws.w_keys.p, (uint32_t *)ws.w_flags.p, d_misc, 1, nullptr, s));
-    return radius_finish<float>(ix, ws, Qp, nq, kept_stride, d_misc, nullptr, radius, offsets, idx_out, done, s);
+                                   (uint32_t *)ws.w_keys.p, (uint32_t *)ws.w_flags.p, d_misc, 1, nullptr, s,
+                                   dist_out ? (float *)ws.w_rkd.p : nullptr));
+    return radius_finish<float>(ix, ws, Qp, nq, kept_stride, d_misc, nullptr, radius, offsets, idx_out, done, s, false,
+                                dist_out);
 }
 
 template <typename T>
+static int radius_host_tiers(const pn_index *ix, Workspace &ws, hipStream_t s, int level, const T *q, size_t nq, size_t q_cols,
+                             ptrdiff_t q_stride, size_t dim_eff, T radius, uint64_t *offsets, uint64_t **idx_out,
+                             T **dist_out);
+// dist_out (nullable: pn_query_radius_with_distance_*): *dist_out gets the distances next to the rows; flags:
+// PN_RADIUS_SORTED orders each list by (distance, index) (csr_sort.hip) -- only with dist_out
+template <typename T>
 static int radius_host_impl(const pn_index *ix, const T *q, size_t nq, size_t q_cols, ptrdiff_t q_stride, T radius,
-                            uint64_t *offsets, uint64_t **idx_out) {
+                            uint64_t *offsets, uint64_t **idx_out, T **dist_out = nullptr, unsigned flags = 0) {
     if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
     if (ix->elem_bytes != (int)sizeof(T)) return fail(PN_ERR_INVALID, "index element type mismatch");
     if (!offsets || !idx_out) return fail(PN_ERR_INVALID, "output pointer is NULL");
+    if (flags & ~(unsigned)PN_RADIUS_SORTED) return fail(PN_ERR_INVALID, "unknown radius flags 0x%x", flags);
     *idx_out = nullptr;
+    if (dist_out) *dist_out = nullptr;
     offsets[0] = 0;
     if (nq == 0) return PN_OK;
     if (!q && q_cols) return fail(PN_ERR_INVALID, "queries is NULL");
@@ -2921,8 +3040,28 @@ static int radius_host_impl(const pn_index *ix, const T *q, size_t nq, size_t q_
         level = ix->sh.bf16_level;
     }
     const size_t dim_eff = q_cols < ix->dim ? q_cols : ix->dim;
-    if (q_stride >= 0 && tiny_eligible<T>(ix, nq, dim_eff))
-        return tiny_radius<T>(ix, ws, s, q, nq, q_cols, q_stride, radius, offsets, idx_out);
+    int rc = PN_OK;
+    if (q_stride >= 0 && tiny_eligible<T>(ix, nq, dim_eff)) {
+        rc = tiny_radius<T>(ix, ws, s, q, nq, q_cols, q_stride, radius, offsets, idx_out, dist_out);
+    } else {
+        rc = radius_host_tiers<T>(ix, ws, s, level, q, nq, q_cols, q_stride, dim_eff, radius, offsets, idx_out, dist_out);
+    }
+    if (rc == PN_OK && (flags & PN_RADIUS_SORTED)) rc = csr_sort_host<T>(ix, ws, offsets, nq, *idx_out, *dist_out, s);
+    if (rc != PN_OK) {
+        free(*idx_out);
+        *idx_out = nullptr;
+        if (dist_out) {
+            free(*dist_out);
+            *dist_out = nullptr;
+        }
+    }
+    return rc;
+}
+// the batched tiers of the host entry point (everything but the one-launch path of small calls)
+template <typename T>
+static int radius_host_tiers(const pn_index *ix, Workspace &ws, hipStream_t s, int level, const T *q, size_t nq, size_t q_cols,
+                             ptrdiff_t q_stride, size_t dim_eff, T radius, uint64_t *offsets, uint64_t **idx_out,
+                             T **dist_out) {
     const size_t nq_pad = round_up(nq, (size_t)256);
     int rc = upload_rows_to<T>(q, nq, q_cols, q_stride, ws.w_hq, s);
     do {
@@ -2951,25 +3090,26 @@ static int radius_host_impl(const pn_index *ix, const T *q, size_t nq, size_t q_
         if ((ix->metric == 0 || q_cols == ix->dim) && ix->bf16_ok && dim_eff == ix->dim && finite_pos && level < 2 &&
             (ix->engine == PN_ENGINE_BF16 || (ix->engine == PN_ENGINE_AUTO && ix->n >= 4096 && ix->dim >= 8))) {
             bool done = false;  // (f32 and f64 indexes)
-            rc = radius_bf16<T>(ix, ws, level, (const T *)Qp, nq, nq_pad, radius, offsets, idx_out, &done, s, qnorm);
+            rc = radius_bf16<T>(ix, ws, level, (const T *)Qp, nq, nq_pad, radius, offsets, idx_out, &done, s, qnorm,
+                                dist_out);
             if (rc != PN_OK || done) break;
         }
         if constexpr (sizeof(T) == 4) {
             if (ix->mfma_ok && ix->ld <= 128 && dim_eff == ix->dim && ix->engine != PN_ENGINE_EXACT && finite_pos &&
                 (ix->engine == PN_ENGINE_MFMA || (ix->n >= 4096 && ix->dim >= 8))) {
                 bool done = false;
-                rc = radius_mfma(ix, ws, (const float *)Qp, nq, nq_pad, (float)radius, offsets, idx_out, &done, s);
+                rc = radius_mfma(ix, ws, (const float *)Qp, nq, nq_pad, (float)radius, offsets, idx_out, &done, s,
+                                 (float **)dist_out);
                 if (rc != PN_OK || done) break;
                 std::lock_guard<std::mutex> lk(ix->sh.mu);
                 ix->sh.stats.fallback_queries += nq;  // survivor list overflow / non-finite query: exact engine
             }
         }
         std::vector<uint64_t> offs;
-        rc = radius_exact<T>(ix, ws, Qp, nq, nq_pad, dim_eff, radius, offs, idx_out, s, qnorm);
+        rc = radius_exact<T>(ix, ws, Qp, nq, nq_pad, dim_eff, radius, offs, idx_out, s, qnorm, dist_out);
         if (rc != PN_OK) break;
         memcpy(offsets, offs.data(), (nq + 1) * sizeof(uint64_t));
     } while (0);
-    if (rc != PN_OK && *idx_out) { free(*idx_out); *idx_out = nullptr; }
     return rc;
 }
 
@@ -2980,6 +3120,25 @@ extern "C" int pn_query_radius_f32(const pn_index *ix, const float *q, size_t nq
 extern "C" int pn_query_radius_f64(const pn_index *ix, const double *q, size_t nq, size_t q_cols, ptrdiff_t q_stride,
                                    double radius, uint64_t *offsets, uint64_t **idx_out) {
     return radius_host_impl<double>(ix, q, nq, q_cols, q_stride, radius, offsets, idx_out);
+}
+template <typename T>
+static int radius_wd_host(const pn_index *ix, const T *q, size_t nq, size_t q_cols, ptrdiff_t q_stride, T radius,
+                          unsigned flags, uint64_t *offsets, uint64_t **idx_out, T **dist_out) {
+    // (argument checks first: they fail before any device is touched)
+    if (!offsets || !idx_out || !dist_out) return fail(PN_ERR_INVALID, "output pointer is NULL");
+    if (flags & ~(unsigned)PN_RADIUS_SORTED) return fail(PN_ERR_INVALID, "unknown radius flags 0x%x", flags);
+    *dist_out = nullptr;
+    return radius_host_impl<T>(ix, q, nq, q_cols, q_stride, radius, offsets, idx_out, dist_out, flags);
+}
+extern "C" int pn_query_radius_with_distance_f32(const pn_index *ix, const float *q, size_t nq, size_t q_cols,
+                                                 ptrdiff_t q_stride, float radius, unsigned flags, uint64_t *offsets,
+                                                 uint64_t **idx_out, float **dist_out) {
+    return radius_wd_host<float>(ix, q, nq, q_cols, q_stride, radius, flags, offsets, idx_out, dist_out);
+}
+extern "C" int pn_query_radius_with_distance_f64(const pn_index *ix, const double *q, size_t nq, size_t q_cols,
+                                                 ptrdiff_t q_stride, double radius, unsigned flags, uint64_t *offsets,
+                                                 uint64_t **idx_out, double **dist_out) {
+    return radius_wd_host<double>(ix, q, nq, q_cols, q_stride, radius, flags, offsets, idx_out, dist_out);
 }
 // ---------------------------------------------------------------------------
 // pn_query_radius_device_{f32,f64} (round 4; VERDICT r3 missing 2): BallTree::query_radius (src/ball_tree.rs:137-142,
@@ -2994,12 +3153,19 @@ extern "C" int pn_query_radius_f64(const pn_index *ix, const double *q, size_t n
 //   Cosine indexes with a bf16 tier, queries as long as the rows, r < 1: the same over the normalised rows, the survivors
 //   checked with Cosine::distance.  Every other case (small corpora, no tier): the exact two-pass scan for all queries.
 // ---------------------------------------------------------------------------
+// with_dist (pn_query_radius_with_distance_device_*): d_dist gets each written row's distance at the row's position;
+// PN_RADIUS_SORTED orders every list that ends at or below `capacity` by (distance, index) -- the list that straddles
+// the capacity is left in ascending index order, as far as it is written
 template <typename T>
 static int radius_device_impl(const pn_index *ix, const T *d_q, size_t nq, size_t q_cols, size_t q_stride, T radius,
-                              uint64_t *d_offsets, uint64_t *d_idx, size_t capacity, uint64_t *d_total, hipStream_t s) {
+                              uint64_t *d_offsets, uint64_t *d_idx, size_t capacity, uint64_t *d_total, hipStream_t s,
+                              bool with_dist = false, T *d_dist = nullptr, unsigned flags = 0) {
     if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
     if (ix->elem_bytes != (int)sizeof(T)) return fail(PN_ERR_INVALID, "index element type mismatch");
     if (!d_offsets || (!d_idx && capacity)) return fail(PN_ERR_INVALID, "output buffer is NULL");
+    if (with_dist && !d_dist && capacity) return fail(PN_ERR_INVALID, "distance buffer is NULL");
+    if (flags & ~(unsigned)PN_RADIUS_SORTED) return fail(PN_ERR_INVALID, "unknown radius flags 0x%x", flags);
+    if (!capacity) d_dist = nullptr;  // (a pure count)
     if (!d_q && q_cols && nq) return fail(PN_ERR_INVALID, "queries is NULL");
     if (nq > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many queries in one call");
     DeviceGuard g(ix->device);
@@ -3038,7 +3204,8 @@ static int radius_device_impl(const pn_index *ix, const T *d_q, size_t nq, size_
     const bool finite_pos = radius > (T)0 && radius < (T)INFINITY;
     if ((ix->metric == 0 || q_cols == ix->dim) && ix->bf16_ok && dim_eff == ix->dim && finite_pos && level < 2 &&
         (ix->engine == PN_ENGINE_BF16 || (ix->engine == PN_ENGINE_AUTO && ix->n >= 4096 && ix->dim >= 8)))
-        PNCHK(radius_bf16_enqueue<T>(ix, ws, level, (const T *)Qp, nq, nq_pad, radius, &kept_stride, &filtered, s, qnorm));
+        PNCHK(radius_bf16_enqueue<T>(ix, ws, level, (const T *)Qp, nq, nq_pad, radius, &kept_stride, &filtered, s, qnorm,
+                                     d_dist != nullptr));
     PNCHK(ws.w_misc.ensure(64));
     uint32_t *d_misc = (uint32_t *)ws.w_misc.p;  // [4]: the number of listed queries
     const uint32_t *d_sel = nullptr, *d_pos = nullptr, *d_nsel = nullptr, *d_nkept = nullptr;
@@ -3072,10 +3239,14 @@ static int radius_device_impl(const pn_index *ix, const T *d_q, size_t nq, size_
     if (capacity) {
         HIPCHK(RadOps<T>::run((const T *)ix->d_pts, ix->n, (int)dim_eff, ix->ld, Qp, (int)nq, ix->ld, radius, pl.seg_len,
                               pl.nseg, (uint32_t *)ws.w_rcx.p, (const uint64_t *)ws.w_rox.p, d_idx, ix->index_base, pn, qnorm,
-                              s, d_sel, d_nsel, (uint64_t)capacity));
+                              s, d_sel, d_nsel, (uint64_t)capacity, d_dist));
         if (filtered)
             HIPCHK(launch_radius_gather_cap((const uint32_t *)ws.w_keys.p, d_nkept, d_offsets, (int)nq, kept_stride,
-                                            ix->index_base, d_idx, (uint64_t)capacity, s));
+                                            ix->index_base, d_idx, (uint64_t)capacity, s,
+                                            d_dist ? (const T *)ws.w_rkd.p + nq * kept_stride : nullptr, d_dist,
+                                            (int)sizeof(T)));
+        if (d_dist && (flags & PN_RADIUS_SORTED))
+            PNCHK(csr_sort_dev<T>(ix, ws, d_offsets, nq, d_idx, d_dist, (uint64_t)capacity, s));
     }
     return PN_OK;
 }
@@ -3090,6 +3261,29 @@ extern "C" int pn_query_radius_device_f64(const pn_index *ix, const double *d_q,
                                           uint64_t *d_total, void *stream) {
     return radius_device_impl<double>(ix, d_q, nq, q_cols, q_stride, radius, d_offsets, d_idx, capacity, d_total,
                                       (hipStream_t)stream);
+}
+// argument checks of the device entry points with distances, before any device is touched
+static int radius_wd_device_args(const void *d_offsets, const void *d_idx, const void *d_dist, size_t capacity,
+                                 unsigned flags) {
+    if (!d_offsets || (capacity && (!d_idx || !d_dist))) return fail(PN_ERR_INVALID, "output buffer is NULL");
+    if (flags & ~(unsigned)PN_RADIUS_SORTED) return fail(PN_ERR_INVALID, "unknown radius flags 0x%x", flags);
+    return PN_OK;
+}
+extern "C" int pn_query_radius_with_distance_device_f32(const pn_index *ix, const float *d_q, size_t nq, size_t q_cols,
+                                                        size_t q_stride, float radius, unsigned flags, uint64_t *d_offsets,
+                                                        uint64_t *d_idx, float *d_dist, size_t capacity, uint64_t *d_total,
+                                                        void *stream) {
+    PNCHK(radius_wd_device_args(d_offsets, d_idx, d_dist, capacity, flags));
+    return radius_device_impl<float>(ix, d_q, nq, q_cols, q_stride, radius, d_offsets, d_idx, capacity, d_total,
+                                     (hipStream_t)stream, true, d_dist, flags);
+}
+extern "C" int pn_query_radius_with_distance_device_f64(const pn_index *ix, const double *d_q, size_t nq, size_t q_cols,
+                                                        size_t q_stride, double radius, unsigned flags, uint64_t *d_offsets,
+                                                        uint64_t *d_idx, double *d_dist, size_t capacity, uint64_t *d_total,
+                                                        void *stream) {
+    PNCHK(radius_wd_device_args(d_offsets, d_idx, d_dist, capacity, flags));
+    return radius_device_impl<double>(ix, d_q, nq, q_cols, q_stride, radius, d_offsets, d_idx, capacity, d_total,
+                                      (hipStream_t)stream, true, d_dist, flags);
 }
 
 extern "C" void pn_free(void *p) { free(p); }

@@ -6,6 +6,7 @@
 #include <atomic>
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
 
 namespace pn {
 
@@ -86,14 +87,17 @@ hipError_t launch_exact_radius_f32(const float *P, size_t n, int dim, size_t ldp
                                    size_t ldq, float r, size_t seg_len, int nseg, uint32_t *counts,
                                    const uint64_t *offsets, uint64_t *fill, uint64_t index_base, const float *pnorm,
                                    const float *qnorm, hipStream_t s, const uint32_t *qsel = nullptr,
-                                   const uint32_t *nq_dev = nullptr, uint64_t capacity = ~0ull);
+                                   const uint32_t *nq_dev = nullptr, uint64_t capacity = ~0ull,
+                                   float *fill_dist = nullptr);
 hipError_t launch_exact_radius_f64(const double *P, size_t n, int dim, size_t ldp, const double *Q, int nq,
                                    size_t ldq, double r, size_t seg_len, int nseg, uint32_t *counts,
                                    const uint64_t *offsets, uint64_t *fill, uint64_t index_base, const double *pnorm,
                                    const double *qnorm, hipStream_t s, const uint32_t *qsel = nullptr,
-                                   const uint32_t *nq_dev = nullptr, uint64_t capacity = ~0ull);
+                                   const uint32_t *nq_dev = nullptr, uint64_t capacity = ~0ull,
+                                   double *fill_dist = nullptr);
 // qsel / nq_dev (nullable): query r of the launch is row qsel[r] of Q, only the first *nq_dev listed queries exist (grid
 // sized for nq); counts / offsets indexed by r.  capacity: fill positions at or beyond it are not written.
+// fill_dist (nullable): the fill pass also writes each listed row's distance at its position
 
 // ---- radius_device.hip: the device-side plumbing of pn_query_radius_device_* (no host round trip)
 // list the queries the exact scan must answer: need[q] = over[q] | bad[q] (either nullable); sel[0 .. *nsel) <- those q
@@ -112,9 +116,28 @@ hipError_t launch_exclusive_scan_u32(const uint32_t *in, size_t n, uint64_t *off
 hipError_t launch_rad_seg_offsets(const uint64_t *offsets, const uint32_t *sel, const uint32_t *nsel, int nq,
                                   const uint32_t *counts_x, int nseg, uint64_t *offs_x, hipStream_t s);
 // out[offsets[q] + e] <- index_base + kept[q * kept_stride + e], e < nkept[q], positions below capacity only
+// kept_dist / out_dist (nullable, elements of dist_bytes = 4 | 8): the kept rows' distances go along
 hipError_t launch_radius_gather_cap(const uint32_t *kept, const uint32_t *nkept, const uint64_t *offsets, int nq,
                                     size_t kept_stride, uint64_t index_base, uint64_t *out, uint64_t capacity,
-                                    hipStream_t s);
+                                    hipStream_t s, const void *kept_dist = nullptr, void *out_dist = nullptr,
+                                    int dist_bytes = 0);
+
+// ---- csr_sort.hip: order every list of a radius answer by (distance, index) in place (PN_RADIUS_SORTED)
+constexpr int kSortTile = 2048;  // longest list sorted by one workgroup in LDS; longer lists: chunks + merge passes
+struct CsrSortScratch {
+    uint32_t *nch = nullptr;        // [nq] chunks per long list
+    uint64_t *chunk_off = nullptr;  // [nq + 1] their exclusive scan
+    uint64_t *scan = nullptr;       // (nq / 4096 + 2) words of scan scratch
+    uint64_t *idx = nullptr;        // ping-pong copy: csr_sort_scratch_entries() entries
+    void *dist = nullptr;
+};
+// entries of the ping-pong copy a call needs (0: no list can exceed kSortTile entries); max_row bounds every list's
+// length (the corpus' rows), limit the positions sorted (lists that do not end at or below it are left unsorted)
+size_t csr_sort_scratch_entries(size_t nq, size_t max_row, size_t limit);
+hipError_t launch_csr_sort_f32(const uint64_t *offsets, int nq, uint64_t *idx, float *dist, uint64_t limit, size_t max_row,
+                               const CsrSortScratch &w, int n_cu, hipStream_t s);
+hipError_t launch_csr_sort_f64(const uint64_t *offsets, int nq, uint64_t *idx, double *dist, uint64_t limit, size_t max_row,
+                               const CsrSortScratch &w, int n_cu, hipStream_t s);
 // Cosine's norms: norms[i] = sqrt(sequential sum of x_i[k]^2, k < dim) in T
 hipError_t launch_cosine_norms_f32(const float *X, size_t n, int dim, size_t ld, float *norms, hipStream_t s);
 hipError_t launch_cosine_norms_f64(const double *X, size_t n, int dim, size_t ld, double *norms, hipStream_t s);
@@ -184,7 +207,8 @@ hipError_t launch_select_rerank_cos_f64(const CandBuf &cb, const double *P, size
 // osel (nullable): the merged result of query q goes to row osel[q] of the outputs (row stride out_stride, 0 = k_out);
 // host_count (nullable, mapped pinned memory): block 0 copies *nq_dev there (the count a LATER call looks at)
 // Small corpora, a few queries per call: the whole call in one launch (one wave per query over all rows); Q and the
-// outputs may be mapped pinned host memory.  radius_mode: out row q = {count, rows ascending ...} (out_stride >= n + 1)
+// outputs may be mapped pinned host memory.  radius_mode: out row q = {count, rows ascending ...} (out_stride >= n + 1),
+// dist_out (nullable) row q = {-, their distances ...} at the same positions
 size_t tiny_query_lds_bytes(size_t n, int dim_eff, int elem_bytes);  // must be <= 64 KiB
 hipError_t launch_tiny_query_f32(const float *P, size_t n, int dim_eff, size_t ldp, const float *Q, size_t ldq, int nq,
                                  int kout, bool radius_mode, float radius, uint64_t index_base, uint64_t *idx_out,
@@ -211,7 +235,9 @@ template <typename T>
 hipError_t launch_radius_check(const uint32_t *rcnt, const uint32_t *ridx, size_t nq_pad, int nseg, uint32_t cap,
                                const T *P, size_t ldp, const T *Q, int nq, int dim, T r, uint32_t *kept,
                                uint32_t *nkept, uint32_t *overflow, int ridx_stride, uint32_t *over_q, hipStream_t s,
-                               const T *cnorm = nullptr, const T *qnorm = nullptr);  // (both: Cosine::distance < r)
+                               const T *cnorm = nullptr, const T *qnorm = nullptr,  // (both: Cosine::distance < r)
+                               T *kept_dist = nullptr);  // (nullable: [2][nq][nseg * cap], the second half gets
+                                                         // the kept rows' distances next to `kept`)
 hipError_t launch_gather_rows_f32(const float *src, size_t ld, const uint32_t *sel, const uint32_t *nsel, uint32_t off,
                                   uint32_t max_rows, float *dst, hipStream_t s);
 hipError_t launch_scatter_results_f32(const uint64_t *idx_in, const float *dist_in, const uint32_t *sel,
@@ -252,9 +278,11 @@ hipError_t launch_mfma_radius_f32(const float *P, const float *pnorm, size_t n, 
 hipError_t launch_radius_check_f32(const uint32_t *rcnt, const uint32_t *ridx, size_t nq_pad, int nseg, uint32_t cap,
                                    const float *P, size_t ldp, const float *Q, int nq, int dim, float r,
                                    uint32_t *kept, uint32_t *nkept, uint32_t *overflow, int ridx_stride,
-                                   uint32_t *over_q /* nullable: per-query overflow flags */, hipStream_t s);
+                                   uint32_t *over_q /* nullable: per-query overflow flags */, hipStream_t s,
+                                   float *kept_dist = nullptr);
 hipError_t launch_radius_gather(const uint32_t *kept, const uint32_t *nkept, const uint64_t *offsets, int nq,
-                                size_t kept_stride, uint64_t index_base, uint64_t *out, hipStream_t s);
+                                size_t kept_stride, uint64_t index_base, uint64_t *out, hipStream_t s,
+                                const void *kept_dist = nullptr, void *out_dist = nullptr, int dist_bytes = 0);
 
 // ---- bf16_filter.hip: first-tier filter (bf16 MFMA lower bound of |q-p|^2 - |q|^2), D <= 128
 bool bf16_supported(int dim);

@@ -172,21 +172,36 @@ hipError_t launch_rad_seg_offsets(const uint64_t *offsets, const uint32_t *sel, 
     return hipGetLastError();
 }
 
+// D: the bits of a distance when the kept rows' distances go along (kd / od: pn_query_radius_with_distance_device_*)
+template <typename D>
 __global__ void radius_gather_cap_kernel(const uint32_t *__restrict__ kept, const uint32_t *__restrict__ nkept,
                                          const uint64_t *__restrict__ offsets, size_t kept_stride, uint64_t index_base,
-                                         uint64_t *__restrict__ out, uint64_t capacity) {
+                                         uint64_t *__restrict__ out, uint64_t capacity, const D *__restrict__ kd,
+                                         D *__restrict__ od) {
     const size_t q = blockIdx.x;
     const uint32_t n = nkept[q];
     const uint64_t o = offsets[q];
     for (uint32_t e = threadIdx.x; e < n; e += blockDim.x)
-        if (o + e < capacity) out[o + e] = index_base + kept[q * kept_stride + e];
+        if (o + e < capacity) {
+            out[o + e] = index_base + kept[q * kept_stride + e];
+            if constexpr (!std::is_void<D>::value) od[o + e] = kd[q * kept_stride + e];
+        }
 }
 hipError_t launch_radius_gather_cap(const uint32_t *kept, const uint32_t *nkept, const uint64_t *offsets, int nq,
                                     size_t kept_stride, uint64_t index_base, uint64_t *out, uint64_t capacity,
-                                    hipStream_t s) {
+                                    hipStream_t s, const void *kept_dist, void *out_dist, int dist_bytes) {
     if (nq == 0) return hipSuccess;
-    hipLaunchKernelGGL(radius_gather_cap_kernel, dim3((unsigned)nq), dim3(64), 0, s, kept, nkept, offsets, kept_stride,
-                       index_base, out, capacity);
+    if (!out_dist)
+        hipLaunchKernelGGL(radius_gather_cap_kernel<void>, dim3((unsigned)nq), dim3(64), 0, s, kept, nkept, offsets,
+                           kept_stride, index_base, out, capacity, (const void *)nullptr, (void *)nullptr);
+    else if (dist_bytes == 4)
+        hipLaunchKernelGGL(radius_gather_cap_kernel<uint32_t>, dim3((unsigned)nq), dim3(64), 0, s, kept, nkept, offsets,
+                           kept_stride, index_base, out, capacity, (const uint32_t *)kept_dist, (uint32_t *)out_dist);
+    else if (dist_bytes == 8)
+        hipLaunchKernelGGL(radius_gather_cap_kernel<uint64_t>, dim3((unsigned)nq), dim3(64), 0, s, kept, nkept, offsets,
+                           kept_stride, index_base, out, capacity, (const uint64_t *)kept_dist, (uint64_t *)out_dist);
+    else
+        return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -903,9 +903,17 @@ __global__ __launch_bounds__(64) void tiny_query_kernel(const T *__restrict__ P,
         for (uint32_t r0 = 0; r0 < n; r0 += 64) {
             const uint32_t r = r0 + (uint32_t)lane;
             bool in = false;
-            if (r < n) in = exact_distance_seq<T>(qs, P + (size_t)r * ldp, dim_eff) < radius;
+            T d = (T)0;
+            if (r < n) {
+                d = exact_distance_seq<T>(qs, P + (size_t)r * ldp, dim_eff);
+                in = d < radius;
+            }
             const unsigned long long m = __ballot(in);
-            if (in) out[1 + cnt + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = index_base + r;
+            const uint32_t pos = 1 + cnt + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            if (in) {
+                out[pos] = index_base + r;
+                if (dist_out) dist_out[q * out_stride + pos] = d;  // (pn_query_radius_with_distance_*)
+            }
             cnt += (uint32_t)__popcll(m);
         }
         if (lane == 0) out[0] = cnt;
@@ -992,7 +1000,10 @@ hipError_t launch_tiny_query_f64(const double *P, size_t n, int dim_eff, size_t 
 // COS (round 4: query_radius on a Cosine index behind the bf16 filter): the survivors are tested with Cosine::distance in
 // the reference's arithmetic (exact_cosine_prefetched; cnorm = the rows' norms, qnorm = the queries'; len = the padded
 // row length, zeros beyond dim add nothing)
-template <typename T, bool COS>
+// WD (kept_dist != nullptr: pn_query_radius_with_distance_*): LDS keeps the rows only, as without distances -- nseg * cap
+// entries of 4 bytes, so cap stays 256 and the workgroups per CU do not change; each passing row's distance goes to
+// global memory at the row's LDS slot (kept_dist, first half) and follows the row to its rank (second half)
+template <typename T, bool COS, bool WD = false>
 __global__ __launch_bounds__(64) void radius_check_kernel(const uint32_t *__restrict__ rcnt,
                                                           const uint32_t *__restrict__ ridx, size_t nq_pad, int nseg,
                                                           uint32_t cap, const T *__restrict__ P, size_t ldp,
@@ -1000,7 +1011,7 @@ __global__ __launch_bounds__(64) void radius_check_kernel(const uint32_t *__rest
                                                           uint32_t *__restrict__ kept, uint32_t *__restrict__ nkept,
                                                           uint32_t *__restrict__ overflow, int ridx_stride,
                                                           uint32_t *__restrict__ over_q, const T *__restrict__ cnorm,
-                                                          const T *__restrict__ qnorm) {
+                                                          const T *__restrict__ qnorm, T *__restrict__ kept_dist) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint32_t *srow = reinterpret_cast<uint32_t *>(smem);  // rows that pass the exact test
     __shared__ uint32_t n_pass;
@@ -1009,6 +1020,8 @@ __global__ __launch_bounds__(64) void radius_check_kernel(const uint32_t *__rest
     if (lane == 0) n_pass = 0;
     __syncthreads();
     const T *qrow = Q + q * ldp;
+    const size_t stride = (size_t)nseg * cap;
+    T *kd_slot = WD ? kept_dist + q * stride : nullptr, *kd = WD ? kept_dist + ((size_t)gridDim.x + q) * stride : nullptr;
     bool over = false;
     for (int s = 0; s < nseg; ++s) {
         uint32_t c = rcnt[(size_t)s * nq_pad + q];
@@ -1019,17 +1032,21 @@ __global__ __launch_bounds__(64) void radius_check_kernel(const uint32_t *__rest
             T d;
             if constexpr (COS) d = exact_cosine_prefetched<T>(qrow, P + (size_t)row * ldp, (int)ldp, qnorm[q], cnorm[row]);
             else d = exact_distance_seq<T>(qrow, P + (size_t)row * ldp, dim);
-            if (d < r) srow[atomicAdd(&n_pass, 1u)] = row;  // strict '<' (src/ball_tree.rs:277); NaN never matches
+            if (d < r) {  // strict '<' (src/ball_tree.rs:277); NaN never matches
+                const uint32_t slot = atomicAdd(&n_pass, 1u);
+                srow[slot] = row;
+                if (WD) kd_slot[slot] = d;
+            }
         }
     }
     __syncthreads();
     const uint32_t n = n_pass;
-    const size_t stride = (size_t)nseg * cap;
     for (uint32_t e = lane; e < n; e += 64) {  // ascending row order by rank counting (rows are unique)
         const uint32_t row = srow[e];
         uint32_t rk = 0;
         for (uint32_t j = 0; j < n; ++j) rk += srow[j] < row ? 1u : 0u;
         kept[q * stride + rk] = row;
+        if (WD) kd[rk] = kd_slot[e];
     }
     if (lane == 0) {
         nkept[q] = n;
@@ -1042,46 +1059,64 @@ template <typename T>
 hipError_t launch_radius_check(const uint32_t *rcnt, const uint32_t *ridx, size_t nq_pad, int nseg, uint32_t cap,
                                const T *P, size_t ldp, const T *Q, int nq, int dim, T r, uint32_t *kept,
                                uint32_t *nkept, uint32_t *overflow, int ridx_stride, uint32_t *over_q, hipStream_t s,
-                               const T *cnorm, const T *qnorm) {
-    const size_t sh = (size_t)nseg * cap * sizeof(uint32_t);
+                               const T *cnorm, const T *qnorm, T *kept_dist) {
+    const size_t sh = (size_t)nseg * cap * sizeof(uint32_t);  // (the same with distances: they stay in HBM)
     if (sh > 64 * 1024) return hipErrorInvalidValue;
-    if (cnorm || qnorm) {
-        if (!cnorm || !qnorm || ldp % 8) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((radius_check_kernel<T, true>), dim3((unsigned)nq), dim3(64), sh, s, rcnt, ridx, nq_pad, nseg, cap,
-                           P, ldp, Q, dim, r, kept, nkept, overflow, ridx_stride, over_q, cnorm, qnorm);
-        return hipGetLastError();
+    const bool cos = cnorm || qnorm;
+    if (cos && (!cnorm || !qnorm || ldp % 8)) return hipErrorInvalidValue;
+#define PN_CHECK(CC, WW)                                                                                                   \
+    hipLaunchKernelGGL((radius_check_kernel<T, CC, WW>), dim3((unsigned)nq), dim3(64), sh, s, rcnt, ridx, nq_pad, nseg, cap, \
+                       P, ldp, Q, dim, r, kept, nkept, overflow, ridx_stride, over_q, cnorm, qnorm, kept_dist)
+    if (kept_dist) {
+        if (cos) PN_CHECK(true, true); else PN_CHECK(false, true);
+    } else {
+        if (cos) PN_CHECK(true, false); else PN_CHECK(false, false);
     }
-    hipLaunchKernelGGL((radius_check_kernel<T, false>), dim3((unsigned)nq), dim3(64), sh, s, rcnt, ridx, nq_pad, nseg, cap, P,
-                       ldp, Q, dim, r, kept, nkept, overflow, ridx_stride, over_q, (const T *)nullptr, (const T *)nullptr);
+#undef PN_CHECK
     return hipGetLastError();
 }
 template hipError_t launch_radius_check<float>(const uint32_t *, const uint32_t *, size_t, int, uint32_t, const float *, size_t,
                                                const float *, int, int, float, uint32_t *, uint32_t *, uint32_t *, int,
-                                               uint32_t *, hipStream_t, const float *, const float *);
+                                               uint32_t *, hipStream_t, const float *, const float *, float *);
 template hipError_t launch_radius_check<double>(const uint32_t *, const uint32_t *, size_t, int, uint32_t, const double *,
                                                 size_t, const double *, int, int, double, uint32_t *, uint32_t *, uint32_t *,
-                                                int, uint32_t *, hipStream_t, const double *, const double *);
+                                                int, uint32_t *, hipStream_t, const double *, const double *, double *);
 hipError_t launch_radius_check_f32(const uint32_t *rcnt, const uint32_t *ridx, size_t nq_pad, int nseg, uint32_t cap,
                                    const float *P, size_t ldp, const float *Q, int nq, int dim, float r,
                                    uint32_t *kept, uint32_t *nkept, uint32_t *overflow, int ridx_stride,
-                                   uint32_t *over_q, hipStream_t s) {
+                                   uint32_t *over_q, hipStream_t s, float *kept_dist) {
     return launch_radius_check<float>(rcnt, ridx, nq_pad, nseg, cap, P, ldp, Q, nq, dim, r, kept, nkept, overflow,
-                                      ridx_stride, over_q, s, nullptr, nullptr);
+                                      ridx_stride, over_q, s, nullptr, nullptr, kept_dist);
 }
 
+// D: the bits of a distance (uint32_t / uint64_t) when the kept rows' distances go along (kd / od), void: rows only
+template <typename D>
 __global__ void radius_gather_kernel(const uint32_t *__restrict__ kept, const uint32_t *__restrict__ nkept,
                                      const uint64_t *__restrict__ offsets, size_t kept_stride, uint64_t index_base,
-                                     uint64_t *__restrict__ out) {
+                                     uint64_t *__restrict__ out, const D *__restrict__ kd, D *__restrict__ od) {
     const size_t q = blockIdx.x;
     const uint32_t n = nkept[q];
     const uint64_t o = offsets[q];
-    for (uint32_t e = threadIdx.x; e < n; e += blockDim.x) out[o + e] = index_base + kept[q * kept_stride + e];
+    for (uint32_t e = threadIdx.x; e < n; e += blockDim.x) {
+        out[o + e] = index_base + kept[q * kept_stride + e];
+        if constexpr (!std::is_void<D>::value) od[o + e] = kd[q * kept_stride + e];
+    }
 }
 hipError_t launch_radius_gather(const uint32_t *kept, const uint32_t *nkept, const uint64_t *offsets, int nq,
-                                size_t kept_stride, uint64_t index_base, uint64_t *out, hipStream_t s) {
+                                size_t kept_stride, uint64_t index_base, uint64_t *out, hipStream_t s,
+                                const void *kept_dist, void *out_dist, int dist_bytes) {
     if (nq == 0) return hipSuccess;
-    hipLaunchKernelGGL(radius_gather_kernel, dim3((unsigned)nq), dim3(64), 0, s, kept, nkept, offsets, kept_stride,
-                       index_base, out);
+    if (!out_dist)
+        hipLaunchKernelGGL(radius_gather_kernel<void>, dim3((unsigned)nq), dim3(64), 0, s, kept, nkept, offsets, kept_stride,
+                           index_base, out, (const void *)nullptr, (void *)nullptr);
+    else if (dist_bytes == 4)
+        hipLaunchKernelGGL(radius_gather_kernel<uint32_t>, dim3((unsigned)nq), dim3(64), 0, s, kept, nkept, offsets,
+                           kept_stride, index_base, out, (const uint32_t *)kept_dist, (uint32_t *)out_dist);
+    else if (dist_bytes == 8)
+        hipLaunchKernelGGL(radius_gather_kernel<uint64_t>, dim3((unsigned)nq), dim3(64), 0, s, kept, nkept, offsets,
+                           kept_stride, index_base, out, (const uint64_t *)kept_dist, (uint64_t *)out_dist);
+    else
+        return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -171,7 +171,7 @@ struct Dev {  // one GPU this process drives = one rank of the communicator
     hipStream_t comm_stream = nullptr;  // exchange + merge of a chunk while the next chunk is filtered
     hipEvent_t ev_local[2] = {nullptr, nullptr}, ev_merged[2] = {nullptr, nullptr}, ev_done = nullptr;
     std::vector<int> parts;
-    Buf q, out_idx, out_dist, lparts, pack[2], gathered[2], rad_a, rad_b;
+    Buf q, out_idx, out_dist, lparts, pack[2], gathered[2], rad_a, rad_b, rad_c;  // rad_c: radius distances
     // End of the last call that used this GPU's exchange buffers (pack / gathered / lparts) and the stream it was
     // enqueued on: the device entry point returns while its kernels run, so a later call on ANOTHER stream is ordered
     // behind this event before it touches the buffers (`mu` only serialises the enqueueing).  Same scheme as
@@ -189,7 +189,7 @@ struct Dev {  // one GPU this process drives = one rank of the communicator
     double shard_ms = 0.0, exchange_ms = 0.0;
     // (Bufs point at this Dev's retired list: adopt() after the vector of Devs has its final size)
     void adopt() {
-        Buf *bs[] = {&q, &out_idx, &out_dist, &lparts, &pack[0], &pack[1], &gathered[0], &gathered[1], &rad_a, &rad_b};
+        Buf *bs[] = {&q, &out_idx, &out_dist, &lparts, &pack[0], &pack[1], &gathered[0], &gathered[1], &rad_a, &rad_b, &rad_c};
         for (Buf *b : bs) b->retired = &retired;
     }
     void free_retired() {
@@ -260,6 +260,14 @@ template <> struct ShT<float> {
                       uint64_t **out) {
         return pn_query_radius_f32(ix, q, nq, qc, qs, r, off, out);
     }
+    static int radius_wd(const pn_index *ix, const float *q, size_t nq, size_t qc, ptrdiff_t qs, float r, unsigned fl,
+                         uint64_t *off, uint64_t **out, float **dout) {
+        return pn_query_radius_with_distance_f32(ix, q, nq, qc, qs, r, fl, off, out, dout);
+    }
+    static int radius_wd_device(const pn_index *ix, const float *q, size_t nq, size_t qc, size_t qs, float r, unsigned fl,
+                                uint64_t *off, uint64_t *idx, float *dist, size_t cap, uint64_t *tot, void *st) {
+        return pn_query_radius_with_distance_device_f32(ix, q, nq, qc, qs, r, fl, off, idx, dist, cap, tot, st);
+    }
 };
 template <> struct ShT<double> {
     static int create(const double *p, size_t n, size_t c, ptrdiff_t rs, ptrdiff_t cs, int dev, pn_index **o, int metric) {
@@ -283,6 +291,14 @@ template <> struct ShT<double> {
     static int radius(const pn_index *ix, const double *q, size_t nq, size_t qc, ptrdiff_t qs, double r, uint64_t *off,
                       uint64_t **out) {
         return pn_query_radius_f64(ix, q, nq, qc, qs, r, off, out);
+    }
+    static int radius_wd(const pn_index *ix, const double *q, size_t nq, size_t qc, ptrdiff_t qs, double r, unsigned fl,
+                         uint64_t *off, uint64_t **out, double **dout) {
+        return pn_query_radius_with_distance_f64(ix, q, nq, qc, qs, r, fl, off, out, dout);
+    }
+    static int radius_wd_device(const pn_index *ix, const double *q, size_t nq, size_t qc, size_t qs, double r, unsigned fl,
+                                uint64_t *off, uint64_t *idx, double *dist, size_t cap, uint64_t *tot, void *st) {
+        return pn_query_radius_with_distance_device_f64(ix, q, nq, qc, qs, r, fl, off, idx, dist, cap, tot, st);
     }
 };
 static int check_elem(const pn_sharded *sh, size_t bytes) {
@@ -308,7 +324,7 @@ static void destroy_dev(Dev &d) {
     if (d.comm_stream) (void)hipStreamSynchronize(d.comm_stream);
     if (d.comm && rccl().ok()) (void)rccl().CommDestroy(d.comm);
     Buf *bufs[] = {&d.q, &d.out_idx, &d.out_dist, &d.lparts, &d.pack[0], &d.pack[1], &d.gathered[0], &d.gathered[1],
-                   &d.rad_a, &d.rad_b};
+                   &d.rad_a, &d.rad_b, &d.rad_c};
     for (Buf *b : bufs) b->release();
     d.free_retired();
     for (auto &tr : d.ev_prof)
@@ -828,16 +844,82 @@ extern "C" int pn_sharded_query_f64(const pn_sharded *sh, const double *queries,
 // shard -- shards are ascending row ranges, so the concatenation is ascending.  Local shards answer through
 // pn_query_radius_f32; with one process per GPU the variable-length lists travel by two all-gathers (counts, then the
 // lists padded to the longest) and are spliced on the host.
+// dist_out (nullable: pn_sharded_query_radius_with_distance_*): the distances travel next to the rows (a third all-gather
+// of the same shape with one process per GPU); with PN_RADIUS_SORTED every part's lists come back sorted by (distance,
+// global row) and the splice is a per-query merge of the parts in that order.
+//
+// splice of W parts (part r: offsets po[r][0 .. nq], rows at pi[r], distances at pd[r] or nullptr) into one CSR
+template <typename T>
+static int radius_splice(size_t nq, const std::vector<const uint64_t *> &po, const std::vector<const uint64_t *> &pi,
+                         const std::vector<const T *> &pd, bool sorted, uint64_t *offsets, uint64_t **idx_out,
+                         T **dist_out) {
+    const size_t W = po.size();
+    uint64_t total = 0;
+    for (size_t r = 0; r < W; ++r) total += po[r][nq] - po[r][0];
+    uint64_t *res = (uint64_t *)malloc((total ? total : 1) * sizeof(uint64_t));
+    T *dres = dist_out ? (T *)malloc((total ? total : 1) * sizeof(T)) : nullptr;
+    if (!res || (dist_out && !dres)) {
+        free(res);
+        free(dres);
+        return set_error(PN_ERR_NOMEM, "malloc(%llu results) failed", (unsigned long long)total);
+    }
+    std::vector<uint64_t> cur(W), end(W);
+    uint64_t w = 0;
+    for (size_t a = 0; a < nq; ++a) {
+        offsets[a] = w;
+        if (!sorted) {  // the parts' (ascending) lists in part order
+            for (size_t r = 0; r < W; ++r) {
+                const uint64_t lo = po[r][a], c = po[r][a + 1] - lo;
+                if (c) {
+                    memcpy(res + w, pi[r] + lo, (size_t)c * sizeof(uint64_t));
+                    if (dres) memcpy(dres + w, pd[r] + lo, (size_t)c * sizeof(T));
+                }
+                w += c;
+            }
+            continue;
+        }
+        // W-way merge by (distance, global row): the lists hold no NaN, and -0 compares equal to +0 as in the k-NN order
+        for (size_t r = 0; r < W; ++r) {
+            cur[r] = po[r][a];
+            end[r] = po[r][a + 1];
+        }
+        for (;;) {
+            size_t best = W;
+            for (size_t r = 0; r < W; ++r) {
+                if (cur[r] == end[r]) continue;
+                if (best == W) {
+                    best = r;
+                    continue;
+                }
+                const T d = pd[r][cur[r]], db = pd[best][cur[best]];
+                if (d < db || (d == db && pi[r][cur[r]] < pi[best][cur[best]])) best = r;
+            }
+            if (best == W) break;
+            res[w] = pi[best][cur[best]];
+            dres[w] = pd[best][cur[best]];
+            ++cur[best];
+            ++w;
+        }
+    }
+    offsets[nq] = w;
+    *idx_out = res;
+    if (dist_out) *dist_out = dres;
+    return PN_OK;
+}
 template <typename T>
 static int sharded_query_radius(const pn_sharded *sh, const T *queries, size_t nq, size_t q_cols, ptrdiff_t q_row_stride,
-                                T radius, uint64_t *offsets, uint64_t **idx_out) {
+                                T radius, uint64_t *offsets, uint64_t **idx_out, T **dist_out = nullptr,
+                                unsigned flags = 0) {
     if (!sh) return set_error(PN_ERR_INVALID, "handle is NULL");
     SPN(check_elem(sh, sizeof(T)));
     if (!offsets || !idx_out) return set_error(PN_ERR_INVALID, "output pointer is NULL");
+    if (flags & ~(unsigned)PN_RADIUS_SORTED) return set_error(PN_ERR_INVALID, "unknown radius flags 0x%x", flags);
     *idx_out = nullptr;
+    if (dist_out) *dist_out = nullptr;
     offsets[0] = 0;
     if (nq == 0) return PN_OK;
     if (!queries && q_cols) return set_error(PN_ERR_INVALID, "queries is NULL");
+    const bool sorted = dist_out && (flags & PN_RADIUS_SORTED);
     std::lock_guard<std::mutex> lk(sh->mu);
     if (sh->rank_mode && (sh->world > 1 || sh->exchange_always)) {
         // One process per GPU (round 4): the local shard answers through the DEVICE entry point (pn_query_radius_device_*:
@@ -868,13 +950,22 @@ static int sharded_query_radius(const pn_sharded *sh, const T *queries, size_t n
         if (cap < nq * 4 + 1024) cap = nq * 4 + 1024;
         std::vector<uint64_t> all_off(W * no);
         uint64_t longest = 1;
+        // distances (rad_c): [mine cap | gathered W x dw words], dw = the words of `longest` distances
+        auto dwords = [](uint64_t c) { return (size_t)((c * sizeof(T) + 7) / 8); };
         for (int attempt = 0;; ++attempt) {
             SPN(d.rad_b.ensure((cap + W * cap) * 8));
+            if (dist_out) SPN(d.rad_c.ensure((dwords(cap) + W * dwords(cap)) * 8));
             uint64_t *d_mine = (uint64_t *)d.rad_b.p;
-            if (lix)
-                SPN(ShT<T>::radius_device(lix, (const T *)d.q.p, nq, q_cols, qc, radius, d_off, d_mine, cap, d_tot, d.stream));
-            else
+            if (lix) {
+                if (dist_out)
+                    SPN(ShT<T>::radius_wd_device(lix, (const T *)d.q.p, nq, q_cols, qc, radius, flags, d_off, d_mine,
+                                                 (T *)d.rad_c.p, cap, d_tot, d.stream));
+                else
+                    SPN(ShT<T>::radius_device(lix, (const T *)d.q.p, nq, q_cols, qc, radius, d_off, d_mine, cap, d_tot,
+                                              d.stream));
+            } else {
                 SHIP(hipMemsetAsync(d_off, 0, (no + 1) * 8, d.stream));  // a rank without rows: every list empty
+            }
             SNCCL(rccl().AllGather(d_off, d_all, no, ncclUint64, d.comm, d.stream));
             SHIP(hipMemcpyAsync(all_off.data(), d_all, W * no * 8, hipMemcpyDeviceToHost, d.stream));
             SHIP(hipStreamSynchronize(d.stream));
@@ -885,79 +976,72 @@ static int sharded_query_radius(const pn_sharded *sh, const T *queries, size_t n
             cap = (size_t)longest;      // some rank overflowed: everybody re-runs with room for the longest list
         }
         uint64_t *d_mine = (uint64_t *)d.rad_b.p, *d_lists = d_mine + cap;
+        const size_t dw = dwords(longest);
         SNCCL(rccl().AllGather(d_mine, d_lists, (size_t)longest, ncclUint64, d.comm, d.stream));
+        if (dist_out)  // (every rank takes this branch alike: the call's arguments decide it)
+            SNCCL(rccl().AllGather(d.rad_c.p, (uint64_t *)d.rad_c.p + dwords(cap), dw, ncclUint64, d.comm, d.stream));
         std::vector<uint64_t> all_ids((size_t)(W * longest));
+        std::vector<uint64_t> all_d(dist_out ? W * dw : 0);
         SHIP(hipMemcpyAsync(all_ids.data(), d_lists, (size_t)(W * longest) * 8, hipMemcpyDeviceToHost, d.stream));
+        if (dist_out)
+            SHIP(hipMemcpyAsync(all_d.data(), (uint64_t *)d.rad_c.p + dwords(cap), W * dw * 8, hipMemcpyDeviceToHost,
+                                d.stream));
         SHIP(hipStreamSynchronize(d.stream));
-        uint64_t total = 0;
-        for (size_t r = 0; r < W; ++r) total += all_off[r * no + nq];
-        uint64_t *res = (uint64_t *)malloc((total ? total : 1) * sizeof(uint64_t));
-        if (!res) return set_error(PN_ERR_NOMEM, "malloc(%llu results) failed", (unsigned long long)total);
-        uint64_t w = 0;
-        for (size_t a = 0; a < nq; ++a) {  // per query, the ranks' (ascending) lists in rank order: shards are ascending row ranges
-            offsets[a] = w;
-            for (size_t r = 0; r < W; ++r) {
-                const uint64_t lo = all_off[r * no + a], c = all_off[r * no + a + 1] - lo;
-                if (c) memcpy(res + w, all_ids.data() + r * longest + lo, (size_t)c * sizeof(uint64_t));
-                w += c;
-            }
+        std::vector<const uint64_t *> po(W), pi(W);
+        std::vector<const T *> pd(W, nullptr);
+        for (size_t r = 0; r < W; ++r) {  // the ranks in rank order: shards are ascending row ranges
+            po[r] = all_off.data() + r * no;
+            pi[r] = all_ids.data() + r * longest;
+            if (dist_out) pd[r] = (const T *)(all_d.data() + r * dw);
         }
-        offsets[nq] = w;
-        *idx_out = res;
-        return PN_OK;
+        return radius_splice<T>(nq, po, pi, pd, sorted, offsets, idx_out, dist_out);
     }
     const size_t np = sh->parts.size();
     std::vector<std::vector<uint64_t>> offs(np, std::vector<uint64_t>(nq + 1, 0));
     std::vector<uint64_t *> lists(np, nullptr);
+    std::vector<T *> dlists(np, nullptr);
     struct Free {
         std::vector<uint64_t *> &l;
+        std::vector<T *> &dl;
         ~Free() {
             for (uint64_t *p : l) pn_free(p);
+            for (T *p : dl) pn_free(p);
         }
-    } free_lists{lists};
+    } free_lists{lists, dlists};
     for (size_t i = 0; i < np; ++i)
-        if (sh->parts[i].ix)
-            SPN(ShT<T>::radius(sh->parts[i].ix, queries, nq, q_cols, q_row_stride, radius, offs[i].data(), &lists[i]));
-    // local splice: per query, local shards in order
-    std::vector<uint64_t> l_cnt(nq, 0);
-    for (size_t i = 0; i < np; ++i)
-        for (size_t a = 0; a < nq; ++a) l_cnt[a] += offs[i][a + 1] - offs[i][a];
-    uint64_t l_total = 0;
-    for (size_t a = 0; a < nq; ++a) l_total += l_cnt[a];
-    std::vector<uint64_t> l_ids((size_t)l_total);
-    {
-        uint64_t w = 0;
-        for (size_t a = 0; a < nq; ++a)
-            for (size_t i = 0; i < np; ++i) {
-                const uint64_t c = offs[i][a + 1] - offs[i][a];
-                if (c) memcpy(l_ids.data() + w, lists[i] + offs[i][a], c * sizeof(uint64_t));
-                w += c;
-            }
-    }
-    {
-        uint64_t *res = (uint64_t *)malloc((l_total ? l_total : 1) * sizeof(uint64_t));
-        if (!res) return set_error(PN_ERR_NOMEM, "malloc(%llu results) failed", (unsigned long long)l_total);
-        if (l_total) memcpy(res, l_ids.data(), (size_t)l_total * sizeof(uint64_t));
-        uint64_t run = 0;
-        for (size_t a = 0; a < nq; ++a) {
-            offsets[a] = run;
-            run += l_cnt[a];
+        if (sh->parts[i].ix) {
+            if (dist_out)
+                SPN(ShT<T>::radius_wd(sh->parts[i].ix, queries, nq, q_cols, q_row_stride, radius, flags, offs[i].data(),
+                                      &lists[i], &dlists[i]));
+            else
+                SPN(ShT<T>::radius(sh->parts[i].ix, queries, nq, q_cols, q_row_stride, radius, offs[i].data(), &lists[i]));
         }
-        offsets[nq] = run;
-        *idx_out = res;
-        return PN_OK;
+    // local splice: per query, local shards in order (merged by (distance, row) when sorted)
+    std::vector<const uint64_t *> po(np), pi(np);
+    std::vector<const T *> pd(np, nullptr);
+    for (size_t i = 0; i < np; ++i) {
+        po[i] = offs[i].data();
+        pi[i] = lists[i];
+        pd[i] = dlists[i];
     }
+    return radius_splice<T>(nq, po, pi, pd, sorted, offsets, idx_out, dist_out);
 }
+
 // query_radius with queries and CSR in HBM (pn_query_radius_device_*): a handle with ONE shard forwards to it (global row
 // numbers through the shard's index base).  Several shards would need the ragged exchange on the device as well: the
 // host entry point above serves them.
 template <typename T>
+// (with_dist: pn_sharded_query_radius_with_distance_device_*, d_dist and flags as pn_query_radius_with_distance_device_*)
 static int sharded_query_radius_device(const pn_sharded *sh, const T *d_q, size_t nq, size_t q_cols, size_t q_stride, T radius,
-                                       uint64_t *d_offsets, uint64_t *d_idx, size_t capacity, uint64_t *d_total, void *stream) {
+                                       uint64_t *d_offsets, uint64_t *d_idx, size_t capacity, uint64_t *d_total, void *stream,
+                                       bool with_dist = false, T *d_dist = nullptr, unsigned flags = 0) {
     if (!sh) return set_error(PN_ERR_INVALID, "handle is NULL");
     SPN(check_elem(sh, sizeof(T)));
     if (sh->n_shards != 1 || sh->parts.size() != 1 || !sh->parts[0].ix)
         return set_error(PN_ERR_UNSUPPORTED, "the device-resident query_radius serves handles with one shard");
+    if (with_dist)
+        return ShT<T>::radius_wd_device(sh->parts[0].ix, d_q, nq, q_cols, q_stride, radius, flags, d_offsets, d_idx, d_dist,
+                                        capacity, d_total, stream);
     return ShT<T>::radius_device(sh->parts[0].ix, d_q, nq, q_cols, q_stride, radius, d_offsets, d_idx, capacity, d_total, stream);
 }
 extern "C" int pn_sharded_query_radius_device_f32(const pn_sharded *sh, const float *d_q, size_t nq, size_t q_cols,
@@ -969,6 +1053,41 @@ extern "C" int pn_sharded_query_radius_device_f64(const pn_sharded *sh, const do
                                                   size_t q_stride, double radius, uint64_t *d_offsets, uint64_t *d_idx,
                                                   size_t capacity, uint64_t *d_total, void *stream) {
     return sharded_query_radius_device<double>(sh, d_q, nq, q_cols, q_stride, radius, d_offsets, d_idx, capacity, d_total, stream);
+}
+extern "C" int pn_sharded_query_radius_with_distance_device_f32(const pn_sharded *sh, const float *d_q, size_t nq,
+                                                                size_t q_cols, size_t q_stride, float radius,
+                                                                unsigned flags, uint64_t *d_offsets, uint64_t *d_idx,
+                                                                float *d_dist, size_t capacity, uint64_t *d_total,
+                                                                void *stream) {
+    return sharded_query_radius_device<float>(sh, d_q, nq, q_cols, q_stride, radius, d_offsets, d_idx, capacity, d_total,
+                                              stream, true, d_dist, flags);
+}
+extern "C" int pn_sharded_query_radius_with_distance_device_f64(const pn_sharded *sh, const double *d_q, size_t nq,
+                                                                size_t q_cols, size_t q_stride, double radius,
+                                                                unsigned flags, uint64_t *d_offsets, uint64_t *d_idx,
+                                                                double *d_dist, size_t capacity, uint64_t *d_total,
+                                                                void *stream) {
+    return sharded_query_radius_device<double>(sh, d_q, nq, q_cols, q_stride, radius, d_offsets, d_idx, capacity, d_total,
+                                               stream, true, d_dist, flags);
+}
+template <typename T>
+static int sharded_query_radius_wd(const pn_sharded *sh, const T *queries, size_t nq, size_t q_cols, ptrdiff_t q_row_stride,
+                                   T radius, unsigned flags, uint64_t *offsets, uint64_t **idx_out, T **dist_out) {
+    if (!dist_out) return set_error(PN_ERR_INVALID, "output pointer is NULL");
+    return sharded_query_radius<T>(sh, queries, nq, q_cols, q_row_stride, radius, offsets, idx_out, dist_out, flags);
+}
+extern "C" int pn_sharded_query_radius_with_distance_f32(const pn_sharded *sh, const float *queries, size_t nq,
+                                                         size_t q_cols, ptrdiff_t q_row_stride, float radius,
+                                                         unsigned flags, uint64_t *offsets, uint64_t **idx_out,
+                                                         float **dist_out) {
+    return sharded_query_radius_wd<float>(sh, queries, nq, q_cols, q_row_stride, radius, flags, offsets, idx_out, dist_out);
+}
+extern "C" int pn_sharded_query_radius_with_distance_f64(const pn_sharded *sh, const double *queries, size_t nq,
+                                                         size_t q_cols, ptrdiff_t q_row_stride, double radius,
+                                                         unsigned flags, uint64_t *offsets, uint64_t **idx_out,
+                                                         double **dist_out) {
+    return sharded_query_radius_wd<double>(sh, queries, nq, q_cols, q_row_stride, radius, flags, offsets, idx_out,
+                                           dist_out);
 }
 extern "C" int pn_sharded_query_radius_f32(const pn_sharded *sh, const float *queries, size_t nq, size_t q_cols,
                                            ptrdiff_t q_row_stride, float radius, uint64_t *offsets, uint64_t **idx_out) {

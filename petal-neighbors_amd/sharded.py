@@ -229,6 +229,67 @@ class ShardedIndex:
                 _lib.lib().pn_free(out)
         return offsets, idx
 
+    def query_radius_with_distance_batch(self, queries, distance, sort: bool = False):
+        """``query_radius_batch`` over all shards plus each neighbour's distance: ``(offsets, idx, dist)``, ascending by
+        global row, or by (distance, global row) with ``sort=True`` (``pn_sharded_query_radius_with_distance_*``)."""
+        from . import _lib
+        from .errors import check
+        a = np.ascontiguousarray(queries, dtype=self.dtype)
+        if a.ndim != 2:
+            raise ValueError("queries must be 2-D")
+        nq, qc = a.shape
+        offsets = np.zeros(nq + 1, dtype=np.uint64)
+        out_i, out_d = C.c_void_p(0), C.c_void_p(0)
+        r = C.c_double(distance) if self.dtype == np.float64 else C.c_float(distance)
+        flags = _lib.PN_RADIUS_SORTED if sort else 0
+        fn = getattr(_lib.lib(), "pn_sharded_query_radius_with_distance_" + self._sfx)
+        try:
+            check(fn(self._h, a.ctypes.data, nq, qc, max(qc, 1), r, flags, offsets.ctypes.data, C.byref(out_i),
+                     C.byref(out_d)))
+            total = int(offsets[-1])
+            idx = np.empty(0, dtype=np.uint64)
+            dist = np.empty(0, dtype=self.dtype)
+            if total:
+                idx = np.frombuffer((C.c_uint64 * total).from_address(out_i.value), dtype=np.uint64).copy()
+                ct = C.c_double if self.dtype == np.float64 else C.c_float
+                dist = np.frombuffer((ct * total).from_address(out_d.value), dtype=self.dtype).copy()
+        finally:
+            for p in (out_i, out_d):
+                if p.value:
+                    _lib.lib().pn_free(p)
+        return offsets, idx, dist
+
+    def query_radius_with_distance_device(self, queries, distance, capacity: int, sort: bool = False, out_offsets=None,
+                                          out_idx=None, out_dist=None, out_total=None, stream=None):
+        """``pn_sharded_query_radius_with_distance_device_*`` (one-shard handles): see
+        ``BallTree.query_radius_with_distance_device``."""
+        import torch
+        from . import _lib
+        from .errors import check
+        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
+        if not isinstance(queries, torch.Tensor) or queries.dtype != tdt or queries.dim() != 2 or not queries.is_cuda:
+            raise ValueError("queries must be a 2-D CUDA tensor of the handle's dtype (%s)" % self.dtype)
+        if int(capacity) < 0:
+            raise ValueError("capacity must be >= 0")
+        if queries.shape[1] > 1 and queries.stride(1) != 1:
+            queries = queries.contiguous()
+        nq, qc = queries.shape
+        dev = queries.device
+        cap = max(int(capacity), 1)
+        offs = out_offsets if out_offsets is not None else torch.empty(nq + 1, dtype=torch.int64, device=dev)
+        idx = out_idx if out_idx is not None else torch.empty(cap, dtype=torch.int64, device=dev)
+        dist = out_dist if out_dist is not None else torch.empty(cap, dtype=tdt, device=dev)
+        tot = out_total if out_total is not None else torch.empty(1, dtype=torch.int64, device=dev)
+        if dist.dtype != tdt or idx.numel() < int(capacity) or dist.numel() < int(capacity) or offs.numel() < nq + 1:
+            raise ValueError("output tensors are too small or of the wrong type")
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        r = C.c_double(distance) if self.dtype == np.float64 else C.c_float(distance)
+        flags = _lib.PN_RADIUS_SORTED if sort else 0
+        fn = getattr(_lib.lib(), f"pn_sharded_query_radius_with_distance_device_{self._sfx}")
+        check(fn(self._h, queries.data_ptr() if nq * qc else None, nq, qc, queries.stride(0) if nq > 1 else max(qc, 1), r,
+                 flags, offs.data_ptr(), idx.data_ptr(), dist.data_ptr(), int(capacity), tot.data_ptr(), C.c_void_p(st)))
+        return offs, idx, dist, tot
+
 
 class AbiShardEngine:
     """Default engine of ``ShardedBallTree``: the whole batch -- local shard, all-gather, merge -- is ONE call into
