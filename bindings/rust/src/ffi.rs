@@ -5,6 +5,7 @@ use std::os::raw::{c_char, c_int, c_uint, c_void};
 
 /// `flags` of the radius calls with distances: each list by (distance, index) ascending
 pub const PN_RADIUS_SORTED: c_uint = 1;
+pub const PN_SELF_INCLUDE: c_uint = 2;
 
 #[repr(C)]
 pub struct pn_index {
@@ -75,6 +76,25 @@ extern "C" {
                                                             flags: c_uint, d_offsets: *mut u64, d_idx: *mut u64,
                                                             d_dist: *mut f64, capacity: usize, d_total: *mut u64,
                                                             stream: *mut c_void) -> c_int;
+
+    /// self-queries: every indexed row against its own index, the row itself left out (PN_SELF_INCLUDE keeps it)
+    pub fn pn_query_self_f32(index: *const pn_index, k: usize, flags: c_uint, idx_out: *mut u64, dist_out: *mut f32) -> c_int;
+    pub fn pn_query_self_f64(index: *const pn_index, k: usize, flags: c_uint, idx_out: *mut u64, dist_out: *mut f64) -> c_int;
+    pub fn pn_query_self_device_f32(index: *const pn_index, k: usize, flags: c_uint, d_idx: *mut u64, d_dist: *mut f32,
+                                    stream: *mut c_void) -> c_int;
+    pub fn pn_query_self_device_f64(index: *const pn_index, k: usize, flags: c_uint, d_idx: *mut u64, d_dist: *mut f64,
+                                    stream: *mut c_void) -> c_int;
+    /// dist_out nullable (PN_RADIUS_SORTED needs it); *idx_out / *dist_out released with pn_free
+    pub fn pn_query_radius_self_f32(index: *const pn_index, radius: f32, flags: c_uint, offsets: *mut u64,
+                                    idx_out: *mut *mut u64, dist_out: *mut *mut f32) -> c_int;
+    pub fn pn_query_radius_self_f64(index: *const pn_index, radius: f64, flags: c_uint, offsets: *mut u64,
+                                    idx_out: *mut *mut u64, dist_out: *mut *mut f64) -> c_int;
+    pub fn pn_query_radius_self_device_f32(index: *const pn_index, radius: f32, flags: c_uint, d_offsets: *mut u64,
+                                           d_idx: *mut u64, d_dist: *mut f32, capacity: usize, d_total: *mut u64,
+                                           stream: *mut c_void) -> c_int;
+    pub fn pn_query_radius_self_device_f64(index: *const pn_index, radius: f64, flags: c_uint, d_offsets: *mut u64,
+                                           d_idx: *mut u64, d_dist: *mut f64, capacity: usize, d_total: *mut u64,
+                                           stream: *mut c_void) -> c_int;
 
     pub fn pn_pairwise_f32(x: *const f32, n_rows: usize, n_cols: usize, row_stride: isize, device: c_int,
                            out: *mut f32) -> c_int;

@@ -41,6 +41,11 @@ pub trait Elem: Copy + Default + PartialOrd + 'static {
     unsafe fn radius_wd(ix: *const ffi::pn_index, q: *const Self, qc: usize, r: Self, flags: std::os::raw::c_uint,
                         off: *mut u64, out: *mut *mut u64, dout: *mut *mut Self) -> c_int;
     #[doc(hidden)]
+    unsafe fn self_knn(ix: *const ffi::pn_index, k: usize, flags: std::os::raw::c_uint, i: *mut u64, d: *mut Self) -> c_int;
+    #[doc(hidden)]
+    unsafe fn self_radius(ix: *const ffi::pn_index, r: Self, flags: std::os::raw::c_uint, off: *mut u64, out: *mut *mut u64,
+                          dout: *mut *mut Self) -> c_int;
+    #[doc(hidden)]
     unsafe fn radius_of(ix: *const ffi::pn_index, n: u64, out: *mut Self) -> c_int;
     #[doc(hidden)]
     unsafe fn lower_bound(ix: *const ffi::pn_index, a: u64, b: u64, out: *mut Self) -> c_int;
@@ -53,7 +58,7 @@ pub trait Elem: Copy + Default + PartialOrd + 'static {
 }
 macro_rules! impl_elem {
     ($t:ty, $create:ident, $create_cos:ident, $query:ident, $radius:ident, $radius_wd:ident, $rad_of:ident, $lb:ident,
-     $eu:ident, $reu:ident, $cos:ident, $pw:ident, $pwc:ident) => {
+     $eu:ident, $reu:ident, $cos:ident, $pw:ident, $pwc:ident, $self_knn:ident, $self_rad:ident) => {
         impl Elem for $t {
             unsafe fn create(p: *const Self, n: usize, d: usize, rs: isize, cs: isize, cosine: bool, out: *mut *mut ffi::pn_index) -> c_int {
                 if cosine { ffi::$create_cos(p, n, d, rs, cs, 0, out) } else { ffi::$create(p, n, d, rs, cs, 0, out) }
@@ -67,6 +72,13 @@ macro_rules! impl_elem {
             unsafe fn radius_wd(ix: *const ffi::pn_index, q: *const Self, qc: usize, r: Self, flags: std::os::raw::c_uint,
                                 off: *mut u64, out: *mut *mut u64, dout: *mut *mut Self) -> c_int {
                 ffi::$radius_wd(ix, q, 1, qc, qc as isize, r, flags, off, out, dout)
+            }
+            unsafe fn self_knn(ix: *const ffi::pn_index, k: usize, flags: std::os::raw::c_uint, i: *mut u64, d: *mut Self) -> c_int {
+                ffi::$self_knn(ix, k, flags, i, d)
+            }
+            unsafe fn self_radius(ix: *const ffi::pn_index, r: Self, flags: std::os::raw::c_uint, off: *mut u64,
+                                  out: *mut *mut u64, dout: *mut *mut Self) -> c_int {
+                ffi::$self_rad(ix, r, flags, off, out, dout)
             }
             unsafe fn radius_of(ix: *const ffi::pn_index, n: u64, out: *mut Self) -> c_int { ffi::$rad_of(ix, n, out) }
             unsafe fn lower_bound(ix: *const ffi::pn_index, a: u64, b: u64, out: *mut Self) -> c_int { ffi::$lb(ix, a, b, out) }
@@ -83,11 +95,11 @@ macro_rules! impl_elem {
 impl_elem!(f32, pn_index_create_f32, pn_index_create_cosine_f32, pn_query_f32, pn_query_radius_f32,
            pn_query_radius_with_distance_f32, pn_tree_radius_of_f32,
            pn_tree_node_distance_lower_bound_f32, pn_euclidean_f32, pn_reuclidean_f32, pn_cosine_f32, pn_pairwise_f32,
-           pn_pairwise_cosine_f32);
+           pn_pairwise_cosine_f32, pn_query_self_f32, pn_query_radius_self_f32);
 impl_elem!(f64, pn_index_create_f64, pn_index_create_cosine_f64, pn_query_f64, pn_query_radius_f64,
            pn_query_radius_with_distance_f64, pn_tree_radius_of_f64,
            pn_tree_node_distance_lower_bound_f64, pn_euclidean_f64, pn_reuclidean_f64, pn_cosine_f64, pn_pairwise_f64,
-           pn_pairwise_cosine_f64);
+           pn_pairwise_cosine_f64, pn_query_self_f64, pn_query_radius_self_f64);
 
 pub mod distance {
     use super::*;
@@ -216,6 +228,36 @@ impl<'a, A: Elem, M: Metric<A>> BallTree<'a, A, M> {
             ffi::pn_free(dout as *mut _);
         }
         (idx, dist)
+    }
+    /// extension: the k nearest OTHER rows of every indexed row, (n, min(k, n - 1)) indices and distances ordered by
+    /// (distance, index); `include_self` keeps each row in its own list ((n, min(k, n)): `query_batch(points, k)`)
+    pub fn query_self(&self, k: usize, include_self: bool) -> (Array2<u64>, Array2<A>) {
+        let n = self.points.nrows();
+        let kout = k.min(if include_self { n } else { n - 1 });
+        let (mut idx, mut dist) = (Array2::<u64>::zeros((n, kout)), Array2::<A>::default((n, kout)));
+        let flags = if include_self { ffi::PN_SELF_INCLUDE } else { 0 };
+        if kout > 0 {
+            ok(unsafe { A::self_knn(self.handle, k, flags, idx.as_mut_ptr(), dist.as_mut_ptr()) });
+        }
+        (idx, dist)
+    }
+    /// extension: { j != i : distance(p_i, p_j) < r } for every indexed row i as CSR (offsets [n + 1], indices,
+    /// distances); ascending indices, or nearest first with `sorted`; `include_self` keeps row i where d(i, i) < r
+    pub fn query_radius_self(&self, r: A, sorted: bool, include_self: bool) -> (Vec<u64>, Vec<usize>, Vec<A>) {
+        let n = self.points.nrows();
+        let mut off = vec![0u64; n + 1];
+        let mut out: *mut u64 = std::ptr::null_mut();
+        let mut dout: *mut A = std::ptr::null_mut();
+        let flags = (if sorted { ffi::PN_RADIUS_SORTED } else { 0 }) | (if include_self { ffi::PN_SELF_INCLUDE } else { 0 });
+        ok(unsafe { A::self_radius(self.handle, r, flags, off.as_mut_ptr(), &mut out, &mut dout) });
+        let total = off[n] as usize;
+        let idx = unsafe { std::slice::from_raw_parts(out, total) }.iter().map(|&i| i as usize).collect();
+        let dist = unsafe { std::slice::from_raw_parts(dout, total) }.to_vec();
+        unsafe {
+            ffi::pn_free(out as *mut _);
+            ffi::pn_free(dout as *mut _);
+        }
+        (off, idx, dist)
     }
     /// extension: the rows of `queries` in ONE call (what the GPU is for); (nq, min(k, n)) indices and distances
     pub fn query_batch(&self, queries: ArrayView2<A>, k: usize) -> (Array2<u64>, Array2<A>) {

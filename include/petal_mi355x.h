@@ -57,7 +57,8 @@ extern "C" {
  * pn_debug_seed_model_feedback, PN_OPT_BF16_WAVES, PN_OPT_SEED_MODEL, pn_info.seed_model (the former reserved word);
  * PN_OPT_MFMA_STRUCTURE = 1 is now PN_ERR_INVALID.  Everything of version 2 is unchanged.
  * Additive within version 3 (callers detect them by symbol): pn_query_radius_with_distance_{,device_}{f32,f64},
- * pn_sharded_query_radius_with_distance_{,device_}{f32,f64}, PN_RADIUS_SORTED. */
+ * pn_sharded_query_radius_with_distance_{,device_}{f32,f64}, PN_RADIUS_SORTED; pn_query_self_{,device_}{f32,f64},
+ * pn_query_radius_self_{,device_}{f32,f64}, PN_SELF_INCLUDE. */
 #define PN_ABI_VERSION 3
 
 /* ---- error codes.  EMPTY / NOT_CONTIGUOUS are ArrayError (src/lib.rs:9-16). */
@@ -272,6 +273,51 @@ int pn_query_radius_with_distance_device_f64(const pn_index *index, const double
                                              size_t q_row_stride, double radius, unsigned flags, uint64_t *d_offsets,
                                              uint64_t *d_idx, double *d_dist, size_t capacity, uint64_t *d_total,
                                              void *stream);
+
+/* ---- self-queries: every indexed row i against its own index (DBSCAN / OPTICS / HDBSCAN core distances, kNN graphs),
+ * the row itself left out.  The queries are the index's own rows in HBM: nothing is copied up, and every tier serves
+ * them as it serves ordinary queries of the rows' length.  Rows are answered 2^18 at a time (k-NN and radius alike), so
+ * the handle's workspace is sized as for a batch of at most 2^18 queries: a chunk's rows are packed into it like any
+ * query batch's (the narrow bf16 tier's k-NN reads them in place), never the whole corpus.  Row i is identified as
+ * i + PN_OPT_INDEX_BASE.  Not for row-sharded handles.  pn_stats.queries counts n queries, as a batch of n would.
+ *
+ * k-NN: row i's answer is the first kout entries of the list of the rows j != i, ordered as pn_query_*'s answers
+ * ((distance, index), NaN last), distances bit-identical to metric.distance(p_i, p_j); kout = min(k, n - 1).  Exactly:
+ * pn_query_*(rows, k + 1) with, in each row's answer, the entry i + base dropped if present, else the last one -- for
+ * every input: duplicated rows, NaN rows, Cosine (where a row's distance to itself need not be 0).
+ * flags: PN_SELF_INCLUDE keeps row i in its own list: kout = min(k, n) and the answer equals pn_query_*(rows, k).  Any
+ * other bit, PN_RADIUS_SORTED included: PN_ERR_INVALID.  kout = 0 (k = 0, or n = 1 without the flag) writes nothing.
+ * Host entry points: idx_out / dist_out [n][kout]; the device holds O(2^18 x (k + 1)) entries of staging beyond the
+ * workspace (rows are answered 2^18 at a time).  Device entry points: d_idx / d_dist [n][kout] in HBM, enqueued on
+ * `stream` with the ordering contract of pn_query_device_*. */
+#define PN_SELF_INCLUDE 2
+int pn_query_self_f32(const pn_index *index, size_t k, unsigned flags, uint64_t *idx_out, float *dist_out);
+int pn_query_self_f64(const pn_index *index, size_t k, unsigned flags, uint64_t *idx_out, double *dist_out);
+int pn_query_self_device_f32(const pn_index *index, size_t k, unsigned flags, uint64_t *d_idx, float *d_dist, void *stream);
+int pn_query_self_device_f64(const pn_index *index, size_t k, unsigned flags, uint64_t *d_idx, double *d_dist,
+                             void *stream);
+/* radius: row i's list is { j != i : distance(p_i, p_j) < r } -- the index sets and edge cases of pn_query_radius_* (r <= 0,
+ * NaN, +inf, Cosine r >= 1) -- in ascending index order, or nearest-first by (distance, index) with PN_RADIUS_SORTED;
+ * PN_SELF_INCLUDE keeps row i wherever distance(p_i, p_i) < r (the answer is then pn_query_radius_with_distance_*'s for
+ * the rows).  Distances are optional (dist_out / d_dist NULL); PN_RADIUS_SORTED needs them.  Unknown flag bits:
+ * PN_ERR_INVALID.
+ * Host entry points: offsets [n + 1] caller-allocated; *idx_out (and *dist_out) allocated by the library (pn_free).  They
+ * run the pipeline twice -- a count, then the lists into staging of the exact total -- and fail with PN_ERR_DEVICE if a
+ * row's self flag (its own distance below r, evaluated from the row) ever disagreed with its list.
+ * Device entry points: the capacity contract of pn_query_radius_with_distance_device_* -- d_offsets [n + 1] always
+ * complete, entries below `capacity` written, capacity = 0 only counts (d_idx / d_dist may then be NULL), d_total[0]
+ * (nullable) = d_offsets[n], and its sorted / straddle rule.  Scratch beyond a 2^18-query batch's: one chunk's lists with
+ * the rows themselves, capacity + 2^18 entries (at most 2^18 x n), and O(2^18) words, in the handle's workspace.  They
+ * read nothing back, so they do not report a flag / list disagreement (the offsets stay well formed); the host entry
+ * points do. */
+int pn_query_radius_self_f32(const pn_index *index, float radius, unsigned flags, uint64_t *offsets, uint64_t **idx_out,
+                             float **dist_out);
+int pn_query_radius_self_f64(const pn_index *index, double radius, unsigned flags, uint64_t *offsets, uint64_t **idx_out,
+                             double **dist_out);
+int pn_query_radius_self_device_f32(const pn_index *index, float radius, unsigned flags, uint64_t *d_offsets,
+                                    uint64_t *d_idx, float *d_dist, size_t capacity, uint64_t *d_total, void *stream);
+int pn_query_radius_self_device_f64(const pn_index *index, double radius, unsigned flags, uint64_t *d_offsets,
+                                    uint64_t *d_idx, double *d_dist, size_t capacity, uint64_t *d_total, void *stream);
 
 /* ---- distance::pairwise(x, &Euclidean) (src/distance.rs:58-74): n x n
  * symmetric matrix, zero diagonal, n < 2 -> zeros. Host in, host out. */

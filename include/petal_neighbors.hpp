@@ -81,6 +81,14 @@ inline std::vector<double> pairwise(const double *x, size_t n, size_t d, int dev
 }
 }  // namespace distance
 
+// the CSR answer of BallTree::query_radius_self: row i's neighbours are idx[offsets[i] .. offsets[i + 1]] (dist beside
+// them when asked for)
+template <typename A>
+struct SelfRadius {
+    std::vector<size_t> offsets, idx;
+    std::vector<A> dist;
+};
+
 // BallTree<'a, A, M> (src/ball_tree.rs:15-24): M = distance::Euclidean (default) or distance::Cosine.  Under Cosine
 // every query is an exact scan (cosine distance is not a metric; see pn_index_create_cosine_* in petal_mi355x.h).
 template <typename A, typename M = distance::Euclidean>
@@ -223,6 +231,42 @@ class BallTree {
             check(pn_query_f32(h_, queries, nq, len, (ptrdiff_t)len, k, idx_out, dist_out));
         else
             check(pn_query_f64(h_, queries, nq, len, (ptrdiff_t)len, k, idx_out, dist_out));
+    }
+    // extension: self-queries (pn_query_self_*): the k nearest OTHER rows of every indexed row, [n][kout] row-major with
+    // kout = min(k, n - 1); include_self keeps each row in its own list (kout = min(k, n))
+    std::pair<std::vector<size_t>, std::vector<A>> query_self(size_t k, bool include_self) const {
+        const size_t cap = include_self ? n_ : n_ - 1;
+        const size_t kout = k < cap ? k : cap;
+        std::vector<uint64_t> idx(n_ * kout);
+        std::vector<A> dist(n_ * kout);
+        const unsigned flags = include_self ? PN_SELF_INCLUDE : 0u;
+        if (kout) {
+            if constexpr (kF32)
+                check(pn_query_self_f32(h_, k, flags, idx.data(), dist.data()));
+            else
+                check(pn_query_self_f64(h_, k, flags, idx.data(), dist.data()));
+        }
+        return {std::vector<size_t>(idx.begin(), idx.end()), std::move(dist)};
+    }
+    // extension: { j != i : distance(p_i, p_j) < r } for every indexed row i (pn_query_radius_self_*) as CSR; dist stays
+    // empty unless with_distance; sorted (needs with_distance): nearest first by (distance, index)
+    SelfRadius<A> query_radius_self(A r, bool with_distance, bool sorted, bool include_self) const {
+        SelfRadius<A> res;
+        std::vector<uint64_t> off(n_ + 1, 0);
+        uint64_t *out = nullptr;
+        A *dout = nullptr;
+        const unsigned flags = (sorted ? PN_RADIUS_SORTED : 0u) | (include_self ? PN_SELF_INCLUDE : 0u);
+        if constexpr (kF32)
+            check(pn_query_radius_self_f32(h_, r, flags, off.data(), &out, with_distance ? &dout : nullptr));
+        else
+            check(pn_query_radius_self_f64(h_, r, flags, off.data(), &out, with_distance ? &dout : nullptr));
+        const uint64_t total = off[n_];
+        res.offsets.assign(off.begin(), off.end());
+        res.idx.assign(out, out + total);
+        if (dout) res.dist.assign(dout, dout + total);
+        pn_free(out);
+        pn_free(dout);
+        return res;
     }
     pn_index *handle() const { return h_; }
 };

@@ -23,6 +23,7 @@ PN_OPT_SHARED_THRESHOLDS = 8
 PN_OPT_BF16_WAVES = 9
 PN_OPT_SEED_MODEL = 10
 PN_RADIUS_SORTED = 1
+PN_SELF_INCLUDE = 2
 
 
 class PnInfo(C.Structure):
@@ -84,6 +85,14 @@ SIGNATURES = {
                                                       _vp, _vp]),
     "pn_query_radius_with_distance_device_f64": (_i, [_vp, _vp, _sz, _sz, _sz, C.c_double, C.c_uint, _vp, _vp, _vp, _sz,
                                                       _vp, _vp]),
+    "pn_query_self_f32": (_i, [_vp, _sz, C.c_uint, _vp, _vp]),
+    "pn_query_self_f64": (_i, [_vp, _sz, C.c_uint, _vp, _vp]),
+    "pn_query_self_device_f32": (_i, [_vp, _sz, C.c_uint, _vp, _vp, _vp]),
+    "pn_query_self_device_f64": (_i, [_vp, _sz, C.c_uint, _vp, _vp, _vp]),
+    "pn_query_radius_self_f32": (_i, [_vp, C.c_float, C.c_uint, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "pn_query_radius_self_f64": (_i, [_vp, C.c_double, C.c_uint, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "pn_query_radius_self_device_f32": (_i, [_vp, C.c_float, C.c_uint, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "pn_query_radius_self_device_f64": (_i, [_vp, C.c_double, C.c_uint, _vp, _vp, _vp, _sz, _vp, _vp]),
     "pn_free": (None, [_vp]),
     "pn_pairwise_f32": (_i, [_vp, _sz, _sz, _ssz, _i, _vp]),
     "pn_pairwise_f64": (_i, [_vp, _sz, _sz, _ssz, _i, _vp]),

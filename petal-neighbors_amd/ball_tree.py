@@ -367,3 +367,102 @@ class BallTree:
                                                  queries.stride(0) if nq > 1 else max(qc, 1), int(k),
                                                  out_idx.data_ptr(), out_dist.data_ptr(), C.c_void_p(st)))
         return out_idx, out_dist
+
+    # ------------------------------------------------------------- self-queries
+    # Every indexed row against its own index, the row itself left out (``pn_query_self_*`` / ``pn_query_radius_self_*``):
+    # the rows already in HBM are the queries -- nothing is sent up again.
+    def _self_flags(self, include_self, sort=False):
+        return (_lib.PN_SELF_INCLUDE if include_self else 0) | (_lib.PN_RADIUS_SORTED if sort else 0)
+
+    def _self_k(self, k, include_self):
+        if int(k) < 0:
+            raise ValueError("k must be >= 0")
+        return min(int(k), self._n if include_self else self._n - 1)
+
+    def query_self(self, k: int, include_self: bool = False):
+        """The k nearest OTHER rows of every indexed row: ``(idx uint64 [n, kout], dist [n, kout])``, kout = min(k, n - 1),
+        each row's list ordered by (distance, index).  ``include_self=True``: the row stays in its own list, kout =
+        min(k, n) -- ``query_batch(rows, k)``."""
+        kout = self._self_k(k, include_self)
+        idx = np.empty((self._n, kout), dtype=np.uint64)
+        dist = np.empty((self._n, kout), dtype=self.dtype)
+        if kout:
+            fn = getattr(_lib.lib(), f"pn_query_self_{self._sfx}")
+            check(fn(self._h, int(k), self._self_flags(include_self), idx.ctypes.data, dist.ctypes.data))
+        return idx, dist
+
+    def query_self_device(self, k: int, include_self: bool = False, out_idx=None, out_dist=None, stream=None):
+        """``query_self`` with the results in HBM: CUDA tensors ``(idx int64 [n, kout], dist [n, kout])``, enqueued on
+        ``stream`` (default: the current torch stream)."""
+        import torch
+        tdt = torch.float32 if self._sfx == "f32" else torch.float64
+        kout = self._self_k(k, include_self)
+        dev = torch.device("cuda", self.device)
+        if out_idx is None:
+            out_idx = torch.empty((self._n, kout), dtype=torch.int64, device=dev)
+        if out_dist is None:
+            out_dist = torch.empty((self._n, kout), dtype=tdt, device=dev)
+        if out_dist.dtype != tdt or out_idx.numel() < self._n * kout or out_dist.numel() < self._n * kout:
+            raise ValueError("output tensors are too small or of the wrong type")
+        if kout:
+            st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+            check(getattr(_lib.lib(), f"pn_query_self_device_{self._sfx}")(
+                self._h, int(k), self._self_flags(include_self), out_idx.data_ptr(), out_dist.data_ptr(), C.c_void_p(st)))
+        return out_idx, out_dist
+
+    def query_radius_self(self, r, with_distance: bool = False, sort: bool = False, include_self: bool = False):
+        """``{ j != i : distance(p_i, p_j) < r }`` for every indexed row i, as CSR: ``(offsets uint64 [n+1], idx uint64,
+        dist or None)``; lists ascending by index, or by (distance, index) with ``sort=True`` (needs ``with_distance``).
+        ``include_self=True`` keeps row i wherever its distance to itself is below r."""
+        if sort and not with_distance:
+            raise ValueError("sort=True needs with_distance=True")
+        offsets = np.zeros(self._n + 1, dtype=np.uint64)
+        out_i, out_d = C.c_void_p(0), C.c_void_p(0)
+        rr = C.c_float(r) if self._sfx == "f32" else C.c_double(r)
+        fn = getattr(_lib.lib(), f"pn_query_radius_self_{self._sfx}")
+        try:
+            check(fn(self._h, rr, self._self_flags(include_self, sort), offsets.ctypes.data, C.byref(out_i),
+                     C.byref(out_d) if with_distance else None))
+            total = int(offsets[-1])
+            idx = np.empty(0, dtype=np.uint64)
+            dist = np.empty(0, dtype=self.dtype) if with_distance else None
+            if total:
+                idx = np.frombuffer((C.c_uint64 * total).from_address(out_i.value), dtype=np.uint64).copy()
+                if with_distance:
+                    ct = C.c_float if self._sfx == "f32" else C.c_double
+                    dist = np.frombuffer((ct * total).from_address(out_d.value), dtype=self.dtype).copy()
+        finally:
+            for p in (out_i, out_d):
+                if p.value:
+                    _lib.lib().pn_free(p)
+        return offsets, idx, dist
+
+    def query_radius_self_device(self, r, capacity: int, with_distance: bool = False, sort: bool = False,
+                                 include_self: bool = False, out_offsets=None, out_idx=None, out_dist=None, out_total=None,
+                                 stream=None):
+        """``query_radius_self`` in HBM with the capacity contract of ``query_radius_with_distance_device``: CUDA tensors
+        ``(offsets int64 [n+1], idx int64 [capacity], dist [capacity] or None, total int64 [1])``."""
+        import torch
+        tdt = torch.float32 if self._sfx == "f32" else torch.float64
+        if int(capacity) < 0:
+            raise ValueError("capacity must be >= 0")
+        if sort and not with_distance:
+            raise ValueError("sort=True needs with_distance=True")
+        dev = torch.device("cuda", self.device)
+        cap = max(int(capacity), 1)
+        offs = out_offsets if out_offsets is not None else torch.empty(self._n + 1, dtype=torch.int64, device=dev)
+        idx = out_idx if out_idx is not None else torch.empty(cap, dtype=torch.int64, device=dev)
+        dist = None
+        if with_distance:
+            dist = out_dist if out_dist is not None else torch.empty(cap, dtype=tdt, device=dev)
+            if dist.dtype != tdt or dist.numel() < int(capacity):
+                raise ValueError("output tensors are too small or of the wrong type")
+        tot = out_total if out_total is not None else torch.empty(1, dtype=torch.int64, device=dev)
+        if idx.numel() < int(capacity) or offs.numel() < self._n + 1:
+            raise ValueError("output tensors are too small")
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        rr = C.c_float(r) if self._sfx == "f32" else C.c_double(r)
+        fn = getattr(_lib.lib(), f"pn_query_radius_self_device_{self._sfx}")
+        check(fn(self._h, rr, self._self_flags(include_self, sort), offs.data_ptr(), idx.data_ptr(),
+                 dist.data_ptr() if dist is not None else None, int(capacity), tot.data_ptr(), C.c_void_p(st)))
+        return offs, idx, dist, tot

@@ -41,6 +41,7 @@ UNITS = [
     ("sharded.hip", []),
     ("radius_device.hip", []),
     ("csr_sort.hip", []),
+    ("self_graph.hip", ["-ffp-contract=off"]),
     ("metric.cpp", ["-ffp-contract=off"]),
     ("tree.cpp", ["-ffp-contract=off"]),
 ]

@@ -142,6 +142,10 @@ struct Workspace {
     DevBuf w_rpos, w_rfin, w_rcx, w_rox, w_rscan;  // pn_query_radius_device_*: list positions, counts, per-segment counts / offsets, scan scratch
     DevBuf w_rkd;  // pn_query_radius_with_distance_*: the filter tier's kept rows' distances ([2][nq][kept_stride])
     DevBuf w_cs_nch, w_cs_off, w_cs_scan, w_cs_idx, w_cs_dist, w_cs_hoff;  // PN_RADIUS_SORTED: csr_sort.hip's scratch
+    // self-queries (pn_query_self_*, pn_query_radius_self_*): the pipeline's answers with the rows themselves, a chunk's
+    // inner offsets and scanned counts, self flags (+ the disagreement word), adjusted counts, scan scratch, and the host
+    // radius entry's offsets + total
+    DevBuf w_sf_idx, w_sf_dist, w_sf_off, w_sf_coff, w_sf_flag, w_sf_cnt, w_sf_scan, w_sf_hoff;
     // small calls (tiny_*): mapped pinned host memory the one kernel of the call reads its queries from and writes its
     // answers to -- no copy commands
     void *pin_in = nullptr, *pin_out = nullptr;
@@ -167,7 +171,7 @@ struct Workspace {
     hipEvent_t done = nullptr;
     hipStream_t last_stream = nullptr;
     bool in_flight = false;
-    DevBuf *all[43] = {&w_cs_hoff, &w_rkd, &w_cs_nch, &w_cs_off, &w_cs_scan, &w_cs_idx, &w_cs_dist, &w_gqn, &w_rpos, &w_rfin, &w_rcx, &w_rox, &w_rscan, &w_q, &w_qnorm, &w_qnrm, &w_keys, &w_idx, &w_cnt, &w_tau, &w_flags, &w_sel, &w_misc, &w2_keys, &w2_idx,
+    DevBuf *all[51] = {&w_sf_idx, &w_sf_dist, &w_sf_off, &w_sf_coff, &w_sf_flag, &w_sf_cnt, &w_sf_scan, &w_sf_hoff, &w_cs_hoff, &w_rkd, &w_cs_nch, &w_cs_off, &w_cs_scan, &w_cs_idx, &w_cs_dist, &w_gqn, &w_rpos, &w_rfin, &w_rcx, &w_rox, &w_rscan, &w_q, &w_qnorm, &w_qnrm, &w_keys, &w_idx, &w_cnt, &w_tau, &w_flags, &w_sel, &w_misc, &w2_keys, &w2_idx,
                        &w2_cnt, &w2_tau, &w_lo, &w_bq, &w_qn, &w_qbad, &w_gq, &w_gidx, &w_gdist, &w_gsel, &w_seed,
                        &w_qstat, &w_lists, &w_hq, &w_hidx, &w_hdist, &w_fparts, &w_pcnt};
     std::vector<void *> retired;  // outgrown allocations, freed once `done` has passed (DevBuf::ensure)
@@ -3157,6 +3161,10 @@ extern "C" int pn_query_radius_with_distance_f64(const pn_index *ix, const doubl
 // PN_RADIUS_SORTED orders every list that ends at or below `capacity` by (distance, index) -- the list that straddles
 // the capacity is left in ascending index order, as far as it is written
 template <typename T>
+static int radius_device_enqueue(const pn_index *ix, Workspace &ws, const T *d_q, size_t nq, size_t q_cols, size_t q_stride,
+                                 T radius, uint64_t *d_offsets, uint64_t *d_idx, size_t capacity, uint64_t *d_total,
+                                 hipStream_t s, T *d_dist, unsigned flags, bool count_queries = true);
+template <typename T>
 static int radius_device_impl(const pn_index *ix, const T *d_q, size_t nq, size_t q_cols, size_t q_stride, T radius,
                               uint64_t *d_offsets, uint64_t *d_idx, size_t capacity, uint64_t *d_total, hipStream_t s,
                               bool with_dist = false, T *d_dist = nullptr, unsigned flags = 0) {
@@ -3178,13 +3186,21 @@ static int radius_device_impl(const pn_index *ix, const T *d_q, size_t nq, size_
     WsLease lease(ix);
     lease.s = s;
     PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
-    Workspace &ws = *lease.ws;
+    return radius_device_enqueue<T>(ix, *lease.ws, d_q, nq, q_cols, q_stride, radius, d_offsets, d_idx, capacity, d_total,
+                                    s, d_dist, flags);
+}
+// the pipeline of radius_device_impl in a workspace the caller holds (also the self-queries' inner call); nq >= 1,
+// arguments checked.  count_queries: add nq to pn_stats.queries
+template <typename T>
+static int radius_device_enqueue(const pn_index *ix, Workspace &ws, const T *d_q, size_t nq, size_t q_cols, size_t q_stride,
+                                 T radius, uint64_t *d_offsets, uint64_t *d_idx, size_t capacity, uint64_t *d_total,
+                                 hipStream_t s, T *d_dist, unsigned flags, bool count_queries) {
     int level;
     {
         std::lock_guard<std::mutex> lk(ix->sh.mu);
         recs_collect(ix, false);
         level = ix->sh.bf16_level;
-        ix->sh.stats.queries += nq;
+        if (count_queries) ix->sh.stats.queries += nq;
     }
     const size_t dim_eff = q_cols < ix->dim ? q_cols : ix->dim;
     const size_t nq_pad = round_up(nq, (size_t)256);
@@ -3284,6 +3300,279 @@ extern "C" int pn_query_radius_with_distance_device_f64(const pn_index *ix, cons
     PNCHK(radius_wd_device_args(d_offsets, d_idx, d_dist, capacity, flags));
     return radius_device_impl<double>(ix, d_q, nq, q_cols, q_stride, radius, d_offsets, d_idx, capacity, d_total,
                                       (hipStream_t)stream, true, d_dist, flags);
+}
+
+// ---------------------------------------------------------------------------
+// self-queries: every indexed row against its own index (pn_query_self_*, pn_query_radius_self_*).  The queries are the
+// rows in HBM (d_pts, q_stride = ld, q_cols = dim: every tier serves them as it serves ordinary queries, the narrow bf16
+// tier's fused pack reads them in place); the row itself is taken out of its answer by self_graph.hip.
+// ---------------------------------------------------------------------------
+static int self_args(const pn_index *ix, unsigned flags, unsigned allowed, int elem_bytes) {
+    if (flags & ~allowed) return fail(PN_ERR_INVALID, "unknown self-query flags 0x%x", flags);
+    if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
+    if (ix->elem_bytes != elem_bytes) return fail(PN_ERR_INVALID, "index element type mismatch");
+    return PN_OK;
+}
+// k-NN: kout = min(k, n - 1) answers per row (min(k, n) with PN_SELF_INCLUDE); kin = what the pipeline is asked for
+static void self_knn_sizes(const pn_index *ix, size_t k, bool include, size_t *kin, size_t *kout) {
+    if (include) {
+        *kout = *kin = k < ix->n ? k : ix->n;
+        return;
+    }
+    *kout = k < ix->n - 1 ? k : ix->n - 1;
+    *kin = *kout + 1;
+}
+constexpr size_t kSelfChunk = (size_t)1 << 18;  // rows per pipeline call (query_enqueue's own chunk)
+// rows [r0, r0 + nqc): their answers [nqc][kout] at oi / od
+template <typename T>
+static int self_knn_chunk(const pn_index *ix, Workspace &ws, size_t r0, size_t nqc, size_t kin, size_t kout, bool include,
+                          uint64_t *oi, T *od, hipStream_t s) {
+    const T *rows = (const T *)ix->d_pts + r0 * ix->ld;
+    if (include) return query_enqueue<T>(ix, ws, rows, nqc, ix->dim, ix->ld, kout, oi, od, kout, s);
+    PNCHK(ws.w_sf_idx.ensure(nqc * kin * sizeof(uint64_t)));
+    PNCHK(ws.w_sf_dist.ensure(nqc * kin * sizeof(T)));
+    uint64_t *si = (uint64_t *)ws.w_sf_idx.p;
+    T *sd = (T *)ws.w_sf_dist.p;
+    PNCHK(query_enqueue<T>(ix, ws, rows, nqc, ix->dim, ix->ld, kin, si, sd, kin, s));
+    if constexpr (sizeof(T) == 4)
+        HIPCHK(launch_knn_self_exclude_f32(si, sd, nqc, (int)kin, (int)kout, ix->index_base + r0, oi, od, s));
+    else
+        HIPCHK(launch_knn_self_exclude_f64(si, sd, nqc, (int)kin, (int)kout, ix->index_base + r0, oi, od, s));
+    return PN_OK;
+}
+template <typename T>
+static int self_knn_device(const pn_index *ix, size_t k, unsigned flags, uint64_t *d_idx, T *d_dist, hipStream_t s) {
+    PNCHK(self_args(ix, flags, PN_SELF_INCLUDE, (int)sizeof(T)));
+    if (!d_idx || !d_dist) return fail(PN_ERR_INVALID, "output buffer is NULL");
+    const bool include = flags & PN_SELF_INCLUDE;
+    size_t kin, kout;
+    self_knn_sizes(ix, k, include, &kin, &kout);
+    if (kout == 0) return PN_OK;  // k = 0, or a single row without itself: nothing to write
+    if (kin > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "k too large");
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    lease.s = s;
+    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
+    for (size_t r0 = 0; r0 < ix->n; r0 += kSelfChunk) {
+        const size_t nqc = ix->n - r0 < kSelfChunk ? ix->n - r0 : kSelfChunk;
+        PNCHK(self_knn_chunk<T>(ix, *lease.ws, r0, nqc, kin, kout, include, d_idx + r0 * kout, d_dist + r0 * kout, s));
+    }
+    return PN_OK;
+}
+// host outputs: each chunk's answer is staged in the workspace and copied down, so the device holds O(chunk x (k + 1))
+template <typename T>
+static int self_knn_host(const pn_index *ix, size_t k, unsigned flags, uint64_t *idx_out, T *dist_out) {
+    PNCHK(self_args(ix, flags, PN_SELF_INCLUDE, (int)sizeof(T)));
+    if (!idx_out || !dist_out) return fail(PN_ERR_INVALID, "output buffer is NULL");
+    const bool include = flags & PN_SELF_INCLUDE;
+    size_t kin, kout;
+    self_knn_sizes(ix, k, include, &kin, &kout);
+    if (kout == 0) return PN_OK;
+    if (kin > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "k too large");
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
+    Workspace &ws = *lease.ws;
+    hipStream_t s = lease.s;
+    for (size_t r0 = 0; r0 < ix->n; r0 += kSelfChunk) {
+        const size_t nqc = ix->n - r0 < kSelfChunk ? ix->n - r0 : kSelfChunk;
+        PNCHK(ws.w_hidx.ensure(nqc * kout * sizeof(uint64_t)));
+        PNCHK(ws.w_hdist.ensure(nqc * kout * sizeof(T)));
+        PNCHK(self_knn_chunk<T>(ix, ws, r0, nqc, kin, kout, include, (uint64_t *)ws.w_hidx.p, (T *)ws.w_hdist.p, s));
+        HIPCHK(hipMemcpyAsync(idx_out + r0 * kout, ws.w_hidx.p, nqc * kout * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(dist_out + r0 * kout, ws.w_hdist.p, nqc * kout * sizeof(T), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));  // (the staging buffers are reused by the next chunk)
+    }
+    return PN_OK;
+}
+extern "C" int pn_query_self_f32(const pn_index *ix, size_t k, unsigned flags, uint64_t *idx_out, float *dist_out) {
+    return self_knn_host<float>(ix, k, flags, idx_out, dist_out);
+}
+extern "C" int pn_query_self_f64(const pn_index *ix, size_t k, unsigned flags, uint64_t *idx_out, double *dist_out) {
+    return self_knn_host<double>(ix, k, flags, idx_out, dist_out);
+}
+extern "C" int pn_query_self_device_f32(const pn_index *ix, size_t k, unsigned flags, uint64_t *d_idx, float *d_dist,
+                                        void *stream) {
+    return self_knn_device<float>(ix, k, flags, d_idx, d_dist, (hipStream_t)stream);
+}
+extern "C" int pn_query_self_device_f64(const pn_index *ix, size_t k, unsigned flags, uint64_t *d_idx, double *d_dist,
+                                        void *stream) {
+    return self_knn_device<double>(ix, k, flags, d_idx, d_dist, (hipStream_t)stream);
+}
+
+// Radius, 2^18 rows per pipeline call like k-NN: the chunk's lists with the rows themselves go to scratch (unsorted,
+// ascending index); the self flags and adjusted counts come from the rows alone; the chunk's counts are scanned and placed
+// behind the rows before it in d_offsets (on the device: nothing is read back), and its lists are compacted at those
+// offsets below the capacity.  Scratch per chunk: capacity + nqc entries -- the chunk's entry at final position p <
+// capacity comes from a chunk-local inner position of at most (p - its first offset) + nqc, since only the chunk's rows
+// before it lose an entry.  PN_RADIUS_SORTED then sorts the final lists under the capacity: the straddle rule of
+// pn_query_radius_with_distance_device_* unchanged.  PN_SELF_INCLUDE: the same without the exclusion.  The workspace
+// word w_sf_bad counts disagreements between a self flag and the pipeline's list (self_graph.hip; never expected).
+template <typename T>
+static int radius_self_enqueue(const pn_index *ix, Workspace &ws, T radius, unsigned flags, uint64_t *d_offsets,
+                               uint64_t *d_idx, T *d_dist, size_t capacity, uint64_t *d_total, hipStream_t s,
+                               bool count_queries) {
+    const size_t n = ix->n;
+    const bool exclude = !(flags & PN_SELF_INCLUDE);
+    if (!capacity) d_dist = nullptr;  // (a pure count)
+    const size_t chunk = n < kSelfChunk ? n : kSelfChunk;
+    // inner capacity per chunk: capacity + chunk, never beyond the chunk x n entries its lists can hold
+    size_t in_cap = 0;
+    if (capacity) {
+        in_cap = capacity + chunk;
+        if (n < ((size_t)1 << 32) && in_cap > chunk * n) in_cap = chunk * n;
+    }
+    PNCHK(ws.w_sf_off.ensure((chunk + 1) * sizeof(uint64_t)));
+    PNCHK(ws.w_sf_coff.ensure((chunk + 1) * sizeof(uint64_t)));
+    PNCHK(ws.w_sf_flag.ensure(chunk * sizeof(uint32_t) + 64));
+    PNCHK(ws.w_sf_cnt.ensure(chunk * sizeof(uint32_t)));
+    PNCHK(ws.w_sf_scan.ensure((chunk / 4096 + 2) * sizeof(uint64_t)));
+    uint64_t *in_off = (uint64_t *)ws.w_sf_off.p, *part = (uint64_t *)ws.w_sf_coff.p, *in_idx = nullptr;
+    uint32_t *flag = (uint32_t *)ws.w_sf_flag.p, *cnt = (uint32_t *)ws.w_sf_cnt.p;
+    uint32_t *bad = (uint32_t *)((char *)ws.w_sf_flag.p + chunk * sizeof(uint32_t));
+    T *in_dist = nullptr;
+    if (in_cap) {
+        PNCHK(ws.w_sf_idx.ensure(in_cap * sizeof(uint64_t)));
+        in_idx = (uint64_t *)ws.w_sf_idx.p;
+        if (d_dist) {
+            PNCHK(ws.w_sf_dist.ensure(in_cap * sizeof(T)));
+            in_dist = (T *)ws.w_sf_dist.p;
+        }
+    }
+    HIPCHK(hipMemsetAsync(bad, 0, sizeof(uint32_t), s));
+    HIPCHK(hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), s));
+    const T *cn_all = ix->metric == 1 ? (const T *)ix->d_cnorm : nullptr;
+    for (size_t r0 = 0; r0 < n; r0 += chunk) {
+        const size_t nqc = n - r0 < chunk ? n - r0 : chunk;
+        const T *rows = (const T *)ix->d_pts + r0 * ix->ld;
+        PNCHK(radius_device_enqueue<T>(ix, ws, rows, nqc, ix->dim, ix->ld, radius, in_off, in_idx, in_cap, nullptr, s,
+                                       in_dist, 0, count_queries));
+        const T *cn = cn_all ? cn_all + r0 : nullptr;
+        if constexpr (sizeof(T) == 4)
+            HIPCHK(launch_radius_self_counts_f32(rows, nqc, (int)ix->dim, ix->ld, cn, radius, exclude, in_off, flag, cnt, bad, s));
+        else
+            HIPCHK(launch_radius_self_counts_f64(rows, nqc, (int)ix->dim, ix->ld, cn, radius, exclude, in_off, flag, cnt, bad, s));
+        HIPCHK(launch_exclusive_scan_u32(cnt, nqc, part, (uint64_t *)ws.w_sf_scan.p, nullptr, s));
+        HIPCHK(launch_radius_self_place(part, nqc, d_offsets + r0, s));
+        if (!capacity) continue;
+        if constexpr (sizeof(T) == 4)
+            HIPCHK(launch_radius_self_compact_f32(in_off, in_idx, in_dist, in_cap, flag, d_offsets + r0, nqc,
+                                                  ix->index_base + r0, d_idx, d_dist, capacity, bad, s));
+        else
+            HIPCHK(launch_radius_self_compact_f64(in_off, in_idx, in_dist, in_cap, flag, d_offsets + r0, nqc,
+                                                  ix->index_base + r0, d_idx, d_dist, capacity, bad, s));
+    }
+    if (d_total) HIPCHK(hipMemcpyAsync(d_total, d_offsets + n, sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+    if (capacity && d_dist && (flags & PN_RADIUS_SORTED))
+        PNCHK(csr_sort_dev<T>(ix, ws, d_offsets, n, d_idx, d_dist, (uint64_t)capacity, s));
+    return PN_OK;
+}
+// (argument checks of the radius self-queries, before any device is touched: flags, outputs, then the handle)
+static int radius_self_args(const pn_index *ix, unsigned flags, bool has_offsets, bool has_idx, bool has_dist, int elem_bytes) {
+    if (flags & ~(unsigned)(PN_RADIUS_SORTED | PN_SELF_INCLUDE)) return fail(PN_ERR_INVALID, "unknown self-query flags 0x%x", flags);
+    if (!has_offsets || !has_idx) return fail(PN_ERR_INVALID, "output buffer is NULL");
+    if ((flags & PN_RADIUS_SORTED) && !has_dist) return fail(PN_ERR_INVALID, "PN_RADIUS_SORTED needs the distance output");
+    return self_args(ix, flags, PN_RADIUS_SORTED | PN_SELF_INCLUDE, elem_bytes);
+}
+template <typename T>
+static int radius_self_device(const pn_index *ix, T radius, unsigned flags, uint64_t *d_offsets, uint64_t *d_idx, T *d_dist,
+                              size_t capacity, uint64_t *d_total, hipStream_t s) {
+    // (capacity 0 only counts: no list buffers needed)
+    PNCHK(radius_self_args(ix, flags, d_offsets != nullptr, d_idx != nullptr || !capacity, d_dist != nullptr || !capacity,
+                           (int)sizeof(T)));
+    if (ix->n > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many rows for one self-query");
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    lease.s = s;
+    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
+    return radius_self_enqueue<T>(ix, *lease.ws, radius, flags, d_offsets, d_idx, d_dist, capacity, d_total, s, true);
+}
+// host outputs: a count-only pass, then one pass with the exact total into the workspace's staging buffers; the lists are
+// then allocated here (pn_free).  Both passes run the pipeline (the count is not kept between calls).
+template <typename T>
+static int radius_self_host(const pn_index *ix, T radius, unsigned flags, uint64_t *offsets, uint64_t **idx_out,
+                            T **dist_out) {
+    PNCHK(radius_self_args(ix, flags, offsets != nullptr, idx_out != nullptr, dist_out != nullptr, (int)sizeof(T)));
+    *idx_out = nullptr;
+    if (dist_out) *dist_out = nullptr;
+    const size_t n = ix->n;
+    if (n > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many rows for one self-query");
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
+    Workspace &ws = *lease.ws;
+    hipStream_t s = lease.s;
+    PNCHK(ws.w_sf_hoff.ensure((n + 2) * sizeof(uint64_t)));
+    uint64_t *d_off = (uint64_t *)ws.w_sf_hoff.p, *d_tot = d_off + n + 1;
+    // the disagreement word of radius_self_enqueue (behind the flags of one chunk)
+    auto bad_word = [&](uint32_t *out) -> int {
+        const size_t chunk = n < kSelfChunk ? n : kSelfChunk;
+        HIPCHK(hipMemcpyAsync(out, (const char *)ws.w_sf_flag.p + chunk * sizeof(uint32_t), sizeof(uint32_t),
+                              hipMemcpyDeviceToHost, s));
+        return PN_OK;
+    };
+    uint64_t total = 0;
+    uint32_t bad = 0;
+    PNCHK(radius_self_enqueue<T>(ix, ws, radius, flags, d_off, nullptr, nullptr, 0, d_tot, s, true));
+    HIPCHK(hipMemcpyAsync(&total, d_tot, sizeof total, hipMemcpyDeviceToHost, s));
+    PNCHK(bad_word(&bad));
+    HIPCHK(hipStreamSynchronize(s));
+    if (total) {
+        PNCHK(ws.w_hidx.ensure(total * sizeof(uint64_t)));
+        if (dist_out) PNCHK(ws.w_hdist.ensure(total * sizeof(T)));
+        PNCHK(radius_self_enqueue<T>(ix, ws, radius, flags, d_off, (uint64_t *)ws.w_hidx.p,
+                                     dist_out ? (T *)ws.w_hdist.p : nullptr, total, nullptr, s, false));
+        uint32_t bad2 = 0;
+        PNCHK(bad_word(&bad2));
+        HIPCHK(hipStreamSynchronize(s));
+        bad += bad2;
+    }
+    if (bad)
+        return fail(PN_ERR_DEVICE, "self-query: %u self flags disagree with the radius lists (internal error)", bad);
+    uint64_t *out = (uint64_t *)malloc((total ? total : 1) * sizeof(uint64_t));
+    T *dout = dist_out ? (T *)malloc((total ? total : 1) * sizeof(T)) : nullptr;
+    if (!out || (dist_out && !dout)) {
+        free(out);
+        free(dout);
+        (void)hipStreamSynchronize(s);
+        return fail(PN_ERR_NOMEM, "malloc(%llu results) failed", (unsigned long long)total);
+    }
+    hipError_t e = hipMemcpyAsync(offsets, d_off, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && total) e = hipMemcpyAsync(out, ws.w_hidx.p, total * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && total && dout) e = hipMemcpyAsync(dout, ws.w_hdist.p, total * sizeof(T), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        free(out);
+        free(dout);
+        return fail(PN_ERR_DEVICE, "copying the self-query's lists back: %s", hipGetErrorString(e));
+    }
+    *idx_out = out;
+    if (dist_out) *dist_out = dout;
+    std::lock_guard<std::mutex> lk(ix->sh.mu);
+    ix->sh.stats.radius_results += total;
+    return PN_OK;
+}
+extern "C" int pn_query_radius_self_f32(const pn_index *ix, float radius, unsigned flags, uint64_t *offsets,
+                                        uint64_t **idx_out, float **dist_out) {
+    return radius_self_host<float>(ix, radius, flags, offsets, idx_out, dist_out);
+}
+extern "C" int pn_query_radius_self_f64(const pn_index *ix, double radius, unsigned flags, uint64_t *offsets,
+                                        uint64_t **idx_out, double **dist_out) {
+    return radius_self_host<double>(ix, radius, flags, offsets, idx_out, dist_out);
+}
+extern "C" int pn_query_radius_self_device_f32(const pn_index *ix, float radius, unsigned flags, uint64_t *d_offsets,
+                                               uint64_t *d_idx, float *d_dist, size_t capacity, uint64_t *d_total,
+                                               void *stream) {
+    return radius_self_device<float>(ix, radius, flags, d_offsets, d_idx, d_dist, capacity, d_total, (hipStream_t)stream);
+}
+extern "C" int pn_query_radius_self_device_f64(const pn_index *ix, double radius, unsigned flags, uint64_t *d_offsets,
+                                               uint64_t *d_idx, double *d_dist, size_t capacity, uint64_t *d_total,
+                                               void *stream) {
+    return radius_self_device<double>(ix, radius, flags, d_offsets, d_idx, d_dist, capacity, d_total, (hipStream_t)stream);
 }
 
 extern "C" void pn_free(void *p) { free(p); }

@@ -122,6 +122,33 @@ hipError_t launch_radius_gather_cap(const uint32_t *kept, const uint32_t *nkept,
                                     hipStream_t s, const void *kept_dist = nullptr, void *out_dist = nullptr,
                                     int dist_bytes = 0);
 
+// ---- self_graph.hip: self-queries of an index (pn_query_self_*, pn_query_radius_self_*)
+// out[q][r] (r < kout = kin - 1) <- in[q][r] with the entry equal to self0 + q dropped, else the last one
+hipError_t launch_knn_self_exclude_f32(const uint64_t *in_idx, const float *in_dist, size_t nq, int kin, int kout,
+                                       uint64_t self0, uint64_t *out_idx, float *out_dist, hipStream_t s);
+hipError_t launch_knn_self_exclude_f64(const uint64_t *in_idx, const double *in_dist, size_t nq, int kin, int kout,
+                                       uint64_t self0, uint64_t *out_idx, double *out_dist, hipStream_t s);
+// flag[i] <- exclude && distance(p_i, p_i) < r in the metric's arithmetic (cnorm: the rows' Cosine norms, NULL for
+// Euclidean); cnt[i] <- in_off[i + 1] - in_off[i] - flag[i]; *bad += flagged rows with an empty list (never, see the kernel)
+hipError_t launch_radius_self_counts_f32(const float *P, size_t n, int dim, size_t ld, const float *cnorm, float r,
+                                         bool exclude, const uint64_t *in_off, uint32_t *flag, uint32_t *cnt, uint32_t *bad,
+                                         hipStream_t s);
+hipError_t launch_radius_self_counts_f64(const double *P, size_t n, int dim, size_t ld, const double *cnorm, double r,
+                                         bool exclude, const uint64_t *in_off, uint32_t *flag, uint32_t *cnt, uint32_t *bad,
+                                         hipStream_t s);
+// out[1 + j] <- out[0] + part[j + 1], j < nq (a chunk's scan behind the rows before it)
+hipError_t launch_radius_self_place(const uint64_t *part, size_t nq, uint64_t *out, hipStream_t s);
+// out[out_off[i] + t] <- row i's list (in_off, ascending index, entries below in_cap) without self0 + i where flag[i],
+// positions below cap only; out_dist / in_dist nullable together; *bad += flagged, wholly written lists without it
+hipError_t launch_radius_self_compact_f32(const uint64_t *in_off, const uint64_t *in_idx, const float *in_dist,
+                                          uint64_t in_cap, const uint32_t *flag, const uint64_t *out_off, size_t n,
+                                          uint64_t self0, uint64_t *out_idx, float *out_dist, uint64_t cap, uint32_t *bad,
+                                          hipStream_t s);
+hipError_t launch_radius_self_compact_f64(const uint64_t *in_off, const uint64_t *in_idx, const double *in_dist,
+                                          uint64_t in_cap, const uint32_t *flag, const uint64_t *out_off, size_t n,
+                                          uint64_t self0, uint64_t *out_idx, double *out_dist, uint64_t cap, uint32_t *bad,
+                                          hipStream_t s);
+
 // ---- csr_sort.hip: order every list of a radius answer by (distance, index) in place (PN_RADIUS_SORTED)
 constexpr int kSortTile = 2048;  // longest list sorted by one workgroup in LDS; longer lists: chunks + merge passes
 struct CsrSortScratch {
