@@ -76,6 +76,26 @@ extern "C" {
                                                             flags: c_uint, d_offsets: *mut u64, d_idx: *mut u64,
                                                             d_dist: *mut f64, capacity: usize, d_total: *mut u64,
                                                             stream: *mut c_void) -> c_int;
+    /// self-queries over row shards: the local rows against the whole corpus (global rows), as pn_query_self_* /
+    /// pn_query_radius_self_*; collective in rank mode
+    pub fn pn_sharded_query_self_f32(sharded: *const pn_sharded, k: usize, flags: c_uint, idx_out: *mut u64,
+                                     dist_out: *mut f32) -> c_int;
+    pub fn pn_sharded_query_self_f64(sharded: *const pn_sharded, k: usize, flags: c_uint, idx_out: *mut u64,
+                                     dist_out: *mut f64) -> c_int;
+    pub fn pn_sharded_query_self_device_f32(sharded: *const pn_sharded, k: usize, flags: c_uint, d_idx: *mut u64,
+                                            d_dist: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn pn_sharded_query_self_device_f64(sharded: *const pn_sharded, k: usize, flags: c_uint, d_idx: *mut u64,
+                                            d_dist: *mut f64, stream: *mut c_void) -> c_int;
+    pub fn pn_sharded_query_radius_self_f32(sharded: *const pn_sharded, radius: f32, flags: c_uint, offsets: *mut u64,
+                                            idx_out: *mut *mut u64, dist_out: *mut *mut f32) -> c_int;
+    pub fn pn_sharded_query_radius_self_f64(sharded: *const pn_sharded, radius: f64, flags: c_uint, offsets: *mut u64,
+                                            idx_out: *mut *mut u64, dist_out: *mut *mut f64) -> c_int;
+    pub fn pn_sharded_query_radius_self_device_f32(sharded: *const pn_sharded, radius: f32, flags: c_uint,
+                                                   d_offsets: *mut u64, d_idx: *mut u64, d_dist: *mut f32,
+                                                   capacity: usize, d_total: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn pn_sharded_query_radius_self_device_f64(sharded: *const pn_sharded, radius: f64, flags: c_uint,
+                                                   d_offsets: *mut u64, d_idx: *mut u64, d_dist: *mut f64,
+                                                   capacity: usize, d_total: *mut u64, stream: *mut c_void) -> c_int;
 
     /// self-queries: every indexed row against its own index, the row itself left out (PN_SELF_INCLUDE keeps it)
     pub fn pn_query_self_f32(index: *const pn_index, k: usize, flags: c_uint, idx_out: *mut u64, dist_out: *mut f32) -> c_int;

@@ -352,6 +352,32 @@ impl ShardedBallTree {
         }
         (idx, dist)
     }
+    /// `BallTree::query_self` of the whole corpus over the shards: (n, min(k, n - 1)) global rows and distances
+    pub fn query_self(&self, k: usize, include_self: bool) -> (Array2<u64>, Array2<f32>) {
+        let kout = k.min(if include_self { self.n } else { self.n - 1 });
+        let (mut idx, mut dist) = (Array2::<u64>::zeros((self.n, kout)), Array2::<f32>::zeros((self.n, kout)));
+        let flags = if include_self { ffi::PN_SELF_INCLUDE } else { 0 };
+        if kout > 0 {
+            ok(unsafe { ffi::pn_sharded_query_self_f32(self.handle, k, flags, idx.as_mut_ptr(), dist.as_mut_ptr()) });
+        }
+        (idx, dist)
+    }
+    /// `BallTree::query_radius_self` of the whole corpus over the shards: CSR (offsets [n + 1], global rows, distances)
+    pub fn query_radius_self(&self, r: f32, sorted: bool, include_self: bool) -> (Vec<u64>, Vec<usize>, Vec<f32>) {
+        let mut off = vec![0u64; self.n + 1];
+        let mut out: *mut u64 = std::ptr::null_mut();
+        let mut dout: *mut f32 = std::ptr::null_mut();
+        let flags = (if sorted { ffi::PN_RADIUS_SORTED } else { 0 }) | (if include_self { ffi::PN_SELF_INCLUDE } else { 0 });
+        ok(unsafe { ffi::pn_sharded_query_radius_self_f32(self.handle, r, flags, off.as_mut_ptr(), &mut out, &mut dout) });
+        let total = off[self.n] as usize;
+        let idx = unsafe { std::slice::from_raw_parts(out, total) }.iter().map(|&i| i as usize).collect();
+        let dist = unsafe { std::slice::from_raw_parts(dout, total) }.to_vec();
+        unsafe {
+            ffi::pn_free(out as *mut _);
+            ffi::pn_free(dout as *mut _);
+        }
+        (off, idx, dist)
+    }
 }
 impl Drop for ShardedBallTree {
     fn drop(&mut self) { unsafe { ffi::pn_sharded_destroy(self.handle) } }

@@ -58,7 +58,8 @@ extern "C" {
  * PN_OPT_MFMA_STRUCTURE = 1 is now PN_ERR_INVALID.  Everything of version 2 is unchanged.
  * Additive within version 3 (callers detect them by symbol): pn_query_radius_with_distance_{,device_}{f32,f64},
  * pn_sharded_query_radius_with_distance_{,device_}{f32,f64}, PN_RADIUS_SORTED; pn_query_self_{,device_}{f32,f64},
- * pn_query_radius_self_{,device_}{f32,f64}, PN_SELF_INCLUDE. */
+ * pn_query_radius_self_{,device_}{f32,f64}, PN_SELF_INCLUDE; pn_sharded_query_self_{,device_}{f32,f64},
+ * pn_sharded_query_radius_self_{,device_}{f32,f64}. */
 #define PN_ABI_VERSION 3
 
 /* ---- error codes.  EMPTY / NOT_CONTIGUOUS are ArrayError (src/lib.rs:9-16). */
@@ -279,7 +280,8 @@ int pn_query_radius_with_distance_device_f64(const pn_index *index, const double
  * them as it serves ordinary queries of the rows' length.  Rows are answered 2^18 at a time (k-NN and radius alike), so
  * the handle's workspace is sized as for a batch of at most 2^18 queries: a chunk's rows are packed into it like any
  * query batch's (the narrow bf16 tier's k-NN reads them in place), never the whole corpus.  Row i is identified as
- * i + PN_OPT_INDEX_BASE.  Not for row-sharded handles.  pn_stats.queries counts n queries, as a batch of n would.
+ * i + PN_OPT_INDEX_BASE.  Row-sharded handles: pn_sharded_query_self_* below.  pn_stats.queries counts n queries, as a
+ * batch of n would.
  *
  * k-NN: row i's answer is the first kout entries of the list of the rows j != i, ordered as pn_query_*'s answers
  * ((distance, index), NaN last), distances bit-identical to metric.distance(p_i, p_j); kout = min(k, n - 1).  Exactly:
@@ -492,6 +494,40 @@ int pn_sharded_query_radius_with_distance_device_f64(const pn_sharded *sharded, 
                                                      size_t q_cols, size_t q_row_stride, double radius, unsigned flags,
                                                      uint64_t *d_offsets, uint64_t *d_idx, double *d_dist,
                                                      size_t capacity, uint64_t *d_total, void *stream);
+/* self-queries over row shards: every LOCAL row (rows [local_first_row, local_first_row + local_rows) of
+ * pn_sharded_info -- all n rows for a pn_sharded_create_* handle, the rank's own rows in rank mode, none for a rank beyond
+ * the corpus) against the whole corpus, with global row numbers.  The answer of local row i is bit-identical to that of
+ * global row local_first_row + i from pn_query_self_* / pn_query_radius_self_* over the whole corpus (same indices,
+ * distance bits and order) for every shard count and placement; flags, kout and errors are theirs.  In rank mode every
+ * entry is collective: all ranks call it with the same k / r / flags.
+ * Each step, every GPU contributes up to 2^18 / world of its rows, one all-gather makes them the query batch of every
+ * GPU, and each GPU keeps only the answers of its own rows: the workspace stays that of a 2^18-query batch.  A rank whose
+ * local work fails still enters the step's exchange; the host entry points then fail on every rank (the device entry
+ * returns the error on the failing rank only -- it reads nothing back).
+ *   pn_sharded_query_self_*               host [local_rows][kout]
+ *   pn_sharded_query_self_device_*        [local_rows][kout] in HBM of the ONE GPU the handle drives (rank mode, or all
+ *                                         shards on one device; else PN_ERR_UNSUPPORTED), enqueued on `stream` with the
+ *                                         contract of pn_sharded_query_device_*
+ *   pn_sharded_query_radius_self_*        CSR over the local rows: offsets [local_rows + 1], *idx_out / *dist_out
+ *                                         allocated by the library (pn_free)
+ *   pn_sharded_query_radius_self_device_* pn_query_radius_self_device_* on a handle with ONE shard; several shards:
+ *                                         PN_ERR_UNSUPPORTED (their ragged exchange goes through the host entry). */
+int pn_sharded_query_self_f32(const pn_sharded *sharded, size_t k, unsigned flags, uint64_t *idx_out, float *dist_out);
+int pn_sharded_query_self_f64(const pn_sharded *sharded, size_t k, unsigned flags, uint64_t *idx_out, double *dist_out);
+int pn_sharded_query_self_device_f32(const pn_sharded *sharded, size_t k, unsigned flags, uint64_t *d_idx, float *d_dist,
+                                     void *stream);
+int pn_sharded_query_self_device_f64(const pn_sharded *sharded, size_t k, unsigned flags, uint64_t *d_idx, double *d_dist,
+                                     void *stream);
+int pn_sharded_query_radius_self_f32(const pn_sharded *sharded, float radius, unsigned flags, uint64_t *offsets,
+                                     uint64_t **idx_out, float **dist_out);
+int pn_sharded_query_radius_self_f64(const pn_sharded *sharded, double radius, unsigned flags, uint64_t *offsets,
+                                     uint64_t **idx_out, double **dist_out);
+int pn_sharded_query_radius_self_device_f32(const pn_sharded *sharded, float radius, unsigned flags, uint64_t *d_offsets,
+                                            uint64_t *d_idx, float *d_dist, size_t capacity, uint64_t *d_total,
+                                            void *stream);
+int pn_sharded_query_radius_self_device_f64(const pn_sharded *sharded, double radius, unsigned flags, uint64_t *d_offsets,
+                                            uint64_t *d_idx, double *d_dist, size_t capacity, uint64_t *d_total,
+                                            void *stream);
 
 /* ---- diagnostic: the first-tier filter's lower bounds themselves.  bounds_out[q * n_rows + i] = L'(q, p_i)
  * for the first n_rows corpus rows (clamped to n_points), with L' + qnorm_out[q] <= |q - p_i|^2 in real

@@ -365,6 +365,40 @@ class ShardedBallTreeT {
         pn_free(dout);
         return r;
     }
+    // self-queries over the shards (pn_sharded_query_self_*): BallTreeT::query_self of the whole corpus, global rows
+    std::pair<std::vector<size_t>, std::vector<A>> query_self(size_t k, bool include_self) const {
+        const size_t cap = include_self ? n_ : n_ - 1;
+        const size_t kout = k < cap ? k : cap;
+        std::vector<uint64_t> idx(n_ * kout);
+        std::vector<A> dist(n_ * kout);
+        const unsigned flags = include_self ? PN_SELF_INCLUDE : 0u;
+        if (kout) {
+            if constexpr (std::is_same<A, float>::value)
+                check(pn_sharded_query_self_f32(h_, k, flags, idx.data(), dist.data()));
+            else
+                check(pn_sharded_query_self_f64(h_, k, flags, idx.data(), dist.data()));
+        }
+        return {std::vector<size_t>(idx.begin(), idx.end()), std::move(dist)};
+    }
+    // pn_sharded_query_radius_self_*: BallTreeT::query_radius_self of the whole corpus, global rows
+    SelfRadius<A> query_radius_self(A r, bool with_distance, bool sorted, bool include_self) const {
+        SelfRadius<A> res;
+        std::vector<uint64_t> off(n_ + 1, 0);
+        uint64_t *out = nullptr;
+        A *dout = nullptr;
+        const unsigned flags = (sorted ? PN_RADIUS_SORTED : 0u) | (include_self ? PN_SELF_INCLUDE : 0u);
+        if constexpr (std::is_same<A, float>::value)
+            check(pn_sharded_query_radius_self_f32(h_, r, flags, off.data(), &out, with_distance ? &dout : nullptr));
+        else
+            check(pn_sharded_query_radius_self_f64(h_, r, flags, off.data(), &out, with_distance ? &dout : nullptr));
+        const uint64_t total = off[n_];
+        res.offsets.assign(off.begin(), off.end());
+        res.idx.assign(out, out + total);
+        if (dout) res.dist.assign(dout, dout + total);
+        pn_free(out);
+        pn_free(dout);
+        return res;
+    }
 };
 using ShardedBallTree = ShardedBallTreeT<float>;
 

@@ -150,6 +150,14 @@ SIGNATURES = {
                                                               _vp, _sz, _vp, _vp]),
     "pn_sharded_query_radius_with_distance_device_f64": (_i, [_vp, _vp, _sz, _sz, _sz, C.c_double, C.c_uint, _vp, _vp,
                                                               _vp, _sz, _vp, _vp]),
+    "pn_sharded_query_self_f32": (_i, [_vp, _sz, C.c_uint, _vp, _vp]),
+    "pn_sharded_query_self_f64": (_i, [_vp, _sz, C.c_uint, _vp, _vp]),
+    "pn_sharded_query_self_device_f32": (_i, [_vp, _sz, C.c_uint, _vp, _vp, _vp]),
+    "pn_sharded_query_self_device_f64": (_i, [_vp, _sz, C.c_uint, _vp, _vp, _vp]),
+    "pn_sharded_query_radius_self_f32": (_i, [_vp, C.c_float, C.c_uint, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "pn_sharded_query_radius_self_f64": (_i, [_vp, C.c_double, C.c_uint, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "pn_sharded_query_radius_self_device_f32": (_i, [_vp, C.c_float, C.c_uint, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "pn_sharded_query_radius_self_device_f64": (_i, [_vp, C.c_double, C.c_uint, _vp, _vp, _vp, _sz, _vp, _vp]),
 }
 
 _lib = None

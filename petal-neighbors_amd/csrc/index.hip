@@ -2244,6 +2244,10 @@ int query_device_strided_f64(const pn_index *ix, const double *d_q, size_t nq, s
                              uint64_t *d_idx, double *d_dist, size_t out_stride, hipStream_t s) {
     return query_device_strided_impl<double>(ix, d_q, nq, q_cols, q_stride, k, d_idx, d_dist, out_stride, s);
 }
+const void *index_rows(const pn_index *ix, size_t *ld) {
+    *ld = ix->ld;
+    return ix->d_pts;
+}
 }  // namespace pn
 
 extern "C" int pn_query_device_f32(const pn_index *ix, const float *d_q, size_t nq, size_t q_cols, size_t q_stride,

@@ -424,6 +424,8 @@ int query_device_strided_f32(const pn_index *ix, const float *d_q, size_t nq, si
                              uint64_t *d_idx, float *d_dist, size_t out_stride, hipStream_t s);
 int query_device_strided_f64(const pn_index *ix, const double *d_q, size_t nq, size_t q_cols, size_t q_stride, size_t k,
                              uint64_t *d_idx, double *d_dist, size_t out_stride, hipStream_t s);
+// the index's rows in HBM as the queries of its self-queries read them: [n][*ld] of its element type (sharded.hip)
+const void *index_rows(const pn_index *ix, size_t *ld);
 int merge_topk_device_keys_f32(const uint64_t *pi, const float *pd, size_t np, size_t is, size_t ds, size_t nq, size_t kp,
                                size_t ko, uint64_t *oi, float *od, int device, void *stream, bool signed_keys);
 int merge_topk_device_keys_f64(const uint64_t *pi, const double *pd, size_t np, size_t is, size_t ds, size_t nq, size_t kp,

@@ -172,6 +172,7 @@ struct Dev {  // one GPU this process drives = one rank of the communicator
     hipEvent_t ev_local[2] = {nullptr, nullptr}, ev_merged[2] = {nullptr, nullptr}, ev_done = nullptr;
     std::vector<int> parts;
     Buf q, out_idx, out_dist, lparts, pack[2], gathered[2], rad_a, rad_b, rad_c;  // rad_c: radius distances
+    Buf sf_rows, sf_idx, sf_dist;  // self-queries: a step's gathered rows, its slice's merged (k + 1)-answers
     // End of the last call that used this GPU's exchange buffers (pack / gathered / lparts) and the stream it was
     // enqueued on: the device entry point returns while its kernels run, so a later call on ANOTHER stream is ordered
     // behind this event before it touches the buffers (`mu` only serialises the enqueueing).  Same scheme as
@@ -189,7 +190,8 @@ struct Dev {  // one GPU this process drives = one rank of the communicator
     double shard_ms = 0.0, exchange_ms = 0.0;
     // (Bufs point at this Dev's retired list: adopt() after the vector of Devs has its final size)
     void adopt() {
-        Buf *bs[] = {&q, &out_idx, &out_dist, &lparts, &pack[0], &pack[1], &gathered[0], &gathered[1], &rad_a, &rad_b, &rad_c};
+        Buf *bs[] = {&q, &out_idx, &out_dist, &lparts, &pack[0], &pack[1], &gathered[0], &gathered[1], &rad_a, &rad_b, &rad_c,
+                     &sf_rows, &sf_idx, &sf_dist};
         for (Buf *b : bs) b->retired = &retired;
     }
     void free_retired() {
@@ -268,6 +270,23 @@ template <> struct ShT<float> {
                                 uint64_t *off, uint64_t *idx, float *dist, size_t cap, uint64_t *tot, void *st) {
         return pn_query_radius_with_distance_device_f32(ix, q, nq, qc, qs, r, fl, off, idx, dist, cap, tot, st);
     }
+    static int self(const pn_index *ix, size_t k, unsigned fl, uint64_t *oi, float *od) {
+        return pn_query_self_f32(ix, k, fl, oi, od);
+    }
+    static int self_device(const pn_index *ix, size_t k, unsigned fl, uint64_t *oi, float *od, hipStream_t s) {
+        return pn_query_self_device_f32(ix, k, fl, oi, od, s);
+    }
+    static int radius_self(const pn_index *ix, float r, unsigned fl, uint64_t *off, uint64_t **out, float **dout) {
+        return pn_query_radius_self_f32(ix, r, fl, off, out, dout);
+    }
+    static int radius_self_device(const pn_index *ix, float r, unsigned fl, uint64_t *off, uint64_t *idx, float *dist, size_t cap,
+                                  uint64_t *tot, void *st) {
+        return pn_query_radius_self_device_f32(ix, r, fl, off, idx, dist, cap, tot, st);
+    }
+    static hipError_t exclude(const uint64_t *ii, const float *id, size_t nq, int kin, int kout, uint64_t self0, uint64_t *oi,
+                              float *od, hipStream_t s) {
+        return launch_knn_self_exclude_f32(ii, id, nq, kin, kout, self0, oi, od, s);
+    }
 };
 template <> struct ShT<double> {
     static int create(const double *p, size_t n, size_t c, ptrdiff_t rs, ptrdiff_t cs, int dev, pn_index **o, int metric) {
@@ -300,6 +319,23 @@ template <> struct ShT<double> {
                                 uint64_t *off, uint64_t *idx, double *dist, size_t cap, uint64_t *tot, void *st) {
         return pn_query_radius_with_distance_device_f64(ix, q, nq, qc, qs, r, fl, off, idx, dist, cap, tot, st);
     }
+    static int self(const pn_index *ix, size_t k, unsigned fl, uint64_t *oi, double *od) {
+        return pn_query_self_f64(ix, k, fl, oi, od);
+    }
+    static int self_device(const pn_index *ix, size_t k, unsigned fl, uint64_t *oi, double *od, hipStream_t s) {
+        return pn_query_self_device_f64(ix, k, fl, oi, od, s);
+    }
+    static int radius_self(const pn_index *ix, double r, unsigned fl, uint64_t *off, uint64_t **out, double **dout) {
+        return pn_query_radius_self_f64(ix, r, fl, off, out, dout);
+    }
+    static int radius_self_device(const pn_index *ix, double r, unsigned fl, uint64_t *off, uint64_t *idx, double *dist, size_t cap,
+                                  uint64_t *tot, void *st) {
+        return pn_query_radius_self_device_f64(ix, r, fl, off, idx, dist, cap, tot, st);
+    }
+    static hipError_t exclude(const uint64_t *ii, const double *id, size_t nq, int kin, int kout, uint64_t self0, uint64_t *oi,
+                              double *od, hipStream_t s) {
+        return launch_knn_self_exclude_f64(ii, id, nq, kin, kout, self0, oi, od, s);
+    }
 };
 static int check_elem(const pn_sharded *sh, size_t bytes) {
     if (sh->elem_bytes != (int)bytes) return set_error(PN_ERR_INVALID, "handle element type mismatch (f%d handle)", sh->elem_bytes * 8);
@@ -324,7 +360,7 @@ static void destroy_dev(Dev &d) {
     if (d.comm_stream) (void)hipStreamSynchronize(d.comm_stream);
     if (d.comm && rccl().ok()) (void)rccl().CommDestroy(d.comm);
     Buf *bufs[] = {&d.q, &d.out_idx, &d.out_dist, &d.lparts, &d.pack[0], &d.pack[1], &d.gathered[0], &d.gathered[1],
-                   &d.rad_a, &d.rad_b, &d.rad_c};
+                   &d.rad_a, &d.rad_b, &d.rad_c, &d.sf_rows, &d.sf_idx, &d.sf_dist};
     for (Buf *b : bufs) b->release();
     d.free_retired();
     for (auto &tr : d.ev_prof)
@@ -1096,4 +1132,620 @@ extern "C" int pn_sharded_query_radius_f32(const pn_sharded *sh, const float *qu
 extern "C" int pn_sharded_query_radius_f64(const pn_sharded *sh, const double *queries, size_t nq, size_t q_cols,
                                            ptrdiff_t q_row_stride, double radius, uint64_t *offsets, uint64_t **idx_out) {
     return sharded_query_radius<double>(sh, queries, nq, q_cols, q_row_stride, radius, offsets, idx_out);
+}
+
+// ---------------------------------------------------------------------------
+// self-queries over row shards (pn_sharded_query_self_*, pn_sharded_query_radius_self_*): every local row asked against
+// the whole corpus, the row itself left out -- bit for bit the answer of pn_query_self_* / pn_query_radius_self_* over
+// the unsharded corpus.
+//
+// Steps: every GPU of the communicator contributes up to c = 2^18 / world of its own rows (its parts' d_pts in row order,
+// zero rows once it has none left) and ONE all-gather makes the step's world x c rows the query batch on every GPU, so a
+// step is never larger than the single index's self chunk.  The step count comes from n_total, world and the shard rule
+// alone: every rank runs the same sequence of collectives.
+//   k-NN:   enqueue_local with k + 1 over the batch, the packed all-gather (+ one status word per GPU), then each GPU
+//           merges only ITS slice of the batch (part pointers offset by rank x c queries) and drops the row's own global
+//           index (knn_self_exclude_kernel).  The merged top-(k + 1) by (distance, global row) is the single index's.
+//   radius: each local shard's device pipeline over the batch; offsets | status all-gathered; the lists (and distances)
+//           padded to the longest, all-gathered; each rank splices its slice on the host, drops the row's own index (it
+//           appears at most once, in its owner's part) and merges the parts by (distance, global row) when sorted.  One
+//           process: the parts' lists are read from every GPU directly, no list exchange.
+// A rank whose local work fails still enters every collective of the call; the status words make the host entry points
+// fail on every rank after the step's exchange.  The exchange buffers of the call are allocated before its first
+// collective.  One GPU without a forced exchange (virtual shards): no gather, each part's rows are the queries in place.
+// ---------------------------------------------------------------------------
+namespace {
+constexpr uint64_t kSelfStep = (uint64_t)1 << 18;  // query rows per step over all GPUs = the single index's self chunk
+struct SelfSeg {  // rows [a, a + m) of part `part` (part-local) at position j of its GPU's slice of the step
+    int part;
+    uint64_t a, m, j;
+};
+struct SelfGeom {
+    uint64_t most = 0;   // the most rows any GPU holds
+    uint64_t c = 1;      // rows per GPU and step
+    uint64_t steps = 0;
+    uint64_t first = 0;  // first local row (local row i = global row first + i)
+    size_t qs = 1;       // row stride of the gathered batch
+    bool gather = true;  // rows travel by all-gather (else: one GPU, queried in place)
+};
+}  // namespace
+
+static uint64_t dev_rows(const pn_sharded *sh, const Dev &d) {
+    uint64_t s = 0;
+    for (int p : d.parts) s += sh->parts[p].hi - sh->parts[p].lo;
+    return s;
+}
+static SelfGeom self_geom(const pn_sharded *sh) {
+    SelfGeom g;
+    if (sh->rank_mode)  // rank 0 holds the most: the same number on every rank
+        g.most = std::min<uint64_t>(sh->per, sh->n_total);
+    else
+        for (const Dev &d : sh->devs) g.most = std::max(g.most, dev_rows(sh, d));
+    g.c = std::max<uint64_t>(1, kSelfStep / (uint64_t)sh->world);
+    if (g.most && g.c > g.most) g.c = g.most;
+    g.steps = (g.most + g.c - 1) / g.c;
+    g.first = sh->parts.empty() ? 0 : sh->parts.front().lo;
+    g.qs = sh->dim ? sh->dim : 1;
+    g.gather = sh->world > 1 || sh->exchange_always;
+    return g;
+}
+// d's rows at positions [p0, p0 + cnt) of its parts' rows in part order, cut at part boundaries
+static void self_segs(const pn_sharded *sh, const Dev &d, uint64_t p0, uint64_t cnt, std::vector<SelfSeg> &out) {
+    out.clear();
+    uint64_t cum = 0;
+    for (int pi : d.parts) {
+        const uint64_t sz = sh->parts[pi].hi - sh->parts[pi].lo;
+        const uint64_t b = std::max(cum, p0), e = std::min(cum + sz, p0 + cnt);
+        if (b < e) out.push_back({pi, b - cum, e - b, b - p0});
+        cum += sz;
+    }
+}
+template <typename T>
+static const T *part_rows(const pn_sharded *sh, int part, size_t *ld) {
+    return (const T *)index_rows(sh->parts[part].ix, ld);
+}
+// the step's rows of d into d.q ([cs][qs], zero rows after its own): the send buffer of the rows all-gather
+template <typename T>
+static int self_pack_rows(const pn_sharded *sh, Dev &d, const std::vector<SelfSeg> &segs, uint64_t cs, size_t qs,
+                          hipStream_t s) {
+    T *q = (T *)d.q.p;
+    uint64_t mine = 0;
+    for (const SelfSeg &g : segs) {
+        size_t ld;
+        const T *rows = part_rows<T>(sh, g.part, &ld);
+        if (sh->dim)
+            SHIP(hipMemcpy2DAsync(q + g.j * qs, qs * sizeof(T), rows + g.a * ld, ld * sizeof(T), sh->dim * sizeof(T),
+                                  (size_t)g.m, hipMemcpyDeviceToDevice, s));
+        mine = g.j + g.m;
+    }
+    if (mine < cs) SHIP(hipMemsetAsync(q + mine * qs, 0, (size_t)(cs - mine) * qs * sizeof(T), s));
+    return PN_OK;
+}
+template <typename T> static ncclDataType_t nccl_type() { return sizeof(T) == 4 ? ncclFloat32 : ncclFloat64; }
+// ONE all-gather of every local GPU's d.q into its d.sf_rows (grouped when this process drives several GPUs)
+template <typename T>
+static int self_gather_rows(const pn_sharded *sh, uint64_t cs, size_t qs, const std::vector<hipStream_t> &st) {
+    SNCCL(rccl().GroupStart());
+    for (size_t i = 0; i < sh->devs.size(); ++i) {
+        Dev &d = sh->devs[i];
+        ncclResult_t r = rccl().AllGather(d.q.p, d.sf_rows.p, (size_t)cs * qs, nccl_type<T>(), d.comm, st[i]);
+        if (r != ncclSuccess) {
+            (void)rccl().GroupEnd();
+            return set_error(PN_ERR_COMM, "ncclAllGather: %s", rccl().GetErrorString(r));
+        }
+    }
+    SNCCL(rccl().GroupEnd());
+    return PN_OK;
+}
+static void keep_first(int &rc, int r) {
+    if (rc == PN_OK) rc = r;
+}
+static int hip_rc(hipError_t e, const char *what) {
+    if (e == hipSuccess) return PN_OK;
+    return set_error(e == hipErrorOutOfMemory ? PN_ERR_NOMEM : PN_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
+}
+
+// k-NN.  device: idx_out / dist_out in HBM of the one GPU, enqueued on `stream`; else host arrays, each step staged in
+// d.out_idx / d.out_dist and copied down.  Arguments checked, kout >= 1, the handle locked.
+template <typename T>
+static int self_knn_run(const pn_sharded *sh, size_t kin, size_t kout, bool include, uint64_t *idx_out, T *dist_out,
+                        bool device, const std::vector<hipStream_t> &st) {
+    std::vector<Dev> &devs = sh->devs;
+    const SelfGeom G = self_geom(sh);
+    const size_t W = (size_t)sh->world, kp = k_part_of(sh, kin), kd = k_dev_of(sh, kin), qs = G.qs;
+    constexpr size_t kDW = 8 / sizeof(T);
+    if (!G.gather && kd != kin) return set_error(PN_ERR_DEVICE, "self-query: %zu slots per GPU for k + 1 = %zu", kd, kin);
+    // every buffer of the call before its first collective
+    const size_t words_max = packed_words<T>(G.gather ? W * G.c : G.c, kd) + 1;  // + the status word
+    for (size_t i = 0; i < devs.size(); ++i) {
+        Dev &d = devs[i];
+        SetGuard g(d.device);
+        if (!g.ok) return set_error(PN_ERR_DEVICE, "hipSetDevice(%d) failed", d.device);
+        SPN(d.pack[0].ensure(words_max * 8));
+        if (G.gather) {
+            SPN(d.q.ensure((size_t)G.c * qs * sizeof(T)));
+            SPN(d.sf_rows.ensure(W * (size_t)G.c * qs * sizeof(T)));
+            SPN(d.gathered[0].ensure(W * words_max * 8));
+            SPN(d.sf_idx.ensure((size_t)G.c * kin * 8));
+            SPN(d.sf_dist.ensure((size_t)G.c * kin * sizeof(T)));
+        }
+        if (!device) {
+            SPN(d.out_idx.ensure((size_t)G.c * kout * 8));
+            SPN(d.out_dist.ensure((size_t)G.c * kout * sizeof(T)));
+        }
+    }
+    // a segment's (k + 1)-answers (stride kin) -> its rows of the output, the row itself dropped
+    auto emit = [&](size_t i, const SelfSeg &sg, const uint64_t *si, const T *sd) -> int {
+        Dev &d = devs[i];
+        const uint64_t g0 = sh->parts[sg.part].lo + sg.a, row = g0 - G.first;
+        uint64_t *oi = device ? idx_out + row * kout : (uint64_t *)d.out_idx.p + sg.j * kout;
+        T *od = device ? dist_out + row * kout : (T *)d.out_dist.p + sg.j * kout;
+        const size_t cells = (size_t)sg.m * kout;
+        if (include) {
+            SHIP(hipMemcpyAsync(oi, si, cells * 8, hipMemcpyDeviceToDevice, st[i]));
+            SHIP(hipMemcpyAsync(od, sd, cells * sizeof(T), hipMemcpyDeviceToDevice, st[i]));
+        } else {
+            SHIP(ShT<T>::exclude(si, sd, (size_t)sg.m, (int)kin, (int)kout, g0, oi, od, st[i]));
+        }
+        if (!device) {
+            SHIP(hipMemcpyAsync(idx_out + row * kout, oi, cells * 8, hipMemcpyDeviceToHost, st[i]));
+            SHIP(hipMemcpyAsync(dist_out + row * kout, od, cells * sizeof(T), hipMemcpyDeviceToHost, st[i]));
+        }
+        return PN_OK;
+    };
+    auto sync_all = [&]() -> int {
+        for (size_t i = 0; i < devs.size(); ++i) {
+            SetGuard g(devs[i].device);
+            SHIP(hipStreamSynchronize(st[i]));
+        }
+        return PN_OK;
+    };
+    std::vector<std::vector<SelfSeg>> segs(devs.size());
+    std::vector<uint64_t> status(W);
+    int rc = PN_OK;  // this process's first local failure: the remaining collectives of the step are still entered
+    for (uint64_t step = 0; step < G.steps; ++step) {
+        const uint64_t p0 = step * G.c, cs = std::min<uint64_t>(G.c, G.most - p0);
+        for (size_t i = 0; i < devs.size(); ++i) self_segs(sh, devs[i], p0, cs, segs[i]);
+        if (!G.gather) {  // one GPU: each segment's rows are the queries, in place; no collective
+            Dev &d = devs[0];
+            SetGuard g(d.device);
+            for (const SelfSeg &sg : segs[0]) {
+                size_t ld;
+                const T *rows = part_rows<T>(sh, sg.part, &ld);
+                SPN(enqueue_local<T>(sh, d, rows + sg.a * ld, (size_t)sg.m, sh->dim, ld, kin, kp, kd, 0, st[0]));
+                const uint64_t *pi = (const uint64_t *)d.pack[0].p;
+                SPN(emit(0, sg, pi, reinterpret_cast<const T *>(pi + sg.m * kd)));
+            }
+            if (!device) SPN(sync_all());
+            continue;
+        }
+        const size_t nqb = W * (size_t)cs, words = packed_words<T>(nqb, kd);
+        for (size_t i = 0; i < devs.size(); ++i) {
+            SetGuard g(devs[i].device);
+            if (rc == PN_OK) keep_first(rc, self_pack_rows<T>(sh, devs[i], segs[i], cs, qs, st[i]));
+        }
+        SPN(self_gather_rows<T>(sh, cs, qs, st));
+        for (size_t i = 0; i < devs.size(); ++i) {
+            Dev &d = devs[i];
+            SetGuard g(d.device);
+            if (rc == PN_OK)
+                keep_first(rc, enqueue_local<T>(sh, d, (const T *)d.sf_rows.p, nqb, sh->dim, qs, kin, kp, kd, 0, st[i]));
+            keep_first(rc, hip_rc(hipMemsetAsync((uint64_t *)d.pack[0].p + words, rc == PN_OK ? 0 : 0xFF, 8, st[i]),
+                                  "status word"));
+        }
+        SNCCL(rccl().GroupStart());
+        for (size_t i = 0; i < devs.size(); ++i) {
+            Dev &d = devs[i];
+            ncclResult_t r = rccl().AllGather(d.pack[0].p, d.gathered[0].p, words + 1, ncclUint64, d.comm, st[i]);
+            if (r != ncclSuccess) {
+                (void)rccl().GroupEnd();
+                return set_error(PN_ERR_COMM, "ncclAllGather: %s", rccl().GetErrorString(r));
+            }
+        }
+        SNCCL(rccl().GroupEnd());
+        // this GPU's slice of the batch: queries [rank cs, rank cs + its rows) of every part
+        for (size_t i = 0; i < devs.size() && rc == PN_OK; ++i) {
+            Dev &d = devs[i];
+            SetGuard g(d.device);
+            const uint64_t *gb = (const uint64_t *)d.gathered[0].p;
+            const T *gd = reinterpret_cast<const T *>(gb + nqb * kd);
+            const size_t j0 = (size_t)d.comm_rank * (size_t)cs;
+            for (const SelfSeg &sg : segs[i]) {
+                uint64_t *ti = (uint64_t *)d.sf_idx.p + sg.j * kin;
+                T *td = (T *)d.sf_dist.p + sg.j * kin;
+                keep_first(rc, ShT<T>::merge(gb + (j0 + sg.j) * kd, gd + (j0 + sg.j) * kd, W, words + 1, kDW * (words + 1),
+                                             (size_t)sg.m, kd, kin, ti, td, d.device, st[i], sh->metric == 1));
+                if (rc == PN_OK) keep_first(rc, emit(i, sg, ti, td));
+            }
+        }
+        if (device) continue;  // (enqueue and return: the failing rank reports after the call's last collective)
+        {
+            Dev &d = devs[0];
+            SetGuard g(d.device);
+            keep_first(rc, hip_rc(hipMemcpy2DAsync(status.data(), 8, (const uint64_t *)d.gathered[0].p + words,
+                                                   (words + 1) * 8, 8, W, hipMemcpyDeviceToHost, st[0]),
+                                  "status words"));
+        }
+        SPN(sync_all());
+        if (rc != PN_OK) return rc;
+        for (size_t r = 0; r < W; ++r)  // every rank sees the same words: all fail after the same step
+            if (status[r]) return set_error(PN_ERR_DEVICE, "self-query: rank %zu failed in its local work", r);
+    }
+    return rc;
+}
+
+template <typename T>
+static int sharded_query_self(const pn_sharded *sh, size_t k, unsigned flags, uint64_t *idx_out, T *dist_out, bool device,
+                              void *stream) {
+    if (flags & ~(unsigned)PN_SELF_INCLUDE) return set_error(PN_ERR_INVALID, "unknown self-query flags 0x%x", flags);
+    if (!sh) return set_error(PN_ERR_INVALID, "handle is NULL");
+    SPN(check_elem(sh, sizeof(T)));
+    if (!idx_out || !dist_out) return set_error(PN_ERR_INVALID, "output buffer is NULL");
+    if (device && sh->devs.size() != 1)
+        return set_error(PN_ERR_UNSUPPORTED, "device-resident self-queries need a handle that drives ONE GPU (one process "
+                                             "per GPU, or all shards on one device); use pn_sharded_query_self_*");
+    const bool include = flags & PN_SELF_INCLUDE;
+    const uint64_t n = sh->n_total;
+    const size_t kout = (size_t)std::min<uint64_t>(k, include ? n : n - 1), kin = include ? kout : kout + 1;
+    if (kout == 0) return PN_OK;  // (every rank alike: k and n_total decide it)
+    if (kin > 0x7FFFFFFFull) return set_error(PN_ERR_UNSUPPORTED, "k too large");
+    if (sh->n_shards == 1 && !sh->exchange_always) {  // one shard: the single index's own self-query
+        const pn_index *ix = sh->parts[0].ix;
+        return device ? ShT<T>::self_device(ix, k, flags, idx_out, dist_out, (hipStream_t)stream)
+                      : ShT<T>::self(ix, k, flags, idx_out, dist_out);
+    }
+    std::lock_guard<std::mutex> lk(sh->mu);
+    std::vector<hipStream_t> st(sh->devs.size());
+    for (size_t i = 0; i < sh->devs.size(); ++i) {
+        Dev &d = sh->devs[i];
+        st[i] = device ? (hipStream_t)stream : d.stream;
+        SetGuard g(d.device);
+        if (!g.ok) return set_error(PN_ERR_DEVICE, "hipSetDevice(%d) failed", d.device);
+        SPN(acquire_dev(d, st[i]));
+    }
+    if (!device) return self_knn_run<T>(sh, kin, kout, include, idx_out, dist_out, false, st);
+    SetGuard g(sh->devs[0].device);
+    DevUse in_use{sh->devs[0], st[0]};  // records the end-of-use event on every return path
+    return self_knn_run<T>(sh, kin, kout, include, idx_out, dist_out, true, st);
+}
+extern "C" int pn_sharded_query_self_f32(const pn_sharded *sh, size_t k, unsigned flags, uint64_t *idx_out, float *dist_out) {
+    return sharded_query_self<float>(sh, k, flags, idx_out, dist_out, false, nullptr);
+}
+extern "C" int pn_sharded_query_self_f64(const pn_sharded *sh, size_t k, unsigned flags, uint64_t *idx_out,
+                                         double *dist_out) {
+    return sharded_query_self<double>(sh, k, flags, idx_out, dist_out, false, nullptr);
+}
+extern "C" int pn_sharded_query_self_device_f32(const pn_sharded *sh, size_t k, unsigned flags, uint64_t *d_idx,
+                                                float *d_dist, void *stream) {
+    return sharded_query_self<float>(sh, k, flags, d_idx, d_dist, true, stream);
+}
+extern "C" int pn_sharded_query_self_device_f64(const pn_sharded *sh, size_t k, unsigned flags, uint64_t *d_idx,
+                                                double *d_dist, void *stream) {
+    return sharded_query_self<double>(sh, k, flags, d_idx, d_dist, true, stream);
+}
+
+// Radius: the spliced lists of the local rows, gathered piece by piece (a piece = a segment's rows of one step) and put
+// in local row order at the end.
+namespace {
+template <typename T>
+struct SelfLists {
+    std::vector<uint64_t> cnt;  // per local row
+    std::vector<uint64_t> idx;
+    std::vector<T> dist;
+    struct Piece {
+        uint64_t row0, m, at;
+    };
+    std::vector<Piece> pieces;
+};
+}  // namespace
+// rows q0 .. q0 + m of a batch (global rows g0 ..), local rows row0 ..: the parts' lists (part r: offsets po[r], rows
+// pi[r], distances pd[r] or nullptr; ascending rows, or by (distance, row) when sorted) spliced, the row's own index
+// dropped unless include
+template <typename T>
+static void self_splice(const std::vector<const uint64_t *> &po, const std::vector<const uint64_t *> &pi,
+                        const std::vector<const T *> &pd, size_t q0, uint64_t m, uint64_t g0, uint64_t row0, bool exclude,
+                        bool sorted, bool wd, SelfLists<T> &out) {
+    const size_t W = po.size();
+    out.pieces.push_back({row0, m, (uint64_t)out.idx.size()});
+    std::vector<uint64_t> cur(W), end(W);
+    for (uint64_t t = 0; t < m; ++t) {
+        const size_t q = q0 + (size_t)t;
+        const uint64_t self = g0 + t, before = out.idx.size();
+        auto put = [&](size_t r, uint64_t e) {
+            if (exclude && pi[r][e] == self) return;
+            out.idx.push_back(pi[r][e]);
+            if (wd) out.dist.push_back(pd[r][e]);
+        };
+        if (!sorted) {
+            for (size_t r = 0; r < W; ++r)
+                for (uint64_t e = po[r][q]; e < po[r][q + 1]; ++e) put(r, e);
+        } else {  // W-way merge by (distance, global row), as radius_splice
+            for (size_t r = 0; r < W; ++r) {
+                cur[r] = po[r][q];
+                end[r] = po[r][q + 1];
+            }
+            for (;;) {
+                size_t best = W;
+                for (size_t r = 0; r < W; ++r) {
+                    if (cur[r] == end[r]) continue;
+                    if (best == W) {
+                        best = r;
+                        continue;
+                    }
+                    const T d = pd[r][cur[r]], db = pd[best][cur[best]];
+                    if (d < db || (d == db && pi[r][cur[r]] < pi[best][cur[best]])) best = r;
+                }
+                if (best == W) break;
+                put(best, cur[best]++);
+            }
+        }
+        out.cnt[row0 + t] = out.idx.size() - before;
+    }
+}
+// one part's CSR over a batch of queries on its GPU, read back to the host (one process: no list exchange needed)
+template <typename T>
+static int self_part_radius(const pn_sharded *sh, int part, const T *batch, size_t nqb, size_t qs, T radius, unsigned inner,
+                            bool wd, std::vector<uint64_t> &off, std::vector<uint64_t> &ids, std::vector<T> &ds) {
+    const Part &p = sh->parts[part];
+    Dev &d = sh->devs[p.dev_slot];
+    off.assign(nqb + 1, 0);
+    ids.clear();
+    ds.clear();
+    if (!p.ix) return PN_OK;
+    SPN(d.rad_a.ensure((nqb + 2) * 8));
+    uint64_t *d_off = (uint64_t *)d.rad_a.p, *d_tot = d_off + nqb + 1;
+    size_t cap = std::max<size_t>(d.rad_b.bytes / 8, nqb * 4 + 1024);  // (one process: a local decision)
+    uint64_t total = 0;
+    for (int attempt = 0;; ++attempt) {
+        SPN(d.rad_b.ensure(cap * 8));
+        if (wd) SPN(d.rad_c.ensure(cap * sizeof(T)));
+        if (wd)
+            SPN(ShT<T>::radius_wd_device(p.ix, batch, nqb, sh->dim, qs, radius, inner, d_off, (uint64_t *)d.rad_b.p,
+                                         (T *)d.rad_c.p, cap, d_tot, d.stream));
+        else
+            SPN(ShT<T>::radius_device(p.ix, batch, nqb, sh->dim, qs, radius, d_off, (uint64_t *)d.rad_b.p, cap, d_tot,
+                                      d.stream));
+        SHIP(hipMemcpyAsync(&total, d_tot, 8, hipMemcpyDeviceToHost, d.stream));
+        SHIP(hipStreamSynchronize(d.stream));
+        if (total <= cap) break;
+        if (attempt) return set_error(PN_ERR_DEVICE, "radius lists changed size between two passes");
+        cap = (size_t)total;
+    }
+    ids.resize((size_t)total);
+    if (wd) ds.resize((size_t)total);
+    SHIP(hipMemcpyAsync(off.data(), d_off, (nqb + 1) * 8, hipMemcpyDeviceToHost, d.stream));
+    if (total) SHIP(hipMemcpyAsync(ids.data(), d.rad_b.p, (size_t)total * 8, hipMemcpyDeviceToHost, d.stream));
+    if (total && wd) SHIP(hipMemcpyAsync(ds.data(), d.rad_c.p, (size_t)total * sizeof(T), hipMemcpyDeviceToHost, d.stream));
+    SHIP(hipStreamSynchronize(d.stream));
+    return PN_OK;
+}
+
+template <typename T>
+static int self_radius_run(const pn_sharded *sh, T radius, unsigned flags, bool wd, SelfLists<T> &out) {
+    std::vector<Dev> &devs = sh->devs;
+    const SelfGeom G = self_geom(sh);
+    const size_t W = (size_t)sh->world, qs = G.qs;
+    const bool exclude = !(flags & PN_SELF_INCLUDE), sorted = flags & PN_RADIUS_SORTED;
+    const unsigned inner = flags & PN_RADIUS_SORTED;
+    auto dwords = [](uint64_t c) { return (size_t)((c * sizeof(T) + 7) / 8); };
+    std::vector<hipStream_t> st(devs.size());
+    for (size_t i = 0; i < devs.size(); ++i) {
+        Dev &d = devs[i];
+        st[i] = d.stream;
+        SetGuard g(d.device);
+        if (!g.ok) return set_error(PN_ERR_DEVICE, "hipSetDevice(%d) failed", d.device);
+        SPN(acquire_dev(d, d.stream));
+        if (G.gather) {
+            SPN(d.q.ensure((size_t)G.c * qs * sizeof(T)));
+            SPN(d.sf_rows.ensure(W * (size_t)G.c * qs * sizeof(T)));
+        }
+        // rank mode, rad_a: [local offsets no | status 1 | total 1 | gathered W (no + 1)], no = batch + 1
+        if (sh->rank_mode) SPN(d.rad_a.ensure(((W * G.c + 3) + W * (W * G.c + 2)) * 8));
+    }
+    std::vector<std::vector<SelfSeg>> segs(devs.size());
+    const size_t np = sh->parts.size();
+    std::vector<std::vector<uint64_t>> offs(np), lists(np);
+    std::vector<std::vector<T>> dl(np);
+    std::vector<const uint64_t *> po, pi;
+    std::vector<const T *> pd;
+    std::vector<uint64_t> all_off, all_ids, all_d;
+    size_t cap = 0;  // rank mode: list capacity per rank, from gathered values only (the same on every rank)
+    for (uint64_t step = 0; step < G.steps; ++step) {
+        const uint64_t p0 = step * G.c, cs = std::min<uint64_t>(G.c, G.most - p0);
+        for (size_t i = 0; i < devs.size(); ++i) self_segs(sh, devs[i], p0, cs, segs[i]);
+        if (!G.gather) {  // one GPU: each segment's rows in place against every part
+            for (const SelfSeg &sg : segs[0]) {
+                size_t ld;
+                const T *rows = part_rows<T>(sh, sg.part, &ld) + sg.a * ld;
+                po.assign(np, nullptr);
+                pi.assign(np, nullptr);
+                pd.assign(np, nullptr);
+                for (size_t p = 0; p < np; ++p) {
+                    SetGuard g(devs[0].device);
+                    SPN(self_part_radius<T>(sh, (int)p, rows, (size_t)sg.m, ld, radius, inner, wd, offs[p], lists[p], dl[p]));
+                    po[p] = offs[p].data();
+                    pi[p] = lists[p].data();
+                    pd[p] = wd ? dl[p].data() : nullptr;
+                }
+                const uint64_t g0 = sh->parts[sg.part].lo + sg.a;
+                self_splice<T>(po, pi, pd, 0, sg.m, g0, g0 - G.first, exclude, sorted, wd, out);
+            }
+            continue;
+        }
+        const size_t nqb = W * (size_t)cs, no = nqb + 1;
+        int rc = PN_OK;
+        for (size_t i = 0; i < devs.size(); ++i) {
+            SetGuard g(devs[i].device);
+            keep_first(rc, self_pack_rows<T>(sh, devs[i], segs[i], cs, qs, st[i]));
+        }
+        if (!sh->rank_mode) {  // one process: no collective fails halfway for a local reason
+            SPN(rc);
+            SPN(self_gather_rows<T>(sh, cs, qs, st));
+            po.assign(np, nullptr);
+            pi.assign(np, nullptr);
+            pd.assign(np, nullptr);
+            for (size_t p = 0; p < np; ++p) {
+                Dev &d = devs[sh->parts[p].dev_slot];
+                SetGuard g(d.device);
+                SPN(self_part_radius<T>(sh, (int)p, (const T *)d.sf_rows.p, nqb, qs, radius, inner, wd, offs[p], lists[p],
+                                        dl[p]));
+                po[p] = offs[p].data();
+                pi[p] = lists[p].data();
+                pd[p] = wd ? dl[p].data() : nullptr;
+            }
+            for (size_t i = 0; i < devs.size(); ++i)
+                for (const SelfSeg &sg : segs[i]) {
+                    const uint64_t g0 = sh->parts[sg.part].lo + sg.a;
+                    self_splice<T>(po, pi, pd, (size_t)devs[i].comm_rank * cs + sg.j, sg.m, g0, g0 - G.first, exclude,
+                                   sorted, wd, out);
+                }
+            continue;
+        }
+        // one process per GPU: the rank-mode exchange of sharded_query_radius over the step's batch
+        Dev &d = devs[0];
+        SetGuard g(d.device);
+        const hipStream_t s = d.stream;
+        SPN(self_gather_rows<T>(sh, cs, qs, st));
+        const pn_index *lix = sh->parts.empty() ? nullptr : sh->parts[0].ix;
+        uint64_t *d_off = (uint64_t *)d.rad_a.p, *d_tot = d_off + no + 1, *d_all = d_off + no + 2;
+        if (cap < nqb * 4 + 1024) cap = nqb * 4 + 1024;
+        all_off.resize(W * (no + 1));
+        uint64_t longest = 1;
+        for (int attempt = 0;; ++attempt) {
+            int lrc = rc;
+            if (lrc == PN_OK) lrc = d.rad_b.ensure((cap + W * cap) * 8);
+            if (lrc == PN_OK && wd) lrc = d.rad_c.ensure((dwords(cap) + W * dwords(cap)) * 8);
+            if (lrc == PN_OK) {
+                if (!lix)  // a rank without rows: every list empty
+                    lrc = hip_rc(hipMemsetAsync(d_off, 0, no * 8, s), "offsets");
+                else if (wd)
+                    lrc = ShT<T>::radius_wd_device(lix, (const T *)d.sf_rows.p, nqb, sh->dim, qs, radius, inner, d_off,
+                                                   (uint64_t *)d.rad_b.p, (T *)d.rad_c.p, cap, d_tot, s);
+                else
+                    lrc = ShT<T>::radius_device(lix, (const T *)d.sf_rows.p, nqb, sh->dim, qs, radius, d_off,
+                                                (uint64_t *)d.rad_b.p, cap, d_tot, s);
+            }
+            keep_first(rc, lrc);
+            // the status word travels with the offsets: a failed rank still enters the exchange, and all ranks stop
+            SHIP(hipMemsetAsync(d_off + no, rc == PN_OK ? 0 : 0xFF, 8, s));
+            SNCCL(rccl().AllGather(d_off, d_all, no + 1, ncclUint64, d.comm, s));
+            SHIP(hipMemcpyAsync(all_off.data(), d_all, W * (no + 1) * 8, hipMemcpyDeviceToHost, s));
+            SHIP(hipStreamSynchronize(s));
+            if (rc != PN_OK) return rc;
+            longest = 1;
+            for (size_t r = 0; r < W; ++r) {
+                if (all_off[r * (no + 1) + no])
+                    return set_error(PN_ERR_DEVICE, "self-query: rank %zu failed in its local work", r);
+                longest = std::max<uint64_t>(longest, all_off[r * (no + 1) + nqb]);
+            }
+            if (longest <= cap) break;  // every rank's lists fit (all ranks see the same numbers: same decision)
+            if (attempt) return set_error(PN_ERR_DEVICE, "radius lists changed size between two passes");
+            cap = (size_t)longest;  // some rank overflowed: everybody re-runs with room for the longest
+        }
+        uint64_t *d_mine = (uint64_t *)d.rad_b.p, *d_lists = d_mine + cap;
+        const size_t dw = dwords(longest);
+        SNCCL(rccl().AllGather(d_mine, d_lists, (size_t)longest, ncclUint64, d.comm, s));
+        if (wd)  // (every rank alike: the call's arguments decide it)
+            SNCCL(rccl().AllGather(d.rad_c.p, (uint64_t *)d.rad_c.p + dwords(cap), dw, ncclUint64, d.comm, s));
+        all_ids.resize((size_t)(W * longest));
+        all_d.resize(wd ? W * dw : 0);
+        SHIP(hipMemcpyAsync(all_ids.data(), d_lists, (size_t)(W * longest) * 8, hipMemcpyDeviceToHost, s));
+        if (wd)
+            SHIP(hipMemcpyAsync(all_d.data(), (uint64_t *)d.rad_c.p + dwords(cap), W * dw * 8, hipMemcpyDeviceToHost, s));
+        SHIP(hipStreamSynchronize(s));
+        po.assign(W, nullptr);
+        pi.assign(W, nullptr);
+        pd.assign(W, nullptr);
+        for (size_t r = 0; r < W; ++r) {  // the ranks in rank order: shards are ascending row ranges
+            po[r] = all_off.data() + r * (no + 1);
+            pi[r] = all_ids.data() + r * longest;
+            if (wd) pd[r] = (const T *)(all_d.data() + r * dw);
+        }
+        for (const SelfSeg &sg : segs[0]) {
+            const uint64_t g0 = sh->parts[sg.part].lo + sg.a;
+            self_splice<T>(po, pi, pd, (size_t)d.comm_rank * cs + sg.j, sg.m, g0, g0 - G.first, exclude, sorted, wd, out);
+        }
+    }
+    return PN_OK;
+}
+
+template <typename T>
+static int sharded_query_radius_self(const pn_sharded *sh, T radius, unsigned flags, uint64_t *offsets, uint64_t **idx_out,
+                                     T **dist_out) {
+    if (flags & ~(unsigned)(PN_RADIUS_SORTED | PN_SELF_INCLUDE))
+        return set_error(PN_ERR_INVALID, "unknown self-query flags 0x%x", flags);
+    if (!offsets || !idx_out) return set_error(PN_ERR_INVALID, "output buffer is NULL");
+    if ((flags & PN_RADIUS_SORTED) && !dist_out)
+        return set_error(PN_ERR_INVALID, "PN_RADIUS_SORTED needs the distance output");
+    *idx_out = nullptr;
+    if (dist_out) *dist_out = nullptr;
+    if (!sh) return set_error(PN_ERR_INVALID, "handle is NULL");
+    SPN(check_elem(sh, sizeof(T)));
+    if (sh->n_shards == 1 && !sh->exchange_always)  // one shard: the single index's own self-query
+        return ShT<T>::radius_self(sh->parts[0].ix, radius, flags, offsets, idx_out, dist_out);
+    std::lock_guard<std::mutex> lk(sh->mu);
+    uint64_t local = 0;
+    for (const Part &p : sh->parts) local += p.hi - p.lo;
+    SelfLists<T> out;
+    const bool wd = dist_out != nullptr;
+    try {
+        out.cnt.assign((size_t)local, 0);
+        SPN(self_radius_run<T>(sh, radius, flags, wd, out));
+    } catch (const std::bad_alloc &) {
+        return set_error(PN_ERR_NOMEM, "host allocation failed");
+    }
+    // local row order
+    const uint64_t total = out.idx.size();
+    uint64_t *res = (uint64_t *)malloc((total ? total : 1) * sizeof(uint64_t));
+    T *dres = wd ? (T *)malloc((total ? total : 1) * sizeof(T)) : nullptr;
+    if (!res || (wd && !dres)) {
+        free(res);
+        free(dres);
+        return set_error(PN_ERR_NOMEM, "malloc(%llu results) failed", (unsigned long long)total);
+    }
+    offsets[0] = 0;
+    for (uint64_t i = 0; i < local; ++i) offsets[i + 1] = offsets[i] + out.cnt[i];
+    for (const auto &pc : out.pieces) {
+        const uint64_t dst = offsets[pc.row0], len = offsets[pc.row0 + pc.m] - dst;
+        if (!len) continue;
+        memcpy(res + dst, out.idx.data() + pc.at, (size_t)len * sizeof(uint64_t));
+        if (wd) memcpy(dres + dst, out.dist.data() + pc.at, (size_t)len * sizeof(T));
+    }
+    *idx_out = res;
+    if (dist_out) *dist_out = dres;
+    return PN_OK;
+}
+extern "C" int pn_sharded_query_radius_self_f32(const pn_sharded *sh, float radius, unsigned flags, uint64_t *offsets,
+                                                uint64_t **idx_out, float **dist_out) {
+    return sharded_query_radius_self<float>(sh, radius, flags, offsets, idx_out, dist_out);
+}
+extern "C" int pn_sharded_query_radius_self_f64(const pn_sharded *sh, double radius, unsigned flags, uint64_t *offsets,
+                                                uint64_t **idx_out, double **dist_out) {
+    return sharded_query_radius_self<double>(sh, radius, flags, offsets, idx_out, dist_out);
+}
+// pn_query_radius_self_device_* on a handle with ONE shard; several shards: PN_ERR_UNSUPPORTED, as
+// pn_sharded_query_radius_device_*
+template <typename T>
+static int sharded_query_radius_self_device(const pn_sharded *sh, T radius, unsigned flags, uint64_t *d_offsets,
+                                            uint64_t *d_idx, T *d_dist, size_t capacity, uint64_t *d_total, void *stream) {
+    if (flags & ~(unsigned)(PN_RADIUS_SORTED | PN_SELF_INCLUDE))
+        return set_error(PN_ERR_INVALID, "unknown self-query flags 0x%x", flags);
+    if (!d_offsets || (capacity && !d_idx)) return set_error(PN_ERR_INVALID, "output buffer is NULL");
+    if ((flags & PN_RADIUS_SORTED) && capacity && !d_dist)
+        return set_error(PN_ERR_INVALID, "PN_RADIUS_SORTED needs the distance output");
+    if (!sh) return set_error(PN_ERR_INVALID, "handle is NULL");
+    SPN(check_elem(sh, sizeof(T)));
+    if (sh->n_shards != 1 || sh->parts.size() != 1 || !sh->parts[0].ix)
+        return set_error(PN_ERR_UNSUPPORTED, "the device-resident radius self-query serves handles with one shard");
+    return ShT<T>::radius_self_device(sh->parts[0].ix, radius, flags, d_offsets, d_idx, d_dist, capacity, d_total, stream);
+}
+extern "C" int pn_sharded_query_radius_self_device_f32(const pn_sharded *sh, float radius, unsigned flags,
+                                                       uint64_t *d_offsets, uint64_t *d_idx, float *d_dist, size_t capacity,
+                                                       uint64_t *d_total, void *stream) {
+    return sharded_query_radius_self_device<float>(sh, radius, flags, d_offsets, d_idx, d_dist, capacity, d_total, stream);
+}
+extern "C" int pn_sharded_query_radius_self_device_f64(const pn_sharded *sh, double radius, unsigned flags,
+                                                       uint64_t *d_offsets, uint64_t *d_idx, double *d_dist,
+                                                       size_t capacity, uint64_t *d_total, void *stream) {
+    return sharded_query_radius_self_device<double>(sh, radius, flags, d_offsets, d_idx, d_dist, capacity, d_total, stream);
 }

@@ -49,6 +49,7 @@ class ShardedIndex:
         self.n_shards, self.world, self.rank = int(info.n_shards), int(info.world), int(info.rank)
         self.local_first_row, self.local_rows = int(info.local_first_row), int(info.local_rows)
         self.mfma_eligible, self.bf16_eligible = bool(info.mfma_eligible), bool(info.bf16_eligible)
+        self.device = None  # the GPU of the device entry points (set by the constructors below)
 
     @classmethod
     def from_host(cls, points, devices, metric=None):
@@ -70,7 +71,9 @@ class ShardedIndex:
         sfx = "f64" if a.dtype == np.float64 else "f32"
         create = getattr(_lib.lib(), ("pn_sharded_create_cosine_" if isinstance(metric, Cosine) else "pn_sharded_create_") + sfx)
         check(create(a.ctypes.data if a.size else None, n, d, rs, cs if d > 1 else 1, devs, len(devices), C.byref(h)))
-        return cls(h.value, keep=a, dtype=a.dtype)
+        out = cls(h.value, keep=a, dtype=a.dtype)
+        out.device = int(devices[0]) if len(set(int(x) for x in devices)) == 1 else None
+        return out
 
     @staticmethod
     def unique_id() -> bytes:
@@ -108,7 +111,9 @@ class ShardedIndex:
         idb = C.create_string_buffer(bytes(comm_id), _lib.PN_COMM_ID_BYTES)
         create = _lib.lib().pn_sharded_create_rank_device_f64 if f64 else _lib.lib().pn_sharded_create_rank_device_f32
         check(create(ptr, nl, d, ld, int(n_total), int(rank), int(world), idb, int(device), C.c_void_p(st), C.byref(h)))
-        return cls(h.value, dtype=np.float64 if f64 else np.float32)
+        out = cls(h.value, dtype=np.float64 if f64 else np.float32)
+        out.device = int(device)
+        return out
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None
@@ -288,6 +293,127 @@ class ShardedIndex:
         fn = getattr(_lib.lib(), f"pn_sharded_query_radius_with_distance_device_{self._sfx}")
         check(fn(self._h, queries.data_ptr() if nq * qc else None, nq, qc, queries.stride(0) if nq > 1 else max(qc, 1), r,
                  flags, offs.data_ptr(), idx.data_ptr(), dist.data_ptr(), int(capacity), tot.data_ptr(), C.c_void_p(st)))
+        return offs, idx, dist, tot
+
+
+    # ---- self-queries (pn_sharded_query_self_*, pn_sharded_query_radius_self_*): the BallTree methods of the same names
+    # over the whole corpus, answered for the LOCAL rows (rows local_first_row .. local_first_row + local_rows), global
+    # row numbers.  In rank mode every rank calls them with the same arguments.
+    def _self_flags(self, include_self, sort=False):
+        from . import _lib
+        return (_lib.PN_SELF_INCLUDE if include_self else 0) | (_lib.PN_RADIUS_SORTED if sort else 0)
+
+    def _self_k(self, k, include_self):
+        if int(k) < 0:
+            raise ValueError("k must be >= 0")
+        return min(int(k), self.n if include_self else self.n - 1)
+
+    def query_self(self, k: int, include_self: bool = False):
+        """The k nearest OTHER rows of every local row: ``(idx uint64 [local_rows, kout], dist [local_rows, kout])``,
+        kout = min(k, n - 1) (``include_self``: min(k, n)), ordered by (distance, global row)."""
+        from . import _lib
+        from .errors import check
+        kout = self._self_k(k, include_self)
+        idx = np.empty((self.local_rows, kout), dtype=np.uint64)
+        dist = np.empty((self.local_rows, kout), dtype=self.dtype)
+        if kout:  # (a rank without rows still takes part: NumPy's empty arrays keep a non-NULL buffer)
+            check(getattr(_lib.lib(), "pn_sharded_query_self_" + self._sfx)(
+                self._h, int(k), self._self_flags(include_self), idx.ctypes.data, dist.ctypes.data))
+        return idx, dist
+
+    def query_self_device(self, k: int, include_self: bool = False, out_idx=None, out_dist=None, stream=None):
+        """``query_self`` with the results in HBM of the handle's GPU: CUDA tensors ``(idx int64 [local_rows, kout],
+        dist [local_rows, kout])``, enqueued on ``stream`` (default: the current torch stream)."""
+        import torch
+        from . import _lib
+        from .errors import check
+        if self.device is None:
+            raise ValueError("device-resident self-queries need a handle that drives ONE GPU")
+        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
+        kout = self._self_k(k, include_self)
+        dev = torch.device("cuda", self.device)
+        rows = self.local_rows
+        if out_idx is None:
+            out_idx = torch.empty((rows, kout), dtype=torch.int64, device=dev)
+        if out_dist is None:
+            out_dist = torch.empty((rows, kout), dtype=tdt, device=dev)
+        if out_dist.dtype != tdt or out_idx.numel() < rows * kout or out_dist.numel() < rows * kout:
+            raise ValueError("output tensors are too small or of the wrong type")
+        if kout:
+            st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+            keep = None
+            pi, pd = out_idx.data_ptr(), out_dist.data_ptr()
+            if not rows:  # (placeholders a rank without rows hands in: nothing is written to them)
+                keep = (torch.empty(1, dtype=torch.int64, device=dev), torch.empty(1, dtype=tdt, device=dev))
+                pi, pd = keep[0].data_ptr(), keep[1].data_ptr()
+            check(getattr(_lib.lib(), "pn_sharded_query_self_device_" + self._sfx)(
+                self._h, int(k), self._self_flags(include_self), pi, pd, C.c_void_p(st)))
+            del keep
+        return out_idx, out_dist
+
+    def query_radius_self(self, r, with_distance: bool = False, sort: bool = False, include_self: bool = False):
+        """``{ j != i : distance(p_i, p_j) < r }`` for every local row i, as CSR over the local rows: ``(offsets uint64
+        [local_rows + 1], idx uint64, dist or None)``; ascending by global row, or by (distance, row) with ``sort=True``
+        (needs ``with_distance``)."""
+        from . import _lib
+        from .errors import check
+        if sort and not with_distance:
+            raise ValueError("sort=True needs with_distance=True")
+        offsets = np.zeros(self.local_rows + 1, dtype=np.uint64)
+        out_i, out_d = C.c_void_p(0), C.c_void_p(0)
+        rr = C.c_float(r) if self._sfx == "f32" else C.c_double(r)
+        fn = getattr(_lib.lib(), "pn_sharded_query_radius_self_" + self._sfx)
+        try:
+            check(fn(self._h, rr, self._self_flags(include_self, sort), offsets.ctypes.data, C.byref(out_i),
+                     C.byref(out_d) if with_distance else None))
+            total = int(offsets[-1])
+            idx = np.empty(0, dtype=np.uint64)
+            dist = np.empty(0, dtype=self.dtype) if with_distance else None
+            if total:
+                idx = np.frombuffer((C.c_uint64 * total).from_address(out_i.value), dtype=np.uint64).copy()
+                if with_distance:
+                    ct = C.c_float if self._sfx == "f32" else C.c_double
+                    dist = np.frombuffer((ct * total).from_address(out_d.value), dtype=self.dtype).copy()
+        finally:
+            for p in (out_i, out_d):
+                if p.value:
+                    _lib.lib().pn_free(p)
+        return offsets, idx, dist
+
+    def query_radius_self_device(self, r, capacity: int, with_distance: bool = False, sort: bool = False,
+                                 include_self: bool = False, out_offsets=None, out_idx=None, out_dist=None, out_total=None,
+                                 stream=None):
+        """``BallTree.query_radius_self_device`` on a handle with ONE shard (several shards: PN_ERR_UNSUPPORTED, the
+        host entry ``query_radius_self`` serves them): CUDA tensors ``(offsets int64 [n+1], idx int64 [capacity], dist
+        [capacity] or None, total int64 [1])``."""
+        import torch
+        from . import _lib
+        from .errors import check
+        if int(capacity) < 0:
+            raise ValueError("capacity must be >= 0")
+        if sort and not with_distance:
+            raise ValueError("sort=True needs with_distance=True")
+        if self.device is None:
+            raise ValueError("device-resident self-queries need a handle that drives ONE GPU")
+        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
+        dev = torch.device("cuda", self.device)
+        cap = max(int(capacity), 1)
+        rows = self.local_rows
+        offs = out_offsets if out_offsets is not None else torch.empty(rows + 1, dtype=torch.int64, device=dev)
+        idx = out_idx if out_idx is not None else torch.empty(cap, dtype=torch.int64, device=dev)
+        dist = None
+        if with_distance:
+            dist = out_dist if out_dist is not None else torch.empty(cap, dtype=tdt, device=dev)
+            if dist.dtype != tdt or dist.numel() < int(capacity):
+                raise ValueError("output tensors are too small or of the wrong type")
+        tot = out_total if out_total is not None else torch.empty(1, dtype=torch.int64, device=dev)
+        if idx.numel() < int(capacity) or offs.numel() < rows + 1:
+            raise ValueError("output tensors are too small")
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        rr = C.c_float(r) if self._sfx == "f32" else C.c_double(r)
+        fn = getattr(_lib.lib(), "pn_sharded_query_radius_self_device_" + self._sfx)
+        check(fn(self._h, rr, self._self_flags(include_self, sort), offs.data_ptr(), idx.data_ptr(),
+                 dist.data_ptr() if dist is not None else None, int(capacity), tot.data_ptr(), C.c_void_p(st)))
         return offs, idx, dist, tot
 
 
