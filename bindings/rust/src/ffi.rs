@@ -116,6 +116,32 @@ extern "C" {
                                            d_idx: *mut u64, d_dist: *mut f64, capacity: usize, d_total: *mut u64,
                                            stream: *mut c_void) -> c_int;
 
+    /// one radius per query (radii [nq]; self-queries: [n]): list q is the scalar entry point's for query q with radii[q]
+    pub fn pn_query_radii_f32(index: *const pn_index, queries: *const f32, nq: usize, q_cols: usize, q_row_stride: isize,
+                              radii: *const f32, flags: c_uint, offsets: *mut u64, idx_out: *mut *mut u64,
+                              dist_out: *mut *mut f32) -> c_int;
+    pub fn pn_query_radii_f64(index: *const pn_index, queries: *const f64, nq: usize, q_cols: usize, q_row_stride: isize,
+                              radii: *const f64, flags: c_uint, offsets: *mut u64, idx_out: *mut *mut u64,
+                              dist_out: *mut *mut f64) -> c_int;
+    pub fn pn_query_radii_device_f32(index: *const pn_index, d_queries: *const f32, nq: usize, q_cols: usize,
+                                     q_row_stride: usize, d_radii: *const f32, flags: c_uint, d_offsets: *mut u64,
+                                     d_idx: *mut u64, d_dist: *mut f32, capacity: usize, d_total: *mut u64,
+                                     stream: *mut c_void) -> c_int;
+    pub fn pn_query_radii_device_f64(index: *const pn_index, d_queries: *const f64, nq: usize, q_cols: usize,
+                                     q_row_stride: usize, d_radii: *const f64, flags: c_uint, d_offsets: *mut u64,
+                                     d_idx: *mut u64, d_dist: *mut f64, capacity: usize, d_total: *mut u64,
+                                     stream: *mut c_void) -> c_int;
+    pub fn pn_query_radii_self_f32(index: *const pn_index, radii: *const f32, flags: c_uint, offsets: *mut u64,
+                                   idx_out: *mut *mut u64, dist_out: *mut *mut f32) -> c_int;
+    pub fn pn_query_radii_self_f64(index: *const pn_index, radii: *const f64, flags: c_uint, offsets: *mut u64,
+                                   idx_out: *mut *mut u64, dist_out: *mut *mut f64) -> c_int;
+    pub fn pn_query_radii_self_device_f32(index: *const pn_index, d_radii: *const f32, flags: c_uint, d_offsets: *mut u64,
+                                          d_idx: *mut u64, d_dist: *mut f32, capacity: usize, d_total: *mut u64,
+                                          stream: *mut c_void) -> c_int;
+    pub fn pn_query_radii_self_device_f64(index: *const pn_index, d_radii: *const f64, flags: c_uint, d_offsets: *mut u64,
+                                          d_idx: *mut u64, d_dist: *mut f64, capacity: usize, d_total: *mut u64,
+                                          stream: *mut c_void) -> c_int;
+
     pub fn pn_pairwise_f32(x: *const f32, n_rows: usize, n_cols: usize, row_stride: isize, device: c_int,
                            out: *mut f32) -> c_int;
     pub fn pn_pairwise_f64(x: *const f64, n_rows: usize, n_cols: usize, row_stride: isize, device: c_int,

@@ -46,6 +46,12 @@ pub trait Elem: Copy + Default + PartialOrd + 'static {
     unsafe fn self_radius(ix: *const ffi::pn_index, r: Self, flags: std::os::raw::c_uint, off: *mut u64, out: *mut *mut u64,
                           dout: *mut *mut Self) -> c_int;
     #[doc(hidden)]
+    unsafe fn radii(ix: *const ffi::pn_index, q: *const Self, nq: usize, qc: usize, r: *const Self,
+                    flags: std::os::raw::c_uint, off: *mut u64, out: *mut *mut u64, dout: *mut *mut Self) -> c_int;
+    #[doc(hidden)]
+    unsafe fn self_radii(ix: *const ffi::pn_index, r: *const Self, flags: std::os::raw::c_uint, off: *mut u64,
+                         out: *mut *mut u64, dout: *mut *mut Self) -> c_int;
+    #[doc(hidden)]
     unsafe fn radius_of(ix: *const ffi::pn_index, n: u64, out: *mut Self) -> c_int;
     #[doc(hidden)]
     unsafe fn lower_bound(ix: *const ffi::pn_index, a: u64, b: u64, out: *mut Self) -> c_int;
@@ -58,7 +64,8 @@ pub trait Elem: Copy + Default + PartialOrd + 'static {
 }
 macro_rules! impl_elem {
     ($t:ty, $create:ident, $create_cos:ident, $query:ident, $radius:ident, $radius_wd:ident, $rad_of:ident, $lb:ident,
-     $eu:ident, $reu:ident, $cos:ident, $pw:ident, $pwc:ident, $self_knn:ident, $self_rad:ident) => {
+     $eu:ident, $reu:ident, $cos:ident, $pw:ident, $pwc:ident, $self_knn:ident, $self_rad:ident, $radii:ident,
+     $self_radii:ident) => {
         impl Elem for $t {
             unsafe fn create(p: *const Self, n: usize, d: usize, rs: isize, cs: isize, cosine: bool, out: *mut *mut ffi::pn_index) -> c_int {
                 if cosine { ffi::$create_cos(p, n, d, rs, cs, 0, out) } else { ffi::$create(p, n, d, rs, cs, 0, out) }
@@ -80,6 +87,14 @@ macro_rules! impl_elem {
                                   out: *mut *mut u64, dout: *mut *mut Self) -> c_int {
                 ffi::$self_rad(ix, r, flags, off, out, dout)
             }
+            unsafe fn radii(ix: *const ffi::pn_index, q: *const Self, nq: usize, qc: usize, r: *const Self,
+                            flags: std::os::raw::c_uint, off: *mut u64, out: *mut *mut u64, dout: *mut *mut Self) -> c_int {
+                ffi::$radii(ix, q, nq, qc, qc as isize, r, flags, off, out, dout)
+            }
+            unsafe fn self_radii(ix: *const ffi::pn_index, r: *const Self, flags: std::os::raw::c_uint, off: *mut u64,
+                                 out: *mut *mut u64, dout: *mut *mut Self) -> c_int {
+                ffi::$self_radii(ix, r, flags, off, out, dout)
+            }
             unsafe fn radius_of(ix: *const ffi::pn_index, n: u64, out: *mut Self) -> c_int { ffi::$rad_of(ix, n, out) }
             unsafe fn lower_bound(ix: *const ffi::pn_index, a: u64, b: u64, out: *mut Self) -> c_int { ffi::$lb(ix, a, b, out) }
             unsafe fn euclid(a: *const Self, b: *const Self, n: usize, squared: bool) -> Self {
@@ -95,11 +110,13 @@ macro_rules! impl_elem {
 impl_elem!(f32, pn_index_create_f32, pn_index_create_cosine_f32, pn_query_f32, pn_query_radius_f32,
            pn_query_radius_with_distance_f32, pn_tree_radius_of_f32,
            pn_tree_node_distance_lower_bound_f32, pn_euclidean_f32, pn_reuclidean_f32, pn_cosine_f32, pn_pairwise_f32,
-           pn_pairwise_cosine_f32, pn_query_self_f32, pn_query_radius_self_f32);
+           pn_pairwise_cosine_f32, pn_query_self_f32, pn_query_radius_self_f32, pn_query_radii_f32,
+           pn_query_radii_self_f32);
 impl_elem!(f64, pn_index_create_f64, pn_index_create_cosine_f64, pn_query_f64, pn_query_radius_f64,
            pn_query_radius_with_distance_f64, pn_tree_radius_of_f64,
            pn_tree_node_distance_lower_bound_f64, pn_euclidean_f64, pn_reuclidean_f64, pn_cosine_f64, pn_pairwise_f64,
-           pn_pairwise_cosine_f64, pn_query_self_f64, pn_query_radius_self_f64);
+           pn_pairwise_cosine_f64, pn_query_self_f64, pn_query_radius_self_f64, pn_query_radii_f64,
+           pn_query_radii_self_f64);
 
 pub mod distance {
     use super::*;
@@ -253,6 +270,44 @@ impl<'a, A: Elem, M: Metric<A>> BallTree<'a, A, M> {
         let total = off[n] as usize;
         let idx = unsafe { std::slice::from_raw_parts(out, total) }.iter().map(|&i| i as usize).collect();
         let dist = unsafe { std::slice::from_raw_parts(dout, total) }.to_vec();
+        unsafe {
+            ffi::pn_free(out as *mut _);
+            ffi::pn_free(dout as *mut _);
+        }
+        (off, idx, dist)
+    }
+    /// extension: `query_radius_self` with one radius per row (`radii.len()` = the number of rows): row i's list is the
+    /// scalar call's for `radii[i]`
+    pub fn query_radii_self(&self, radii: &[A], sorted: bool, include_self: bool) -> (Vec<u64>, Vec<usize>, Vec<A>) {
+        let n = self.points.nrows();
+        assert_eq!(radii.len(), n, "one radius per indexed row");
+        let mut off = vec![0u64; n + 1];
+        let mut out: *mut u64 = std::ptr::null_mut();
+        let mut dout: *mut A = std::ptr::null_mut();
+        let flags = (if sorted { ffi::PN_RADIUS_SORTED } else { 0 }) | (if include_self { ffi::PN_SELF_INCLUDE } else { 0 });
+        ok(unsafe { A::self_radii(self.handle, radii.as_ptr(), flags, off.as_mut_ptr(), &mut out, &mut dout) });
+        Self::take_csr(off, out, dout)
+    }
+    /// extension: the rows of `queries` in one call, one radius each (`radii.len()` = the number of queries): list q is
+    /// `query_radius_with_distance(queries.row(q), radii[q])` -- CSR (offsets [nq + 1], indices, distances)
+    pub fn query_radii(&self, queries: ArrayView2<A>, radii: &[A], sorted: bool) -> (Vec<u64>, Vec<usize>, Vec<A>) {
+        let q = queries.as_standard_layout();
+        let (nq, d) = q.dim();
+        assert_eq!(radii.len(), nq, "one radius per query");
+        let mut off = vec![0u64; nq + 1];
+        let mut out: *mut u64 = std::ptr::null_mut();
+        let mut dout: *mut A = std::ptr::null_mut();
+        let flags = if sorted { ffi::PN_RADIUS_SORTED } else { 0 };
+        ok(unsafe { A::radii(self.handle, q.as_ptr(), nq, d, radii.as_ptr(), flags, off.as_mut_ptr(), &mut out, &mut dout) });
+        Self::take_csr(off, out, dout)
+    }
+    fn take_csr(off: Vec<u64>, out: *mut u64, dout: *mut A) -> (Vec<u64>, Vec<usize>, Vec<A>) {
+        let total = *off.last().unwrap() as usize;
+        let (mut idx, mut dist) = (Vec::new(), Vec::new());
+        if total > 0 {
+            idx = unsafe { std::slice::from_raw_parts(out, total) }.iter().map(|&i| i as usize).collect();
+            dist = unsafe { std::slice::from_raw_parts(dout, total) }.to_vec();
+        }
         unsafe {
             ffi::pn_free(out as *mut _);
             ffi::pn_free(dout as *mut _);

@@ -59,7 +59,7 @@ extern "C" {
  * Additive within version 3 (callers detect them by symbol): pn_query_radius_with_distance_{,device_}{f32,f64},
  * pn_sharded_query_radius_with_distance_{,device_}{f32,f64}, PN_RADIUS_SORTED; pn_query_self_{,device_}{f32,f64},
  * pn_query_radius_self_{,device_}{f32,f64}, PN_SELF_INCLUDE; pn_sharded_query_self_{,device_}{f32,f64},
- * pn_sharded_query_radius_self_{,device_}{f32,f64}. */
+ * pn_sharded_query_radius_self_{,device_}{f32,f64}; pn_query_radii_{,device_,self_,self_device_}{f32,f64}. */
 #define PN_ABI_VERSION 3
 
 /* ---- error codes.  EMPTY / NOT_CONTIGUOUS are ArrayError (src/lib.rs:9-16). */
@@ -320,6 +320,48 @@ int pn_query_radius_self_device_f32(const pn_index *index, float radius, unsigne
                                     uint64_t *d_idx, float *d_dist, size_t capacity, uint64_t *d_total, void *stream);
 int pn_query_radius_self_device_f64(const pn_index *index, double radius, unsigned flags, uint64_t *d_offsets,
                                     uint64_t *d_idx, double *d_dist, size_t capacity, uint64_t *d_total, void *stream);
+
+/* ---- one radius per query (scikit-learn's BallTree.query_radius(X, r) with an array r): radii [nq] (self-queries:
+ * [n], row i's own radius) in the index's element type.  List q is the single list pn_query_radius_with_distance_*
+ * returns for query q alone with radius radii[q] and the same flags -- same index set, same order, bit-identical distances
+ * (self-queries: pn_query_radius_self_* with radii[i], row i's list) -- so the scalar contract holds PER QUERY: strict '<';
+ * a radius <= 0 or NaN gives an empty list and +inf every row whose distance is not NaN; Cosine radii >= 1 are answered
+ * by the exact scan; ascending index order, or nearest-first by (distance, index) with PN_RADIUS_SORTED, which needs
+ * the distances; PN_SELF_INCLUDE on the self entry points only; unknown flag bits: PN_ERR_INVALID; PN_OPT_INDEX_BASE
+ * applies; pn_stats.queries / radius_results advance as the corresponding scalar entry point's do.  Distances are optional
+ * (dist_out / d_dist NULL).  radii NULL with nq > 0 (n > 0): PN_ERR_INVALID, like every argument error reported before
+ * any device is touched.
+ * Which tier answers a query is decided per query ON THE DEVICE: a query whose radius the first tier cannot serve (not
+ * finite positive, Cosine r >= 1, r^2 beyond the filter's range) or whose survivor list overflows is listed on the device
+ * and answered by the exact scan with its own radius, while the rest of the batch stays in the filter.  The number of
+ * listed queries is added (by a kernel, nothing is read back) to the device word pn_index_get_stats folds into
+ * pn_stats.fallback_queries -- once per call; the scalar entry points do not report it.  It counts queries listed OUT OF
+ * an entered first tier: a call that never enters it (fewer than 4096 rows or 8 columns, queries of another length than
+ * the rows, an engine option) answers every query by the exact scan, as the scalar call does, and adds nothing.
+ * Device entry points: the capacity contract of pn_query_radius_with_distance_device_* (d_offsets always complete, entries
+ * below `capacity` written, capacity = 0 only counts and d_idx / d_dist may then be NULL, d_total (nullable) = the total,
+ * the same sorted / straddle rule); d_radii in HBM; nothing is read back, everything is enqueued on `stream`.
+ * Host entry points: built on that pipeline, as pn_query_radius_self_* -- queries and radii up, a counting pass, the
+ * exact total allocated (pn_free), a fill pass.  The scalar host path's f32 MFMA radius tier and its one-launch path for
+ * tiny corpora do not take arrays: the latency of small calls is not a goal of these entry points. */
+int pn_query_radii_f32(const pn_index *index, const float *queries, size_t nq, size_t q_cols, ptrdiff_t q_row_stride,
+                       const float *radii, unsigned flags, uint64_t *offsets, uint64_t **idx_out, float **dist_out);
+int pn_query_radii_f64(const pn_index *index, const double *queries, size_t nq, size_t q_cols, ptrdiff_t q_row_stride,
+                       const double *radii, unsigned flags, uint64_t *offsets, uint64_t **idx_out, double **dist_out);
+int pn_query_radii_device_f32(const pn_index *index, const float *d_queries, size_t nq, size_t q_cols, size_t q_row_stride,
+                              const float *d_radii, unsigned flags, uint64_t *d_offsets, uint64_t *d_idx, float *d_dist,
+                              size_t capacity, uint64_t *d_total, void *stream);
+int pn_query_radii_device_f64(const pn_index *index, const double *d_queries, size_t nq, size_t q_cols,
+                              size_t q_row_stride, const double *d_radii, unsigned flags, uint64_t *d_offsets,
+                              uint64_t *d_idx, double *d_dist, size_t capacity, uint64_t *d_total, void *stream);
+int pn_query_radii_self_f32(const pn_index *index, const float *radii, unsigned flags, uint64_t *offsets,
+                            uint64_t **idx_out, float **dist_out);
+int pn_query_radii_self_f64(const pn_index *index, const double *radii, unsigned flags, uint64_t *offsets,
+                            uint64_t **idx_out, double **dist_out);
+int pn_query_radii_self_device_f32(const pn_index *index, const float *d_radii, unsigned flags, uint64_t *d_offsets,
+                                   uint64_t *d_idx, float *d_dist, size_t capacity, uint64_t *d_total, void *stream);
+int pn_query_radii_self_device_f64(const pn_index *index, const double *d_radii, unsigned flags, uint64_t *d_offsets,
+                                   uint64_t *d_idx, double *d_dist, size_t capacity, uint64_t *d_total, void *stream);
 
 /* ---- distance::pairwise(x, &Euclidean) (src/distance.rs:58-74): n x n
  * symmetric matrix, zero diagonal, n < 2 -> zeros. Host in, host out. */

@@ -268,7 +268,51 @@ class BallTree {
         pn_free(dout);
         return res;
     }
+    // extension: one radius per row (pn_query_radii_self_*): radii [size()], row i's list is the scalar overload's for
+    // r = radii[i].  (Taken for pointer arguments only: a literal 0 or NULL stays a call of the scalar overload.)
+    template <typename P, typename = typename std::enable_if<std::is_pointer<P>::value &&
+                                                             std::is_convertible<P, const A *>::value>::type>
+    SelfRadius<A> query_radius_self(P radii, bool with_distance, bool sorted, bool include_self) const {
+        std::vector<uint64_t> off(n_ + 1, 0);
+        uint64_t *out = nullptr;
+        A *dout = nullptr;
+        const unsigned flags = (sorted ? PN_RADIUS_SORTED : 0u) | (include_self ? PN_SELF_INCLUDE : 0u);
+        if constexpr (kF32)
+            check(pn_query_radii_self_f32(h_, radii, flags, off.data(), &out, with_distance ? &dout : nullptr));
+        else
+            check(pn_query_radii_self_f64(h_, radii, flags, off.data(), &out, with_distance ? &dout : nullptr));
+        return take_csr(off, out, dout);
+    }
+    // extension: nq queries of `len` elements (contiguous rows), one radius each (pn_query_radii_*): list q is
+    // query_radius / query_radius_with_distance(queries + q * len, len, radii[q], sorted); the same CSR struct
+    SelfRadius<A> query_radii(const A *queries, size_t nq, size_t len, const A *radii, bool with_distance,
+                              bool sorted) const {
+        std::vector<uint64_t> off(nq + 1, 0);
+        uint64_t *out = nullptr;
+        A *dout = nullptr;
+        const unsigned flags = sorted ? PN_RADIUS_SORTED : 0u;
+        if constexpr (kF32)
+            check(pn_query_radii_f32(h_, queries, nq, len, (ptrdiff_t)len, radii, flags, off.data(), &out,
+                                     with_distance ? &dout : nullptr));
+        else
+            check(pn_query_radii_f64(h_, queries, nq, len, (ptrdiff_t)len, radii, flags, off.data(), &out,
+                                     with_distance ? &dout : nullptr));
+        return take_csr(off, out, dout);
+    }
     pn_index *handle() const { return h_; }
+
+  private:
+    // a library-allocated CSR answer (offsets, lists, distances or NULL) into vectors; the lists are freed
+    static SelfRadius<A> take_csr(const std::vector<uint64_t> &off, uint64_t *out, A *dout) {
+        SelfRadius<A> res;
+        const uint64_t total = off.back();
+        res.offsets.assign(off.begin(), off.end());
+        if (out) res.idx.assign(out, out + total);
+        if (dout) res.dist.assign(dout, dout + total);
+        pn_free(out);
+        pn_free(dout);
+        return res;
+    }
 };
 
 // VantagePointTree (src/vantage_point_tree.rs:13-98): the reference's second index answers 1-NN only and returns the

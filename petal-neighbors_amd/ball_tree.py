@@ -203,6 +203,68 @@ class BallTree:
             raise ValueError("queries must be 2-D")
         return a
 
+    # One radius per query (``pn_query_radii_*``): the batch-shaped radius methods take, for ``distance`` / ``r``, a scalar
+    # or a 1-D array of one radius per query (self-queries: per indexed row).  A scalar goes to the scalar entry points.
+    def _radii(self, r, count):
+        """None for a scalar radius, else the ``count`` radii as a contiguous array of the tree's dtype."""
+        if np.ndim(r) == 0:
+            return None
+        if isinstance(r, np.ndarray) and r.dtype != self.dtype:
+            raise ValueError(f"radii must have the tree's dtype {self.dtype}, not {r.dtype}")
+        a = np.ascontiguousarray(r, dtype=self.dtype)
+        if a.ndim != 1:
+            raise ValueError("radii must be a scalar or 1-D")
+        if a.shape[0] != count:
+            raise ValueError(f"{a.shape[0]} radii for {count} queries")
+        return a
+
+    def _radii_device(self, r, count, dev):
+        """None for a scalar radius, else ``r`` checked: ``count`` radii, a contiguous 1-D CUDA tensor of the tree's dtype
+        on device ``dev`` (the call only enqueues work: the tensor is read later, so no temporary copy is made here)."""
+        if np.ndim(r) == 0:  # (a tensor answers with its own .ndim: nothing is copied)
+            return None
+        import torch
+        tdt = torch.float32 if self._sfx == "f32" else torch.float64
+        if not isinstance(r, torch.Tensor) or not r.is_cuda or r.dtype != tdt:
+            raise ValueError("radii must be a scalar or a CUDA tensor of the tree's element type")
+        if r.dim() != 1:
+            raise ValueError("radii must be a scalar or 1-D")
+        if r.shape[0] != count:
+            raise ValueError(f"{r.shape[0]} radii for {count} queries")
+        if r.device != dev:
+            raise ValueError(f"radii are on {r.device}, the queries / the index on {dev}")
+        if count > 1 and r.stride(0) != 1:
+            raise ValueError("radii must be contiguous")
+        return r
+
+    def _csr_out(self, offsets, out_i, out_d, with_distance):
+        """Copies of the library-allocated CSR lists (freed by the caller)."""
+        total = int(offsets[-1])
+        idx = np.empty(0, dtype=np.uint64)
+        dist = np.empty(0, dtype=self.dtype) if with_distance else None
+        if total:
+            idx = np.frombuffer((C.c_uint64 * total).from_address(out_i.value), dtype=np.uint64).copy()
+            if with_distance:
+                ct = C.c_float if self._sfx == "f32" else C.c_double
+                dist = np.frombuffer((ct * total).from_address(out_d.value), dtype=self.dtype).copy()
+        return idx, dist
+
+    def _query_radii(self, a, radii, with_distance, sort):
+        nq, qc = a.shape
+        offsets = np.zeros(nq + 1, dtype=np.uint64)
+        out_i, out_d = C.c_void_p(0), C.c_void_p(0)
+        fn = getattr(_lib.lib(), f"pn_query_radii_{self._sfx}")
+        try:
+            check(fn(self._h, a.ctypes.data, nq, qc, max(qc, 1), radii.ctypes.data if nq else None,
+                     _lib.PN_RADIUS_SORTED if sort else 0, offsets.ctypes.data, C.byref(out_i),
+                     C.byref(out_d) if with_distance else None))
+            idx, dist = self._csr_out(offsets, out_i, out_d, with_distance)
+        finally:
+            for p in (out_i, out_d):
+                if p.value:
+                    _lib.lib().pn_free(p)
+        return offsets, idx, dist
+
     def query_batch(self, queries, k: int):
         """k-NN for every row of ``queries``: (nq, min(k, n)) indices (uint64) and distances."""
         a = self._queries(queries, False)
@@ -231,9 +293,13 @@ class BallTree:
         return int(idx[0]), dist[0]
 
     def query_radius_batch(self, queries, distance):
-        """CSR (offsets[nq+1], indices) of ``{ i : dist(q, p_i) < distance }``, ascending per query."""
+        """CSR (offsets[nq+1], indices) of ``{ i : dist(q, p_i) < distance }``, ascending per query.  ``distance``: a
+        scalar, or a 1-D array of nq radii -- list q is then the scalar call's for query q with ``distance[q]``."""
         a = self._queries(queries, False)
         nq, qc = a.shape
+        radii = self._radii(distance, nq)
+        if radii is not None:
+            return self._query_radii(a, radii, False, False)[:2]
         offsets = np.zeros(nq + 1, dtype=np.uint64)
         out = C.c_void_p(0)
         r = C.c_float(distance) if self._sfx == "f32" else C.c_double(distance)
@@ -260,9 +326,12 @@ class BallTree:
     def query_radius_with_distance_batch(self, queries, distance, sort: bool = False):
         """``query_radius_batch`` plus each neighbour's distance (``pn_query_radius_with_distance_*``):
         ``(offsets uint64 [nq+1], idx uint64, dist)``.  The lists are ascending by index, or by (distance, index) --
-        nearest first, the k-NN order -- with ``sort=True``."""
+        nearest first, the k-NN order -- with ``sort=True``.  ``distance``: a scalar, or a 1-D array of nq radii."""
         a = self._queries(queries, False)
         nq, qc = a.shape
+        radii = self._radii(distance, nq)
+        if radii is not None:
+            return self._query_radii(a, radii, True, sort)
         offsets = np.zeros(nq + 1, dtype=np.uint64)
         out_i, out_d = C.c_void_p(0), C.c_void_p(0)
         r = C.c_float(distance) if self._sfx == "f32" else C.c_double(distance)
@@ -310,6 +379,13 @@ class BallTree:
         idx = out_idx if out_idx is not None else torch.empty(max(int(capacity), 1), dtype=torch.int64, device=dev)
         tot = out_total if out_total is not None else torch.empty(1, dtype=torch.int64, device=dev)
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        radii = self._radii_device(distance, nq, dev)
+        if radii is not None:  # one radius per query
+            fn = getattr(_lib.lib(), f"pn_query_radii_device_{self._sfx}")
+            check(fn(self._h, queries.data_ptr() if nq * qc else None, nq, qc, queries.stride(0) if nq > 1 else max(qc, 1),
+                     radii.data_ptr() if nq else None, 0, offs.data_ptr(), idx.data_ptr(), None, int(capacity),
+                     tot.data_ptr(), C.c_void_p(st)))
+            return offs, idx, tot
         r = C.c_float(distance) if self._sfx == "f32" else C.c_double(distance)
         fn = getattr(_lib.lib(), f"pn_query_radius_device_{self._sfx}")
         check(fn(self._h, queries.data_ptr() if nq * qc else None, nq, qc, queries.stride(0) if nq > 1 else max(qc, 1), r,
@@ -340,8 +416,15 @@ class BallTree:
         if dist.dtype != tdt or idx.numel() < int(capacity) or dist.numel() < int(capacity) or offs.numel() < nq + 1:
             raise ValueError("output tensors are too small or of the wrong type")
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        r = C.c_float(distance) if self._sfx == "f32" else C.c_double(distance)
         flags = _lib.PN_RADIUS_SORTED if sort else 0
+        radii = self._radii_device(distance, nq, dev)
+        if radii is not None:  # one radius per query
+            fn = getattr(_lib.lib(), f"pn_query_radii_device_{self._sfx}")
+            check(fn(self._h, queries.data_ptr() if nq * qc else None, nq, qc, queries.stride(0) if nq > 1 else max(qc, 1),
+                     radii.data_ptr() if nq else None, flags, offs.data_ptr(), idx.data_ptr(), dist.data_ptr(),
+                     int(capacity), tot.data_ptr(), C.c_void_p(st)))
+            return offs, idx, dist, tot
+        r = C.c_float(distance) if self._sfx == "f32" else C.c_double(distance)
         fn = getattr(_lib.lib(), f"pn_query_radius_with_distance_device_{self._sfx}")
         check(fn(self._h, queries.data_ptr() if nq * qc else None, nq, qc, queries.stride(0) if nq > 1 else max(qc, 1), r,
                  flags, offs.data_ptr(), idx.data_ptr(), dist.data_ptr(), int(capacity), tot.data_ptr(), C.c_void_p(st)))
@@ -413,13 +496,19 @@ class BallTree:
     def query_radius_self(self, r, with_distance: bool = False, sort: bool = False, include_self: bool = False):
         """``{ j != i : distance(p_i, p_j) < r }`` for every indexed row i, as CSR: ``(offsets uint64 [n+1], idx uint64,
         dist or None)``; lists ascending by index, or by (distance, index) with ``sort=True`` (needs ``with_distance``).
-        ``include_self=True`` keeps row i wherever its distance to itself is below r."""
+        ``include_self=True`` keeps row i wherever its distance to itself is below r.  ``r``: a scalar, or a 1-D array of
+        n radii, row i's own (``pn_query_radii_self_*``)."""
         if sort and not with_distance:
             raise ValueError("sort=True needs with_distance=True")
+        radii = self._radii(r, self._n)
         offsets = np.zeros(self._n + 1, dtype=np.uint64)
         out_i, out_d = C.c_void_p(0), C.c_void_p(0)
-        rr = C.c_float(r) if self._sfx == "f32" else C.c_double(r)
-        fn = getattr(_lib.lib(), f"pn_query_radius_self_{self._sfx}")
+        if radii is not None:
+            rr = radii.ctypes.data
+            fn = getattr(_lib.lib(), f"pn_query_radii_self_{self._sfx}")
+        else:
+            rr = C.c_float(r) if self._sfx == "f32" else C.c_double(r)
+            fn = getattr(_lib.lib(), f"pn_query_radius_self_{self._sfx}")
         try:
             check(fn(self._h, rr, self._self_flags(include_self, sort), offsets.ctypes.data, C.byref(out_i),
                      C.byref(out_d) if with_distance else None))
@@ -441,7 +530,8 @@ class BallTree:
                                  include_self: bool = False, out_offsets=None, out_idx=None, out_dist=None, out_total=None,
                                  stream=None):
         """``query_radius_self`` in HBM with the capacity contract of ``query_radius_with_distance_device``: CUDA tensors
-        ``(offsets int64 [n+1], idx int64 [capacity], dist [capacity] or None, total int64 [1])``."""
+        ``(offsets int64 [n+1], idx int64 [capacity], dist [capacity] or None, total int64 [1])``.  ``r``: a scalar, or a
+        1-D CUDA tensor of n radii of the tree's element type."""
         import torch
         tdt = torch.float32 if self._sfx == "f32" else torch.float64
         if int(capacity) < 0:
@@ -449,6 +539,7 @@ class BallTree:
         if sort and not with_distance:
             raise ValueError("sort=True needs with_distance=True")
         dev = torch.device("cuda", self.device)
+        radii = self._radii_device(r, self._n, dev)
         cap = max(int(capacity), 1)
         offs = out_offsets if out_offsets is not None else torch.empty(self._n + 1, dtype=torch.int64, device=dev)
         idx = out_idx if out_idx is not None else torch.empty(cap, dtype=torch.int64, device=dev)
@@ -461,8 +552,12 @@ class BallTree:
         if idx.numel() < int(capacity) or offs.numel() < self._n + 1:
             raise ValueError("output tensors are too small")
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        rr = C.c_float(r) if self._sfx == "f32" else C.c_double(r)
-        fn = getattr(_lib.lib(), f"pn_query_radius_self_device_{self._sfx}")
+        if radii is not None:
+            rr = radii.data_ptr()
+            fn = getattr(_lib.lib(), f"pn_query_radii_self_device_{self._sfx}")
+        else:
+            rr = C.c_float(r) if self._sfx == "f32" else C.c_double(r)
+            fn = getattr(_lib.lib(), f"pn_query_radius_self_device_{self._sfx}")
         check(fn(self._h, rr, self._self_flags(include_self, sort), offs.data_ptr(), idx.data_ptr(),
                  dist.data_ptr() if dist is not None else None, int(capacity), tot.data_ptr(), C.c_void_p(st)))
         return offs, idx, dist, tot

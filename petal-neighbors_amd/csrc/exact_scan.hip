@@ -329,7 +329,10 @@ __global__ __launch_bounds__(256) void exact_radius_kernel(
     const T *__restrict__ P, size_t n, int dim, size_t ldp, const T *__restrict__ Q, int nq, size_t ldq, T r,
     size_t seg_len, int nseg, uint32_t *__restrict__ counts, const uint64_t *__restrict__ offsets,
     uint64_t *__restrict__ fill, uint64_t index_base, const T *__restrict__ pnorm, const T *__restrict__ qnorm,
-    const uint32_t *__restrict__ qsel, const uint32_t *__restrict__ nq_dev, uint64_t capacity, T *__restrict__ fill_dist) {
+    const uint32_t *__restrict__ qsel, const uint32_t *__restrict__ nq_dev, uint64_t capacity, T *__restrict__ fill_dist,
+    const T *__restrict__ radii) {
+    // radii (nullable; pn_query_radii_*): query q is compared with radii[q] -- a listed query with radii[qsel[r]], as its
+    // norm is qnorm[qsel[r]] -- instead of r; the comparison itself (strict, NaN never matches) is the scalar's
     // fill_dist (WD: FILL with distances): each written row's distance, the d it was compared by, at the same position
     // (a template flag: the index-only fill keeps its registers)
     // qsel / nq_dev (nullable; the device-resident entry point, pn_query_radius_device_*): query r of the launch is row
@@ -363,6 +366,12 @@ __global__ __launch_bounds__(256) void exact_radius_kernel(
         const size_t q = q0 + qb + a;
         obase[a] = (FILL && q < (size_t)nq) ? offsets[q * nseg + seg] : 0;
     }
+    T r4[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const size_t q = q0 + qb + a;
+        r4[a] = (radii && q < (size_t)nq) ? radii[qsel_t ? qsel_t[qb + a] : q] : r;
+    }
     bool first = true;
     for (size_t p0 = p_begin; p0 < p_end; p0 += kTileP) {
         T acc[4][4];
@@ -387,7 +396,7 @@ __global__ __launch_bounds__(256) void exact_radius_kernel(
             for (int b = 0; b < 4; ++b) {
                 const bool v = qv && (p0 + pb + b) < p_end;
                 const T d = COS ? (T)1 - acc[a][b] / (qn4[a] * pn4[b]) : pn_sqrt(acc[a][b]);
-                if (v && d < r) m |= 1u << b;  // NaN distances never match
+                if (v && d < r4[a]) m |= 1u << b;  // NaN distances never match
             }
             mask[a] = m;
             anyp |= m != 0;
@@ -435,11 +444,11 @@ static hipError_t launch_exact_radius(const T *P, size_t n, int dim, size_t ldp,
                                       T r, size_t seg_len, int nseg, uint32_t *counts, const uint64_t *offsets,
                                       uint64_t *fill, uint64_t index_base, const T *pnorm, const T *qnorm,
                                       hipStream_t s, const uint32_t *qsel = nullptr, const uint32_t *nq_dev = nullptr,
-                                      uint64_t capacity = ~0ull, T *fill_dist = nullptr) {
+                                      uint64_t capacity = ~0ull, T *fill_dist = nullptr, const T *radii = nullptr) {
     dim3 grid((unsigned)(round_up((size_t)nq, kTileQ) / kTileQ), (unsigned)nseg), block(256);
 #define PN_RAD(FF, CC, WW)                                                                                          \
     hipLaunchKernelGGL((exact_radius_kernel<T, FF, CC, WW>), grid, block, 0, s, P, n, dim, ldp, Q, nq, ldq, r, seg_len, \
-                       nseg, counts, offsets, fill, index_base, pnorm, qnorm, qsel, nq_dev, capacity, fill_dist)
+                       nseg, counts, offsets, fill, index_base, pnorm, qnorm, qsel, nq_dev, capacity, fill_dist, radii)
     if (fill && fill_dist) {
         if (pnorm) PN_RAD(true, true, true); else PN_RAD(true, false, true);
     } else if (fill) {
@@ -454,17 +463,17 @@ hipError_t launch_exact_radius_f32(const float *P, size_t n, int dim, size_t ldp
                                    size_t ldq, float r, size_t seg_len, int nseg, uint32_t *counts,
                                    const uint64_t *offsets, uint64_t *fill, uint64_t index_base, const float *pnorm,
                                    const float *qnorm, hipStream_t s, const uint32_t *qsel, const uint32_t *nq_dev,
-                                   uint64_t capacity, float *fill_dist) {
+                                   uint64_t capacity, float *fill_dist, const float *radii) {
     return launch_exact_radius<float>(P, n, dim, ldp, Q, nq, ldq, r, seg_len, nseg, counts, offsets, fill,
-                                      index_base, pnorm, qnorm, s, qsel, nq_dev, capacity, fill_dist);
+                                      index_base, pnorm, qnorm, s, qsel, nq_dev, capacity, fill_dist, radii);
 }
 hipError_t launch_exact_radius_f64(const double *P, size_t n, int dim, size_t ldp, const double *Q, int nq,
                                    size_t ldq, double r, size_t seg_len, int nseg, uint32_t *counts,
                                    const uint64_t *offsets, uint64_t *fill, uint64_t index_base, const double *pnorm,
                                    const double *qnorm, hipStream_t s, const uint32_t *qsel, const uint32_t *nq_dev,
-                                   uint64_t capacity, double *fill_dist) {
+                                   uint64_t capacity, double *fill_dist, const double *radii) {
     return launch_exact_radius<double>(P, n, dim, ldp, Q, nq, ldq, r, seg_len, nseg, counts, offsets, fill,
-                                       index_base, pnorm, qnorm, s, qsel, nq_dev, capacity, fill_dist);
+                                       index_base, pnorm, qnorm, s, qsel, nq_dev, capacity, fill_dist, radii);
 }
 
 // ---------------------------------------------------------------------------

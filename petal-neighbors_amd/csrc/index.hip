@@ -138,6 +138,7 @@ struct Workspace {
     DevBuf w_q, w_qnorm, w_qnrm, w_keys, w_idx, w_cnt, w_tau, w_flags, w_sel, w_misc, w2_keys, w2_idx, w2_cnt, w2_tau, w_lo;
     DevBuf w_bq, w_qn, w_qbad, w_gq, w_gqn, w_gidx, w_gdist, w_gsel, w_seed, w_qstat, w_lists;  // bf16 tier, second tier
     DevBuf w_hq, w_hidx, w_hdist;  // staging of the host entry points (queries up, results down)
+    DevBuf w_hrad;                 // pn_query_radii_*: the host entry points' radii, uploaded
     DevBuf w_fparts;               // second tier, many-segment path: per-group partial results
     DevBuf w_rpos, w_rfin, w_rcx, w_rox, w_rscan;  // pn_query_radius_device_*: list positions, counts, per-segment counts / offsets, scan scratch
     DevBuf w_rkd;  // pn_query_radius_with_distance_*: the filter tier's kept rows' distances ([2][nq][kept_stride])
@@ -171,7 +172,7 @@ struct Workspace {
     hipEvent_t done = nullptr;
     hipStream_t last_stream = nullptr;
     bool in_flight = false;
-    DevBuf *all[51] = {&w_sf_idx, &w_sf_dist, &w_sf_off, &w_sf_coff, &w_sf_flag, &w_sf_cnt, &w_sf_scan, &w_sf_hoff, &w_cs_hoff, &w_rkd, &w_cs_nch, &w_cs_off, &w_cs_scan, &w_cs_idx, &w_cs_dist, &w_gqn, &w_rpos, &w_rfin, &w_rcx, &w_rox, &w_rscan, &w_q, &w_qnorm, &w_qnrm, &w_keys, &w_idx, &w_cnt, &w_tau, &w_flags, &w_sel, &w_misc, &w2_keys, &w2_idx,
+    DevBuf *all[52] = {&w_hrad, &w_sf_idx, &w_sf_dist, &w_sf_off, &w_sf_coff, &w_sf_flag, &w_sf_cnt, &w_sf_scan, &w_sf_hoff, &w_cs_hoff, &w_rkd, &w_cs_nch, &w_cs_off, &w_cs_scan, &w_cs_idx, &w_cs_dist, &w_gqn, &w_rpos, &w_rfin, &w_rcx, &w_rox, &w_rscan, &w_q, &w_qnorm, &w_qnrm, &w_keys, &w_idx, &w_cnt, &w_tau, &w_flags, &w_sel, &w_misc, &w2_keys, &w2_idx,
                        &w2_cnt, &w2_tau, &w_lo, &w_bq, &w_qn, &w_qbad, &w_gq, &w_gidx, &w_gdist, &w_gsel, &w_seed,
                        &w_qstat, &w_lists, &w_hq, &w_hidx, &w_hdist, &w_fparts, &w_pcnt};
     std::vector<void *> retired;  // outgrown allocations, freed once `done` has passed (DevBuf::ensure)
@@ -2547,18 +2548,20 @@ template <> struct RadOps<float> {
     static hipError_t run(const float *P, size_t n, int dim, size_t ldp, const float *Q, int nq, size_t ldq, float r,
                           size_t seg_len, int nseg, uint32_t *counts, const uint64_t *offs, uint64_t *fill,
                           uint64_t base, const float *pn, const float *qn, hipStream_t s, const uint32_t *qsel = nullptr,
-                          const uint32_t *nq_dev = nullptr, uint64_t capacity = ~0ull, float *fill_dist = nullptr) {
+                          const uint32_t *nq_dev = nullptr, uint64_t capacity = ~0ull, float *fill_dist = nullptr,
+                          const float *radii = nullptr) {
         return launch_exact_radius_f32(P, n, dim, ldp, Q, nq, ldq, r, seg_len, nseg, counts, offs, fill, base, pn, qn, s, qsel,
-                                       nq_dev, capacity, fill_dist);
+                                       nq_dev, capacity, fill_dist, radii);
     }
 };
 template <> struct RadOps<double> {
     static hipError_t run(const double *P, size_t n, int dim, size_t ldp, const double *Q, int nq, size_t ldq, double r,
                           size_t seg_len, int nseg, uint32_t *counts, const uint64_t *offs, uint64_t *fill,
                           uint64_t base, const double *pn, const double *qn, hipStream_t s, const uint32_t *qsel = nullptr,
-                          const uint32_t *nq_dev = nullptr, uint64_t capacity = ~0ull, double *fill_dist = nullptr) {
+                          const uint32_t *nq_dev = nullptr, uint64_t capacity = ~0ull, double *fill_dist = nullptr,
+                          const double *radii = nullptr) {
         return launch_exact_radius_f64(P, n, dim, ldp, Q, nq, ldq, r, seg_len, nseg, counts, offs, fill, base, pn, qn, s, qsel,
-                                       nq_dev, capacity, fill_dist);
+                                       nq_dev, capacity, fill_dist, radii);
     }
 };
 
@@ -2857,13 +2860,16 @@ static int radius_finish(const pn_index *ix, Workspace &ws, const T *Qp, size_t 
 // (enqueue only: the filter against each query's fixed bound and the exact check of the survivors.  Leaves, per query, the
 // kept rows in w_keys [nq][*kept_stride] (ascending), their number in w_flags, an overflow flag in w_sel, w_qbad for
 // queries the filter cannot serve, d_misc[0] / [1] = how many of either.  *enq = false: the radius cannot be served.)
+// radii (nullable, [nq] in HBM; pn_query_radii_*): one radius per query instead of `radius`.  Whether a radius can be
+// served is then decided per query on the device (radii_tau.hip): a query whose radius cannot is flagged in w_qbad and
+// its threshold admits no row.
 template <typename T>
 static int radius_bf16_enqueue(const pn_index *ix, Workspace &ws, int level, const T *Qp, size_t nq, size_t nq_pad, T radius,
                                size_t *kept_stride_out, bool *enq, hipStream_t s, const T *qnorm = nullptr,
-                               bool want_dist = false) {
+                               bool want_dist = false, const T *radii = nullptr) {
     *enq = false;
     const bool cosine = ix->metric == 1;  // (round 4: the filter over the normalised rows, Cosine::distance check)
-    if (cosine && (!qnorm || !ix->d_cnorm || !(radius < (T)1))) return PN_OK;  // (r >= 1: half the sphere -- exact scan)
+    if (cosine && (!qnorm || !ix->d_cnorm || (!radii && !(radius < (T)1)))) return PN_OK;  // (r >= 1: half the sphere -- exact scan)
     const int cap = 256;  // up to 224 rows within the radius per (segment, query) before the call overflows
     const size_t q_tiles = nq_pad / 256, r_tiles = (ix->n + 63) / 64;
     size_t n_wg = (size_t)ix->n_cu * 2;
@@ -2894,7 +2900,7 @@ static int radius_bf16_enqueue(const pn_index *ix, Workspace &ws, int level, con
                          ? ((double)radius * (double)radius + 1e-37) / (1.0 - (double)(ix->dim + 4) * 5.9604644775390625e-08)
                          : ((double)radius * (double)radius * (1.0 + 8.881784197001252e-16) + 1e-300) /
                                (1.0 - (double)(ix->dim + 4) * 1.1102230246251565e-16);  // (f64: r^2 itself is rounded)
-    if (!(t < 1e37)) return PN_OK;  // let the exact engine decide
+    if (!radii && !(t < 1e37)) return PN_OK;  // let the exact engine decide
     PNCHK(ws.w_bq.ensure(bf16_query_bytes(nq_pad, (int)ix->dim, ix->bf16_ci)));
     PNCHK(ws.w_qn.ensure(nq_pad * sizeof(double)));
     PNCHK(ws.w_qbad.ensure(nq_pad * sizeof(uint32_t)));
@@ -2921,8 +2927,11 @@ static int radius_bf16_enqueue(const pn_index *ix, Workspace &ws, int level, con
         HIPCHK(launch_bf16_pack_queries(Qp, ix->d_mu, nq, nq_pad, (int)ix->dim, ix->ld, ws.w_bq.p, (double *)ws.w_qn.p,
                                         (uint32_t *)ws.w_qbad.p, ix->bf16_ci, ix->bf16_bmax, ix->bf16_dmax, s));
     PNCHK(ws.w_gsel.ensure(nq_pad * sizeof(uint32_t)));
+    if (radii)  // (before the flags are counted: it adds the queries whose radius the filter cannot serve)
+        HIPCHK(launch_bf16_radii_tau<T>((const double *)ws.w_qn.p, radii, nq, nq_pad, (int)ix->dim, cosine,
+                                        (uint32_t *)ws.w_seed.p, (uint32_t *)ws.w_qbad.p, s));
     HIPCHK(launch_compact_flags((const uint32_t *)ws.w_qbad.p, (int)nq, (uint32_t *)ws.w_gsel.p, d_misc + 1, s));
-    HIPCHK(launch_bf16_radius_tau((const double *)ws.w_qn.p, nq_pad, t, (uint32_t *)ws.w_seed.p, s));
+    if (!radii) HIPCHK(launch_bf16_radius_tau((const double *)ws.w_qn.p, nq_pad, t, (uint32_t *)ws.w_seed.p, s));
     CandBuf cb{ws.w_idx.p, (uint32_t *)ws.w_idx.p + 1, (uint32_t *)ws.w_cnt.p, ws.w_tau.p, nq_pad, nseg, cap, 2};
     // PN_OPT_PROFILE: the filter launch between two events of the workspace (the radius entry points wait for their
     // stream anyway: the bracket is resolved in radius_finish's shadow, below)
@@ -2945,7 +2954,7 @@ static int radius_bf16_enqueue(const pn_index *ix, Workspace &ws, int level, con
                                   (const T *)ix->d_pts, ix->ld, Qp, (int)nq, (int)ix->dim, radius,
                                   (uint32_t *)ws.w_keys.p, (uint32_t *)ws.w_flags.p, d_misc, 2,
                                   (uint32_t *)ws.w_sel.p, s, cosine ? (const T *)ix->d_cnorm : nullptr,
-                                  cosine ? qnorm : nullptr, want_dist ? (T *)ws.w_rkd.p : nullptr));
+                                  cosine ? qnorm : nullptr, want_dist ? (T *)ws.w_rkd.p : nullptr, radii));
     *kept_stride_out = kept_stride;
     *enq = true;
     return PN_OK;
@@ -3167,11 +3176,13 @@ extern "C" int pn_query_radius_with_distance_f64(const pn_index *ix, const doubl
 template <typename T>
 static int radius_device_enqueue(const pn_index *ix, Workspace &ws, const T *d_q, size_t nq, size_t q_cols, size_t q_stride,
                                  T radius, uint64_t *d_offsets, uint64_t *d_idx, size_t capacity, uint64_t *d_total,
-                                 hipStream_t s, T *d_dist, unsigned flags, bool count_queries = true);
+                                 hipStream_t s, T *d_dist, unsigned flags, bool count_queries = true,
+                                 const T *d_radii = nullptr, bool add_listed = false);
 template <typename T>
 static int radius_device_impl(const pn_index *ix, const T *d_q, size_t nq, size_t q_cols, size_t q_stride, T radius,
                               uint64_t *d_offsets, uint64_t *d_idx, size_t capacity, uint64_t *d_total, hipStream_t s,
-                              bool with_dist = false, T *d_dist = nullptr, unsigned flags = 0) {
+                              bool with_dist = false, T *d_dist = nullptr, unsigned flags = 0,
+                              const T *d_radii = nullptr) {
     if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
     if (ix->elem_bytes != (int)sizeof(T)) return fail(PN_ERR_INVALID, "index element type mismatch");
     if (!d_offsets || (!d_idx && capacity)) return fail(PN_ERR_INVALID, "output buffer is NULL");
@@ -3191,14 +3202,20 @@ static int radius_device_impl(const pn_index *ix, const T *d_q, size_t nq, size_
     lease.s = s;
     PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
     return radius_device_enqueue<T>(ix, *lease.ws, d_q, nq, q_cols, q_stride, radius, d_offsets, d_idx, capacity, d_total,
-                                    s, d_dist, flags);
+                                    s, d_dist, flags, true, d_radii, d_radii != nullptr);
 }
 // the pipeline of radius_device_impl in a workspace the caller holds (also the self-queries' inner call); nq >= 1,
 // arguments checked.  count_queries: add nq to pn_stats.queries
+// d_radii (nullable, [nq] in HBM; pn_query_radii_*): query q's radius is d_radii[q], `radius` is not looked at, and
+// nothing about the radii is decided here: the first tier is entered whenever the index and the queries' shape allow it,
+// the threshold kernel flags the queries whose own radius it cannot serve, and the exact scan compares each listed query
+// with its own radius.  add_listed: the number of listed queries is added to the index's device counter of fallback
+// queries (d_stats[0]) -- by a kernel, nothing is read back; a call that enters no first tier lists nothing and adds nothing
 template <typename T>
 static int radius_device_enqueue(const pn_index *ix, Workspace &ws, const T *d_q, size_t nq, size_t q_cols, size_t q_stride,
                                  T radius, uint64_t *d_offsets, uint64_t *d_idx, size_t capacity, uint64_t *d_total,
-                                 hipStream_t s, T *d_dist, unsigned flags, bool count_queries) {
+                                 hipStream_t s, T *d_dist, unsigned flags, bool count_queries, const T *d_radii,
+                                 bool add_listed) {
     int level;
     {
         std::lock_guard<std::mutex> lk(ix->sh.mu);
@@ -3221,11 +3238,11 @@ static int radius_device_enqueue(const pn_index *ix, Workspace &ws, const T *d_q
     // ---- first tier (enqueue only)
     bool filtered = false;
     size_t kept_stride = 0;
-    const bool finite_pos = radius > (T)0 && radius < (T)INFINITY;
+    const bool finite_pos = d_radii || (radius > (T)0 && radius < (T)INFINITY);  // (an array: decided per query)
     if ((ix->metric == 0 || q_cols == ix->dim) && ix->bf16_ok && dim_eff == ix->dim && finite_pos && level < 2 &&
         (ix->engine == PN_ENGINE_BF16 || (ix->engine == PN_ENGINE_AUTO && ix->n >= 4096 && ix->dim >= 8)))
         PNCHK(radius_bf16_enqueue<T>(ix, ws, level, (const T *)Qp, nq, nq_pad, radius, &kept_stride, &filtered, s, qnorm,
-                                     d_dist != nullptr));
+                                     d_dist != nullptr, d_radii));
     PNCHK(ws.w_misc.ensure(64));
     uint32_t *d_misc = (uint32_t *)ws.w_misc.p;  // [4]: the number of listed queries
     const uint32_t *d_sel = nullptr, *d_pos = nullptr, *d_nsel = nullptr, *d_nkept = nullptr;
@@ -3239,6 +3256,7 @@ static int radius_device_enqueue(const pn_index *ix, Workspace &ws, const T *d_q
         d_pos = (const uint32_t *)ws.w_rpos.p;
         d_nsel = d_misc + 4;
         d_nkept = (const uint32_t *)ws.w_flags.p;
+        if (add_listed && ix->d_stats) HIPCHK(launch_radii_add_listed(d_nsel, ix->d_stats, s));
     }
     // ---- exact two-pass scan for the listed queries (all of them without a first tier), driven by the device-side list
     const size_t q_tiles_r = round_up(nq, (size_t)kTileQ) / kTileQ;
@@ -3250,7 +3268,8 @@ static int radius_device_enqueue(const pn_index *ix, Workspace &ws, const T *d_q
     PNCHK(ws.w_rscan.ensure((nq / 4096 + 2) * sizeof(uint64_t)));
     const T *pn = qnorm ? (const T *)ix->d_cnorm : nullptr;
     HIPCHK(RadOps<T>::run((const T *)ix->d_pts, ix->n, (int)dim_eff, ix->ld, Qp, (int)nq, ix->ld, radius, pl.seg_len, pl.nseg,
-                          (uint32_t *)ws.w_rcx.p, nullptr, nullptr, ix->index_base, pn, qnorm, s, d_sel, d_nsel, ~0ull));
+                          (uint32_t *)ws.w_rcx.p, nullptr, nullptr, ix->index_base, pn, qnorm, s, d_sel, d_nsel, ~0ull,
+                          nullptr, d_radii));
     HIPCHK(launch_rad_counts(d_nkept, d_pos, (const uint32_t *)ws.w_rcx.p, pl.nseg, (int)nq, (uint32_t *)ws.w_rfin.p, s));
     HIPCHK(launch_exclusive_scan_u32((const uint32_t *)ws.w_rfin.p, nq, d_offsets, (uint64_t *)ws.w_rscan.p, d_total, s));
     HIPCHK(launch_rad_seg_offsets(d_offsets, d_sel, d_nsel, (int)nq, (const uint32_t *)ws.w_rcx.p, pl.nseg,
@@ -3259,7 +3278,7 @@ static int radius_device_enqueue(const pn_index *ix, Workspace &ws, const T *d_q
     if (capacity) {
         HIPCHK(RadOps<T>::run((const T *)ix->d_pts, ix->n, (int)dim_eff, ix->ld, Qp, (int)nq, ix->ld, radius, pl.seg_len,
                               pl.nseg, (uint32_t *)ws.w_rcx.p, (const uint64_t *)ws.w_rox.p, d_idx, ix->index_base, pn, qnorm,
-                              s, d_sel, d_nsel, (uint64_t)capacity, d_dist));
+                              s, d_sel, d_nsel, (uint64_t)capacity, d_dist, d_radii));
         if (filtered)
             HIPCHK(launch_radius_gather_cap((const uint32_t *)ws.w_keys.p, d_nkept, d_offsets, (int)nq, kept_stride,
                                             ix->index_base, d_idx, (uint64_t)capacity, s,
@@ -3417,7 +3436,7 @@ extern "C" int pn_query_self_device_f64(const pn_index *ix, size_t k, unsigned f
 template <typename T>
 static int radius_self_enqueue(const pn_index *ix, Workspace &ws, T radius, unsigned flags, uint64_t *d_offsets,
                                uint64_t *d_idx, T *d_dist, size_t capacity, uint64_t *d_total, hipStream_t s,
-                               bool count_queries) {
+                               bool count_queries, const T *d_radii = nullptr) {  // (d_radii: [n] in HBM, row i's own radius)
     const size_t n = ix->n;
     const bool exclude = !(flags & PN_SELF_INCLUDE);
     if (!capacity) d_dist = nullptr;  // (a pure count)
@@ -3451,13 +3470,16 @@ static int radius_self_enqueue(const pn_index *ix, Workspace &ws, T radius, unsi
     for (size_t r0 = 0; r0 < n; r0 += chunk) {
         const size_t nqc = n - r0 < chunk ? n - r0 : chunk;
         const T *rows = (const T *)ix->d_pts + r0 * ix->ld;
+        const T *rad = d_radii ? d_radii + r0 : nullptr;  // (the chunk's rows' radii)
         PNCHK(radius_device_enqueue<T>(ix, ws, rows, nqc, ix->dim, ix->ld, radius, in_off, in_idx, in_cap, nullptr, s,
-                                       in_dist, 0, count_queries));
+                                       in_dist, 0, count_queries, rad, rad && count_queries));
         const T *cn = cn_all ? cn_all + r0 : nullptr;
         if constexpr (sizeof(T) == 4)
-            HIPCHK(launch_radius_self_counts_f32(rows, nqc, (int)ix->dim, ix->ld, cn, radius, exclude, in_off, flag, cnt, bad, s));
+            HIPCHK(launch_radius_self_counts_f32(rows, nqc, (int)ix->dim, ix->ld, cn, radius, exclude, in_off, flag, cnt, bad, s,
+                                                 rad));
         else
-            HIPCHK(launch_radius_self_counts_f64(rows, nqc, (int)ix->dim, ix->ld, cn, radius, exclude, in_off, flag, cnt, bad, s));
+            HIPCHK(launch_radius_self_counts_f64(rows, nqc, (int)ix->dim, ix->ld, cn, radius, exclude, in_off, flag, cnt, bad, s,
+                                                 rad));
         HIPCHK(launch_exclusive_scan_u32(cnt, nqc, part, (uint64_t *)ws.w_sf_scan.p, nullptr, s));
         HIPCHK(launch_radius_self_place(part, nqc, d_offsets + r0, s));
         if (!capacity) continue;
@@ -3482,7 +3504,7 @@ static int radius_self_args(const pn_index *ix, unsigned flags, bool has_offsets
 }
 template <typename T>
 static int radius_self_device(const pn_index *ix, T radius, unsigned flags, uint64_t *d_offsets, uint64_t *d_idx, T *d_dist,
-                              size_t capacity, uint64_t *d_total, hipStream_t s) {
+                              size_t capacity, uint64_t *d_total, hipStream_t s, const T *d_radii = nullptr) {
     // (capacity 0 only counts: no list buffers needed)
     PNCHK(radius_self_args(ix, flags, d_offsets != nullptr, d_idx != nullptr || !capacity, d_dist != nullptr || !capacity,
                            (int)sizeof(T)));
@@ -3492,14 +3514,16 @@ static int radius_self_device(const pn_index *ix, T radius, unsigned flags, uint
     WsLease lease(ix);
     lease.s = s;
     PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
-    return radius_self_enqueue<T>(ix, *lease.ws, radius, flags, d_offsets, d_idx, d_dist, capacity, d_total, s, true);
+    return radius_self_enqueue<T>(ix, *lease.ws, radius, flags, d_offsets, d_idx, d_dist, capacity, d_total, s, true, d_radii);
 }
 // host outputs: a count-only pass, then one pass with the exact total into the workspace's staging buffers; the lists are
 // then allocated here (pn_free).  Both passes run the pipeline (the count is not kept between calls).
 template <typename T>
 static int radius_self_host(const pn_index *ix, T radius, unsigned flags, uint64_t *offsets, uint64_t **idx_out,
-                            T **dist_out) {
+                            T **dist_out, const T *radii = nullptr, bool per_row = false) {
+    // (per_row: pn_query_radii_self_* -- radii [n] on the host, uploaded once for both passes)
     PNCHK(radius_self_args(ix, flags, offsets != nullptr, idx_out != nullptr, dist_out != nullptr, (int)sizeof(T)));
+    if (per_row && !radii && ix->n) return fail(PN_ERR_INVALID, "radii is NULL");
     *idx_out = nullptr;
     if (dist_out) *dist_out = nullptr;
     const size_t n = ix->n;
@@ -3521,7 +3545,13 @@ static int radius_self_host(const pn_index *ix, T radius, unsigned flags, uint64
     };
     uint64_t total = 0;
     uint32_t bad = 0;
-    PNCHK(radius_self_enqueue<T>(ix, ws, radius, flags, d_off, nullptr, nullptr, 0, d_tot, s, true));
+    const T *d_radii = nullptr;
+    if (per_row) {
+        PNCHK(ws.w_hrad.ensure(n * sizeof(T)));
+        HIPCHK(hipMemcpyAsync(ws.w_hrad.p, radii, n * sizeof(T), hipMemcpyHostToDevice, s));
+        d_radii = (const T *)ws.w_hrad.p;
+    }
+    PNCHK(radius_self_enqueue<T>(ix, ws, radius, flags, d_off, nullptr, nullptr, 0, d_tot, s, true, d_radii));
     HIPCHK(hipMemcpyAsync(&total, d_tot, sizeof total, hipMemcpyDeviceToHost, s));
     PNCHK(bad_word(&bad));
     HIPCHK(hipStreamSynchronize(s));
@@ -3529,7 +3559,7 @@ static int radius_self_host(const pn_index *ix, T radius, unsigned flags, uint64
         PNCHK(ws.w_hidx.ensure(total * sizeof(uint64_t)));
         if (dist_out) PNCHK(ws.w_hdist.ensure(total * sizeof(T)));
         PNCHK(radius_self_enqueue<T>(ix, ws, radius, flags, d_off, (uint64_t *)ws.w_hidx.p,
-                                     dist_out ? (T *)ws.w_hdist.p : nullptr, total, nullptr, s, false));
+                                     dist_out ? (T *)ws.w_hdist.p : nullptr, total, nullptr, s, false, d_radii));
         uint32_t bad2 = 0;
         PNCHK(bad_word(&bad2));
         HIPCHK(hipStreamSynchronize(s));
@@ -3577,6 +3607,144 @@ extern "C" int pn_query_radius_self_device_f64(const pn_index *ix, double radius
                                                uint64_t *d_idx, double *d_dist, size_t capacity, uint64_t *d_total,
                                                void *stream) {
     return radius_self_device<double>(ix, radius, flags, d_offsets, d_idx, d_dist, capacity, d_total, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------
+// One radius per query: pn_query_radii_{,device_,self_,self_device_}{f32,f64}.  List q is the scalar entry point's list
+// for query q alone with radii[q].  Everything runs on the device pipeline above (radius_device_enqueue with d_radii): the
+// scalar host path's f32 MFMA radius tier and the one-launch path of small calls do not know about arrays.
+// ---------------------------------------------------------------------------
+// (argument checks, before any device is touched: flags, outputs, the radii, then the handle)
+static int radii_args(const pn_index *ix, unsigned flags, unsigned allowed, bool has_offsets, bool has_idx, bool has_dist,
+                      bool has_radii, int elem_bytes) {
+    if (flags & ~allowed) return fail(PN_ERR_INVALID, "unknown radius flags 0x%x", flags);
+    if (!has_offsets || !has_idx) return fail(PN_ERR_INVALID, "output buffer is NULL");
+    if ((flags & PN_RADIUS_SORTED) && !has_dist) return fail(PN_ERR_INVALID, "PN_RADIUS_SORTED needs the distance output");
+    if (!has_radii) return fail(PN_ERR_INVALID, "radii is NULL");
+    if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
+    if (ix->elem_bytes != elem_bytes) return fail(PN_ERR_INVALID, "index element type mismatch");
+    return PN_OK;
+}
+template <typename T>
+static int radii_device(const pn_index *ix, const T *d_q, size_t nq, size_t q_cols, size_t q_stride, const T *d_radii,
+                        unsigned flags, uint64_t *d_offsets, uint64_t *d_idx, T *d_dist, size_t capacity, uint64_t *d_total,
+                        hipStream_t s) {
+    PNCHK(radii_args(ix, flags, PN_RADIUS_SORTED, d_offsets != nullptr, d_idx != nullptr || !capacity,
+                     d_dist != nullptr || !capacity, d_radii != nullptr || !nq, (int)sizeof(T)));
+    return radius_device_impl<T>(ix, d_q, nq, q_cols, q_stride, (T)0, d_offsets, d_idx, capacity, d_total, s, false, d_dist,
+                                 flags, d_radii);
+}
+// host outputs, as radius_self_host: queries and radii up, a count-only pass, one pass with the exact total into the
+// workspace's staging buffers, lists down into arrays allocated here (pn_free)
+template <typename T>
+static int radii_host(const pn_index *ix, const T *q, size_t nq, size_t q_cols, ptrdiff_t q_stride, const T *radii,
+                      unsigned flags, uint64_t *offsets, uint64_t **idx_out, T **dist_out) {
+    PNCHK(radii_args(ix, flags, PN_RADIUS_SORTED, offsets != nullptr, idx_out != nullptr, dist_out != nullptr,
+                     radii != nullptr || !nq, (int)sizeof(T)));
+    *idx_out = nullptr;
+    if (dist_out) *dist_out = nullptr;
+    offsets[0] = 0;
+    if (nq == 0) return PN_OK;
+    if (!q && q_cols) return fail(PN_ERR_INVALID, "queries is NULL");
+    if (nq > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many queries in one call");
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
+    Workspace &ws = *lease.ws;
+    hipStream_t s = lease.s;
+    PNCHK(upload_rows_to<T>(q, nq, q_cols, q_stride, ws.w_hq, s));
+    PNCHK(ws.w_hrad.ensure(nq * sizeof(T)));
+    HIPCHK(hipMemcpyAsync(ws.w_hrad.p, radii, nq * sizeof(T), hipMemcpyHostToDevice, s));
+    PNCHK(ws.w_sf_hoff.ensure((nq + 2) * sizeof(uint64_t)));
+    const T *d_q = (const T *)ws.w_hq.p, *d_radii = (const T *)ws.w_hrad.p;
+    const size_t ldq = q_cols ? q_cols : 1;
+    uint64_t *d_off = (uint64_t *)ws.w_sf_hoff.p, *d_tot = d_off + nq + 1;
+    uint64_t total = 0;
+    // (pn_stats.queries is left alone, as by pn_query_radius_*; the listed queries are added once, by the counting pass)
+    PNCHK(radius_device_enqueue<T>(ix, ws, d_q, nq, q_cols, ldq, (T)0, d_off, nullptr, 0, d_tot, s, nullptr, flags, false,
+                                   d_radii, true));
+    HIPCHK(hipMemcpyAsync(&total, d_tot, sizeof total, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (total) {
+        PNCHK(ws.w_hidx.ensure(total * sizeof(uint64_t)));
+        if (dist_out) PNCHK(ws.w_hdist.ensure(total * sizeof(T)));
+        PNCHK(radius_device_enqueue<T>(ix, ws, d_q, nq, q_cols, ldq, (T)0, d_off, (uint64_t *)ws.w_hidx.p, total, nullptr, s,
+                                       dist_out ? (T *)ws.w_hdist.p : nullptr, flags, false, d_radii, false));
+    }
+    uint64_t *out = (uint64_t *)malloc((total ? total : 1) * sizeof(uint64_t));
+    T *dout = dist_out ? (T *)malloc((total ? total : 1) * sizeof(T)) : nullptr;
+    if (!out || (dist_out && !dout)) {
+        free(out);
+        free(dout);
+        (void)hipStreamSynchronize(s);
+        return fail(PN_ERR_NOMEM, "malloc(%llu results) failed", (unsigned long long)total);
+    }
+    hipError_t e = hipMemcpyAsync(offsets, d_off, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && total) e = hipMemcpyAsync(out, ws.w_hidx.p, total * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && total && dout) e = hipMemcpyAsync(dout, ws.w_hdist.p, total * sizeof(T), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        free(out);
+        free(dout);
+        return fail(PN_ERR_DEVICE, "copying the radius lists back: %s", hipGetErrorString(e));
+    }
+    *idx_out = out;
+    if (dist_out) *dist_out = dout;
+    std::lock_guard<std::mutex> lk(ix->sh.mu);
+    ix->sh.stats.radius_results += total;
+    return PN_OK;
+}
+template <typename T>
+static int radii_self_device(const pn_index *ix, const T *d_radii, unsigned flags, uint64_t *d_offsets, uint64_t *d_idx,
+                             T *d_dist, size_t capacity, uint64_t *d_total, hipStream_t s) {
+    PNCHK(radii_args(ix, flags, PN_RADIUS_SORTED | PN_SELF_INCLUDE, d_offsets != nullptr, d_idx != nullptr || !capacity,
+                     d_dist != nullptr || !capacity, d_radii != nullptr, (int)sizeof(T)));
+    return radius_self_device<T>(ix, (T)0, flags, d_offsets, d_idx, d_dist, capacity, d_total, s, d_radii);
+}
+extern "C" int pn_query_radii_f32(const pn_index *ix, const float *q, size_t nq, size_t q_cols, ptrdiff_t q_stride,
+                                  const float *radii, unsigned flags, uint64_t *offsets, uint64_t **idx_out,
+                                  float **dist_out) {
+    return radii_host<float>(ix, q, nq, q_cols, q_stride, radii, flags, offsets, idx_out, dist_out);
+}
+extern "C" int pn_query_radii_f64(const pn_index *ix, const double *q, size_t nq, size_t q_cols, ptrdiff_t q_stride,
+                                  const double *radii, unsigned flags, uint64_t *offsets, uint64_t **idx_out,
+                                  double **dist_out) {
+    return radii_host<double>(ix, q, nq, q_cols, q_stride, radii, flags, offsets, idx_out, dist_out);
+}
+extern "C" int pn_query_radii_device_f32(const pn_index *ix, const float *d_q, size_t nq, size_t q_cols, size_t q_stride,
+                                         const float *d_radii, unsigned flags, uint64_t *d_offsets, uint64_t *d_idx,
+                                         float *d_dist, size_t capacity, uint64_t *d_total, void *stream) {
+    return radii_device<float>(ix, d_q, nq, q_cols, q_stride, d_radii, flags, d_offsets, d_idx, d_dist, capacity, d_total,
+                               (hipStream_t)stream);
+}
+extern "C" int pn_query_radii_device_f64(const pn_index *ix, const double *d_q, size_t nq, size_t q_cols, size_t q_stride,
+                                         const double *d_radii, unsigned flags, uint64_t *d_offsets, uint64_t *d_idx,
+                                         double *d_dist, size_t capacity, uint64_t *d_total, void *stream) {
+    return radii_device<double>(ix, d_q, nq, q_cols, q_stride, d_radii, flags, d_offsets, d_idx, d_dist, capacity, d_total,
+                                (hipStream_t)stream);
+}
+extern "C" int pn_query_radii_self_f32(const pn_index *ix, const float *radii, unsigned flags, uint64_t *offsets,
+                                       uint64_t **idx_out, float **dist_out) {
+    PNCHK(radii_args(ix, flags, PN_RADIUS_SORTED | PN_SELF_INCLUDE, offsets != nullptr, idx_out != nullptr,
+                     dist_out != nullptr, radii != nullptr, 4));
+    return radius_self_host<float>(ix, 0.0f, flags, offsets, idx_out, dist_out, radii, true);
+}
+extern "C" int pn_query_radii_self_f64(const pn_index *ix, const double *radii, unsigned flags, uint64_t *offsets,
+                                       uint64_t **idx_out, double **dist_out) {
+    PNCHK(radii_args(ix, flags, PN_RADIUS_SORTED | PN_SELF_INCLUDE, offsets != nullptr, idx_out != nullptr,
+                     dist_out != nullptr, radii != nullptr, 8));
+    return radius_self_host<double>(ix, 0.0, flags, offsets, idx_out, dist_out, radii, true);
+}
+extern "C" int pn_query_radii_self_device_f32(const pn_index *ix, const float *d_radii, unsigned flags, uint64_t *d_offsets,
+                                              uint64_t *d_idx, float *d_dist, size_t capacity, uint64_t *d_total,
+                                              void *stream) {
+    return radii_self_device<float>(ix, d_radii, flags, d_offsets, d_idx, d_dist, capacity, d_total, (hipStream_t)stream);
+}
+extern "C" int pn_query_radii_self_device_f64(const pn_index *ix, const double *d_radii, unsigned flags, uint64_t *d_offsets,
+                                              uint64_t *d_idx, double *d_dist, size_t capacity, uint64_t *d_total,
+                                              void *stream) {
+    return radii_self_device<double>(ix, d_radii, flags, d_offsets, d_idx, d_dist, capacity, d_total, (hipStream_t)stream);
 }
 
 extern "C" void pn_free(void *p) { free(p); }

@@ -88,13 +88,13 @@ hipError_t launch_exact_radius_f32(const float *P, size_t n, int dim, size_t ldp
                                    const uint64_t *offsets, uint64_t *fill, uint64_t index_base, const float *pnorm,
                                    const float *qnorm, hipStream_t s, const uint32_t *qsel = nullptr,
                                    const uint32_t *nq_dev = nullptr, uint64_t capacity = ~0ull,
-                                   float *fill_dist = nullptr);
+                                   float *fill_dist = nullptr, const float *radii = nullptr);
 hipError_t launch_exact_radius_f64(const double *P, size_t n, int dim, size_t ldp, const double *Q, int nq,
                                    size_t ldq, double r, size_t seg_len, int nseg, uint32_t *counts,
                                    const uint64_t *offsets, uint64_t *fill, uint64_t index_base, const double *pnorm,
                                    const double *qnorm, hipStream_t s, const uint32_t *qsel = nullptr,
                                    const uint32_t *nq_dev = nullptr, uint64_t capacity = ~0ull,
-                                   double *fill_dist = nullptr);
+                                   double *fill_dist = nullptr, const double *radii = nullptr);
 // qsel / nq_dev (nullable): query r of the launch is row qsel[r] of Q, only the first *nq_dev listed queries exist (grid
 // sized for nq); counts / offsets indexed by r.  capacity: fill positions at or beyond it are not written.
 // fill_dist (nullable): the fill pass also writes each listed row's distance at its position
@@ -132,10 +132,10 @@ hipError_t launch_knn_self_exclude_f64(const uint64_t *in_idx, const double *in_
 // Euclidean); cnt[i] <- in_off[i + 1] - in_off[i] - flag[i]; *bad += flagged rows with an empty list (never, see the kernel)
 hipError_t launch_radius_self_counts_f32(const float *P, size_t n, int dim, size_t ld, const float *cnorm, float r,
                                          bool exclude, const uint64_t *in_off, uint32_t *flag, uint32_t *cnt, uint32_t *bad,
-                                         hipStream_t s);
+                                         hipStream_t s, const float *radii = nullptr);
 hipError_t launch_radius_self_counts_f64(const double *P, size_t n, int dim, size_t ld, const double *cnorm, double r,
                                          bool exclude, const uint64_t *in_off, uint32_t *flag, uint32_t *cnt, uint32_t *bad,
-                                         hipStream_t s);
+                                         hipStream_t s, const double *radii = nullptr);
 // out[1 + j] <- out[0] + part[j + 1], j < nq (a chunk's scan behind the rows before it)
 hipError_t launch_radius_self_place(const uint64_t *part, size_t nq, uint64_t *out, hipStream_t s);
 // out[out_off[i] + t] <- row i's list (in_off, ascending index, entries below in_cap) without self0 + i where flag[i],
@@ -263,8 +263,9 @@ hipError_t launch_radius_check(const uint32_t *rcnt, const uint32_t *ridx, size_
                                const T *P, size_t ldp, const T *Q, int nq, int dim, T r, uint32_t *kept,
                                uint32_t *nkept, uint32_t *overflow, int ridx_stride, uint32_t *over_q, hipStream_t s,
                                const T *cnorm = nullptr, const T *qnorm = nullptr,  // (both: Cosine::distance < r)
-                               T *kept_dist = nullptr);  // (nullable: [2][nq][nseg * cap], the second half gets
-                                                         // the kept rows' distances next to `kept`)
+                               T *kept_dist = nullptr,  // (nullable: [2][nq][nseg * cap], the second half gets
+                                                        // the kept rows' distances next to `kept`)
+                               const T *radii = nullptr);  // (nullable, [nq]: query q is compared with radii[q], not r)
 hipError_t launch_gather_rows_f32(const float *src, size_t ld, const uint32_t *sel, const uint32_t *nsel, uint32_t off,
                                   uint32_t max_rows, float *dst, hipStream_t s);
 hipError_t launch_scatter_results_f32(const uint64_t *idx_in, const float *dist_in, const uint32_t *sel,
@@ -408,6 +409,16 @@ int bf16_cell_max(int kp, int cap, int nseg, bool wide);  // entries a cell hold
 hipError_t launch_bf16_seed(const float *lists, size_t nq_pad, int nseg, int rank, uint32_t *out, hipStream_t s,
                             size_t nq = 0);
 hipError_t launch_bf16_radius_tau(const double *qn, size_t nq_pad, double tau_r, uint32_t *out, hipStream_t s);
+
+// ---- radii_tau.hip: launch_bf16_radius_tau for one radius per query (pn_query_radii_*).  radii [nq] in the index's
+// type T; out[q] = the threshold key launch_bf16_radius_tau gives for tau_r(radii[q]) (the three formulas of
+// radius_bf16_enqueue, evaluated per query in f64); a query whose radius the filter cannot serve (not finite positive,
+// Cosine r >= 1, tau_r >= 1e37) gets the key of -inf and qbad[q] = 1; q >= nq: -inf
+template <typename T>
+hipError_t launch_bf16_radii_tau(const double *qn, const T *radii, size_t nq, size_t nq_pad, int dim, bool cosine,
+                                 uint32_t *out, uint32_t *qbad, hipStream_t s);
+// stats[0] += *nsel (one thread; the listed queries of a pn_query_radii_* call into pn_stats.fallback_queries)
+hipError_t launch_radii_add_listed(const uint32_t *nsel, unsigned long long *stats, hipStream_t s);
 // diagnostic: out[q][row] = L'(q, row), q < nq, row < n_rows
 hipError_t launch_bf16_bound(const void *img, const void *B, size_t n_rows, size_t nq, int dim, float *out, bool ci,
                              hipStream_t s);

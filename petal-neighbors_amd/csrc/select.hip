@@ -1011,7 +1011,8 @@ __global__ __launch_bounds__(64) void radius_check_kernel(const uint32_t *__rest
                                                           uint32_t *__restrict__ kept, uint32_t *__restrict__ nkept,
                                                           uint32_t *__restrict__ overflow, int ridx_stride,
                                                           uint32_t *__restrict__ over_q, const T *__restrict__ cnorm,
-                                                          const T *__restrict__ qnorm, T *__restrict__ kept_dist) {
+                                                          const T *__restrict__ qnorm, T *__restrict__ kept_dist,
+                                                          const T *__restrict__ radii) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint32_t *srow = reinterpret_cast<uint32_t *>(smem);  // rows that pass the exact test
     __shared__ uint32_t n_pass;
@@ -1020,6 +1021,7 @@ __global__ __launch_bounds__(64) void radius_check_kernel(const uint32_t *__rest
     if (lane == 0) n_pass = 0;
     __syncthreads();
     const T *qrow = Q + q * ldp;
+    if (radii) r = radii[q];  // (pn_query_radii_*: the query's own radius)
     const size_t stride = (size_t)nseg * cap;
     T *kd_slot = WD ? kept_dist + q * stride : nullptr, *kd = WD ? kept_dist + ((size_t)gridDim.x + q) * stride : nullptr;
     bool over = false;
@@ -1059,14 +1061,14 @@ template <typename T>
 hipError_t launch_radius_check(const uint32_t *rcnt, const uint32_t *ridx, size_t nq_pad, int nseg, uint32_t cap,
                                const T *P, size_t ldp, const T *Q, int nq, int dim, T r, uint32_t *kept,
                                uint32_t *nkept, uint32_t *overflow, int ridx_stride, uint32_t *over_q, hipStream_t s,
-                               const T *cnorm, const T *qnorm, T *kept_dist) {
+                               const T *cnorm, const T *qnorm, T *kept_dist, const T *radii) {
     const size_t sh = (size_t)nseg * cap * sizeof(uint32_t);  // (the same with distances: they stay in HBM)
     if (sh > 64 * 1024) return hipErrorInvalidValue;
     const bool cos = cnorm || qnorm;
     if (cos && (!cnorm || !qnorm || ldp % 8)) return hipErrorInvalidValue;
 #define PN_CHECK(CC, WW)                                                                                                   \
     hipLaunchKernelGGL((radius_check_kernel<T, CC, WW>), dim3((unsigned)nq), dim3(64), sh, s, rcnt, ridx, nq_pad, nseg, cap, \
-                       P, ldp, Q, dim, r, kept, nkept, overflow, ridx_stride, over_q, cnorm, qnorm, kept_dist)
+                       P, ldp, Q, dim, r, kept, nkept, overflow, ridx_stride, over_q, cnorm, qnorm, kept_dist, radii)
     if (kept_dist) {
         if (cos) PN_CHECK(true, true); else PN_CHECK(false, true);
     } else {
@@ -1077,16 +1079,16 @@ hipError_t launch_radius_check(const uint32_t *rcnt, const uint32_t *ridx, size_
 }
 template hipError_t launch_radius_check<float>(const uint32_t *, const uint32_t *, size_t, int, uint32_t, const float *, size_t,
                                                const float *, int, int, float, uint32_t *, uint32_t *, uint32_t *, int,
-                                               uint32_t *, hipStream_t, const float *, const float *, float *);
+                                               uint32_t *, hipStream_t, const float *, const float *, float *, const float *);
 template hipError_t launch_radius_check<double>(const uint32_t *, const uint32_t *, size_t, int, uint32_t, const double *,
                                                 size_t, const double *, int, int, double, uint32_t *, uint32_t *, uint32_t *,
-                                                int, uint32_t *, hipStream_t, const double *, const double *, double *);
+                                                int, uint32_t *, hipStream_t, const double *, const double *, double *, const double *);
 hipError_t launch_radius_check_f32(const uint32_t *rcnt, const uint32_t *ridx, size_t nq_pad, int nseg, uint32_t cap,
                                    const float *P, size_t ldp, const float *Q, int nq, int dim, float r,
                                    uint32_t *kept, uint32_t *nkept, uint32_t *overflow, int ridx_stride,
                                    uint32_t *over_q, hipStream_t s, float *kept_dist) {
     return launch_radius_check<float>(rcnt, ridx, nq_pad, nseg, cap, P, ldp, Q, nq, dim, r, kept, nkept, overflow,
-                                      ridx_stride, over_q, s, nullptr, nullptr, kept_dist);
+                                      ridx_stride, over_q, s, nullptr, nullptr, kept_dist, nullptr);
 }
 
 // D: the bits of a distance (uint32_t / uint64_t) when the kept rows' distances go along (kd / od), void: rows only

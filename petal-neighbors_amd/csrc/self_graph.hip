@@ -66,7 +66,7 @@ __global__ __launch_bounds__(256) void radius_self_counts_kernel(const T *__rest
                                                                  const T *__restrict__ cnorm, T r, bool exclude,
                                                                  const uint64_t *__restrict__ in_off,
                                                                  uint32_t *__restrict__ flag, uint32_t *__restrict__ cnt,
-                                                                 uint32_t *__restrict__ bad) {
+                                                                 uint32_t *__restrict__ bad, const T *__restrict__ radii) {
 #pragma clang fp contract(off)
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void radius_self_counts_kernel(const T *__rest
             }
         }
         const T d = COS ? (T)1 - acc / (cnorm[i] * cnorm[i]) : self_sqrt(acc);
-        f = d < r ? 1u : 0u;  // NaN distances never match
+        f = d < (radii ? radii[i] : r) ? 1u : 0u;  // NaN distances never match (radii: pn_query_radii_self_*, row i's own)
         if (f && len == 0) {
             atomicAdd(bad, 1u);
             f = 0;
@@ -174,26 +174,26 @@ hipError_t launch_knn_self_exclude_f64(const uint64_t *in_idx, const double *in_
 template <typename T>
 static hipError_t launch_radius_self_counts(const T *P, size_t n, int dim, size_t ld, const T *cnorm, T r, bool exclude,
                                            const uint64_t *in_off, uint32_t *flag, uint32_t *cnt, uint32_t *bad,
-                                           hipStream_t s) {
+                                           hipStream_t s, const T *radii) {
     if (n == 0) return hipSuccess;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
     if (cnorm)
         hipLaunchKernelGGL((radius_self_counts_kernel<T, true>), grid, block, 0, s, P, n, dim, ld, cnorm, r, exclude, in_off,
-                           flag, cnt, bad);
+                           flag, cnt, bad, radii);
     else
         hipLaunchKernelGGL((radius_self_counts_kernel<T, false>), grid, block, 0, s, P, n, dim, ld, cnorm, r, exclude, in_off,
-                           flag, cnt, bad);
+                           flag, cnt, bad, radii);
     return hipGetLastError();
 }
 hipError_t launch_radius_self_counts_f32(const float *P, size_t n, int dim, size_t ld, const float *cnorm, float r,
                                          bool exclude, const uint64_t *in_off, uint32_t *flag, uint32_t *cnt, uint32_t *bad,
-                                         hipStream_t s) {
-    return launch_radius_self_counts<float>(P, n, dim, ld, cnorm, r, exclude, in_off, flag, cnt, bad, s);
+                                         hipStream_t s, const float *radii) {
+    return launch_radius_self_counts<float>(P, n, dim, ld, cnorm, r, exclude, in_off, flag, cnt, bad, s, radii);
 }
 hipError_t launch_radius_self_counts_f64(const double *P, size_t n, int dim, size_t ld, const double *cnorm, double r,
                                          bool exclude, const uint64_t *in_off, uint32_t *flag, uint32_t *cnt, uint32_t *bad,
-                                         hipStream_t s) {
-    return launch_radius_self_counts<double>(P, n, dim, ld, cnorm, r, exclude, in_off, flag, cnt, bad, s);
+                                         hipStream_t s, const double *radii) {
+    return launch_radius_self_counts<double>(P, n, dim, ld, cnorm, r, exclude, in_off, flag, cnt, bad, s, radii);
 }
 hipError_t launch_radius_self_place(const uint64_t *part, size_t nq, uint64_t *out, hipStream_t s) {
     if (nq == 0) return hipSuccess;
