@@ -104,6 +104,16 @@ extern "C" {
                                     stream: *mut c_void) -> c_int;
     pub fn pn_query_self_device_f64(index: *const pn_index, k: usize, flags: c_uint, d_idx: *mut u64, d_dist: *mut f64,
                                     stream: *mut c_void) -> c_int;
+    /// DBSCAN on the device: labels [n] (-1 = noise), core [n] bytes (nullable), n_clusters [1] (nullable); flags = 0.
+    /// The device entry points write in stream order and block the host once
+    pub fn pn_dbscan_f32(index: *const pn_index, eps: f32, min_samples: usize, flags: c_uint, labels: *mut i64,
+                         core: *mut u8, n_clusters: *mut u64) -> c_int;
+    pub fn pn_dbscan_f64(index: *const pn_index, eps: f64, min_samples: usize, flags: c_uint, labels: *mut i64,
+                         core: *mut u8, n_clusters: *mut u64) -> c_int;
+    pub fn pn_dbscan_device_f32(index: *const pn_index, eps: f32, min_samples: usize, flags: c_uint, d_labels: *mut i64,
+                                d_core: *mut u8, d_n_clusters: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn pn_dbscan_device_f64(index: *const pn_index, eps: f64, min_samples: usize, flags: c_uint, d_labels: *mut i64,
+                                d_core: *mut u8, d_n_clusters: *mut u64, stream: *mut c_void) -> c_int;
     /// dist_out nullable (PN_RADIUS_SORTED needs it); *idx_out / *dist_out released with pn_free
     pub fn pn_query_radius_self_f32(index: *const pn_index, radius: f32, flags: c_uint, offsets: *mut u64,
                                     idx_out: *mut *mut u64, dist_out: *mut *mut f32) -> c_int;

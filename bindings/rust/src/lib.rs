@@ -52,6 +52,9 @@ pub trait Elem: Copy + Default + PartialOrd + 'static {
     unsafe fn self_radii(ix: *const ffi::pn_index, r: *const Self, flags: std::os::raw::c_uint, off: *mut u64,
                          out: *mut *mut u64, dout: *mut *mut Self) -> c_int;
     #[doc(hidden)]
+    unsafe fn dbscan(ix: *const ffi::pn_index, eps: Self, min_samples: usize, labels: *mut i64, core: *mut u8,
+                     ncl: *mut u64) -> c_int;
+    #[doc(hidden)]
     unsafe fn radius_of(ix: *const ffi::pn_index, n: u64, out: *mut Self) -> c_int;
     #[doc(hidden)]
     unsafe fn lower_bound(ix: *const ffi::pn_index, a: u64, b: u64, out: *mut Self) -> c_int;
@@ -65,7 +68,7 @@ pub trait Elem: Copy + Default + PartialOrd + 'static {
 macro_rules! impl_elem {
     ($t:ty, $create:ident, $create_cos:ident, $query:ident, $radius:ident, $radius_wd:ident, $rad_of:ident, $lb:ident,
      $eu:ident, $reu:ident, $cos:ident, $pw:ident, $pwc:ident, $self_knn:ident, $self_rad:ident, $radii:ident,
-     $self_radii:ident) => {
+     $self_radii:ident, $dbscan:ident) => {
         impl Elem for $t {
             unsafe fn create(p: *const Self, n: usize, d: usize, rs: isize, cs: isize, cosine: bool, out: *mut *mut ffi::pn_index) -> c_int {
                 if cosine { ffi::$create_cos(p, n, d, rs, cs, 0, out) } else { ffi::$create(p, n, d, rs, cs, 0, out) }
@@ -95,6 +98,10 @@ macro_rules! impl_elem {
                                  out: *mut *mut u64, dout: *mut *mut Self) -> c_int {
                 ffi::$self_radii(ix, r, flags, off, out, dout)
             }
+            unsafe fn dbscan(ix: *const ffi::pn_index, eps: Self, min_samples: usize, labels: *mut i64, core: *mut u8,
+                             ncl: *mut u64) -> c_int {
+                ffi::$dbscan(ix, eps, min_samples, 0, labels, core, ncl)
+            }
             unsafe fn radius_of(ix: *const ffi::pn_index, n: u64, out: *mut Self) -> c_int { ffi::$rad_of(ix, n, out) }
             unsafe fn lower_bound(ix: *const ffi::pn_index, a: u64, b: u64, out: *mut Self) -> c_int { ffi::$lb(ix, a, b, out) }
             unsafe fn euclid(a: *const Self, b: *const Self, n: usize, squared: bool) -> Self {
@@ -111,12 +118,12 @@ impl_elem!(f32, pn_index_create_f32, pn_index_create_cosine_f32, pn_query_f32, p
            pn_query_radius_with_distance_f32, pn_tree_radius_of_f32,
            pn_tree_node_distance_lower_bound_f32, pn_euclidean_f32, pn_reuclidean_f32, pn_cosine_f32, pn_pairwise_f32,
            pn_pairwise_cosine_f32, pn_query_self_f32, pn_query_radius_self_f32, pn_query_radii_f32,
-           pn_query_radii_self_f32);
+           pn_query_radii_self_f32, pn_dbscan_f32);
 impl_elem!(f64, pn_index_create_f64, pn_index_create_cosine_f64, pn_query_f64, pn_query_radius_f64,
            pn_query_radius_with_distance_f64, pn_tree_radius_of_f64,
            pn_tree_node_distance_lower_bound_f64, pn_euclidean_f64, pn_reuclidean_f64, pn_cosine_f64, pn_pairwise_f64,
            pn_pairwise_cosine_f64, pn_query_self_f64, pn_query_radius_self_f64, pn_query_radii_f64,
-           pn_query_radii_self_f64);
+           pn_query_radii_self_f64, pn_dbscan_f64);
 
 pub mod distance {
     use super::*;
@@ -275,6 +282,18 @@ impl<'a, A: Elem, M: Metric<A>> BallTree<'a, A, M> {
             ffi::pn_free(dout as *mut _);
         }
         (off, idx, dist)
+    }
+    /// extension: DBSCAN of the indexed rows on the device: (labels, core flags, number of clusters).  A row's
+    /// neighbourhood is { j : distance(p_i, p_j) < eps }, itself included where its own distance is below eps; clusters
+    /// are numbered by ascending lowest core row, a border row takes the lowest-numbered cluster among its core
+    /// neighbours, noise is -1
+    pub fn dbscan(&self, eps: A, min_samples: usize) -> (Vec<i64>, Vec<bool>, usize) {
+        let n = self.points.nrows();
+        let mut labels = vec![-1i64; n];
+        let mut core = vec![0u8; n];
+        let mut ncl = 0u64;
+        ok(unsafe { A::dbscan(self.handle, eps, min_samples, labels.as_mut_ptr(), core.as_mut_ptr(), &mut ncl) });
+        (labels, core.iter().map(|&c| c != 0).collect(), ncl as usize)
     }
     /// extension: `query_radius_self` with one radius per row (`radii.len()` = the number of rows): row i's list is the
     /// scalar call's for `radii[i]`

@@ -59,7 +59,8 @@ extern "C" {
  * Additive within version 3 (callers detect them by symbol): pn_query_radius_with_distance_{,device_}{f32,f64},
  * pn_sharded_query_radius_with_distance_{,device_}{f32,f64}, PN_RADIUS_SORTED; pn_query_self_{,device_}{f32,f64},
  * pn_query_radius_self_{,device_}{f32,f64}, PN_SELF_INCLUDE; pn_sharded_query_self_{,device_}{f32,f64},
- * pn_sharded_query_radius_self_{,device_}{f32,f64}; pn_query_radii_{,device_,self_,self_device_}{f32,f64}. */
+ * pn_sharded_query_radius_self_{,device_}{f32,f64}; pn_query_radii_{,device_,self_,self_device_}{f32,f64};
+ * pn_dbscan_{,device_}{f32,f64}, PN_OPT_DBSCAN_PIECE. */
 #define PN_ABI_VERSION 3
 
 /* ---- error codes.  EMPTY / NOT_CONTIGUOUS are ArrayError (src/lib.rs:9-16). */
@@ -107,10 +108,13 @@ enum {
                                   the 4-wave kernel (two column blocks per wave, two waves per SIMD) for long ones; 4 / 8
                                   = always that kernel where it applies.  Never changes a result (A/B measurements,
                                   tests of both kernels). */
-    PN_OPT_SEED_MODEL = 10       /* bf16 tier, indexes of narrow rows (D <= 128) whose seed model was accepted at build
+    PN_OPT_SEED_MODEL = 10,      /* bf16 tier, indexes of narrow rows (D <= 128) whose seed model was accepted at build
                                   (pn_info.seed_model): 1 (default) = k-NN calls with k <= 128 take their starting
                                   thresholds from the model (no scout launch); 0 = always scout.  Never changes a result:
                                   a threshold only decides which tier answers a query. */
+    PN_OPT_DBSCAN_PIECE = 11     /* pn_dbscan_*: the most list entries (64-bit indices in workspace scratch) one piece of
+                                  the union stage holds; 0 (default) = 2^27, i.e. 1 GiB.  A row whose own list is longer
+                                  is a piece of its own.  Never changes a result. */
 };
 
 typedef struct pn_index pn_index;
@@ -362,6 +366,38 @@ int pn_query_radii_self_device_f32(const pn_index *index, const float *d_radii, 
                                    uint64_t *d_idx, float *d_dist, size_t capacity, uint64_t *d_total, void *stream);
 int pn_query_radii_self_device_f64(const pn_index *index, const double *d_radii, unsigned flags, uint64_t *d_offsets,
                                    uint64_t *d_idx, double *d_dist, size_t capacity, uint64_t *d_total, void *stream);
+
+/* ---- DBSCAN on the device: cluster labels of the indexed rows without materialising the eps-graph.
+ * For a radius eps and min_samples >= 1:
+ *   N(i)    = { j : distance(p_i, p_j) < eps }: row i's list from pn_query_radius_self_* with PN_SELF_INCLUDE -- strict '<',
+ *             bit-identical distances, row i itself counted iff its own distance is < eps (a NaN row: empty).  eps <= 0 or
+ *             NaN: every N(i) is empty by definition, every row is noise.
+ *   core[i] = |N(i)| >= min_samples.
+ *   Clusters are the connected components of the core rows under "j in N(i)", numbered 0, 1, ... by ascending lowest core
+ *   row.  labels[i] = its component's number for a core row; for a non-core row with a core row in N(i) (a border row) the
+ *   LOWEST-numbered cluster among its core neighbours; -1 otherwise (noise).
+ * This is the labelling of the classic scan-order algorithm (rows visited in index order, each new cluster expanded fully
+ * before the next; scikit-learn's, with '<' in place of '<='), and it depends on the data alone, not on scheduling:
+ * every union links the larger root under the smaller.
+ * labels [n] int64; core [n] bytes of 0 / 1, nullable; n_clusters [1], nullable.  flags must be 0.  Euclidean and Cosine
+ * indexes alike; PN_OPT_INDEX_BASE does not affect the labels.  flags != 0, min_samples == 0, NULL labels, a NULL index, a
+ * wrong element type: PN_ERR_INVALID, in that order, before any device is touched; more than 2^31 - 1 rows:
+ * PN_ERR_UNSUPPORTED (parents are 32-bit).  pn_stats.queries counts n queries.
+ * The call runs the radius pipeline twice over the rows -- a count, then the lists piece by piece (at most 2^18 rows and
+ * PN_OPT_DBSCAN_PIECE entries each) into workspace scratch, where a union-find kernel consumes them.  Device memory beyond
+ * a 2^18-query batch's workspace: 37 bytes per row, 8 bytes per entry of the largest piece, 4 bytes per entry of the
+ * non-core rows' lists (fewer than n (min_samples - 1) entries).
+ * Device entry points: outputs in HBM, written in stream order on `stream`; the call BLOCKS THE HOST ONCE, after the
+ * counting pass, to read the n + 1 offsets it cuts the pieces from -- it is not capturable into a graph.
+ * Not yet: row-sharded handles (pn_sharded_*) and one eps per row. */
+int pn_dbscan_f32(const pn_index *index, float eps, size_t min_samples, unsigned flags, int64_t *labels, uint8_t *core,
+                  uint64_t *n_clusters);
+int pn_dbscan_f64(const pn_index *index, double eps, size_t min_samples, unsigned flags, int64_t *labels, uint8_t *core,
+                  uint64_t *n_clusters);
+int pn_dbscan_device_f32(const pn_index *index, float eps, size_t min_samples, unsigned flags, int64_t *d_labels,
+                         uint8_t *d_core, uint64_t *d_n_clusters, void *stream);
+int pn_dbscan_device_f64(const pn_index *index, double eps, size_t min_samples, unsigned flags, int64_t *d_labels,
+                         uint8_t *d_core, uint64_t *d_n_clusters, void *stream);
 
 /* ---- distance::pairwise(x, &Euclidean) (src/distance.rs:58-74): n x n
  * symmetric matrix, zero diagonal, n < 2 -> zeros. Host in, host out. */

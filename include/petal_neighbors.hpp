@@ -81,6 +81,12 @@ inline std::vector<double> pairwise(const double *x, size_t n, size_t d, int dev
 }
 }  // namespace distance
 
+// the answer of BallTree::dbscan
+struct Dbscan {
+    std::vector<int64_t> labels;  // [n]: cluster number, -1 = noise
+    std::vector<uint8_t> core;    // [n]: 1 = core row
+    size_t n_clusters = 0;
+};
 // the CSR answer of BallTree::query_radius_self: row i's neighbours are idx[offsets[i] .. offsets[i + 1]] (dist beside
 // them when asked for)
 template <typename A>
@@ -266,6 +272,21 @@ class BallTree {
         if (dout) res.dist.assign(dout, dout + total);
         pn_free(out);
         pn_free(dout);
+        return res;
+    }
+    // extension: DBSCAN of the indexed rows on the device (pn_dbscan_*): labels[i] = the row's cluster (numbered by
+    // ascending lowest core row; a border row takes the lowest-numbered cluster among its core neighbours) or -1 for
+    // noise; core[i] = the row has at least min_samples rows within eps (strict '<', itself included)
+    Dbscan dbscan(A eps, size_t min_samples) const {
+        Dbscan res;
+        res.labels.resize(n_);
+        res.core.resize(n_);
+        uint64_t ncl = 0;
+        if constexpr (kF32)
+            check(pn_dbscan_f32(h_, eps, min_samples, 0u, res.labels.data(), res.core.data(), &ncl));
+        else
+            check(pn_dbscan_f64(h_, eps, min_samples, 0u, res.labels.data(), res.core.data(), &ncl));
+        res.n_clusters = (size_t)ncl;
         return res;
     }
     // extension: one radius per row (pn_query_radii_self_*): radii [size()], row i's list is the scalar overload's for

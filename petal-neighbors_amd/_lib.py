@@ -22,6 +22,7 @@ PN_OPT_EXCHANGE_ALWAYS = 7
 PN_OPT_SHARED_THRESHOLDS = 8
 PN_OPT_BF16_WAVES = 9
 PN_OPT_SEED_MODEL = 10
+PN_OPT_DBSCAN_PIECE = 11
 PN_RADIUS_SORTED = 1
 PN_SELF_INCLUDE = 2
 
@@ -101,6 +102,10 @@ SIGNATURES = {
     "pn_query_radii_self_f64": (_i, [_vp, _vp, C.c_uint, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "pn_query_radii_self_device_f32": (_i, [_vp, _vp, C.c_uint, _vp, _vp, _vp, _sz, _vp, _vp]),
     "pn_query_radii_self_device_f64": (_i, [_vp, _vp, C.c_uint, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "pn_dbscan_f32": (_i, [_vp, C.c_float, _sz, C.c_uint, _vp, _vp, _vp]),
+    "pn_dbscan_f64": (_i, [_vp, C.c_double, _sz, C.c_uint, _vp, _vp, _vp]),
+    "pn_dbscan_device_f32": (_i, [_vp, C.c_float, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
+    "pn_dbscan_device_f64": (_i, [_vp, C.c_double, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
     "pn_free": (None, [_vp]),
     "pn_pairwise_f32": (_i, [_vp, _sz, _sz, _ssz, _i, _vp]),
     "pn_pairwise_f64": (_i, [_vp, _sz, _sz, _ssz, _i, _vp]),

@@ -561,3 +561,37 @@ class BallTree:
         check(fn(self._h, rr, self._self_flags(include_self, sort), offs.data_ptr(), idx.data_ptr(),
                  dist.data_ptr() if dist is not None else None, int(capacity), tot.data_ptr(), C.c_void_p(st)))
         return offs, idx, dist, tot
+
+    # ------------------------------------------------------------------- DBSCAN
+    def _dbscan_args(self, eps, min_samples):
+        if int(min_samples) < 1:
+            raise ValueError("min_samples must be >= 1")
+        return (C.c_float(eps) if self._sfx == "f32" else C.c_double(eps)), int(min_samples)
+
+    def dbscan(self, eps, min_samples: int):
+        """DBSCAN of the indexed rows on the device (``pn_dbscan_*``): ``(labels int64 [n], core bool [n])``.  Row i's
+        neighbourhood is ``{ j : distance(p_i, p_j) < eps }`` (itself included where its own distance is below eps), a
+        core row has at least ``min_samples`` of them, clusters are numbered by ascending lowest core row, a border row
+        takes the lowest-numbered cluster among its core neighbours, noise is -1."""
+        e, m = self._dbscan_args(eps, min_samples)
+        labels = np.empty(self._n, dtype=np.int64)
+        core = np.empty(self._n, dtype=np.uint8)
+        check(getattr(_lib.lib(), f"pn_dbscan_{self._sfx}")(self._h, e, m, 0, labels.ctypes.data, core.ctypes.data, None))
+        return labels, core.astype(bool)
+
+    def dbscan_device(self, eps, min_samples: int, out_labels=None, out_core=None, out_n_clusters=None, stream=None):
+        """``dbscan`` with the results in HBM: CUDA tensors ``(labels int64 [n], core uint8 [n], n_clusters int64 [1])``,
+        written in stream order on ``stream`` (default: the current torch stream).  The call waits for the device once."""
+        e, m = self._dbscan_args(eps, min_samples)
+        import torch
+        dev = torch.device("cuda", self.device)
+        labels = out_labels if out_labels is not None else torch.empty(self._n, dtype=torch.int64, device=dev)
+        core = out_core if out_core is not None else torch.empty(self._n, dtype=torch.uint8, device=dev)
+        ncl = out_n_clusters if out_n_clusters is not None else torch.empty(1, dtype=torch.int64, device=dev)
+        if labels.dtype != torch.int64 or core.dtype != torch.uint8 or ncl.dtype != torch.int64 or \
+                labels.numel() < self._n or core.numel() < self._n or ncl.numel() < 1:
+            raise ValueError("output tensors are too small or of the wrong type")
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        check(getattr(_lib.lib(), f"pn_dbscan_device_{self._sfx}")(
+            self._h, e, m, 0, labels.data_ptr(), core.data_ptr(), ncl.data_ptr(), C.c_void_p(st)))
+        return labels, core, ncl

@@ -42,6 +42,7 @@ UNITS = [
     ("radius_device.hip", []),
     ("csr_sort.hip", []),
     ("self_graph.hip", ["-ffp-contract=off"]),
+    ("components.hip", []),
     ("radii_tau.hip", ["-ffp-contract=off"]),
     ("metric.cpp", ["-ffp-contract=off"]),
     ("tree.cpp", ["-ffp-contract=off"]),

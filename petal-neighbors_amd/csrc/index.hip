@@ -147,6 +147,9 @@ struct Workspace {
     // inner offsets and scanned counts, self flags (+ the disagreement word), adjusted counts, scan scratch, and the host
     // radius entry's offsets + total
     DevBuf w_sf_idx, w_sf_dist, w_sf_off, w_sf_coff, w_sf_flag, w_sf_cnt, w_sf_scan, w_sf_hoff;
+    // pn_dbscan_*: the O(n) arrays of a call (offsets, parents, roots, ... carved from one buffer), the border rows' side
+    // lists, and the host entry's outputs
+    DevBuf w_db, w_db_side, w_db_out;
     // small calls (tiny_*): mapped pinned host memory the one kernel of the call reads its queries from and writes its
     // answers to -- no copy commands
     void *pin_in = nullptr, *pin_out = nullptr;
@@ -172,7 +175,7 @@ struct Workspace {
     hipEvent_t done = nullptr;
     hipStream_t last_stream = nullptr;
     bool in_flight = false;
-    DevBuf *all[52] = {&w_hrad, &w_sf_idx, &w_sf_dist, &w_sf_off, &w_sf_coff, &w_sf_flag, &w_sf_cnt, &w_sf_scan, &w_sf_hoff, &w_cs_hoff, &w_rkd, &w_cs_nch, &w_cs_off, &w_cs_scan, &w_cs_idx, &w_cs_dist, &w_gqn, &w_rpos, &w_rfin, &w_rcx, &w_rox, &w_rscan, &w_q, &w_qnorm, &w_qnrm, &w_keys, &w_idx, &w_cnt, &w_tau, &w_flags, &w_sel, &w_misc, &w2_keys, &w2_idx,
+    DevBuf *all[55] = {&w_db, &w_db_side, &w_db_out, &w_hrad, &w_sf_idx, &w_sf_dist, &w_sf_off, &w_sf_coff, &w_sf_flag, &w_sf_cnt, &w_sf_scan, &w_sf_hoff, &w_cs_hoff, &w_rkd, &w_cs_nch, &w_cs_off, &w_cs_scan, &w_cs_idx, &w_cs_dist, &w_gqn, &w_rpos, &w_rfin, &w_rcx, &w_rox, &w_rscan, &w_q, &w_qnorm, &w_qnrm, &w_keys, &w_idx, &w_cnt, &w_tau, &w_flags, &w_sel, &w_misc, &w2_keys, &w2_idx,
                        &w2_cnt, &w2_tau, &w_lo, &w_bq, &w_qn, &w_qbad, &w_gq, &w_gidx, &w_gdist, &w_gsel, &w_seed,
                        &w_qstat, &w_lists, &w_hq, &w_hidx, &w_hdist, &w_fparts, &w_pcnt};
     std::vector<void *> retired;  // outgrown allocations, freed once `done` has passed (DevBuf::ensure)
@@ -239,6 +242,7 @@ struct pn_index {
     double sm_sigma = 0.0;              // standard deviation of ln(rank a model threshold really has / rank it aimed at)
     bool sm_ok = false;
     int seed_model = 1;      // PN_OPT_SEED_MODEL: 1 (default) use it where it was accepted, 0 never
+    uint64_t dbscan_piece = 0;  // PN_OPT_DBSCAN_PIECE: list entries per piece of pn_dbscan_*, 0 = 2^27
     // state that queries on a shared `const pn_index *` update: internally synchronised by `mu`
     struct Shared {
         std::mutex mu;
@@ -991,6 +995,10 @@ extern "C" int pn_index_set_option(pn_index *ix, int option, int64_t value) {
         case PN_OPT_SEED_MODEL:
             if (value != 0 && value != 1) return fail(PN_ERR_INVALID, "bad seed-model switch (0 or 1)");
             ix->seed_model = (int)value;
+            return PN_OK;
+        case PN_OPT_DBSCAN_PIECE:
+            if (value < 0) return fail(PN_ERR_INVALID, "bad DBSCAN piece size");
+            ix->dbscan_piece = (uint64_t)value;
             return PN_OK;
         default: return fail(PN_ERR_INVALID, "unknown option %d", option);
     }
@@ -3607,6 +3615,136 @@ extern "C" int pn_query_radius_self_device_f64(const pn_index *ix, double radius
                                                uint64_t *d_idx, double *d_dist, size_t capacity, uint64_t *d_total,
                                                void *stream) {
     return radius_self_device<double>(ix, radius, flags, d_offsets, d_idx, d_dist, capacity, d_total, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------
+// DBSCAN: pn_dbscan_{,device_}{f32,f64} (the kernels and the argument for schedule independence: components.hip).
+//   1. count: radius_self_enqueue with capacity 0 and PN_SELF_INCLUDE gives the offsets of the eps-graph, no lists.  From
+//      them: core[], parent[i] = i and the lengths of the non-core rows' side lists, scanned on the device.  The offsets
+//      and the side lists' total are read back -- the one host wait of a call -- to cut the pieces and size the side lists.
+//   2. union: a piece is a contiguous row range of at most 2^18 rows whose lists hold at most E entries together
+//      (PN_OPT_DBSCAN_PIECE, default 2^27; a longer single row is a piece of its own).  radius_device_enqueue writes the
+//      piece's lists into workspace scratch of exactly the piece's total, the union kernel reads them there.
+//   3. finish: flatten, flag and scan the core roots into cluster numbers, label.
+// Device memory beyond a 2^18-query batch's workspace: 37 bytes per row, 8 bytes per entry of the largest piece and 4
+// bytes per entry of the non-core rows' lists (< n (min_samples - 1) entries) -- never the graph.
+// ---------------------------------------------------------------------------
+constexpr uint64_t kDbscanPiece = (uint64_t)1 << 27;
+static int dbscan_args(const pn_index *ix, unsigned flags, size_t min_samples, const void *labels, int elem_bytes) {
+    if (flags) return fail(PN_ERR_INVALID, "unknown DBSCAN flags 0x%x", flags);
+    if (min_samples == 0) return fail(PN_ERR_INVALID, "min_samples must be at least 1");
+    if (!labels) return fail(PN_ERR_INVALID, "labels is NULL");
+    if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
+    if (ix->elem_bytes != elem_bytes) return fail(PN_ERR_INVALID, "index element type mismatch");
+    if (ix->n > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many rows for DBSCAN (32-bit parents)");
+    return PN_OK;
+}
+// in a held workspace, on stream s; outputs in HBM; blocks the host once (after the counting pass)
+template <typename T>
+static int dbscan_enqueue(const pn_index *ix, Workspace &ws, T eps, size_t min_samples, int64_t *d_labels, uint8_t *d_core,
+                          uint64_t *d_ncl, hipStream_t s) {
+    const size_t n = ix->n;
+    if (!(eps > (T)0)) {  // eps <= 0 or NaN: every neighbourhood is empty by definition
+        HIPCHK(launch_dbscan_noise(n, d_labels, d_core, d_ncl, s));
+        return PN_OK;
+    }
+    // one buffer, carved: 64-bit arrays first
+    const size_t scan_words = n / 4096 + 2;
+    const size_t bytes64 = ((n + 1) * 3 + scan_words) * sizeof(uint64_t), bytes32 = 3 * n * sizeof(uint32_t);
+    PNCHK(ws.w_db.ensure(bytes64 + bytes32 + n));
+    uint64_t *off = (uint64_t *)ws.w_db.p, *side_off = off + n + 1, *num = side_off + n + 1, *scan = num + n + 1;
+    uint32_t *parent = (uint32_t *)(scan + scan_words), *word = parent + n, *root = word + n;
+    uint8_t *core = (uint8_t *)(root + n);
+    // ---- 1. count
+    PNCHK(radius_self_enqueue<T>(ix, ws, eps, PN_SELF_INCLUDE, off, nullptr, nullptr, 0, nullptr, s, true));
+    HIPCHK(launch_dbscan_init(off, n, (uint64_t)min_samples, core, parent, word, s));  // word = side list lengths
+    HIPCHK(launch_exclusive_scan_u32(word, n, side_off, scan, nullptr, s));
+    std::vector<uint64_t> h_off;
+    try {
+        h_off.resize(n + 1);
+    } catch (const std::bad_alloc &) {
+        return fail(PN_ERR_NOMEM, "host allocation of %zu offsets failed", n + 1);
+    }
+    uint64_t side_total = 0;
+    HIPCHK(hipMemcpyAsync(h_off.data(), off, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&side_total, side_off + n, sizeof side_total, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    PNCHK(ws.w_db_side.ensure((side_total ? side_total : 1) * sizeof(uint32_t)));
+    uint32_t *side = (uint32_t *)ws.w_db_side.p;
+    // ---- 2. union, piece by piece
+    const uint64_t E = ix->dbscan_piece ? ix->dbscan_piece : kDbscanPiece;
+    PNCHK(ws.w_sf_off.ensure((std::min(n, kSelfChunk) + 1) * sizeof(uint64_t)));
+    uint64_t *in_off = (uint64_t *)ws.w_sf_off.p;
+    for (size_t a = 0; a < n;) {
+        const size_t lim = n - a < kSelfChunk ? n : a + kSelfChunk;
+        // the last b in (a, lim] with off[b] - off[a] <= E, at least a + 1
+        size_t b = (size_t)(std::upper_bound(h_off.begin() + a + 1, h_off.begin() + lim + 1, h_off[a] + E) - h_off.begin()) - 1;
+        if (b <= a) b = a + 1;
+        const uint64_t total = h_off[b] - h_off[a];
+        if (total) {
+            PNCHK(ws.w_sf_idx.ensure(total * sizeof(uint64_t)));
+            uint64_t *in_idx = (uint64_t *)ws.w_sf_idx.p;
+            PNCHK(radius_device_enqueue<T>(ix, ws, (const T *)ix->d_pts + a * ix->ld, b - a, ix->dim, ix->ld, eps, in_off, in_idx,
+                                           (size_t)total, nullptr, s, nullptr, 0, false));
+            HIPCHK(launch_dbscan_union(in_off, in_idx, total, b - a, a, n, ix->index_base, core, parent, side_off, side, s));
+        }
+        a = b;
+    }
+    // ---- 3. finish
+    HIPCHK(launch_dbscan_flatten(parent, core, n, root, word, s));  // word = root flags
+    HIPCHK(launch_exclusive_scan_u32(word, n, num, scan, d_ncl, s));
+    HIPCHK(launch_dbscan_label(root, num, core, side_off, side, n, d_labels, s));
+    if (d_core) HIPCHK(hipMemcpyAsync(d_core, core, n, hipMemcpyDeviceToDevice, s));
+    return PN_OK;
+}
+template <typename T>
+static int dbscan_device(const pn_index *ix, T eps, size_t min_samples, unsigned flags, int64_t *d_labels, uint8_t *d_core,
+                         uint64_t *d_ncl, hipStream_t s) {
+    PNCHK(dbscan_args(ix, flags, min_samples, d_labels, (int)sizeof(T)));
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    lease.s = s;
+    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
+    return dbscan_enqueue<T>(ix, *lease.ws, eps, min_samples, d_labels, d_core, d_ncl, s);
+}
+template <typename T>
+static int dbscan_host(const pn_index *ix, T eps, size_t min_samples, unsigned flags, int64_t *labels, uint8_t *core,
+                       uint64_t *n_clusters) {
+    PNCHK(dbscan_args(ix, flags, min_samples, labels, (int)sizeof(T)));
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
+    Workspace &ws = *lease.ws;
+    hipStream_t s = lease.s;
+    const size_t n = ix->n;
+    PNCHK(ws.w_db_out.ensure((n + 1) * sizeof(uint64_t) + n));
+    int64_t *d_labels = (int64_t *)ws.w_db_out.p;
+    uint64_t *d_ncl = (uint64_t *)(d_labels + n);
+    uint8_t *d_core = (uint8_t *)(d_ncl + 1);
+    PNCHK(dbscan_enqueue<T>(ix, ws, eps, min_samples, d_labels, d_core, d_ncl, s));
+    HIPCHK(hipMemcpyAsync(labels, d_labels, n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    if (core) HIPCHK(hipMemcpyAsync(core, d_core, n, hipMemcpyDeviceToHost, s));
+    if (n_clusters) HIPCHK(hipMemcpyAsync(n_clusters, d_ncl, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return PN_OK;
+}
+extern "C" int pn_dbscan_f32(const pn_index *ix, float eps, size_t min_samples, unsigned flags, int64_t *labels,
+                             uint8_t *core, uint64_t *n_clusters) {
+    return dbscan_host<float>(ix, eps, min_samples, flags, labels, core, n_clusters);
+}
+extern "C" int pn_dbscan_f64(const pn_index *ix, double eps, size_t min_samples, unsigned flags, int64_t *labels,
+                             uint8_t *core, uint64_t *n_clusters) {
+    return dbscan_host<double>(ix, eps, min_samples, flags, labels, core, n_clusters);
+}
+extern "C" int pn_dbscan_device_f32(const pn_index *ix, float eps, size_t min_samples, unsigned flags, int64_t *d_labels,
+                                    uint8_t *d_core, uint64_t *d_n_clusters, void *stream) {
+    return dbscan_device<float>(ix, eps, min_samples, flags, d_labels, d_core, d_n_clusters, (hipStream_t)stream);
+}
+extern "C" int pn_dbscan_device_f64(const pn_index *ix, double eps, size_t min_samples, unsigned flags, int64_t *d_labels,
+                                    uint8_t *d_core, uint64_t *d_n_clusters, void *stream) {
+    return dbscan_device<double>(ix, eps, min_samples, flags, d_labels, d_core, d_n_clusters, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------

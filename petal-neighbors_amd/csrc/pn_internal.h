@@ -149,6 +149,24 @@ hipError_t launch_radius_self_compact_f64(const uint64_t *in_off, const uint64_t
                                           uint64_t self0, uint64_t *out_idx, double *out_dist, uint64_t cap, uint32_t *bad,
                                           hipStream_t s);
 
+// ---- components.hip: DBSCAN over the radius self-lists (pn_dbscan_*): lock-free union-find on the core rows
+// core[i] <- off[i + 1] - off[i] >= min_samples; parent[i] <- i; side_len[i] <- core[i] ? 0 : the list's length
+hipError_t launch_dbscan_init(const uint64_t *off, size_t n, uint64_t min_samples, uint8_t *core, uint32_t *parent,
+                              uint32_t *side_len, hipStream_t s);
+// a piece's lists (rows r0 .. r0 + nq, entries base + j, all of them below in_cap): core rows are united with the core rows
+// of their lists, non-core rows copy theirs to side[side_off[row] ..], non-core entries as 0xFFFFFFFF
+hipError_t launch_dbscan_union(const uint64_t *in_off, const uint64_t *in_idx, uint64_t in_cap, size_t nq, size_t r0,
+                               size_t n, uint64_t base, const uint8_t *core, uint32_t *parent, const uint64_t *side_off,
+                               uint32_t *side, hipStream_t s);
+// root[i] <- find(i) (core rows, else 0xFFFFFFFF); is_root[i] <- root[i] == i
+hipError_t launch_dbscan_flatten(uint32_t *parent, const uint8_t *core, size_t n, uint32_t *root, uint32_t *is_root,
+                                 hipStream_t s);
+// labels[i] <- num[root[i]] (core) | num[smallest root in the side list] (border) | -1; num = exclusive scan of is_root
+hipError_t launch_dbscan_label(const uint32_t *root, const uint64_t *num, const uint8_t *core, const uint64_t *side_off,
+                               const uint32_t *side, size_t n, int64_t *labels, hipStream_t s);
+// labels <- -1, core (nullable) <- 0, *n_clusters (nullable) <- 0
+hipError_t launch_dbscan_noise(size_t n, int64_t *labels, uint8_t *core, uint64_t *n_clusters, hipStream_t s);
+
 // ---- csr_sort.hip: order every list of a radius answer by (distance, index) in place (PN_RADIUS_SORTED)
 constexpr int kSortTile = 2048;  // longest list sorted by one workgroup in LDS; longer lists: chunks + merge passes
 struct CsrSortScratch {
