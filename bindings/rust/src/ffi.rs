@@ -114,6 +114,17 @@ extern "C" {
                                 d_core: *mut u8, d_n_clusters: *mut u64, stream: *mut c_void) -> c_int;
     pub fn pn_dbscan_device_f64(index: *const pn_index, eps: f64, min_samples: usize, flags: c_uint, d_labels: *mut i64,
                                 d_core: *mut u8, d_n_clusters: *mut u64, stream: *mut c_void) -> c_int;
+    /// Minimum spanning tree under mutual reachability: core [n] (nullable: no cores), src / dst / weight [n - 1] ascending
+    /// by (weight, src, dst), work_out (nullable, a host pointer in both variants) = {rounds, rows scanned}; flags = 0.
+    /// The device entry points write in stream order and block the host once per round
+    pub fn pn_mst_f32(index: *const pn_index, core: *const f32, flags: c_uint, src_out: *mut u64, dst_out: *mut u64,
+                      weight_out: *mut f32, work_out: *mut u64) -> c_int;
+    pub fn pn_mst_f64(index: *const pn_index, core: *const f64, flags: c_uint, src_out: *mut u64, dst_out: *mut u64,
+                      weight_out: *mut f64, work_out: *mut u64) -> c_int;
+    pub fn pn_mst_device_f32(index: *const pn_index, d_core: *const f32, flags: c_uint, d_src: *mut u64, d_dst: *mut u64,
+                             d_weight: *mut f32, work_out: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn pn_mst_device_f64(index: *const pn_index, d_core: *const f64, flags: c_uint, d_src: *mut u64, d_dst: *mut u64,
+                             d_weight: *mut f64, work_out: *mut u64, stream: *mut c_void) -> c_int;
     /// dist_out nullable (PN_RADIUS_SORTED needs it); *idx_out / *dist_out released with pn_free
     pub fn pn_query_radius_self_f32(index: *const pn_index, radius: f32, flags: c_uint, offsets: *mut u64,
                                     idx_out: *mut *mut u64, dist_out: *mut *mut f32) -> c_int;

@@ -60,7 +60,7 @@ extern "C" {
  * pn_sharded_query_radius_with_distance_{,device_}{f32,f64}, PN_RADIUS_SORTED; pn_query_self_{,device_}{f32,f64},
  * pn_query_radius_self_{,device_}{f32,f64}, PN_SELF_INCLUDE; pn_sharded_query_self_{,device_}{f32,f64},
  * pn_sharded_query_radius_self_{,device_}{f32,f64}; pn_query_radii_{,device_,self_,self_device_}{f32,f64};
- * pn_dbscan_{,device_}{f32,f64}, PN_OPT_DBSCAN_PIECE. */
+ * pn_dbscan_{,device_}{f32,f64}, PN_OPT_DBSCAN_PIECE; pn_mst_{,device_}{f32,f64}, PN_OPT_MST_BATCH. */
 #define PN_ABI_VERSION 3
 
 /* ---- error codes.  EMPTY / NOT_CONTIGUOUS are ArrayError (src/lib.rs:9-16). */
@@ -112,9 +112,12 @@ enum {
                                   (pn_info.seed_model): 1 (default) = k-NN calls with k <= 128 take their starting
                                   thresholds from the model (no scout launch); 0 = always scout.  Never changes a result:
                                   a threshold only decides which tier answers a query. */
-    PN_OPT_DBSCAN_PIECE = 11     /* pn_dbscan_*: the most list entries (64-bit indices in workspace scratch) one piece of
+    PN_OPT_DBSCAN_PIECE = 11,    /* pn_dbscan_*: the most list entries (64-bit indices in workspace scratch) one piece of
                                   the union stage holds; 0 (default) = 2^27, i.e. 1 GiB.  A row whose own list is longer
                                   is a piece of its own.  Never changes a result. */
+    PN_OPT_MST_BATCH = 12        /* pn_mst_*: the most listed rows one scan launch takes; 0 (default) = 2^18, the
+                                  self-queries' chunk; negative: PN_ERR_INVALID.  Never changes a result (it lets tests
+                                  force several launches per round at small n). */
 };
 
 typedef struct pn_index pn_index;
@@ -398,6 +401,41 @@ int pn_dbscan_device_f32(const pn_index *index, float eps, size_t min_samples, u
                          uint8_t *d_core, uint64_t *d_n_clusters, void *stream);
 int pn_dbscan_device_f64(const pn_index *index, double eps, size_t min_samples, unsigned flags, int64_t *d_labels,
                          uint8_t *d_core, uint64_t *d_n_clusters, void *stream);
+
+/* ---- Minimum spanning tree of the indexed rows under mutual reachability (HDBSCAN; single linkage without cores),
+ * exact and on the device.  The graph is complete over the n rows; the edge {i, j}, i < j, weighs
+ *     w(i, j) = max(d(i, j), core[i], core[j]),
+ * d = the index's metric.distance(p_i, p_j), bit-identical to the reference and symmetric bit for bit, the maximum taken in
+ * the library's key order: NaN above +inf, -0 counts as +0 (a weight is written as the value of its key: -0 as +0, any NaN
+ * as the canonical quiet NaN); a Cosine index orders all floats, on a Euclidean index a negative core value acts as 0.
+ * core: n values of the index's element type, row i's core distance -- for HDBSCAN the distance to its min_samples-th
+ * nearest OTHER row, the last column of pn_query_self_*(min_samples) (scikit-learn counts the row itself: its m is this
+ * library's m - 1).  core == NULL: no cores, w = d -- the Euclidean / Cosine MST, i.e. single linkage (on a Euclidean index
+ * the same as all zeros).
+ * Edges are totally ordered by (key(w), i, j), and the answer is THE minimum spanning tree under that strict order: n - 1
+ * edges with src < dst (PN_OPT_INDEX_BASE added to both ends), written ascending in that order -- the merge order of a
+ * single-linkage dendrogram.  Because the order is strict the result depends on the data alone, not on scheduling, the
+ * engine or PN_OPT_MST_BATCH.  Rows with NaN coordinates are vertices like any other: their edges weigh NaN and come last.
+ * n = 1 writes nothing and succeeds.
+ * flags must be 0.  Argument errors, before any device is touched and in this order: flags != 0, a NULL output with n > 1,
+ * NULL index, wrong element type: PN_ERR_INVALID; more than 2^31 - 1 rows: PN_ERR_UNSUPPORTED.  pn_stats.queries counts n.
+ * work_out (nullable, a HOST pointer in both variants) receives {rounds, rows scanned}: the Boruvka rounds run, and the rows
+ * handed to a scan summed over the rounds (a round answered by the k-NN pipeline counts n).  Without cores round 0 is
+ * pn_query_self_device_*(k = 1) on the handle's engine; every other round is an exact masked scan of the rows whose cached
+ * candidate has joined their own component.  Device memory beyond a 2^18-query batch's workspace: about
+ * 100 bytes per row (f64: 130).
+ * Device entry points: d_core (nullable) and the outputs in HBM, written in stream order on `stream`; the call BLOCKS THE
+ * HOST ONCE PER ROUND, to read the number of components left and the length of the list of rows to scan -- like
+ * pn_dbscan_device_* it is not capturable into a graph.
+ * Not in this version: row-sharded handles (pn_sharded_*), and a first-tier (bf16) filter for the masked scans. */
+int pn_mst_f32(const pn_index *index, const float *core, unsigned flags, uint64_t *src_out, uint64_t *dst_out,
+               float *weight_out, uint64_t *work_out);
+int pn_mst_f64(const pn_index *index, const double *core, unsigned flags, uint64_t *src_out, uint64_t *dst_out,
+               double *weight_out, uint64_t *work_out);
+int pn_mst_device_f32(const pn_index *index, const float *d_core, unsigned flags, uint64_t *d_src, uint64_t *d_dst,
+                      float *d_weight, uint64_t *work_out, void *stream);
+int pn_mst_device_f64(const pn_index *index, const double *d_core, unsigned flags, uint64_t *d_src, uint64_t *d_dst,
+                      double *d_weight, uint64_t *work_out, void *stream);
 
 /* ---- distance::pairwise(x, &Euclidean) (src/distance.rs:58-74): n x n
  * symmetric matrix, zero diagonal, n < 2 -> zeros. Host in, host out. */

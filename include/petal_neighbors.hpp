@@ -87,6 +87,13 @@ struct Dbscan {
     std::vector<uint8_t> core;    // [n]: 1 = core row
     size_t n_clusters = 0;
 };
+// the answer of BallTree::mst: n - 1 edges with src < dst, ascending by (weight, src, dst)
+template <typename A>
+struct Mst {
+    std::vector<size_t> src, dst;
+    std::vector<A> weight;
+    size_t rounds = 0, rows_scanned = 0;  // Boruvka rounds run, rows handed to a scan over all of them
+};
 // the CSR answer of BallTree::query_radius_self: row i's neighbours are idx[offsets[i] .. offsets[i + 1]] (dist beside
 // them when asked for)
 template <typename A>
@@ -287,6 +294,26 @@ class BallTree {
         else
             check(pn_dbscan_f64(h_, eps, min_samples, 0u, res.labels.data(), res.core.data(), &ncl));
         res.n_clusters = (size_t)ncl;
+        return res;
+    }
+    // extension: the minimum spanning tree of the indexed rows under mutual reachability (pn_mst_*): edge {i, j} weighs
+    // max(distance(i, j), core[i], core[j]), edges are ordered by (weight, i, j), the tree is the unique one under that
+    // strict order.  core: size() values, row i's core distance -- for HDBSCAN the distance to its min_samples-th nearest
+    // OTHER row -- or nullptr for the plain Euclidean / Cosine MST (single linkage)
+    Mst<A> mst(const A *core = nullptr) const {
+        Mst<A> res;
+        const size_t ne = n_ ? n_ - 1 : 0;
+        std::vector<uint64_t> src(ne), dst(ne);
+        res.weight.resize(ne);
+        uint64_t work[2] = {0, 0};
+        if constexpr (kF32)
+            check(pn_mst_f32(h_, core, 0u, src.data(), dst.data(), res.weight.data(), work));
+        else
+            check(pn_mst_f64(h_, core, 0u, src.data(), dst.data(), res.weight.data(), work));
+        res.src.assign(src.begin(), src.end());
+        res.dst.assign(dst.begin(), dst.end());
+        res.rounds = (size_t)work[0];
+        res.rows_scanned = (size_t)work[1];
         return res;
     }
     // extension: one radius per row (pn_query_radii_self_*): radii [size()], row i's list is the scalar overload's for

@@ -23,6 +23,7 @@ PN_OPT_SHARED_THRESHOLDS = 8
 PN_OPT_BF16_WAVES = 9
 PN_OPT_SEED_MODEL = 10
 PN_OPT_DBSCAN_PIECE = 11
+PN_OPT_MST_BATCH = 12
 PN_RADIUS_SORTED = 1
 PN_SELF_INCLUDE = 2
 
@@ -106,6 +107,10 @@ SIGNATURES = {
     "pn_dbscan_f64": (_i, [_vp, C.c_double, _sz, C.c_uint, _vp, _vp, _vp]),
     "pn_dbscan_device_f32": (_i, [_vp, C.c_float, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
     "pn_dbscan_device_f64": (_i, [_vp, C.c_double, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
+    "pn_mst_f32": (_i, [_vp, _vp, C.c_uint, _vp, _vp, _vp, _vp]),
+    "pn_mst_f64": (_i, [_vp, _vp, C.c_uint, _vp, _vp, _vp, _vp]),
+    "pn_mst_device_f32": (_i, [_vp, _vp, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
+    "pn_mst_device_f64": (_i, [_vp, _vp, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
     "pn_free": (None, [_vp]),
     "pn_pairwise_f32": (_i, [_vp, _sz, _sz, _ssz, _i, _vp]),
     "pn_pairwise_f64": (_i, [_vp, _sz, _sz, _ssz, _i, _vp]),

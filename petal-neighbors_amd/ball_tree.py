@@ -595,3 +595,67 @@ class BallTree:
         check(getattr(_lib.lib(), f"pn_dbscan_device_{self._sfx}")(
             self._h, e, m, 0, labels.data_ptr(), core.data_ptr(), ncl.data_ptr(), C.c_void_p(st)))
         return labels, core, ncl
+
+    # ---------------------------------------------------------------------- MST
+    # The minimum spanning tree of the indexed rows under mutual reachability (``pn_mst_*``): edge {i, j} weighs
+    # max(d(i, j), core[i], core[j]), edges are ordered by (weight, i, j) and the tree is the unique one under that strict
+    # order, its n - 1 edges written ascending -- the merge order of a single-linkage dendrogram.  ``core[i]`` is row i's
+    # core distance: for HDBSCAN the distance to its ``min_samples``-th nearest OTHER row, ``query_self(min_samples)``'s
+    # last column (scikit-learn counts the row itself, so its m is this library's m - 1).  ``core=None``: the plain
+    # Euclidean / Cosine MST (single linkage).
+    def mst(self, core=None):
+        """``(src uint64 [n-1], dst uint64 [n-1], weight [n-1])`` with ``src < dst``, ascending by (weight, src, dst).
+        ``core``: None or n values (converted to the tree's element type).  ``self.last_mst_work`` then holds
+        ``(rounds, rows scanned)``."""
+        c = None
+        if core is not None:
+            c = np.ascontiguousarray(core, dtype=self.dtype)
+            if c.ndim != 1 or c.shape[0] != self._n:
+                raise ValueError(f"core must hold one value per indexed row ({self._n})")
+        ne = max(self._n - 1, 0)
+        src = np.empty(ne, dtype=np.uint64)
+        dst = np.empty(ne, dtype=np.uint64)
+        weight = np.empty(ne, dtype=self.dtype)
+        work = np.zeros(2, dtype=np.uint64)
+        check(getattr(_lib.lib(), f"pn_mst_{self._sfx}")(self._h, c.ctypes.data if c is not None else None, 0,
+                                                       src.ctypes.data, dst.ctypes.data, weight.ctypes.data,
+                                                       work.ctypes.data))
+        self.last_mst_work = (int(work[0]), int(work[1]))
+        return src, dst, weight
+
+    def mst_device(self, core=None, out_src=None, out_dst=None, out_weight=None, stream=None):
+        """``mst`` in HBM: ``core`` None or a 1-D CUDA tensor of n values of the tree's element type; CUDA tensors
+        ``(src int64 [n-1], dst int64 [n-1], weight [n-1])`` written in stream order on ``stream`` (default: the current
+        torch stream).  The call waits for the device once per Boruvka round."""
+        import torch
+        tdt = torch.float32 if self._sfx == "f32" else torch.float64
+        dev = torch.device("cuda", self.device)
+        ne = max(self._n - 1, 0)
+        if core is not None:
+            if not isinstance(core, torch.Tensor):
+                raise ValueError("core must be a CUDA tensor (or None)")
+            if core.dtype != tdt or core.dim() != 1 or core.numel() != self._n or not core.is_cuda:
+                raise ValueError(f"core must be a 1-D CUDA tensor of {self._n} values of the tree's element type")
+            core = core.contiguous()
+        for t, want in ((out_src, torch.int64), (out_dst, torch.int64), (out_weight, tdt)):
+            if t is not None and (t.dtype != want or t.numel() < ne or not t.is_contiguous()):
+                raise ValueError("output tensors are too small or of the wrong type")
+        src = out_src if out_src is not None else torch.empty(ne, dtype=torch.int64, device=dev)
+        dst = out_dst if out_dst is not None else torch.empty(ne, dtype=torch.int64, device=dev)
+        weight = out_weight if out_weight is not None else torch.empty(ne, dtype=tdt, device=dev)
+        work = np.zeros(2, dtype=np.uint64)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        check(getattr(_lib.lib(), f"pn_mst_device_{self._sfx}")(
+            self._h, core.data_ptr() if core is not None else None, 0, src.data_ptr(), dst.data_ptr(), weight.data_ptr(),
+            work.ctypes.data, C.c_void_p(st)))
+        self.last_mst_work = (int(work[0]), int(work[1]))
+        return src, dst, weight
+
+    def mutual_reachability_mst(self, min_samples: int):
+        """HDBSCAN's tree without leaving HBM: ``query_self_device(min_samples)``'s last column -- the distance to the
+        ``min_samples``-th nearest other row -- fed to ``mst_device``, all on the current torch stream.  Returns CUDA
+        tensors ``(src, dst, weight)``."""
+        if int(min_samples) < 1 or int(min_samples) > self._n - 1:
+            raise ValueError("min_samples must be in [1, n - 1]")
+        _, dist = self.query_self_device(int(min_samples))
+        return self.mst_device(dist[:, -1].contiguous())

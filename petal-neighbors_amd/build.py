@@ -43,6 +43,7 @@ UNITS = [
     ("csr_sort.hip", []),
     ("self_graph.hip", ["-ffp-contract=off"]),
     ("components.hip", []),
+    ("mst.hip", []),
     ("radii_tau.hip", ["-ffp-contract=off"]),
     ("metric.cpp", ["-ffp-contract=off"]),
     ("tree.cpp", ["-ffp-contract=off"]),
@@ -50,6 +51,7 @@ UNITS = [
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
           "-fno-fast-math", "-fhip-fp32-correctly-rounded-divide-sqrt"]
 HEADERS = [os.path.join(CSRC, "pn_internal.h"), os.path.join(CSRC, "topk_buffer.h"), os.path.join(CSRC, "host_tree.h"),
+           os.path.join(CSRC, "union_find.h"),
            os.path.join(os.path.dirname(HERE), "include", "petal_mi355x.h")]
 
 

@@ -592,4 +592,139 @@ hipError_t launch_cosine_pairwise_f64(const double *X, size_t n, int dim, size_t
     return launch_cosine_pairwise<double>(X, n, dim, ld, norms, out, s);
 }
 
+// ---------------------------------------------------------------------------
+// Masked nearest-outside-row scan of pn_mst_* (mst.hip): for each listed row i = qsel[r] the least edge, in edge order,
+// from i to any row j of another component.  The edge {i, j} weighs w = max(d(i, j), core[i], core[j]) in key order, and
+// the edges are ordered by (key(w), min(i, j), max(i, j)).  For a FIXED i that order over j is simply ascending
+// (key(w(i, j)), j): j < i < j' compares (j, i) with (i, j') -- decided by j < i -- and two partners on the same side of i
+// differ in the one coordinate that is not i.  That is what makes a per-row minimum of (key, j) enough.
+//
+// Built on compute_tile: the listed rows are the queries, read in place through qsel, every row of the index is the other
+// side; d is the reference's fold, bit for bit, and symmetric bit for bit (q - p and p - q differ in sign only and are
+// squared; q * p and |q| * |p| commute), so both ends of an edge see the same key.  The epilogue masks the pairs inside one
+// component (comp[j] == comp[i], which covers j == i) and keeps one running minimum (key, j) per (lane, query) -- no
+// candidate buffers.  A lane meets its rows in ascending j, so a strict '<' keeps the smallest j among equal keys; a wave
+// whose 16 x 64 block lies inside one component skips the epilogue.  The 16 lanes that share a query reduce in registers
+// (xor shuffles over the lane bits above the query's two); the segments of a query leave their minima in
+// seg_key / seg_j [seg][nq_pad], reduced by mst.hip -- a pure minimum at every level, so the answer depends on the data alone.
+// comp[] and ckey[] (the rows' core keys) come from earlier launches and are read plainly.
+// ---------------------------------------------------------------------------
+template <typename T, bool COS>
+__global__ __launch_bounds__(256) void mst_scan_kernel(const T *__restrict__ P, size_t n, int dim, size_t ldp,
+                                                       const uint32_t *__restrict__ qsel, int nq, size_t seg_len,
+                                                       const uint32_t *__restrict__ comp,
+                                                       const typename KeyOf<T>::type *__restrict__ ckey,
+                                                       const T *__restrict__ cnorm,
+                                                       typename KeyOf<T>::type *__restrict__ seg_key,
+                                                       uint32_t *__restrict__ seg_j, size_t nq_pad) {
+    using KeyT = typename KeyOf<T>::type;
+    constexpr KeyT KMAX = KeyOf<T>::kMax;
+    __shared__ __attribute__((aligned(32))) T Qs[kChunkK][kTileQ];
+    __shared__ __attribute__((aligned(32))) T Ps[kChunkK][kTileP];
+
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tq = lane & 3, tp = lane >> 2;
+    const int qb = wave * 16 + tq * 4, pb = tp * 4;
+    const size_t q0 = (size_t)blockIdx.x * kTileQ;
+    const size_t seg = blockIdx.y;
+    const size_t p_begin = seg * seg_len < n ? seg * seg_len : n;
+    const size_t p_end = (p_begin + seg_len < n) ? p_begin + seg_len : n;
+
+    const uint32_t *qsel_t = qsel + q0;
+    const int q_valid = (int)((size_t)nq - q0 < (size_t)kTileQ ? (size_t)nq - q0 : (size_t)kTileQ);
+    uint32_t qc[4];
+    KeyT qk[4], bk[4];
+    uint32_t bj[4];
+    T qn4[4];
+    bool qv[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        qv[a] = qb + a < q_valid;
+        const uint32_t row = qsel_t[qv[a] ? qb + a : 0];
+        qc[a] = comp[row];
+        qk[a] = ckey[row];
+        qn4[a] = COS ? cnorm[row] : (T)0;
+        bk[a] = KMAX;
+        bj[a] = 0xFFFFFFFFu;
+    }
+    bool first = true;
+    for (size_t p0 = p_begin; p0 < p_end; p0 += kTileP) {
+        T acc[4][4];
+        compute_tile<T, COS>(P + p0 * ldp, ldp, P, ldp, dim, first, acc, Qs, Ps, tid, qb, pb, qsel_t, q_valid);
+        first = false;
+        uint32_t pc[4];
+        KeyT pk[4];
+        T pn4[4];
+        bool mixed = false;  // some pair of this lane's block joins two components
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const size_t j = p0 + pb + b;
+            const bool v = j < p_end;
+            pc[b] = v ? comp[j] : 0u;
+            pk[b] = v ? ckey[j] : (KeyT)0;
+            pn4[b] = (COS && v) ? cnorm[j] : (T)1;
+#pragma unroll
+            for (int a = 0; a < 4; ++a) mixed |= v && qv[a] && pc[b] != qc[a];
+        }
+        if (!__any(mixed)) continue;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const size_t j = p0 + pb + b;
+                const bool v = qv[a] && j < p_end && pc[b] != qc[a];
+                KeyT kk = COS ? dist_key_signed((T)1 - acc[a][b] / (qn4[a] * pn4[b])) : dist_key(pn_sqrt(acc[a][b]));
+                kk = kk > qk[a] ? kk : qk[a];
+                kk = kk > pk[b] ? kk : pk[b];
+                if (v && kk < bk[a]) {  // (strict: j ascends within a lane)
+                    bk[a] = kk;
+                    bj[a] = (uint32_t)j;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+#pragma unroll
+        for (int m = 4; m < 64; m <<= 1) {
+            const KeyT ok = __shfl_xor(bk[a], m);
+            const uint32_t oj = __shfl_xor(bj[a], m);
+            if (ok < bk[a] || (ok == bk[a] && oj < bj[a])) {
+                bk[a] = ok;
+                bj[a] = oj;
+            }
+        }
+        if (tp == 0) {  // (queries beyond nq: KMAX / none, inside the padded row of the buffers)
+            seg_key[seg * nq_pad + q0 + qb + a] = bk[a];
+            seg_j[seg * nq_pad + q0 + qb + a] = bj[a];
+        }
+    }
+}
+
+template <typename T>
+static hipError_t launch_mst_scan(const T *P, size_t n, int dim, size_t ldp, const uint32_t *qsel, int nq, size_t seg_len,
+                                  int nseg, const uint32_t *comp, const typename KeyOf<T>::type *ckey, const T *cnorm,
+                                  typename KeyOf<T>::type *seg_key, uint32_t *seg_j, hipStream_t s) {
+    if (nq <= 0) return hipSuccess;
+    const size_t nq_pad = round_up((size_t)nq, kTileQ);
+    dim3 grid((unsigned)(nq_pad / kTileQ), (unsigned)nseg), block(256);
+    if (cnorm)
+        hipLaunchKernelGGL((mst_scan_kernel<T, true>), grid, block, 0, s, P, n, dim, ldp, qsel, nq, seg_len, comp, ckey, cnorm,
+                           seg_key, seg_j, nq_pad);
+    else
+        hipLaunchKernelGGL((mst_scan_kernel<T, false>), grid, block, 0, s, P, n, dim, ldp, qsel, nq, seg_len, comp, ckey, cnorm,
+                           seg_key, seg_j, nq_pad);
+    return hipGetLastError();
+}
+hipError_t launch_mst_scan_f32(const float *P, size_t n, int dim, size_t ldp, const uint32_t *qsel, int nq, size_t seg_len,
+                               int nseg, const uint32_t *comp, const uint32_t *ckey, const float *cnorm, uint32_t *seg_key,
+                               uint32_t *seg_j, hipStream_t s) {
+    return launch_mst_scan<float>(P, n, dim, ldp, qsel, nq, seg_len, nseg, comp, ckey, cnorm, seg_key, seg_j, s);
+}
+hipError_t launch_mst_scan_f64(const double *P, size_t n, int dim, size_t ldp, const uint32_t *qsel, int nq, size_t seg_len,
+                               int nseg, const uint32_t *comp, const uint64_t *ckey, const double *cnorm, uint64_t *seg_key,
+                               uint32_t *seg_j, hipStream_t s) {
+    return launch_mst_scan<double>(P, n, dim, ldp, qsel, nq, seg_len, nseg, comp, ckey, cnorm, seg_key, seg_j, s);
+}
+
 }  // namespace pn

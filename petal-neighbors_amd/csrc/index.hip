@@ -150,6 +150,8 @@ struct Workspace {
     // pn_dbscan_*: the O(n) arrays of a call (offsets, parents, roots, ... carved from one buffer), the border rows' side
     // lists, and the host entry's outputs
     DevBuf w_db, w_db_side, w_db_out;
+    // pn_mst_*: the scratch of mst.hip (+ round 0's 1-NN answer), and the host entry's core distances and outputs
+    DevBuf w_mst, w_mst_io;
     // small calls (tiny_*): mapped pinned host memory the one kernel of the call reads its queries from and writes its
     // answers to -- no copy commands
     void *pin_in = nullptr, *pin_out = nullptr;
@@ -175,7 +177,7 @@ struct Workspace {
     hipEvent_t done = nullptr;
     hipStream_t last_stream = nullptr;
     bool in_flight = false;
-    DevBuf *all[55] = {&w_db, &w_db_side, &w_db_out, &w_hrad, &w_sf_idx, &w_sf_dist, &w_sf_off, &w_sf_coff, &w_sf_flag, &w_sf_cnt, &w_sf_scan, &w_sf_hoff, &w_cs_hoff, &w_rkd, &w_cs_nch, &w_cs_off, &w_cs_scan, &w_cs_idx, &w_cs_dist, &w_gqn, &w_rpos, &w_rfin, &w_rcx, &w_rox, &w_rscan, &w_q, &w_qnorm, &w_qnrm, &w_keys, &w_idx, &w_cnt, &w_tau, &w_flags, &w_sel, &w_misc, &w2_keys, &w2_idx,
+    DevBuf *all[57] = {&w_mst, &w_mst_io, &w_db, &w_db_side, &w_db_out, &w_hrad, &w_sf_idx, &w_sf_dist, &w_sf_off, &w_sf_coff, &w_sf_flag, &w_sf_cnt, &w_sf_scan, &w_sf_hoff, &w_cs_hoff, &w_rkd, &w_cs_nch, &w_cs_off, &w_cs_scan, &w_cs_idx, &w_cs_dist, &w_gqn, &w_rpos, &w_rfin, &w_rcx, &w_rox, &w_rscan, &w_q, &w_qnorm, &w_qnrm, &w_keys, &w_idx, &w_cnt, &w_tau, &w_flags, &w_sel, &w_misc, &w2_keys, &w2_idx,
                        &w2_cnt, &w2_tau, &w_lo, &w_bq, &w_qn, &w_qbad, &w_gq, &w_gidx, &w_gdist, &w_gsel, &w_seed,
                        &w_qstat, &w_lists, &w_hq, &w_hidx, &w_hdist, &w_fparts, &w_pcnt};
     std::vector<void *> retired;  // outgrown allocations, freed once `done` has passed (DevBuf::ensure)
@@ -243,6 +245,7 @@ struct pn_index {
     bool sm_ok = false;
     int seed_model = 1;      // PN_OPT_SEED_MODEL: 1 (default) use it where it was accepted, 0 never
     uint64_t dbscan_piece = 0;  // PN_OPT_DBSCAN_PIECE: list entries per piece of pn_dbscan_*, 0 = 2^27
+    uint64_t mst_batch = 0;     // PN_OPT_MST_BATCH: listed rows per scan launch of pn_mst_*, 0 = 2^18
     // state that queries on a shared `const pn_index *` update: internally synchronised by `mu`
     struct Shared {
         std::mutex mu;
@@ -999,6 +1002,10 @@ extern "C" int pn_index_set_option(pn_index *ix, int option, int64_t value) {
         case PN_OPT_DBSCAN_PIECE:
             if (value < 0) return fail(PN_ERR_INVALID, "bad DBSCAN piece size");
             ix->dbscan_piece = (uint64_t)value;
+            return PN_OK;
+        case PN_OPT_MST_BATCH:
+            if (value < 0) return fail(PN_ERR_INVALID, "bad MST batch size");
+            ix->mst_batch = (uint64_t)value;
             return PN_OK;
         default: return fail(PN_ERR_INVALID, "unknown option %d", option);
     }
@@ -3745,6 +3752,127 @@ extern "C" int pn_dbscan_device_f32(const pn_index *ix, float eps, size_t min_sa
 extern "C" int pn_dbscan_device_f64(const pn_index *ix, double eps, size_t min_samples, unsigned flags, int64_t *d_labels,
                                     uint8_t *d_core, uint64_t *d_n_clusters, void *stream) {
     return dbscan_device<double>(ix, eps, min_samples, flags, d_labels, d_core, d_n_clusters, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------
+// Minimum spanning tree under mutual reachability: pn_mst_{,device_}{f32,f64} (the rounds, their kernels and the argument
+// for a result that depends on the data alone: mst.hip; the masked scan: exact_scan.hip).  Here: the argument checks, the
+// workspace, and round 0 of an un-cored call -- every row's nearest other row by (distance, index), which is the k = 1
+// self-query and so goes through query_enqueue and whichever tier the handle's engine selects.
+// ---------------------------------------------------------------------------
+static int mst_args(const pn_index *ix, unsigned flags, const void *src, const void *dst, const void *weight, int elem_bytes) {
+    if (flags) return fail(PN_ERR_INVALID, "unknown MST flags 0x%x", flags);
+    if ((!src || !dst || !weight) && (!ix || ix->n > 1))
+        return fail(PN_ERR_INVALID, "%s is NULL", !src ? "src_out" : !dst ? "dst_out" : "weight_out");
+    if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
+    if (ix->elem_bytes != elem_bytes) return fail(PN_ERR_INVALID, "index element type mismatch");
+    if (ix->n > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many rows for an MST (32-bit components)");
+    return PN_OK;
+}
+// in a held workspace, on stream s; d_core nullable, outputs in HBM; blocks the host once per round
+template <typename T>
+static int mst_run(const pn_index *ix, Workspace &ws, const T *d_core, uint64_t *d_src, uint64_t *d_dst, T *d_weight,
+                   uint64_t *work_out, hipStream_t s) {
+    const size_t n = ix->n;
+    if (work_out) work_out[0] = work_out[1] = 0;
+    if (n < 2) {
+        std::lock_guard<std::mutex> lk(ix->sh.mu);
+        ix->sh.stats.queries += n;
+        return PN_OK;
+    }
+    MstArgs a;
+    a.P = ix->d_pts;
+    a.n = n;
+    a.ld = ix->ld;
+    a.dim = (int)ix->dim;
+    a.cnorm = ix->metric == 1 ? ix->d_cnorm : nullptr;
+    a.d_core = d_core;
+    a.index_base = ix->index_base;
+    a.batch = ix->mst_batch ? (size_t)std::min<uint64_t>(ix->mst_batch, (uint64_t)1 << 24) : kSelfChunk;
+    a.n_cu = ix->n_cu;
+    a.d_src = d_src;
+    a.d_dst = d_dst;
+    a.d_weight = d_weight;
+    const size_t scratch = round_up(mst_buffer_bytes(n, (int)sizeof(T), a.batch, a.n_cu), (size_t)16);
+    PNCHK(ws.w_mst.ensure(scratch + (d_core ? 0 : n * (sizeof(uint64_t) + sizeof(T)))));
+    a.buf = ws.w_mst.p;
+    if (!d_core) {
+        uint64_t *nn_idx = (uint64_t *)((char *)ws.w_mst.p + scratch);
+        T *nn_dist = (T *)(nn_idx + n);
+        for (size_t r0 = 0; r0 < n; r0 += kSelfChunk) {  // (counts the n queries)
+            const size_t nqc = n - r0 < kSelfChunk ? n - r0 : kSelfChunk;
+            PNCHK(self_knn_chunk<T>(ix, ws, r0, nqc, 2, 1, false, nn_idx + r0, nn_dist + r0, s));
+        }
+        a.nn_idx = nn_idx;
+        a.nn_dist = nn_dist;
+    } else {
+        std::lock_guard<std::mutex> lk(ix->sh.mu);
+        ix->sh.stats.queries += n;
+    }
+    int rc;
+    if constexpr (sizeof(T) == 4)
+        rc = mst_enqueue_f32(a, s);
+    else
+        rc = mst_enqueue_f64(a, s);
+    if (rc == PN_OK && work_out) {
+        work_out[0] = a.work[0];
+        work_out[1] = a.work[1];
+    }
+    return rc;
+}
+template <typename T>
+static int mst_device(const pn_index *ix, const T *d_core, unsigned flags, uint64_t *d_src, uint64_t *d_dst, T *d_weight,
+                      uint64_t *work_out, hipStream_t s) {
+    PNCHK(mst_args(ix, flags, d_src, d_dst, d_weight, (int)sizeof(T)));
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    lease.s = s;
+    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
+    return mst_run<T>(ix, *lease.ws, d_core, d_src, d_dst, d_weight, work_out, s);
+}
+template <typename T>
+static int mst_host(const pn_index *ix, const T *core, unsigned flags, uint64_t *src, uint64_t *dst, T *weight,
+                    uint64_t *work_out) {
+    PNCHK(mst_args(ix, flags, src, dst, weight, (int)sizeof(T)));
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
+    Workspace &ws = *lease.ws;
+    hipStream_t s = lease.s;
+    const size_t n = ix->n, ne = n ? n - 1 : 0;
+    PNCHK(ws.w_mst_io.ensure(2 * ne * sizeof(uint64_t) + (ne + n) * sizeof(T) + 64));
+    uint64_t *d_src = (uint64_t *)ws.w_mst_io.p, *d_dst = d_src + ne;
+    T *d_weight = (T *)(d_dst + ne), *d_core = nullptr;
+    if (core && n > 1) {
+        d_core = d_weight + ne;
+        HIPCHK(hipMemcpyAsync(d_core, core, n * sizeof(T), hipMemcpyHostToDevice, s));
+    }
+    PNCHK(mst_run<T>(ix, ws, d_core, d_src, d_dst, d_weight, work_out, s));
+    if (ne) {
+        HIPCHK(hipMemcpyAsync(src, d_src, ne * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(dst, d_dst, ne * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(weight, d_weight, ne * sizeof(T), hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    return PN_OK;
+}
+extern "C" int pn_mst_f32(const pn_index *ix, const float *core, unsigned flags, uint64_t *src_out, uint64_t *dst_out,
+                          float *weight_out, uint64_t *work_out) {
+    return mst_host<float>(ix, core, flags, src_out, dst_out, weight_out, work_out);
+}
+extern "C" int pn_mst_f64(const pn_index *ix, const double *core, unsigned flags, uint64_t *src_out, uint64_t *dst_out,
+                          double *weight_out, uint64_t *work_out) {
+    return mst_host<double>(ix, core, flags, src_out, dst_out, weight_out, work_out);
+}
+extern "C" int pn_mst_device_f32(const pn_index *ix, const float *d_core, unsigned flags, uint64_t *d_src, uint64_t *d_dst,
+                                 float *d_weight, uint64_t *work_out, void *stream) {
+    return mst_device<float>(ix, d_core, flags, d_src, d_dst, d_weight, work_out, (hipStream_t)stream);
+}
+extern "C" int pn_mst_device_f64(const pn_index *ix, const double *d_core, unsigned flags, uint64_t *d_src, uint64_t *d_dst,
+                                 double *d_weight, uint64_t *work_out, void *stream) {
+    return mst_device<double>(ix, d_core, flags, d_src, d_dst, d_weight, work_out, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------

@@ -167,6 +167,41 @@ hipError_t launch_dbscan_label(const uint32_t *root, const uint64_t *num, const 
 // labels <- -1, core (nullable) <- 0, *n_clusters (nullable) <- 0
 hipError_t launch_dbscan_noise(size_t n, int64_t *labels, uint8_t *core, uint64_t *n_clusters, hipStream_t s);
 
+// ---- exact_scan.hip, for mst.hip: the masked nearest-outside-row scan.  Listed row qsel[r] (r < nq) against rows
+// [0, n) in nseg segments of seg_len rows (a multiple of kTileP): seg_key / seg_j [seg][round_up(nq, kTileQ)] <- the
+// segment's least (key(max(d, core keys)), j) over rows j with comp[j] != comp[qsel[r]], or (kMax, 0xFFFFFFFF).
+// comp / ckey: [n]; cnorm: the rows' Cosine norms, NULL for Euclidean (then the keys are the unsigned ones)
+hipError_t launch_mst_scan_f32(const float *P, size_t n, int dim, size_t ldp, const uint32_t *qsel, int nq, size_t seg_len,
+                               int nseg, const uint32_t *comp, const uint32_t *ckey, const float *cnorm, uint32_t *seg_key,
+                               uint32_t *seg_j, hipStream_t s);
+hipError_t launch_mst_scan_f64(const double *P, size_t n, int dim, size_t ldp, const uint32_t *qsel, int nq, size_t seg_len,
+                               int nseg, const uint32_t *comp, const uint64_t *ckey, const double *cnorm, uint64_t *seg_key,
+                               uint32_t *seg_j, hipStream_t s);
+
+// ---- mst.hip: Boruvka under the strict edge order (pn_mst_*): bookkeeping kernels and the round loop
+struct MstArgs {
+    const void *P = nullptr;      // the index's rows [n_pad][ld] of T
+    size_t n = 0, ld = 0;
+    int dim = 0;
+    const void *cnorm = nullptr;  // Cosine: the rows' norms (T); NULL: Euclidean
+    const void *d_core = nullptr; // [n] of T in HBM, nullable (all zeros)
+    // round 0 of the un-cored call, answered by the k-NN pipeline: every row's nearest other row (index_base added) and
+    // its distance, [n] each; both NULL: round 0 is a full scan
+    const uint64_t *nn_idx = nullptr;
+    const void *nn_dist = nullptr;
+    uint64_t index_base = 0;
+    size_t batch = 0;             // listed rows per scan launch (>= 1)
+    int n_cu = 256;
+    void *buf = nullptr;          // mst_buffer_bytes() bytes of scratch
+    uint64_t *d_src = nullptr, *d_dst = nullptr;  // [n - 1]
+    void *d_weight = nullptr;     // [n - 1] of T
+    uint64_t work[2] = {0, 0};    // out: rounds, rows scanned
+};
+size_t mst_buffer_bytes(size_t n, int elem_bytes, size_t batch, int n_cu);
+// enqueues on s, blocks the host once per round; PN_OK or an error code with pn_last_error() set
+int mst_enqueue_f32(MstArgs &a, hipStream_t s);
+int mst_enqueue_f64(MstArgs &a, hipStream_t s);
+
 // ---- csr_sort.hip: order every list of a radius answer by (distance, index) in place (PN_RADIUS_SORTED)
 constexpr int kSortTile = 2048;  // longest list sorted by one workgroup in LDS; longer lists: chunks + merge passes
 struct CsrSortScratch {
