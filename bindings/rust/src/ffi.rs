@@ -125,6 +125,31 @@ extern "C" {
                              d_weight: *mut f32, work_out: *mut u64, stream: *mut c_void) -> c_int;
     pub fn pn_mst_device_f64(index: *const pn_index, d_core: *const f64, flags: c_uint, d_src: *mut u64, d_dst: *mut u64,
                              d_weight: *mut f64, work_out: *mut u64, stream: *mut c_void) -> c_int;
+    /// Single-linkage dendrogram of n - 1 sorted tree edges (as pn_mst_* writes them): left / right / weight_out / size
+    /// [n - 1], node n + r = the r-th merge; flags = 0.  Edges that are no spanning tree: PN_ERR_INVALID (device entry:
+    /// written to d_error, an int32 in HBM, nullable; it never waits for the device)
+    pub fn pn_linkage_f32(index: *const pn_index, src: *const u64, dst: *const u64, weight: *const f32, flags: c_uint,
+                          left_out: *mut u64, right_out: *mut u64, weight_out: *mut f32, size_out: *mut u64) -> c_int;
+    pub fn pn_linkage_f64(index: *const pn_index, src: *const u64, dst: *const u64, weight: *const f64, flags: c_uint,
+                          left_out: *mut u64, right_out: *mut u64, weight_out: *mut f64, size_out: *mut u64) -> c_int;
+    pub fn pn_linkage_device_f32(index: *const pn_index, d_src: *const u64, d_dst: *const u64, d_weight: *const f32,
+                                 flags: c_uint, d_left: *mut u64, d_right: *mut u64, d_weight_out: *mut f32,
+                                 d_size: *mut u64, d_error: *mut i32, stream: *mut c_void) -> c_int;
+    pub fn pn_linkage_device_f64(index: *const pn_index, d_src: *const u64, d_dst: *const u64, d_weight: *const f64,
+                                 flags: c_uint, d_left: *mut u64, d_right: *mut u64, d_weight_out: *mut f64,
+                                 d_size: *mut u64, d_error: *mut i32, stream: *mut c_void) -> c_int;
+    /// HDBSCAN: labels [n] (-1 = noise), probabilities [n] (nullable), n_clusters [1] (nullable); min_samples counts other
+    /// rows; flags = 0.  The device entry points keep the host waits of pn_mst_device_* and add none
+    pub fn pn_hdbscan_f32(index: *const pn_index, min_samples: usize, min_cluster_size: usize, flags: c_uint,
+                          labels: *mut i64, probabilities: *mut f32, n_clusters: *mut u64) -> c_int;
+    pub fn pn_hdbscan_f64(index: *const pn_index, min_samples: usize, min_cluster_size: usize, flags: c_uint,
+                          labels: *mut i64, probabilities: *mut f64, n_clusters: *mut u64) -> c_int;
+    pub fn pn_hdbscan_device_f32(index: *const pn_index, min_samples: usize, min_cluster_size: usize, flags: c_uint,
+                                 d_labels: *mut i64, d_probabilities: *mut f32, d_n_clusters: *mut u64,
+                                 stream: *mut c_void) -> c_int;
+    pub fn pn_hdbscan_device_f64(index: *const pn_index, min_samples: usize, min_cluster_size: usize, flags: c_uint,
+                                 d_labels: *mut i64, d_probabilities: *mut f64, d_n_clusters: *mut u64,
+                                 stream: *mut c_void) -> c_int;
     /// dist_out nullable (PN_RADIUS_SORTED needs it); *idx_out / *dist_out released with pn_free
     pub fn pn_query_radius_self_f32(index: *const pn_index, radius: f32, flags: c_uint, offsets: *mut u64,
                                     idx_out: *mut *mut u64, dist_out: *mut *mut f32) -> c_int;

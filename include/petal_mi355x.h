@@ -60,7 +60,8 @@ extern "C" {
  * pn_sharded_query_radius_with_distance_{,device_}{f32,f64}, PN_RADIUS_SORTED; pn_query_self_{,device_}{f32,f64},
  * pn_query_radius_self_{,device_}{f32,f64}, PN_SELF_INCLUDE; pn_sharded_query_self_{,device_}{f32,f64},
  * pn_sharded_query_radius_self_{,device_}{f32,f64}; pn_query_radii_{,device_,self_,self_device_}{f32,f64};
- * pn_dbscan_{,device_}{f32,f64}, PN_OPT_DBSCAN_PIECE; pn_mst_{,device_}{f32,f64}, PN_OPT_MST_BATCH. */
+ * pn_dbscan_{,device_}{f32,f64}, PN_OPT_DBSCAN_PIECE; pn_mst_{,device_}{f32,f64}, PN_OPT_MST_BATCH;
+ * pn_linkage_{,device_}{f32,f64}, pn_hdbscan_{,device_}{f32,f64}. */
 #define PN_ABI_VERSION 3
 
 /* ---- error codes.  EMPTY / NOT_CONTIGUOUS are ArrayError (src/lib.rs:9-16). */
@@ -436,6 +437,75 @@ int pn_mst_device_f32(const pn_index *index, const float *d_core, unsigned flags
                       float *d_weight, uint64_t *work_out, void *stream);
 int pn_mst_device_f64(const pn_index *index, const double *d_core, unsigned flags, uint64_t *d_src, uint64_t *d_dst,
                       double *d_weight, uint64_t *work_out, void *stream);
+
+/* ---- Single-linkage dendrogram of a spanning tree's sorted edges, on the device.
+ * Input: the n - 1 edges of a spanning tree over the rows 0 .. n - 1 in the format pn_mst_* writes -- PN_OPT_INDEX_BASE
+ * added to both ends, in merge order (pn_mst_* writes them ascending); the handle supplies n, the device and the workspace.
+ * Output: SciPy's linkage layout as four arrays of length n - 1.  The r-th edge makes node n + r with the children
+ * left[r] and right[r]: node ids, < n a row (no index base), >= n an earlier merge; left is the subtree that holds
+ * src[r], right the one that holds dst[r]; weight_out[r] = weight[r] (it may be the same array); size[r] = the rows
+ * under the node.  The result is a function of the edges alone: it is the tree a sequential union-find over the edges in
+ * the given order builds, whatever the schedule.  The work is log2(n) levels of O(n) each and no step walks the tree, so
+ * the time does not grow with the dendrogram's height.  n <= 1 writes nothing and succeeds.
+ * Edges that do not form a spanning tree (an end that is no row, a repeated edge, a cycle: the last node does not hold
+ * n rows): PN_ERR_INVALID after the device work, the outputs unspecified.  The host variant reads that one word back;
+ * the device variant writes PN_OK or PN_ERR_INVALID to d_error[0] (an int32 in HBM, nullable) in stream order, returns
+ * PN_OK and never waits for the device.
+ * flags must be 0.  Argument errors, before any device is touched and in this order: flags != 0, a NULL array with n > 1
+ * (src, dst, weight, left, right, weight_out, size), NULL index, wrong element type: PN_ERR_INVALID; more than 2^31 - 1
+ * rows: PN_ERR_UNSUPPORTED.  Device memory: 48 bytes per row. */
+int pn_linkage_f32(const pn_index *index, const uint64_t *src, const uint64_t *dst, const float *weight, unsigned flags,
+                   uint64_t *left_out, uint64_t *right_out, float *weight_out, uint64_t *size_out);
+int pn_linkage_f64(const pn_index *index, const uint64_t *src, const uint64_t *dst, const double *weight, unsigned flags,
+                   uint64_t *left_out, uint64_t *right_out, double *weight_out, uint64_t *size_out);
+int pn_linkage_device_f32(const pn_index *index, const uint64_t *d_src, const uint64_t *d_dst, const float *d_weight,
+                          unsigned flags, uint64_t *d_left, uint64_t *d_right, float *d_weight_out, uint64_t *d_size,
+                          int32_t *d_error, void *stream);
+int pn_linkage_device_f64(const pn_index *index, const uint64_t *d_src, const uint64_t *d_dst, const double *d_weight,
+                          unsigned flags, uint64_t *d_left, uint64_t *d_right, double *d_weight_out, uint64_t *d_size,
+                          int32_t *d_error, void *stream);
+
+/* ---- HDBSCAN labels of the indexed rows, on the device: pn_query_self_device_*(min_samples)'s last column (the core
+ * distances) -> pn_mst_device_* -> the dendrogram above -> condensed tree, stability, excess-of-mass selection, labels and
+ * membership probabilities.  Nothing leaves HBM but the outputs.
+ * labels: n int64, 0 .. n_clusters - 1 or -1 (noise); probabilities (nullable): n values of the index's element type;
+ * n_clusters (nullable): one word.  min_samples counts OTHER rows (scikit-learn counts the row itself: its min_samples is
+ * this library's + 1); m = min_cluster_size.  The contract, all arithmetic in f64:
+ *   lambda(w) of a merge weight w: 1 / w for w > 2^-100; 2^100 for w <= 2^-100 (duplicate rows, Cosine's non-positive
+ *     weights: finite, so no inf - inf); 0 for a NaN weight.  lambda(node) = lambda(the node's weight).
+ *   A dendrogram node is a TRUE SPLIT when both children hold at least m rows.  The condensed clusters are the root and
+ *     both children of every true split; ctop(x), for a node of at least m rows, is its nearest ancestor-or-self that is
+ *     such a cluster top.
+ *   Row p FALLS OUT at a(p), its lowest ancestor with at least m rows: out of the cluster ctop(a(p)), with
+ *     lambda_p = lambda(a(p)).
+ *   birth(c) = lambda(parent(top of c)), 0 for the root.
+ *     stability(c) = sum over the rows p that fall out of c of (lambda_p - birth(c))
+ *                    + size(s) * (lambda(s) - birth(c)), s = the true split that ends c, if there is one.
+ *     death(c) = the largest of those lambda.
+ *   Selection (excess of mass), bottom-up: a non-root cluster is FLAGGED unless the sum of its children's best values is
+ *     strictly greater than its stability; best = the stability if flagged, else that sum.  The root is never flagged
+ *     (no allow_single_cluster in this version).  SELECTED are the flagged clusters without a flagged ancestor.
+ *   labels[p] = the selected ancestor-or-self of the cluster p falls out of, else -1; the selected clusters are numbered
+ *     by ascending lowest member row, like pn_dbscan_*.  probabilities[p] = min(lambda_p, death) / death with the
+ *     selected cluster's death, 1 where death == 0, 0 for noise.
+ *   n < m, or no true split: all noise, 0 clusters.  Rows with NaN coordinates end as noise.
+ * This is scikit-learn's tree_to_labels(..., "eom", allow_single_cluster=False) up to the numbering.  The result depends
+ * on the data alone: the tree is unique (pn_mst_*), the dendrogram a function of it, the stability sums have a shape
+ * fixed by the tree (no floating-point atomics) and everything else is integer or a maximum.
+ * flags must be 0.  Argument errors, before any device is touched and in this order: flags != 0, NULL labels, NULL index,
+ * wrong element type, min_cluster_size < 2, min_samples outside [1, n - 1] when n >= 2: PN_ERR_INVALID; more than
+ * 2^31 - 1 rows: PN_ERR_UNSUPPORTED.  Device memory beyond pn_mst_*'s: about 190 bytes per row (f64: 200).
+ * Device entry points: the outputs in HBM, written in stream order on `stream`; the call keeps the host waits of
+ * pn_mst_device_* (one per Boruvka round) and adds none: the dendrogram and the extraction are enqueued and left.
+ * Not in this version: row-sharded handles, allow_single_cluster, leaf selection, a cluster_selection_epsilon. */
+int pn_hdbscan_f32(const pn_index *index, size_t min_samples, size_t min_cluster_size, unsigned flags, int64_t *labels,
+                   float *probabilities, uint64_t *n_clusters);
+int pn_hdbscan_f64(const pn_index *index, size_t min_samples, size_t min_cluster_size, unsigned flags, int64_t *labels,
+                   double *probabilities, uint64_t *n_clusters);
+int pn_hdbscan_device_f32(const pn_index *index, size_t min_samples, size_t min_cluster_size, unsigned flags,
+                          int64_t *d_labels, float *d_probabilities, uint64_t *d_n_clusters, void *stream);
+int pn_hdbscan_device_f64(const pn_index *index, size_t min_samples, size_t min_cluster_size, unsigned flags,
+                          int64_t *d_labels, double *d_probabilities, uint64_t *d_n_clusters, void *stream);
 
 /* ---- distance::pairwise(x, &Euclidean) (src/distance.rs:58-74): n x n
  * symmetric matrix, zero diagonal, n < 2 -> zeros. Host in, host out. */

@@ -3,6 +3,7 @@
 // the C ABI in petal_mi355x.h.  Same names, argument meaning and error behaviour as the
 // Rust types; results as std::vector like the Rust `Vec`s.  Link with -lpetal_mi355x.
 #pragma once
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <stdexcept>
@@ -93,6 +94,20 @@ struct Mst {
     std::vector<size_t> src, dst;
     std::vector<A> weight;
     size_t rounds = 0, rows_scanned = 0;  // Boruvka rounds run, rows handed to a scan over all of them
+};
+// the answer of BallTree::linkage, SciPy's layout: merge r makes node n + r with the children left[r] (the subtree that
+// holds the edge's src) and right[r]; ids below n are rows; size[r] = rows under the node
+template <typename A>
+struct Linkage {
+    std::vector<size_t> left, right, size;
+    std::vector<A> weight;
+};
+// the answer of BallTree::hdbscan
+template <typename A>
+struct Hdbscan {
+    std::vector<int64_t> labels;   // [n]: cluster number (by ascending lowest member row), -1 = noise
+    std::vector<A> probabilities;  // [n]: membership strength, 0 for noise
+    size_t n_clusters = 0;
 };
 // the CSR answer of BallTree::query_radius_self: row i's neighbours are idx[offsets[i] .. offsets[i + 1]] (dist beside
 // them when asked for)
@@ -314,6 +329,43 @@ class BallTree {
         res.dst.assign(dst.begin(), dst.end());
         res.rounds = (size_t)work[0];
         res.rows_scanned = (size_t)work[1];
+        return res;
+    }
+    // extension: the single-linkage dendrogram (pn_linkage_*) of a spanning tree's edges in merge order -- by default
+    // those of mst(core).  Edges that are no spanning tree throw
+    Linkage<A> linkage(const Mst<A> &tree) const {
+        Linkage<A> res;
+        const size_t ne = n_ ? n_ - 1 : 0;
+        if (tree.src.size() != ne || tree.dst.size() != ne || tree.weight.size() != ne)
+            throw std::invalid_argument("linkage: the tree must hold n - 1 edges");
+        std::vector<uint64_t> src(tree.src.begin(), tree.src.end()), dst(tree.dst.begin(), tree.dst.end());
+        std::vector<uint64_t> left(ne), right(ne), size(ne);
+        res.weight.resize(ne);
+        if constexpr (kF32)
+            check(pn_linkage_f32(h_, src.data(), dst.data(), tree.weight.data(), 0u, left.data(), right.data(),
+                                 res.weight.data(), size.data()));
+        else
+            check(pn_linkage_f64(h_, src.data(), dst.data(), tree.weight.data(), 0u, left.data(), right.data(),
+                                 res.weight.data(), size.data()));
+        res.left.assign(left.begin(), left.end());
+        res.right.assign(right.begin(), right.end());
+        res.size.assign(size.begin(), size.end());
+        return res;
+    }
+    Linkage<A> linkage(const A *core = nullptr) const { return linkage(mst(core)); }
+    // extension: HDBSCAN labels and membership probabilities on the device (pn_hdbscan_*).  min_samples counts OTHER rows
+    // (scikit-learn's value minus one); 0 = min_cluster_size, capped at size() - 1
+    Hdbscan<A> hdbscan(size_t min_cluster_size, size_t min_samples = 0) const {
+        Hdbscan<A> res;
+        if (min_samples == 0) min_samples = std::max<size_t>(std::min(min_cluster_size, n_ ? n_ - 1 : 0), 1);
+        res.labels.resize(n_);
+        res.probabilities.resize(n_);
+        uint64_t ncl = 0;
+        if constexpr (kF32)
+            check(pn_hdbscan_f32(h_, min_samples, min_cluster_size, 0u, res.labels.data(), res.probabilities.data(), &ncl));
+        else
+            check(pn_hdbscan_f64(h_, min_samples, min_cluster_size, 0u, res.labels.data(), res.probabilities.data(), &ncl));
+        res.n_clusters = (size_t)ncl;
         return res;
     }
     // extension: one radius per row (pn_query_radii_self_*): radii [size()], row i's list is the scalar overload's for

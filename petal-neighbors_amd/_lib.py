@@ -111,6 +111,14 @@ SIGNATURES = {
     "pn_mst_f64": (_i, [_vp, _vp, C.c_uint, _vp, _vp, _vp, _vp]),
     "pn_mst_device_f32": (_i, [_vp, _vp, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
     "pn_mst_device_f64": (_i, [_vp, _vp, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
+    "pn_linkage_f32": (_i, [_vp, _vp, _vp, _vp, C.c_uint, _vp, _vp, _vp, _vp]),
+    "pn_linkage_f64": (_i, [_vp, _vp, _vp, _vp, C.c_uint, _vp, _vp, _vp, _vp]),
+    "pn_linkage_device_f32": (_i, [_vp, _vp, _vp, _vp, C.c_uint, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pn_linkage_device_f64": (_i, [_vp, _vp, _vp, _vp, C.c_uint, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pn_hdbscan_f32": (_i, [_vp, _sz, _sz, C.c_uint, _vp, _vp, _vp]),
+    "pn_hdbscan_f64": (_i, [_vp, _sz, _sz, C.c_uint, _vp, _vp, _vp]),
+    "pn_hdbscan_device_f32": (_i, [_vp, _sz, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
+    "pn_hdbscan_device_f64": (_i, [_vp, _sz, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
     "pn_free": (None, [_vp]),
     "pn_pairwise_f32": (_i, [_vp, _sz, _sz, _ssz, _i, _vp]),
     "pn_pairwise_f64": (_i, [_vp, _sz, _sz, _ssz, _i, _vp]),

@@ -659,3 +659,112 @@ class BallTree:
             raise ValueError("min_samples must be in [1, n - 1]")
         _, dist = self.query_self_device(int(min_samples))
         return self.mst_device(dist[:, -1].contiguous())
+
+    # ------------------------------------------------------- dendrogram, HDBSCAN
+    # The single-linkage dendrogram of sorted tree edges (``pn_linkage_*``) in SciPy's layout: the r-th edge makes node
+    # n + r with children ``left[r]`` (the subtree that holds ``src[r]``) and ``right[r]``; ids below n are rows.
+    def linkage(self, core=None, edges=None):
+        """``(left uint64 [n-1], right uint64 [n-1], weight [n-1], size uint64 [n-1])``: the dendrogram of
+        ``edges = (src, dst, weight)`` -- a spanning tree's edges in merge order, as ``mst`` returns them -- or, without
+        ``edges``, of ``self.mst(core)``.  Edges that are no spanning tree raise."""
+        if edges is None:
+            edges = self.mst(core)
+        elif core is not None:
+            raise ValueError("give core or edges, not both")
+        ne = max(self._n - 1, 0)
+        src = np.ascontiguousarray(edges[0], dtype=np.uint64)
+        dst = np.ascontiguousarray(edges[1], dtype=np.uint64)
+        w = np.ascontiguousarray(edges[2], dtype=self.dtype)
+        for t in (src, dst, w):
+            if t.ndim != 1 or t.shape[0] != ne:
+                raise ValueError(f"edges must be three arrays of n - 1 = {ne} values")
+        left = np.empty(ne, dtype=np.uint64)
+        right = np.empty(ne, dtype=np.uint64)
+        weight = np.empty(ne, dtype=self.dtype)
+        size = np.empty(ne, dtype=np.uint64)
+        check(getattr(_lib.lib(), f"pn_linkage_{self._sfx}")(
+            self._h, src.ctypes.data, dst.ctypes.data, w.ctypes.data, 0, left.ctypes.data, right.ctypes.data,
+            weight.ctypes.data, size.ctypes.data))
+        return left, right, weight, size
+
+    def linkage_device(self, core=None, edges=None, out_left=None, out_right=None, out_weight=None, out_size=None,
+                       out_error=None, stream=None):
+        """``linkage`` in HBM: ``edges`` are CUDA tensors ``(src int64, dst int64, weight)`` (default:
+        ``mst_device(core)``); returns CUDA tensors ``(left int64, right int64, weight, size int64, error int32 [1])``
+        written in stream order on ``stream`` (default: the current torch stream) without waiting for the device.
+        ``error[0]`` is 0, or ``PN_ERR_INVALID`` when the edges are no spanning tree."""
+        import torch
+        tdt = torch.float32 if self._sfx == "f32" else torch.float64
+        dev = torch.device("cuda", self.device)
+        ne = max(self._n - 1, 0)
+        if edges is None:
+            edges = self.mst_device(core, stream=stream)
+        elif core is not None:
+            raise ValueError("give core or edges, not both")
+        src, dst, w = edges
+        for t, want in ((src, torch.int64), (dst, torch.int64), (w, tdt)):
+            if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != want or t.dim() != 1 or t.numel() != ne
+                    or not t.is_contiguous()):
+                raise ValueError(f"edges must be three contiguous 1-D CUDA tensors of n - 1 = {ne} values (int64, int64, "
+                                 "the tree's element type)")
+        for t, want, need in ((out_left, torch.int64, ne), (out_right, torch.int64, ne), (out_weight, tdt, ne),
+                              (out_size, torch.int64, ne), (out_error, torch.int32, 1)):
+            if t is not None and (t.dtype != want or t.numel() < need or not t.is_contiguous() or not t.is_cuda):
+                raise ValueError("output tensors are too small or of the wrong type")
+        left = out_left if out_left is not None else torch.empty(ne, dtype=torch.int64, device=dev)
+        right = out_right if out_right is not None else torch.empty(ne, dtype=torch.int64, device=dev)
+        weight = out_weight if out_weight is not None else torch.empty(ne, dtype=tdt, device=dev)
+        size = out_size if out_size is not None else torch.empty(ne, dtype=torch.int64, device=dev)
+        err = out_error if out_error is not None else torch.zeros(1, dtype=torch.int32, device=dev)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        check(getattr(_lib.lib(), f"pn_linkage_device_{self._sfx}")(
+            self._h, src.data_ptr(), dst.data_ptr(), w.data_ptr(), 0, left.data_ptr(), right.data_ptr(), weight.data_ptr(),
+            size.data_ptr(), err.data_ptr(), C.c_void_p(st)))
+        return left, right, weight, size, err
+
+    def _hdbscan_args(self, min_cluster_size, min_samples):
+        m = int(min_cluster_size)
+        if m < 2:
+            raise ValueError("min_cluster_size must be at least 2")
+        if min_samples is None:
+            k = max(min(m, self._n - 1), 1)
+        else:
+            k = int(min_samples)
+            if self._n >= 2 and (k < 1 or k > self._n - 1):
+                raise ValueError("min_samples must be in [1, n - 1]")
+        return m, k
+
+    def hdbscan(self, min_cluster_size, min_samples=None):
+        """HDBSCAN on the device (``pn_hdbscan_*``): ``(labels int64 [n], probabilities [n])``; labels are
+        0 .. n_clusters - 1 by ascending lowest member row, -1 is noise.  ``min_samples`` counts OTHER rows (scikit-learn's
+        value minus one); the default is ``min_cluster_size``, capped at n - 1.  ``self.last_n_clusters`` then holds the
+        number of clusters."""
+        m, k = self._hdbscan_args(min_cluster_size, min_samples)
+        labels = np.empty(self._n, dtype=np.int64)
+        prob = np.empty(self._n, dtype=self.dtype)
+        ncl = np.zeros(1, dtype=np.uint64)
+        check(getattr(_lib.lib(), f"pn_hdbscan_{self._sfx}")(self._h, k, m, 0, labels.ctypes.data, prob.ctypes.data,
+                                                            ncl.ctypes.data))
+        self.last_n_clusters = int(ncl[0])
+        return labels, prob
+
+    def hdbscan_device(self, min_cluster_size, min_samples=None, out_labels=None, out_probabilities=None,
+                       out_n_clusters=None, stream=None):
+        """``hdbscan`` in HBM: CUDA tensors ``(labels int64 [n], probabilities [n], n_clusters int64 [1])`` written in
+        stream order on ``stream`` (default: the current torch stream).  The call waits for the device once per Boruvka
+        round of the tree and not after it."""
+        import torch
+        m, k = self._hdbscan_args(min_cluster_size, min_samples)
+        tdt = torch.float32 if self._sfx == "f32" else torch.float64
+        dev = torch.device("cuda", self.device)
+        n = self._n
+        for t, want, need in ((out_labels, torch.int64, n), (out_probabilities, tdt, n), (out_n_clusters, torch.int64, 1)):
+            if t is not None and (t.dtype != want or t.numel() < need or not t.is_contiguous() or not t.is_cuda):
+                raise ValueError("output tensors are too small or of the wrong type")
+        labels = out_labels if out_labels is not None else torch.empty(n, dtype=torch.int64, device=dev)
+        prob = out_probabilities if out_probabilities is not None else torch.empty(n, dtype=tdt, device=dev)
+        ncl = out_n_clusters if out_n_clusters is not None else torch.zeros(1, dtype=torch.int64, device=dev)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        check(getattr(_lib.lib(), f"pn_hdbscan_device_{self._sfx}")(
+            self._h, k, m, 0, labels.data_ptr(), prob.data_ptr(), ncl.data_ptr(), C.c_void_p(st)))
+        return labels, prob, ncl

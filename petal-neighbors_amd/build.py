@@ -44,6 +44,7 @@ UNITS = [
     ("self_graph.hip", ["-ffp-contract=off"]),
     ("components.hip", []),
     ("mst.hip", []),
+    ("linkage.hip", []),
     ("radii_tau.hip", ["-ffp-contract=off"]),
     ("metric.cpp", ["-ffp-contract=off"]),
     ("tree.cpp", ["-ffp-contract=off"]),

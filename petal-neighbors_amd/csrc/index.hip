@@ -152,6 +152,9 @@ struct Workspace {
     DevBuf w_db, w_db_side, w_db_out;
     // pn_mst_*: the scratch of mst.hip (+ round 0's 1-NN answer), and the host entry's core distances and outputs
     DevBuf w_mst, w_mst_io;
+    // pn_linkage_* / pn_hdbscan_*: the scratch of linkage.hip (+ the core distances and the tree edges of an HDBSCAN call),
+    // and the host entries' inputs and outputs
+    DevBuf w_hdb, w_hdb_io;
     // small calls (tiny_*): mapped pinned host memory the one kernel of the call reads its queries from and writes its
     // answers to -- no copy commands
     void *pin_in = nullptr, *pin_out = nullptr;
@@ -177,7 +180,7 @@ struct Workspace {
     hipEvent_t done = nullptr;
     hipStream_t last_stream = nullptr;
     bool in_flight = false;
-    DevBuf *all[57] = {&w_mst, &w_mst_io, &w_db, &w_db_side, &w_db_out, &w_hrad, &w_sf_idx, &w_sf_dist, &w_sf_off, &w_sf_coff, &w_sf_flag, &w_sf_cnt, &w_sf_scan, &w_sf_hoff, &w_cs_hoff, &w_rkd, &w_cs_nch, &w_cs_off, &w_cs_scan, &w_cs_idx, &w_cs_dist, &w_gqn, &w_rpos, &w_rfin, &w_rcx, &w_rox, &w_rscan, &w_q, &w_qnorm, &w_qnrm, &w_keys, &w_idx, &w_cnt, &w_tau, &w_flags, &w_sel, &w_misc, &w2_keys, &w2_idx,
+    DevBuf *all[59] = {&w_hdb, &w_hdb_io, &w_mst, &w_mst_io, &w_db, &w_db_side, &w_db_out, &w_hrad, &w_sf_idx, &w_sf_dist, &w_sf_off, &w_sf_coff, &w_sf_flag, &w_sf_cnt, &w_sf_scan, &w_sf_hoff, &w_cs_hoff, &w_rkd, &w_cs_nch, &w_cs_off, &w_cs_scan, &w_cs_idx, &w_cs_dist, &w_gqn, &w_rpos, &w_rfin, &w_rcx, &w_rox, &w_rscan, &w_q, &w_qnorm, &w_qnrm, &w_keys, &w_idx, &w_cnt, &w_tau, &w_flags, &w_sel, &w_misc, &w2_keys, &w2_idx,
                        &w2_cnt, &w2_tau, &w_lo, &w_bq, &w_qn, &w_qbad, &w_gq, &w_gidx, &w_gdist, &w_gsel, &w_seed,
                        &w_qstat, &w_lists, &w_hq, &w_hidx, &w_hdist, &w_fparts, &w_pcnt};
     std::vector<void *> retired;  // outgrown allocations, freed once `done` has passed (DevBuf::ensure)
@@ -3873,6 +3876,222 @@ extern "C" int pn_mst_device_f32(const pn_index *ix, const float *d_core, unsign
 extern "C" int pn_mst_device_f64(const pn_index *ix, const double *d_core, unsigned flags, uint64_t *d_src, uint64_t *d_dst,
                                  double *d_weight, uint64_t *work_out, void *stream) {
     return mst_device<double>(ix, d_core, flags, d_src, d_dst, d_weight, work_out, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------
+// Single-linkage dendrogram of sorted tree edges: pn_linkage_{,device_}{f32,f64}, and HDBSCAN labels:
+// pn_hdbscan_{,device_}{f32,f64} = the min_samples self-query's last column -> mst_run -> the dendrogram -> the extraction
+// (both in linkage.hip, which holds the algorithms and why their results depend on the data alone).  Here: the argument
+// checks, the workspace and the chain.  Nothing after the MST waits for the device.
+// ---------------------------------------------------------------------------
+static int linkage_args(const pn_index *ix, unsigned flags, const void *src, const void *dst, const void *weight,
+                        const void *left, const void *right, const void *weight_out, const void *size, int elem_bytes) {
+    if (flags) return fail(PN_ERR_INVALID, "unknown linkage flags 0x%x", flags);
+    if ((!src || !dst || !weight || !left || !right || !weight_out || !size) && (!ix || ix->n > 1))
+        return fail(PN_ERR_INVALID, "%s is NULL",
+                    !src ? "src" : !dst ? "dst" : !weight ? "weight" : !left ? "left_out" : !right ? "right_out"
+                    : !weight_out ? "weight_out" : "size_out");
+    if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
+    if (ix->elem_bytes != elem_bytes) return fail(PN_ERR_INVALID, "index element type mismatch");
+    if (ix->n > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many rows for a dendrogram (32-bit names)");
+    return PN_OK;
+}
+template <typename T>
+static int linkage_run(const pn_index *ix, void *buf, const uint64_t *d_src, const uint64_t *d_dst, const T *d_weight,
+                       uint64_t *d_left, uint64_t *d_right, T *d_weight_out, uint64_t *d_size, int32_t *d_err, hipStream_t s) {
+    LinkageArgs a;
+    a.n = ix->n;
+    a.index_base = ix->index_base;
+    a.d_src = d_src;
+    a.d_dst = d_dst;
+    a.d_weight = d_weight;
+    a.buf = buf;
+    a.d_left = d_left;
+    a.d_right = d_right;
+    a.d_size = d_size;
+    a.d_weight_out = d_weight_out;
+    a.d_err = d_err;
+    if constexpr (sizeof(T) == 4)
+        return linkage_enqueue_f32(a, s);
+    else
+        return linkage_enqueue_f64(a, s);
+}
+template <typename T>
+static int linkage_device(const pn_index *ix, const uint64_t *d_src, const uint64_t *d_dst, const T *d_weight, unsigned flags,
+                          uint64_t *d_left, uint64_t *d_right, T *d_weight_out, uint64_t *d_size, int32_t *d_err,
+                          hipStream_t s) {
+    PNCHK(linkage_args(ix, flags, d_src, d_dst, d_weight, d_left, d_right, d_weight_out, d_size, (int)sizeof(T)));
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    lease.s = s;
+    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
+    if (ix->n < 2) {
+        if (d_err) HIPCHK(hipMemsetAsync(d_err, 0, sizeof(int32_t), s));
+        return PN_OK;
+    }
+    PNCHK(lease.ws->w_hdb.ensure(linkage_buffer_bytes(ix->n)));
+    return linkage_run<T>(ix, lease.ws->w_hdb.p, d_src, d_dst, d_weight, d_left, d_right, d_weight_out, d_size, d_err, s);
+}
+template <typename T>
+static int linkage_host(const pn_index *ix, const uint64_t *src, const uint64_t *dst, const T *weight, unsigned flags,
+                        uint64_t *left, uint64_t *right, T *weight_out, uint64_t *size) {
+    PNCHK(linkage_args(ix, flags, src, dst, weight, left, right, weight_out, size, (int)sizeof(T)));
+    if (ix->n < 2) return PN_OK;
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
+    Workspace &ws = *lease.ws;
+    hipStream_t s = lease.s;
+    const size_t n = ix->n, ne = n - 1;
+    PNCHK(ws.w_hdb.ensure(linkage_buffer_bytes(n)));
+    PNCHK(ws.w_hdb_io.ensure(5 * ne * sizeof(uint64_t) + 2 * ne * sizeof(T) + 64));
+    uint64_t *d_src = (uint64_t *)ws.w_hdb_io.p, *d_dst = d_src + ne, *d_left = d_dst + ne, *d_right = d_left + ne,
+             *d_size = d_right + ne;
+    T *d_w = (T *)(d_size + ne), *d_wo = d_w + ne;
+    int32_t *d_err = (int32_t *)(d_wo + ne);
+    HIPCHK(hipMemcpyAsync(d_src, src, ne * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_dst, dst, ne * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_w, weight, ne * sizeof(T), hipMemcpyHostToDevice, s));
+    PNCHK(linkage_run<T>(ix, ws.w_hdb.p, d_src, d_dst, d_w, d_left, d_right, d_wo, d_size, d_err, s));
+    int32_t err = 0;
+    HIPCHK(hipMemcpyAsync(left, d_left, ne * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(right, d_right, ne * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(size, d_size, ne * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(weight_out, d_wo, ne * sizeof(T), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&err, d_err, sizeof err, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (err) return fail(PN_ERR_INVALID, "the edges are not a spanning tree of the %zu indexed rows", n);
+    return PN_OK;
+}
+extern "C" int pn_linkage_f32(const pn_index *ix, const uint64_t *src, const uint64_t *dst, const float *weight, unsigned flags,
+                              uint64_t *left_out, uint64_t *right_out, float *weight_out, uint64_t *size_out) {
+    return linkage_host<float>(ix, src, dst, weight, flags, left_out, right_out, weight_out, size_out);
+}
+extern "C" int pn_linkage_f64(const pn_index *ix, const uint64_t *src, const uint64_t *dst, const double *weight, unsigned flags,
+                              uint64_t *left_out, uint64_t *right_out, double *weight_out, uint64_t *size_out) {
+    return linkage_host<double>(ix, src, dst, weight, flags, left_out, right_out, weight_out, size_out);
+}
+extern "C" int pn_linkage_device_f32(const pn_index *ix, const uint64_t *d_src, const uint64_t *d_dst, const float *d_weight,
+                                     unsigned flags, uint64_t *d_left, uint64_t *d_right, float *d_weight_out,
+                                     uint64_t *d_size, int32_t *d_error, void *stream) {
+    return linkage_device<float>(ix, d_src, d_dst, d_weight, flags, d_left, d_right, d_weight_out, d_size, d_error,
+                                 (hipStream_t)stream);
+}
+extern "C" int pn_linkage_device_f64(const pn_index *ix, const uint64_t *d_src, const uint64_t *d_dst, const double *d_weight,
+                                     unsigned flags, uint64_t *d_left, uint64_t *d_right, double *d_weight_out,
+                                     uint64_t *d_size, int32_t *d_error, void *stream) {
+    return linkage_device<double>(ix, d_src, d_dst, d_weight, flags, d_left, d_right, d_weight_out, d_size, d_error,
+                                  (hipStream_t)stream);
+}
+
+static int hdbscan_args(const pn_index *ix, size_t min_samples, size_t min_cluster_size, unsigned flags, const void *labels,
+                        int elem_bytes) {
+    if (flags) return fail(PN_ERR_INVALID, "unknown HDBSCAN flags 0x%x", flags);
+    if (!labels) return fail(PN_ERR_INVALID, "labels is NULL");
+    if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
+    if (ix->elem_bytes != elem_bytes) return fail(PN_ERR_INVALID, "index element type mismatch");
+    if (min_cluster_size < 2) return fail(PN_ERR_INVALID, "min_cluster_size must be at least 2");
+    if (ix->n >= 2 && (min_samples < 1 || min_samples > ix->n - 1))
+        return fail(PN_ERR_INVALID, "min_samples must be in [1, n - 1] = [1, %zu]", ix->n - 1);
+    if (ix->n > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many rows for HDBSCAN (32-bit names)");
+    return PN_OK;
+}
+// in a held workspace, on stream s; outputs in HBM; the host waits of mst_run, none after it
+template <typename T>
+static int hdbscan_enqueue(const pn_index *ix, Workspace &ws, size_t min_samples, size_t min_cluster_size, int64_t *d_labels,
+                           T *d_prob, uint64_t *d_ncl, hipStream_t s) {
+    const size_t n = ix->n;
+    if (n < min_cluster_size) {  // (n <= 1 included) no node holds min_cluster_size rows: all noise
+        HIPCHK(launch_dbscan_noise(n, d_labels, nullptr, d_ncl, s));
+        if (d_prob && n) HIPCHK(hipMemsetAsync(d_prob, 0, n * sizeof(T), s));
+        std::lock_guard<std::mutex> lk(ix->sh.mu);
+        ix->sh.stats.queries += n;
+        return PN_OK;
+    }
+    const size_t ne = n - 1, scratch = round_up(hdbscan_buffer_bytes(n), (size_t)16);
+    PNCHK(ws.w_hdb.ensure(scratch + 2 * ne * sizeof(uint64_t) + (ne + n) * sizeof(T)));
+    uint64_t *d_src = (uint64_t *)((char *)ws.w_hdb.p + scratch), *d_dst = d_src + ne;
+    T *d_weight = (T *)(d_dst + ne), *d_core = d_weight + ne;
+    // ---- core distances: the last column of the min_samples self-query, chunk by chunk
+    const size_t kout = min_samples, kin = kout + 1;
+    for (size_t r0 = 0; r0 < n; r0 += kSelfChunk) {
+        const size_t nqc = n - r0 < kSelfChunk ? n - r0 : kSelfChunk;
+        PNCHK(ws.w_hidx.ensure(nqc * kout * sizeof(uint64_t)));
+        PNCHK(ws.w_hdist.ensure(nqc * kout * sizeof(T)));
+        PNCHK(self_knn_chunk<T>(ix, ws, r0, nqc, kin, kout, false, (uint64_t *)ws.w_hidx.p, (T *)ws.w_hdist.p, s));
+        if constexpr (sizeof(T) == 4)
+            HIPCHK(launch_last_column_f32((const T *)ws.w_hdist.p, nqc, kout, d_core + r0, s));
+        else
+            HIPCHK(launch_last_column_f64((const T *)ws.w_hdist.p, nqc, kout, d_core + r0, s));
+    }
+    // ---- the tree, the dendrogram, the labels
+    PNCHK(mst_run<T>(ix, ws, d_core, d_src, d_dst, d_weight, nullptr, s));
+    PNCHK(linkage_run<T>(ix, ws.w_hdb.p, d_src, d_dst, d_weight, nullptr, nullptr, nullptr, nullptr, nullptr, s));
+    HdbscanArgs h;
+    h.n = n;
+    h.min_cluster_size = min_cluster_size;
+    h.d_weight = d_weight;
+    h.buf = ws.w_hdb.p;
+    h.d_labels = d_labels;
+    h.d_prob = d_prob;
+    h.d_n_clusters = d_ncl;
+    if constexpr (sizeof(T) == 4)
+        return hdbscan_extract_enqueue_f32(h, s);
+    else
+        return hdbscan_extract_enqueue_f64(h, s);
+}
+template <typename T>
+static int hdbscan_device(const pn_index *ix, size_t min_samples, size_t min_cluster_size, unsigned flags, int64_t *d_labels,
+                          T *d_prob, uint64_t *d_ncl, hipStream_t s) {
+    PNCHK(hdbscan_args(ix, min_samples, min_cluster_size, flags, d_labels, (int)sizeof(T)));
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    lease.s = s;
+    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
+    return hdbscan_enqueue<T>(ix, *lease.ws, min_samples, min_cluster_size, d_labels, d_prob, d_ncl, s);
+}
+template <typename T>
+static int hdbscan_host(const pn_index *ix, size_t min_samples, size_t min_cluster_size, unsigned flags, int64_t *labels,
+                        T *prob, uint64_t *n_clusters) {
+    PNCHK(hdbscan_args(ix, min_samples, min_cluster_size, flags, labels, (int)sizeof(T)));
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
+    Workspace &ws = *lease.ws;
+    hipStream_t s = lease.s;
+    const size_t n = ix->n;
+    PNCHK(ws.w_hdb_io.ensure((n + 1) * sizeof(uint64_t) + n * sizeof(T)));
+    int64_t *d_labels = (int64_t *)ws.w_hdb_io.p;
+    uint64_t *d_ncl = (uint64_t *)(d_labels + n);
+    T *d_prob = (T *)(d_ncl + 1);
+    PNCHK(hdbscan_enqueue<T>(ix, ws, min_samples, min_cluster_size, d_labels, d_prob, d_ncl, s));
+    if (n) HIPCHK(hipMemcpyAsync(labels, d_labels, n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    if (prob && n) HIPCHK(hipMemcpyAsync(prob, d_prob, n * sizeof(T), hipMemcpyDeviceToHost, s));
+    if (n_clusters) HIPCHK(hipMemcpyAsync(n_clusters, d_ncl, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return PN_OK;
+}
+extern "C" int pn_hdbscan_f32(const pn_index *ix, size_t min_samples, size_t min_cluster_size, unsigned flags, int64_t *labels,
+                              float *probabilities, uint64_t *n_clusters) {
+    return hdbscan_host<float>(ix, min_samples, min_cluster_size, flags, labels, probabilities, n_clusters);
+}
+extern "C" int pn_hdbscan_f64(const pn_index *ix, size_t min_samples, size_t min_cluster_size, unsigned flags, int64_t *labels,
+                              double *probabilities, uint64_t *n_clusters) {
+    return hdbscan_host<double>(ix, min_samples, min_cluster_size, flags, labels, probabilities, n_clusters);
+}
+extern "C" int pn_hdbscan_device_f32(const pn_index *ix, size_t min_samples, size_t min_cluster_size, unsigned flags,
+                                     int64_t *d_labels, float *d_probabilities, uint64_t *d_n_clusters, void *stream) {
+    return hdbscan_device<float>(ix, min_samples, min_cluster_size, flags, d_labels, d_probabilities, d_n_clusters,
+                                 (hipStream_t)stream);
+}
+extern "C" int pn_hdbscan_device_f64(const pn_index *ix, size_t min_samples, size_t min_cluster_size, unsigned flags,
+                                     int64_t *d_labels, double *d_probabilities, uint64_t *d_n_clusters, void *stream) {
+    return hdbscan_device<double>(ix, min_samples, min_cluster_size, flags, d_labels, d_probabilities, d_n_clusters,
+                                  (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------

@@ -202,6 +202,38 @@ size_t mst_buffer_bytes(size_t n, int elem_bytes, size_t batch, int n_cu);
 int mst_enqueue_f32(MstArgs &a, hipStream_t s);
 int mst_enqueue_f64(MstArgs &a, hipStream_t s);
 
+// ---- linkage.hip: the single-linkage dendrogram of sorted tree edges (pn_linkage_*) and HDBSCAN's extraction from it
+// (pn_hdbscan_*); nothing in it waits for the device
+struct LinkageArgs {
+    size_t n = 0;
+    uint64_t index_base = 0;
+    const uint64_t *d_src = nullptr, *d_dst = nullptr;  // [n - 1], as pn_mst_* writes them
+    const void *d_weight = nullptr;                     // [n - 1] of T
+    void *buf = nullptr;                                // linkage_buffer_bytes() (or hdbscan_buffer_bytes()) of scratch
+    // outputs [n - 1], all three or none; d_weight_out (of T) nullable or d_weight itself; d_err [1] nullable
+    uint64_t *d_left = nullptr, *d_right = nullptr, *d_size = nullptr;
+    void *d_weight_out = nullptr;
+    int32_t *d_err = nullptr;
+};
+size_t linkage_buffer_bytes(size_t n);
+int linkage_enqueue_f32(const LinkageArgs &a, hipStream_t s);
+int linkage_enqueue_f64(const LinkageArgs &a, hipStream_t s);
+// the extraction reads the dendrogram that linkage_enqueue_* left at the head of the same buffer; n >= min_cluster_size
+struct HdbscanArgs {
+    size_t n = 0, min_cluster_size = 2;
+    const void *d_weight = nullptr;  // [n - 1] of T: the merge weights
+    void *buf = nullptr;             // hdbscan_buffer_bytes() of scratch
+    int64_t *d_labels = nullptr;     // [n]
+    void *d_prob = nullptr;          // [n] of T, nullable
+    uint64_t *d_n_clusters = nullptr;  // [1], nullable
+};
+size_t hdbscan_buffer_bytes(size_t n);
+int hdbscan_extract_enqueue_f32(const HdbscanArgs &a, hipStream_t s);
+int hdbscan_extract_enqueue_f64(const HdbscanArgs &a, hipStream_t s);
+// out[i] = d[i][k - 1] of a [rows][k] matrix (the core distances out of a self-query's answer)
+hipError_t launch_last_column_f32(const float *d, size_t rows, size_t k, float *out, hipStream_t s);
+hipError_t launch_last_column_f64(const double *d, size_t rows, size_t k, double *out, hipStream_t s);
+
 // ---- csr_sort.hip: order every list of a radius answer by (distance, index) in place (PN_RADIUS_SORTED)
 constexpr int kSortTile = 2048;  // longest list sorted by one workgroup in LDS; longer lists: chunks + merge passes
 struct CsrSortScratch {
