@@ -150,6 +150,27 @@ extern "C" {
     pub fn pn_hdbscan_device_f64(index: *const pn_index, min_samples: usize, min_cluster_size: usize, flags: c_uint,
                                  d_labels: *mut i64, d_probabilities: *mut f64, d_n_clusters: *mut u64,
                                  stream: *mut c_void) -> c_int;
+    /// Local Outlier Factor of the indexed rows: lof [n] (required), lrd [n] and kdist [n] (nullable; the fit that
+    /// pn_lof_score_* takes back); k counts other rows, 1 <= k <= n - 1; flags = 0.  The device entry points never wait
+    pub fn pn_lof_f32(index: *const pn_index, k: usize, flags: c_uint, lof: *mut f64, lrd: *mut f64,
+                      kdist: *mut f32) -> c_int;
+    pub fn pn_lof_f64(index: *const pn_index, k: usize, flags: c_uint, lof: *mut f64, lrd: *mut f64,
+                      kdist: *mut f64) -> c_int;
+    pub fn pn_lof_device_f32(index: *const pn_index, k: usize, flags: c_uint, d_lof: *mut f64, d_lrd: *mut f64,
+                             d_kdist: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn pn_lof_device_f64(index: *const pn_index, k: usize, flags: c_uint, d_lof: *mut f64, d_lrd: *mut f64,
+                             d_kdist: *mut f64, stream: *mut c_void) -> c_int;
+    /// scores [nq] of new points against a fit (lrd, kdist of pn_lof_* with the same k)
+    pub fn pn_lof_score_f32(index: *const pn_index, queries: *const f32, nq: usize, q_cols: usize, q_row_stride: isize,
+                            k: usize, lrd: *const f64, kdist: *const f32, flags: c_uint, score_out: *mut f64) -> c_int;
+    pub fn pn_lof_score_f64(index: *const pn_index, queries: *const f64, nq: usize, q_cols: usize, q_row_stride: isize,
+                            k: usize, lrd: *const f64, kdist: *const f64, flags: c_uint, score_out: *mut f64) -> c_int;
+    pub fn pn_lof_score_device_f32(index: *const pn_index, d_queries: *const f32, nq: usize, q_cols: usize,
+                                   q_row_stride: usize, k: usize, d_lrd: *const f64, d_kdist: *const f32, flags: c_uint,
+                                   d_score: *mut f64, stream: *mut c_void) -> c_int;
+    pub fn pn_lof_score_device_f64(index: *const pn_index, d_queries: *const f64, nq: usize, q_cols: usize,
+                                   q_row_stride: usize, k: usize, d_lrd: *const f64, d_kdist: *const f64, flags: c_uint,
+                                   d_score: *mut f64, stream: *mut c_void) -> c_int;
     /// dist_out nullable (PN_RADIUS_SORTED needs it); *idx_out / *dist_out released with pn_free
     pub fn pn_query_radius_self_f32(index: *const pn_index, radius: f32, flags: c_uint, offsets: *mut u64,
                                     idx_out: *mut *mut u64, dist_out: *mut *mut f32) -> c_int;

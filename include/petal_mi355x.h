@@ -61,7 +61,8 @@ extern "C" {
  * pn_query_radius_self_{,device_}{f32,f64}, PN_SELF_INCLUDE; pn_sharded_query_self_{,device_}{f32,f64},
  * pn_sharded_query_radius_self_{,device_}{f32,f64}; pn_query_radii_{,device_,self_,self_device_}{f32,f64};
  * pn_dbscan_{,device_}{f32,f64}, PN_OPT_DBSCAN_PIECE; pn_mst_{,device_}{f32,f64}, PN_OPT_MST_BATCH;
- * pn_linkage_{,device_}{f32,f64}, pn_hdbscan_{,device_}{f32,f64}. */
+ * pn_linkage_{,device_}{f32,f64}, pn_hdbscan_{,device_}{f32,f64}; pn_lof_{,device_}{f32,f64},
+ * pn_lof_score_{,device_}{f32,f64}. */
 #define PN_ABI_VERSION 3
 
 /* ---- error codes.  EMPTY / NOT_CONTIGUOUS are ArrayError (src/lib.rs:9-16). */
@@ -506,6 +507,59 @@ int pn_hdbscan_device_f32(const pn_index *index, size_t min_samples, size_t min_
                           int64_t *d_labels, float *d_probabilities, uint64_t *d_n_clusters, void *stream);
 int pn_hdbscan_device_f64(const pn_index *index, size_t min_samples, size_t min_cluster_size, unsigned flags,
                           int64_t *d_labels, double *d_probabilities, uint64_t *d_n_clusters, void *stream);
+
+/* ---- Local Outlier Factor of the indexed rows, on the device (scikit-learn's neighbors.LocalOutlierFactor with
+ * n_neighbors = k): the k self-query -> the graph packed in HBM -> one gather pass for the local reachability densities
+ * and one for the scores.  Nothing leaves HBM but the outputs.
+ * lof: n doubles, required; lrd (nullable): n doubles; kdist (nullable): n values of the index's element type.  lrd and
+ * kdist are what pn_lof_score_* takes back: the library keeps no fit in the handle.  The contract, all arithmetic in IEEE
+ * f64, unfused, no special cases:
+ *   For row i let (j_0 .. j_{k-1}, d_0 .. d_{k-1}) be its answer from pn_query_self_*(k) with flags 0: the k nearest OTHER
+ *     rows ordered by (distance, index), NaN last, the distances bit-identical to the reference metric.
+ *   kdist[i] = d_{k-1}, in the index's element type: the bits of the last column of pn_query_self_*.
+ *   v_t = NaN if d_t or kdist[j_t] is NaN, else max((double)d_t, (double)kdist[j_t], +0.0).  The clamp at 0 matters only for
+ *     a Cosine index, where a distance can be a few ulp below 0; the NaN rule is np.maximum's, not fmax's.
+ *   S_i = (...((0.0 + v_0) + v_1) ... + v_{k-1}): added one by one in list order.
+ *   lrd[i] = 1.0 / (S_i / (double)k + 1e-10): scikit-learn's formula with its 1e-10, so duplicate rows give lrd = 1e10,
+ *     never inf.
+ *   lof[i] = (...((0.0 + lrd[j_0] / lrd[i]) + lrd[j_1] / lrd[i]) ... ) / (double)k: each ratio divided first, added in list
+ *     order.
+ *   Score of a query q (pn_lof_score_*): (j_t, d_t) = q's answer from pn_query_*(q, k) -- the query is excluded from
+ *     nothing -- v_t as above from d_t and kdist[j_t], lrd_q = 1.0 / (S / k + 1e-10), score = (sum_t lrd[j_t] / lrd_q) / k
+ *     in the same order.  lrd and kdist are those of pn_lof_* with the same k.  A fitted row scored as a query finds itself
+ *     at distance 0 and so does not reproduce its fit score; scikit-learn's score_samples behaves the same way.
+ * lof = -negative_outlier_factor_ of LocalOutlierFactor(n_neighbors = k), up to this library's distance arithmetic and tie
+ * order.  The result depends on the data alone: the k-NN answer is unique and fixes the order of every sum; there are no
+ * floating-point atomics and no reduction whose shape depends on the launch.
+ * A row with a NaN coordinate scores NaN, and so does every row with such a row in its list.  Euclidean and Cosine
+ * indexes, f32 and f64.  PN_OPT_INDEX_BASE affects no output (neighbour ids are used without the base).
+ * pn_stats.queries advances by n for a fit and by nq for a scoring call.
+ * flags must be 0.  Argument errors, before any device is touched and in this order: flags != 0; NULL lof / score_out
+ * (scoring with nq > 0: also NULL queries, lrd or kdist); NULL index; wrong element type; k outside [1, n - 1] (an index
+ * of fewer than 2 rows is always an error): PN_ERR_INVALID; more than 2^31 - 1 rows: PN_ERR_UNSUPPORTED (stored
+ * neighbour ids are 32-bit).  nq = 0 writes nothing and succeeds.
+ * Device entry points: the outputs (and lrd, kdist, the queries of a scoring call) in HBM, everything enqueued on
+ * `stream`; the call never waits for the device, as the self-query it builds on does not.
+ * Device memory of a fit, beyond a 2^18-query batch's workspace: n * k * (4 + sizeof T) + n * (8 + sizeof T) bytes -- the
+ * whole graph as 32-bit ids and distances, plus lrd and kdist where the caller supplied no buffer.  Scoring: a 2^18-query
+ * batch's workspace and its k-NN answer.
+ * Not in this version: row-sharded handles. */
+int pn_lof_f32(const pn_index *index, size_t k, unsigned flags, double *lof, double *lrd, float *kdist);
+int pn_lof_f64(const pn_index *index, size_t k, unsigned flags, double *lof, double *lrd, double *kdist);
+int pn_lof_device_f32(const pn_index *index, size_t k, unsigned flags, double *d_lof, double *d_lrd, float *d_kdist,
+                      void *stream);
+int pn_lof_device_f64(const pn_index *index, size_t k, unsigned flags, double *d_lof, double *d_lrd, double *d_kdist,
+                      void *stream);
+int pn_lof_score_f32(const pn_index *index, const float *queries, size_t nq, size_t q_cols, ptrdiff_t q_row_stride,
+                     size_t k, const double *lrd, const float *kdist, unsigned flags, double *score_out);
+int pn_lof_score_f64(const pn_index *index, const double *queries, size_t nq, size_t q_cols, ptrdiff_t q_row_stride,
+                     size_t k, const double *lrd, const double *kdist, unsigned flags, double *score_out);
+int pn_lof_score_device_f32(const pn_index *index, const float *d_queries, size_t nq, size_t q_cols, size_t q_row_stride,
+                            size_t k, const double *d_lrd, const float *d_kdist, unsigned flags, double *d_score,
+                            void *stream);
+int pn_lof_score_device_f64(const pn_index *index, const double *d_queries, size_t nq, size_t q_cols, size_t q_row_stride,
+                            size_t k, const double *d_lrd, const double *d_kdist, unsigned flags, double *d_score,
+                            void *stream);
 
 /* ---- distance::pairwise(x, &Euclidean) (src/distance.rs:58-74): n x n
  * symmetric matrix, zero diagonal, n < 2 -> zeros. Host in, host out. */

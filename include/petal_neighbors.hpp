@@ -109,6 +109,13 @@ struct Hdbscan {
     std::vector<A> probabilities;  // [n]: membership strength, 0 for noise
     size_t n_clusters = 0;
 };
+// the answer of BallTree::lof: lof[i] = row i's Local Outlier Factor; lrd (local reachability densities) and kdist
+// (distances to the k-th nearest other row) are the fit that BallTree::lof_score takes back
+template <typename A>
+struct Lof {
+    std::vector<double> lof, lrd;
+    std::vector<A> kdist;
+};
 // the CSR answer of BallTree::query_radius_self: row i's neighbours are idx[offsets[i] .. offsets[i + 1]] (dist beside
 // them when asked for)
 template <typename A>
@@ -367,6 +374,33 @@ class BallTree {
             check(pn_hdbscan_f64(h_, min_samples, min_cluster_size, 0u, res.labels.data(), res.probabilities.data(), &ncl));
         res.n_clusters = (size_t)ncl;
         return res;
+    }
+    // extension: Local Outlier Factor on the device (pn_lof_*): scikit-learn's LocalOutlierFactor(n_neighbors = k), lof =
+    // -negative_outlier_factor_; k counts OTHER rows, 1 <= k <= size() - 1
+    Lof<A> lof(size_t k) const {
+        Lof<A> res;
+        res.lof.resize(n_);
+        res.lrd.resize(n_);
+        res.kdist.resize(n_);
+        if constexpr (kF32)
+            check(pn_lof_f32(h_, k, 0u, res.lof.data(), res.lrd.data(), res.kdist.data()));
+        else
+            check(pn_lof_f64(h_, k, 0u, res.lof.data(), res.lrd.data(), res.kdist.data()));
+        return res;
+    }
+    // extension: the scores of nq new points (row-major, as long as the indexed rows) against a fit of the same k (pn_lof_score_*).  A
+    // fitted row scored here finds itself at distance 0: it does not reproduce its fit score
+    std::vector<double> lof_score(const A *queries, size_t nq, const Lof<A> &fit, size_t k) const {
+        if (fit.lrd.size() != n_ || fit.kdist.size() != n_)
+            throw std::invalid_argument("lof_score: the fit must hold one lrd and one kdist per indexed row");
+        std::vector<double> score(nq);
+        double none = 0.0;  // (nq = 0: the library still wants an address)
+        double *out = nq ? score.data() : &none;
+        if constexpr (kF32)
+            check(pn_lof_score_f32(h_, queries, nq, dim_, (ptrdiff_t)dim_, k, fit.lrd.data(), fit.kdist.data(), 0u, out));
+        else
+            check(pn_lof_score_f64(h_, queries, nq, dim_, (ptrdiff_t)dim_, k, fit.lrd.data(), fit.kdist.data(), 0u, out));
+        return score;
     }
     // extension: one radius per row (pn_query_radii_self_*): radii [size()], row i's list is the scalar overload's for
     // r = radii[i].  (Taken for pointer arguments only: a literal 0 or NULL stays a call of the scalar overload.)

@@ -119,6 +119,14 @@ SIGNATURES = {
     "pn_hdbscan_f64": (_i, [_vp, _sz, _sz, C.c_uint, _vp, _vp, _vp]),
     "pn_hdbscan_device_f32": (_i, [_vp, _sz, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
     "pn_hdbscan_device_f64": (_i, [_vp, _sz, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
+    "pn_lof_f32": (_i, [_vp, _sz, C.c_uint, _vp, _vp, _vp]),
+    "pn_lof_f64": (_i, [_vp, _sz, C.c_uint, _vp, _vp, _vp]),
+    "pn_lof_device_f32": (_i, [_vp, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
+    "pn_lof_device_f64": (_i, [_vp, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
+    "pn_lof_score_f32": (_i, [_vp, _vp, _sz, _sz, _ssz, _sz, _vp, _vp, C.c_uint, _vp]),
+    "pn_lof_score_f64": (_i, [_vp, _vp, _sz, _sz, _ssz, _sz, _vp, _vp, C.c_uint, _vp]),
+    "pn_lof_score_device_f32": (_i, [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, C.c_uint, _vp, _vp]),
+    "pn_lof_score_device_f64": (_i, [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, C.c_uint, _vp, _vp]),
     "pn_free": (None, [_vp]),
     "pn_pairwise_f32": (_i, [_vp, _sz, _sz, _ssz, _i, _vp]),
     "pn_pairwise_f64": (_i, [_vp, _sz, _sz, _ssz, _i, _vp]),

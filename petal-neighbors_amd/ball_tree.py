@@ -768,3 +768,95 @@ class BallTree:
         check(getattr(_lib.lib(), f"pn_hdbscan_device_{self._sfx}")(
             self._h, k, m, 0, labels.data_ptr(), prob.data_ptr(), ncl.data_ptr(), C.c_void_p(st)))
         return labels, prob, ncl
+
+    # ------------------------------------------------------ Local Outlier Factor
+    # scikit-learn's ``LocalOutlierFactor(n_neighbors=k)`` on the device (``pn_lof_*``): the k self-query, packed in HBM,
+    # one gather pass for the local reachability densities and one for the scores; ``lof == -negative_outlier_factor_``.
+    # ``lrd`` and ``kdist`` are the fit: ``lof_score`` takes them back to score new points (``score_samples`` negated).
+    def _lof_k(self, k):
+        k = int(k)
+        if k < 1 or k > self._n - 1:
+            raise ValueError(f"k must be in [1, n - 1] = [1, {self._n - 1}]")
+        return k
+
+    def _lof_on_device(self, t, want, need):
+        """``t`` is a contiguous CUDA tensor of dtype ``want`` on the tree's device with at least ``need`` elements"""
+        import torch
+        return (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == self.device and t.dtype == want
+                and t.numel() >= need and t.is_contiguous())
+
+    def lof(self, k: int = 20, full: bool = False):
+        """Local Outlier Factor of every indexed row over its ``k`` nearest OTHER rows: ``scores float64 [n]``, or
+        ``(scores, lrd float64 [n], kdist [n])`` with ``full=True``."""
+        k = self._lof_k(k)
+        scores = np.empty(self._n, dtype=np.float64)
+        lrd = np.empty(self._n, dtype=np.float64) if full else None
+        kdist = np.empty(self._n, dtype=self.dtype) if full else None
+        check(getattr(_lib.lib(), f"pn_lof_{self._sfx}")(self._h, k, 0, scores.ctypes.data,
+                                                        lrd.ctypes.data if full else None,
+                                                        kdist.ctypes.data if full else None))
+        return (scores, lrd, kdist) if full else scores
+
+    def lof_device(self, k: int = 20, out_lof=None, out_lrd=None, out_kdist=None, stream=None):
+        """``lof`` in HBM: CUDA tensors ``(lof float64 [n], lrd float64 [n], kdist [n])`` written in stream order on
+        ``stream`` (default: the current torch stream); the call does not wait for the device."""
+        import torch
+        k = self._lof_k(k)
+        tdt = torch.float32 if self._sfx == "f32" else torch.float64
+        dev = torch.device("cuda", self.device)
+        n = self._n
+        for t, want in ((out_lof, torch.float64), (out_lrd, torch.float64), (out_kdist, tdt)):
+            if t is not None and not self._lof_on_device(t, want, n):
+                raise ValueError(f"output tensors must be contiguous CUDA tensors of at least {n} values on the tree's "
+                                 "device (float64; kdist of the tree's element type)")
+        lof = out_lof if out_lof is not None else torch.empty(n, dtype=torch.float64, device=dev)
+        lrd = out_lrd if out_lrd is not None else torch.empty(n, dtype=torch.float64, device=dev)
+        kdist = out_kdist if out_kdist is not None else torch.empty(n, dtype=tdt, device=dev)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        check(getattr(_lib.lib(), f"pn_lof_device_{self._sfx}")(self._h, k, 0, lof.data_ptr(), lrd.data_ptr(),
+                                                               kdist.data_ptr(), C.c_void_p(st)))
+        return lof, lrd, kdist
+
+    def lof_score(self, queries, k: int, lrd, kdist):
+        """Outlier scores ``float64 [nq]`` of new points against a fit: ``lrd`` and ``kdist`` are ``lof(k, full=True)``'s,
+        with the same ``k``.  A fitted row scored here finds itself at distance 0, so it does not reproduce its fit score
+        (scikit-learn's ``score_samples`` behaves the same way)."""
+        k = self._lof_k(k)
+        lrd = np.ascontiguousarray(lrd, dtype=np.float64)
+        kdist = np.ascontiguousarray(kdist, dtype=self.dtype)
+        if lrd.ndim != 1 or lrd.shape[0] != self._n or kdist.ndim != 1 or kdist.shape[0] != self._n:
+            raise ValueError(f"lrd and kdist must hold one value per indexed row ({self._n})")
+        a = self._queries(queries, False)
+        nq, qc = a.shape
+        scores = np.empty(nq, dtype=np.float64)
+        if nq:
+            check(getattr(_lib.lib(), f"pn_lof_score_{self._sfx}")(
+                self._h, a.ctypes.data, nq, qc, max(qc, 1), k, lrd.ctypes.data, kdist.ctypes.data, 0, scores.ctypes.data))
+        return scores
+
+    def lof_score_device(self, queries, k: int, lrd, kdist, out=None, stream=None):
+        """``lof_score`` in HBM: ``queries`` a 2-D CUDA tensor of the tree's element type, ``lrd`` (float64) and ``kdist``
+        contiguous 1-D CUDA tensors of n values (``lof_device``'s); returns the CUDA tensor ``scores float64 [nq]``,
+        written in stream order on ``stream`` (default: the current torch stream)."""
+        import torch
+        k = self._lof_k(k)
+        tdt = torch.float32 if self._sfx == "f32" else torch.float64
+        for t, want in ((lrd, torch.float64), (kdist, tdt)):
+            if not self._lof_on_device(t, want, self._n) or t.dim() != 1 or t.numel() != self._n:
+                raise ValueError(f"lrd and kdist must be contiguous 1-D CUDA tensors of {self._n} values on the tree's "
+                                 "device (float64, the tree's element type)")
+        if (not isinstance(queries, torch.Tensor) or queries.dtype != tdt or queries.dim() != 2 or not queries.is_cuda
+                or queries.device.index != self.device):
+            raise ValueError(f"queries must be a 2-D {tdt} CUDA tensor on the tree's device")
+        if queries.shape[1] > 1 and queries.stride(1) != 1:
+            queries = queries.contiguous()
+        nq, qc = queries.shape
+        if out is not None and not self._lof_on_device(out, torch.float64, nq):
+            raise ValueError(f"out must be a contiguous float64 CUDA tensor of at least {nq} values on the tree's device")
+        scores = out if out is not None else torch.empty(nq, dtype=torch.float64, device=queries.device)
+        if nq:
+            st = stream if stream is not None else torch.cuda.current_stream(queries.device).cuda_stream
+            check(getattr(_lib.lib(), f"pn_lof_score_device_{self._sfx}")(
+                self._h, queries.data_ptr(), nq, qc, queries.stride(0) if nq > 1 else max(qc, 1), k, lrd.data_ptr(),
+                kdist.data_ptr(), 0, scores.data_ptr(), C.c_void_p(st)))
+        return scores

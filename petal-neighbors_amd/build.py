@@ -45,6 +45,7 @@ UNITS = [
     ("components.hip", []),
     ("mst.hip", []),
     ("linkage.hip", []),
+    ("lof.hip", ["-ffp-contract=off"]),
     ("radii_tau.hip", ["-ffp-contract=off"]),
     ("metric.cpp", ["-ffp-contract=off"]),
     ("tree.cpp", ["-ffp-contract=off"]),

@@ -155,6 +155,9 @@ struct Workspace {
     // pn_linkage_* / pn_hdbscan_*: the scratch of linkage.hip (+ the core distances and the tree edges of an HDBSCAN call),
     // and the host entries' inputs and outputs
     DevBuf w_hdb, w_hdb_io;
+    // pn_lof_* / pn_lof_score_*: the graph store of a fit ([n][k] uint32 ids, [n][k] distances; + lrd and kdist when the
+    // caller keeps neither), and the host entries' inputs and outputs
+    DevBuf w_lof, w_lof_io;
     // small calls (tiny_*): mapped pinned host memory the one kernel of the call reads its queries from and writes its
     // answers to -- no copy commands
     void *pin_in = nullptr, *pin_out = nullptr;
@@ -180,7 +183,7 @@ struct Workspace {
     hipEvent_t done = nullptr;
     hipStream_t last_stream = nullptr;
     bool in_flight = false;
-    DevBuf *all[59] = {&w_hdb, &w_hdb_io, &w_mst, &w_mst_io, &w_db, &w_db_side, &w_db_out, &w_hrad, &w_sf_idx, &w_sf_dist, &w_sf_off, &w_sf_coff, &w_sf_flag, &w_sf_cnt, &w_sf_scan, &w_sf_hoff, &w_cs_hoff, &w_rkd, &w_cs_nch, &w_cs_off, &w_cs_scan, &w_cs_idx, &w_cs_dist, &w_gqn, &w_rpos, &w_rfin, &w_rcx, &w_rox, &w_rscan, &w_q, &w_qnorm, &w_qnrm, &w_keys, &w_idx, &w_cnt, &w_tau, &w_flags, &w_sel, &w_misc, &w2_keys, &w2_idx,
+    DevBuf *all[61] = {&w_lof, &w_lof_io, &w_hdb, &w_hdb_io, &w_mst, &w_mst_io, &w_db, &w_db_side, &w_db_out, &w_hrad, &w_sf_idx, &w_sf_dist, &w_sf_off, &w_sf_coff, &w_sf_flag, &w_sf_cnt, &w_sf_scan, &w_sf_hoff, &w_cs_hoff, &w_rkd, &w_cs_nch, &w_cs_off, &w_cs_scan, &w_cs_idx, &w_cs_dist, &w_gqn, &w_rpos, &w_rfin, &w_rcx, &w_rox, &w_rscan, &w_q, &w_qnorm, &w_qnrm, &w_keys, &w_idx, &w_cnt, &w_tau, &w_flags, &w_sel, &w_misc, &w2_keys, &w2_idx,
                        &w2_cnt, &w2_tau, &w_lo, &w_bq, &w_qn, &w_qbad, &w_gq, &w_gidx, &w_gdist, &w_gsel, &w_seed,
                        &w_qstat, &w_lists, &w_hq, &w_hidx, &w_hdist, &w_fparts, &w_pcnt};
     std::vector<void *> retired;  // outgrown allocations, freed once `done` has passed (DevBuf::ensure)
@@ -4092,6 +4095,189 @@ extern "C" int pn_hdbscan_device_f64(const pn_index *ix, size_t min_samples, siz
                                      int64_t *d_labels, double *d_probabilities, uint64_t *d_n_clusters, void *stream) {
     return hdbscan_device<double>(ix, min_samples, min_cluster_size, flags, d_labels, d_probabilities, d_n_clusters,
                                   (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------
+// Local Outlier Factor: pn_lof_{,device_}{f32,f64} (the scores of the indexed rows) and pn_lof_score_{,device_}{f32,f64}
+// (new points against a fit).  The fit = the self-query, chunk by chunk, packed into the graph store, then one gather
+// pass for lrd and one for lof; scoring = the ordinary k-NN query, chunk by chunk, and one fused kernel (lof.hip holds
+// the kernels and the arithmetic).  Here: the argument checks, the workspace and the chain.  Nothing waits for the device
+// but the host entries' final copy.
+// ---------------------------------------------------------------------------
+static int lof_k_rows(const pn_index *ix, size_t k, int elem_bytes) {
+    if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
+    if (ix->elem_bytes != elem_bytes) return fail(PN_ERR_INVALID, "index element type mismatch");
+    if (ix->n < 2) return fail(PN_ERR_INVALID, "LOF needs at least 2 rows (the index holds %zu)", ix->n);
+    if (k < 1 || k > ix->n - 1) return fail(PN_ERR_INVALID, "k must be in [1, n - 1] = [1, %zu]", ix->n - 1);
+    if (ix->n > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many rows for LOF (32-bit neighbour ids)");
+    return PN_OK;
+}
+static int lof_args(const pn_index *ix, size_t k, unsigned flags, const void *lof, int elem_bytes) {
+    if (flags) return fail(PN_ERR_INVALID, "unknown LOF flags 0x%x", flags);
+    if (!lof) return fail(PN_ERR_INVALID, "lof is NULL");
+    return lof_k_rows(ix, k, elem_bytes);
+}
+static int lof_score_args(const pn_index *ix, const void *queries, size_t nq, size_t k, const void *lrd, const void *kdist,
+                          unsigned flags, const void *score, int elem_bytes) {
+    if (flags) return fail(PN_ERR_INVALID, "unknown LOF flags 0x%x", flags);
+    if (!score) return fail(PN_ERR_INVALID, "score_out is NULL");
+    if (nq && (!queries || !lrd || !kdist))
+        return fail(PN_ERR_INVALID, "%s is NULL", !queries ? "queries" : !lrd ? "lrd" : "kdist");
+    return lof_k_rows(ix, k, elem_bytes);
+}
+// in a held workspace, on stream s; outputs in HBM (d_lrd, d_kdist nullable: then they live behind the store)
+template <typename T>
+static int lof_enqueue(const pn_index *ix, Workspace &ws, size_t k, double *d_lof, double *d_lrd, T *d_kdist, hipStream_t s) {
+    const size_t n = ix->n;
+    const size_t ids_bytes = round_up(n * k * sizeof(uint32_t), (size_t)16), dist_bytes = round_up(n * k * sizeof(T), (size_t)16);
+    PNCHK(ws.w_lof.ensure(ids_bytes + dist_bytes + (d_lrd ? 0 : n * sizeof(double)) + (d_kdist ? 0 : n * sizeof(T))));
+    uint32_t *ids = (uint32_t *)ws.w_lof.p;
+    T *dist = (T *)((char *)ws.w_lof.p + ids_bytes);
+    char *tail = (char *)ws.w_lof.p + ids_bytes + dist_bytes;
+    if (!d_lrd) {
+        d_lrd = (double *)tail;
+        tail += n * sizeof(double);
+    }
+    if (!d_kdist) d_kdist = (T *)tail;
+    // ---- the graph: the k self-query, chunk by chunk, packed into the store
+    for (size_t r0 = 0; r0 < n; r0 += kSelfChunk) {
+        const size_t nqc = n - r0 < kSelfChunk ? n - r0 : kSelfChunk;
+        PNCHK(ws.w_hidx.ensure(nqc * k * sizeof(uint64_t)));
+        PNCHK(ws.w_hdist.ensure(nqc * k * sizeof(T)));
+        PNCHK(self_knn_chunk<T>(ix, ws, r0, nqc, k + 1, k, false, (uint64_t *)ws.w_hidx.p, (T *)ws.w_hdist.p, s));
+        if constexpr (sizeof(T) == 4)
+            HIPCHK(launch_lof_pack_f32((const uint64_t *)ws.w_hidx.p, (const T *)ws.w_hdist.p, nqc, (int)k, ix->index_base,
+                                       ids + r0 * k, dist + r0 * k, d_kdist + r0, s));
+        else
+            HIPCHK(launch_lof_pack_f64((const uint64_t *)ws.w_hidx.p, (const T *)ws.w_hdist.p, nqc, (int)k, ix->index_base,
+                                       ids + r0 * k, dist + r0 * k, d_kdist + r0, s));
+    }
+    // ---- two gather passes over it
+    if constexpr (sizeof(T) == 4)
+        HIPCHK(launch_lof_lrd_f32(ids, dist, d_kdist, n, (int)k, d_lrd, s));
+    else
+        HIPCHK(launch_lof_lrd_f64(ids, dist, d_kdist, n, (int)k, d_lrd, s));
+    HIPCHK(launch_lof_lof(ids, d_lrd, n, (int)k, d_lof, s));
+    return PN_OK;
+}
+template <typename T>
+static int lof_device(const pn_index *ix, size_t k, unsigned flags, double *d_lof, double *d_lrd, T *d_kdist, hipStream_t s) {
+    PNCHK(lof_args(ix, k, flags, d_lof, (int)sizeof(T)));
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    lease.s = s;
+    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
+    return lof_enqueue<T>(ix, *lease.ws, k, d_lof, d_lrd, d_kdist, s);
+}
+template <typename T>
+static int lof_host(const pn_index *ix, size_t k, unsigned flags, double *lof, double *lrd, T *kdist) {
+    PNCHK(lof_args(ix, k, flags, lof, (int)sizeof(T)));
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
+    Workspace &ws = *lease.ws;
+    hipStream_t s = lease.s;
+    const size_t n = ix->n;
+    PNCHK(ws.w_lof_io.ensure(2 * n * sizeof(double) + n * sizeof(T)));
+    double *d_lof = (double *)ws.w_lof_io.p, *d_lrd = d_lof + n;
+    T *d_kdist = (T *)(d_lrd + n);
+    PNCHK(lof_enqueue<T>(ix, ws, k, d_lof, d_lrd, d_kdist, s));
+    HIPCHK(hipMemcpyAsync(lof, d_lof, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (lrd) HIPCHK(hipMemcpyAsync(lrd, d_lrd, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (kdist) HIPCHK(hipMemcpyAsync(kdist, d_kdist, n * sizeof(T), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return PN_OK;
+}
+extern "C" int pn_lof_f32(const pn_index *ix, size_t k, unsigned flags, double *lof, double *lrd, float *kdist) {
+    return lof_host<float>(ix, k, flags, lof, lrd, kdist);
+}
+extern "C" int pn_lof_f64(const pn_index *ix, size_t k, unsigned flags, double *lof, double *lrd, double *kdist) {
+    return lof_host<double>(ix, k, flags, lof, lrd, kdist);
+}
+extern "C" int pn_lof_device_f32(const pn_index *ix, size_t k, unsigned flags, double *d_lof, double *d_lrd, float *d_kdist,
+                                 void *stream) {
+    return lof_device<float>(ix, k, flags, d_lof, d_lrd, d_kdist, (hipStream_t)stream);
+}
+extern "C" int pn_lof_device_f64(const pn_index *ix, size_t k, unsigned flags, double *d_lof, double *d_lrd, double *d_kdist,
+                                 void *stream) {
+    return lof_device<double>(ix, k, flags, d_lof, d_lrd, d_kdist, (hipStream_t)stream);
+}
+
+// queries, lrd, kdist and the scores in HBM; the queries' k-NN answer is staged per 2^18-query chunk
+template <typename T>
+static int lof_score_enqueue(const pn_index *ix, Workspace &ws, const T *d_q, size_t nq, size_t q_cols, size_t q_stride,
+                             size_t k, const double *d_lrd, const T *d_kdist, double *d_score, hipStream_t s) {
+    for (size_t q0 = 0; q0 < nq; q0 += kSelfChunk) {
+        const size_t nqc = nq - q0 < kSelfChunk ? nq - q0 : kSelfChunk;
+        PNCHK(ws.w_hidx.ensure(nqc * k * sizeof(uint64_t)));
+        PNCHK(ws.w_hdist.ensure(nqc * k * sizeof(T)));
+        PNCHK(query_enqueue<T>(ix, ws, d_q + q0 * q_stride, nqc, q_cols, q_stride, k, (uint64_t *)ws.w_hidx.p,
+                               (T *)ws.w_hdist.p, k, s));
+        if constexpr (sizeof(T) == 4)
+            HIPCHK(launch_lof_score_f32((const uint64_t *)ws.w_hidx.p, (const T *)ws.w_hdist.p, nqc, (int)k, ix->index_base,
+                                        ix->n, d_lrd, d_kdist, d_score + q0, s));
+        else
+            HIPCHK(launch_lof_score_f64((const uint64_t *)ws.w_hidx.p, (const T *)ws.w_hdist.p, nqc, (int)k, ix->index_base,
+                                        ix->n, d_lrd, d_kdist, d_score + q0, s));
+    }
+    return PN_OK;
+}
+template <typename T>
+static int lof_score_device(const pn_index *ix, const T *d_q, size_t nq, size_t q_cols, size_t q_stride, size_t k,
+                            const double *d_lrd, const T *d_kdist, unsigned flags, double *d_score, hipStream_t s) {
+    PNCHK(lof_score_args(ix, d_q, nq, k, d_lrd, d_kdist, flags, d_score, (int)sizeof(T)));
+    if (nq == 0) return PN_OK;
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    lease.s = s;
+    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
+    return lof_score_enqueue<T>(ix, *lease.ws, d_q, nq, q_cols, q_stride, k, d_lrd, d_kdist, d_score, s);
+}
+template <typename T>
+static int lof_score_host(const pn_index *ix, const T *q, size_t nq, size_t q_cols, ptrdiff_t q_stride, size_t k,
+                          const double *lrd, const T *kdist, unsigned flags, double *score) {
+    PNCHK(lof_score_args(ix, q, nq, k, lrd, kdist, flags, score, (int)sizeof(T)));
+    if (nq == 0) return PN_OK;
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
+    Workspace &ws = *lease.ws;
+    hipStream_t s = lease.s;
+    const size_t n = ix->n;
+    PNCHK(upload_rows_to<T>(q, nq, q_cols, q_stride, ws.w_hq, s));
+    PNCHK(ws.w_lof_io.ensure((n + nq) * sizeof(double) + n * sizeof(T)));
+    double *d_lrd = (double *)ws.w_lof_io.p, *d_score = d_lrd + n;
+    T *d_kdist = (T *)(d_score + nq);
+    HIPCHK(hipMemcpyAsync(d_lrd, lrd, n * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_kdist, kdist, n * sizeof(T), hipMemcpyHostToDevice, s));
+    PNCHK(lof_score_enqueue<T>(ix, ws, (const T *)ws.w_hq.p, nq, q_cols, q_cols ? q_cols : 1, k, d_lrd, d_kdist, d_score, s));
+    HIPCHK(hipMemcpyAsync(score, d_score, nq * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return PN_OK;
+}
+extern "C" int pn_lof_score_f32(const pn_index *ix, const float *queries, size_t nq, size_t q_cols, ptrdiff_t q_row_stride,
+                                size_t k, const double *lrd, const float *kdist, unsigned flags, double *score_out) {
+    return lof_score_host<float>(ix, queries, nq, q_cols, q_row_stride, k, lrd, kdist, flags, score_out);
+}
+extern "C" int pn_lof_score_f64(const pn_index *ix, const double *queries, size_t nq, size_t q_cols, ptrdiff_t q_row_stride,
+                                size_t k, const double *lrd, const double *kdist, unsigned flags, double *score_out) {
+    return lof_score_host<double>(ix, queries, nq, q_cols, q_row_stride, k, lrd, kdist, flags, score_out);
+}
+extern "C" int pn_lof_score_device_f32(const pn_index *ix, const float *d_queries, size_t nq, size_t q_cols,
+                                       size_t q_row_stride, size_t k, const double *d_lrd, const float *d_kdist,
+                                       unsigned flags, double *d_score, void *stream) {
+    return lof_score_device<float>(ix, d_queries, nq, q_cols, q_row_stride, k, d_lrd, d_kdist, flags, d_score,
+                                   (hipStream_t)stream);
+}
+extern "C" int pn_lof_score_device_f64(const pn_index *ix, const double *d_queries, size_t nq, size_t q_cols,
+                                       size_t q_row_stride, size_t k, const double *d_lrd, const double *d_kdist,
+                                       unsigned flags, double *d_score, void *stream) {
+    return lof_score_device<double>(ix, d_queries, nq, q_cols, q_row_stride, k, d_lrd, d_kdist, flags, d_score,
+                                    (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------

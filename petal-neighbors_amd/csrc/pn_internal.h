@@ -234,6 +234,25 @@ int hdbscan_extract_enqueue_f64(const HdbscanArgs &a, hipStream_t s);
 hipError_t launch_last_column_f32(const float *d, size_t rows, size_t k, float *out, hipStream_t s);
 hipError_t launch_last_column_f64(const double *d, size_t rows, size_t k, double *out, hipStream_t s);
 
+// ---- lof.hip: Local Outlier Factor over the self-k-NN graph (pn_lof_*, pn_lof_score_*); nothing in it waits for the device.
+// pack: a self-query chunk's answer [nq][k] (ids with the index base) -> the store's rows: ids [nq][k] uint32 without the
+// base, dist [nq][k], kdist [nq] = the last column
+hipError_t launch_lof_pack_f32(const uint64_t *in_idx, const float *in_dist, size_t nq, int k, uint64_t index_base,
+                               uint32_t *ids, float *dist, float *kdist, hipStream_t s);
+hipError_t launch_lof_pack_f64(const uint64_t *in_idx, const double *in_dist, size_t nq, int k, uint64_t index_base,
+                               uint32_t *ids, double *dist, double *kdist, hipStream_t s);
+// lrd [n] from the store and kdist [n]; lof [n] from the store's ids and lrd [n]
+hipError_t launch_lof_lrd_f32(const uint32_t *ids, const float *dist, const float *kdist, size_t n, int k, double *lrd,
+                              hipStream_t s);
+hipError_t launch_lof_lrd_f64(const uint32_t *ids, const double *dist, const double *kdist, size_t n, int k, double *lrd,
+                              hipStream_t s);
+hipError_t launch_lof_lof(const uint32_t *ids, const double *lrd, size_t n, int k, double *lof, hipStream_t s);
+// score [nq] of queries from their k-NN answer [nq][k] (ids with the index base) and the fit's lrd [n], kdist [n]
+hipError_t launch_lof_score_f32(const uint64_t *q_idx, const float *q_dist, size_t nq, int k, uint64_t index_base, size_t n,
+                                const double *lrd, const float *kdist, double *score, hipStream_t s);
+hipError_t launch_lof_score_f64(const uint64_t *q_idx, const double *q_dist, size_t nq, int k, uint64_t index_base, size_t n,
+                                const double *lrd, const double *kdist, double *score, hipStream_t s);
+
 // ---- csr_sort.hip: order every list of a radius answer by (distance, index) in place (PN_RADIUS_SORTED)
 constexpr int kSortTile = 2048;  // longest list sorted by one workgroup in LDS; longer lists: chunks + merge passes
 struct CsrSortScratch {
