@@ -190,83 +190,18 @@ __device__ __forceinline__ size_t bf_wide_at(size_t r, int k, int dim) {  // bf1
     return tile + ((size_t)(k >> 6) * kWR + rr) * (size_t)(kWPitch / 2) + (size_t)slot * 8 + (size_t)(k & 7);
 }
 
-// One thread per (padded) corpus row: bf16 row + the five extra columns, written into the tile image.
-// narrow (D <= 128): img = [n_tiles][64][CP][8] bf16, CP = 2*KS + 1 chunks per row (last chunk is padding).
+// The tile image of a corpus row: its bf16 coordinates + the five extra columns (or, CI layout, its norm in the tile's
+// padding chunks).  narrow (D <= 128): img = [n_tiles][64][CP][8] bf16, CP = 2*KS + 1 chunks per row (last chunk is padding).
 // T: the index's element type.  An f64 corpus gets the SAME bf16 images (the bound is a statement about real vectors;
 // every constant is computed in f64 from the f64 coordinates), so f64 indexes are served by this tier too.
-template <typename T>
-__global__ void bf16_pack_corpus_kernel(const T *__restrict__ P, const float *__restrict__ mu, size_t n, int dim,
-                                        size_t ld, int KS, uint16_t *__restrict__ img, size_t n_rows_img,
-                                        uint32_t *__restrict__ bad, int wide, int ci) {
-    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_rows_img) return;
-    const int CP = 2 * KS + 1;
-    const int E = bf16_extra_col(dim);
-    auto at = [&](int k) -> uint16_t & { return wide ? img[bf_wide_at(r, k, dim)] : img[r * (size_t)CP * 8 + k]; };
-    // CI layout: the f32 norm of row rr of a tile lives in the padding chunk of the tile's row rr / 4, slot rr % 4
-    float *norm_slot = nullptr;
-    if (ci) {
-        const size_t t = r / kBP, rr = r % kBP;
-        norm_slot = reinterpret_cast<float *>(img + ((t * kBP + rr / 4) * (size_t)CP + (size_t)(CP - 1)) * 8) + (rr % 4);
-    }
-    if (wide) {
-        const int ncol = 64 * bf16_wide_nkc(dim) + (bf16_wide_has_x(dim) ? 16 : 0);
-        for (int k = 0; k < ncol; ++k) at(k) = 0;
-    } else {
-        // CI: the padding chunks of a tile's first 16 rows are written by the rows whose norms they hold
-        const int nz = (ci && (r % kBP) < 16) ? (CP - 1) * 8 : CP * 8;
-        for (int k = 0; k < nz; ++k) at(k) = 0;
-    }
-    if (r >= n) {
-        // 1.7e38: never among the k' smallest of real rows (select.hip drops rows >= n anyway)
-        if (ci) *norm_slot = 1.7e38f; else at(E) = 0x7F00u;
-        return;
-    }
-    double pn = 0.0, en = 0.0, hn = 0.0;
-    bool finite = true;
-    const T *src = P + r * ld;
-    for (int k = 0; k < dim; ++k) {
-        const double x = (double)src[k];
-        finite = finite && (fabs(x) < 1.0e30);  // also false for NaN
-        const double c = x - (double)mu[k];  // centred coordinate (header: translation)
-        const float cf = (float)c;
-        const uint16_t hb = (fabsf(cf) < 8.67361737988403547e-19f) ? (uint16_t)0 : bf_rne(cf);  // 2^-60
-        const float xh = bf_f(hb);
-        at(k) = hb;
-        pn += c * c;
-        const double e = c - (double)xh;
-        en += e * e;
-        hn += (double)xh * (double)xh;
-    }
-    if (!finite || !(pn < 1.2676506002282294e30)) {  // 2^100
-        atomicOr(bad, 1u);
-        if (ci) *norm_slot = 1.7e38f; else at(E) = 0x7F80u;
-        return;
-    }
-    if (ci) {  // |p|^2 (1 - g), rounded down to f32: the chain's initial accumulator value
-        *norm_slot = f_down(pn * (1.0 - kG) / kUp);
-        return;
-    }
-    // |p|^2 (1 - g), rounded down, in three truncated bf16 pieces
-    double rem = pn * (1.0 - kG) / kUp;
-    const uint16_t h0 = bf_trunc(f_down(rem));
-    rem -= (double)bf_f(h0);
-    const uint16_t h1 = bf_trunc(f_down(rem));
-    rem -= (double)bf_f(h1);
-    const uint16_t h2 = bf_trunc(f_down(rem));
-    at(E + 0) = h0;
-    at(E + 1) = h1;
-    at(E + 2) = h2;
-    const double e_n = sqrt(en) * kUp, h_n = sqrt(hn) * kUp, p_n = sqrt(pn) * kUp;
-    at(E + 3) = bf_up(f_up((2.0 * e_n + 2.0 * kG * h_n) * (1.0 + 2.0 * kG)));
-    at(E + 4) = bf_up(f_up(2.0 * p_n * (1.0 + 2.0 * kG)));
-}
-
+// A query's image: bf16 B row [K] (chunk c at 8c), |q|^2 rounded down (f64), flag; ci: no extra columns,
+// qn[q] = |q|^2 (down) - E(q) (up), E(q) = Aq bmax + Cq dmax (header of bf16_ci_dim).
+//
 // Eight lanes per row (narrow rows): lane `sub` of a row owns the CH = 2 KS columns [sub CH, sub CH + CH) -- 16-byte
 // loads from the padded rows, its part of the three f64 sums, an 8-lane butterfly for the row's totals (any summation
 // order is inside the 2^-40 the norms are widened by) -- what bf16_pack_queries8_kernel does for queries.  The
-// thread-per-row kernels below read their rows one 4-byte element at a time, 64 rows' lines per instruction, and wrote
-// the image in 2-byte stores twice (zero fill, then values): 1M x 128 took 3.46 ms to pack and 2.1 ms for the row
+// thread-per-row kernels before these read their rows one 4-byte element at a time, 64 rows' lines per instruction, and
+// wrote the image in 2-byte stores twice (zero fill, then values): 1M x 128 took 3.46 ms to pack and 2.1 ms for the row
 // statistics -- 0.23 TB/s.  x[i] (centred coordinate, f64) and hb[i] (its bf16) of column c0 + i; columns at or beyond
 // dim are zero.  Returns false for a non-finite coordinate in the lane's part.
 template <typename T>
@@ -487,68 +422,11 @@ __global__ void bf16_row_stats_kernel(const T *__restrict__ P, const float *__re
     }
 }
 
-// One thread per (padded) query: bf16 B row [K] (chunk c at 8c), |q|^2 rounded down (f64), flag.
-// ci: no extra columns; qn[q] = |q|^2 (down) - E(q) (up), E(q) = Aq bmax + Cq dmax (header of bf16_ci_dim)
-template <typename T>
-__global__ void bf16_pack_queries_kernel(const T *__restrict__ Q, const float *__restrict__ mu, size_t nq,
-                                         size_t nq_pad, int dim, size_t ld, int KS, uint16_t *__restrict__ B,
-                                         double *__restrict__ qn, uint32_t *__restrict__ qbad, int wide, int ci,
-                                         double bmax, double dmax) {
-    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= nq_pad) return;
-    const int K = 16 * KS, E = bf16_extra_col(dim);
-    auto at = [&](int k) -> uint16_t & { return wide ? B[bf_wide_at(q, k, dim)] : B[q * (size_t)K + k]; };
-    if (wide) {
-        const int ncol = 64 * bf16_wide_nkc(dim) + (bf16_wide_has_x(dim) ? 16 : 0);
-        for (int k = 0; k < ncol; ++k) at(k) = 0;
-    } else {
-        for (int k = 0; k < K; ++k) at(k) = 0;
-    }
-    double s = 0.0, en = 0.0, hn = 0.0;
-    bool finite = true;
-    if (q < nq) {
-        const T *src = Q + q * ld;
-        for (int k = 0; k < dim; ++k) {
-            const double x = (double)src[k];
-            finite = finite && (fabs(x) < 1.0e30);
-            const double c = x - (double)mu[k];
-            const float cf = (float)c;
-            const uint16_t hb = (fabsf(cf) < 8.67361737988403547e-19f) ? (uint16_t)0 : bf_rne(cf);
-            const float xh = bf_f(hb);
-            at(k) = bf_rne(-2.0f * xh);  // exact: a power-of-two multiple of a bf16 value
-            s += c * c;
-            const double e = c - (double)xh;
-            en += e * e;
-            hn += (double)xh * (double)xh;
-        }
-    }
-    const bool ok = finite && (s < 1.2676506002282294e30);
-    if (ci) {
-        if (!ok)
-            for (int k = 0; k < dim; ++k) at(k) = 0;
-        const double eq = (sqrt(hn) * kUp * bmax + sqrt(en) * kUp * dmax) * kUp;
-        qn[q] = ok ? s / kUp - eq : 0.0;
-        qbad[q] = ok ? 0u : 1u;
-        return;
-    }
-    at(E + 0) = 0x3F80u;  // 1.0
-    at(E + 1) = 0x3F80u;
-    at(E + 2) = 0x3F80u;
-    if (ok) {
-        at(E + 3) = (uint16_t)(bf_up(f_up(sqrt(hn) * kUp)) | 0x8000u);  // -Aq
-        at(E + 4) = (uint16_t)(bf_up(f_up(sqrt(en) * kUp)) | 0x8000u);  // -Cq
-    } else {
-        for (int k = 0; k < dim; ++k) at(k) = 0;  // keep the arithmetic finite; the query is re-run exactly
-    }
-    qn[q] = ok ? s / kUp : 0.0;
-    qbad[q] = ok ? 0u : 1u;
-}
-
 // Wide rows (corpus and queries share the K-chunked layout), EIGHT lanes per row: lane `sub` packs the 16-byte slots
 // sub, sub + 8, ... (8 columns each: two 16-byte loads, one 16-byte store at the slot's swizzled place), the three f64
 // sums go through an 8-lane butterfly, and the slot(s) holding the five extra values are stored last, by their owners,
-// with the values in place.  The thread-per-row kernels (kept below for reference builds, -DPN_DIAG_BF_PACK1) wrote
-// every row twice in 2-byte stores: 1M x 768 took 21.4 ms to pack, 10^4 queries 0.28 ms of every step.
+// with the values in place.  The thread-per-row kernels before this one wrote every row twice in 2-byte stores: 1M x 768
+// took 21.4 ms to pack, 10^4 queries 0.28 ms of every step.
 template <typename T, bool QRY>
 __global__ void bf16_pack_wide8_kernel(const T *__restrict__ X, const float *__restrict__ mu, size_t n_valid,
                                        size_t n_rows_img, int dim, size_t ld, uint16_t *__restrict__ img,
@@ -1025,26 +903,14 @@ __device__ __forceinline__ void bf_compact_finish(uint2 *ce, const uint32_t (&ke
 // (Round 1 tagged every bound with its register number first -- one v_and_or_b32 each, 2/3 of the fast path's vector
 // work -- so that the rare path needed no search; with seeded thresholds the rare path is rare enough to search.)
 // CI: the chain starts from c0 (the 16 row norms of this lane's rows) instead of zero.
-#ifdef PN_DIAG_KLA  // timing experiments: fragment lookahead
-constexpr int kLA = PN_DIAG_KLA;
-#else
 constexpr int kLA = 3;
-#endif
 // Tags (the register number in a bound's low four mantissa bits) are written inside a rare-path entry (bf_slow).
-// Measured alternative, -DPN_DIAG_BF_SHADOWTAG: the main loop writes them while it takes the minimum (bf_chain_p), for
-// kernels with buffers of 128 slots and more, so that an entry needs no tagging pass.  With survivors frequent (1M x
-// 128, k = 100) that was 2 % faster than tagging inside the entry -- but the 32 tagged values per chain cost the
-// kernel ~50 registers (the compiler keeps them beside the accumulator tuples they came from), the KS >= 5 variants
-// spill, and on long runs it is 10 % slower (10M x 128, 10^5 queries, k = 100: 239 vs 215 ms).
-#ifdef PN_DIAG_BF_SHADOWTAG
-constexpr int kBfTagFromM = 2;
-#else
-constexpr int kBfTagFromM = 1000;
-#endif
-#ifndef PN_DIAG_BF_FINALKEEP
-#define PN_DIAG_BF_FINALKEEP 32
-#endif
-constexpr int kBfFinalKeep = PN_DIAG_BF_FINALKEEP;  // 64-slot buffers holding at most this many entries end a run uncut
+// Measured alternative: the main loop writes them while it takes the minimum (bf_chain_p), for kernels with buffers of
+// 128 slots and more, so that an entry needs no tagging pass.  With survivors frequent (1M x 128, k = 100) that was 2 %
+// faster than tagging inside the entry -- but the 32 tagged values per chain cost the kernel ~50 registers (the compiler
+// keeps them beside the accumulator tuples they came from), the KS >= 5 variants spill, and on long runs it is 10 %
+// slower (10M x 128, 10^5 queries, k = 100: 239 vs 215 ms): not used.
+constexpr int kBfFinalKeep = 32;  // 64-slot buffers holding at most this many entries end a run uncut
 constexpr int kScoutList = 12;  // smallest block minima a lane keeps during a scout pass
 // smallest (mn) and second smallest (sec) of 16 finite values: triples give (min3, med3); the second smallest overall
 // is the smaller of {second smallest of the triples' minima, the smallest of the triples' medians} -- 21 instructions.
@@ -1067,34 +933,10 @@ __device__ __forceinline__ void bf_min2(const f32x16 &v, float &mn, float &sec) 
     (void)big;
 }
 
-struct BfPend {
-    float v0, v1;      // pending keys (tagged bounds)
-    uint32_t r0, r1;   // their rows
-    uint32_t c;        // slots in use
-};
-__device__ __forceinline__ void bf_capture(BfPend &pd, float mn, float tau, uint32_t rowb) {
-    const bool hit = mn < tau;
-    const uint32_t t = __float_as_uint(mn) & 15u;
-    const uint32_t row = rowb + (t & 3u) + 8u * (t >> 2);  // C/D map of the 32x32 MFMA (rowb includes 4 h)
-    const bool s0 = hit && pd.c == 0u, s1 = hit && pd.c != 0u;
-    pd.v0 = s0 ? mn : pd.v0;
-    pd.r0 = s0 ? row : pd.r0;
-    pd.v1 = s1 ? mn : pd.v1;
-    pd.r1 = s1 ? row : pd.r1;
-    pd.c += hit ? 1u : 0u;
-}
-// EMB (main pass): in the shadow the VALU also (1) writes each bound's register number into its low four mantissa bits
-// (one v_and_or_b32), so that the minimum names its row, and (2) compares every bound with the query's threshold; the
-// scalar unit folds the sixteen lane masks into `dup` = lanes that hold MORE THAN ONE bound below the threshold.  With
-// dup == 0 (all but one check in a few thousand) a lane's only survivor is its minimum, and the caller captures it
-// without a branch (bf_capture).  The tagged values differ from the bounds by less than 2^-19 relative, which the
-// proof in select.hip subtracts.
-template <int KS, bool CI, bool EMB>
+template <int KS, bool CI>
 __device__ __forceinline__ void bf_chain(const char *arow, const bf16x8 (&pre)[kLA], const bf16x8 (&b0)[KS],
                                          const bf16x8 (&b1)[KS], const f32x16 &c0, f32x16 &w0, f32x16 &w1, f32x16 &r0,
-                                         f32x16 &r1, float &m0, float &m1, float tau0, float tau1,
-                                         unsigned long long &dup0, unsigned long long &dup1, BfPend &pd0, BfPend &pd1,
-                                         float cap0, float cap1, uint32_t cap_rowb) {
+                                         f32x16 &r1, float &m0, float &m1) {
     bf16x8 f[KS];
 #pragma unroll
     for (int i = 0; i < kLA && i < KS; ++i) f[i] = pre[i];
@@ -1111,54 +953,16 @@ __device__ __forceinline__ void bf_chain(const char *arow, const bf16x8 (&pre)[k
             w0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[ks], b0[ks], ks ? w0 : z, 0, 0, 0);
             w1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[ks], b1[ks], ks ? w1 : z, 0, 0, 0);
         }
-        if (EMB && ks == 1) {
-            // the survivors of the block filtered BEFORE this chain (its minima cap0 / cap1, +inf where the general path
-            // has dealt with it) go to their pending slots here, in the matrix pipe's shadow: whatever a wave does
-            // between two chains is on its critical path, whatever it does inside one is not
-            bf_capture(pd0, cap0, tau0, cap_rowb);
-            bf_capture(pd1, cap1, tau1, cap_rowb);
-        }
-#ifdef PN_DIAG_BF_NOSCAN  // timing-only: no minimum
-        if (ks == 0) {
-            m0 = __uint_as_float(0x7F800000u);
-            m1 = m0;
-            dup0 = dup1 = 0ull;
-            asm volatile("" ::"v"(r0[0]), "v"(r1[0]));
-        }
-        if (false) {
-#else
-        if (ks == 0) {
-#endif
-            if (EMB) {
+        // this step's share of the other block's minimum: registers [16 ks / KS, 16 (ks + 1) / KS)
 #pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    r0[i] = __uint_as_float((__float_as_uint(r0[i]) & 0xFFFFFFF0u) | (uint32_t)i);
-                    r1[i] = __uint_as_float((__float_as_uint(r1[i]) & 0xFFFFFFF0u) | (uint32_t)i);
-                }
-                // smallest AND second smallest of the 16 bounds by triples (v_min3 / v_med3): a lane holds two bounds
-                // below its threshold exactly when its second smallest is -- no per-register compares, no scalar work
-                float s0, s1;
-                bf_min2(r0, m0, s0);
-                bf_min2(r1, m1, s1);
-                dup0 = __ballot(s0 < tau0);
-                dup1 = __ballot(s1 < tau1);
-            }
+        for (int i = 16 * ks / KS; i < 16 * (ks + 1) / KS; ++i) {
+            m0 = i ? fminf(m0, r0[i]) : r0[0];
+            m1 = i ? fminf(m1, r1[i]) : r1[0];
         }
-#ifndef PN_DIAG_BF_NOSCAN
-        if (!EMB) {  // this step's share of the other block's minimum: registers [16 ks / KS, 16 (ks + 1) / KS)
-#pragma unroll
-            for (int i = 16 * ks / KS; i < 16 * (ks + 1) / KS; ++i) {
-                m0 = i ? fminf(m0, r0[i]) : r0[0];
-                m1 = i ? fminf(m1, r1[i]) : r1[0];
-            }
-        }
-#endif
-#ifndef PN_DIAG_BF_NOSCHED
         // One step = one fragment read (kLA steps ahead of its use), two MFMAs, a slice of the minimum -- and the
         // scheduler keeps it that way.  Left alone it sinks the reads next to their uses to save registers (the kernel
         // sits just under the two-waves-per-SIMD limit) and waits for them with lgkmcnt(0) in the middle of the chain.
-        if (!EMB) __builtin_amdgcn_sched_barrier(0);
-#endif
+        __builtin_amdgcn_sched_barrier(0);
     }
 }
 
@@ -1184,7 +988,7 @@ __device__ __forceinline__ f32x16 bf_cinit(const char *tb, int blk, int h) {
 // fragments of its own left to request, it requests the same for the NEXT chain (narow / ntb, nblk: the other block of
 // this tile, or block 0 of the next tile).  So no chain waits for LDS at its head, and whatever sits between two
 // chains (the survivor check, the barrier, the LDS-DMA issue) does not delay the first MFMA behind it by a round trip.
-template <int KS, bool CI, int CP, bool TAG>
+template <int KS, bool CI, int CP>
 __device__ __forceinline__ void bf_chain_p(const char *arow, bf16x8 (&pre)[kLA], const bf16x8 (&b0)[KS],
                                            const bf16x8 (&b1)[KS], f32x16 &c, f32x16 &w0, f32x16 &w1, f32x16 &r0,
                                            f32x16 &r1, float &m0, float &m1, const char *narow, const char *ntb,
@@ -1196,11 +1000,6 @@ __device__ __forceinline__ void bf_chain_p(const char *arow, bf16x8 (&pre)[kLA],
     f32x16 z, nc = c;
 #pragma unroll
     for (int i = 0; i < 16; ++i) z[i] = 0.0f;
-#ifdef PN_DIAG_BF_NOSCAN  // timing-only: no minimum
-    m0 = __uint_as_float(0x7F800000u);
-    m1 = m0;
-    asm volatile("" ::"v"(r0[0]), "v"(r1[0]));
-#endif
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
         if (ks + kLA < KS) f[ks + kLA] = *reinterpret_cast<const bf16x8 *>(arow + 32 * (ks + kLA));
@@ -1220,51 +1019,21 @@ __device__ __forceinline__ void bf_chain_p(const char *arow, bf16x8 (&pre)[kLA],
                     nc[4 * g + 2] = v[2];
                     nc[4 * g + 3] = v[3];
                 }
-#ifdef PN_DIAG_BF_1632  // TIMING ONLY (wrong results): the same flops as two v_mfma_f32_16x16x32_bf16 per 32x32x16
-            {
-                typedef float f32x4_t __attribute__((ext_vector_type(4)));
-                const f32x16 s0 = ks ? w0 : c, s1 = ks ? w1 : c;
-                f32x4_t q00 = __builtin_shufflevector(s0, s0, 0, 1, 2, 3), q01 = __builtin_shufflevector(s0, s0, 4, 5, 6, 7);
-                f32x4_t q10 = __builtin_shufflevector(s1, s1, 0, 1, 2, 3), q11 = __builtin_shufflevector(s1, s1, 4, 5, 6, 7);
-                q00 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[ks], b0[ks], q00, 0, 0, 0);
-                q01 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[ks], b0[ks], q01, 0, 0, 0);
-                q10 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[ks], b1[ks], q10, 0, 0, 0);
-                q11 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[ks], b1[ks], q11, 0, 0, 0);
-                w0 = s0;
-                w1 = s1;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    w0[i] = q00[i];
-                    w0[4 + i] = q01[i];
-                    w1[i] = q10[i];
-                    w1[4 + i] = q11[i];
-                }
-            }
-#else
             w0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[ks], b0[ks], ks ? w0 : c, 0, 0, 0);
             w1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[ks], b1[ks], ks ? w1 : c, 0, 0, 0);
-#endif
-#ifndef PN_DIAG_BF_NOKEEPC
             // c outlives both MFMAs that read it: otherwise the second one accumulates IN c's registers, its proper
             // registers serve as fragment space meanwhile, and sixteen moves that wait for the matrix pipe bring the
             // result home before the last step
             if (ks == 0) asm volatile("" ::"v"(c));
-#endif
         } else {
             w0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[ks], b0[ks], ks ? w0 : z, 0, 0, 0);
             w1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[ks], b1[ks], ks ? w1 : z, 0, 0, 0);
         }
-#ifndef PN_DIAG_BF_NOSCAN
 #pragma unroll
         for (int i = 16 * ks / KS; i < 16 * (ks + 1) / KS; ++i) {  // this step's share of the other block's minimum
-            if (TAG) {  // the register number goes into the low four mantissa bits first (one v_and_or_b32): see bf_slow
-                r0[i] = __uint_as_float((__float_as_uint(r0[i]) & 0xFFFFFFF0u) | (uint32_t)i);
-                r1[i] = __uint_as_float((__float_as_uint(r1[i]) & 0xFFFFFFF0u) | (uint32_t)i);
-            }
             m0 = i ? fminf(m0, r0[i]) : r0[0];
             m1 = i ? fminf(m1, r1[i]) : r1[0];
         }
-#endif
         __builtin_amdgcn_sched_barrier(0);  // a step stays a step (see bf_chain)
     }
     c = nc;
@@ -1412,20 +1181,11 @@ __device__ __forceinline__ void bf_refresher(const uint2 *__restrict__ cand, con
 // SH (shared thresholds, above): entries are stored write-through, and a buffer about to be compacted is first
 // published as empty under the wave's next tag (pc_blk = the published words of this query block's 32 buffers, pc_tag =
 // epoch | the wave's compaction count, advanced here).
-// INPLACE: the tags are written into acc itself (the caller's accumulator is dead after this check: the next chain
-// overwrites it) -- sixteen registers less where the rare path is the kernel's register peak (bf16_filter8_kernel)
-template <int M, bool RAD, bool TAGGED = false, bool SH = false, bool INPLACE = false>
+template <int M, bool RAD, bool SH = false>
 __device__ __forceinline__ void bf_slow(const f32x16 &acc, float mn, float &tau, uint32_t &cnt, uint32_t row0, int h,
                                         int jq, int lane, uint32_t kp, uint2 *ceq, uint2 *ce_blk,
                                         uint32_t &ns BF_DBG_ARG, uint32_t *pc_blk = nullptr, uint32_t *pc_ncomp = nullptr,
                                         uint32_t pc_epoch = 0) {
-#ifdef PN_DIAG_BF_NOSLOW  // timing-only build: results are wrong
-    asm volatile("" ::"v"(acc[0]), "v"(tau));
-#ifdef PN_DIAG_BF_FAKESLOW
-    __builtin_amdgcn_s_sleep(PN_DIAG_BF_FAKESLOW);  // a rare path of 64 * N cycles that touches nothing
-#endif
-    return;
-#endif
     constexpr uint32_t CAP = 64u * M;
     BF_COUNT(0, 1);
 #ifdef PN_DIAG_BF_COUNT
@@ -1446,53 +1206,23 @@ __device__ __forceinline__ void bf_slow(const f32x16 &acc, float mn, float &tau,
     // branched per register -- sixteen vector-compare -> scalar-branch round trips, 1130 cycles per entry at ~0.4
     // entries per tile and wave; measured alternative to that: all compares first, then a scalar loop over the
     // registers with survivors and a switch to read them, 1320 cycles.)
-#ifndef PN_DIAG_BF_SLOW_LOOP
-    unsigned long long seen = 0ull, dup = 0ull;  // (seen: only the counting builds read it)
+    // The bounds are tagged here -- each register's number into the low four mantissa bits of a copy -- so that the
+    // minimum names its register, the sixteen values are distinct, and "some lane has two survivors" is "its second
+    // smallest passes": 16 + 21 instructions (bf_min2) instead of 16 compares + 47 scalar + 16 selects.  An entry is
+    // ~100 dependent instructions otherwise, and priced like a 950-cycle sleep (calibrated against timing-only builds
+    // whose entries sleep: 256 cycles +0.08 ms on C2, 512 cycles +0.24 ms, the real thing +0.52 ms).
+    f32x16 v;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) v[r] = __uint_as_float((__float_as_uint(acc[r]) & 0xFFFFFFF0u) | (uint32_t)r);
+    float sec;
+    bf_min2(v, mn, sec);
+    const unsigned long long dup = __ballot(sec < t);
+    // (a bound within 15 ulp of the threshold may pass or fail differently tagged: either is a valid filter --
+    // the thresholds reported to the proof are tagged values' thresholds minus the allowance, select.hip)
+    const uint32_t ridx = (mn < t) ? (__float_as_uint(mn) & 15u) : 16u;
+    const unsigned long long seen = __ballot(mn < t);  // (only the counting builds read it)
     (void)seen;
-    uint32_t ridx = 16u;
-    if (TAGGED) {
-        // The narrow kernel's main loop wrote every bound's register number into its low four mantissa bits while
-        // it took the minimum (in the matrix pipe's shadow, where vector instructions are nearly free): the minimum
-        // names its register, the sixteen values are distinct, and "some lane has two survivors" is "its second
-        // smallest passes" -- 21 instructions (bf_min2) instead of 16 compares + 47 scalar + 16 selects.  An entry is
-        // ~100 dependent instructions otherwise, and priced like a 950-cycle sleep (calibrated against timing-only
-        // builds whose entries sleep: 256 cycles +0.08 ms on C2, 512 cycles +0.24 ms, the real thing +0.52 ms).
-        float mn2, sec;
-        bf_min2(acc, mn2, sec);
-        dup = __ballot(sec < t);
-        ridx = (mn < t) ? (__float_as_uint(mn) & 15u) : 16u;
-        seen = __ballot(mn < t);
-        (void)mn2;
-    } else {
-#ifdef PN_DIAG_BF_SEARCH_MASKS  // the version before: sixteen compares, lane masks folded on the scalar unit, sixteen selects
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const bool p = acc[r] < t;
-            const unsigned long long m = __ballot(p);
-            dup |= seen & m;
-            seen |= m;
-            ridx = p ? (uint32_t)r : ridx;
-        }
-#else
-        // untagged bounds (64-slot buffers, the wide kernel): tag a copy here and proceed as above -- 16 + 21
-        // instructions instead of 79
-        f32x16 vloc;
-        f32x16 &v = INPLACE ? const_cast<f32x16 &>(acc) : vloc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) v[r] = __uint_as_float((__float_as_uint(acc[r]) & 0xFFFFFFF0u) | (uint32_t)r);
-        float sec;
-        bf_min2(v, mn, sec);
-        dup = __ballot(sec < t);
-        // (a bound within 15 ulp of the threshold may pass or fail differently tagged: either is a valid filter --
-        // the thresholds reported to the proof are tagged values' thresholds minus the allowance, select.hip)
-        ridx = (mn < t) ? (__float_as_uint(mn) & 15u) : 16u;
-        seen = __ballot(mn < t);
-#endif
-    }
     if (dup == 0ull) {
-#ifdef PN_DIAG_BF_NOAPPEND  // timing-only: the search, nothing else
-        asm volatile("" ::"v"(ridx));
-#else
         const bool p = ridx < 16u;
         const uint32_t pp = p ? 1u : 0u;
         const auto sw = __builtin_amdgcn_permlane32_swap(pp, pp, false, false);
@@ -1500,19 +1230,13 @@ __device__ __forceinline__ void bf_slow(const f32x16 &acc, float mn, float &tau,
         if (p) {
             const uint32_t o = cnt + (h ? other : 0u);  // half 0 writes first
             // C/D map of the 32x32 MFMA: row = (r & 3) + 8 (r >> 2) + 4 h
-#ifdef PN_DIAG_BF_NOSTORE  // timing-only: everything but the store instruction
-            asm volatile("" ::"v"(o), "v"(f2s(mn)), "v"(rowb + (ridx & 3u) + 8u * (ridx >> 2)));
-#else
             if (SH) sh_store_entry(ceq + o, f2s(mn), rowb + (ridx & 3u) + 8u * (ridx >> 2));
             else ceq[o] = make_uint2(f2s(mn), rowb + (ridx & 3u) + 8u * (ridx >> 2));
-#endif
         }
         BF_COUNT(1, __popcll(seen));
         cnt += pp + other;
         ns += 1;
-#endif
     } else
-#endif
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const float v = acc[r];
@@ -1575,61 +1299,6 @@ __device__ __forceinline__ void bf_slow(const f32x16 &acc, float mn, float &tau,
         if (tc_) BF_COUNT(4, t3_ - tc_);
     }
 #endif
-}
-
-// Survivors wait in registers: per lane and query block two pending (key, row) slots.  bf_capture is straight-line code
-// -- a compare, the row number from the minimum's tag, four selects -- so a check that finds a survivor costs what a
-// check that finds none costs, and the waves of a workgroup stay in step (with the append behind a branch, ~20 % of the
-// checks entered it, each entry delayed its wave by a few hundred cycles, and the tile barrier made the other three
-// waves wait for it: measured 0.66 of 2.8 ms on C2).  bf_flush appends the pending entries of one query block; the
-// caller runs it when some lane has both slots in use (every ~20 tiles) and at the end of the run.
-template <int M, bool RAD>
-__device__ __forceinline__ void bf_flush(BfPend &pd, float &tau, uint32_t &cnt, int h, int jq, int lane, uint32_t kp,
-                                         uint2 *ceq, uint2 *ce_blk, uint32_t &ns BF_DBG_ARG) {
-    constexpr uint32_t CAP = 64u * M;
-    BF_COUNT(0, 1);
-#pragma unroll
-    for (int sl = 0; sl < 2; ++sl) {
-        const bool p = pd.c > (uint32_t)sl;
-        if (__any(p)) {
-            const uint32_t pp = p ? 1u : 0u;
-            const auto sw = __builtin_amdgcn_permlane32_swap(pp, pp, false, false);
-            const uint32_t other = h ? sw[0] : sw[1];  // the other half's lane of the same query
-            const uint32_t o = cnt + (h ? other : 0u);  // half 0 writes first
-            // (o >= CAP only for a radius buffer that has already overflowed: count CAP + 1, nothing is kept)
-            if (p && o < CAP) ceq[o] = make_uint2(f2s(sl ? pd.v1 : pd.v0), sl ? pd.r1 : pd.r0);
-            BF_COUNT(1, __popcll(__ballot(p)));
-            cnt += pp + other;
-            ns += 1;
-        }
-    }
-    pd.c = 0u;
-    if (RAD) {
-        if (cnt > CAP - 32) {  // would need compacting: overflow, and nothing more is stored
-            cnt = CAP + 1;
-            tau = __uint_as_float(0xFF800000u);
-        }
-        return;
-    }
-    unsigned long long need = __ballot(h == 0 && cnt > CAP - 32);
-    if (need) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the entries must have left before they are read back
-        ns = 0;
-        do {
-            const int j = __builtin_ctzll(need);
-            need &= need - 1;
-            const uint32_t cj = (uint32_t)__builtin_amdgcn_readlane((int)cnt, j);
-            uint32_t T, nn;
-            BF_COUNT(2, 1);
-            bf_compact<M>(ce_blk + (size_t)j * CAP, cj, kp, lane, T, nn);
-            if (jq == j) {
-                tau = fminf(tau, s2f(T));  // never RAISED (a shared word may have lowered tau below entries stored earlier): what is
-                                           // reported must be <= every value rows were dropped against
-                cnt = nn;
-            }
-        } while (need);
-        ns += 16;  // at least: forces the plain wait at the next barrier
-    }
 }
 
 // Wait until this wave's LDS-DMA has landed WITHOUT waiting for the youngest candidate stores: vector-memory
@@ -1722,7 +1391,7 @@ __device__ __forceinline__ float bf_seed_lane(const float *__restrict__ lists, s
     for (int i = 1; i < kScoutList; ++i) r = (uint32_t)i + 1u == rank ? l[i] : r;
     return r;
 }
-template <int KS, int M, bool RAD, bool CI, int MODE, bool CAPT, bool SH = false>
+template <int KS, int M, bool RAD, bool CI, int MODE, bool SH = false>
 __global__ __launch_bounds__(256, 2) void bf16_filter_kernel(const char *__restrict__ img, uint32_t n_tiles,
                                                              const u32x4 *__restrict__ Bq, uint32_t q_tiles,
                                                              uint32_t kp_keep, uint2 *__restrict__ cand,
@@ -1732,12 +1401,11 @@ __global__ __launch_bounds__(256, 2) void bf16_filter_kernel(const char *__restr
                                                              uint32_t scout_max,
                                                              const uint32_t *tau_init,
                                                              float *__restrict__ scout_out, BfShared sh) {
-    static_assert(!SH || (MODE == 2 && !RAD && !CAPT), "shared thresholds: main pass of a k-NN call only");
+    static_assert(!SH || (MODE == 2 && !RAD), "shared thresholds: main pass of a k-NN call only");
     // k' in the low half; the high half: entries up to which a buffer ends its run uncut (0: k'; see the end of a run)
     const uint32_t kp = kp_keep & 0xFFFFu, keep_arg = kp_keep >> 16;
     constexpr int C = 2 * KS, CP = C + 1;
     constexpr uint32_t CAP = 64u * M;
-    constexpr bool TAG = M >= kBfTagFromM;
     constexpr int TB = kBP * CP * 16;  // bytes per tile image
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     char *tiles = reinterpret_cast<char *>(smem_raw);  // [NBUF][TB] (the scout pass uses two of them)
@@ -1747,13 +1415,7 @@ __global__ __launch_bounds__(256, 2) void bf16_filter_kernel(const char *__restr
     // Measured on one device, full s_barrier vs split: 1M x 128 k = 100 3.62 -> 3.46 ms per step; C2 (64-slot buffers,
     // shared thresholds) 2.29 vs 2.31-2.36: not there.  A fourth tile buffer (landing waited for 1.5 tiles after the
     // request instead of 0.5) made C2 4 % slower and changed nothing at k = 100: the wait is not LDS-DMA latency.
-#ifdef PN_DIAG_BF_FULLBARRIER
-    constexpr bool kSplit = false;
-#elif defined(PN_DIAG_BF_SPLITBARRIER)
-    constexpr bool kSplit = true;
-#else
     constexpr bool kSplit = M >= 2;
-#endif
     volatile uint32_t *arrive = reinterpret_cast<volatile uint32_t *>(tiles + NBUF * TB);
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1775,7 +1437,6 @@ __global__ __launch_bounds__(256, 2) void bf16_filter_kernel(const char *__restr
     const unsigned long long U = (unsigned long long)q_tiles * split * tps;
     const unsigned long long W = SH ? sh.n_main : gridDim.x;
     unsigned long long w = blockIdx.x;
-#ifndef PN_DIAG_BF_NOREMAP
     // Which slice a hardware block takes (aligned grids: c = W / q_tiles whole workgroups per query tile, slice
     // q c + p = row range p of query tile q).  Hardware block b runs on XCD b % 8 and every XCD has its own L2, so
     // the blocks of one XCD take a contiguous range of the RANGE-MAJOR order (p, q): the workgroups resident on an
@@ -1790,7 +1451,6 @@ __global__ __launch_bounds__(256, 2) void bf16_filter_kernel(const char *__restr
         const uint32_t c = (uint32_t)W / q_tiles;
         w = (unsigned long long)(L % q_tiles) * c + L / q_tiles;
     }
-#endif
     unsigned long long u0 = w * U / W;
     const unsigned long long u1 = (w + 1) * U / W;
 
@@ -1804,20 +1464,13 @@ __global__ __launch_bounds__(256, 2) void bf16_filter_kernel(const char *__restr
         // advances the global and the LDS address alike)
         const char *ws = src + wave * (P * 1024);
         char *wd = dst + wave * (P * 1024);
-#ifndef PN_DIAG_BF_NODMA  // NODMA is timing-only: tiles are never loaded
         static_assert(P <= 5, "piece schedule written out for up to five pieces per wave");
-#ifdef PN_DIAG_BF_HALFDMA  // TIMING ONLY (wrong results): half the LDS-DMA instructions -- what an 8-wave workgroup would issue per wave
-        if (0 < n_mine) __builtin_amdgcn_global_load_lds((glb_void_b *)ws, (lds_void_b *)wd, 16, 0, 0);
-        if (P > 2 && 2 < n_mine) __builtin_amdgcn_global_load_lds((glb_void_b *)ws, (lds_void_b *)wd, 16, 2048, 0);
-#else
         if (0 < n_mine) __builtin_amdgcn_global_load_lds((glb_void_b *)ws, (lds_void_b *)wd, 16, 0, 0);
         if (P > 1 && 1 < n_mine) __builtin_amdgcn_global_load_lds((glb_void_b *)ws, (lds_void_b *)wd, 16, 1024, 0);
         if (P > 2 && 2 < n_mine) __builtin_amdgcn_global_load_lds((glb_void_b *)ws, (lds_void_b *)wd, 16, 2048, 0);
         if (P > 3 && 3 < n_mine) __builtin_amdgcn_global_load_lds((glb_void_b *)ws, (lds_void_b *)wd, 16, 3072, 0);
         if (P > 4 && 4 < n_mine)
             __builtin_amdgcn_global_load_lds((glb_void_b *)(ws + 4096), (lds_void_b *)(wd + 4096), 16, 0, 0);
-#endif
-#endif
     };
 
     while (u0 < u1) {
@@ -1869,9 +1522,6 @@ __global__ __launch_bounds__(256, 2) void bf16_filter_kernel(const char *__restr
         // value is valid -- rows are only ever dropped against the threshold that is finally reported -- a
         // threshold that turns out too low merely sends the query to the next tier.
         const uint32_t run_len = rt1 - rt0;
-#ifdef PN_DIAG_BF_NOSCOUT
-        uint32_t t_scout = 0;
-#else
         uint32_t t_scout = run_len / 16u < 64u ? run_len / 16u : 64u;
         if (t_scout > scout_max) t_scout = scout_max;  // host: keeps the scouted rows' share of true neighbours tiny
         if (t_scout < 4u) t_scout = 0;
@@ -1893,7 +1543,6 @@ __global__ __launch_bounds__(256, 2) void bf16_filter_kernel(const char *__restr
                 tau1 = s2f(SH ? sh_load(tau_init + q0 + 32 + jq) : tau_init[q0 + 32 + jq]);
             }
         }
-#endif
         if (MODE == 1 || (MODE == 0 && scout_out)) {  // scout-only launch: every run contributes its lists
             t_scout = run_len < scout_max ? run_len : scout_max;
             if (t_scout < 1u) t_scout = 1u;
@@ -1936,14 +1585,10 @@ __global__ __launch_bounds__(256, 2) void bf16_filter_kernel(const char *__restr
                 }
                 if (rt + 1 < rt0 + t_scout) dma_tile(rt + 1, cs ^ 1);
                 float m0, m1;
-                unsigned long long du0, du1;
-                BfPend dp_{0.0f, 0.0f, 0u, 0u, 0u};
-                bf_chain<KS, CI, false>(arow0, pre0, b0, b1, c0, x00, x01, x10, x11, m0, m1, 0.0f, 0.0f, du0, du1, dp_, dp_,
-                                        0.0f, 0.0f, 0u);
+                bf_chain<KS, CI>(arow0, pre0, b0, b1, c0, x00, x01, x10, x11, m0, m1);
                 insert(s0, m0);
                 insert(s1, m1);
-                bf_chain<KS, CI, false>(arow1, pre1, b0, b1, c1, x10, x11, x00, x01, m0, m1, 0.0f, 0.0f, du0, du1, dp_, dp_,
-                                        0.0f, 0.0f, 0u);
+                bf_chain<KS, CI>(arow1, pre1, b0, b1, c1, x10, x11, x00, x01, m0, m1);
                 insert(s0, m0);
                 insert(s1, m1);
                 __syncthreads();
@@ -1991,15 +1636,13 @@ __global__ __launch_bounds__(256, 2) void bf16_filter_kernel(const char *__restr
         uint2 *ceq0 = ce_blk0 + (size_t)jq * CAP, *ceq1 = ce_blk1 + (size_t)jq * CAP;
         uint32_t ns = 0;
 
-        // Two ways to deal with the survivors of a (32-row block, query block) check, chosen by the host per plan:
-        //  * CAPT = false (small k': a check finds a survivor in ~20 % of the cases): a branch into bf_slow, which finds
-        //    the survivors' registers by compare and appends them at once;
-        //  * CAPT = true (larger k': survivors are frequent): branch-free capture into two pending register slots per
-        //    lane inside the next chain's shadow (bf_capture), appended in batches (bf_flush).  It costs ~80 vector
-        //    instructions more per chain whether anything survives or not -- measured on one device, 1M rows: k = 10
-        //    2.79 (branch) vs 3.14 ms (capture) at D = 128, 2.10 vs 2.24 at D = 64; k = 100 4.50 vs 4.20 at D = 128,
-        //    3.98 vs 3.18 at D = 64.
-        if (!CAPT) {
+        // The survivors of a (32-row block, query block) check: a branch into bf_slow, which finds the survivors' registers
+        // and appends them at once (a check finds a survivor in ~20 % of the cases at small k').  Measured alternative:
+        // branch-free capture into two pending register slots per lane inside the next chain's shadow, appended in
+        // batches -- ~80 vector instructions more per chain whether anything survives or not, ~25 registers over the
+        // budget of two workgroups per CU.  Measured on one device, 1M rows: k = 10 2.79 (branch) vs 3.14 ms (capture) at
+        // D = 128, 2.10 vs 2.24 at D = 64; k = 100 4.50 vs 4.20 at D = 128, 3.98 vs 3.18 at D = 64 -- but the spills cost
+        // more than that on the plans that scout for themselves (configs[2] at full size: 250 -> 335 ms): not used.
         // Software pipeline over the tiles of the run, three LDS buffers (tile rt in buffer (rt - rt0) % 3):
         //   chain A: block 0 of tile rt -> a0x, the VALU takes the minima of a1x (block 1 of tile rt-1) in its shadow;
         //            its last steps request block 1's first fragments and accumulator init
@@ -2056,15 +1699,13 @@ __global__ __launch_bounds__(256, 2) void bf16_filter_kernel(const char *__restr
             // rare-path entry that made the other three wait at every such barrier (a wave's time at the barrier was
             // 26 % of its run, most of it waiting for siblings' detours) -- no longer stops anybody.
             if (kSplit && rt > rt0) {
-#if !defined(PN_DIAG_BF_NOWAIT)
                 bf_wait_dma(ns);
-#endif
                 if (lane == 0) __hip_atomic_fetch_add(const_cast<uint32_t *>(arrive), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
 #if defined(PN_DIAG_BF_COUNT)
             unsigned long long tc0_ = bf_stamp_nw();
 #endif
-            bf_chain_p<KS, CI, CP, TAG>(arow0, pre, b0, b1, cc, a00, a01, a10, a11, m0, m1, arow1, tb, 1, h);
+            bf_chain_p<KS, CI, CP>(arow0, pre, b0, b1, cc, a00, a01, a10, a11, m0, m1, arow1, tb, 1, h);
 #if defined(PN_DIAG_BF_COUNT)
             {
                 unsigned long long tc1_ = bf_stamp_nw();
@@ -2076,29 +1717,23 @@ __global__ __launch_bounds__(256, 2) void bf16_filter_kernel(const char *__restr
             if (rt == rt0) { m0 = __uint_as_float(0x7F800000u); m1 = m0; }  // nothing precedes the first tile
             if (__any(m0 < tau0 || m1 < tau1)) {
                 const uint32_t row0 = (rt - 1) * kBP + 32;
-                if (__any(m0 < tau0)) bf_slow<M, RAD, TAG, SH>(a10, m0, tau0, cnt0, row0, h, jq, lane, kp, ceq0, ce_blk0, ns BF_DBG_PASS, pc_blk0, &sh_ncomp, sh.epoch);
-                if (__any(m1 < tau1)) bf_slow<M, RAD, TAG, SH>(a11, m1, tau1, cnt1, row0, h, jq, lane, kp, ceq1, ce_blk1, ns BF_DBG_PASS, pc_blk1, &sh_ncomp, sh.epoch);
+                if (__any(m0 < tau0)) bf_slow<M, RAD, SH>(a10, m0, tau0, cnt0, row0, h, jq, lane, kp, ceq0, ce_blk0, ns BF_DBG_PASS, pc_blk0, &sh_ncomp, sh.epoch);
+                if (__any(m1 < tau1)) bf_slow<M, RAD, SH>(a11, m1, tau1, cnt1, row0, h, jq, lane, kp, ceq1, ce_blk1, ns BF_DBG_PASS, pc_blk1, &sh_ncomp, sh.epoch);
             }
             // mid-tile barrier
 #if defined(PN_DIAG_BF_COUNT)
             const unsigned long long tb0_ = bf_stamp();
 #endif
             if (!kSplit) {  // everything at one s_barrier in the middle of the tile
-#if !defined(PN_DIAG_BF_NOWAIT)  // NOWAIT is timing-only: tiles may be read before they landed
                 if (sh_point) ns = 0;  // a publish point: every entry stored so far must have reached memory (vmcnt(0))
                 bf_wait_dma(ns);
-#endif
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#ifndef PN_DIAG_BF_NOBARRIER  // NOBARRIER is timing-only
                 __builtin_amdgcn_s_barrier();
-#endif
                 asm volatile("" ::: "memory");
             } else {
                 if (rt > rt0) {  // all four waves have arrived at tile rt (see the top of the loop)
                     const uint32_t want = 4u * (rt - rt0);
-#ifndef PN_DIAG_BF_NOBARRIER
                     while (*arrive < want) __builtin_amdgcn_s_sleep(1);
-#endif
                 }
                 asm volatile("" ::: "memory");
                 // a publish point: every entry stored so far must have reached memory before the counts that cover it
@@ -2135,7 +1770,7 @@ __global__ __launch_bounds__(256, 2) void bf16_filter_kernel(const char *__restr
 #if defined(PN_DIAG_BF_COUNT)
             unsigned long long tc2_ = bf_stamp_nw();
 #endif
-            bf_chain_p<KS, CI, CP, TAG>(arow1, pre, b0, b1, cc, a10, a11, a00, a01, p0, p1, ntb + (jq * CP + h) * 16, ntb, 0, h);
+            bf_chain_p<KS, CI, CP>(arow1, pre, b0, b1, cc, a10, a11, a00, a01, p0, p1, ntb + (jq * CP + h) * 16, ntb, 0, h);
 #if defined(PN_DIAG_BF_COUNT)
             {
                 unsigned long long tc3_ = bf_stamp_nw();
@@ -2146,8 +1781,8 @@ __global__ __launch_bounds__(256, 2) void bf16_filter_kernel(const char *__restr
 #endif
             if (__any(p0 < tau0 || p1 < tau1)) {
                 const uint32_t row0 = rt * kBP;
-                if (__any(p0 < tau0)) bf_slow<M, RAD, TAG, SH>(a00, p0, tau0, cnt0, row0, h, jq, lane, kp, ceq0, ce_blk0, ns BF_DBG_PASS, pc_blk0, &sh_ncomp, sh.epoch);
-                if (__any(p1 < tau1)) bf_slow<M, RAD, TAG, SH>(a01, p1, tau1, cnt1, row0, h, jq, lane, kp, ceq1, ce_blk1, ns BF_DBG_PASS, pc_blk1, &sh_ncomp, sh.epoch);
+                if (__any(p0 < tau0)) bf_slow<M, RAD, SH>(a00, p0, tau0, cnt0, row0, h, jq, lane, kp, ceq0, ce_blk0, ns BF_DBG_PASS, pc_blk0, &sh_ncomp, sh.epoch);
+                if (__any(p1 < tau1)) bf_slow<M, RAD, SH>(a01, p1, tau1, cnt1, row0, h, jq, lane, kp, ceq1, ce_blk1, ns BF_DBG_PASS, pc_blk1, &sh_ncomp, sh.epoch);
             }
             cur = nxt;
         }
@@ -2158,13 +1793,6 @@ __global__ __launch_bounds__(256, 2) void bf16_filter_kernel(const char *__restr
             }
         }
         {  // drain: block 1 of the last tile
-            if (TAG) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    a10[i] = __uint_as_float((__float_as_uint(a10[i]) & 0xFFFFFFF0u) | (uint32_t)i);
-                    a11[i] = __uint_as_float((__float_as_uint(a11[i]) & 0xFFFFFFF0u) | (uint32_t)i);
-                }
-            }
             float m0 = a10[0], m1 = a11[0];
 #pragma unroll
             for (int i = 1; i < 16; ++i) {
@@ -2172,142 +1800,14 @@ __global__ __launch_bounds__(256, 2) void bf16_filter_kernel(const char *__restr
                 m1 = fminf(m1, a11[i]);
             }
             const uint32_t row0 = (rt1 - 1) * kBP + 32;
-            if (__any(m0 < tau0)) bf_slow<M, RAD, TAG, SH>(a10, m0, tau0, cnt0, row0, h, jq, lane, kp, ceq0, ce_blk0, ns BF_DBG_PASS, pc_blk0, &sh_ncomp, sh.epoch);
-            if (__any(m1 < tau1)) bf_slow<M, RAD, TAG, SH>(a11, m1, tau1, cnt1, row0, h, jq, lane, kp, ceq1, ce_blk1, ns BF_DBG_PASS, pc_blk1, &sh_ncomp, sh.epoch);
+            if (__any(m0 < tau0)) bf_slow<M, RAD, SH>(a10, m0, tau0, cnt0, row0, h, jq, lane, kp, ceq0, ce_blk0, ns BF_DBG_PASS, pc_blk0, &sh_ncomp, sh.epoch);
+            if (__any(m1 < tau1)) bf_slow<M, RAD, SH>(a11, m1, tau1, cnt1, row0, h, jq, lane, kp, ceq1, ce_blk1, ns BF_DBG_PASS, pc_blk1, &sh_ncomp, sh.epoch);
             if (SH) {  // the run is over: its buffers are cut below and read "empty" to the refreshers from now on
                 if (h == 0) {
                     sh_store(pc_blk0 + jq, sh_tag(sh.epoch, sh_ncomp + 1u));
                     sh_store(pc_blk1 + jq, sh_tag(sh.epoch, sh_ncomp + 1u));
                 }
             }
-        }
-        } else {
-        // ---- prologue: first tile -> LDS[0]
-        __syncthreads();  // previous run's readers are done with both buffers
-        dma_tile(rt0, 0);
-        __syncthreads();  // carries the vmcnt(0)
-        // Pipeline per tile rt (two 32-row blocks, accumulators a0x / a1x for the two query blocks x):
-        //   [barrier passed: tile rt is in LDS]  first fragments of both blocks requested; DMA of tile rt+1
-        //   rare path for block 0 of tile rt-1 (minima taken during the previous chain)
-        //   chain(block 0) -> a0x while the VALU takes the minima of a1x (block 1 of tile rt-1); its rare path
-        //   chain(block 1) -> a1x while the VALU takes the minima of a0x; barrier
-        f32x16 a00, a01, a10, a11;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {  // "nothing here yet": above every threshold
-            a00[r] = 3.0e38f;
-            a01[r] = 3.0e38f;
-            a10[r] = 3.0e38f;
-            a11[r] = 3.0e38f;
-        }
-        float p0 = __uint_as_float(0x7F800000u), p1 = p0;  // (tagged) minima of a00 / a01 still to be filtered
-        unsigned long long dp0 = 0ull, dp1 = 0ull;         // lanes with more than one survivor in a00 / a01
-        BfPend pd0{0.0f, 0.0f, 0u, 0u, 0u}, pd1{0.0f, 0.0f, 0u, 0u, 0u};
-        // one (block, query block) result: the general path when some lane holds several survivors (rare), else the
-        // branch-free capture; then a flush when some lane has both pending slots in use
-#define PN_BF_DUPS(ACC0, ACC1, MN0, MN1, DUP0, DUP1, ROW0)                                                               \
-    do { /* some lane holds several survivors (rare): general path now, the capture in the next chain then skips it */  \
-        if ((DUP0) | (DUP1)) {                                                                                            \
-            if (DUP0) {                                                                                                   \
-                bf_slow<M, RAD>(ACC0, MN0, tau0, cnt0, (ROW0), h, jq, lane, kp, ceq0, ce_blk0, ns BF_DBG_PASS);               \
-                MN0 = __uint_as_float(0x7F800000u);                                                                       \
-            }                                                                                                             \
-            if (DUP1) {                                                                                                   \
-                bf_slow<M, RAD>(ACC1, MN1, tau1, cnt1, (ROW0), h, jq, lane, kp, ceq1, ce_blk1, ns BF_DBG_PASS);               \
-                MN1 = __uint_as_float(0x7F800000u);                                                                       \
-            }                                                                                                             \
-        }                                                                                                                 \
-    } while (0)
-#define PN_BF_FLUSH_IF_FULL()                                                                                             \
-    do {                                                                                                                  \
-        if (__any(pd0.c > 1u || pd1.c > 1u)) {                                                                            \
-            bf_flush<M, RAD>(pd0, tau0, cnt0, h, jq, lane, kp, ceq0, ce_blk0, ns BF_DBG_PASS);                            \
-            bf_flush<M, RAD>(pd1, tau1, cnt1, h, jq, lane, kp, ceq1, ce_blk1, ns BF_DBG_PASS);                            \
-        }                                                                                                                 \
-    } while (0)
-        int cur = 0;
-        for (uint32_t rt = rt0; rt < rt1; ++rt, cur ^= 1) {
-            const char *tb = tiles + cur * TB;
-            const char *arow0 = tb + (jq * CP + h) * 16;
-            const char *arow1 = arow0 + 32 * CP * 16;
-            bf16x8 pre0[kLA];
-#pragma unroll
-            for (int i = 0; i < kLA; ++i) pre0[i] = *reinterpret_cast<const bf16x8 *>(arow0 + 32 * (i < KS ? i : 0));
-            f32x16 c0 = a00;  // (placeholder unless CI)
-            if (CI) c0 = bf_cinit<CP>(tb, 0, h);
-            if (rt + 1 < rt1) dma_tile(rt + 1, cur ^ 1);
-            ns = 0;
-            // block 0 of tile rt-1 (scanned in the shadow of that tile's second chain): captured inside the first chain
-            PN_BF_DUPS(a00, a01, p0, p1, dp0, dp1, (rt - 1) * kBP);
-            PN_BF_FLUSH_IF_FULL();
-            float m0, m1;
-            unsigned long long dm0, dm1;
-            bf_chain<KS, CI, true>(arow0, pre0, b0, b1, c0, a00, a01, a10, a11, m0, m1, tau0, tau1, dm0, dm1, pd0, pd1, p0, p1,
-                                   (rt - 1) * kBP + 4u * (uint32_t)h);
-            if (rt == rt0) {  // nothing precedes the first tile
-                m0 = __uint_as_float(0x7F800000u);
-                m1 = m0;
-                dm0 = dm1 = 0ull;
-            }
-            // the second block's first fragments (and norms) are requested only now: their registers are not live
-            // across the first chain, and the filter step below covers the LDS latency
-            bf16x8 pre1[kLA];
-#pragma unroll
-            for (int i = 0; i < kLA; ++i) pre1[i] = *reinterpret_cast<const bf16x8 *>(arow1 + 32 * (i < KS ? i : 0));
-            f32x16 c1 = a10;  // (placeholder unless CI)
-            if (CI) c1 = bf_cinit<CP>(tb, 1, h);
-            // block 1 of tile rt-1 (scanned in the shadow of the chain just issued): captured inside the second chain
-            PN_BF_DUPS(a10, a11, m0, m1, dm0, dm1, (rt - 1) * kBP + 32);
-            PN_BF_FLUSH_IF_FULL();
-            bf_chain<KS, CI, true>(arow1, pre1, b0, b1, c1, a10, a11, a00, a01, p0, p1, tau0, tau1, dp0, dp1, pd0, pd1, m0, m1,
-                                   (rt - 1) * kBP + 32u + 4u * (uint32_t)h);
-            // tile barrier: every wave's share of tile rt+1 has landed and nobody still reads tile rt
-#if defined(PN_DIAG_BF_COUNT)
-            const unsigned long long tb0_ = bf_stamp();
-#endif
-#if !defined(PN_DIAG_BF_NOWAIT)  // NOWAIT is timing-only: tiles may be read before they landed
-            bf_wait_dma(ns);
-#endif
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#ifndef PN_DIAG_BF_NOBARRIER  // NOBARRIER is timing-only
-            __builtin_amdgcn_s_barrier();
-#endif
-            asm volatile("" ::: "memory");
-#if defined(PN_DIAG_BF_COUNT)
-            BF_COUNT(6, bf_stamp() - tb0_);
-#endif
-        }
-        {  // drain: both blocks of the last tile, then whatever is still pending
-            unsigned long long dm0 = 0ull, dm1 = 0ull, sn0 = 0ull, sn1 = 0ull;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                a10[i] = __uint_as_float((__float_as_uint(a10[i]) & 0xFFFFFFF0u) | (uint32_t)i);
-                a11[i] = __uint_as_float((__float_as_uint(a11[i]) & 0xFFFFFFF0u) | (uint32_t)i);
-                const unsigned long long k0 = __ballot(a10[i] < tau0), k1 = __ballot(a11[i] < tau1);
-                dm0 |= sn0 & k0;
-                sn0 |= k0;
-                dm1 |= sn1 & k1;
-                sn1 |= k1;
-            }
-            float m0 = a10[0], m1 = a11[0];
-#pragma unroll
-            for (int i = 1; i < 16; ++i) {
-                m0 = fminf(m0, a10[i]);
-                m1 = fminf(m1, a11[i]);
-            }
-            PN_BF_DUPS(a00, a01, p0, p1, dp0, dp1, (rt1 - 1) * kBP);
-            PN_BF_FLUSH_IF_FULL();
-            bf_capture(pd0, p0, tau0, (rt1 - 1) * kBP + 4u * (uint32_t)h);
-            bf_capture(pd1, p1, tau1, (rt1 - 1) * kBP + 4u * (uint32_t)h);
-            // (a threshold lowered meanwhile only makes dm0 / dm1 conservative)
-            PN_BF_DUPS(a10, a11, m0, m1, dm0, dm1, (rt1 - 1) * kBP + 32);
-            PN_BF_FLUSH_IF_FULL();
-            bf_capture(pd0, m0, tau0, (rt1 - 1) * kBP + 32u + 4u * (uint32_t)h);
-            bf_capture(pd1, m1, tau1, (rt1 - 1) * kBP + 32u + 4u * (uint32_t)h);
-            bf_flush<M, RAD>(pd0, tau0, cnt0, h, jq, lane, kp, ceq0, ce_blk0, ns BF_DBG_PASS);
-            bf_flush<M, RAD>(pd1, tau1, cnt1, h, jq, lane, kp, ceq1, ce_blk1, ns BF_DBG_PASS);
-        }
-#undef PN_BF_DUPS
-#undef PN_BF_FLUSH_IF_FULL
         }
         // ---- end of run: at most kp candidates per query stay; publish count and threshold
         {
@@ -2319,23 +1819,18 @@ __global__ __launch_bounds__(256, 2) void bf16_filter_kernel(const char *__restr
             // buffer over as it is is always valid (the proof only gets a looser threshold); what it costs is re-rank
             // LDS, which is sized for what a cell can hold.  Measured (round 3, one device, a 125 k-row shard of C2 /
             // C2): every buffer cut to k' = 13: kernel 0.530 / 2.34 ms, step 0.644 / 2.48; none cut
-            // (-DPN_DIAG_BF_FINALCOMPACT_FROM=2; cells of up to 64 entries): kernel 0.467 / 2.34, step 0.659 / 2.50 --
+            // (cells of up to 64 entries): kernel 0.467 / 2.34, step 0.659 / 2.50 --
             // the serial tail of up to 128 compactions per wave (16 % of a shard's run) is gone but the re-rank's waves
             // per CU halve with 9 KB of LDS each.  So the host names the count up to which a buffer stays uncut
             // (bf16_cell_max: 32 of 64 slots while the re-rank's LDS stays near 5 KB; a buffer holds 18 entries on
             // average at the end of a run): DESIGN.md 4.0.
-#ifdef PN_DIAG_BF_FINALCOMPACT_FROM
-            constexpr bool kFinalCompact = M >= (PN_DIAG_BF_FINALCOMPACT_FROM);
-#else
-            constexpr bool kFinalCompact = true;
-#endif
             const uint32_t kfin = keep_arg > kp ? keep_arg : kp;
             // 64-slot buffers four at a time: their entries are requested together, then selected one after the other
             // (a buffer at a time pays a memory round trip per buffer: up to 128 in a row at the end of every run;
             // larger buffers stay one at a time -- four of them in registers made the kernel spill)
             constexpr int NB = M == 1 ? 4 : 1;
             auto final_compact = [&](uint2 *ce_blk, float &tau, uint32_t &cnt) {
-                unsigned long long need = RAD || !kFinalCompact ? 0ull : __ballot(h == 0 && cnt > kfin);
+                unsigned long long need = RAD ? 0ull : __ballot(h == 0 && cnt > kfin);
                 while (need) {
                     int jj[NB];
                     uint32_t cj[NB], key[NB][M], ixs[NB][M];
@@ -2358,10 +1853,6 @@ __global__ __launch_bounds__(256, 2) void bf16_filter_kernel(const char *__restr
             };
             final_compact(ce_blk0, tau0, cnt0);
             final_compact(ce_blk1, tau1, cnt1);
-#if defined(PN_DIAG_BF_NOSTORE) || defined(PN_DIAG_BF_NOSLOW)
-            cnt0 = 0;  // timing-only builds: the buffers hold no valid rows
-            cnt1 = 0;
-#endif
             if (h == 0) {
                 ccnt[cell0 + jq] = cnt0;
                 ctau[cell0 + jq] = f2s(tau0);
@@ -2406,9 +1897,9 @@ __global__ __launch_bounds__(256, 2) void bf16_filter_kernel(const char *__restr
 // Main pass only (thresholds given: MODE 2 of bf16_filter_kernel), 64- and 128-slot buffers, k-NN; the scout launch,
 // radius queries and 256-slot buffers keep the 4-wave kernel.
 // ---------------------------------------------------------------------------
-#ifndef PN_BF8_LA
-#define PN_BF8_LA 3
-#endif
+// One chain of the 8-wave kernel: KS MFMAs of one 32-row block against the wave's query block while the VALU takes the
+// minimum of the other block's bounds (r).  This variant starts from registers -- its first fragments `pre` and its
+// accumulator init `c` were requested during the PREVIOUS chain, as in bf_chain_p.
 template <int KS, bool CI, int CP, int LA>
 __device__ __forceinline__ void bf_chain1(const char *arow, bf16x8 (&pre)[LA], const bf16x8 (&b)[KS], f32x16 &c,
                                           f32x16 &w, f32x16 &r, float &m, const char *narow, const char *ntb, int nblk,
@@ -2453,7 +1944,7 @@ __device__ __forceinline__ void bf_chain1(const char *arow, bf16x8 (&pre)[LA], c
 
 // The same chain starting COLD: its first fragments and its accumulator init are requested at its head.  With four
 // waves per SIMD the other waves' chains cover that LDS round trip, and nothing of the NEXT chain is held across the
-// survivor check and the barrier: 24 registers less than bf_chain1 (PN_BF8_PREFETCH picks the variant; measured A/B).
+// survivor check and the barrier: 24 registers less than bf_chain1 (kBf8Prefetch picks the variant; measured A/B).
 template <int KS, bool CI, int CP, int LA>
 __device__ __forceinline__ void bf_chain1c(const char *arow, const char *tb, int blk, int h, const bf16x8 (&b)[KS], f32x16 &w,
                                            f32x16 &r, float &m) {
@@ -2461,13 +1952,8 @@ __device__ __forceinline__ void bf_chain1c(const char *arow, const char *tb, int
 #pragma unroll
     for (int i = 0; i < LA && i < KS; ++i) f[i] = *reinterpret_cast<const bf16x8 *>(arow + 32 * i);
     f32x16 c;
-#ifdef PN_DIAG_BF8_NOCINIT  // TIMING ONLY (wrong results): no row-norm reads -- how much of the kernel is LDS bandwidth
-    if (false) {
-    } else {
-#else
     if (CI) c = bf_cinit<CP>(tb, blk, h);
     else {
-#endif
 #pragma unroll
         for (int i = 0; i < 16; ++i) c[i] = 0.0f;
     }
@@ -2482,9 +1968,7 @@ __device__ __forceinline__ void bf_chain1c(const char *arow, const char *tb, int
     }
 }
 
-#ifndef PN_BF8_PREFETCH
-#define PN_BF8_PREFETCH 0
-#endif
+constexpr bool kBf8Prefetch = false;  // bf_chain1 (true) or bf_chain1c (false)
 template <int KS, bool CI, bool SH, int M = 1>
 __global__ __launch_bounds__(512, 4) void bf16_filter8_kernel(const char *__restrict__ img, uint32_t n_tiles,
                                                               const u32x4 *__restrict__ Bq, uint32_t q_tiles,
@@ -2496,13 +1980,9 @@ __global__ __launch_bounds__(512, 4) void bf16_filter8_kernel(const char *__rest
     constexpr uint32_t CAP = 64u * M;
     constexpr int TB = kBP * CP * 16;  // bytes per tile image
     constexpr int NBUF = 3, NW = 8;
-    constexpr int LA = PN_BF8_LA;  // fragment lookahead (the 4-wave kernel: kLA = 3)
-    constexpr bool PREF = PN_BF8_PREFETCH != 0;  // chains start from registers requested during the previous chain
-#ifdef PN_BF8_SPLITBARRIER  // arrive at the top of a tile, wait for the count in mid-tile (bf16_filter_kernel, kSplit)
-    constexpr bool kSplit8 = true;
-#else
-    constexpr bool kSplit8 = false;
-#endif
+    constexpr int LA = 3;  // fragment lookahead (the 4-wave kernel: kLA = 3)
+    constexpr bool PREF = kBf8Prefetch;  // chains start from registers requested during the previous chain
+    constexpr bool kSplit8 = false;  // arrive at the top of a tile, wait for the count in mid-tile (bf16_filter_kernel, kSplit)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     char *tiles = reinterpret_cast<char *>(smem_raw);  // [NBUF][TB]
     volatile uint32_t *arrive = reinterpret_cast<volatile uint32_t *>(tiles + NBUF * TB);  // split barrier's arrival counter
@@ -2612,8 +2092,8 @@ __global__ __launch_bounds__(512, 4) void bf16_filter8_kernel(const char *__rest
             else bf_chain1c<KS, CI, CP, LA>(arow0, tb, 0, h, b, a0, a1, m);
             if (rt == rt0) m = __uint_as_float(0x7F800000u);  // nothing precedes the first tile
             if (__any(m < tau))
-                bf_slow<M, false, false, SH>(a1, m, tau, cnt, (rt - 1) * kBP + 32, h, jq, lane, kp, ceq, ce_blk, ns BF_DBG_PASS,
-                                             pc_blk, &sh_ncomp, sh.epoch);
+                bf_slow<M, false, SH>(a1, m, tau, cnt, (rt - 1) * kBP + 32, h, jq, lane, kp, ceq, ce_blk, ns BF_DBG_PASS,
+                                      pc_blk, &sh_ncomp, sh.epoch);
             // mid-tile barrier: every wave's pieces of tile rt + 1 have landed, nobody reads tile rt - 1 any more
             if (!kSplit8) {
                 if (sh_point) ns = 0;  // a publish point: every entry stored so far must have reached memory (vmcnt(0))
@@ -2652,8 +2132,8 @@ __global__ __launch_bounds__(512, 4) void bf16_filter8_kernel(const char *__rest
             if (PREF) bf_chain1<KS, CI, CP, LA>(arow1, pre, b, cc, a1, a0, p, ntb + (jq * CP + h) * 16, ntb, 0, h);
             else bf_chain1c<KS, CI, CP, LA>(arow1, tb, 1, h, b, a1, a0, p);
             if (__any(p < tau))
-                bf_slow<M, false, false, SH>(a0, p, tau, cnt, rt * kBP, h, jq, lane, kp, ceq, ce_blk, ns BF_DBG_PASS, pc_blk,
-                                             &sh_ncomp, sh.epoch);
+                bf_slow<M, false, SH>(a0, p, tau, cnt, rt * kBP, h, jq, lane, kp, ceq, ce_blk, ns BF_DBG_PASS, pc_blk,
+                                      &sh_ncomp, sh.epoch);
             cur = nxt;
         }
         if (SH) {
@@ -2664,8 +2144,8 @@ __global__ __launch_bounds__(512, 4) void bf16_filter8_kernel(const char *__rest
 #pragma unroll
             for (int i = 1; i < 16; ++i) m = fminf(m, a1[i]);
             if (__any(m < tau))
-                bf_slow<M, false, false, SH>(a1, m, tau, cnt, (rt1 - 1) * kBP + 32, h, jq, lane, kp, ceq, ce_blk, ns BF_DBG_PASS,
-                                             pc_blk, &sh_ncomp, sh.epoch);
+                bf_slow<M, false, SH>(a1, m, tau, cnt, (rt1 - 1) * kBP + 32, h, jq, lane, kp, ceq, ce_blk, ns BF_DBG_PASS,
+                                      pc_blk, &sh_ncomp, sh.epoch);
             if (SH) {  // the run is over: its buffers may be cut below and read "empty" to the refreshers from now on
                 if (h == 0) sh_store(pc_blk + jq, sh_tag(sh.epoch, sh_ncomp + 1u));
             }
@@ -2748,12 +2228,10 @@ __global__ __launch_bounds__(512, 1) void bf16_wide_kernel(const char *__restric
     // workgroups of different query tiles that walk the same rows share each corpus tile.
     uint32_t w = blockIdx.x;
     const uint32_t W = gridDim.x;
-#ifndef PN_DIAG_BF_WIDE_NOREMAP
     {   // XCD x runs the blocks b = x, x + 8, ...: it gets the logical range that starts where XCD x - 1's ends
         const uint32_t x = blockIdx.x & 7u, base = W >> 3, rem = W & 7u;  // XCDs 0 .. rem-1 run base + 1 blocks
         w = x * base + (x < rem ? x : rem) + (blockIdx.x >> 3);
     }
-#endif
     // Balanced persistent partition (as bf16_filter_kernel): the work is the list of (query tile, row tile) units in
     // query-major order, workgroup w owns the contiguous slice [w U / W, (w+1) U / W) and walks it in runs that stay
     // inside one query tile.  Segment of a run = ordinal of the workgroup among those touching that query tile.
@@ -2858,18 +2336,11 @@ __global__ __launch_bounds__(512, 1) void bf16_wide_kernel(const char *__restric
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 bf16x8 na[4], nb[2];
-#ifndef PN_DIAG_BF_WIDE_NOAHEAD
-                constexpr bool kAhead = true;
-#else
-                constexpr bool kAhead = false;
-#endif
                 if (s < 3) {
-                    if (kAhead) {
 #pragma unroll
-                        for (int qb = 0; qb < 2; ++qb)
-                            nb[qb] = *reinterpret_cast<const bf16x8 *>(B + qb * 32 * kWPitch + slot_off[s < 3 ? s + 1 : s]);
-                        na[3] = *reinterpret_cast<const bf16x8 *>(A + 3 * 32 * kWPitch + slot_off[s < 3 ? s + 1 : s]);
-                    }
+                    for (int qb = 0; qb < 2; ++qb)
+                        nb[qb] = *reinterpret_cast<const bf16x8 *>(B + qb * 32 * kWPitch + slot_off[s < 3 ? s + 1 : s]);
+                    na[3] = *reinterpret_cast<const bf16x8 *>(A + 3 * 32 * kWPitch + slot_off[s < 3 ? s + 1 : s]);
                 }
 #pragma unroll
                 for (int rb = 0; rb < 4; ++rb) {
@@ -2880,38 +2351,24 @@ __global__ __launch_bounds__(512, 1) void bf16_wide_kernel(const char *__restric
                         const int piece = m / 3;
                         if (m == 26) {  // ninth piece: the extras of the next row tile travel with its chunk 0
                             __builtin_amdgcn_sched_barrier(0);
-#ifndef PN_DIAG_BF_NODMA
                             if (has_x && c + 1 == nkc && rt + 1 < rt_end) issue_x(rt + 1);
-#endif
                             __builtin_amdgcn_sched_barrier(0);
                         }
                         if (m % 3 == 2 && piece < kWDma) {
                             __builtin_amdgcn_sched_barrier(0);
-#ifndef PN_DIAG_BF_NODMA  // NODMA is timing-only: the tiles are never loaded
                             if (more)
-#else
-                            if (false)
-#endif
                                 __builtin_amdgcn_global_load_lds((glb_void_b *)(nsrc + piece * 1024),
                                                                  (lds_void_b *)(ndst + piece * 1024), 16, 0, 0);
                             __builtin_amdgcn_sched_barrier(0);
                         }
                     }
-                    if (kAhead && s < 3 && rb < 3) {  // a[rb] is dead: the next step's fragment may land in its registers
+                    if (s < 3 && rb < 3) {  // a[rb] is dead: the next step's fragment may land in its registers
                         __builtin_amdgcn_sched_barrier(0);
                         na[rb] = *reinterpret_cast<const bf16x8 *>(A + rb * 32 * kWPitch + slot_off[s < 3 ? s + 1 : s]);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
                 if (s < 3) {
-                    if (!kAhead) {
-#pragma unroll
-                        for (int rb = 0; rb < 4; ++rb)
-                            na[rb] = *reinterpret_cast<const bf16x8 *>(A + rb * 32 * kWPitch + slot_off[s < 3 ? s + 1 : s]);
-#pragma unroll
-                        for (int qb = 0; qb < 2; ++qb)
-                            nb[qb] = *reinterpret_cast<const bf16x8 *>(B + qb * 32 * kWPitch + slot_off[s < 3 ? s + 1 : s]);
-                    }
 #pragma unroll
                     for (int rb = 0; rb < 4; ++rb) a[rb] = na[rb];
                     b[0] = nb[0];
@@ -2935,9 +2392,6 @@ __global__ __launch_bounds__(512, 1) void bf16_wide_kernel(const char *__restric
     // the 5th smallest block minimum of the wave's rows
     const uint32_t run_len = rt1 - rt0;
     uint32_t t_scout = run_len / 32u < scout_max ? run_len / 32u : scout_max;
-#ifdef PN_DIAG_BF_NOSCOUT
-    t_scout = 0;
-#endif
     if (tau_init) {  // thresholds given by the caller (radius: each query's fixed bound; k-NN: the shared seed)
         t_scout = 0;
         tau0 = s2f(tau_init[q0 + jq]);
@@ -3016,14 +2470,10 @@ __global__ __launch_bounds__(512, 1) void bf16_wide_kernel(const char *__restric
                 m1 = fminf(m1, acc[rb][1][i]);
             }
             const uint32_t row0 = rt * (uint32_t)kWR + (uint32_t)(rh * 128 + rb * 32);
-#ifdef PN_DIAG_BF_WIDE_NOSLOW  // TIMING / TRAFFIC ONLY (wrong results): no survivor handling -- co-walking workgroups do not drift
-            asm volatile("" ::"v"(m0), "v"(m1), "v"(row0));
-#else
             if (__any(m0 < tau0))
                 bf_slow<M, RAD>(acc[rb][0], m0, tau0, cnt0, row0, h, jq, lane, kp, ceq0, ce_blk0, ns BF_DBG_PASS);
             if (__any(m1 < tau1))
                 bf_slow<M, RAD>(acc[rb][1], m1, tau1, cnt1, row0, h, jq, lane, kp, ceq1, ce_blk1, ns BF_DBG_PASS);
-#endif
         }
     }
     // ---- end of run: at most kp candidates per query stay; publish count and threshold
@@ -3046,10 +2496,6 @@ __global__ __launch_bounds__(512, 1) void bf16_wide_kernel(const char *__restric
         bf_compact<M>(ce_blk1 + (size_t)j * CAP, cj, kp, lane, T, nn);
         if (jq == j) { tau1 = fminf(tau1, s2f(T)); cnt1 = nn; }
     }
-#if defined(PN_DIAG_BF_NOSTORE) || defined(PN_DIAG_BF_NOSLOW)
-    cnt0 = 0;
-    cnt1 = 0;
-#endif
     if (h == 0) {
         ccnt[cell0 + jq] = cnt0;
         ctau[cell0 + jq] = f2s(tau0);
@@ -3171,25 +2617,16 @@ size_t bf16_query_bytes(size_t nq_pad, int dim, bool ci) {
         return (nq_pad + kWR - 1) / kWR * bf16_wide_tile_bytes(dim);
     return nq_pad * (size_t)bf16_ks_for(dim, ci) * 32;
 }
-#ifdef PN_DIAG_BF_CAP
-int bf16_cap_for(int kp) { return kp + 32 <= PN_DIAG_BF_CAP ? PN_DIAG_BF_CAP : 256; }
-#else
 // a buffer is compacted once fewer than 32 free slots remain; a compaction is also what refreshes the threshold,
 // so small k' take the small buffer (measured: k' = 12, 64 slots 4.7 ms vs 128 slots 5.2 ms on the headline config)
 int bf16_cap_for(int kp) { return kp <= 16 ? 64 : kp <= 64 ? 128 : 256; }
-#endif
 int bf16_query_tile() { return kBQ; }
 // entries a (segment, query) cell holds at most when a k-NN launch has finished: every run ends with a cut to k'
 int bf16_cell_max(int kp, int cap, int nseg, bool wide) {
-#ifdef PN_DIAG_BF_FINALCOMPACT_FROM
-    return cap;
-#else
     const int cut = kp < cap ? kp : cap;
-#ifdef PN_DIAG_BF_FINALKEEP128  // experiment: 128-slot buffers end their runs uncut up to this many entries.  Measured at
-    // 1M x 128, k = 100 (k' = 42, 65 entries per buffer at the end of a run, the cut 4.9 % of a wave's run): kernel 2.86
-    // -> 2.81 / 2.75 ms at 64 / 96 entries, step 3.29 -> 3.35 / 3.54 -- the re-rank's LDS and gather lose more: not used.
-    if (!wide && cap == 128 && nseg >= 1) return (PN_DIAG_BF_FINALKEEP128) > cut ? (PN_DIAG_BF_FINALKEEP128) : cut;
-#endif
+    // (128-slot buffers ending their runs uncut as well: measured at 1M x 128, k = 100 (k' = 42, 65 entries per buffer at
+    // the end of a run, the cut 4.9 % of a wave's run): kernel 2.86 -> 2.81 / 2.75 ms at 64 / 96 entries, step 3.29 ->
+    // 3.35 / 3.54 -- the re-rank's LDS and gather lose more: not used.)
     if (wide || cap != 64 || nseg < 1) return cut;
     // 64-slot buffers of the narrow kernel end a run uncut up to `keep` entries (CandBuf::final_keep; the kernel's end of
     // run has the measurements): as many as keep the re-rank's LDS -- 12 bytes per slot a query's cells can hold -- near
@@ -3197,7 +2634,6 @@ int bf16_cell_max(int kp, int cap, int nseg, bool wide) {
     int keep = 384 / nseg;
     if (keep > kBfFinalKeep) keep = kBfFinalKeep;
     return keep > cut ? keep : cut;
-#endif
 }
 
 // per-dimension sums of the corpus in f64 (any translation vector is valid; the mean minimises the norms);
@@ -3256,7 +2692,6 @@ hipError_t launch_bf16_decide_mu(const double *sums, size_t n, int dim, bool nev
 template <typename T>
 hipError_t launch_bf16_row_stats(const T *P, const float *mu, size_t n, int dim, size_t ld, double *out4,
                                  hipStream_t s) {
-#ifndef PN_DIAG_BF_PACK1
     if (!bf16_is_wide(dim)) {  // (row statistics decide about the CI layout: its step count bounds the columns a lane owns)
         const size_t rows = (n + 31) / 32 * 32;  // whole blocks of 256 threads = 32 rows
         const size_t blocks = rows * 8 / 256;
@@ -3264,7 +2699,6 @@ hipError_t launch_bf16_row_stats(const T *P, const float *mu, size_t n, int dim,
                            n, dim, ld, bf16_ks_for(dim, false), rows, out4);
         return hipGetLastError();
     }
-#endif
     hipLaunchKernelGGL(bf16_row_stats_kernel<T>, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, s, P, mu, n, dim, ld, out4);
     return hipGetLastError();
 }
@@ -3277,32 +2711,20 @@ hipError_t launch_bf16_pack_corpus(const T *P, const float *mu, size_t n, int di
     const bool wide = bf16_is_wide(dim);
     if (wide && ci) return hipErrorInvalidValue;
     const size_t rows = wide ? (n + kWR - 1) / kWR * kWR : (n + kBP - 1) / kBP * kBP;
-#ifndef PN_DIAG_BF_PACK1
     if (wide) {  // rows is a multiple of 256
         hipLaunchKernelGGL((bf16_pack_wide8_kernel<T, false>), dim3((unsigned)(rows * 8 / 256)), dim3(256), 0, s, P, mu, n, rows,
                            dim, ld, static_cast<uint16_t *>(img), (double *)nullptr, (uint32_t *)nullptr, bad, Bf16SeedModel{});
         return hipGetLastError();
     }
-    if (!wide) {  // rows is a multiple of 64: whole blocks of 256 threads = 32 rows
-        hipLaunchKernelGGL(bf16_pack_corpus8_kernel<T>, dim3((unsigned)(rows * 8 / 256)), dim3(256), 0, s, P, mu, n, dim, ld,
-                           bf16_ks_for(dim, ci), static_cast<uint16_t *>(img), rows, bad, ci ? 1 : 0);
-        return hipGetLastError();
-    }
-#endif
-    hipLaunchKernelGGL(bf16_pack_corpus_kernel<T>, dim3((unsigned)((rows + 127) / 128)), dim3(128), 0, s, P, mu, n, dim, ld,
-                       bf16_ks_for(dim, ci), static_cast<uint16_t *>(img), rows, bad, wide ? 1 : 0, ci ? 1 : 0);
+    // narrow rows: rows is a multiple of 64 -- whole blocks of 256 threads = 32 rows
+    hipLaunchKernelGGL(bf16_pack_corpus8_kernel<T>, dim3((unsigned)(rows * 8 / 256)), dim3(256), 0, s, P, mu, n, dim, ld,
+                       bf16_ks_for(dim, ci), static_cast<uint16_t *>(img), rows, bad, ci ? 1 : 0);
     return hipGetLastError();
 }
 template hipError_t launch_bf16_pack_corpus<float>(const float *, const float *, size_t, int, size_t, void *, uint32_t *, bool, hipStream_t);
 template hipError_t launch_bf16_pack_corpus<double>(const double *, const float *, size_t, int, size_t, void *, uint32_t *, bool, hipStream_t);
 
-bool bf16_pack_fused_supported(int dim) {
-#ifdef PN_DIAG_BF_PACKQ1
-    return false;
-#else
-    return !bf16_is_wide(dim);
-#endif
-}
+bool bf16_pack_fused_supported(int dim) { return !bf16_is_wide(dim); }
 template <typename T>
 hipError_t launch_bf16_pack_queries(const T *Q, const float *mu, size_t nq, size_t nq_pad, int dim, size_t ld,
                                     void *B, double *qn, uint32_t *qbad, bool ci, double bmax, double dmax,
@@ -3311,25 +2733,16 @@ hipError_t launch_bf16_pack_queries(const T *Q, const float *mu, size_t nq, size
     Bf16SeedModel sm{};
     if (smp) sm = *smp;
     if (sm.seed_out && (!sm.m1 || !sm.a || !sm.b)) return hipErrorInvalidValue;
-#ifndef PN_DIAG_BF_PACKQ1
     if (!bf16_is_wide(dim)) {  // nq_pad is a multiple of 256: whole blocks
         hipLaunchKernelGGL(bf16_pack_queries8_kernel<T>, dim3((unsigned)(nq_pad * 8 / 256)), dim3(256), 0, s, Q, mu, nq,
                            nq_pad, dim, ld, bf16_ks_for(dim, ci), static_cast<uint16_t *>(B), qn, qbad, ci ? 1 : 0,
                            bmax, dmax, Qp, ldq, misc, sm);
         return hipGetLastError();
     }
-#endif
-#ifndef PN_DIAG_BF_PACK1
-    if (bf16_is_wide(dim) && !ci && nq_pad % 32 == 0) {  // (nq_pad is a multiple of 256 for wide rows)
-        hipLaunchKernelGGL((bf16_pack_wide8_kernel<T, true>), dim3((unsigned)(nq_pad * 8 / 256)), dim3(256), 0, s, Q, mu, nq, nq_pad,
-                           dim, ld, static_cast<uint16_t *>(B), qn, qbad, (uint32_t *)nullptr, sm);
-        return hipGetLastError();
-    }
-#endif
-    if (sm.seed_out) return hipErrorInvalidValue;  // (model seeds come from the eight-lanes-per-query kernels only)
-    hipLaunchKernelGGL(bf16_pack_queries_kernel<T>, dim3((unsigned)((nq_pad + 127) / 128)), dim3(128), 0, s, Q, mu, nq, nq_pad,
-                       dim, ld, bf16_ks_for(dim, ci), static_cast<uint16_t *>(B), qn, qbad, bf16_is_wide(dim) ? 1 : 0,
-                       ci ? 1 : 0, bmax, dmax);
+    // wide rows: no CI layout, and whole blocks of 32 queries (every caller pads nq_pad to a multiple of 256)
+    if (ci || nq_pad % 32 != 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((bf16_pack_wide8_kernel<T, true>), dim3((unsigned)(nq_pad * 8 / 256)), dim3(256), 0, s, Q, mu, nq, nq_pad,
+                       dim, ld, static_cast<uint16_t *>(B), qn, qbad, (uint32_t *)nullptr, sm);
     return hipGetLastError();
 }
 // Per-dimension power sums of the corpus translated by mu: out[j * dim + k] = sum over rows of (p_k - mu_k)^(j + 1),
@@ -3372,27 +2785,10 @@ template hipError_t launch_bf16_pack_queries<double>(const double *, const float
                                                      uint32_t *, bool, double, double, hipStream_t, double *, size_t, uint32_t *,
                                                      const Bf16SeedModel *);
 
-// The branch-free capture path (CAPT, see the kernel) is measured, parity-tested and NOT used by default: it wins where
-// survivors are frequent and the kernel is launched with thresholds (1M x 128, k = 100: 4.50 -> 4.20 ms) but needs ~25
-// registers more than the 256 a wave has at two workgroups per CU, and the spills cost more than it saves on the plans
-// that scout for themselves (configs[2] at full size: 250 -> 335 ms).  -DPN_DIAG_BF_CAPT turns it on for k' > 16.
-#ifdef PN_DIAG_BF_CAPT
-constexpr bool kBfCapture = true;
-#else
-constexpr bool kBfCapture = false;
-#endif
-#ifdef PN_DIAG_BF_NO8  // diagnostic builds of the 4-wave kernel's experiments
-constexpr bool kBf8Enabled = false;
-#else
-constexpr bool kBf8Enabled = true;
-#endif
 // (450 until the end of round 4; with thresholds from the seed model and 25 row ranges per query tile a 500 k-row shard
 // of C2 runs 312-tile runs and the 4-wave kernel is 3.5 % faster there, 156- and 78-tile runs are even / 1 % in favour
 // of 8 waves: profiles/r04_waves_ab_model.log)
-#ifndef PN_BF8_MAXRUN
-#define PN_BF8_MAXRUN 200
-#endif
-constexpr uint32_t kBf8MaxRun = PN_BF8_MAXRUN;  // runs shorter than this many tiles take the 8-wave main-pass kernel
+constexpr uint32_t kBf8MaxRun = 200;  // runs shorter than this many tiles take the 8-wave main-pass kernel
 constexpr size_t kBf8MaxImage = (size_t)768 << 20;  // ... on corpora whose tile image is at most this large
 template <int KS, int M, bool RAD, bool CI>
 static hipError_t launch_bf16_t(const void *img, uint32_t n_tiles, const void *B, uint32_t q_tiles, uint32_t kp,
@@ -3413,7 +2809,7 @@ static hipError_t launch_bf16_t(const void *img, uint32_t n_tiles, const void *B
     }
 #define PN_BF_LAUNCH_MODE(MD)                                                                                          \
     {                                                                                                                   \
-        auto kern = bf16_filter_kernel<KS, M, RAD, CI, MD, kBfCapture && (M > 1) && !RAD>;                                                             \
+        auto kern = bf16_filter_kernel<KS, M, RAD, CI, MD>;                                                             \
         static LdsAttrOnce lds_attr; /* per instantiation */                                                            \
         const hipError_t e = lds_attr.ensure(reinterpret_cast<const void *>(kern), sh);                                 \
         if (e != hipSuccess) return e;                                                                                  \
@@ -3424,7 +2820,7 @@ static hipError_t launch_bf16_t(const void *img, uint32_t n_tiles, const void *B
     }
     // The 8-wave kernel (bf16_filter8_kernel): main pass of a k-NN call (thresholds given), 64-slot buffers, aligned
     // partition -- every workgroup one whole run
-    if constexpr (M <= 4 && !RAD && !kBfCapture && kBf8Enabled) {
+    if constexpr (M <= 4 && !RAD) {
         const bool aligned = split == 1 && (uint32_t)n_wg >= q_tiles && (uint32_t)n_wg % q_tiles == 0;
         // Measured on one device (round 4, profiles/r04_waves_ab.log): at C2 (1302-tile runs) the 8-wave kernel is 7-9 %
         // SLOWER than the 4-wave kernel (2.47-2.50 vs 2.28-2.31 ms: twice the LDS fragment traffic, an 8-wave meeting per
@@ -3441,7 +2837,7 @@ static hipError_t launch_bf16_t(const void *img, uint32_t n_tiles, const void *B
         const size_t image_bytes = (size_t)n_tiles * kBP * (2 * KS + 1) * 16;
         const bool want8 = cb.bf16_waves == 8 || (cb.bf16_waves == 0 && image_bytes <= kBf8MaxImage &&
                                                   (M >= 2 || run_tiles < kBf8MaxRun));
-        if (want8 && aligned && !scout_out && (tau_init || bsh.seed_lists) && kBf8Enabled) {
+        if (want8 && aligned && !scout_out && (tau_init || bsh.seed_lists)) {
             if (use_sh && (!tau_init || shp->n_refresh < 1 || M > 2)) return hipErrorInvalidValue;
             BfShared a = bsh;
             if (use_sh) {
@@ -3452,7 +2848,7 @@ static hipError_t launch_bf16_t(const void *img, uint32_t n_tiles, const void *B
                 a.rank = shp->rank;
             }
             const unsigned grid = (unsigned)(n_wg + (use_sh ? shp->n_refresh : 0));
-#define PN_BF8_LAUNCH(SHV)                                                                                               \
+#define PN_BF_LAUNCH8(SHV)                                                                                              \
     {                                                                                                                   \
         auto kern = bf16_filter8_kernel<KS, CI, SHV, M>;                                                                  \
         static LdsAttrOnce lds_attr; /* per instantiation */                                                            \
@@ -3462,15 +2858,15 @@ static hipError_t launch_bf16_t(const void *img, uint32_t n_tiles, const void *B
                            static_cast<const u32x4 *>(B), q_tiles, kp_keep, static_cast<uint2 *>(cb.keys), cb.cnt,      \
                            static_cast<uint32_t *>(cb.tau), cb.nq_pad, tau_init, a);                                    \
     }
-            if (use_sh) PN_BF8_LAUNCH(true) else PN_BF8_LAUNCH(false)
-#undef PN_BF8_LAUNCH
+            if (use_sh) PN_BF_LAUNCH8(true) else PN_BF_LAUNCH8(false)
+#undef PN_BF_LAUNCH8
             return hipGetLastError();
         }
     }
     if (use_sh) {  // shared thresholds: main pass with refresher workgroups behind the n_wg main ones
-        if constexpr (!RAD && M <= 2 && !kBfCapture) {
+        if constexpr (!RAD && M <= 2) {
             if (!tau_init || scout_out || split != 1 || shp->n_refresh < 1) return hipErrorInvalidValue;
-            auto kern = bf16_filter_kernel<KS, M, false, CI, 2, false, true>;
+            auto kern = bf16_filter_kernel<KS, M, false, CI, 2, true>;
             static LdsAttrOnce lds_attr;
             const hipError_t e = lds_attr.ensure(reinterpret_cast<const void *>(kern), sh);
             if (e != hipSuccess) return e;
@@ -3534,11 +2930,7 @@ int bf16_segments(size_t q_tiles, int n_wg, int split) {
 }
 
 bool bf16_shared_supported(int cap) {
-#ifdef PN_DIAG_BF_CAPT
-    return false;
-#else
     return cap == 64 || cap == 128;
-#endif
 }
 hipError_t launch_bf16_filter(const void *img, size_t n, int dim, const void *B, int kp, const CandBuf &cb, int n_wg,
                               int split, int scout_max, const uint32_t *tau_init, bool radius, float *scout_out,

@@ -515,13 +515,7 @@ static int finish_index(pn_index *ix, const T *d_src, size_t row_stride, hipStre
         // translation vector = per-dimension mean when that shrinks the squared norms enough: f64 sums, decided on the device
         HIPCHK(hipMalloc((void **)&ix->d_mu, ix->dim * sizeof(float)));
         HIPCHK(col_sums());
-#ifdef PN_DIAG_NO_CENTER
-        const bool never_center = true;
-#else
-        const bool never_center = false;
-#endif
-        HIPCHK(launch_bf16_decide_mu(d_sums, ix->n, (int)ix->dim, never_center, ix->d_mu, d_w + 2, s));
-#ifndef PN_DIAG_NO_CI
+        HIPCHK(launch_bf16_decide_mu(d_sums, ix->n, (int)ix->dim, /*never=*/false, ix->d_mu, d_w + 2, s));
         if (bf16_ci_candidate((int)ix->dim)) {
             // the extra columns would cost an MFMA step of their own: drop them when the corpus-wide maxima of the
             // bound's per-row constants are close to their means (homogeneous row norms).  The image's layout depends
@@ -535,7 +529,6 @@ static int finish_index(pn_index *ix, const T *d_src, size_t row_stride, hipStre
             ix->bf16_bmax = h_st[0];
             ix->bf16_dmax = h_st[1];
         }
-#endif
         HIPCHK(hipMalloc(&ix->d_img, bf16_image_bytes(ix->n, (int)ix->dim, ix->bf16_ci)));
         HIPCHK(pack());
         if (bf16_hw_state(ix->device).load() < 0)  // first bf16 index on this device: the self-test rides along
@@ -876,14 +869,10 @@ static void rec_resolve(const pn_index *ix, CallRec &r) {
         // a call that handed more than 1/16 of its queries to the next tier: this corpus defeats the current plan
         // -- widen it, then turn the tier off (sticky; takes effect from the next call on)
         const size_t nf = *r.h_nflag;
-#if !defined(PN_DIAG_BF_NOSLOW) && !defined(PN_DIAG_BF_NOSTORE) && !defined(PN_DIAG_BF_NOBARRIER) && !defined(PN_DIAG_BF_NOWAIT) && !defined(PN_DIAG_BF_NOAPPEND)  // timing-only builds flag queries by design
         // (a call seeded by the index's model instead of a scout launch: more than one query in 128 unproven means the
         // model does not fit these queries -- back to the scout, for good; the plan itself is not to blame)
         if (seed_model_feedback(sh, r.model_seed, nf, r.nq)) {
         } else if (nf * 16 > r.nq && r.nq >= 64 && ix->filter_slots == 0 && sh.bf16_level < 2) sh.bf16_level += 1;
-#else
-        (void)nf;
-#endif
     }
     r.pending = false;
 }
@@ -1635,7 +1624,6 @@ static Bf16Plan bf16_plan_wide(const pn_index *ix, size_t nq_pad, size_t kout, i
     // Shared scout (see bf16_plan): the rows scouted by all waves of a query form one sample; lambda = expected
     // number of the R relevant rows in it (<= 1.2), seed_rank = smallest rank with P(Poisson >= rank) <= 1e-7
     p.shared_scout = false;
-#ifndef PN_DIAG_NO_SHARED_SCOUT
     if (p.ok && level == 0 && ix->filter_slots == 0 && segs >= 4.0) {
         const size_t run_len = q_tiles * r_tiles / (size_t)p.n_wg;
         double lam_w = 1.2, t_cap_w = 16.0;
@@ -1659,7 +1647,6 @@ static Bf16Plan bf16_plan_wide(const pn_index *ix, size_t nq_pad, size_t kout, i
             p.shared_scout = p.seed_rank <= bf16_scout_list();
         }
     }
-#endif
     p.first_eval = (int)std::ceil(R);
     plan_seed_model(ix, p, R, kout, p.shared_scout);
     if (plan_knobs().debug)
@@ -1838,7 +1825,6 @@ static Bf16Plan bf16_plan(const pn_index *ix, size_t nq_pad, size_t kout, int le
     // relevant rows inside the sample (kept <= 1.2); the seed must stay above them: seed_rank = smallest rank with
     // P(Poisson(lambda) >= rank) <= 1e-7 (a seed that is too low only sends the query to the next tier).
     p.shared_scout = false;
-#ifndef PN_DIAG_NO_SHARED_SCOUT
     if (p.ok && level == 0 && ix->filter_slots == 0 && p.split == 1 && per_tile >= 2 &&
         p.n_wg % (int)q_tiles == 0) {
         const size_t run_len = r_tiles / per_tile;
@@ -1875,7 +1861,6 @@ static Bf16Plan bf16_plan(const pn_index *ix, size_t nq_pad, size_t kout, int le
             p.scout_tiles = p.scout_tiles * 3 / 4;
         }
     }
-#endif
     // Shared thresholds: with the whole grid resident (main workgroups + refreshers <= the 2 n_cu workgroup slots) the
     // slots the aligned partition leaves idle run refreshers.  r = R + 5.5 sqrt(R) (k = 10: 51): on uniform 1M x 128
     // data the rows whose bound lies below the 10th neighbour's distance number 22 +- 5.3 (max 44 over 256 queries,

@@ -309,11 +309,7 @@ __device__ __forceinline__ void v2_step(const float *__restrict__ P, const float
     const f32x4 fa1 = *reinterpret_cast<const f32x4 *>(trow + 32 * STR + foff[0]);
     const float an0 = h ? 1.0f : pnl[cur * kV2P + jq];
     const float an1 = h ? 1.0f : pnl[cur * kV2P + 32 + jq];
-#ifdef PN_DIAG_NO_STAGE
-    if (false) {
-#else
     if (more) {
-#endif
         if constexpr (GLDS) {
             v2_dma_tile<NKG>(P, pnorm, tiles, pnl, rt + 1, cur ^ 1, wave, lane);
         } else {
@@ -327,34 +323,22 @@ __device__ __forceinline__ void v2_step(const float *__restrict__ P, const float
     }
 
     const BlockScan s1 = v2_chain<NKG>(trow, foff, fa0, an0, bn, b, acc0, acc1, tau);
-#ifdef PN_DIAG_NO_SLOWPATH
-    asm volatile("" ::"v"(s1.m), "v"(s1.am), "v"(s1.npass));
-#else
     if (__any(s1.npass != 0)) {
         PN_T0();
         v2_slow<M>(acc1, s1, tau, (rt - 1) * kV2P + 32, h, wave, lane, kp, cand_k, cand_i, taus_w, cnts_w, ckq, ciq,
                 cnt_q, tau_q, GC);
         PN_T1(3);
     }
-#endif
     const BlockScan s0 = v2_chain<NKG>(trow + 32 * STR, foff, fa1, an1, bn, b, acc1, acc0, tau);
-#ifdef PN_DIAG_NO_SLOWPATH
-    asm volatile("" ::"v"(s0.m), "v"(s0.am), "v"(s0.npass));
-#else
     if (__any(s0.npass != 0)) {
         PN_T0();
         v2_slow<M>(acc0, s0, tau, rt * kV2P, h, wave, lane, kp, cand_k, cand_i, taus_w, cnts_w, ckq, ciq, cnt_q, tau_q, GC);
         PN_T1(3);
     }
-#endif
 
     // register-staged tile rt+1 -> LDS[cur^1] (its loads had both chains to land); with LDS-DMA the
     // data is already on its way into LDS and the barrier below carries the vmcnt(0)
-#ifdef PN_DIAG_NO_STAGE
-    if (false) {
-#else
     if (!GLDS && more) {
-#endif
         float *dst_ = tiles + (cur ^ 1) * kV2P * STR;
 #pragma unroll
         for (int i_ = 0; i_ < NLD; ++i_) {
@@ -364,13 +348,11 @@ __device__ __forceinline__ void v2_step(const float *__restrict__ P, const float
         }
         if (tid < kV2P) pnl[(cur ^ 1) * kV2P + tid] = stn;
     }
-#ifndef PN_DIAG_NO_BARRIER
     {
         PN_T0();
         __syncthreads();
         PN_T1(4);
     }
-#endif
 }
 
 // GC = false: candidate buffers in LDS, one workgroup per CU.  GC = true: candidate buffers in HBM
@@ -483,13 +465,9 @@ __global__ __launch_bounds__(256, GC ? 2 : 1) void mfma_filter_v2_kernel(
                 sc.am = lt ? i : sc.am;
                 sc.npass += acc1[i] < tau ? 1u : 0u;
             }
-#ifndef PN_DIAG_NO_SLOWPATH
             if (__any(sc.npass != 0))
                 v2_slow<M>(acc1, sc, tau, (rt1 - 1) * kV2P + 32, h, wave, lane, kp, cand_k, cand_i, taus_w, cnts_w, ckq,
                         ciq, cnt_q, tau_q, GC);
-#else
-            asm volatile("" ::"v"(sc.m));
-#endif
         }
 
         // ---- flush this run: <= kp candidates per query, count and threshold, to HBM

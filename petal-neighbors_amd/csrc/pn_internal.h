@@ -435,7 +435,7 @@ hipError_t launch_bf16_column_sums(const T *P, size_t n, int dim, size_t ld, dou
 // core's accumulation error against the allowance the bf16 bound makes for it (bf16_filter.hip, bf16_selftest_kernel)
 hipError_t launch_bf16_selftest(float *out, hipStream_t s);
 // mu [dim] <- the per-dimension mean (f32) when translating by it shrinks the sum of squared norms 16x (wide rows: 2x), else
-// zero; words[0] <- 1 / 0 accordingly.  never: always zero (diagnostic builds)
+// zero; words[0] <- 1 / 0 accordingly.  never: always zero (no caller asks for it)
 hipError_t launch_bf16_decide_mu(const double *sums, size_t n, int dim, bool never, float *mu, uint32_t *words, hipStream_t s);
 // out4 (zeroed by the caller): max Bp, max Dp, sum Bp, sum Dp over the rows
 template <typename T>

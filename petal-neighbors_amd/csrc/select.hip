@@ -272,13 +272,10 @@ __device__ __forceinline__ float exact_distance_f32(const float *__restrict__ q,
 // whole cost of the re-rank kernel.  len must be a multiple of 4 (device rows are zero padded to a multiple of 8:
 // the padding adds (0-0)*(0-0) = +0, which leaves every partial sum unchanged).
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
-#ifndef PN_DIAG_RR_PREFETCH
-#define PN_DIAG_RR_PREFETCH 16
-#endif
 __device__ __forceinline__ float exact_distance_prefetched_f32(const float *qs, const float *__restrict__ p, int len) {
 #pragma clang fp contract(off)
     float s = 0.0f;
-    constexpr int NV = PN_DIAG_RR_PREFETCH;  // 16-byte loads in flight per round
+    constexpr int NV = 16;  // 16-byte loads in flight per round
     for (int k0 = 0; k0 < len; k0 += 4 * NV) {
         f32x4_t v[NV];
 #pragma unroll
@@ -324,13 +321,11 @@ __device__ __forceinline__ KeyT kth_smallest_regs(const KeyT *a, uint32_t n, uin
 // ... of n LDS words: in registers up to 512 of them, else one ballot per 64 words and bit over LDS
 __device__ __forceinline__ uint32_t kth_smallest_lds(const uint32_t *a, uint32_t n, uint32_t k, int lane) {
     uint32_t T = 0;
-#ifndef PN_DIAG_SELECT_LDS
     if (n <= 128u) return kth_smallest_regs<uint32_t, 2>(a, n, k, lane);
     if (n <= 192u) return kth_smallest_regs<uint32_t, 3>(a, n, k, lane);
     if (n <= 256u) return kth_smallest_regs<uint32_t, 4>(a, n, k, lane);
     if (n <= 384u) return kth_smallest_regs<uint32_t, 6>(a, n, k, lane);
     if (n <= 512u) return kth_smallest_regs<uint32_t, 8>(a, n, k, lane);
-#endif
     for (int b = 31; b >= 0; --b) {
         const uint32_t cand = T | (1u << b);
         uint32_t c = 0;
@@ -499,11 +494,8 @@ extern "C" int pn_debug_read_rr(unsigned long long *out, int nq) {
 #else
 #define RR_STAMP(i) ((void)0)
 #endif
-#ifndef PN_DIAG_RR_WAVES
-#define PN_DIAG_RR_WAVES 1
-#endif
 template <typename T, bool COS = false>
-__global__ __launch_bounds__(64, PN_DIAG_RR_WAVES) void select_rerank_kernel(
+__global__ __launch_bounds__(64, 1) void select_rerank_kernel(
     const uint32_t *__restrict__ ctau, const uint32_t *__restrict__ cidx, const uint32_t *__restrict__ ccnt,
     size_t nq_pad, int nseg, int cap, const T *__restrict__ P, size_t ldp, const T *__restrict__ Q,
     size_t ldq, int dim, uint32_t n_rows, int kout, uint64_t index_base, uint64_t *__restrict__ idx_out,
