@@ -171,6 +171,33 @@ extern "C" {
     pub fn pn_lof_score_device_f64(index: *const pn_index, d_queries: *const f64, nq: usize, q_cols: usize,
                                    q_row_stride: usize, k: usize, d_lrd: *const f64, d_kdist: *const f64, flags: c_uint,
                                    d_score: *mut f64, stream: *mut c_void) -> c_int;
+    /// OPTICS of the indexed rows: ordering [n] (row numbers, no index base) and reachability [n] required, predecessor [n]
+    /// and core_distances [n] nullable; min_samples counts other rows, 1 <= min_samples <= n - 1; flags = 0.  The device
+    /// entry points write in stream order and block the host once
+    pub fn pn_optics_f32(index: *const pn_index, min_samples: usize, max_eps: f32, flags: c_uint, ordering: *mut u64,
+                         reachability: *mut f32, predecessor: *mut i64, core_distances: *mut f32) -> c_int;
+    pub fn pn_optics_f64(index: *const pn_index, min_samples: usize, max_eps: f64, flags: c_uint, ordering: *mut u64,
+                         reachability: *mut f64, predecessor: *mut i64, core_distances: *mut f64) -> c_int;
+    pub fn pn_optics_device_f32(index: *const pn_index, min_samples: usize, max_eps: f32, flags: c_uint,
+                                d_ordering: *mut u64, d_reachability: *mut f32, d_predecessor: *mut i64,
+                                d_core_distances: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn pn_optics_device_f64(index: *const pn_index, min_samples: usize, max_eps: f64, flags: c_uint,
+                                d_ordering: *mut u64, d_reachability: *mut f64, d_predecessor: *mut i64,
+                                d_core_distances: *mut f64, stream: *mut c_void) -> c_int;
+    /// DBSCAN labels at eps read off an ordering: labels [n] (-1 = noise, clusters numbered by first appearance in the
+    /// ordering), n_clusters [1] nullable; an ordering that is no permutation: PN_ERR_INVALID (device: d_error [1], nullable)
+    pub fn pn_optics_dbscan_f32(index: *const pn_index, ordering: *const u64, reachability: *const f32,
+                                core_distances: *const f32, eps: f32, flags: c_uint, labels: *mut i64,
+                                n_clusters: *mut u64) -> c_int;
+    pub fn pn_optics_dbscan_f64(index: *const pn_index, ordering: *const u64, reachability: *const f64,
+                                core_distances: *const f64, eps: f64, flags: c_uint, labels: *mut i64,
+                                n_clusters: *mut u64) -> c_int;
+    pub fn pn_optics_dbscan_device_f32(index: *const pn_index, d_ordering: *const u64, d_reachability: *const f32,
+                                       d_core_distances: *const f32, eps: f32, flags: c_uint, d_labels: *mut i64,
+                                       d_n_clusters: *mut u64, d_error: *mut i32, stream: *mut c_void) -> c_int;
+    pub fn pn_optics_dbscan_device_f64(index: *const pn_index, d_ordering: *const u64, d_reachability: *const f64,
+                                       d_core_distances: *const f64, eps: f64, flags: c_uint, d_labels: *mut i64,
+                                       d_n_clusters: *mut u64, d_error: *mut i32, stream: *mut c_void) -> c_int;
     /// dist_out nullable (PN_RADIUS_SORTED needs it); *idx_out / *dist_out released with pn_free
     pub fn pn_query_radius_self_f32(index: *const pn_index, radius: f32, flags: c_uint, offsets: *mut u64,
                                     idx_out: *mut *mut u64, dist_out: *mut *mut f32) -> c_int;

@@ -62,7 +62,8 @@ extern "C" {
  * pn_sharded_query_radius_self_{,device_}{f32,f64}; pn_query_radii_{,device_,self_,self_device_}{f32,f64};
  * pn_dbscan_{,device_}{f32,f64}, PN_OPT_DBSCAN_PIECE; pn_mst_{,device_}{f32,f64}, PN_OPT_MST_BATCH;
  * pn_linkage_{,device_}{f32,f64}, pn_hdbscan_{,device_}{f32,f64}; pn_lof_{,device_}{f32,f64},
- * pn_lof_score_{,device_}{f32,f64}. */
+ * pn_lof_score_{,device_}{f32,f64}; pn_optics_{,device_}{f32,f64}, pn_optics_dbscan_{,device_}{f32,f64},
+ * PN_OPT_OPTICS_PIECE. */
 #define PN_ABI_VERSION 3
 
 /* ---- error codes.  EMPTY / NOT_CONTIGUOUS are ArrayError (src/lib.rs:9-16). */
@@ -117,9 +118,13 @@ enum {
     PN_OPT_DBSCAN_PIECE = 11,    /* pn_dbscan_*: the most list entries (64-bit indices in workspace scratch) one piece of
                                   the union stage holds; 0 (default) = 2^27, i.e. 1 GiB.  A row whose own list is longer
                                   is a piece of its own.  Never changes a result. */
-    PN_OPT_MST_BATCH = 12        /* pn_mst_*: the most listed rows one scan launch takes; 0 (default) = 2^18, the
+    PN_OPT_MST_BATCH = 12,       /* pn_mst_*: the most listed rows one scan launch takes; 0 (default) = 2^18, the
                                   self-queries' chunk; negative: PN_ERR_INVALID.  Never changes a result (it lets tests
                                   force several launches per round at small n). */
+    PN_OPT_OPTICS_PIECE = 13     /* pn_optics_*: the most list entries one piece of the graph fill holds in workspace
+                                  scratch before it is packed into the graph store; 0 (default) = 2^27; negative:
+                                  PN_ERR_INVALID.  A row whose own list is longer is a piece of its own.  Never changes a
+                                  result (it lets tests force several pieces at small n). */
 };
 
 typedef struct pn_index pn_index;
@@ -560,6 +565,83 @@ int pn_lof_score_device_f32(const pn_index *index, const float *d_queries, size_
 int pn_lof_score_device_f64(const pn_index *index, const double *d_queries, size_t nq, size_t q_cols, size_t q_row_stride,
                             size_t k, const double *d_lrd, const double *d_kdist, unsigned flags, double *d_score,
                             void *stream);
+
+/* ---- OPTICS on the device (scikit-learn's cluster.OPTICS with metric = this index's, min_samples = this library's + 1):
+ * the ordering, the reachability plot, predecessors and core distances of the indexed rows, and the DBSCAN labelling at
+ * any eps <= max_eps read off that ordering.  The min_samples self-query gives the core distances, the max_eps radius
+ * self-query the graph, which is kept whole in HBM; nothing leaves HBM but the outputs.
+ * min_samples >= 1 counts OTHER rows, as pn_hdbscan_* and pn_lof_* do; max_eps is in the index's element type.  The
+ * contract:
+ *   core[i]  = the last column of pn_query_self_*(min_samples), flags 0, if that value is < max_eps -- strict '<', like
+ *              every radius in this library; a NaN value is not < max_eps -- else +inf (undefined).
+ *   N(i)     = { j != i : distance(p_i, p_j) < max_eps } with the distances of pn_query_radius_self_*(max_eps), flags 0:
+ *              bit-identical to the metric.  max_eps <= 0 or NaN: empty lists everywhere; +inf: every row whose distance
+ *              is not NaN.
+ *   Start:     reach[i] = +inf, pred[i] = -1, nothing processed.
+ *   n times:   p = the unprocessed row with the smallest (reach, row): reach compared by IEEE '<', ties broken by the
+ *              lower row.  p is appended to the ordering and marked processed.  If core[p] is finite, then for every
+ *              unprocessed q in N(p): new = d(p, q) > core[p] ? d(p, q) : core[p]; if new < reach[q] (strict):
+ *              reach[q] = new, pred[q] = p.
+ * ordering [n] uint64: row numbers WITHOUT PN_OPT_INDEX_BASE (they index the other three arrays); reachability [n] of
+ * the element type, indexed by row, +inf for a row picked with nothing reaching it; predecessor [n] int64, -1 for such a
+ * row, nullable; core_distances [n] of the element type, nullable.  ordering and reachability are required.
+ * This is scikit-learn's algorithm on THIS library's distances: ordering_ and predecessor_ equal those of
+ * OPTICS(min_samples + 1, max_eps, metric = "precomputed") fed with this library's distance matrix, up to this library's
+ * distance arithmetic -- scikit-learn's own pairwise distances differ in the last bits and break the frequent exact ties
+ * reach = core[p] differently.  The result depends on the data alone: nothing in it depends on scheduling, the engine
+ * or PN_OPT_OPTICS_PIECE.  A row with a NaN coordinate has an empty list and an undefined core and appears in no list:
+ * it comes out as an isolated +inf entry.  Euclidean and Cosine indexes, f32 and f64.  n = 1: ordering = {0}, reach and
+ * core +inf, pred -1.  pn_stats.queries advances by n.
+ * flags must be 0.  Argument errors, before any device is touched and in this order: flags != 0; NULL ordering or
+ * reachability; NULL index; wrong element type; min_samples outside [1, n - 1] when n >= 2: PN_ERR_INVALID; more than
+ * 2^31 - 1 rows: PN_ERR_UNSUPPORTED (stored neighbour ids are 32-bit).
+ * The call: the self-query chunk by chunk for the cores; a counting pass of the per-row-radius pipeline (radius max_eps
+ * for the rows with a defined core, 0 for the others: only core rows ever relax anything, so the others cost no entries);
+ * a fill piece by piece (at most 2^18 rows and PN_OPT_OPTICS_PIECE entries each), every piece repacked into the graph
+ * store; then ONE launch of ONE workgroup that runs the n dependent steps over a 64-ary tournament tree of packed
+ * (reach, row) keys -- no launch per step, no host round trip, no waiting between workgroups.
+ * Device memory beyond a 2^18-query batch's workspace, with E = the number of stored list entries:
+ * E * (4 + sizeof T) + 8 (n + 1) bytes for the graph (32-bit ids, distances, offsets), (8 + sizeof T) bytes per entry of the
+ * largest piece while it is filled, and about 4.1 * sizeof T bytes per row (radii, cores, and the tree's 1.016 n keys of
+ * 2 * sizeof T bytes).  A graph that does not fit: PN_ERR_NOMEM, pn_last_error() names the bytes the graph store needs.
+ * Device entry points: outputs in HBM, written in stream order on `stream`; the call BLOCKS THE HOST ONCE, after the
+ * counting pass, to read the n + 1 offsets it cuts the pieces from -- like pn_dbscan_device_* it is not capturable into a
+ * graph.
+ *
+ * pn_optics_dbscan_*: the labels DBSCAN(eps, min_samples) gives, read off an ordering (scikit-learn's
+ * cluster_optics_dbscan with '<' in place of '<='); eps <= the max_eps of the ordering.  The handle supplies n, the
+ * device and the workspace; ordering, reachability and core_distances are pn_optics_*'s outputs.
+ *   far[i]  = !(reach[i] < eps);  near[i] = core[i] < eps.
+ *   labels[ordering[t]] = (the number of s <= t with far && near at ordering[s]) - 1; then labels[i] = -1 wherever
+ *   far[i] && !near[i].
+ * Clusters are numbered by first appearance in the ordering -- this is NOT pn_dbscan_*'s "lowest member row" numbering;
+ * the partition of the rows with core < eps is the same, border rows may be assigned differently.  labels [n] int64;
+ * n_clusters [1] nullable.  On the device: a flag pass, one prefix sum over the ordering, a scatter; nothing waits.
+ * An ordering that is not a permutation of 0 .. n - 1: PN_ERR_INVALID after the device work, the labels unspecified.
+ * The host variant reads that one word back; the device variant writes PN_OK or PN_ERR_INVALID to d_error[0] (an int32
+ * in HBM, nullable) in stream order, returns PN_OK and never waits for the device.
+ * flags must be 0.  Argument errors, before any device is touched and in this order: flags != 0; NULL labels; NULL
+ * ordering, reachability or core_distances; NULL index; wrong element type: PN_ERR_INVALID; more than 2^31 - 1 rows:
+ * PN_ERR_UNSUPPORTED.  Device memory: 16 bytes per row.
+ * Not in this version: row-sharded handles, xi extraction. */
+int pn_optics_f32(const pn_index *index, size_t min_samples, float max_eps, unsigned flags, uint64_t *ordering,
+                  float *reachability, int64_t *predecessor, float *core_distances);
+int pn_optics_f64(const pn_index *index, size_t min_samples, double max_eps, unsigned flags, uint64_t *ordering,
+                  double *reachability, int64_t *predecessor, double *core_distances);
+int pn_optics_device_f32(const pn_index *index, size_t min_samples, float max_eps, unsigned flags, uint64_t *d_ordering,
+                         float *d_reachability, int64_t *d_predecessor, float *d_core_distances, void *stream);
+int pn_optics_device_f64(const pn_index *index, size_t min_samples, double max_eps, unsigned flags, uint64_t *d_ordering,
+                         double *d_reachability, int64_t *d_predecessor, double *d_core_distances, void *stream);
+int pn_optics_dbscan_f32(const pn_index *index, const uint64_t *ordering, const float *reachability,
+                         const float *core_distances, float eps, unsigned flags, int64_t *labels, uint64_t *n_clusters);
+int pn_optics_dbscan_f64(const pn_index *index, const uint64_t *ordering, const double *reachability,
+                         const double *core_distances, double eps, unsigned flags, int64_t *labels, uint64_t *n_clusters);
+int pn_optics_dbscan_device_f32(const pn_index *index, const uint64_t *d_ordering, const float *d_reachability,
+                                const float *d_core_distances, float eps, unsigned flags, int64_t *d_labels,
+                                uint64_t *d_n_clusters, int32_t *d_error, void *stream);
+int pn_optics_dbscan_device_f64(const pn_index *index, const uint64_t *d_ordering, const double *d_reachability,
+                                const double *d_core_distances, double eps, unsigned flags, int64_t *d_labels,
+                                uint64_t *d_n_clusters, int32_t *d_error, void *stream);
 
 /* ---- distance::pairwise(x, &Euclidean) (src/distance.rs:58-74): n x n
  * symmetric matrix, zero diagonal, n < 2 -> zeros. Host in, host out. */

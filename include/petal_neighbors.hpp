@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -115,6 +116,19 @@ template <typename A>
 struct Lof {
     std::vector<double> lof, lrd;
     std::vector<A> kdist;
+};
+// the answer of BallTree::optics: ordering[t] = the t-th row OPTICS visits (a plain row number); reachability, predecessor
+// (-1 = none) and core_distances are indexed by row, +inf where undefined
+template <typename A>
+struct Optics {
+    std::vector<size_t> ordering;
+    std::vector<A> reachability, core_distances;
+    std::vector<int64_t> predecessor;
+};
+// the answer of BallTree::optics_dbscan: labels [n], clusters numbered by first appearance in the ordering, -1 = noise
+struct OpticsDbscan {
+    std::vector<int64_t> labels;
+    size_t n_clusters = 0;
 };
 // the CSR answer of BallTree::query_radius_self: row i's neighbours are idx[offsets[i] .. offsets[i + 1]] (dist beside
 // them when asked for)
@@ -401,6 +415,41 @@ class BallTree {
         else
             check(pn_lof_score_f64(h_, queries, nq, dim_, (ptrdiff_t)dim_, k, fit.lrd.data(), fit.kdist.data(), 0u, out));
         return score;
+    }
+    // extension: OPTICS on the device (pn_optics_*): scikit-learn's OPTICS(min_samples + 1, max_eps) on this library's
+    // distances; min_samples counts OTHER rows, every radius is a strict '<'
+    Optics<A> optics(size_t min_samples, A max_eps = std::numeric_limits<A>::infinity()) const {
+        Optics<A> res;
+        std::vector<uint64_t> ord(n_);
+        res.reachability.resize(n_);
+        res.core_distances.resize(n_);
+        res.predecessor.resize(n_);
+        if constexpr (kF32)
+            check(pn_optics_f32(h_, min_samples, max_eps, 0u, ord.data(), res.reachability.data(), res.predecessor.data(),
+                                res.core_distances.data()));
+        else
+            check(pn_optics_f64(h_, min_samples, max_eps, 0u, ord.data(), res.reachability.data(), res.predecessor.data(),
+                                res.core_distances.data()));
+        res.ordering.assign(ord.begin(), ord.end());
+        return res;
+    }
+    // extension: the DBSCAN labels at eps (<= the ordering's max_eps) read off an ordering (pn_optics_dbscan_*): clusters
+    // numbered by first appearance in the ordering, -1 = noise.  An ordering that is no permutation of the rows throws
+    OpticsDbscan optics_dbscan(const Optics<A> &o, A eps) const {
+        if (o.ordering.size() != n_ || o.reachability.size() != n_ || o.core_distances.size() != n_)
+            throw std::invalid_argument("optics_dbscan: the ordering must hold one entry per indexed row");
+        OpticsDbscan res;
+        std::vector<uint64_t> ord(o.ordering.begin(), o.ordering.end());
+        res.labels.resize(n_);
+        uint64_t ncl = 0;
+        if constexpr (kF32)
+            check(pn_optics_dbscan_f32(h_, ord.data(), o.reachability.data(), o.core_distances.data(), eps, 0u,
+                                       res.labels.data(), &ncl));
+        else
+            check(pn_optics_dbscan_f64(h_, ord.data(), o.reachability.data(), o.core_distances.data(), eps, 0u,
+                                       res.labels.data(), &ncl));
+        res.n_clusters = (size_t)ncl;
+        return res;
     }
     // extension: one radius per row (pn_query_radii_self_*): radii [size()], row i's list is the scalar overload's for
     // r = radii[i].  (Taken for pointer arguments only: a literal 0 or NULL stays a call of the scalar overload.)

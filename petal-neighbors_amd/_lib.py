@@ -24,6 +24,7 @@ PN_OPT_BF16_WAVES = 9
 PN_OPT_SEED_MODEL = 10
 PN_OPT_DBSCAN_PIECE = 11
 PN_OPT_MST_BATCH = 12
+PN_OPT_OPTICS_PIECE = 13
 PN_RADIUS_SORTED = 1
 PN_SELF_INCLUDE = 2
 
@@ -127,6 +128,14 @@ SIGNATURES = {
     "pn_lof_score_f64": (_i, [_vp, _vp, _sz, _sz, _ssz, _sz, _vp, _vp, C.c_uint, _vp]),
     "pn_lof_score_device_f32": (_i, [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, C.c_uint, _vp, _vp]),
     "pn_lof_score_device_f64": (_i, [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, C.c_uint, _vp, _vp]),
+    "pn_optics_f32": (_i, [_vp, _sz, C.c_float, C.c_uint, _vp, _vp, _vp, _vp]),
+    "pn_optics_f64": (_i, [_vp, _sz, C.c_double, C.c_uint, _vp, _vp, _vp, _vp]),
+    "pn_optics_device_f32": (_i, [_vp, _sz, C.c_float, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
+    "pn_optics_device_f64": (_i, [_vp, _sz, C.c_double, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
+    "pn_optics_dbscan_f32": (_i, [_vp, _vp, _vp, _vp, C.c_float, C.c_uint, _vp, _vp]),
+    "pn_optics_dbscan_f64": (_i, [_vp, _vp, _vp, _vp, C.c_double, C.c_uint, _vp, _vp]),
+    "pn_optics_dbscan_device_f32": (_i, [_vp, _vp, _vp, _vp, C.c_float, C.c_uint, _vp, _vp, _vp, _vp]),
+    "pn_optics_dbscan_device_f64": (_i, [_vp, _vp, _vp, _vp, C.c_double, C.c_uint, _vp, _vp, _vp, _vp]),
     "pn_free": (None, [_vp]),
     "pn_pairwise_f32": (_i, [_vp, _sz, _sz, _ssz, _i, _vp]),
     "pn_pairwise_f64": (_i, [_vp, _sz, _sz, _ssz, _i, _vp]),

@@ -860,3 +860,94 @@ class BallTree:
                 self._h, queries.data_ptr(), nq, qc, queries.stride(0) if nq > 1 else max(qc, 1), k, lrd.data_ptr(),
                 kdist.data_ptr(), 0, scores.data_ptr(), C.c_void_p(st)))
         return scores
+
+    # ------------------------------------------------------------------- OPTICS
+    # scikit-learn's ``OPTICS(min_samples + 1, max_eps)`` on the device (``pn_optics_*``): the ordering, the reachability
+    # plot, predecessors and core distances, and (``optics_dbscan``) the DBSCAN labels at any eps <= max_eps read off the
+    # ordering.  ``min_samples`` counts OTHER rows; every radius is a strict '<'.  ``ordering`` holds plain row numbers
+    # (no ``PN_OPT_INDEX_BASE``): it indexes the other arrays.
+    def _optics_args(self, min_samples, max_eps):
+        k = int(min_samples)
+        if k < 1 or (self._n >= 2 and k > self._n - 1):
+            raise ValueError(f"min_samples must be in [1, n - 1] = [1, {max(self._n - 1, 1)}]")
+        return k, (C.c_float(max_eps) if self._sfx == "f32" else C.c_double(max_eps))
+
+    def optics(self, min_samples: int, max_eps=np.inf):
+        """``(ordering uint64 [n], reachability [n], predecessor int64 [n], core_distances [n])``: rows in the order
+        OPTICS visits them; ``reachability`` / ``predecessor`` / ``core_distances`` are indexed by row (+inf, -1, +inf
+        where undefined)."""
+        k, e = self._optics_args(min_samples, max_eps)
+        ordering = np.empty(self._n, dtype=np.uint64)
+        reach = np.empty(self._n, dtype=self.dtype)
+        pred = np.empty(self._n, dtype=np.int64)
+        core = np.empty(self._n, dtype=self.dtype)
+        check(getattr(_lib.lib(), f"pn_optics_{self._sfx}")(self._h, k, e, 0, ordering.ctypes.data, reach.ctypes.data,
+                                                           pred.ctypes.data, core.ctypes.data))
+        return ordering, reach, pred, core
+
+    def optics_device(self, min_samples: int, max_eps=np.inf, out_ordering=None, out_reachability=None,
+                      out_predecessor=None, out_core=None, stream=None):
+        """``optics`` in HBM: CUDA tensors ``(ordering int64 [n], reachability [n], predecessor int64 [n],
+        core_distances [n])`` written in stream order on ``stream`` (default: the current torch stream).  The call waits
+        for the device once, after the counting pass."""
+        import torch
+        k, e = self._optics_args(min_samples, max_eps)
+        tdt = torch.float32 if self._sfx == "f32" else torch.float64
+        dev = torch.device("cuda", self.device)
+        n = self._n
+        for t, want in ((out_ordering, torch.int64), (out_reachability, tdt), (out_predecessor, torch.int64), (out_core, tdt)):
+            if t is not None and not self._lof_on_device(t, want, n):
+                raise ValueError(f"output tensors must be contiguous CUDA tensors of at least {n} values on the tree's "
+                                 "device (int64; reachability and core distances of the tree's element type)")
+        ordering = out_ordering if out_ordering is not None else torch.empty(n, dtype=torch.int64, device=dev)
+        reach = out_reachability if out_reachability is not None else torch.empty(n, dtype=tdt, device=dev)
+        pred = out_predecessor if out_predecessor is not None else torch.empty(n, dtype=torch.int64, device=dev)
+        core = out_core if out_core is not None else torch.empty(n, dtype=tdt, device=dev)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        check(getattr(_lib.lib(), f"pn_optics_device_{self._sfx}")(
+            self._h, k, e, 0, ordering.data_ptr(), reach.data_ptr(), pred.data_ptr(), core.data_ptr(), C.c_void_p(st)))
+        return ordering, reach, pred, core
+
+    def optics_dbscan(self, eps, ordering, reachability, core_distances):
+        """``(labels int64 [n], n_clusters)``: the DBSCAN labels at ``eps`` (<= the ordering's max_eps) read off
+        ``optics``'s outputs; clusters are numbered by first appearance in the ordering, noise is -1.  An ordering that
+        is no permutation of the rows raises ``PetalError``."""
+        o = np.ascontiguousarray(ordering, dtype=np.uint64)
+        r = np.ascontiguousarray(reachability, dtype=self.dtype)
+        c = np.ascontiguousarray(core_distances, dtype=self.dtype)
+        for a in (o, r, c):
+            if a.ndim != 1 or a.shape[0] != self._n:
+                raise ValueError(f"ordering, reachability and core_distances must hold one value per indexed row ({self._n})")
+        e = C.c_float(eps) if self._sfx == "f32" else C.c_double(eps)
+        labels = np.empty(self._n, dtype=np.int64)
+        ncl = np.zeros(1, dtype=np.uint64)
+        check(getattr(_lib.lib(), f"pn_optics_dbscan_{self._sfx}")(self._h, o.ctypes.data, r.ctypes.data, c.ctypes.data, e, 0,
+                                                                  labels.ctypes.data, ncl.ctypes.data))
+        return labels, int(ncl[0])
+
+    def optics_dbscan_device(self, eps, ordering, reachability, core_distances, out_labels=None, out_n_clusters=None,
+                             out_error=None, stream=None):
+        """``optics_dbscan`` in HBM: the inputs are ``optics_device``'s tensors; returns CUDA tensors ``(labels int64 [n],
+        n_clusters int64 [1], error int32 [1])`` written in stream order on ``stream`` (default: the current torch
+        stream) without waiting for the device.  ``error[0]`` is 0, or ``PN_ERR_INVALID`` when the ordering is no
+        permutation of the rows."""
+        import torch
+        tdt = torch.float32 if self._sfx == "f32" else torch.float64
+        n = self._n
+        for t, want in ((ordering, torch.int64), (reachability, tdt), (core_distances, tdt)):
+            if not self._lof_on_device(t, want, n) or t.dim() != 1 or t.numel() != n:
+                raise ValueError(f"ordering, reachability and core_distances must be contiguous 1-D CUDA tensors of {n} "
+                                 "values on the tree's device (int64, the tree's element type)")
+        for t, want, need in ((out_labels, torch.int64, n), (out_n_clusters, torch.int64, 1), (out_error, torch.int32, 1)):
+            if t is not None and not self._lof_on_device(t, want, need):
+                raise ValueError("output tensors are too small or of the wrong type")
+        dev = torch.device("cuda", self.device)
+        labels = out_labels if out_labels is not None else torch.empty(n, dtype=torch.int64, device=dev)
+        ncl = out_n_clusters if out_n_clusters is not None else torch.zeros(1, dtype=torch.int64, device=dev)
+        err = out_error if out_error is not None else torch.zeros(1, dtype=torch.int32, device=dev)
+        e = C.c_float(eps) if self._sfx == "f32" else C.c_double(eps)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        check(getattr(_lib.lib(), f"pn_optics_dbscan_device_{self._sfx}")(
+            self._h, ordering.data_ptr(), reachability.data_ptr(), core_distances.data_ptr(), e, 0, labels.data_ptr(),
+            ncl.data_ptr(), err.data_ptr(), C.c_void_p(st)))
+        return labels, ncl, err

@@ -158,6 +158,9 @@ struct Workspace {
     // pn_lof_* / pn_lof_score_*: the graph store of a fit ([n][k] uint32 ids, [n][k] distances; + lrd and kdist when the
     // caller keeps neither), and the host entries' inputs and outputs
     DevBuf w_lof, w_lof_io;
+    // pn_optics_* / pn_optics_dbscan_*: the O(n) arrays of a call (offsets, radii, the tournament tree), the graph store
+    // (uint32 ids and distances of every core row's list), and the host entries' inputs and outputs
+    DevBuf w_opt, w_opt_graph, w_opt_io;
     // small calls (tiny_*): mapped pinned host memory the one kernel of the call reads its queries from and writes its
     // answers to -- no copy commands
     void *pin_in = nullptr, *pin_out = nullptr;
@@ -183,7 +186,7 @@ struct Workspace {
     hipEvent_t done = nullptr;
     hipStream_t last_stream = nullptr;
     bool in_flight = false;
-    DevBuf *all[61] = {&w_lof, &w_lof_io, &w_hdb, &w_hdb_io, &w_mst, &w_mst_io, &w_db, &w_db_side, &w_db_out, &w_hrad, &w_sf_idx, &w_sf_dist, &w_sf_off, &w_sf_coff, &w_sf_flag, &w_sf_cnt, &w_sf_scan, &w_sf_hoff, &w_cs_hoff, &w_rkd, &w_cs_nch, &w_cs_off, &w_cs_scan, &w_cs_idx, &w_cs_dist, &w_gqn, &w_rpos, &w_rfin, &w_rcx, &w_rox, &w_rscan, &w_q, &w_qnorm, &w_qnrm, &w_keys, &w_idx, &w_cnt, &w_tau, &w_flags, &w_sel, &w_misc, &w2_keys, &w2_idx,
+    DevBuf *all[64] = {&w_opt, &w_opt_graph, &w_opt_io, &w_lof, &w_lof_io, &w_hdb, &w_hdb_io, &w_mst, &w_mst_io, &w_db, &w_db_side, &w_db_out, &w_hrad, &w_sf_idx, &w_sf_dist, &w_sf_off, &w_sf_coff, &w_sf_flag, &w_sf_cnt, &w_sf_scan, &w_sf_hoff, &w_cs_hoff, &w_rkd, &w_cs_nch, &w_cs_off, &w_cs_scan, &w_cs_idx, &w_cs_dist, &w_gqn, &w_rpos, &w_rfin, &w_rcx, &w_rox, &w_rscan, &w_q, &w_qnorm, &w_qnrm, &w_keys, &w_idx, &w_cnt, &w_tau, &w_flags, &w_sel, &w_misc, &w2_keys, &w2_idx,
                        &w2_cnt, &w2_tau, &w_lo, &w_bq, &w_qn, &w_qbad, &w_gq, &w_gidx, &w_gdist, &w_gsel, &w_seed,
                        &w_qstat, &w_lists, &w_hq, &w_hidx, &w_hdist, &w_fparts, &w_pcnt};
     std::vector<void *> retired;  // outgrown allocations, freed once `done` has passed (DevBuf::ensure)
@@ -252,6 +255,7 @@ struct pn_index {
     int seed_model = 1;      // PN_OPT_SEED_MODEL: 1 (default) use it where it was accepted, 0 never
     uint64_t dbscan_piece = 0;  // PN_OPT_DBSCAN_PIECE: list entries per piece of pn_dbscan_*, 0 = 2^27
     uint64_t mst_batch = 0;     // PN_OPT_MST_BATCH: listed rows per scan launch of pn_mst_*, 0 = 2^18
+    uint64_t optics_piece = 0;  // PN_OPT_OPTICS_PIECE: list entries per fill piece of pn_optics_*, 0 = 2^27
     // state that queries on a shared `const pn_index *` update: internally synchronised by `mu`
     struct Shared {
         std::mutex mu;
@@ -1001,6 +1005,10 @@ extern "C" int pn_index_set_option(pn_index *ix, int option, int64_t value) {
         case PN_OPT_MST_BATCH:
             if (value < 0) return fail(PN_ERR_INVALID, "bad MST batch size");
             ix->mst_batch = (uint64_t)value;
+            return PN_OK;
+        case PN_OPT_OPTICS_PIECE:
+            if (value < 0) return fail(PN_ERR_INVALID, "bad OPTICS piece size");
+            ix->optics_piece = (uint64_t)value;
             return PN_OK;
         default: return fail(PN_ERR_INVALID, "unknown option %d", option);
     }
@@ -3743,6 +3751,264 @@ extern "C" int pn_dbscan_device_f32(const pn_index *ix, float eps, size_t min_sa
 extern "C" int pn_dbscan_device_f64(const pn_index *ix, double eps, size_t min_samples, unsigned flags, int64_t *d_labels,
                                     uint8_t *d_core, uint64_t *d_n_clusters, void *stream) {
     return dbscan_device<double>(ix, eps, min_samples, flags, d_labels, d_core, d_n_clusters, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------
+// OPTICS: pn_optics_{,device_}{f32,f64} and the extraction pn_optics_dbscan_{,device_}{f32,f64} (the kernels, the
+// tournament tree and the argument for schedule independence: optics.hip).
+//   1. cores: the min_samples self-query chunk by chunk; its last column under the '< max_eps' rule gives core[] and the
+//      per-row radii (max_eps for a defined core, 0 otherwise: a row that never relaxes anything stores no list).
+//   2. count: radius_self_enqueue with capacity 0 and those radii gives the graph's offsets.  They are read back -- the one
+//      host wait of a call -- to size the graph store and cut the pieces.
+//   3. fill: a piece is a contiguous row range of at most 2^18 rows whose lists hold at most E entries together
+//      (PN_OPT_OPTICS_PIECE, default 2^27; a longer single row is a piece of its own).  radius_device_enqueue writes the
+//      piece's lists (the rows themselves among them) into workspace scratch; the repack kernel drops each row from its own
+//      list and stores 32-bit ids and distances at the final offsets.
+//   4. order: one launch of one workgroup.
+// Device memory beyond a 2^18-query batch's workspace: E * (4 + sizeof T) + 8 (n + 1) bytes for the graph, (8 + sizeof T)
+// bytes per entry of the largest piece, about 4.1 * sizeof T bytes per row for radii, cores and the tree.
+// ---------------------------------------------------------------------------
+constexpr uint64_t kOpticsPiece = (uint64_t)1 << 27;
+static int optics_args(const pn_index *ix, size_t min_samples, unsigned flags, const void *ordering, const void *reach,
+                       int elem_bytes) {
+    if (flags) return fail(PN_ERR_INVALID, "unknown OPTICS flags 0x%x", flags);
+    if (!ordering) return fail(PN_ERR_INVALID, "ordering is NULL");
+    if (!reach) return fail(PN_ERR_INVALID, "reachability is NULL");
+    if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
+    if (ix->elem_bytes != elem_bytes) return fail(PN_ERR_INVALID, "index element type mismatch");
+    if (ix->n >= 2 && (min_samples < 1 || min_samples > ix->n - 1))
+        return fail(PN_ERR_INVALID, "min_samples must be in [1, n - 1] = [1, %zu]", ix->n - 1);
+    if (ix->n > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many rows for OPTICS (32-bit neighbour ids)");
+    return PN_OK;
+}
+// in a held workspace, on stream s; outputs in HBM (d_pred, d_core nullable); blocks the host once (after the counting pass)
+template <typename T>
+static int optics_enqueue(const pn_index *ix, Workspace &ws, size_t min_samples, T max_eps, uint64_t *d_ordering, T *d_reach,
+                          int64_t *d_pred, T *d_core, hipStream_t s) {
+    const size_t n = ix->n;
+    if (!n) return PN_OK;
+    // one buffer, carved: the tree (16-byte keys in f64) first, then the offsets, then radii and cores
+    const size_t tree_bytes = round_up(optics_tree_bytes(n, (int)sizeof(T)), (size_t)16);
+    PNCHK(ws.w_opt.ensure(tree_bytes + (n + 1) * sizeof(uint64_t) + 2 * n * sizeof(T)));
+    void *tree = ws.w_opt.p;
+    uint64_t *off = (uint64_t *)((char *)ws.w_opt.p + tree_bytes);
+    T *radii = (T *)(off + n + 1);
+    if (!d_core) d_core = radii + n;
+    // ---- 1. core distances and the rows' radii
+    if (n < 2) {
+        if constexpr (sizeof(T) == 4)
+            HIPCHK(launch_optics_core_f32(nullptr, n, 1, max_eps, d_core, radii, s));
+        else
+            HIPCHK(launch_optics_core_f64(nullptr, n, 1, max_eps, d_core, radii, s));
+        std::lock_guard<std::mutex> lk(ix->sh.mu);
+        ix->sh.stats.queries += n;
+    } else {
+        const size_t kout = min_samples, kin = kout + 1;
+        for (size_t r0 = 0; r0 < n; r0 += kSelfChunk) {
+            const size_t nqc = n - r0 < kSelfChunk ? n - r0 : kSelfChunk;
+            PNCHK(ws.w_hidx.ensure(nqc * kout * sizeof(uint64_t)));
+            PNCHK(ws.w_hdist.ensure(nqc * kout * sizeof(T)));
+            PNCHK(self_knn_chunk<T>(ix, ws, r0, nqc, kin, kout, false, (uint64_t *)ws.w_hidx.p, (T *)ws.w_hdist.p, s));
+            if constexpr (sizeof(T) == 4)
+                HIPCHK(launch_optics_core_f32((const T *)ws.w_hdist.p, nqc, kout, max_eps, d_core + r0, radii + r0, s));
+            else
+                HIPCHK(launch_optics_core_f64((const T *)ws.w_hdist.p, nqc, kout, max_eps, d_core + r0, radii + r0, s));
+        }
+    }
+    // ---- 2. count (max_eps <= 0 or NaN, or a single row: every list is empty by definition)
+    uint64_t total = 0;
+    std::vector<uint64_t> h_off;
+    if (n >= 2 && max_eps > (T)0) {
+        PNCHK(radius_self_enqueue<T>(ix, ws, max_eps, 0, off, nullptr, nullptr, 0, nullptr, s, false, radii));
+        try {
+            h_off.resize(n + 1);
+        } catch (const std::bad_alloc &) {
+            return fail(PN_ERR_NOMEM, "host allocation of %zu offsets failed", n + 1);
+        }
+        HIPCHK(hipMemcpyAsync(h_off.data(), off, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        total = h_off[n];
+    } else {
+        HIPCHK(hipMemsetAsync(off, 0, (n + 1) * sizeof(uint64_t), s));
+    }
+    // ---- 3. the graph store, filled piece by piece
+    const size_t ids_bytes = round_up((size_t)(total ? total : 1) * sizeof(uint32_t), (size_t)16);
+    const size_t graph_bytes = ids_bytes + (size_t)(total ? total : 1) * sizeof(T);
+    if (ws.w_opt_graph.ensure(graph_bytes) != PN_OK)
+        return fail(PN_ERR_NOMEM, "the OPTICS graph needs %zu bytes of device memory (%llu entries): lower max_eps",
+                    graph_bytes, (unsigned long long)total);
+    uint32_t *ids = (uint32_t *)ws.w_opt_graph.p;
+    T *dist = (T *)((char *)ws.w_opt_graph.p + ids_bytes);
+    if (total) {
+        const uint64_t E = ix->optics_piece ? ix->optics_piece : kOpticsPiece;
+        PNCHK(ws.w_sf_off.ensure((std::min(n, kSelfChunk) + 1) * sizeof(uint64_t)));
+        uint64_t *in_off = (uint64_t *)ws.w_sf_off.p;
+        for (size_t a = 0; a < n;) {
+            const size_t lim = n - a < kSelfChunk ? n : a + kSelfChunk;
+            // the last b in (a, lim] with off[b] - off[a] <= E, at least a + 1
+            size_t b = (size_t)(std::upper_bound(h_off.begin() + a + 1, h_off.begin() + lim + 1, h_off[a] + E) - h_off.begin()) - 1;
+            if (b <= a) b = a + 1;
+            const uint64_t piece = h_off[b] - h_off[a];
+            if (piece) {
+                const uint64_t in_cap = piece + (b - a);  // (each row may list itself)
+                PNCHK(ws.w_sf_idx.ensure(in_cap * sizeof(uint64_t)));
+                PNCHK(ws.w_sf_dist.ensure(in_cap * sizeof(T)));
+                uint64_t *in_idx = (uint64_t *)ws.w_sf_idx.p;
+                T *in_dist = (T *)ws.w_sf_dist.p;
+                PNCHK(radius_device_enqueue<T>(ix, ws, (const T *)ix->d_pts + a * ix->ld, b - a, ix->dim, ix->ld, max_eps, in_off,
+                                               in_idx, (size_t)in_cap, nullptr, s, in_dist, 0, false, radii + a, false));
+                if constexpr (sizeof(T) == 4)
+                    HIPCHK(launch_optics_repack_f32(in_off, in_idx, in_dist, in_cap, b - a, a, ix->index_base, off, ids, dist, s));
+                else
+                    HIPCHK(launch_optics_repack_f64(in_off, in_idx, in_dist, in_cap, b - a, a, ix->index_base, off, ids, dist, s));
+            }
+            a = b;
+        }
+    }
+    // ---- 4. the ordering
+    if constexpr (sizeof(T) == 4)
+        HIPCHK(launch_optics_order_f32(n, off, ids, dist, total, d_core, tree, d_ordering, d_reach, d_pred, s));
+    else
+        HIPCHK(launch_optics_order_f64(n, off, ids, dist, total, d_core, tree, d_ordering, d_reach, d_pred, s));
+    return PN_OK;
+}
+template <typename T>
+static int optics_device(const pn_index *ix, size_t min_samples, T max_eps, unsigned flags, uint64_t *d_ordering, T *d_reach,
+                         int64_t *d_pred, T *d_core, hipStream_t s) {
+    PNCHK(optics_args(ix, min_samples, flags, d_ordering, d_reach, (int)sizeof(T)));
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    lease.s = s;
+    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
+    return optics_enqueue<T>(ix, *lease.ws, min_samples, max_eps, d_ordering, d_reach, d_pred, d_core, s);
+}
+template <typename T>
+static int optics_host(const pn_index *ix, size_t min_samples, T max_eps, unsigned flags, uint64_t *ordering, T *reach,
+                       int64_t *pred, T *core) {
+    PNCHK(optics_args(ix, min_samples, flags, ordering, reach, (int)sizeof(T)));
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
+    Workspace &ws = *lease.ws;
+    hipStream_t s = lease.s;
+    const size_t n = ix->n;
+    PNCHK(ws.w_opt_io.ensure(2 * n * sizeof(uint64_t) + 2 * n * sizeof(T)));
+    uint64_t *d_ordering = (uint64_t *)ws.w_opt_io.p;
+    int64_t *d_pred = (int64_t *)(d_ordering + n);
+    T *d_reach = (T *)(d_pred + n), *d_core = d_reach + n;
+    PNCHK(optics_enqueue<T>(ix, ws, min_samples, max_eps, d_ordering, d_reach, d_pred, d_core, s));
+    HIPCHK(hipMemcpyAsync(ordering, d_ordering, n * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(reach, d_reach, n * sizeof(T), hipMemcpyDeviceToHost, s));
+    if (pred) HIPCHK(hipMemcpyAsync(pred, d_pred, n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    if (core) HIPCHK(hipMemcpyAsync(core, d_core, n * sizeof(T), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return PN_OK;
+}
+extern "C" int pn_optics_f32(const pn_index *ix, size_t min_samples, float max_eps, unsigned flags, uint64_t *ordering,
+                             float *reachability, int64_t *predecessor, float *core_distances) {
+    return optics_host<float>(ix, min_samples, max_eps, flags, ordering, reachability, predecessor, core_distances);
+}
+extern "C" int pn_optics_f64(const pn_index *ix, size_t min_samples, double max_eps, unsigned flags, uint64_t *ordering,
+                             double *reachability, int64_t *predecessor, double *core_distances) {
+    return optics_host<double>(ix, min_samples, max_eps, flags, ordering, reachability, predecessor, core_distances);
+}
+extern "C" int pn_optics_device_f32(const pn_index *ix, size_t min_samples, float max_eps, unsigned flags, uint64_t *d_ordering,
+                                    float *d_reachability, int64_t *d_predecessor, float *d_core_distances, void *stream) {
+    return optics_device<float>(ix, min_samples, max_eps, flags, d_ordering, d_reachability, d_predecessor, d_core_distances,
+                                (hipStream_t)stream);
+}
+extern "C" int pn_optics_device_f64(const pn_index *ix, size_t min_samples, double max_eps, unsigned flags, uint64_t *d_ordering,
+                                    double *d_reachability, int64_t *d_predecessor, double *d_core_distances, void *stream) {
+    return optics_device<double>(ix, min_samples, max_eps, flags, d_ordering, d_reachability, d_predecessor, d_core_distances,
+                                 (hipStream_t)stream);
+}
+
+static int optics_dbscan_args(const pn_index *ix, const void *ordering, const void *reach, const void *core, unsigned flags,
+                              const void *labels, int elem_bytes) {
+    if (flags) return fail(PN_ERR_INVALID, "unknown OPTICS flags 0x%x", flags);
+    if (!labels) return fail(PN_ERR_INVALID, "labels is NULL");
+    if (!ordering || !reach || !core)
+        return fail(PN_ERR_INVALID, "%s is NULL", !ordering ? "ordering" : !reach ? "reachability" : "core_distances");
+    if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
+    if (ix->elem_bytes != elem_bytes) return fail(PN_ERR_INVALID, "index element type mismatch");
+    if (ix->n > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many rows for OPTICS (32-bit counters)");
+    return PN_OK;
+}
+template <typename T>
+static int optics_dbscan_enqueue(const pn_index *ix, Workspace &ws, const uint64_t *d_ordering, const T *d_reach, const T *d_core,
+                                 T eps, int64_t *d_labels, uint64_t *d_ncl, int32_t *d_err, hipStream_t s) {
+    const size_t n = ix->n;
+    if (!n) return PN_OK;
+    PNCHK(ws.w_opt.ensure(optics_extract_bytes(n)));
+    if constexpr (sizeof(T) == 4)
+        HIPCHK(launch_optics_extract_f32(d_ordering, d_reach, d_core, n, eps, ws.w_opt.p, d_labels, d_ncl, d_err, s));
+    else
+        HIPCHK(launch_optics_extract_f64(d_ordering, d_reach, d_core, n, eps, ws.w_opt.p, d_labels, d_ncl, d_err, s));
+    return PN_OK;
+}
+template <typename T>
+static int optics_dbscan_device(const pn_index *ix, const uint64_t *d_ordering, const T *d_reach, const T *d_core, T eps,
+                                unsigned flags, int64_t *d_labels, uint64_t *d_ncl, int32_t *d_err, hipStream_t s) {
+    PNCHK(optics_dbscan_args(ix, d_ordering, d_reach, d_core, flags, d_labels, (int)sizeof(T)));
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    lease.s = s;
+    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
+    return optics_dbscan_enqueue<T>(ix, *lease.ws, d_ordering, d_reach, d_core, eps, d_labels, d_ncl, d_err, s);
+}
+template <typename T>
+static int optics_dbscan_host(const pn_index *ix, const uint64_t *ordering, const T *reach, const T *core, T eps, unsigned flags,
+                              int64_t *labels, uint64_t *n_clusters) {
+    PNCHK(optics_dbscan_args(ix, ordering, reach, core, flags, labels, (int)sizeof(T)));
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
+    Workspace &ws = *lease.ws;
+    hipStream_t s = lease.s;
+    const size_t n = ix->n;
+    PNCHK(ws.w_opt_io.ensure((2 * n + 2) * sizeof(uint64_t) + 2 * n * sizeof(T)));
+    uint64_t *d_ordering = (uint64_t *)ws.w_opt_io.p;
+    int64_t *d_labels = (int64_t *)(d_ordering + n);
+    uint64_t *d_ncl = (uint64_t *)(d_labels + n);
+    int32_t *d_err = (int32_t *)(d_ncl + 1);
+    T *d_reach = (T *)(d_ncl + 2), *d_core = d_reach + n;
+    HIPCHK(hipMemcpyAsync(d_ordering, ordering, n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_reach, reach, n * sizeof(T), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_core, core, n * sizeof(T), hipMemcpyHostToDevice, s));
+    PNCHK(optics_dbscan_enqueue<T>(ix, ws, d_ordering, d_reach, d_core, eps, d_labels, d_ncl, d_err, s));
+    int32_t err = PN_OK;
+    HIPCHK(hipMemcpyAsync(&err, d_err, sizeof err, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(labels, d_labels, n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    if (n_clusters) HIPCHK(hipMemcpyAsync(n_clusters, d_ncl, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (err != PN_OK) return fail(PN_ERR_INVALID, "ordering is not a permutation of the rows 0 .. n - 1");
+    return PN_OK;
+}
+extern "C" int pn_optics_dbscan_f32(const pn_index *ix, const uint64_t *ordering, const float *reachability,
+                                    const float *core_distances, float eps, unsigned flags, int64_t *labels,
+                                    uint64_t *n_clusters) {
+    return optics_dbscan_host<float>(ix, ordering, reachability, core_distances, eps, flags, labels, n_clusters);
+}
+extern "C" int pn_optics_dbscan_f64(const pn_index *ix, const uint64_t *ordering, const double *reachability,
+                                    const double *core_distances, double eps, unsigned flags, int64_t *labels,
+                                    uint64_t *n_clusters) {
+    return optics_dbscan_host<double>(ix, ordering, reachability, core_distances, eps, flags, labels, n_clusters);
+}
+extern "C" int pn_optics_dbscan_device_f32(const pn_index *ix, const uint64_t *d_ordering, const float *d_reachability,
+                                           const float *d_core_distances, float eps, unsigned flags, int64_t *d_labels,
+                                           uint64_t *d_n_clusters, int32_t *d_error, void *stream) {
+    return optics_dbscan_device<float>(ix, d_ordering, d_reachability, d_core_distances, eps, flags, d_labels, d_n_clusters,
+                                       d_error, (hipStream_t)stream);
+}
+extern "C" int pn_optics_dbscan_device_f64(const pn_index *ix, const uint64_t *d_ordering, const double *d_reachability,
+                                           const double *d_core_distances, double eps, unsigned flags, int64_t *d_labels,
+                                           uint64_t *d_n_clusters, int32_t *d_error, void *stream) {
+    return optics_dbscan_device<double>(ix, d_ordering, d_reachability, d_core_distances, eps, flags, d_labels, d_n_clusters,
+                                        d_error, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------

@@ -253,6 +253,39 @@ hipError_t launch_lof_score_f32(const uint64_t *q_idx, const float *q_dist, size
 hipError_t launch_lof_score_f64(const uint64_t *q_idx, const double *q_dist, size_t nq, int k, uint64_t index_base, size_t n,
                                 const double *lrd, const double *kdist, double *score, hipStream_t s);
 
+// ---- optics.hip: OPTICS over the max_eps self-graph (pn_optics_*) and the extraction at one eps (pn_optics_dbscan_*);
+// nothing in it waits for the device.
+// core[i] <- v < max_eps ? v : +inf, v = in_dist[i][k - 1] of a self-query chunk's answer [nq][k] (in_dist == nullptr: +inf);
+// radii[i] <- max_eps where core[i] is finite, else 0 (the row's list stays empty)
+hipError_t launch_optics_core_f32(const float *in_dist, size_t nq, size_t k, float max_eps, float *core, float *radii,
+                                  hipStream_t s);
+hipError_t launch_optics_core_f64(const double *in_dist, size_t nq, size_t k, double max_eps, double *core, double *radii,
+                                  hipStream_t s);
+// a fill piece's lists (rows [row0, row0 + rows), piece-local offsets in_off, 64-bit ids with the index base, the rows
+// themselves among them; entries below in_cap are there) -> the graph store at the final offsets off[row0 ..]: uint32 ids
+// without the base, the row itself dropped
+hipError_t launch_optics_repack_f32(const uint64_t *in_off, const uint64_t *in_idx, const float *in_dist, uint64_t in_cap,
+                                    size_t rows, size_t row0, uint64_t index_base, const uint64_t *off, uint32_t *ids,
+                                    float *dist, hipStream_t s);
+hipError_t launch_optics_repack_f64(const uint64_t *in_off, const uint64_t *in_idx, const double *in_dist, uint64_t in_cap,
+                                    size_t rows, size_t row0, uint64_t index_base, const uint64_t *off, uint32_t *ids,
+                                    double *dist, hipStream_t s);
+// the ordering: one workgroup runs the n steps.  tree: optics_tree_bytes(n, sizeof T) bytes, 16-byte aligned; pred nullable
+size_t optics_tree_bytes(size_t n, int elem_bytes);
+hipError_t launch_optics_order_f32(size_t n, const uint64_t *off, const uint32_t *ids, const float *dist, uint64_t n_entries,
+                                   const float *core, void *tree, uint64_t *ordering, float *reach, int64_t *pred,
+                                   hipStream_t s);
+hipError_t launch_optics_order_f64(size_t n, const uint64_t *off, const uint32_t *ids, const double *dist, uint64_t n_entries,
+                                   const double *core, void *tree, uint64_t *ordering, double *reach, int64_t *pred,
+                                   hipStream_t s);
+// labels of the DBSCAN clustering at eps from an ordering; buf: optics_extract_bytes(n) bytes; n_clusters, d_error nullable
+// (*d_error <- PN_OK, or PN_ERR_INVALID when ordering is no permutation of 0 .. n - 1: the labels are then unspecified)
+size_t optics_extract_bytes(size_t n);
+hipError_t launch_optics_extract_f32(const uint64_t *ordering, const float *reach, const float *core, size_t n, float eps,
+                                     void *buf, int64_t *labels, uint64_t *n_clusters, int32_t *d_error, hipStream_t s);
+hipError_t launch_optics_extract_f64(const uint64_t *ordering, const double *reach, const double *core, size_t n, double eps,
+                                     void *buf, int64_t *labels, uint64_t *n_clusters, int32_t *d_error, hipStream_t s);
+
 // ---- csr_sort.hip: order every list of a radius answer by (distance, index) in place (PN_RADIUS_SORTED)
 constexpr int kSortTile = 2048;  // longest list sorted by one workgroup in LDS; longer lists: chunks + merge passes
 struct CsrSortScratch {
