@@ -27,6 +27,20 @@ def test_random_sharded_handles_match_the_oracle(pn, oracle_mod, seed):
         assert fuzz_sharded.run_case(100 * seed + c, rng)
 
 
+_GRAPH_REDRAWS = []
+
+
+@pytest.mark.parametrize("seed", [41, 42])
+def test_random_graph_calls_on_one_handle(pn, oracle_mod, seed):
+    """tests/fuzz_graph.py: every graph entry point on one handle against one dense want side, two passes with the options
+    and parameters changed in between; n from 1 to 4500, D from 1 to 200, f32 / f64, Euclidean / Cosine, five families."""
+    import fuzz_graph
+    rng = np.random.default_rng(seed)
+    for params in [fuzz_graph.draw_params(100 * seed + c, rng) for c in range(5)]:  # (the shapes do not depend on the calls)
+        _GRAPH_REDRAWS.append(fuzz_graph.run_case(params, rng) > 0)
+    assert sum(_GRAPH_REDRAWS) <= 1  # at most one of the ten cases of the two seeds redrew its data
+
+
 @pytest.mark.parametrize("seed", [31])
 def test_random_large_indexes_with_the_seed_model(pn, oracle_mod, seed):
     """tests/fuzz_seed_model.py: 10^5 .. 6 10^5 rows (where the seed model is fitted), ten data families, four kinds of
