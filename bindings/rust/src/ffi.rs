@@ -6,6 +6,12 @@ use std::os::raw::{c_char, c_int, c_uint, c_void};
 /// `flags` of the radius calls with distances: each list by (distance, index) ascending
 pub const PN_RADIUS_SORTED: c_uint = 1;
 pub const PN_SELF_INCLUDE: c_uint = 2;
+/// `kernel` of the pn_kde_* calls
+pub const PN_KDE_GAUSSIAN: c_int = 0;
+pub const PN_KDE_TOPHAT: c_int = 1;
+pub const PN_KDE_EPANECHNIKOV: c_int = 2;
+pub const PN_KDE_EXPONENTIAL: c_int = 3;
+pub const PN_KDE_LINEAR: c_int = 4;
 
 #[repr(C)]
 pub struct pn_index {
@@ -198,6 +204,32 @@ extern "C" {
     pub fn pn_optics_dbscan_device_f64(index: *const pn_index, d_ordering: *const u64, d_reachability: *const f64,
                                        d_core_distances: *const f64, eps: f64, flags: c_uint, d_labels: *mut i64,
                                        d_n_clusters: *mut u64, d_error: *mut i32, stream: *mut c_void) -> c_int;
+    /// kernel density sums: per query the raw sum of `kernel` (PN_KDE_*) over the rows within the kernel's cutoff, the
+    /// number of terms and the cutoff; h: n_h = 1 or one bandwidth per query; sum nullable if count is given (then only
+    /// the counting pass runs); flags = 0 (self entries: PN_SELF_INCLUDE or 0).  The device entry points write in stream
+    /// order and block the host once when a sum is asked for
+    pub fn pn_kde_f32(index: *const pn_index, queries: *const f32, nq: usize, q_cols: usize, q_row_stride: isize,
+                      h: *const f32, n_h: usize, kernel: c_int, atol: f64, flags: c_uint, sum_out: *mut f64,
+                      count_out: *mut u64, cutoff_out: *mut f32) -> c_int;
+    pub fn pn_kde_device_f32(index: *const pn_index, d_queries: *const f32, nq: usize, q_cols: usize, q_row_stride: usize,
+                             d_h: *const f32, n_h: usize, kernel: c_int, atol: f64, flags: c_uint, d_sum: *mut f64,
+                             d_count: *mut u64, d_cutoff: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn pn_kde_self_f32(index: *const pn_index, h: *const f32, n_h: usize, kernel: c_int, atol: f64, flags: c_uint,
+                           sum_out: *mut f64, count_out: *mut u64, cutoff_out: *mut f32) -> c_int;
+    pub fn pn_kde_self_device_f32(index: *const pn_index, d_h: *const f32, n_h: usize, kernel: c_int, atol: f64,
+                                  flags: c_uint, d_sum: *mut f64, d_count: *mut u64, d_cutoff: *mut f32,
+                                  stream: *mut c_void) -> c_int;
+    pub fn pn_kde_f64(index: *const pn_index, queries: *const f64, nq: usize, q_cols: usize, q_row_stride: isize,
+                      h: *const f64, n_h: usize, kernel: c_int, atol: f64, flags: c_uint, sum_out: *mut f64,
+                      count_out: *mut u64, cutoff_out: *mut f64) -> c_int;
+    pub fn pn_kde_device_f64(index: *const pn_index, d_queries: *const f64, nq: usize, q_cols: usize, q_row_stride: usize,
+                             d_h: *const f64, n_h: usize, kernel: c_int, atol: f64, flags: c_uint, d_sum: *mut f64,
+                             d_count: *mut u64, d_cutoff: *mut f64, stream: *mut c_void) -> c_int;
+    pub fn pn_kde_self_f64(index: *const pn_index, h: *const f64, n_h: usize, kernel: c_int, atol: f64, flags: c_uint,
+                           sum_out: *mut f64, count_out: *mut u64, cutoff_out: *mut f64) -> c_int;
+    pub fn pn_kde_self_device_f64(index: *const pn_index, d_h: *const f64, n_h: usize, kernel: c_int, atol: f64,
+                                  flags: c_uint, d_sum: *mut f64, d_count: *mut u64, d_cutoff: *mut f64,
+                                  stream: *mut c_void) -> c_int;
     /// dist_out nullable (PN_RADIUS_SORTED needs it); *idx_out / *dist_out released with pn_free
     pub fn pn_query_radius_self_f32(index: *const pn_index, radius: f32, flags: c_uint, offsets: *mut u64,
                                     idx_out: *mut *mut u64, dist_out: *mut *mut f32) -> c_int;

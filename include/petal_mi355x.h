@@ -63,7 +63,7 @@ extern "C" {
  * pn_dbscan_{,device_}{f32,f64}, PN_OPT_DBSCAN_PIECE; pn_mst_{,device_}{f32,f64}, PN_OPT_MST_BATCH;
  * pn_linkage_{,device_}{f32,f64}, pn_hdbscan_{,device_}{f32,f64}; pn_lof_{,device_}{f32,f64},
  * pn_lof_score_{,device_}{f32,f64}; pn_optics_{,device_}{f32,f64}, pn_optics_dbscan_{,device_}{f32,f64},
- * PN_OPT_OPTICS_PIECE. */
+ * PN_OPT_OPTICS_PIECE; pn_kde_{,device_,self_,self_device_}{f32,f64}, PN_KDE_*, PN_OPT_KDE_PIECE. */
 #define PN_ABI_VERSION 3
 
 /* ---- error codes.  EMPTY / NOT_CONTIGUOUS are ArrayError (src/lib.rs:9-16). */
@@ -121,10 +121,23 @@ enum {
     PN_OPT_MST_BATCH = 12,       /* pn_mst_*: the most listed rows one scan launch takes; 0 (default) = 2^18, the
                                   self-queries' chunk; negative: PN_ERR_INVALID.  Never changes a result (it lets tests
                                   force several launches per round at small n). */
-    PN_OPT_OPTICS_PIECE = 13     /* pn_optics_*: the most list entries one piece of the graph fill holds in workspace
+    PN_OPT_OPTICS_PIECE = 13,    /* pn_optics_*: the most list entries one piece of the graph fill holds in workspace
                                   scratch before it is packed into the graph store; 0 (default) = 2^27; negative:
                                   PN_ERR_INVALID.  A row whose own list is longer is a piece of its own.  Never changes a
                                   result (it lets tests force several pieces at small n). */
+    PN_OPT_KDE_PIECE = 14        /* pn_kde_*: the most list entries (a 64-bit index and a distance each, in workspace
+                                  scratch) one piece of the sum stage holds; 0 (default) = 2^27; negative: PN_ERR_INVALID.
+                                  A query whose own list is longer is a piece of its own.  Never changes a result. */
+};
+
+/* kernels of pn_kde_* (scikit-learn's names; its sixth, `cosine`, is left out: the name collides with the Cosine metric
+ * and its normaliser is an alternating series that cancels to a negative number at D = 16) */
+enum {
+    PN_KDE_GAUSSIAN = 0,
+    PN_KDE_TOPHAT = 1,
+    PN_KDE_EPANECHNIKOV = 2,
+    PN_KDE_EXPONENTIAL = 3,
+    PN_KDE_LINEAR = 4
 };
 
 typedef struct pn_index pn_index;
@@ -642,6 +655,78 @@ int pn_optics_dbscan_device_f32(const pn_index *index, const uint64_t *d_orderin
 int pn_optics_dbscan_device_f64(const pn_index *index, const uint64_t *d_ordering, const double *d_reachability,
                                 const double *d_core_distances, double eps, unsigned flags, int64_t *d_labels,
                                 uint64_t *d_n_clusters, int32_t *d_error, void *stream);
+
+/* ---- Kernel density sums on the device (the engine of scikit-learn's neighbors.KernelDensity and of
+ * BallTree.kernel_density; with count alone: query_radius(count_only = True)): per query the raw, unnormalised sum of
+ * the kernel over the rows within a cutoff, the number of such rows, and the cutoff.  The cutoff kernel -> a counting
+ * pass of the per-query-radius pipeline -> the lists with distances piece by piece into workspace scratch -> one wave
+ * per query sums its list.  Nothing leaves HBM but the outputs; normalisation and logarithms are the callers'.
+ * h: the bandwidths, in the index's element type T; n_h = 1 (one for all queries) or the number of queries / rows (one
+ * each: the balloon estimator).  kernel: PN_KDE_*.  atol: a double, finite and >= 0, the absolute error the two smooth
+ * kernels may trade for a finite cutoff; the three compact kernels ignore it.  The contract:
+ *   Cutoff c_q (T) of query q with bandwidth h_q:
+ *     tophat, epanechnikov, linear: c_q = h_q.
+ *     gaussian, exponential: with n = the number of indexed rows, on the host in f64
+ *       L = log((double)n / atol);  f = (gaussian ? sqrt(2.0 * L) : L) * (1.0 + 2^-30)       (libm log, IEEE sqrt)
+ *     and per query x = (double)h_q * f (one f64 product), c_q = (T)x rounded to nearest, then the next T towards +inf
+ *     if (double)c_q < x: the smallest T >= x.  So c_q >= h_q sqrt(2 ln(n / atol)) resp. h_q ln(n / atol), and exceeds
+ *     it by less than a factor (1 + 2^-30)(1 + 2^-23) (f32; f64: (1 + 2^-30)(1 + 2^-52)); the safety factor 2^-30 covers the
+ *     rounding of log, sqrt and the product.
+ *     atol >= n: c_q = 0, the list is empty.  atol == 0: c_q = +inf, every row with a non-NaN distance is a term.
+ *     A bandwidth in an array that is not positive, or NaN, is its own cutoff: such a radius gives an empty list.
+ *   List L_q = what pn_query_radii_with_distance_* returns for q with radius c_q and flags 0: the rows with
+ *     distance < c_q (strict), in ascending row index, the distances bit-identical to the reference metric; a row whose
+ *     distance is NaN is in no list.  Self entries: the list of pn_query_radii_self_* with the same flags -- by default the
+ *     row itself is left out (the leave-one-out density), PN_SELF_INCLUDE keeps it.
+ *   Terms, in IEEE f64, unfused, operations in the order written, d = max((double)dist, +0.0) (the clamp pn_lof_* uses: a
+ *     Cosine distance can be a few ulp below 0) and h = (double)h_q:
+ *       tophat 1.0;  epanechnikov 1.0 - (d*d) / (h*h);  linear 1.0 - d / h;
+ *       gaussian exp(-((d*d) / (2.0 * (h*h))));  exponential exp(-(d / h))     (exp: the device library's f64 exp)
+ *   Sum, fixed shape: with the terms t_0 .. t_{m-1} in list order,
+ *       lane partial P_l = (...((0.0 + t_l) + t_{l+64}) + t_{l+128} ...) for l = 0 .. 63 (missing positions add nothing),
+ *       S = (...((P_0 + P_1) + P_2) ... + P_63).
+ *     The shape depends on m alone: one wave per query, no floating-point atomics, no reduction whose shape depends on
+ *     the launch -- the result depends on the data alone, not on the engine, PN_OPT_KDE_PIECE or scheduling.
+ *   Guarantee: with S_all the same sum over every row (the atol = 0 result), S_all - atol <= S <= S_all up to the rounding
+ *     of the sums: a row left out has d >= c_q, so its term is at most atol / n.
+ * Outputs, per query: sum (f64; nullable only if count is given -- then only the counting pass runs and no list is ever
+ * written), count (uint64, nullable: m), cutoff (T, nullable: c_q).
+ * Euclidean and Cosine indexes, f32 and f64.  PN_OPT_INDEX_BASE affects no output.  A query with a NaN coordinate has an
+ * empty list: sum 0, count 0.  pn_stats.queries advances by nq (n for the self entries).
+ * flags: 0 for the query entries; PN_SELF_INCLUDE or 0 for the self entries.  Argument errors, before any device is
+ * touched and in this order: unknown flags; unknown kernel; atol negative, NaN or infinite; sum and count both NULL;
+ * with nq > 0 NULL queries (q_cols > 0) or NULL h (self entries: NULL h); n_h neither 1 nor nq; NULL index; wrong element
+ * type: PN_ERR_INVALID; more than 2^31 - 1 rows or queries: PN_ERR_UNSUPPORTED.  The self entries compare n_h with n
+ * after the handle's checks.  Host entries with n_h = 1: a bandwidth that is not finite and positive is PN_ERR_INVALID,
+ * checked last.  nq = 0 writes nothing and succeeds.
+ * Device entry points: queries, h and the outputs in HBM, written in stream order on `stream`; with a sum the call BLOCKS
+ * THE HOST ONCE, after the counting pass, to read the nq + 1 offsets it cuts the pieces from -- like pn_dbscan_device_* it
+ * is not capturable into a graph.  Without a sum nothing waits.
+ * Device memory beyond a 2^18-query batch's workspace: 16 + 2 sizeof T bytes per query, and 8 + sizeof T bytes per entry
+ * of the largest piece (at most 2^18 queries and PN_OPT_KDE_PIECE entries; a longer single list is a piece of its own).
+ * Known slow case: with atol = 0 the two smooth kernels list every row for every query; all queries then go through the
+ * exact scan and n entries each are written and read back -- the price of an exact infinite-support sum.
+ * Not in this version: row-sharded handles, scikit-learn's `cosine` kernel, rtol. */
+int pn_kde_f32(const pn_index *index, const float *queries, size_t nq, size_t q_cols, ptrdiff_t q_row_stride,
+               const float *h, size_t n_h, int kernel, double atol, unsigned flags, double *sum_out, uint64_t *count_out,
+               float *cutoff_out);
+int pn_kde_f64(const pn_index *index, const double *queries, size_t nq, size_t q_cols, ptrdiff_t q_row_stride,
+               const double *h, size_t n_h, int kernel, double atol, unsigned flags, double *sum_out, uint64_t *count_out,
+               double *cutoff_out);
+int pn_kde_device_f32(const pn_index *index, const float *d_queries, size_t nq, size_t q_cols, size_t q_row_stride,
+                      const float *d_h, size_t n_h, int kernel, double atol, unsigned flags, double *d_sum,
+                      uint64_t *d_count, float *d_cutoff, void *stream);
+int pn_kde_device_f64(const pn_index *index, const double *d_queries, size_t nq, size_t q_cols, size_t q_row_stride,
+                      const double *d_h, size_t n_h, int kernel, double atol, unsigned flags, double *d_sum,
+                      uint64_t *d_count, double *d_cutoff, void *stream);
+int pn_kde_self_f32(const pn_index *index, const float *h, size_t n_h, int kernel, double atol, unsigned flags,
+                    double *sum_out, uint64_t *count_out, float *cutoff_out);
+int pn_kde_self_f64(const pn_index *index, const double *h, size_t n_h, int kernel, double atol, unsigned flags,
+                    double *sum_out, uint64_t *count_out, double *cutoff_out);
+int pn_kde_self_device_f32(const pn_index *index, const float *d_h, size_t n_h, int kernel, double atol, unsigned flags,
+                           double *d_sum, uint64_t *d_count, float *d_cutoff, void *stream);
+int pn_kde_self_device_f64(const pn_index *index, const double *d_h, size_t n_h, int kernel, double atol, unsigned flags,
+                           double *d_sum, uint64_t *d_count, double *d_cutoff, void *stream);
 
 /* ---- distance::pairwise(x, &Euclidean) (src/distance.rs:58-74): n x n
  * symmetric matrix, zero diagonal, n < 2 -> zeros. Host in, host out. */

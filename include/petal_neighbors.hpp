@@ -117,6 +117,14 @@ struct Lof {
     std::vector<double> lof, lrd;
     std::vector<A> kdist;
 };
+// the answer of BallTree::kernel_density: per query the raw kernel sum (not normalised), the number of terms and the
+// cutoff radius the terms were taken within
+template <typename A>
+struct Kde {
+    std::vector<double> sum;
+    std::vector<size_t> count;
+    std::vector<A> cutoff;
+};
 // the answer of BallTree::optics: ordering[t] = the t-th row OPTICS visits (a plain row number); reachability, predecessor
 // (-1 = none) and core_distances are indexed by row, +inf where undefined
 template <typename A>
@@ -415,6 +423,54 @@ class BallTree {
         else
             check(pn_lof_score_f64(h_, queries, nq, dim_, (ptrdiff_t)dim_, k, fit.lrd.data(), fit.kdist.data(), 0u, out));
         return score;
+    }
+    // extension: kernel density sums on the device (pn_kde_*): per query the raw sum of `kernel` (PN_KDE_*) with bandwidth
+    // h over the rows within the kernel's cutoff, in a fixed order; atol lets the two smooth kernels stop at a finite
+    // cutoff (sum_all - atol <= sum <= sum_all), atol = 0 visits every row.  Normalisation is the caller's
+    Kde<A> kernel_density(const A *queries, size_t nq, A h, int kernel = PN_KDE_GAUSSIAN, double atol = 0.0) const {
+        return kernel_density(queries, nq, &h, 1, kernel, atol);
+    }
+    // ... with one bandwidth per query (n_h = nq; the balloon estimator) or one for all (n_h = 1)
+    Kde<A> kernel_density(const A *queries, size_t nq, const A *h, size_t n_h, int kernel = PN_KDE_GAUSSIAN,
+                          double atol = 0.0) const {
+        Kde<A> res;
+        res.sum.resize(nq);
+        res.cutoff.resize(nq);
+        std::vector<uint64_t> cnt(nq);
+        double none = 0.0;  // (nq = 0: the library still wants an address)
+        double *out = nq ? res.sum.data() : &none;
+        if constexpr (kF32)
+            check(pn_kde_f32(h_, queries, nq, dim_, (ptrdiff_t)dim_, h, n_h, kernel, atol, 0u, out, cnt.data(), res.cutoff.data()));
+        else
+            check(pn_kde_f64(h_, queries, nq, dim_, (ptrdiff_t)dim_, h, n_h, kernel, atol, 0u, out, cnt.data(), res.cutoff.data()));
+        res.count.assign(cnt.begin(), cnt.end());
+        return res;
+    }
+    // extension: the same for the indexed rows themselves (pn_kde_self_*); by default each row is left out of its own sum
+    // (the leave-one-out density)
+    Kde<A> kernel_density_self(A h, int kernel = PN_KDE_GAUSSIAN, double atol = 0.0, bool include_self = false) const {
+        Kde<A> res;
+        res.sum.resize(n_);
+        res.cutoff.resize(n_);
+        std::vector<uint64_t> cnt(n_);
+        const unsigned flags = include_self ? PN_SELF_INCLUDE : 0u;
+        if constexpr (kF32)
+            check(pn_kde_self_f32(h_, &h, 1, kernel, atol, flags, res.sum.data(), cnt.data(), res.cutoff.data()));
+        else
+            check(pn_kde_self_f64(h_, &h, 1, kernel, atol, flags, res.sum.data(), cnt.data(), res.cutoff.data()));
+        res.count.assign(cnt.begin(), cnt.end());
+        return res;
+    }
+    // extension: the number of rows with distance < r (strict) per query; only the counting pass runs, no list is written
+    std::vector<size_t> query_radius_count(const A *queries, size_t nq, A r) const {
+        std::vector<uint64_t> cnt(nq);
+        uint64_t none = 0;
+        uint64_t *out = nq ? cnt.data() : &none;
+        if constexpr (kF32)
+            check(pn_kde_f32(h_, queries, nq, dim_, (ptrdiff_t)dim_, &r, 1, PN_KDE_TOPHAT, 0.0, 0u, nullptr, out, nullptr));
+        else
+            check(pn_kde_f64(h_, queries, nq, dim_, (ptrdiff_t)dim_, &r, 1, PN_KDE_TOPHAT, 0.0, 0u, nullptr, out, nullptr));
+        return std::vector<size_t>(cnt.begin(), cnt.end());
     }
     // extension: OPTICS on the device (pn_optics_*): scikit-learn's OPTICS(min_samples + 1, max_eps) on this library's
     // distances; min_samples counts OTHER rows, every radius is a strict '<'

@@ -25,6 +25,8 @@ PN_OPT_SEED_MODEL = 10
 PN_OPT_DBSCAN_PIECE = 11
 PN_OPT_MST_BATCH = 12
 PN_OPT_OPTICS_PIECE = 13
+PN_OPT_KDE_PIECE = 14
+PN_KDE_GAUSSIAN, PN_KDE_TOPHAT, PN_KDE_EPANECHNIKOV, PN_KDE_EXPONENTIAL, PN_KDE_LINEAR = 0, 1, 2, 3, 4
 PN_RADIUS_SORTED = 1
 PN_SELF_INCLUDE = 2
 
@@ -128,6 +130,14 @@ SIGNATURES = {
     "pn_lof_score_f64": (_i, [_vp, _vp, _sz, _sz, _ssz, _sz, _vp, _vp, C.c_uint, _vp]),
     "pn_lof_score_device_f32": (_i, [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, C.c_uint, _vp, _vp]),
     "pn_lof_score_device_f64": (_i, [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, C.c_uint, _vp, _vp]),
+    "pn_kde_f32": (_i, [_vp, _vp, _sz, _sz, _ssz, _vp, _sz, C.c_int, C.c_double, C.c_uint, _vp, _vp, _vp]),
+    "pn_kde_f64": (_i, [_vp, _vp, _sz, _sz, _ssz, _vp, _sz, C.c_int, C.c_double, C.c_uint, _vp, _vp, _vp]),
+    "pn_kde_device_f32": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _sz, C.c_int, C.c_double, C.c_uint, _vp, _vp, _vp, _vp]),
+    "pn_kde_device_f64": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _sz, C.c_int, C.c_double, C.c_uint, _vp, _vp, _vp, _vp]),
+    "pn_kde_self_f32": (_i, [_vp, _vp, _sz, C.c_int, C.c_double, C.c_uint, _vp, _vp, _vp]),
+    "pn_kde_self_f64": (_i, [_vp, _vp, _sz, C.c_int, C.c_double, C.c_uint, _vp, _vp, _vp]),
+    "pn_kde_self_device_f32": (_i, [_vp, _vp, _sz, C.c_int, C.c_double, C.c_uint, _vp, _vp, _vp, _vp]),
+    "pn_kde_self_device_f64": (_i, [_vp, _vp, _sz, C.c_int, C.c_double, C.c_uint, _vp, _vp, _vp, _vp]),
     "pn_optics_f32": (_i, [_vp, _sz, C.c_float, C.c_uint, _vp, _vp, _vp, _vp]),
     "pn_optics_f64": (_i, [_vp, _sz, C.c_double, C.c_uint, _vp, _vp, _vp, _vp]),
     "pn_optics_device_f32": (_i, [_vp, _sz, C.c_float, C.c_uint, _vp, _vp, _vp, _vp, _vp]),

@@ -12,6 +12,7 @@ point per call (src/ball_tree.rs:102); ``nq = 1`` is that call.
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -28,6 +29,39 @@ def _float_array(a):
     if a.dtype not in (np.float32, np.float64):  # `A: FloatCore` is f32 or f64 in practice
         a = a.astype(np.float64)
     return a
+
+
+KDE_KERNELS = {"gaussian": _lib.PN_KDE_GAUSSIAN, "tophat": _lib.PN_KDE_TOPHAT, "epanechnikov": _lib.PN_KDE_EPANECHNIKOV,
+               "exponential": _lib.PN_KDE_EXPONENTIAL, "linear": _lib.PN_KDE_LINEAR}
+
+
+def _log_vn(d):
+    """log of the volume of the unit ball in ``d`` dimensions"""
+    return 0.5 * d * math.log(math.pi) - math.lgamma(0.5 * d + 1.0)
+
+
+def _log_sn(d):
+    """log of the surface of the unit sphere in ``d + 1`` dimensions"""
+    return math.log(2.0 * math.pi) + _log_vn(d - 1)
+
+
+def kde_log_norm(kernel: str, dim: int, h):
+    """log of the normaliser of ``kernel`` with bandwidth ``h`` (scalar or array) in ``dim`` dimensions: the density is
+    ``exp(kde_log_norm) * sum / n``.  The closed forms are scikit-learn's (``_kde_norm`` of its ball tree)."""
+    if kernel not in KDE_KERNELS:
+        raise ValueError(f"unknown kernel {kernel!r}: one of {sorted(KDE_KERNELS)}")
+    d = int(dim)
+    if kernel == "gaussian":
+        factor = 0.5 * d * math.log(2.0 * math.pi)
+    elif kernel == "tophat":
+        factor = _log_vn(d)
+    elif kernel == "epanechnikov":
+        factor = _log_vn(d) + math.log(2.0 / (d + 2.0))
+    elif kernel == "exponential":
+        factor = _log_sn(d - 1) + math.lgamma(d)
+    else:
+        factor = _log_vn(d) - math.log(d + 1.0)
+    return -factor - d * np.log(np.asarray(h, dtype=np.float64))
 
 
 class BallTree:
@@ -951,3 +985,162 @@ class BallTree:
             self._h, ordering.data_ptr(), reachability.data_ptr(), core_distances.data_ptr(), e, 0, labels.data_ptr(),
             ncl.data_ptr(), err.data_ptr(), C.c_void_p(st)))
         return labels, ncl, err
+
+    # -------------------------------------------------- kernel density estimation
+    # scikit-learn's ``BallTree.kernel_density`` on the device (``pn_kde_*``): per query the sum of the kernel over the rows
+    # within the kernel's cutoff, one wave per query in a fixed order.  ``h`` is a scalar or one bandwidth per query (the
+    # balloon estimator); ``atol`` lets the two smooth kernels stop at a finite cutoff (``sum_all - atol <= sum <= sum_all``);
+    # with ``atol=0`` they visit every row.  Every comparison is a strict '<'.
+    def _kde_args(self, h, kernel, atol, count, normalize=False):
+        """(kernel number, the bandwidths as a contiguous array of the tree's dtype: one, or ``count``)"""
+        if kernel not in KDE_KERNELS:
+            raise ValueError(f"unknown kernel {kernel!r}: one of {sorted(KDE_KERNELS)}")
+        atol = float(atol)
+        if not (atol >= 0.0) or math.isinf(atol):
+            raise ValueError("atol must be finite and >= 0")
+        if normalize:
+            from .distance import Cosine
+            if isinstance(self.metric, Cosine):
+                raise ValueError("normalize=True needs a Euclidean tree: the normalisers are volumes of Euclidean balls")
+        ha = self._radii(h, count)
+        if ha is None:
+            ha = np.array([h], dtype=self.dtype)
+            if not (ha[0] > 0) or not np.isfinite(ha[0]):
+                raise ValueError("the bandwidth must be finite and positive")
+        return KDE_KERNELS[kernel], ha
+
+    def _kde_finish(self, s, ha, kernel, return_log, normalize):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            if return_log:
+                out = np.log(s)
+                return out + kde_log_norm(kernel, self._dim, ha if ha.shape[0] > 1 else ha[0]) if normalize else out
+            return s * np.exp(kde_log_norm(kernel, self._dim, ha if ha.shape[0] > 1 else ha[0])) if normalize else s
+
+    def kernel_density(self, queries, h, kernel: str = "gaussian", atol: float = 0.0, return_log: bool = False,
+                       normalize: bool = True):
+        """Kernel density of every row of ``queries``: ``float64 [nq]``.  With ``normalize`` the kernel's normaliser for the
+        row dimension is applied, as scikit-learn's ``BallTree.kernel_density`` does; the result is not divided by n.  An
+        empty list gives 0 (``-inf`` with ``return_log``)."""
+        a = self._queries(queries, False)
+        nq, qc = a.shape
+        kn, ha = self._kde_args(h, kernel, atol, nq, normalize)
+        s = np.zeros(nq, dtype=np.float64)
+        if nq:
+            check(getattr(_lib.lib(), f"pn_kde_{self._sfx}")(self._h, a.ctypes.data, nq, qc, max(qc, 1), ha.ctypes.data,
+                                                            ha.shape[0], kn, float(atol), 0, s.ctypes.data, None, None))
+        return self._kde_finish(s, ha, kernel, return_log, normalize)
+
+    def kernel_density_self(self, h, kernel: str = "gaussian", atol: float = 0.0, return_log: bool = False,
+                            normalize: bool = True, include_self: bool = False):
+        """``kernel_density`` of the indexed rows themselves; by default each row is left out of its own estimate (the
+        leave-one-out density)."""
+        kn, ha = self._kde_args(h, kernel, atol, self._n, normalize)
+        s = np.zeros(self._n, dtype=np.float64)
+        check(getattr(_lib.lib(), f"pn_kde_self_{self._sfx}")(self._h, ha.ctypes.data, ha.shape[0], kn, float(atol),
+                                                             _lib.PN_SELF_INCLUDE if include_self else 0, s.ctypes.data,
+                                                             None, None))
+        return self._kde_finish(s, ha, kernel, return_log, normalize)
+
+    def kernel_density_raw(self, queries, h, kernel: str = "gaussian", atol: float = 0.0, include_self: bool = False):
+        """The C ABI's three outputs on the host: ``(sum float64, count uint64, cutoff)`` per query; ``queries=None``: the
+        indexed rows themselves (``include_self`` as in ``kernel_density_self``)."""
+        if queries is None:
+            nq = self._n
+            kn, ha = self._kde_args(h, kernel, atol, nq)
+        else:
+            a = self._queries(queries, False)
+            nq, qc = a.shape
+            kn, ha = self._kde_args(h, kernel, atol, nq)
+        s = np.zeros(nq, dtype=np.float64)
+        cnt = np.zeros(nq, dtype=np.uint64)
+        cut = np.zeros(nq, dtype=self.dtype)
+        if queries is None:
+            check(getattr(_lib.lib(), f"pn_kde_self_{self._sfx}")(
+                self._h, ha.ctypes.data, ha.shape[0], kn, float(atol), _lib.PN_SELF_INCLUDE if include_self else 0,
+                s.ctypes.data, cnt.ctypes.data, cut.ctypes.data))
+        elif nq:
+            check(getattr(_lib.lib(), f"pn_kde_{self._sfx}")(self._h, a.ctypes.data, nq, qc, max(qc, 1), ha.ctypes.data,
+                                                            ha.shape[0], kn, float(atol), 0, s.ctypes.data, cnt.ctypes.data,
+                                                            cut.ctypes.data))
+        return s, cnt, cut
+
+    def _kde_device_args(self, h, kernel, atol, count, outs):
+        import torch
+        if kernel not in KDE_KERNELS:
+            raise ValueError(f"unknown kernel {kernel!r}: one of {sorted(KDE_KERNELS)}")
+        atol = float(atol)
+        if not (atol >= 0.0) or math.isinf(atol):
+            raise ValueError("atol must be finite and >= 0")
+        tdt = torch.float32 if self._sfx == "f32" else torch.float64
+        dev = torch.device("cuda", self.device)
+        ht = self._radii_device(h, count, dev)
+        if ht is None and (not (float(h) > 0.0) or math.isinf(float(h))):
+            raise ValueError("the bandwidth must be finite and positive")
+        for t, want in zip(outs, (torch.float64, torch.int64, tdt)):
+            if t is not None and not self._lof_on_device(t, want, count):
+                raise ValueError(f"output tensors must be contiguous CUDA tensors of at least {count} values on the tree's "
+                                 "device (sum float64, count int64, cutoff of the tree's element type)")
+        if ht is None:
+            ht = torch.full((1,), float(h), dtype=tdt, device=dev)
+        s = outs[0] if outs[0] is not None else torch.empty(count, dtype=torch.float64, device=dev)
+        cnt = outs[1] if outs[1] is not None else torch.empty(count, dtype=torch.int64, device=dev)
+        cut = outs[2] if outs[2] is not None else torch.empty(count, dtype=tdt, device=dev)
+        return KDE_KERNELS[kernel], ht, s, cnt, cut
+
+    def kernel_density_device(self, queries, h, kernel: str = "gaussian", atol: float = 0.0, out_sum=None, out_count=None,
+                              out_cutoff=None, stream=None):
+        """The raw sums in HBM: ``queries`` a 2-D CUDA tensor of the tree's element type, ``h`` a scalar or a 1-D CUDA tensor
+        of one bandwidth per query; returns CUDA tensors ``(sum float64 [nq], count int64 [nq], cutoff [nq])`` written in
+        stream order on ``stream`` (default: the current torch stream).  The call waits for the device once (it reads
+        the list offsets back to cut its pieces) and cannot be captured into a graph."""
+        import torch
+        tdt = torch.float32 if self._sfx == "f32" else torch.float64
+        if (not isinstance(queries, torch.Tensor) or queries.dtype != tdt or queries.dim() != 2 or not queries.is_cuda
+                or queries.device.index != self.device):
+            raise ValueError(f"queries must be a 2-D {tdt} CUDA tensor on the tree's device")
+        if queries.shape[1] > 1 and queries.stride(1) != 1:
+            queries = queries.contiguous()
+        nq, qc = queries.shape
+        kn, ht, s, cnt, cut = self._kde_device_args(h, kernel, atol, nq, (out_sum, out_count, out_cutoff))
+        if nq:
+            st = stream if stream is not None else torch.cuda.current_stream(queries.device).cuda_stream
+            check(getattr(_lib.lib(), f"pn_kde_device_{self._sfx}")(
+                self._h, queries.data_ptr(), nq, qc, queries.stride(0) if nq > 1 else max(qc, 1), ht.data_ptr(),
+                ht.shape[0], kn, float(atol), 0, s.data_ptr(), cnt.data_ptr(), cut.data_ptr(), C.c_void_p(st)))
+        return s, cnt, cut
+
+    def kernel_density_self_device(self, h, kernel: str = "gaussian", atol: float = 0.0, include_self: bool = False,
+                                   out_sum=None, out_count=None, out_cutoff=None, stream=None):
+        """``kernel_density_device`` of the indexed rows themselves (``h``: a scalar or one bandwidth per row)."""
+        import torch
+        kn, ht, s, cnt, cut = self._kde_device_args(h, kernel, atol, self._n, (out_sum, out_count, out_cutoff))
+        st = stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
+        check(getattr(_lib.lib(), f"pn_kde_self_device_{self._sfx}")(
+            self._h, ht.data_ptr(), ht.shape[0], kn, float(atol), _lib.PN_SELF_INCLUDE if include_self else 0,
+            s.data_ptr(), cnt.data_ptr(), cut.data_ptr(), C.c_void_p(st)))
+        return s, cnt, cut
+
+    def query_radius_count(self, queries, r):
+        """The number of rows with distance < ``r`` (strict) per query: ``uint64 [nq]``; ``r`` a scalar or one radius per
+        query.  Only the counting pass runs: no list is written (scikit-learn's ``query_radius(count_only=True)``)."""
+        a = self._queries(queries, False)
+        nq, qc = a.shape
+        ra = self._radii(r, nq)
+        if ra is None:  # (a radius that is not finite and positive is served as an array: empty lists, or every row)
+            ok = float(r) > 0.0 and not math.isinf(float(r))
+            ra = np.array([r], dtype=self.dtype) if ok else np.full(nq, r, dtype=self.dtype)
+        cnt = np.zeros(nq, dtype=np.uint64)
+        if nq:
+            check(getattr(_lib.lib(), f"pn_kde_{self._sfx}")(self._h, a.ctypes.data, nq, qc, max(qc, 1), ra.ctypes.data,
+                                                            ra.shape[0], _lib.PN_KDE_TOPHAT, 0.0, 0, None, cnt.ctypes.data,
+                                                            None))
+        return cnt
+
+    def two_point_correlation(self, queries, r):
+        """For each entry of the 1-D array ``r``: the number of (query, row) pairs with distance < ``r[i]``, ``int64``.
+        scikit-learn's ``two_point_correlation`` counts distance <= r; every radius in this library is strict."""
+        ra = np.asarray(r)
+        if ra.ndim != 1:
+            raise ValueError("r must be 1-D")
+        a = self._queries(queries, False)
+        return np.array([int(self.query_radius_count(a, x).sum()) for x in ra.tolist()], dtype=np.int64)

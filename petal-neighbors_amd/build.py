@@ -46,6 +46,7 @@ UNITS = [
     ("mst.hip", []),
     ("linkage.hip", []),
     ("lof.hip", ["-ffp-contract=off"]),
+    ("kde.hip", ["-ffp-contract=off"]),
     ("optics.hip", ["-ffp-contract=off"]),
     ("radii_tau.hip", ["-ffp-contract=off"]),
     ("metric.cpp", ["-ffp-contract=off"]),

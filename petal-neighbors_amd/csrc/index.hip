@@ -161,6 +161,9 @@ struct Workspace {
     // pn_optics_* / pn_optics_dbscan_*: the O(n) arrays of a call (offsets, radii, the tournament tree), the graph store
     // (uint32 ids and distances of every core row's list), and the host entries' inputs and outputs
     DevBuf w_opt, w_opt_graph, w_opt_io;
+    // pn_kde_*: the O(nq) arrays of a call (offsets, bandwidths, cutoffs; + count when the caller keeps none), and the host
+    // entries' inputs and outputs
+    DevBuf w_kde, w_kde_io;
     // small calls (tiny_*): mapped pinned host memory the one kernel of the call reads its queries from and writes its
     // answers to -- no copy commands
     void *pin_in = nullptr, *pin_out = nullptr;
@@ -186,7 +189,7 @@ struct Workspace {
     hipEvent_t done = nullptr;
     hipStream_t last_stream = nullptr;
     bool in_flight = false;
-    DevBuf *all[64] = {&w_opt, &w_opt_graph, &w_opt_io, &w_lof, &w_lof_io, &w_hdb, &w_hdb_io, &w_mst, &w_mst_io, &w_db, &w_db_side, &w_db_out, &w_hrad, &w_sf_idx, &w_sf_dist, &w_sf_off, &w_sf_coff, &w_sf_flag, &w_sf_cnt, &w_sf_scan, &w_sf_hoff, &w_cs_hoff, &w_rkd, &w_cs_nch, &w_cs_off, &w_cs_scan, &w_cs_idx, &w_cs_dist, &w_gqn, &w_rpos, &w_rfin, &w_rcx, &w_rox, &w_rscan, &w_q, &w_qnorm, &w_qnrm, &w_keys, &w_idx, &w_cnt, &w_tau, &w_flags, &w_sel, &w_misc, &w2_keys, &w2_idx,
+    DevBuf *all[66] = {&w_kde, &w_kde_io, &w_opt, &w_opt_graph, &w_opt_io, &w_lof, &w_lof_io, &w_hdb, &w_hdb_io, &w_mst, &w_mst_io, &w_db, &w_db_side, &w_db_out, &w_hrad, &w_sf_idx, &w_sf_dist, &w_sf_off, &w_sf_coff, &w_sf_flag, &w_sf_cnt, &w_sf_scan, &w_sf_hoff, &w_cs_hoff, &w_rkd, &w_cs_nch, &w_cs_off, &w_cs_scan, &w_cs_idx, &w_cs_dist, &w_gqn, &w_rpos, &w_rfin, &w_rcx, &w_rox, &w_rscan, &w_q, &w_qnorm, &w_qnrm, &w_keys, &w_idx, &w_cnt, &w_tau, &w_flags, &w_sel, &w_misc, &w2_keys, &w2_idx,
                        &w2_cnt, &w2_tau, &w_lo, &w_bq, &w_qn, &w_qbad, &w_gq, &w_gidx, &w_gdist, &w_gsel, &w_seed,
                        &w_qstat, &w_lists, &w_hq, &w_hidx, &w_hdist, &w_fparts, &w_pcnt};
     std::vector<void *> retired;  // outgrown allocations, freed once `done` has passed (DevBuf::ensure)
@@ -256,6 +259,7 @@ struct pn_index {
     uint64_t dbscan_piece = 0;  // PN_OPT_DBSCAN_PIECE: list entries per piece of pn_dbscan_*, 0 = 2^27
     uint64_t mst_batch = 0;     // PN_OPT_MST_BATCH: listed rows per scan launch of pn_mst_*, 0 = 2^18
     uint64_t optics_piece = 0;  // PN_OPT_OPTICS_PIECE: list entries per fill piece of pn_optics_*, 0 = 2^27
+    uint64_t kde_piece = 0;     // PN_OPT_KDE_PIECE: list entries per piece of pn_kde_*, 0 = 2^27
     // state that queries on a shared `const pn_index *` update: internally synchronised by `mu`
     struct Shared {
         std::mutex mu;
@@ -1009,6 +1013,10 @@ extern "C" int pn_index_set_option(pn_index *ix, int option, int64_t value) {
         case PN_OPT_OPTICS_PIECE:
             if (value < 0) return fail(PN_ERR_INVALID, "bad OPTICS piece size");
             ix->optics_piece = (uint64_t)value;
+            return PN_OK;
+        case PN_OPT_KDE_PIECE:
+            if (value < 0) return fail(PN_ERR_INVALID, "bad KDE piece size");
+            ix->kde_piece = (uint64_t)value;
             return PN_OK;
         default: return fail(PN_ERR_INVALID, "unknown option %d", option);
     }
@@ -4667,6 +4675,203 @@ extern "C" int pn_query_radii_self_device_f64(const pn_index *ix, const double *
                                               uint64_t *d_idx, double *d_dist, size_t capacity, uint64_t *d_total,
                                               void *stream) {
     return radii_self_device<double>(ix, d_radii, flags, d_offsets, d_idx, d_dist, capacity, d_total, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------
+// Kernel density estimation: pn_kde_{,device_,self_,self_device_}{f32,f64} (the kernels and the shape of the sum: kde.hip).
+//   1. cutoff: one kernel turns the bandwidths (one, or one per query) into the per-query cutoffs c_q and broadcasts h.
+//      Every call goes through the d_radii path of the radius pipeline: one implementation, and a constant array gives
+//      the scalar call's thresholds word for word.
+//   2. count: radius_device_enqueue / radius_self_enqueue with capacity 0 gives the offsets, and from them `count`.
+//      Without a sum that is all.  Otherwise the offsets are read back -- the one host wait of a call -- to cut the pieces.
+//      (A self call that leaves the rows out counts with PN_SELF_INCLUDE: the pieces below hold the rows themselves, and
+//      the sum kernel drops each row's own entry and writes the count.)
+//   3. sum: a piece is a contiguous query range of at most 2^18 queries whose lists hold at most E entries together
+//      (PN_OPT_KDE_PIECE, default 2^27; a longer single list is a piece of its own).  radius_device_enqueue writes the
+//      piece's lists with distances into workspace scratch of exactly the piece's total, kde_sum_kernel reads them there.
+// Device memory beyond a 2^18-query batch's workspace: 16 + 2 sizeof T bytes per query and 8 + sizeof T bytes per entry of
+// the largest piece -- never the lists of the call.
+// ---------------------------------------------------------------------------
+constexpr uint64_t kKdePiece = (uint64_t)1 << 27;
+// (before any device is touched; `inputs`: the name of the first NULL input of a call with queries, or nullptr; nq: the
+// number of queries where the caller knows it without the handle, else n_h itself)
+static int kde_args(const pn_index *ix, unsigned flags, unsigned allowed, int kernel, double atol, const void *sum,
+                    const void *count, const char *null_input, size_t n_h, size_t nq, int elem_bytes) {
+    if (flags & ~allowed) return fail(PN_ERR_INVALID, "unknown KDE flags 0x%x", flags);
+    if (kernel < PN_KDE_GAUSSIAN || kernel > PN_KDE_LINEAR) return fail(PN_ERR_INVALID, "unknown KDE kernel %d", kernel);
+    if (!(atol >= 0.0) || !std::isfinite(atol)) return fail(PN_ERR_INVALID, "atol must be finite and >= 0");
+    if (!sum && !count) return fail(PN_ERR_INVALID, "sum and count are both NULL");
+    if (null_input) return fail(PN_ERR_INVALID, "%s is NULL", null_input);
+    if (n_h != 1 && n_h != nq) return fail(PN_ERR_INVALID, "n_h must be 1 or the number of queries (%zu)", nq);
+    if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
+    if (ix->elem_bytes != elem_bytes) return fail(PN_ERR_INVALID, "index element type mismatch");
+    if (ix->n > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many rows for KDE");
+    if (nq > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many queries in one call");
+    return PN_OK;
+}
+// in a held workspace, on stream s; everything in HBM; nq >= 1.  self: the queries are the indexed rows (d_q is not
+// looked at, nq = n), flags = PN_SELF_INCLUDE or 0.  Blocks the host once (after the counting pass) when d_sum is given.
+template <typename T>
+static int kde_enqueue(const pn_index *ix, Workspace &ws, bool self, const T *d_q, size_t nq, size_t q_cols, size_t q_stride,
+                       const T *d_h, size_t n_h, int kernel, double atol, unsigned flags, double *d_sum, uint64_t *d_count,
+                       T *d_cutoff, hipStream_t s) {
+    // ---- 1. cutoff (the header states this sequence)
+    int mode = 0;
+    double f = 0.0;
+    if (kernel == PN_KDE_GAUSSIAN || kernel == PN_KDE_EXPONENTIAL) {
+        if (atol == 0.0)
+            mode = 3;
+        else if (atol >= (double)ix->n)
+            mode = 2;
+        else {
+            const double L = std::log((double)ix->n / atol);
+            f = (kernel == PN_KDE_GAUSSIAN ? std::sqrt(2.0 * L) : L) * (1.0 + 9.313225746154785e-10);  // (1 + 2^-30)
+            mode = 1;
+        }
+    }
+    PNCHK(ws.w_kde.ensure((nq + 2) * sizeof(uint64_t) + 2 * nq * sizeof(T)));
+    uint64_t *off = (uint64_t *)ws.w_kde.p;
+    T *hq = (T *)(off + nq + 2), *cut = d_cutoff ? d_cutoff : hq + nq;
+    HIPCHK(launch_kde_cutoff<T>(d_h, n_h, nq, mode, f, hq, cut, s));
+    // ---- 2. count
+    const bool exclude = self && !(flags & PN_SELF_INCLUDE);
+    if (self)
+        PNCHK(radius_self_enqueue<T>(ix, ws, (T)0, d_sum ? (unsigned)PN_SELF_INCLUDE : flags, off, nullptr, nullptr, 0, nullptr, s,
+                                     true, cut));
+    else
+        PNCHK(radius_device_enqueue<T>(ix, ws, d_q, nq, q_cols, q_stride, (T)0, off, nullptr, 0, nullptr, s, nullptr, 0, true,
+                                       cut, true));
+    if (d_count && !(d_sum && exclude)) HIPCHK(launch_kde_counts(off, nq, d_count, s));
+    if (!d_sum) return PN_OK;
+    std::vector<uint64_t> h_off;
+    try {
+        h_off.resize(nq + 1);
+    } catch (const std::bad_alloc &) {
+        return fail(PN_ERR_NOMEM, "host allocation of %zu offsets failed", nq + 1);
+    }
+    HIPCHK(hipMemcpyAsync(h_off.data(), off, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    // (a query whose piece is empty gets its zeros here)
+    HIPCHK(hipMemsetAsync(d_sum, 0, nq * sizeof(double), s));
+    if (d_count && exclude) HIPCHK(hipMemsetAsync(d_count, 0, nq * sizeof(uint64_t), s));
+    HIPCHK(hipStreamSynchronize(s));
+    // ---- 3. sum, piece by piece
+    const uint64_t E = ix->kde_piece ? ix->kde_piece : kKdePiece;
+    PNCHK(ws.w_sf_off.ensure((std::min(nq, kSelfChunk) + 1) * sizeof(uint64_t)));
+    for (size_t a = 0; a < nq;) {
+        const size_t lim = nq - a < kSelfChunk ? nq : a + kSelfChunk;
+        // the last b in (a, lim] with off[b] - off[a] <= E, at least a + 1
+        size_t b = (size_t)(std::upper_bound(h_off.begin() + a + 1, h_off.begin() + lim + 1, h_off[a] + E) - h_off.begin()) - 1;
+        if (b <= a) b = a + 1;
+        const uint64_t total = h_off[b] - h_off[a];
+        if (total) {
+            PNCHK(ws.w_sf_idx.ensure(total * sizeof(uint64_t)));
+            PNCHK(ws.w_sf_dist.ensure(total * sizeof(T)));
+            uint64_t *in_off = (uint64_t *)ws.w_sf_off.p, *in_idx = (uint64_t *)ws.w_sf_idx.p;
+            T *in_dist = (T *)ws.w_sf_dist.p;
+            const T *qp = self ? (const T *)ix->d_pts + a * ix->ld : d_q + a * q_stride;
+            PNCHK(radius_device_enqueue<T>(ix, ws, qp, b - a, self ? ix->dim : q_cols, self ? ix->ld : q_stride, (T)0, in_off,
+                                           in_idx, (size_t)total, nullptr, s, in_dist, 0, false, cut + a, false));
+            HIPCHK(launch_kde_sum<T>(in_off, in_idx, in_dist, hq + a, b - a, kernel, exclude ? ix->index_base + a : ~0ull,
+                                     d_sum + a, d_count && exclude ? d_count + a : nullptr, s));
+        }
+        a = b;
+    }
+    return PN_OK;
+}
+template <typename T>
+static int kde_device(const pn_index *ix, bool self, const T *d_q, size_t nq, size_t q_cols, size_t q_stride, const T *d_h,
+                      size_t n_h, int kernel, double atol, unsigned flags, double *d_sum, uint64_t *d_count, T *d_cutoff,
+                      hipStream_t s) {
+    const char *null_input = self ? (!d_h ? "h" : nullptr) : nq ? (!d_q && q_cols ? "queries" : !d_h ? "h" : nullptr) : nullptr;
+    PNCHK(kde_args(ix, flags, self ? (unsigned)PN_SELF_INCLUDE : 0u, kernel, atol, d_sum, d_count, null_input, n_h,
+                   self ? n_h : nq, (int)sizeof(T)));
+    if (self) {
+        nq = ix->n;
+        if (n_h != 1 && n_h != nq) return fail(PN_ERR_INVALID, "n_h must be 1 or the number of rows (%zu)", nq);
+    }
+    if (nq == 0) return PN_OK;
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    lease.s = s;
+    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
+    return kde_enqueue<T>(ix, *lease.ws, self, d_q, nq, q_cols, q_stride, d_h, n_h, kernel, atol, flags, d_sum, d_count,
+                          d_cutoff, s);
+}
+template <typename T>
+static int kde_host(const pn_index *ix, bool self, const T *q, size_t nq, size_t q_cols, ptrdiff_t q_stride, const T *h,
+                    size_t n_h, int kernel, double atol, unsigned flags, double *sum, uint64_t *count, T *cutoff) {
+    const char *null_input = self ? (!h ? "h" : nullptr) : nq ? (!q && q_cols ? "queries" : !h ? "h" : nullptr) : nullptr;
+    PNCHK(kde_args(ix, flags, self ? (unsigned)PN_SELF_INCLUDE : 0u, kernel, atol, sum, count, null_input, n_h,
+                   self ? n_h : nq, (int)sizeof(T)));
+    if (self) {
+        nq = ix->n;
+        if (n_h != 1 && n_h != nq) return fail(PN_ERR_INVALID, "n_h must be 1 or the number of rows (%zu)", nq);
+    }
+    if (nq == 0) return PN_OK;
+    if (n_h == 1 && !(h[0] > (T)0 && h[0] < (T)INFINITY))
+        return fail(PN_ERR_INVALID, "the bandwidth must be finite and positive");
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
+    Workspace &ws = *lease.ws;
+    hipStream_t s = lease.s;
+    if (!self) PNCHK(upload_rows_to<T>(q, nq, q_cols, q_stride, ws.w_hq, s));
+    PNCHK(ws.w_kde_io.ensure(nq * (sizeof(double) + sizeof(uint64_t) + sizeof(T)) + n_h * sizeof(T)));
+    double *d_sum = (double *)ws.w_kde_io.p;
+    uint64_t *d_count = (uint64_t *)(d_sum + nq);
+    T *d_cutoff = (T *)(d_count + nq), *d_h = d_cutoff + nq;
+    HIPCHK(hipMemcpyAsync(d_h, h, n_h * sizeof(T), hipMemcpyHostToDevice, s));
+    PNCHK(kde_enqueue<T>(ix, ws, self, self ? nullptr : (const T *)ws.w_hq.p, nq, q_cols, q_cols ? q_cols : 1, d_h, n_h, kernel,
+                         atol, flags, sum ? d_sum : nullptr, count ? d_count : nullptr, d_cutoff, s));
+    if (sum) HIPCHK(hipMemcpyAsync(sum, d_sum, nq * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (count) HIPCHK(hipMemcpyAsync(count, d_count, nq * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    if (cutoff) HIPCHK(hipMemcpyAsync(cutoff, d_cutoff, nq * sizeof(T), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return PN_OK;
+}
+extern "C" int pn_kde_f32(const pn_index *ix, const float *queries, size_t nq, size_t q_cols, ptrdiff_t q_row_stride,
+                          const float *h, size_t n_h, int kernel, double atol, unsigned flags, double *sum_out,
+                          uint64_t *count_out, float *cutoff_out) {
+    return kde_host<float>(ix, false, queries, nq, q_cols, q_row_stride, h, n_h, kernel, atol, flags, sum_out, count_out,
+                           cutoff_out);
+}
+extern "C" int pn_kde_f64(const pn_index *ix, const double *queries, size_t nq, size_t q_cols, ptrdiff_t q_row_stride,
+                          const double *h, size_t n_h, int kernel, double atol, unsigned flags, double *sum_out,
+                          uint64_t *count_out, double *cutoff_out) {
+    return kde_host<double>(ix, false, queries, nq, q_cols, q_row_stride, h, n_h, kernel, atol, flags, sum_out, count_out,
+                            cutoff_out);
+}
+extern "C" int pn_kde_device_f32(const pn_index *ix, const float *d_queries, size_t nq, size_t q_cols, size_t q_row_stride,
+                                 const float *d_h, size_t n_h, int kernel, double atol, unsigned flags, double *d_sum,
+                                 uint64_t *d_count, float *d_cutoff, void *stream) {
+    return kde_device<float>(ix, false, d_queries, nq, q_cols, q_row_stride, d_h, n_h, kernel, atol, flags, d_sum, d_count,
+                             d_cutoff, (hipStream_t)stream);
+}
+extern "C" int pn_kde_device_f64(const pn_index *ix, const double *d_queries, size_t nq, size_t q_cols, size_t q_row_stride,
+                                 const double *d_h, size_t n_h, int kernel, double atol, unsigned flags, double *d_sum,
+                                 uint64_t *d_count, double *d_cutoff, void *stream) {
+    return kde_device<double>(ix, false, d_queries, nq, q_cols, q_row_stride, d_h, n_h, kernel, atol, flags, d_sum, d_count,
+                              d_cutoff, (hipStream_t)stream);
+}
+extern "C" int pn_kde_self_f32(const pn_index *ix, const float *h, size_t n_h, int kernel, double atol, unsigned flags,
+                               double *sum_out, uint64_t *count_out, float *cutoff_out) {
+    return kde_host<float>(ix, true, nullptr, 0, 0, 0, h, n_h, kernel, atol, flags, sum_out, count_out, cutoff_out);
+}
+extern "C" int pn_kde_self_f64(const pn_index *ix, const double *h, size_t n_h, int kernel, double atol, unsigned flags,
+                               double *sum_out, uint64_t *count_out, double *cutoff_out) {
+    return kde_host<double>(ix, true, nullptr, 0, 0, 0, h, n_h, kernel, atol, flags, sum_out, count_out, cutoff_out);
+}
+extern "C" int pn_kde_self_device_f32(const pn_index *ix, const float *d_h, size_t n_h, int kernel, double atol,
+                                      unsigned flags, double *d_sum, uint64_t *d_count, float *d_cutoff, void *stream) {
+    return kde_device<float>(ix, true, nullptr, 0, 0, 0, d_h, n_h, kernel, atol, flags, d_sum, d_count, d_cutoff,
+                             (hipStream_t)stream);
+}
+extern "C" int pn_kde_self_device_f64(const pn_index *ix, const double *d_h, size_t n_h, int kernel, double atol,
+                                      unsigned flags, double *d_sum, uint64_t *d_count, double *d_cutoff, void *stream) {
+    return kde_device<double>(ix, true, nullptr, 0, 0, 0, d_h, n_h, kernel, atol, flags, d_sum, d_count, d_cutoff,
+                              (hipStream_t)stream);
 }
 
 extern "C" void pn_free(void *p) { free(p); }

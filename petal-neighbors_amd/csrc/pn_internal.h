@@ -253,6 +253,19 @@ hipError_t launch_lof_score_f32(const uint64_t *q_idx, const float *q_dist, size
 hipError_t launch_lof_score_f64(const uint64_t *q_idx, const double *q_dist, size_t nq, int k, uint64_t index_base, size_t n,
                                 const double *lrd, const double *kdist, double *score, hipStream_t s);
 
+// ---- kde.hip: kernel density sums over the radius lists (pn_kde_*); nothing in it waits for the device.
+// hq [nq] <- h broadcast (n_h = 1) or copied (n_h = nq); cut [nq] <- the cutoffs.  mode 0: cut = h; 1: the smallest T >=
+// (double)h * f; 2: 0; 3: +inf; a bandwidth that is not positive is its own cutoff in every mode
+template <typename T>
+hipError_t launch_kde_cutoff(const T *h, size_t n_h, size_t nq, int mode, double f, T *hq, T *cut, hipStream_t s);
+// count[q] = off[q + 1] - off[q]
+hipError_t launch_kde_counts(const uint64_t *off, size_t nq, uint64_t *count, hipStream_t s);
+// sum [nq] (and count [nq], nullable) of a piece's lists (piece-local offsets off, 64-bit ids with the index base,
+// distances) with the bandwidths hq [nq]; own_first != ~0: query q is row id own_first + q and its own entry is left out
+template <typename T>
+hipError_t launch_kde_sum(const uint64_t *off, const uint64_t *idx, const T *dist, const T *hq, size_t nq, int kernel,
+                          uint64_t own_first, double *sum, uint64_t *count, hipStream_t s);
+
 // ---- optics.hip: OPTICS over the max_eps self-graph (pn_optics_*) and the extraction at one eps (pn_optics_dbscan_*);
 // nothing in it waits for the device.
 // core[i] <- v < max_eps ? v : +inf, v = in_dist[i][k - 1] of a self-query chunk's answer [nq][k] (in_dist == nullptr: +inf);
