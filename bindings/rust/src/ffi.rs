@@ -6,6 +6,9 @@ use std::os::raw::{c_char, c_int, c_uint, c_void};
 /// `flags` of the radius calls with distances: each list by (distance, index) ascending
 pub const PN_RADIUS_SORTED: c_uint = 1;
 pub const PN_SELF_INCLUDE: c_uint = 2;
+/// `flags` of pn_mean_shift_*: the indexed rows are the seeds / of pn_mean_shift_labels_*: rows beyond h of every centre get -1
+pub const PN_MS_SEED_ROWS: c_uint = 4;
+pub const PN_MS_ORPHANS: c_uint = 8;
 /// `kernel` of the pn_kde_* calls
 pub const PN_KDE_GAUSSIAN: c_int = 0;
 pub const PN_KDE_TOPHAT: c_int = 1;
@@ -230,6 +233,47 @@ extern "C" {
     pub fn pn_kde_self_device_f64(index: *const pn_index, d_h: *const f64, n_h: usize, kernel: c_int, atol: f64,
                                   flags: c_uint, d_sum: *mut f64, d_count: *mut u64, d_cutoff: *mut f64,
                                   stream: *mut c_void) -> c_int;
+    /// mean shift (flat kernel): seeds to modes (only the seeds still moving are queried; the device entry blocks the
+    /// host twice per iteration; work = {iterations, seed-steps} in host memory, nullable), modes to centres, rows to
+    /// labels (these two never wait); h: n_h = 1 or one bandwidth per seed; iterations / shift nullable
+    pub fn pn_mean_shift_f32(index: *const pn_index, seeds: *const f32, ns: usize, s_cols: usize, s_row_stride: isize,
+                             h: *const f32, n_h: usize, tol: f64, max_iter: usize, flags: c_uint, modes_out: *mut f32,
+                             points_within_out: *mut u64, iterations_out: *mut u32, shift_out: *mut f64,
+                             work: *mut u64) -> c_int;
+    pub fn pn_mean_shift_device_f32(index: *const pn_index, d_seeds: *const f32, ns: usize, s_cols: usize,
+                                    s_row_stride: usize, d_h: *const f32, n_h: usize, tol: f64, max_iter: usize,
+                                    flags: c_uint, d_modes: *mut f32, d_points_within: *mut u64, d_iterations: *mut u32,
+                                    d_shift: *mut f64, work: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn pn_mean_shift_merge_f32(index: *const pn_index, modes: *const f32, ns: usize, points_within: *const u64, h: f32,
+                                   flags: c_uint, centres_out: *mut f32, centre_points_out: *mut u64,
+                                   centre_of_seed_out: *mut i64, n_centres_out: *mut u64) -> c_int;
+    pub fn pn_mean_shift_merge_device_f32(index: *const pn_index, d_modes: *const f32, ns: usize,
+                                          d_points_within: *const u64, h: f32, flags: c_uint, d_centres: *mut f32,
+                                          d_centre_points: *mut u64, d_centre_of_seed: *mut i64, d_n_centres: *mut u64,
+                                          stream: *mut c_void) -> c_int;
+    pub fn pn_mean_shift_labels_f32(index: *const pn_index, centres: *const f32, nc: usize, h: f32, flags: c_uint,
+                                    labels: *mut i64) -> c_int;
+    pub fn pn_mean_shift_labels_device_f32(index: *const pn_index, d_centres: *const f32, nc: usize, h: f32, flags: c_uint,
+                                           d_labels: *mut i64, stream: *mut c_void) -> c_int;
+    pub fn pn_mean_shift_f64(index: *const pn_index, seeds: *const f64, ns: usize, s_cols: usize, s_row_stride: isize,
+                             h: *const f64, n_h: usize, tol: f64, max_iter: usize, flags: c_uint, modes_out: *mut f64,
+                             points_within_out: *mut u64, iterations_out: *mut u32, shift_out: *mut f64,
+                             work: *mut u64) -> c_int;
+    pub fn pn_mean_shift_device_f64(index: *const pn_index, d_seeds: *const f64, ns: usize, s_cols: usize,
+                                    s_row_stride: usize, d_h: *const f64, n_h: usize, tol: f64, max_iter: usize,
+                                    flags: c_uint, d_modes: *mut f64, d_points_within: *mut u64, d_iterations: *mut u32,
+                                    d_shift: *mut f64, work: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn pn_mean_shift_merge_f64(index: *const pn_index, modes: *const f64, ns: usize, points_within: *const u64, h: f64,
+                                   flags: c_uint, centres_out: *mut f64, centre_points_out: *mut u64,
+                                   centre_of_seed_out: *mut i64, n_centres_out: *mut u64) -> c_int;
+    pub fn pn_mean_shift_merge_device_f64(index: *const pn_index, d_modes: *const f64, ns: usize,
+                                          d_points_within: *const u64, h: f64, flags: c_uint, d_centres: *mut f64,
+                                          d_centre_points: *mut u64, d_centre_of_seed: *mut i64, d_n_centres: *mut u64,
+                                          stream: *mut c_void) -> c_int;
+    pub fn pn_mean_shift_labels_f64(index: *const pn_index, centres: *const f64, nc: usize, h: f64, flags: c_uint,
+                                    labels: *mut i64) -> c_int;
+    pub fn pn_mean_shift_labels_device_f64(index: *const pn_index, d_centres: *const f64, nc: usize, h: f64, flags: c_uint,
+                                           d_labels: *mut i64, stream: *mut c_void) -> c_int;
     /// dist_out nullable (PN_RADIUS_SORTED needs it); *idx_out / *dist_out released with pn_free
     pub fn pn_query_radius_self_f32(index: *const pn_index, radius: f32, flags: c_uint, offsets: *mut u64,
                                     idx_out: *mut *mut u64, dist_out: *mut *mut f32) -> c_int;

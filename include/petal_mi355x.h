@@ -63,7 +63,8 @@ extern "C" {
  * pn_dbscan_{,device_}{f32,f64}, PN_OPT_DBSCAN_PIECE; pn_mst_{,device_}{f32,f64}, PN_OPT_MST_BATCH;
  * pn_linkage_{,device_}{f32,f64}, pn_hdbscan_{,device_}{f32,f64}; pn_lof_{,device_}{f32,f64},
  * pn_lof_score_{,device_}{f32,f64}; pn_optics_{,device_}{f32,f64}, pn_optics_dbscan_{,device_}{f32,f64},
- * PN_OPT_OPTICS_PIECE; pn_kde_{,device_,self_,self_device_}{f32,f64}, PN_KDE_*, PN_OPT_KDE_PIECE. */
+ * PN_OPT_OPTICS_PIECE; pn_kde_{,device_,self_,self_device_}{f32,f64}, PN_KDE_*, PN_OPT_KDE_PIECE;
+ * pn_mean_shift_{,device_,merge_,merge_device_,labels_,labels_device_}{f32,f64}, PN_MS_*, PN_OPT_MS_PIECE. */
 #define PN_ABI_VERSION 3
 
 /* ---- error codes.  EMPTY / NOT_CONTIGUOUS are ArrayError (src/lib.rs:9-16). */
@@ -125,9 +126,12 @@ enum {
                                   scratch before it is packed into the graph store; 0 (default) = 2^27; negative:
                                   PN_ERR_INVALID.  A row whose own list is longer is a piece of its own.  Never changes a
                                   result (it lets tests force several pieces at small n). */
-    PN_OPT_KDE_PIECE = 14        /* pn_kde_*: the most list entries (a 64-bit index and a distance each, in workspace
+    PN_OPT_KDE_PIECE = 14,       /* pn_kde_*: the most list entries (a 64-bit index and a distance each, in workspace
                                   scratch) one piece of the sum stage holds; 0 (default) = 2^27; negative: PN_ERR_INVALID.
                                   A query whose own list is longer is a piece of its own.  Never changes a result. */
+    PN_OPT_MS_PIECE = 15         /* pn_mean_shift_*: the most list entries (a 64-bit index each, in workspace scratch) one
+                                  piece of an iteration's step stage holds; 0 (default) = 2^27; negative: PN_ERR_INVALID.
+                                  A seed whose own list is longer is a piece of its own.  Never changes a result. */
 };
 
 /* kernels of pn_kde_* (scikit-learn's names; its sixth, `cosine`, is left out: the name collides with the Cosine metric
@@ -727,6 +731,102 @@ int pn_kde_self_device_f32(const pn_index *index, const float *d_h, size_t n_h, 
                            double *d_sum, uint64_t *d_count, float *d_cutoff, void *stream);
 int pn_kde_self_device_f64(const pn_index *index, const double *d_h, size_t n_h, int kernel, double atol, unsigned flags,
                            double *d_sum, uint64_t *d_count, double *d_cutoff, void *stream);
+
+/* ---- Mean shift on the device (scikit-learn's cluster.MeanShift with its flat kernel: the mode seeking of
+ * _mean_shift_single_seed, the merge of the converged modes, the labels): it climbs the tophat density pn_kde_* evaluates.
+ * Three entries, each usable alone: pn_mean_shift_* moves seeds to their modes, pn_mean_shift_merge_* turns modes into
+ * centres, pn_mean_shift_labels_* labels the indexed rows.  Euclidean indexes only (a Cosine index: PN_ERR_UNSUPPORTED),
+ * f32 and f64; T is the index's element type.  Every operation below is plain IEEE f64, unfused, unless it says T.
+ * The contract:
+ *   One step of a seed at position p (T, dim columns) with bandwidth h (T):
+ *     List L = what pn_query_radii_* returns for p with radius h and flags 0: the rows with distance < h (strict), in
+ *       ascending row index; h <= 0 or NaN gives an empty list; m = its length.
+ *     Dead seed: m == 0 -- the position is unchanged and points_within = 0.
+ *     Sum, fixed shape, for every column c, with x = the indexed rows as given at index build:
+ *       lane partial P_l = (...((0.0 + (double)x[L_l][c]) + (double)x[L_{l+64}][c]) + ...) for l = 0 .. 63 (missing
+ *       positions add nothing),  S_c = (...((P_0 + P_1) + P_2) ... + P_63).
+ *       This is the shape of the pn_kde_* sum: the result depends on the list alone -- no floating-point atomics, no
+ *       reduction whose shape depends on the launch, PN_OPT_MS_PIECE or scheduling.
+ *     New position p'_c = (T)(S_c / (double)m).
+ *     Shift: dd_c = (double)p'_c - (double)p_c, t_c = dd_c * dd_c, summed in the same 64-partial shape over the columns
+ *       (column c goes to partial c mod 64, ascending c within a partial), shift = sqrt(that sum), correctly rounded.
+ *   Mode seeking, a seed starting at p^0, t = 1, 2, ...: at iteration t take the list at p^(t-1).  An empty list: the seed
+ *     stops dead -- mode = p^(t-1), points_within = 0, iterations = t - 1, shift = NaN.  Otherwise p^t is the step's
+ *     result, and the seed stops when shift <= tol or t == max_iter: mode = p^t, points_within = m (the list the last mean
+ *     was taken over, as in scikit-learn), iterations = t, shift = the last one.  max_iter = 1 is exactly one step.  A
+ *     seed that has stopped is never queried again.  This is scikit-learn's _mean_shift_single_seed with '<' for '<='.
+ *   Merge of modes [ns][dim], points_within [ns] at bandwidth h (T, one value): dead seeds (points_within = 0) take no
+ *     part.  The live ones are ranked by (points_within descending, seed number ascending) -- one 64-bit key; scikit-learn
+ *     breaks ties of points_within by the coordinates instead.  Walking the ranks, a mode is a centre iff no earlier
+ *     centre c has d(centre_c, mode) < h, d = the library's Euclidean distance in T, the bits of pn_euclidean_*.  Centres
+ *     are numbered in rank order.  (A points_within above 2^31 - 1, which only a caller's own counts can hold, ranks as
+ *     2^31 - 1.)  centre_of_seed[i] = the lowest-numbered centre within h of mode i (a centre's own
+ *     number), -1 for a dead seed.  centre_points[c] = that centre's points_within.  Rows of centres_out and
+ *     centre_points_out at and beyond n_centres are not written.
+ *   Labels: labels[i] = the answer of a k = 1 pn_query_* for indexed row i on an index made of the centres: the nearest
+ *     centre by (distance, centre number).  With PN_MS_ORPHANS a row whose nearest centre is not < h away gets -1
+ *     (scikit-learn's cluster_all = False); without it h is not looked at.  nc == 0 gives all -1.
+ * pn_mean_shift_*: seeds [ns] rows of s_cols columns; s_cols must equal the index's dim (no zip truncation: a mean needs
+ * every column).  PN_MS_SEED_ROWS: the indexed rows are the seeds -- seeds must be NULL, ns is taken as n.  h: n_h = 1 (one
+ * bandwidth) or ns (one per seed).  tol: a double >= 0.  Outputs by seed: modes_out [ns][dim] dense, points_within_out,
+ * iterations_out (nullable), shift_out (nullable); work (nullable, HOST memory in both entries) = {iterations run,
+ * seed-steps}: the second is the sum over the iterations of the seeds queried in that iteration.  pn_stats.queries
+ * advances by the seed-steps.  PN_OPT_INDEX_BASE affects no output.
+ * Argument errors, before any device is touched and in this order: unknown flags; tol NaN or negative; max_iter == 0;
+ * NULL outputs (modes, points_within; merge: centres, n_centres; labels: labels); NULL inputs (seeds -- or seeds given
+ * with PN_MS_SEED_ROWS --, h; merge: modes, points_within; labels: centres with nc > 0); n_h neither 1 nor ns; s_cols == 0;
+ * NULL index; wrong element type: PN_ERR_INVALID; a Cosine index: PN_ERR_UNSUPPORTED; then, with the handle: s_cols other
+ * than dim, n_h neither 1 nor n with PN_MS_SEED_ROWS: PN_ERR_INVALID; more than 2^31 - 1 rows or seeds:
+ * PN_ERR_UNSUPPORTED.  ns = 0 writes nothing and succeeds (merge: n_centres = 0).
+ * Device entry points: everything in HBM but work, written in stream order on `stream`.  Mode seeking BLOCKS THE HOST
+ * TWICE PER ITERATION: once after the counting pass, to read the active seeds' offsets it cuts the pieces from, and once
+ * after the compaction, to read the number of seeds that go on -- it is not capturable into a graph.  Merge and labels
+ * never wait: the merge is a rank sort and 2 ceil(ns / 1024) launches, the labels are one launch.
+ * Device memory: mode seeking 2 (dim + 1) sizeof T + 24 bytes per seed, 8 bytes per entry of the largest piece (at most
+ * 2^18 seeds and PN_OPT_MS_PIECE entries), and the radius pipeline's workspace -- for a piece that of a batch of at most
+ * 2^18 queries, for the counting pass, which takes the active seeds in one call, a padded copy of their positions and 12
+ * bytes per (seed, row segment): proportional to the active seeds, never ns x lists.  Merge: 16 N + 12 ns + 40 bytes
+ * with N = ns rounded up to a power of two, at least 1024 (28 to 44 bytes per seed at large ns) -- no ns x ns graph.  Known slow case of the merge: a bandwidth so small that nearly every mode is a centre -- the
+ * exact work is ns x n_centres x dim.
+ * Not in this version: row-sharded handles, Cosine, kernels other than the flat one, estimate_bandwidth. */
+#define PN_MS_SEED_ROWS 4
+#define PN_MS_ORPHANS 8
+int pn_mean_shift_f32(const pn_index *index, const float *seeds, size_t ns, size_t s_cols, ptrdiff_t s_row_stride,
+                      const float *h, size_t n_h, double tol, size_t max_iter, unsigned flags, float *modes_out,
+                      uint64_t *points_within_out, uint32_t *iterations_out, double *shift_out, uint64_t *work);
+int pn_mean_shift_device_f32(const pn_index *index, const float *d_seeds, size_t ns, size_t s_cols, size_t s_row_stride,
+                             const float *d_h, size_t n_h, double tol, size_t max_iter, unsigned flags, float *d_modes,
+                             uint64_t *d_points_within, uint32_t *d_iterations, double *d_shift, uint64_t *work,
+                             void *stream);
+int pn_mean_shift_merge_f32(const pn_index *index, const float *modes, size_t ns, const uint64_t *points_within,
+                            float h, unsigned flags, float *centres_out, uint64_t *centre_points_out,
+                            int64_t *centre_of_seed_out, uint64_t *n_centres_out);
+int pn_mean_shift_merge_device_f32(const pn_index *index, const float *d_modes, size_t ns,
+                                   const uint64_t *d_points_within, float h, unsigned flags, float *d_centres,
+                                   uint64_t *d_centre_points, int64_t *d_centre_of_seed, uint64_t *d_n_centres,
+                                   void *stream);
+int pn_mean_shift_labels_f32(const pn_index *index, const float *centres, size_t nc, float h, unsigned flags,
+                             int64_t *labels);
+int pn_mean_shift_labels_device_f32(const pn_index *index, const float *d_centres, size_t nc, float h, unsigned flags,
+                                    int64_t *d_labels, void *stream);
+int pn_mean_shift_f64(const pn_index *index, const double *seeds, size_t ns, size_t s_cols, ptrdiff_t s_row_stride,
+                      const double *h, size_t n_h, double tol, size_t max_iter, unsigned flags, double *modes_out,
+                      uint64_t *points_within_out, uint32_t *iterations_out, double *shift_out, uint64_t *work);
+int pn_mean_shift_device_f64(const pn_index *index, const double *d_seeds, size_t ns, size_t s_cols,
+                             size_t s_row_stride, const double *d_h, size_t n_h, double tol, size_t max_iter,
+                             unsigned flags, double *d_modes, uint64_t *d_points_within, uint32_t *d_iterations,
+                             double *d_shift, uint64_t *work, void *stream);
+int pn_mean_shift_merge_f64(const pn_index *index, const double *modes, size_t ns, const uint64_t *points_within,
+                            double h, unsigned flags, double *centres_out, uint64_t *centre_points_out,
+                            int64_t *centre_of_seed_out, uint64_t *n_centres_out);
+int pn_mean_shift_merge_device_f64(const pn_index *index, const double *d_modes, size_t ns,
+                                   const uint64_t *d_points_within, double h, unsigned flags, double *d_centres,
+                                   uint64_t *d_centre_points, int64_t *d_centre_of_seed, uint64_t *d_n_centres,
+                                   void *stream);
+int pn_mean_shift_labels_f64(const pn_index *index, const double *centres, size_t nc, double h, unsigned flags,
+                             int64_t *labels);
+int pn_mean_shift_labels_device_f64(const pn_index *index, const double *d_centres, size_t nc, double h, unsigned flags,
+                                    int64_t *d_labels, void *stream);
 
 /* ---- distance::pairwise(x, &Euclidean) (src/distance.rs:58-74): n x n
  * symmetric matrix, zero diagonal, n < 2 -> zeros. Host in, host out. */

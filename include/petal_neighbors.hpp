@@ -125,6 +125,22 @@ struct Kde {
     std::vector<size_t> count;
     std::vector<A> cutoff;
 };
+// the answers of BallTree::mean_shift_modes / mean_shift_merge / mean_shift: modes [ns][dim] dense, per seed the rows within
+// the bandwidth of the last mean (0: a dead seed), the iterations and the last shift (NaN: dead); centres [n_centres][dim]
+// in rank order with their points, centre_of_seed (-1: dead); labels per indexed row (-1: an orphan)
+template <typename A>
+struct MeanShift {
+    std::vector<A> modes;
+    std::vector<size_t> points_within;
+    std::vector<uint32_t> iterations;
+    std::vector<double> shift;
+    size_t n_iter = 0, seed_steps = 0;
+    std::vector<A> centres;
+    std::vector<size_t> centre_points;
+    std::vector<int64_t> centre_of_seed;
+    size_t n_centres = 0;
+    std::vector<int64_t> labels;
+};
 // the answer of BallTree::optics: ordering[t] = the t-th row OPTICS visits (a plain row number); reachability, predecessor
 // (-1 = none) and core_distances are indexed by row, +inf where undefined
 template <typename A>
@@ -471,6 +487,70 @@ class BallTree {
         else
             check(pn_kde_f64(h_, queries, nq, dim_, (ptrdiff_t)dim_, &r, 1, PN_KDE_TOPHAT, 0.0, 0u, nullptr, out, nullptr));
         return std::vector<size_t>(cnt.begin(), cnt.end());
+    }
+    // extension: mean shift on the device (pn_mean_shift_*; scikit-learn's MeanShift with its flat kernel, every radius a
+    // strict '<').  mean_shift_modes moves the seeds (seeds == nullptr: every indexed row) to their modes; only the seeds
+    // still moving are queried.  tol < 0: 1e-3 * h
+    MeanShift<A> mean_shift_modes(A h, const A *seeds = nullptr, size_t ns = 0, double tol = -1.0, size_t max_iter = 300) const {
+        MeanShift<A> res;
+        const bool rows = seeds == nullptr;
+        if (rows) ns = n_;
+        res.modes.resize(ns * dim_ + 1);
+        res.iterations.resize(ns + 1);
+        res.shift.resize(ns + 1);
+        std::vector<uint64_t> pw(ns + 1);
+        uint64_t work[2] = {0, 0};
+        if (tol < 0.0) tol = 1e-3 * (double)h;
+        const unsigned flags = rows ? (unsigned)PN_MS_SEED_ROWS : 0u;
+        if constexpr (kF32)
+            check(pn_mean_shift_f32(h_, seeds, rows ? 0 : ns, dim_, (ptrdiff_t)dim_, &h, 1, tol, max_iter, flags, res.modes.data(),
+                                    pw.data(), res.iterations.data(), res.shift.data(), work));
+        else
+            check(pn_mean_shift_f64(h_, seeds, rows ? 0 : ns, dim_, (ptrdiff_t)dim_, &h, 1, tol, max_iter, flags, res.modes.data(),
+                                    pw.data(), res.iterations.data(), res.shift.data(), work));
+        res.modes.resize(ns * dim_);
+        res.iterations.resize(ns);
+        res.shift.resize(ns);
+        res.points_within.assign(pw.begin(), pw.begin() + ns);
+        res.n_iter = (size_t)work[0];
+        res.seed_steps = (size_t)work[1];
+        return res;
+    }
+    // ... the merge of res.modes into res.centres (ranked by points_within descending, then seed number)
+    void mean_shift_merge(MeanShift<A> &res, A h) const {
+        const size_t ns = res.points_within.size();
+        std::vector<uint64_t> pw(res.points_within.begin(), res.points_within.end()), cp(ns + 1);
+        res.centres.resize(ns * dim_ + 1);
+        res.centre_of_seed.resize(ns + 1);
+        uint64_t nc = 0;
+        if constexpr (kF32)
+            check(pn_mean_shift_merge_f32(h_, res.modes.data(), ns, pw.data(), h, 0u, res.centres.data(), cp.data(),
+                                          res.centre_of_seed.data(), &nc));
+        else
+            check(pn_mean_shift_merge_f64(h_, res.modes.data(), ns, pw.data(), h, 0u, res.centres.data(), cp.data(),
+                                          res.centre_of_seed.data(), &nc));
+        res.n_centres = (size_t)nc;
+        res.centres.resize(res.n_centres * dim_);
+        res.centre_of_seed.resize(ns);
+        res.centre_points.assign(cp.begin(), cp.begin() + res.n_centres);
+    }
+    // ... the nearest centre of every indexed row; cluster_all = false: -1 unless it is within h
+    void mean_shift_labels(MeanShift<A> &res, A h, bool cluster_all = true) const {
+        res.labels.resize(n_ + 1);
+        const unsigned flags = cluster_all ? 0u : (unsigned)PN_MS_ORPHANS;
+        if constexpr (kF32)
+            check(pn_mean_shift_labels_f32(h_, res.centres.data(), res.n_centres, h, flags, res.labels.data()));
+        else
+            check(pn_mean_shift_labels_f64(h_, res.centres.data(), res.n_centres, h, flags, res.labels.data()));
+        res.labels.resize(n_);
+    }
+    // ... the three in a row: scikit-learn's MeanShift(bandwidth = h, seeds, cluster_all).fit(rows)
+    MeanShift<A> mean_shift(A h, const A *seeds = nullptr, size_t ns = 0, bool cluster_all = true, double tol = -1.0,
+                            size_t max_iter = 300) const {
+        MeanShift<A> res = mean_shift_modes(h, seeds, ns, tol, max_iter);
+        mean_shift_merge(res, h);
+        mean_shift_labels(res, h, cluster_all);
+        return res;
     }
     // extension: OPTICS on the device (pn_optics_*): scikit-learn's OPTICS(min_samples + 1, max_eps) on this library's
     // distances; min_samples counts OTHER rows, every radius is a strict '<'

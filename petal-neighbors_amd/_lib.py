@@ -26,9 +26,12 @@ PN_OPT_DBSCAN_PIECE = 11
 PN_OPT_MST_BATCH = 12
 PN_OPT_OPTICS_PIECE = 13
 PN_OPT_KDE_PIECE = 14
+PN_OPT_MS_PIECE = 15
 PN_KDE_GAUSSIAN, PN_KDE_TOPHAT, PN_KDE_EPANECHNIKOV, PN_KDE_EXPONENTIAL, PN_KDE_LINEAR = 0, 1, 2, 3, 4
 PN_RADIUS_SORTED = 1
 PN_SELF_INCLUDE = 2
+PN_MS_SEED_ROWS = 4
+PN_MS_ORPHANS = 8
 
 
 class PnInfo(C.Structure):
@@ -138,6 +141,20 @@ SIGNATURES = {
     "pn_kde_self_f64": (_i, [_vp, _vp, _sz, C.c_int, C.c_double, C.c_uint, _vp, _vp, _vp]),
     "pn_kde_self_device_f32": (_i, [_vp, _vp, _sz, C.c_int, C.c_double, C.c_uint, _vp, _vp, _vp, _vp]),
     "pn_kde_self_device_f64": (_i, [_vp, _vp, _sz, C.c_int, C.c_double, C.c_uint, _vp, _vp, _vp, _vp]),
+    "pn_mean_shift_f32": (_i, [_vp, _vp, _sz, _sz, _ssz, _vp, _sz, C.c_double, _sz, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
+    "pn_mean_shift_device_f32": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _sz, C.c_double, _sz, C.c_uint, _vp, _vp, _vp, _vp, _vp,
+                                    _vp]),
+    "pn_mean_shift_merge_f32": (_i, [_vp, _vp, _sz, _vp, C.c_float, C.c_uint, _vp, _vp, _vp, _vp]),
+    "pn_mean_shift_merge_device_f32": (_i, [_vp, _vp, _sz, _vp, C.c_float, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
+    "pn_mean_shift_labels_f32": (_i, [_vp, _vp, _sz, C.c_float, C.c_uint, _vp]),
+    "pn_mean_shift_labels_device_f32": (_i, [_vp, _vp, _sz, C.c_float, C.c_uint, _vp, _vp]),
+    "pn_mean_shift_f64": (_i, [_vp, _vp, _sz, _sz, _ssz, _vp, _sz, C.c_double, _sz, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
+    "pn_mean_shift_device_f64": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _sz, C.c_double, _sz, C.c_uint, _vp, _vp, _vp, _vp, _vp,
+                                    _vp]),
+    "pn_mean_shift_merge_f64": (_i, [_vp, _vp, _sz, _vp, C.c_double, C.c_uint, _vp, _vp, _vp, _vp]),
+    "pn_mean_shift_merge_device_f64": (_i, [_vp, _vp, _sz, _vp, C.c_double, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
+    "pn_mean_shift_labels_f64": (_i, [_vp, _vp, _sz, C.c_double, C.c_uint, _vp]),
+    "pn_mean_shift_labels_device_f64": (_i, [_vp, _vp, _sz, C.c_double, C.c_uint, _vp, _vp]),
     "pn_optics_f32": (_i, [_vp, _sz, C.c_float, C.c_uint, _vp, _vp, _vp, _vp]),
     "pn_optics_f64": (_i, [_vp, _sz, C.c_double, C.c_uint, _vp, _vp, _vp, _vp]),
     "pn_optics_device_f32": (_i, [_vp, _sz, C.c_float, C.c_uint, _vp, _vp, _vp, _vp, _vp]),

@@ -64,6 +64,24 @@ def kde_log_norm(kernel: str, dim: int, h):
     return -factor - d * np.log(np.asarray(h, dtype=np.float64))
 
 
+def mean_shift_bin_seeds(X, bin_size, min_bin_freq: int = 1):
+    """Seeds for ``BallTree.mean_shift`` on a grid of cell size ``bin_size``: the centres of the cells that hold at least
+    ``min_bin_freq`` rows of ``X``, the same set of rows as scikit-learn's ``get_bin_seeds`` (``X`` itself when
+    ``bin_size`` is 0, or when every row is a cell of its own)."""
+    X = np.asarray(X)
+    if X.ndim != 2:
+        raise ValueError("X must be 2-D")
+    if not (float(bin_size) >= 0.0):
+        raise ValueError("bin_size must be >= 0")
+    if bin_size == 0:
+        return X
+    cells, counts = np.unique(np.round(X / bin_size), axis=0, return_counts=True)
+    seeds = cells[counts >= min_bin_freq].astype(np.float32)  # (scikit-learn keeps its cell points in float32)
+    if seeds.shape[0] == X.shape[0]:
+        return X
+    return seeds * bin_size
+
+
 class BallTree:
     """``BallTree<'a, A, Euclidean>``: ``points`` / ``metric`` stay readable like the pub fields
     at src/ball_tree.rs:20-23 (``idx`` and ``nodes`` do not exist: no tree is built)."""
@@ -1144,3 +1162,193 @@ class BallTree:
             raise ValueError("r must be 1-D")
         a = self._queries(queries, False)
         return np.array([int(self.query_radius_count(a, x).sum()) for x in ra.tolist()], dtype=np.int64)
+
+    # -------------------------------------------------- mean shift
+    # scikit-learn's ``MeanShift`` (flat kernel) on the device (``pn_mean_shift_*``): seeds climb to the modes of the tophat
+    # density, every step the mean of a radius list summed by one wave in a fixed order; only the seeds still moving are
+    # queried.  Then the converged modes are merged into centres and the rows labelled.  Every comparison is a strict '<'.
+    def _ms_check(self):
+        from .distance import Cosine
+        if isinstance(self.metric, Cosine):
+            raise ValueError("mean shift needs a Euclidean tree")
+
+    def _ms_h(self, h, count):
+        ha = self._radii(h, count)
+        if ha is None:
+            ha = np.array([h], dtype=self.dtype)
+        return ha
+
+    @staticmethod
+    def _ms_tol(h, tol, max_iter):
+        if tol is None:
+            if np.ndim(h) != 0:
+                raise ValueError("tol must be given with one bandwidth per seed")
+            tol = 1e-3 * float(h)
+        tol = float(tol)
+        if not (tol >= 0.0):
+            raise ValueError("tol must be >= 0")
+        if int(max_iter) < 1:
+            raise ValueError("max_iter must be at least 1")
+        return tol, int(max_iter)
+
+    def mean_shift_modes(self, h, seeds=None, tol=None, max_iter: int = 300, full: bool = False):
+        """Moves every seed (``seeds=None``: every indexed row) to its mode with bandwidth ``h`` (a scalar, or one per seed):
+        ``(modes [ns][dim], points_within uint64 [ns])``; with ``full=True`` also ``iterations uint32 [ns]``,
+        ``shift float64 [ns]`` and ``work = (iterations run, seed-steps)``.  A seed with no row within ``h`` is dead:
+        ``points_within`` 0, ``shift`` NaN.  ``tol`` defaults to ``1e-3 * h``.  ``last_n_iter`` holds the iterations run."""
+        self._ms_check()
+        tol, max_iter = self._ms_tol(h, tol, max_iter)
+        if seeds is None:
+            a, ns, flags = None, self._n, _lib.PN_MS_SEED_ROWS
+        else:
+            a = self._queries(seeds, False)
+            ns, flags = a.shape[0], 0
+            if a.shape[1] != self._dim:
+                raise ValueError(f"seeds must have the tree's {self._dim} columns")
+        ha = self._ms_h(h, ns)
+        modes = np.zeros((ns, self._dim), dtype=self.dtype)
+        pw = np.zeros(ns, dtype=np.uint64)
+        it = np.zeros(ns, dtype=np.uint32)
+        sh = np.zeros(ns, dtype=np.float64)
+        work = np.zeros(2, dtype=np.uint64)
+        check(getattr(_lib.lib(), f"pn_mean_shift_{self._sfx}")(
+            self._h, None if a is None else a.ctypes.data, 0 if a is None else ns, self._dim, self._dim, ha.ctypes.data,
+            ha.shape[0], tol, max_iter, flags, modes.ctypes.data, pw.ctypes.data, it.ctypes.data, sh.ctypes.data,
+            work.ctypes.data))
+        self.last_n_iter = int(work[0])
+        return (modes, pw, it, sh, (int(work[0]), int(work[1]))) if full else (modes, pw)
+
+    def mean_shift_modes_device(self, h, seeds=None, tol=None, max_iter: int = 300, stream=None):
+        """``mean_shift_modes`` in HBM: ``seeds`` a 2-D CUDA tensor of the tree's element type (or None: the indexed rows),
+        ``h`` a scalar or a 1-D CUDA tensor of one bandwidth per seed; returns CUDA tensors ``(modes, points_within int64,
+        iterations int32, shift float64)`` and ``work``.  The call waits for the device twice per iteration and cannot
+        be captured into a graph."""
+        import torch
+        self._ms_check()
+        tol, max_iter = self._ms_tol(h, tol, max_iter)
+        tdt = torch.float32 if self._sfx == "f32" else torch.float64
+        dev = torch.device("cuda", self.device)
+        if seeds is None:
+            ns, flags, sp, stride = self._n, _lib.PN_MS_SEED_ROWS, None, 0
+        else:
+            if (not isinstance(seeds, torch.Tensor) or seeds.dtype != tdt or seeds.dim() != 2 or not seeds.is_cuda
+                    or seeds.device.index != self.device):
+                raise ValueError(f"seeds must be a 2-D {tdt} CUDA tensor on the tree's device")
+            if seeds.shape[1] != self._dim:
+                raise ValueError(f"seeds must have the tree's {self._dim} columns")
+            if seeds.shape[1] > 1 and seeds.stride(1) != 1:
+                seeds = seeds.contiguous()
+            ns, flags, sp = seeds.shape[0], 0, seeds.data_ptr()
+            stride = seeds.stride(0) if ns > 1 else self._dim
+        ht = self._radii_device(h, ns, dev)
+        if ht is None:
+            ht = torch.full((1,), float(h), dtype=tdt, device=dev)
+        modes = torch.zeros((ns, self._dim), dtype=tdt, device=dev)
+        pw = torch.zeros(ns, dtype=torch.int64, device=dev)
+        it = torch.zeros(ns, dtype=torch.int32, device=dev)
+        sh = torch.zeros(ns, dtype=torch.float64, device=dev)
+        work = np.zeros(2, dtype=np.uint64)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        check(getattr(_lib.lib(), f"pn_mean_shift_device_{self._sfx}")(
+            self._h, sp, 0 if seeds is None else ns, self._dim, stride, ht.data_ptr(), ht.shape[0], tol, max_iter, flags,
+            modes.data_ptr(), pw.data_ptr(), it.data_ptr(), sh.data_ptr(), work.ctypes.data, C.c_void_p(st)))
+        self.last_n_iter = int(work[0])
+        return modes, pw, it, sh, (int(work[0]), int(work[1]))
+
+    def mean_shift_merge(self, modes, points_within, h):
+        """scikit-learn's merge of converged modes: ``(centres [nc][dim], centre_points uint64 [nc], centre_of_seed int64
+        [ns])``.  Live modes are ranked by (``points_within`` descending, seed ascending); a mode is a centre iff no earlier
+        centre lies within ``h``; ``centre_of_seed`` is the lowest-numbered centre within ``h``, -1 for a dead seed."""
+        self._ms_check()
+        m = self._queries(modes, False)
+        if m.shape[1] != self._dim:
+            raise ValueError(f"modes must have the tree's {self._dim} columns")
+        ns = m.shape[0]
+        pw = np.ascontiguousarray(points_within, dtype=np.uint64)
+        if pw.shape != (ns,):
+            raise ValueError("points_within must hold one count per mode")
+        if np.ndim(h) != 0:
+            raise ValueError("the merge takes one bandwidth")
+        centres = np.zeros((ns, self._dim), dtype=self.dtype)
+        cp = np.zeros(ns, dtype=np.uint64)
+        cos = np.zeros(ns, dtype=np.int64)
+        nc = C.c_uint64(0)
+        check(getattr(_lib.lib(), f"pn_mean_shift_merge_{self._sfx}")(
+            self._h, m.ctypes.data if ns else None, ns, pw.ctypes.data if ns else None, float(h), 0, centres.ctypes.data,
+            cp.ctypes.data, cos.ctypes.data, C.byref(nc)))
+        k = int(nc.value)
+        return centres[:k].copy(), cp[:k].copy(), cos
+
+    def mean_shift_merge_device(self, modes, points_within, h, stream=None):
+        """``mean_shift_merge`` in HBM: CUDA tensors in, ``(centres [ns][dim], centre_points int64 [ns], centre_of_seed int64
+        [ns], n_centres int64 [1])`` out -- the first ``n_centres`` rows of the first two are written.  Never waits."""
+        import torch
+        self._ms_check()
+        tdt = torch.float32 if self._sfx == "f32" else torch.float64
+        dev = torch.device("cuda", self.device)
+        if (not isinstance(modes, torch.Tensor) or modes.dtype != tdt or modes.dim() != 2 or modes.shape[1] != self._dim
+                or not self._lof_on_device(modes, tdt, 0)):
+            raise ValueError(f"modes must be a contiguous [ns][{self._dim}] {tdt} CUDA tensor on the tree's device")
+        ns = modes.shape[0]
+        if not self._lof_on_device(points_within, torch.int64, ns) or points_within.numel() != ns:
+            raise ValueError("points_within must be a contiguous int64 CUDA tensor of one count per mode")
+        if np.ndim(h) != 0:
+            raise ValueError("the merge takes one bandwidth")
+        centres = torch.zeros((ns, self._dim), dtype=tdt, device=dev)
+        cp = torch.zeros(ns, dtype=torch.int64, device=dev)
+        cos = torch.zeros(ns, dtype=torch.int64, device=dev)
+        nc = torch.zeros(1, dtype=torch.int64, device=dev)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        check(getattr(_lib.lib(), f"pn_mean_shift_merge_device_{self._sfx}")(
+            self._h, modes.data_ptr() if ns else None, ns, points_within.data_ptr() if ns else None, float(h), 0,
+            centres.data_ptr(), cp.data_ptr(), cos.data_ptr(), nc.data_ptr(), C.c_void_p(st)))
+        return centres, cp, cos, nc
+
+    def mean_shift_labels(self, centres, h, cluster_all: bool = True):
+        """The nearest centre of every indexed row by (distance, centre number): ``int64 [n]``; with
+        ``cluster_all=False`` a row whose nearest centre is not within ``h`` gets -1."""
+        self._ms_check()
+        c = self._queries(centres, False)
+        if c.shape[0] and c.shape[1] != self._dim:
+            raise ValueError(f"centres must have the tree's {self._dim} columns")
+        if np.ndim(h) != 0:
+            raise ValueError("the labels take one bandwidth")
+        labels = np.empty(self._n, dtype=np.int64)
+        check(getattr(_lib.lib(), f"pn_mean_shift_labels_{self._sfx}")(
+            self._h, c.ctypes.data if c.shape[0] else None, c.shape[0], float(h), 0 if cluster_all else _lib.PN_MS_ORPHANS,
+            labels.ctypes.data))
+        return labels
+
+    def mean_shift_labels_device(self, centres, h, cluster_all: bool = True, n_centres=None, out_labels=None, stream=None):
+        """``mean_shift_labels`` in HBM: ``centres`` a contiguous 2-D CUDA tensor, of which the first ``n_centres`` rows
+        (default: all) are the centres; returns the labels, a CUDA int64 tensor.  Never waits."""
+        import torch
+        self._ms_check()
+        tdt = torch.float32 if self._sfx == "f32" else torch.float64
+        dev = torch.device("cuda", self.device)
+        if (not isinstance(centres, torch.Tensor) or centres.dim() != 2 or not self._lof_on_device(centres, tdt, 0)
+                or (centres.shape[0] and centres.shape[1] != self._dim)):
+            raise ValueError(f"centres must be a contiguous [nc][{self._dim}] {tdt} CUDA tensor on the tree's device")
+        nc = centres.shape[0] if n_centres is None else int(n_centres)
+        if nc < 0 or nc > centres.shape[0]:
+            raise ValueError("n_centres exceeds the rows of centres")
+        if np.ndim(h) != 0:
+            raise ValueError("the labels take one bandwidth")
+        if out_labels is not None and not self._lof_on_device(out_labels, torch.int64, self._n):
+            raise ValueError(f"out_labels must be a contiguous int64 CUDA tensor of at least {self._n} values")
+        labels = out_labels if out_labels is not None else torch.empty(self._n, dtype=torch.int64, device=dev)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        check(getattr(_lib.lib(), f"pn_mean_shift_labels_device_{self._sfx}")(
+            self._h, centres.data_ptr() if nc else None, nc, float(h), 0 if cluster_all else _lib.PN_MS_ORPHANS,
+            labels.data_ptr(), C.c_void_p(st)))
+        return labels
+
+    def mean_shift(self, h, seeds=None, cluster_all: bool = True, tol=None, max_iter: int = 300):
+        """scikit-learn's ``MeanShift(bandwidth=h, seeds=seeds, cluster_all=cluster_all).fit(rows)``: ``(labels int64 [n],
+        centres [nc][dim])``; ``last_n_iter`` holds the iterations run.  ``seeds=None``: every row is a seed
+        (``mean_shift_bin_seeds`` gives scikit-learn's ``bin_seeding``)."""
+        if np.ndim(h) != 0:
+            raise ValueError("mean_shift takes one bandwidth")
+        modes, pw = self.mean_shift_modes(h, seeds, tol, max_iter)
+        centres, _, _ = self.mean_shift_merge(modes, pw, h)
+        return self.mean_shift_labels(centres, h, cluster_all), centres

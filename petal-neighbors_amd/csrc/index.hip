@@ -164,6 +164,9 @@ struct Workspace {
     // pn_kde_*: the O(nq) arrays of a call (offsets, bandwidths, cutoffs; + count when the caller keeps none), and the host
     // entries' inputs and outputs
     DevBuf w_kde, w_kde_io;
+    // pn_mean_shift_*: the O(active seeds) arrays of a call (offsets, two copies of positions, bandwidths and slots, the
+    // stop flags) or the merge's scratch, and the host entries' inputs and outputs
+    DevBuf w_ms, w_ms_io;
     // small calls (tiny_*): mapped pinned host memory the one kernel of the call reads its queries from and writes its
     // answers to -- no copy commands
     void *pin_in = nullptr, *pin_out = nullptr;
@@ -189,7 +192,7 @@ struct Workspace {
     hipEvent_t done = nullptr;
     hipStream_t last_stream = nullptr;
     bool in_flight = false;
-    DevBuf *all[66] = {&w_kde, &w_kde_io, &w_opt, &w_opt_graph, &w_opt_io, &w_lof, &w_lof_io, &w_hdb, &w_hdb_io, &w_mst, &w_mst_io, &w_db, &w_db_side, &w_db_out, &w_hrad, &w_sf_idx, &w_sf_dist, &w_sf_off, &w_sf_coff, &w_sf_flag, &w_sf_cnt, &w_sf_scan, &w_sf_hoff, &w_cs_hoff, &w_rkd, &w_cs_nch, &w_cs_off, &w_cs_scan, &w_cs_idx, &w_cs_dist, &w_gqn, &w_rpos, &w_rfin, &w_rcx, &w_rox, &w_rscan, &w_q, &w_qnorm, &w_qnrm, &w_keys, &w_idx, &w_cnt, &w_tau, &w_flags, &w_sel, &w_misc, &w2_keys, &w2_idx,
+    DevBuf *all[68] = {&w_ms, &w_ms_io, &w_kde, &w_kde_io, &w_opt, &w_opt_graph, &w_opt_io, &w_lof, &w_lof_io, &w_hdb, &w_hdb_io, &w_mst, &w_mst_io, &w_db, &w_db_side, &w_db_out, &w_hrad, &w_sf_idx, &w_sf_dist, &w_sf_off, &w_sf_coff, &w_sf_flag, &w_sf_cnt, &w_sf_scan, &w_sf_hoff, &w_cs_hoff, &w_rkd, &w_cs_nch, &w_cs_off, &w_cs_scan, &w_cs_idx, &w_cs_dist, &w_gqn, &w_rpos, &w_rfin, &w_rcx, &w_rox, &w_rscan, &w_q, &w_qnorm, &w_qnrm, &w_keys, &w_idx, &w_cnt, &w_tau, &w_flags, &w_sel, &w_misc, &w2_keys, &w2_idx,
                        &w2_cnt, &w2_tau, &w_lo, &w_bq, &w_qn, &w_qbad, &w_gq, &w_gidx, &w_gdist, &w_gsel, &w_seed,
                        &w_qstat, &w_lists, &w_hq, &w_hidx, &w_hdist, &w_fparts, &w_pcnt};
     std::vector<void *> retired;  // outgrown allocations, freed once `done` has passed (DevBuf::ensure)
@@ -260,6 +263,7 @@ struct pn_index {
     uint64_t mst_batch = 0;     // PN_OPT_MST_BATCH: listed rows per scan launch of pn_mst_*, 0 = 2^18
     uint64_t optics_piece = 0;  // PN_OPT_OPTICS_PIECE: list entries per fill piece of pn_optics_*, 0 = 2^27
     uint64_t kde_piece = 0;     // PN_OPT_KDE_PIECE: list entries per piece of pn_kde_*, 0 = 2^27
+    uint64_t ms_piece = 0;      // PN_OPT_MS_PIECE: list entries per piece of pn_mean_shift_*, 0 = 2^27
     // state that queries on a shared `const pn_index *` update: internally synchronised by `mu`
     struct Shared {
         std::mutex mu;
@@ -1017,6 +1021,10 @@ extern "C" int pn_index_set_option(pn_index *ix, int option, int64_t value) {
         case PN_OPT_KDE_PIECE:
             if (value < 0) return fail(PN_ERR_INVALID, "bad KDE piece size");
             ix->kde_piece = (uint64_t)value;
+            return PN_OK;
+        case PN_OPT_MS_PIECE:
+            if (value < 0) return fail(PN_ERR_INVALID, "bad mean shift piece size");
+            ix->ms_piece = (uint64_t)value;
             return PN_OK;
         default: return fail(PN_ERR_INVALID, "unknown option %d", option);
     }
@@ -4873,6 +4881,336 @@ extern "C" int pn_kde_self_device_f64(const pn_index *ix, const double *d_h, siz
     return kde_device<double>(ix, true, nullptr, 0, 0, 0, d_h, n_h, kernel, atol, flags, d_sum, d_count, d_cutoff,
                               (hipStream_t)stream);
 }
+
+// ---------------------------------------------------------------------------
+// Mean shift: pn_mean_shift_{,device_}*, pn_mean_shift_merge_{,device_}*, pn_mean_shift_labels_{,device_}* (the kernels and
+// the shape of the sums: mean_shift.hip).  Mode seeking keeps a dense array of the seeds still moving; per iteration:
+//   1. count: radius_device_enqueue with capacity 0 over the active positions through the d_radii path (a constant array
+//      gives the scalar call's thresholds word for word) gives the offsets, which are read back -- the
+//      first host wait of an iteration -- to cut the pieces.
+//   2. step: a piece is a contiguous range of at most 2^18 active seeds whose lists hold at most E entries together
+//      (PN_OPT_MS_PIECE, default 2^27; a longer single list is a piece of its own).  radius_device_enqueue writes the
+//      piece's lists, without distances, into workspace scratch of exactly the piece's total; ms_step_kernel reads them
+//      there, moves the positions in place, and finishes the seeds that stop.
+//   3. compact: the seeds that go on are listed and gathered into the other copy of the arrays; their number is read
+//      back -- the second host wait -- for the next iteration's launches.
+// A seed that has stopped is in no later count, fill or step.  Device memory: 2 (dim + 1) sizeof T + 24 bytes per seed of
+// the call, 8 bytes per entry of the largest piece, and the radius pipeline's workspace -- a piece's is that of at most
+// 2^18 queries; the counting pass takes the active seeds in one call (as kde_enqueue's does), so its padded query copy
+// and its 12 bytes per (seed, row segment) grow with the active seeds.
+// ---------------------------------------------------------------------------
+constexpr uint64_t kMsPiece = (uint64_t)1 << 27;
+constexpr unsigned kMsFlags = PN_MS_SEED_ROWS;
+// (before any device is touched; the header states the order)
+static int ms_args(const pn_index *ix, unsigned flags, double tol, size_t max_iter, const void *modes, const void *points,
+                   const void *seeds, size_t ns, size_t s_cols, const void *h, size_t n_h, int elem_bytes) {
+    const bool rows = (flags & PN_MS_SEED_ROWS) != 0;
+    if (flags & ~kMsFlags) return fail(PN_ERR_INVALID, "unknown mean shift flags 0x%x", flags);
+    if (!(tol >= 0.0)) return fail(PN_ERR_INVALID, "tol must be >= 0");
+    if (max_iter == 0) return fail(PN_ERR_INVALID, "max_iter must be at least 1");
+    if (!modes || !points) return fail(PN_ERR_INVALID, "modes or points_within is NULL");
+    if (rows && seeds) return fail(PN_ERR_INVALID, "seeds must be NULL with PN_MS_SEED_ROWS");
+    if (!rows && ns && !seeds) return fail(PN_ERR_INVALID, "seeds is NULL");
+    if (!h) return fail(PN_ERR_INVALID, "h is NULL");
+    if (n_h != 1 && !rows && n_h != ns) return fail(PN_ERR_INVALID, "n_h must be 1 or the number of seeds (%zu)", ns);
+    if (n_h == 0) return fail(PN_ERR_INVALID, "n_h must be 1 or the number of seeds");
+    if (!rows && s_cols == 0) return fail(PN_ERR_INVALID, "s_cols must be the index's dim");
+    if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
+    if (ix->elem_bytes != elem_bytes) return fail(PN_ERR_INVALID, "index element type mismatch");
+    if (ix->metric != 0) return fail(PN_ERR_UNSUPPORTED, "mean shift needs a Euclidean index");
+    if (!rows && s_cols != ix->dim) return fail(PN_ERR_INVALID, "s_cols must be the index's dim (%zu)", ix->dim);
+    if (rows && n_h != 1 && n_h != ix->n) return fail(PN_ERR_INVALID, "n_h must be 1 or the number of rows (%zu)", ix->n);
+    if (ix->n > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many rows for mean shift");
+    if (ns > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many seeds in one call");
+    return PN_OK;
+}
+// in a held workspace, on stream s; everything in HBM but work (host, nullable); ns >= 1.  Blocks the host twice per
+// iteration.
+template <typename T>
+static int ms_enqueue(const pn_index *ix, Workspace &ws, const T *d_seeds, size_t ns, size_t s_stride, const T *d_h, size_t n_h,
+                      double tol, size_t max_iter, T *d_modes, uint64_t *d_points, uint32_t *d_iters, double *d_shift,
+                      uint64_t *work, hipStream_t s) {
+    const size_t dim = ix->dim;
+    const size_t o_pos = (ns + 2) * sizeof(uint64_t), pos_bytes = round_up(ns * dim * sizeof(T), (size_t)8),
+                 h_bytes = round_up(ns * sizeof(T), (size_t)8), u_bytes = round_up(ns * sizeof(uint32_t), (size_t)8);
+    PNCHK(ws.w_ms.ensure(o_pos + 2 * pos_bytes + 2 * h_bytes + 4 * u_bytes + 16));
+    char *base = (char *)ws.w_ms.p;
+    uint64_t *off = (uint64_t *)base;
+    T *pos[2] = {(T *)(base + o_pos), (T *)(base + o_pos + pos_bytes)};
+    T *hq[2] = {(T *)(base + o_pos + 2 * pos_bytes), (T *)(base + o_pos + 2 * pos_bytes + h_bytes)};
+    char *u = base + o_pos + 2 * pos_bytes + 2 * h_bytes;
+    uint32_t *slot[2] = {(uint32_t *)u, (uint32_t *)(u + u_bytes)};
+    uint32_t *keep = (uint32_t *)(u + 2 * u_bytes), *sel = (uint32_t *)(u + 3 * u_bytes), *nsel = (uint32_t *)(u + 4 * u_bytes);
+    HIPCHK(launch_ms_init<T>(d_seeds, s_stride, ns, (int)dim, d_h, n_h, pos[0], hq[0], slot[0], s));
+    const uint64_t E = ix->ms_piece ? ix->ms_piece : kMsPiece;
+    std::vector<uint64_t> h_off;
+    try {
+        h_off.resize(ns + 1);
+    } catch (const std::bad_alloc &) {
+        return fail(PN_ERR_NOMEM, "host allocation of %zu offsets failed", ns + 1);
+    }
+    PNCHK(ws.w_sf_off.ensure((std::min(ns, kSelfChunk) + 1) * sizeof(uint64_t)));
+    uint64_t iterations = 0, seed_steps = 0;
+    size_t na = ns;
+    int cur = 0;
+    for (size_t t = 1; na > 0; ++t) {
+        // ---- 1. count
+        PNCHK(radius_device_enqueue<T>(ix, ws, pos[cur], na, dim, dim, (T)0, off, nullptr, 0, nullptr, s, nullptr, 0, true,
+                                       hq[cur], true));
+        HIPCHK(hipMemcpyAsync(h_off.data(), off, (na + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        ++iterations;
+        seed_steps += na;
+        // ---- 2. step, piece by piece
+        for (size_t a = 0; a < na;) {
+            const size_t lim = na - a < kSelfChunk ? na : a + kSelfChunk;
+            // the last b in (a, lim] with off[b] - off[a] <= E, at least a + 1
+            size_t b = (size_t)(std::upper_bound(h_off.begin() + a + 1, h_off.begin() + lim + 1, h_off[a] + E) - h_off.begin()) - 1;
+            if (b <= a) b = a + 1;
+            const uint64_t total = h_off[b] - h_off[a];
+            MsStep<T> st{};
+            st.index_base = ix->index_base;
+            st.X = (const T *)ix->d_pts;
+            st.ld = ix->ld;
+            st.dim = (int)dim;
+            st.pos = pos[cur] + a * dim;
+            st.slot = slot[cur] + a;
+            st.nq = b - a;
+            st.tol = tol;
+            st.iter = (uint32_t)std::min<size_t>(t, 0xFFFFFFFFu);
+            st.last = t >= max_iter;
+            st.keep = keep + a;
+            st.modes = d_modes;
+            st.points = d_points;
+            st.iters = d_iters;
+            st.shift = d_shift;
+            if (total) {
+                PNCHK(ws.w_sf_idx.ensure(total * sizeof(uint64_t)));
+                st.off = (const uint64_t *)ws.w_sf_off.p;
+                st.idx = (const uint64_t *)ws.w_sf_idx.p;
+                PNCHK(radius_device_enqueue<T>(ix, ws, pos[cur] + a * dim, b - a, dim, dim, (T)0, (uint64_t *)ws.w_sf_off.p,
+                                               (uint64_t *)ws.w_sf_idx.p, (size_t)total, nullptr, s, nullptr, 0, false,
+                                               hq[cur] + a, false));
+                HIPCHK(launch_ms_step<T>(st, s));
+            } else {
+                HIPCHK(launch_ms_dead<T>(st, s));
+            }
+            a = b;
+        }
+        if (t >= max_iter) break;  // (every seed has stopped)
+        // ---- 3. compact
+        uint32_t h_n = 0;
+        HIPCHK(hipMemsetAsync(nsel, 0, sizeof(uint32_t), s));
+        HIPCHK(launch_compact_flags(keep, (int)na, sel, nsel, s));
+        HIPCHK(launch_ms_gather<T>(sel, nsel, na, (int)dim, pos[cur], hq[cur], slot[cur], pos[cur ^ 1], hq[cur ^ 1],
+                                   slot[cur ^ 1], s));
+        HIPCHK(hipMemcpyAsync(&h_n, nsel, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        na = h_n;
+        cur ^= 1;
+    }
+    if (work) {
+        work[0] = iterations;
+        work[1] = seed_steps;
+    }
+    return PN_OK;
+}
+template <typename T>
+static int ms_device(const pn_index *ix, const T *d_seeds, size_t ns, size_t s_cols, size_t s_stride, const T *d_h, size_t n_h,
+                     double tol, size_t max_iter, unsigned flags, T *d_modes, uint64_t *d_points, uint32_t *d_iters,
+                     double *d_shift, uint64_t *work, hipStream_t s) {
+    PNCHK(ms_args(ix, flags, tol, max_iter, d_modes, d_points, d_seeds, ns, s_cols, d_h, n_h, (int)sizeof(T)));
+    if (work) work[0] = work[1] = 0;
+    if (flags & PN_MS_SEED_ROWS) {
+        ns = ix->n;
+        d_seeds = (const T *)ix->d_pts;
+        s_stride = ix->ld;
+    }
+    if (ns == 0) return PN_OK;
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    lease.s = s;
+    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
+    return ms_enqueue<T>(ix, *lease.ws, d_seeds, ns, s_stride, d_h, n_h, tol, max_iter, d_modes, d_points, d_iters, d_shift,
+                         work, s);
+}
+template <typename T>
+static int ms_host(const pn_index *ix, const T *seeds, size_t ns, size_t s_cols, ptrdiff_t s_stride, const T *h, size_t n_h,
+                   double tol, size_t max_iter, unsigned flags, T *modes, uint64_t *points, uint32_t *iters, double *shift,
+                   uint64_t *work) {
+    PNCHK(ms_args(ix, flags, tol, max_iter, modes, points, seeds, ns, s_cols, h, n_h, (int)sizeof(T)));
+    if (work) work[0] = work[1] = 0;
+    const bool rows = (flags & PN_MS_SEED_ROWS) != 0;
+    if (rows) ns = ix->n;
+    if (ns == 0) return PN_OK;
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
+    Workspace &ws = *lease.ws;
+    hipStream_t s = lease.s;
+    const size_t dim = ix->dim;
+    if (!rows) PNCHK(upload_rows_to<T>(seeds, ns, dim, s_stride, ws.w_hq, s));
+    const size_t m_bytes = round_up(ns * dim * sizeof(T), (size_t)8), h_bytes = round_up(n_h * sizeof(T), (size_t)8);
+    PNCHK(ws.w_ms_io.ensure(ns * (sizeof(double) + sizeof(uint64_t) + sizeof(uint32_t)) + m_bytes + h_bytes));
+    double *d_shift = (double *)ws.w_ms_io.p;
+    uint64_t *d_points = (uint64_t *)(d_shift + ns);
+    T *d_modes = (T *)(d_points + ns);
+    T *d_h = (T *)((char *)d_modes + m_bytes);
+    uint32_t *d_iters = (uint32_t *)((char *)d_h + h_bytes);
+    HIPCHK(hipMemcpyAsync(d_h, h, n_h * sizeof(T), hipMemcpyHostToDevice, s));
+    PNCHK(ms_enqueue<T>(ix, ws, rows ? (const T *)ix->d_pts : (const T *)ws.w_hq.p, ns, rows ? ix->ld : dim, d_h, n_h, tol,
+                        max_iter, d_modes, d_points, iters ? d_iters : nullptr, shift ? d_shift : nullptr, work, s));
+    HIPCHK(hipMemcpyAsync(modes, d_modes, ns * dim * sizeof(T), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(points, d_points, ns * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    if (iters) HIPCHK(hipMemcpyAsync(iters, d_iters, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (shift) HIPCHK(hipMemcpyAsync(shift, d_shift, ns * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return PN_OK;
+}
+// ---- merge: rank sort + 2 ceil(ns / 1024) round launches (mean_shift.hip); nothing is read back
+static int ms_merge_args(const pn_index *ix, unsigned flags, const void *centres, const void *n_centres, const void *modes,
+                         const void *points, size_t ns, int elem_bytes) {
+    if (flags) return fail(PN_ERR_INVALID, "unknown mean shift flags 0x%x", flags);
+    if (!centres || !n_centres) return fail(PN_ERR_INVALID, "centres or n_centres is NULL");
+    if (ns && (!modes || !points)) return fail(PN_ERR_INVALID, "modes or points_within is NULL");
+    if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
+    if (ix->elem_bytes != elem_bytes) return fail(PN_ERR_INVALID, "index element type mismatch");
+    if (ix->metric != 0) return fail(PN_ERR_UNSUPPORTED, "mean shift needs a Euclidean index");
+    if (ns > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many seeds in one call");
+    return PN_OK;
+}
+template <typename T>
+static int ms_merge_device(const pn_index *ix, const T *d_modes, size_t ns, const uint64_t *d_points, T h, unsigned flags,
+                           T *d_centres, uint64_t *d_centre_points, int64_t *d_centre_of_seed, uint64_t *d_n_centres,
+                           hipStream_t s) {
+    PNCHK(ms_merge_args(ix, flags, d_centres, d_n_centres, d_modes, d_points, ns, (int)sizeof(T)));
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    lease.s = s;
+    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
+    PNCHK(lease.ws->w_ms.ensure(ms_merge_bytes(ns)));
+    HIPCHK(ms_merge_enqueue<T>(d_modes, ns, (int)ix->dim, d_points, h, lease.ws->w_ms.p, d_centres, d_centre_points,
+                               d_centre_of_seed, d_n_centres, s));
+    return PN_OK;
+}
+template <typename T>
+static int ms_merge_host(const pn_index *ix, const T *modes, size_t ns, const uint64_t *points, T h, unsigned flags, T *centres,
+                         uint64_t *centre_points, int64_t *centre_of_seed, uint64_t *n_centres) {
+    PNCHK(ms_merge_args(ix, flags, centres, n_centres, modes, points, ns, (int)sizeof(T)));
+    if (ns == 0) {
+        *n_centres = 0;
+        return PN_OK;
+    }
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
+    Workspace &ws = *lease.ws;
+    hipStream_t s = lease.s;
+    const size_t dim = ix->dim, m_bytes = round_up(ns * dim * sizeof(T), (size_t)8);
+    PNCHK(ws.w_ms_io.ensure(ns * 3 * sizeof(uint64_t) + 8 + 2 * m_bytes));
+    uint64_t *d_points = (uint64_t *)ws.w_ms_io.p, *d_cp = d_points + ns, *d_nc = d_cp + ns;
+    int64_t *d_cos = (int64_t *)(d_nc + 1);
+    T *d_modes = (T *)(d_cos + ns), *d_centres = (T *)((char *)d_modes + m_bytes);
+    HIPCHK(hipMemcpyAsync(d_modes, modes, ns * dim * sizeof(T), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_points, points, ns * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    PNCHK(ws.w_ms.ensure(ms_merge_bytes(ns)));
+    HIPCHK(ms_merge_enqueue<T>(d_modes, ns, (int)dim, d_points, h, ws.w_ms.p, d_centres, d_cp, d_cos, d_nc, s));
+    HIPCHK(hipMemcpyAsync(n_centres, d_nc, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const size_t nc = (size_t)*n_centres;
+    if (nc) HIPCHK(hipMemcpyAsync(centres, d_centres, nc * dim * sizeof(T), hipMemcpyDeviceToHost, s));
+    if (nc && centre_points) HIPCHK(hipMemcpyAsync(centre_points, d_cp, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    if (centre_of_seed) HIPCHK(hipMemcpyAsync(centre_of_seed, d_cos, ns * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return PN_OK;
+}
+// ---- labels: one exact launch against the centres
+static int ms_labels_args(const pn_index *ix, unsigned flags, const void *labels, const void *centres, size_t nc,
+                          int elem_bytes) {
+    if (flags & ~(unsigned)PN_MS_ORPHANS) return fail(PN_ERR_INVALID, "unknown mean shift flags 0x%x", flags);
+    if (!labels) return fail(PN_ERR_INVALID, "labels is NULL");
+    if (nc && !centres) return fail(PN_ERR_INVALID, "centres is NULL");
+    if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
+    if (ix->elem_bytes != elem_bytes) return fail(PN_ERR_INVALID, "index element type mismatch");
+    if (ix->metric != 0) return fail(PN_ERR_UNSUPPORTED, "mean shift needs a Euclidean index");
+    if (ix->n > 0x7FFFFFFFull || nc > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many rows or centres");
+    return PN_OK;
+}
+template <typename T>
+static int ms_labels_device(const pn_index *ix, const T *d_centres, size_t nc, T h, unsigned flags, int64_t *d_labels,
+                            hipStream_t s) {
+    PNCHK(ms_labels_args(ix, flags, d_labels, d_centres, nc, (int)sizeof(T)));
+    if (ix->n == 0) return PN_OK;
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    HIPCHK(launch_ms_labels<T>((const T *)ix->d_pts, ix->n, ix->ld, (int)ix->dim, d_centres, nc, h,
+                               (flags & PN_MS_ORPHANS) != 0, d_labels, s));
+    return PN_OK;
+}
+template <typename T>
+static int ms_labels_host(const pn_index *ix, const T *centres, size_t nc, T h, unsigned flags, int64_t *labels) {
+    PNCHK(ms_labels_args(ix, flags, labels, centres, nc, (int)sizeof(T)));
+    if (ix->n == 0) return PN_OK;
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
+    Workspace &ws = *lease.ws;
+    hipStream_t s = lease.s;
+    const size_t c_bytes = nc * ix->dim * sizeof(T);
+    PNCHK(ws.w_ms_io.ensure(ix->n * sizeof(int64_t) + c_bytes + 8));
+    int64_t *d_labels = (int64_t *)ws.w_ms_io.p;
+    T *d_centres = (T *)(d_labels + ix->n);
+    if (nc) HIPCHK(hipMemcpyAsync(d_centres, centres, c_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(launch_ms_labels<T>((const T *)ix->d_pts, ix->n, ix->ld, (int)ix->dim, d_centres, nc, h,
+                               (flags & PN_MS_ORPHANS) != 0, d_labels, s));
+    HIPCHK(hipMemcpyAsync(labels, d_labels, ix->n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return PN_OK;
+}
+#define PN_MS_ENTRIES(SFX, T)                                                                                                  \
+    extern "C" int pn_mean_shift_##SFX(const pn_index *ix, const T *seeds, size_t ns, size_t s_cols, ptrdiff_t s_row_stride,    \
+                                       const T *h, size_t n_h, double tol, size_t max_iter, unsigned flags, T *modes_out,      \
+                                       uint64_t *points_within_out, uint32_t *iterations_out, double *shift_out,               \
+                                       uint64_t *work) {                                                                       \
+        return ms_host<T>(ix, seeds, ns, s_cols, s_row_stride, h, n_h, tol, max_iter, flags, modes_out, points_within_out,     \
+                          iterations_out, shift_out, work);                                                                    \
+    }                                                                                                                          \
+    extern "C" int pn_mean_shift_device_##SFX(const pn_index *ix, const T *d_seeds, size_t ns, size_t s_cols,                  \
+                                              size_t s_row_stride, const T *d_h, size_t n_h, double tol, size_t max_iter,      \
+                                              unsigned flags, T *d_modes, uint64_t *d_points_within, uint32_t *d_iterations,   \
+                                              double *d_shift, uint64_t *work, void *stream) {                                 \
+        return ms_device<T>(ix, d_seeds, ns, s_cols, s_row_stride, d_h, n_h, tol, max_iter, flags, d_modes, d_points_within,   \
+                            d_iterations, d_shift, work, (hipStream_t)stream);                                                 \
+    }                                                                                                                          \
+    extern "C" int pn_mean_shift_merge_##SFX(const pn_index *ix, const T *modes, size_t ns, const uint64_t *points_within,     \
+                                             T h, unsigned flags, T *centres_out, uint64_t *centre_points_out,                 \
+                                             int64_t *centre_of_seed_out, uint64_t *n_centres_out) {                           \
+        return ms_merge_host<T>(ix, modes, ns, points_within, h, flags, centres_out, centre_points_out, centre_of_seed_out,    \
+                                n_centres_out);                                                                                \
+    }                                                                                                                          \
+    extern "C" int pn_mean_shift_merge_device_##SFX(const pn_index *ix, const T *d_modes, size_t ns,                           \
+                                                    const uint64_t *d_points_within, T h, unsigned flags, T *d_centres,        \
+                                                    uint64_t *d_centre_points, int64_t *d_centre_of_seed,                      \
+                                                    uint64_t *d_n_centres, void *stream) {                                     \
+        return ms_merge_device<T>(ix, d_modes, ns, d_points_within, h, flags, d_centres, d_centre_points, d_centre_of_seed,    \
+                                  d_n_centres, (hipStream_t)stream);                                                           \
+    }                                                                                                                          \
+    extern "C" int pn_mean_shift_labels_##SFX(const pn_index *ix, const T *centres, size_t nc, T h, unsigned flags,            \
+                                              int64_t *labels) {                                                               \
+        return ms_labels_host<T>(ix, centres, nc, h, flags, labels);                                                           \
+    }                                                                                                                          \
+    extern "C" int pn_mean_shift_labels_device_##SFX(const pn_index *ix, const T *d_centres, size_t nc, T h, unsigned flags,   \
+                                                     int64_t *d_labels, void *stream) {                                        \
+        return ms_labels_device<T>(ix, d_centres, nc, h, flags, d_labels, (hipStream_t)stream);                                \
+    }
+PN_MS_ENTRIES(f32, float)
+PN_MS_ENTRIES(f64, double)
+#undef PN_MS_ENTRIES
 
 extern "C" void pn_free(void *p) { free(p); }
 

@@ -303,10 +303,19 @@ __global__ __launch_bounds__(256) void mst_output_kernel(size_t ne, const typena
 }
 
 dim3 rows_grid(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
-size_t sort_len(size_t n) {  // the n - 1 edges padded to a power of two, at least one LDS block
-    size_t N = kSortBlock;
-    while (N < n - 1) N <<= 1;
-    return N;
+size_t sort_len(size_t n) { return sort_key_pair_len(n - 1); }  // the n - 1 edges padded for the network
+
+// the network over N (a power of two >= kSortBlock) padded elements: also mean_shift.hip's rank sort
+template <typename K>
+hipError_t sort_key_pair(K *e_key, unsigned long long *e_pair, size_t N2, hipStream_t s) {
+    const dim3 lg((unsigned)(N2 / kSortBlock)), lb(kSortBlock / 2), blk(256);
+    hipLaunchKernelGGL((mst_sort_local_kernel<K>), lg, lb, 0, s, e_key, e_pair, (size_t)2, (size_t)kSortBlock);
+    for (size_t k = 2 * (size_t)kSortBlock; k <= N2; k <<= 1) {
+        for (size_t j = k / 2; j >= (size_t)kSortBlock; j >>= 1)
+            hipLaunchKernelGGL((mst_sort_step_kernel<K>), rows_grid(N2 / 2), blk, 0, s, e_key, e_pair, N2 / 2, k, j);
+        hipLaunchKernelGGL((mst_sort_local_kernel<K>), lg, lb, 0, s, e_key, e_pair, k, k);
+    }
+    return hipGetLastError();
 }
 
 // the scratch of a call, carved from one buffer: 64-bit arrays first
@@ -461,14 +470,7 @@ int mst_enqueue(MstArgs &a, hipStream_t s) {
         hipLaunchKernelGGL((mst_sort_pad_kernel<K>), rows_grid(N2 - ne), blk, 0, s, ne, N2, e_key, e_pair);
         MSTCHK(hipGetLastError());
     }
-    const dim3 lg((unsigned)(N2 / kSortBlock)), lb(kSortBlock / 2);
-    hipLaunchKernelGGL((mst_sort_local_kernel<K>), lg, lb, 0, s, e_key, e_pair, (size_t)2, (size_t)kSortBlock);
-    for (size_t k = 2 * (size_t)kSortBlock; k <= N2; k <<= 1) {
-        for (size_t j = k / 2; j >= (size_t)kSortBlock; j >>= 1)
-            hipLaunchKernelGGL((mst_sort_step_kernel<K>), rows_grid(N2 / 2), blk, 0, s, e_key, e_pair, N2 / 2, k, j);
-        hipLaunchKernelGGL((mst_sort_local_kernel<K>), lg, lb, 0, s, e_key, e_pair, k, k);
-    }
-    MSTCHK(hipGetLastError());
+    MSTCHK(sort_key_pair<K>(e_key, e_pair, N2, s));
     hipLaunchKernelGGL((mst_output_kernel<T>), rows_grid(ne), blk, 0, s, ne, e_key, e_pair, a.index_base, cosm, a.d_src, a.d_dst,
                        (T *)a.d_weight);
     MSTCHK(hipGetLastError());
@@ -482,6 +484,14 @@ int mst_enqueue(MstArgs &a, hipStream_t s) {
 size_t mst_buffer_bytes(size_t n, int elem_bytes, size_t batch, int n_cu) {
     if (n < 2) return 0;
     return Layout(n, elem_bytes, batch ? batch : 1, n_cu).total;
+}
+size_t sort_key_pair_len(size_t count) {
+    size_t N = kSortBlock;
+    while (N < count) N <<= 1;
+    return N;
+}
+hipError_t launch_sort_key_pair_u64(uint64_t *key, unsigned long long *pair, size_t N, hipStream_t s) {
+    return sort_key_pair<uint64_t>(key, pair, N, s);
 }
 int mst_enqueue_f32(MstArgs &a, hipStream_t s) { return mst_enqueue<float>(a, s); }
 int mst_enqueue_f64(MstArgs &a, hipStream_t s) { return mst_enqueue<double>(a, s); }

@@ -266,6 +266,65 @@ template <typename T>
 hipError_t launch_kde_sum(const uint64_t *off, const uint64_t *idx, const T *dist, const T *hq, size_t nq, int kernel,
                           uint64_t own_first, double *sum, uint64_t *count, hipStream_t s);
 
+// ---- mean_shift.hip: mean shift over the radius lists (pn_mean_shift_*); nothing in it waits for the device.
+// the start of a call: pos [ns][dim] dense <- the seeds' rows (row stride s_stride), hq [ns] <- h broadcast (n_h = 1) or
+// copied, slot[i] <- i
+template <typename T>
+hipError_t launch_ms_init(const T *seeds, size_t s_stride, size_t ns, int dim, const T *h, size_t n_h, T *pos, T *hq,
+                          uint32_t *slot, hipStream_t s);
+// One step of a piece's nq active seeds (one wave each).  off / idx: the piece's CSR as radius_device_enqueue writes it
+// without distances (piece-local offsets, 64-bit row ids with index_base); X [n][ld]: the indexed rows (ld a multiple of
+// kRowAlign); pos [nq][dim] dense: read, and overwritten with the new positions; slot [nq]: each seed's output row.
+// iter: the iteration's number t >= 1; last: t == max_iter.  keep[q] <- 0 where the seed stopped (shift <= tol, last, or
+// an empty list: dead), else 1; a stopped seed's mode [dim], points_within, iterations (nullable) and shift (nullable) go
+// to its slot of the outputs.
+template <typename T>
+struct MsStep {
+    const uint64_t *off, *idx;
+    uint64_t index_base;
+    const T *X;
+    size_t ld;
+    int dim;
+    T *pos;
+    const uint32_t *slot;
+    size_t nq;
+    double tol;
+    uint32_t iter;
+    int last;
+    uint32_t *keep;
+    T *modes;
+    uint64_t *points;
+    uint32_t *iters;
+    double *shift;
+};
+template <typename T>
+hipError_t launch_ms_step(const MsStep<T> &a, hipStream_t s);
+// a piece whose lists are all empty (no CSR exists): every seed of it stops dead (the fields off, idx, X are not read)
+template <typename T>
+hipError_t launch_ms_dead(const MsStep<T> &a, hipStream_t s);
+// the next iteration's active set: row i < *nsel of the outputs <- row sel[i] of the inputs (grid sized for n_in)
+template <typename T>
+hipError_t launch_ms_gather(const uint32_t *sel, const uint32_t *nsel, size_t n_in, int dim, const T *pos_in, const T *h_in,
+                            const uint32_t *slot_in, T *pos_out, T *h_out, uint32_t *slot_out, hipStream_t s);
+// The merge of the converged modes (the contract: petal_mi355x.h).  buf: ms_merge_bytes(ns) bytes of scratch, 8-byte
+// aligned.  Enqueues the rank sort and 2 ceil(ns / kMsMergeRound) round launches; nothing is read back.
+constexpr int kMsMergeRound = 1024;  // consecutive ranks one round of the merge decides
+size_t ms_merge_bytes(size_t ns);
+template <typename T>
+hipError_t ms_merge_enqueue(const T *modes, size_t ns, int dim, const uint64_t *points, T h, void *buf, T *centres,
+                            uint64_t *centre_points, int64_t *centre_of_seed, uint64_t *n_centres, hipStream_t s);
+// labels[i] <- the centre nearest to row i of X by (distance key, centre number): a k = 1 query's answer on an index made
+// of the centres; orphans: -1 unless that distance is < h; nc == 0: all -1
+template <typename T>
+hipError_t launch_ms_labels(const T *X, size_t n, size_t ld, int dim, const T *centres, size_t nc, T h, bool orphans,
+                            int64_t *labels, hipStream_t s);
+
+// ---- mst.hip, for mean_shift.hip: the bitonic network over (key, pair), ascending by key then pair.  N =
+// sort_key_pair_len(count): count padded to a power of two, at least the block one workgroup sorts in LDS; the caller pads
+// the arrays (all-ones keys sort last)
+size_t sort_key_pair_len(size_t count);
+hipError_t launch_sort_key_pair_u64(uint64_t *key, unsigned long long *pair, size_t N, hipStream_t s);
+
 // ---- optics.hip: OPTICS over the max_eps self-graph (pn_optics_*) and the extraction at one eps (pn_optics_dbscan_*);
 // nothing in it waits for the device.
 // core[i] <- v < max_eps ? v : +inf, v = in_dist[i][k - 1] of a self-query chunk's answer [nq][k] (in_dist == nullptr: +inf);
