@@ -6,15 +6,25 @@ The want side of a case is the dense distance matrix in the index's element type
 oracle's scalar distance per pair, checked again on sampled pairs) and nothing else: the k-NN lists are its rows ordered by
 (key, index), the radius lists its entries strictly below the radius, and cores, Prim's tree, the dendrogram, HDBSCAN, DBSCAN
 and OPTICS come out of it through the references of the other modules, imported, not restated.  LOF is the reference over
-the library's own query_self, which the same call first anchors to the matrix.
+the library's own query_self, which the same call first anchors to the matrix.  The KDE sums and the mean shift step are
+tests/density_reference.py over the matrix' lists: the entries strictly below each query's cutoff, the rows with a NaN in
+no list (and dead seeds); the mean shift labels are the matrix' columns of the centres, by (key, centre number).
 
 The got side calls query_self, query_radius_self (scalar and per-row radii), dbscan, mst (plain and cored), linkage,
 hdbscan, lof + lof_score, optics and optics_dbscan on one handle, host or device entry drawn at random, the device outputs
-on a stream of their own.  Pass 1 uses the case's parameters in a random order.  Pass 2 draws an engine, an index base,
-the DBSCAN / OPTICS pieces and the MST batch, then runs everything in another order with larger k / min_samples and eps
-halved, then with smaller ones -- so every shared workspace buffer is regrown and reused by another owner in between --
-and finally repeats calls with pass 1's parameters: those must reproduce pass 1 byte for byte.  All comparisons are
-array equality; floats by their bits with equal NaN masks.
+on a stream of their own; and, borrowing the same workspace scratch, kde_self (the rows as their own queries: a kernel,
+include_self and a scalar bandwidth or one per row drawn per round, from eps), kde (a subset of the rows and one NaN query
+as external queries; on a Cosine tree the normalised density must raise, the raw sums are checked all the same) and
+mean_shift (one step of the rows as seeds, then the labels against centres picked from the rows; on a Cosine tree the call
+must raise).  The compact kernels and mean shift compare bit for bit; the smooth kernels take atol = 0 up to 1000 rows
+(every row in every list) and atol = 1 above, where the returned cutoff is held against the header's and the sums against
+the bound of tests/test_gpu_kde.py.  Pass 1 uses the case's parameters in a random order.  Pass 2 draws an engine, an index
+base, the DBSCAN / OPTICS / KDE / mean shift pieces and the MST batch, then runs everything in another order with larger
+k / min_samples and eps halved, then with smaller ones -- so every shared workspace buffer is regrown and reused by another
+owner in between -- and finally repeats calls with pass 1's parameters: those must reproduce pass 1 byte for byte.  All
+other comparisons are array equality; floats by their bits with equal NaN masks.  Whatever the KDE and mean shift entries
+draw -- kernels, flags, host or device entry, their places in the order, their pieces -- comes from a generator of the
+case's own, so the draws of the graph entries do not depend on the entries beside them.
 
 Conditions (asserted on the want side before any device call, printed, never tolerances): HDBSCAN's least relative gap
 >= MIN_GAP; OPTICS has a row with infinite core distance and a finite reachability; DBSCAN has two clusters and a noise
@@ -34,9 +44,11 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import oracle  # noqa: E402
 import petal_neighbors_amd as pn  # noqa: E402
 from petal_neighbors_amd import _lib  # noqa: E402
+from density_reference import kde_sums, ms_step  # noqa: E402
 from optics_reference import cpu_extract, cpu_optics, csr_from_dense, same_partition  # noqa: E402
 from test_gpu_dbscan import cpu_dbscan  # noqa: E402
 from test_gpu_hdbscan import MIN_GAP, ref_hdbscan  # noqa: E402
+from test_gpu_kde import COMPACT, SMOOTH, cutoff_within_bounds, smooth_bound, smooth_cutoff  # noqa: E402
 from test_gpu_linkage import seq_linkage  # noqa: E402
 from test_gpu_lof import ref_fit, ref_score, same_bits  # noqa: E402
 from test_gpu_mst import (bits_of_keys, core_keys_from, keys_of, prim, sampled_pairs_match_the_oracle,  # noqa: E402
@@ -44,7 +56,12 @@ from test_gpu_mst import (bits_of_keys, core_keys_from, keys_of, prim, sampled_p
 
 KMAX = 64  # the longest k-NN list a case asks for
 BLOB_FAMILIES = ("blobs", "dups", "sorted", "dups_nan")
-ENTRIES = ("self", "radius", "radii", "dbscan", "mst", "mst_cored", "linkage", "hdbscan", "lof", "optics", "extract")
+GRAPH_ENTRIES = ("self", "radius", "radii", "dbscan", "mst", "mst_cored", "linkage", "hdbscan", "lof", "optics", "extract")
+DENSITY_ENTRIES = ("kde", "kde_self", "mean_shift")
+ENTRIES = GRAPH_ENTRIES + DENSITY_ENTRIES
+KDE_QUERIES = 192  # rows a case takes as external KDE queries, at most (one NaN query is added)
+KDE_ATOL = 1.0     # the smooth kernels' atol above 1000 rows (at most: atol = 0, every row in every list)
+MS_CENTRES = 7     # rows a case takes as centres for the labels, at most
 
 
 # ------------------------------------------------------------------------------------------------------------ data
@@ -121,6 +138,16 @@ class Want:
         off = np.zeros(self.n + 1, dtype=np.int64)
         off[1:] = np.cumsum(m.sum(axis=1))
         return off, cols.astype(np.int64), self.d[rows, cols]
+
+    def lists_of(self, sel, r):
+        """CSR (offsets, dist) of { j : d[sel_q, j] < r_q }, ascending j: the rows ``sel`` as external queries"""
+        r = np.asarray(r, dtype=self.dt)
+        d = self.d[sel]
+        with np.errstate(invalid="ignore"):
+            m = d < (r[:, None] if r.ndim else r)
+        off = np.zeros(len(sel) + 1, dtype=np.int64)
+        off[1:] = np.cumsum(m.sum(axis=1))
+        return off, d[m]
 
     def core_keys(self, k):
         return self.memo(("ck", k), lambda: core_keys_from(self.dk, k))
@@ -203,9 +230,9 @@ def eq(got, want, what):
 
 
 class Runner:
-    def __init__(self, tree, w, rng):
+    def __init__(self, tree, w, rng, rng2):
         import torch
-        self.torch, self.tree, self.w, self.rng = torch, tree, w, rng
+        self.torch, self.tree, self.w, self.rng, self.rng2 = torch, tree, w, rng, rng2
         self.dev = torch.device("cuda", 0)
         self.stream = torch.cuda.Stream(self.dev)
         self.tdt = torch.float32 if w.dt == np.float32 else torch.float64
@@ -214,6 +241,9 @@ class Runner:
 
     def device(self):
         return bool(self.rng.integers(0, 2))
+
+    def device2(self):
+        return bool(self.rng2.integers(0, 2))
 
     def on_stream(self, fn):
         """fn(stream handle) enqueued on the runner's own stream; its tensors as numpy arrays"""
@@ -426,6 +456,121 @@ class Runner:
             blob += labels.tobytes()
         return blob
 
+    def bandwidths(self, count, eps, per_query):
+        """the scalar eps, or one bandwidth per query: eps * (0.5 .. 1), every 97th from the second on not positive or NaN
+        (Cosine distances may lie a few ulp below 0: no bandwidth 0 there)"""
+        if not per_query:
+            return self.w.dt.type(eps)
+        h = (float(eps) * np.random.default_rng(count).uniform(0.5, 1.0, count)).astype(self.w.dt)
+        bad = np.arange(1, count, 97)
+        h[bad] = np.resize(np.array([-1.0 if self.w.cosine else 0.0, -1.0, np.nan], dtype=self.w.dt), len(bad))
+        return h
+
+    def kde_compare(self, got, lists_at, h, count, kernel, atol, what):
+        """(sum, count, cutoff) of one KDE call against the matrix: ``lists_at(cutoffs)`` gives (offsets, distances)"""
+        w = self.w
+        s, cnt, cut = got
+        hq = np.full(count, h, dtype=w.dt) if np.ndim(h) == 0 else h
+        live = hq > 0
+        if kernel in COMPACT:
+            eq_bits(cut, hq, what + ": cutoff against h")
+        elif atol == 0.0:
+            eq_bits(cut, np.where(live, w.dt.type(np.inf), hq), what + ": cutoff against +inf")
+        else:
+            eq_bits(cut[~live], hq[~live], what + ": cutoff of a bandwidth that is not positive")
+            assert cutoff_within_bounds(cut[live], smooth_cutoff(kernel, hq[live].astype(np.float64), w.n, atol)), what
+        off, dist = lists_at(cut)
+        want, want_cnt = kde_sums(off, dist, hq, kernel)
+        eq(cnt, want_cnt, what + ": count")
+        if kernel in COMPACT:
+            eq_bits(s, want, what + ": sum")
+        else:
+            dev, bound = np.abs(s - want), smooth_bound(want, want_cnt)
+            assert (dev <= bound).all(), f"{what}: {int((dev > bound).sum())} sums beyond the bound"
+        return s.tobytes() + cnt.astype(np.int64).tobytes() + cut.tobytes()
+
+    def kde_self(self, q):
+        t, w = self.tree, self.w
+        kernel, include, per_row = q["kde"]["self_kernel"], q["kde"]["include"], q["kde"]["per_row"] and w.n >= 2
+        atol = 0.0 if kernel in COMPACT or w.n <= 1000 else KDE_ATOL
+        h = self.bandwidths(w.n, q["eps"], per_row)
+        what = (f"{self.tag} kernel_density_raw(None, {'one h per row' if per_row else h}, {kernel}, atol={atol}, "
+                f"include_self={include})")
+        if self.device2():
+            dh = self.up(h) if per_row else float(h)
+            got = self.on_stream(lambda s: t.kernel_density_self_device(dh, kernel, atol, include, stream=s))
+        else:
+            got = t.kernel_density_raw(None, h, kernel, atol, include_self=include)
+        return self.kde_compare(got, lambda cut: w.lists(cut, include, False)[::2], h, w.n, kernel, atol, what)
+
+    def kde(self, q):
+        t, w = self.tree, self.w
+        kernel, per_query = q["kde"]["kernel"], q["kde"]["per_query"]
+        atol = 0.0 if kernel in COMPACT or w.n <= 1000 else KDE_ATOL
+        sel = np.sort(np.random.default_rng(w.n + 1).choice(w.n, min(w.n, KDE_QUERIES), replace=False))
+        qs = np.ascontiguousarray(np.concatenate([w.x[sel], np.full((1, w.x.shape[1]), np.nan, dtype=w.dt)]))
+        nq = len(qs)
+        h = self.bandwidths(nq, q["eps"], per_query)
+        what = f"{self.tag} kernel_density_raw({nq} queries, {'one h per query' if per_query else h}, {kernel}, atol={atol})"
+        if self.device2():
+            dq, dh = self.up(qs), self.up(h) if per_query else float(h)
+            got = self.on_stream(lambda s: t.kernel_density_device(dq, dh, kernel, atol, stream=s))
+        else:
+            got = t.kernel_density_raw(qs, h, kernel, atol)
+        assert got[0][-1] == 0 and got[1][-1] == 0, what + ": the NaN query"
+
+        def lists_at(cut):  # the matrix rows of the subset; the NaN query lists nothing
+            off, dist = w.lists_of(sel, cut[:-1])
+            return np.concatenate([off, off[-1:]]), dist
+        blob = self.kde_compare(got, lists_at, h, nq, kernel, atol, what)
+        if w.cosine:  # the normalisers are volumes of Euclidean balls
+            try:
+                t.kernel_density(qs, h, kernel=kernel, atol=atol)
+            except ValueError:
+                return blob
+            raise AssertionError(what + ": kernel_density(normalize=True) on a Cosine tree must raise")
+        return blob
+
+    def mean_shift(self, q):
+        t, w = self.tree, self.w
+        h = w.dt.type(q["eps"])
+        what = f"{self.tag} mean_shift_modes({h}, the rows, max_iter=1)"
+        if w.cosine:
+            try:
+                t.mean_shift_modes(h, None, tol=0.0, max_iter=1)
+            except ValueError:
+                return b""
+            raise AssertionError(what + ": on a Cosine tree must raise")
+        off, idx, _ = w.lists(h, True, False)
+        w_modes, w_pw, w_shift = ms_step(w.x, w.x, off, idx)
+        if self.device2():
+            modes, pw, it, sh, work = self.on_stream(lambda s: t.mean_shift_modes_device(float(h), None, tol=0.0, max_iter=1, stream=s))
+        else:
+            modes, pw, it, sh, work = t.mean_shift_modes(h, None, tol=0.0, max_iter=1, full=True)
+        eq(pw, w_pw, what + ": points_within")
+        eq(it, w_pw > 0, what + ": iterations")
+        eq_bits(modes, w_modes, what + ": modes")
+        eq_bits(sh, w_shift, what + ": shift")
+        assert tuple(work) == (1, w.n), what
+        nan_rows = np.isnan(w.x).any(axis=1)
+        assert (w_pw[nan_rows] == 0).all() and np.isnan(w_shift[nan_rows]).all(), what  # in no list: dead seeds
+        blob = modes.tobytes() + pw.astype(np.int64).tobytes() + sh.tobytes()
+        # the labels against centres picked from the rows: the matrix columns, by (key, centre number)
+        cs = np.sort(np.random.default_rng(w.n + 2).choice(w.n, min(w.n, MS_CENTRES), replace=False))
+        centres = np.ascontiguousarray(w.x[cs])
+        lab = np.argmin(w.dk[:, cs], axis=1).astype(np.int64)  # (the first of equal minima: the lower centre)
+        with np.errstate(invalid="ignore"):
+            near = w.d[np.arange(w.n), cs[lab]] < h
+        for cluster_all in (True, False):
+            if self.device2():
+                dc = self.up(centres)
+                got = self.on_stream(lambda s: [t.mean_shift_labels_device(dc, float(h), cluster_all, stream=s)])[0]
+            else:
+                got = t.mean_shift_labels(centres, h, cluster_all)
+            eq(got, lab if cluster_all else np.where(near, lab, -1), f"{self.tag} mean_shift_labels({len(cs)} rows, {h}, {cluster_all})")
+            blob += got.tobytes()
+        return blob
+
     def call(self, name, q):
         if name == "lof" and self.w.n < 2:
             try:
@@ -434,6 +579,22 @@ class Runner:
                 return b""
             raise AssertionError("lof on one row must raise")
         return {"self": self.self_}.get(name, getattr(self, name, None))(q)
+
+
+def draw_kde(rng):
+    """what a round's KDE calls use: one kernel each, the self entry's flag, scalar or per-query bandwidths"""
+    kernels = COMPACT + SMOOTH
+    return {"kernel": str(rng.choice(kernels)), "self_kernel": str(rng.choice(kernels)), "include": bool(rng.integers(0, 2)),
+            "per_query": bool(rng.integers(0, 2)), "per_row": bool(rng.integers(0, 2))}
+
+
+def order_of(rng, rng2):
+    """the graph entries in a random order drawn from ``rng``, the KDE and mean shift entries put in at places drawn from
+    ``rng2``: what ``rng`` gives the graph entries does not depend on the entries beside them"""
+    names = [str(x) for x in rng.permutation(GRAPH_ENTRIES)]
+    for name in DENSITY_ENTRIES:
+        names.insert(int(rng2.integers(0, len(names) + 1)), name)
+    return names
 
 
 def pieces_value(rng, total):
@@ -447,16 +608,18 @@ def run_once(p, seed, rng, what):
     w = Want(x, p["cosine"])
     q = derive(p, w)
     q["include"] = bool(rng.integers(0, 2))
+    rng2 = np.random.default_rng([int(seed), 0x4DE5])  # every draw of the KDE and mean shift entries: the case's own generator
+    q["kde"] = draw_kde(rng2)
     n, dim = x.shape
     ok, text = conditions(q, w)
     must = p["family"] in BLOB_FAMILIES and n >= 1000
-    print(f"{what}: k {q['k']}, min_samples {q['ms']}, min_cluster_size {q['m']}; {text}{'' if ok or not must else ' -- MISSED'}",
-          flush=True)
+    print(f"{what}: k {q['k']}, min_samples {q['ms']}, min_cluster_size {q['m']}, kde {q['kde']}; {text}"
+          f"{'' if ok or not must else ' -- MISSED'}", flush=True)
     if must and not ok:
         return None
     tree = pn.BallTree.new(x, pn.distance.Cosine()) if p["cosine"] else pn.BallTree.euclidean(x)
     try:
-        r = Runner(tree, w, rng)
+        r = Runner(tree, w, rng, rng2)
         # a row with a non-finite value rules the bf16 tier out for the whole index, by design: such a case runs the exact
         # scan at its width, and that is asserted instead
         finite = bool(np.isfinite(x).all())
@@ -467,8 +630,8 @@ def run_once(p, seed, rng, what):
         # ---- pass 1
         r.tag = "pass 1:"
         first = {}
-        for name in rng.permutation(ENTRIES):
-            first[str(name)] = r.call(str(name), q)
+        for name in order_of(rng, rng2):
+            first[name] = r.call(name, q)
         after = tree.stats()
         dq, dc, df = (after[f] - before[f] for f in ("queries", "candidates", "fallback_queries"))
         print(f"{what}: pass 1 served {dq} queries, {dc} candidates, {df} fallback queries", flush=True)
@@ -483,23 +646,26 @@ def run_once(p, seed, rng, what):
         tree.set_option(_lib.PN_OPT_INDEX_BASE, r.base)
         entries = int(w.lists(q["eps"], True, False)[0][-1])
         opts = {_lib.PN_OPT_DBSCAN_PIECE: pieces_value(rng, entries), _lib.PN_OPT_OPTICS_PIECE: pieces_value(rng, entries),
-                _lib.PN_OPT_MST_BATCH: pieces_value(rng, n)}
+                _lib.PN_OPT_MST_BATCH: pieces_value(rng, n), _lib.PN_OPT_KDE_PIECE: pieces_value(rng2, entries),
+                _lib.PN_OPT_MS_PIECE: pieces_value(rng2, entries)}
         for o, v in opts.items():
             tree.set_option(o, v)
         print(f"{what}: pass 2 under engine {engine}, index base {r.base}, dbscan / optics piece "
-              f"{opts[_lib.PN_OPT_DBSCAN_PIECE]} / {opts[_lib.PN_OPT_OPTICS_PIECE]}, mst batch {opts[_lib.PN_OPT_MST_BATCH]}", flush=True)
+              f"{opts[_lib.PN_OPT_DBSCAN_PIECE]} / {opts[_lib.PN_OPT_OPTICS_PIECE]}, mst batch {opts[_lib.PN_OPT_MST_BATCH]}, "
+              f"kde / mean shift piece {opts[_lib.PN_OPT_KDE_PIECE]} / {opts[_lib.PN_OPT_MS_PIECE]}", flush=True)
         half = w.dt.type(0.5)
         larger = dict(q, k=max(min(2 * q["k"] + 3, n - 1, KMAX), 1), ms=max(min(2 * q["ms"] + 1, n - 1, KMAX), 1), m=2 * q["m"],
-                      eps=q["eps"] * half, max_eps=q["max_eps"] * half, include=not q["include"])
-        smaller = dict(q, k=max(q["k"] // 2, 1), ms=max(q["ms"] // 2, 1), m=max(q["m"] // 2, 2), eps=q["eps"] * half)
+                      eps=q["eps"] * half, max_eps=q["max_eps"] * half, include=not q["include"], kde=draw_kde(rng2))
+        smaller = dict(q, k=max(q["k"] // 2, 1), ms=max(q["ms"] // 2, 1), m=max(q["m"] // 2, 2), eps=q["eps"] * half,
+                       kde=draw_kde(rng2))
         for tag, qq in (("pass 2, larger:", larger), ("pass 2, smaller:", smaller)):
             r.tag = tag
-            for name in rng.permutation(ENTRIES):
-                r.call(str(name), qq)
+            for name in order_of(rng, rng2):
+                r.call(name, qq)
         r.tag = "pass 2, unchanged:"
-        for name in rng.permutation(ENTRIES):
-            got = r.call(str(name), q)
-            assert got == first[str(name)], f"{what}: {name} with unchanged parameters differs from pass 1"
+        for name in order_of(rng, rng2):
+            got = r.call(name, q)
+            assert got == first[name], f"{what}: {name} with unchanged parameters differs from pass 1"
     finally:
         tree.close()
     return True

@@ -32,8 +32,9 @@ _GRAPH_REDRAWS = []
 
 @pytest.mark.parametrize("seed", [41, 42])
 def test_random_graph_calls_on_one_handle(pn, oracle_mod, seed):
-    """tests/fuzz_graph.py: every graph entry point on one handle against one dense want side, two passes with the options
-    and parameters changed in between; n from 1 to 4500, D from 1 to 200, f32 / f64, Euclidean / Cosine, five families."""
+    """tests/fuzz_graph.py: every graph entry point, KDE and mean shift on one handle against one dense want side, two passes
+    with the options and parameters changed in between; n from 1 to 4500, D from 1 to 200, f32 / f64, Euclidean / Cosine,
+    five families."""
     import fuzz_graph
     rng = np.random.default_rng(seed)
     for params in [fuzz_graph.draw_params(100 * seed + c, rng) for c in range(5)]:  # (the shapes do not depend on the calls)

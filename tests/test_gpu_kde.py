@@ -67,6 +67,25 @@ def same_bits(got, want, what):
     assert bad.size == 0, f"{what}: {bad.size} values differ, first at {bad[:5]}: {got[~gn][bad[:5]]} against {want[~wn][bad[:5]]}"
 
 
+def smooth_bound(want, want_cnt):
+    """the bound on |S_dev - S_ref| of a smooth kernel's sum ``want`` over ``want_cnt`` terms (the device library's exp
+    against numpy's, term by term, then the sum's own rounding)"""
+    m = np.asarray(want_cnt).astype(np.float64)
+    return U * (8.0 + 2.0 * (np.ceil(m / 64.0) + 64.0)) * want
+
+
+def smooth_cutoff(kernel, hd, n, atol):
+    """the header's cutoff of a smooth kernel in exact arithmetic: hd (the bandwidth in the tree's type, as f64) times
+    sqrt(2 ln(n / atol)) or ln(n / atol)"""
+    return hd * (math.sqrt(2.0 * math.log(n / atol)) if kernel == "gaussian" else math.log(n / atol))
+
+
+def cutoff_within_bounds(cut, f):
+    """the returned cutoffs against ``smooth_cutoff``: not below it, and not above by more than the factor's slack"""
+    c = np.asarray(cut).astype(np.float64)
+    return bool((c >= f * (1.0 - 2.0 ** -40)).all() and (c <= f * (1.0 + 2.0 ** -20)).all())
+
+
 def h_array(tree, h, nq):
     return np.full(nq, h, dtype=tree.dtype) if np.ndim(h) == 0 else np.asarray(h, dtype=tree.dtype)
 
@@ -88,8 +107,7 @@ def check(tree, q, h, kernel, what, atol=0.0, include_self=False):
         same_bits(cut, hq, what + ": cutoff against h")
         same_bits(s, want, what + ": sum")
     else:
-        m = want_cnt.astype(np.float64)
-        bound = U * (8.0 + 2.0 * (np.ceil(m / 64.0) + 64.0)) * want
+        bound = smooth_bound(want, want_cnt)
         dev = np.abs(s - want)
         print(f"{what}: largest |S_dev - S_ref| / (2^-53 S_ref) = {float(np.max(dev[want > 0] / (U * want[want > 0]), initial=0.0)):.3f}")
         assert (dev <= bound).all(), f"{what}: {int((dev > bound).sum())} sums beyond the bound, worst {float((dev / np.maximum(bound, 1e-300)).max()):.3f} x"
@@ -333,8 +351,7 @@ def test_atol_bounds_the_truncation(big, kernel):
         s, c, cut = check(tree, q, h, kernel, f"{kernel} atol = {atol}", atol=atol)
         assert (s0 - atol - eps <= s).all() and (s <= s0 + eps).all(), atol
         if atol < n:
-            f = hd * (math.sqrt(2.0 * math.log(n / atol)) if kernel == "gaussian" else math.log(n / atol))
-            assert (cut.astype(np.float64) >= f * (1.0 - 2.0 ** -40)).all() and (cut.astype(np.float64) <= f * (1.0 + 2.0 ** -20)).all()
+            assert cutoff_within_bounds(cut, smooth_cutoff(kernel, hd, n, atol))
         else:
             assert (cut == 0).all() and (c == 0).all() and (s == 0).all()
         if atol == 1.0:

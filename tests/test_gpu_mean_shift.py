@@ -177,21 +177,32 @@ def case2(request, pn):
     tree.close()
 
 
-def loop_of_steps(tree, seeds, h, tol, max_iter):
+def loop_of_steps(tree, seeds, h, tol, max_iter, limit=None):
+    """the iteration as repeated ``max_iter = 1`` calls over the seeds still moving; ``h`` a scalar or one bandwidth per
+    seed; ``limit``: every such call takes at most that many positions (the longer ones are made in parts)"""
     ns = seeds.shape[0]
+    per_seed = np.ndim(h) != 0
+
+    def one_step(pos, hh):
+        step = len(pos) if limit is None else limit
+        parts = [tree.mean_shift_modes(hh[a:a + step] if per_seed else hh, pos[a:a + step], tol=0.0, max_iter=1, full=True)
+                 for a in range(0, len(pos), step)]
+        return [np.concatenate([p[i] for p in parts]) for i in range(4)]
+
     modes = seeds.copy()
     pw = np.zeros(ns, dtype=np.uint64)
     it = np.zeros(ns, dtype=np.uint32)
     sh = np.full(ns, np.nan)
     act = np.arange(ns)
     pos = seeds.copy()
+    hh = np.asarray(h, dtype=tree.dtype) if per_seed else h
     steps = iters = 0
     t = 0
     while act.size:
         t += 1
         iters += 1
         steps += act.size
-        m1, p1, _, s1, _ = tree.mean_shift_modes(h, pos, tol=0.0, max_iter=1, full=True)
+        m1, p1, _, s1 = one_step(pos, hh)
         dead = p1 == 0
         stop = dead | (s1 <= tol) | (t == max_iter)
         modes[act[stop]] = np.where(dead[stop, None], pos[stop], m1[stop])
@@ -199,6 +210,8 @@ def loop_of_steps(tree, seeds, h, tol, max_iter):
         it[act[stop]] = np.where(dead[stop], t - 1, t)
         sh[act[stop]] = s1[stop]
         act, pos = act[~stop], m1[~stop]
+        if per_seed:
+            hh = hh[~stop]
     return modes, pw, it, sh, (iters, steps)
 
 
