@@ -98,7 +98,11 @@ enum {
     PN_OPT_FILTER_SLOTS = 5, /* k' kept by the MFMA filter per (query, segment); 0 = auto */
     PN_OPT_MFMA_STRUCTURE = 6, /* f32 MFMA tier: 0 auto; 2 = persistent partition, LDS candidate buffers, 1 workgroup/CU;
                                  3 = persistent partition, HBM candidate buffers, 2 workgroups/CU (1, the first
-                                 structure -- a (query tile x segment) grid -- was retired in round 4: PN_ERR_INVALID) */
+                                 structure -- a (query tile x segment) grid -- was retired in round 4: PN_ERR_INVALID).
+                                 The LDS buffers of structure 2 hold k' <= 30 candidates per (query, segment): a call
+                                 that needs more (k above 27, or PN_OPT_FILTER_SLOTS above 30) is not an error -- the
+                                 f32 MFMA tier steps aside and the next tier answers it, as for every k' the tier
+                                 cannot hold */
     PN_OPT_EXCHANGE_ALWAYS = 7, /* pn_sharded_set_option only.  A handle with ONE shard answers straight into the
                                   caller's buffers (nothing to exchange); 1 sends it through the packed buffer, the
                                   all-gather and the merge all the same (tests: RCCL at world size 1) */

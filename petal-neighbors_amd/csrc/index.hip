@@ -1639,9 +1639,9 @@ static Bf16Plan bf16_plan_wide(const pn_index *ix, size_t nq_pad, size_t kout, i
         p.ok = level < 2 && p.kp + 32 <= 256;
         p.cap = p.ok ? bf16_cap_for(p.kp) : 0;
         // the re-rank kernel gathers all cells of a query into 64 KiB of LDS (12 B per slot + the query row)
-        if (best == 1 || (size_t)p.nseg * (size_t)p.cap * 12 + (ix->dim + 8) * 4 <= 60 * 1024) break;
+        if (best == 1 || select_rerank_lds_bytes(p.nseg, p.cap, 0, ix->dim, 4) <= 60 * 1024) break;
     }
-    if ((size_t)p.nseg * (size_t)p.cap * 12 + (ix->dim + 8) * 4 > 64 * 1024) p.ok = false;
+    if (select_rerank_lds_bytes(p.nseg, p.cap, 0, ix->dim, 4) > kSelectRerankLdsMax) p.ok = false;
     // a wave scouts 128 rows per tile; the scouted rows should hold < 0.1 of the R relevant rows in expectation
     const double sm = (double)ix->n / (10.0 * R) / 128.0;
     p.scout_max = sm > 32.0 ? 32 : (int)sm;
@@ -1928,37 +1928,60 @@ static Bf16Plan bf16_plan(const pn_index *ix, size_t nq_pad, size_t kout, int le
                 p.scout_tiles, p.seed_rank, p.scout_max, p.n_refresh, p.sh_rank, (int)p.model_seed, p.model_z);
     return p;
 }
-// f32 MFMA filter -> exact re-rank + proof -> (second tier, enqueued by the caller) exact engine for flagged queries
-static int run_mfma(const pn_index *ix, Workspace &ws, const float *Qp, size_t nq, size_t nq_pad, size_t kout,
-                    uint64_t *d_idx, float *d_dist, size_t out_stride, hipStream_t s, CallRec *rec) {
-    // candidate slots kept per (segment, query)
+// Plan of the f32 MFMA tier for one call: query_enqueue asks it whether the tier serves the call at all (ok), run_mfma
+// launches what it says.  A call it turns down goes to the next tier -- never back to the caller as an error.
+struct MfmaPlan {
+    bool ok = false;
+    int kp = 0;    // candidate slots kept per (segment, query)
+    int cap = 0;   // slots of a cell in the buffers the re-rank reads
+    int n_wg = 0, nseg = 0;
+    bool two_per_cu = false;  // HBM candidate buffers, two workgroups per CU (structure 3)
+};
+static MfmaPlan mfma_plan(const pn_index *ix, size_t kout, size_t nq_pad) {
+    MfmaPlan p;
     const size_t kp = mfma_slots(ix, kout, nq_pad);
-    // persistent-partition kernels: k' <= 30 with LDS candidate buffers (structure 2, wide rows), k' <= 224 with
+    // the filter keeps kp = kout + margin candidates per (segment, query) in <= 256 slots
+    if (kp + 64 > 256) return p;
+    // persistent-partition kernels: k' <= 30 with LDS candidate buffers (structure 2, wide rows), larger k' only with
     // HBM candidate buffers and two workgroups per CU (structure 3, the default for D <= 128)
     const bool hbm_ok = (ix->mfma_structure == 0 || ix->mfma_structure == 3);
-    const bool v2 = kp <= 30 || (hbm_ok && ix->ld <= 128 && kp <= 224);
-    if (!v2) return fail(PN_ERR_UNSUPPORTED, ix->ld > 128 ? "wide rows need k' <= 30 on the MFMA path"
-                                                            : "k' = %zu is beyond the MFMA path's buffers", kp);
-    const int cap = (int)round_up(kp, 32);
+    if (kp > 30 && !(hbm_ok && ix->ld <= 128)) return p;
+    p.kp = (int)kp;
+    p.cap = (int)round_up(kp, 32);
+    p.two_per_cu = hbm_ok;
+    // at most ~32 workgroups per query tile and at least ~32 row tiles per workgroup
+    const size_t q_tiles = nq_pad / 128, r_tiles = (ix->n + 63) / 64;
+    size_t n_wg = (size_t)(p.two_per_cu ? 2 * ix->n_cu : ix->n_cu);
+    size_t cap_wg = q_tiles * 32;
+    const size_t by_work = (q_tiles * r_tiles + 31) / 32;
+    if (by_work < cap_wg) cap_wg = by_work;
+    if (cap_wg < 1) cap_wg = 1;
+    if (n_wg > cap_wg) n_wg = cap_wg;
+    int nseg = mfma_v2_max_segments(q_tiles, (int)n_wg);
+    // The re-rank gathers all cells of a query into LDS; a cell holds at most k' entries once the filter has made its
+    // final cut (mfma_filter_v2.hip, "flush this run").  Where 33 segments of a large k' do not fit, fewer workgroups
+    // share a query tile: ceil(n_wg / q_tiles) + 1 segments, so (nseg - 1) * q_tiles workgroups give nseg of them.
+    while (nseg > 2 && select_rerank_lds_bytes(nseg, p.cap, p.kp, ix->dim, sizeof(float)) > kSelectRerankLdsMax) --nseg;
+    if (select_rerank_lds_bytes(nseg, p.cap, p.kp, ix->dim, sizeof(float)) > kSelectRerankLdsMax) return p;
+    if (nseg < mfma_v2_max_segments(q_tiles, (int)n_wg)) n_wg = (size_t)(nseg - 1) * q_tiles;
+    p.n_wg = (int)n_wg;
+    p.nseg = mfma_v2_max_segments(q_tiles, p.n_wg);
+    p.ok = true;
+    return p;
+}
+
+// f32 MFMA filter -> exact re-rank + proof -> (second tier, enqueued by the caller) exact engine for flagged queries
+static int run_mfma(const pn_index *ix, Workspace &ws, const MfmaPlan &plan, const float *Qp, size_t nq, size_t nq_pad,
+                    size_t kout, uint64_t *d_idx, float *d_dist, size_t out_stride, hipStream_t s, CallRec *rec) {
+    if (!plan.ok) return fail(PN_ERR_UNSUPPORTED, "MFMA tier cannot serve k = %zu", kout);
+    const size_t kp = (size_t)plan.kp;
+    const int cap = plan.cap, n_wg = plan.n_wg;
+    const bool two_per_cu = plan.two_per_cu;
     // scaled query norms (same kernel as the corpus norms)
     PNCHK(ws.w_qnorm.ensure(nq_pad * sizeof(float)));
     uint32_t *d_misc = (uint32_t *)ws.w_misc.p;  // [0] flagged count, [1] non-finite query norms, [4] second-tier list length
     HIPCHK(launch_row_norms_f32(Qp, nq_pad, nq, (int)ix->dim, ix->ld, mfma_alpha(ix->dim), (float *)ws.w_qnorm.p,
                                 d_misc + 1, s));
-    // structure 3: persistent partition with HBM candidate buffers and two workgroups per CU
-    const bool two_per_cu = hbm_ok;
-    int n_wg = two_per_cu ? 2 * ix->n_cu : ix->n_cu;
-    struct { int nseg; } plan{};
-    {
-        // at most ~32 workgroups per query tile and at least ~32 row tiles per workgroup
-        const size_t q_tiles = nq_pad / 128, r_tiles = (ix->n + 63) / 64;
-        size_t cap_wg = q_tiles * 32;
-        const size_t by_work = (q_tiles * r_tiles + 31) / 32;
-        if (by_work < cap_wg) cap_wg = by_work;
-        if (cap_wg < 1) cap_wg = 1;
-        if ((size_t)n_wg > cap_wg) n_wg = (int)cap_wg;
-        plan.nseg = mfma_v2_max_segments(nq_pad / 128, n_wg);
-    }
     const size_t cells = (size_t)plan.nseg * nq_pad;
     const size_t slots = cells * (size_t)cap;
     PNCHK(ws.w_keys.ensure(slots * sizeof(uint32_t)));
@@ -1986,7 +2009,7 @@ static int run_mfma(const pn_index *ix, Workspace &ws, const float *Qp, size_t n
     if (prof) HIPCHK(hipEventRecord(rec->ev[1], s));
     HIPCHK(launch_select_rerank_f32(cb, (const float *)ix->d_pts, ix->n, (int)ix->dim, ix->ld, Qp, (int)nq, ix->ld,
                                     (int)kout, ix->index_base, d_idx, d_dist, out_stride, (uint32_t *)ws.w_flags.p,
-                                    d_misc, nullptr, nullptr, (uint32_t *)ws.w_gsel.p, ix->d_stats, s));
+                                    d_misc, nullptr, nullptr, (uint32_t *)ws.w_gsel.p, ix->d_stats, s, 0, plan.kp));
     return PN_OK;
 }
 
@@ -2167,6 +2190,7 @@ static int query_enqueue(const pn_index *ix, Workspace &ws, const T *d_q, size_t
         T *od = d_dist + qs * out_stride;
         bool use_mfma = false, use_bf16 = false;
         Bf16Plan bplan{};
+        MfmaPlan mplan{};
         const T *qnorm = nullptr;
         if (ix->metric == 1) {  // Cosine: each query's norm over ITS OWN length (src/distance.rs:92-97), not the zip's
             PNCHK(ws.w_qnorm.ensure(nq_pad * sizeof(T)));
@@ -2176,9 +2200,8 @@ static int query_enqueue(const pn_index *ix, Workspace &ws, const T *d_q, size_t
         }
         if constexpr (sizeof(T) == 4) {
             if (ix->mfma_ok && dim_eff == ix->dim && ix->engine != PN_ENGINE_EXACT && ix->engine != PN_ENGINE_BF16) {
-                // the filter keeps kp = kout + margin candidates per (segment, query) in <= 256 slots
-                use_mfma = mfma_slots(ix, kout, nq_pad) + 64 <= 256;
-                if (ix->ld > 128 && mfma_slots(ix, kout, nq_pad) > 30) use_mfma = false;  // wide rows: LDS-buffer kernel only
+                mplan = mfma_plan(ix, kout, nq_pad);
+                use_mfma = mplan.ok;
                 if (ix->engine == PN_ENGINE_AUTO && (ix->n < 4096 || ix->dim < 8)) use_mfma = false;
             }
         }
@@ -2190,9 +2213,10 @@ static int query_enqueue(const pn_index *ix, Workspace &ws, const T *d_q, size_t
             (ix->engine == PN_ENGINE_BF16 || (ix->engine == PN_ENGINE_AUTO && ix->n >= 4096 && ix->dim >= 8))) {
             bplan = bf16_plan(ix, nq_pad, kout, level);
             use_bf16 = bplan.ok;
-            // the re-rank's LDS: (8 or 12) bytes per candidate slot + the query row
-            if (use_bf16 && (size_t)bplan.nseg * (size_t)bf16_cell_max(bplan.kp, bplan.cap, bplan.nseg, bf16_is_wide((int)ix->dim)) * (sizeof(T) + 8) +
-                                    (ix->dim + 8) * sizeof(T) > 64 * 1024)
+            // the re-rank's LDS: what its launcher will ask for (run_bf16 launches with cell_max = bf16_cell_max)
+            if (use_bf16 && select_rerank_lds_bytes(bplan.nseg, bplan.cap,
+                                                    bf16_cell_max(bplan.kp, bplan.cap, bplan.nseg, bf16_is_wide((int)ix->dim)),
+                                                    ix->dim, sizeof(T)) > kSelectRerankLdsMax)
                 use_bf16 = false;
         }
         // the head of the call: the zero-padded copy of the queries (+ the call's counters, zeroed) -- for narrow rows
@@ -2207,7 +2231,7 @@ static int query_enqueue(const pn_index *ix, Workspace &ws, const T *d_q, size_t
                 PNCHK(run_bf16<T>(ix, ws, bplan, (const T *)Qp, nqc, nq_pad, kout, oi, od, out_stride, s, rec,
                                   fused_head ? (const T *)(d_q + qs * q_stride) : nullptr, q_stride, qnorm));
             else if constexpr (sizeof(T) == 4)
-                PNCHK(run_mfma(ix, ws, (const float *)Qp, nqc, nq_pad, kout, oi, (float *)od, out_stride, s, rec));
+                PNCHK(run_mfma(ix, ws, mplan, (const float *)Qp, nqc, nq_pad, kout, oi, (float *)od, out_stride, s, rec));
             // the flagged count reaches pinned memory behind everything else (written by the second tier's merge
             // kernel, else by a copy); a LATER call looks at it
             uint32_t *h_dev = nullptr;

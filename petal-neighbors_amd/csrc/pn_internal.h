@@ -422,6 +422,14 @@ hipError_t launch_select_rerank_f32(const CandBuf &cb, const float *P, size_t n,
                                     unsigned long long *stats, hipStream_t s, int first_eval = 0, int cell_max = 0);
 // first_eval: candidates (smallest bounds first) evaluated in the first round, >= kout (0: kout); cell_max: entries a
 // (segment, query) cell holds at most (0: cb.cap) -- sizes the kernel's LDS
+// The re-rank kernel's dynamic LDS: 12 (f32) or 16 (f64) bytes per entry the nseg cells of a query can hold + the query
+// row.  The launchers refuse a launch above kSelectRerankLdsMax; a planner asks THIS function before it picks a tier, so
+// that what it admits is what the launcher takes.
+constexpr size_t kSelectRerankLdsMax = 64 * 1024;
+inline size_t select_rerank_lds_bytes(int nseg, int cap, int cell_max, size_t dim, size_t elem_bytes) {
+    const size_t per_cell = cell_max > 0 && cell_max < cap ? (size_t)cell_max : (size_t)cap;
+    return (size_t)nseg * per_cell * (elem_bytes + 8) + (dim + 8) * elem_bytes;
+}
 // f64 indexes behind the bf16 filter (qn required): distances in the reference's f64 fold, proof with u = 2^-53
 hipError_t launch_select_rerank_f64(const CandBuf &cb, const double *P, size_t n, int dim, size_t ldp,
                                     const double *Q, int nq, size_t ldq, int kout, uint64_t index_base,

@@ -810,9 +810,9 @@ static hipError_t launch_select_rerank(const CandBuf &cb, const T *P, size_t n, 
     const uint32_t *ckey = static_cast<const uint32_t *>(cb.keys);
     // LDS for what the cells can HOLD (cell_max entries each: the filter's k' after its final cut), not for their
     // capacity: C2 12 x 13 entries = 1.9 KB instead of 9.2 KB, and the waves per CU are no longer set by LDS
-    const size_t per_cell = cell_max > 0 && cell_max < cb.cap ? (size_t)cell_max : (size_t)cb.cap;
-    const size_t sh = (size_t)cb.nseg * per_cell * (sizeof(KeyT) + 8) + ((size_t)dim + 8) * sizeof(T);
-    if (sh > 64 * 1024) return hipErrorInvalidValue;
+    static_assert(sizeof(KeyT) == sizeof(T), "select_rerank_lds_bytes counts a key as one element");
+    const size_t sh = select_rerank_lds_bytes(cb.nseg, cb.cap, cell_max, (size_t)dim, sizeof(T));
+    if (sh > kSelectRerankLdsMax) return hipErrorInvalidValue;
     if (cnorm) {  // a Cosine index: the bf16 filter's (key, row) pairs only
         if (!ckey || !qnorm || !qn) return hipErrorInvalidValue;
         hipLaunchKernelGGL((select_rerank_kernel<T, true>), dim3((unsigned)nq), dim3(64), sh, s,
