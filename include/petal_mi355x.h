@@ -113,9 +113,13 @@ enum {
                                   result: only how many candidates the filter keeps. */
     PN_OPT_BF16_WAVES = 9,       /* bf16 tier, narrow rows, main pass of a k-NN call: 0 (default) = the library picks -- the
                                   8-wave kernel (one 32-query column block per wave, four waves per SIMD) for short runs,
-                                  the 4-wave kernel (two column blocks per wave, two waves per SIMD) for long ones; 4 / 8
-                                  = always that kernel where it applies.  Never changes a result (A/B measurements,
-                                  tests of both kernels). */
+                                  the 4-wave kernel (two column blocks per wave, two waves per SIMD) or, for long runs
+                                  over at least two query tiles with 64-slot buffers and no refreshers on a grid that
+                                  fills every workgroup slot of the device, the paired
+                                  kernel (one 8-wave workgroup per CU over two query tiles, its SIMD partners in
+                                  anti-phase); 4 / 8 = always that kernel where it applies; 16 = the paired kernel where
+                                  it applies, else the 4-wave kernel.  Never changes a result (A/B measurements, tests
+                                  of all three kernels). */
     PN_OPT_SEED_MODEL = 10,      /* bf16 tier, indexes of narrow rows (D <= 128) whose seed model was accepted at build
                                   (pn_info.seed_model): 1 (default) = k-NN calls with k <= 128 take their starting
                                   thresholds from the model (no scout launch); 0 = always scout.  Never changes a result:

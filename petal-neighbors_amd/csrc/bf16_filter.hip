@@ -54,6 +54,9 @@
 #include "pn_internal.h"
 #include "topk_buffer.h"
 
+#include <cstdio>
+#include <cstdlib>
+
 namespace pn {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -988,11 +991,17 @@ __device__ __forceinline__ f32x16 bf_cinit(const char *tb, int blk, int h) {
 // fragments of its own left to request, it requests the same for the NEXT chain (narow / ntb, nblk: the other block of
 // this tile, or block 0 of the next tile).  So no chain waits for LDS at its head, and whatever sits between two
 // chains (the survivor check, the barrier, the LDS-DMA issue) does not delay the first MFMA behind it by a round trip.
-template <int KS, bool CI, int CP>
+// MID: something to do in front of step MID::at(KS) (the paired kernel's lagging half meets its workgroup in mid-chain,
+// bf16_filter_kernel_pair); nothing for everybody else.
+struct BfNoMid {
+    static constexpr int at(int) { return -1; }
+    __device__ __forceinline__ void operator()() const {}
+};
+template <int KS, bool CI, int CP, typename MID = BfNoMid>
 __device__ __forceinline__ void bf_chain_p(const char *arow, bf16x8 (&pre)[kLA], const bf16x8 (&b0)[KS],
                                            const bf16x8 (&b1)[KS], f32x16 &c, f32x16 &w0, f32x16 &w1, f32x16 &r0,
                                            f32x16 &r1, float &m0, float &m1, const char *narow, const char *ntb,
-                                           int nblk, int h) {
+                                           int nblk, int h, MID mid = MID()) {
     typedef float f32x4_ __attribute__((ext_vector_type(4)));
     bf16x8 f[KS];
 #pragma unroll
@@ -1002,6 +1011,7 @@ __device__ __forceinline__ void bf_chain_p(const char *arow, bf16x8 (&pre)[kLA],
     for (int i = 0; i < 16; ++i) z[i] = 0.0f;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
+        if (ks == MID::at(KS)) mid();
         if (ks + kLA < KS) f[ks + kLA] = *reinterpret_cast<const bf16x8 *>(arow + 32 * (ks + kLA));
         // the next chain's first fragments: fragment i at step max(0, KS - kLA + i)
 #pragma unroll
@@ -2187,6 +2197,294 @@ __global__ __launch_bounds__(512, 4) void bf16_filter8_kernel(const char *__rest
 }
 
 // ---------------------------------------------------------------------------
+// bf16_filter_kernel_pair (round 5) -- the main pass of a k-NN call with ONE 8-wave workgroup per CU whose SIMD
+// partners run in ANTI-PHASE.
+//
+// In bf16_filter_kernel the two waves of a SIMD belong to two independent workgroups, and what each does outside its
+// MFMA chains (survivor check, tile barrier, LDS-DMA issue) falls wherever chance puts it against the other's: both
+// are outside their chains 29 % of the time and the matrix pipe idles.  Here the partners are the two
+// halves of one workgroup -- waves 0-3 serve query tile 2t, waves 4-7 query tile 2t + 1, over the SAME row range, tile
+// stream and three LDS tile buffers -- so that the one s_barrier per tile ties their phases together.  A wave is
+// exactly the 4-wave kernel's wave (two 32-query column blocks, B fragments in 8 KS registers, bf_chain_p, bf_slow,
+// the end-of-run cut, one writer per (segment, query) cell); the 2 KS + 1 pieces of a tile are spread over the eight
+// waves as in bf16_filter8_kernel.
+//
+// Schedule of tile rt (chain A: row block 0, chain B: row block 1; "survivors" is the rare-path check):
+//   waves 0-3 (LEAD):  chain A | survivors | DMA wait + s_barrier | DMA issue rt+2 | chain B | survivors
+//   waves 4-7 (LAG):   chain A, first KS/2 steps | DMA wait + s_barrier | rest of chain A | survivors | DMA issue rt+2
+//                      | chain B | survivors
+// Both do the same work between two barriers, the lagging half displaced by half a chain: its gaps (survivors and DMA
+// issue after chain A, survivors after chain B) fall into the leading half's chains and the other way round.
+//
+// What the barrier B(rt) certifies is what it certifies in the 4-wave kernel, and three buffers still suffice:
+//  * tile rt+1 has landed: every wave's pieces of it were issued behind B(rt-1) and are waited for (the counted
+//    vmcnt of bf_wait_dma) before the wave arrives at B(rt); its first readers are the last steps of chain B of tile
+//    rt (the requests for the next chain), behind B(rt) in both roles;
+//  * nobody reads tile rt-1 any more, so its buffer can take tile rt+2 (issued behind B(rt) in both roles): the last
+//    reads of tile rt-1 are the fragment requests of chain B of tile rt-1.  The leading half has finished chain A of
+//    tile rt since and waits lgkmcnt(0).  The lagging half finished that chain half a chain before it arrives; it
+//    does not wait for its LDS reads in flight (fragments of tile rt, kLA steps ahead), and need not: LDS reads of a
+//    wave return in order, and the MFMAs of the steps before the barrier have consumed fragments requested AFTER the
+//    last request into tile rt-1.
+// Barrier counts are the same in both roles by construction: the prologue's __syncthreads is executed before the
+// roles part, and the roles are two instantiations of ONE loop (bf_pair_run) over the same rt0 .. rt1 with exactly one
+// s_barrier per iteration and none behind the loop.
+//
+// Main pass only (thresholds given), 64-slot buffers, aligned partition, no refreshers.  With an odd number of
+// query tiles the upper half of the last pair has no queries: it moves its DMA pieces, meets every barrier and runs its
+// chains against zero B fragments with thresholds of -inf -- nothing survives, it reads and writes no query data.
+// STAG (diagnostic builds: -DPN_DIAG_PAIR_STAGGER=0 / 2): 0 = both halves in the leading placement, 2 = the lagging
+// half displaced by a whole chain (barrier in front of chain A), where the gaps coincide again.
+// ---------------------------------------------------------------------------
+#ifndef PN_DIAG_PAIR_STAGGER
+#define PN_DIAG_PAIR_STAGGER 1
+#endif
+constexpr int kPairStagger = PN_DIAG_PAIR_STAGGER;  // 1: half a chain
+#ifndef PN_DIAG_PAIR_MID4
+#define PN_DIAG_PAIR_MID4 2
+#endif
+struct BfPairMeet {  // the lagging half's tile barrier, inside chain A: after KS / 2 steps (diagnostic builds: KS MID4 / 4),
+    uint32_t ns;     // at least one -- the argument above needs an MFMA of this chain in front of the barrier
+    static constexpr int at(int ks) { return ks * PN_DIAG_PAIR_MID4 / 4 > 1 ? ks * PN_DIAG_PAIR_MID4 / 4 : 1; }
+    __device__ __forceinline__ void operator()() const {
+        bf_wait_dma(ns);
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+    }
+};
+
+template <int KS, bool CI, int STAG>
+__device__ __forceinline__ void bf_pair_run(const char *__restrict__ img, char *tiles, uint32_t kp, uint32_t kfin, uint2 *__restrict__ cand,
+                                            uint32_t *__restrict__ ccnt, uint32_t *__restrict__ ctau,
+                                            const bf16x8 (&b0)[KS], const bf16x8 (&b1)[KS], float tau0, float tau1,
+                                            uint32_t rt0, uint32_t rt1, size_t cell0, bool active, int wave, int lane) {
+    constexpr int C = 2 * KS, CP = C + 1;
+    constexpr uint32_t CAP = 64u;
+    constexpr int TB = kBP * CP * 16;  // bytes per tile image
+    constexpr int NBUF = 3, NW = 8;
+    const int jq = lane & 31, h = lane >> 5;
+    BF_DBG_DECL;
+    // wave w moves the consecutive pieces [w P, w P + P) of a tile (bf16_filter8_kernel)
+    constexpr int P = (CP + NW - 1) / NW;
+    static_assert(P <= 3, "piece schedule written out for up to three pieces per wave");
+    const int n_mine = CP - wave * P < P ? (CP - wave * P > 0 ? CP - wave * P : 0) : P;
+    const uint32_t lane_off = (uint32_t)lane * 16u;
+    auto dma_tile = [&](uint32_t rt, int buf) {
+        const char *wbase = img + ((size_t)rt * (size_t)TB + (size_t)(wave * (P * 1024)));  // wave-uniform
+        const char *ws = wbase + lane_off;
+        char *wd = tiles + buf * TB + wave * (P * 1024);
+        if (0 < n_mine) __builtin_amdgcn_global_load_lds((glb_void_b *)ws, (lds_void_b *)wd, 16, 0, 0);
+        if (P > 1 && 1 < n_mine) __builtin_amdgcn_global_load_lds((glb_void_b *)ws, (lds_void_b *)wd, 16, 1024, 0);
+        if (P > 2 && 2 < n_mine) __builtin_amdgcn_global_load_lds((glb_void_b *)ws, (lds_void_b *)wd, 16, 2048, 0);
+    };
+
+    uint32_t cnt0 = 0, cnt1 = 0;
+    uint2 *ce_blk0 = cand + cell0 * CAP;          // query block 0: 32 buffers
+    uint2 *ce_blk1 = ce_blk0 + (size_t)32 * CAP;  // query block 1
+    uint2 *ceq0 = ce_blk0 + (size_t)jq * CAP, *ceq1 = ce_blk1 + (size_t)jq * CAP;
+    uint32_t ns = 0;
+
+    f32x16 a00, a01, a10, a11;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {  // "nothing here yet": above every threshold
+        a00[r] = 3.0e38f;
+        a01[r] = 3.0e38f;
+        a10[r] = 3.0e38f;
+        a11[r] = 3.0e38f;
+    }
+    bf16x8 pre[kLA];
+    f32x16 cc = a00;  // (placeholder unless CI)
+    {
+        const char *ar = tiles + (jq * CP + h) * 16;
+#pragma unroll
+        for (int i = 0; i < kLA; ++i) pre[i] = *reinterpret_cast<const bf16x8 *>(ar + 32 * (i < KS ? i : 0));
+        if (CI) cc = bf_cinit<CP>(tiles, 0, h);
+    }
+    int cur = 0;
+    for (uint32_t rt = rt0; rt < rt1; ++rt) {  // ONE s_barrier per iteration, whatever STAG
+        const int nxt = cur == NBUF - 1 ? 0 : cur + 1, prv = cur == 0 ? NBUF - 1 : cur - 1;
+        const char *tb = tiles + cur * TB;
+        const char *arow0 = tb + (jq * CP + h) * 16;
+        const char *arow1 = arow0 + 32 * CP * 16;
+        float m0, m1, p0, p1;
+        if (STAG == 2) BfPairMeet{ns}();
+        if (STAG == 1)
+            bf_chain_p<KS, CI, CP>(arow0, pre, b0, b1, cc, a00, a01, a10, a11, m0, m1, arow1, tb, 1, h, BfPairMeet{ns});
+        else
+            bf_chain_p<KS, CI, CP>(arow0, pre, b0, b1, cc, a00, a01, a10, a11, m0, m1, arow1, tb, 1, h);
+        if (rt == rt0) { m0 = __uint_as_float(0x7F800000u); m1 = m0; }  // nothing precedes the first tile
+        if (__any(m0 < tau0 || m1 < tau1)) {
+            const uint32_t row0 = (rt - 1) * kBP + 32;
+            if (__any(m0 < tau0)) bf_slow<1, false>(a10, m0, tau0, cnt0, row0, h, jq, lane, kp, ceq0, ce_blk0, ns BF_DBG_PASS);
+            if (__any(m1 < tau1)) bf_slow<1, false>(a11, m1, tau1, cnt1, row0, h, jq, lane, kp, ceq1, ce_blk1, ns BF_DBG_PASS);
+        }
+        if (STAG == 0) {  // the leading placement: between the tile's two chains
+            bf_wait_dma(ns);
+#ifndef PN_DIAG_PAIR_NOLGKM
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#endif
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+        }
+        if (rt + 2 < rt1) {
+            dma_tile(rt + 2, prv);
+            ns = 0;
+        }
+        const bool last = rt + 1 >= rt1;  // (then the requests below are never used: any valid LDS address)
+        const char *ntb = last ? tb : tiles + nxt * TB;
+        bf_chain_p<KS, CI, CP>(arow1, pre, b0, b1, cc, a10, a11, a00, a01, p0, p1, ntb + (jq * CP + h) * 16, ntb, 0, h);
+        if (__any(p0 < tau0 || p1 < tau1)) {
+            const uint32_t row0 = rt * kBP;
+            if (__any(p0 < tau0)) bf_slow<1, false>(a00, p0, tau0, cnt0, row0, h, jq, lane, kp, ceq0, ce_blk0, ns BF_DBG_PASS);
+            if (__any(p1 < tau1)) bf_slow<1, false>(a01, p1, tau1, cnt1, row0, h, jq, lane, kp, ceq1, ce_blk1, ns BF_DBG_PASS);
+        }
+        cur = nxt;
+    }
+    {  // drain: block 1 of the last tile
+        float m0 = a10[0], m1 = a11[0];
+#pragma unroll
+        for (int i = 1; i < 16; ++i) {
+            m0 = fminf(m0, a10[i]);
+            m1 = fminf(m1, a11[i]);
+        }
+        const uint32_t row0 = (rt1 - 1) * kBP + 32;
+        if (__any(m0 < tau0)) bf_slow<1, false>(a10, m0, tau0, cnt0, row0, h, jq, lane, kp, ceq0, ce_blk0, ns BF_DBG_PASS);
+        if (__any(m1 < tau1)) bf_slow<1, false>(a11, m1, tau1, cnt1, row0, h, jq, lane, kp, ceq1, ce_blk1, ns BF_DBG_PASS);
+    }
+    // ---- end of run (no barrier from here on): a buffer holding more than kfin entries is cut to its k' smallest, four
+    // buffers' entries requested together (bf16_filter_kernel); publish count and threshold
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    auto final_compact = [&](uint2 *ce_blk, float &tau, uint32_t &cnt) {
+        constexpr int NB = 4;
+        unsigned long long need = __ballot(h == 0 && cnt > kfin);
+        while (need) {
+            int jj[NB];
+            uint32_t cj[NB], key[NB][1], ixs[NB][1];
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                jj[b] = need ? __builtin_ctzll(need) : -1;
+                if (need) need &= need - 1;
+                cj[b] = jj[b] >= 0 ? (uint32_t)__builtin_amdgcn_readlane((int)cnt, jj[b] >= 0 ? jj[b] : 0) : 0u;
+                if (jj[b] >= 0) bf_compact_load<1>(ce_blk + (size_t)jj[b] * CAP, cj[b], lane, key[b], ixs[b]);
+            }
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                if (jj[b] >= 0) {
+                    uint32_t T, nn;
+                    bf_compact_finish<1>(ce_blk + (size_t)jj[b] * CAP, key[b], ixs[b], cj[b], kp, lane, T, nn);
+                    if (jq == jj[b]) { tau = fminf(tau, s2f(T)); cnt = nn; }
+                }
+            }
+        }
+    };
+    final_compact(ce_blk0, tau0, cnt0);
+    final_compact(ce_blk1, tau1, cnt1);
+    if (active && h == 0) {
+        ccnt[cell0 + jq] = cnt0;
+        ctau[cell0 + jq] = f2s(tau0);
+        ccnt[cell0 + 32 + jq] = cnt1;
+        ctau[cell0 + 32 + jq] = f2s(tau1);
+    }
+    BF_DBG_FLUSH(lane);
+}
+
+template <int KS, bool CI>
+__global__ __launch_bounds__(512, 2) void bf16_filter_kernel_pair(const char *__restrict__ img, uint32_t n_tiles,
+                                                                  const u32x4 *__restrict__ Bq, uint32_t q_tiles,
+                                                                  uint32_t kp_keep, uint2 *__restrict__ cand,
+                                                                  uint32_t *__restrict__ ccnt,
+                                                                  uint32_t *__restrict__ ctau, size_t nq_pad,
+                                                                  const uint32_t *tau_init, BfShared sh) {
+    const uint32_t kp = kp_keep & 0xFFFFu, keep_arg = kp_keep >> 16;
+    const uint32_t kfin = keep_arg > kp ? keep_arg : kp;
+    constexpr int CP = 2 * KS + 1;
+    constexpr int TB = kBP * CP * 16;  // bytes per tile image
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    char *tiles = reinterpret_cast<char *>(smem_raw);  // [3][TB]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int jq = lane & 31, h = lane >> 5;
+    constexpr int C = 2 * KS;
+    // Aligned partition (the host guarantees it), counted in PAIRS of query tiles: W = c n_pairs workgroups, workgroup
+    // w = row range p of pair t in the range-major, XCD-contiguous order of bf16_filter_kernel (the blocks of one XCD
+    // walk the same row range).  The c row ranges are the 4-wave kernel's: every (segment, query) cell keeps its writer.
+    const uint32_t W = gridDim.x, n_pairs = (q_tiles + 1u) >> 1, c_per = W / n_pairs;
+    uint32_t w;
+    {
+        const uint32_t b = blockIdx.x, x = b & 7u, base = W >> 3, rem = W & 7u;
+        const uint32_t L = x * base + (x < rem ? x : rem) + (b >> 3);  // XCDs 0 .. rem-1 run base + 1 blocks
+        w = (L % n_pairs) * c_per + L / n_pairs;
+    }
+    const uint32_t pt = w / c_per, seg = w % c_per;
+    const uint32_t rt0 = (uint32_t)((unsigned long long)seg * n_tiles / c_per);
+    const uint32_t rt1 = (uint32_t)((unsigned long long)(seg + 1) * n_tiles / c_per);
+    if (rt0 >= rt1) return;  // (workgroup-uniform)
+    const uint32_t qt = 2u * pt + (uint32_t)(wave >> 2);
+    const bool active = qt < q_tiles;  // odd q_tiles: the last pair's upper half has no queries
+    const size_t q0 = active ? (size_t)qt * kBQ + (size_t)(wave & 3) * 64 : 0;  // first query of this wave
+    const size_t cell0 = (size_t)seg * nq_pad + q0;                             // its (segment, query) cell
+
+    // ---- per-run state: B fragments and thresholds in registers (requested in front of the prologue's barrier, whose
+    // vmcnt(0) covers them: the tile loop then never waits for vector memory at its top)
+    bf16x8 b0[KS], b1[KS];
+    float tau0 = __uint_as_float(0xFF800000u), tau1 = tau0;  // (a half without queries keeps -inf)
+    if (active) {
+        const u32x4 *br0 = Bq + (q0 + jq) * (size_t)C + h;
+        const u32x4 *br1 = br0 + (size_t)32 * C;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const u32x4 v0 = br0[2 * ks], v1 = br1[2 * ks];
+            b0[ks] = __builtin_bit_cast(bf16x8, v0);
+            b1[ks] = __builtin_bit_cast(bf16x8, v1);
+        }
+        if (sh.seed_lists) {  // as the 4-wave kernel: lane L derives query q0 + L's threshold, the lanes pick up their two
+            const size_t ql = q0 + (size_t)lane;
+            float sd = __uint_as_float(0xFF800000u);
+            if (ql < (size_t)sh.seed_nq) {
+                const uint32_t key = f2s(bf_seed_lane(sh.seed_lists, nq_pad, sh.nseg, sh.seed_rank, ql));
+                sd = s2f(key == 0xFFFFFFFFu ? key : key + 1u);  // rows with a bound EQUAL to it still pass the strict '<'
+            }
+            tau0 = __shfl(sd, jq);
+            tau1 = __shfl(sd, 32 + jq);
+        } else {
+            tau0 = s2f(tau_init[q0 + jq]);
+            tau1 = s2f(tau_init[q0 + 32 + jq]);
+        }
+    } else {
+        const u32x4 zero = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            b0[ks] = __builtin_bit_cast(bf16x8, zero);
+            b1[ks] = b0[ks];
+        }
+    }
+    // prologue, the same instructions for both halves: the run's first two tiles, one barrier (it carries the vmcnt(0))
+    {
+        constexpr int P = (CP + 7) / 8;
+        const int n_mine = CP - wave * P < P ? (CP - wave * P > 0 ? CP - wave * P : 0) : P;
+        // (rt0 + t < rt1, and `rt + 2 < rt1` / `last` in bf_pair_run: the guards of one- and two-tile runs.  No call
+        // reaches them -- the plan's shortest aligned run is ~9-12 tiles, tests/test_gpu_bf16_pair.py -- so they are
+        // argued, not exercised: a one-tile run loads one tile, meets its one barrier and requests nothing further.)
+        for (uint32_t t = 0; t < 2u && rt0 + t < rt1; ++t) {
+            const char *ws = img + ((size_t)(rt0 + t) * (size_t)TB + (size_t)(wave * (P * 1024))) + (uint32_t)lane * 16u;
+            char *wd = tiles + t * TB + wave * (P * 1024);
+            if (0 < n_mine) __builtin_amdgcn_global_load_lds((glb_void_b *)ws, (lds_void_b *)wd, 16, 0, 0);
+            if (P > 1 && 1 < n_mine) __builtin_amdgcn_global_load_lds((glb_void_b *)ws, (lds_void_b *)wd, 16, 1024, 0);
+            if (P > 2 && 2 < n_mine) __builtin_amdgcn_global_load_lds((glb_void_b *)ws, (lds_void_b *)wd, 16, 2048, 0);
+        }
+    }
+    __syncthreads();
+    // the two roles: one loop, two placements of its barrier; split by wave number >= 4, the SIMD partner of wave w is
+    // wave w + 4 (MI355X_MICROARCH.md, "Two waves per SIMD", item 9)
+    if (wave >= 4)
+        bf_pair_run<KS, CI, kPairStagger>(img, tiles, kp, kfin, cand, ccnt, ctau, b0, b1, tau0, tau1, rt0, rt1, cell0,
+                                          active, wave, lane);
+    else
+        bf_pair_run<KS, CI, 0>(img, tiles, kp, kfin, cand, ccnt, ctau, b0, b1, tau0, tau1, rt0, rt1, cell0, active, wave,
+                               lane);
+}
+
+// ---------------------------------------------------------------------------
 // Wide rows (128 < D <= 1024): the query operand no longer fits the register file, so the contraction is a
 // K-chunked tile product with BOTH operands streamed through LDS:
 //  * a workgroup is 8 waves and owns a 256-row x 256-query tile; wave (rh, qg) computes the 128 x 64 sub-tile of
@@ -2790,6 +3088,16 @@ template hipError_t launch_bf16_pack_queries<double>(const double *, const float
 // of 8 waves: profiles/r04_waves_ab_model.log)
 constexpr uint32_t kBf8MaxRun = 200;  // runs shorter than this many tiles take the 8-wave main-pass kernel
 constexpr size_t kBf8MaxImage = (size_t)768 << 20;  // ... on corpora whose tile image is at most this large
+constexpr bool kPairAuto = true;      // the automatic choice may take the paired kernel (bf16_filter_kernel_pair)
+#ifndef PN_DIAG_PAIR_MIN_RUN
+#define PN_DIAG_PAIR_MIN_RUN 200
+#endif
+constexpr uint32_t kPairMinRun = PN_DIAG_PAIR_MIN_RUN;  // ... for runs of at least this many tiles (64-slot buffers, >= 2 query tiles)
+// PN_DEBUG_PLAN: one line per main-pass launch of a k-NN call -- which kernel (4 / 8 / pair) and its grid
+static void bf_debug_kernel(const char *which, unsigned grid, unsigned block) {
+    static const bool on = getenv("PN_DEBUG_PLAN") != nullptr;
+    if (on) std::fprintf(stderr, "bf16 main pass: kernel %s grid %u x %u\n", which, grid, block);
+}
 template <int KS, int M, bool RAD, bool CI>
 static hipError_t launch_bf16_t(const void *img, uint32_t n_tiles, const void *B, uint32_t q_tiles, uint32_t kp,
                                 const CandBuf &cb, int n_wg, uint32_t split, uint32_t spp, uint32_t scout_max,
@@ -2835,6 +3143,31 @@ static hipError_t launch_bf16_t(const void *img, uint32_t n_tiles, const void *B
         // buffers 181 vs 196 ms; 12.5M x 96: 1.89 vs 2.01 s -- while at 1M rows the 8-wave kernel holds its 0-9 %: the
         // automatic choice takes it only where the image is at most kBf8MaxImage bytes)
         const size_t image_bytes = (size_t)n_tiles * kBP * (2 * KS + 1) * 16;
+        // The paired kernel (bf16_filter_kernel_pair): where the 8-wave kernel may run, with 64-slot buffers, no
+        // refreshers and at least two query tiles.  PN_OPT_BF16_WAVES = 16 forces it where it applies; the automatic
+        // choice takes it for the long runs (the A/B behind kPairMinRun).
+        if constexpr (M == 1) {
+            const bool can_pair = aligned && !scout_out && (tau_init || bsh.seed_lists) && !use_sh && q_tiles >= 2;
+            // (automatic choice: only grids of the 4-wave kernel that fill every workgroup slot -- two of its workgroups
+            // then share a CU anyway, which is the regime of the A/B.  A grid below that gives each 4-wave workgroup a CU
+            // or a SIMD quarter of its own; pairing would put two waves on every SIMD of half as many CUs: not measured,
+            // and by the cycle budget a loss.)
+            const bool fills = cb.wg_slots > 0 && n_wg >= cb.wg_slots;
+            const bool want_pair = cb.bf16_waves == 16 || (cb.bf16_waves == 0 && kPairAuto && fills &&
+                                                           run_tiles >= kPairMinRun && image_bytes <= kBf8MaxImage);
+            if (want_pair && can_pair) {
+                const unsigned grid = (unsigned)(((q_tiles + 1u) / 2u) * ((uint32_t)n_wg / q_tiles));
+                auto kern = bf16_filter_kernel_pair<KS, CI>;
+                static LdsAttrOnce lds_attr; /* per instantiation */
+                const hipError_t e = lds_attr.ensure(reinterpret_cast<const void *>(kern), sh);
+                if (e != hipSuccess) return e;
+                bf_debug_kernel("pair", grid, 512);
+                hipLaunchKernelGGL(kern, dim3(grid), dim3(512), sh, s, static_cast<const char *>(img), n_tiles,
+                                   static_cast<const u32x4 *>(B), q_tiles, kp_keep, static_cast<uint2 *>(cb.keys), cb.cnt,
+                                   static_cast<uint32_t *>(cb.tau), cb.nq_pad, tau_init, bsh);
+                return hipGetLastError();
+            }
+        }
         const bool want8 = cb.bf16_waves == 8 || (cb.bf16_waves == 0 && image_bytes <= kBf8MaxImage &&
                                                   (M >= 2 || run_tiles < kBf8MaxRun));
         if (want8 && aligned && !scout_out && (tau_init || bsh.seed_lists)) {
@@ -2858,6 +3191,7 @@ static hipError_t launch_bf16_t(const void *img, uint32_t n_tiles, const void *B
                            static_cast<const u32x4 *>(B), q_tiles, kp_keep, static_cast<uint2 *>(cb.keys), cb.cnt,      \
                            static_cast<uint32_t *>(cb.tau), cb.nq_pad, tau_init, a);                                    \
     }
+            bf_debug_kernel("8", grid, 512);
             if (use_sh) PN_BF_LAUNCH8(true) else PN_BF_LAUNCH8(false)
 #undef PN_BF_LAUNCH8
             return hipGetLastError();
@@ -2876,6 +3210,7 @@ static hipError_t launch_bf16_t(const void *img, uint32_t n_tiles, const void *B
             a.n_main = (uint32_t)n_wg;
             a.epoch = shp->epoch;
             a.rank = shp->rank;
+            bf_debug_kernel("4", (unsigned)(n_wg + shp->n_refresh), 256);
             hipLaunchKernelGGL(kern, dim3((unsigned)(n_wg + shp->n_refresh)), dim3(256), sh, s,
                                static_cast<const char *>(img), n_tiles, static_cast<const u32x4 *>(B), q_tiles, kp_keep,
                                static_cast<uint2 *>(cb.keys), cb.cnt, static_cast<uint32_t *>(cb.tau), cb.nq_pad, split,
@@ -2889,6 +3224,7 @@ static hipError_t launch_bf16_t(const void *img, uint32_t n_tiles, const void *B
         if (RAD) return hipErrorInvalidValue;
         PN_BF_LAUNCH_MODE(1)
     } else if (tau_init) {
+        if (!RAD) bf_debug_kernel("4", (unsigned)n_wg, 256);
         PN_BF_LAUNCH_MODE(2)
     } else {
         if (RAD) return hipErrorInvalidValue;

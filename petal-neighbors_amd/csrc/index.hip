@@ -250,7 +250,7 @@ struct pn_index {
     int filter_slots = 0;
     int mfma_structure = 0;  // 0 auto, 2 = persistent partition with LDS buffers, 3 = with HBM buffers (1: retired)
     int shared_tau = 1;      // PN_OPT_SHARED_THRESHOLDS: 0 off, 1 auto, >= 2 the rank itself
-    int bf16_waves = 0;      // PN_OPT_BF16_WAVES: 0 auto (8-wave main-pass kernel where it applies), 4 = 4-wave kernel
+    int bf16_waves = 0;      // PN_OPT_BF16_WAVES: 0 auto, 4 = 4-wave kernel, 8 = 8-wave kernel, 16 = paired kernel (where they apply)
     // Seed model (round 4, seed_model_build): starting thresholds of a k-NN call from per-dimension moments of the corpus,
     // calibrated against the scout's own seeds at build time -- the calls it serves run WITHOUT the scout launch.
     float *d_smodel = nullptr;   // [3][ld] f32: M1_k | 4 (M2_k - M1_k^2) | 4 (M3_k - M2_k M1_k), zero padded
@@ -999,7 +999,7 @@ extern "C" int pn_index_set_option(pn_index *ix, int option, int64_t value) {
             ix->shared_tau = (int)value;
             return PN_OK;
         case PN_OPT_BF16_WAVES:
-            if (value != 0 && value != 4 && value != 8) return fail(PN_ERR_INVALID, "bad wave count (0, 4 or 8)");
+            if (value != 0 && value != 4 && value != 8 && value != 16) return fail(PN_ERR_INVALID, "bad wave count (0, 4, 8 or 16)");
             ix->bf16_waves = (int)value;
             return PN_OK;
         case PN_OPT_SEED_MODEL:
@@ -2072,6 +2072,7 @@ static int run_bf16(const pn_index *ix, Workspace &ws, const Bf16Plan &plan, con
     CandBuf cb{ws.w_keys.p, (uint32_t *)ws.w_keys.p + 1, (uint32_t *)ws.w_cnt.p, ws.w_tau.p, nq_pad, nseg, cap, 2};
     cb.final_keep = bf16_cell_max((int)kp, cap, nseg, bf16_is_wide((int)ix->dim));  // what the re-rank sizes its LDS for
     cb.bf16_waves = ix->bf16_waves;
+    cb.wg_slots = 2 * ix->n_cu;
     if (!plan.aligned) {  // cells without a writer must read "empty" (an aligned partition writes every cell)
         HIPCHK(hipMemsetAsync(ws.w_cnt.p, 0, cells * sizeof(uint32_t), s));
         HIPCHK(hipMemsetD32Async((hipDeviceptr_t)ws.w_tau.p, (int)0xFF800000u, cells, s));

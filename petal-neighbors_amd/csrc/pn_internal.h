@@ -62,7 +62,9 @@ struct CandBuf {
     int cap;         // slots per (segment, query); multiple of 64
     int idx_stride = 1;  // 2: keys and idx interleaved as (key, row) pairs, idx = keys + 1 (bf16 filter)
     int final_keep = 0;  // bf16 filter, 64-slot buffers: a buffer holding at most this many entries ends its run uncut (0: k')
-    int bf16_waves = 0;  // PN_OPT_BF16_WAVES: 0 = the 8-wave main-pass kernel where it applies, 4 = the 4-wave kernel
+    int bf16_waves = 0;  // PN_OPT_BF16_WAVES: 0 = the library picks, 4 / 8 = that main-pass kernel, 16 = the paired kernel (where they apply)
+    int wg_slots = 0;    // bf16 filter: the device's workgroup slots of the 4-wave kernel (2 per CU); 0 = unknown, and the
+                         // automatic choice then never takes the paired kernel
 };
 
 inline size_t round_up(size_t a, size_t b) { return (a + b - 1) / b * b; }

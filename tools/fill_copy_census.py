@@ -6,7 +6,7 @@ usage: fill_copy_census.py <rocprofv3 *_kernel_trace.csv>   -> counts before the
 import csv, json, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-main = [i for i, r in enumerate(rows) if ("bf16_filter_kernel<" in r["Kernel_Name"] and ", 2, " in r["Kernel_Name"]) or "bf16_filter8_kernel" in r["Kernel_Name"]]
+main = [i for i, r in enumerate(rows) if ("bf16_filter_kernel<" in r["Kernel_Name"] and ", 2, " in r["Kernel_Name"]) or "bf16_filter8_kernel" in r["Kernel_Name"] or "bf16_filter_kernel_pair" in r["Kernel_Name"]]
 first, last = main[0], main[-1]
 def census(lo, hi):
     c = {}

@@ -11,7 +11,8 @@ find $O/stats -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/kernel_s
 find $O/stats -name "*kernel_trace.csv" | head -1 | xargs -I{} python3 $R/tools/fill_copy_census.py {} > $O/fill_copy_census.json
 cat $O/fill_copy_census.json
 i=0
-for set in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVES SQ_BUSY_CYCLES"; do
+# PN_PMC_EXTRA: one more counter set in a pass of its own (e.g. "SQ_WAIT_ANY SQ_VALU_MFMA_COEXEC_CYCLES SQ_WAVE_CYCLES")
+for set in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVES SQ_BUSY_CYCLES" ${PN_PMC_EXTRA:+"$PN_PMC_EXTRA"}; do
   i=$((i+1))
   rocprofv3 --kernel-trace --pmc $set --output-format csv -d $O/pmc/p$i -o p -- python3 $R/bench.py --no-verify --no-cpu-baseline --steps 3 --warmup 1 $BA > $O/pmc_p$i.log 2>&1 || { echo pmc pass $i failed; tail -3 $O/pmc_p$i.log; exit 1; }
 done
