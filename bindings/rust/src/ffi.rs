@@ -274,6 +274,34 @@ extern "C" {
                                     labels: *mut i64) -> c_int;
     pub fn pn_mean_shift_labels_device_f64(index: *const pn_index, d_centres: *const f64, nc: usize, h: f64, flags: c_uint,
                                            d_labels: *mut i64, stream: *mut c_void) -> c_int;
+    /// k-means (include/petal_mi355x.h): dist / counts / inertia / iterations / shift2 outputs nullable
+    pub fn pn_kmeans_assign_f32(index: *const pn_index, centres: *const f32, nc: usize, flags: c_uint,
+                                labels_out: *mut i64, dist_out: *mut f32, inertia_out: *mut f64) -> c_int;
+    pub fn pn_kmeans_assign_device_f32(index: *const pn_index, d_centres: *const f32, nc: usize, flags: c_uint,
+                                       d_labels: *mut i64, d_dist: *mut f32, d_inertia: *mut f64,
+                                       stream: *mut c_void) -> c_int;
+    pub fn pn_kmeans_f32(index: *const pn_index, init_centres: *const f32, nc: usize, tol: f64, max_iter: usize,
+                         flags: c_uint, centres_out: *mut f32, labels_out: *mut i64, dist_out: *mut f32,
+                         counts_out: *mut u64, inertia_out: *mut f64, iterations_out: *mut u64,
+                         shift2_out: *mut f64) -> c_int;
+    pub fn pn_kmeans_device_f32(index: *const pn_index, d_init_centres: *const f32, nc: usize, tol: f64, max_iter: usize,
+                                flags: c_uint, d_centres: *mut f32, d_labels: *mut i64, d_dist: *mut f32,
+                                d_counts: *mut u64, d_inertia: *mut f64, d_iterations: *mut u64, d_shift2: *mut f64,
+                                stream: *mut c_void) -> c_int;
+    pub fn pn_kmeans_assign_f64(index: *const pn_index, centres: *const f64, nc: usize, flags: c_uint,
+                                labels_out: *mut i64, dist_out: *mut f64, inertia_out: *mut f64) -> c_int;
+    pub fn pn_kmeans_assign_device_f64(index: *const pn_index, d_centres: *const f64, nc: usize, flags: c_uint,
+                                       d_labels: *mut i64, d_dist: *mut f64, d_inertia: *mut f64,
+                                       stream: *mut c_void) -> c_int;
+    pub fn pn_kmeans_f64(index: *const pn_index, init_centres: *const f64, nc: usize, tol: f64, max_iter: usize,
+                         flags: c_uint, centres_out: *mut f64, labels_out: *mut i64, dist_out: *mut f64,
+                         counts_out: *mut u64, inertia_out: *mut f64, iterations_out: *mut u64,
+                         shift2_out: *mut f64) -> c_int;
+    pub fn pn_kmeans_device_f64(index: *const pn_index, d_init_centres: *const f64, nc: usize, tol: f64, max_iter: usize,
+                                flags: c_uint, d_centres: *mut f64, d_labels: *mut i64, d_dist: *mut f64,
+                                d_counts: *mut u64, d_inertia: *mut f64, d_iterations: *mut u64, d_shift2: *mut f64,
+                                stream: *mut c_void) -> c_int;
+    pub fn pn_kmeans_bounds_f32(index: *const pn_index, centres: *const f32, nc: usize, bounds_out: *mut f64) -> c_int;
     /// dist_out nullable (PN_RADIUS_SORTED needs it); *idx_out / *dist_out released with pn_free
     pub fn pn_query_radius_self_f32(index: *const pn_index, radius: f32, flags: c_uint, offsets: *mut u64,
                                     idx_out: *mut *mut u64, dist_out: *mut *mut f32) -> c_int;

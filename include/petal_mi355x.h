@@ -64,7 +64,9 @@ extern "C" {
  * pn_linkage_{,device_}{f32,f64}, pn_hdbscan_{,device_}{f32,f64}; pn_lof_{,device_}{f32,f64},
  * pn_lof_score_{,device_}{f32,f64}; pn_optics_{,device_}{f32,f64}, pn_optics_dbscan_{,device_}{f32,f64},
  * PN_OPT_OPTICS_PIECE; pn_kde_{,device_,self_,self_device_}{f32,f64}, PN_KDE_*, PN_OPT_KDE_PIECE;
- * pn_mean_shift_{,device_,merge_,merge_device_,labels_,labels_device_}{f32,f64}, PN_MS_*, PN_OPT_MS_PIECE. */
+ * pn_mean_shift_{,device_,merge_,merge_device_,labels_,labels_device_}{f32,f64}, PN_MS_*, PN_OPT_MS_PIECE;
+ * pn_kmeans_{,device_}{f32,f64}, pn_kmeans_assign_{,device_}{f32,f64}, pn_kmeans_bounds_f32,
+ * PN_OPT_KMEANS_FILTER. */
 #define PN_ABI_VERSION 3
 
 /* ---- error codes.  EMPTY / NOT_CONTIGUOUS are ArrayError (src/lib.rs:9-16). */
@@ -137,9 +139,12 @@ enum {
     PN_OPT_KDE_PIECE = 14,       /* pn_kde_*: the most list entries (a 64-bit index and a distance each, in workspace
                                   scratch) one piece of the sum stage holds; 0 (default) = 2^27; negative: PN_ERR_INVALID.
                                   A query whose own list is longer is a piece of its own.  Never changes a result. */
-    PN_OPT_MS_PIECE = 15         /* pn_mean_shift_*: the most list entries (a 64-bit index each, in workspace scratch) one
+    PN_OPT_MS_PIECE = 15,        /* pn_mean_shift_*: the most list entries (a 64-bit index each, in workspace scratch) one
                                   piece of an iteration's step stage holds; 0 (default) = 2^27; negative: PN_ERR_INVALID.
                                   A seed whose own list is longer is a piece of its own.  Never changes a result. */
+    PN_OPT_KMEANS_FILTER = 16    /* pn_kmeans_*: 0 (default) = PN_OPT_ENGINE decides; 1 = the MFMA filter wherever it is
+                                  eligible (8 <= dim <= 320), on any handle; 2 = never.  Other values: PN_ERR_INVALID.
+                                  Never changes a result (it lets tests force the filter at small n). */
 };
 
 /* kernels of pn_kde_* (scikit-learn's names; its sixth, `cosine`, is left out: the name collides with the Cosine metric
@@ -835,6 +840,80 @@ int pn_mean_shift_labels_f64(const pn_index *index, const double *centres, size_
                              int64_t *labels);
 int pn_mean_shift_labels_device_f64(const pn_index *index, const double *d_centres, size_t nc, double h, unsigned flags,
                                     int64_t *d_labels, void *stream);
+
+/* ---- k-means (extension; Euclidean indexes only; T = the index's element type).  DESIGN.md 4.22.
+ *   Assignment of the indexed rows to centres [nc][dim] (dense, T): labels[i] = exactly what
+ *     pn_mean_shift_labels_*(centres, nc, h, flags = 0) writes: the nearest centre by (distance key, centre number), the
+ *     distance being the bits of pn_euclidean_* and a NaN distance the canonical NaN key above +inf; nc == 0 gives all -1.
+ *     dist[i] = that distance, NaN where the label is -1.
+ *   SUM4096, the one sum shape of these entry points; it depends on the length of the sequence alone.  Cut the sequence
+ *     into consecutive segments of 4096 terms.  A segment's sum is the 64-lane shape of pn_kde_* / pn_mean_shift_*:
+ *     P_l = (((0.0 + t_l) + t_(l+64)) + ...) for l = 0 .. 63 (a lane without a term: 0.0), S = ((P_0 + P_1) + ... + P_63).
+ *     The total is ((S_0 + S_1) + S_2) ... in segment order; an empty sequence sums to 0.0.  IEEE f64, unfused, no
+ *     floating-point atomics: the result does not depend on the launch.
+ *   Inertia = SUM4096 over i = 0 .. n - 1 of (double)dist[i] * (double)dist[i], the term of a row with label -1 being 0.0.
+ *   pn_kmeans_*: Lloyd iterations from the caller's initial centres [nc][dim].  Iteration t = 1, 2, ...: assign to the
+ *     current centres; for every cluster c let m_c be the number of its members, taken in ascending row index.  m_c = 0:
+ *     the centre is unchanged (scikit-learn relocates it; a stated deviation, visible in counts_out).  Otherwise, per
+ *     column, S = SUM4096(members' (double)x[i][col]) and the new centre is (T)(S / (double)m_c).  t_c = the sum over the
+ *     columns of ((double)new - (double)old)^2 in the 64-partial shape (column col to partial col mod 64, ascending
+ *     within a partial from 0.0; then ((p_0 + p_1) + ... + p_63)), exactly as mean shift's shift;
+ *     shift2 = (((0.0 + t_0) + t_1) + ...) in centre order.  Stop when shift2 <= tol (a double >= 0, absolute) or
+ *     t == max_iter.  After the stop there is one more assignment to the final centres: labels, distances, counts and
+ *     inertia belong to the centres returned.  iterations = the t of the stop, shift2 = the last one.
+ *   Outputs: centres_out [nc][dim], labels_out [n], dist_out [n] (nullable), counts_out [nc] (nullable: the members of the
+ *   final assignment), inertia_out, iterations_out, shift2_out (one value each, nullable).  flags must be 0.
+ *   PN_OPT_INDEX_BASE affects no output.  pn_stats.queries advances by n per assignment.
+ * Engines (PN_OPT_ENGINE; results never depend on them).  The filter of DESIGN.md 4.22 -- a bf16 MFMA lower bound of every
+ * (row, centre) distance, one candidate per row evaluated exactly, a proof per row -- takes 8 <= dim <= 320, f32 and f64
+ * indexes alike; rows it cannot prove (ties, rows within the filter's slack of a bisector, anything not finite or with a
+ * squared norm of 2^100 or more) are listed on the device and answered by the exact kernel, and their number is added to
+ * pn_stats.fallback_queries.  PN_ENGINE_EXACT: the exact kernel alone.  PN_ENGINE_BF16: the filter wherever it is
+ * eligible (pn_index_set_option accepts that engine, as ever, only on a handle whose k-NN bf16 tier exists;
+ * PN_OPT_KMEANS_FILTER = 1 forces the k-means filter on any handle).  PN_ENGINE_AUTO (and PN_ENGINE_MFMA): the filter
+ * where it is eligible, nc >= 64, dim >= 64 and n * nc * dim >= 8e9 (16e9 where dim < 128); below that the exact kernel, whose whole work is as
+ * small as the filter's fixed cost (and on narrow rows no dearer per centre than the filter).  One centre (nc = 1) is
+ * always the exact kernel's: there is nothing to filter.
+ * Argument errors, before any device is touched and in this order: unknown flags; (pn_kmeans_*) tol NaN or negative;
+ * max_iter == 0; NULL required outputs (labels; pn_kmeans_*: centres_out); NULL inputs (centres with nc > 0; pn_kmeans_*:
+ * the initial centres); (pn_kmeans_*) nc == 0; NULL index; wrong element type: PN_ERR_INVALID; a Cosine index:
+ * PN_ERR_UNSUPPORTED; more than 2^31 - 1 rows or centres: PN_ERR_UNSUPPORTED.  n == 0 succeeds: inertia 0, counts 0, the
+ * centres copied, iterations 0, shift2 0.
+ * Device entry points: everything in HBM, written in stream order on `stream`.  pn_kmeans_assign_device_* never waits.
+ * pn_kmeans_device_* BLOCKS THE HOST ONCE PER ITERATION, to read the stop word (16 bytes) -- it is not capturable into a
+ * graph.  Device memory of a call (workspace of the handle): the exact path needs none per row but sizeof T bytes when
+ * the inertia is asked for without the distances (and 8 bytes per 4096 rows for the inertia); the filter adds
+ * 4 * dp + 32 bytes per row (dp = dim rounded up to 16: the two bf16 row images, packed once per call, their norms, the
+ * candidate, its threshold and the list of unproven rows) and 4 * dp + 4 bytes per centre rounded up to 32;
+ * pn_kmeans_*: 16 N bytes (N = n rounded up to a power of two, at least 1024: the sort of the members' lists),
+ * 8 * dim * (n / 4096 + nc) bytes of segment sums and 36 bytes per centre.
+ * Not in this version: Cosine / spherical k-means, row-sharded handles, mini-batch, empty-cluster relocation, a
+ * device-driven iteration loop. */
+int pn_kmeans_assign_f32(const pn_index *index, const float *centres, size_t nc, unsigned flags, int64_t *labels_out,
+                         float *dist_out, double *inertia_out);
+int pn_kmeans_assign_device_f32(const pn_index *index, const float *d_centres, size_t nc, unsigned flags,
+                                int64_t *d_labels, float *d_dist, double *d_inertia, void *stream);
+int pn_kmeans_f32(const pn_index *index, const float *init_centres, size_t nc, double tol, size_t max_iter, unsigned flags,
+                  float *centres_out, int64_t *labels_out, float *dist_out, uint64_t *counts_out, double *inertia_out,
+                  uint64_t *iterations_out, double *shift2_out);
+int pn_kmeans_device_f32(const pn_index *index, const float *d_init_centres, size_t nc, double tol, size_t max_iter,
+                         unsigned flags, float *d_centres, int64_t *d_labels, float *d_dist, uint64_t *d_counts,
+                         double *d_inertia, uint64_t *d_iterations, double *d_shift2, void *stream);
+int pn_kmeans_assign_f64(const pn_index *index, const double *centres, size_t nc, unsigned flags, int64_t *labels_out,
+                         double *dist_out, double *inertia_out);
+int pn_kmeans_assign_device_f64(const pn_index *index, const double *d_centres, size_t nc, unsigned flags,
+                                int64_t *d_labels, double *d_dist, double *d_inertia, void *stream);
+int pn_kmeans_f64(const pn_index *index, const double *init_centres, size_t nc, double tol, size_t max_iter, unsigned flags,
+                  double *centres_out, int64_t *labels_out, double *dist_out, uint64_t *counts_out, double *inertia_out,
+                  uint64_t *iterations_out, double *shift2_out);
+int pn_kmeans_device_f64(const pn_index *index, const double *d_init_centres, size_t nc, double tol, size_t max_iter,
+                         unsigned flags, double *d_centres, int64_t *d_labels, double *d_dist, uint64_t *d_counts,
+                         double *d_inertia, uint64_t *d_iterations, double *d_shift2, void *stream);
+/* diagnostic: the k-means filter's lower bounds themselves.  bounds_out[i * nc + c] = L(x_i, c) <= |x_i - c|^2 in real
+ * arithmetic for every indexed row i and centre c (kmeans.hip states the bound), NaN where the row or a centre is flagged
+ * (not finite, a squared norm of 2^100 or more).  Host pointers; 8 <= dim <= 320, else PN_ERR_UNSUPPORTED.  Tests check
+ * the inequality pair by pair. */
+int pn_kmeans_bounds_f32(const pn_index *index, const float *centres, size_t nc, double *bounds_out);
 
 /* ---- distance::pairwise(x, &Euclidean) (src/distance.rs:58-74): n x n
  * symmetric matrix, zero diagonal, n < 2 -> zeros. Host in, host out. */

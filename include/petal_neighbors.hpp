@@ -141,6 +141,18 @@ struct MeanShift {
     size_t n_centres = 0;
     std::vector<int64_t> labels;
 };
+// the answer of BallTree::kmeans / kmeans_assign: centres [k][dim] dense, per indexed row the nearest centre (by distance,
+// then centre number) and the distance to it, per centre its members in the final assignment (0: the centre lost them all
+// and kept its place), the inertia in the library's fixed sum shape, the iterations run and the last summed squared move
+template <typename A>
+struct KMeans {
+    std::vector<A> centres;
+    std::vector<int64_t> labels;
+    std::vector<A> dist;
+    std::vector<size_t> counts;
+    double inertia = 0.0, shift2 = 0.0;
+    size_t n_iter = 0;
+};
 // the answer of BallTree::optics: ordering[t] = the t-th row OPTICS visits (a plain row number); reachability, predecessor
 // (-1 = none) and core_distances are indexed by row, +inf where undefined
 template <typename A>
@@ -550,6 +562,43 @@ class BallTree {
         MeanShift<A> res = mean_shift_modes(h, seeds, ns, tol, max_iter);
         mean_shift_merge(res, h);
         mean_shift_labels(res, h, cluster_all);
+        return res;
+    }
+    // extension: k-means on the device (pn_kmeans_*).  kmeans_assign: the nearest of k centres [k][dim] for every indexed
+    // row, the labels of mean_shift_labels, with distances and inertia
+    KMeans<A> kmeans_assign(const A *centres, size_t k) const {
+        KMeans<A> res;
+        res.centres.assign(centres, centres + k * dim_);
+        res.labels.resize(n_ + 1);
+        res.dist.resize(n_ + 1);
+        if constexpr (kF32)
+            check(pn_kmeans_assign_f32(h_, centres, k, 0u, res.labels.data(), res.dist.data(), &res.inertia));
+        else
+            check(pn_kmeans_assign_f64(h_, centres, k, 0u, res.labels.data(), res.dist.data(), &res.inertia));
+        res.labels.resize(n_);
+        res.dist.resize(n_);
+        return res;
+    }
+    // ... Lloyd iterations from the initial centres [k][dim] until the summed squared moves are <= tol (absolute) or
+    // max_iter; a cluster without members keeps its centre
+    KMeans<A> kmeans(const A *init, size_t k, double tol, size_t max_iter = 300) const {
+        KMeans<A> res;
+        res.centres.resize(k * dim_ + 1);
+        res.labels.resize(n_ + 1);
+        res.dist.resize(n_ + 1);
+        std::vector<uint64_t> counts(k + 1);
+        uint64_t iters = 0;
+        if constexpr (kF32)
+            check(pn_kmeans_f32(h_, init, k, tol, max_iter, 0u, res.centres.data(), res.labels.data(), res.dist.data(),
+                                counts.data(), &res.inertia, &iters, &res.shift2));
+        else
+            check(pn_kmeans_f64(h_, init, k, tol, max_iter, 0u, res.centres.data(), res.labels.data(), res.dist.data(),
+                                counts.data(), &res.inertia, &iters, &res.shift2));
+        res.centres.resize(k * dim_);
+        res.labels.resize(n_);
+        res.dist.resize(n_);
+        res.counts.assign(counts.begin(), counts.begin() + k);
+        res.n_iter = (size_t)iters;
         return res;
     }
     // extension: OPTICS on the device (pn_optics_*): scikit-learn's OPTICS(min_samples + 1, max_eps) on this library's

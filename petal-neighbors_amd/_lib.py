@@ -27,6 +27,7 @@ PN_OPT_MST_BATCH = 12
 PN_OPT_OPTICS_PIECE = 13
 PN_OPT_KDE_PIECE = 14
 PN_OPT_MS_PIECE = 15
+PN_OPT_KMEANS_FILTER = 16
 PN_KDE_GAUSSIAN, PN_KDE_TOPHAT, PN_KDE_EPANECHNIKOV, PN_KDE_EXPONENTIAL, PN_KDE_LINEAR = 0, 1, 2, 3, 4
 PN_RADIUS_SORTED = 1
 PN_SELF_INCLUDE = 2
@@ -155,6 +156,15 @@ SIGNATURES = {
     "pn_mean_shift_merge_device_f64": (_i, [_vp, _vp, _sz, _vp, C.c_double, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
     "pn_mean_shift_labels_f64": (_i, [_vp, _vp, _sz, C.c_double, C.c_uint, _vp]),
     "pn_mean_shift_labels_device_f64": (_i, [_vp, _vp, _sz, C.c_double, C.c_uint, _vp, _vp]),
+    "pn_kmeans_assign_f32": (_i, [_vp, _vp, _sz, C.c_uint, _vp, _vp, _vp]),
+    "pn_kmeans_assign_device_f32": (_i, [_vp, _vp, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
+    "pn_kmeans_f32": (_i, [_vp, _vp, _sz, C.c_double, _sz, C.c_uint, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pn_kmeans_device_f32": (_i, [_vp, _vp, _sz, C.c_double, _sz, C.c_uint, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pn_kmeans_assign_f64": (_i, [_vp, _vp, _sz, C.c_uint, _vp, _vp, _vp]),
+    "pn_kmeans_assign_device_f64": (_i, [_vp, _vp, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
+    "pn_kmeans_f64": (_i, [_vp, _vp, _sz, C.c_double, _sz, C.c_uint, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pn_kmeans_device_f64": (_i, [_vp, _vp, _sz, C.c_double, _sz, C.c_uint, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pn_kmeans_bounds_f32": (_i, [_vp, _vp, _sz, _vp]),
     "pn_optics_f32": (_i, [_vp, _sz, C.c_float, C.c_uint, _vp, _vp, _vp, _vp]),
     "pn_optics_f64": (_i, [_vp, _sz, C.c_double, C.c_uint, _vp, _vp, _vp, _vp]),
     "pn_optics_device_f32": (_i, [_vp, _sz, C.c_float, C.c_uint, _vp, _vp, _vp, _vp, _vp]),

@@ -1163,6 +1163,177 @@ class BallTree:
         a = self._queries(queries, False)
         return np.array([int(self.query_radius_count(a, x).sum()) for x in ra.tolist()], dtype=np.int64)
 
+    # -------------------------------------------------- k-means
+    # Lloyd's k-means on the device (``pn_kmeans_*``): the rows are assigned to their nearest centres behind a bf16 MFMA
+    # filter with an exact re-rank and a proof per row, the centres become means summed in a fixed order.  Labels are those
+    # of ``mean_shift_labels``; every sum has one stated shape, so a result does not depend on the engine or the launch.
+    def _km_check(self):
+        from .distance import Cosine
+        if isinstance(self.metric, Cosine):
+            raise ValueError("k-means needs a Euclidean tree")
+
+    def _km_centres(self, centres):
+        c = self._queries(centres, False)
+        if c.shape[0] and c.shape[1] != self._dim:
+            raise ValueError(f"centres must have the tree's {self._dim} columns")
+        return c
+
+    def _km_centres_device(self, centres):
+        import torch
+        tdt = torch.float32 if self._sfx == "f32" else torch.float64
+        if (not isinstance(centres, torch.Tensor) or centres.dim() != 2 or not self._lof_on_device(centres, tdt, 0)
+                or (centres.shape[0] and centres.shape[1] != self._dim)):
+            raise ValueError(f"centres must be a contiguous [nc][{self._dim}] {tdt} CUDA tensor on the tree's device")
+        return tdt, torch.device("cuda", self.device)
+
+    def kmeans_assign(self, centres):
+        """The nearest centre of every indexed row by (distance, centre number), as ``mean_shift_labels`` gives it:
+        ``(labels int64 [n], dist [n], inertia)`` with ``dist`` the distance to that centre and ``inertia`` the sum of
+        the squared distances in the library's fixed shape (a float)."""
+        self._km_check()
+        c = self._km_centres(centres)
+        labels = np.empty(self._n, dtype=np.int64)
+        dist = np.empty(self._n, dtype=self.dtype)
+        inertia = C.c_double(0.0)
+        check(getattr(_lib.lib(), f"pn_kmeans_assign_{self._sfx}")(
+            self._h, c.ctypes.data if c.shape[0] else None, c.shape[0], 0, labels.ctypes.data, dist.ctypes.data,
+            C.byref(inertia)))
+        return labels, dist, float(inertia.value)
+
+    def kmeans_assign_device(self, centres, out_labels=None, out_dist=None, out_inertia=None, stream=None):
+        """``kmeans_assign`` in HBM: ``centres`` a contiguous 2-D CUDA tensor; returns CUDA tensors ``(labels int64 [n],
+        dist [n], inertia float64 [1])``.  Never waits."""
+        import torch
+        self._km_check()
+        tdt, dev = self._km_centres_device(centres)
+        nc = centres.shape[0]
+        for t, want, name in ((out_labels, torch.int64, "out_labels"), (out_dist, tdt, "out_dist")):
+            if t is not None and not self._lof_on_device(t, want, self._n):
+                raise ValueError(f"{name} must be a contiguous {want} CUDA tensor of at least {self._n} values")
+        if out_inertia is not None and not self._lof_on_device(out_inertia, torch.float64, 1):
+            raise ValueError("out_inertia must be a float64 CUDA tensor of one value")
+        labels = out_labels if out_labels is not None else torch.empty(self._n, dtype=torch.int64, device=dev)
+        dist = out_dist if out_dist is not None else torch.empty(self._n, dtype=tdt, device=dev)
+        inertia = out_inertia if out_inertia is not None else torch.zeros(1, dtype=torch.float64, device=dev)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        check(getattr(_lib.lib(), f"pn_kmeans_assign_device_{self._sfx}")(
+            self._h, centres.data_ptr() if nc else None, nc, 0, labels.data_ptr(), dist.data_ptr(), inertia.data_ptr(),
+            C.c_void_p(st)))
+        return labels, dist, inertia
+
+    def _km_tol(self, tol, abs_tol, max_iter):
+        if int(max_iter) < 1:
+            raise ValueError("max_iter must be at least 1")
+        if abs_tol is None:
+            if not (float(tol) >= 0.0):
+                raise ValueError("tol must be >= 0")
+            if self.points is None:
+                raise ValueError("a tree built from a device tensor needs abs_tol (the rows are not on the host)")
+            # scikit-learn's _tolerance: tol times the mean of the columns' variances
+            abs_tol = float(tol) * float(np.mean(np.var(np.asarray(self.points, dtype=np.float64), axis=0)))
+        abs_tol = float(abs_tol)
+        if not (abs_tol >= 0.0):
+            raise ValueError("tol must be >= 0")
+        return abs_tol, int(max_iter)
+
+    def kmeans_plusplus(self, k: int, seed=None):
+        """k-means++ seeding (D^2 sampling): ``k`` rows of the corpus as ``[k][dim]`` host array.  Every round is one
+        ``kmeans_assign_device`` call with the one centre just drawn; the running minimum and the draw are torch's.  NOT
+        bit-contractual: the draws are those of torch's generator (reproducible for one seed in one process and
+        version), the distances are the library's.  An assignment to one centre is always the exact kernel's, whatever
+        engine the tree is set to: a round packs nothing."""
+        import torch
+        self._km_check()
+        k = int(k)
+        if k < 1 or k > self._n:
+            raise ValueError("k must be between 1 and the number of rows")
+        if self.points is None:
+            raise ValueError("kmeans_plusplus needs the rows on the host")
+        tdt = torch.float32 if self._sfx == "f32" else torch.float64
+        dev = torch.device("cuda", self.device)
+        g = torch.Generator(device="cpu")
+        if seed is None:
+            g.seed()
+        else:
+            g.manual_seed(int(seed))
+        rows = np.ascontiguousarray(self.points)
+        chosen = [int(torch.randint(self._n, (1,), generator=g).item())]
+        mind2 = None
+        for _ in range(1, k):
+            c = torch.from_numpy(rows[chosen[-1]:chosen[-1] + 1].copy()).to(dev)
+            _, dist, _ = self.kmeans_assign_device(c)
+            d2 = dist.to(torch.float64) ** 2
+            mind2 = d2 if mind2 is None else torch.minimum(mind2, d2)
+            cs = torch.cumsum(torch.nan_to_num(mind2, nan=0.0, posinf=0.0), 0)
+            total = float(cs[-1].item())
+            if not total > 0.0:
+                raise ValueError("fewer distinct rows than centres")
+            u = float(torch.rand(1, generator=g, dtype=torch.float64).item()) * total
+            i = int(torch.searchsorted(cs, torch.tensor([u], dtype=torch.float64, device=dev), right=True).item())
+            chosen.append(min(i, self._n - 1))
+        return rows[np.asarray(chosen)].copy()
+
+    def kmeans(self, centres_or_k, tol: float = 1e-4, max_iter: int = 300, seed=None, abs_tol=None, full: bool = False):
+        """Lloyd's k-means from the given initial centres ``[k][dim]``, or from ``kmeans_plusplus(k, seed)`` when an integer
+        is given: ``(centres [k][dim], labels int64 [n], inertia)``; with ``full=True`` also ``dist [n]``, ``counts uint64
+        [k]``, ``iterations`` and ``shift2``.  ``tol`` is scikit-learn's: relative to the mean variance of the columns
+        (computed on the host); ``abs_tol`` gives the absolute bound on the summed squared moves itself.  A cluster that
+        loses every member keeps its centre (scikit-learn relocates it): look at ``counts``.  ``last_n_iter`` holds the
+        iterations run."""
+        self._km_check()
+        abs_tol, max_iter = self._km_tol(tol, abs_tol, max_iter)
+        if np.ndim(centres_or_k) == 0:
+            init = self.kmeans_plusplus(int(centres_or_k), seed)
+        else:
+            init = self._km_centres(centres_or_k)
+        k = init.shape[0]
+        if k < 1:
+            raise ValueError("k-means needs at least one centre")
+        init = np.ascontiguousarray(init, dtype=self.dtype)
+        centres = np.zeros((k, self._dim), dtype=self.dtype)
+        labels = np.empty(self._n, dtype=np.int64)
+        dist = np.empty(self._n, dtype=self.dtype)
+        counts = np.zeros(k, dtype=np.uint64)
+        inertia, shift2, iters = C.c_double(0.0), C.c_double(0.0), C.c_uint64(0)
+        check(getattr(_lib.lib(), f"pn_kmeans_{self._sfx}")(
+            self._h, init.ctypes.data, k, abs_tol, max_iter, 0, centres.ctypes.data, labels.ctypes.data, dist.ctypes.data,
+            counts.ctypes.data, C.byref(inertia), C.byref(iters), C.byref(shift2)))
+        self.last_n_iter = int(iters.value)
+        if full:
+            return centres, labels, float(inertia.value), dist, counts, int(iters.value), float(shift2.value)
+        return centres, labels, float(inertia.value)
+
+    def kmeans_device(self, centres, abs_tol, max_iter: int = 300, stream=None):
+        """``kmeans`` in HBM from initial centres given as a contiguous 2-D CUDA tensor, with the absolute tolerance:
+        CUDA tensors ``(centres, labels int64 [n], dist [n], counts int64 [k], inertia float64 [1], iterations int64 [1],
+        shift2 float64 [1])``.  The call waits for the device once per iteration and cannot be captured into a graph."""
+        import torch
+        self._km_check()
+        tdt, dev = self._km_centres_device(centres)
+        abs_tol, max_iter = self._km_tol(0.0, abs_tol, max_iter)
+        k = centres.shape[0]
+        if k < 1:
+            raise ValueError("k-means needs at least one centre")
+        out_c = torch.empty((k, self._dim), dtype=tdt, device=dev)
+        labels = torch.empty(self._n, dtype=torch.int64, device=dev)
+        dist = torch.empty(self._n, dtype=tdt, device=dev)
+        counts = torch.zeros(k, dtype=torch.int64, device=dev)
+        inertia = torch.zeros(1, dtype=torch.float64, device=dev)
+        iters = torch.zeros(1, dtype=torch.int64, device=dev)
+        shift2 = torch.zeros(1, dtype=torch.float64, device=dev)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        check(getattr(_lib.lib(), f"pn_kmeans_device_{self._sfx}")(
+            self._h, centres.data_ptr(), k, abs_tol, max_iter, 0, out_c.data_ptr(), labels.data_ptr(), dist.data_ptr(),
+            counts.data_ptr(), inertia.data_ptr(), iters.data_ptr(), shift2.data_ptr(), C.c_void_p(st)))
+        return out_c, labels, dist, counts, inertia, iters, shift2
+
+    def kmeans_bounds(self, centres):
+        """Diagnostic: the k-means filter's lower bounds ``L[i][c] <= |x_i - c|^2`` (float64 ``[n][nc]``), f32 trees."""
+        c = self._km_centres(centres)
+        out = np.zeros((self._n, c.shape[0]), dtype=np.float64)
+        check(_lib.lib().pn_kmeans_bounds_f32(self._h, c.ctypes.data if c.shape[0] else None, c.shape[0], out.ctypes.data))
+        return out
+
     # -------------------------------------------------- mean shift
     # scikit-learn's ``MeanShift`` (flat kernel) on the device (``pn_mean_shift_*``): seeds climb to the modes of the tophat
     # density, every step the mean of a radius list summed by one wave in a fixed order; only the seeds still moving are

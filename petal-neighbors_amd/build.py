@@ -48,6 +48,7 @@ UNITS = [
     ("lof.hip", ["-ffp-contract=off"]),
     ("kde.hip", ["-ffp-contract=off"]),
     ("mean_shift.hip", ["-ffp-contract=off"]),
+    ("kmeans.hip", ["-ffp-contract=off"]),
     ("optics.hip", ["-ffp-contract=off"]),
     ("radii_tau.hip", ["-ffp-contract=off"]),
     ("metric.cpp", ["-ffp-contract=off"]),

@@ -167,6 +167,9 @@ struct Workspace {
     // pn_mean_shift_*: the O(active seeds) arrays of a call (offsets, two copies of positions, bandwidths and slots, the
     // stop flags) or the merge's scratch, and the host entries' inputs and outputs
     DevBuf w_ms, w_ms_io;
+    // pn_kmeans_*: the packed rows (once per call), the packed centres, the O(n) arrays of an assignment (candidates,
+    // thresholds, the list of unproven rows, distances, inertia segments), the update's scratch, the host entries' staging
+    DevBuf w_km_rows, w_km_cent, w_km, w_km_upd, w_km_io;
     // small calls (tiny_*): mapped pinned host memory the one kernel of the call reads its queries from and writes its
     // answers to -- no copy commands
     void *pin_in = nullptr, *pin_out = nullptr;
@@ -192,7 +195,7 @@ struct Workspace {
     hipEvent_t done = nullptr;
     hipStream_t last_stream = nullptr;
     bool in_flight = false;
-    DevBuf *all[68] = {&w_ms, &w_ms_io, &w_kde, &w_kde_io, &w_opt, &w_opt_graph, &w_opt_io, &w_lof, &w_lof_io, &w_hdb, &w_hdb_io, &w_mst, &w_mst_io, &w_db, &w_db_side, &w_db_out, &w_hrad, &w_sf_idx, &w_sf_dist, &w_sf_off, &w_sf_coff, &w_sf_flag, &w_sf_cnt, &w_sf_scan, &w_sf_hoff, &w_cs_hoff, &w_rkd, &w_cs_nch, &w_cs_off, &w_cs_scan, &w_cs_idx, &w_cs_dist, &w_gqn, &w_rpos, &w_rfin, &w_rcx, &w_rox, &w_rscan, &w_q, &w_qnorm, &w_qnrm, &w_keys, &w_idx, &w_cnt, &w_tau, &w_flags, &w_sel, &w_misc, &w2_keys, &w2_idx,
+    DevBuf *all[73] = {&w_km_rows, &w_km_cent, &w_km, &w_km_upd, &w_km_io, &w_ms, &w_ms_io, &w_kde, &w_kde_io, &w_opt, &w_opt_graph, &w_opt_io, &w_lof, &w_lof_io, &w_hdb, &w_hdb_io, &w_mst, &w_mst_io, &w_db, &w_db_side, &w_db_out, &w_hrad, &w_sf_idx, &w_sf_dist, &w_sf_off, &w_sf_coff, &w_sf_flag, &w_sf_cnt, &w_sf_scan, &w_sf_hoff, &w_cs_hoff, &w_rkd, &w_cs_nch, &w_cs_off, &w_cs_scan, &w_cs_idx, &w_cs_dist, &w_gqn, &w_rpos, &w_rfin, &w_rcx, &w_rox, &w_rscan, &w_q, &w_qnorm, &w_qnrm, &w_keys, &w_idx, &w_cnt, &w_tau, &w_flags, &w_sel, &w_misc, &w2_keys, &w2_idx,
                        &w2_cnt, &w2_tau, &w_lo, &w_bq, &w_qn, &w_qbad, &w_gq, &w_gidx, &w_gdist, &w_gsel, &w_seed,
                        &w_qstat, &w_lists, &w_hq, &w_hidx, &w_hdist, &w_fparts, &w_pcnt};
     std::vector<void *> retired;  // outgrown allocations, freed once `done` has passed (DevBuf::ensure)
@@ -264,6 +267,7 @@ struct pn_index {
     uint64_t optics_piece = 0;  // PN_OPT_OPTICS_PIECE: list entries per fill piece of pn_optics_*, 0 = 2^27
     uint64_t kde_piece = 0;     // PN_OPT_KDE_PIECE: list entries per piece of pn_kde_*, 0 = 2^27
     uint64_t ms_piece = 0;      // PN_OPT_MS_PIECE: list entries per piece of pn_mean_shift_*, 0 = 2^27
+    int kmeans_filter = 0;      // PN_OPT_KMEANS_FILTER: 0 = the engine decides, 1 = the filter wherever it is eligible, 2 = never
     // state that queries on a shared `const pn_index *` update: internally synchronised by `mu`
     struct Shared {
         std::mutex mu;
@@ -1025,6 +1029,10 @@ extern "C" int pn_index_set_option(pn_index *ix, int option, int64_t value) {
         case PN_OPT_MS_PIECE:
             if (value < 0) return fail(PN_ERR_INVALID, "bad mean shift piece size");
             ix->ms_piece = (uint64_t)value;
+            return PN_OK;
+        case PN_OPT_KMEANS_FILTER:
+            if (value < 0 || value > 2) return fail(PN_ERR_INVALID, "bad k-means filter choice %lld", (long long)value);
+            ix->kmeans_filter = (int)value;
             return PN_OK;
         default: return fail(PN_ERR_INVALID, "unknown option %d", option);
     }
@@ -5236,6 +5244,292 @@ static int ms_labels_host(const pn_index *ix, const T *centres, size_t nc, T h, 
 PN_MS_ENTRIES(f32, float)
 PN_MS_ENTRIES(f64, double)
 #undef PN_MS_ENTRIES
+
+// ---------------------------------------------------------------------------
+// k-means: pn_kmeans_assign_{,device_}*, pn_kmeans_{,device_}*, pn_kmeans_bounds_f32 (the kernels, the bound and the shape
+// of the sums: kmeans.hip).  An assignment is
+//   filter path:  [pack the rows, once per call] pack the centres -> filter (MFMA) -> re-rank and proof, which lists the
+//                 rows it cannot prove -> the exact kernel over the list (its grid is sized for n; the count stays on the
+//                 device and is added to the handle's fallback counter by a kernel)
+//   exact path:   the exact kernel over every row
+// and nothing of it waits for the device.  The iteration loop of pn_kmeans_* reads 16 bytes {shift2, stop} per iteration.
+// ---------------------------------------------------------------------------
+// One centre leaves nothing to filter (every row is its member): the exact kernel, whatever is forced.  PN_ENGINE_AUTO
+// takes the filter from 64 centres, 64 columns and 8 * 10^9 (row, centre, column) products on -- 16 * 10^9 below 128
+// columns: below that the exact kernel's whole work is as small as the filter's fixed cost (packing the rows, eight
+// launches), and on narrow rows the filter gains too little per centre to make it up (the line)
+constexpr size_t kKmAutoMinCentres = 64, kKmAutoMinDim = 64, kKmAutoWideDim = 128;
+constexpr double kKmAutoMinWork = 8e9, kKmAutoMinWorkNarrow = 16e9;
+static bool km_use_filter(const pn_index *ix, size_t nc) {
+    if (nc < 2 || ix->n == 0 || !km_filter_supported((int)ix->dim) || ix->kmeans_filter == 2) return false;
+    if (ix->kmeans_filter == 1) return true;
+    if (ix->engine == PN_ENGINE_EXACT) return false;
+    if (ix->engine == PN_ENGINE_BF16) return true;
+    return nc >= kKmAutoMinCentres && ix->dim >= kKmAutoMinDim &&
+           (double)ix->n * (double)nc * (double)ix->dim >= (ix->dim >= kKmAutoWideDim ? kKmAutoMinWork : kKmAutoMinWorkNarrow);
+}
+// (before any device is touched; the header states the order)
+static int km_args(const pn_index *ix, bool loop, unsigned flags, double tol, size_t max_iter, const void *labels,
+                   const void *centres_out, const void *centres, size_t nc, int elem_bytes) {
+    if (flags) return fail(PN_ERR_INVALID, "unknown k-means flags 0x%x", flags);
+    if (loop && !(tol >= 0.0)) return fail(PN_ERR_INVALID, "tol must be >= 0");
+    if (loop && max_iter == 0) return fail(PN_ERR_INVALID, "max_iter must be at least 1");
+    if (!labels) return fail(PN_ERR_INVALID, "labels is NULL");
+    if (loop && !centres_out) return fail(PN_ERR_INVALID, "centres_out is NULL");
+    if ((nc || loop) && !centres) return fail(PN_ERR_INVALID, "centres is NULL");
+    if (loop && nc == 0) return fail(PN_ERR_INVALID, "k-means needs at least one centre");
+    if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
+    if (ix->elem_bytes != elem_bytes) return fail(PN_ERR_INVALID, "index element type mismatch");
+    if (ix->metric != 0) return fail(PN_ERR_UNSUPPORTED, "k-means needs a Euclidean index");
+    if (ix->n > 0x7FFFFFFFull || nc > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many rows or centres");
+    return PN_OK;
+}
+// the rows' image of a call (filter path only)
+template <typename T>
+static int km_pack_rows(const pn_index *ix, Workspace &ws, KmRowImage *rows, hipStream_t s) {
+    PNCHK(ws.w_km_rows.ensure(km_row_image_bytes(ix->n, (int)ix->dim)));
+    *rows = km_row_image_at(ws.w_km_rows.p, ix->n, (int)ix->dim);
+    HIPCHK(launch_km_pack_rows<T>((const T *)ix->d_pts, ix->n, ix->ld, (int)ix->dim, *rows, s));
+    return PN_OK;
+}
+// One assignment, in a held workspace on stream s; n >= 1.  rows: the packed rows when the filter is used, else nullptr.
+// d_dist nullable unless d_inertia is given.
+template <typename T>
+static int km_assign_enqueue(const pn_index *ix, Workspace &ws, const KmRowImage *rows, const T *d_centres, size_t nc,
+                             int64_t *d_labels, T *d_dist, double *d_inertia, hipStream_t s) {
+    const size_t n = ix->n;
+    const int dim = (int)ix->dim;
+    const T *X = (const T *)ix->d_pts;
+    // w_km: nsel (8 bytes) | [inertia without the caller's distances: dist [n] T] | [inertia: its segments] | [filter:
+    // cand [n] u32 | tau [n] f32 | sel [n] u32]
+    const size_t n2 = round_up(n, (size_t)2);
+    const bool filter = rows && nc;
+    const size_t dist_bytes = d_inertia && !d_dist ? n2 * sizeof(T) : 0, seg_bytes = d_inertia ? km_inertia_bytes(n) : 0;
+    PNCHK(ws.w_km.ensure(8 + dist_bytes + seg_bytes + (filter ? n2 * 12 : 0)));
+    uint32_t *nsel = (uint32_t *)ws.w_km.p;
+    T *own_dist = (T *)(nsel + 2);
+    void *seg = (void *)((char *)own_dist + dist_bytes);
+    uint32_t *cand = (uint32_t *)((char *)seg + seg_bytes), *sel = cand + 2 * n2;
+    float *tau = (float *)(cand + n2);
+    if (d_inertia && !d_dist) d_dist = own_dist;
+    if (filter) {
+        PNCHK(ws.w_km_cent.ensure(km_centre_image_bytes(nc, dim)));
+        const KmCentreImage ci = km_centre_image_at(ws.w_km_cent.p, nc, dim);
+        HIPCHK(launch_km_pack_centres<T>(d_centres, nc, dim, ci, s));
+        HIPCHK(launch_km_filter(*rows, n, ci, nc, cand, tau, s));
+        HIPCHK(hipMemsetAsync(nsel, 0, sizeof(uint32_t), s));
+        HIPCHK(launch_km_rerank<T>(X, n, ix->ld, dim, d_centres, nc, cand, tau, *rows, ci, sel, nsel, d_labels, d_dist, s));
+        HIPCHK(launch_km_exact<T>(X, n, ix->ld, dim, d_centres, nc, sel, nsel, d_labels, d_dist, s));
+        if (ix->d_stats) HIPCHK(launch_radii_add_listed(nsel, ix->d_stats, s));
+    } else {
+        HIPCHK(launch_km_exact<T>(X, n, ix->ld, dim, d_centres, nc, nullptr, nullptr, d_labels, d_dist, s));
+    }
+    if (d_inertia) HIPCHK(launch_km_inertia<T>(d_labels, d_dist, n, seg, d_inertia, s));
+    std::lock_guard<std::mutex> lk(ix->sh.mu);
+    ix->sh.stats.queries += n;
+    return PN_OK;
+}
+template <typename T>
+static int km_assign_device(const pn_index *ix, const T *d_centres, size_t nc, unsigned flags, int64_t *d_labels, T *d_dist,
+                            double *d_inertia, hipStream_t s) {
+    PNCHK(km_args(ix, false, flags, 0.0, 1, d_labels, nullptr, d_centres, nc, (int)sizeof(T)));
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    if (ix->n == 0) {
+        if (d_inertia) HIPCHK(hipMemsetAsync(d_inertia, 0, sizeof(double), s));
+        return PN_OK;
+    }
+    WsLease lease(ix);
+    lease.s = s;
+    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
+    KmRowImage rows;
+    const bool filter = km_use_filter(ix, nc);
+    if (filter) PNCHK(km_pack_rows<T>(ix, *lease.ws, &rows, s));
+    return km_assign_enqueue<T>(ix, *lease.ws, filter ? &rows : nullptr, d_centres, nc, d_labels, d_dist, d_inertia, s);
+}
+template <typename T>
+static int km_assign_host(const pn_index *ix, const T *centres, size_t nc, unsigned flags, int64_t *labels, T *dist,
+                          double *inertia) {
+    PNCHK(km_args(ix, false, flags, 0.0, 1, labels, nullptr, centres, nc, (int)sizeof(T)));
+    if (ix->n == 0) {
+        if (inertia) *inertia = 0.0;
+        return PN_OK;
+    }
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
+    Workspace &ws = *lease.ws;
+    hipStream_t s = lease.s;
+    const size_t n = ix->n, c_bytes = round_up(nc * ix->dim * sizeof(T), (size_t)8), d_bytes = round_up(n * sizeof(T), (size_t)8);
+    PNCHK(ws.w_km_io.ensure(n * sizeof(int64_t) + 8 + d_bytes + c_bytes));
+    int64_t *d_labels = (int64_t *)ws.w_km_io.p;
+    double *d_inertia = (double *)(d_labels + n);
+    T *d_dist = (T *)(d_inertia + 1), *d_centres = (T *)((char *)d_dist + d_bytes);
+    if (nc) HIPCHK(hipMemcpyAsync(d_centres, centres, nc * ix->dim * sizeof(T), hipMemcpyHostToDevice, s));
+    KmRowImage rows;
+    const bool filter = km_use_filter(ix, nc);
+    if (filter) PNCHK(km_pack_rows<T>(ix, ws, &rows, s));
+    PNCHK(km_assign_enqueue<T>(ix, ws, filter ? &rows : nullptr, d_centres, nc, d_labels, dist || inertia ? d_dist : nullptr,
+                               inertia ? d_inertia : nullptr, s));
+    HIPCHK(hipMemcpyAsync(labels, d_labels, n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    if (dist) HIPCHK(hipMemcpyAsync(dist, d_dist, n * sizeof(T), hipMemcpyDeviceToHost, s));
+    if (inertia) HIPCHK(hipMemcpyAsync(inertia, d_inertia, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return PN_OK;
+}
+// The iterations, in a held workspace on stream s; everything in HBM, d_centres holds the initial centres on entry;
+// n, nc >= 1.  Blocks the host once per iteration.
+template <typename T>
+static int km_loop_enqueue(const pn_index *ix, Workspace &ws, size_t nc, double tol, size_t max_iter, T *d_centres,
+                           int64_t *d_labels, T *d_dist, uint64_t *d_counts, double *d_inertia, uint64_t *d_iterations,
+                           double *d_shift2, hipStream_t s) {
+    const size_t n = ix->n;
+    const int dim = (int)ix->dim;
+    KmRowImage rows;
+    const bool filter = km_use_filter(ix, nc);
+    if (filter) PNCHK(km_pack_rows<T>(ix, ws, &rows, s));
+    PNCHK(ws.w_km_upd.ensure(km_update_bytes(n, nc, dim)));
+    struct {
+        double shift2;
+        unsigned long long stop;
+    } h_stop = {0.0, 0};
+    uint64_t iterations = 0;
+    double *d_stop = nullptr;
+    for (size_t t = 1;; ++t) {
+        PNCHK(km_assign_enqueue<T>(ix, ws, filter ? &rows : nullptr, d_centres, nc, d_labels, (T *)nullptr, nullptr, s));
+        HIPCHK(km_update_enqueue<T>((const T *)ix->d_pts, n, ix->ld, dim, d_labels, nc, ws.w_km_upd.p, d_centres, nullptr, tol,
+                                    t >= max_iter, &d_stop, s));
+        HIPCHK(hipMemcpyAsync(&h_stop, d_stop, sizeof h_stop, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        iterations = t;
+        if (h_stop.stop || t >= max_iter) break;
+    }
+    PNCHK(km_assign_enqueue<T>(ix, ws, filter ? &rows : nullptr, d_centres, nc, d_labels, d_dist, d_inertia, s));
+    if (d_counts)
+        HIPCHK(km_update_enqueue<T>((const T *)ix->d_pts, n, ix->ld, dim, d_labels, nc, ws.w_km_upd.p, (T *)nullptr, d_counts,
+                                    0.0, 1, nullptr, s));
+    if (d_shift2) HIPCHK(hipMemcpyAsync(d_shift2, d_stop, sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (d_iterations) HIPCHK(hipMemcpyAsync(d_iterations, &iterations, sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    if (d_iterations) HIPCHK(hipStreamSynchronize(s));  // (the source is this frame's)
+    return PN_OK;
+}
+template <typename T>
+static int km_device(const pn_index *ix, const T *d_init, size_t nc, double tol, size_t max_iter, unsigned flags, T *d_centres,
+                     int64_t *d_labels, T *d_dist, uint64_t *d_counts, double *d_inertia, uint64_t *d_iterations,
+                     double *d_shift2, hipStream_t s) {
+    PNCHK(km_args(ix, true, flags, tol, max_iter, d_labels, d_centres, d_init, nc, (int)sizeof(T)));
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    if (d_centres != d_init)
+        HIPCHK(hipMemcpyAsync(d_centres, d_init, nc * ix->dim * sizeof(T), hipMemcpyDeviceToDevice, s));
+    if (ix->n == 0) {
+        if (d_counts) HIPCHK(hipMemsetAsync(d_counts, 0, nc * sizeof(uint64_t), s));
+        if (d_inertia) HIPCHK(hipMemsetAsync(d_inertia, 0, sizeof(double), s));
+        if (d_iterations) HIPCHK(hipMemsetAsync(d_iterations, 0, sizeof(uint64_t), s));
+        if (d_shift2) HIPCHK(hipMemsetAsync(d_shift2, 0, sizeof(double), s));
+        return PN_OK;
+    }
+    WsLease lease(ix);
+    lease.s = s;
+    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
+    return km_loop_enqueue<T>(ix, *lease.ws, nc, tol, max_iter, d_centres, d_labels, d_dist, d_counts, d_inertia, d_iterations,
+                              d_shift2, s);
+}
+template <typename T>
+static int km_host(const pn_index *ix, const T *init, size_t nc, double tol, size_t max_iter, unsigned flags, T *centres,
+                   int64_t *labels, T *dist, uint64_t *counts, double *inertia, uint64_t *iterations, double *shift2) {
+    PNCHK(km_args(ix, true, flags, tol, max_iter, labels, centres, init, nc, (int)sizeof(T)));
+    const size_t n = ix->n, dim = ix->dim;
+    if (n == 0) {
+        if (centres != init) memmove(centres, init, nc * dim * sizeof(T));
+        if (counts) memset(counts, 0, nc * sizeof(uint64_t));
+        if (inertia) *inertia = 0.0;
+        if (iterations) *iterations = 0;
+        if (shift2) *shift2 = 0.0;
+        return PN_OK;
+    }
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
+    Workspace &ws = *lease.ws;
+    hipStream_t s = lease.s;
+    const size_t c_bytes = round_up(nc * dim * sizeof(T), (size_t)8), d_bytes = round_up(n * sizeof(T), (size_t)8);
+    PNCHK(ws.w_km_io.ensure(n * sizeof(int64_t) + 24 + nc * sizeof(uint64_t) + d_bytes + c_bytes));
+    int64_t *d_labels = (int64_t *)ws.w_km_io.p;
+    double *d_inertia = (double *)(d_labels + n), *d_shift2 = d_inertia + 1;
+    uint64_t *d_iters = (uint64_t *)(d_shift2 + 1), *d_counts = d_iters + 1;
+    T *d_dist = (T *)(d_counts + nc), *d_centres = (T *)((char *)d_dist + d_bytes);
+    HIPCHK(hipMemcpyAsync(d_centres, init, nc * dim * sizeof(T), hipMemcpyHostToDevice, s));
+    PNCHK(km_loop_enqueue<T>(ix, ws, nc, tol, max_iter, d_centres, d_labels, dist || inertia ? d_dist : nullptr,
+                             counts ? d_counts : nullptr, inertia ? d_inertia : nullptr, d_iters,
+                             d_shift2, s));
+    HIPCHK(hipMemcpyAsync(centres, d_centres, nc * dim * sizeof(T), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(labels, d_labels, n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    if (dist) HIPCHK(hipMemcpyAsync(dist, d_dist, n * sizeof(T), hipMemcpyDeviceToHost, s));
+    if (counts) HIPCHK(hipMemcpyAsync(counts, d_counts, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    if (inertia) HIPCHK(hipMemcpyAsync(inertia, d_inertia, sizeof(double), hipMemcpyDeviceToHost, s));
+    if (iterations) HIPCHK(hipMemcpyAsync(iterations, d_iters, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    if (shift2) HIPCHK(hipMemcpyAsync(shift2, d_shift2, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return PN_OK;
+}
+extern "C" int pn_kmeans_bounds_f32(const pn_index *ix, const float *centres, size_t nc, double *bounds_out) {
+    if (!bounds_out) return fail(PN_ERR_INVALID, "bounds_out is NULL");
+    if (nc && !centres) return fail(PN_ERR_INVALID, "centres is NULL");
+    if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
+    if (ix->elem_bytes != 4) return fail(PN_ERR_INVALID, "index element type mismatch");
+    if (ix->metric != 0) return fail(PN_ERR_UNSUPPORTED, "k-means needs a Euclidean index");
+    if (!km_filter_supported((int)ix->dim)) return fail(PN_ERR_UNSUPPORTED, "the k-means filter takes 8 <= dim <= 320");
+    if (ix->n > 0x7FFFFFFFull || nc > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many rows or centres");
+    if (ix->n == 0 || nc == 0) return PN_OK;
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    WsLease lease(ix);
+    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
+    Workspace &ws = *lease.ws;
+    hipStream_t s = lease.s;
+    const int dim = (int)ix->dim;
+    const size_t c_bytes = round_up(nc * ix->dim * sizeof(float), (size_t)8);
+    PNCHK(ws.w_km_io.ensure(ix->n * nc * sizeof(double) + c_bytes));
+    double *d_bounds = (double *)ws.w_km_io.p;
+    float *d_centres = (float *)(d_bounds + ix->n * nc);
+    HIPCHK(hipMemcpyAsync(d_centres, centres, nc * ix->dim * sizeof(float), hipMemcpyHostToDevice, s));
+    KmRowImage rows;
+    PNCHK(km_pack_rows<float>(ix, ws, &rows, s));
+    PNCHK(ws.w_km_cent.ensure(km_centre_image_bytes(nc, dim)));
+    const KmCentreImage ci = km_centre_image_at(ws.w_km_cent.p, nc, dim);
+    HIPCHK(launch_km_pack_centres<float>(d_centres, nc, dim, ci, s));
+    HIPCHK(launch_km_bounds(rows, ix->n, ci, nc, d_bounds, s));
+    HIPCHK(hipMemcpyAsync(bounds_out, d_bounds, ix->n * nc * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return PN_OK;
+}
+#define PN_KM_ENTRIES(SFX, T)                                                                                                  \
+    extern "C" int pn_kmeans_assign_##SFX(const pn_index *ix, const T *centres, size_t nc, unsigned flags, int64_t *labels_out, \
+                                          T *dist_out, double *inertia_out) {                                                  \
+        return km_assign_host<T>(ix, centres, nc, flags, labels_out, dist_out, inertia_out);                                   \
+    }                                                                                                                          \
+    extern "C" int pn_kmeans_assign_device_##SFX(const pn_index *ix, const T *d_centres, size_t nc, unsigned flags,            \
+                                                 int64_t *d_labels, T *d_dist, double *d_inertia, void *stream) {              \
+        return km_assign_device<T>(ix, d_centres, nc, flags, d_labels, d_dist, d_inertia, (hipStream_t)stream);                \
+    }                                                                                                                          \
+    extern "C" int pn_kmeans_##SFX(const pn_index *ix, const T *init_centres, size_t nc, double tol, size_t max_iter,          \
+                                   unsigned flags, T *centres_out, int64_t *labels_out, T *dist_out, uint64_t *counts_out,     \
+                                   double *inertia_out, uint64_t *iterations_out, double *shift2_out) {                        \
+        return km_host<T>(ix, init_centres, nc, tol, max_iter, flags, centres_out, labels_out, dist_out, counts_out,           \
+                          inertia_out, iterations_out, shift2_out);                                                            \
+    }                                                                                                                          \
+    extern "C" int pn_kmeans_device_##SFX(const pn_index *ix, const T *d_init_centres, size_t nc, double tol, size_t max_iter, \
+                                          unsigned flags, T *d_centres, int64_t *d_labels, T *d_dist, uint64_t *d_counts,      \
+                                          double *d_inertia, uint64_t *d_iterations, double *d_shift2, void *stream) {         \
+        return km_device<T>(ix, d_init_centres, nc, tol, max_iter, flags, d_centres, d_labels, d_dist, d_counts, d_inertia,    \
+                            d_iterations, d_shift2, (hipStream_t)stream);                                                      \
+    }
+PN_KM_ENTRIES(f32, float)
+PN_KM_ENTRIES(f64, double)
+#undef PN_KM_ENTRIES
 
 extern "C" void pn_free(void *p) { free(p); }
 

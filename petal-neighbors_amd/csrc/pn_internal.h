@@ -321,7 +321,63 @@ template <typename T>
 hipError_t launch_ms_labels(const T *X, size_t n, size_t ld, int dim, const T *centres, size_t nc, T h, bool orphans,
                             int64_t *labels, hipStream_t s);
 
-// ---- mst.hip, for mean_shift.hip: the bitonic network over (key, pair), ascending by key then pair.  N =
+// ---- kmeans.hip: k-means (pn_kmeans_*, pn_kmeans_assign_*); nothing in it waits for the device.
+// The filter takes 8 <= dim <= 320 (km_filter_supported); its tiles (the test suite
+// asks for them): 128 rows per workgroup (64 beyond 256 padded columns), 32 centres per MFMA tile.
+bool km_filter_supported(int dim);
+int km_row_tile();
+int km_centre_tile();
+// the packed operands, carved from one 16-byte aligned buffer each (km_*_image_bytes, km_*_image_at)
+struct KmRowImage {
+    uint16_t *img = nullptr, *lo = nullptr;  // [n_img][dp] bf16 bits each (x^ and x~), rows at and beyond n zero
+    double *xn = nullptr;     // [n] |x|^2 rounded down; NaN: the row is flagged (not finite, or a norm beyond 2^100)
+    float *xh = nullptr, *xl = nullptr, *xe = nullptr;  // [n] upper bounds of |x^|, |x~| and |e_x|
+    size_t n_img = 0;         // n rounded up to the row tile
+    int dp = 0;               // dim rounded up to 16
+};
+struct KmCentreImage {
+    uint16_t *img = nullptr, *lo = nullptr;  // [nc_pad][dp] each
+    float *cn = nullptr;      // [nc_pad] |c|^2 rounded down, +inf for the padding
+    unsigned long long *cc = nullptr;  // [8]: the bits of Ce, B, Ch, Cl (kmeans.hip), then the "a centre is flagged" word
+    size_t nc_pad = 0;
+};
+size_t km_row_image_bytes(size_t n, int dim);
+size_t km_centre_image_bytes(size_t nc, int dim);
+KmRowImage km_row_image_at(void *buf, size_t n, int dim);
+KmCentreImage km_centre_image_at(void *buf, size_t nc, int dim);
+template <typename T>
+hipError_t launch_km_pack_rows(const T *X, size_t n, size_t ld, int dim, const KmRowImage &r, hipStream_t s);
+template <typename T>
+hipError_t launch_km_pack_centres(const T *centres, size_t nc, int dim, const KmCentreImage &c, hipStream_t s);
+// cand [n] <- the centre of each row's smallest key, tau [n] <- the second smallest key (+inf: there is none)
+hipError_t launch_km_filter(const KmRowImage &r, size_t n, const KmCentreImage &c, size_t nc, uint32_t *cand, float *tau,
+                            hipStream_t s);
+// diagnostic: bounds[i * nc + c] <- L(x_i, c)
+hipError_t launch_km_bounds(const KmRowImage &r, size_t n, const KmCentreImage &c, size_t nc, double *bounds, hipStream_t s);
+// the candidates in the reference's fold; proven rows get their label and distance (dist nullable), the others are listed:
+// sel[0 .. *nsel) in any order (nsel zeroed by the caller, sel [n])
+template <typename T>
+hipError_t launch_km_rerank(const T *X, size_t n, size_t ld, int dim, const T *centres, size_t nc, const uint32_t *cand,
+                            const float *tau, const KmRowImage &r, const KmCentreImage &c, uint32_t *sel, uint32_t *nsel,
+                            int64_t *labels, T *dist, hipStream_t s);
+// every row (sel == nullptr) or the listed rows against every centre: launch_ms_labels' answer, and the distance
+// (nullable); nc == 0: labels -1, distances NaN
+template <typename T>
+hipError_t launch_km_exact(const T *X, size_t n, size_t ld, int dim, const T *centres, size_t nc, const uint32_t *sel,
+                           const uint32_t *nsel, int64_t *labels, T *dist, hipStream_t s);
+// *out <- SUM4096 of (double)dist[i]^2 (0 where labels[i] < 0); buf: km_inertia_bytes(n)
+size_t km_inertia_bytes(size_t n);
+template <typename T>
+hipError_t launch_km_inertia(const int64_t *labels, const T *dist, size_t n, void *buf, double *out, hipStream_t s);
+// The members' lists of labels [n] (one sort), counts [nc] (nullable) and, with centres != nullptr, one update of the
+// centres [nc][dim] in place; *stop_out <- where the 16 bytes {shift2, stop word = shift2 <= tol || last} will be (in
+// buf: km_update_bytes(n, nc, dim), 8-byte aligned).  n, nc >= 1.
+size_t km_update_bytes(size_t n, size_t nc, int dim);
+template <typename T>
+hipError_t km_update_enqueue(const T *X, size_t n, size_t ld, int dim, const int64_t *labels, size_t nc, void *buf,
+                             T *centres, uint64_t *counts, double tol, int last, double **stop_out, hipStream_t s);
+
+// ---- mst.hip, for mean_shift.hip and kmeans.hip: the bitonic network over (key, pair), ascending by key then pair.  N =
 // sort_key_pair_len(count): count padded to a power of two, at least the block one workgroup sorts in LDS; the caller pads
 // the arrays (all-ones keys sort last)
 size_t sort_key_pair_len(size_t count);
