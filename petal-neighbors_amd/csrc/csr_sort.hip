@@ -213,8 +213,8 @@ size_t csr_sort_scratch_entries(size_t nq, size_t max_row, size_t limit) {
 }
 
 template <typename T>
-static hipError_t launch_csr_sort(const uint64_t *offsets, int nq, uint64_t *idx, T *dist, uint64_t limit, size_t max_row,
-                                  const CsrSortScratch &w, int n_cu, hipStream_t s) {
+hipError_t launch_csr_sort(const uint64_t *offsets, int nq, uint64_t *idx, T *dist, uint64_t limit, size_t max_row,
+                           const CsrSortScratch &w, int n_cu, hipStream_t s) {
     if (nq <= 0) return hipSuccess;
     hipLaunchKernelGGL(csr_sort_short_kernel<T>, dim3((unsigned)nq), dim3(kSortThreads), 0, s, offsets, nq, idx, dist, limit,
                        w.nch);
@@ -240,13 +240,9 @@ static hipError_t launch_csr_sort(const uint64_t *offsets, int nq, uint64_t *idx
                            (const uint64_t *)w.chunk_off, idx, dist, (const uint64_t *)w.idx, (const T *)w.dist);
     return hipGetLastError();
 }
-hipError_t launch_csr_sort_f32(const uint64_t *offsets, int nq, uint64_t *idx, float *dist, uint64_t limit, size_t max_row,
-                               const CsrSortScratch &w, int n_cu, hipStream_t s) {
-    return launch_csr_sort<float>(offsets, nq, idx, dist, limit, max_row, w, n_cu, s);
-}
-hipError_t launch_csr_sort_f64(const uint64_t *offsets, int nq, uint64_t *idx, double *dist, uint64_t limit, size_t max_row,
-                               const CsrSortScratch &w, int n_cu, hipStream_t s) {
-    return launch_csr_sort<double>(offsets, nq, idx, dist, limit, max_row, w, n_cu, s);
-}
+template hipError_t launch_csr_sort<float>(const uint64_t *, int, uint64_t *, float *, uint64_t, size_t,
+                                           const CsrSortScratch &, int, hipStream_t);
+template hipError_t launch_csr_sort<double>(const uint64_t *, int, uint64_t *, double *, uint64_t, size_t,
+                                            const CsrSortScratch &, int, hipStream_t);
 
 }  // namespace pn

@@ -271,10 +271,10 @@ __global__ __launch_bounds__(256) void exact_knn_kernel(
 }
 
 template <typename T>
-static hipError_t launch_exact_knn(const T *P, size_t n, int dim, size_t ldp, const T *Q, int nq, size_t ldq,
-                                   int kp, size_t seg_len, const CandBuf &cb, const void *lo_key,
-                                   const uint32_t *lo_idx, const uint32_t *nq_dev, uint32_t nq_off, const T *pnorm,
-                                   const T *qnorm, hipStream_t s, const uint32_t *qsel = nullptr) {
+hipError_t launch_exact_knn(const T *P, size_t n, int dim, size_t ldp, const T *Q, int nq, size_t ldq, int kp,
+                            size_t seg_len, const CandBuf &cb, const void *lo_key, const uint32_t *lo_idx,
+                            const uint32_t *nq_dev, uint32_t nq_off, const T *pnorm, const T *qnorm, hipStream_t s,
+                            const uint32_t *qsel) {
     using KeyT = typename KeyOf<T>::type;
     dim3 grid((unsigned)(cb.nq_pad / kTileQ), (unsigned)cb.nseg), block(256);
     const bool cosm = pnorm != nullptr;
@@ -303,20 +303,12 @@ static hipError_t launch_exact_knn(const T *P, size_t n, int dim, size_t ldp, co
     return hipGetLastError();
 }
 
-hipError_t launch_exact_knn_f32(const float *P, size_t n, int dim, size_t ldp, const float *Q, int nq,
-                                size_t ldq, int kp, size_t seg_len, const CandBuf &cb, const void *lo_key,
-                                const uint32_t *lo_idx, const uint32_t *nq_dev, uint32_t nq_off, const float *pnorm,
-                                const float *qnorm, hipStream_t s, const uint32_t *qsel) {
-    return launch_exact_knn<float>(P, n, dim, ldp, Q, nq, ldq, kp, seg_len, cb, lo_key, lo_idx, nq_dev, nq_off, pnorm,
-                                   qnorm, s, qsel);
-}
-hipError_t launch_exact_knn_f64(const double *P, size_t n, int dim, size_t ldp, const double *Q, int nq,
-                                size_t ldq, int kp, size_t seg_len, const CandBuf &cb, const void *lo_key,
-                                const uint32_t *lo_idx, const uint32_t *nq_dev, uint32_t nq_off, const double *pnorm,
-                                const double *qnorm, hipStream_t s, const uint32_t *qsel) {
-    return launch_exact_knn<double>(P, n, dim, ldp, Q, nq, ldq, kp, seg_len, cb, lo_key, lo_idx, nq_dev, nq_off, pnorm,
-                                    qnorm, s, qsel);
-}
+template hipError_t launch_exact_knn<float>(const float *, size_t, int, size_t, const float *, int, size_t, int, size_t,
+                                            const CandBuf &, const void *, const uint32_t *, const uint32_t *, uint32_t,
+                                            const float *, const float *, hipStream_t, const uint32_t *);
+template hipError_t launch_exact_knn<double>(const double *, size_t, int, size_t, const double *, int, size_t, int,
+                                             size_t, const CandBuf &, const void *, const uint32_t *, const uint32_t *,
+                                             uint32_t, const double *, const double *, hipStream_t, const uint32_t *);
 
 // ---------------------------------------------------------------------------
 // query_radius: { i : distance(q, p_i) < r } (strict, src/ball_tree.rs:277),
@@ -440,11 +432,10 @@ __global__ __launch_bounds__(256) void exact_radius_kernel(
 }
 
 template <typename T>
-static hipError_t launch_exact_radius(const T *P, size_t n, int dim, size_t ldp, const T *Q, int nq, size_t ldq,
-                                      T r, size_t seg_len, int nseg, uint32_t *counts, const uint64_t *offsets,
-                                      uint64_t *fill, uint64_t index_base, const T *pnorm, const T *qnorm,
-                                      hipStream_t s, const uint32_t *qsel = nullptr, const uint32_t *nq_dev = nullptr,
-                                      uint64_t capacity = ~0ull, T *fill_dist = nullptr, const T *radii = nullptr) {
+hipError_t launch_exact_radius(const T *P, size_t n, int dim, size_t ldp, const T *Q, int nq, size_t ldq, T r,
+                               size_t seg_len, int nseg, uint32_t *counts, const uint64_t *offsets, uint64_t *fill,
+                               uint64_t index_base, const T *pnorm, const T *qnorm, hipStream_t s, const uint32_t *qsel,
+                               const uint32_t *nq_dev, uint64_t capacity, T *fill_dist, const T *radii) {
     dim3 grid((unsigned)(round_up((size_t)nq, kTileQ) / kTileQ), (unsigned)nseg), block(256);
 #define PN_RAD(FF, CC, WW)                                                                                          \
     hipLaunchKernelGGL((exact_radius_kernel<T, FF, CC, WW>), grid, block, 0, s, P, n, dim, ldp, Q, nq, ldq, r, seg_len, \
@@ -459,22 +450,14 @@ static hipError_t launch_exact_radius(const T *P, size_t n, int dim, size_t ldp,
 #undef PN_RAD
     return hipGetLastError();
 }
-hipError_t launch_exact_radius_f32(const float *P, size_t n, int dim, size_t ldp, const float *Q, int nq,
-                                   size_t ldq, float r, size_t seg_len, int nseg, uint32_t *counts,
-                                   const uint64_t *offsets, uint64_t *fill, uint64_t index_base, const float *pnorm,
-                                   const float *qnorm, hipStream_t s, const uint32_t *qsel, const uint32_t *nq_dev,
-                                   uint64_t capacity, float *fill_dist, const float *radii) {
-    return launch_exact_radius<float>(P, n, dim, ldp, Q, nq, ldq, r, seg_len, nseg, counts, offsets, fill,
-                                      index_base, pnorm, qnorm, s, qsel, nq_dev, capacity, fill_dist, radii);
-}
-hipError_t launch_exact_radius_f64(const double *P, size_t n, int dim, size_t ldp, const double *Q, int nq,
-                                   size_t ldq, double r, size_t seg_len, int nseg, uint32_t *counts,
-                                   const uint64_t *offsets, uint64_t *fill, uint64_t index_base, const double *pnorm,
-                                   const double *qnorm, hipStream_t s, const uint32_t *qsel, const uint32_t *nq_dev,
-                                   uint64_t capacity, double *fill_dist, const double *radii) {
-    return launch_exact_radius<double>(P, n, dim, ldp, Q, nq, ldq, r, seg_len, nseg, counts, offsets, fill,
-                                       index_base, pnorm, qnorm, s, qsel, nq_dev, capacity, fill_dist, radii);
-}
+template hipError_t launch_exact_radius<float>(const float *, size_t, int, size_t, const float *, int, size_t, float,
+                                               size_t, int, uint32_t *, const uint64_t *, uint64_t *, uint64_t,
+                                               const float *, const float *, hipStream_t, const uint32_t *,
+                                               const uint32_t *, uint64_t, float *, const float *);
+template hipError_t launch_exact_radius<double>(const double *, size_t, int, size_t, const double *, int, size_t,
+                                                double, size_t, int, uint32_t *, const uint64_t *, uint64_t *, uint64_t,
+                                                const double *, const double *, hipStream_t, const uint32_t *,
+                                                const uint32_t *, uint64_t, double *, const double *);
 
 // ---------------------------------------------------------------------------
 // distance::pairwise (src/distance.rs:58-74): out[i][j] = distance(x_i, x_j), zero diagonal.  Like the reference,
@@ -516,19 +499,15 @@ __global__ __launch_bounds__(256) void exact_pairwise_kernel(const T *__restrict
 }
 
 template <typename T>
-static hipError_t launch_exact_pairwise(const T *X, size_t n, int dim, size_t ld, T *out, hipStream_t s) {
+hipError_t launch_exact_pairwise(const T *X, size_t n, int dim, size_t ld, T *out, hipStream_t s) {
     const unsigned long long t = (unsigned long long)(round_up(n, kTileQ) / kTileQ);
     const unsigned long long blocks = t * (t + 1) / 2;
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
     hipLaunchKernelGGL((exact_pairwise_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, s, X, n, dim, ld, out, (uint32_t)t);
     return hipGetLastError();
 }
-hipError_t launch_exact_pairwise_f32(const float *X, size_t n, int dim, size_t ld, float *out, hipStream_t s) {
-    return launch_exact_pairwise<float>(X, n, dim, ld, out, s);
-}
-hipError_t launch_exact_pairwise_f64(const double *X, size_t n, int dim, size_t ld, double *out, hipStream_t s) {
-    return launch_exact_pairwise<double>(X, n, dim, ld, out, s);
-}
+template hipError_t launch_exact_pairwise<float>(const float *, size_t, int, size_t, float *, hipStream_t);
+template hipError_t launch_exact_pairwise<double>(const double *, size_t, int, size_t, double *, hipStream_t);
 
 // ---------------------------------------------------------------------------
 // distance::pairwise(x, &Cosine) (src/distance.rs:58-74, 85-107): out[i][j] = 1 - dot(x_i, x_j) / (|x_i| |x_j|),
@@ -566,31 +545,24 @@ __global__ void cosine_pairwise_kernel(const T *__restrict__ X, size_t n, int di
     const T den = norms[i] * norms[j];
     out[i * n + j] = (T)1 - dot / den;
 }
-hipError_t launch_cosine_norms_f32(const float *X, size_t n, int dim, size_t ld, float *norms, hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL((cosine_norms_kernel<float>), dim3((unsigned)((n + 127) / 128)), dim3(128), 0, s, X, n, dim, ld, norms);
-    return hipGetLastError();
-}
-hipError_t launch_cosine_norms_f64(const double *X, size_t n, int dim, size_t ld, double *norms, hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL((cosine_norms_kernel<double>), dim3((unsigned)((n + 127) / 128)), dim3(128), 0, s, X, n, dim, ld, norms);
-    return hipGetLastError();
-}
 template <typename T>
-static hipError_t launch_cosine_pairwise(const T *X, size_t n, int dim, size_t ld, T *norms, T *out, hipStream_t s) {
+hipError_t launch_cosine_norms(const T *X, size_t n, int dim, size_t ld, T *norms, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL((cosine_norms_kernel<T>), dim3((unsigned)((n + 127) / 128)), dim3(128), 0, s, X, n, dim, ld, norms);
+    return hipGetLastError();
+}
+template hipError_t launch_cosine_norms<float>(const float *, size_t, int, size_t, float *, hipStream_t);
+template hipError_t launch_cosine_norms<double>(const double *, size_t, int, size_t, double *, hipStream_t);
+template <typename T>
+hipError_t launch_cosine_pairwise(const T *X, size_t n, int dim, size_t ld, T *norms, T *out, hipStream_t s) {
     hipLaunchKernelGGL((cosine_norms_kernel<T>), dim3((unsigned)((n + 127) / 128)), dim3(128), 0, s, X, n, dim, ld, norms);
     hipLaunchKernelGGL((cosine_pairwise_kernel<T>), dim3((unsigned)((n + 127) / 128), (unsigned)n), dim3(128), 0, s, X, n,
                        dim, ld, norms, out);
     return hipGetLastError();
 }
-hipError_t launch_cosine_pairwise_f32(const float *X, size_t n, int dim, size_t ld, float *norms, float *out,
-                                      hipStream_t s) {
-    return launch_cosine_pairwise<float>(X, n, dim, ld, norms, out, s);
-}
-hipError_t launch_cosine_pairwise_f64(const double *X, size_t n, int dim, size_t ld, double *norms, double *out,
-                                      hipStream_t s) {
-    return launch_cosine_pairwise<double>(X, n, dim, ld, norms, out, s);
-}
+template hipError_t launch_cosine_pairwise<float>(const float *, size_t, int, size_t, float *, float *, hipStream_t);
+template hipError_t launch_cosine_pairwise<double>(const double *, size_t, int, size_t, double *, double *,
+                                                   hipStream_t);
 
 // ---------------------------------------------------------------------------
 // Masked nearest-outside-row scan of pn_mst_* (mst.hip): for each listed row i = qsel[r] the least edge, in edge order,
@@ -702,9 +674,9 @@ __global__ __launch_bounds__(256) void mst_scan_kernel(const T *__restrict__ P, 
 }
 
 template <typename T>
-static hipError_t launch_mst_scan(const T *P, size_t n, int dim, size_t ldp, const uint32_t *qsel, int nq, size_t seg_len,
-                                  int nseg, const uint32_t *comp, const typename KeyOf<T>::type *ckey, const T *cnorm,
-                                  typename KeyOf<T>::type *seg_key, uint32_t *seg_j, hipStream_t s) {
+hipError_t launch_mst_scan(const T *P, size_t n, int dim, size_t ldp, const uint32_t *qsel, int nq, size_t seg_len,
+                           int nseg, const uint32_t *comp, const typename KeyOf<T>::type *ckey, const T *cnorm,
+                           typename KeyOf<T>::type *seg_key, uint32_t *seg_j, hipStream_t s) {
     if (nq <= 0) return hipSuccess;
     const size_t nq_pad = round_up((size_t)nq, kTileQ);
     dim3 grid((unsigned)(nq_pad / kTileQ), (unsigned)nseg), block(256);
@@ -716,15 +688,11 @@ static hipError_t launch_mst_scan(const T *P, size_t n, int dim, size_t ldp, con
                            seg_key, seg_j, nq_pad);
     return hipGetLastError();
 }
-hipError_t launch_mst_scan_f32(const float *P, size_t n, int dim, size_t ldp, const uint32_t *qsel, int nq, size_t seg_len,
-                               int nseg, const uint32_t *comp, const uint32_t *ckey, const float *cnorm, uint32_t *seg_key,
-                               uint32_t *seg_j, hipStream_t s) {
-    return launch_mst_scan<float>(P, n, dim, ldp, qsel, nq, seg_len, nseg, comp, ckey, cnorm, seg_key, seg_j, s);
-}
-hipError_t launch_mst_scan_f64(const double *P, size_t n, int dim, size_t ldp, const uint32_t *qsel, int nq, size_t seg_len,
-                               int nseg, const uint32_t *comp, const uint64_t *ckey, const double *cnorm, uint64_t *seg_key,
-                               uint32_t *seg_j, hipStream_t s) {
-    return launch_mst_scan<double>(P, n, dim, ldp, qsel, nq, seg_len, nseg, comp, ckey, cnorm, seg_key, seg_j, s);
-}
+template hipError_t launch_mst_scan<float>(const float *, size_t, int, size_t, const uint32_t *, int, size_t, int,
+                                           const uint32_t *, const KeyOf<float>::type *, const float *,
+                                           KeyOf<float>::type *, uint32_t *, hipStream_t);
+template hipError_t launch_mst_scan<double>(const double *, size_t, int, size_t, const uint32_t *, int, size_t, int,
+                                            const uint32_t *, const KeyOf<double>::type *, const double *,
+                                            KeyOf<double>::type *, uint32_t *, hipStream_t);
 
 }  // namespace pn

@@ -129,14 +129,12 @@ struct DevBuf {
     }
 };
 
-// Per-call scratch.  A query call takes one workspace from the index's pool for its whole duration, so calls from
-// several host threads on one handle run side by side (BallTree queries take &self, `Euclidean: Sync`,
-// src/distance.rs:19).  The *_device entry points return while their kernels are still running: `done` marks the end
-// of the last call that used the workspace, and a later call on ANOTHER stream waits for it before touching the
-// buffers (same stream: stream order is enough).
-struct Workspace {
+// The buffers of a workspace: DevBuf members ONLY.  Workspace walks this struct as an array of them -- to hand every
+// buffer its `retired` list and to release them at destruction -- so a buffer declared here is registered by being
+// declared.
+struct WorkspaceBufs {
     DevBuf w_q, w_qnorm, w_qnrm, w_keys, w_idx, w_cnt, w_tau, w_flags, w_sel, w_misc, w2_keys, w2_idx, w2_cnt, w2_tau, w_lo;
-    DevBuf w_bq, w_qn, w_qbad, w_gq, w_gqn, w_gidx, w_gdist, w_gsel, w_seed, w_qstat, w_lists;  // bf16 tier, second tier
+    DevBuf w_bq, w_qn, w_qbad, w_gq, w_gqn, w_gsel, w_seed, w_lists;  // bf16 tier, second tier
     DevBuf w_hq, w_hidx, w_hdist;  // staging of the host entry points (queries up, results down)
     DevBuf w_hrad;                 // pn_query_radii_*: the host entry points' radii, uploaded
     DevBuf w_fparts;               // second tier, many-segment path: per-group partial results
@@ -170,6 +168,16 @@ struct Workspace {
     // pn_kmeans_*: the packed rows (once per call), the packed centres, the O(n) arrays of an assignment (candidates,
     // thresholds, the list of unproven rows, distances, inertia segments), the update's scratch, the host entries' staging
     DevBuf w_km_rows, w_km_cent, w_km, w_km_upd, w_km_io;
+    DevBuf w_pcnt;                 // shared thresholds: the segments' published fill counts [nseg][nq_pad]
+};
+static_assert(std::is_standard_layout<WorkspaceBufs>::value && sizeof(WorkspaceBufs) % sizeof(DevBuf) == 0,
+              "WorkspaceBufs holds DevBuf members only");
+// Per-call scratch.  A query call takes one workspace from the index's pool for its whole duration, so calls from
+// several host threads on one handle run side by side (BallTree queries take &self, `Euclidean: Sync`,
+// src/distance.rs:19).  The *_device entry points return while their kernels are still running: `done` marks the end
+// of the last call that used the workspace, and a later call on ANOTHER stream waits for it before touching the
+// buffers (same stream: stream order is enough).
+struct Workspace : WorkspaceBufs {
     // small calls (tiny_*): mapped pinned host memory the one kernel of the call reads its queries from and writes its
     // answers to -- no copy commands
     void *pin_in = nullptr, *pin_out = nullptr;
@@ -187,7 +195,6 @@ struct Workspace {
         *have = want;
         return PN_OK;
     }
-    DevBuf w_pcnt;                 // shared thresholds: the segments' published fill counts [nseg][nq_pad]
     uint32_t sh_epoch = 0;         // epoch of the last launch that published into w_pcnt (1 .. 4095)
     size_t sh_nseg = 0, sh_nq_pad = 0;  // geometry w_pcnt was last used with (a change: zero it once)
     hipStream_t stream = nullptr;  // the host entry points run here
@@ -195,12 +202,11 @@ struct Workspace {
     hipEvent_t done = nullptr;
     hipStream_t last_stream = nullptr;
     bool in_flight = false;
-    DevBuf *all[73] = {&w_km_rows, &w_km_cent, &w_km, &w_km_upd, &w_km_io, &w_ms, &w_ms_io, &w_kde, &w_kde_io, &w_opt, &w_opt_graph, &w_opt_io, &w_lof, &w_lof_io, &w_hdb, &w_hdb_io, &w_mst, &w_mst_io, &w_db, &w_db_side, &w_db_out, &w_hrad, &w_sf_idx, &w_sf_dist, &w_sf_off, &w_sf_coff, &w_sf_flag, &w_sf_cnt, &w_sf_scan, &w_sf_hoff, &w_cs_hoff, &w_rkd, &w_cs_nch, &w_cs_off, &w_cs_scan, &w_cs_idx, &w_cs_dist, &w_gqn, &w_rpos, &w_rfin, &w_rcx, &w_rox, &w_rscan, &w_q, &w_qnorm, &w_qnrm, &w_keys, &w_idx, &w_cnt, &w_tau, &w_flags, &w_sel, &w_misc, &w2_keys, &w2_idx,
-                       &w2_cnt, &w2_tau, &w_lo, &w_bq, &w_qn, &w_qbad, &w_gq, &w_gidx, &w_gdist, &w_gsel, &w_seed,
-                       &w_qstat, &w_lists, &w_hq, &w_hidx, &w_hdist, &w_fparts, &w_pcnt};
     std::vector<void *> retired;  // outgrown allocations, freed once `done` has passed (DevBuf::ensure)
+    DevBuf *begin() { return reinterpret_cast<DevBuf *>(static_cast<WorkspaceBufs *>(this)); }
+    DevBuf *end() { return begin() + sizeof(WorkspaceBufs) / sizeof(DevBuf); }
     Workspace() {
-        for (DevBuf *b : all) b->retired = &retired;
+        for (DevBuf &b : *this) b.retired = &retired;
     }
     Workspace(const Workspace &) = delete;
     Workspace &operator=(const Workspace &) = delete;
@@ -457,12 +463,7 @@ static int finish_index(pn_index *ix, const T *d_src, size_t row_stride, hipStre
     HIPCHK(hipMemsetAsync(ix->d_stats, 0, kPnStatWords * sizeof(unsigned long long), s));
     const size_t bytes = ix->n_pad * ix->ld * sizeof(T);
     HIPCHK(hipMalloc(&ix->d_pts, bytes ? bytes : 256));
-    if (sizeof(T) == 4)
-        HIPCHK(launch_pack_rows_f32((const float *)d_src, ix->n, ix->dim, row_stride, (float *)ix->d_pts, ix->n_pad,
-                                    ix->ld, s));
-    else
-        HIPCHK(launch_pack_rows_f64((const double *)d_src, ix->n, ix->dim, row_stride, (double *)ix->d_pts,
-                                    ix->n_pad, ix->ld, s));
+    HIPCHK(launch_pack_rows<T>(d_src, ix->n, ix->dim, row_stride, (T *)ix->d_pts, ix->n_pad, ix->ld, s));
     ix->mfma_ok = false;
     ix->bf16_ok = false;
     ix->bf16_ci = false;
@@ -471,10 +472,7 @@ static int finish_index(pn_index *ix, const T *d_src, size_t row_stride, hipStre
         // Cosine: the rows' norms (sequential sum of squares + sqrt, in T) for the exact evaluation of Cosine::distance
         HIPCHK(hipMalloc(&ix->d_cnorm, ix->n_pad * sizeof(T)));
         HIPCHK(hipMemsetAsync(ix->d_cnorm, 0, ix->n_pad * sizeof(T), s));
-        if (sizeof(T) == 4)
-            HIPCHK(launch_cosine_norms_f32((const float *)ix->d_pts, ix->n, (int)ix->dim, ix->ld, (float *)ix->d_cnorm, s));
-        else
-            HIPCHK(launch_cosine_norms_f64((const double *)ix->d_pts, ix->n, (int)ix->dim, ix->ld, (double *)ix->d_cnorm, s));
+        HIPCHK(launch_cosine_norms<T>((const T *)ix->d_pts, ix->n, (int)ix->dim, ix->ld, (T *)ix->d_cnorm, s));
     }
     // device scratch: column sums [dim + 1] | BuildWords
     DevTmp scr, nrm;
@@ -733,7 +731,7 @@ extern "C" void pn_index_destroy(pn_index *ix) {
     handle_wait(ix, true);
     if (ix->stream) (void)hipStreamSynchronize(ix->stream);
     for (Workspace *ws : ix->sh.all_ws) {
-        for (DevBuf *b : ws->all) b->release();
+        for (DevBuf &b : *ws) b.release();
         ws->free_retired();
         for (hipEvent_t e : ws->ev_r)
             if (e) (void)hipEventDestroy(e);
@@ -820,6 +818,28 @@ struct WsLease {  // releases on every return path
     explicit WsLease(const pn_index *i) : ix(i) {}
     ~WsLease() {
         if (ws) ws_release(ix, ws, s);
+    }
+};
+// One call on a handle: the handle's device made current, then a workspace leased for the call.  Members are destroyed
+// in reverse order of declaration: the lease first (ws_release records the end-of-use event, which needs the device
+// current), then the guard.
+struct CallScope {
+    DeviceGuard g;
+    WsLease lease;
+    explicit CallScope(const pn_index *ix) : g(ix->device), lease(ix) {}
+    int guard() const { return g.ok ? PN_OK : fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", lease.ix->device); }
+    // on a caller's stream.  NULL is HIP's default stream (what torch.cuda.current_stream() is unless changed): work is
+    // ordered with the caller's other default-stream work, as a caller of a *_device entry point expects
+    int on_stream(hipStream_t caller) { return open(caller, false); }
+    int own_stream() { return open(nullptr, true); }  // on the workspace's own stream: the host entry points
+    Workspace &ws() const { return *lease.ws; }
+    hipStream_t s() const { return lease.s; }
+
+private:
+    int open(hipStream_t st, bool own) {
+        PNCHK(guard());
+        lease.s = st;
+        return ws_acquire(lease.ix, &lease.s, own, &lease.ws);
     }
 };
 
@@ -1102,90 +1122,6 @@ static ScanPlan plan_segments(size_t n, size_t q_tiles, int cap, int forced, siz
 // ---------------------------------------------------------------------------
 // k-NN
 // ---------------------------------------------------------------------------
-template <typename T> struct Ops;
-template <> struct Ops<float> {
-    static hipError_t rerank(const CandBuf &cb, const float *P, size_t n, int dim, size_t ldp, const float *Q, int nq,
-                             size_t ldq, int kout, uint64_t base, uint64_t *io, float *dd, size_t os, uint32_t *flags,
-                             uint32_t *nf, const double *qn, const uint32_t *qbad, uint32_t *sel, unsigned long long *st,
-                             hipStream_t s, int fe, int cm) {
-        return launch_select_rerank_f32(cb, P, n, dim, ldp, Q, nq, ldq, kout, base, io, dd, os, flags, nf, qn, qbad, sel, st,
-                                        s, fe, cm);
-    }
-    static hipError_t rerank_cos(const CandBuf &cb, const float *P, size_t n, int dim, size_t ldp, const float *Q, int nq,
-                                 size_t ldq, int kout, uint64_t base, uint64_t *io, float *dd, size_t os, uint32_t *flags,
-                                 uint32_t *nf, const double *qn, const uint32_t *qbad, uint32_t *sel, unsigned long long *st,
-                                 hipStream_t s, int fe, int cm, const float *cn, const float *qnorm) {
-        return launch_select_rerank_cos_f32(cb, P, n, dim, ldp, Q, nq, ldq, kout, base, io, dd, os, flags, nf, qn, qbad, sel,
-                                            st, s, fe, cm, cn, qnorm);
-    }
-    static hipError_t pack(const float *s, size_t n, size_t c, size_t rs, float *d, size_t np, size_t ld, hipStream_t st) {
-        return launch_pack_rows_f32(s, n, c, rs, d, np, ld, st);
-    }
-    static hipError_t knn(const float *P, size_t n, int dim, size_t ldp, const float *Q, int nq, size_t ldq, int kp,
-                          size_t seg_len, const CandBuf &cb, const void *lk, const uint32_t *li, const uint32_t *nd,
-                          uint32_t no, const float *pn, const float *qn, hipStream_t s, const uint32_t *qsel = nullptr) {
-        return launch_exact_knn_f32(P, n, dim, ldp, Q, nq, ldq, kp, seg_len, cb, lk, li, nd, no, pn, qn, s, qsel);
-    }
-    static hipError_t cnorms(const float *X, size_t n, int dim, size_t ld, float *o, hipStream_t s) {
-        return launch_cosine_norms_f32(X, n, dim, ld, o, s);
-    }
-    static hipError_t select(const CandBuf &cb, int nq, int kout, uint64_t base, uint64_t *io, float *dd, size_t os,
-                             size_t oo, void *lk, uint32_t *li, const uint32_t *nd, uint32_t no, bool sk, hipStream_t s,
-                             const uint32_t *osel = nullptr) {
-        return launch_select_exact_f32(cb, nq, kout, base, io, dd, os, oo, lk, li, nd, no, sk, s, osel);
-    }
-    static hipError_t select_groups(const CandBuf &cb, int groups, int kp, int nq, int kout, uint64_t base, uint64_t *io,
-                                    float *dd, size_t gs, const uint32_t *nd, uint32_t no, hipStream_t s, bool sk = false) {
-        return launch_select_exact_groups_f32(cb, groups, kp, nq, kout, base, io, dd, gs, nd, no, s, sk);
-    }
-    static hipError_t merge(const uint64_t *pi, const float *pd, int np, size_t is, size_t ds, int nq, int kp, int ko,
-                            uint64_t *io, float *dd, hipStream_t s, const uint32_t *nd, const uint32_t *osel, size_t os,
-                            uint32_t *hc, bool sk = false) {
-        return launch_merge_topk_f32(pi, pd, np, is, ds, nq, kp, ko, io, dd, s, nd, osel, os, hc, sk);
-    }
-};
-template <> struct Ops<double> {
-    static hipError_t rerank(const CandBuf &cb, const double *P, size_t n, int dim, size_t ldp, const double *Q, int nq,
-                             size_t ldq, int kout, uint64_t base, uint64_t *io, double *dd, size_t os, uint32_t *flags,
-                             uint32_t *nf, const double *qn, const uint32_t *qbad, uint32_t *sel, unsigned long long *st,
-                             hipStream_t s, int fe, int cm) {
-        return launch_select_rerank_f64(cb, P, n, dim, ldp, Q, nq, ldq, kout, base, io, dd, os, flags, nf, qn, qbad, sel, st,
-                                        s, fe, cm);
-    }
-    static hipError_t rerank_cos(const CandBuf &cb, const double *P, size_t n, int dim, size_t ldp, const double *Q, int nq,
-                                 size_t ldq, int kout, uint64_t base, uint64_t *io, double *dd, size_t os, uint32_t *flags,
-                                 uint32_t *nf, const double *qn, const uint32_t *qbad, uint32_t *sel, unsigned long long *st,
-                                 hipStream_t s, int fe, int cm, const double *cn, const double *qnorm) {
-        return launch_select_rerank_cos_f64(cb, P, n, dim, ldp, Q, nq, ldq, kout, base, io, dd, os, flags, nf, qn, qbad, sel,
-                                            st, s, fe, cm, cn, qnorm);
-    }
-    static hipError_t pack(const double *s, size_t n, size_t c, size_t rs, double *d, size_t np, size_t ld, hipStream_t st) {
-        return launch_pack_rows_f64(s, n, c, rs, d, np, ld, st);
-    }
-    static hipError_t knn(const double *P, size_t n, int dim, size_t ldp, const double *Q, int nq, size_t ldq, int kp,
-                          size_t seg_len, const CandBuf &cb, const void *lk, const uint32_t *li, const uint32_t *nd,
-                          uint32_t no, const double *pn, const double *qn, hipStream_t s, const uint32_t *qsel = nullptr) {
-        return launch_exact_knn_f64(P, n, dim, ldp, Q, nq, ldq, kp, seg_len, cb, lk, li, nd, no, pn, qn, s, qsel);
-    }
-    static hipError_t cnorms(const double *X, size_t n, int dim, size_t ld, double *o, hipStream_t s) {
-        return launch_cosine_norms_f64(X, n, dim, ld, o, s);
-    }
-    static hipError_t select(const CandBuf &cb, int nq, int kout, uint64_t base, uint64_t *io, double *dd, size_t os,
-                             size_t oo, void *lk, uint32_t *li, const uint32_t *nd, uint32_t no, bool sk, hipStream_t s,
-                             const uint32_t *osel = nullptr) {
-        return launch_select_exact_f64(cb, nq, kout, base, io, dd, os, oo, lk, li, nd, no, sk, s, osel);
-    }
-    static hipError_t select_groups(const CandBuf &cb, int groups, int kp, int nq, int kout, uint64_t base, uint64_t *io,
-                                    double *dd, size_t gs, const uint32_t *nd, uint32_t no, hipStream_t s, bool sk = false) {
-        return launch_select_exact_groups_f64(cb, groups, kp, nq, kout, base, io, dd, gs, nd, no, s, sk);
-    }
-    static hipError_t merge(const uint64_t *pi, const double *pd, int np, size_t is, size_t ds, int nq, int kp, int ko,
-                            uint64_t *io, double *dd, hipStream_t s, const uint32_t *nd, const uint32_t *osel, size_t os,
-                            uint32_t *hc, bool sk = false) {
-        return launch_merge_topk_f64(pi, pd, np, is, ds, nq, kp, ko, io, dd, s, nd, osel, os, hc, sk);
-    }
-};
-
 // exact engine on packed queries Qp [nq_pad][ld]; results of query q to d_idx/d_dist[q * out_stride + r], r < kout.
 // second_tier: the queries are the ones a filter tier flagged -- their number lives on the device (nq_dev, of which
 // this round covers [nq_off, nq_off + nq)), the grids are sized for nq and surplus query tiles exit at once; few
@@ -1229,12 +1165,12 @@ static int run_exact(const pn_index *ix, Workspace &ws, const T *Qp, size_t nq, 
     }
     for (size_t done = 0; done < kout; done += kRound) {
         const size_t kr = kout - done < kRound ? kout - done : kRound;
-        HIPCHK(Ops<T>::knn((const T *)ix->d_pts, ix->n, dim_eff, ix->ld, Qp, (int)nq, ix->ld, (int)kr, pl.seg_len, cb,
-                           done ? lo_key : nullptr, done ? lo_idx : nullptr, nq_dev, nq_off,
-                           qnorm ? (const T *)ix->d_cnorm : nullptr, qnorm, s, rowsel));
+        HIPCHK(launch_exact_knn<T>((const T *)ix->d_pts, ix->n, dim_eff, ix->ld, Qp, (int)nq, ix->ld, (int)kr, pl.seg_len, cb,
+                                   done ? lo_key : nullptr, done ? lo_idx : nullptr, nq_dev, nq_off,
+                                   qnorm ? (const T *)ix->d_cnorm : nullptr, qnorm, s, rowsel));
         if (prof && done == 0) HIPCHK(hipEventRecord(rec->ev[1], s));
-        HIPCHK(Ops<T>::select(cb, (int)nq, (int)kr, ix->index_base, d_idx, d_dist, out_stride, done, lo_key, lo_idx,
-                              nq_dev, nq_off, qnorm != nullptr, s, rowsel));
+        HIPCHK(launch_select_exact<T>(cb, (int)nq, (int)kr, ix->index_base, d_idx, d_dist, out_stride, done, lo_key, lo_idx,
+                                      nq_dev, nq_off, qnorm != nullptr, s, rowsel));
     }
     return PN_OK;
 }
@@ -1284,15 +1220,15 @@ static int second_tier_exact(const pn_index *ix, Workspace &ws, const T *Qp, siz
         uint64_t *p_idx = (uint64_t *)ws.w_fparts.p;
         T *p_dist = (T *)(p_idx + groups * Ff_pad * kout);
         CandBuf cb{ws.w2_keys.p, (uint32_t *)ws.w2_idx.p, (uint32_t *)ws.w2_cnt.p, ws.w2_tau.p, Ff_pad, (int)nseg, cap};
-        HIPCHK(Ops<T>::knn((const T *)ix->d_pts, ix->n, (int)ix->dim, ix->ld, Qp, (int)Ff, ix->ld, (int)kout, seg_len, cb,
-                           nullptr, nullptr, d_nsel, 0, cosq ? (const T *)ix->d_cnorm : nullptr, qnorm, s, d_sel));
+        HIPCHK(launch_exact_knn<T>((const T *)ix->d_pts, ix->n, (int)ix->dim, ix->ld, Qp, (int)Ff, ix->ld, (int)kout, seg_len,
+                                   cb, nullptr, nullptr, d_nsel, 0, cosq ? (const T *)ix->d_cnorm : nullptr, qnorm, s, d_sel));
         CandBuf cg = cb;
         cg.nseg = 16;
         // (index_base is added by the group selection; the merge orders the parts' GLOBAL indices)
-        HIPCHK(Ops<T>::select_groups(cg, (int)groups, (int)kout, (int)Ff, (int)kout, ix->index_base, p_idx, p_dist,
-                                     Ff_pad * kout, d_nsel, 0, s, cosq));
-        HIPCHK(Ops<T>::merge(p_idx, p_dist, (int)groups, Ff_pad * kout, Ff_pad * kout, (int)Ff, (int)kout, (int)kout, d_idx,
-                             d_dist, s, d_nsel, d_sel, out_stride, h_count, cosq));
+        HIPCHK(launch_select_exact_groups<T>(cg, (int)groups, (int)kout, (int)Ff, (int)kout, ix->index_base, p_idx, p_dist,
+                                             Ff_pad * kout, d_nsel, 0, s, cosq));
+        HIPCHK(launch_merge_topk<T>(p_idx, p_dist, (int)groups, Ff_pad * kout, Ff_pad * kout, (int)Ff, (int)kout, (int)kout,
+                                    d_idx, d_dist, s, d_nsel, d_sel, out_stride, h_count, cosq));
         *count_published = h_count != nullptr;
         first = Ff;
     }
@@ -2015,9 +1951,9 @@ static int run_mfma(const pn_index *ix, Workspace &ws, const MfmaPlan &plan, con
     HIPCHK(launch_mfma_filter_v2_f32((const float *)ix->d_pts, ix->d_norm, ix->n, ix->ld, Qp, (const float *)ws.w_qnorm.p,
                                      ix->ld, (int)kp, cb, n_wg, gcand, s));
     if (prof) HIPCHK(hipEventRecord(rec->ev[1], s));
-    HIPCHK(launch_select_rerank_f32(cb, (const float *)ix->d_pts, ix->n, (int)ix->dim, ix->ld, Qp, (int)nq, ix->ld,
-                                    (int)kout, ix->index_base, d_idx, d_dist, out_stride, (uint32_t *)ws.w_flags.p,
-                                    d_misc, nullptr, nullptr, (uint32_t *)ws.w_gsel.p, ix->d_stats, s, 0, plan.kp));
+    HIPCHK(launch_select_rerank<float>(cb, (const float *)ix->d_pts, ix->n, (int)ix->dim, ix->ld, Qp, (int)nq, ix->ld,
+                                       (int)kout, ix->index_base, d_idx, d_dist, out_stride, (uint32_t *)ws.w_flags.p, d_misc,
+                                       nullptr, nullptr, (uint32_t *)ws.w_gsel.p, ix->d_stats, s, 0, plan.kp));
     return PN_OK;
 }
 
@@ -2155,16 +2091,16 @@ static int run_bf16(const pn_index *ix, Workspace &ws, const Bf16Plan &plan, con
     }
     if (prof) HIPCHK(hipEventRecord(rec->ev[1], s));
     if (cosine) {
-        HIPCHK(Ops<T>::rerank_cos(cb, (const T *)ix->d_pts, ix->n, (int)ix->dim, ix->ld, Qp, (int)nq, ix->ld, (int)kout,
-                                  ix->index_base, d_idx, d_dist, out_stride, (uint32_t *)ws.w_flags.p, d_misc,
-                                  (const double *)ws.w_qn.p, (const uint32_t *)ws.w_qbad.p, (uint32_t *)ws.w_gsel.p,
-                                  ix->d_stats, s, plan.first_eval, cb.final_keep, (const T *)ix->d_cnorm, qnorm));
+        HIPCHK(launch_select_rerank<T>(cb, (const T *)ix->d_pts, ix->n, (int)ix->dim, ix->ld, Qp, (int)nq, ix->ld, (int)kout,
+                                       ix->index_base, d_idx, d_dist, out_stride, (uint32_t *)ws.w_flags.p, d_misc,
+                                       (const double *)ws.w_qn.p, (const uint32_t *)ws.w_qbad.p, (uint32_t *)ws.w_gsel.p,
+                                       ix->d_stats, s, plan.first_eval, cb.final_keep, (const T *)ix->d_cnorm, qnorm));
         return PN_OK;
     }
-    HIPCHK(Ops<T>::rerank(cb, (const T *)ix->d_pts, ix->n, (int)ix->dim, ix->ld, Qp, (int)nq, ix->ld, (int)kout,
-                          ix->index_base, d_idx, d_dist, out_stride, (uint32_t *)ws.w_flags.p, d_misc,
-                          (const double *)ws.w_qn.p, (const uint32_t *)ws.w_qbad.p, (uint32_t *)ws.w_gsel.p, ix->d_stats, s,
-                          plan.first_eval, cb.final_keep));
+    HIPCHK(launch_select_rerank<T>(cb, (const T *)ix->d_pts, ix->n, (int)ix->dim, ix->ld, Qp, (int)nq, ix->ld, (int)kout,
+                                   ix->index_base, d_idx, d_dist, out_stride, (uint32_t *)ws.w_flags.p, d_misc,
+                                   (const double *)ws.w_qn.p, (const uint32_t *)ws.w_qbad.p, (uint32_t *)ws.w_gsel.p,
+                                   ix->d_stats, s, plan.first_eval, cb.final_keep));
     return PN_OK;
 }
 
@@ -2204,7 +2140,7 @@ static int query_enqueue(const pn_index *ix, Workspace &ws, const T *d_q, size_t
         if (ix->metric == 1) {  // Cosine: each query's norm over ITS OWN length (src/distance.rs:92-97), not the zip's
             PNCHK(ws.w_qnorm.ensure(nq_pad * sizeof(T)));
             HIPCHK(hipMemsetAsync(ws.w_qnorm.p, 0, nq_pad * sizeof(T), s));
-            HIPCHK(Ops<T>::cnorms(d_q + qs * q_stride, nqc, (int)q_cols, q_stride, (T *)ws.w_qnorm.p, s));
+            HIPCHK(launch_cosine_norms<T>(d_q + qs * q_stride, nqc, (int)q_cols, q_stride, (T *)ws.w_qnorm.p, s));
             qnorm = (const T *)ws.w_qnorm.p;
         }
         if constexpr (sizeof(T) == 4) {
@@ -2231,7 +2167,7 @@ static int query_enqueue(const pn_index *ix, Workspace &ws, const T *d_q, size_t
         // the head of the call: the zero-padded copy of the queries (+ the call's counters, zeroed) -- for narrow rows
         // on the bf16 tier both are by-products of the tier's own query pack kernel (run_bf16)
         const bool fused_head = use_bf16 && !bplan.wide && ix->metric != 1 && bf16_pack_fused_supported((int)ix->dim);
-        if (!fused_head) HIPCHK(Ops<T>::pack(d_q + qs * q_stride, nqc, dim_eff, q_stride, Qp, nq_pad, ix->ld, s));
+        if (!fused_head) HIPCHK(launch_pack_rows<T>(d_q + qs * q_stride, nqc, dim_eff, q_stride, Qp, nq_pad, ix->ld, s));
         if (use_bf16 || use_mfma) {
             PNCHK(ws.w_misc.ensure(64));
             if (!fused_head) HIPCHK(hipMemsetAsync(ws.w_misc.p, 0, 64, s));
@@ -2271,14 +2207,9 @@ static int query_device_impl(const pn_index *ix, const T *d_q, size_t nq, size_t
     if (!d_q && q_cols) return fail(PN_ERR_INVALID, "queries is NULL");
     if (!d_idx || !d_dist) return fail(PN_ERR_INVALID, "output buffer is NULL");
     if (nq > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many queries in one call");
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    // s == NULL is HIP's default stream (what torch.cuda.current_stream() is unless changed): work is
-    // ordered with the caller's other default-stream work, as a caller of a *_device entry point expects
-    WsLease lease(ix);
-    lease.s = s;
-    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
-    return query_enqueue<T>(ix, *lease.ws, d_q, nq, q_cols, q_stride, kout, d_idx, d_dist, kout, s);
+    CallScope call(ix);
+    PNCHK(call.on_stream(s));
+    return query_enqueue<T>(ix, call.ws(), d_q, nq, q_cols, q_stride, kout, d_idx, d_dist, kout, s);
 }
 
 namespace pn {
@@ -2293,12 +2224,9 @@ static int query_device_strided_impl(const pn_index *ix, const T *d_q, size_t nq
     if (nq == 0 || kout == 0) return PN_OK;
     if ((!d_q && q_cols) || !d_idx || !d_dist || out_stride < kout) return fail(PN_ERR_INVALID, "bad argument");
     if (nq > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many queries in one call");
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    lease.s = s;
-    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
-    return query_enqueue<T>(ix, *lease.ws, d_q, nq, q_cols, q_stride, kout, d_idx, d_dist, out_stride, s);
+    CallScope call(ix);
+    PNCHK(call.on_stream(s));
+    return query_enqueue<T>(ix, call.ws(), d_q, nq, q_cols, q_stride, kout, d_idx, d_dist, out_stride, s);
 }
 int query_device_strided_f32(const pn_index *ix, const float *d_q, size_t nq, size_t q_cols, size_t q_stride, size_t k,
                              uint64_t *d_idx, float *d_dist, size_t out_stride, hipStream_t s) {
@@ -2379,12 +2307,8 @@ static bool tiny_eligible(const pn_index *ix, size_t nq, size_t dim_eff) {
 template <typename T>
 static hipError_t tiny_launch(const pn_index *ix, size_t dim_eff, const T *Qd, size_t ldq, size_t nq, size_t kout, bool rad,
                               T radius, uint64_t *io, T *dd, size_t os, hipStream_t s) {
-    if constexpr (sizeof(T) == 4)
-        return launch_tiny_query_f32((const float *)ix->d_pts, ix->n, (int)dim_eff, ix->ld, Qd, ldq, (int)nq, (int)kout, rad,
-                                     radius, ix->index_base, io, dd, os, s);
-    else
-        return launch_tiny_query_f64((const double *)ix->d_pts, ix->n, (int)dim_eff, ix->ld, Qd, ldq, (int)nq, (int)kout, rad,
-                                     radius, ix->index_base, io, dd, os, s);
+    return launch_tiny_query<T>((const T *)ix->d_pts, ix->n, (int)dim_eff, ix->ld, Qd, ldq, (int)nq, (int)kout, rad, radius,
+                                ix->index_base, io, dd, os, s);
 }
 // stages the queries in the workspace's pinned input buffer; *Qd = its device address
 template <typename T>
@@ -2467,12 +2391,10 @@ static int query_host_impl(const pn_index *ix, const T *q, size_t nq, size_t q_c
     if (!q && q_cols) return fail(PN_ERR_INVALID, "queries is NULL");
     if (!idx_out || !dist_out) return fail(PN_ERR_INVALID, "output buffer is NULL");
     if (nq > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many queries in one call");
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
-    Workspace &ws = *lease.ws;
-    hipStream_t s = lease.s;
+    CallScope call(ix);
+    PNCHK(call.own_stream());
+    Workspace &ws = call.ws();
+    hipStream_t s = call.s();
     if (q_stride >= 0 && tiny_eligible<T>(ix, nq, q_cols < ix->dim ? q_cols : ix->dim))
         return tiny_knn<T>(ix, ws, s, q, nq, q_cols, q_stride, kout, idx_out, dist_out);
     // a small batch against a large corpus: the kernels read the queries from, and write the answers to, mapped pinned
@@ -2564,12 +2486,10 @@ extern "C" int pn_bf16_bounds_f32(const pn_index *ix, const float *q, size_t nq,
     if (nq == 0 || n_rows == 0) return PN_OK;
     if (n_rows > ix->n) n_rows = ix->n;
     if (nq * n_rows > ((size_t)1 << 28)) return fail(PN_ERR_INVALID, "too many bounds requested");
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
-    Workspace &ws = *lease.ws;
-    hipStream_t s = lease.s;
+    CallScope call(ix);
+    PNCHK(call.own_stream());
+    Workspace &ws = call.ws();
+    hipStream_t s = call.s();
     float *d_q = nullptr, *d_out = nullptr;
     int rc = upload_rows<float>(q, nq, q_cols, q_stride, &d_q);
     do {
@@ -2585,7 +2505,7 @@ extern "C" int pn_bf16_bounds_f32(const pn_index *ix, const float *q, size_t nq,
             break;
         }
         float *Qp = (float *)ws.w_q.p;
-        if (launch_pack_rows_f32(d_q, nq, ix->dim, q_cols, Qp, nq_pad, ix->ld, s) != hipSuccess ||
+        if (launch_pack_rows<float>(d_q, nq, ix->dim, q_cols, Qp, nq_pad, ix->ld, s) != hipSuccess ||
             launch_bf16_pack_queries(Qp, ix->d_mu, nq, nq_pad, (int)ix->dim, ix->ld, ws.w_bq.p, (double *)ws.w_qn.p,
                                      (uint32_t *)ws.w_qbad.p, ix->bf16_ci, ix->bf16_bmax, ix->bf16_dmax, s) != hipSuccess ||
             launch_bf16_bound(ix->d_img, ws.w_bq.p, n_rows, nq, (int)ix->dim, d_out, ix->bf16_ci, s) != hipSuccess ||
@@ -2606,28 +2526,6 @@ extern "C" int pn_bf16_bounds_f32(const pn_index *ix, const float *q, size_t nq,
 // ---------------------------------------------------------------------------
 // radius (two-pass CSR on the exact engine)
 // ---------------------------------------------------------------------------
-template <typename T> struct RadOps;
-template <> struct RadOps<float> {
-    static hipError_t run(const float *P, size_t n, int dim, size_t ldp, const float *Q, int nq, size_t ldq, float r,
-                          size_t seg_len, int nseg, uint32_t *counts, const uint64_t *offs, uint64_t *fill,
-                          uint64_t base, const float *pn, const float *qn, hipStream_t s, const uint32_t *qsel = nullptr,
-                          const uint32_t *nq_dev = nullptr, uint64_t capacity = ~0ull, float *fill_dist = nullptr,
-                          const float *radii = nullptr) {
-        return launch_exact_radius_f32(P, n, dim, ldp, Q, nq, ldq, r, seg_len, nseg, counts, offs, fill, base, pn, qn, s, qsel,
-                                       nq_dev, capacity, fill_dist, radii);
-    }
-};
-template <> struct RadOps<double> {
-    static hipError_t run(const double *P, size_t n, int dim, size_t ldp, const double *Q, int nq, size_t ldq, double r,
-                          size_t seg_len, int nseg, uint32_t *counts, const uint64_t *offs, uint64_t *fill,
-                          uint64_t base, const double *pn, const double *qn, hipStream_t s, const uint32_t *qsel = nullptr,
-                          const uint32_t *nq_dev = nullptr, uint64_t capacity = ~0ull, double *fill_dist = nullptr,
-                          const double *radii = nullptr) {
-        return launch_exact_radius_f64(P, n, dim, ldp, Q, nq, ldq, r, seg_len, nseg, counts, offs, fill, base, pn, qn, s, qsel,
-                                       nq_dev, capacity, fill_dist, radii);
-    }
-};
-
 // PN_RADIUS_SORTED: every list of the CSR (d_off [nq + 1], d_idx / d_dist on the device) that ends at or below `limit`
 // ordered by (distance, index) in place, on stream s (csr_sort.hip); scratch from the workspace
 template <typename T>
@@ -2648,10 +2546,7 @@ static int csr_sort_dev(const pn_index *ix, Workspace &ws, const uint64_t *d_off
         w.idx = (uint64_t *)ws.w_cs_idx.p;
         w.dist = ws.w_cs_dist.p;
     }
-    if constexpr (sizeof(T) == 4)
-        HIPCHK(launch_csr_sort_f32(d_off, (int)nq, d_idx, d_dist, limit, ix->n, w, ix->n_cu, s));
-    else
-        HIPCHK(launch_csr_sort_f64(d_off, (int)nq, d_idx, d_dist, limit, ix->n, w, ix->n_cu, s));
+    HIPCHK(launch_csr_sort<T>(d_off, (int)nq, d_idx, d_dist, limit, ix->n, w, ix->n_cu, s));
     return PN_OK;
 }
 // the host entry point's answer (host arrays) sorted on the device: up, csr_sort_dev, down (through the workspace's
@@ -2706,9 +2601,9 @@ static int radius_exact(const pn_index *ix, Workspace &ws, const T *Qp, size_t n
             break;
         }
         if (hipMemsetAsync(d_counts, 0, cells * 4, s) != hipSuccess ||
-            RadOps<T>::run((const T *)ix->d_pts, ix->n, (int)dim_eff, ix->ld, Qp, (int)nq, ix->ld, radius, pl.seg_len,
-                           pl.nseg, d_counts, nullptr, nullptr, ix->index_base, qnorm ? (const T *)ix->d_cnorm : nullptr,
-                           qnorm, s) != hipSuccess) {
+            launch_exact_radius<T>((const T *)ix->d_pts, ix->n, (int)dim_eff, ix->ld, Qp, (int)nq, ix->ld, radius, pl.seg_len,
+                                   pl.nseg, d_counts, nullptr, nullptr, ix->index_base,
+                                   qnorm ? (const T *)ix->d_cnorm : nullptr, qnorm, s) != hipSuccess) {
             rc = fail(PN_ERR_DEVICE, "radius count pass failed: %s", hipGetErrorString(hipGetLastError()));
             break;
         }
@@ -2747,9 +2642,9 @@ static int radius_exact(const pn_index *ix, Workspace &ws, const T *Qp, size_t n
             break;
         }
         if (hipMemcpyAsync(d_offs, h_offs.data(), cells * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
-            RadOps<T>::run((const T *)ix->d_pts, ix->n, (int)dim_eff, ix->ld, Qp, (int)nq, ix->ld, radius, pl.seg_len,
-                           pl.nseg, d_counts, d_offs, d_fill, ix->index_base, qnorm ? (const T *)ix->d_cnorm : nullptr, qnorm,
-                           s, nullptr, nullptr, ~0ull, d_fill_d) != hipSuccess ||
+            launch_exact_radius<T>((const T *)ix->d_pts, ix->n, (int)dim_eff, ix->ld, Qp, (int)nq, ix->ld, radius, pl.seg_len,
+                                   pl.nseg, d_counts, d_offs, d_fill, ix->index_base, qnorm ? (const T *)ix->d_cnorm : nullptr,
+                                   qnorm, s, nullptr, nullptr, ~0ull, d_fill_d) != hipSuccess ||
             hipMemcpyAsync(h_out, d_fill, run * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
             (dout && hipMemcpyAsync(*dout, d_fill_d, run * sizeof(T), hipMemcpyDeviceToHost, s) != hipSuccess) ||
             hipStreamSynchronize(s) != hipSuccess) {
@@ -2854,7 +2749,7 @@ static int radius_finish(const pn_index *ix, Workspace &ws, const T *Qp, size_t 
         const T *gqnorm = nullptr;
         if (rc == PN_OK && cosine) {  // a Cosine index: the gathered queries' norms (their rows are dim long: over the row)
             if (ws.w_gqn.ensure(nf_pad * sizeof(T)) != PN_OK || hipMemsetAsync(ws.w_gqn.p, 0, nf_pad * sizeof(T), s) != hipSuccess ||
-                Ops<T>::cnorms((const T *)ws.w_gq.p, nf, (int)ix->dim, ix->ld, (T *)ws.w_gqn.p, s) != hipSuccess)
+                launch_cosine_norms<T>((const T *)ws.w_gq.p, nf, (int)ix->dim, ix->ld, (T *)ws.w_gqn.p, s) != hipSuccess)
                 rc = fail(PN_ERR_DEVICE, "radius fallback query norms failed");
             gqnorm = (const T *)ws.w_gqn.p;
         }
@@ -3107,12 +3002,10 @@ static int radius_host_impl(const pn_index *ix, const T *q, size_t nq, size_t q_
     if (nq == 0) return PN_OK;
     if (!q && q_cols) return fail(PN_ERR_INVALID, "queries is NULL");
     if (nq > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many queries in one call");
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
-    Workspace &ws = *lease.ws;
-    hipStream_t s = lease.s;
+    CallScope call(ix);
+    PNCHK(call.own_stream());
+    Workspace &ws = call.ws();
+    hipStream_t s = call.s();
     int level;
     {
         std::lock_guard<std::mutex> lk(ix->sh.mu);
@@ -3149,7 +3042,7 @@ static int radius_host_tiers(const pn_index *ix, Workspace &ws, hipStream_t s, i
         rc = ws.w_q.ensure(nq_pad * ix->ld * sizeof(T));
         if (rc != PN_OK) break;
         T *Qp = (T *)ws.w_q.p;
-        if (Ops<T>::pack((const T *)ws.w_hq.p, nq, dim_eff, q_cols ? q_cols : 1, Qp, nq_pad, ix->ld, s) != hipSuccess) {
+        if (launch_pack_rows<T>((const T *)ws.w_hq.p, nq, dim_eff, q_cols ? q_cols : 1, Qp, nq_pad, ix->ld, s) != hipSuccess) {
             rc = fail(PN_ERR_DEVICE, "pack failed");
             break;
         }
@@ -3159,7 +3052,8 @@ static int radius_host_tiers(const pn_index *ix, Workspace &ws, hipStream_t s, i
             rc = ws.w_qnorm.ensure(nq_pad * sizeof(T));
             if (rc != PN_OK) break;
             if (hipMemsetAsync(ws.w_qnorm.p, 0, nq_pad * sizeof(T), s) != hipSuccess ||
-                Ops<T>::cnorms((const T *)ws.w_hq.p, nq, (int)q_cols, q_cols ? q_cols : 1, (T *)ws.w_qnorm.p, s) != hipSuccess) {
+                launch_cosine_norms<T>((const T *)ws.w_hq.p, nq, (int)q_cols, q_cols ? q_cols : 1, (T *)ws.w_qnorm.p,
+                                       s) != hipSuccess) {
                 rc = fail(PN_ERR_DEVICE, "query norms failed");
                 break;
             }
@@ -3254,17 +3148,15 @@ static int radius_device_impl(const pn_index *ix, const T *d_q, size_t nq, size_
     if (!capacity) d_dist = nullptr;  // (a pure count)
     if (!d_q && q_cols && nq) return fail(PN_ERR_INVALID, "queries is NULL");
     if (nq > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many queries in one call");
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    CallScope call(ix);
+    PNCHK(call.guard());
     if (nq == 0) {
         HIPCHK(hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), s));
         if (d_total) HIPCHK(hipMemsetAsync(d_total, 0, sizeof(uint64_t), s));
         return PN_OK;
     }
-    WsLease lease(ix);
-    lease.s = s;
-    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
-    return radius_device_enqueue<T>(ix, *lease.ws, d_q, nq, q_cols, q_stride, radius, d_offsets, d_idx, capacity, d_total,
+    PNCHK(call.on_stream(s));
+    return radius_device_enqueue<T>(ix, call.ws(), d_q, nq, q_cols, q_stride, radius, d_offsets, d_idx, capacity, d_total,
                                     s, d_dist, flags, true, d_radii, d_radii != nullptr);
 }
 // the pipeline of radius_device_impl in a workspace the caller holds (also the self-queries' inner call); nq >= 1,
@@ -3290,12 +3182,12 @@ static int radius_device_enqueue(const pn_index *ix, Workspace &ws, const T *d_q
     const size_t nq_pad = round_up(nq, (size_t)256);
     PNCHK(ws.w_q.ensure(nq_pad * ix->ld * sizeof(T)));
     T *Qp = (T *)ws.w_q.p;
-    HIPCHK(Ops<T>::pack(d_q, nq, dim_eff, q_stride, Qp, nq_pad, ix->ld, s));
+    HIPCHK(launch_pack_rows<T>(d_q, nq, dim_eff, q_stride, Qp, nq_pad, ix->ld, s));
     const T *qnorm = nullptr;
     if (ix->metric == 1) {  // Cosine: the queries' norms over their own length
         PNCHK(ws.w_qnorm.ensure(nq_pad * sizeof(T)));
         HIPCHK(hipMemsetAsync(ws.w_qnorm.p, 0, nq_pad * sizeof(T), s));
-        HIPCHK(Ops<T>::cnorms(d_q, nq, (int)q_cols, q_stride, (T *)ws.w_qnorm.p, s));
+        HIPCHK(launch_cosine_norms<T>(d_q, nq, (int)q_cols, q_stride, (T *)ws.w_qnorm.p, s));
         qnorm = (const T *)ws.w_qnorm.p;
     }
     // ---- first tier (enqueue only)
@@ -3330,18 +3222,18 @@ static int radius_device_enqueue(const pn_index *ix, Workspace &ws, const T *d_q
     PNCHK(ws.w_rfin.ensure(nq_pad * sizeof(uint32_t)));
     PNCHK(ws.w_rscan.ensure((nq / 4096 + 2) * sizeof(uint64_t)));
     const T *pn = qnorm ? (const T *)ix->d_cnorm : nullptr;
-    HIPCHK(RadOps<T>::run((const T *)ix->d_pts, ix->n, (int)dim_eff, ix->ld, Qp, (int)nq, ix->ld, radius, pl.seg_len, pl.nseg,
-                          (uint32_t *)ws.w_rcx.p, nullptr, nullptr, ix->index_base, pn, qnorm, s, d_sel, d_nsel, ~0ull,
-                          nullptr, d_radii));
+    HIPCHK(launch_exact_radius<T>((const T *)ix->d_pts, ix->n, (int)dim_eff, ix->ld, Qp, (int)nq, ix->ld, radius, pl.seg_len,
+                                  pl.nseg, (uint32_t *)ws.w_rcx.p, nullptr, nullptr, ix->index_base, pn, qnorm, s, d_sel,
+                                  d_nsel, ~0ull, nullptr, d_radii));
     HIPCHK(launch_rad_counts(d_nkept, d_pos, (const uint32_t *)ws.w_rcx.p, pl.nseg, (int)nq, (uint32_t *)ws.w_rfin.p, s));
     HIPCHK(launch_exclusive_scan_u32((const uint32_t *)ws.w_rfin.p, nq, d_offsets, (uint64_t *)ws.w_rscan.p, d_total, s));
     HIPCHK(launch_rad_seg_offsets(d_offsets, d_sel, d_nsel, (int)nq, (const uint32_t *)ws.w_rcx.p, pl.nseg,
                                   (uint64_t *)ws.w_rox.p, s));
     // (a fill pass needs a buffer to fill: with capacity 0 the call is a pure count)
     if (capacity) {
-        HIPCHK(RadOps<T>::run((const T *)ix->d_pts, ix->n, (int)dim_eff, ix->ld, Qp, (int)nq, ix->ld, radius, pl.seg_len,
-                              pl.nseg, (uint32_t *)ws.w_rcx.p, (const uint64_t *)ws.w_rox.p, d_idx, ix->index_base, pn, qnorm,
-                              s, d_sel, d_nsel, (uint64_t)capacity, d_dist, d_radii));
+        HIPCHK(launch_exact_radius<T>((const T *)ix->d_pts, ix->n, (int)dim_eff, ix->ld, Qp, (int)nq, ix->ld, radius,
+                                      pl.seg_len, pl.nseg, (uint32_t *)ws.w_rcx.p, (const uint64_t *)ws.w_rox.p, d_idx,
+                                      ix->index_base, pn, qnorm, s, d_sel, d_nsel, (uint64_t)capacity, d_dist, d_radii));
         if (filtered)
             HIPCHK(launch_radius_gather_cap((const uint32_t *)ws.w_keys.p, d_nkept, d_offsets, (int)nq, kept_stride,
                                             ix->index_base, d_idx, (uint64_t)capacity, s,
@@ -3420,10 +3312,7 @@ static int self_knn_chunk(const pn_index *ix, Workspace &ws, size_t r0, size_t n
     uint64_t *si = (uint64_t *)ws.w_sf_idx.p;
     T *sd = (T *)ws.w_sf_dist.p;
     PNCHK(query_enqueue<T>(ix, ws, rows, nqc, ix->dim, ix->ld, kin, si, sd, kin, s));
-    if constexpr (sizeof(T) == 4)
-        HIPCHK(launch_knn_self_exclude_f32(si, sd, nqc, (int)kin, (int)kout, ix->index_base + r0, oi, od, s));
-    else
-        HIPCHK(launch_knn_self_exclude_f64(si, sd, nqc, (int)kin, (int)kout, ix->index_base + r0, oi, od, s));
+    HIPCHK(launch_knn_self_exclude<T>(si, sd, nqc, (int)kin, (int)kout, ix->index_base + r0, oi, od, s));
     return PN_OK;
 }
 template <typename T>
@@ -3435,14 +3324,11 @@ static int self_knn_device(const pn_index *ix, size_t k, unsigned flags, uint64_
     self_knn_sizes(ix, k, include, &kin, &kout);
     if (kout == 0) return PN_OK;  // k = 0, or a single row without itself: nothing to write
     if (kin > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "k too large");
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    lease.s = s;
-    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
+    CallScope call(ix);
+    PNCHK(call.on_stream(s));
     for (size_t r0 = 0; r0 < ix->n; r0 += kSelfChunk) {
         const size_t nqc = ix->n - r0 < kSelfChunk ? ix->n - r0 : kSelfChunk;
-        PNCHK(self_knn_chunk<T>(ix, *lease.ws, r0, nqc, kin, kout, include, d_idx + r0 * kout, d_dist + r0 * kout, s));
+        PNCHK(self_knn_chunk<T>(ix, call.ws(), r0, nqc, kin, kout, include, d_idx + r0 * kout, d_dist + r0 * kout, s));
     }
     return PN_OK;
 }
@@ -3456,12 +3342,10 @@ static int self_knn_host(const pn_index *ix, size_t k, unsigned flags, uint64_t 
     self_knn_sizes(ix, k, include, &kin, &kout);
     if (kout == 0) return PN_OK;
     if (kin > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "k too large");
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
-    Workspace &ws = *lease.ws;
-    hipStream_t s = lease.s;
+    CallScope call(ix);
+    PNCHK(call.own_stream());
+    Workspace &ws = call.ws();
+    hipStream_t s = call.s();
     for (size_t r0 = 0; r0 < ix->n; r0 += kSelfChunk) {
         const size_t nqc = ix->n - r0 < kSelfChunk ? ix->n - r0 : kSelfChunk;
         PNCHK(ws.w_hidx.ensure(nqc * kout * sizeof(uint64_t)));
@@ -3537,21 +3421,13 @@ static int radius_self_enqueue(const pn_index *ix, Workspace &ws, T radius, unsi
         PNCHK(radius_device_enqueue<T>(ix, ws, rows, nqc, ix->dim, ix->ld, radius, in_off, in_idx, in_cap, nullptr, s,
                                        in_dist, 0, count_queries, rad, rad && count_queries));
         const T *cn = cn_all ? cn_all + r0 : nullptr;
-        if constexpr (sizeof(T) == 4)
-            HIPCHK(launch_radius_self_counts_f32(rows, nqc, (int)ix->dim, ix->ld, cn, radius, exclude, in_off, flag, cnt, bad, s,
-                                                 rad));
-        else
-            HIPCHK(launch_radius_self_counts_f64(rows, nqc, (int)ix->dim, ix->ld, cn, radius, exclude, in_off, flag, cnt, bad, s,
-                                                 rad));
+        HIPCHK(launch_radius_self_counts<T>(rows, nqc, (int)ix->dim, ix->ld, cn, radius, exclude, in_off, flag, cnt, bad, s,
+                                            rad));
         HIPCHK(launch_exclusive_scan_u32(cnt, nqc, part, (uint64_t *)ws.w_sf_scan.p, nullptr, s));
         HIPCHK(launch_radius_self_place(part, nqc, d_offsets + r0, s));
         if (!capacity) continue;
-        if constexpr (sizeof(T) == 4)
-            HIPCHK(launch_radius_self_compact_f32(in_off, in_idx, in_dist, in_cap, flag, d_offsets + r0, nqc,
-                                                  ix->index_base + r0, d_idx, d_dist, capacity, bad, s));
-        else
-            HIPCHK(launch_radius_self_compact_f64(in_off, in_idx, in_dist, in_cap, flag, d_offsets + r0, nqc,
-                                                  ix->index_base + r0, d_idx, d_dist, capacity, bad, s));
+        HIPCHK(launch_radius_self_compact<T>(in_off, in_idx, in_dist, in_cap, flag, d_offsets + r0, nqc, ix->index_base + r0,
+                                             d_idx, d_dist, capacity, bad, s));
     }
     if (d_total) HIPCHK(hipMemcpyAsync(d_total, d_offsets + n, sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
     if (capacity && d_dist && (flags & PN_RADIUS_SORTED))
@@ -3572,12 +3448,9 @@ static int radius_self_device(const pn_index *ix, T radius, unsigned flags, uint
     PNCHK(radius_self_args(ix, flags, d_offsets != nullptr, d_idx != nullptr || !capacity, d_dist != nullptr || !capacity,
                            (int)sizeof(T)));
     if (ix->n > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many rows for one self-query");
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    lease.s = s;
-    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
-    return radius_self_enqueue<T>(ix, *lease.ws, radius, flags, d_offsets, d_idx, d_dist, capacity, d_total, s, true, d_radii);
+    CallScope call(ix);
+    PNCHK(call.on_stream(s));
+    return radius_self_enqueue<T>(ix, call.ws(), radius, flags, d_offsets, d_idx, d_dist, capacity, d_total, s, true, d_radii);
 }
 // host outputs: a count-only pass, then one pass with the exact total into the workspace's staging buffers; the lists are
 // then allocated here (pn_free).  Both passes run the pipeline (the count is not kept between calls).
@@ -3591,12 +3464,10 @@ static int radius_self_host(const pn_index *ix, T radius, unsigned flags, uint64
     if (dist_out) *dist_out = nullptr;
     const size_t n = ix->n;
     if (n > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many rows for one self-query");
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
-    Workspace &ws = *lease.ws;
-    hipStream_t s = lease.s;
+    CallScope call(ix);
+    PNCHK(call.own_stream());
+    Workspace &ws = call.ws();
+    hipStream_t s = call.s();
     PNCHK(ws.w_sf_hoff.ensure((n + 2) * sizeof(uint64_t)));
     uint64_t *d_off = (uint64_t *)ws.w_sf_hoff.p, *d_tot = d_off + n + 1;
     // the disagreement word of radius_self_enqueue (behind the flags of one chunk)
@@ -3756,23 +3627,18 @@ template <typename T>
 static int dbscan_device(const pn_index *ix, T eps, size_t min_samples, unsigned flags, int64_t *d_labels, uint8_t *d_core,
                          uint64_t *d_ncl, hipStream_t s) {
     PNCHK(dbscan_args(ix, flags, min_samples, d_labels, (int)sizeof(T)));
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    lease.s = s;
-    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
-    return dbscan_enqueue<T>(ix, *lease.ws, eps, min_samples, d_labels, d_core, d_ncl, s);
+    CallScope call(ix);
+    PNCHK(call.on_stream(s));
+    return dbscan_enqueue<T>(ix, call.ws(), eps, min_samples, d_labels, d_core, d_ncl, s);
 }
 template <typename T>
 static int dbscan_host(const pn_index *ix, T eps, size_t min_samples, unsigned flags, int64_t *labels, uint8_t *core,
                        uint64_t *n_clusters) {
     PNCHK(dbscan_args(ix, flags, min_samples, labels, (int)sizeof(T)));
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
-    Workspace &ws = *lease.ws;
-    hipStream_t s = lease.s;
+    CallScope call(ix);
+    PNCHK(call.own_stream());
+    Workspace &ws = call.ws();
+    hipStream_t s = call.s();
     const size_t n = ix->n;
     PNCHK(ws.w_db_out.ensure((n + 1) * sizeof(uint64_t) + n));
     int64_t *d_labels = (int64_t *)ws.w_db_out.p;
@@ -3845,10 +3711,7 @@ static int optics_enqueue(const pn_index *ix, Workspace &ws, size_t min_samples,
     if (!d_core) d_core = radii + n;
     // ---- 1. core distances and the rows' radii
     if (n < 2) {
-        if constexpr (sizeof(T) == 4)
-            HIPCHK(launch_optics_core_f32(nullptr, n, 1, max_eps, d_core, radii, s));
-        else
-            HIPCHK(launch_optics_core_f64(nullptr, n, 1, max_eps, d_core, radii, s));
+        HIPCHK(launch_optics_core<T>(nullptr, n, 1, max_eps, d_core, radii, s));
         std::lock_guard<std::mutex> lk(ix->sh.mu);
         ix->sh.stats.queries += n;
     } else {
@@ -3858,10 +3721,7 @@ static int optics_enqueue(const pn_index *ix, Workspace &ws, size_t min_samples,
             PNCHK(ws.w_hidx.ensure(nqc * kout * sizeof(uint64_t)));
             PNCHK(ws.w_hdist.ensure(nqc * kout * sizeof(T)));
             PNCHK(self_knn_chunk<T>(ix, ws, r0, nqc, kin, kout, false, (uint64_t *)ws.w_hidx.p, (T *)ws.w_hdist.p, s));
-            if constexpr (sizeof(T) == 4)
-                HIPCHK(launch_optics_core_f32((const T *)ws.w_hdist.p, nqc, kout, max_eps, d_core + r0, radii + r0, s));
-            else
-                HIPCHK(launch_optics_core_f64((const T *)ws.w_hdist.p, nqc, kout, max_eps, d_core + r0, radii + r0, s));
+            HIPCHK(launch_optics_core<T>((const T *)ws.w_hdist.p, nqc, kout, max_eps, d_core + r0, radii + r0, s));
         }
     }
     // ---- 2. count (max_eps <= 0 or NaN, or a single row: every list is empty by definition)
@@ -3906,42 +3766,31 @@ static int optics_enqueue(const pn_index *ix, Workspace &ws, size_t min_samples,
                 T *in_dist = (T *)ws.w_sf_dist.p;
                 PNCHK(radius_device_enqueue<T>(ix, ws, (const T *)ix->d_pts + a * ix->ld, b - a, ix->dim, ix->ld, max_eps, in_off,
                                                in_idx, (size_t)in_cap, nullptr, s, in_dist, 0, false, radii + a, false));
-                if constexpr (sizeof(T) == 4)
-                    HIPCHK(launch_optics_repack_f32(in_off, in_idx, in_dist, in_cap, b - a, a, ix->index_base, off, ids, dist, s));
-                else
-                    HIPCHK(launch_optics_repack_f64(in_off, in_idx, in_dist, in_cap, b - a, a, ix->index_base, off, ids, dist, s));
+                HIPCHK(launch_optics_repack<T>(in_off, in_idx, in_dist, in_cap, b - a, a, ix->index_base, off, ids, dist, s));
             }
             a = b;
         }
     }
     // ---- 4. the ordering
-    if constexpr (sizeof(T) == 4)
-        HIPCHK(launch_optics_order_f32(n, off, ids, dist, total, d_core, tree, d_ordering, d_reach, d_pred, s));
-    else
-        HIPCHK(launch_optics_order_f64(n, off, ids, dist, total, d_core, tree, d_ordering, d_reach, d_pred, s));
+    HIPCHK(launch_optics_order<T>(n, off, ids, dist, total, d_core, tree, d_ordering, d_reach, d_pred, s));
     return PN_OK;
 }
 template <typename T>
 static int optics_device(const pn_index *ix, size_t min_samples, T max_eps, unsigned flags, uint64_t *d_ordering, T *d_reach,
                          int64_t *d_pred, T *d_core, hipStream_t s) {
     PNCHK(optics_args(ix, min_samples, flags, d_ordering, d_reach, (int)sizeof(T)));
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    lease.s = s;
-    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
-    return optics_enqueue<T>(ix, *lease.ws, min_samples, max_eps, d_ordering, d_reach, d_pred, d_core, s);
+    CallScope call(ix);
+    PNCHK(call.on_stream(s));
+    return optics_enqueue<T>(ix, call.ws(), min_samples, max_eps, d_ordering, d_reach, d_pred, d_core, s);
 }
 template <typename T>
 static int optics_host(const pn_index *ix, size_t min_samples, T max_eps, unsigned flags, uint64_t *ordering, T *reach,
                        int64_t *pred, T *core) {
     PNCHK(optics_args(ix, min_samples, flags, ordering, reach, (int)sizeof(T)));
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
-    Workspace &ws = *lease.ws;
-    hipStream_t s = lease.s;
+    CallScope call(ix);
+    PNCHK(call.own_stream());
+    Workspace &ws = call.ws();
+    hipStream_t s = call.s();
     const size_t n = ix->n;
     PNCHK(ws.w_opt_io.ensure(2 * n * sizeof(uint64_t) + 2 * n * sizeof(T)));
     uint64_t *d_ordering = (uint64_t *)ws.w_opt_io.p;
@@ -3991,33 +3840,25 @@ static int optics_dbscan_enqueue(const pn_index *ix, Workspace &ws, const uint64
     const size_t n = ix->n;
     if (!n) return PN_OK;
     PNCHK(ws.w_opt.ensure(optics_extract_bytes(n)));
-    if constexpr (sizeof(T) == 4)
-        HIPCHK(launch_optics_extract_f32(d_ordering, d_reach, d_core, n, eps, ws.w_opt.p, d_labels, d_ncl, d_err, s));
-    else
-        HIPCHK(launch_optics_extract_f64(d_ordering, d_reach, d_core, n, eps, ws.w_opt.p, d_labels, d_ncl, d_err, s));
+    HIPCHK(launch_optics_extract<T>(d_ordering, d_reach, d_core, n, eps, ws.w_opt.p, d_labels, d_ncl, d_err, s));
     return PN_OK;
 }
 template <typename T>
 static int optics_dbscan_device(const pn_index *ix, const uint64_t *d_ordering, const T *d_reach, const T *d_core, T eps,
                                 unsigned flags, int64_t *d_labels, uint64_t *d_ncl, int32_t *d_err, hipStream_t s) {
     PNCHK(optics_dbscan_args(ix, d_ordering, d_reach, d_core, flags, d_labels, (int)sizeof(T)));
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    lease.s = s;
-    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
-    return optics_dbscan_enqueue<T>(ix, *lease.ws, d_ordering, d_reach, d_core, eps, d_labels, d_ncl, d_err, s);
+    CallScope call(ix);
+    PNCHK(call.on_stream(s));
+    return optics_dbscan_enqueue<T>(ix, call.ws(), d_ordering, d_reach, d_core, eps, d_labels, d_ncl, d_err, s);
 }
 template <typename T>
 static int optics_dbscan_host(const pn_index *ix, const uint64_t *ordering, const T *reach, const T *core, T eps, unsigned flags,
                               int64_t *labels, uint64_t *n_clusters) {
     PNCHK(optics_dbscan_args(ix, ordering, reach, core, flags, labels, (int)sizeof(T)));
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
-    Workspace &ws = *lease.ws;
-    hipStream_t s = lease.s;
+    CallScope call(ix);
+    PNCHK(call.own_stream());
+    Workspace &ws = call.ws();
+    hipStream_t s = call.s();
     const size_t n = ix->n;
     PNCHK(ws.w_opt_io.ensure((2 * n + 2) * sizeof(uint64_t) + 2 * n * sizeof(T)));
     uint64_t *d_ordering = (uint64_t *)ws.w_opt_io.p;
@@ -4116,10 +3957,7 @@ static int mst_run(const pn_index *ix, Workspace &ws, const T *d_core, uint64_t 
         ix->sh.stats.queries += n;
     }
     int rc;
-    if constexpr (sizeof(T) == 4)
-        rc = mst_enqueue_f32(a, s);
-    else
-        rc = mst_enqueue_f64(a, s);
+    rc = mst_enqueue<T>(a, s);
     if (rc == PN_OK && work_out) {
         work_out[0] = a.work[0];
         work_out[1] = a.work[1];
@@ -4130,23 +3968,18 @@ template <typename T>
 static int mst_device(const pn_index *ix, const T *d_core, unsigned flags, uint64_t *d_src, uint64_t *d_dst, T *d_weight,
                       uint64_t *work_out, hipStream_t s) {
     PNCHK(mst_args(ix, flags, d_src, d_dst, d_weight, (int)sizeof(T)));
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    lease.s = s;
-    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
-    return mst_run<T>(ix, *lease.ws, d_core, d_src, d_dst, d_weight, work_out, s);
+    CallScope call(ix);
+    PNCHK(call.on_stream(s));
+    return mst_run<T>(ix, call.ws(), d_core, d_src, d_dst, d_weight, work_out, s);
 }
 template <typename T>
 static int mst_host(const pn_index *ix, const T *core, unsigned flags, uint64_t *src, uint64_t *dst, T *weight,
                     uint64_t *work_out) {
     PNCHK(mst_args(ix, flags, src, dst, weight, (int)sizeof(T)));
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
-    Workspace &ws = *lease.ws;
-    hipStream_t s = lease.s;
+    CallScope call(ix);
+    PNCHK(call.own_stream());
+    Workspace &ws = call.ws();
+    hipStream_t s = call.s();
     const size_t n = ix->n, ne = n ? n - 1 : 0;
     PNCHK(ws.w_mst_io.ensure(2 * ne * sizeof(uint64_t) + (ne + n) * sizeof(T) + 64));
     uint64_t *d_src = (uint64_t *)ws.w_mst_io.p, *d_dst = d_src + ne;
@@ -4214,39 +4047,31 @@ static int linkage_run(const pn_index *ix, void *buf, const uint64_t *d_src, con
     a.d_size = d_size;
     a.d_weight_out = d_weight_out;
     a.d_err = d_err;
-    if constexpr (sizeof(T) == 4)
-        return linkage_enqueue_f32(a, s);
-    else
-        return linkage_enqueue_f64(a, s);
+    return linkage_enqueue<T>(a, s);
 }
 template <typename T>
 static int linkage_device(const pn_index *ix, const uint64_t *d_src, const uint64_t *d_dst, const T *d_weight, unsigned flags,
                           uint64_t *d_left, uint64_t *d_right, T *d_weight_out, uint64_t *d_size, int32_t *d_err,
                           hipStream_t s) {
     PNCHK(linkage_args(ix, flags, d_src, d_dst, d_weight, d_left, d_right, d_weight_out, d_size, (int)sizeof(T)));
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    lease.s = s;
-    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
+    CallScope call(ix);
+    PNCHK(call.on_stream(s));
     if (ix->n < 2) {
         if (d_err) HIPCHK(hipMemsetAsync(d_err, 0, sizeof(int32_t), s));
         return PN_OK;
     }
-    PNCHK(lease.ws->w_hdb.ensure(linkage_buffer_bytes(ix->n)));
-    return linkage_run<T>(ix, lease.ws->w_hdb.p, d_src, d_dst, d_weight, d_left, d_right, d_weight_out, d_size, d_err, s);
+    PNCHK(call.ws().w_hdb.ensure(linkage_buffer_bytes(ix->n)));
+    return linkage_run<T>(ix, call.ws().w_hdb.p, d_src, d_dst, d_weight, d_left, d_right, d_weight_out, d_size, d_err, s);
 }
 template <typename T>
 static int linkage_host(const pn_index *ix, const uint64_t *src, const uint64_t *dst, const T *weight, unsigned flags,
                         uint64_t *left, uint64_t *right, T *weight_out, uint64_t *size) {
     PNCHK(linkage_args(ix, flags, src, dst, weight, left, right, weight_out, size, (int)sizeof(T)));
     if (ix->n < 2) return PN_OK;
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
-    Workspace &ws = *lease.ws;
-    hipStream_t s = lease.s;
+    CallScope call(ix);
+    PNCHK(call.own_stream());
+    Workspace &ws = call.ws();
+    hipStream_t s = call.s();
     const size_t n = ix->n, ne = n - 1;
     PNCHK(ws.w_hdb.ensure(linkage_buffer_bytes(n)));
     PNCHK(ws.w_hdb_io.ensure(5 * ne * sizeof(uint64_t) + 2 * ne * sizeof(T) + 64));
@@ -4324,10 +4149,7 @@ static int hdbscan_enqueue(const pn_index *ix, Workspace &ws, size_t min_samples
         PNCHK(ws.w_hidx.ensure(nqc * kout * sizeof(uint64_t)));
         PNCHK(ws.w_hdist.ensure(nqc * kout * sizeof(T)));
         PNCHK(self_knn_chunk<T>(ix, ws, r0, nqc, kin, kout, false, (uint64_t *)ws.w_hidx.p, (T *)ws.w_hdist.p, s));
-        if constexpr (sizeof(T) == 4)
-            HIPCHK(launch_last_column_f32((const T *)ws.w_hdist.p, nqc, kout, d_core + r0, s));
-        else
-            HIPCHK(launch_last_column_f64((const T *)ws.w_hdist.p, nqc, kout, d_core + r0, s));
+        HIPCHK(launch_last_column<T>((const T *)ws.w_hdist.p, nqc, kout, d_core + r0, s));
     }
     // ---- the tree, the dendrogram, the labels
     PNCHK(mst_run<T>(ix, ws, d_core, d_src, d_dst, d_weight, nullptr, s));
@@ -4340,32 +4162,24 @@ static int hdbscan_enqueue(const pn_index *ix, Workspace &ws, size_t min_samples
     h.d_labels = d_labels;
     h.d_prob = d_prob;
     h.d_n_clusters = d_ncl;
-    if constexpr (sizeof(T) == 4)
-        return hdbscan_extract_enqueue_f32(h, s);
-    else
-        return hdbscan_extract_enqueue_f64(h, s);
+    return hdbscan_extract_enqueue<T>(h, s);
 }
 template <typename T>
 static int hdbscan_device(const pn_index *ix, size_t min_samples, size_t min_cluster_size, unsigned flags, int64_t *d_labels,
                           T *d_prob, uint64_t *d_ncl, hipStream_t s) {
     PNCHK(hdbscan_args(ix, min_samples, min_cluster_size, flags, d_labels, (int)sizeof(T)));
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    lease.s = s;
-    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
-    return hdbscan_enqueue<T>(ix, *lease.ws, min_samples, min_cluster_size, d_labels, d_prob, d_ncl, s);
+    CallScope call(ix);
+    PNCHK(call.on_stream(s));
+    return hdbscan_enqueue<T>(ix, call.ws(), min_samples, min_cluster_size, d_labels, d_prob, d_ncl, s);
 }
 template <typename T>
 static int hdbscan_host(const pn_index *ix, size_t min_samples, size_t min_cluster_size, unsigned flags, int64_t *labels,
                         T *prob, uint64_t *n_clusters) {
     PNCHK(hdbscan_args(ix, min_samples, min_cluster_size, flags, labels, (int)sizeof(T)));
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
-    Workspace &ws = *lease.ws;
-    hipStream_t s = lease.s;
+    CallScope call(ix);
+    PNCHK(call.own_stream());
+    Workspace &ws = call.ws();
+    hipStream_t s = call.s();
     const size_t n = ix->n;
     PNCHK(ws.w_hdb_io.ensure((n + 1) * sizeof(uint64_t) + n * sizeof(T)));
     int64_t *d_labels = (int64_t *)ws.w_hdb_io.p;
@@ -4445,40 +4259,28 @@ static int lof_enqueue(const pn_index *ix, Workspace &ws, size_t k, double *d_lo
         PNCHK(ws.w_hidx.ensure(nqc * k * sizeof(uint64_t)));
         PNCHK(ws.w_hdist.ensure(nqc * k * sizeof(T)));
         PNCHK(self_knn_chunk<T>(ix, ws, r0, nqc, k + 1, k, false, (uint64_t *)ws.w_hidx.p, (T *)ws.w_hdist.p, s));
-        if constexpr (sizeof(T) == 4)
-            HIPCHK(launch_lof_pack_f32((const uint64_t *)ws.w_hidx.p, (const T *)ws.w_hdist.p, nqc, (int)k, ix->index_base,
-                                       ids + r0 * k, dist + r0 * k, d_kdist + r0, s));
-        else
-            HIPCHK(launch_lof_pack_f64((const uint64_t *)ws.w_hidx.p, (const T *)ws.w_hdist.p, nqc, (int)k, ix->index_base,
-                                       ids + r0 * k, dist + r0 * k, d_kdist + r0, s));
+        HIPCHK(launch_lof_pack<T>((const uint64_t *)ws.w_hidx.p, (const T *)ws.w_hdist.p, nqc, (int)k, ix->index_base,
+                                  ids + r0 * k, dist + r0 * k, d_kdist + r0, s));
     }
     // ---- two gather passes over it
-    if constexpr (sizeof(T) == 4)
-        HIPCHK(launch_lof_lrd_f32(ids, dist, d_kdist, n, (int)k, d_lrd, s));
-    else
-        HIPCHK(launch_lof_lrd_f64(ids, dist, d_kdist, n, (int)k, d_lrd, s));
+    HIPCHK(launch_lof_lrd<T>(ids, dist, d_kdist, n, (int)k, d_lrd, s));
     HIPCHK(launch_lof_lof(ids, d_lrd, n, (int)k, d_lof, s));
     return PN_OK;
 }
 template <typename T>
 static int lof_device(const pn_index *ix, size_t k, unsigned flags, double *d_lof, double *d_lrd, T *d_kdist, hipStream_t s) {
     PNCHK(lof_args(ix, k, flags, d_lof, (int)sizeof(T)));
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    lease.s = s;
-    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
-    return lof_enqueue<T>(ix, *lease.ws, k, d_lof, d_lrd, d_kdist, s);
+    CallScope call(ix);
+    PNCHK(call.on_stream(s));
+    return lof_enqueue<T>(ix, call.ws(), k, d_lof, d_lrd, d_kdist, s);
 }
 template <typename T>
 static int lof_host(const pn_index *ix, size_t k, unsigned flags, double *lof, double *lrd, T *kdist) {
     PNCHK(lof_args(ix, k, flags, lof, (int)sizeof(T)));
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
-    Workspace &ws = *lease.ws;
-    hipStream_t s = lease.s;
+    CallScope call(ix);
+    PNCHK(call.own_stream());
+    Workspace &ws = call.ws();
+    hipStream_t s = call.s();
     const size_t n = ix->n;
     PNCHK(ws.w_lof_io.ensure(2 * n * sizeof(double) + n * sizeof(T)));
     double *d_lof = (double *)ws.w_lof_io.p, *d_lrd = d_lof + n;
@@ -4515,12 +4317,8 @@ static int lof_score_enqueue(const pn_index *ix, Workspace &ws, const T *d_q, si
         PNCHK(ws.w_hdist.ensure(nqc * k * sizeof(T)));
         PNCHK(query_enqueue<T>(ix, ws, d_q + q0 * q_stride, nqc, q_cols, q_stride, k, (uint64_t *)ws.w_hidx.p,
                                (T *)ws.w_hdist.p, k, s));
-        if constexpr (sizeof(T) == 4)
-            HIPCHK(launch_lof_score_f32((const uint64_t *)ws.w_hidx.p, (const T *)ws.w_hdist.p, nqc, (int)k, ix->index_base,
-                                        ix->n, d_lrd, d_kdist, d_score + q0, s));
-        else
-            HIPCHK(launch_lof_score_f64((const uint64_t *)ws.w_hidx.p, (const T *)ws.w_hdist.p, nqc, (int)k, ix->index_base,
-                                        ix->n, d_lrd, d_kdist, d_score + q0, s));
+        HIPCHK(launch_lof_score<T>((const uint64_t *)ws.w_hidx.p, (const T *)ws.w_hdist.p, nqc, (int)k, ix->index_base, ix->n,
+                                   d_lrd, d_kdist, d_score + q0, s));
     }
     return PN_OK;
 }
@@ -4529,24 +4327,19 @@ static int lof_score_device(const pn_index *ix, const T *d_q, size_t nq, size_t 
                             const double *d_lrd, const T *d_kdist, unsigned flags, double *d_score, hipStream_t s) {
     PNCHK(lof_score_args(ix, d_q, nq, k, d_lrd, d_kdist, flags, d_score, (int)sizeof(T)));
     if (nq == 0) return PN_OK;
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    lease.s = s;
-    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
-    return lof_score_enqueue<T>(ix, *lease.ws, d_q, nq, q_cols, q_stride, k, d_lrd, d_kdist, d_score, s);
+    CallScope call(ix);
+    PNCHK(call.on_stream(s));
+    return lof_score_enqueue<T>(ix, call.ws(), d_q, nq, q_cols, q_stride, k, d_lrd, d_kdist, d_score, s);
 }
 template <typename T>
 static int lof_score_host(const pn_index *ix, const T *q, size_t nq, size_t q_cols, ptrdiff_t q_stride, size_t k,
                           const double *lrd, const T *kdist, unsigned flags, double *score) {
     PNCHK(lof_score_args(ix, q, nq, k, lrd, kdist, flags, score, (int)sizeof(T)));
     if (nq == 0) return PN_OK;
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
-    Workspace &ws = *lease.ws;
-    hipStream_t s = lease.s;
+    CallScope call(ix);
+    PNCHK(call.own_stream());
+    Workspace &ws = call.ws();
+    hipStream_t s = call.s();
     const size_t n = ix->n;
     PNCHK(upload_rows_to<T>(q, nq, q_cols, q_stride, ws.w_hq, s));
     PNCHK(ws.w_lof_io.ensure((n + nq) * sizeof(double) + n * sizeof(T)));
@@ -4618,12 +4411,10 @@ static int radii_host(const pn_index *ix, const T *q, size_t nq, size_t q_cols, 
     if (nq == 0) return PN_OK;
     if (!q && q_cols) return fail(PN_ERR_INVALID, "queries is NULL");
     if (nq > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many queries in one call");
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
-    Workspace &ws = *lease.ws;
-    hipStream_t s = lease.s;
+    CallScope call(ix);
+    PNCHK(call.own_stream());
+    Workspace &ws = call.ws();
+    hipStream_t s = call.s();
     PNCHK(upload_rows_to<T>(q, nq, q_cols, q_stride, ws.w_hq, s));
     PNCHK(ws.w_hrad.ensure(nq * sizeof(T)));
     HIPCHK(hipMemcpyAsync(ws.w_hrad.p, radii, nq * sizeof(T), hipMemcpyHostToDevice, s));
@@ -4831,12 +4622,9 @@ static int kde_device(const pn_index *ix, bool self, const T *d_q, size_t nq, si
         if (n_h != 1 && n_h != nq) return fail(PN_ERR_INVALID, "n_h must be 1 or the number of rows (%zu)", nq);
     }
     if (nq == 0) return PN_OK;
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    lease.s = s;
-    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
-    return kde_enqueue<T>(ix, *lease.ws, self, d_q, nq, q_cols, q_stride, d_h, n_h, kernel, atol, flags, d_sum, d_count,
+    CallScope call(ix);
+    PNCHK(call.on_stream(s));
+    return kde_enqueue<T>(ix, call.ws(), self, d_q, nq, q_cols, q_stride, d_h, n_h, kernel, atol, flags, d_sum, d_count,
                           d_cutoff, s);
 }
 template <typename T>
@@ -4852,12 +4640,10 @@ static int kde_host(const pn_index *ix, bool self, const T *q, size_t nq, size_t
     if (nq == 0) return PN_OK;
     if (n_h == 1 && !(h[0] > (T)0 && h[0] < (T)INFINITY))
         return fail(PN_ERR_INVALID, "the bandwidth must be finite and positive");
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
-    Workspace &ws = *lease.ws;
-    hipStream_t s = lease.s;
+    CallScope call(ix);
+    PNCHK(call.own_stream());
+    Workspace &ws = call.ws();
+    hipStream_t s = call.s();
     if (!self) PNCHK(upload_rows_to<T>(q, nq, q_cols, q_stride, ws.w_hq, s));
     PNCHK(ws.w_kde_io.ensure(nq * (sizeof(double) + sizeof(uint64_t) + sizeof(T)) + n_h * sizeof(T)));
     double *d_sum = (double *)ws.w_kde_io.p;
@@ -5060,12 +4846,9 @@ static int ms_device(const pn_index *ix, const T *d_seeds, size_t ns, size_t s_c
         s_stride = ix->ld;
     }
     if (ns == 0) return PN_OK;
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    lease.s = s;
-    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
-    return ms_enqueue<T>(ix, *lease.ws, d_seeds, ns, s_stride, d_h, n_h, tol, max_iter, d_modes, d_points, d_iters, d_shift,
+    CallScope call(ix);
+    PNCHK(call.on_stream(s));
+    return ms_enqueue<T>(ix, call.ws(), d_seeds, ns, s_stride, d_h, n_h, tol, max_iter, d_modes, d_points, d_iters, d_shift,
                          work, s);
 }
 template <typename T>
@@ -5077,12 +4860,10 @@ static int ms_host(const pn_index *ix, const T *seeds, size_t ns, size_t s_cols,
     const bool rows = (flags & PN_MS_SEED_ROWS) != 0;
     if (rows) ns = ix->n;
     if (ns == 0) return PN_OK;
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
-    Workspace &ws = *lease.ws;
-    hipStream_t s = lease.s;
+    CallScope call(ix);
+    PNCHK(call.own_stream());
+    Workspace &ws = call.ws();
+    hipStream_t s = call.s();
     const size_t dim = ix->dim;
     if (!rows) PNCHK(upload_rows_to<T>(seeds, ns, dim, s_stride, ws.w_hq, s));
     const size_t m_bytes = round_up(ns * dim * sizeof(T), (size_t)8), h_bytes = round_up(n_h * sizeof(T), (size_t)8);
@@ -5119,13 +4900,10 @@ static int ms_merge_device(const pn_index *ix, const T *d_modes, size_t ns, cons
                            T *d_centres, uint64_t *d_centre_points, int64_t *d_centre_of_seed, uint64_t *d_n_centres,
                            hipStream_t s) {
     PNCHK(ms_merge_args(ix, flags, d_centres, d_n_centres, d_modes, d_points, ns, (int)sizeof(T)));
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    lease.s = s;
-    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
-    PNCHK(lease.ws->w_ms.ensure(ms_merge_bytes(ns)));
-    HIPCHK(ms_merge_enqueue<T>(d_modes, ns, (int)ix->dim, d_points, h, lease.ws->w_ms.p, d_centres, d_centre_points,
+    CallScope call(ix);
+    PNCHK(call.on_stream(s));
+    PNCHK(call.ws().w_ms.ensure(ms_merge_bytes(ns)));
+    HIPCHK(ms_merge_enqueue<T>(d_modes, ns, (int)ix->dim, d_points, h, call.ws().w_ms.p, d_centres, d_centre_points,
                                d_centre_of_seed, d_n_centres, s));
     return PN_OK;
 }
@@ -5137,12 +4915,10 @@ static int ms_merge_host(const pn_index *ix, const T *modes, size_t ns, const ui
         *n_centres = 0;
         return PN_OK;
     }
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
-    Workspace &ws = *lease.ws;
-    hipStream_t s = lease.s;
+    CallScope call(ix);
+    PNCHK(call.own_stream());
+    Workspace &ws = call.ws();
+    hipStream_t s = call.s();
     const size_t dim = ix->dim, m_bytes = round_up(ns * dim * sizeof(T), (size_t)8);
     PNCHK(ws.w_ms_io.ensure(ns * 3 * sizeof(uint64_t) + 8 + 2 * m_bytes));
     uint64_t *d_points = (uint64_t *)ws.w_ms_io.p, *d_cp = d_points + ns, *d_nc = d_cp + ns;
@@ -5188,12 +4964,10 @@ template <typename T>
 static int ms_labels_host(const pn_index *ix, const T *centres, size_t nc, T h, unsigned flags, int64_t *labels) {
     PNCHK(ms_labels_args(ix, flags, labels, centres, nc, (int)sizeof(T)));
     if (ix->n == 0) return PN_OK;
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
-    Workspace &ws = *lease.ws;
-    hipStream_t s = lease.s;
+    CallScope call(ix);
+    PNCHK(call.own_stream());
+    Workspace &ws = call.ws();
+    hipStream_t s = call.s();
     const size_t c_bytes = nc * ix->dim * sizeof(T);
     PNCHK(ws.w_ms_io.ensure(ix->n * sizeof(int64_t) + c_bytes + 8));
     int64_t *d_labels = (int64_t *)ws.w_ms_io.p;
@@ -5333,19 +5107,17 @@ template <typename T>
 static int km_assign_device(const pn_index *ix, const T *d_centres, size_t nc, unsigned flags, int64_t *d_labels, T *d_dist,
                             double *d_inertia, hipStream_t s) {
     PNCHK(km_args(ix, false, flags, 0.0, 1, d_labels, nullptr, d_centres, nc, (int)sizeof(T)));
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    CallScope call(ix);
+    PNCHK(call.guard());
     if (ix->n == 0) {
         if (d_inertia) HIPCHK(hipMemsetAsync(d_inertia, 0, sizeof(double), s));
         return PN_OK;
     }
-    WsLease lease(ix);
-    lease.s = s;
-    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
+    PNCHK(call.on_stream(s));
     KmRowImage rows;
     const bool filter = km_use_filter(ix, nc);
-    if (filter) PNCHK(km_pack_rows<T>(ix, *lease.ws, &rows, s));
-    return km_assign_enqueue<T>(ix, *lease.ws, filter ? &rows : nullptr, d_centres, nc, d_labels, d_dist, d_inertia, s);
+    if (filter) PNCHK(km_pack_rows<T>(ix, call.ws(), &rows, s));
+    return km_assign_enqueue<T>(ix, call.ws(), filter ? &rows : nullptr, d_centres, nc, d_labels, d_dist, d_inertia, s);
 }
 template <typename T>
 static int km_assign_host(const pn_index *ix, const T *centres, size_t nc, unsigned flags, int64_t *labels, T *dist,
@@ -5355,12 +5127,10 @@ static int km_assign_host(const pn_index *ix, const T *centres, size_t nc, unsig
         if (inertia) *inertia = 0.0;
         return PN_OK;
     }
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
-    Workspace &ws = *lease.ws;
-    hipStream_t s = lease.s;
+    CallScope call(ix);
+    PNCHK(call.own_stream());
+    Workspace &ws = call.ws();
+    hipStream_t s = call.s();
     const size_t n = ix->n, c_bytes = round_up(nc * ix->dim * sizeof(T), (size_t)8), d_bytes = round_up(n * sizeof(T), (size_t)8);
     PNCHK(ws.w_km_io.ensure(n * sizeof(int64_t) + 8 + d_bytes + c_bytes));
     int64_t *d_labels = (int64_t *)ws.w_km_io.p;
@@ -5419,8 +5189,8 @@ static int km_device(const pn_index *ix, const T *d_init, size_t nc, double tol,
                      int64_t *d_labels, T *d_dist, uint64_t *d_counts, double *d_inertia, uint64_t *d_iterations,
                      double *d_shift2, hipStream_t s) {
     PNCHK(km_args(ix, true, flags, tol, max_iter, d_labels, d_centres, d_init, nc, (int)sizeof(T)));
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
+    CallScope call(ix);
+    PNCHK(call.guard());
     if (d_centres != d_init)
         HIPCHK(hipMemcpyAsync(d_centres, d_init, nc * ix->dim * sizeof(T), hipMemcpyDeviceToDevice, s));
     if (ix->n == 0) {
@@ -5430,10 +5200,8 @@ static int km_device(const pn_index *ix, const T *d_init, size_t nc, double tol,
         if (d_shift2) HIPCHK(hipMemsetAsync(d_shift2, 0, sizeof(double), s));
         return PN_OK;
     }
-    WsLease lease(ix);
-    lease.s = s;
-    PNCHK(ws_acquire(ix, &lease.s, false, &lease.ws));
-    return km_loop_enqueue<T>(ix, *lease.ws, nc, tol, max_iter, d_centres, d_labels, d_dist, d_counts, d_inertia, d_iterations,
+    PNCHK(call.on_stream(s));
+    return km_loop_enqueue<T>(ix, call.ws(), nc, tol, max_iter, d_centres, d_labels, d_dist, d_counts, d_inertia, d_iterations,
                               d_shift2, s);
 }
 template <typename T>
@@ -5449,12 +5217,10 @@ static int km_host(const pn_index *ix, const T *init, size_t nc, double tol, siz
         if (shift2) *shift2 = 0.0;
         return PN_OK;
     }
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
-    Workspace &ws = *lease.ws;
-    hipStream_t s = lease.s;
+    CallScope call(ix);
+    PNCHK(call.own_stream());
+    Workspace &ws = call.ws();
+    hipStream_t s = call.s();
     const size_t c_bytes = round_up(nc * dim * sizeof(T), (size_t)8), d_bytes = round_up(n * sizeof(T), (size_t)8);
     PNCHK(ws.w_km_io.ensure(n * sizeof(int64_t) + 24 + nc * sizeof(uint64_t) + d_bytes + c_bytes));
     int64_t *d_labels = (int64_t *)ws.w_km_io.p;
@@ -5484,12 +5250,10 @@ extern "C" int pn_kmeans_bounds_f32(const pn_index *ix, const float *centres, si
     if (!km_filter_supported((int)ix->dim)) return fail(PN_ERR_UNSUPPORTED, "the k-means filter takes 8 <= dim <= 320");
     if (ix->n > 0x7FFFFFFFull || nc > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many rows or centres");
     if (ix->n == 0 || nc == 0) return PN_OK;
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", ix->device);
-    WsLease lease(ix);
-    PNCHK(ws_acquire(ix, &lease.s, true, &lease.ws));
-    Workspace &ws = *lease.ws;
-    hipStream_t s = lease.s;
+    CallScope call(ix);
+    PNCHK(call.own_stream());
+    Workspace &ws = call.ws();
+    hipStream_t s = call.s();
     const int dim = (int)ix->dim;
     const size_t c_bytes = round_up(nc * ix->dim * sizeof(float), (size_t)8);
     PNCHK(ws.w_km_io.ensure(ix->n * nc * sizeof(double) + c_bytes));
@@ -5555,10 +5319,8 @@ static int pairwise_device_impl(const T *d_x, size_t n, size_t cols, size_t row_
     const size_t ld = pick_ld(cols), n_pad = round_up(n, (size_t)kRowPad);
     T *d_p = nullptr;
     HIPCHK(hipMalloc((void **)&d_p, n_pad * ld * sizeof(T)));
-    hipError_t e = Ops<T>::pack(d_x, n, cols, row_stride ? row_stride : 1, d_p, n_pad, ld, s);
-    if (e == hipSuccess)
-        e = (sizeof(T) == 4) ? launch_exact_pairwise_f32((const float *)d_p, n, (int)cols, ld, (float *)d_out, s)
-                             : launch_exact_pairwise_f64((const double *)d_p, n, (int)cols, ld, (double *)d_out, s);
+    hipError_t e = launch_pack_rows<T>(d_x, n, cols, row_stride ? row_stride : 1, d_p, n_pad, ld, s);
+    if (e == hipSuccess) e = launch_exact_pairwise<T>(d_p, n, (int)cols, ld, d_out, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);  // the working copy must outlive the kernel
     (void)hipFree(d_p);
     if (e != hipSuccess) return fail(PN_ERR_DEVICE, "pairwise: %s", hipGetErrorString(e));
@@ -5598,15 +5360,11 @@ static int pairwise_impl(const T *x, size_t n, size_t cols, ptrdiff_t row_stride
             rc = fail(PN_ERR_NOMEM, "hipMalloc pairwise failed");
             break;
         }
-        hipError_t e = Ops<T>::pack(d_x, n, cols, cols ? cols : 1, d_p, n_pad, ld, nullptr);
+        hipError_t e = launch_pack_rows<T>(d_x, n, cols, cols ? cols : 1, d_p, n_pad, ld, nullptr);
         if (e == hipSuccess && cosine)
-            e = (sizeof(T) == 4) ? launch_cosine_pairwise_f32((const float *)d_p, n, (int)cols, ld, (float *)d_n,
-                                                              (float *)d_o, nullptr)
-                                 : launch_cosine_pairwise_f64((const double *)d_p, n, (int)cols, ld, (double *)d_n,
-                                                              (double *)d_o, nullptr);
+            e = launch_cosine_pairwise<T>(d_p, n, (int)cols, ld, d_n, d_o, nullptr);
         else if (e == hipSuccess)
-            e = (sizeof(T) == 4) ? launch_exact_pairwise_f32((const float *)d_p, n, (int)cols, ld, (float *)d_o, nullptr)
-                                 : launch_exact_pairwise_f64((const double *)d_p, n, (int)cols, ld, (double *)d_o, nullptr);
+            e = launch_exact_pairwise<T>(d_p, n, (int)cols, ld, d_o, nullptr);
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  // (the kernels above ran on the default stream)
         if (e == hipSuccess) e = hipMemcpy(out, d_o, n * n * sizeof(T), hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(PN_ERR_DEVICE, "pairwise: %s", hipGetErrorString(e));
@@ -5769,14 +5527,9 @@ static int merge_topk_device_impl(const uint64_t *d_idx_parts, const T *d_dist_p
     PNCHK(check_device(device));
     DeviceGuard g(device);
     if (!g.ok) return fail(PN_ERR_DEVICE, "hipSetDevice(%d) failed", device);
-    if constexpr (sizeof(T) == 4)
-        HIPCHK(launch_merge_topk_f32(d_idx_parts, d_dist_parts, (int)n_parts, idx_part_stride, dist_part_stride, (int)nq,
-                                     (int)k_part, (int)k_out, d_idx_out, d_dist_out, (hipStream_t)stream, nullptr, nullptr, 0,
-                                     nullptr, signed_keys));
-    else
-        HIPCHK(launch_merge_topk_f64(d_idx_parts, d_dist_parts, (int)n_parts, idx_part_stride, dist_part_stride, (int)nq,
-                                     (int)k_part, (int)k_out, d_idx_out, d_dist_out, (hipStream_t)stream, nullptr, nullptr, 0,
-                                     nullptr, signed_keys));
+    HIPCHK(launch_merge_topk<T>(d_idx_parts, d_dist_parts, (int)n_parts, idx_part_stride, dist_part_stride, (int)nq,
+                                (int)k_part, (int)k_out, d_idx_out, d_dist_out, (hipStream_t)stream, nullptr, nullptr, 0,
+                                nullptr, signed_keys));
     return PN_OK;
 }
 namespace pn {

@@ -155,6 +155,8 @@ struct LinkLayout {
                              hipGetErrorString(e_));                                                         \
     } while (0)
 
+}  // namespace
+
 template <typename T>
 int linkage_enqueue(const LinkageArgs &g, hipStream_t s) {
     const size_t n = g.n;
@@ -182,7 +184,10 @@ int linkage_enqueue(const LinkageArgs &g, hipStream_t s) {
     }
     return PN_OK;
 }
+template int linkage_enqueue<float>(const LinkageArgs &, hipStream_t);
+template int linkage_enqueue<double>(const LinkageArgs &, hipStream_t);
 
+namespace {
 // --------------------------------------------------------------------------------------------- part 2: extraction
 // lambda of a merge weight, in f64: 1 / w above 2^-100, 2^100 at or below it (duplicates, Cosine's non-positive weights:
 // finite, so no inf - inf), 0 for NaN
@@ -394,6 +399,8 @@ struct ExtractLayout {
     }
 };
 
+}  // namespace
+
 template <typename T>
 int hdbscan_extract_enqueue(const HdbscanArgs &g, hipStream_t s) {
     const size_t n = g.n, N = 2 * n - 1, ne = n - 1;
@@ -447,7 +454,10 @@ int hdbscan_extract_enqueue(const HdbscanArgs &g, hipStream_t s) {
     LKCHK(hipGetLastError());
     return PN_OK;
 }
+template int hdbscan_extract_enqueue<float>(const HdbscanArgs &, hipStream_t);
+template int hdbscan_extract_enqueue<double>(const HdbscanArgs &, hipStream_t);
 
+namespace {
 template <typename T>
 __global__ __launch_bounds__(256) void last_column_kernel(const T *__restrict__ d, size_t rows, size_t k, T *__restrict__ out) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -457,20 +467,15 @@ __global__ __launch_bounds__(256) void last_column_kernel(const T *__restrict__ 
 }  // namespace
 
 size_t linkage_buffer_bytes(size_t n) { return n < 2 ? 0 : round_up(LinkLayout(n).words * 4, (size_t)16); }
-int linkage_enqueue_f32(const LinkageArgs &a, hipStream_t s) { return linkage_enqueue<float>(a, s); }
-int linkage_enqueue_f64(const LinkageArgs &a, hipStream_t s) { return linkage_enqueue<double>(a, s); }
 
 size_t hdbscan_buffer_bytes(size_t n) { return n < 2 ? 0 : ExtractLayout(n).total; }
-int hdbscan_extract_enqueue_f32(const HdbscanArgs &a, hipStream_t s) { return hdbscan_extract_enqueue<float>(a, s); }
-int hdbscan_extract_enqueue_f64(const HdbscanArgs &a, hipStream_t s) { return hdbscan_extract_enqueue<double>(a, s); }
 
-hipError_t launch_last_column_f32(const float *d, size_t rows, size_t k, float *out, hipStream_t s) {
-    if (rows) hipLaunchKernelGGL((last_column_kernel<float>), grid_of(rows), dim3(256), 0, s, d, rows, k, out);
+template <typename T>
+hipError_t launch_last_column(const T *d, size_t rows, size_t k, T *out, hipStream_t s) {
+    if (rows) hipLaunchKernelGGL((last_column_kernel<T>), grid_of(rows), dim3(256), 0, s, d, rows, k, out);
     return hipGetLastError();
 }
-hipError_t launch_last_column_f64(const double *d, size_t rows, size_t k, double *out, hipStream_t s) {
-    if (rows) hipLaunchKernelGGL((last_column_kernel<double>), grid_of(rows), dim3(256), 0, s, d, rows, k, out);
-    return hipGetLastError();
-}
+template hipError_t launch_last_column<float>(const float *, size_t, size_t, float *, hipStream_t);
+template hipError_t launch_last_column<double>(const double *, size_t, size_t, double *, hipStream_t);
 
 }  // namespace pn

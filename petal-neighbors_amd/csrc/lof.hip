@@ -148,38 +148,30 @@ static unsigned lof_grid(size_t rows, int L) {
 }
 
 template <typename T>
-static hipError_t launch_lof_pack(const uint64_t *in_idx, const T *in_dist, size_t nq, int k, uint64_t index_base,
-                                  uint32_t *ids, T *dist, T *kdist, hipStream_t s) {
+hipError_t launch_lof_pack(const uint64_t *in_idx, const T *in_dist, size_t nq, int k, uint64_t index_base,
+                           uint32_t *ids, T *dist, T *kdist, hipStream_t s) {
     if (nq == 0 || k <= 0) return hipSuccess;
     hipLaunchKernelGGL((lof_pack_kernel<T>), dim3((unsigned)((nq * (size_t)k + 255) / 256)), dim3(256), 0, s, in_idx,
                        in_dist, nq, k, index_base, ids, dist, kdist);
     return hipGetLastError();
 }
-hipError_t launch_lof_pack_f32(const uint64_t *in_idx, const float *in_dist, size_t nq, int k, uint64_t index_base,
-                               uint32_t *ids, float *dist, float *kdist, hipStream_t s) {
-    return launch_lof_pack<float>(in_idx, in_dist, nq, k, index_base, ids, dist, kdist, s);
-}
-hipError_t launch_lof_pack_f64(const uint64_t *in_idx, const double *in_dist, size_t nq, int k, uint64_t index_base,
-                               uint32_t *ids, double *dist, double *kdist, hipStream_t s) {
-    return launch_lof_pack<double>(in_idx, in_dist, nq, k, index_base, ids, dist, kdist, s);
-}
+template hipError_t launch_lof_pack<float>(const uint64_t *, const float *, size_t, int, uint64_t, uint32_t *, float *,
+                                           float *, hipStream_t);
+template hipError_t launch_lof_pack<double>(const uint64_t *, const double *, size_t, int, uint64_t, uint32_t *,
+                                            double *, double *, hipStream_t);
 
 template <typename T>
-static hipError_t launch_lof_lrd(const uint32_t *ids, const T *dist, const T *kdist, size_t n, int k, double *lrd,
-                                 hipStream_t s) {
+hipError_t launch_lof_lrd(const uint32_t *ids, const T *dist, const T *kdist, size_t n, int k, double *lrd,
+                          hipStream_t s) {
     if (n == 0 || k <= 0) return hipSuccess;
     const int L = lof_group(k);
     hipLaunchKernelGGL((lof_lrd_kernel<T>), dim3(lof_grid(n, L)), dim3(256), 0, s, ids, dist, kdist, n, k, L, lrd);
     return hipGetLastError();
 }
-hipError_t launch_lof_lrd_f32(const uint32_t *ids, const float *dist, const float *kdist, size_t n, int k, double *lrd,
-                              hipStream_t s) {
-    return launch_lof_lrd<float>(ids, dist, kdist, n, k, lrd, s);
-}
-hipError_t launch_lof_lrd_f64(const uint32_t *ids, const double *dist, const double *kdist, size_t n, int k, double *lrd,
-                              hipStream_t s) {
-    return launch_lof_lrd<double>(ids, dist, kdist, n, k, lrd, s);
-}
+template hipError_t launch_lof_lrd<float>(const uint32_t *, const float *, const float *, size_t, int, double *,
+                                          hipStream_t);
+template hipError_t launch_lof_lrd<double>(const uint32_t *, const double *, const double *, size_t, int, double *,
+                                           hipStream_t);
 hipError_t launch_lof_lof(const uint32_t *ids, const double *lrd, size_t n, int k, double *lof, hipStream_t s) {
     if (n == 0 || k <= 0) return hipSuccess;
     const int L = lof_group(k);
@@ -188,21 +180,17 @@ hipError_t launch_lof_lof(const uint32_t *ids, const double *lrd, size_t n, int 
 }
 
 template <typename T>
-static hipError_t launch_lof_score(const uint64_t *q_idx, const T *q_dist, size_t nq, int k, uint64_t index_base, size_t n,
-                                   const double *lrd, const T *kdist, double *score, hipStream_t s) {
+hipError_t launch_lof_score(const uint64_t *q_idx, const T *q_dist, size_t nq, int k, uint64_t index_base, size_t n,
+                            const double *lrd, const T *kdist, double *score, hipStream_t s) {
     if (nq == 0 || k <= 0) return hipSuccess;
     const int L = lof_group(k);
     hipLaunchKernelGGL((lof_score_kernel<T>), dim3(lof_grid(nq, L)), dim3(256), 0, s, q_idx, q_dist, nq, k, L, index_base, n,
                        lrd, kdist, score);
     return hipGetLastError();
 }
-hipError_t launch_lof_score_f32(const uint64_t *q_idx, const float *q_dist, size_t nq, int k, uint64_t index_base, size_t n,
-                                const double *lrd, const float *kdist, double *score, hipStream_t s) {
-    return launch_lof_score<float>(q_idx, q_dist, nq, k, index_base, n, lrd, kdist, score, s);
-}
-hipError_t launch_lof_score_f64(const uint64_t *q_idx, const double *q_dist, size_t nq, int k, uint64_t index_base, size_t n,
-                                const double *lrd, const double *kdist, double *score, hipStream_t s) {
-    return launch_lof_score<double>(q_idx, q_dist, nq, k, index_base, n, lrd, kdist, score, s);
-}
+template hipError_t launch_lof_score<float>(const uint64_t *, const float *, size_t, int, uint64_t, size_t,
+                                            const double *, const float *, double *, hipStream_t);
+template hipError_t launch_lof_score<double>(const uint64_t *, const double *, size_t, int, uint64_t, size_t,
+                                             const double *, const double *, double *, hipStream_t);
 
 }  // namespace pn

@@ -349,16 +349,7 @@ struct Layout {
                              hipGetErrorString(e_));                                                         \
     } while (0)
 
-inline hipError_t mst_launch_scan(const float *P, size_t n, int dim, size_t ld, const uint32_t *qsel, int nq, size_t seg_len,
-                                  int nseg, const uint32_t *comp, const uint32_t *ckey, const float *cnorm, uint32_t *sk,
-                                  uint32_t *sj, hipStream_t s) {
-    return launch_mst_scan_f32(P, n, dim, ld, qsel, nq, seg_len, nseg, comp, ckey, cnorm, sk, sj, s);
-}
-inline hipError_t mst_launch_scan(const double *P, size_t n, int dim, size_t ld, const uint32_t *qsel, int nq, size_t seg_len,
-                                  int nseg, const uint32_t *comp, const uint64_t *ckey, const double *cnorm, uint64_t *sk,
-                                  uint32_t *sj, hipStream_t s) {
-    return launch_mst_scan_f64(P, n, dim, ld, qsel, nq, seg_len, nseg, comp, ckey, cnorm, sk, sj, s);
-}
+}  // namespace
 
 template <typename T>
 int mst_enqueue(MstArgs &a, hipStream_t s) {
@@ -394,8 +385,8 @@ int mst_enqueue(MstArgs &a, hipStream_t s) {
             const size_t seg_tiles = (row_tiles + nseg - 1) / nseg;
             nseg = (row_tiles + seg_tiles - 1) / seg_tiles;
             if (nseg * qt * kTileQ > L.seg_entries) return set_error(PN_ERR_DEVICE, "MST scan plan exceeds its scratch (internal error)");
-            MSTCHK(mst_launch_scan(P, n, a.dim, a.ld, list + r0, (int)nq, seg_tiles * kTileP, (int)nseg, comp, ckey, cnorm,
-                                   seg_key, seg_j, s));
+            MSTCHK(launch_mst_scan<T>(P, n, a.dim, a.ld, list + r0, (int)nq, seg_tiles * kTileP, (int)nseg, comp, ckey, cnorm,
+                                      seg_key, seg_j, s));
             hipLaunchKernelGGL((mst_reduce_kernel<K>), rows_grid(nq), blk, 0, s, list + r0, nq, qt * kTileQ, (int)nseg, seg_key,
                                seg_j, cand_key, cand_j);
             MSTCHK(hipGetLastError());
@@ -479,8 +470,6 @@ int mst_enqueue(MstArgs &a, hipStream_t s) {
     return PN_OK;
 }
 
-}  // namespace
-
 size_t mst_buffer_bytes(size_t n, int elem_bytes, size_t batch, int n_cu) {
     if (n < 2) return 0;
     return Layout(n, elem_bytes, batch ? batch : 1, n_cu).total;
@@ -493,7 +482,7 @@ size_t sort_key_pair_len(size_t count) {
 hipError_t launch_sort_key_pair_u64(uint64_t *key, unsigned long long *pair, size_t N, hipStream_t s) {
     return sort_key_pair<uint64_t>(key, pair, N, s);
 }
-int mst_enqueue_f32(MstArgs &a, hipStream_t s) { return mst_enqueue<float>(a, s); }
-int mst_enqueue_f64(MstArgs &a, hipStream_t s) { return mst_enqueue<double>(a, s); }
+template int mst_enqueue<float>(MstArgs &, hipStream_t);
+template int mst_enqueue<double>(MstArgs &, hipStream_t);
 
 }  // namespace pn

@@ -300,62 +300,45 @@ __global__ __launch_bounds__(256) void optics_label_kernel(const uint64_t *__res
 
 // ---- launchers
 template <typename T>
-static hipError_t optics_core_t(const T *in_dist, size_t nq, size_t k, T max_eps, T *core, T *radii, hipStream_t s) {
+hipError_t launch_optics_core(const T *in_dist, size_t nq, size_t k, T max_eps, T *core, T *radii, hipStream_t s) {
     if (!nq) return hipSuccess;
     hipLaunchKernelGGL((optics_core_kernel<T>), dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, in_dist, nq, k, max_eps, core,
                        radii);
     return hipGetLastError();
 }
-hipError_t launch_optics_core_f32(const float *in_dist, size_t nq, size_t k, float max_eps, float *core, float *radii,
-                                  hipStream_t s) {
-    return optics_core_t<float>(in_dist, nq, k, max_eps, core, radii, s);
-}
-hipError_t launch_optics_core_f64(const double *in_dist, size_t nq, size_t k, double max_eps, double *core, double *radii,
-                                  hipStream_t s) {
-    return optics_core_t<double>(in_dist, nq, k, max_eps, core, radii, s);
-}
+template hipError_t launch_optics_core<float>(const float *, size_t, size_t, float, float *, float *, hipStream_t);
+template hipError_t launch_optics_core<double>(const double *, size_t, size_t, double, double *, double *, hipStream_t);
 template <typename T>
-static hipError_t optics_repack_t(const uint64_t *in_off, const uint64_t *in_idx, const T *in_dist, uint64_t in_cap, size_t rows,
-                                  size_t row0, uint64_t index_base, const uint64_t *off, uint32_t *ids, T *dist, hipStream_t s) {
+hipError_t launch_optics_repack(const uint64_t *in_off, const uint64_t *in_idx, const T *in_dist, uint64_t in_cap,
+                                size_t rows, size_t row0, uint64_t index_base, const uint64_t *off, uint32_t *ids,
+                                T *dist, hipStream_t s) {
     if (!rows) return hipSuccess;
     hipLaunchKernelGGL((optics_repack_kernel<T>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, in_off, in_idx, in_dist, in_cap,
                        rows, row0, index_base, off, ids, dist);
     return hipGetLastError();
 }
-hipError_t launch_optics_repack_f32(const uint64_t *in_off, const uint64_t *in_idx, const float *in_dist, uint64_t in_cap,
-                                    size_t rows, size_t row0, uint64_t index_base, const uint64_t *off, uint32_t *ids,
-                                    float *dist, hipStream_t s) {
-    return optics_repack_t<float>(in_off, in_idx, in_dist, in_cap, rows, row0, index_base, off, ids, dist, s);
-}
-hipError_t launch_optics_repack_f64(const uint64_t *in_off, const uint64_t *in_idx, const double *in_dist, uint64_t in_cap,
-                                    size_t rows, size_t row0, uint64_t index_base, const uint64_t *off, uint32_t *ids,
-                                    double *dist, hipStream_t s) {
-    return optics_repack_t<double>(in_off, in_idx, in_dist, in_cap, rows, row0, index_base, off, ids, dist, s);
-}
+template hipError_t launch_optics_repack<float>(const uint64_t *, const uint64_t *, const float *, uint64_t, size_t,
+                                                size_t, uint64_t, const uint64_t *, uint32_t *, float *, hipStream_t);
+template hipError_t launch_optics_repack<double>(const uint64_t *, const uint64_t *, const double *, uint64_t, size_t,
+                                                 size_t, uint64_t, const uint64_t *, uint32_t *, double *, hipStream_t);
 size_t optics_tree_bytes(size_t n, int elem_bytes) { return optics_tree_keys(n) * (elem_bytes == 4 ? 8 : 16); }
 template <typename T>
-static hipError_t optics_order_t(size_t n, const uint64_t *off, const uint32_t *ids, const T *dist, uint64_t n_entries,
-                                 const T *core, void *tree, uint64_t *ordering, T *reach, int64_t *pred, hipStream_t s) {
+hipError_t launch_optics_order(size_t n, const uint64_t *off, const uint32_t *ids, const T *dist, uint64_t n_entries,
+                               const T *core, void *tree, uint64_t *ordering, T *reach, int64_t *pred, hipStream_t s) {
     if (!n) return hipSuccess;
     hipLaunchKernelGGL((optics_order_kernel<T>), dim3(1), dim3(kOptThreads), 0, s, (uint32_t)n, off, ids, dist, n_entries, core,
                        tree, ordering, reach, pred);
     return hipGetLastError();
 }
-hipError_t launch_optics_order_f32(size_t n, const uint64_t *off, const uint32_t *ids, const float *dist, uint64_t n_entries,
-                                   const float *core, void *tree, uint64_t *ordering, float *reach, int64_t *pred,
-                                   hipStream_t s) {
-    return optics_order_t<float>(n, off, ids, dist, n_entries, core, tree, ordering, reach, pred, s);
-}
-hipError_t launch_optics_order_f64(size_t n, const uint64_t *off, const uint32_t *ids, const double *dist, uint64_t n_entries,
-                                   const double *core, void *tree, uint64_t *ordering, double *reach, int64_t *pred,
-                                   hipStream_t s) {
-    return optics_order_t<double>(n, off, ids, dist, n_entries, core, tree, ordering, reach, pred, s);
-}
+template hipError_t launch_optics_order<float>(size_t, const uint64_t *, const uint32_t *, const float *, uint64_t,
+                                               const float *, void *, uint64_t *, float *, int64_t *, hipStream_t);
+template hipError_t launch_optics_order<double>(size_t, const uint64_t *, const uint32_t *, const double *, uint64_t,
+                                                const double *, void *, uint64_t *, double *, int64_t *, hipStream_t);
 // buf: optics_extract_bytes(n) bytes of scratch
 size_t optics_extract_bytes(size_t n) { return (n + 1 + n / 4096 + 2) * sizeof(uint64_t) + (2 * n + 2) * sizeof(uint32_t); }
 template <typename T>
-static hipError_t optics_extract_t(const uint64_t *ordering, const T *reach, const T *core, size_t n, T eps, void *buf,
-                                   int64_t *labels, uint64_t *n_clusters, int32_t *d_error, hipStream_t s) {
+hipError_t launch_optics_extract(const uint64_t *ordering, const T *reach, const T *core, size_t n, T eps, void *buf,
+                                 int64_t *labels, uint64_t *n_clusters, int32_t *d_error, hipStream_t s) {
     uint64_t *excl = (uint64_t *)buf, *scan = excl + n + 1;
     uint32_t *flag = (uint32_t *)(scan + n / 4096 + 2), *seen = flag + n, *err = seen + n;
     hipError_t e = hipMemsetAsync(seen, 0, (n + 1) * sizeof(uint32_t), s);  // (seen and the error word behind it)
@@ -368,13 +351,9 @@ static hipError_t optics_extract_t(const uint64_t *ordering, const T *reach, con
                        n_clusters, err, d_error);
     return hipGetLastError();
 }
-hipError_t launch_optics_extract_f32(const uint64_t *ordering, const float *reach, const float *core, size_t n, float eps,
-                                     void *buf, int64_t *labels, uint64_t *n_clusters, int32_t *d_error, hipStream_t s) {
-    return optics_extract_t<float>(ordering, reach, core, n, eps, buf, labels, n_clusters, d_error, s);
-}
-hipError_t launch_optics_extract_f64(const uint64_t *ordering, const double *reach, const double *core, size_t n, double eps,
-                                     void *buf, int64_t *labels, uint64_t *n_clusters, int32_t *d_error, hipStream_t s) {
-    return optics_extract_t<double>(ordering, reach, core, n, eps, buf, labels, n_clusters, d_error, s);
-}
+template hipError_t launch_optics_extract<float>(const uint64_t *, const float *, const float *, size_t, float, void *,
+                                                 int64_t *, uint64_t *, int32_t *, hipStream_t);
+template hipError_t launch_optics_extract<double>(const uint64_t *, const double *, const double *, size_t, double,
+                                                  void *, int64_t *, uint64_t *, int32_t *, hipStream_t);
 
 }  // namespace pn

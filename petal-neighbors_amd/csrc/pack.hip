@@ -21,8 +21,8 @@ __global__ void pack_rows_kernel(const T *__restrict__ src, size_t n, size_t col
 }
 
 template <typename T>
-static hipError_t launch_pack_rows(const T *src, size_t n, size_t cols, size_t row_stride, T *dst, size_t n_pad,
-                                   size_t ld, hipStream_t s) {
+hipError_t launch_pack_rows(const T *src, size_t n, size_t cols, size_t row_stride, T *dst, size_t n_pad, size_t ld,
+                            hipStream_t s) {
     const size_t total = n_pad * ld;
     if (total == 0) return hipSuccess;
     size_t blocks = (total + 255) / 256;
@@ -31,14 +31,10 @@ static hipError_t launch_pack_rows(const T *src, size_t n, size_t cols, size_t r
                        n_pad, ld);
     return hipGetLastError();
 }
-hipError_t launch_pack_rows_f32(const float *src, size_t n, size_t cols, size_t row_stride, float *dst, size_t n_pad,
-                                size_t ld, hipStream_t s) {
-    return launch_pack_rows<float>(src, n, cols, row_stride, dst, n_pad, ld, s);
-}
-hipError_t launch_pack_rows_f64(const double *src, size_t n, size_t cols, size_t row_stride, double *dst,
-                                size_t n_pad, size_t ld, hipStream_t s) {
-    return launch_pack_rows<double>(src, n, cols, row_stride, dst, n_pad, ld, s);
-}
+template hipError_t launch_pack_rows<float>(const float *, size_t, size_t, size_t, float *, size_t, size_t,
+                                            hipStream_t);
+template hipError_t launch_pack_rows<double>(const double *, size_t, size_t, size_t, double *, size_t, size_t,
+                                             hipStream_t);
 
 // ---------------------------------------------------------------------------
 // counter-based generator shared (by restatement) with oracle_fill_uniform_f32

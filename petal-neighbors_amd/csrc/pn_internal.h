@@ -76,27 +76,18 @@ inline size_t round_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 // pnorm / qnorm (nullable, together): the index's metric is Cosine -- distance = 1 - dot / (qnorm[q] pnorm[row])
 // qsel (nullable, f32 Euclidean only): query r of the launch is row qsel[nq_off + r] of Q -- the flagged queries of a
 // filter tier read in place (no gather launch)
-hipError_t launch_exact_knn_f32(const float *P, size_t n, int dim, size_t ldp, const float *Q, int nq,
-                                size_t ldq, int kp, size_t seg_len, const CandBuf &cb, const void *lo_key,
-                                const uint32_t *lo_idx, const uint32_t *nq_dev, uint32_t nq_off, const float *pnorm,
-                                const float *qnorm, hipStream_t s, const uint32_t *qsel = nullptr);
-hipError_t launch_exact_knn_f64(const double *P, size_t n, int dim, size_t ldp, const double *Q, int nq,
-                                size_t ldq, int kp, size_t seg_len, const CandBuf &cb, const void *lo_key,
-                                const uint32_t *lo_idx, const uint32_t *nq_dev, uint32_t nq_off, const double *pnorm,
-                                const double *qnorm, hipStream_t s, const uint32_t *qsel = nullptr);
+template <typename T>
+hipError_t launch_exact_knn(const T *P, size_t n, int dim, size_t ldp, const T *Q, int nq, size_t ldq, int kp,
+                            size_t seg_len, const CandBuf &cb, const void *lo_key, const uint32_t *lo_idx,
+                            const uint32_t *nq_dev, uint32_t nq_off, const T *pnorm, const T *qnorm, hipStream_t s,
+                            const uint32_t *qsel = nullptr);
 // radius: count pass (fill == nullptr) then fill pass.  counts/offsets are [query][seg].
-hipError_t launch_exact_radius_f32(const float *P, size_t n, int dim, size_t ldp, const float *Q, int nq,
-                                   size_t ldq, float r, size_t seg_len, int nseg, uint32_t *counts,
-                                   const uint64_t *offsets, uint64_t *fill, uint64_t index_base, const float *pnorm,
-                                   const float *qnorm, hipStream_t s, const uint32_t *qsel = nullptr,
-                                   const uint32_t *nq_dev = nullptr, uint64_t capacity = ~0ull,
-                                   float *fill_dist = nullptr, const float *radii = nullptr);
-hipError_t launch_exact_radius_f64(const double *P, size_t n, int dim, size_t ldp, const double *Q, int nq,
-                                   size_t ldq, double r, size_t seg_len, int nseg, uint32_t *counts,
-                                   const uint64_t *offsets, uint64_t *fill, uint64_t index_base, const double *pnorm,
-                                   const double *qnorm, hipStream_t s, const uint32_t *qsel = nullptr,
-                                   const uint32_t *nq_dev = nullptr, uint64_t capacity = ~0ull,
-                                   double *fill_dist = nullptr, const double *radii = nullptr);
+template <typename T>
+hipError_t launch_exact_radius(const T *P, size_t n, int dim, size_t ldp, const T *Q, int nq, size_t ldq, T r,
+                               size_t seg_len, int nseg, uint32_t *counts, const uint64_t *offsets, uint64_t *fill,
+                               uint64_t index_base, const T *pnorm, const T *qnorm, hipStream_t s,
+                               const uint32_t *qsel = nullptr, const uint32_t *nq_dev = nullptr,
+                               uint64_t capacity = ~0ull, T *fill_dist = nullptr, const T *radii = nullptr);
 // qsel / nq_dev (nullable): query r of the launch is row qsel[r] of Q, only the first *nq_dev listed queries exist (grid
 // sized for nq); counts / offsets indexed by r.  capacity: fill positions at or beyond it are not written.
 // fill_dist (nullable): the fill pass also writes each listed row's distance at its position
@@ -126,30 +117,23 @@ hipError_t launch_radius_gather_cap(const uint32_t *kept, const uint32_t *nkept,
 
 // ---- self_graph.hip: self-queries of an index (pn_query_self_*, pn_query_radius_self_*)
 // out[q][r] (r < kout = kin - 1) <- in[q][r] with the entry equal to self0 + q dropped, else the last one
-hipError_t launch_knn_self_exclude_f32(const uint64_t *in_idx, const float *in_dist, size_t nq, int kin, int kout,
-                                       uint64_t self0, uint64_t *out_idx, float *out_dist, hipStream_t s);
-hipError_t launch_knn_self_exclude_f64(const uint64_t *in_idx, const double *in_dist, size_t nq, int kin, int kout,
-                                       uint64_t self0, uint64_t *out_idx, double *out_dist, hipStream_t s);
+template <typename T>
+hipError_t launch_knn_self_exclude(const uint64_t *in_idx, const T *in_dist, size_t nq, int kin, int kout,
+                                   uint64_t self0, uint64_t *out_idx, T *out_dist, hipStream_t s);
 // flag[i] <- exclude && distance(p_i, p_i) < r in the metric's arithmetic (cnorm: the rows' Cosine norms, NULL for
 // Euclidean); cnt[i] <- in_off[i + 1] - in_off[i] - flag[i]; *bad += flagged rows with an empty list (never, see the kernel)
-hipError_t launch_radius_self_counts_f32(const float *P, size_t n, int dim, size_t ld, const float *cnorm, float r,
-                                         bool exclude, const uint64_t *in_off, uint32_t *flag, uint32_t *cnt, uint32_t *bad,
-                                         hipStream_t s, const float *radii = nullptr);
-hipError_t launch_radius_self_counts_f64(const double *P, size_t n, int dim, size_t ld, const double *cnorm, double r,
-                                         bool exclude, const uint64_t *in_off, uint32_t *flag, uint32_t *cnt, uint32_t *bad,
-                                         hipStream_t s, const double *radii = nullptr);
+template <typename T>
+hipError_t launch_radius_self_counts(const T *P, size_t n, int dim, size_t ld, const T *cnorm, T r, bool exclude,
+                                     const uint64_t *in_off, uint32_t *flag, uint32_t *cnt, uint32_t *bad,
+                                     hipStream_t s, const T *radii = nullptr);
 // out[1 + j] <- out[0] + part[j + 1], j < nq (a chunk's scan behind the rows before it)
 hipError_t launch_radius_self_place(const uint64_t *part, size_t nq, uint64_t *out, hipStream_t s);
 // out[out_off[i] + t] <- row i's list (in_off, ascending index, entries below in_cap) without self0 + i where flag[i],
 // positions below cap only; out_dist / in_dist nullable together; *bad += flagged, wholly written lists without it
-hipError_t launch_radius_self_compact_f32(const uint64_t *in_off, const uint64_t *in_idx, const float *in_dist,
-                                          uint64_t in_cap, const uint32_t *flag, const uint64_t *out_off, size_t n,
-                                          uint64_t self0, uint64_t *out_idx, float *out_dist, uint64_t cap, uint32_t *bad,
-                                          hipStream_t s);
-hipError_t launch_radius_self_compact_f64(const uint64_t *in_off, const uint64_t *in_idx, const double *in_dist,
-                                          uint64_t in_cap, const uint32_t *flag, const uint64_t *out_off, size_t n,
-                                          uint64_t self0, uint64_t *out_idx, double *out_dist, uint64_t cap, uint32_t *bad,
-                                          hipStream_t s);
+template <typename T>
+hipError_t launch_radius_self_compact(const uint64_t *in_off, const uint64_t *in_idx, const T *in_dist, uint64_t in_cap,
+                                      const uint32_t *flag, const uint64_t *out_off, size_t n, uint64_t self0,
+                                      uint64_t *out_idx, T *out_dist, uint64_t cap, uint32_t *bad, hipStream_t s);
 
 // ---- components.hip: DBSCAN over the radius self-lists (pn_dbscan_*): lock-free union-find on the core rows
 // core[i] <- off[i + 1] - off[i] >= min_samples; parent[i] <- i; side_len[i] <- core[i] ? 0 : the list's length
@@ -173,12 +157,10 @@ hipError_t launch_dbscan_noise(size_t n, int64_t *labels, uint8_t *core, uint64_
 // [0, n) in nseg segments of seg_len rows (a multiple of kTileP): seg_key / seg_j [seg][round_up(nq, kTileQ)] <- the
 // segment's least (key(max(d, core keys)), j) over rows j with comp[j] != comp[qsel[r]], or (kMax, 0xFFFFFFFF).
 // comp / ckey: [n]; cnorm: the rows' Cosine norms, NULL for Euclidean (then the keys are the unsigned ones)
-hipError_t launch_mst_scan_f32(const float *P, size_t n, int dim, size_t ldp, const uint32_t *qsel, int nq, size_t seg_len,
-                               int nseg, const uint32_t *comp, const uint32_t *ckey, const float *cnorm, uint32_t *seg_key,
-                               uint32_t *seg_j, hipStream_t s);
-hipError_t launch_mst_scan_f64(const double *P, size_t n, int dim, size_t ldp, const uint32_t *qsel, int nq, size_t seg_len,
-                               int nseg, const uint32_t *comp, const uint64_t *ckey, const double *cnorm, uint64_t *seg_key,
-                               uint32_t *seg_j, hipStream_t s);
+template <typename T>
+hipError_t launch_mst_scan(const T *P, size_t n, int dim, size_t ldp, const uint32_t *qsel, int nq, size_t seg_len,
+                           int nseg, const uint32_t *comp, const typename KeyOf<T>::type *ckey, const T *cnorm,
+                           typename KeyOf<T>::type *seg_key, uint32_t *seg_j, hipStream_t s);
 
 // ---- mst.hip: Boruvka under the strict edge order (pn_mst_*): bookkeeping kernels and the round loop
 struct MstArgs {
@@ -201,8 +183,8 @@ struct MstArgs {
 };
 size_t mst_buffer_bytes(size_t n, int elem_bytes, size_t batch, int n_cu);
 // enqueues on s, blocks the host once per round; PN_OK or an error code with pn_last_error() set
-int mst_enqueue_f32(MstArgs &a, hipStream_t s);
-int mst_enqueue_f64(MstArgs &a, hipStream_t s);
+template <typename T>
+int mst_enqueue(MstArgs &a, hipStream_t s);
 
 // ---- linkage.hip: the single-linkage dendrogram of sorted tree edges (pn_linkage_*) and HDBSCAN's extraction from it
 // (pn_hdbscan_*); nothing in it waits for the device
@@ -218,9 +200,9 @@ struct LinkageArgs {
     int32_t *d_err = nullptr;
 };
 size_t linkage_buffer_bytes(size_t n);
-int linkage_enqueue_f32(const LinkageArgs &a, hipStream_t s);
-int linkage_enqueue_f64(const LinkageArgs &a, hipStream_t s);
-// the extraction reads the dendrogram that linkage_enqueue_* left at the head of the same buffer; n >= min_cluster_size
+template <typename T>
+int linkage_enqueue(const LinkageArgs &a, hipStream_t s);
+// the extraction reads the dendrogram that linkage_enqueue left at the head of the same buffer; n >= min_cluster_size
 struct HdbscanArgs {
     size_t n = 0, min_cluster_size = 2;
     const void *d_weight = nullptr;  // [n - 1] of T: the merge weights
@@ -230,30 +212,27 @@ struct HdbscanArgs {
     uint64_t *d_n_clusters = nullptr;  // [1], nullable
 };
 size_t hdbscan_buffer_bytes(size_t n);
-int hdbscan_extract_enqueue_f32(const HdbscanArgs &a, hipStream_t s);
-int hdbscan_extract_enqueue_f64(const HdbscanArgs &a, hipStream_t s);
+template <typename T>
+int hdbscan_extract_enqueue(const HdbscanArgs &a, hipStream_t s);
 // out[i] = d[i][k - 1] of a [rows][k] matrix (the core distances out of a self-query's answer)
-hipError_t launch_last_column_f32(const float *d, size_t rows, size_t k, float *out, hipStream_t s);
-hipError_t launch_last_column_f64(const double *d, size_t rows, size_t k, double *out, hipStream_t s);
+template <typename T>
+hipError_t launch_last_column(const T *d, size_t rows, size_t k, T *out, hipStream_t s);
 
 // ---- lof.hip: Local Outlier Factor over the self-k-NN graph (pn_lof_*, pn_lof_score_*); nothing in it waits for the device.
 // pack: a self-query chunk's answer [nq][k] (ids with the index base) -> the store's rows: ids [nq][k] uint32 without the
 // base, dist [nq][k], kdist [nq] = the last column
-hipError_t launch_lof_pack_f32(const uint64_t *in_idx, const float *in_dist, size_t nq, int k, uint64_t index_base,
-                               uint32_t *ids, float *dist, float *kdist, hipStream_t s);
-hipError_t launch_lof_pack_f64(const uint64_t *in_idx, const double *in_dist, size_t nq, int k, uint64_t index_base,
-                               uint32_t *ids, double *dist, double *kdist, hipStream_t s);
+template <typename T>
+hipError_t launch_lof_pack(const uint64_t *in_idx, const T *in_dist, size_t nq, int k, uint64_t index_base,
+                           uint32_t *ids, T *dist, T *kdist, hipStream_t s);
 // lrd [n] from the store and kdist [n]; lof [n] from the store's ids and lrd [n]
-hipError_t launch_lof_lrd_f32(const uint32_t *ids, const float *dist, const float *kdist, size_t n, int k, double *lrd,
-                              hipStream_t s);
-hipError_t launch_lof_lrd_f64(const uint32_t *ids, const double *dist, const double *kdist, size_t n, int k, double *lrd,
-                              hipStream_t s);
+template <typename T>
+hipError_t launch_lof_lrd(const uint32_t *ids, const T *dist, const T *kdist, size_t n, int k, double *lrd,
+                          hipStream_t s);
 hipError_t launch_lof_lof(const uint32_t *ids, const double *lrd, size_t n, int k, double *lof, hipStream_t s);
 // score [nq] of queries from their k-NN answer [nq][k] (ids with the index base) and the fit's lrd [n], kdist [n]
-hipError_t launch_lof_score_f32(const uint64_t *q_idx, const float *q_dist, size_t nq, int k, uint64_t index_base, size_t n,
-                                const double *lrd, const float *kdist, double *score, hipStream_t s);
-hipError_t launch_lof_score_f64(const uint64_t *q_idx, const double *q_dist, size_t nq, int k, uint64_t index_base, size_t n,
-                                const double *lrd, const double *kdist, double *score, hipStream_t s);
+template <typename T>
+hipError_t launch_lof_score(const uint64_t *q_idx, const T *q_dist, size_t nq, int k, uint64_t index_base, size_t n,
+                            const double *lrd, const T *kdist, double *score, hipStream_t s);
 
 // ---- kde.hip: kernel density sums over the radius lists (pn_kde_*); nothing in it waits for the device.
 // hq [nq] <- h broadcast (n_h = 1) or copied (n_h = nq); cut [nq] <- the cutoffs.  mode 0: cut = h; 1: the smallest T >=
@@ -387,34 +366,26 @@ hipError_t launch_sort_key_pair_u64(uint64_t *key, unsigned long long *pair, siz
 // nothing in it waits for the device.
 // core[i] <- v < max_eps ? v : +inf, v = in_dist[i][k - 1] of a self-query chunk's answer [nq][k] (in_dist == nullptr: +inf);
 // radii[i] <- max_eps where core[i] is finite, else 0 (the row's list stays empty)
-hipError_t launch_optics_core_f32(const float *in_dist, size_t nq, size_t k, float max_eps, float *core, float *radii,
-                                  hipStream_t s);
-hipError_t launch_optics_core_f64(const double *in_dist, size_t nq, size_t k, double max_eps, double *core, double *radii,
-                                  hipStream_t s);
+template <typename T>
+hipError_t launch_optics_core(const T *in_dist, size_t nq, size_t k, T max_eps, T *core, T *radii, hipStream_t s);
 // a fill piece's lists (rows [row0, row0 + rows), piece-local offsets in_off, 64-bit ids with the index base, the rows
 // themselves among them; entries below in_cap are there) -> the graph store at the final offsets off[row0 ..]: uint32 ids
 // without the base, the row itself dropped
-hipError_t launch_optics_repack_f32(const uint64_t *in_off, const uint64_t *in_idx, const float *in_dist, uint64_t in_cap,
-                                    size_t rows, size_t row0, uint64_t index_base, const uint64_t *off, uint32_t *ids,
-                                    float *dist, hipStream_t s);
-hipError_t launch_optics_repack_f64(const uint64_t *in_off, const uint64_t *in_idx, const double *in_dist, uint64_t in_cap,
-                                    size_t rows, size_t row0, uint64_t index_base, const uint64_t *off, uint32_t *ids,
-                                    double *dist, hipStream_t s);
+template <typename T>
+hipError_t launch_optics_repack(const uint64_t *in_off, const uint64_t *in_idx, const T *in_dist, uint64_t in_cap,
+                                size_t rows, size_t row0, uint64_t index_base, const uint64_t *off, uint32_t *ids,
+                                T *dist, hipStream_t s);
 // the ordering: one workgroup runs the n steps.  tree: optics_tree_bytes(n, sizeof T) bytes, 16-byte aligned; pred nullable
 size_t optics_tree_bytes(size_t n, int elem_bytes);
-hipError_t launch_optics_order_f32(size_t n, const uint64_t *off, const uint32_t *ids, const float *dist, uint64_t n_entries,
-                                   const float *core, void *tree, uint64_t *ordering, float *reach, int64_t *pred,
-                                   hipStream_t s);
-hipError_t launch_optics_order_f64(size_t n, const uint64_t *off, const uint32_t *ids, const double *dist, uint64_t n_entries,
-                                   const double *core, void *tree, uint64_t *ordering, double *reach, int64_t *pred,
-                                   hipStream_t s);
+template <typename T>
+hipError_t launch_optics_order(size_t n, const uint64_t *off, const uint32_t *ids, const T *dist, uint64_t n_entries,
+                               const T *core, void *tree, uint64_t *ordering, T *reach, int64_t *pred, hipStream_t s);
 // labels of the DBSCAN clustering at eps from an ordering; buf: optics_extract_bytes(n) bytes; n_clusters, d_error nullable
 // (*d_error <- PN_OK, or PN_ERR_INVALID when ordering is no permutation of 0 .. n - 1: the labels are then unspecified)
 size_t optics_extract_bytes(size_t n);
-hipError_t launch_optics_extract_f32(const uint64_t *ordering, const float *reach, const float *core, size_t n, float eps,
-                                     void *buf, int64_t *labels, uint64_t *n_clusters, int32_t *d_error, hipStream_t s);
-hipError_t launch_optics_extract_f64(const uint64_t *ordering, const double *reach, const double *core, size_t n, double eps,
-                                     void *buf, int64_t *labels, uint64_t *n_clusters, int32_t *d_error, hipStream_t s);
+template <typename T>
+hipError_t launch_optics_extract(const uint64_t *ordering, const T *reach, const T *core, size_t n, T eps, void *buf,
+                                 int64_t *labels, uint64_t *n_clusters, int32_t *d_error, hipStream_t s);
 
 // ---- csr_sort.hip: order every list of a radius answer by (distance, index) in place (PN_RADIUS_SORTED)
 constexpr int kSortTile = 2048;  // longest list sorted by one workgroup in LDS; longer lists: chunks + merge passes
@@ -428,40 +399,31 @@ struct CsrSortScratch {
 // entries of the ping-pong copy a call needs (0: no list can exceed kSortTile entries); max_row bounds every list's
 // length (the corpus' rows), limit the positions sorted (lists that do not end at or below it are left unsorted)
 size_t csr_sort_scratch_entries(size_t nq, size_t max_row, size_t limit);
-hipError_t launch_csr_sort_f32(const uint64_t *offsets, int nq, uint64_t *idx, float *dist, uint64_t limit, size_t max_row,
-                               const CsrSortScratch &w, int n_cu, hipStream_t s);
-hipError_t launch_csr_sort_f64(const uint64_t *offsets, int nq, uint64_t *idx, double *dist, uint64_t limit, size_t max_row,
-                               const CsrSortScratch &w, int n_cu, hipStream_t s);
+template <typename T>
+hipError_t launch_csr_sort(const uint64_t *offsets, int nq, uint64_t *idx, T *dist, uint64_t limit, size_t max_row,
+                           const CsrSortScratch &w, int n_cu, hipStream_t s);
 // Cosine's norms: norms[i] = sqrt(sequential sum of x_i[k]^2, k < dim) in T
-hipError_t launch_cosine_norms_f32(const float *X, size_t n, int dim, size_t ld, float *norms, hipStream_t s);
-hipError_t launch_cosine_norms_f64(const double *X, size_t n, int dim, size_t ld, double *norms, hipStream_t s);
-hipError_t launch_exact_pairwise_f32(const float *X, size_t n, int dim, size_t ld, float *out, hipStream_t s);
-hipError_t launch_exact_pairwise_f64(const double *X, size_t n, int dim, size_t ld, double *out, hipStream_t s);
+template <typename T>
+hipError_t launch_cosine_norms(const T *X, size_t n, int dim, size_t ld, T *norms, hipStream_t s);
+template <typename T>
+hipError_t launch_exact_pairwise(const T *X, size_t n, int dim, size_t ld, T *out, hipStream_t s);
 // distance::pairwise under the Cosine metric; norms: n elements of scratch
-hipError_t launch_cosine_pairwise_f32(const float *X, size_t n, int dim, size_t ld, float *norms, float *out,
-                                      hipStream_t s);
-hipError_t launch_cosine_pairwise_f64(const double *X, size_t n, int dim, size_t ld, double *norms, double *out,
-                                      hipStream_t s);
+template <typename T>
+hipError_t launch_cosine_pairwise(const T *X, size_t n, int dim, size_t ld, T *norms, T *out, hipStream_t s);
 
 // ---- select.hip
 // Exact mode: keys are exact distance keys; picks the kout smallest (key, idx).
 // writes results r < kout of query q at [q * out_stride + out_off + r]; when lo_key != nullptr also
 // records the last (key, row) written per query as the next round's lower bound
 // osel (nullable): the results of query q go to output row osel[nq_off + q] instead of row q (scatter in place)
-hipError_t launch_select_exact_f32(const CandBuf &cb, int nq, int kout, uint64_t index_base, uint64_t *idx_out,
-                                   float *dist_out, size_t out_stride, size_t out_off, void *lo_key,
-                                   uint32_t *lo_idx, const uint32_t *nq_dev, uint32_t nq_off, bool signed_keys,
-                                   hipStream_t s, const uint32_t *osel = nullptr);
-hipError_t launch_select_exact_f64(const CandBuf &cb, int nq, int kout, uint64_t index_base, uint64_t *idx_out,
-                                   double *dist_out, size_t out_stride, size_t out_off, void *lo_key,
-                                   uint32_t *lo_idx, const uint32_t *nq_dev, uint32_t nq_off, bool signed_keys,
-                                   hipStream_t s, const uint32_t *osel = nullptr);
-hipError_t launch_select_exact_groups_f32(const CandBuf &cb, int groups, int kp, int nq, int kout, uint64_t index_base,
-                                          uint64_t *idx_out, float *dist_out, size_t out_group_stride,
-                                          const uint32_t *nq_dev, uint32_t nq_off, hipStream_t s, bool signed_keys = false);
-hipError_t launch_select_exact_groups_f64(const CandBuf &cb, int groups, int kp, int nq, int kout, uint64_t index_base,
-                                          uint64_t *idx_out, double *dist_out, size_t out_group_stride,
-                                          const uint32_t *nq_dev, uint32_t nq_off, hipStream_t s, bool signed_keys = false);
+template <typename T>
+hipError_t launch_select_exact(const CandBuf &cb, int nq, int kout, uint64_t index_base, uint64_t *idx_out, T *dist_out,
+                               size_t out_stride, size_t out_off, void *lo_key, uint32_t *lo_idx, const uint32_t *nq_dev,
+                               uint32_t nq_off, bool signed_keys, hipStream_t s, const uint32_t *osel = nullptr);
+template <typename T>
+hipError_t launch_select_exact_groups(const CandBuf &cb, int groups, int kp, int nq, int kout, uint64_t index_base,
+                                      uint64_t *idx_out, T *dist_out, size_t out_group_stride, const uint32_t *nq_dev,
+                                      uint32_t nq_off, hipStream_t s, bool signed_keys = false);
 // MFMA mode: keys are f32 lower bounds L; recomputes every candidate's distance
 // in the reference's operation order, selects, and verifies the filter's
 // exclusions (flags[q] = 1 -> the query must be re-run exactly).
@@ -473,11 +435,12 @@ hipError_t launch_select_exact_groups_f64(const CandBuf &cb, int groups, int kp,
 // device counters, kPnStatWords words: [0] fallback queries, then kPnStatSlots pairs {candidates, exact evaluations}
 // that the queries add to by q mod kPnStatSlots (10^4 waves adding to ONE address cost as much as the whole kernel)
 constexpr int kPnStatSlots = 64, kPnStatWords = 4 + 2 * kPnStatSlots;
-hipError_t launch_select_rerank_f32(const CandBuf &cb, const float *P, size_t n, int dim, size_t ldp,
-                                    const float *Q, int nq, size_t ldq, int kout, uint64_t index_base,
-                                    uint64_t *idx_out, float *dist_out, size_t out_stride, uint32_t *flags,
-                                    uint32_t *n_flagged, const double *qn, const uint32_t *qbad, uint32_t *sel,
-                                    unsigned long long *stats, hipStream_t s, int first_eval = 0, int cell_max = 0);
+template <typename T>
+hipError_t launch_select_rerank(const CandBuf &cb, const T *P, size_t n, int dim, size_t ldp, const T *Q, int nq, size_t ldq,
+                                int kout, uint64_t index_base, uint64_t *idx_out, T *dist_out, size_t out_stride,
+                                uint32_t *flags, uint32_t *n_flagged, const double *qn, const uint32_t *qbad, uint32_t *sel,
+                                unsigned long long *stats, hipStream_t s, int first_eval = 0, int cell_max = 0,
+                                const T *cnorm = nullptr, const T *qnorm = nullptr);
 // first_eval: candidates (smallest bounds first) evaluated in the first round, >= kout (0: kout); cell_max: entries a
 // (segment, query) cell holds at most (0: cb.cap) -- sizes the kernel's LDS
 // The re-rank kernel's dynamic LDS: 12 (f32) or 16 (f64) bytes per entry the nseg cells of a query can hold + the query
@@ -488,46 +451,25 @@ inline size_t select_rerank_lds_bytes(int nseg, int cap, int cell_max, size_t di
     const size_t per_cell = cell_max > 0 && cell_max < cap ? (size_t)cell_max : (size_t)cap;
     return (size_t)nseg * per_cell * (elem_bytes + 8) + (dim + 8) * elem_bytes;
 }
-// f64 indexes behind the bf16 filter (qn required): distances in the reference's f64 fold, proof with u = 2^-53
-hipError_t launch_select_rerank_f64(const CandBuf &cb, const double *P, size_t n, int dim, size_t ldp,
-                                    const double *Q, int nq, size_t ldq, int kout, uint64_t index_base,
-                                    uint64_t *idx_out, double *dist_out, size_t out_stride, uint32_t *flags,
-                                    uint32_t *n_flagged, const double *qn, const uint32_t *qbad, uint32_t *sel,
-                                    unsigned long long *stats, hipStream_t s, int first_eval = 0, int cell_max = 0);
-// Cosine indexes behind the bf16 filter (select.hip, cos_proof_lb): cnorm [n] / qnorm [nq] = the rows' / queries' norms in
-// the index's type (cosine_norms_kernel), candidates evaluated by Cosine::distance, order-preserving keys of ALL floats
-hipError_t launch_select_rerank_cos_f32(const CandBuf &cb, const float *P, size_t n, int dim, size_t ldp, const float *Q,
-                                        int nq, size_t ldq, int kout, uint64_t index_base, uint64_t *idx_out,
-                                        float *dist_out, size_t out_stride, uint32_t *flags, uint32_t *n_flagged,
-                                        const double *qn, const uint32_t *qbad, uint32_t *sel, unsigned long long *stats,
-                                        hipStream_t s, int first_eval, int cell_max, const float *cnorm, const float *qnorm);
-hipError_t launch_select_rerank_cos_f64(const CandBuf &cb, const double *P, size_t n, int dim, size_t ldp, const double *Q,
-                                        int nq, size_t ldq, int kout, uint64_t index_base, uint64_t *idx_out,
-                                        double *dist_out, size_t out_stride, uint32_t *flags, uint32_t *n_flagged,
-                                        const double *qn, const uint32_t *qbad, uint32_t *sel, unsigned long long *stats,
-                                        hipStream_t s, int first_eval, int cell_max, const double *cnorm, const double *qnorm);
+// f64 indexes (behind the bf16 filter only: qn required): distances in the reference's f64 fold, proof with u = 2^-53
+// cnorm / qnorm (nullable, together): a Cosine index behind the bf16 filter (select.hip, cos_proof_lb) -- the rows' [n] /
+// queries' [nq] norms in the index's type (cosine_norms_kernel), candidates evaluated by Cosine::distance,
+// order-preserving keys of ALL floats
 // osel (nullable): the merged result of query q goes to row osel[q] of the outputs (row stride out_stride, 0 = k_out);
 // host_count (nullable, mapped pinned memory): block 0 copies *nq_dev there (the count a LATER call looks at)
 // Small corpora, a few queries per call: the whole call in one launch (one wave per query over all rows); Q and the
 // outputs may be mapped pinned host memory.  radius_mode: out row q = {count, rows ascending ...} (out_stride >= n + 1),
 // dist_out (nullable) row q = {-, their distances ...} at the same positions
 size_t tiny_query_lds_bytes(size_t n, int dim_eff, int elem_bytes);  // must be <= 64 KiB
-hipError_t launch_tiny_query_f32(const float *P, size_t n, int dim_eff, size_t ldp, const float *Q, size_t ldq, int nq,
-                                 int kout, bool radius_mode, float radius, uint64_t index_base, uint64_t *idx_out,
-                                 float *dist_out, size_t out_stride, hipStream_t s);
-hipError_t launch_tiny_query_f64(const double *P, size_t n, int dim_eff, size_t ldp, const double *Q, size_t ldq, int nq,
-                                 int kout, bool radius_mode, double radius, uint64_t index_base, uint64_t *idx_out,
-                                 double *dist_out, size_t out_stride, hipStream_t s);
-hipError_t launch_merge_topk_f32(const uint64_t *idx_parts, const float *dist_parts, int n_parts,
-                                 size_t idx_part_stride, size_t dist_part_stride, int nq, int k_part, int k_out,
-                                 uint64_t *idx_out, float *dist_out, hipStream_t s, const uint32_t *nq_dev = nullptr,
-                                 const uint32_t *osel = nullptr, size_t out_stride = 0, uint32_t *host_count = nullptr,
-                                 bool signed_keys = false);
-hipError_t launch_merge_topk_f64(const uint64_t *idx_parts, const double *dist_parts, int n_parts,
-                                 size_t idx_part_stride, size_t dist_part_stride, int nq, int k_part, int k_out,
-                                 uint64_t *idx_out, double *dist_out, hipStream_t s, const uint32_t *nq_dev = nullptr,
-                                 const uint32_t *osel = nullptr, size_t out_stride = 0, uint32_t *host_count = nullptr,
-                                 bool signed_keys = false);
+template <typename T>
+hipError_t launch_tiny_query(const T *P, size_t n, int dim_eff, size_t ldp, const T *Q, size_t ldq, int nq, int kout,
+                             bool radius_mode, T radius, uint64_t index_base, uint64_t *idx_out, T *dist_out,
+                             size_t out_stride, hipStream_t s);
+template <typename T>
+hipError_t launch_merge_topk(const uint64_t *idx_parts, const T *dist_parts, int n_parts, size_t idx_part_stride,
+                             size_t dist_part_stride, int nq, int k_part, int k_out, uint64_t *idx_out, T *dist_out,
+                             hipStream_t s, const uint32_t *nq_dev = nullptr, const uint32_t *osel = nullptr,
+                             size_t out_stride = 0, uint32_t *host_count = nullptr, bool signed_keys = false);
 // gather rows sel[off + i] of src into dst row i / scatter result rows i back to query sel[off + i], for
 // i < min(max_rows, *nsel - off): the count stays on the device
 template <typename T>  // T = float | double (explicitly instantiated)
@@ -550,10 +492,9 @@ hipError_t launch_compact_flags(const uint32_t *flags, int nq, uint32_t *sel, ui
 
 // ---- pack.hip
 // dst[r][c] = (r < n && c < cols) ? src[r*row_stride + c] : 0  for r < n_pad, c < ld
-hipError_t launch_pack_rows_f32(const float *src, size_t n, size_t cols, size_t row_stride, float *dst,
-                                size_t n_pad, size_t ld, hipStream_t s);
-hipError_t launch_pack_rows_f64(const double *src, size_t n, size_t cols, size_t row_stride, double *dst,
-                                size_t n_pad, size_t ld, hipStream_t s);
+template <typename T>
+hipError_t launch_pack_rows(const T *src, size_t n, size_t cols, size_t row_stride, T *dst, size_t n_pad, size_t ld,
+                            hipStream_t s);
 hipError_t launch_fill_uniform_f32(float *out, uint64_t count, uint64_t seed, uint64_t first, hipStream_t s);
 // scaled squared row norms for the MFMA lower bound (see mfma_filter_v2.hip)
 hipError_t launch_row_norms_f32(const float *X, size_t n_pad, size_t n, int dim, size_t ld, float alpha,

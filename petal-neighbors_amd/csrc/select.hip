@@ -185,7 +185,7 @@ __global__ __launch_bounds__(64) void select_exact_kernel(const typename KeyOf<T
 }
 
 template <typename T>
-static hipError_t launch_select_exact(const CandBuf &cb, int nq, int kout, uint64_t index_base, uint64_t *idx_out,
+static hipError_t select_exact_launch(const CandBuf &cb, int nq, int kout, uint64_t index_base, uint64_t *idx_out,
                                       T *dist_out, int kp_bound, size_t out_stride, size_t out_off, void *lo_key,
                                       uint32_t *lo_idx, const uint32_t *nq_dev, uint32_t nq_off, bool signed_keys,
                                       hipStream_t s, int groups = 1, size_t out_group_stride = 0,
@@ -203,32 +203,30 @@ static hipError_t launch_select_exact(const CandBuf &cb, int nq, int kout, uint6
 // two-level selection, first level: `groups` groups of cb.nseg segments each (cb describes group 0, the groups follow
 // each other in the candidate buffers); group g's top kout of every query to idx_out/dist_out + g * out_group_stride.
 // kp: entries a cell holds at most (the scan kernel's final compaction leaves <= its kp)
-hipError_t launch_select_exact_groups_f32(const CandBuf &cb, int groups, int kp, int nq, int kout, uint64_t index_base,
-                                          uint64_t *idx_out, float *dist_out, size_t out_group_stride,
-                                          const uint32_t *nq_dev, uint32_t nq_off, hipStream_t s, bool signed_keys) {
-    return launch_select_exact<float>(cb, nq, kout, index_base, idx_out, dist_out, kp, (size_t)kout, 0, nullptr, nullptr,
-                                      nq_dev, nq_off, signed_keys, s, groups, out_group_stride);
+template <typename T>
+hipError_t launch_select_exact_groups(const CandBuf &cb, int groups, int kp, int nq, int kout, uint64_t index_base,
+                                      uint64_t *idx_out, T *dist_out, size_t out_group_stride, const uint32_t *nq_dev,
+                                      uint32_t nq_off, hipStream_t s, bool signed_keys) {
+    return select_exact_launch<T>(cb, nq, kout, index_base, idx_out, dist_out, kp, (size_t)kout, 0, nullptr, nullptr,
+                                  nq_dev, nq_off, signed_keys, s, groups, out_group_stride);
 }
-hipError_t launch_select_exact_groups_f64(const CandBuf &cb, int groups, int kp, int nq, int kout, uint64_t index_base,
-                                          uint64_t *idx_out, double *dist_out, size_t out_group_stride,
-                                          const uint32_t *nq_dev, uint32_t nq_off, hipStream_t s, bool signed_keys) {
-    return launch_select_exact<double>(cb, nq, kout, index_base, idx_out, dist_out, kp, (size_t)kout, 0, nullptr, nullptr,
-                                       nq_dev, nq_off, signed_keys, s, groups, out_group_stride);
+template hipError_t launch_select_exact_groups<float>(const CandBuf &, int, int, int, int, uint64_t, uint64_t *, float *,
+                                                      size_t, const uint32_t *, uint32_t, hipStream_t, bool);
+template hipError_t launch_select_exact_groups<double>(const CandBuf &, int, int, int, int, uint64_t, uint64_t *, double *,
+                                                       size_t, const uint32_t *, uint32_t, hipStream_t, bool);
+template <typename T>
+hipError_t launch_select_exact(const CandBuf &cb, int nq, int kout, uint64_t index_base, uint64_t *idx_out, T *dist_out,
+                               size_t out_stride, size_t out_off, void *lo_key, uint32_t *lo_idx, const uint32_t *nq_dev,
+                               uint32_t nq_off, bool signed_keys, hipStream_t s, const uint32_t *osel) {
+    return select_exact_launch<T>(cb, nq, kout, index_base, idx_out, dist_out, cb.cap, out_stride, out_off, lo_key, lo_idx,
+                                  nq_dev, nq_off, signed_keys, s, 1, 0, osel);
 }
-hipError_t launch_select_exact_f32(const CandBuf &cb, int nq, int kout, uint64_t index_base, uint64_t *idx_out,
-                                   float *dist_out, size_t out_stride, size_t out_off, void *lo_key,
-                                   uint32_t *lo_idx, const uint32_t *nq_dev, uint32_t nq_off, bool signed_keys,
-                                   hipStream_t s, const uint32_t *osel) {
-    return launch_select_exact<float>(cb, nq, kout, index_base, idx_out, dist_out, cb.cap, out_stride, out_off,
-                                      lo_key, lo_idx, nq_dev, nq_off, signed_keys, s, 1, 0, osel);
-}
-hipError_t launch_select_exact_f64(const CandBuf &cb, int nq, int kout, uint64_t index_base, uint64_t *idx_out,
-                                   double *dist_out, size_t out_stride, size_t out_off, void *lo_key,
-                                   uint32_t *lo_idx, const uint32_t *nq_dev, uint32_t nq_off, bool signed_keys,
-                                   hipStream_t s, const uint32_t *osel) {
-    return launch_select_exact<double>(cb, nq, kout, index_base, idx_out, dist_out, cb.cap, out_stride, out_off,
-                                       lo_key, lo_idx, nq_dev, nq_off, signed_keys, s, 1, 0, osel);
-}
+template hipError_t launch_select_exact<float>(const CandBuf &, int, int, uint64_t, uint64_t *, float *, size_t, size_t,
+                                               void *, uint32_t *, const uint32_t *, uint32_t, bool, hipStream_t,
+                                               const uint32_t *);
+template hipError_t launch_select_exact<double>(const CandBuf &, int, int, uint64_t, uint64_t *, double *, size_t, size_t,
+                                                void *, uint32_t *, const uint32_t *, uint32_t, bool, hipStream_t,
+                                                const uint32_t *);
 
 // ---------------------------------------------------------------------------
 // MFMA mode: exact re-rank + verification.  block = 64 threads = one query.
@@ -800,12 +798,13 @@ __global__ __launch_bounds__(64, 1) void select_rerank_kernel(
 }
 
 template <typename T>
-static hipError_t launch_select_rerank(const CandBuf &cb, const T *P, size_t n, int dim, size_t ldp, const T *Q, int nq,
-                                       size_t ldq, int kout, uint64_t index_base, uint64_t *idx_out, T *dist_out,
-                                       size_t out_stride, uint32_t *flags, uint32_t *n_flagged, const double *qn,
-                                       const uint32_t *qbad, uint32_t *sel, unsigned long long *stats, hipStream_t s,
-                                       int first_eval, int cell_max, const T *cnorm = nullptr, const T *qnorm = nullptr) {
+hipError_t launch_select_rerank(const CandBuf &cb, const T *P, size_t n, int dim, size_t ldp, const T *Q, int nq, size_t ldq,
+                                int kout, uint64_t index_base, uint64_t *idx_out, T *dist_out, size_t out_stride,
+                                uint32_t *flags, uint32_t *n_flagged, const double *qn, const uint32_t *qbad, uint32_t *sel,
+                                unsigned long long *stats, hipStream_t s, int first_eval, int cell_max, const T *cnorm,
+                                const T *qnorm) {
     using KeyT = typename KeyOf<T>::type;
+    if (sizeof(T) == 8 && !qn) return hipErrorInvalidValue;  // (only the bf16 tier serves f64)
     // with filter keys in the buffers (both MFMA tiers) candidates are evaluated lazily
     const uint32_t *ckey = static_cast<const uint32_t *>(cb.keys);
     // LDS for what the cells can HOLD (cell_max entries each: the filter's k' after its final cut), not for their
@@ -828,42 +827,14 @@ static hipError_t launch_select_rerank(const CandBuf &cb, const T *P, size_t n, 
                        (const T *)nullptr);
     return hipGetLastError();
 }
-hipError_t launch_select_rerank_f32(const CandBuf &cb, const float *P, size_t n, int dim, size_t ldp,
-                                    const float *Q, int nq, size_t ldq, int kout, uint64_t index_base,
-                                    uint64_t *idx_out, float *dist_out, size_t out_stride, uint32_t *flags,
-                                    uint32_t *n_flagged, const double *qn, const uint32_t *qbad, uint32_t *sel,
-                                    unsigned long long *stats, hipStream_t s, int first_eval, int cell_max) {
-    return launch_select_rerank<float>(cb, P, n, dim, ldp, Q, nq, ldq, kout, index_base, idx_out, dist_out, out_stride,
-                                       flags, n_flagged, qn, qbad, sel, stats, s, first_eval, cell_max);
-}
-// f64 indexes behind the bf16 filter: the candidates' distances in the reference's f64 fold, the proof with u = 2^-53
-hipError_t launch_select_rerank_f64(const CandBuf &cb, const double *P, size_t n, int dim, size_t ldp,
-                                    const double *Q, int nq, size_t ldq, int kout, uint64_t index_base,
-                                    uint64_t *idx_out, double *dist_out, size_t out_stride, uint32_t *flags,
-                                    uint32_t *n_flagged, const double *qn, const uint32_t *qbad, uint32_t *sel,
-                                    unsigned long long *stats, hipStream_t s, int first_eval, int cell_max) {
-    if (!qn) return hipErrorInvalidValue;  // (only the bf16 tier serves f64)
-    return launch_select_rerank<double>(cb, P, n, dim, ldp, Q, nq, ldq, kout, index_base, idx_out, dist_out, out_stride,
-                                        flags, n_flagged, qn, qbad, sel, stats, s, first_eval, cell_max);
-}
-// Cosine indexes behind the bf16 filter: candidates evaluated by Cosine::distance (cnorm / qnorm: the rows' and the queries'
-// norms in the index's type), signed keys, cos_proof_lb
-hipError_t launch_select_rerank_cos_f32(const CandBuf &cb, const float *P, size_t n, int dim, size_t ldp, const float *Q,
-                                        int nq, size_t ldq, int kout, uint64_t index_base, uint64_t *idx_out,
-                                        float *dist_out, size_t out_stride, uint32_t *flags, uint32_t *n_flagged,
-                                        const double *qn, const uint32_t *qbad, uint32_t *sel, unsigned long long *stats,
-                                        hipStream_t s, int first_eval, int cell_max, const float *cnorm, const float *qnorm) {
-    return launch_select_rerank<float>(cb, P, n, dim, ldp, Q, nq, ldq, kout, index_base, idx_out, dist_out, out_stride,
-                                       flags, n_flagged, qn, qbad, sel, stats, s, first_eval, cell_max, cnorm, qnorm);
-}
-hipError_t launch_select_rerank_cos_f64(const CandBuf &cb, const double *P, size_t n, int dim, size_t ldp, const double *Q,
-                                        int nq, size_t ldq, int kout, uint64_t index_base, uint64_t *idx_out,
-                                        double *dist_out, size_t out_stride, uint32_t *flags, uint32_t *n_flagged,
-                                        const double *qn, const uint32_t *qbad, uint32_t *sel, unsigned long long *stats,
-                                        hipStream_t s, int first_eval, int cell_max, const double *cnorm, const double *qnorm) {
-    return launch_select_rerank<double>(cb, P, n, dim, ldp, Q, nq, ldq, kout, index_base, idx_out, dist_out, out_stride,
-                                        flags, n_flagged, qn, qbad, sel, stats, s, first_eval, cell_max, cnorm, qnorm);
-}
+template hipError_t launch_select_rerank<float>(const CandBuf &, const float *, size_t, int, size_t, const float *, int, size_t,
+                                                int, uint64_t, uint64_t *, float *, size_t, uint32_t *, uint32_t *,
+                                                const double *, const uint32_t *, uint32_t *, unsigned long long *,
+                                                hipStream_t, int, int, const float *, const float *);
+template hipError_t launch_select_rerank<double>(const CandBuf &, const double *, size_t, int, size_t, const double *, int,
+                                                 size_t, int, uint64_t, uint64_t *, double *, size_t, uint32_t *, uint32_t *,
+                                                 const double *, const uint32_t *, uint32_t *, unsigned long long *,
+                                                 hipStream_t, int, int, const double *, const double *);
 
 // ---------------------------------------------------------------------------
 // Small corpora, a point (or a few) per call -- the reference's own call pattern (benches/ball_tree.rs:22-62: 64 x 10
@@ -960,9 +931,9 @@ __global__ __launch_bounds__(64) void tiny_query_kernel(const T *__restrict__ P,
     }
 }
 template <typename T>
-static hipError_t launch_tiny_query(const T *P, size_t n, int dim_eff, size_t ldp, const T *Q, size_t ldq, int nq,
-                                    int kout, bool radius_mode, T radius, uint64_t index_base, uint64_t *idx_out,
-                                    T *dist_out, size_t out_stride, hipStream_t s) {
+hipError_t launch_tiny_query(const T *P, size_t n, int dim_eff, size_t ldp, const T *Q, size_t ldq, int nq, int kout,
+                             bool radius_mode, T radius, uint64_t index_base, uint64_t *idx_out, T *dist_out,
+                             size_t out_stride, hipStream_t s) {
     using KeyT = typename KeyOf<T>::type;
     const size_t sh = (size_t)((dim_eff + 7) / 8 * 8) * sizeof(T) + n * (sizeof(KeyT) + sizeof(uint32_t));
     if (sh > 64 * 1024 || n == 0 || n > 0xFFFFFFFFull) return hipErrorInvalidValue;
@@ -973,18 +944,10 @@ static hipError_t launch_tiny_query(const T *P, size_t n, int dim_eff, size_t ld
 size_t tiny_query_lds_bytes(size_t n, int dim_eff, int elem_bytes) {
     return (size_t)((dim_eff + 7) / 8 * 8) * (size_t)elem_bytes + n * ((size_t)elem_bytes + 4);
 }
-hipError_t launch_tiny_query_f32(const float *P, size_t n, int dim_eff, size_t ldp, const float *Q, size_t ldq, int nq,
-                                 int kout, bool radius_mode, float radius, uint64_t index_base, uint64_t *idx_out,
-                                 float *dist_out, size_t out_stride, hipStream_t s) {
-    return launch_tiny_query<float>(P, n, dim_eff, ldp, Q, ldq, nq, kout, radius_mode, radius, index_base, idx_out, dist_out,
-                                    out_stride, s);
-}
-hipError_t launch_tiny_query_f64(const double *P, size_t n, int dim_eff, size_t ldp, const double *Q, size_t ldq, int nq,
-                                 int kout, bool radius_mode, double radius, uint64_t index_base, uint64_t *idx_out,
-                                 double *dist_out, size_t out_stride, hipStream_t s) {
-    return launch_tiny_query<double>(P, n, dim_eff, ldp, Q, ldq, nq, kout, radius_mode, radius, index_base, idx_out,
-                                     dist_out, out_stride, s);
-}
+template hipError_t launch_tiny_query<float>(const float *, size_t, int, size_t, const float *, size_t, int, int, bool,
+                                             float, uint64_t, uint64_t *, float *, size_t, hipStream_t);
+template hipError_t launch_tiny_query<double>(const double *, size_t, int, size_t, const double *, size_t, int, int,
+                                              bool, double, uint64_t, uint64_t *, double *, size_t, hipStream_t);
 
 // ---------------------------------------------------------------------------
 // radius: exact check of the filter's survivors.  block = 64 threads = one query.
@@ -1236,10 +1199,10 @@ __global__ __launch_bounds__(64) void merge_sorted_topk_kernel(const uint64_t *_
 }
 
 template <typename T>
-static hipError_t launch_merge_topk(const uint64_t *idx_parts, const T *dist_parts, int n_parts, size_t idx_part_stride,
-                                    size_t dist_part_stride, int nq, int k_part, int k_out, uint64_t *idx_out,
-                                    T *dist_out, hipStream_t s, const uint32_t *nq_dev, const uint32_t *osel,
-                                    size_t out_stride, uint32_t *host_count, bool signed_keys) {
+hipError_t launch_merge_topk(const uint64_t *idx_parts, const T *dist_parts, int n_parts, size_t idx_part_stride,
+                             size_t dist_part_stride, int nq, int k_part, int k_out, uint64_t *idx_out, T *dist_out,
+                             hipStream_t s, const uint32_t *nq_dev, const uint32_t *osel, size_t out_stride,
+                             uint32_t *host_count, bool signed_keys) {
     const size_t sh = (size_t)n_parts * k_part * (8 + sizeof(typename KeyOf<T>::type));
     if (out_stride == 0) out_stride = (size_t)k_out;
     if (sh > 64 * 1024) {  // beyond the LDS-resident merge: the rank-by-binary-search merge of sorted parts
@@ -1253,20 +1216,12 @@ static hipError_t launch_merge_topk(const uint64_t *idx_parts, const T *dist_par
                        host_count, signed_keys ? 1 : 0);
     return hipGetLastError();
 }
-hipError_t launch_merge_topk_f32(const uint64_t *idx_parts, const float *dist_parts, int n_parts,
-                                 size_t idx_part_stride, size_t dist_part_stride, int nq, int k_part, int k_out,
-                                 uint64_t *idx_out, float *dist_out, hipStream_t s, const uint32_t *nq_dev,
-                                 const uint32_t *osel, size_t out_stride, uint32_t *host_count, bool signed_keys) {
-    return launch_merge_topk<float>(idx_parts, dist_parts, n_parts, idx_part_stride, dist_part_stride, nq, k_part, k_out,
-                                    idx_out, dist_out, s, nq_dev, osel, out_stride, host_count, signed_keys);
-}
-hipError_t launch_merge_topk_f64(const uint64_t *idx_parts, const double *dist_parts, int n_parts,
-                                 size_t idx_part_stride, size_t dist_part_stride, int nq, int k_part, int k_out,
-                                 uint64_t *idx_out, double *dist_out, hipStream_t s, const uint32_t *nq_dev,
-                                 const uint32_t *osel, size_t out_stride, uint32_t *host_count, bool signed_keys) {
-    return launch_merge_topk<double>(idx_parts, dist_parts, n_parts, idx_part_stride, dist_part_stride, nq, k_part, k_out,
-                                     idx_out, dist_out, s, nq_dev, osel, out_stride, host_count, signed_keys);
-}
+template hipError_t launch_merge_topk<float>(const uint64_t *, const float *, int, size_t, size_t, int, int, int,
+                                             uint64_t *, float *, hipStream_t, const uint32_t *, const uint32_t *,
+                                             size_t, uint32_t *, bool);
+template hipError_t launch_merge_topk<double>(const uint64_t *, const double *, int, size_t, size_t, int, int, int,
+                                              uint64_t *, double *, hipStream_t, const uint32_t *, const uint32_t *,
+                                              size_t, uint32_t *, bool);
 
 // ---------------------------------------------------------------------------
 // fallback plumbing: list flagged queries, gather their rows, scatter results

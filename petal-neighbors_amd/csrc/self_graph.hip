@@ -153,8 +153,8 @@ static int pick_group(size_t len) {
 }
 
 template <typename T>
-static hipError_t launch_knn_self_exclude(const uint64_t *in_idx, const T *in_dist, size_t nq, int kin, int kout,
-                                         uint64_t self0, uint64_t *out_idx, T *out_dist, hipStream_t s) {
+hipError_t launch_knn_self_exclude(const uint64_t *in_idx, const T *in_dist, size_t nq, int kin, int kout,
+                                   uint64_t self0, uint64_t *out_idx, T *out_dist, hipStream_t s) {
     if (nq == 0 || kout <= 0) return hipSuccess;
     const int L = pick_group((size_t)kin);
     const size_t rows_per_block = 256 / (size_t)L;
@@ -162,19 +162,15 @@ static hipError_t launch_knn_self_exclude(const uint64_t *in_idx, const T *in_di
                        0, s, in_idx, in_dist, nq, kin, kout, L, self0, out_idx, out_dist);
     return hipGetLastError();
 }
-hipError_t launch_knn_self_exclude_f32(const uint64_t *in_idx, const float *in_dist, size_t nq, int kin, int kout,
-                                       uint64_t self0, uint64_t *out_idx, float *out_dist, hipStream_t s) {
-    return launch_knn_self_exclude<float>(in_idx, in_dist, nq, kin, kout, self0, out_idx, out_dist, s);
-}
-hipError_t launch_knn_self_exclude_f64(const uint64_t *in_idx, const double *in_dist, size_t nq, int kin, int kout,
-                                       uint64_t self0, uint64_t *out_idx, double *out_dist, hipStream_t s) {
-    return launch_knn_self_exclude<double>(in_idx, in_dist, nq, kin, kout, self0, out_idx, out_dist, s);
-}
+template hipError_t launch_knn_self_exclude<float>(const uint64_t *, const float *, size_t, int, int, uint64_t,
+                                                   uint64_t *, float *, hipStream_t);
+template hipError_t launch_knn_self_exclude<double>(const uint64_t *, const double *, size_t, int, int, uint64_t,
+                                                    uint64_t *, double *, hipStream_t);
 
 template <typename T>
-static hipError_t launch_radius_self_counts(const T *P, size_t n, int dim, size_t ld, const T *cnorm, T r, bool exclude,
-                                           const uint64_t *in_off, uint32_t *flag, uint32_t *cnt, uint32_t *bad,
-                                           hipStream_t s, const T *radii) {
+hipError_t launch_radius_self_counts(const T *P, size_t n, int dim, size_t ld, const T *cnorm, T r, bool exclude,
+                                     const uint64_t *in_off, uint32_t *flag, uint32_t *cnt, uint32_t *bad,
+                                     hipStream_t s, const T *radii) {
     if (n == 0) return hipSuccess;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
     if (cnorm)
@@ -185,16 +181,12 @@ static hipError_t launch_radius_self_counts(const T *P, size_t n, int dim, size_
                            flag, cnt, bad, radii);
     return hipGetLastError();
 }
-hipError_t launch_radius_self_counts_f32(const float *P, size_t n, int dim, size_t ld, const float *cnorm, float r,
-                                         bool exclude, const uint64_t *in_off, uint32_t *flag, uint32_t *cnt, uint32_t *bad,
-                                         hipStream_t s, const float *radii) {
-    return launch_radius_self_counts<float>(P, n, dim, ld, cnorm, r, exclude, in_off, flag, cnt, bad, s, radii);
-}
-hipError_t launch_radius_self_counts_f64(const double *P, size_t n, int dim, size_t ld, const double *cnorm, double r,
-                                         bool exclude, const uint64_t *in_off, uint32_t *flag, uint32_t *cnt, uint32_t *bad,
-                                         hipStream_t s, const double *radii) {
-    return launch_radius_self_counts<double>(P, n, dim, ld, cnorm, r, exclude, in_off, flag, cnt, bad, s, radii);
-}
+template hipError_t launch_radius_self_counts<float>(const float *, size_t, int, size_t, const float *, float, bool,
+                                                     const uint64_t *, uint32_t *, uint32_t *, uint32_t *, hipStream_t,
+                                                     const float *);
+template hipError_t launch_radius_self_counts<double>(const double *, size_t, int, size_t, const double *, double, bool,
+                                                      const uint64_t *, uint32_t *, uint32_t *, uint32_t *, hipStream_t,
+                                                      const double *);
 hipError_t launch_radius_self_place(const uint64_t *part, size_t nq, uint64_t *out, hipStream_t s) {
     if (nq == 0) return hipSuccess;
     hipLaunchKernelGGL(radius_self_place_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, part, nq, out);
@@ -202,10 +194,9 @@ hipError_t launch_radius_self_place(const uint64_t *part, size_t nq, uint64_t *o
 }
 
 template <typename T>
-static hipError_t launch_radius_self_compact(const uint64_t *in_off, const uint64_t *in_idx, const T *in_dist,
-                                            uint64_t in_cap, const uint32_t *flag, const uint64_t *out_off, size_t n,
-                                            uint64_t self0, uint64_t *out_idx, T *out_dist, uint64_t cap, uint32_t *bad,
-                                            hipStream_t s) {
+hipError_t launch_radius_self_compact(const uint64_t *in_off, const uint64_t *in_idx, const T *in_dist, uint64_t in_cap,
+                                      const uint32_t *flag, const uint64_t *out_off, size_t n, uint64_t self0,
+                                      uint64_t *out_idx, T *out_dist, uint64_t cap, uint32_t *bad, hipStream_t s) {
     if (n == 0 || cap == 0) return hipSuccess;
     constexpr int L = 32;  // lists average tens of entries in the intended use; longer ones take more trips
     const size_t rows_per_block = 256 / L;
@@ -214,19 +205,11 @@ static hipError_t launch_radius_self_compact(const uint64_t *in_off, const uint6
                        bad);
     return hipGetLastError();
 }
-hipError_t launch_radius_self_compact_f32(const uint64_t *in_off, const uint64_t *in_idx, const float *in_dist,
-                                          uint64_t in_cap, const uint32_t *flag, const uint64_t *out_off, size_t n,
-                                          uint64_t self0, uint64_t *out_idx, float *out_dist, uint64_t cap, uint32_t *bad,
-                                          hipStream_t s) {
-    return launch_radius_self_compact<float>(in_off, in_idx, in_dist, in_cap, flag, out_off, n, self0, out_idx, out_dist,
-                                             cap, bad, s);
-}
-hipError_t launch_radius_self_compact_f64(const uint64_t *in_off, const uint64_t *in_idx, const double *in_dist,
-                                          uint64_t in_cap, const uint32_t *flag, const uint64_t *out_off, size_t n,
-                                          uint64_t self0, uint64_t *out_idx, double *out_dist, uint64_t cap, uint32_t *bad,
-                                          hipStream_t s) {
-    return launch_radius_self_compact<double>(in_off, in_idx, in_dist, in_cap, flag, out_off, n, self0, out_idx, out_dist,
-                                              cap, bad, s);
-}
+template hipError_t launch_radius_self_compact<float>(const uint64_t *, const uint64_t *, const float *, uint64_t,
+                                                      const uint32_t *, const uint64_t *, size_t, uint64_t, uint64_t *,
+                                                      float *, uint64_t, uint32_t *, hipStream_t);
+template hipError_t launch_radius_self_compact<double>(const uint64_t *, const uint64_t *, const double *, uint64_t,
+                                                       const uint32_t *, const uint64_t *, size_t, uint64_t, uint64_t *,
+                                                       double *, uint64_t, uint32_t *, hipStream_t);
 
 }  // namespace pn

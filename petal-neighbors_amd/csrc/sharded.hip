@@ -283,10 +283,6 @@ template <> struct ShT<float> {
                                   uint64_t *tot, void *st) {
         return pn_query_radius_self_device_f32(ix, r, fl, off, idx, dist, cap, tot, st);
     }
-    static hipError_t exclude(const uint64_t *ii, const float *id, size_t nq, int kin, int kout, uint64_t self0, uint64_t *oi,
-                              float *od, hipStream_t s) {
-        return launch_knn_self_exclude_f32(ii, id, nq, kin, kout, self0, oi, od, s);
-    }
 };
 template <> struct ShT<double> {
     static int create(const double *p, size_t n, size_t c, ptrdiff_t rs, ptrdiff_t cs, int dev, pn_index **o, int metric) {
@@ -331,10 +327,6 @@ template <> struct ShT<double> {
     static int radius_self_device(const pn_index *ix, double r, unsigned fl, uint64_t *off, uint64_t *idx, double *dist, size_t cap,
                                   uint64_t *tot, void *st) {
         return pn_query_radius_self_device_f64(ix, r, fl, off, idx, dist, cap, tot, st);
-    }
-    static hipError_t exclude(const uint64_t *ii, const double *id, size_t nq, int kin, int kout, uint64_t self0, uint64_t *oi,
-                              double *od, hipStream_t s) {
-        return launch_knn_self_exclude_f64(ii, id, nq, kin, kout, self0, oi, od, s);
     }
 };
 static int check_elem(const pn_sharded *sh, size_t bytes) {
@@ -1285,7 +1277,7 @@ static int self_knn_run(const pn_sharded *sh, size_t kin, size_t kout, bool incl
             SHIP(hipMemcpyAsync(oi, si, cells * 8, hipMemcpyDeviceToDevice, st[i]));
             SHIP(hipMemcpyAsync(od, sd, cells * sizeof(T), hipMemcpyDeviceToDevice, st[i]));
         } else {
-            SHIP(ShT<T>::exclude(si, sd, (size_t)sg.m, (int)kin, (int)kout, g0, oi, od, st[i]));
+            SHIP(launch_knn_self_exclude<T>(si, sd, (size_t)sg.m, (int)kin, (int)kout, g0, oi, od, st[i]));
         }
         if (!device) {
             SHIP(hipMemcpyAsync(idx_out + row * kout, oi, cells * 8, hipMemcpyDeviceToHost, st[i]));

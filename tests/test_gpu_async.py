@@ -79,3 +79,58 @@ def test_sharded_query_device_is_asynchronous_too(pn, oracle_mod):
     assert dist.cpu().numpy().tobytes() == odist.tobytes()
     assert np.array_equal(idx.cpu().numpy().astype(np.uint64), oidx)
     del keep
+
+
+# The two tests below call with LARGER shapes than their warm-up, so the workspace's buffers are outgrown behind the
+# filler: an outgrown allocation must be retired to the workspace's list (DevBuf::ensure), never freed on the spot --
+# hipFree waits for the whole device, filler included.  Every workspace buffer gets that list by being a member of
+# WorkspaceBufs (index.hip).
+def _grow_corpus():
+    return np.random.default_rng(7).random((20000, 32), dtype=np.float32)
+
+
+def test_query_device_outgrows_its_buffers_without_waiting(pn, oracle_mod):
+    import torch
+    pts = _grow_corpus()
+    qs = np.random.default_rng(8).random((2048, 32), dtype=np.float32)
+    tree = pn.BallTree.euclidean(pts)
+    dq = torch.from_numpy(qs).cuda()
+    tree.query_device(dq[:64], 5)        # warm-up: every query-sized buffer at 64 queries, k = 5
+    torch.cuda.synchronize()
+    stream = torch.cuda.Stream()
+    ev, keep = _busy(torch, stream)
+    assert not ev.query(), "the stream drained before the test could look (box too fast for the filler)"
+    t0 = time.perf_counter()
+    with torch.cuda.stream(stream):
+        idx, dist = tree.query_device(dq, 10)
+    dt = (time.perf_counter() - t0) * 1e3
+    still_busy = not ev.query()
+    assert still_busy, f"pn_query_device_f32 waited for the device when its buffers grew ({dt:.1f} ms)"
+    assert dt < 50.0, f"enqueueing took {dt:.1f} ms"
+    stream.synchronize()
+    oidx, odist = oracle_mod.brute_knn(pts, qs, 10)
+    assert dist.cpu().numpy().tobytes() == odist.tobytes()
+    assert np.array_equal(idx.cpu().numpy().astype(np.uint64), oidx)
+    del keep
+
+
+def test_lof_device_outgrows_its_graph_store_without_waiting(pn):
+    import torch
+    pts = _grow_corpus()
+    tree = pn.BallTree.euclidean(pts)
+    tree.lof_device(3)                   # warm-up: the graph store (w_lof) at k = 3
+    torch.cuda.synchronize()
+    stream = torch.cuda.Stream()
+    ev, keep = _busy(torch, stream)
+    assert not ev.query(), "the stream drained before the test could look (box too fast for the filler)"
+    t0 = time.perf_counter()
+    with torch.cuda.stream(stream):
+        lof, _, _ = tree.lof_device(20)
+    dt = (time.perf_counter() - t0) * 1e3
+    still_busy = not ev.query()
+    assert still_busy, f"pn_lof_device_f32 waited for the device when its graph store grew ({dt:.1f} ms)"
+    assert dt < 50.0, f"enqueueing took {dt:.1f} ms"
+    stream.synchronize()
+    want = pn.BallTree.euclidean(pts).lof(20)    # the host entry on a fresh handle
+    assert lof.cpu().numpy().tobytes() == want.tobytes()
+    del keep
