@@ -55,190 +55,129 @@ class PnShardedInfo(C.Structure):
                 ("bf16_eligible", C.c_int32)]
 
 
-_sz, _ssz, _i, _vp, _u64 = C.c_size_t, C.c_ssize_t, C.c_int, C.c_void_p, C.c_uint64
-_u64p, _f32p, _f64p = C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.POINTER(C.c_double)
+_sz, _ssz, _i, _vp, _u64, _cu, _d = C.c_size_t, C.c_ssize_t, C.c_int, C.c_void_p, C.c_uint64, C.c_uint, C.c_double
+_u64p, _ip, _vpp = C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_void_p)
+_R, _RP = "real", "real*"  # the handle's element type and a pointer to it: c_float / c_double by suffix
 
-# every symbol include/petal_mi355x.h declares: name -> (restype, argtypes)
-SIGNATURES = {
+# queries / centres / seeds on the host (rows, nq, qc, stride) and in HBM
+_QH, _QD = [_vp, _vp, _sz, _sz, _ssz], [_vp, _vp, _sz, _sz, _sz]
+# the CSR results of the radius searches: host (offsets, idx**, dist**), device (offsets, idx, dist, capacity, total, stream)
+_CSR_H, _CSR_D = [_vp, _vpp, _vpp], [_vp, _vp, _vp, _sz, _vp, _vp]
+_CREATE = [_vp, _sz, _sz, _ssz, _ssz, _i, _vpp]
+_SH_CREATE = [_vp, _sz, _sz, _ssz, _ssz, _ip, _i, _vpp]
+_PAIRWISE = [_vp, _sz, _sz, _ssz, _i, _vp]
+
+# stem -> (restype, argtypes): declared once, expanded to stem_f32 and stem_f64 with _R / _RP as the suffix's type
+PAIRED = {
+    "pn_index_create": (_i, _CREATE),
+    "pn_index_create_cosine": (_i, _CREATE),
+    "pn_pairwise_device": (_i, [_vp, _sz, _sz, _sz, _i, _vp, _vp]),
+    "pn_index_create_device": (_i, [_vp, _sz, _sz, _sz, _i, _vp, _vpp]),
+    "pn_query": (_i, _QH + [_sz, _vp, _vp]),
+    "pn_query_device": (_i, _QD + [_sz, _vp, _vp, _vp]),
+    "pn_query_nearest": (_i, _QH + [_vp, _vp]),
+    "pn_query_radius": (_i, _QH + [_R, _vp, _vpp]),
+    "pn_query_radius_device": (_i, _QD + [_R, _vp, _vp, _sz, _vp, _vp]),
+    "pn_query_radius_with_distance": (_i, _QH + [_R, _cu] + _CSR_H),
+    "pn_query_radius_with_distance_device": (_i, _QD + [_R, _cu] + _CSR_D),
+    "pn_query_self": (_i, [_vp, _sz, _cu, _vp, _vp]),
+    "pn_query_self_device": (_i, [_vp, _sz, _cu, _vp, _vp, _vp]),
+    "pn_query_radius_self": (_i, [_vp, _R, _cu] + _CSR_H),
+    "pn_query_radius_self_device": (_i, [_vp, _R, _cu] + _CSR_D),
+    "pn_query_radii": (_i, _QH + [_vp, _cu] + _CSR_H),
+    "pn_query_radii_device": (_i, _QD + [_vp, _cu] + _CSR_D),
+    "pn_query_radii_self": (_i, [_vp, _vp, _cu] + _CSR_H),
+    "pn_query_radii_self_device": (_i, [_vp, _vp, _cu] + _CSR_D),
+    "pn_dbscan": (_i, [_vp, _R, _sz, _cu] + [_vp] * 3),
+    "pn_dbscan_device": (_i, [_vp, _R, _sz, _cu] + [_vp] * 4),
+    "pn_mst": (_i, [_vp, _vp, _cu] + [_vp] * 4),
+    "pn_mst_device": (_i, [_vp, _vp, _cu] + [_vp] * 5),
+    "pn_linkage": (_i, [_vp] * 4 + [_cu] + [_vp] * 4),
+    "pn_linkage_device": (_i, [_vp] * 4 + [_cu] + [_vp] * 6),
+    "pn_hdbscan": (_i, [_vp, _sz, _sz, _cu] + [_vp] * 3),
+    "pn_hdbscan_device": (_i, [_vp, _sz, _sz, _cu] + [_vp] * 4),
+    "pn_lof": (_i, [_vp, _sz, _cu] + [_vp] * 3),
+    "pn_lof_device": (_i, [_vp, _sz, _cu] + [_vp] * 4),
+    "pn_lof_score": (_i, _QH + [_sz, _vp, _vp, _cu, _vp]),
+    "pn_lof_score_device": (_i, _QD + [_sz, _vp, _vp, _cu, _vp, _vp]),
+    "pn_kde": (_i, _QH + [_vp, _sz, _i, _d, _cu] + [_vp] * 3),
+    "pn_kde_device": (_i, _QD + [_vp, _sz, _i, _d, _cu] + [_vp] * 4),
+    "pn_kde_self": (_i, [_vp, _vp, _sz, _i, _d, _cu] + [_vp] * 3),
+    "pn_kde_self_device": (_i, [_vp, _vp, _sz, _i, _d, _cu] + [_vp] * 4),
+    "pn_mean_shift": (_i, _QH + [_vp, _sz, _d, _sz, _cu] + [_vp] * 5),
+    "pn_mean_shift_device": (_i, _QD + [_vp, _sz, _d, _sz, _cu] + [_vp] * 6),
+    "pn_mean_shift_merge": (_i, [_vp, _vp, _sz, _vp, _R, _cu] + [_vp] * 4),
+    "pn_mean_shift_merge_device": (_i, [_vp, _vp, _sz, _vp, _R, _cu] + [_vp] * 5),
+    "pn_mean_shift_labels": (_i, [_vp, _vp, _sz, _R, _cu, _vp]),
+    "pn_mean_shift_labels_device": (_i, [_vp, _vp, _sz, _R, _cu, _vp, _vp]),
+    "pn_kmeans_assign": (_i, [_vp, _vp, _sz, _cu] + [_vp] * 3),
+    "pn_kmeans_assign_device": (_i, [_vp, _vp, _sz, _cu] + [_vp] * 4),
+    "pn_kmeans": (_i, [_vp, _vp, _sz, _d, _sz, _cu] + [_vp] * 7),
+    "pn_kmeans_device": (_i, [_vp, _vp, _sz, _d, _sz, _cu] + [_vp] * 8),
+    "pn_optics": (_i, [_vp, _sz, _R, _cu] + [_vp] * 4),
+    "pn_optics_device": (_i, [_vp, _sz, _R, _cu] + [_vp] * 5),
+    "pn_optics_dbscan": (_i, [_vp] * 4 + [_R, _cu, _vp, _vp]),
+    "pn_optics_dbscan_device": (_i, [_vp] * 4 + [_R, _cu] + [_vp] * 4),
+    "pn_pairwise": (_i, _PAIRWISE),
+    "pn_pairwise_cosine": (_i, _PAIRWISE),
+    "pn_cosine": (_R, [_vp, _sz, _vp, _sz]),
+    "pn_euclidean": (_R, [_vp, _vp, _sz]),
+    "pn_reuclidean": (_R, [_vp, _vp, _sz]),
+    "pn_rdistance_to_distance": (_R, [_R]),
+    "pn_distance_to_rdistance": (_R, [_R]),
+    "pn_merge_topk_device": (_i, [_vp, _vp] + [_sz] * 6 + [_vp, _vp, _i, _vp]),
+    "pn_tree_radius_of": (_i, [_vp, _u64, _RP]),
+    "pn_tree_node_distance_lower_bound": (_i, [_vp, _u64, _u64, _RP]),
+    "pn_sharded_create": (_i, _SH_CREATE),
+    "pn_sharded_create_cosine": (_i, _SH_CREATE),
+    "pn_sharded_create_rank_device": (_i, [_vp, _sz, _sz, _sz, _u64, _i, _i, _vp, _i, _vp, _vpp]),
+}
+# the sharded handle's searches take the arguments of the single index's
+for _stem in ("query", "query_device", "query_radius", "query_radius_device", "query_radius_with_distance",
+              "query_radius_with_distance_device", "query_self", "query_self_device", "query_radius_self",
+              "query_radius_self_device"):
+    PAIRED["pn_sharded_" + _stem] = PAIRED["pn_" + _stem]
+
+# the symbols without an f32 / f64 twin
+UNPAIRED = {
     "pn_last_error": (C.c_char_p, []),
     "pn_strerror": (C.c_char_p, [_i]),
     "pn_abi_version": (_i, []),
-    "pn_device_count": (_i, [C.POINTER(_i)]),
-    "pn_index_create_f32": (_i, [_vp, _sz, _sz, _ssz, _ssz, _i, C.POINTER(_vp)]),
-    "pn_index_create_f64": (_i, [_vp, _sz, _sz, _ssz, _ssz, _i, C.POINTER(_vp)]),
-    "pn_index_create_cosine_f32": (_i, [_vp, _sz, _sz, _ssz, _ssz, _i, C.POINTER(_vp)]),
-    "pn_index_create_cosine_f64": (_i, [_vp, _sz, _sz, _ssz, _ssz, _i, C.POINTER(_vp)]),
-    "pn_pairwise_device_f32": (_i, [_vp, _sz, _sz, _sz, _i, _vp, _vp]),
-    "pn_pairwise_device_f64": (_i, [_vp, _sz, _sz, _sz, _i, _vp, _vp]),
-    "pn_index_create_device_f32": (_i, [_vp, _sz, _sz, _sz, _i, _vp, C.POINTER(_vp)]),
-    "pn_index_create_device_f64": (_i, [_vp, _sz, _sz, _sz, _i, _vp, C.POINTER(_vp)]),
+    "pn_device_count": (_i, [_ip]),
     "pn_index_destroy": (None, [_vp]),
     "pn_index_info": (_i, [_vp, C.POINTER(PnInfo)]),
     "pn_index_set_option": (_i, [_vp, _i, C.c_int64]),
     "pn_index_get_stats": (_i, [_vp, C.POINTER(PnStats), _i]),
-    "pn_query_f32": (_i, [_vp, _vp, _sz, _sz, _ssz, _sz, _vp, _vp]),
-    "pn_query_f64": (_i, [_vp, _vp, _sz, _sz, _ssz, _sz, _vp, _vp]),
-    "pn_query_device_f32": (_i, [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, _vp]),
-    "pn_query_device_f64": (_i, [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, _vp]),
-    "pn_query_nearest_f32": (_i, [_vp, _vp, _sz, _sz, _ssz, _vp, _vp]),
-    "pn_query_nearest_f64": (_i, [_vp, _vp, _sz, _sz, _ssz, _vp, _vp]),
-    "pn_query_radius_f32": (_i, [_vp, _vp, _sz, _sz, _ssz, C.c_float, _vp, C.POINTER(_vp)]),
-    "pn_query_radius_device_f32": (_i, [_vp, _vp, _sz, _sz, _sz, C.c_float, _vp, _vp, _sz, _vp, _vp]),
-    "pn_query_radius_device_f64": (_i, [_vp, _vp, _sz, _sz, _sz, C.c_double, _vp, _vp, _sz, _vp, _vp]),
-    "pn_query_radius_f64": (_i, [_vp, _vp, _sz, _sz, _ssz, C.c_double, _vp, C.POINTER(_vp)]),
-    "pn_query_radius_with_distance_f32": (_i, [_vp, _vp, _sz, _sz, _ssz, C.c_float, C.c_uint, _vp, C.POINTER(_vp),
-                                               C.POINTER(_vp)]),
-    "pn_query_radius_with_distance_f64": (_i, [_vp, _vp, _sz, _sz, _ssz, C.c_double, C.c_uint, _vp, C.POINTER(_vp),
-                                               C.POINTER(_vp)]),
-    "pn_query_radius_with_distance_device_f32": (_i, [_vp, _vp, _sz, _sz, _sz, C.c_float, C.c_uint, _vp, _vp, _vp, _sz,
-                                                      _vp, _vp]),
-    "pn_query_radius_with_distance_device_f64": (_i, [_vp, _vp, _sz, _sz, _sz, C.c_double, C.c_uint, _vp, _vp, _vp, _sz,
-                                                      _vp, _vp]),
-    "pn_query_self_f32": (_i, [_vp, _sz, C.c_uint, _vp, _vp]),
-    "pn_query_self_f64": (_i, [_vp, _sz, C.c_uint, _vp, _vp]),
-    "pn_query_self_device_f32": (_i, [_vp, _sz, C.c_uint, _vp, _vp, _vp]),
-    "pn_query_self_device_f64": (_i, [_vp, _sz, C.c_uint, _vp, _vp, _vp]),
-    "pn_query_radius_self_f32": (_i, [_vp, C.c_float, C.c_uint, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
-    "pn_query_radius_self_f64": (_i, [_vp, C.c_double, C.c_uint, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
-    "pn_query_radius_self_device_f32": (_i, [_vp, C.c_float, C.c_uint, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "pn_query_radius_self_device_f64": (_i, [_vp, C.c_double, C.c_uint, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "pn_query_radii_f32": (_i, [_vp, _vp, _sz, _sz, _ssz, _vp, C.c_uint, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
-    "pn_query_radii_f64": (_i, [_vp, _vp, _sz, _sz, _ssz, _vp, C.c_uint, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
-    "pn_query_radii_device_f32": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, C.c_uint, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "pn_query_radii_device_f64": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, C.c_uint, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "pn_query_radii_self_f32": (_i, [_vp, _vp, C.c_uint, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
-    "pn_query_radii_self_f64": (_i, [_vp, _vp, C.c_uint, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
-    "pn_query_radii_self_device_f32": (_i, [_vp, _vp, C.c_uint, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "pn_query_radii_self_device_f64": (_i, [_vp, _vp, C.c_uint, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "pn_dbscan_f32": (_i, [_vp, C.c_float, _sz, C.c_uint, _vp, _vp, _vp]),
-    "pn_dbscan_f64": (_i, [_vp, C.c_double, _sz, C.c_uint, _vp, _vp, _vp]),
-    "pn_dbscan_device_f32": (_i, [_vp, C.c_float, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
-    "pn_dbscan_device_f64": (_i, [_vp, C.c_double, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
-    "pn_mst_f32": (_i, [_vp, _vp, C.c_uint, _vp, _vp, _vp, _vp]),
-    "pn_mst_f64": (_i, [_vp, _vp, C.c_uint, _vp, _vp, _vp, _vp]),
-    "pn_mst_device_f32": (_i, [_vp, _vp, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
-    "pn_mst_device_f64": (_i, [_vp, _vp, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
-    "pn_linkage_f32": (_i, [_vp, _vp, _vp, _vp, C.c_uint, _vp, _vp, _vp, _vp]),
-    "pn_linkage_f64": (_i, [_vp, _vp, _vp, _vp, C.c_uint, _vp, _vp, _vp, _vp]),
-    "pn_linkage_device_f32": (_i, [_vp, _vp, _vp, _vp, C.c_uint, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "pn_linkage_device_f64": (_i, [_vp, _vp, _vp, _vp, C.c_uint, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "pn_hdbscan_f32": (_i, [_vp, _sz, _sz, C.c_uint, _vp, _vp, _vp]),
-    "pn_hdbscan_f64": (_i, [_vp, _sz, _sz, C.c_uint, _vp, _vp, _vp]),
-    "pn_hdbscan_device_f32": (_i, [_vp, _sz, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
-    "pn_hdbscan_device_f64": (_i, [_vp, _sz, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
-    "pn_lof_f32": (_i, [_vp, _sz, C.c_uint, _vp, _vp, _vp]),
-    "pn_lof_f64": (_i, [_vp, _sz, C.c_uint, _vp, _vp, _vp]),
-    "pn_lof_device_f32": (_i, [_vp, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
-    "pn_lof_device_f64": (_i, [_vp, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
-    "pn_lof_score_f32": (_i, [_vp, _vp, _sz, _sz, _ssz, _sz, _vp, _vp, C.c_uint, _vp]),
-    "pn_lof_score_f64": (_i, [_vp, _vp, _sz, _sz, _ssz, _sz, _vp, _vp, C.c_uint, _vp]),
-    "pn_lof_score_device_f32": (_i, [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, C.c_uint, _vp, _vp]),
-    "pn_lof_score_device_f64": (_i, [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, C.c_uint, _vp, _vp]),
-    "pn_kde_f32": (_i, [_vp, _vp, _sz, _sz, _ssz, _vp, _sz, C.c_int, C.c_double, C.c_uint, _vp, _vp, _vp]),
-    "pn_kde_f64": (_i, [_vp, _vp, _sz, _sz, _ssz, _vp, _sz, C.c_int, C.c_double, C.c_uint, _vp, _vp, _vp]),
-    "pn_kde_device_f32": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _sz, C.c_int, C.c_double, C.c_uint, _vp, _vp, _vp, _vp]),
-    "pn_kde_device_f64": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _sz, C.c_int, C.c_double, C.c_uint, _vp, _vp, _vp, _vp]),
-    "pn_kde_self_f32": (_i, [_vp, _vp, _sz, C.c_int, C.c_double, C.c_uint, _vp, _vp, _vp]),
-    "pn_kde_self_f64": (_i, [_vp, _vp, _sz, C.c_int, C.c_double, C.c_uint, _vp, _vp, _vp]),
-    "pn_kde_self_device_f32": (_i, [_vp, _vp, _sz, C.c_int, C.c_double, C.c_uint, _vp, _vp, _vp, _vp]),
-    "pn_kde_self_device_f64": (_i, [_vp, _vp, _sz, C.c_int, C.c_double, C.c_uint, _vp, _vp, _vp, _vp]),
-    "pn_mean_shift_f32": (_i, [_vp, _vp, _sz, _sz, _ssz, _vp, _sz, C.c_double, _sz, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
-    "pn_mean_shift_device_f32": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _sz, C.c_double, _sz, C.c_uint, _vp, _vp, _vp, _vp, _vp,
-                                    _vp]),
-    "pn_mean_shift_merge_f32": (_i, [_vp, _vp, _sz, _vp, C.c_float, C.c_uint, _vp, _vp, _vp, _vp]),
-    "pn_mean_shift_merge_device_f32": (_i, [_vp, _vp, _sz, _vp, C.c_float, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
-    "pn_mean_shift_labels_f32": (_i, [_vp, _vp, _sz, C.c_float, C.c_uint, _vp]),
-    "pn_mean_shift_labels_device_f32": (_i, [_vp, _vp, _sz, C.c_float, C.c_uint, _vp, _vp]),
-    "pn_mean_shift_f64": (_i, [_vp, _vp, _sz, _sz, _ssz, _vp, _sz, C.c_double, _sz, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
-    "pn_mean_shift_device_f64": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _sz, C.c_double, _sz, C.c_uint, _vp, _vp, _vp, _vp, _vp,
-                                    _vp]),
-    "pn_mean_shift_merge_f64": (_i, [_vp, _vp, _sz, _vp, C.c_double, C.c_uint, _vp, _vp, _vp, _vp]),
-    "pn_mean_shift_merge_device_f64": (_i, [_vp, _vp, _sz, _vp, C.c_double, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
-    "pn_mean_shift_labels_f64": (_i, [_vp, _vp, _sz, C.c_double, C.c_uint, _vp]),
-    "pn_mean_shift_labels_device_f64": (_i, [_vp, _vp, _sz, C.c_double, C.c_uint, _vp, _vp]),
-    "pn_kmeans_assign_f32": (_i, [_vp, _vp, _sz, C.c_uint, _vp, _vp, _vp]),
-    "pn_kmeans_assign_device_f32": (_i, [_vp, _vp, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
-    "pn_kmeans_f32": (_i, [_vp, _vp, _sz, C.c_double, _sz, C.c_uint, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "pn_kmeans_device_f32": (_i, [_vp, _vp, _sz, C.c_double, _sz, C.c_uint, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "pn_kmeans_assign_f64": (_i, [_vp, _vp, _sz, C.c_uint, _vp, _vp, _vp]),
-    "pn_kmeans_assign_device_f64": (_i, [_vp, _vp, _sz, C.c_uint, _vp, _vp, _vp, _vp]),
-    "pn_kmeans_f64": (_i, [_vp, _vp, _sz, C.c_double, _sz, C.c_uint, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "pn_kmeans_device_f64": (_i, [_vp, _vp, _sz, C.c_double, _sz, C.c_uint, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pn_kmeans_bounds_f32": (_i, [_vp, _vp, _sz, _vp]),
-    "pn_optics_f32": (_i, [_vp, _sz, C.c_float, C.c_uint, _vp, _vp, _vp, _vp]),
-    "pn_optics_f64": (_i, [_vp, _sz, C.c_double, C.c_uint, _vp, _vp, _vp, _vp]),
-    "pn_optics_device_f32": (_i, [_vp, _sz, C.c_float, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
-    "pn_optics_device_f64": (_i, [_vp, _sz, C.c_double, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
-    "pn_optics_dbscan_f32": (_i, [_vp, _vp, _vp, _vp, C.c_float, C.c_uint, _vp, _vp]),
-    "pn_optics_dbscan_f64": (_i, [_vp, _vp, _vp, _vp, C.c_double, C.c_uint, _vp, _vp]),
-    "pn_optics_dbscan_device_f32": (_i, [_vp, _vp, _vp, _vp, C.c_float, C.c_uint, _vp, _vp, _vp, _vp]),
-    "pn_optics_dbscan_device_f64": (_i, [_vp, _vp, _vp, _vp, C.c_double, C.c_uint, _vp, _vp, _vp, _vp]),
     "pn_free": (None, [_vp]),
-    "pn_pairwise_f32": (_i, [_vp, _sz, _sz, _ssz, _i, _vp]),
-    "pn_pairwise_f64": (_i, [_vp, _sz, _sz, _ssz, _i, _vp]),
-    "pn_pairwise_cosine_f32": (_i, [_vp, _sz, _sz, _ssz, _i, _vp]),
-    "pn_pairwise_cosine_f64": (_i, [_vp, _sz, _sz, _ssz, _i, _vp]),
-    "pn_cosine_f32": (C.c_float, [_vp, _sz, _vp, _sz]),
-    "pn_cosine_f64": (C.c_double, [_vp, _sz, _vp, _sz]),
-    "pn_euclidean_f32": (C.c_float, [_vp, _vp, _sz]),
-    "pn_euclidean_f64": (C.c_double, [_vp, _vp, _sz]),
-    "pn_reuclidean_f32": (C.c_float, [_vp, _vp, _sz]),
-    "pn_reuclidean_f64": (C.c_double, [_vp, _vp, _sz]),
-    "pn_rdistance_to_distance_f32": (C.c_float, [C.c_float]),
-    "pn_rdistance_to_distance_f64": (C.c_double, [C.c_double]),
-    "pn_distance_to_rdistance_f32": (C.c_float, [C.c_float]),
-    "pn_distance_to_rdistance_f64": (C.c_double, [C.c_double]),
-    "pn_merge_topk_device_f32": (_i, [_vp, _vp, _sz, _sz, _sz, _sz, _sz, _sz, _vp, _vp, _i, _vp]),
-    "pn_merge_topk_device_f64": (_i, [_vp, _vp, _sz, _sz, _sz, _sz, _sz, _sz, _vp, _vp, _i, _vp]),
     "pn_fill_uniform_device_f32": (_i, [_vp, _u64, _u64, _u64, _i, _vp]),
-    "pn_bf16_bounds_f32": (_i, [_vp, _vp, _sz, _sz, _ssz, _sz, _vp, _vp, _vp]),
+    "pn_bf16_bounds_f32": (_i, _QH + [_sz, _vp, _vp, _vp]),
     "pn_bf16_selftest": (_i, [_i, _vp]),
     "pn_debug_seed_model_feedback": (_i, [_vp, _i, _u64, _u64, _vp]),
-    "pn_sharded_query_radius_device_f32": (_i, [_vp, _vp, _sz, _sz, _sz, C.c_float, _vp, _vp, _sz, _vp, _vp]),
-    "pn_sharded_query_radius_device_f64": (_i, [_vp, _vp, _sz, _sz, _sz, C.c_double, _vp, _vp, _sz, _vp, _vp]),
     "pn_tree_num_nodes": (_i, [_vp, _u64p]),
-    "pn_tree_children_of": (_i, [_vp, _u64, C.POINTER(_i), _u64p, _u64p]),
+    "pn_tree_children_of": (_i, [_vp, _u64, _ip, _u64p, _u64p]),
     "pn_tree_points_of": (_i, [_vp, _u64, C.POINTER(_u64p), _u64p]),
-    "pn_tree_radius_of_f32": (_i, [_vp, _u64, _f32p]),
-    "pn_tree_radius_of_f64": (_i, [_vp, _u64, _f64p]),
-    "pn_tree_compare_nodes": (_i, [_vp, _u64, _u64, C.POINTER(_i)]),
-    "pn_tree_node_distance_lower_bound_f32": (_i, [_vp, _u64, _u64, _f32p]),
-    "pn_tree_node_distance_lower_bound_f64": (_i, [_vp, _u64, _u64, _f64p]),
+    "pn_tree_compare_nodes": (_i, [_vp, _u64, _u64, _ip]),
     "pn_tree_centroid_of": (_i, [_vp, _u64, _vp]),
     "pn_comm_unique_id": (_i, [_vp]),
-    "pn_sharded_create_f32": (_i, [_vp, _sz, _sz, _ssz, _ssz, C.POINTER(_i), _i, C.POINTER(_vp)]),
-    "pn_sharded_create_rank_device_f32": (_i, [_vp, _sz, _sz, _sz, _u64, _i, _i, _vp, _i, _vp, C.POINTER(_vp)]),
     "pn_sharded_destroy": (None, [_vp]),
     "pn_sharded_info": (_i, [_vp, C.POINTER(PnShardedInfo)]),
     "pn_sharded_set_option": (_i, [_vp, _i, C.c_int64]),
     "pn_sharded_get_stats": (_i, [_vp, C.POINTER(PnStats), _i]),
-    "pn_sharded_query_f32": (_i, [_vp, _vp, _sz, _sz, _ssz, _sz, _vp, _vp]),
-    "pn_sharded_query_device_f32": (_i, [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, _vp]),
-    "pn_sharded_query_radius_f32": (_i, [_vp, _vp, _sz, _sz, _ssz, C.c_float, _vp, C.POINTER(_vp)]),
-    "pn_sharded_create_f64": (_i, [_vp, _sz, _sz, _ssz, _ssz, C.POINTER(_i), _i, C.POINTER(_vp)]),
-    "pn_sharded_create_cosine_f32": (_i, [_vp, _sz, _sz, _ssz, _ssz, C.POINTER(_i), _i, C.POINTER(_vp)]),
-    "pn_sharded_create_cosine_f64": (_i, [_vp, _sz, _sz, _ssz, _ssz, C.POINTER(_i), _i, C.POINTER(_vp)]),
-    "pn_sharded_create_rank_device_f64": (_i, [_vp, _sz, _sz, _sz, _u64, _i, _i, _vp, _i, _vp, C.POINTER(_vp)]),
-    "pn_sharded_query_f64": (_i, [_vp, _vp, _sz, _sz, _ssz, _sz, _vp, _vp]),
-    "pn_sharded_query_device_f64": (_i, [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, _vp]),
-    "pn_sharded_query_radius_f64": (_i, [_vp, _vp, _sz, _sz, _ssz, C.c_double, _vp, C.POINTER(_vp)]),
-    "pn_sharded_query_radius_with_distance_f32": (_i, [_vp, _vp, _sz, _sz, _ssz, C.c_float, C.c_uint, _vp,
-                                                       C.POINTER(_vp), C.POINTER(_vp)]),
-    "pn_sharded_query_radius_with_distance_f64": (_i, [_vp, _vp, _sz, _sz, _ssz, C.c_double, C.c_uint, _vp,
-                                                       C.POINTER(_vp), C.POINTER(_vp)]),
-    "pn_sharded_query_radius_with_distance_device_f32": (_i, [_vp, _vp, _sz, _sz, _sz, C.c_float, C.c_uint, _vp, _vp,
-                                                              _vp, _sz, _vp, _vp]),
-    "pn_sharded_query_radius_with_distance_device_f64": (_i, [_vp, _vp, _sz, _sz, _sz, C.c_double, C.c_uint, _vp, _vp,
-                                                              _vp, _sz, _vp, _vp]),
-    "pn_sharded_query_self_f32": (_i, [_vp, _sz, C.c_uint, _vp, _vp]),
-    "pn_sharded_query_self_f64": (_i, [_vp, _sz, C.c_uint, _vp, _vp]),
-    "pn_sharded_query_self_device_f32": (_i, [_vp, _sz, C.c_uint, _vp, _vp, _vp]),
-    "pn_sharded_query_self_device_f64": (_i, [_vp, _sz, C.c_uint, _vp, _vp, _vp]),
-    "pn_sharded_query_radius_self_f32": (_i, [_vp, C.c_float, C.c_uint, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
-    "pn_sharded_query_radius_self_f64": (_i, [_vp, C.c_double, C.c_uint, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
-    "pn_sharded_query_radius_self_device_f32": (_i, [_vp, C.c_float, C.c_uint, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "pn_sharded_query_radius_self_device_f64": (_i, [_vp, C.c_double, C.c_uint, _vp, _vp, _vp, _sz, _vp, _vp]),
 }
+
+REAL = {"f32": C.c_float, "f64": C.c_double}  # suffix -> the ctypes scalar of the element type
+
+
+def _expand(t, real):
+    return real if t is _R else C.POINTER(real) if t is _RP else t
+
+
+# every symbol include/petal_mi355x.h declares: name -> (restype, argtypes)
+SIGNATURES = dict(UNPAIRED)
+for _stem, (_res, _args) in PAIRED.items():
+    for _sfx, _real in REAL.items():
+        SIGNATURES[f"{_stem}_{_sfx}"] = (_expand(_res, _real), [_expand(t, _real) for t in _args])
 
 _lib = None
 

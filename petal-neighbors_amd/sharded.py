@@ -21,6 +21,11 @@ import ctypes as C
 
 import numpy as np
 
+from . import _lib
+from ._binding import NP, Handle, stream_arg, suffix
+from .distance import Cosine
+from .errors import check
+
 ABSENT = np.uint64(0xFFFFFFFFFFFFFFFF)
 
 
@@ -33,16 +38,17 @@ def shard_bounds(n: int, world: int, rank: int):
     return lo, hi
 
 
-class ShardedIndex:
-    """A ``pn_sharded`` handle (include/petal_mi355x.h): row shards + RCCL exchange behind the ABI."""
+class ShardedIndex(Handle):
+    """A ``pn_sharded`` handle (include/petal_mi355x.h): row shards + RCCL exchange behind the ABI.  The searches are
+    ``_binding.Handle``'s, shared with ``BallTree``: k-NN and radius lists count the whole corpus (``n``), self-queries
+    answer for this process's ``local_rows``."""
+    _prefix = _object = "pn_sharded_"
 
     def __init__(self, handle, keep=None, dtype=np.float32):
-        from . import _lib
-        from .errors import check
         self._h = C.c_void_p(handle)
         self._keep = keep
         self.dtype = np.dtype(dtype)   # float32 or float64: the element type of corpus, queries and distances
-        self._sfx = "f64" if self.dtype == np.float64 else "f32"
+        self._sfx = suffix(self.dtype)
         info = _lib.PnShardedInfo()
         check(_lib.lib().pn_sharded_info(self._h, C.byref(info)))
         self.n, self.dim = int(info.n_points), int(info.dim)
@@ -51,12 +57,32 @@ class ShardedIndex:
         self.mfma_eligible, self.bf16_eligible = bool(info.mfma_eligible), bool(info.bf16_eligible)
         self.device = None  # the GPU of the device entry points (set by the constructors below)
 
+    @property
+    def _total(self):
+        return self.n
+
+    @property
+    def _rows(self):
+        return self.local_rows
+
+    @property
+    def _dev(self):
+        if self.device is None:
+            raise ValueError("device-resident self-queries need a handle that drives ONE GPU")
+        return super()._dev
+
+    # there is no pn_sharded_query_radii_*: an array of radii is taken for a scalar and fails in ``_real(r)``, before
+    # any library call
+    def _radii(self, r, count):
+        return None
+
+    def _radii_device(self, r, count, dev):
+        return None
+
     @classmethod
     def from_host(cls, points, devices, metric=None):
         """``BallTree::new`` over ``len(devices)`` row shards driven by this process; shard g lives on
         ``devices[g]`` (a device may be named several times).  ``metric``: None / ``Euclidean()`` or ``Cosine()``."""
-        from . import _lib
-        from .errors import check
         a = np.asarray(points)
         if a.dtype not in (np.float32, np.float64):   # (an f64 array gives an f64 handle, like BallTree::new is generic over A)
             a = a.astype(np.float32)
@@ -67,18 +93,15 @@ class ShardedIndex:
         rs, cs = (a.strides[0] // item, a.strides[1] // item) if n and d else (max(d, 1), 1)
         devs = (C.c_int * len(devices))(*[int(x) for x in devices])
         h = C.c_void_p(0)
-        from .distance import Cosine
-        sfx = "f64" if a.dtype == np.float64 else "f32"
-        create = getattr(_lib.lib(), ("pn_sharded_create_cosine_" if isinstance(metric, Cosine) else "pn_sharded_create_") + sfx)
-        check(create(a.ctypes.data if a.size else None, n, d, rs, cs if d > 1 else 1, devs, len(devices), C.byref(h)))
+        stem = "pn_sharded_create_cosine_" if isinstance(metric, Cosine) else "pn_sharded_create_"
+        check(getattr(_lib.lib(), stem + suffix(a.dtype))(a.ctypes.data if a.size else None, n, d, rs, cs if d > 1 else 1,
+                                                           devs, len(devices), C.byref(h)))
         out = cls(h.value, keep=a, dtype=a.dtype)
         out.device = int(devices[0]) if len(set(int(x) for x in devices)) == 1 else None
         return out
 
     @staticmethod
     def unique_id() -> bytes:
-        from . import _lib
-        from .errors import check
         buf = C.create_string_buffer(_lib.PN_COMM_ID_BYTES)
         check(_lib.lib().pn_comm_unique_id(buf))
         return buf.raw
@@ -90,331 +113,35 @@ class ShardedIndex:
         shard).  ``dtype`` is the element type of the WHOLE job (every rank must pass the same one: the packed parts of
         the all-gather are sized by it); it defaults to the rows' type and must be given where a rank may hold no rows."""
         import torch
-        from . import _lib
-        from .errors import check
         h = C.c_void_p(0)
         if dtype is None:
-            dtype = np.float64 if (rows is not None and rows.dtype == torch.float64) else np.float32
+            dtype = NP[suffix(rows.dtype)] if rows is not None else np.float32
         dtype = np.dtype(dtype)
         if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
             raise ValueError("dtype must be float32 or float64")
-        f64 = dtype == np.float64
-        if rows is not None and rows.dtype != (torch.float64 if f64 else torch.float32):
+        sfx = suffix(dtype)
+        if rows is not None and rows.dtype != getattr(torch, dtype.name):
             raise ValueError("rows are %s but the job's element type is %s" % (rows.dtype, dtype))
         if rows is not None and rows.numel():
-            if rows.dtype not in (torch.float32, torch.float64) or rows.dim() != 2 or not rows.is_cuda or (rows.shape[1] > 1 and rows.stride(1) != 1):
+            if rows.dim() != 2 or not rows.is_cuda or (rows.shape[1] > 1 and rows.stride(1) != 1):
                 raise ValueError("rows must be a row-major 2-D float32 or float64 CUDA tensor")
             ptr, nl, d, ld = rows.data_ptr(), rows.shape[0], rows.shape[1], (rows.stride(0) if rows.shape[0] > 1 else max(rows.shape[1], 1))
-            st = stream if stream is not None else torch.cuda.current_stream(rows.device).cuda_stream
+            st = stream_arg(stream, rows.device)
         else:
-            ptr, nl, d, ld, st = None, 0, (rows.shape[1] if rows is not None else 0), 1, 0
+            ptr, nl, d, ld, st = None, 0, (rows.shape[1] if rows is not None else 0), 1, C.c_void_p(0)
         idb = C.create_string_buffer(bytes(comm_id), _lib.PN_COMM_ID_BYTES)
-        create = _lib.lib().pn_sharded_create_rank_device_f64 if f64 else _lib.lib().pn_sharded_create_rank_device_f32
-        check(create(ptr, nl, d, ld, int(n_total), int(rank), int(world), idb, int(device), C.c_void_p(st), C.byref(h)))
-        out = cls(h.value, dtype=np.float64 if f64 else np.float32)
+        check(getattr(_lib.lib(), "pn_sharded_create_rank_device_" + sfx)(
+            ptr, nl, d, ld, int(n_total), int(rank), int(world), idb, int(device), st, C.byref(h)))
+        out = cls(h.value, dtype=dtype)
         out.device = int(device)
         return out
-
-    def close(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            from . import _lib
-            _lib.lib().pn_sharded_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_option(self, opt: int, value: int):
-        from . import _lib
-        from .errors import check
-        check(_lib.lib().pn_sharded_set_option(self._h, opt, int(value)))
-        return self
-
-    def set_engine(self, name: str):
-        from . import _lib
-        from .ball_tree import ENGINES
-        return self.set_option(_lib.PN_OPT_ENGINE, ENGINES[name])
-
-    def stats(self, reset: bool = False):
-        from . import _lib
-        from .errors import check
-        s = _lib.PnStats()
-        check(_lib.lib().pn_sharded_get_stats(self._h, C.byref(s), int(reset)))
-        return {k: getattr(s, k) for k, _ in s._fields_ if k != "reserved"}
 
     def num_points(self) -> int:
         return self.n
 
-    def query_batch(self, queries, k: int):
-        """host queries (nq, d) -> (idx uint64, dist of the handle's dtype) of shape (nq, min(k, n))"""
-        from . import _lib
-        from .errors import check
-        a = np.ascontiguousarray(queries, dtype=self.dtype)
-        if a.ndim != 2:
-            raise ValueError("queries must be 2-D")
-        nq, qc = a.shape
-        kout = min(int(k), self.n)
-        idx = np.empty((nq, kout), dtype=np.uint64)
-        dist = np.empty((nq, kout), dtype=self.dtype)
-        if nq and kout:
-            check(getattr(_lib.lib(), "pn_sharded_query_" + self._sfx)(self._h, a.ctypes.data, nq, qc, max(qc, 1), int(k),
-                                                                      idx.ctypes.data, dist.ctypes.data))
-        return idx, dist
-
     def query(self, point, k: int):
         i, d = self.query_batch(np.asarray(point, dtype=self.dtype).reshape(1, -1), k)
         return i[0], d[0]
-
-    def query_device(self, queries, k: int, out_idx=None, out_dist=None, stream=None):
-        """queries / results in HBM (torch CUDA tensors), enqueued on the current stream"""
-        import torch
-        from . import _lib
-        from .errors import check
-        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
-        if queries.dtype != tdt or queries.dim() != 2 or not queries.is_cuda:
-            raise ValueError("queries must be a 2-D CUDA tensor of the handle's dtype (%s)" % self.dtype)
-        if queries.shape[1] > 1 and queries.stride(1) != 1:
-            queries = queries.contiguous()
-        nq, qc = queries.shape
-        kout = min(int(k), self.n)
-        if out_idx is None:
-            out_idx = torch.empty((nq, kout), dtype=torch.int64, device=queries.device)
-        if out_dist is None:
-            out_dist = torch.empty((nq, kout), dtype=tdt, device=queries.device)
-        if nq and kout:
-            st = stream if stream is not None else torch.cuda.current_stream(queries.device).cuda_stream
-            check(getattr(_lib.lib(), "pn_sharded_query_device_" + self._sfx)(
-                self._h, queries.data_ptr(), nq, qc, queries.stride(0) if nq > 1 else max(qc, 1), int(k),
-                out_idx.data_ptr(), out_dist.data_ptr(), C.c_void_p(st)))
-        return out_idx, out_dist
-
-    def query_radius_device(self, queries, distance, capacity: int, out_offsets=None, out_idx=None, out_total=None,
-                            stream=None):
-        """``pn_sharded_query_radius_device_*`` (one-shard handles): see ``BallTree.query_radius_device``."""
-        import torch
-        from . import _lib
-        from .errors import check
-        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
-        if queries.dtype != tdt or queries.dim() != 2 or not queries.is_cuda:
-            raise ValueError("queries must be a 2-D CUDA tensor of the handle's dtype (%s)" % self.dtype)
-        if queries.shape[1] > 1 and queries.stride(1) != 1:
-            queries = queries.contiguous()
-        nq, qc = queries.shape
-        dev = queries.device
-        offs = out_offsets if out_offsets is not None else torch.empty(nq + 1, dtype=torch.int64, device=dev)
-        idx = out_idx if out_idx is not None else torch.empty(max(int(capacity), 1), dtype=torch.int64, device=dev)
-        tot = out_total if out_total is not None else torch.empty(1, dtype=torch.int64, device=dev)
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        r = C.c_double(distance) if self.dtype == np.float64 else C.c_float(distance)
-        fn = getattr(_lib.lib(), f"pn_sharded_query_radius_device_{self._sfx}")
-        check(fn(self._h, queries.data_ptr() if nq * qc else None, nq, qc, queries.stride(0) if nq > 1 else max(qc, 1), r,
-                 offs.data_ptr(), idx.data_ptr(), int(capacity), tot.data_ptr(), C.c_void_p(st)))
-        return offs, idx, tot
-
-    def query_radius_batch(self, queries, distance):
-        """CSR (offsets[nq+1], indices) of ``{ i : dist(q, p_i) < distance }`` over all shards, ascending per query."""
-        from . import _lib
-        from .errors import check
-        a = np.ascontiguousarray(queries, dtype=self.dtype)
-        nq, qc = a.shape
-        offsets = np.zeros(nq + 1, dtype=np.uint64)
-        out = C.c_void_p(0)
-        r = C.c_double(distance) if self.dtype == np.float64 else C.c_float(distance)
-        check(getattr(_lib.lib(), "pn_sharded_query_radius_" + self._sfx)(self._h, a.ctypes.data, nq, qc, max(qc, 1), r,
-                                                                         offsets.ctypes.data, C.byref(out)))
-        total = int(offsets[-1])
-        try:
-            idx = (np.frombuffer((C.c_uint64 * total).from_address(out.value), dtype=np.uint64).copy()
-                   if total else np.empty(0, dtype=np.uint64))
-        finally:
-            if out.value:
-                _lib.lib().pn_free(out)
-        return offsets, idx
-
-    def query_radius_with_distance_batch(self, queries, distance, sort: bool = False):
-        """``query_radius_batch`` over all shards plus each neighbour's distance: ``(offsets, idx, dist)``, ascending by
-        global row, or by (distance, global row) with ``sort=True`` (``pn_sharded_query_radius_with_distance_*``)."""
-        from . import _lib
-        from .errors import check
-        a = np.ascontiguousarray(queries, dtype=self.dtype)
-        if a.ndim != 2:
-            raise ValueError("queries must be 2-D")
-        nq, qc = a.shape
-        offsets = np.zeros(nq + 1, dtype=np.uint64)
-        out_i, out_d = C.c_void_p(0), C.c_void_p(0)
-        r = C.c_double(distance) if self.dtype == np.float64 else C.c_float(distance)
-        flags = _lib.PN_RADIUS_SORTED if sort else 0
-        fn = getattr(_lib.lib(), "pn_sharded_query_radius_with_distance_" + self._sfx)
-        try:
-            check(fn(self._h, a.ctypes.data, nq, qc, max(qc, 1), r, flags, offsets.ctypes.data, C.byref(out_i),
-                     C.byref(out_d)))
-            total = int(offsets[-1])
-            idx = np.empty(0, dtype=np.uint64)
-            dist = np.empty(0, dtype=self.dtype)
-            if total:
-                idx = np.frombuffer((C.c_uint64 * total).from_address(out_i.value), dtype=np.uint64).copy()
-                ct = C.c_double if self.dtype == np.float64 else C.c_float
-                dist = np.frombuffer((ct * total).from_address(out_d.value), dtype=self.dtype).copy()
-        finally:
-            for p in (out_i, out_d):
-                if p.value:
-                    _lib.lib().pn_free(p)
-        return offsets, idx, dist
-
-    def query_radius_with_distance_device(self, queries, distance, capacity: int, sort: bool = False, out_offsets=None,
-                                          out_idx=None, out_dist=None, out_total=None, stream=None):
-        """``pn_sharded_query_radius_with_distance_device_*`` (one-shard handles): see
-        ``BallTree.query_radius_with_distance_device``."""
-        import torch
-        from . import _lib
-        from .errors import check
-        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
-        if not isinstance(queries, torch.Tensor) or queries.dtype != tdt or queries.dim() != 2 or not queries.is_cuda:
-            raise ValueError("queries must be a 2-D CUDA tensor of the handle's dtype (%s)" % self.dtype)
-        if int(capacity) < 0:
-            raise ValueError("capacity must be >= 0")
-        if queries.shape[1] > 1 and queries.stride(1) != 1:
-            queries = queries.contiguous()
-        nq, qc = queries.shape
-        dev = queries.device
-        cap = max(int(capacity), 1)
-        offs = out_offsets if out_offsets is not None else torch.empty(nq + 1, dtype=torch.int64, device=dev)
-        idx = out_idx if out_idx is not None else torch.empty(cap, dtype=torch.int64, device=dev)
-        dist = out_dist if out_dist is not None else torch.empty(cap, dtype=tdt, device=dev)
-        tot = out_total if out_total is not None else torch.empty(1, dtype=torch.int64, device=dev)
-        if dist.dtype != tdt or idx.numel() < int(capacity) or dist.numel() < int(capacity) or offs.numel() < nq + 1:
-            raise ValueError("output tensors are too small or of the wrong type")
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        r = C.c_double(distance) if self.dtype == np.float64 else C.c_float(distance)
-        flags = _lib.PN_RADIUS_SORTED if sort else 0
-        fn = getattr(_lib.lib(), f"pn_sharded_query_radius_with_distance_device_{self._sfx}")
-        check(fn(self._h, queries.data_ptr() if nq * qc else None, nq, qc, queries.stride(0) if nq > 1 else max(qc, 1), r,
-                 flags, offs.data_ptr(), idx.data_ptr(), dist.data_ptr(), int(capacity), tot.data_ptr(), C.c_void_p(st)))
-        return offs, idx, dist, tot
-
-
-    # ---- self-queries (pn_sharded_query_self_*, pn_sharded_query_radius_self_*): the BallTree methods of the same names
-    # over the whole corpus, answered for the LOCAL rows (rows local_first_row .. local_first_row + local_rows), global
-    # row numbers.  In rank mode every rank calls them with the same arguments.
-    def _self_flags(self, include_self, sort=False):
-        from . import _lib
-        return (_lib.PN_SELF_INCLUDE if include_self else 0) | (_lib.PN_RADIUS_SORTED if sort else 0)
-
-    def _self_k(self, k, include_self):
-        if int(k) < 0:
-            raise ValueError("k must be >= 0")
-        return min(int(k), self.n if include_self else self.n - 1)
-
-    def query_self(self, k: int, include_self: bool = False):
-        """The k nearest OTHER rows of every local row: ``(idx uint64 [local_rows, kout], dist [local_rows, kout])``,
-        kout = min(k, n - 1) (``include_self``: min(k, n)), ordered by (distance, global row)."""
-        from . import _lib
-        from .errors import check
-        kout = self._self_k(k, include_self)
-        idx = np.empty((self.local_rows, kout), dtype=np.uint64)
-        dist = np.empty((self.local_rows, kout), dtype=self.dtype)
-        if kout:  # (a rank without rows still takes part: NumPy's empty arrays keep a non-NULL buffer)
-            check(getattr(_lib.lib(), "pn_sharded_query_self_" + self._sfx)(
-                self._h, int(k), self._self_flags(include_self), idx.ctypes.data, dist.ctypes.data))
-        return idx, dist
-
-    def query_self_device(self, k: int, include_self: bool = False, out_idx=None, out_dist=None, stream=None):
-        """``query_self`` with the results in HBM of the handle's GPU: CUDA tensors ``(idx int64 [local_rows, kout],
-        dist [local_rows, kout])``, enqueued on ``stream`` (default: the current torch stream)."""
-        import torch
-        from . import _lib
-        from .errors import check
-        if self.device is None:
-            raise ValueError("device-resident self-queries need a handle that drives ONE GPU")
-        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
-        kout = self._self_k(k, include_self)
-        dev = torch.device("cuda", self.device)
-        rows = self.local_rows
-        if out_idx is None:
-            out_idx = torch.empty((rows, kout), dtype=torch.int64, device=dev)
-        if out_dist is None:
-            out_dist = torch.empty((rows, kout), dtype=tdt, device=dev)
-        if out_dist.dtype != tdt or out_idx.numel() < rows * kout or out_dist.numel() < rows * kout:
-            raise ValueError("output tensors are too small or of the wrong type")
-        if kout:
-            st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-            keep = None
-            pi, pd = out_idx.data_ptr(), out_dist.data_ptr()
-            if not rows:  # (placeholders a rank without rows hands in: nothing is written to them)
-                keep = (torch.empty(1, dtype=torch.int64, device=dev), torch.empty(1, dtype=tdt, device=dev))
-                pi, pd = keep[0].data_ptr(), keep[1].data_ptr()
-            check(getattr(_lib.lib(), "pn_sharded_query_self_device_" + self._sfx)(
-                self._h, int(k), self._self_flags(include_self), pi, pd, C.c_void_p(st)))
-            del keep
-        return out_idx, out_dist
-
-    def query_radius_self(self, r, with_distance: bool = False, sort: bool = False, include_self: bool = False):
-        """``{ j != i : distance(p_i, p_j) < r }`` for every local row i, as CSR over the local rows: ``(offsets uint64
-        [local_rows + 1], idx uint64, dist or None)``; ascending by global row, or by (distance, row) with ``sort=True``
-        (needs ``with_distance``)."""
-        from . import _lib
-        from .errors import check
-        if sort and not with_distance:
-            raise ValueError("sort=True needs with_distance=True")
-        offsets = np.zeros(self.local_rows + 1, dtype=np.uint64)
-        out_i, out_d = C.c_void_p(0), C.c_void_p(0)
-        rr = C.c_float(r) if self._sfx == "f32" else C.c_double(r)
-        fn = getattr(_lib.lib(), "pn_sharded_query_radius_self_" + self._sfx)
-        try:
-            check(fn(self._h, rr, self._self_flags(include_self, sort), offsets.ctypes.data, C.byref(out_i),
-                     C.byref(out_d) if with_distance else None))
-            total = int(offsets[-1])
-            idx = np.empty(0, dtype=np.uint64)
-            dist = np.empty(0, dtype=self.dtype) if with_distance else None
-            if total:
-                idx = np.frombuffer((C.c_uint64 * total).from_address(out_i.value), dtype=np.uint64).copy()
-                if with_distance:
-                    ct = C.c_float if self._sfx == "f32" else C.c_double
-                    dist = np.frombuffer((ct * total).from_address(out_d.value), dtype=self.dtype).copy()
-        finally:
-            for p in (out_i, out_d):
-                if p.value:
-                    _lib.lib().pn_free(p)
-        return offsets, idx, dist
-
-    def query_radius_self_device(self, r, capacity: int, with_distance: bool = False, sort: bool = False,
-                                 include_self: bool = False, out_offsets=None, out_idx=None, out_dist=None, out_total=None,
-                                 stream=None):
-        """``BallTree.query_radius_self_device`` on a handle with ONE shard (several shards: PN_ERR_UNSUPPORTED, the
-        host entry ``query_radius_self`` serves them): CUDA tensors ``(offsets int64 [n+1], idx int64 [capacity], dist
-        [capacity] or None, total int64 [1])``."""
-        import torch
-        from . import _lib
-        from .errors import check
-        if int(capacity) < 0:
-            raise ValueError("capacity must be >= 0")
-        if sort and not with_distance:
-            raise ValueError("sort=True needs with_distance=True")
-        if self.device is None:
-            raise ValueError("device-resident self-queries need a handle that drives ONE GPU")
-        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
-        dev = torch.device("cuda", self.device)
-        cap = max(int(capacity), 1)
-        rows = self.local_rows
-        offs = out_offsets if out_offsets is not None else torch.empty(rows + 1, dtype=torch.int64, device=dev)
-        idx = out_idx if out_idx is not None else torch.empty(cap, dtype=torch.int64, device=dev)
-        dist = None
-        if with_distance:
-            dist = out_dist if out_dist is not None else torch.empty(cap, dtype=tdt, device=dev)
-            if dist.dtype != tdt or dist.numel() < int(capacity):
-                raise ValueError("output tensors are too small or of the wrong type")
-        tot = out_total if out_total is not None else torch.empty(1, dtype=torch.int64, device=dev)
-        if idx.numel() < int(capacity) or offs.numel() < rows + 1:
-            raise ValueError("output tensors are too small")
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        rr = C.c_float(r) if self._sfx == "f32" else C.c_double(r)
-        fn = getattr(_lib.lib(), "pn_sharded_query_radius_self_device_" + self._sfx)
-        check(fn(self._h, rr, self._self_flags(include_self, sort), offs.data_ptr(), idx.data_ptr(),
-                 dist.data_ptr() if dist is not None else None, int(capacity), tot.data_ptr(), C.c_void_p(st)))
-        return offs, idx, dist, tot
 
 
 class AbiShardEngine:
