@@ -12,6 +12,7 @@ those units under ``build/`` for the no-FMA audit in tests/test_build.py.
 from __future__ import annotations
 
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -56,7 +57,8 @@ UNITS = [
 ]
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
           "-fno-fast-math", "-fhip-fp32-correctly-rounded-divide-sqrt"]
-HEADERS = [os.path.join(CSRC, "pn_internal.h"), os.path.join(CSRC, "topk_buffer.h"), os.path.join(CSRC, "host_tree.h"),
+HEADERS = [os.path.join(CSRC, "pn_internal.h"), os.path.join(CSRC, "bf16_launch.h"), os.path.join(CSRC, "topk_buffer.h"),
+           os.path.join(CSRC, "host_tree.h"),
            os.path.join(CSRC, "union_find.h"),
            os.path.join(os.path.dirname(HERE), "include", "petal_mi355x.h")]
 
@@ -66,6 +68,26 @@ def hipcc() -> str:
         if c and os.path.exists(c):
             return c
     raise RuntimeError("hipcc not found: the MI355X library cannot be built (no CPU fallback exists)")
+
+
+def _sees_diag_flags(path: str, seen: set | None = None) -> bool:
+    """Does this file, or a header of the project that it includes (followed through), name a macro this build sets?
+    (bf16_launch.h reads -DPN_DIAG_PAIR_MIN_RUN for the plan in index.hip, which never spells it.)  Flags that are no
+    -D switch may touch anything: every unit then counts."""
+    names = [f[2:].split("=")[0] for f in DIAG if f.startswith("-D")]
+    if len(names) != len(DIAG):
+        return True
+    seen = set() if seen is None else seen
+    seen.add(path)
+    text = open(path).read()
+    if any(n in text for n in names):
+        return True
+    for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', text, re.M):
+        for d in (os.path.dirname(path), os.path.join(os.path.dirname(HERE), "include")):
+            h = os.path.normpath(os.path.join(d, inc))
+            if h not in seen and os.path.exists(h) and _sees_diag_flags(h, seen):
+                return True
+    return False
 
 
 def _stale(target: str, deps: list[str]) -> bool:
@@ -94,7 +116,7 @@ def build(force: bool = False, keep_asm: bool = False, verbose: bool = False) ->
     for src, extra in UNITS:
         sp = os.path.join(CSRC, src)
         obj = os.path.join(BUILD, os.path.splitext(src)[0] + ".o")
-        if DIAG and "PN_DIAG" not in open(sp).read():
+        if DIAG and not _sees_diag_flags(sp):
             # a unit that never looks at a diagnostic flag: the product object is the same object
             prod = os.path.join(BUILD_PRODUCT, os.path.splitext(src)[0] + ".o")
             if os.path.exists(prod) and not _stale(prod, [sp, me] + HEADERS):

@@ -1356,7 +1356,7 @@ struct BfShared {
     uint32_t epoch;   // 1 .. 4095, different from the previous launch on these buffers
     uint32_t rank;    // r: the shared threshold is the r-th smallest bound of the union
     uint32_t nseg;    // segments per query
-    // seed in the kernel (Bf16Shared in pn_internal.h): lists of the scout launch -> starting thresholds (main launch);
+    // seed in the kernel (Bf16SeedLists in pn_internal.h): lists of the scout launch -> starting thresholds (main launch);
     // words the scout launch sets to +inf
     const float *seed_lists;
     uint32_t seed_rank, seed_nq;
@@ -3083,229 +3083,147 @@ template hipError_t launch_bf16_pack_queries<double>(const double *, const float
                                                      uint32_t *, bool, double, double, hipStream_t, double *, size_t, uint32_t *,
                                                      const Bf16SeedModel *);
 
-// (450 until the end of round 4; with thresholds from the seed model and 25 row ranges per query tile a 500 k-row shard
-// of C2 runs 312-tile runs and the 4-wave kernel is 3.5 % faster there, 156- and 78-tile runs are even / 1 % in favour
-// of 8 waves: profiles/r04_waves_ab_model.log)
-constexpr uint32_t kBf8MaxRun = 200;  // runs shorter than this many tiles take the 8-wave main-pass kernel
-constexpr size_t kBf8MaxImage = (size_t)768 << 20;  // ... on corpora whose tile image is at most this large
-constexpr bool kPairAuto = true;      // the automatic choice may take the paired kernel (bf16_filter_kernel_pair)
-#ifndef PN_DIAG_PAIR_MIN_RUN
-#define PN_DIAG_PAIR_MIN_RUN 200
-#endif
-constexpr uint32_t kPairMinRun = PN_DIAG_PAIR_MIN_RUN;  // ... for runs of at least this many tiles (64-slot buffers, >= 2 query tiles)
+// ---- launchers of the filter kernels: they run what the descriptor (Bf16Launch, pn_internal.h) names or refuse it --
+// which main-pass kernel serves a call is bf16_main_kernel's decision (bf16_launch.h), made by the plan in index.hip
+static_assert(kBQ == (int)kBf16QueryTile && kBP == (int)kBf16RowTile && kWR == (int)kBf16WideTile, "bf16_launch.h");
 // PN_DEBUG_PLAN: one line per main-pass launch of a k-NN call -- which kernel (4 / 8 / pair) and its grid
 static void bf_debug_kernel(const char *which, unsigned grid, unsigned block) {
-    static const bool on = getenv("PN_DEBUG_PLAN") != nullptr;
-    if (on) std::fprintf(stderr, "bf16 main pass: kernel %s grid %u x %u\n", which, grid, block);
+    if (debug_plan()) std::fprintf(stderr, "bf16 main pass: kernel %s grid %u x %u\n", which, grid, block);
+}
+template <auto Kern, typename... A>
+static hipError_t bf_go(unsigned grid, unsigned block, size_t sh, hipStream_t s, A... args) {
+    static LdsAttrOnce lds_attr;  // per instantiation
+    const hipError_t e = lds_attr.ensure(reinterpret_cast<const void *>(Kern), sh);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(Kern, dim3(grid), dim3(block), sh, s, args...);
+    return hipGetLastError();
+}
+// What both launchers ask of a descriptor: buffers that fit the grid, a grid that is bf16_grid's, and the pointers
+// its pass needs -- no others.
+static bool bf_launch_valid(const Bf16Launch &l, bool wide) {
+    const CandBuf &cb = l.cb;
+    const Bf16Grid &g = l.grid, w = bf16_grid(l.n, cb.nq_pad, g.n_wg, g.split, wide);
+    if (!bf16_supported(l.dim) || bf16_is_wide(l.dim) != wide || cb.nq_pad % kBQ || l.kp < 1 || l.kp + 32 > cb.cap ||
+        (cb.cap != 64 && cb.cap != 128 && cb.cap != 256) || cb.idx_stride != 2 ||
+        cb.idx != static_cast<uint32_t *>(cb.keys) + 1 || g.n_wg < 1 || g.split < 1 || l.scout_tiles < 0)
+        return false;
+    if (g.q_tiles < 1 || g.q_tiles != w.q_tiles || g.n_tiles != w.n_tiles || g.aligned != w.aligned || g.nseg != w.nseg ||
+        g.run_tiles != w.run_tiles || cb.nseg < g.nseg || (wide ? g.split != 1 : (uint32_t)g.split > g.n_tiles))
+        return false;
+    const bool thresholds = l.pass == Bf16Pass::Seeded || l.pass == Bf16Pass::Radius;
+    if (thresholds != (l.tau != nullptr) || (l.pass == Bf16Pass::ScoutOnly) != (l.scout_out != nullptr)) return false;
+    return l.pass != Bf16Pass::Radius || (cb.cap == 256 && !l.refresh);  // (fixed thresholds: nothing to share)
 }
 template <int KS, int M, bool RAD, bool CI>
-static hipError_t launch_bf16_t(const void *img, uint32_t n_tiles, const void *B, uint32_t q_tiles, uint32_t kp,
-                                const CandBuf &cb, int n_wg, uint32_t split, uint32_t spp, uint32_t scout_max,
-                                const uint32_t *tau_init, float *scout_out, const Bf16Shared *shp, hipStream_t s) {
+static hipError_t launch_bf16_t(const Bf16Launch &l, hipStream_t s) {
+    const CandBuf &cb = l.cb;
+    const Bf16Grid &g = l.grid;
     const size_t sh = (size_t)3 * kBP * (2 * KS + 1) * 16 + 16;  // three tile buffers (software-pipelined main loop) + the arrival counter
+    const uint32_t kp = (uint32_t)l.kp, split = (uint32_t)g.split, scout = (uint32_t)l.scout_tiles;
     const uint32_t kp_keep = kp | ((uint32_t)(M <= 2 && !RAD && cb.final_keep > (int)kp ? cb.final_keep : 0) << 16);
-    const bool use_sh = shp && shp->n_refresh > 0;
-    BfShared bsh{};
-    bsh.nseg = (uint32_t)cb.nseg;
-    if (shp) {
-        bsh.seed_lists = shp->seed_lists;
-        bsh.seed_rank = shp->seed_rank;
-        bsh.seed_nq = shp->seed_nq;
-        bsh.seed_words = shp->seed_words;
-        if (bsh.seed_lists && (bsh.seed_rank < 1 || bsh.seed_rank > (uint32_t)kScoutList || !bf16_seed_in_kernel(cb.nseg)))
-            return hipErrorInvalidValue;
+    const uint32_t spp = (uint32_t)bf16_touching((size_t)g.q_tiles * split, g.n_wg);  // segments per row part
+    const unsigned n_wg = (unsigned)g.n_wg, n_all = n_wg + (unsigned)(l.refresh ? l.refresh->n_refresh : 0);
+    BfShared a{};
+    a.nseg = (uint32_t)cb.nseg;
+    if (l.seed) {
+        a.seed_lists = l.seed->lists;
+        a.seed_rank = l.seed->rank;
+        a.seed_nq = l.seed->nq;
+        a.seed_words = l.seed->words;
     }
-#define PN_BF_LAUNCH_MODE(MD)                                                                                          \
-    {                                                                                                                   \
-        auto kern = bf16_filter_kernel<KS, M, RAD, CI, MD>;                                                             \
-        static LdsAttrOnce lds_attr; /* per instantiation */                                                            \
-        const hipError_t e = lds_attr.ensure(reinterpret_cast<const void *>(kern), sh);                                 \
-        if (e != hipSuccess) return e;                                                                                  \
-        hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(256), sh, s, static_cast<const char *>(img), n_tiles,       \
-                           static_cast<const u32x4 *>(B), q_tiles, kp_keep, static_cast<uint2 *>(cb.keys), cb.cnt,      \
-                           static_cast<uint32_t *>(cb.tau), cb.nq_pad, split, spp, scout_max, tau_init, scout_out,      \
-                           bsh);                                                                                        \
+    if (l.refresh) {  // shared thresholds: refresher workgroups behind the n_wg main ones
+        a.pcnt = l.refresh->pcnt;
+        a.done = l.refresh->done;
+        a.n_main = n_wg;
+        a.epoch = l.refresh->epoch;
+        a.rank = l.refresh->rank;
     }
-    // The 8-wave kernel (bf16_filter8_kernel): main pass of a k-NN call (thresholds given), 64-slot buffers, aligned
-    // partition -- every workgroup one whole run
-    if constexpr (M <= 4 && !RAD) {
-        const bool aligned = split == 1 && (uint32_t)n_wg >= q_tiles && (uint32_t)n_wg % q_tiles == 0;
-        // Measured on one device (round 4, profiles/r04_waves_ab.log): at C2 (1302-tile runs) the 8-wave kernel is 7-9 %
-        // SLOWER than the 4-wave kernel (2.47-2.50 vs 2.28-2.31 ms: twice the LDS fragment traffic, an 8-wave meeting per
-        // tile), on a 125 k-row shard of C2 (163-tile runs, where the per-run fixed costs and the buffers' warm-up
-        // dominate) 3-5 % faster -- so it serves the short runs (kBf8MaxRun tiles) and the 128-slot buffers, and
-        // PN_OPT_BF16_WAVES forces either.
-        const uint32_t run_tiles = aligned ? n_tiles / ((uint32_t)n_wg / q_tiles) : 0u;
-        // (second box: a 250 k-row shard, 326-tile runs, 2.5 % faster; a 500 k-row shard, 651 tiles, 3 % slower; 128-slot
-        // buffers -- k = 100, survivors frequent -- 2 % faster at 1M x 128 and 10 % at 1M x 64 whatever the run length)
-        // (end of round 4, profiles/r04_waves_ab_long_runs.log: on corpora whose image is far beyond the 256 MB Infinity
-        // Cache the 4-wave kernel wins at every buffer size -- 10M x 128: k = 100 193 vs 205 ms, k = 10 with 128-slot
-        // buffers 181 vs 196 ms; 12.5M x 96: 1.89 vs 2.01 s -- while at 1M rows the 8-wave kernel holds its 0-9 %: the
-        // automatic choice takes it only where the image is at most kBf8MaxImage bytes)
-        const size_t image_bytes = (size_t)n_tiles * kBP * (2 * KS + 1) * 16;
-        // The paired kernel (bf16_filter_kernel_pair): where the 8-wave kernel may run, with 64-slot buffers, no
-        // refreshers and at least two query tiles.  PN_OPT_BF16_WAVES = 16 forces it where it applies; the automatic
-        // choice takes it for the long runs (the A/B behind kPairMinRun).
-        if constexpr (M == 1) {
-            const bool can_pair = aligned && !scout_out && (tau_init || bsh.seed_lists) && !use_sh && q_tiles >= 2;
-            // (automatic choice: only grids of the 4-wave kernel that fill every workgroup slot -- two of its workgroups
-            // then share a CU anyway, which is the regime of the A/B.  A grid below that gives each 4-wave workgroup a CU
-            // or a SIMD quarter of its own; pairing would put two waves on every SIMD of half as many CUs: not measured,
-            // and by the cycle budget a loss.)
-            const bool fills = cb.wg_slots > 0 && n_wg >= cb.wg_slots;
-            const bool want_pair = cb.bf16_waves == 16 || (cb.bf16_waves == 0 && kPairAuto && fills &&
-                                                           run_tiles >= kPairMinRun && image_bytes <= kBf8MaxImage);
-            if (want_pair && can_pair) {
-                const unsigned grid = (unsigned)(((q_tiles + 1u) / 2u) * ((uint32_t)n_wg / q_tiles));
-                auto kern = bf16_filter_kernel_pair<KS, CI>;
-                static LdsAttrOnce lds_attr; /* per instantiation */
-                const hipError_t e = lds_attr.ensure(reinterpret_cast<const void *>(kern), sh);
-                if (e != hipSuccess) return e;
+    const char *img = static_cast<const char *>(l.img);
+    const u32x4 *B = static_cast<const u32x4 *>(l.B);
+    uint2 *keys = static_cast<uint2 *>(cb.keys);
+    uint32_t *tau = static_cast<uint32_t *>(cb.tau);
+    if constexpr (!RAD) {  // the kernels of the main pass alone
+        if constexpr (M == 1)
+            if (l.kernel == Bf16Kernel::Pair) {
+                const unsigned grid = (unsigned)(((g.q_tiles + 1u) / 2u) * (n_wg / g.q_tiles));
                 bf_debug_kernel("pair", grid, 512);
-                hipLaunchKernelGGL(kern, dim3(grid), dim3(512), sh, s, static_cast<const char *>(img), n_tiles,
-                                   static_cast<const u32x4 *>(B), q_tiles, kp_keep, static_cast<uint2 *>(cb.keys), cb.cnt,
-                                   static_cast<uint32_t *>(cb.tau), cb.nq_pad, tau_init, bsh);
-                return hipGetLastError();
+                return bf_go<bf16_filter_kernel_pair<KS, CI>>(grid, 512, sh, s, img, g.n_tiles, B, g.q_tiles, kp_keep, keys,
+                                                              cb.cnt, tau, cb.nq_pad, l.tau, a);
             }
+        if (l.kernel == Bf16Kernel::Eight) {
+            bf_debug_kernel("8", n_all, 512);
+            return l.refresh ? bf_go<bf16_filter8_kernel<KS, CI, true, M>>(n_all, 512, sh, s, img, g.n_tiles, B, g.q_tiles, kp_keep,
+                                                                          keys, cb.cnt, tau, cb.nq_pad, l.tau, a)
+                             : bf_go<bf16_filter8_kernel<KS, CI, false, M>>(n_all, 512, sh, s, img, g.n_tiles, B, g.q_tiles, kp_keep,
+                                                                           keys, cb.cnt, tau, cb.nq_pad, l.tau, a);
         }
-        const bool want8 = cb.bf16_waves == 8 || (cb.bf16_waves == 0 && image_bytes <= kBf8MaxImage &&
-                                                  (M >= 2 || run_tiles < kBf8MaxRun));
-        if (want8 && aligned && !scout_out && (tau_init || bsh.seed_lists)) {
-            if (use_sh && (!tau_init || shp->n_refresh < 1 || M > 2)) return hipErrorInvalidValue;
-            BfShared a = bsh;
-            if (use_sh) {
-                a.pcnt = shp->pcnt;
-                a.done = shp->done;
-                a.n_main = (uint32_t)n_wg;
-                a.epoch = shp->epoch;
-                a.rank = shp->rank;
+        if constexpr (M <= 2)
+            if (l.refresh) {
+                bf_debug_kernel("4", n_all, 256);
+                return bf_go<bf16_filter_kernel<KS, M, false, CI, 2, true>>(n_all, 256, sh, s, img, g.n_tiles, B, g.q_tiles, kp_keep,
+                                                                           keys, cb.cnt, tau, cb.nq_pad, split, spp, scout, l.tau,
+                                                                           l.scout_out, a);
             }
-            const unsigned grid = (unsigned)(n_wg + (use_sh ? shp->n_refresh : 0));
-#define PN_BF_LAUNCH8(SHV)                                                                                              \
-    {                                                                                                                   \
-        auto kern = bf16_filter8_kernel<KS, CI, SHV, M>;                                                                  \
-        static LdsAttrOnce lds_attr; /* per instantiation */                                                            \
-        const hipError_t e = lds_attr.ensure(reinterpret_cast<const void *>(kern), sh);                                 \
-        if (e != hipSuccess) return e;                                                                                  \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), sh, s, static_cast<const char *>(img), n_tiles,                 \
-                           static_cast<const u32x4 *>(B), q_tiles, kp_keep, static_cast<uint2 *>(cb.keys), cb.cnt,      \
-                           static_cast<uint32_t *>(cb.tau), cb.nq_pad, tau_init, a);                                    \
     }
-            bf_debug_kernel("8", grid, 512);
-            if (use_sh) PN_BF_LAUNCH8(true) else PN_BF_LAUNCH8(false)
-#undef PN_BF_LAUNCH8
-            return hipGetLastError();
-        }
+#define PN_BF_LAUNCH_MODE(MD)                                                                                            \
+    bf_go<bf16_filter_kernel<KS, M, RAD, CI, MD>>(n_wg, 256, sh, s, img, g.n_tiles, B, g.q_tiles, kp_keep, keys, cb.cnt, tau, \
+                                                  cb.nq_pad, split, spp, scout, l.tau, l.scout_out, a)
+    if (l.pass == Bf16Pass::ScoutOnly) return PN_BF_LAUNCH_MODE(1);
+    if (l.pass != Bf16Pass::SelfScout) {
+        if (!RAD) bf_debug_kernel("4", n_wg, 256);
+        return PN_BF_LAUNCH_MODE(2);
     }
-    if (use_sh) {  // shared thresholds: main pass with refresher workgroups behind the n_wg main ones
-        if constexpr (!RAD && M <= 2) {
-            if (!tau_init || scout_out || split != 1 || shp->n_refresh < 1) return hipErrorInvalidValue;
-            auto kern = bf16_filter_kernel<KS, M, false, CI, 2, true>;
-            static LdsAttrOnce lds_attr;
-            const hipError_t e = lds_attr.ensure(reinterpret_cast<const void *>(kern), sh);
-            if (e != hipSuccess) return e;
-            BfShared a = bsh;
-            a.pcnt = shp->pcnt;
-            a.done = shp->done;
-            a.n_main = (uint32_t)n_wg;
-            a.epoch = shp->epoch;
-            a.rank = shp->rank;
-            bf_debug_kernel("4", (unsigned)(n_wg + shp->n_refresh), 256);
-            hipLaunchKernelGGL(kern, dim3((unsigned)(n_wg + shp->n_refresh)), dim3(256), sh, s,
-                               static_cast<const char *>(img), n_tiles, static_cast<const u32x4 *>(B), q_tiles, kp_keep,
-                               static_cast<uint2 *>(cb.keys), cb.cnt, static_cast<uint32_t *>(cb.tau), cb.nq_pad, split,
-                               spp, scout_max, tau_init, scout_out, a);
-            return hipGetLastError();
-        } else {
-            return hipErrorInvalidValue;
-        }
-    }
-    if (scout_out) {
-        if (RAD) return hipErrorInvalidValue;
-        PN_BF_LAUNCH_MODE(1)
-    } else if (tau_init) {
-        if (!RAD) bf_debug_kernel("4", (unsigned)n_wg, 256);
-        PN_BF_LAUNCH_MODE(2)
-    } else {
-        if (RAD) return hipErrorInvalidValue;
-        PN_BF_LAUNCH_MODE(0)
-    }
+    return PN_BF_LAUNCH_MODE(0);
 #undef PN_BF_LAUNCH_MODE
-    return hipGetLastError();
 }
 
 template <int KS, bool CI>
-static hipError_t launch_bf16_m(const void *img, uint32_t n_tiles, const void *B, uint32_t q_tiles, uint32_t kp,
-                                const CandBuf &cb, int n_wg, uint32_t split, uint32_t spp, uint32_t scout_max,
-                                const uint32_t *tau_init, bool radius, float *scout_out, const Bf16Shared *shp,
-                                hipStream_t s) {
-    if (radius)
-        return cb.cap == 256 && tau_init && !(shp && shp->n_refresh > 0) ? launch_bf16_t<KS, 4, true, CI>(img, n_tiles, B, q_tiles, kp, cb, n_wg,
-                                                                                  split, spp, scout_max, tau_init,
-                                                                                  nullptr, nullptr, s)
-                                                 : hipErrorInvalidValue;
-    switch (cb.cap) {
-        case 64:
-            return launch_bf16_t<KS, 1, false, CI>(img, n_tiles, B, q_tiles, kp, cb, n_wg, split, spp, scout_max,
-                                                   tau_init, scout_out, shp, s);
-        case 128:
-            return launch_bf16_t<KS, 2, false, CI>(img, n_tiles, B, q_tiles, kp, cb, n_wg, split, spp, scout_max,
-                                                   tau_init, scout_out, shp, s);
-        case 256:
-            return launch_bf16_t<KS, 4, false, CI>(img, n_tiles, B, q_tiles, kp, cb, n_wg, split, spp, scout_max,
-                                                   tau_init, scout_out, shp, s);
-        default: return hipErrorInvalidValue;
+static hipError_t launch_bf16_m(const Bf16Launch &l, hipStream_t s) {
+    if (l.pass == Bf16Pass::Radius) return launch_bf16_t<KS, 4, true, CI>(l, s);
+    switch (l.cb.cap) {
+        case 64: return launch_bf16_t<KS, 1, false, CI>(l, s);
+        case 128: return launch_bf16_t<KS, 2, false, CI>(l, s);
+        default: return launch_bf16_t<KS, 4, false, CI>(l, s);
     }
-}
-
-// cb: keys = (key, row) pairs [nseg][nq_pad][cap] (cb.idx = keys + 1, cb.idx_stride = 2), cap = bf16_cap_for(kp);
-// cnt/tau PRE-INITIALISED to 0 / sortable(+inf);
-// nseg >= mfma_v2_max_segments(nq_pad / 256, n_wg)
-int bf16_segments(size_t q_tiles, int n_wg, int split) {
-    return split * mfma_v2_max_segments(q_tiles * (size_t)split, n_wg);
 }
 
 bool bf16_shared_supported(int cap) {
     return cap == 64 || cap == 128;
 }
-hipError_t launch_bf16_filter(const void *img, size_t n, int dim, const void *B, int kp, const CandBuf &cb, int n_wg,
-                              int split, int scout_max, const uint32_t *tau_init, bool radius, float *scout_out,
-                              bool ci, hipStream_t s, const Bf16Shared *shp) {
-    if (!bf16_supported(dim) || bf16_is_wide(dim) || cb.nq_pad % kBQ || kp < 1 || kp + 32 > cb.cap || cb.idx_stride != 2 ||
-        cb.idx != static_cast<uint32_t *>(cb.keys) + 1 || split < 1 || scout_max < 0 || (ci && !bf16_ci_dim(dim)))
+// cb: keys = (key, row) pairs [nseg][nq_pad][cap] (cb.idx = keys + 1, cb.idx_stride = 2), cap = bf16_cap_for(kp);
+// cnt/tau PRE-INITIALISED to 0 / sortable(+inf) where the partition is not aligned
+hipError_t launch_bf16_filter(const Bf16Launch &l, hipStream_t s) {
+    const CandBuf &cb = l.cb;
+    if (!bf_launch_valid(l, false) || (l.ci && !bf16_ci_dim(l.dim)) ||
+        !bf16_kernel_applies(l.kernel, l.grid, cb.cap, l.pass, l.refresh.has_value()))
         return hipErrorInvalidValue;
-    const uint32_t n_tiles = (uint32_t)((n + kBP - 1) / kBP);
-    const uint32_t q_tiles = (uint32_t)(cb.nq_pad / kBQ);
-    if ((uint32_t)split > n_tiles) return hipErrorInvalidValue;
-    if (shp && shp->n_refresh > 0 &&
-        (!(split == 1 && (uint32_t)n_wg >= q_tiles && (uint32_t)n_wg % q_tiles == 0) || !bf16_shared_supported(cb.cap) ||
-                shp->epoch < 1 || shp->epoch > 4095 || shp->rank < 1 || !shp->pcnt || !shp->done))
-        return hipErrorInvalidValue;  // shared thresholds need the aligned partition (exactly nseg cells per query)
-    const uint32_t spp = (uint32_t)mfma_v2_max_segments((size_t)q_tiles * split, n_wg);
-    // a whole number of workgroups per query tile (and no row parts): every (segment, query) cell has exactly one
-    // writer and there are exactly n_wg / q_tiles segments
-    const bool aligned = split == 1 && (uint32_t)n_wg >= q_tiles && (uint32_t)n_wg % q_tiles == 0;
-    if (cb.nseg < (aligned ? n_wg / (int)q_tiles : (int)(spp * split))) return hipErrorInvalidValue;
-    const uint32_t sp = (uint32_t)split, sm = (uint32_t)scout_max;
+    if (l.refresh) {  // shared thresholds need the main pass of an aligned partition (exactly nseg cells per query)
+        const Bf16Refresh &r = *l.refresh;
+        if (l.pass != Bf16Pass::Seeded || !l.grid.aligned || !bf16_shared_supported(cb.cap) || r.n_refresh < 1 ||
+            r.epoch < 1 || r.epoch > 4095 || r.rank < 1 || !r.pcnt || !r.done)
+            return hipErrorInvalidValue;
+    }
+    if (l.seed && (!l.seed->lists || l.seed->rank < 1 || l.seed->rank > (uint32_t)kScoutList || !bf16_seed_in_kernel(cb.nseg)))
+        return hipErrorInvalidValue;
 #define PN_BF_CASE(K, C) \
-    case K: return launch_bf16_m<K, C>(img, n_tiles, B, q_tiles, (uint32_t)kp, cb, n_wg, sp, spp, sm, tau_init, radius, scout_out, shp, s);
+    case K: return launch_bf16_m<K, C>(l, s);
 #ifdef PN_DEV_KS8_ONLY  // development builds: only the D = 128 CI instantiation (compiles in a fraction of the time)
-    if (ci) {
-        switch (bf16_ks_for(dim, true)) {
+    if (l.ci) {
+        switch (bf16_ks_for(l.dim, true)) {
             PN_BF_CASE(8, true)
             default: return hipErrorInvalidValue;
         }
     }
     return hipErrorInvalidValue;
 #else
-    if (ci) {
-        switch (bf16_ks_for(dim, true)) {
+    if (l.ci) {
+        switch (bf16_ks_for(l.dim, true)) {
             PN_BF_CASE(2, true) PN_BF_CASE(3, true) PN_BF_CASE(4, true) PN_BF_CASE(5, true) PN_BF_CASE(6, true)
             PN_BF_CASE(7, true) PN_BF_CASE(8, true)
             default: return hipErrorInvalidValue;
         }
     }
-    switch (bf16_ks_for(dim, false)) {
+    switch (bf16_ks_for(l.dim, false)) {
         PN_BF_CASE(2, false) PN_BF_CASE(3, false) PN_BF_CASE(4, false) PN_BF_CASE(5, false) PN_BF_CASE(6, false)
         PN_BF_CASE(7, false) PN_BF_CASE(8, false) PN_BF_CASE(9, false)
         default: return hipErrorInvalidValue;
@@ -3497,53 +3415,28 @@ hipError_t launch_bf16_bound(const void *img, const void *B, size_t n_rows, size
     return hipGetLastError();
 }
 
-// ---- wide rows: launchers
-// cb: as for launch_bf16_filter, with cb.nseg >= bf16_wide_segments(q_tiles, n_wg); cells without a writer must
-// read "empty" (cnt 0, tau +inf, lists +inf) unless n_wg is a multiple of the number of query tiles
-int bf16_wide_segments(size_t q_tiles, int n_wg) {  // cells per query: two row halves per touching workgroup
-    if (n_wg > 0 && (size_t)n_wg % q_tiles == 0) return 2 * (int)((size_t)n_wg / q_tiles);  // aligned: exact
-    return 2 * mfma_v2_max_segments(q_tiles, n_wg);
-}
-
-hipError_t launch_bf16_wide_filter(const void *img, size_t n, int dim, const void *B, int kp, const CandBuf &cb,
-                                   int n_wg, int scout_max, const uint32_t *tau_init, bool radius, float *scout_out,
-                                   hipStream_t s) {
-    if (!bf16_supported(dim) || !bf16_is_wide(dim) || cb.nq_pad % kWR || kp < 1 || kp + 32 > cb.cap ||
-        cb.idx_stride != 2 || cb.idx != static_cast<uint32_t *>(cb.keys) + 1 || n_wg < 1 || scout_max < 0 ||
-        cb.nseg < bf16_wide_segments(cb.nq_pad / kWR, n_wg) || (radius && (cb.cap != 256 || !tau_init)))
-        return hipErrorInvalidValue;
-    const uint32_t n_tiles = (uint32_t)((n + kWR - 1) / kWR);
-    const uint32_t nkc = (uint32_t)bf16_wide_nkc(dim), has_x = bf16_wide_has_x(dim) ? 1u : 0u;
-    const uint32_t tile_bytes = (uint32_t)bf16_wide_tile_bytes(dim);
-    if ((unsigned long long)n_wg > (unsigned long long)(cb.nq_pad / kWR) * n_tiles) return hipErrorInvalidValue;
-    const size_t grid = (size_t)n_wg;
+// ---- wide rows: launcher.  The kernel reads its pass off its arguments (l.tau, l.scout_out: bf_launch_valid ties
+// them to l.pass); cells without a writer must read "empty" (cnt 0, tau +inf, lists +inf) unless the grid is aligned
+template <int M, bool RAD>
+static hipError_t launch_bf16_wide_t(const Bf16Launch &l, hipStream_t s) {
     const size_t sh = (size_t)2 * kWStage + 2 * kWXPiece;  // two stages + two extras pieces
-#define PN_WIDE_CASE(MM, RR)                                                                                        \
-    {                                                                                                               \
-        auto kern = bf16_wide_kernel<MM, RR>;                                                                       \
-        static LdsAttrOnce lds_attr;                                                                                \
-        {                                                                                                           \
-            const hipError_t e = lds_attr.ensure(reinterpret_cast<const void *>(kern), sh);                         \
-            if (e != hipSuccess) return e;                                                                          \
-        }                                                                                                           \
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), sh, s, static_cast<const char *>(img), n_tiles,   \
-                           static_cast<const char *>(B), nkc, tile_bytes, has_x, (uint32_t)kp,                      \
-                           static_cast<uint2 *>(cb.keys), cb.cnt,                                                   \
-                           static_cast<uint32_t *>(cb.tau), cb.nq_pad, (uint32_t)scout_max, tau_init, scout_out);   \
+    return bf_go<bf16_wide_kernel<M, RAD>>((unsigned)l.grid.n_wg, 512, sh, s, static_cast<const char *>(l.img), l.grid.n_tiles,
+                                           static_cast<const char *>(l.B), (uint32_t)bf16_wide_nkc(l.dim),
+                                           (uint32_t)bf16_wide_tile_bytes(l.dim), bf16_wide_has_x(l.dim) ? 1u : 0u,
+                                           (uint32_t)l.kp, static_cast<uint2 *>(l.cb.keys), l.cb.cnt,
+                                           static_cast<uint32_t *>(l.cb.tau), l.cb.nq_pad, (uint32_t)l.scout_tiles, l.tau,
+                                           l.scout_out);
+}
+hipError_t launch_bf16_wide_filter(const Bf16Launch &l, hipStream_t s) {
+    if (!bf_launch_valid(l, true) || l.kernel != Bf16Kernel::Wide || l.seed || l.refresh ||
+        (unsigned long long)l.grid.n_wg > (unsigned long long)l.grid.q_tiles * l.grid.n_tiles)
+        return hipErrorInvalidValue;
+    if (l.pass == Bf16Pass::Radius) return launch_bf16_wide_t<4, true>(l, s);
+    switch (l.cb.cap) {
+        case 64: return launch_bf16_wide_t<1, false>(l, s);
+        case 128: return launch_bf16_wide_t<2, false>(l, s);
+        default: return launch_bf16_wide_t<4, false>(l, s);
     }
-    if (radius) {
-        if (scout_out) return hipErrorInvalidValue;
-        PN_WIDE_CASE(4, true)
-    } else {
-        switch (cb.cap) {
-            case 64: PN_WIDE_CASE(1, false) break;
-            case 128: PN_WIDE_CASE(2, false) break;
-            case 256: PN_WIDE_CASE(4, false) break;
-            default: return hipErrorInvalidValue;
-        }
-    }
-#undef PN_WIDE_CASE
-    return hipGetLastError();
 }
 
 // debug / test entry for wide rows: the same MFMA chain, step by step in the kernel's order

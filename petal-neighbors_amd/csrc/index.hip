@@ -1295,7 +1295,7 @@ static const PlanKnobs &plan_knobs() {
             const char *e = getenv("PN_EXP_MODEL_ALL_PLANS");
             v.model_shared_only = e && e[0] == '0';
         }
-        v.debug = getenv("PN_DEBUG_PLAN") != nullptr;
+        v.debug = debug_plan();
         return v;
     }();
     return k;
@@ -1372,12 +1372,11 @@ static int seed_model_build(pn_index *ix, const T *rows, hipStream_t s) {
     cb.cap = 64;
     HIPCHK(hipMemsetD32Async((hipDeviceptr_t)lists.p, (int)0x7F800000u, words, s));
     // scout-only launch over every tile of every run (scout_max beyond any run's length): buffers are not touched
-    if (wide)
-        HIPCHK(launch_bf16_wide_filter(ix->d_img, ix->n, dim, bq.p, 24, cb, NWG, (int)(r_tiles / NWG + 2), nullptr, false,
-                                       (float *)lists.p, s));
-    else
-        HIPCHK(launch_bf16_filter(ix->d_img, ix->n, dim, bq.p, 24, cb, NWG, 1, (int)(r_tiles / NWG + 2), nullptr, false,
-                                  (float *)lists.p, ix->bf16_ci, s, nullptr));
+    Bf16Launch scout{ix->d_img, ix->n, dim, ix->bf16_ci, bq.p, 24, cb, bf16_grid(ix->n, NQ, NWG, 1, wide), Bf16Pass::ScoutOnly,
+                     wide ? Bf16Kernel::Wide : Bf16Kernel::Four};
+    scout.scout_tiles = (int)(r_tiles / NWG + 2);
+    scout.scout_out = (float *)lists.p;
+    HIPCHK(wide ? launch_bf16_wide_filter(scout, s) : launch_bf16_filter(scout, s));
     std::vector<double> h_mom(4 * (size_t)dim);
     std::vector<T> h_q(NQ * ld);
     std::vector<float> h_mu((size_t)dim), h_lists(words);
@@ -1496,8 +1495,11 @@ static int seed_model_build(pn_index *ix, const T *rows, hipStream_t s) {
 }
 
 struct Bf16Plan {
-    int n_wg, split, nseg, kp, cap, scout_max;
-    bool ok, aligned;
+    Bf16Grid grid;           // the partition: workgroups, row parts, segments per query, aligned or not (bf16_launch.h)
+    Bf16Pass main_pass;      // the main launch: Seeded (thresholds from the shared scout or the seed model) or SelfScout
+    Bf16Kernel main_kernel;  // what runs it: bf16_main_kernel's answer for this plan (wide rows: Wide)
+    int kp, cap, scout_max;
+    bool ok;
     // shared scout (several segments per query): scout-only launch, merged seed of rank seed_rank, main launch
     bool shared_scout;
     int scout_tiles, seed_rank;
@@ -1537,7 +1539,7 @@ static void plan_seed_model(const pn_index *ix, Bf16Plan &p, double R, size_t ko
 static Bf16Plan bf16_plan_wide(const pn_index *ix, size_t nq_pad, size_t kout, int level) {
     Bf16Plan p{};
     p.wide = true;
-    p.split = 1;
+    p.main_kernel = Bf16Kernel::Wide;
     const size_t q_tiles = nq_pad / 256, r_tiles = (ix->n + 255) / 256;
     // c workgroups per query tile, each a row range: the fewest within 8 % of the best CU occupancy among those that
     // leave every run at least 8 row tiles (every run pays a scout pass and a pipeline fill, every segment adds k'
@@ -1564,10 +1566,8 @@ static Bf16Plan bf16_plan_wide(const pn_index *ix, size_t nq_pad, size_t kout, i
     for (;; best = (best + 1) / 2) {
         size_t n_wg = q_tiles * best;
         if (n_wg > q_tiles * r_tiles) n_wg = q_tiles * r_tiles;  // tiny corpora: one unit per workgroup at least
-        p.n_wg = (int)n_wg;
+        p.grid = bf16_grid(ix->n, nq_pad, (int)n_wg, 1, true);
         p.per_tile = (int)(n_wg / q_tiles > 0 ? n_wg / q_tiles : 1);  // workgroups per query tile
-        p.aligned = n_wg % q_tiles == 0;
-        p.nseg = bf16_wide_segments(q_tiles, p.n_wg);
         segs = 2.0 * (double)p.per_tile;  // segments a query's relevant rows are spread over
         double kp;
         if (ix->filter_slots > 0)
@@ -1583,9 +1583,9 @@ static Bf16Plan bf16_plan_wide(const pn_index *ix, size_t nq_pad, size_t kout, i
         p.ok = level < 2 && p.kp + 32 <= 256;
         p.cap = p.ok ? bf16_cap_for(p.kp) : 0;
         // the re-rank kernel gathers all cells of a query into 64 KiB of LDS (12 B per slot + the query row)
-        if (best == 1 || select_rerank_lds_bytes(p.nseg, p.cap, 0, ix->dim, 4) <= 60 * 1024) break;
+        if (best == 1 || select_rerank_lds_bytes(p.grid.nseg, p.cap, 0, ix->dim, 4) <= 60 * 1024) break;
     }
-    if (select_rerank_lds_bytes(p.nseg, p.cap, 0, ix->dim, 4) > kSelectRerankLdsMax) p.ok = false;
+    if (select_rerank_lds_bytes(p.grid.nseg, p.cap, 0, ix->dim, 4) > kSelectRerankLdsMax) p.ok = false;
     // a wave scouts 128 rows per tile; the scouted rows should hold < 0.1 of the R relevant rows in expectation
     const double sm = (double)ix->n / (10.0 * R) / 128.0;
     p.scout_max = sm > 32.0 ? 32 : (int)sm;
@@ -1593,7 +1593,7 @@ static Bf16Plan bf16_plan_wide(const pn_index *ix, size_t nq_pad, size_t kout, i
     // number of the R relevant rows in it (<= 1.2), seed_rank = smallest rank with P(Poisson >= rank) <= 1e-7
     p.shared_scout = false;
     if (p.ok && level == 0 && ix->filter_slots == 0 && segs >= 4.0) {
-        const size_t run_len = q_tiles * r_tiles / (size_t)p.n_wg;
+        const size_t run_len = q_tiles * r_tiles / (size_t)p.grid.n_wg;
         double lam_w = 1.2, t_cap_w = 16.0;
         if (plan_knobs().scout_lambda > 0.0) lam_w = plan_knobs().scout_lambda;  // experiments only
         if (plan_knobs().scout_cap > 0.0) t_cap_w = plan_knobs().scout_cap;      // experiments only
@@ -1603,7 +1603,7 @@ static Bf16Plan bf16_plan_wide(const pn_index *ix, size_t nq_pad, size_t kout, i
         p.scout_tiles = (int)t;
         if (p.scout_tiles >= 1) {
             // a query tile may be touched by one workgroup more than per_tile: the sample is at most this large
-            const double lam = R * (double)p.scout_tiles * 128.0 * (double)p.nseg / (double)ix->n;
+            const double lam = R * (double)p.scout_tiles * 128.0 * (double)p.grid.nseg / (double)ix->n;
             double term = std::exp(-lam), cdf = term;
             int rank = 1;
             while (1.0 - cdf > 1e-7 && rank < 2 * bf16_scout_list()) {
@@ -1617,10 +1617,11 @@ static Bf16Plan bf16_plan_wide(const pn_index *ix, size_t nq_pad, size_t kout, i
     }
     p.first_eval = (int)std::ceil(R);
     plan_seed_model(ix, p, R, kout, p.shared_scout);
+    p.main_pass = p.shared_scout ? Bf16Pass::Seeded : Bf16Pass::SelfScout;
     if (plan_knobs().debug)
         fprintf(stderr, "bf16_plan_wide: n %zu q_tiles %zu k %zu R %.0f: n_wg %d per_tile %d nseg %d kp %d cap %d shared_scout %d "
                         "scout_tiles %d seed_rank %d model_seed %d z %.3f\n",
-                ix->n, q_tiles, kout, R, p.n_wg, p.per_tile, p.nseg, p.kp, p.cap, (int)p.shared_scout, p.scout_tiles, p.seed_rank,
+                ix->n, q_tiles, kout, R, p.grid.n_wg, p.per_tile, p.grid.nseg, p.kp, p.cap, (int)p.shared_scout, p.scout_tiles, p.seed_rank,
                 (int)p.model_seed, p.model_z);
     return p;
 }
@@ -1711,7 +1712,6 @@ static Bf16Plan bf16_plan(const pn_index *ix, size_t nq_pad, size_t kout, int le
     // a query-tile boundary is two runs, each with its own operand load, scout pass and buffer warm-up, and those
     // workgroups set the kernel's time (C2: 512 workgroups = 12.8 per tile 4.34 ms, 480 = 12 per tile 3.62 ms)
     if (n_wg > q_tiles && !plan_knobs().unaligned) n_wg = n_wg / q_tiles * q_tiles;
-    p.n_wg = (int)n_wg;
     // rows whose bound lies below the k-th neighbour's distance: ~1.2 k on benign data once the vectors are
     // translated by the corpus mean (measured: 11.8 for k = 10, 116 for k = 100); planned with a margin
     // (norm-in-accumulator layout: the per-query error constant uses the corpus maxima -- measured 23 / 237 rows for
@@ -1746,7 +1746,6 @@ static Bf16Plan bf16_plan(const pn_index *ix, size_t nq_pad, size_t kout, int le
         if (c != per_tile && kp_of(c) <= 224.0) {
             per_tile = c;
             n_wg = q_tiles * c;
-            p.n_wg = (int)n_wg;
         }
     }
     auto kp_for = [&](int split) -> double {
@@ -1761,29 +1760,26 @@ static Bf16Plan bf16_plan(const pn_index *ix, size_t nq_pad, size_t kout, int le
     };
     // split the rows of a query tile into parts only while one buffer would need more than 128 slots
     // (every part pays its own warm-up), and keep parts of at least 256 tiles
-    p.split = 1;
+    int split = 1;
     if (level == 0 && ix->opt_segments == 0 && ix->filter_slots == 0)
-        while (p.split < 8 && kp_for(p.split) > 96.0 && r_tiles / (size_t)(2 * p.split) >= 256 &&
-               (size_t)(2 * p.split) > per_tile)  // (only where more parts ARE more segments: few workgroups per query tile)
-            p.split *= 2;
-    double kp = kp_for(p.split);
+        while (split < 8 && kp_for(split) > 96.0 && r_tiles / (size_t)(2 * split) >= 256 &&
+               (size_t)(2 * split) > per_tile)  // (only where more parts ARE more segments: few workgroups per query tile)
+            split *= 2;
+    double kp = kp_for(split);
     // A k' between 17 and 31 lives in 128-slot buffers anyway, so the tail it is planned against costs nothing but
     // candidates there: the count of relevant rows varies from query to query (22 +- 5.3, up to 44 of 256 queries for
     // k = 10: heavier than Poisson), and the queries at the upper end are the ones that overflow a segment.  Measured,
     // 10M x 128, 10^5 queries, k = 10, 5 segments: k' = 20 left 15 queries per batch to the second tier -- 15 exact
     // scans of 10^7 rows, 22 of the step's 215 ms; planned for twice the mean (k' = 30): see DESIGN.md 4.0.
     if (level == 0 && ix->filter_slots == 0 && kp > 16.0 && kp < 32.0) {
-        const double per2 = 2.0 * R / (double)(per_tile > (size_t)p.split ? per_tile : (size_t)p.split);
+        const double per2 = 2.0 * R / (double)(per_tile > (size_t)split ? per_tile : (size_t)split);
         const double v = per2 + n_sigma * std::sqrt(per2) + 3.0;
         kp = v < 32.0 ? (v > kp ? v : kp) : 32.0;
     }
     p.kp = (int)std::ceil(kp);
     p.ok = level < 2 && p.kp + 32 <= 256;
     p.cap = p.ok ? bf16_cap_for(p.kp) : 0;
-    p.nseg = bf16_segments(q_tiles, p.n_wg, p.split);
-    // aligned partition: exactly n_wg / q_tiles segments, every cell written by exactly one workgroup
-    p.aligned = p.split == 1 && (size_t)p.n_wg >= q_tiles && (size_t)p.n_wg % q_tiles == 0;
-    if (p.aligned) p.nseg = p.n_wg / (int)q_tiles;
+    p.grid = bf16_grid(ix->n, nq_pad, (int)n_wg, split);  // (aligned or not, and the segments per query that follow)
     // scouted rows should hold < 0.1 of the R relevant rows in expectation: tiles <= N / (10 R) / 64
     const double sm = (double)r_tiles / (10.0 * R);
     p.scout_max = sm > 64.0 ? 64 : (int)sm;
@@ -1793,8 +1789,7 @@ static Bf16Plan bf16_plan(const pn_index *ix, size_t nq_pad, size_t kout, int le
     // relevant rows inside the sample (kept <= 1.2); the seed must stay above them: seed_rank = smallest rank with
     // P(Poisson(lambda) >= rank) <= 1e-7 (a seed that is too low only sends the query to the next tier).
     p.shared_scout = false;
-    if (p.ok && level == 0 && ix->filter_slots == 0 && p.split == 1 && per_tile >= 2 &&
-        p.n_wg % (int)q_tiles == 0) {
+    if (p.ok && level == 0 && ix->filter_slots == 0 && p.grid.aligned && per_tile >= 2) {
         const size_t run_len = r_tiles / per_tile;
         // How large a sample: its share of the corpus is lambda / R, and the seed lands at the corpus' rank
         // seed_rank(lambda) R / lambda -- ~7.5 R at lambda = 1.2, ~3 R at 9.  For k = 10 (R = 24) lambda = 1.2 is a
@@ -1824,7 +1819,7 @@ static Bf16Plan bf16_plan(const pn_index *ix, size_t nq_pad, size_t kout, int le
                 ++rank;
             }
             p.seed_rank = rank < 5 ? 5 : rank;
-            p.shared_scout = p.seed_rank < 96 && p.seed_rank <= 6 * p.nseg;
+            p.shared_scout = p.seed_rank < 96 && p.seed_rank <= 6 * p.grid.nseg;
             if (p.shared_scout || p.scout_tiles < 8) break;
             p.scout_tiles = p.scout_tiles * 3 / 4;
         }
@@ -1850,9 +1845,9 @@ static Bf16Plan bf16_plan(const pn_index *ix, size_t nq_pad, size_t kout, int le
     p.sh_rank = 0;
     // (with thresholds from the seed model the segments start where sharing would only bring them later: measured on
     // one device, C2: 2.09-2.11 ms with refreshers, 2.06-2.07 without -- sharing stays for explicit ranks and scouted plans)
-    if (p.shared_scout && p.aligned && ix->shared_tau != 0 && !(p.model_seed && ix->shared_tau == 1) &&
+    if (p.shared_scout && p.grid.aligned && ix->shared_tau != 0 && !(p.model_seed && ix->shared_tau == 1) &&
         bf16_shared_supported(p.cap)) {
-        const int slots = 2 * ix->n_cu - p.n_wg;
+        const int slots = 2 * ix->n_cu - p.grid.n_wg;
         const int rank = ix->shared_tau >= 2 ? ix->shared_tau : (int)std::ceil(R + 5.5 * std::sqrt(R));
         // (a refresher holds up to 512 keys of a query's union in registers -- and at k = 100 (r = 330, 128-slot buffers)
         // sharing measured 6 % SLOWER, 3.44 -> 3.65 ms: there a buffer's own compactions already keep its threshold near
@@ -1860,15 +1855,21 @@ static Bf16Plan bf16_plan(const pn_index *ix, size_t nq_pad, size_t kout, int le
         // ~0.25 ms, so short runs end before it pays: a 125 k-row shard of C2, 163 tiles per run, measured 2-4 % slower)
         size_t sh_min_run = 320;  // (same-device A/B: 326-tile runs, a 250 k-row shard of C2, 0.88-0.91 -> 0.875-0.885 ms; 163-tile runs +4 %)
         if (plan_knobs().sh_min_run) sh_min_run = plan_knobs().sh_min_run;  // experiments only
-        if (slots >= 4 && rank <= 256 && rank < p.nseg * p.cap && r_tiles / per_tile >= sh_min_run) {
+        if (slots >= 4 && rank <= 256 && rank < p.grid.nseg * p.cap && r_tiles / per_tile >= sh_min_run) {
             p.n_refresh = slots > 64 ? 64 : slots;
             p.sh_rank = rank;
         }
     }
+    // The main launch filters against given thresholds (the shared scout's seed, the seed model's) or scouts for itself;
+    // which kernel runs it is decided here, by bf16_main_kernel, from what only the plan knows: the device's workgroup
+    // slots and PN_OPT_BF16_WAVES go no further.  The launcher runs what the plan names (and refuses what cannot run).
+    p.main_pass = p.shared_scout || (p.model_seed && ix->d_smodel) ? Bf16Pass::Seeded : Bf16Pass::SelfScout;
+    p.main_kernel = bf16_main_kernel(p.grid, p.cap, p.main_pass, p.n_refresh > 0,
+                                     bf16_image_bytes(ix->n, (int)ix->dim, ix->bf16_ci), 2 * ix->n_cu, ix->bf16_waves);
     if (plan_knobs().debug)  // development aid: what a call was planned as
         fprintf(stderr, "bf16_plan: n %zu q_tiles %zu k %zu R %.0f: n_wg %d per_tile %zu split %d nseg %d kp %d cap %d aligned %d "
                         "shared_scout %d scout_tiles %d seed_rank %d scout_max %d n_refresh %d sh_rank %d model_seed %d z %.3f\n",
-                ix->n, q_tiles, kout, R, p.n_wg, per_tile, p.split, p.nseg, p.kp, p.cap, (int)p.aligned, (int)p.shared_scout,
+                ix->n, q_tiles, kout, R, p.grid.n_wg, per_tile, split, p.grid.nseg, p.kp, p.cap, (int)p.grid.aligned, (int)p.shared_scout,
                 p.scout_tiles, p.seed_rank, p.scout_max, p.n_refresh, p.sh_rank, (int)p.model_seed, p.model_z);
     return p;
 }
@@ -1969,7 +1970,7 @@ static int run_bf16(const pn_index *ix, Workspace &ws, const Bf16Plan &plan, con
     if (!plan.ok) return fail(PN_ERR_UNSUPPORTED, "bf16 tier cannot serve k = %zu", kout);
     const bool cosine = ix->metric == 1;
     if (cosine && (!qnorm || d_q_raw)) return fail(PN_ERR_INVALID, "Cosine tier: query norms missing");
-    const int n_wg = plan.n_wg, cap = plan.cap, nseg = plan.nseg;
+    const int cap = plan.cap, nseg = plan.grid.nseg;
     const size_t kp = (size_t)plan.kp;
     const size_t cells = (size_t)nseg * nq_pad, slots = cells * (size_t)cap;
     PNCHK(ws.w_bq.ensure(bf16_query_bytes(nq_pad, (int)ix->dim, ix->bf16_ci)));
@@ -2015,9 +2016,7 @@ static int run_bf16(const pn_index *ix, Workspace &ws, const Bf16Plan &plan, con
                                         (T *)nullptr, 0, nullptr, model ? &smd : nullptr));
     CandBuf cb{ws.w_keys.p, (uint32_t *)ws.w_keys.p + 1, (uint32_t *)ws.w_cnt.p, ws.w_tau.p, nq_pad, nseg, cap, 2};
     cb.final_keep = bf16_cell_max((int)kp, cap, nseg, bf16_is_wide((int)ix->dim));  // what the re-rank sizes its LDS for
-    cb.bf16_waves = ix->bf16_waves;
-    cb.wg_slots = 2 * ix->n_cu;
-    if (!plan.aligned) {  // cells without a writer must read "empty" (an aligned partition writes every cell)
+    if (!plan.grid.aligned) {  // cells without a writer must read "empty" (an aligned partition writes every cell)
         HIPCHK(hipMemsetAsync(ws.w_cnt.p, 0, cells * sizeof(uint32_t), s));
         HIPCHK(hipMemsetD32Async((hipDeviceptr_t)ws.w_tau.p, (int)0xFF800000u, cells, s));
     }
@@ -2027,35 +2026,31 @@ static int run_bf16(const pn_index *ix, Workspace &ws, const Bf16Plan &plan, con
         rec->hot = true;
         rec->two_launches = plan.shared_scout && !model;  // the dominant kernel runs twice per call: both launches are timed
     }
+    // The chain: [scout-only launch -> [seed kernel]] -> main launch, each a descriptor over the same partition
+    Bf16Launch main{ix->d_img, ix->n, (int)ix->dim, ix->bf16_ci, ws.w_bq.p, (int)kp, cb, plan.grid, plan.main_pass, plan.main_kernel};
+    auto launch = [&](const Bf16Launch &l) { return plan.wide ? launch_bf16_wide_filter(l, s) : launch_bf16_filter(l, s); };
     if (plan.shared_scout) {
         const size_t words = cells * 2 * (size_t)bf16_scout_list();
         PNCHK(ws.w_lists.ensure(words * sizeof(float)));
         PNCHK(ws.w_seed.ensure(nq_pad * sizeof(uint32_t)));
-        if (!plan.aligned)
+        if (!plan.grid.aligned)
             HIPCHK(hipMemsetD32Async((hipDeviceptr_t)ws.w_lists.p, (int)0x7F800000u, words, s));  // +inf: unused cells
-        if (plan.wide && !model)
-            HIPCHK(launch_bf16_wide_filter(ix->d_img, ix->n, (int)ix->dim, ws.w_bq.p, (int)kp, cb, plan.n_wg,
-                                           plan.scout_tiles, nullptr, false, (float *)ws.w_lists.p, s));
-        // narrow rows, up to 32 segments: the main launch derives its starting thresholds from the lists itself (a
-        // lane per query in its prologue) -- one launch less in the chain (the seed kernel: 17.6 us on a 10^4-query batch)
-        const bool seed_in_kernel = !model && !plan.wide && bf16_seed_in_kernel(nseg) && plan.seed_rank <= bf16_scout_list();
-        Bf16Shared seed{};
-        if (seed_in_kernel) {
-            seed.seed_lists = (const float *)ws.w_lists.p;
-            seed.seed_rank = (uint32_t)plan.seed_rank;
-            seed.seed_nq = (uint32_t)nq;
-            seed.seed_words = (uint32_t *)ws.w_seed.p;
+        if (!model) {  // (with the seed model the query pack kernel has written the thresholds already)
+            // narrow rows, up to 32 segments: the main launch derives its starting thresholds from the lists itself (a
+            // lane per query in its prologue) -- one launch less in the chain (the seed kernel: 17.6 us on a 10^4-query batch)
+            if (!plan.wide && bf16_seed_in_kernel(nseg) && plan.seed_rank <= bf16_scout_list())
+                main.seed = Bf16SeedLists{(const float *)ws.w_lists.p, (uint32_t)plan.seed_rank, (uint32_t)nq, (uint32_t *)ws.w_seed.p};
+            Bf16Launch scout = main;
+            scout.pass = Bf16Pass::ScoutOnly;
+            scout.kernel = plan.wide ? Bf16Kernel::Wide : Bf16Kernel::Four;
+            scout.scout_tiles = plan.scout_tiles;
+            scout.scout_out = (float *)ws.w_lists.p;
+            if (plan.n_refresh == 0) scout.seed.reset();  // (it sets the seed words to +inf for the refreshers alone)
+            HIPCHK(launch(scout));
+            if (!main.seed)
+                HIPCHK(launch_bf16_seed((const float *)ws.w_lists.p, nq_pad, nseg, plan.seed_rank, (uint32_t *)ws.w_seed.p, s, nq));
         }
-        if (!plan.wide && !model)
-            HIPCHK(launch_bf16_filter(ix->d_img, ix->n, (int)ix->dim, ws.w_bq.p, (int)kp, cb, n_wg, 1, plan.scout_tiles,
-                                      nullptr, false, (float *)ws.w_lists.p, ix->bf16_ci, s,
-                                      seed_in_kernel && plan.n_refresh > 0 ? &seed : nullptr));
-        if (!seed_in_kernel && !model)
-            HIPCHK(launch_bf16_seed((const float *)ws.w_lists.p, nq_pad, nseg, plan.seed_rank, (uint32_t *)ws.w_seed.p, s, nq));
-        if (plan.wide)
-            HIPCHK(launch_bf16_wide_filter(ix->d_img, ix->n, (int)ix->dim, ws.w_bq.p, (int)kp, cb, plan.n_wg, 0,
-                                           (const uint32_t *)ws.w_seed.p, false, nullptr, s));
-        else if (plan.n_refresh > 0) {
+        if (plan.n_refresh > 0) {
             // shared thresholds: published counts tagged with this launch's epoch; d_misc[8] (zeroed with d_misc at the
             // start of the call) counts the main workgroups that are done
             const void *pc_before = ws.w_pcnt.p;
@@ -2067,28 +2062,14 @@ static int run_bf16(const pn_index *ix, Workspace &ws, const Bf16Plan &plan, con
                 ws.sh_nq_pad = nq_pad;
             }
             ws.sh_epoch = ws.sh_epoch % 4095u + 1u;
-            Bf16Shared shp = seed;
-            shp.pcnt = (uint32_t *)ws.w_pcnt.p;
-            shp.done = d_misc + 8;
-            shp.epoch = ws.sh_epoch;
-            shp.rank = (uint32_t)plan.sh_rank;
-            shp.n_refresh = plan.n_refresh;
-            HIPCHK(launch_bf16_filter(ix->d_img, ix->n, (int)ix->dim, ws.w_bq.p, (int)kp, cb, n_wg, 1, 0,
-                                      (const uint32_t *)ws.w_seed.p, false, nullptr, ix->bf16_ci, s, &shp));
-        } else
-            HIPCHK(launch_bf16_filter(ix->d_img, ix->n, (int)ix->dim, ws.w_bq.p, (int)kp, cb, n_wg, 1, 0,
-                                      (const uint32_t *)ws.w_seed.p, false, nullptr, ix->bf16_ci, s,
-                                      seed_in_kernel ? &seed : nullptr));
-    } else if (plan.wide) {
-        HIPCHK(launch_bf16_wide_filter(ix->d_img, ix->n, (int)ix->dim, ws.w_bq.p, (int)kp, cb, plan.n_wg,
-                                       plan.scout_max, nullptr, false, nullptr, s));
-    } else if (model) {  // any partition: thresholds from the seed model, no scouting inside the runs
-        HIPCHK(launch_bf16_filter(ix->d_img, ix->n, (int)ix->dim, ws.w_bq.p, (int)kp, cb, n_wg, plan.split, 0,
-                                  (const uint32_t *)ws.w_seed.p, false, nullptr, ix->bf16_ci, s));
-    } else {
-        HIPCHK(launch_bf16_filter(ix->d_img, ix->n, (int)ix->dim, ws.w_bq.p, (int)kp, cb, n_wg, plan.split,
-                                  plan.scout_max, nullptr, false, nullptr, ix->bf16_ci, s));
+            main.refresh = Bf16Refresh{(uint32_t *)ws.w_pcnt.p, d_misc + 8, ws.sh_epoch, (uint32_t)plan.sh_rank, plan.n_refresh};
+        }
     }
+    if (plan.main_pass == Bf16Pass::Seeded)
+        main.tau = (const uint32_t *)ws.w_seed.p;  // from the seed kernel, the main launch's own prologue or the seed model
+    else
+        main.scout_tiles = plan.scout_max;
+    HIPCHK(launch(main));
     if (prof) HIPCHK(hipEventRecord(rec->ev[1], s));
     if (cosine) {
         HIPCHK(launch_select_rerank<T>(cb, (const T *)ix->d_pts, ix->n, (int)ix->dim, ix->ld, Qp, (int)nq, ix->ld, (int)kout,
@@ -2159,8 +2140,8 @@ static int query_enqueue(const pn_index *ix, Workspace &ws, const T *d_q, size_t
             bplan = bf16_plan(ix, nq_pad, kout, level);
             use_bf16 = bplan.ok;
             // the re-rank's LDS: what its launcher will ask for (run_bf16 launches with cell_max = bf16_cell_max)
-            if (use_bf16 && select_rerank_lds_bytes(bplan.nseg, bplan.cap,
-                                                    bf16_cell_max(bplan.kp, bplan.cap, bplan.nseg, bf16_is_wide((int)ix->dim)),
+            if (use_bf16 && select_rerank_lds_bytes(bplan.grid.nseg, bplan.cap,
+                                                    bf16_cell_max(bplan.kp, bplan.cap, bplan.grid.nseg, bf16_is_wide((int)ix->dim)),
                                                     ix->dim, sizeof(T)) > kSelectRerankLdsMax)
                 use_bf16 = false;
         }
@@ -2838,12 +2819,14 @@ static int radius_bf16_enqueue(const pn_index *ix, Workspace &ws, int level, con
     if (n_wg > cap_wg) n_wg = cap_wg;
     n_wg = bf16_grid_wgs(ix, q_tiles, r_tiles, n_wg);
     const bool wide = bf16_is_wide((int)ix->dim);
-    int wide_wg = 1;
+    Bf16Grid grid = bf16_grid(ix->n, nq_pad, (int)n_wg, 1);
     if (wide) {  // the k-NN plan's partition, at most 32 segments per query (the check kernel's LDS budget)
-        wide_wg = bf16_plan_wide(ix, nq_pad, 1, level).n_wg;
-        while (wide_wg > 1 && bf16_wide_segments(q_tiles, wide_wg) > 32) wide_wg = (wide_wg + 1) / 2;
+        grid = bf16_plan_wide(ix, nq_pad, 1, level).grid;
+        while (grid.n_wg > 1 && grid.nseg > 32) grid = bf16_grid(ix->n, nq_pad, (grid.n_wg + 1) / 2, 1, true);
     }
-    const int nseg = wide ? bf16_wide_segments(q_tiles, wide_wg) : bf16_segments(q_tiles, (int)n_wg, 1);
+    // (narrow rows: buffers for the segments of an UNALIGNED partition of these workgroups, whatever the grid is -- the
+    // check kernel walks nseg cells per query and w_cnt is zeroed below)
+    const int nseg = wide ? grid.nseg : bf16_segments(q_tiles, (int)n_wg, 1);
     const size_t cells = (size_t)nseg * nq_pad;
     const size_t kept_stride = (size_t)nseg * cap;
     // tau_r = (r^2 + 1e-37) / (1 - (D+4) 2^-24): every row whose reference distance is < r has a squared distance
@@ -2901,12 +2884,10 @@ static int radius_bf16_enqueue(const pn_index *ix, Workspace &ws, int level, con
         }
         HIPCHK(hipEventRecord(ws.ev_r[0], s));
     }
-    if (wide)
-        HIPCHK(launch_bf16_wide_filter(ix->d_img, ix->n, (int)ix->dim, ws.w_bq.p, cap - 32, cb, wide_wg, 0,
-                                       (const uint32_t *)ws.w_seed.p, true, nullptr, s));
-    else
-        HIPCHK(launch_bf16_filter(ix->d_img, ix->n, (int)ix->dim, ws.w_bq.p, cap - 32, cb, (int)n_wg, 1, 0,
-                                  (const uint32_t *)ws.w_seed.p, true, nullptr, ix->bf16_ci, s));
+    Bf16Launch pass{ix->d_img, ix->n, (int)ix->dim, ix->bf16_ci, ws.w_bq.p, cap - 32, cb, grid, Bf16Pass::Radius,
+                    wide ? Bf16Kernel::Wide : Bf16Kernel::Four};
+    pass.tau = (const uint32_t *)ws.w_seed.p;
+    HIPCHK(wide ? launch_bf16_wide_filter(pass, s) : launch_bf16_filter(pass, s));
     if (prof) HIPCHK(hipEventRecord(ws.ev_r[1], s));
     HIPCHK(launch_radius_check<T>((const uint32_t *)ws.w_cnt.p, (const uint32_t *)ws.w_idx.p + 1, nq_pad, nseg, cap,
                                   (const T *)ix->d_pts, ix->ld, Qp, (int)nq, (int)ix->dim, radius,

@@ -929,7 +929,7 @@ extern "C" int pn_debug_read(unsigned long long *out, int reset) {
 #endif
 
 int mfma_v2_max_segments(size_t q_tiles, int n_wg) {
-    return (int)((n_wg + q_tiles - 1) / q_tiles) + 1;
+    return bf16_touching(q_tiles, n_wg);  // (bf16_launch.h: the bf16 tier lays its workgroups out the same way)
 }
 
 template <int NKG, bool GC, int M>

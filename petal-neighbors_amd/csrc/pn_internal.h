@@ -6,9 +6,19 @@
 #include <atomic>
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
+#include <optional>
 #include <type_traits>
 
+#include "bf16_launch.h"
+
 namespace pn {
+
+// PN_DEBUG_PLAN (read once per process): index.hip prints every bf16 plan, bf16_filter.hip every main-pass launch
+inline bool debug_plan() {
+    static const bool on = getenv("PN_DEBUG_PLAN") != nullptr;
+    return on;
+}
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel instantiation, device): the attribute belongs to
 // the device's copy of the kernel, and index handles on different devices -- or threads -- may launch the same
@@ -62,9 +72,6 @@ struct CandBuf {
     int cap;         // slots per (segment, query); multiple of 64
     int idx_stride = 1;  // 2: keys and idx interleaved as (key, row) pairs, idx = keys + 1 (bf16 filter)
     int final_keep = 0;  // bf16 filter, 64-slot buffers: a buffer holding at most this many entries ends its run uncut (0: k')
-    int bf16_waves = 0;  // PN_OPT_BF16_WAVES: 0 = the library picks, 4 / 8 = that main-pass kernel, 16 = the paired kernel (where they apply)
-    int wg_slots = 0;    // bf16 filter: the device's workgroup slots of the 4-wave kernel (2 per CU); 0 = unknown, and the
-                         // automatic choice then never takes the paired kernel
 };
 
 inline size_t round_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
@@ -582,42 +589,52 @@ hipError_t launch_bf16_pack_queries(const T *Q, const float *mu, size_t nq, size
 // out[j * dim + k] += sum over rows of (p_k - mu_k)^(j + 1), j = 0 .. 3 (zeroed by the caller)
 template <typename T>
 hipError_t launch_bf16_column_moments(const T *P, const float *mu, size_t n, int dim, size_t ld, double *out, hipStream_t s);
-// split: row parts per query tile (>= 1); cb.nseg >= bf16_segments(q_tiles, n_wg, split); scout_max: cap on the
-// tiles of a run that are contracted first, without buffers, to seed the threshold (0 = no scouting)
-int bf16_segments(size_t q_tiles, int n_wg, int split);
-// tau_init (nullable, [nq_pad] sortable keys): starting thresholds instead of the scout pass.  radius = true:
-// fixed thresholds (tau_init required, cb.cap == 256), buffers overflow (count = cap + 1) instead of compacting
-// scout_out (nullable): scout-only launch -- no buffers are touched; every run leaves its lanes' smallest block
-// minima in scout_out[cell][2][bf16_scout_list()] (pre-filled with +inf by the caller)
-// shp (nullable; main pass of an aligned k-NN plan with tau_init only): shared thresholds -- n_refresh extra "refresher"
-// workgroups merge what the segments of a query hold and lower the query's word in tau_init while the pass runs
-// (bf16_filter.hip, "Shared thresholds").  pcnt: [nseg][nq_pad] words (zeroed whenever the geometry changes), done: one
-// word, ZEROED before the launch; epoch 1 .. 4095, different from the previous launch on pcnt; rank: r-th smallest.
-struct Bf16Shared {
+// One launch of the first tier.  grid: bf16_grid of (n, cb.nq_pad, n_wg, split) -- cb.nseg >= grid.nseg, and cells without
+// a writer must read "empty" (cnt 0, tau +inf, lists +inf) unless grid.aligned; cb.cnt / cb.tau as the pass needs them.
+// scout_tiles: ScoutOnly -- the tiles of a run that are scouted; SelfScout -- the cap on the tiles a run contracts
+// first, without buffers, to seed its threshold (0 = none).  Wide rows: in 256-row tiles.
+// tau ([nq_pad] sortable keys; Seeded, Radius): starting / fixed thresholds.  scout_out (ScoutOnly): every run leaves
+// its lanes' smallest block minima in scout_out[cell][2][bf16_scout_list()] (pre-filled with +inf unless aligned).
+// Seed in the kernel (narrow rows, <= 32 segments, bf16_seed_in_kernel): the main launch derives its starting
+// thresholds itself from the scout launch's `lists` (rank-th smallest of a query's union, `nq` real queries) -- no
+// bf16_seed_kernel launch between; the scout launch of a plan with refreshers is given it too and sets `words`
+// ([nq_pad], the words the refreshers lower) to +inf.
+struct Bf16SeedLists {
+    const float *lists;
+    uint32_t rank, nq;
+    uint32_t *words;
+};
+// Shared thresholds (Seeded pass of an aligned plan, 64- / 128-slot buffers): n_refresh extra "refresher" workgroups merge
+// what the segments of a query hold and lower the query's word in tau while the pass runs (bf16_filter.hip, "Shared
+// thresholds").  pcnt: [nseg][nq_pad] words (zeroed whenever the geometry changes), done: one word, ZEROED before the
+// launch; epoch 1 .. 4095, different from the previous launch on pcnt; rank: r-th smallest.
+struct Bf16Refresh {
     uint32_t *pcnt, *done;
     uint32_t epoch, rank;
-    int n_refresh;  // 0: no shared thresholds (the seed fields below may still be set)
-    // Seed in the kernel (narrow rows, <= 32 segments): the scout-only launch is given `seed_words` ([nq_pad], set to
-    // +inf there: the words the refreshers lower), the main launch `seed_lists` (the scout launch's lists) + the rank
-    // and the number of real queries, and derives its starting thresholds itself -- no bf16_seed_kernel launch between
-    const float *seed_lists = nullptr;
-    uint32_t seed_rank = 0, seed_nq = 0;
-    uint32_t *seed_words = nullptr;
+    int n_refresh;
+};
+struct Bf16Launch {
+    const void *img;  // corpus tile images of n rows of dim columns; ci: the layout (narrow rows)
+    size_t n;
+    int dim;
+    bool ci;
+    const void *B;    // packed queries
+    int kp;
+    CandBuf cb;
+    Bf16Grid grid;
+    Bf16Pass pass;
+    Bf16Kernel kernel;  // what bf16_main_kernel chose (narrow rows) or Wide: the launcher checks that it may run, no more
+    int scout_tiles = 0;
+    const uint32_t *tau = nullptr;
+    float *scout_out = nullptr;
+    std::optional<Bf16SeedLists> seed;
+    std::optional<Bf16Refresh> refresh;
 };
 bool bf16_seed_in_kernel(int nseg);
 bool bf16_shared_supported(int cap);
-hipError_t launch_bf16_filter(const void *img, size_t n, int dim, const void *B, int kp, const CandBuf &cb, int n_wg,
-                              int split, int scout_max, const uint32_t *tau_init, bool radius, float *scout_out,
-                              bool ci, hipStream_t s, const Bf16Shared *shp = nullptr);
-// wide rows: n_wg persistent workgroups (one per CU) over equal slices of the (query tile, row tile) list;
-// cb.nseg >= bf16_wide_segments(q_tiles, n_wg) (a workgroup's two row halves are two segments); cells without a writer
-// must read "empty" unless n_wg is a multiple of q_tiles; scout_max in 256-row tiles
-// tau_init (nullable): starting thresholds per query; radius: fixed thresholds, overflow instead of compaction (cap 256);
-// scout_out (nullable): scout-only launch, lists as for launch_bf16_filter
-int bf16_wide_segments(size_t q_tiles, int n_wg);
-hipError_t launch_bf16_wide_filter(const void *img, size_t n, int dim, const void *B, int kp, const CandBuf &cb,
-                                   int n_wg, int scout_max, const uint32_t *tau_init, bool radius, float *scout_out,
-                                   hipStream_t s);
+hipError_t launch_bf16_filter(const Bf16Launch &l, hipStream_t s);
+// wide rows: grid.n_wg persistent workgroups (one per CU) over equal slices of the (query tile, row tile) list
+hipError_t launch_bf16_wide_filter(const Bf16Launch &l, hipStream_t s);
 int bf16_scout_list();
 int bf16_cell_max(int kp, int cap, int nseg, bool wide);  // entries a cell holds at most after a k-NN launch = CandBuf::final_keep to launch with
 // out[q] = key just above the rank-th smallest value over the lists of q's nseg cells
