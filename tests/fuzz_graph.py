@@ -8,23 +8,27 @@ oracle's scalar distance per pair, checked again on sampled pairs) and nothing e
 and OPTICS come out of it through the references of the other modules, imported, not restated.  LOF is the reference over
 the library's own query_self, which the same call first anchors to the matrix.  The KDE sums and the mean shift step are
 tests/density_reference.py over the matrix' lists: the entries strictly below each query's cutoff, the rows with a NaN in
-no list (and dead seeds); the mean shift labels are the matrix' columns of the centres, by (key, centre number).
+no list (and dead seeds); the mean shift labels are the matrix' columns of the centres, by (key, centre number), and so are
+the labels and distances of a k-means assignment; its inertia and the k-means loop are tests/kmeans_reference.py.
 
 The got side calls query_self, query_radius_self (scalar and per-row radii), dbscan, mst (plain and cored), linkage,
 hdbscan, lof + lof_score, optics and optics_dbscan on one handle, host or device entry drawn at random, the device outputs
 on a stream of their own; and, borrowing the same workspace scratch, kde_self (the rows as their own queries: a kernel,
 include_self and a scalar bandwidth or one per row drawn per round, from eps), kde (a subset of the rows and one NaN query
-as external queries; on a Cosine tree the normalised density must raise, the raw sums are checked all the same) and
+as external queries; on a Cosine tree the normalised density must raise, the raw sums are checked all the same),
 mean_shift (one step of the rows as seeds, then the labels against centres picked from the rows; on a Cosine tree the call
-must raise).  The compact kernels and mean shift compare bit for bit; the smooth kernels take atol = 0 up to 1000 rows
-(every row in every list) and atol = 1 above, where the returned cutoff is held against the header's and the sums against
+must raise) and kmeans (an assignment to 1, 2, 7, 33 or 70 of the rows as centres, then two iterations of the loop from the
+same centres; on a Cosine tree all four entries must raise).  The compact kernels, mean shift and k-means compare bit
+for bit; the smooth kernels take atol = 0 up to 1000 rows (every row in every list) and atol = 1 above, where the returned cutoff is held against the header's and the sums against
 the bound of tests/test_gpu_kde.py.  Pass 1 uses the case's parameters in a random order.  Pass 2 draws an engine, an index
-base, the DBSCAN / OPTICS / KDE / mean shift pieces and the MST batch, then runs everything in another order with larger
-k / min_samples and eps halved, then with smaller ones -- so every shared workspace buffer is regrown and reused by another
+base, the DBSCAN / OPTICS / KDE / mean shift pieces, the MST batch and PN_OPT_KMEANS_FILTER, then runs everything in
+another order with larger k / min_samples and eps halved, then with smaller ones -- so every shared workspace buffer is regrown and reused by another
 owner in between -- and finally repeats calls with pass 1's parameters: those must reproduce pass 1 byte for byte.  All
 other comparisons are array equality; floats by their bits with equal NaN masks.  Whatever the KDE and mean shift entries
 draw -- kernels, flags, host or device entry, their places in the order, their pieces -- comes from a generator of the
-case's own, so the draws of the graph entries do not depend on the entries beside them.
+case's own, and whatever the k-means entry draws -- its centres, host or device entry, its place in the order, the filter
+option -- from another, so the draws of the graph entries do not depend on the entries beside them, nor those of the KDE and
+mean shift entries on k-means.
 
 Conditions (asserted on the want side before any device call, printed, never tolerances): HDBSCAN's least relative gap
 >= MIN_GAP; OPTICS has a row with infinite core distance and a finite reachability; DBSCAN has two clusters and a noise
@@ -42,6 +46,7 @@ _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, _ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import oracle  # noqa: E402
+import kmeans_reference  # noqa: E402
 import petal_neighbors_amd as pn  # noqa: E402
 from petal_neighbors_amd import _lib  # noqa: E402
 from density_reference import kde_sums, ms_step  # noqa: E402
@@ -58,10 +63,13 @@ KMAX = 64  # the longest k-NN list a case asks for
 BLOB_FAMILIES = ("blobs", "dups", "sorted", "dups_nan")
 GRAPH_ENTRIES = ("self", "radius", "radii", "dbscan", "mst", "mst_cored", "linkage", "hdbscan", "lof", "optics", "extract")
 DENSITY_ENTRIES = ("kde", "kde_self", "mean_shift")
-ENTRIES = GRAPH_ENTRIES + DENSITY_ENTRIES
+KMEANS_ENTRIES = ("kmeans",)
+ENTRIES = GRAPH_ENTRIES + DENSITY_ENTRIES + KMEANS_ENTRIES
 KDE_QUERIES = 192  # rows a case takes as external KDE queries, at most (one NaN query is added)
 KDE_ATOL = 1.0     # the smooth kernels' atol above 1000 rows (at most: atol = 0, every row in every list)
 MS_CENTRES = 7     # rows a case takes as centres for the labels, at most
+KM_CENTRES = (1, 2, 7, 33, 70)  # rows a round takes as k-means centres: one of these, at most n
+KM_ITERATIONS = 2
 
 
 # ------------------------------------------------------------------------------------------------------------ data
@@ -230,9 +238,9 @@ def eq(got, want, what):
 
 
 class Runner:
-    def __init__(self, tree, w, rng, rng2):
+    def __init__(self, tree, w, rng, rng2, rng3):
         import torch
-        self.torch, self.tree, self.w, self.rng, self.rng2 = torch, tree, w, rng, rng2
+        self.torch, self.tree, self.w, self.rng, self.rng2, self.rng3 = torch, tree, w, rng, rng2, rng3
         self.dev = torch.device("cuda", 0)
         self.stream = torch.cuda.Stream(self.dev)
         self.tdt = torch.float32 if w.dt == np.float32 else torch.float64
@@ -244,6 +252,9 @@ class Runner:
 
     def device2(self):
         return bool(self.rng2.integers(0, 2))
+
+    def device3(self):
+        return bool(self.rng3.integers(0, 2))
 
     def on_stream(self, fn):
         """fn(stream handle) enqueued on the runner's own stream; its tensors as numpy arrays"""
@@ -571,6 +582,58 @@ class Runner:
             blob += got.tobytes()
         return blob
 
+    def kmeans(self, q):
+        t, w, torch = self.tree, self.w, self.torch
+        cs = q["km"]
+        nc = len(cs)
+        centres = np.ascontiguousarray(w.x[cs])
+        what = f"{self.tag} kmeans_assign({nc} rows)"
+        if w.cosine:
+            for fn in (lambda: t.kmeans_assign(centres), lambda: t.kmeans_assign_device(self.up(centres)),
+                       lambda: t.kmeans(centres, abs_tol=0.0, max_iter=KM_ITERATIONS),
+                       lambda: t.kmeans_device(self.up(centres), 0.0, KM_ITERATIONS)):
+                try:
+                    fn()
+                except ValueError:
+                    continue
+                raise AssertionError(what + ": on a Cosine tree must raise")
+            return b""
+        # the assignment against the matrix: its columns of the centres, by (key, centre number)
+        lab = np.argmin(w.dk[:, cs], axis=1).astype(np.int64)  # (the first of equal minima: the lower centre)
+        w_dist = np.ascontiguousarray(w.d[np.arange(w.n), cs[lab]])
+        w_inertia = kmeans_reference.inertia(lab, w_dist)
+        before = t.stats()["queries"]
+        if self.device3():
+            dc = self.up(centres)
+            labels, dist, inertia = self.on_stream(lambda s: t.kmeans_assign_device(dc, stream=s))
+            inertia = inertia[0]
+        else:
+            labels, dist, inertia = t.kmeans_assign(centres)
+        assert t.stats()["queries"] - before == w.n, what
+        eq(labels, lab, what + ": labels")
+        eq_bits(dist, w_dist, what + ": distances")
+        eq_bits(np.array([inertia], dtype=np.float64), np.array([w_inertia]), what + ": inertia")
+        blob = labels.astype(np.int64).tobytes() + dist.tobytes()
+        # two iterations from the same centres against the reference of the loop
+        what = f"{self.tag} kmeans({nc} rows, abs_tol=0, max_iter={KM_ITERATIONS})"
+        want = w.memo(("km", cs.tobytes()), lambda: kmeans_reference.kmeans(w.x, centres, 0.0, KM_ITERATIONS,
+                                                                          assign=kmeans_reference.assign_matrix))
+        if self.device3():
+            dc = self.up(centres)
+            c, l, d, cnt, inr, it, s2 = self.on_stream(lambda s: t.kmeans_device(dc, 0.0, KM_ITERATIONS, stream=s))
+            inr, it, s2 = inr[0], int(it[0]), s2[0]
+        else:
+            c, l, inr, d, cnt, it, s2 = t.kmeans(centres, abs_tol=0.0, max_iter=KM_ITERATIONS, full=True)
+        w_c, w_l, w_d, w_cnt, w_inr, w_it, w_s2 = want
+        assert it == w_it, what + ": iterations"
+        eq(l, w_l, what + ": labels")
+        eq(cnt, w_cnt.astype(np.int64), what + ": counts")
+        eq_bits(c, w_c, what + ": centres")
+        eq_bits(d, w_d, what + ": distances")
+        eq_bits(np.array([inr, s2], dtype=np.float64), np.array([w_inr, w_s2], dtype=np.float64),
+                what + ": inertia, shift2")
+        return blob + c.tobytes() + l.astype(np.int64).tobytes() + d.tobytes() + cnt.astype(np.int64).tobytes()
+
     def call(self, name, q):
         if name == "lof" and self.w.n < 2:
             try:
@@ -588,12 +651,21 @@ def draw_kde(rng):
             "per_query": bool(rng.integers(0, 2)), "per_row": bool(rng.integers(0, 2))}
 
 
-def order_of(rng, rng2):
+def draw_km(rng3, n):
+    """what a round's k-means calls use: the rows taken as centres, ascending"""
+    nc = min(int(rng3.choice(KM_CENTRES)), n)
+    return np.sort(rng3.choice(n, nc, replace=False))
+
+
+def order_of(rng, rng2, rng3):
     """the graph entries in a random order drawn from ``rng``, the KDE and mean shift entries put in at places drawn from
-    ``rng2``: what ``rng`` gives the graph entries does not depend on the entries beside them"""
+    ``rng2``, then the k-means entry at a place drawn from ``rng3``: what ``rng`` gives the graph entries does not depend
+    on the entries beside them, nor what ``rng2`` gives the density entries"""
     names = [str(x) for x in rng.permutation(GRAPH_ENTRIES)]
     for name in DENSITY_ENTRIES:
         names.insert(int(rng2.integers(0, len(names) + 1)), name)
+    for name in KMEANS_ENTRIES:
+        names.insert(int(rng3.integers(0, len(names) + 1)), name)
     return names
 
 
@@ -611,15 +683,18 @@ def run_once(p, seed, rng, what):
     rng2 = np.random.default_rng([int(seed), 0x4DE5])  # every draw of the KDE and mean shift entries: the case's own generator
     q["kde"] = draw_kde(rng2)
     n, dim = x.shape
+    rng3 = np.random.default_rng([int(seed), 0x4B4D])  # ... and every draw of the k-means entry
+    q["km"] = draw_km(rng3, n)
     ok, text = conditions(q, w)
     must = p["family"] in BLOB_FAMILIES and n >= 1000
     print(f"{what}: k {q['k']}, min_samples {q['ms']}, min_cluster_size {q['m']}, kde {q['kde']}; {text}"
+          f"; kmeans from {len(q['km'])} rows"
           f"{'' if ok or not must else ' -- MISSED'}", flush=True)
     if must and not ok:
         return None
     tree = pn.BallTree.new(x, pn.distance.Cosine()) if p["cosine"] else pn.BallTree.euclidean(x)
     try:
-        r = Runner(tree, w, rng, rng2)
+        r = Runner(tree, w, rng, rng2, rng3)
         # a row with a non-finite value rules the bf16 tier out for the whole index, by design: such a case runs the exact
         # scan at its width, and that is asserted instead
         finite = bool(np.isfinite(x).all())
@@ -630,7 +705,7 @@ def run_once(p, seed, rng, what):
         # ---- pass 1
         r.tag = "pass 1:"
         first = {}
-        for name in order_of(rng, rng2):
+        for name in order_of(rng, rng2, rng3):
             first[name] = r.call(name, q)
         after = tree.stats()
         dq, dc, df = (after[f] - before[f] for f in ("queries", "candidates", "fallback_queries"))
@@ -650,20 +725,23 @@ def run_once(p, seed, rng, what):
                 _lib.PN_OPT_MS_PIECE: pieces_value(rng2, entries)}
         for o, v in opts.items():
             tree.set_option(o, v)
+        km_filter = int(rng3.choice([0, 1, 2]))
+        tree.set_option(_lib.PN_OPT_KMEANS_FILTER, km_filter)
         print(f"{what}: pass 2 under engine {engine}, index base {r.base}, dbscan / optics piece "
               f"{opts[_lib.PN_OPT_DBSCAN_PIECE]} / {opts[_lib.PN_OPT_OPTICS_PIECE]}, mst batch {opts[_lib.PN_OPT_MST_BATCH]}, "
-              f"kde / mean shift piece {opts[_lib.PN_OPT_KDE_PIECE]} / {opts[_lib.PN_OPT_MS_PIECE]}", flush=True)
+              f"kde / mean shift piece {opts[_lib.PN_OPT_KDE_PIECE]} / {opts[_lib.PN_OPT_MS_PIECE]}, kmeans filter {km_filter}",
+              flush=True)
         half = w.dt.type(0.5)
         larger = dict(q, k=max(min(2 * q["k"] + 3, n - 1, KMAX), 1), ms=max(min(2 * q["ms"] + 1, n - 1, KMAX), 1), m=2 * q["m"],
-                      eps=q["eps"] * half, max_eps=q["max_eps"] * half, include=not q["include"], kde=draw_kde(rng2))
+                      eps=q["eps"] * half, max_eps=q["max_eps"] * half, include=not q["include"], kde=draw_kde(rng2), km=draw_km(rng3, n))
         smaller = dict(q, k=max(q["k"] // 2, 1), ms=max(q["ms"] // 2, 1), m=max(q["m"] // 2, 2), eps=q["eps"] * half,
-                       kde=draw_kde(rng2))
+                       kde=draw_kde(rng2), km=draw_km(rng3, n))
         for tag, qq in (("pass 2, larger:", larger), ("pass 2, smaller:", smaller)):
             r.tag = tag
-            for name in order_of(rng, rng2):
+            for name in order_of(rng, rng2, rng3):
                 r.call(name, qq)
         r.tag = "pass 2, unchanged:"
-        for name in order_of(rng, rng2):
+        for name in order_of(rng, rng2, rng3):
             got = r.call(name, q)
             assert got == first[name], f"{what}: {name} with unchanged parameters differs from pass 1"
     finally:

@@ -1,6 +1,8 @@
 """A numpy restatement of the k-means contract of include/petal_mi355x.h (pn_kmeans_*, pn_kmeans_assign_*): the
 distance fold in the index's type, the (distance key, centre number) order, SUM4096, the update, shift2 and the stop
-rule.  Slow and plain on purpose: it is the oracle of tests/test_gpu_kmeans.py."""
+rule.  Slow and plain on purpose: it is the oracle of tests/test_gpu_kmeans.py, tests/test_gpu_kmeans_edges.py and the
+k-means entry of tests/fuzz_graph.py.  fold_matrix / assign_matrix are the same operations on all centres at once, for
+the shapes with thousands of centres; tests/test_kmeans_reference.py pins them to the plain ones bit for bit."""
 import numpy as np
 
 SEG = 4096
@@ -42,6 +44,29 @@ def assign(X, C):
         dist[take] = d[take]
         best[take] = k[take]
     return labels, dist
+
+
+def fold_matrix(X, C):
+    """fold_distances of every row of X to every centre of C at once, [n][nc]: the same sub, mul, add per column, each
+    rounded in X's type, then the square root -- element by element the operations of fold_distances, so the same bits"""
+    dt = X.dtype
+    C = np.asarray(C, dtype=dt)
+    s = np.zeros((X.shape[0], C.shape[0]), dtype=dt)
+    with np.errstate(all="ignore"):
+        for k in range(X.shape[1]):
+            diff = (C[None, :, k] - X[:, k, None]).astype(dt)
+            s = (s + (diff * diff).astype(dt)).astype(dt)
+        return np.sqrt(s).astype(dt)
+
+
+def assign_matrix(X, C):
+    """assign(X, C) through fold_matrix: the first minimum of the keys is the lower centre number"""
+    n = X.shape[0]
+    if C.shape[0] == 0:
+        return np.full(n, -1, dtype=np.int64), np.full(n, np.nan, dtype=X.dtype)
+    d = fold_matrix(X, C)
+    labels = np.argmin(_keys(d), axis=1).astype(np.int64)
+    return labels, d[np.arange(n), labels]
 
 
 def sum4096(t):
@@ -110,8 +135,9 @@ def update(X, C, labels):
     return new, np.float64(shift2)
 
 
-def kmeans(X, init, tol, max_iter):
-    """(centres, labels, dist, counts uint64, inertia, iterations, shift2)"""
+def kmeans(X, init, tol, max_iter, assign=assign):
+    """(centres, labels, dist, counts uint64, inertia, iterations, shift2); ``assign=assign_matrix`` gives the same bits
+    sooner on wide rows"""
     C = np.array(init, dtype=X.dtype, copy=True)
     t, shift2 = 0, np.float64(0.0)
     while True:

@@ -134,3 +134,46 @@ def test_lof_device_outgrows_its_graph_store_without_waiting(pn):
     want = pn.BallTree.euclidean(pts).lof(20)    # the host entry on a fresh handle
     assert lof.cpu().numpy().tobytes() == want.tobytes()
     del keep
+
+
+# pn_kmeans_assign_device_* "never waits" (the header): with the filter forced its whole chain -- packing, the MFMA
+# filter, re-rank and proof, the exact kernel over the listed rows, the inertia -- is enqueued behind the filler, the
+# count of listed rows staying on the device.
+def _kmeans_assign_behind_the_filler(pn, warm_nc, nc, what):
+    import torch
+    import kmeans_reference as ref
+    from petal_neighbors_amd import _lib
+    pts = _grow_corpus()
+    cs = np.random.default_rng(9).random((max(warm_nc, nc), 32), dtype=np.float32)
+    cs[0] = cs[1] = pts[17]              # twins on a row: a row the proof must refuse, so the list is not empty
+    tree = pn.BallTree.euclidean(pts)
+    tree.set_option(_lib.PN_OPT_KMEANS_FILTER, 1)
+    dc = torch.from_numpy(cs).cuda()
+    tree.kmeans_assign_device(dc[:warm_nc].contiguous())     # warm-up: the row image, the centre image at warm_nc
+    torch.cuda.synchronize()
+    centres = dc[:nc].contiguous()
+    stream = torch.cuda.Stream()
+    ev, keep = _busy(torch, stream)
+    assert not ev.query(), "the stream drained before the test could look (box too fast for the filler)"
+    t0 = time.perf_counter()
+    with torch.cuda.stream(stream):
+        labels, dist, inertia = tree.kmeans_assign_device(centres)
+    dt = (time.perf_counter() - t0) * 1e3
+    still_busy = not ev.query()
+    assert still_busy, f"pn_kmeans_assign_device_f32 {what} ({dt:.1f} ms)"
+    assert dt < 50.0, f"enqueueing took {dt:.1f} ms"
+    stream.synchronize()
+    wl, wd = ref.assign(pts, cs[:nc])
+    assert np.array_equal(labels.cpu().numpy(), wl)
+    assert dist.cpu().numpy().tobytes() == wd.tobytes()
+    assert inertia.cpu().numpy()[0].tobytes() == np.float64(ref.inertia(wl, wd)).tobytes()
+    assert wl[17] == 0 and wd[17] == 0 and tree.stats()["fallback_queries"] >= 1
+    del keep
+
+
+def test_kmeans_assign_device_returns_before_its_stream_has_drained(pn):
+    _kmeans_assign_behind_the_filler(pn, 40, 40, "came back only after the work queued in front of it had finished")
+
+
+def test_kmeans_assign_device_outgrows_its_centre_image_without_waiting(pn):
+    _kmeans_assign_behind_the_filler(pn, 2, 300, "waited for the device when its centre image grew")

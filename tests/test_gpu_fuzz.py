@@ -32,8 +32,8 @@ _GRAPH_REDRAWS = []
 
 @pytest.mark.parametrize("seed", [41, 42])
 def test_random_graph_calls_on_one_handle(pn, oracle_mod, seed):
-    """tests/fuzz_graph.py: every graph entry point, KDE and mean shift on one handle against one dense want side, two passes
-    with the options and parameters changed in between; n from 1 to 4500, D from 1 to 200, f32 / f64, Euclidean / Cosine,
+    """tests/fuzz_graph.py: every graph entry point, KDE, mean shift and k-means on one handle against one dense want side,
+    two passes with the options and parameters changed in between; n from 1 to 4500, D from 1 to 200, f32 / f64, Euclidean / Cosine,
     five families."""
     import fuzz_graph
     rng = np.random.default_rng(seed)

@@ -1,5 +1,5 @@
-"""Every graph entry point, and the KDE and mean shift entries that borrow the same workspace scratch (tests/fuzz_graph.py:
-one handle, one dense want side, two passes) at the smallest shapes where the code underneath changes.  Nothing above the k-NN layer ran on rows wider than 16 columns before: D > 128 is where the
+"""Every graph entry point, and the KDE, mean shift and k-means entries that borrow the same workspace scratch
+(tests/fuzz_graph.py: one handle, one dense want side, two passes) at the smallest shapes where the code underneath changes.  Nothing above the k-NN layer ran on rows wider than 16 columns before: D > 128 is where the
 bf16 tier switches to the K-chunked kernel and the chunked image layout, n >= 4096 with D >= 8 is where the auto engine
 moves the self-queries to the tier at all.
 

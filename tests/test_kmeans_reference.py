@@ -1,6 +1,7 @@
 """The numpy restatement of the k-means contract (tests/kmeans_reference.py) on cases computed by hand: it is the
 oracle of the GPU tests, so it is checked on its own first.  No GPU."""
 import numpy as np
+import pytest
 
 import kmeans_reference as ref
 
@@ -70,6 +71,53 @@ def test_sum4096_shape():
     M = rng.standard_normal((9000, 3))
     cols = ref.sum4096_columns(M)
     assert [ref.sum4096(M[:, j]) for j in range(3)] == cols.tolist()
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).tobytes()
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("shape", [(300, 17, 40), (65, 1, 3), (7, 33, 1)])
+def test_the_vectorised_fold_is_the_fold_bit_for_bit(shape, dtype):
+    """fold_matrix / assign_matrix (the want side of the many-centre tests) against fold_distances / assign, by their bits
+    (NaN payloads included: the operations are the same ones), with a NaN row, an inf row and a duplicated centre"""
+    n, dim, nc = shape
+    rng = np.random.default_rng(17 * n + dim)
+    X = (rng.standard_normal((n, dim)) * 10.0 ** rng.integers(-3, 4, (n, 1))).astype(dtype)
+    C = (rng.standard_normal((nc, dim)) * 3.0).astype(dtype)
+    if dtype == np.float64:
+        X, C = X * (1.0 + 2.0 ** -30), C * (1.0 - 2.0 ** -31)  # (low bits an f32 cannot hold)
+    X[1, dim // 2] = np.nan
+    X[2, 0] = np.inf
+    X[3, dim - 1] = -np.inf
+    if nc >= 3:
+        C[nc - 1] = C[1]  # a duplicated centre: the lower number wins
+        X[4] = C[1]       # ... at distance 0, too
+    M = ref.fold_matrix(X, C)
+    assert M.shape == (n, nc) and M.dtype == dtype
+    for c in range(nc):
+        assert _bits(M[:, c]) == _bits(ref.fold_distances(X, C[c])), c
+    wl, wd = ref.assign(X, C)
+    gl, gd = ref.assign_matrix(X, C)
+    assert gl.dtype == wl.dtype and np.array_equal(gl, wl) and gd.dtype == wd.dtype and _bits(gd) == _bits(wd)
+    assert wl[1] == 0 and np.isnan(wd[1]) and np.isinf(wd[2]) and np.isinf(wd[3])
+    if nc >= 3:
+        assert wl[4] == 1 and wd[4] == 0 and (wl != nc - 1).all()
+    # the loop over either assignment (NaN rows make centre 0 NaN after the first update: NaN payloads are not compared)
+    a, b = ref.kmeans(X, C, 0.0, 3), ref.kmeans(X, C, 0.0, 3, assign=ref.assign_matrix)
+    for u, v in zip(a, b):
+        u, v = np.atleast_1d(np.asarray(u)), np.atleast_1d(np.asarray(v))
+        assert u.dtype == v.dtype and u.shape == v.shape
+        nan = np.isnan(u) if u.dtype.kind == "f" else np.zeros(u.shape, dtype=bool)
+        assert np.array_equal(nan, np.isnan(v) if v.dtype.kind == "f" else nan) and _bits(u[~nan]) == _bits(v[~nan])
+    good = np.isfinite(X).all(axis=1)
+    a, b = ref.kmeans(X[good], C, 0.0, 3), ref.kmeans(X[good], C, 0.0, 3, assign=ref.assign_matrix)
+    assert all(_bits(u) == _bits(v) for u, v in zip(a, b)) and np.isfinite(a[0]).all() and a[5] >= 2
+    # no centres
+    gl, gd = ref.assign_matrix(X, C[:0])
+    wl, wd = ref.assign(X, C[:0])
+    assert np.array_equal(gl, wl) and gd.dtype == wd.dtype and np.all(np.isnan(gd))
 
 
 def test_fold_is_sequential_in_the_rows_type():
