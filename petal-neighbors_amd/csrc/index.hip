@@ -19,6 +19,7 @@
 
 #include "../../include/petal_mi355x.h"
 #include "pn_internal.h"
+#include "csr_pieces.h"
 
 using namespace pn;
 
@@ -232,6 +233,7 @@ constexpr int kCallRecs = 16;
 
 constexpr int kSeedModelRetry = 64, kSeedModelMaxRetries = 3;  // (see rec_resolve)
 constexpr int kSeedModelGrid = 7;  // seed model: z calibrated at the corpus ranks 16, 32, ..., 1024
+enum PieceFamily { kPieceDbscan, kPieceOptics, kPieceKde, kPieceMs, kPieceFamilies };  // (who walks a CSR in pieces: PieceWalk)
 struct pn_index {
     int device = 0;
     int elem_bytes = 4;
@@ -268,11 +270,10 @@ struct pn_index {
     double sm_sigma = 0.0;              // standard deviation of ln(rank a model threshold really has / rank it aimed at)
     bool sm_ok = false;
     int seed_model = 1;      // PN_OPT_SEED_MODEL: 1 (default) use it where it was accepted, 0 never
-    uint64_t dbscan_piece = 0;  // PN_OPT_DBSCAN_PIECE: list entries per piece of pn_dbscan_*, 0 = 2^27
+    // PN_OPT_{DBSCAN,OPTICS,KDE,MS}_PIECE: list entries per piece of pn_dbscan_* / pn_optics_* (fill) / pn_kde_* /
+    // pn_mean_shift_*, 0 = kGraphPiece (csr_pieces.h)
+    uint64_t piece[kPieceFamilies] = {};
     uint64_t mst_batch = 0;     // PN_OPT_MST_BATCH: listed rows per scan launch of pn_mst_*, 0 = 2^18
-    uint64_t optics_piece = 0;  // PN_OPT_OPTICS_PIECE: list entries per fill piece of pn_optics_*, 0 = 2^27
-    uint64_t kde_piece = 0;     // PN_OPT_KDE_PIECE: list entries per piece of pn_kde_*, 0 = 2^27
-    uint64_t ms_piece = 0;      // PN_OPT_MS_PIECE: list entries per piece of pn_mean_shift_*, 0 = 2^27
     int kmeans_filter = 0;      // PN_OPT_KMEANS_FILTER: 0 = the engine decides, 1 = the filter wherever it is eligible, 2 = never
     // state that queries on a shared `const pn_index *` update: internally synchronised by `mu`
     struct Shared {
@@ -988,6 +989,11 @@ extern "C" int pn_index_info(const pn_index *ix, pn_info *out) {
     return PN_OK;
 }
 
+static int set_piece(pn_index *ix, PieceFamily family, int64_t value, const char *bad) {
+    if (value < 0) return fail(PN_ERR_INVALID, "%s", bad);
+    ix->piece[family] = (uint64_t)value;
+    return PN_OK;
+}
 extern "C" int pn_index_set_option(pn_index *ix, int option, int64_t value) {
     if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
     std::lock_guard<std::mutex> lk(ix->sh.mu);
@@ -1030,26 +1036,14 @@ extern "C" int pn_index_set_option(pn_index *ix, int option, int64_t value) {
             if (value != 0 && value != 1) return fail(PN_ERR_INVALID, "bad seed-model switch (0 or 1)");
             ix->seed_model = (int)value;
             return PN_OK;
-        case PN_OPT_DBSCAN_PIECE:
-            if (value < 0) return fail(PN_ERR_INVALID, "bad DBSCAN piece size");
-            ix->dbscan_piece = (uint64_t)value;
-            return PN_OK;
+        case PN_OPT_DBSCAN_PIECE: return set_piece(ix, kPieceDbscan, value, "bad DBSCAN piece size");
         case PN_OPT_MST_BATCH:
             if (value < 0) return fail(PN_ERR_INVALID, "bad MST batch size");
             ix->mst_batch = (uint64_t)value;
             return PN_OK;
-        case PN_OPT_OPTICS_PIECE:
-            if (value < 0) return fail(PN_ERR_INVALID, "bad OPTICS piece size");
-            ix->optics_piece = (uint64_t)value;
-            return PN_OK;
-        case PN_OPT_KDE_PIECE:
-            if (value < 0) return fail(PN_ERR_INVALID, "bad KDE piece size");
-            ix->kde_piece = (uint64_t)value;
-            return PN_OK;
-        case PN_OPT_MS_PIECE:
-            if (value < 0) return fail(PN_ERR_INVALID, "bad mean shift piece size");
-            ix->ms_piece = (uint64_t)value;
-            return PN_OK;
+        case PN_OPT_OPTICS_PIECE: return set_piece(ix, kPieceOptics, value, "bad OPTICS piece size");
+        case PN_OPT_KDE_PIECE: return set_piece(ix, kPieceKde, value, "bad KDE piece size");
+        case PN_OPT_MS_PIECE: return set_piece(ix, kPieceMs, value, "bad mean shift piece size");
         case PN_OPT_KMEANS_FILTER:
             if (value < 0 || value > 2) return fail(PN_ERR_INVALID, "bad k-means filter choice %lld", (long long)value);
             ix->kmeans_filter = (int)value;
@@ -3111,53 +3105,60 @@ extern "C" int pn_query_radius_with_distance_f64(const pn_index *ix, const doubl
 // with_dist (pn_query_radius_with_distance_device_*): d_dist gets each written row's distance at the row's position;
 // PN_RADIUS_SORTED orders every list that ends at or below `capacity` by (distance, index) -- the list that straddles
 // the capacity is left in ascending index order, as far as it is written
+// One request to the device radius pipeline (radius_device_enqueue, radius_self_enqueue).  Its threshold is built by
+// within(r), one radius for all, or by within_each(d_radii), [nq] in HBM (the self pipeline: [n], row i's own): query q's
+// radius is then d_radii[q], `radius` is not looked at.
 template <typename T>
-static int radius_device_enqueue(const pn_index *ix, Workspace &ws, const T *d_q, size_t nq, size_t q_cols, size_t q_stride,
-                                 T radius, uint64_t *d_offsets, uint64_t *d_idx, size_t capacity, uint64_t *d_total,
-                                 hipStream_t s, T *d_dist, unsigned flags, bool count_queries = true,
-                                 const T *d_radii = nullptr, bool add_listed = false);
+struct RadiusWithin {
+    T radius;
+    const T *d_radii;
+};
 template <typename T>
-static int radius_device_impl(const pn_index *ix, const T *d_q, size_t nq, size_t q_cols, size_t q_stride, T radius,
-                              uint64_t *d_offsets, uint64_t *d_idx, size_t capacity, uint64_t *d_total, hipStream_t s,
-                              bool with_dist = false, T *d_dist = nullptr, unsigned flags = 0,
-                              const T *d_radii = nullptr) {
-    if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
-    if (ix->elem_bytes != (int)sizeof(T)) return fail(PN_ERR_INVALID, "index element type mismatch");
-    if (!d_offsets || (!d_idx && capacity)) return fail(PN_ERR_INVALID, "output buffer is NULL");
-    if (with_dist && !d_dist && capacity) return fail(PN_ERR_INVALID, "distance buffer is NULL");
-    if (flags & ~(unsigned)PN_RADIUS_SORTED) return fail(PN_ERR_INVALID, "unknown radius flags 0x%x", flags);
-    if (!capacity) d_dist = nullptr;  // (a pure count)
-    if (!d_q && q_cols && nq) return fail(PN_ERR_INVALID, "queries is NULL");
-    if (nq > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many queries in one call");
-    CallScope call(ix);
-    PNCHK(call.guard());
-    if (nq == 0) {
-        HIPCHK(hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), s));
-        if (d_total) HIPCHK(hipMemsetAsync(d_total, 0, sizeof(uint64_t), s));
-        return PN_OK;
-    }
-    PNCHK(call.on_stream(s));
-    return radius_device_enqueue<T>(ix, call.ws(), d_q, nq, q_cols, q_stride, radius, d_offsets, d_idx, capacity, d_total,
-                                    s, d_dist, flags, true, d_radii, d_radii != nullptr);
+static RadiusWithin<T> within(T radius) { return {radius, nullptr}; }
+template <typename T>
+static RadiusWithin<T> within_each(const T *d_radii) { return {(T)0, d_radii}; }
+template <typename T>
+static RadiusWithin<T> from_row(const RadiusWithin<T> &w, size_t a) {  // (the same threshold for the queries from row a on)
+    return {w.radius, w.d_radii ? w.d_radii + a : nullptr};
 }
-// the pipeline of radius_device_impl in a workspace the caller holds (also the self-queries' inner call); nq >= 1,
-// arguments checked.  count_queries: add nq to pn_stats.queries
-// d_radii (nullable, [nq] in HBM; pn_query_radii_*): query q's radius is d_radii[q], `radius` is not looked at, and
-// nothing about the radii is decided here: the first tier is entered whenever the index and the queries' shape allow it,
-// the threshold kernel flags the queries whose own radius it cannot serve, and the exact scan compares each listed query
-// with its own radius.  add_listed: the number of listed queries is added to the index's device counter of fallback
-// queries (d_stats[0]) -- by a kernel, nothing is read back; a call that enters no first tier lists nothing and adds nothing
 template <typename T>
-static int radius_device_enqueue(const pn_index *ix, Workspace &ws, const T *d_q, size_t nq, size_t q_cols, size_t q_stride,
-                                 T radius, uint64_t *d_offsets, uint64_t *d_idx, size_t capacity, uint64_t *d_total,
-                                 hipStream_t s, T *d_dist, unsigned flags, bool count_queries, const T *d_radii,
-                                 bool add_listed) {
+struct RadiusQueries {  // in HBM: nq rows of q_cols values, q_stride apart
+    const T *d_q;
+    size_t nq, q_cols, q_stride;
+};
+template <typename T>
+struct RadiusOut {  // in HBM: offsets [nq + 1]; the first `capacity` entries of the lists (0: a pure count, no buffers);
+    uint64_t *d_offsets, *d_idx;  // d_dist (nullable): their distances; d_total (nullable): [1] = d_offsets[nq]
+    T *d_dist;
+    size_t capacity;
+    uint64_t *d_total;
+};
+template <typename T>
+struct RadiusCall {
+    RadiusQueries<T> q;  // (radius_self_enqueue does not look: its queries are the index's rows)
+    RadiusWithin<T> within;
+    RadiusOut<T> out;
+    unsigned flags = 0;         // PN_RADIUS_SORTED; radius_self_enqueue: PN_SELF_INCLUDE too
+    bool count_queries = true;  // pn_stats.queries += nq
+    bool add_listed = false;    // pn_stats.fallback_queries += the queries the first tier lists for the exact scan (by a kernel,
+                                // into d_stats[0]).  radius_self_enqueue: where it counts and has one radius per row, instead
+};
+// the pipeline of radius_device_impl (below) in a workspace the caller holds (also the self-queries' inner call);
+// nq >= 1, arguments checked.  With one radius per query (pn_query_radii_*) nothing about the radii is decided here: the
+// first tier is entered whenever the index and the queries' shape allow it, the threshold kernel flags the queries whose
+// own radius it cannot serve, and the exact scan compares each listed query with its own radius.
+template <typename T>
+static int radius_device_enqueue(const pn_index *ix, Workspace &ws, const RadiusCall<T> &call, hipStream_t s) {
+    const T *d_q = call.q.d_q, *d_radii = call.within.d_radii, radius = call.within.radius;
+    const size_t nq = call.q.nq, q_cols = call.q.q_cols, q_stride = call.q.q_stride, capacity = call.out.capacity;
+    uint64_t *d_offsets = call.out.d_offsets, *d_idx = call.out.d_idx, *d_total = call.out.d_total;
+    T *d_dist = call.out.d_dist;
     int level;
     {
         std::lock_guard<std::mutex> lk(ix->sh.mu);
         recs_collect(ix, false);
         level = ix->sh.bf16_level;
-        if (count_queries) ix->sh.stats.queries += nq;
+        if (call.count_queries) ix->sh.stats.queries += nq;
     }
     const size_t dim_eff = q_cols < ix->dim ? q_cols : ix->dim;
     const size_t nq_pad = round_up(nq, (size_t)256);
@@ -3192,7 +3193,7 @@ static int radius_device_enqueue(const pn_index *ix, Workspace &ws, const T *d_q
         d_pos = (const uint32_t *)ws.w_rpos.p;
         d_nsel = d_misc + 4;
         d_nkept = (const uint32_t *)ws.w_flags.p;
-        if (add_listed && ix->d_stats) HIPCHK(launch_radii_add_listed(d_nsel, ix->d_stats, s));
+        if (call.add_listed && ix->d_stats) HIPCHK(launch_radii_add_listed(d_nsel, ix->d_stats, s));
     }
     // ---- exact two-pass scan for the listed queries (all of them without a first tier), driven by the device-side list
     const size_t q_tiles_r = round_up(nq, (size_t)kTileQ) / kTileQ;
@@ -3220,21 +3221,46 @@ static int radius_device_enqueue(const pn_index *ix, Workspace &ws, const T *d_q
                                             ix->index_base, d_idx, (uint64_t)capacity, s,
                                             d_dist ? (const T *)ws.w_rkd.p + nq * kept_stride : nullptr, d_dist,
                                             (int)sizeof(T)));
-        if (d_dist && (flags & PN_RADIUS_SORTED))
+        if (d_dist && (call.flags & PN_RADIUS_SORTED))
             PNCHK(csr_sort_dev<T>(ix, ws, d_offsets, nq, d_idx, d_dist, (uint64_t)capacity, s));
     }
     return PN_OK;
 }
+template <typename T>
+static int radius_device_impl(const pn_index *ix, const T *d_q, size_t nq, size_t q_cols, size_t q_stride,
+                              RadiusWithin<T> within, uint64_t *d_offsets, uint64_t *d_idx, size_t capacity,
+                              uint64_t *d_total, hipStream_t s, bool with_dist = false, T *d_dist = nullptr,
+                              unsigned flags = 0) {
+    if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
+    if (ix->elem_bytes != (int)sizeof(T)) return fail(PN_ERR_INVALID, "index element type mismatch");
+    if (!d_offsets || (!d_idx && capacity)) return fail(PN_ERR_INVALID, "output buffer is NULL");
+    if (with_dist && !d_dist && capacity) return fail(PN_ERR_INVALID, "distance buffer is NULL");
+    if (flags & ~(unsigned)PN_RADIUS_SORTED) return fail(PN_ERR_INVALID, "unknown radius flags 0x%x", flags);
+    if (!capacity) d_dist = nullptr;  // (a pure count)
+    if (!d_q && q_cols && nq) return fail(PN_ERR_INVALID, "queries is NULL");
+    if (nq > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many queries in one call");
+    CallScope call(ix);
+    PNCHK(call.guard());
+    if (nq == 0) {
+        HIPCHK(hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), s));
+        if (d_total) HIPCHK(hipMemsetAsync(d_total, 0, sizeof(uint64_t), s));
+        return PN_OK;
+    }
+    PNCHK(call.on_stream(s));
+    RadiusCall<T> c{{d_q, nq, q_cols, q_stride}, within, {d_offsets, d_idx, d_dist, capacity, d_total}, flags};
+    c.add_listed = within.d_radii != nullptr;  // (pn_query_radii_device_*: the listed queries count as fallback queries)
+    return radius_device_enqueue<T>(ix, call.ws(), c, s);
+}
 extern "C" int pn_query_radius_device_f32(const pn_index *ix, const float *d_q, size_t nq, size_t q_cols, size_t q_stride,
                                           float radius, uint64_t *d_offsets, uint64_t *d_idx, size_t capacity,
                                           uint64_t *d_total, void *stream) {
-    return radius_device_impl<float>(ix, d_q, nq, q_cols, q_stride, radius, d_offsets, d_idx, capacity, d_total,
+    return radius_device_impl<float>(ix, d_q, nq, q_cols, q_stride, within(radius), d_offsets, d_idx, capacity, d_total,
                                      (hipStream_t)stream);
 }
 extern "C" int pn_query_radius_device_f64(const pn_index *ix, const double *d_q, size_t nq, size_t q_cols, size_t q_stride,
                                           double radius, uint64_t *d_offsets, uint64_t *d_idx, size_t capacity,
                                           uint64_t *d_total, void *stream) {
-    return radius_device_impl<double>(ix, d_q, nq, q_cols, q_stride, radius, d_offsets, d_idx, capacity, d_total,
+    return radius_device_impl<double>(ix, d_q, nq, q_cols, q_stride, within(radius), d_offsets, d_idx, capacity, d_total,
                                       (hipStream_t)stream);
 }
 // argument checks of the device entry points with distances, before any device is touched
@@ -3249,7 +3275,7 @@ extern "C" int pn_query_radius_with_distance_device_f32(const pn_index *ix, cons
                                                         uint64_t *d_idx, float *d_dist, size_t capacity, uint64_t *d_total,
                                                         void *stream) {
     PNCHK(radius_wd_device_args(d_offsets, d_idx, d_dist, capacity, flags));
-    return radius_device_impl<float>(ix, d_q, nq, q_cols, q_stride, radius, d_offsets, d_idx, capacity, d_total,
+    return radius_device_impl<float>(ix, d_q, nq, q_cols, q_stride, within(radius), d_offsets, d_idx, capacity, d_total,
                                      (hipStream_t)stream, true, d_dist, flags);
 }
 extern "C" int pn_query_radius_with_distance_device_f64(const pn_index *ix, const double *d_q, size_t nq, size_t q_cols,
@@ -3257,7 +3283,7 @@ extern "C" int pn_query_radius_with_distance_device_f64(const pn_index *ix, cons
                                                         uint64_t *d_idx, double *d_dist, size_t capacity, uint64_t *d_total,
                                                         void *stream) {
     PNCHK(radius_wd_device_args(d_offsets, d_idx, d_dist, capacity, flags));
-    return radius_device_impl<double>(ix, d_q, nq, q_cols, q_stride, radius, d_offsets, d_idx, capacity, d_total,
+    return radius_device_impl<double>(ix, d_q, nq, q_cols, q_stride, within(radius), d_offsets, d_idx, capacity, d_total,
                                       (hipStream_t)stream, true, d_dist, flags);
 }
 
@@ -3362,12 +3388,12 @@ extern "C" int pn_query_self_device_f64(const pn_index *ix, size_t k, unsigned f
 // pn_query_radius_with_distance_device_* unchanged.  PN_SELF_INCLUDE: the same without the exclusion.  The workspace
 // word w_sf_bad counts disagreements between a self flag and the pipeline's list (self_graph.hip; never expected).
 template <typename T>
-static int radius_self_enqueue(const pn_index *ix, Workspace &ws, T radius, unsigned flags, uint64_t *d_offsets,
-                               uint64_t *d_idx, T *d_dist, size_t capacity, uint64_t *d_total, hipStream_t s,
-                               bool count_queries, const T *d_radii = nullptr) {  // (d_radii: [n] in HBM, row i's own radius)
-    const size_t n = ix->n;
-    const bool exclude = !(flags & PN_SELF_INCLUDE);
-    if (!capacity) d_dist = nullptr;  // (a pure count)
+static int radius_self_enqueue(const pn_index *ix, Workspace &ws, const RadiusCall<T> &call, hipStream_t s) {
+    const size_t n = ix->n, capacity = call.out.capacity;
+    const T radius = call.within.radius;
+    uint64_t *d_offsets = call.out.d_offsets, *d_idx = call.out.d_idx, *d_total = call.out.d_total;
+    const bool exclude = !(call.flags & PN_SELF_INCLUDE);
+    T *d_dist = capacity ? call.out.d_dist : nullptr;  // (no capacity: a pure count)
     const size_t chunk = n < kSelfChunk ? n : kSelfChunk;
     // inner capacity per chunk: capacity + chunk, never beyond the chunk x n entries its lists can hold
     size_t in_cap = 0;
@@ -3398,9 +3424,11 @@ static int radius_self_enqueue(const pn_index *ix, Workspace &ws, T radius, unsi
     for (size_t r0 = 0; r0 < n; r0 += chunk) {
         const size_t nqc = n - r0 < chunk ? n - r0 : chunk;
         const T *rows = (const T *)ix->d_pts + r0 * ix->ld;
-        const T *rad = d_radii ? d_radii + r0 : nullptr;  // (the chunk's rows' radii)
-        PNCHK(radius_device_enqueue<T>(ix, ws, rows, nqc, ix->dim, ix->ld, radius, in_off, in_idx, in_cap, nullptr, s,
-                                       in_dist, 0, count_queries, rad, rad && count_queries));
+        RadiusCall<T> inner{{rows, nqc, ix->dim, ix->ld}, from_row(call.within, r0), {in_off, in_idx, in_dist, in_cap, nullptr}};
+        const T *rad = inner.within.d_radii;  // (the chunk's rows' radii)
+        inner.count_queries = call.count_queries;
+        inner.add_listed = rad && call.count_queries;
+        PNCHK(radius_device_enqueue<T>(ix, ws, inner, s));
         const T *cn = cn_all ? cn_all + r0 : nullptr;
         HIPCHK(launch_radius_self_counts<T>(rows, nqc, (int)ix->dim, ix->ld, cn, radius, exclude, in_off, flag, cnt, bad, s,
                                             rad));
@@ -3411,7 +3439,7 @@ static int radius_self_enqueue(const pn_index *ix, Workspace &ws, T radius, unsi
                                              d_idx, d_dist, capacity, bad, s));
     }
     if (d_total) HIPCHK(hipMemcpyAsync(d_total, d_offsets + n, sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
-    if (capacity && d_dist && (flags & PN_RADIUS_SORTED))
+    if (capacity && d_dist && (call.flags & PN_RADIUS_SORTED))
         PNCHK(csr_sort_dev<T>(ix, ws, d_offsets, n, d_idx, d_dist, (uint64_t)capacity, s));
     return PN_OK;
 }
@@ -3423,15 +3451,45 @@ static int radius_self_args(const pn_index *ix, unsigned flags, bool has_offsets
     return self_args(ix, flags, PN_RADIUS_SORTED | PN_SELF_INCLUDE, elem_bytes);
 }
 template <typename T>
-static int radius_self_device(const pn_index *ix, T radius, unsigned flags, uint64_t *d_offsets, uint64_t *d_idx, T *d_dist,
-                              size_t capacity, uint64_t *d_total, hipStream_t s, const T *d_radii = nullptr) {
+static int radius_self_device(const pn_index *ix, RadiusWithin<T> within, unsigned flags, uint64_t *d_offsets, uint64_t *d_idx,
+                              T *d_dist, size_t capacity, uint64_t *d_total, hipStream_t s) {
     // (capacity 0 only counts: no list buffers needed)
     PNCHK(radius_self_args(ix, flags, d_offsets != nullptr, d_idx != nullptr || !capacity, d_dist != nullptr || !capacity,
                            (int)sizeof(T)));
     if (ix->n > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many rows for one self-query");
     CallScope call(ix);
     PNCHK(call.on_stream(s));
-    return radius_self_enqueue<T>(ix, call.ws(), radius, flags, d_offsets, d_idx, d_dist, capacity, d_total, s, true, d_radii);
+    const RadiusCall<T> c{{}, within, {d_offsets, d_idx, d_dist, capacity, d_total}, flags};
+    return radius_self_enqueue<T>(ix, call.ws(), c, s);
+}
+// A CSR staged in the workspace (offsets [n + 1] at d_off; `total` entries in w_hidx, and in w_hdist where distances are
+// wanted) goes down to the host: the offsets into the caller's array, the lists into arrays allocated here (pn_free; an
+// empty result is a 1-element allocation).  Waits for the stream.  what: whose lists, for the message of a failed copy.
+template <typename T>
+static int csr_to_host(const pn_index *ix, Workspace &ws, const uint64_t *d_off, size_t n, uint64_t total, uint64_t *offsets,
+                       uint64_t **idx_out, T **dist_out, const char *what, hipStream_t s) {
+    uint64_t *out = (uint64_t *)malloc((total ? total : 1) * sizeof(uint64_t));
+    T *dout = dist_out ? (T *)malloc((total ? total : 1) * sizeof(T)) : nullptr;
+    if (!out || (dist_out && !dout)) {
+        free(out);
+        free(dout);
+        (void)hipStreamSynchronize(s);
+        return fail(PN_ERR_NOMEM, "malloc(%llu results) failed", (unsigned long long)total);
+    }
+    hipError_t e = hipMemcpyAsync(offsets, d_off, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && total) e = hipMemcpyAsync(out, ws.w_hidx.p, total * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && total && dout) e = hipMemcpyAsync(dout, ws.w_hdist.p, total * sizeof(T), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        free(out);
+        free(dout);
+        return fail(PN_ERR_DEVICE, "copying %s lists back: %s", what, hipGetErrorString(e));
+    }
+    *idx_out = out;
+    if (dist_out) *dist_out = dout;
+    std::lock_guard<std::mutex> lk(ix->sh.mu);
+    ix->sh.stats.radius_results += total;
+    return PN_OK;
 }
 // host outputs: a count-only pass, then one pass with the exact total into the workspace's staging buffers; the lists are
 // then allocated here (pn_free).  Both passes run the pipeline (the count is not kept between calls).
@@ -3460,21 +3518,22 @@ static int radius_self_host(const pn_index *ix, T radius, unsigned flags, uint64
     };
     uint64_t total = 0;
     uint32_t bad = 0;
-    const T *d_radii = nullptr;
+    RadiusCall<T> c{{}, within(radius), {d_off, nullptr, nullptr, 0, d_tot}, flags};  // (the counting pass counts the rows)
     if (per_row) {
         PNCHK(ws.w_hrad.ensure(n * sizeof(T)));
         HIPCHK(hipMemcpyAsync(ws.w_hrad.p, radii, n * sizeof(T), hipMemcpyHostToDevice, s));
-        d_radii = (const T *)ws.w_hrad.p;
+        c.within = within_each((const T *)ws.w_hrad.p);
     }
-    PNCHK(radius_self_enqueue<T>(ix, ws, radius, flags, d_off, nullptr, nullptr, 0, d_tot, s, true, d_radii));
+    PNCHK(radius_self_enqueue<T>(ix, ws, c, s));
     HIPCHK(hipMemcpyAsync(&total, d_tot, sizeof total, hipMemcpyDeviceToHost, s));
     PNCHK(bad_word(&bad));
     HIPCHK(hipStreamSynchronize(s));
     if (total) {
         PNCHK(ws.w_hidx.ensure(total * sizeof(uint64_t)));
         if (dist_out) PNCHK(ws.w_hdist.ensure(total * sizeof(T)));
-        PNCHK(radius_self_enqueue<T>(ix, ws, radius, flags, d_off, (uint64_t *)ws.w_hidx.p,
-                                     dist_out ? (T *)ws.w_hdist.p : nullptr, total, nullptr, s, false, d_radii));
+        c.out = {d_off, (uint64_t *)ws.w_hidx.p, dist_out ? (T *)ws.w_hdist.p : nullptr, total, nullptr};
+        c.count_queries = false;
+        PNCHK(radius_self_enqueue<T>(ix, ws, c, s));
         uint32_t bad2 = 0;
         PNCHK(bad_word(&bad2));
         HIPCHK(hipStreamSynchronize(s));
@@ -3482,28 +3541,7 @@ static int radius_self_host(const pn_index *ix, T radius, unsigned flags, uint64
     }
     if (bad)
         return fail(PN_ERR_DEVICE, "self-query: %u self flags disagree with the radius lists (internal error)", bad);
-    uint64_t *out = (uint64_t *)malloc((total ? total : 1) * sizeof(uint64_t));
-    T *dout = dist_out ? (T *)malloc((total ? total : 1) * sizeof(T)) : nullptr;
-    if (!out || (dist_out && !dout)) {
-        free(out);
-        free(dout);
-        (void)hipStreamSynchronize(s);
-        return fail(PN_ERR_NOMEM, "malloc(%llu results) failed", (unsigned long long)total);
-    }
-    hipError_t e = hipMemcpyAsync(offsets, d_off, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && total) e = hipMemcpyAsync(out, ws.w_hidx.p, total * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && total && dout) e = hipMemcpyAsync(dout, ws.w_hdist.p, total * sizeof(T), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-        free(out);
-        free(dout);
-        return fail(PN_ERR_DEVICE, "copying the self-query's lists back: %s", hipGetErrorString(e));
-    }
-    *idx_out = out;
-    if (dist_out) *dist_out = dout;
-    std::lock_guard<std::mutex> lk(ix->sh.mu);
-    ix->sh.stats.radius_results += total;
-    return PN_OK;
+    return csr_to_host<T>(ix, ws, d_off, n, total, offsets, idx_out, dist_out, "the self-query's", s);
 }
 extern "C" int pn_query_radius_self_f32(const pn_index *ix, float radius, unsigned flags, uint64_t *offsets,
                                         uint64_t **idx_out, float **dist_out) {
@@ -3516,27 +3554,82 @@ extern "C" int pn_query_radius_self_f64(const pn_index *ix, double radius, unsig
 extern "C" int pn_query_radius_self_device_f32(const pn_index *ix, float radius, unsigned flags, uint64_t *d_offsets,
                                                uint64_t *d_idx, float *d_dist, size_t capacity, uint64_t *d_total,
                                                void *stream) {
-    return radius_self_device<float>(ix, radius, flags, d_offsets, d_idx, d_dist, capacity, d_total, (hipStream_t)stream);
+    return radius_self_device<float>(ix, within(radius), flags, d_offsets, d_idx, d_dist, capacity, d_total, (hipStream_t)stream);
 }
 extern "C" int pn_query_radius_self_device_f64(const pn_index *ix, double radius, unsigned flags, uint64_t *d_offsets,
                                                uint64_t *d_idx, double *d_dist, size_t capacity, uint64_t *d_total,
                                                void *stream) {
-    return radius_self_device<double>(ix, radius, flags, d_offsets, d_idx, d_dist, capacity, d_total, (hipStream_t)stream);
+    return radius_self_device<double>(ix, within(radius), flags, d_offsets, d_idx, d_dist, capacity, d_total, (hipStream_t)stream);
 }
+
+// The piece walk of DBSCAN, OPTICS, KDE and mean shift.  Each counts its radius lists first (capacity 0) and reads the
+// offsets back into h_off, with whatever else its read-back carries.  walk() cuts the counted CSR (csr_piece_end,
+// csr_pieces.h: at most 2^18 rows and E = PN_OPT_*_PIECE entries, a longer single row is a piece of its own) and per
+// piece has radius_device_enqueue write the rows' lists into scratch, where the consumer's kernel reads them.
+template <typename T>
+struct Piece {  // rows [a, b) of the walk; their lists, `total` entries, as a CSR of its own in scratch of `capacity` entries
+    size_t a, b;
+    uint64_t total, capacity;
+    uint64_t *in_off, *in_idx;  // (total == 0: nothing was asked for, all three are nullptr)
+    T *in_dist;                 // (nullptr unless kPieceDist)
+};
+// what a walk needs: the entries' distances too | scratch of total + rows entries (the count left the rows themselves
+// out, the lists hold them) | the pieces without entries handed to the consumer as well
+enum : unsigned { kPieceDist = 1, kPieceSelfRoom = 2, kPieceEmptyToo = 4 };
+template <typename T>
+struct PieceWalk {
+    const pn_index *ix;
+    Workspace &ws;
+    PieceFamily family;
+    hipStream_t s;
+    std::vector<uint64_t> h_off;  // the counted offsets on the host: the family reads them back into it after host(n)
+    int host(size_t n) {          // (room for the offsets of n rows, the most a walk of this call will have)
+        try {
+            h_off.resize(n + 1);
+        } catch (const std::bad_alloc &) {
+            return fail(PN_ERR_NOMEM, "host allocation of %zu offsets failed", n + 1);
+        }
+        return PN_OK;
+    }
+    // the offsets of one piece on the device (walk() sees to it; mean shift, which walks once per iteration, up front)
+    int scratch() { return ws.w_sf_off.ensure((std::min(h_off.size() - 1, kSelfChunk) + 1) * sizeof(uint64_t)); }
+    // rows: the counted rows, within: their threshold, needs: kPiece*; consume(const Piece<T> &) -> int enqueues the reader
+    template <typename F>
+    int walk(const RadiusQueries<T> &rows, const RadiusWithin<T> &within, unsigned needs, F &&consume) {
+        const uint64_t E = ix->piece[family] ? ix->piece[family] : kGraphPiece;
+        PNCHK(scratch());
+        for (size_t a = 0, b; a < rows.nq; a = b) {
+            b = csr_piece_end(h_off.data(), a, rows.nq, kSelfChunk, E);
+            const uint64_t total = h_off[b] - h_off[a], cap = total + (needs & kPieceSelfRoom ? b - a : 0);
+            Piece<T> p{a, b, total, cap, nullptr, nullptr, nullptr};
+            if (total) {
+                PNCHK(ws.w_sf_idx.ensure(cap * sizeof(uint64_t)));
+                if (needs & kPieceDist) PNCHK(ws.w_sf_dist.ensure(cap * sizeof(T)));
+                p.in_off = (uint64_t *)ws.w_sf_off.p;
+                p.in_idx = (uint64_t *)ws.w_sf_idx.p;
+                p.in_dist = needs & kPieceDist ? (T *)ws.w_sf_dist.p : nullptr;
+                RadiusCall<T> c{{rows.d_q + a * rows.q_stride, b - a, rows.q_cols, rows.q_stride}, from_row(within, a),
+                                {p.in_off, p.in_idx, p.in_dist, (size_t)p.capacity, nullptr}};
+                c.count_queries = false;  // (the counting pass counted them, and added the listed ones where they count)
+                PNCHK(radius_device_enqueue<T>(ix, ws, c, s));
+            }
+            if (p.total || (needs & kPieceEmptyToo)) PNCHK(consume(p));
+        }
+        return PN_OK;
+    }
+};
 
 // ---------------------------------------------------------------------------
 // DBSCAN: pn_dbscan_{,device_}{f32,f64} (the kernels and the argument for schedule independence: components.hip).
 //   1. count: radius_self_enqueue with capacity 0 and PN_SELF_INCLUDE gives the offsets of the eps-graph, no lists.  From
 //      them: core[], parent[i] = i and the lengths of the non-core rows' side lists, scanned on the device.  The offsets
 //      and the side lists' total are read back -- the one host wait of a call -- to cut the pieces and size the side lists.
-//   2. union: a piece is a contiguous row range of at most 2^18 rows whose lists hold at most E entries together
-//      (PN_OPT_DBSCAN_PIECE, default 2^27; a longer single row is a piece of its own).  radius_device_enqueue writes the
-//      piece's lists into workspace scratch of exactly the piece's total, the union kernel reads them there.
+//   2. union: piece by piece (PieceWalk above, E = PN_OPT_DBSCAN_PIECE).  radius_device_enqueue writes the piece's
+//      lists into workspace scratch of exactly the piece's total, the union kernel reads them there.
 //   3. finish: flatten, flag and scan the core roots into cluster numbers, label.
 // Device memory beyond a 2^18-query batch's workspace: 37 bytes per row, 8 bytes per entry of the largest piece and 4
 // bytes per entry of the non-core rows' lists (< n (min_samples - 1) entries) -- never the graph.
 // ---------------------------------------------------------------------------
-constexpr uint64_t kDbscanPiece = (uint64_t)1 << 27;
 static int dbscan_args(const pn_index *ix, unsigned flags, size_t min_samples, const void *labels, int elem_bytes) {
     if (flags) return fail(PN_ERR_INVALID, "unknown DBSCAN flags 0x%x", flags);
     if (min_samples == 0) return fail(PN_ERR_INVALID, "min_samples must be at least 1");
@@ -3563,40 +3656,23 @@ static int dbscan_enqueue(const pn_index *ix, Workspace &ws, T eps, size_t min_s
     uint32_t *parent = (uint32_t *)(scan + scan_words), *word = parent + n, *root = word + n;
     uint8_t *core = (uint8_t *)(root + n);
     // ---- 1. count
-    PNCHK(radius_self_enqueue<T>(ix, ws, eps, PN_SELF_INCLUDE, off, nullptr, nullptr, 0, nullptr, s, true));
+    const RadiusCall<T> count{{}, within(eps), {off, nullptr, nullptr, 0, nullptr}, PN_SELF_INCLUDE};
+    PNCHK(radius_self_enqueue<T>(ix, ws, count, s));
     HIPCHK(launch_dbscan_init(off, n, (uint64_t)min_samples, core, parent, word, s));  // word = side list lengths
     HIPCHK(launch_exclusive_scan_u32(word, n, side_off, scan, nullptr, s));
-    std::vector<uint64_t> h_off;
-    try {
-        h_off.resize(n + 1);
-    } catch (const std::bad_alloc &) {
-        return fail(PN_ERR_NOMEM, "host allocation of %zu offsets failed", n + 1);
-    }
+    PieceWalk<T> pieces{ix, ws, kPieceDbscan, s};
     uint64_t side_total = 0;
-    HIPCHK(hipMemcpyAsync(h_off.data(), off, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    PNCHK(pieces.host(n));
+    HIPCHK(hipMemcpyAsync(pieces.h_off.data(), off, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(&side_total, side_off + n, sizeof side_total, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     PNCHK(ws.w_db_side.ensure((side_total ? side_total : 1) * sizeof(uint32_t)));
     uint32_t *side = (uint32_t *)ws.w_db_side.p;
     // ---- 2. union, piece by piece
-    const uint64_t E = ix->dbscan_piece ? ix->dbscan_piece : kDbscanPiece;
-    PNCHK(ws.w_sf_off.ensure((std::min(n, kSelfChunk) + 1) * sizeof(uint64_t)));
-    uint64_t *in_off = (uint64_t *)ws.w_sf_off.p;
-    for (size_t a = 0; a < n;) {
-        const size_t lim = n - a < kSelfChunk ? n : a + kSelfChunk;
-        // the last b in (a, lim] with off[b] - off[a] <= E, at least a + 1
-        size_t b = (size_t)(std::upper_bound(h_off.begin() + a + 1, h_off.begin() + lim + 1, h_off[a] + E) - h_off.begin()) - 1;
-        if (b <= a) b = a + 1;
-        const uint64_t total = h_off[b] - h_off[a];
-        if (total) {
-            PNCHK(ws.w_sf_idx.ensure(total * sizeof(uint64_t)));
-            uint64_t *in_idx = (uint64_t *)ws.w_sf_idx.p;
-            PNCHK(radius_device_enqueue<T>(ix, ws, (const T *)ix->d_pts + a * ix->ld, b - a, ix->dim, ix->ld, eps, in_off, in_idx,
-                                           (size_t)total, nullptr, s, nullptr, 0, false));
-            HIPCHK(launch_dbscan_union(in_off, in_idx, total, b - a, a, n, ix->index_base, core, parent, side_off, side, s));
-        }
-        a = b;
-    }
+    PNCHK(pieces.walk({(const T *)ix->d_pts, n, ix->dim, ix->ld}, within(eps), 0, [&](const Piece<T> &p) -> int {
+        HIPCHK(launch_dbscan_union(p.in_off, p.in_idx, p.total, p.b - p.a, p.a, n, ix->index_base, core, parent, side_off, side, s));
+        return PN_OK;
+    }));
     // ---- 3. finish
     HIPCHK(launch_dbscan_flatten(parent, core, n, root, word, s));  // word = root flags
     HIPCHK(launch_exclusive_scan_u32(word, n, num, scan, d_ncl, s));
@@ -3656,15 +3732,13 @@ extern "C" int pn_dbscan_device_f64(const pn_index *ix, double eps, size_t min_s
 //      per-row radii (max_eps for a defined core, 0 otherwise: a row that never relaxes anything stores no list).
 //   2. count: radius_self_enqueue with capacity 0 and those radii gives the graph's offsets.  They are read back -- the one
 //      host wait of a call -- to size the graph store and cut the pieces.
-//   3. fill: a piece is a contiguous row range of at most 2^18 rows whose lists hold at most E entries together
-//      (PN_OPT_OPTICS_PIECE, default 2^27; a longer single row is a piece of its own).  radius_device_enqueue writes the
-//      piece's lists (the rows themselves among them) into workspace scratch; the repack kernel drops each row from its own
-//      list and stores 32-bit ids and distances at the final offsets.
+//   3. fill: piece by piece (PieceWalk above, E = PN_OPT_OPTICS_PIECE).  radius_device_enqueue writes the piece's lists
+//      (the rows themselves among them) into workspace scratch; the repack kernel drops each row from its own list and
+//      stores 32-bit ids and distances at the final offsets.
 //   4. order: one launch of one workgroup.
 // Device memory beyond a 2^18-query batch's workspace: E * (4 + sizeof T) + 8 (n + 1) bytes for the graph, (8 + sizeof T)
 // bytes per entry of the largest piece, about 4.1 * sizeof T bytes per row for radii, cores and the tree.
 // ---------------------------------------------------------------------------
-constexpr uint64_t kOpticsPiece = (uint64_t)1 << 27;
 static int optics_args(const pn_index *ix, size_t min_samples, unsigned flags, const void *ordering, const void *reach,
                        int elem_bytes) {
     if (flags) return fail(PN_ERR_INVALID, "unknown OPTICS flags 0x%x", flags);
@@ -3707,17 +3781,15 @@ static int optics_enqueue(const pn_index *ix, Workspace &ws, size_t min_samples,
     }
     // ---- 2. count (max_eps <= 0 or NaN, or a single row: every list is empty by definition)
     uint64_t total = 0;
-    std::vector<uint64_t> h_off;
+    PieceWalk<T> pieces{ix, ws, kPieceOptics, s};
     if (n >= 2 && max_eps > (T)0) {
-        PNCHK(radius_self_enqueue<T>(ix, ws, max_eps, 0, off, nullptr, nullptr, 0, nullptr, s, false, radii));
-        try {
-            h_off.resize(n + 1);
-        } catch (const std::bad_alloc &) {
-            return fail(PN_ERR_NOMEM, "host allocation of %zu offsets failed", n + 1);
-        }
-        HIPCHK(hipMemcpyAsync(h_off.data(), off, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        RadiusCall<T> count{{}, within_each<T>(radii), {off, nullptr, nullptr, 0, nullptr}};
+        count.count_queries = false;  // (the self-query of step 1 counted the rows)
+        PNCHK(radius_self_enqueue<T>(ix, ws, count, s));
+        PNCHK(pieces.host(n));
+        HIPCHK(hipMemcpyAsync(pieces.h_off.data(), off, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
-        total = h_off[n];
+        total = pieces.h_off[n];
     } else {
         HIPCHK(hipMemsetAsync(off, 0, (n + 1) * sizeof(uint64_t), s));
     }
@@ -3729,29 +3801,13 @@ static int optics_enqueue(const pn_index *ix, Workspace &ws, size_t min_samples,
                     graph_bytes, (unsigned long long)total);
     uint32_t *ids = (uint32_t *)ws.w_opt_graph.p;
     T *dist = (T *)((char *)ws.w_opt_graph.p + ids_bytes);
-    if (total) {
-        const uint64_t E = ix->optics_piece ? ix->optics_piece : kOpticsPiece;
-        PNCHK(ws.w_sf_off.ensure((std::min(n, kSelfChunk) + 1) * sizeof(uint64_t)));
-        uint64_t *in_off = (uint64_t *)ws.w_sf_off.p;
-        for (size_t a = 0; a < n;) {
-            const size_t lim = n - a < kSelfChunk ? n : a + kSelfChunk;
-            // the last b in (a, lim] with off[b] - off[a] <= E, at least a + 1
-            size_t b = (size_t)(std::upper_bound(h_off.begin() + a + 1, h_off.begin() + lim + 1, h_off[a] + E) - h_off.begin()) - 1;
-            if (b <= a) b = a + 1;
-            const uint64_t piece = h_off[b] - h_off[a];
-            if (piece) {
-                const uint64_t in_cap = piece + (b - a);  // (each row may list itself)
-                PNCHK(ws.w_sf_idx.ensure(in_cap * sizeof(uint64_t)));
-                PNCHK(ws.w_sf_dist.ensure(in_cap * sizeof(T)));
-                uint64_t *in_idx = (uint64_t *)ws.w_sf_idx.p;
-                T *in_dist = (T *)ws.w_sf_dist.p;
-                PNCHK(radius_device_enqueue<T>(ix, ws, (const T *)ix->d_pts + a * ix->ld, b - a, ix->dim, ix->ld, max_eps, in_off,
-                                               in_idx, (size_t)in_cap, nullptr, s, in_dist, 0, false, radii + a, false));
-                HIPCHK(launch_optics_repack<T>(in_off, in_idx, in_dist, in_cap, b - a, a, ix->index_base, off, ids, dist, s));
-            }
-            a = b;
-        }
-    }
+    if (total)  // (kPieceSelfRoom: each row may list itself)
+        PNCHK(pieces.walk({(const T *)ix->d_pts, n, ix->dim, ix->ld}, within_each<T>(radii), kPieceDist | kPieceSelfRoom,
+                          [&](const Piece<T> &p) -> int {
+                              HIPCHK(launch_optics_repack<T>(p.in_off, p.in_idx, p.in_dist, p.capacity, p.b - p.a, p.a,
+                                                             ix->index_base, off, ids, dist, s));
+                              return PN_OK;
+                          }));
     // ---- 4. the ordering
     HIPCHK(launch_optics_order<T>(n, off, ids, dist, total, d_core, tree, d_ordering, d_reach, d_pred, s));
     return PN_OK;
@@ -4376,8 +4432,8 @@ static int radii_device(const pn_index *ix, const T *d_q, size_t nq, size_t q_co
                         hipStream_t s) {
     PNCHK(radii_args(ix, flags, PN_RADIUS_SORTED, d_offsets != nullptr, d_idx != nullptr || !capacity,
                      d_dist != nullptr || !capacity, d_radii != nullptr || !nq, (int)sizeof(T)));
-    return radius_device_impl<T>(ix, d_q, nq, q_cols, q_stride, (T)0, d_offsets, d_idx, capacity, d_total, s, false, d_dist,
-                                 flags, d_radii);
+    return radius_device_impl<T>(ix, d_q, nq, q_cols, q_stride, within_each(d_radii), d_offsets, d_idx, capacity, d_total, s,
+                                 false, d_dist, flags);
 }
 // host outputs, as radius_self_host: queries and radii up, a count-only pass, one pass with the exact total into the
 // workspace's staging buffers, lists down into arrays allocated here (pn_free)
@@ -4400,50 +4456,30 @@ static int radii_host(const pn_index *ix, const T *q, size_t nq, size_t q_cols, 
     PNCHK(ws.w_hrad.ensure(nq * sizeof(T)));
     HIPCHK(hipMemcpyAsync(ws.w_hrad.p, radii, nq * sizeof(T), hipMemcpyHostToDevice, s));
     PNCHK(ws.w_sf_hoff.ensure((nq + 2) * sizeof(uint64_t)));
-    const T *d_q = (const T *)ws.w_hq.p, *d_radii = (const T *)ws.w_hrad.p;
-    const size_t ldq = q_cols ? q_cols : 1;
     uint64_t *d_off = (uint64_t *)ws.w_sf_hoff.p, *d_tot = d_off + nq + 1;
     uint64_t total = 0;
-    // (pn_stats.queries is left alone, as by pn_query_radius_*; the listed queries are added once, by the counting pass)
-    PNCHK(radius_device_enqueue<T>(ix, ws, d_q, nq, q_cols, ldq, (T)0, d_off, nullptr, 0, d_tot, s, nullptr, flags, false,
-                                   d_radii, true));
+    RadiusCall<T> c{{(const T *)ws.w_hq.p, nq, q_cols, q_cols ? q_cols : 1}, within_each((const T *)ws.w_hrad.p),
+                    {d_off, nullptr, nullptr, 0, d_tot}, flags};
+    c.count_queries = false;  // (pn_stats.queries is left alone, as by pn_query_radius_*)
+    c.add_listed = true;      // (once, by the counting pass)
+    PNCHK(radius_device_enqueue<T>(ix, ws, c, s));
     HIPCHK(hipMemcpyAsync(&total, d_tot, sizeof total, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (total) {
         PNCHK(ws.w_hidx.ensure(total * sizeof(uint64_t)));
         if (dist_out) PNCHK(ws.w_hdist.ensure(total * sizeof(T)));
-        PNCHK(radius_device_enqueue<T>(ix, ws, d_q, nq, q_cols, ldq, (T)0, d_off, (uint64_t *)ws.w_hidx.p, total, nullptr, s,
-                                       dist_out ? (T *)ws.w_hdist.p : nullptr, flags, false, d_radii, false));
+        c.out = {d_off, (uint64_t *)ws.w_hidx.p, dist_out ? (T *)ws.w_hdist.p : nullptr, total, nullptr};
+        c.add_listed = false;
+        PNCHK(radius_device_enqueue<T>(ix, ws, c, s));
     }
-    uint64_t *out = (uint64_t *)malloc((total ? total : 1) * sizeof(uint64_t));
-    T *dout = dist_out ? (T *)malloc((total ? total : 1) * sizeof(T)) : nullptr;
-    if (!out || (dist_out && !dout)) {
-        free(out);
-        free(dout);
-        (void)hipStreamSynchronize(s);
-        return fail(PN_ERR_NOMEM, "malloc(%llu results) failed", (unsigned long long)total);
-    }
-    hipError_t e = hipMemcpyAsync(offsets, d_off, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && total) e = hipMemcpyAsync(out, ws.w_hidx.p, total * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && total && dout) e = hipMemcpyAsync(dout, ws.w_hdist.p, total * sizeof(T), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-        free(out);
-        free(dout);
-        return fail(PN_ERR_DEVICE, "copying the radius lists back: %s", hipGetErrorString(e));
-    }
-    *idx_out = out;
-    if (dist_out) *dist_out = dout;
-    std::lock_guard<std::mutex> lk(ix->sh.mu);
-    ix->sh.stats.radius_results += total;
-    return PN_OK;
+    return csr_to_host<T>(ix, ws, d_off, nq, total, offsets, idx_out, dist_out, "the radius", s);
 }
 template <typename T>
 static int radii_self_device(const pn_index *ix, const T *d_radii, unsigned flags, uint64_t *d_offsets, uint64_t *d_idx,
                              T *d_dist, size_t capacity, uint64_t *d_total, hipStream_t s) {
     PNCHK(radii_args(ix, flags, PN_RADIUS_SORTED | PN_SELF_INCLUDE, d_offsets != nullptr, d_idx != nullptr || !capacity,
                      d_dist != nullptr || !capacity, d_radii != nullptr, (int)sizeof(T)));
-    return radius_self_device<T>(ix, (T)0, flags, d_offsets, d_idx, d_dist, capacity, d_total, s, d_radii);
+    return radius_self_device<T>(ix, within_each(d_radii), flags, d_offsets, d_idx, d_dist, capacity, d_total, s);
 }
 extern "C" int pn_query_radii_f32(const pn_index *ix, const float *q, size_t nq, size_t q_cols, ptrdiff_t q_stride,
                                   const float *radii, unsigned flags, uint64_t *offsets, uint64_t **idx_out,
@@ -4499,13 +4535,11 @@ extern "C" int pn_query_radii_self_device_f64(const pn_index *ix, const double *
 //      Without a sum that is all.  Otherwise the offsets are read back -- the one host wait of a call -- to cut the pieces.
 //      (A self call that leaves the rows out counts with PN_SELF_INCLUDE: the pieces below hold the rows themselves, and
 //      the sum kernel drops each row's own entry and writes the count.)
-//   3. sum: a piece is a contiguous query range of at most 2^18 queries whose lists hold at most E entries together
-//      (PN_OPT_KDE_PIECE, default 2^27; a longer single list is a piece of its own).  radius_device_enqueue writes the
-//      piece's lists with distances into workspace scratch of exactly the piece's total, kde_sum_kernel reads them there.
+//   3. sum: piece by piece (PieceWalk above, E = PN_OPT_KDE_PIECE).  radius_device_enqueue writes the piece's lists
+//      with distances into workspace scratch of exactly the piece's total, kde_sum_kernel reads them there.
 // Device memory beyond a 2^18-query batch's workspace: 16 + 2 sizeof T bytes per query and 8 + sizeof T bytes per entry of
 // the largest piece -- never the lists of the call.
 // ---------------------------------------------------------------------------
-constexpr uint64_t kKdePiece = (uint64_t)1 << 27;
 // (before any device is touched; `inputs`: the name of the first NULL input of a call with queries, or nullptr; nq: the
 // number of queries where the caller knows it without the handle, else n_h itself)
 static int kde_args(const pn_index *ix, unsigned flags, unsigned allowed, int kernel, double atol, const void *sum,
@@ -4548,48 +4582,30 @@ static int kde_enqueue(const pn_index *ix, Workspace &ws, bool self, const T *d_
     HIPCHK(launch_kde_cutoff<T>(d_h, n_h, nq, mode, f, hq, cut, s));
     // ---- 2. count
     const bool exclude = self && !(flags & PN_SELF_INCLUDE);
+    const RadiusQueries<T> queries = self ? RadiusQueries<T>{(const T *)ix->d_pts, nq, ix->dim, ix->ld}
+                                          : RadiusQueries<T>{d_q, nq, q_cols, q_stride};
+    RadiusCall<T> count{queries, within_each<T>(cut), {off, nullptr, nullptr, 0, nullptr}};
     if (self)
-        PNCHK(radius_self_enqueue<T>(ix, ws, (T)0, d_sum ? (unsigned)PN_SELF_INCLUDE : flags, off, nullptr, nullptr, 0, nullptr, s,
-                                     true, cut));
+        count.flags = d_sum ? (unsigned)PN_SELF_INCLUDE : flags;
     else
-        PNCHK(radius_device_enqueue<T>(ix, ws, d_q, nq, q_cols, q_stride, (T)0, off, nullptr, 0, nullptr, s, nullptr, 0, true,
-                                       cut, true));
+        count.add_listed = true;
+    PNCHK(self ? radius_self_enqueue<T>(ix, ws, count, s) : radius_device_enqueue<T>(ix, ws, count, s));
     if (d_count && !(d_sum && exclude)) HIPCHK(launch_kde_counts(off, nq, d_count, s));
     if (!d_sum) return PN_OK;
-    std::vector<uint64_t> h_off;
-    try {
-        h_off.resize(nq + 1);
-    } catch (const std::bad_alloc &) {
-        return fail(PN_ERR_NOMEM, "host allocation of %zu offsets failed", nq + 1);
-    }
-    HIPCHK(hipMemcpyAsync(h_off.data(), off, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    PieceWalk<T> pieces{ix, ws, kPieceKde, s};
+    PNCHK(pieces.host(nq));
+    HIPCHK(hipMemcpyAsync(pieces.h_off.data(), off, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     // (a query whose piece is empty gets its zeros here)
     HIPCHK(hipMemsetAsync(d_sum, 0, nq * sizeof(double), s));
     if (d_count && exclude) HIPCHK(hipMemsetAsync(d_count, 0, nq * sizeof(uint64_t), s));
     HIPCHK(hipStreamSynchronize(s));
     // ---- 3. sum, piece by piece
-    const uint64_t E = ix->kde_piece ? ix->kde_piece : kKdePiece;
-    PNCHK(ws.w_sf_off.ensure((std::min(nq, kSelfChunk) + 1) * sizeof(uint64_t)));
-    for (size_t a = 0; a < nq;) {
-        const size_t lim = nq - a < kSelfChunk ? nq : a + kSelfChunk;
-        // the last b in (a, lim] with off[b] - off[a] <= E, at least a + 1
-        size_t b = (size_t)(std::upper_bound(h_off.begin() + a + 1, h_off.begin() + lim + 1, h_off[a] + E) - h_off.begin()) - 1;
-        if (b <= a) b = a + 1;
-        const uint64_t total = h_off[b] - h_off[a];
-        if (total) {
-            PNCHK(ws.w_sf_idx.ensure(total * sizeof(uint64_t)));
-            PNCHK(ws.w_sf_dist.ensure(total * sizeof(T)));
-            uint64_t *in_off = (uint64_t *)ws.w_sf_off.p, *in_idx = (uint64_t *)ws.w_sf_idx.p;
-            T *in_dist = (T *)ws.w_sf_dist.p;
-            const T *qp = self ? (const T *)ix->d_pts + a * ix->ld : d_q + a * q_stride;
-            PNCHK(radius_device_enqueue<T>(ix, ws, qp, b - a, self ? ix->dim : q_cols, self ? ix->ld : q_stride, (T)0, in_off,
-                                           in_idx, (size_t)total, nullptr, s, in_dist, 0, false, cut + a, false));
-            HIPCHK(launch_kde_sum<T>(in_off, in_idx, in_dist, hq + a, b - a, kernel, exclude ? ix->index_base + a : ~0ull,
-                                     d_sum + a, d_count && exclude ? d_count + a : nullptr, s));
-        }
-        a = b;
-    }
-    return PN_OK;
+    return pieces.walk(queries, count.within, kPieceDist, [&](const Piece<T> &p) -> int {
+        HIPCHK(launch_kde_sum<T>(p.in_off, p.in_idx, p.in_dist, hq + p.a, p.b - p.a, kernel,
+                                 exclude ? ix->index_base + p.a : ~0ull, d_sum + p.a,
+                                 d_count && exclude ? d_count + p.a : nullptr, s));
+        return PN_OK;
+    });
 }
 template <typename T>
 static int kde_device(const pn_index *ix, bool self, const T *d_q, size_t nq, size_t q_cols, size_t q_stride, const T *d_h,
@@ -4688,10 +4704,10 @@ extern "C" int pn_kde_self_device_f64(const pn_index *ix, const double *d_h, siz
 //   1. count: radius_device_enqueue with capacity 0 over the active positions through the d_radii path (a constant array
 //      gives the scalar call's thresholds word for word) gives the offsets, which are read back -- the
 //      first host wait of an iteration -- to cut the pieces.
-//   2. step: a piece is a contiguous range of at most 2^18 active seeds whose lists hold at most E entries together
-//      (PN_OPT_MS_PIECE, default 2^27; a longer single list is a piece of its own).  radius_device_enqueue writes the
-//      piece's lists, without distances, into workspace scratch of exactly the piece's total; ms_step_kernel reads them
-//      there, moves the positions in place, and finishes the seeds that stop.
+//   2. step: piece by piece over the active seeds (PieceWalk above, E = PN_OPT_MS_PIECE; the pieces without entries
+//      too: their seeds are dead).  radius_device_enqueue writes the piece's lists, without distances, into workspace
+//      scratch of exactly the piece's total; ms_step_kernel reads them there, moves the positions in place, and finishes
+//      the seeds that stop.
 //   3. compact: the seeds that go on are listed and gathered into the other copy of the arrays; their number is read
 //      back -- the second host wait -- for the next iteration's launches.
 // A seed that has stopped is in no later count, fill or step.  Device memory: 2 (dim + 1) sizeof T + 24 bytes per seed of
@@ -4699,7 +4715,6 @@ extern "C" int pn_kde_self_device_f64(const pn_index *ix, const double *d_h, siz
 // 2^18 queries; the counting pass takes the active seeds in one call (as kde_enqueue's does), so its padded query copy
 // and its 12 bytes per (seed, row segment) grow with the active seeds.
 // ---------------------------------------------------------------------------
-constexpr uint64_t kMsPiece = (uint64_t)1 << 27;
 constexpr unsigned kMsFlags = PN_MS_SEED_ROWS;
 // (before any device is touched; the header states the order)
 static int ms_args(const pn_index *ix, unsigned flags, double tol, size_t max_iter, const void *modes, const void *points,
@@ -4742,61 +4757,45 @@ static int ms_enqueue(const pn_index *ix, Workspace &ws, const T *d_seeds, size_
     uint32_t *slot[2] = {(uint32_t *)u, (uint32_t *)(u + u_bytes)};
     uint32_t *keep = (uint32_t *)(u + 2 * u_bytes), *sel = (uint32_t *)(u + 3 * u_bytes), *nsel = (uint32_t *)(u + 4 * u_bytes);
     HIPCHK(launch_ms_init<T>(d_seeds, s_stride, ns, (int)dim, d_h, n_h, pos[0], hq[0], slot[0], s));
-    const uint64_t E = ix->ms_piece ? ix->ms_piece : kMsPiece;
-    std::vector<uint64_t> h_off;
-    try {
-        h_off.resize(ns + 1);
-    } catch (const std::bad_alloc &) {
-        return fail(PN_ERR_NOMEM, "host allocation of %zu offsets failed", ns + 1);
-    }
-    PNCHK(ws.w_sf_off.ensure((std::min(ns, kSelfChunk) + 1) * sizeof(uint64_t)));
+    PieceWalk<T> pieces{ix, ws, kPieceMs, s};
+    PNCHK(pieces.host(ns));
+    PNCHK(pieces.scratch());
     uint64_t iterations = 0, seed_steps = 0;
     size_t na = ns;
     int cur = 0;
     for (size_t t = 1; na > 0; ++t) {
         // ---- 1. count
-        PNCHK(radius_device_enqueue<T>(ix, ws, pos[cur], na, dim, dim, (T)0, off, nullptr, 0, nullptr, s, nullptr, 0, true,
-                                       hq[cur], true));
-        HIPCHK(hipMemcpyAsync(h_off.data(), off, (na + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        const RadiusQueries<T> seeds{pos[cur], na, dim, dim};
+        RadiusCall<T> count{seeds, within_each<T>(hq[cur]), {off, nullptr, nullptr, 0, nullptr}};
+        count.add_listed = true;
+        PNCHK(radius_device_enqueue<T>(ix, ws, count, s));
+        HIPCHK(hipMemcpyAsync(pieces.h_off.data(), off, (na + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         ++iterations;
         seed_steps += na;
-        // ---- 2. step, piece by piece
-        for (size_t a = 0; a < na;) {
-            const size_t lim = na - a < kSelfChunk ? na : a + kSelfChunk;
-            // the last b in (a, lim] with off[b] - off[a] <= E, at least a + 1
-            size_t b = (size_t)(std::upper_bound(h_off.begin() + a + 1, h_off.begin() + lim + 1, h_off[a] + E) - h_off.begin()) - 1;
-            if (b <= a) b = a + 1;
-            const uint64_t total = h_off[b] - h_off[a];
+        // ---- 2. step, piece by piece (a piece without entries: its seeds are dead)
+        PNCHK(pieces.walk(seeds, count.within, kPieceEmptyToo, [&](const Piece<T> &p) -> int {
             MsStep<T> st{};
             st.index_base = ix->index_base;
             st.X = (const T *)ix->d_pts;
             st.ld = ix->ld;
             st.dim = (int)dim;
-            st.pos = pos[cur] + a * dim;
-            st.slot = slot[cur] + a;
-            st.nq = b - a;
+            st.pos = pos[cur] + p.a * dim;
+            st.slot = slot[cur] + p.a;
+            st.nq = p.b - p.a;
             st.tol = tol;
             st.iter = (uint32_t)std::min<size_t>(t, 0xFFFFFFFFu);
             st.last = t >= max_iter;
-            st.keep = keep + a;
+            st.keep = keep + p.a;
             st.modes = d_modes;
             st.points = d_points;
             st.iters = d_iters;
             st.shift = d_shift;
-            if (total) {
-                PNCHK(ws.w_sf_idx.ensure(total * sizeof(uint64_t)));
-                st.off = (const uint64_t *)ws.w_sf_off.p;
-                st.idx = (const uint64_t *)ws.w_sf_idx.p;
-                PNCHK(radius_device_enqueue<T>(ix, ws, pos[cur] + a * dim, b - a, dim, dim, (T)0, (uint64_t *)ws.w_sf_off.p,
-                                               (uint64_t *)ws.w_sf_idx.p, (size_t)total, nullptr, s, nullptr, 0, false,
-                                               hq[cur] + a, false));
-                HIPCHK(launch_ms_step<T>(st, s));
-            } else {
-                HIPCHK(launch_ms_dead<T>(st, s));
-            }
-            a = b;
-        }
+            st.off = p.in_off;
+            st.idx = p.in_idx;
+            HIPCHK(p.total ? launch_ms_step<T>(st, s) : launch_ms_dead<T>(st, s));
+            return PN_OK;
+        }));
         if (t >= max_iter) break;  // (every seed has stopped)
         // ---- 3. compact
         uint32_t h_n = 0;
