@@ -58,6 +58,7 @@ UNITS = [
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
           "-fno-fast-math", "-fhip-fp32-correctly-rounded-divide-sqrt"]
 HEADERS = [os.path.join(CSRC, "pn_internal.h"), os.path.join(CSRC, "bf16_launch.h"), os.path.join(CSRC, "csr_pieces.h"),
+           os.path.join(CSRC, "csr_splice.h"),
            os.path.join(CSRC, "topk_buffer.h"),
            os.path.join(CSRC, "host_tree.h"),
            os.path.join(CSRC, "union_find.h"),

@@ -33,6 +33,7 @@
 #include <rccl/rccl.h>
 
 #include "../../include/petal_mi355x.h"
+#include "csr_splice.h"
 #include "pn_internal.h"
 
 using namespace pn;
@@ -188,11 +189,15 @@ struct Dev {  // one GPU this process drives = one rank of the communicator
     bool prof_pending[kProf] = {};
     unsigned prof_next = 0;
     double shard_ms = 0.0, exchange_ms = 0.0;
+    template <typename F>
+    void each_buf(F &&f) {  // every Buf above, once: a new one is named here and nowhere else
+        for (Buf *b : {&q, &out_idx, &out_dist, &lparts, &pack[0], &pack[1], &gathered[0], &gathered[1], &rad_a, &rad_b, &rad_c,
+                       &sf_rows, &sf_idx, &sf_dist})
+            f(*b);
+    }
     // (Bufs point at this Dev's retired list: adopt() after the vector of Devs has its final size)
     void adopt() {
-        Buf *bs[] = {&q, &out_idx, &out_dist, &lparts, &pack[0], &pack[1], &gathered[0], &gathered[1], &rad_a, &rad_b, &rad_c,
-                     &sf_rows, &sf_idx, &sf_dist};
-        for (Buf *b : bs) b->retired = &retired;
+        each_buf([this](Buf &b) { b.retired = &retired; });
     }
     void free_retired() {
         for (void *r : retired) (void)hipFree(r);
@@ -243,91 +248,33 @@ template <> struct ShT<float> {
     static int create(const float *p, size_t n, size_t c, ptrdiff_t rs, ptrdiff_t cs, int dev, pn_index **o, int metric) {
         return metric == 1 ? pn_index_create_cosine_f32(p, n, c, rs, cs, dev, o) : pn_index_create_f32(p, n, c, rs, cs, dev, o);
     }
-    static int create_device(const float *p, size_t n, size_t c, size_t rs, int dev, void *st, pn_index **o) {
-        return pn_index_create_device_f32(p, n, c, rs, dev, st, o);
-    }
-    static int query_strided(const pn_index *ix, const float *q, size_t nq, size_t qc, size_t qs, size_t k, uint64_t *oi,
-                             float *od, size_t os, hipStream_t s) {
-        return query_device_strided_f32(ix, q, nq, qc, qs, k, oi, od, os, s);
-    }
-    static int merge(const uint64_t *pi, const float *pd, size_t np, size_t is, size_t ds, size_t nq, size_t kp, size_t ko,
-                     uint64_t *oi, float *od, int dev, void *s, bool signed_keys) {
-        return merge_topk_device_keys_f32(pi, pd, np, is, ds, nq, kp, ko, oi, od, dev, s, signed_keys);
-    }
-    static int radius_device(const pn_index *ix, const float *q, size_t nq, size_t qc, size_t qs, float r, uint64_t *off,
-                             uint64_t *idx, size_t cap, uint64_t *tot, void *st) {
-        return pn_query_radius_device_f32(ix, q, nq, qc, qs, r, off, idx, cap, tot, st);
-    }
-    static int radius(const pn_index *ix, const float *q, size_t nq, size_t qc, ptrdiff_t qs, float r, uint64_t *off,
-                      uint64_t **out) {
-        return pn_query_radius_f32(ix, q, nq, qc, qs, r, off, out);
-    }
-    static int radius_wd(const pn_index *ix, const float *q, size_t nq, size_t qc, ptrdiff_t qs, float r, unsigned fl,
-                         uint64_t *off, uint64_t **out, float **dout) {
-        return pn_query_radius_with_distance_f32(ix, q, nq, qc, qs, r, fl, off, out, dout);
-    }
-    static int radius_wd_device(const pn_index *ix, const float *q, size_t nq, size_t qc, size_t qs, float r, unsigned fl,
-                                uint64_t *off, uint64_t *idx, float *dist, size_t cap, uint64_t *tot, void *st) {
-        return pn_query_radius_with_distance_device_f32(ix, q, nq, qc, qs, r, fl, off, idx, dist, cap, tot, st);
-    }
-    static int self(const pn_index *ix, size_t k, unsigned fl, uint64_t *oi, float *od) {
-        return pn_query_self_f32(ix, k, fl, oi, od);
-    }
-    static int self_device(const pn_index *ix, size_t k, unsigned fl, uint64_t *oi, float *od, hipStream_t s) {
-        return pn_query_self_device_f32(ix, k, fl, oi, od, s);
-    }
-    static int radius_self(const pn_index *ix, float r, unsigned fl, uint64_t *off, uint64_t **out, float **dout) {
-        return pn_query_radius_self_f32(ix, r, fl, off, out, dout);
-    }
-    static int radius_self_device(const pn_index *ix, float r, unsigned fl, uint64_t *off, uint64_t *idx, float *dist, size_t cap,
-                                  uint64_t *tot, void *st) {
-        return pn_query_radius_self_device_f32(ix, r, fl, off, idx, dist, cap, tot, st);
-    }
+    static constexpr auto create_device = &pn_index_create_device_f32;
+    static constexpr auto query_strided = &query_device_strided_f32;
+    static constexpr auto merge = &merge_topk_device_keys_f32;
+    static constexpr auto radius_device = &pn_query_radius_device_f32;
+    static constexpr auto radius = &pn_query_radius_f32;
+    static constexpr auto radius_wd = &pn_query_radius_with_distance_f32;
+    static constexpr auto radius_wd_device = &pn_query_radius_with_distance_device_f32;
+    static constexpr auto self = &pn_query_self_f32;
+    static constexpr auto self_device = &pn_query_self_device_f32;
+    static constexpr auto radius_self = &pn_query_radius_self_f32;
+    static constexpr auto radius_self_device = &pn_query_radius_self_device_f32;
 };
 template <> struct ShT<double> {
     static int create(const double *p, size_t n, size_t c, ptrdiff_t rs, ptrdiff_t cs, int dev, pn_index **o, int metric) {
         return metric == 1 ? pn_index_create_cosine_f64(p, n, c, rs, cs, dev, o) : pn_index_create_f64(p, n, c, rs, cs, dev, o);
     }
-    static int create_device(const double *p, size_t n, size_t c, size_t rs, int dev, void *st, pn_index **o) {
-        return pn_index_create_device_f64(p, n, c, rs, dev, st, o);
-    }
-    static int query_strided(const pn_index *ix, const double *q, size_t nq, size_t qc, size_t qs, size_t k, uint64_t *oi,
-                             double *od, size_t os, hipStream_t s) {
-        return query_device_strided_f64(ix, q, nq, qc, qs, k, oi, od, os, s);
-    }
-    static int merge(const uint64_t *pi, const double *pd, size_t np, size_t is, size_t ds, size_t nq, size_t kp, size_t ko,
-                     uint64_t *oi, double *od, int dev, void *s, bool signed_keys) {
-        return merge_topk_device_keys_f64(pi, pd, np, is, ds, nq, kp, ko, oi, od, dev, s, signed_keys);
-    }
-    static int radius_device(const pn_index *ix, const double *q, size_t nq, size_t qc, size_t qs, double r, uint64_t *off,
-                             uint64_t *idx, size_t cap, uint64_t *tot, void *st) {
-        return pn_query_radius_device_f64(ix, q, nq, qc, qs, r, off, idx, cap, tot, st);
-    }
-    static int radius(const pn_index *ix, const double *q, size_t nq, size_t qc, ptrdiff_t qs, double r, uint64_t *off,
-                      uint64_t **out) {
-        return pn_query_radius_f64(ix, q, nq, qc, qs, r, off, out);
-    }
-    static int radius_wd(const pn_index *ix, const double *q, size_t nq, size_t qc, ptrdiff_t qs, double r, unsigned fl,
-                         uint64_t *off, uint64_t **out, double **dout) {
-        return pn_query_radius_with_distance_f64(ix, q, nq, qc, qs, r, fl, off, out, dout);
-    }
-    static int radius_wd_device(const pn_index *ix, const double *q, size_t nq, size_t qc, size_t qs, double r, unsigned fl,
-                                uint64_t *off, uint64_t *idx, double *dist, size_t cap, uint64_t *tot, void *st) {
-        return pn_query_radius_with_distance_device_f64(ix, q, nq, qc, qs, r, fl, off, idx, dist, cap, tot, st);
-    }
-    static int self(const pn_index *ix, size_t k, unsigned fl, uint64_t *oi, double *od) {
-        return pn_query_self_f64(ix, k, fl, oi, od);
-    }
-    static int self_device(const pn_index *ix, size_t k, unsigned fl, uint64_t *oi, double *od, hipStream_t s) {
-        return pn_query_self_device_f64(ix, k, fl, oi, od, s);
-    }
-    static int radius_self(const pn_index *ix, double r, unsigned fl, uint64_t *off, uint64_t **out, double **dout) {
-        return pn_query_radius_self_f64(ix, r, fl, off, out, dout);
-    }
-    static int radius_self_device(const pn_index *ix, double r, unsigned fl, uint64_t *off, uint64_t *idx, double *dist, size_t cap,
-                                  uint64_t *tot, void *st) {
-        return pn_query_radius_self_device_f64(ix, r, fl, off, idx, dist, cap, tot, st);
-    }
+    static constexpr auto create_device = &pn_index_create_device_f64;
+    static constexpr auto query_strided = &query_device_strided_f64;
+    static constexpr auto merge = &merge_topk_device_keys_f64;
+    static constexpr auto radius_device = &pn_query_radius_device_f64;
+    static constexpr auto radius = &pn_query_radius_f64;
+    static constexpr auto radius_wd = &pn_query_radius_with_distance_f64;
+    static constexpr auto radius_wd_device = &pn_query_radius_with_distance_device_f64;
+    static constexpr auto self = &pn_query_self_f64;
+    static constexpr auto self_device = &pn_query_self_device_f64;
+    static constexpr auto radius_self = &pn_query_radius_self_f64;
+    static constexpr auto radius_self_device = &pn_query_radius_self_device_f64;
 };
 static int check_elem(const pn_sharded *sh, size_t bytes) {
     if (sh->elem_bytes != (int)bytes) return set_error(PN_ERR_INVALID, "handle element type mismatch (f%d handle)", sh->elem_bytes * 8);
@@ -351,9 +298,7 @@ static void destroy_dev(Dev &d) {
     if (d.stream) (void)hipStreamSynchronize(d.stream);
     if (d.comm_stream) (void)hipStreamSynchronize(d.comm_stream);
     if (d.comm && rccl().ok()) (void)rccl().CommDestroy(d.comm);
-    Buf *bufs[] = {&d.q, &d.out_idx, &d.out_dist, &d.lparts, &d.pack[0], &d.pack[1], &d.gathered[0], &d.gathered[1],
-                   &d.rad_a, &d.rad_b, &d.rad_c, &d.sf_rows, &d.sf_idx, &d.sf_dist};
-    for (Buf *b : bufs) b->release();
+    d.each_buf([](Buf &b) { b.release(); });
     d.free_retired();
     for (auto &tr : d.ev_prof)
         for (hipEvent_t e : tr)
@@ -704,6 +649,57 @@ struct DevUse {
     }
 };
 
+static void keep_first(int &rc, int r) {
+    if (rc == PN_OK) rc = r;
+}
+static int hip_rc(hipError_t e, const char *what) {
+    if (e == hipSuccess) return PN_OK;
+    return set_error(e == hipErrorOutOfMemory ? PN_ERR_NOMEM : PN_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
+}
+// a batch of host queries ([nq] rows of q_cols, q_row_stride elements apart) into d.q, packed, enqueued on `s`
+template <typename T>
+static int upload_queries(Dev &d, const T *queries, size_t nq, size_t q_cols, size_t q_row_stride, hipStream_t s) {
+    SPN(d.q.ensure(nq * (q_cols ? q_cols : 1) * sizeof(T)));
+    if (!q_cols) return PN_OK;
+    if (nq == 1 || q_row_stride == q_cols)
+        SHIP(hipMemcpyAsync(d.q.p, queries, nq * q_cols * sizeof(T), hipMemcpyHostToDevice, s));
+    else
+        SHIP(hipMemcpy2DAsync(d.q.p, q_cols * sizeof(T), queries, q_row_stride * sizeof(T), q_cols * sizeof(T), nq,
+                              hipMemcpyHostToDevice, s));
+    return PN_OK;
+}
+// ONE all-gather of `count` elements per GPU over the GPUs this process drives (grouped: there may be several);
+// of(d, i) names what GPU i sends, where it receives and the stream
+struct GatherEnds {
+    const void *send;
+    void *recv;
+    hipStream_t s;
+};
+template <typename Of>
+static int all_gather_devs(std::vector<Dev> &devs, size_t count, ncclDataType_t type, Of &&of) {
+    SNCCL(rccl().GroupStart());
+    for (size_t i = 0; i < devs.size(); ++i) {
+        const GatherEnds e = of(devs[i], i);
+        ncclResult_t r = rccl().AllGather(e.send, e.recv, count, type, devs[i].comm, e.s);
+        if (r != ncclSuccess) {
+            (void)rccl().GroupEnd();
+            return set_error(PN_ERR_COMM, "ncclAllGather: %s", rccl().GetErrorString(r));
+        }
+    }
+    SNCCL(rccl().GroupEnd());
+    return PN_OK;
+}
+// a part's device radius pipeline over a batch in HBM (pn_query_radius_device_* / ..._with_distance_device_*), with
+// distances (d_dist, flags) or without
+template <typename T>
+static int part_radius_device(const pn_index *ix, const T *d_q, size_t nq, size_t q_cols, size_t q_stride, T radius,
+                              bool wd, unsigned flags, uint64_t *d_off, uint64_t *d_idx, T *d_dist, size_t cap,
+                              uint64_t *d_tot, void *stream) {
+    if (wd)
+        return ShT<T>::radius_wd_device(ix, d_q, nq, q_cols, q_stride, radius, flags, d_off, d_idx, d_dist, cap, d_tot, stream);
+    return ShT<T>::radius_device(ix, d_q, nq, q_cols, q_stride, radius, d_off, d_idx, cap, d_tot, stream);
+}
+
 // rank mode (or one GPU): queries and results on this process's GPU, everything enqueued on `s`
 template <typename T>
 static int query_device_one(const pn_sharded *sh, Dev &d, const T *d_q, size_t nq, size_t q_cols, size_t q_stride,
@@ -807,14 +803,7 @@ static int sharded_query_host(const pn_sharded *sh, const T *queries, size_t nq,
         // calls go back now (the previous host call ended with a stream sync: without this the multi-GPU path and the
         // one-shard early return, which never reach acquire_dev, kept every outgrown buffer until destroy -- ADVICE r3)
         SPN(acquire_dev(d, d.stream));
-        SPN(d.q.ensure(nq * qc * sizeof(T)));
-        if (q_cols) {
-            if (nq == 1 || (size_t)q_row_stride == q_cols)
-                SHIP(hipMemcpyAsync(d.q.p, queries, nq * q_cols * sizeof(T), hipMemcpyHostToDevice, d.stream));
-            else
-                SHIP(hipMemcpy2DAsync(d.q.p, q_cols * sizeof(T), queries, (size_t)q_row_stride * sizeof(T),
-                                      q_cols * sizeof(T), nq, hipMemcpyHostToDevice, d.stream));
-        }
+        SPN(upload_queries<T>(d, queries, nq, q_cols, (size_t)q_row_stride, d.stream));
     }
     Dev &d0 = devs[0];
     {
@@ -833,15 +822,8 @@ static int sharded_query_host(const pn_sharded *sh, const T *queries, size_t nq,
             SPN(d.gathered[0].ensure((size_t)sh->world * words * 8));
             SPN(enqueue_local<T>(sh, d, (const T *)d.q.p, nq, q_cols, qc, k, kp, kd, 0, d.stream));
         }
-        SNCCL(rccl().GroupStart());
-        for (Dev &d : devs) {
-            ncclResult_t r = rccl().AllGather(d.pack[0].p, d.gathered[0].p, words, ncclUint64, d.comm, d.stream);
-            if (r != ncclSuccess) {
-                (void)rccl().GroupEnd();
-                return set_error(PN_ERR_COMM, "ncclAllGather: %s", rccl().GetErrorString(r));
-            }
-        }
-        SNCCL(rccl().GroupEnd());
+        SPN(all_gather_devs(devs, words, ncclUint64,
+                            [](Dev &d, size_t) { return GatherEnds{d.pack[0].p, d.gathered[0].p, d.stream}; }));
         SetGuard g(d0.device);
         SPN(enqueue_merge<T>(sh, d0, nq, kd, k_out, 0, (uint64_t *)d0.out_idx.p, (T *)d0.out_dist.p, d0.stream));
     }
@@ -870,20 +852,23 @@ extern "C" int pn_sharded_query_f64(const pn_sharded *sh, const double *queries,
 // ---------------------------------------------------------------------------
 // BallTree::query_radius over the sharded corpus: per query the ascending global rows of every shard, shard after
 // shard -- shards are ascending row ranges, so the concatenation is ascending.  Local shards answer through
-// pn_query_radius_f32; with one process per GPU the variable-length lists travel by two all-gathers (counts, then the
-// lists padded to the longest) and are spliced on the host.
-// dist_out (nullable: pn_sharded_query_radius_with_distance_*): the distances travel next to the rows (a third all-gather
-// of the same shape with one process per GPU); with PN_RADIUS_SORTED every part's lists come back sorted by (distance,
-// global row) and the splice is a per-query merge of the parts in that order.
+// pn_query_radius_f32 and are spliced on the host (csr_splice.h).  With distances (pn_sharded_query_radius_with_distance_*)
+// they travel next to the rows; with PN_RADIUS_SORTED every part's lists come back sorted by (distance, global row) and
+// the splice is a per-query merge of the parts in that order.
 //
-// splice of W parts (part r: offsets po[r][0 .. nq], rows at pi[r], distances at pd[r] or nullptr) into one CSR
+// One process per GPU: the ragged exchange (rank_radius_exchange), shared with the radius self-queries further down.
+// The rank's shard answers the batch through the DEVICE entry point (counts, scan and fill in HBM), its CSR offsets
+// are all-gathered as they lie in HBM together with one status word, and the lists (and distances) travel device to
+// device, padded to the longest -- the host sees the gathered offsets once (to size the exchange) and the gathered lists
+// once (to splice).  A rank whose local work fails still enters the offsets all-gather of the attempt; the status
+// words make every rank fail after it.
+//
+// splice of W parts over a batch into one CSR
 template <typename T>
-static int radius_splice(size_t nq, const std::vector<const uint64_t *> &po, const std::vector<const uint64_t *> &pi,
-                         const std::vector<const T *> &pd, bool sorted, uint64_t *offsets, uint64_t **idx_out,
+static int radius_splice(size_t nq, const std::vector<CsrPart<T>> &parts, bool sorted, uint64_t *offsets, uint64_t **idx_out,
                          T **dist_out) {
-    const size_t W = po.size();
-    uint64_t total = 0;
-    for (size_t r = 0; r < W; ++r) total += po[r][nq] - po[r][0];
+    const size_t W = parts.size();
+    const uint64_t total = csr_splice_entries(parts.data(), W, nq);  // (a part's offsets need not start at zero)
     uint64_t *res = (uint64_t *)malloc((total ? total : 1) * sizeof(uint64_t));
     T *dres = dist_out ? (T *)malloc((total ? total : 1) * sizeof(T)) : nullptr;
     if (!res || (dist_out && !dres)) {
@@ -891,138 +876,136 @@ static int radius_splice(size_t nq, const std::vector<const uint64_t *> &po, con
         free(dres);
         return set_error(PN_ERR_NOMEM, "malloc(%llu results) failed", (unsigned long long)total);
     }
-    std::vector<uint64_t> cur(W), end(W);
+    std::vector<uint64_t> cur(W);
     uint64_t w = 0;
     for (size_t a = 0; a < nq; ++a) {
         offsets[a] = w;
-        if (!sorted) {  // the parts' (ascending) lists in part order
-            for (size_t r = 0; r < W; ++r) {
-                const uint64_t lo = po[r][a], c = po[r][a + 1] - lo;
-                if (c) {
-                    memcpy(res + w, pi[r] + lo, (size_t)c * sizeof(uint64_t));
-                    if (dres) memcpy(dres + w, pd[r] + lo, (size_t)c * sizeof(T));
-                }
-                w += c;
-            }
-            continue;
-        }
-        // W-way merge by (distance, global row): the lists hold no NaN, and -0 compares equal to +0 as in the k-NN order
-        for (size_t r = 0; r < W; ++r) {
-            cur[r] = po[r][a];
-            end[r] = po[r][a + 1];
-        }
-        for (;;) {
-            size_t best = W;
-            for (size_t r = 0; r < W; ++r) {
-                if (cur[r] == end[r]) continue;
-                if (best == W) {
-                    best = r;
-                    continue;
-                }
-                const T d = pd[r][cur[r]], db = pd[best][cur[best]];
-                if (d < db || (d == db && pi[r][cur[r]] < pi[best][cur[best]])) best = r;
-            }
-            if (best == W) break;
-            res[w] = pi[best][cur[best]];
-            dres[w] = pd[best][cur[best]];
-            ++cur[best];
+        csr_splice_query(parts.data(), W, a, sorted, nullptr, cur.data(), [&](size_t r, uint64_t e) {
+            res[w] = parts[r].rows[e];
+            if (dres) dres[w] = parts[r].dist[e];
             ++w;
-        }
+        });
     }
     offsets[nq] = w;
     *idx_out = res;
     if (dist_out) *dist_out = dres;
     return PN_OK;
 }
+
+namespace {
+// what a rank-mode exchange leaves on the host: the W ranks' parts over the batch, in rank order (shards are ascending
+// row ranges), ready for the splice
+template <typename T>
+struct RankParts {
+    std::vector<uint64_t> off, ids, dist;  // gathered records [W][rec], lists [W][longest], distances [W][dw words]
+    std::vector<CsrPart<T>> parts;
+};
+// rad_a of the exchange over a batch of nqb queries: [local offsets no | status 1 | total 1 | gathered W x rec],
+// no = nqb + 1.  A rank sends its record: its offsets and its status word, rec = no + 1 words.
+struct RadA {
+    uint64_t *off, *status, *tot, *all;
+    size_t no, rec;
+    static size_t words(size_t W, size_t nqb) { return (nqb + 3) + W * (nqb + 2); }
+    RadA(void *p, size_t nqb)
+        : off((uint64_t *)p), status(off + nqb + 1), tot(status + 1), all(tot + 1), no(nqb + 1), rec(nqb + 2) {}
+};
+}  // namespace
+
+// One process per GPU: this rank's part answers the batch (nqb queries in HBM, qs elements apart) through the device
+// radius entry, offsets + status are all-gathered, lists (and distances, wd) travel padded to the longest, the host
+// receives the W parts in x.  Everything on d.stream, the handle locked.
+// rc: what this rank's work for the batch has come to so far.  From here to the offsets all-gather of an attempt no
+// local failure returns: it sets the status word, the rank enters the collective and returns its own error after it;
+// the other ranks return PN_ERR_DEVICE naming it.  A failed collective returns at once: nothing can be done for the peers.
+// cap: list capacity per rank, kept by the caller from one exchange to the next.  It only ever takes values that are
+// the same on every rank (the caller's start, the floor below, the gathered `longest`), so all ranks retry alike.
+template <typename T>
+static int rank_radius_exchange(const pn_sharded *sh, const T *batch, size_t nqb, size_t q_cols, size_t qs, T radius,
+                                unsigned inner, bool wd, int rc, size_t &cap, RankParts<T> &x) {
+    Dev &d = sh->devs[0];
+    const hipStream_t s = d.stream;
+    const size_t W = (size_t)sh->world;
+    const pn_index *lix = sh->parts.empty() ? nullptr : sh->parts[0].ix;
+    // (without its record a rank has nothing to send from or to gather into: the one local failure that cannot travel)
+    SPN(d.rad_a.ensure(RadA::words(W, nqb) * 8));
+    const RadA a(d.rad_a.p, nqb);
+    // rad_b, rows: [mine cap | gathered W x cap].  rad_c, distances: [mine dwords(cap) | gathered W x dwords(cap)] 8-byte
+    // words.  Of both, what `longest` entries take travels per rank.
+    auto dwords = [](uint64_t c) { return (size_t)((c * sizeof(T) + 7) / 8); };
+    if (cap < nqb * 4 + 1024) cap = nqb * 4 + 1024;
+    x.off.resize(W * a.rec);
+    uint64_t longest = 1;
+    for (int attempt = 0;; ++attempt) {
+        int lrc = rc;
+        if (lrc == PN_OK) lrc = d.rad_b.ensure((cap + W * cap) * 8);
+        if (lrc == PN_OK && wd) lrc = d.rad_c.ensure((dwords(cap) + W * dwords(cap)) * 8);
+        if (lrc == PN_OK)  // (a rank without rows: every list empty)
+            lrc = lix ? part_radius_device<T>(lix, batch, nqb, q_cols, qs, radius, wd, inner, a.off, (uint64_t *)d.rad_b.p,
+                                              (T *)d.rad_c.p, cap, a.tot, s)
+                      : hip_rc(hipMemsetAsync(a.off, 0, a.no * 8, s), "offsets");
+        keep_first(rc, lrc);
+        SHIP(hipMemsetAsync(a.status, rc == PN_OK ? 0 : 0xFF, 8, s));
+        SNCCL(rccl().AllGather(a.off, a.all, a.rec, ncclUint64, d.comm, s));
+        SHIP(hipMemcpyAsync(x.off.data(), a.all, W * a.rec * 8, hipMemcpyDeviceToHost, s));
+        SHIP(hipStreamSynchronize(s));
+        if (rc != PN_OK) return rc;
+        longest = 1;
+        for (size_t r = 0; r < W; ++r) {
+            if (x.off[r * a.rec + a.no])
+                return set_error(PN_ERR_DEVICE, "radius exchange: rank %zu failed in its local work", r);
+            longest = std::max<uint64_t>(longest, x.off[r * a.rec + nqb]);
+        }
+        if (longest <= cap) break;  // every rank's lists fit (all ranks see the same numbers: same decision)
+        if (attempt) return set_error(PN_ERR_DEVICE, "radius lists changed size between two passes");
+        cap = (size_t)longest;  // some rank overflowed: everybody re-runs with room for the longest
+    }
+    uint64_t *d_mine = (uint64_t *)d.rad_b.p, *d_lists = d_mine + cap;
+    uint64_t *d_dists = wd ? (uint64_t *)d.rad_c.p + dwords(cap) : nullptr;
+    const size_t dw = dwords(longest);
+    SNCCL(rccl().AllGather(d_mine, d_lists, (size_t)longest, ncclUint64, d.comm, s));
+    if (wd)  // (every rank alike: the call's arguments decide it)
+        SNCCL(rccl().AllGather(d.rad_c.p, d_dists, dw, ncclUint64, d.comm, s));
+    x.ids.resize((size_t)(W * longest));
+    x.dist.resize(wd ? W * dw : 0);
+    SHIP(hipMemcpyAsync(x.ids.data(), d_lists, (size_t)(W * longest) * 8, hipMemcpyDeviceToHost, s));
+    if (wd) SHIP(hipMemcpyAsync(x.dist.data(), d_dists, W * dw * 8, hipMemcpyDeviceToHost, s));
+    SHIP(hipStreamSynchronize(s));
+    x.parts.assign(W, CsrPart<T>{});
+    for (size_t r = 0; r < W; ++r) {
+        x.parts[r].off = x.off.data() + r * a.rec;
+        x.parts[r].rows = x.ids.data() + r * longest;
+        if (wd) x.parts[r].dist = (const T *)(x.dist.data() + r * dw);
+    }
+    return PN_OK;
+}
+
+// wd: pn_sharded_query_radius_with_distance_* (dist_out, flags); else dist_out is nullptr and flags 0
 template <typename T>
 static int sharded_query_radius(const pn_sharded *sh, const T *queries, size_t nq, size_t q_cols, ptrdiff_t q_row_stride,
-                                T radius, uint64_t *offsets, uint64_t **idx_out, T **dist_out = nullptr,
-                                unsigned flags = 0) {
+                                T radius, bool wd, unsigned flags, uint64_t *offsets, uint64_t **idx_out, T **dist_out) {
     if (!sh) return set_error(PN_ERR_INVALID, "handle is NULL");
     SPN(check_elem(sh, sizeof(T)));
-    if (!offsets || !idx_out) return set_error(PN_ERR_INVALID, "output pointer is NULL");
+    if (!offsets || !idx_out || (wd && !dist_out)) return set_error(PN_ERR_INVALID, "output pointer is NULL");
     if (flags & ~(unsigned)PN_RADIUS_SORTED) return set_error(PN_ERR_INVALID, "unknown radius flags 0x%x", flags);
     *idx_out = nullptr;
-    if (dist_out) *dist_out = nullptr;
+    if (wd) *dist_out = nullptr;
     offsets[0] = 0;
     if (nq == 0) return PN_OK;
     if (!queries && q_cols) return set_error(PN_ERR_INVALID, "queries is NULL");
-    const bool sorted = dist_out && (flags & PN_RADIUS_SORTED);
+    const bool sorted = wd && (flags & PN_RADIUS_SORTED);
     std::lock_guard<std::mutex> lk(sh->mu);
     if (sh->rank_mode && (sh->world > 1 || sh->exchange_always)) {
-        // One process per GPU (round 4): the local shard answers through the DEVICE entry point (pn_query_radius_device_*:
-        // counts, scan and fill in HBM), its CSR offsets are all-gathered as they lie in HBM, and the lists travel device
-        // to device -- the host sees the gathered offsets once (to size the exchange) and the gathered lists once (to
-        // splice).  Round 3 built a host CSR on every rank first (two stream synchronisations inside pn_query_radius_*)
-        // and uploaded counts and lists again.
+        if (q_row_stride < 0) return set_error(PN_ERR_UNSUPPORTED, "negative row stride");
         Dev &d = sh->devs[0];
         SetGuard g(d.device);
         if (!g.ok) return set_error(PN_ERR_DEVICE, "hipSetDevice(%d) failed", d.device);
-        SPN(acquire_dev(d, d.stream));
-        const size_t W = (size_t)sh->world, qc = q_cols ? q_cols : 1;
-        const pn_index *lix = sh->parts.empty() ? nullptr : sh->parts[0].ix;
-        if (q_row_stride < 0) return set_error(PN_ERR_UNSUPPORTED, "negative row stride");
-        SPN(d.q.ensure(nq * qc * sizeof(T)));
-        if (q_cols) {
-            if (nq == 1 || (size_t)q_row_stride == q_cols)
-                SHIP(hipMemcpyAsync(d.q.p, queries, nq * q_cols * sizeof(T), hipMemcpyHostToDevice, d.stream));
-            else
-                SHIP(hipMemcpy2DAsync(d.q.p, q_cols * sizeof(T), queries, (size_t)q_row_stride * sizeof(T),
-                                      q_cols * sizeof(T), nq, hipMemcpyHostToDevice, d.stream));
-        }
-        // rad_a: [local offsets nq + 1 | total 1 | pad 1 | gathered offsets W (nq + 1)]
-        const size_t no = nq + 1;
-        SPN(d.rad_a.ensure((no + 2 + W * no) * 8));
-        uint64_t *d_off = (uint64_t *)d.rad_a.p, *d_tot = d_off + no, *d_all = d_off + no + 2;
-        size_t cap = d.rad_b.bytes / 8 / (W + 1);      // this rank's share of what rad_b holds already
-        if (cap < nq * 4 + 1024) cap = nq * 4 + 1024;
-        std::vector<uint64_t> all_off(W * no);
-        uint64_t longest = 1;
-        // distances (rad_c): [mine cap | gathered W x dw words], dw = the words of `longest` distances
-        auto dwords = [](uint64_t c) { return (size_t)((c * sizeof(T) + 7) / 8); };
-        for (int attempt = 0;; ++attempt) {
-            SPN(d.rad_b.ensure((cap + W * cap) * 8));
-            if (dist_out) SPN(d.rad_c.ensure((dwords(cap) + W * dwords(cap)) * 8));
-            uint64_t *d_mine = (uint64_t *)d.rad_b.p;
-            if (lix) {
-                if (dist_out)
-                    SPN(ShT<T>::radius_wd_device(lix, (const T *)d.q.p, nq, q_cols, qc, radius, flags, d_off, d_mine,
-                                                 (T *)d.rad_c.p, cap, d_tot, d.stream));
-                else
-                    SPN(ShT<T>::radius_device(lix, (const T *)d.q.p, nq, q_cols, qc, radius, d_off, d_mine, cap, d_tot,
-                                              d.stream));
-            } else {
-                SHIP(hipMemsetAsync(d_off, 0, (no + 1) * 8, d.stream));  // a rank without rows: every list empty
-            }
-            SNCCL(rccl().AllGather(d_off, d_all, no, ncclUint64, d.comm, d.stream));
-            SHIP(hipMemcpyAsync(all_off.data(), d_all, W * no * 8, hipMemcpyDeviceToHost, d.stream));
-            SHIP(hipStreamSynchronize(d.stream));
-            longest = 1;
-            for (size_t r = 0; r < W; ++r) longest = std::max<uint64_t>(longest, all_off[r * no + nq]);
-            if (longest <= cap) break;  // every rank's list fits its buffer (all ranks see the same numbers: same decision)
-            if (attempt) return set_error(PN_ERR_DEVICE, "radius lists changed size between two passes");
-            cap = (size_t)longest;      // some rank overflowed: everybody re-runs with room for the longest list
-        }
-        uint64_t *d_mine = (uint64_t *)d.rad_b.p, *d_lists = d_mine + cap;
-        const size_t dw = dwords(longest);
-        SNCCL(rccl().AllGather(d_mine, d_lists, (size_t)longest, ncclUint64, d.comm, d.stream));
-        if (dist_out)  // (every rank takes this branch alike: the call's arguments decide it)
-            SNCCL(rccl().AllGather(d.rad_c.p, (uint64_t *)d.rad_c.p + dwords(cap), dw, ncclUint64, d.comm, d.stream));
-        std::vector<uint64_t> all_ids((size_t)(W * longest));
-        std::vector<uint64_t> all_d(dist_out ? W * dw : 0);
-        SHIP(hipMemcpyAsync(all_ids.data(), d_lists, (size_t)(W * longest) * 8, hipMemcpyDeviceToHost, d.stream));
-        if (dist_out)
-            SHIP(hipMemcpyAsync(all_d.data(), (uint64_t *)d.rad_c.p + dwords(cap), W * dw * 8, hipMemcpyDeviceToHost,
-                                d.stream));
-        SHIP(hipStreamSynchronize(d.stream));
-        std::vector<const uint64_t *> po(W), pi(W);
-        std::vector<const T *> pd(W, nullptr);
-        for (size_t r = 0; r < W; ++r) {  // the ranks in rank order: shards are ascending row ranges
-            po[r] = all_off.data() + r * no;
-            pi[r] = all_ids.data() + r * longest;
-            if (dist_out) pd[r] = (const T *)(all_d.data() + r * dw);
-        }
-        return radius_splice<T>(nq, po, pi, pd, sorted, offsets, idx_out, dist_out);
+        // (a failure of this rank from here on is carried into the exchange, not returned in front of it)
+        int rc = acquire_dev(d, d.stream);
+        if (rc == PN_OK) rc = upload_queries<T>(d, queries, nq, q_cols, (size_t)q_row_stride, d.stream);
+        size_t cap = d.rad_b.bytes / 8 / ((size_t)sh->world + 1);  // this rank's share of what rad_b holds already
+        RankParts<T> x;
+        SPN(rank_radius_exchange<T>(sh, (const T *)d.q.p, nq, q_cols, q_cols ? q_cols : 1, radius, flags, wd, rc, cap, x));
+        return radius_splice<T>(nq, x.parts, sorted, offsets, idx_out, dist_out);
     }
     const size_t np = sh->parts.size();
     std::vector<std::vector<uint64_t>> offs(np, std::vector<uint64_t>(nq + 1, 0));
@@ -1038,92 +1021,80 @@ static int sharded_query_radius(const pn_sharded *sh, const T *queries, size_t n
     } free_lists{lists, dlists};
     for (size_t i = 0; i < np; ++i)
         if (sh->parts[i].ix) {
-            if (dist_out)
+            if (wd)
                 SPN(ShT<T>::radius_wd(sh->parts[i].ix, queries, nq, q_cols, q_row_stride, radius, flags, offs[i].data(),
                                       &lists[i], &dlists[i]));
             else
                 SPN(ShT<T>::radius(sh->parts[i].ix, queries, nq, q_cols, q_row_stride, radius, offs[i].data(), &lists[i]));
         }
     // local splice: per query, local shards in order (merged by (distance, row) when sorted)
-    std::vector<const uint64_t *> po(np), pi(np);
-    std::vector<const T *> pd(np, nullptr);
-    for (size_t i = 0; i < np; ++i) {
-        po[i] = offs[i].data();
-        pi[i] = lists[i];
-        pd[i] = dlists[i];
-    }
-    return radius_splice<T>(nq, po, pi, pd, sorted, offsets, idx_out, dist_out);
+    std::vector<CsrPart<T>> parts(np);
+    for (size_t i = 0; i < np; ++i) parts[i] = {offs[i].data(), lists[i], dlists[i]};
+    return radius_splice<T>(nq, parts, sorted, offsets, idx_out, dist_out);
 }
 
 // query_radius with queries and CSR in HBM (pn_query_radius_device_*): a handle with ONE shard forwards to it (global row
 // numbers through the shard's index base).  Several shards would need the ragged exchange on the device as well: the
 // host entry point above serves them.
+// (wd: pn_sharded_query_radius_with_distance_device_*, d_dist and flags as pn_query_radius_with_distance_device_*)
 template <typename T>
-// (with_dist: pn_sharded_query_radius_with_distance_device_*, d_dist and flags as pn_query_radius_with_distance_device_*)
 static int sharded_query_radius_device(const pn_sharded *sh, const T *d_q, size_t nq, size_t q_cols, size_t q_stride, T radius,
-                                       uint64_t *d_offsets, uint64_t *d_idx, size_t capacity, uint64_t *d_total, void *stream,
-                                       bool with_dist = false, T *d_dist = nullptr, unsigned flags = 0) {
+                                       bool wd, unsigned flags, uint64_t *d_offsets, uint64_t *d_idx, T *d_dist,
+                                       size_t capacity, uint64_t *d_total, void *stream) {
     if (!sh) return set_error(PN_ERR_INVALID, "handle is NULL");
     SPN(check_elem(sh, sizeof(T)));
     if (sh->n_shards != 1 || sh->parts.size() != 1 || !sh->parts[0].ix)
         return set_error(PN_ERR_UNSUPPORTED, "the device-resident query_radius serves handles with one shard");
-    if (with_dist)
-        return ShT<T>::radius_wd_device(sh->parts[0].ix, d_q, nq, q_cols, q_stride, radius, flags, d_offsets, d_idx, d_dist,
-                                        capacity, d_total, stream);
-    return ShT<T>::radius_device(sh->parts[0].ix, d_q, nq, q_cols, q_stride, radius, d_offsets, d_idx, capacity, d_total, stream);
+    return part_radius_device<T>(sh->parts[0].ix, d_q, nq, q_cols, q_stride, radius, wd, flags, d_offsets, d_idx, d_dist,
+                                 capacity, d_total, stream);
 }
 extern "C" int pn_sharded_query_radius_device_f32(const pn_sharded *sh, const float *d_q, size_t nq, size_t q_cols,
                                                   size_t q_stride, float radius, uint64_t *d_offsets, uint64_t *d_idx,
                                                   size_t capacity, uint64_t *d_total, void *stream) {
-    return sharded_query_radius_device<float>(sh, d_q, nq, q_cols, q_stride, radius, d_offsets, d_idx, capacity, d_total, stream);
+    return sharded_query_radius_device<float>(sh, d_q, nq, q_cols, q_stride, radius, false, 0, d_offsets, d_idx, nullptr,
+                                              capacity, d_total, stream);
 }
 extern "C" int pn_sharded_query_radius_device_f64(const pn_sharded *sh, const double *d_q, size_t nq, size_t q_cols,
                                                   size_t q_stride, double radius, uint64_t *d_offsets, uint64_t *d_idx,
                                                   size_t capacity, uint64_t *d_total, void *stream) {
-    return sharded_query_radius_device<double>(sh, d_q, nq, q_cols, q_stride, radius, d_offsets, d_idx, capacity, d_total, stream);
+    return sharded_query_radius_device<double>(sh, d_q, nq, q_cols, q_stride, radius, false, 0, d_offsets, d_idx, nullptr,
+                                               capacity, d_total, stream);
 }
 extern "C" int pn_sharded_query_radius_with_distance_device_f32(const pn_sharded *sh, const float *d_q, size_t nq,
                                                                 size_t q_cols, size_t q_stride, float radius,
                                                                 unsigned flags, uint64_t *d_offsets, uint64_t *d_idx,
                                                                 float *d_dist, size_t capacity, uint64_t *d_total,
                                                                 void *stream) {
-    return sharded_query_radius_device<float>(sh, d_q, nq, q_cols, q_stride, radius, d_offsets, d_idx, capacity, d_total,
-                                              stream, true, d_dist, flags);
+    return sharded_query_radius_device<float>(sh, d_q, nq, q_cols, q_stride, radius, true, flags, d_offsets, d_idx, d_dist,
+                                              capacity, d_total, stream);
 }
 extern "C" int pn_sharded_query_radius_with_distance_device_f64(const pn_sharded *sh, const double *d_q, size_t nq,
                                                                 size_t q_cols, size_t q_stride, double radius,
                                                                 unsigned flags, uint64_t *d_offsets, uint64_t *d_idx,
                                                                 double *d_dist, size_t capacity, uint64_t *d_total,
                                                                 void *stream) {
-    return sharded_query_radius_device<double>(sh, d_q, nq, q_cols, q_stride, radius, d_offsets, d_idx, capacity, d_total,
-                                               stream, true, d_dist, flags);
-}
-template <typename T>
-static int sharded_query_radius_wd(const pn_sharded *sh, const T *queries, size_t nq, size_t q_cols, ptrdiff_t q_row_stride,
-                                   T radius, unsigned flags, uint64_t *offsets, uint64_t **idx_out, T **dist_out) {
-    if (!dist_out) return set_error(PN_ERR_INVALID, "output pointer is NULL");
-    return sharded_query_radius<T>(sh, queries, nq, q_cols, q_row_stride, radius, offsets, idx_out, dist_out, flags);
+    return sharded_query_radius_device<double>(sh, d_q, nq, q_cols, q_stride, radius, true, flags, d_offsets, d_idx, d_dist,
+                                               capacity, d_total, stream);
 }
 extern "C" int pn_sharded_query_radius_with_distance_f32(const pn_sharded *sh, const float *queries, size_t nq,
                                                          size_t q_cols, ptrdiff_t q_row_stride, float radius,
                                                          unsigned flags, uint64_t *offsets, uint64_t **idx_out,
                                                          float **dist_out) {
-    return sharded_query_radius_wd<float>(sh, queries, nq, q_cols, q_row_stride, radius, flags, offsets, idx_out, dist_out);
+    return sharded_query_radius<float>(sh, queries, nq, q_cols, q_row_stride, radius, true, flags, offsets, idx_out, dist_out);
 }
 extern "C" int pn_sharded_query_radius_with_distance_f64(const pn_sharded *sh, const double *queries, size_t nq,
                                                          size_t q_cols, ptrdiff_t q_row_stride, double radius,
                                                          unsigned flags, uint64_t *offsets, uint64_t **idx_out,
                                                          double **dist_out) {
-    return sharded_query_radius_wd<double>(sh, queries, nq, q_cols, q_row_stride, radius, flags, offsets, idx_out,
-                                           dist_out);
+    return sharded_query_radius<double>(sh, queries, nq, q_cols, q_row_stride, radius, true, flags, offsets, idx_out, dist_out);
 }
 extern "C" int pn_sharded_query_radius_f32(const pn_sharded *sh, const float *queries, size_t nq, size_t q_cols,
                                            ptrdiff_t q_row_stride, float radius, uint64_t *offsets, uint64_t **idx_out) {
-    return sharded_query_radius<float>(sh, queries, nq, q_cols, q_row_stride, radius, offsets, idx_out);
+    return sharded_query_radius<float>(sh, queries, nq, q_cols, q_row_stride, radius, false, 0, offsets, idx_out, nullptr);
 }
 extern "C" int pn_sharded_query_radius_f64(const pn_sharded *sh, const double *queries, size_t nq, size_t q_cols,
                                            ptrdiff_t q_row_stride, double radius, uint64_t *offsets, uint64_t **idx_out) {
-    return sharded_query_radius<double>(sh, queries, nq, q_cols, q_row_stride, radius, offsets, idx_out);
+    return sharded_query_radius<double>(sh, queries, nq, q_cols, q_row_stride, radius, false, 0, offsets, idx_out, nullptr);
 }
 
 // ---------------------------------------------------------------------------
@@ -1138,10 +1109,11 @@ extern "C" int pn_sharded_query_radius_f64(const pn_sharded *sh, const double *q
 //   k-NN:   enqueue_local with k + 1 over the batch, the packed all-gather (+ one status word per GPU), then each GPU
 //           merges only ITS slice of the batch (part pointers offset by rank x c queries) and drops the row's own global
 //           index (knn_self_exclude_kernel).  The merged top-(k + 1) by (distance, global row) is the single index's.
-//   radius: each local shard's device pipeline over the batch; offsets | status all-gathered; the lists (and distances)
-//           padded to the longest, all-gathered; each rank splices its slice on the host, drops the row's own index (it
-//           appears at most once, in its owner's part) and merges the parts by (distance, global row) when sorted.  One
-//           process: the parts' lists are read from every GPU directly, no list exchange.
+//   radius: each local shard's device pipeline over the batch; one process per GPU: the ragged exchange of the radius
+//           section (rank_radius_exchange) over the step's batch; one process: the parts' lists are read from every GPU
+//           directly, no list exchange.  Each rank splices its slice on the host (csr_splice.h), drops the row's own
+//           index (it appears at most once, in its owner's part) and merges the parts by (distance, global row) when
+//           sorted.
 // A rank whose local work fails still enters every collective of the call; the status words make the host entry points
 // fail on every rank after the step's exchange.  The exchange buffers of the call are allocated before its first
 // collective.  One GPU without a forced exchange (virtual shards): no gather, each part's rows are the queries in place.
@@ -1217,24 +1189,8 @@ template <typename T> static ncclDataType_t nccl_type() { return sizeof(T) == 4 
 // ONE all-gather of every local GPU's d.q into its d.sf_rows (grouped when this process drives several GPUs)
 template <typename T>
 static int self_gather_rows(const pn_sharded *sh, uint64_t cs, size_t qs, const std::vector<hipStream_t> &st) {
-    SNCCL(rccl().GroupStart());
-    for (size_t i = 0; i < sh->devs.size(); ++i) {
-        Dev &d = sh->devs[i];
-        ncclResult_t r = rccl().AllGather(d.q.p, d.sf_rows.p, (size_t)cs * qs, nccl_type<T>(), d.comm, st[i]);
-        if (r != ncclSuccess) {
-            (void)rccl().GroupEnd();
-            return set_error(PN_ERR_COMM, "ncclAllGather: %s", rccl().GetErrorString(r));
-        }
-    }
-    SNCCL(rccl().GroupEnd());
-    return PN_OK;
-}
-static void keep_first(int &rc, int r) {
-    if (rc == PN_OK) rc = r;
-}
-static int hip_rc(hipError_t e, const char *what) {
-    if (e == hipSuccess) return PN_OK;
-    return set_error(e == hipErrorOutOfMemory ? PN_ERR_NOMEM : PN_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
+    return all_gather_devs(sh->devs, (size_t)cs * qs, nccl_type<T>(),
+                           [&](Dev &d, size_t i) { return GatherEnds{d.q.p, d.sf_rows.p, st[i]}; });
 }
 
 // k-NN.  device: idx_out / dist_out in HBM of the one GPU, enqueued on `stream`; else host arrays, each step staged in
@@ -1325,16 +1281,8 @@ static int self_knn_run(const pn_sharded *sh, size_t kin, size_t kout, bool incl
             keep_first(rc, hip_rc(hipMemsetAsync((uint64_t *)d.pack[0].p + words, rc == PN_OK ? 0 : 0xFF, 8, st[i]),
                                   "status word"));
         }
-        SNCCL(rccl().GroupStart());
-        for (size_t i = 0; i < devs.size(); ++i) {
-            Dev &d = devs[i];
-            ncclResult_t r = rccl().AllGather(d.pack[0].p, d.gathered[0].p, words + 1, ncclUint64, d.comm, st[i]);
-            if (r != ncclSuccess) {
-                (void)rccl().GroupEnd();
-                return set_error(PN_ERR_COMM, "ncclAllGather: %s", rccl().GetErrorString(r));
-            }
-        }
-        SNCCL(rccl().GroupEnd());
+        SPN(all_gather_devs(devs, words + 1, ncclUint64,
+                            [&](Dev &d, size_t i) { return GatherEnds{d.pack[0].p, d.gathered[0].p, st[i]}; }));
         // this GPU's slice of the batch: queries [rank cs, rank cs + its rows) of every part
         for (size_t i = 0; i < devs.size() && rc == PN_OK; ++i) {
             Dev &d = devs[i];
@@ -1430,47 +1378,20 @@ struct SelfLists {
     std::vector<Piece> pieces;
 };
 }  // namespace
-// rows q0 .. q0 + m of a batch (global rows g0 ..), local rows row0 ..: the parts' lists (part r: offsets po[r], rows
-// pi[r], distances pd[r] or nullptr; ascending rows, or by (distance, row) when sorted) spliced, the row's own index
-// dropped unless include
+// rows q0 .. q0 + m of a batch (global rows g0 ..), local rows row0 ..: the parts' lists (ascending rows, or by
+// (distance, row) when sorted) spliced, the row's own index dropped unless include
 template <typename T>
-static void self_splice(const std::vector<const uint64_t *> &po, const std::vector<const uint64_t *> &pi,
-                        const std::vector<const T *> &pd, size_t q0, uint64_t m, uint64_t g0, uint64_t row0, bool exclude,
+static void self_splice(const std::vector<CsrPart<T>> &parts, size_t q0, uint64_t m, uint64_t g0, uint64_t row0, bool exclude,
                         bool sorted, bool wd, SelfLists<T> &out) {
-    const size_t W = po.size();
     out.pieces.push_back({row0, m, (uint64_t)out.idx.size()});
-    std::vector<uint64_t> cur(W), end(W);
+    std::vector<uint64_t> cur(parts.size());
     for (uint64_t t = 0; t < m; ++t) {
-        const size_t q = q0 + (size_t)t;
         const uint64_t self = g0 + t, before = out.idx.size();
-        auto put = [&](size_t r, uint64_t e) {
-            if (exclude && pi[r][e] == self) return;
-            out.idx.push_back(pi[r][e]);
-            if (wd) out.dist.push_back(pd[r][e]);
-        };
-        if (!sorted) {
-            for (size_t r = 0; r < W; ++r)
-                for (uint64_t e = po[r][q]; e < po[r][q + 1]; ++e) put(r, e);
-        } else {  // W-way merge by (distance, global row), as radius_splice
-            for (size_t r = 0; r < W; ++r) {
-                cur[r] = po[r][q];
-                end[r] = po[r][q + 1];
-            }
-            for (;;) {
-                size_t best = W;
-                for (size_t r = 0; r < W; ++r) {
-                    if (cur[r] == end[r]) continue;
-                    if (best == W) {
-                        best = r;
-                        continue;
-                    }
-                    const T d = pd[r][cur[r]], db = pd[best][cur[best]];
-                    if (d < db || (d == db && pi[r][cur[r]] < pi[best][cur[best]])) best = r;
-                }
-                if (best == W) break;
-                put(best, cur[best]++);
-            }
-        }
+        csr_splice_query(parts.data(), parts.size(), q0 + (size_t)t, sorted, exclude ? &self : nullptr, cur.data(),
+                         [&](size_t r, uint64_t e) {
+                             out.idx.push_back(parts[r].rows[e]);
+                             if (wd) out.dist.push_back(parts[r].dist[e]);
+                         });
         out.cnt[row0 + t] = out.idx.size() - before;
     }
 }
@@ -1491,12 +1412,8 @@ static int self_part_radius(const pn_sharded *sh, int part, const T *batch, size
     for (int attempt = 0;; ++attempt) {
         SPN(d.rad_b.ensure(cap * 8));
         if (wd) SPN(d.rad_c.ensure(cap * sizeof(T)));
-        if (wd)
-            SPN(ShT<T>::radius_wd_device(p.ix, batch, nqb, sh->dim, qs, radius, inner, d_off, (uint64_t *)d.rad_b.p,
-                                         (T *)d.rad_c.p, cap, d_tot, d.stream));
-        else
-            SPN(ShT<T>::radius_device(p.ix, batch, nqb, sh->dim, qs, radius, d_off, (uint64_t *)d.rad_b.p, cap, d_tot,
-                                      d.stream));
+        SPN(part_radius_device<T>(p.ix, batch, nqb, sh->dim, qs, radius, wd, inner, d_off, (uint64_t *)d.rad_b.p,
+                                  (T *)d.rad_c.p, cap, d_tot, d.stream));
         SHIP(hipMemcpyAsync(&total, d_tot, 8, hipMemcpyDeviceToHost, d.stream));
         SHIP(hipStreamSynchronize(d.stream));
         if (total <= cap) break;
@@ -1519,7 +1436,6 @@ static int self_radius_run(const pn_sharded *sh, T radius, unsigned flags, bool 
     const size_t W = (size_t)sh->world, qs = G.qs;
     const bool exclude = !(flags & PN_SELF_INCLUDE), sorted = flags & PN_RADIUS_SORTED;
     const unsigned inner = flags & PN_RADIUS_SORTED;
-    auto dwords = [](uint64_t c) { return (size_t)((c * sizeof(T) + 7) / 8); };
     std::vector<hipStream_t> st(devs.size());
     for (size_t i = 0; i < devs.size(); ++i) {
         Dev &d = devs[i];
@@ -1531,16 +1447,25 @@ static int self_radius_run(const pn_sharded *sh, T radius, unsigned flags, bool 
             SPN(d.q.ensure((size_t)G.c * qs * sizeof(T)));
             SPN(d.sf_rows.ensure(W * (size_t)G.c * qs * sizeof(T)));
         }
-        // rank mode, rad_a: [local offsets no | status 1 | total 1 | gathered W (no + 1)], no = batch + 1
-        if (sh->rank_mode) SPN(d.rad_a.ensure(((W * G.c + 3) + W * (W * G.c + 2)) * 8));
+        if (sh->rank_mode) SPN(d.rad_a.ensure(RadA::words(W, W * (size_t)G.c) * 8));  // (the largest step's)
     }
     std::vector<std::vector<SelfSeg>> segs(devs.size());
     const size_t np = sh->parts.size();
     std::vector<std::vector<uint64_t>> offs(np), lists(np);
     std::vector<std::vector<T>> dl(np);
-    std::vector<const uint64_t *> po, pi;
-    std::vector<const T *> pd;
-    std::vector<uint64_t> all_off, all_ids, all_d;
+    std::vector<CsrPart<T>> parts;
+    // one process: every part's CSR over a batch of nqb queries (batch_of(d): where GPU d holds it), read back
+    auto read_parts = [&](auto &&batch_of, size_t nqb, size_t stride) -> int {
+        parts.assign(np, CsrPart<T>{});
+        for (size_t p = 0; p < np; ++p) {
+            Dev &d = devs[sh->parts[p].dev_slot];
+            SetGuard g(d.device);
+            SPN(self_part_radius<T>(sh, (int)p, batch_of(d), nqb, stride, radius, inner, wd, offs[p], lists[p], dl[p]));
+            parts[p] = {offs[p].data(), lists[p].data(), wd ? dl[p].data() : nullptr};
+        }
+        return PN_OK;
+    };
+    RankParts<T> x;
     size_t cap = 0;  // rank mode: list capacity per rank, from gathered values only (the same on every rank)
     for (uint64_t step = 0; step < G.steps; ++step) {
         const uint64_t p0 = step * G.c, cs = std::min<uint64_t>(G.c, G.most - p0);
@@ -1549,114 +1474,34 @@ static int self_radius_run(const pn_sharded *sh, T radius, unsigned flags, bool 
             for (const SelfSeg &sg : segs[0]) {
                 size_t ld;
                 const T *rows = part_rows<T>(sh, sg.part, &ld) + sg.a * ld;
-                po.assign(np, nullptr);
-                pi.assign(np, nullptr);
-                pd.assign(np, nullptr);
-                for (size_t p = 0; p < np; ++p) {
-                    SetGuard g(devs[0].device);
-                    SPN(self_part_radius<T>(sh, (int)p, rows, (size_t)sg.m, ld, radius, inner, wd, offs[p], lists[p], dl[p]));
-                    po[p] = offs[p].data();
-                    pi[p] = lists[p].data();
-                    pd[p] = wd ? dl[p].data() : nullptr;
-                }
+                SPN(read_parts([&](Dev &) { return rows; }, (size_t)sg.m, ld));
                 const uint64_t g0 = sh->parts[sg.part].lo + sg.a;
-                self_splice<T>(po, pi, pd, 0, sg.m, g0, g0 - G.first, exclude, sorted, wd, out);
+                self_splice<T>(parts, 0, sg.m, g0, g0 - G.first, exclude, sorted, wd, out);
             }
             continue;
         }
-        const size_t nqb = W * (size_t)cs, no = nqb + 1;
+        const size_t nqb = W * (size_t)cs;
         int rc = PN_OK;
         for (size_t i = 0; i < devs.size(); ++i) {
             SetGuard g(devs[i].device);
             keep_first(rc, self_pack_rows<T>(sh, devs[i], segs[i], cs, qs, st[i]));
         }
+        const std::vector<CsrPart<T>> *from = &parts;
         if (!sh->rank_mode) {  // one process: no collective fails halfway for a local reason
             SPN(rc);
             SPN(self_gather_rows<T>(sh, cs, qs, st));
-            po.assign(np, nullptr);
-            pi.assign(np, nullptr);
-            pd.assign(np, nullptr);
-            for (size_t p = 0; p < np; ++p) {
-                Dev &d = devs[sh->parts[p].dev_slot];
-                SetGuard g(d.device);
-                SPN(self_part_radius<T>(sh, (int)p, (const T *)d.sf_rows.p, nqb, qs, radius, inner, wd, offs[p], lists[p],
-                                        dl[p]));
-                po[p] = offs[p].data();
-                pi[p] = lists[p].data();
-                pd[p] = wd ? dl[p].data() : nullptr;
+            SPN(read_parts([](Dev &d) { return (const T *)d.sf_rows.p; }, nqb, qs));
+        } else {  // one process per GPU: the ragged exchange over the step's batch; a failure so far travels in rc
+            SetGuard g(devs[0].device);
+            SPN(self_gather_rows<T>(sh, cs, qs, st));
+            SPN(rank_radius_exchange<T>(sh, (const T *)devs[0].sf_rows.p, nqb, sh->dim, qs, radius, inner, wd, rc, cap, x));
+            from = &x.parts;
+        }
+        for (size_t i = 0; i < devs.size(); ++i)
+            for (const SelfSeg &sg : segs[i]) {
+                const uint64_t g0 = sh->parts[sg.part].lo + sg.a;
+                self_splice<T>(*from, (size_t)devs[i].comm_rank * cs + sg.j, sg.m, g0, g0 - G.first, exclude, sorted, wd, out);
             }
-            for (size_t i = 0; i < devs.size(); ++i)
-                for (const SelfSeg &sg : segs[i]) {
-                    const uint64_t g0 = sh->parts[sg.part].lo + sg.a;
-                    self_splice<T>(po, pi, pd, (size_t)devs[i].comm_rank * cs + sg.j, sg.m, g0, g0 - G.first, exclude,
-                                   sorted, wd, out);
-                }
-            continue;
-        }
-        // one process per GPU: the rank-mode exchange of sharded_query_radius over the step's batch
-        Dev &d = devs[0];
-        SetGuard g(d.device);
-        const hipStream_t s = d.stream;
-        SPN(self_gather_rows<T>(sh, cs, qs, st));
-        const pn_index *lix = sh->parts.empty() ? nullptr : sh->parts[0].ix;
-        uint64_t *d_off = (uint64_t *)d.rad_a.p, *d_tot = d_off + no + 1, *d_all = d_off + no + 2;
-        if (cap < nqb * 4 + 1024) cap = nqb * 4 + 1024;
-        all_off.resize(W * (no + 1));
-        uint64_t longest = 1;
-        for (int attempt = 0;; ++attempt) {
-            int lrc = rc;
-            if (lrc == PN_OK) lrc = d.rad_b.ensure((cap + W * cap) * 8);
-            if (lrc == PN_OK && wd) lrc = d.rad_c.ensure((dwords(cap) + W * dwords(cap)) * 8);
-            if (lrc == PN_OK) {
-                if (!lix)  // a rank without rows: every list empty
-                    lrc = hip_rc(hipMemsetAsync(d_off, 0, no * 8, s), "offsets");
-                else if (wd)
-                    lrc = ShT<T>::radius_wd_device(lix, (const T *)d.sf_rows.p, nqb, sh->dim, qs, radius, inner, d_off,
-                                                   (uint64_t *)d.rad_b.p, (T *)d.rad_c.p, cap, d_tot, s);
-                else
-                    lrc = ShT<T>::radius_device(lix, (const T *)d.sf_rows.p, nqb, sh->dim, qs, radius, d_off,
-                                                (uint64_t *)d.rad_b.p, cap, d_tot, s);
-            }
-            keep_first(rc, lrc);
-            // the status word travels with the offsets: a failed rank still enters the exchange, and all ranks stop
-            SHIP(hipMemsetAsync(d_off + no, rc == PN_OK ? 0 : 0xFF, 8, s));
-            SNCCL(rccl().AllGather(d_off, d_all, no + 1, ncclUint64, d.comm, s));
-            SHIP(hipMemcpyAsync(all_off.data(), d_all, W * (no + 1) * 8, hipMemcpyDeviceToHost, s));
-            SHIP(hipStreamSynchronize(s));
-            if (rc != PN_OK) return rc;
-            longest = 1;
-            for (size_t r = 0; r < W; ++r) {
-                if (all_off[r * (no + 1) + no])
-                    return set_error(PN_ERR_DEVICE, "self-query: rank %zu failed in its local work", r);
-                longest = std::max<uint64_t>(longest, all_off[r * (no + 1) + nqb]);
-            }
-            if (longest <= cap) break;  // every rank's lists fit (all ranks see the same numbers: same decision)
-            if (attempt) return set_error(PN_ERR_DEVICE, "radius lists changed size between two passes");
-            cap = (size_t)longest;  // some rank overflowed: everybody re-runs with room for the longest
-        }
-        uint64_t *d_mine = (uint64_t *)d.rad_b.p, *d_lists = d_mine + cap;
-        const size_t dw = dwords(longest);
-        SNCCL(rccl().AllGather(d_mine, d_lists, (size_t)longest, ncclUint64, d.comm, s));
-        if (wd)  // (every rank alike: the call's arguments decide it)
-            SNCCL(rccl().AllGather(d.rad_c.p, (uint64_t *)d.rad_c.p + dwords(cap), dw, ncclUint64, d.comm, s));
-        all_ids.resize((size_t)(W * longest));
-        all_d.resize(wd ? W * dw : 0);
-        SHIP(hipMemcpyAsync(all_ids.data(), d_lists, (size_t)(W * longest) * 8, hipMemcpyDeviceToHost, s));
-        if (wd)
-            SHIP(hipMemcpyAsync(all_d.data(), (uint64_t *)d.rad_c.p + dwords(cap), W * dw * 8, hipMemcpyDeviceToHost, s));
-        SHIP(hipStreamSynchronize(s));
-        po.assign(W, nullptr);
-        pi.assign(W, nullptr);
-        pd.assign(W, nullptr);
-        for (size_t r = 0; r < W; ++r) {  // the ranks in rank order: shards are ascending row ranges
-            po[r] = all_off.data() + r * (no + 1);
-            pi[r] = all_ids.data() + r * longest;
-            if (wd) pd[r] = (const T *)(all_d.data() + r * dw);
-        }
-        for (const SelfSeg &sg : segs[0]) {
-            const uint64_t g0 = sh->parts[sg.part].lo + sg.a;
-            self_splice<T>(po, pi, pd, (size_t)d.comm_rank * cs + sg.j, sg.m, g0, g0 - G.first, exclude, sorted, wd, out);
-        }
     }
     return PN_OK;
 }

@@ -177,6 +177,42 @@ def test_rank_entry_at_world_size_one(pn, dtype):
     sh.close()
 
 
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_rank_radius_and_self_radius_share_one_handle(pn, dtype):
+    """query_radius over a batch and query_radius_self go through ONE ragged exchange (rank_radius_exchange) and its
+    buffers: in turn on one rank handle at world size 1 with the exchange forced, each answer the single index's bit for
+    bit.  (a) overflows the starting capacity 40 x 4 + 1024 and re-runs, (b) fits and reuses the grown buffers, (c) is
+    the self-query's longer record and its own capacity, (d) is (a) again after it.
+    Not verified here: a rank that fails (the status word's failing branch needs a second rank)."""
+    import torch
+    from petal_neighbors_amd import _lib
+    n, nq = 3000, 40
+    pts = uniform((n, 8), 91, dtype)
+    qs = uniform((nq, 8), 92, dtype)
+    one = _single(pn, pts)
+    _, d = one.query_batch(qs, 40)
+    r_a, r_b = dtype(np.median(d[:, 39])), dtype(np.median(d[:, 4]))
+    _, ds = one.query_self(20)
+    r_c = dtype(np.median(ds[:, 19]))
+    sh = pn.ShardedIndex.from_rank_device(torch.from_numpy(pts).to("cuda:0"), n, 0, 1, pn.ShardedIndex.unique_id(), 0)
+    sh.set_option(_lib.PN_OPT_EXCHANGE_ALWAYS, 1)
+
+    def call_a(what):
+        want = one.query_radius_with_distance_batch(qs, r_a, sort=True)
+        assert int(want[0][-1]) > nq * 4 + 1024, "the first attempt must overflow"
+        _same_csr(sh.query_radius_with_distance_batch(qs, r_a, sort=True), want, what)
+
+    call_a("(a) sorted with distances, retried")
+    wo, wi = one.query_radius_batch(qs, r_b)
+    assert 0 < int(wo[-1]) <= nq * 4 + 1024, "the second call must fit"
+    go, gi = sh.query_radius_batch(qs, r_b)
+    _same_csr((go, gi, None), (wo, wi, None), "(b) rows only, fits")
+    _same_csr(sh.query_radius_self(r_c, with_distance=True, sort=True), one.query_radius_self(r_c, with_distance=True, sort=True),
+              "(c) self, sorted with distances")
+    call_a("(d) as (a), after the self-query")
+    sh.close()
+
+
 def test_radius_flags_and_edges(pn):
     from petal_neighbors_amd import _lib
     pts = uniform((3000, 10), 71)
