@@ -9,6 +9,7 @@ pub const PN_SELF_INCLUDE: c_uint = 2;
 /// `flags` of pn_mean_shift_*: the indexed rows are the seeds / of pn_mean_shift_labels_*: rows beyond h of every centre get -1
 pub const PN_MS_SEED_ROWS: c_uint = 4;
 pub const PN_MS_ORPHANS: c_uint = 8;
+pub const PN_KNN_WEIGHT_DISTANCE: c_uint = 1;
 /// `kernel` of the pn_kde_* calls
 pub const PN_KDE_GAUSSIAN: c_int = 0;
 pub const PN_KDE_TOPHAT: c_int = 1;
@@ -180,6 +181,49 @@ extern "C" {
     pub fn pn_lof_score_device_f64(index: *const pn_index, d_queries: *const f64, nq: usize, q_cols: usize,
                                    q_row_stride: usize, k: usize, d_lrd: *const f64, d_kdist: *const f64, flags: c_uint,
                                    d_score: *mut f64, stream: *mut c_void) -> c_int;
+    /// k-NN classification: pred [nq] int64 (required; -1 = a list with a NaN distance or a label out of range), proba
+    /// [nq][n_classes] f64 (nullable); labels [n] int64 codes in [0, n_classes); flags = 0 or PN_KNN_WEIGHT_DISTANCE (1);
+    /// 1 <= k <= min(n, 1024).  The _self entries predict every indexed row from its k nearest other rows, k <= n - 1.
+    /// The device entry points never wait
+    pub fn pn_knn_classify_f32(index: *const pn_index, queries: *const f32, nq: usize, q_cols: usize, q_row_stride: isize,
+                               k: usize, labels: *const i64, n_classes: usize, flags: c_uint, pred_out: *mut i64,
+                               proba_out: *mut f64) -> c_int;
+    pub fn pn_knn_classify_f64(index: *const pn_index, queries: *const f64, nq: usize, q_cols: usize, q_row_stride: isize,
+                               k: usize, labels: *const i64, n_classes: usize, flags: c_uint, pred_out: *mut i64,
+                               proba_out: *mut f64) -> c_int;
+    pub fn pn_knn_classify_device_f32(index: *const pn_index, d_queries: *const f32, nq: usize, q_cols: usize,
+                                      q_row_stride: usize, k: usize, d_labels: *const i64, n_classes: usize, flags: c_uint,
+                                      d_pred: *mut i64, d_proba: *mut f64, stream: *mut c_void) -> c_int;
+    pub fn pn_knn_classify_device_f64(index: *const pn_index, d_queries: *const f64, nq: usize, q_cols: usize,
+                                      q_row_stride: usize, k: usize, d_labels: *const i64, n_classes: usize, flags: c_uint,
+                                      d_pred: *mut i64, d_proba: *mut f64, stream: *mut c_void) -> c_int;
+    pub fn pn_knn_classify_self_f32(index: *const pn_index, k: usize, labels: *const i64, n_classes: usize, flags: c_uint,
+                                    pred_out: *mut i64, proba_out: *mut f64) -> c_int;
+    pub fn pn_knn_classify_self_f64(index: *const pn_index, k: usize, labels: *const i64, n_classes: usize, flags: c_uint,
+                                    pred_out: *mut i64, proba_out: *mut f64) -> c_int;
+    pub fn pn_knn_classify_self_device_f32(index: *const pn_index, k: usize, d_labels: *const i64, n_classes: usize,
+                                           flags: c_uint, d_pred: *mut i64, d_proba: *mut f64, stream: *mut c_void) -> c_int;
+    pub fn pn_knn_classify_self_device_f64(index: *const pn_index, k: usize, d_labels: *const i64, n_classes: usize,
+                                           flags: c_uint, d_pred: *mut i64, d_proba: *mut f64, stream: *mut c_void) -> c_int;
+    /// k-NN regression: out [nq][n_out] f64 (required) from targets [n][n_out] f64; flags, k and the _self entries as above
+    pub fn pn_knn_regress_f32(index: *const pn_index, queries: *const f32, nq: usize, q_cols: usize, q_row_stride: isize,
+                              k: usize, targets: *const f64, n_out: usize, flags: c_uint, out: *mut f64) -> c_int;
+    pub fn pn_knn_regress_f64(index: *const pn_index, queries: *const f64, nq: usize, q_cols: usize, q_row_stride: isize,
+                              k: usize, targets: *const f64, n_out: usize, flags: c_uint, out: *mut f64) -> c_int;
+    pub fn pn_knn_regress_device_f32(index: *const pn_index, d_queries: *const f32, nq: usize, q_cols: usize,
+                                     q_row_stride: usize, k: usize, d_targets: *const f64, n_out: usize, flags: c_uint,
+                                     d_out: *mut f64, stream: *mut c_void) -> c_int;
+    pub fn pn_knn_regress_device_f64(index: *const pn_index, d_queries: *const f64, nq: usize, q_cols: usize,
+                                     q_row_stride: usize, k: usize, d_targets: *const f64, n_out: usize, flags: c_uint,
+                                     d_out: *mut f64, stream: *mut c_void) -> c_int;
+    pub fn pn_knn_regress_self_f32(index: *const pn_index, k: usize, targets: *const f64, n_out: usize, flags: c_uint,
+                                   out: *mut f64) -> c_int;
+    pub fn pn_knn_regress_self_f64(index: *const pn_index, k: usize, targets: *const f64, n_out: usize, flags: c_uint,
+                                   out: *mut f64) -> c_int;
+    pub fn pn_knn_regress_self_device_f32(index: *const pn_index, k: usize, d_targets: *const f64, n_out: usize,
+                                          flags: c_uint, d_out: *mut f64, stream: *mut c_void) -> c_int;
+    pub fn pn_knn_regress_self_device_f64(index: *const pn_index, k: usize, d_targets: *const f64, n_out: usize,
+                                          flags: c_uint, d_out: *mut f64, stream: *mut c_void) -> c_int;
     /// OPTICS of the indexed rows: ordering [n] (row numbers, no index base) and reachability [n] required, predecessor [n]
     /// and core_distances [n] nullable; min_samples counts other rows, 1 <= min_samples <= n - 1; flags = 0.  The device
     /// entry points write in stream order and block the host once

@@ -62,7 +62,9 @@ extern "C" {
  * pn_sharded_query_radius_self_{,device_}{f32,f64}; pn_query_radii_{,device_,self_,self_device_}{f32,f64};
  * pn_dbscan_{,device_}{f32,f64}, PN_OPT_DBSCAN_PIECE; pn_mst_{,device_}{f32,f64}, PN_OPT_MST_BATCH;
  * pn_linkage_{,device_}{f32,f64}, pn_hdbscan_{,device_}{f32,f64}; pn_lof_{,device_}{f32,f64},
- * pn_lof_score_{,device_}{f32,f64}; pn_optics_{,device_}{f32,f64}, pn_optics_dbscan_{,device_}{f32,f64},
+ * pn_lof_score_{,device_}{f32,f64}; pn_knn_classify_{,device_,self_,self_device_}{f32,f64},
+ * pn_knn_regress_{,device_,self_,self_device_}{f32,f64}, PN_KNN_WEIGHT_DISTANCE;
+ * pn_optics_{,device_}{f32,f64}, pn_optics_dbscan_{,device_}{f32,f64},
  * PN_OPT_OPTICS_PIECE; pn_kde_{,device_,self_,self_device_}{f32,f64}, PN_KDE_*, PN_OPT_KDE_PIECE;
  * pn_mean_shift_{,device_,merge_,merge_device_,labels_,labels_device_}{f32,f64}, PN_MS_*, PN_OPT_MS_PIECE;
  * pn_kmeans_{,device_}{f32,f64}, pn_kmeans_assign_{,device_}{f32,f64}, pn_kmeans_bounds_f32,
@@ -595,6 +597,91 @@ int pn_lof_score_device_f32(const pn_index *index, const float *d_queries, size_
 int pn_lof_score_device_f64(const pn_index *index, const double *d_queries, size_t nq, size_t q_cols, size_t q_row_stride,
                             size_t k, const double *d_lrd, const double *d_kdist, unsigned flags, double *d_score,
                             void *stream);
+
+/* ---- k-NN classification and regression on the device (scikit-learn's neighbors.KNeighborsClassifier and
+ * KNeighborsRegressor with n_neighbors = k, and their leave-one-out forms): the k-NN query -> one vote or one weighted
+ * mean per list, in HBM.  Neither the [nq][k] lists nor the labels leave the device; nothing leaves HBM but the outputs.
+ * The list of a query is (j_0 .. j_{k-1}, d_0 .. d_{k-1}): for new points (pn_knn_classify_*, pn_knn_regress_*) its answer
+ * from pn_query_*(q, k); for the _self entries row i's answer from pn_query_self_*(k) with flags 0, where k counts OTHER
+ * rows and the row itself is left out (leave-one-out).  The list is ordered by (distance, index), NaN last; ids are taken
+ * without the index base (PN_OPT_INDEX_BASE affects no output).  The contract, all arithmetic in IEEE f64, unfused; every
+ * sum is the sequential fold in list order, starting from 0.0:
+ *   Poison rule: if any d_t is NaN -- or, classifying, any gathered label labels[j_t] is outside [0, n_classes) -- the list
+ *     is answered with pred = `-1`, a proba row of NaN and a regression row of NaN, under both weightings.
+ *   Clamp: v_t = d_t > 0 ? (double)d_t : +0.0.  A Cosine distance a few ulp below 0 counts as 0, as in pn_lof_*.
+ *   Weights: flags = 0 (uniform): w_t = 1.0.  flags = PN_KNN_WEIGHT_DISTANCE: if some v_t == 0 then
+ *     w_t = (v_t == 0) ? 1.0 : 0.0, otherwise w_t = 1.0 / v_t -- scikit-learn's _get_weights rule: a list that holds a
+ *     zero distance counts its zero-distance entries alone.  An infinite distance weighs 0.
+ *   Normaliser: S = (...((0.0 + w_0) + w_1) ... + w_{k-1}); under uniform weights this is exactly k.
+ *   Classification: labels is int64 [n], class codes in [0, n_classes).  W_c = 0.0 + the w_t of the entries with
+ *     labels[j_t] == c, added in list order.  pred = the c with the largest W_c; ties go to the smallest c
+ *     (scikit-learn's weighted_mode / argmax behaviour).  The prediction is taken on the unnormalised W_c, so it never
+ *     depends on the division.  proba[q][c] = W_c / S, 0.0 for a class that is not in the list: a dense double
+ *     [nq][n_classes] output, optional -- NULL: neither computed nor written.
+ *     Where this differs from scikit-learn's predict_proba: their normaliser sums the class row W_0 .. W_{C-1} with NumPy's
+ *     pairwise shape, ours is the list-order S; the difference is a few ulp (none under uniform weights, where both are k).
+ *   Regression: targets is double [n][n_out], contiguous, n_out >= 1.  out[q][o] = N_o / S with
+ *     N_o = (...((0.0 + w_0 * y[j_0][o]) + w_1 * y[j_1][o]) ... ): each product rounded before its addition.  Inf or NaN in
+ *     a target propagates by IEEE rules; with the zero-distance rule 0 * inf is NaN, as in scikit-learn.
+ * The result depends on the data alone: the k-NN answer is unique and fixes the order of every sum; the winner is found by
+ * comparisons on (W_c descending, c ascending), which no order of evaluation changes; there are no floating-point atomics
+ * and no reduction whose shape depends on the launch.
+ * Limits: new points 1 <= k <= n; _self entries 1 <= k <= n - 1 and n >= 2; k > 1024: PN_ERR_UNSUPPORTED for both
+ * families (the class sums compare every list entry with every other); 1 <= n_classes <= 2^31 - 1; more than 2^31 - 1 rows:
+ * PN_ERR_UNSUPPORTED, as pn_lof_*.  Euclidean and Cosine indexes, f32 and f64.
+ * Labels: the host entries scan labels before touching the device and return PN_ERR_INVALID naming the first offending
+ * position and value.  The device entries cannot scan without waiting: they rely on the poison rule, and a label out of
+ * range never causes an out-of-bounds store.
+ * Argument errors, before any device is touched and in this order, the same in the host and device entries: unknown flags;
+ * NULL pred_out (classification) / out (regression); with nq > 0 (the _self entries: always) the first NULL input, named
+ * (queries, then labels or targets); NULL index; wrong element type; n_classes / n_out out of range; k out of range: all
+ * PN_ERR_INVALID; k > 1024, then too many rows: PN_ERR_UNSUPPORTED; the host entries' label scan.  nq = 0 writes nothing and
+ * returns PN_OK after the checks.
+ * pn_stats.queries advances by nq for new points and by n for the _self entries.
+ * Host entry points: strides as pn_lof_score_*; they wait once, for their final copy.  Device entry points: queries, labels
+ * or targets and the outputs in HBM (d_pred int64 [nq], d_proba double [nq][n_classes] or NULL, d_out double [nq][n_out]),
+ * everything enqueued on `stream`; the call never waits for the device.
+ * Device memory beyond a 2^18-query batch's workspace and its k-NN answer: the host entries' labels or targets and outputs.
+ * Not in this version: row-sharded handles, radius-neighbour voting, callable weights, multi-label classification. */
+#define PN_KNN_WEIGHT_DISTANCE 1u /* flags of pn_knn_classify_* / pn_knn_regress_*: weigh each neighbour by 1 / distance */
+int pn_knn_classify_f32(const pn_index *index, const float *queries, size_t nq, size_t q_cols, ptrdiff_t q_row_stride,
+                        size_t k, const int64_t *labels, size_t n_classes, unsigned flags, int64_t *pred_out,
+                        double *proba_out);
+int pn_knn_classify_f64(const pn_index *index, const double *queries, size_t nq, size_t q_cols, ptrdiff_t q_row_stride,
+                        size_t k, const int64_t *labels, size_t n_classes, unsigned flags, int64_t *pred_out,
+                        double *proba_out);
+int pn_knn_classify_device_f32(const pn_index *index, const float *d_queries, size_t nq, size_t q_cols,
+                               size_t q_row_stride, size_t k, const int64_t *d_labels, size_t n_classes, unsigned flags,
+                               int64_t *d_pred, double *d_proba, void *stream);
+int pn_knn_classify_device_f64(const pn_index *index, const double *d_queries, size_t nq, size_t q_cols,
+                               size_t q_row_stride, size_t k, const int64_t *d_labels, size_t n_classes, unsigned flags,
+                               int64_t *d_pred, double *d_proba, void *stream);
+int pn_knn_classify_self_f32(const pn_index *index, size_t k, const int64_t *labels, size_t n_classes, unsigned flags,
+                             int64_t *pred_out, double *proba_out);
+int pn_knn_classify_self_f64(const pn_index *index, size_t k, const int64_t *labels, size_t n_classes, unsigned flags,
+                             int64_t *pred_out, double *proba_out);
+int pn_knn_classify_self_device_f32(const pn_index *index, size_t k, const int64_t *d_labels, size_t n_classes,
+                                    unsigned flags, int64_t *d_pred, double *d_proba, void *stream);
+int pn_knn_classify_self_device_f64(const pn_index *index, size_t k, const int64_t *d_labels, size_t n_classes,
+                                    unsigned flags, int64_t *d_pred, double *d_proba, void *stream);
+int pn_knn_regress_f32(const pn_index *index, const float *queries, size_t nq, size_t q_cols, ptrdiff_t q_row_stride,
+                       size_t k, const double *targets, size_t n_out, unsigned flags, double *out);
+int pn_knn_regress_f64(const pn_index *index, const double *queries, size_t nq, size_t q_cols, ptrdiff_t q_row_stride,
+                       size_t k, const double *targets, size_t n_out, unsigned flags, double *out);
+int pn_knn_regress_device_f32(const pn_index *index, const float *d_queries, size_t nq, size_t q_cols, size_t q_row_stride,
+                              size_t k, const double *d_targets, size_t n_out, unsigned flags, double *d_out,
+                              void *stream);
+int pn_knn_regress_device_f64(const pn_index *index, const double *d_queries, size_t nq, size_t q_cols, size_t q_row_stride,
+                              size_t k, const double *d_targets, size_t n_out, unsigned flags, double *d_out,
+                              void *stream);
+int pn_knn_regress_self_f32(const pn_index *index, size_t k, const double *targets, size_t n_out, unsigned flags,
+                            double *out);
+int pn_knn_regress_self_f64(const pn_index *index, size_t k, const double *targets, size_t n_out, unsigned flags,
+                            double *out);
+int pn_knn_regress_self_device_f32(const pn_index *index, size_t k, const double *d_targets, size_t n_out, unsigned flags,
+                                   double *d_out, void *stream);
+int pn_knn_regress_self_device_f64(const pn_index *index, size_t k, const double *d_targets, size_t n_out, unsigned flags,
+                                   double *d_out, void *stream);
 
 /* ---- OPTICS on the device (scikit-learn's cluster.OPTICS with metric = this index's, min_samples = this library's + 1):
  * the ordering, the reachability plot, predecessors and core distances of the indexed rows, and the DBSCAN labelling at

@@ -117,6 +117,12 @@ struct Lof {
     std::vector<double> lof, lrd;
     std::vector<A> kdist;
 };
+// the answer of BallTree::knn_classify: pred[q] = the winning class code (-1: a poisoned list, one with a NaN distance);
+// proba [nq][n_classes] row-major, empty unless asked for
+struct KnnClasses {
+    std::vector<int64_t> pred;
+    std::vector<double> proba;
+};
 // the answer of BallTree::kernel_density: per query the raw kernel sum (not normalised), the number of terms and the
 // cutoff radius the terms were taken within
 template <typename A>
@@ -451,6 +457,70 @@ class BallTree {
         else
             check(pn_lof_score_f64(h_, queries, nq, dim_, (ptrdiff_t)dim_, k, fit.lrd.data(), fit.kdist.data(), 0u, out));
         return score;
+    }
+    // extension: k-NN classification on the device (pn_knn_classify_*): scikit-learn's KNeighborsClassifier(n_neighbors = k).
+    // labels: one class code in [0, n_classes) per indexed row; distance_weights: 1 / distance instead of uniform weights;
+    // with_proba: also the class shares [nq][n_classes].  pred[q] = -1 for a poisoned list (a NaN distance; labels out of range are refused)
+    KnnClasses knn_classify(const A *queries, size_t nq, size_t k, const std::vector<int64_t> &labels, size_t n_classes,
+                            bool distance_weights = false, bool with_proba = false) const {
+        if (labels.size() != n_) throw std::invalid_argument("knn_classify: one label per indexed row");
+        KnnClasses res;
+        res.pred.resize(nq);
+        if (with_proba) res.proba.resize(nq * n_classes);
+        int64_t none = 0;  // (nq = 0: the library still wants an address)
+        const unsigned flags = distance_weights ? PN_KNN_WEIGHT_DISTANCE : 0u;
+        if constexpr (kF32)
+            check(pn_knn_classify_f32(h_, queries, nq, dim_, (ptrdiff_t)dim_, k, labels.data(), n_classes, flags,
+                                      nq ? res.pred.data() : &none, with_proba ? res.proba.data() : nullptr));
+        else
+            check(pn_knn_classify_f64(h_, queries, nq, dim_, (ptrdiff_t)dim_, k, labels.data(), n_classes, flags,
+                                      nq ? res.pred.data() : &none, with_proba ? res.proba.data() : nullptr));
+        return res;
+    }
+    // the same for every indexed row from its k nearest OTHER rows (leave-one-out), 1 <= k <= size() - 1
+    KnnClasses knn_classify_self(size_t k, const std::vector<int64_t> &labels, size_t n_classes, bool distance_weights = false,
+                                 bool with_proba = false) const {
+        if (labels.size() != n_) throw std::invalid_argument("knn_classify_self: one label per indexed row");
+        KnnClasses res;
+        res.pred.resize(n_);
+        if (with_proba) res.proba.resize(n_ * n_classes);
+        const unsigned flags = distance_weights ? PN_KNN_WEIGHT_DISTANCE : 0u;
+        if constexpr (kF32)
+            check(pn_knn_classify_self_f32(h_, k, labels.data(), n_classes, flags, res.pred.data(),
+                                           with_proba ? res.proba.data() : nullptr));
+        else
+            check(pn_knn_classify_self_f64(h_, k, labels.data(), n_classes, flags, res.pred.data(),
+                                           with_proba ? res.proba.data() : nullptr));
+        return res;
+    }
+    // extension: k-NN regression on the device (pn_knn_regress_*): scikit-learn's KNeighborsRegressor(n_neighbors = k).
+    // targets: [size()][n_out] row-major; the answer is [nq][n_out]
+    std::vector<double> knn_regress(const A *queries, size_t nq, size_t k, const std::vector<double> &targets, size_t n_out,
+                                    bool distance_weights = false) const {
+        if (n_out == 0 || targets.size() != n_ * n_out)
+            throw std::invalid_argument("knn_regress: targets must hold n_out >= 1 values per indexed row");
+        std::vector<double> out(nq * n_out);
+        double none = 0.0;
+        const unsigned flags = distance_weights ? PN_KNN_WEIGHT_DISTANCE : 0u;
+        if constexpr (kF32)
+            check(pn_knn_regress_f32(h_, queries, nq, dim_, (ptrdiff_t)dim_, k, targets.data(), n_out, flags,
+                                     nq ? out.data() : &none));
+        else
+            check(pn_knn_regress_f64(h_, queries, nq, dim_, (ptrdiff_t)dim_, k, targets.data(), n_out, flags,
+                                     nq ? out.data() : &none));
+        return out;
+    }
+    std::vector<double> knn_regress_self(size_t k, const std::vector<double> &targets, size_t n_out,
+                                         bool distance_weights = false) const {
+        if (n_out == 0 || targets.size() != n_ * n_out)
+            throw std::invalid_argument("knn_regress_self: targets must hold n_out >= 1 values per indexed row");
+        std::vector<double> out(n_ * n_out);
+        const unsigned flags = distance_weights ? PN_KNN_WEIGHT_DISTANCE : 0u;
+        if constexpr (kF32)
+            check(pn_knn_regress_self_f32(h_, k, targets.data(), n_out, flags, out.data()));
+        else
+            check(pn_knn_regress_self_f64(h_, k, targets.data(), n_out, flags, out.data()));
+        return out;
     }
     // extension: kernel density sums on the device (pn_kde_*): per query the raw sum of `kernel` (PN_KDE_*) with bandwidth
     // h over the rows within the kernel's cutoff, in a fixed order; atol lets the two smooth kernels stop at a finite

@@ -33,6 +33,7 @@ PN_RADIUS_SORTED = 1
 PN_SELF_INCLUDE = 2
 PN_MS_SEED_ROWS = 4
 PN_MS_ORPHANS = 8
+PN_KNN_WEIGHT_DISTANCE = 1
 
 
 class PnInfo(C.Structure):
@@ -100,6 +101,14 @@ PAIRED = {
     "pn_lof_device": (_i, [_vp, _sz, _cu] + [_vp] * 4),
     "pn_lof_score": (_i, _QH + [_sz, _vp, _vp, _cu, _vp]),
     "pn_lof_score_device": (_i, _QD + [_sz, _vp, _vp, _cu, _vp, _vp]),
+    "pn_knn_classify": (_i, _QH + [_sz, _vp, _sz, _cu, _vp, _vp]),
+    "pn_knn_classify_device": (_i, _QD + [_sz, _vp, _sz, _cu] + [_vp] * 3),
+    "pn_knn_classify_self": (_i, [_vp, _sz, _vp, _sz, _cu, _vp, _vp]),
+    "pn_knn_classify_self_device": (_i, [_vp, _sz, _vp, _sz, _cu] + [_vp] * 3),
+    "pn_knn_regress": (_i, _QH + [_sz, _vp, _sz, _cu, _vp]),
+    "pn_knn_regress_device": (_i, _QD + [_sz, _vp, _sz, _cu, _vp, _vp]),
+    "pn_knn_regress_self": (_i, [_vp, _sz, _vp, _sz, _cu, _vp]),
+    "pn_knn_regress_self_device": (_i, [_vp, _sz, _vp, _sz, _cu, _vp, _vp]),
     "pn_kde": (_i, _QH + [_vp, _sz, _i, _d, _cu] + [_vp] * 3),
     "pn_kde_device": (_i, _QD + [_vp, _sz, _i, _d, _cu] + [_vp] * 4),
     "pn_kde_self": (_i, [_vp, _vp, _sz, _i, _d, _cu] + [_vp] * 3),

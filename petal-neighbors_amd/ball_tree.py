@@ -32,6 +32,7 @@ def _float_array(a):
 
 KDE_KERNELS = {"gaussian": _lib.PN_KDE_GAUSSIAN, "tophat": _lib.PN_KDE_TOPHAT, "epanechnikov": _lib.PN_KDE_EPANECHNIKOV,
                "exponential": _lib.PN_KDE_EXPONENTIAL, "linear": _lib.PN_KDE_LINEAR}
+KNN_WEIGHTS = {"uniform": 0, "distance": _lib.PN_KNN_WEIGHT_DISTANCE}
 
 
 def _log_vn(d):
@@ -479,6 +480,173 @@ class BallTree(Handle):
             check(self._fn("lof_score_device")(self._h, ptr, nq, qc, ld, k, lrd.data_ptr(), kdist.data_ptr(), 0,
                                                scores.data_ptr(), stream_arg(stream, q.device)))
         return scores
+
+    # ------------------------------------------- k-NN classification and regression
+    # scikit-learn's ``KNeighborsClassifier`` / ``KNeighborsRegressor(n_neighbors=k, weights=...)`` on the device
+    # (``pn_knn_classify_*`` / ``pn_knn_regress_*``): the k-NN query, then one vote or one weighted mean per list in HBM; the
+    # ``_self`` methods predict every indexed row from its k nearest OTHER rows (leave-one-out).  Every sum runs in list
+    # order, so the result depends on the data alone (the header has the contract).
+    def _knn_k(self, k, leave_one_out):
+        k, top = int(k), self._n - 1 if leave_one_out else self._n
+        if k < 1 or k > top:
+            raise ValueError(f"k must be in [1, {'n - 1' if leave_one_out else 'n'}] = [1, {top}]")
+        if k > 1024:
+            raise ValueError("k-NN prediction serves k <= 1024")
+        return k
+
+    @staticmethod
+    def _knn_flags(weights):
+        if not isinstance(weights, str) or weights not in KNN_WEIGHTS:
+            raise ValueError(f"weights must be one of {sorted(KNN_WEIGHTS)}, not {weights!r}")
+        return KNN_WEIGHTS[weights]
+
+    def _knn_labels(self, labels):
+        """``(classes, codes int64 [n])`` of any 1-D array of one label per indexed row"""
+        a = np.asarray(labels)
+        if a.ndim != 1 or a.shape[0] != self._n:
+            raise ValueError(f"labels must be 1-D with one label per indexed row ({self._n})")
+        classes, codes = np.unique(a, return_inverse=True)
+        return classes, np.ascontiguousarray(codes.reshape(-1), dtype=np.int64)
+
+    def _knn_targets(self, targets):
+        """``(y float64 [n, n_out], one_d)`` of ``[n]`` or ``[n, n_out]`` targets of any real dtype"""
+        y = np.asarray(targets)
+        if y.ndim not in (1, 2) or y.shape[0] != self._n or (y.ndim == 2 and y.shape[1] < 1):
+            raise ValueError(f"targets must be [n] or [n, n_out >= 1] with one row per indexed row ({self._n})")
+        if y.dtype.kind not in "fiub":
+            raise ValueError(f"targets must be real numbers, not {y.dtype}")
+        return np.ascontiguousarray(y.reshape(self._n, -1), dtype=np.float64), y.ndim == 1
+
+    def _knn_n_classes(self, n_classes):
+        c = int(n_classes)
+        if c < 1 or c > 2 ** 31 - 1:
+            raise ValueError("n_classes must be in [1, 2^31 - 1]")
+        return c
+
+    @staticmethod
+    def _knn_decode(pred, pr, classes, proba):
+        bad = int(np.count_nonzero(pred < 0))
+        if bad:
+            raise ValueError(f"{bad} of {len(pred)} lists are poisoned (a NaN distance): they have no prediction")
+        out = classes[pred]
+        return (out, pr, classes) if proba else out
+
+    def knn_classify(self, queries, k: int, labels, weights: str = "uniform", proba: bool = False):
+        """The class of every row of ``queries`` by the vote of its ``k`` nearest indexed rows.  ``labels``: any 1-D array
+        of one label per indexed row; ``weights``: ``"uniform"`` or ``"distance"`` (1 / distance; a zero distance counts
+        alone).  Returns the predictions in ``labels``' dtype -- ties go to the smallest class -- or, with ``proba=True``,
+        ``(pred, proba float64 [nq, n_classes], classes)``, the columns of ``proba`` in the order of ``classes``."""
+        k, flags = self._knn_k(k, False), self._knn_flags(weights)
+        classes, codes = self._knn_labels(labels)
+        a = self._queries(queries, False)
+        nq, qc = a.shape
+        pred = np.zeros(nq, dtype=np.int64)
+        pr = np.zeros((nq, len(classes)), dtype=np.float64) if proba else None
+        if nq:
+            check(self._fn("knn_classify")(self._h, a.ctypes.data, nq, qc, max(qc, 1), k, codes.ctypes.data, len(classes),
+                                           flags, pred.ctypes.data, pr.ctypes.data if proba else None))
+        return self._knn_decode(pred, pr, classes, proba)
+
+    def knn_classify_self(self, k: int, labels, weights: str = "uniform", proba: bool = False):
+        """``knn_classify`` of every indexed row from its ``k`` nearest OTHER rows: the leave-one-out predictions."""
+        k, flags = self._knn_k(k, True), self._knn_flags(weights)
+        classes, codes = self._knn_labels(labels)
+        pred = np.zeros(self._n, dtype=np.int64)
+        pr = np.zeros((self._n, len(classes)), dtype=np.float64) if proba else None
+        check(self._fn("knn_classify_self")(self._h, k, codes.ctypes.data, len(classes), flags, pred.ctypes.data,
+                                            pr.ctypes.data if proba else None))
+        return self._knn_decode(pred, pr, classes, proba)
+
+    def knn_regress(self, queries, k: int, targets, weights: str = "uniform"):
+        """The weighted mean of the targets of the ``k`` nearest indexed rows, for every row of ``queries``.  ``targets``:
+        ``[n]`` or ``[n, n_out]`` of any real dtype (taken as float64); returns float64 ``[nq]`` or ``[nq, n_out]``.  A
+        query with a NaN distance in its list gets NaN."""
+        k, flags = self._knn_k(k, False), self._knn_flags(weights)
+        y, one_d = self._knn_targets(targets)
+        a = self._queries(queries, False)
+        nq, qc = a.shape
+        out = np.zeros((nq, y.shape[1]), dtype=np.float64)
+        if nq:
+            check(self._fn("knn_regress")(self._h, a.ctypes.data, nq, qc, max(qc, 1), k, y.ctypes.data, y.shape[1], flags,
+                                          out.ctypes.data))
+        return out[:, 0] if one_d else out
+
+    def knn_regress_self(self, k: int, targets, weights: str = "uniform"):
+        """``knn_regress`` of every indexed row from its ``k`` nearest OTHER rows (leave-one-out)."""
+        k, flags = self._knn_k(k, True), self._knn_flags(weights)
+        y, one_d = self._knn_targets(targets)
+        out = np.zeros((self._n, y.shape[1]), dtype=np.float64)
+        check(self._fn("knn_regress_self")(self._h, k, y.ctypes.data, y.shape[1], flags, out.ctypes.data))
+        return out[:, 0] if one_d else out
+
+    def _knn_classify_device(self, q, k, labels, n_classes, weights, proba, out_pred, out_proba, stream):
+        """the two device votes: ``q`` = ``_device_queries``' answer, or None for the indexed rows"""
+        import torch
+        flags, c = self._knn_flags(weights), self._knn_n_classes(n_classes)
+        self._per_row_device(labels, torch.int64, f"labels must be a contiguous 1-D int64 CUDA tensor of {self._n} class "
+                                                  "codes on the tree's device")
+        count, dev = (self._n, self._dev) if q is None else (q[1], q[0].device)
+        specs = [(out_pred, count, torch.int64, count)]
+        if proba:
+            specs.append((out_proba, (count, c), torch.float64, count * c))
+        elif out_proba is not None:
+            raise ValueError("out_proba needs proba=True")
+        outs = self._outs(*specs, dev=dev)
+        pr = outs[1].data_ptr() if proba else None
+        if q is None:
+            check(self._fn("knn_classify_self_device")(self._h, k, labels.data_ptr(), c, flags, outs[0].data_ptr(), pr,
+                                                       stream_arg(stream, dev)))
+        elif count:
+            check(self._fn("knn_classify_device")(self._h, q[3], count, q[2], q[4], k, labels.data_ptr(), c, flags,
+                                                  outs[0].data_ptr(), pr, stream_arg(stream, dev)))
+        return (outs[0], outs[1]) if proba else outs[0]
+
+    def knn_classify_device(self, queries, k: int, labels, n_classes: int, weights: str = "uniform", proba: bool = False,
+                            out_pred=None, out_proba=None, stream=None):
+        """``knn_classify`` in HBM: ``queries`` a 2-D CUDA tensor of the tree's element type, ``labels`` a contiguous int64
+        CUDA tensor of n class codes in ``[0, n_classes)``.  Returns the CUDA tensor ``pred int64 [nq]`` (-1: a list with a
+        NaN distance or a label out of range), or ``(pred, proba float64 [nq, n_classes])`` with ``proba=True``, written in
+        stream order on ``stream`` (default: the current torch stream); the call does not wait for the device."""
+        k = self._knn_k(k, False)
+        q = self._device_queries(queries, on_device=True, null_empty=False)
+        return self._knn_classify_device(q, k, labels, n_classes, weights, proba, out_pred, out_proba, stream)
+
+    def knn_classify_self_device(self, k: int, labels, n_classes: int, weights: str = "uniform", proba: bool = False,
+                                 out_pred=None, out_proba=None, stream=None):
+        """``knn_classify_self`` in HBM, as ``knn_classify_device``: ``pred int64 [n]`` or ``(pred, proba [n, n_classes])``."""
+        k = self._knn_k(k, True)
+        return self._knn_classify_device(None, k, labels, n_classes, weights, proba, out_pred, out_proba, stream)
+
+    def _knn_regress_device(self, q, k, targets, weights, out, stream):
+        import torch
+        flags = self._knn_flags(weights)
+        if (not self._on_device(targets, torch.float64, self._n) or targets.dim() not in (1, 2)
+                or targets.shape[0] != self._n or targets.numel() == 0):
+            raise ValueError(f"targets must be a contiguous float64 CUDA tensor [n] or [n, n_out >= 1] on the tree's device "
+                             f"(n = {self._n})")
+        n_out = targets.numel() // self._n
+        count, dev = (self._n, self._dev) if q is None else (q[1], q[0].device)
+        shape = count if targets.dim() == 1 else (count, n_out)
+        out = self._out(out, shape, torch.float64, count * n_out, dev=dev)
+        if q is None:
+            check(self._fn("knn_regress_self_device")(self._h, k, targets.data_ptr(), n_out, flags, out.data_ptr(),
+                                                      stream_arg(stream, dev)))
+        elif count:
+            check(self._fn("knn_regress_device")(self._h, q[3], count, q[2], q[4], k, targets.data_ptr(), n_out, flags,
+                                                 out.data_ptr(), stream_arg(stream, dev)))
+        return out
+
+    def knn_regress_device(self, queries, k: int, targets, weights: str = "uniform", out=None, stream=None):
+        """``knn_regress`` in HBM: ``targets`` a contiguous float64 CUDA tensor ``[n]`` or ``[n, n_out]``; returns the CUDA
+        tensor float64 ``[nq]`` or ``[nq, n_out]``, written in stream order on ``stream``."""
+        k = self._knn_k(k, False)
+        q = self._device_queries(queries, on_device=True, null_empty=False)
+        return self._knn_regress_device(q, k, targets, weights, out, stream)
+
+    def knn_regress_self_device(self, k: int, targets, weights: str = "uniform", out=None, stream=None):
+        """``knn_regress_self`` in HBM, as ``knn_regress_device``: float64 ``[n]`` or ``[n, n_out]``."""
+        k = self._knn_k(k, True)
+        return self._knn_regress_device(None, k, targets, weights, out, stream)
 
     # ------------------------------------------------------------------- OPTICS
     # scikit-learn's ``OPTICS(min_samples + 1, max_eps)`` on the device (``pn_optics_*``): the ordering, the reachability

@@ -47,6 +47,7 @@ UNITS = [
     ("mst.hip", []),
     ("linkage.hip", []),
     ("lof.hip", ["-ffp-contract=off"]),
+    ("knn_predict.hip", ["-ffp-contract=off"]),
     ("kde.hip", ["-ffp-contract=off"]),
     ("mean_shift.hip", ["-ffp-contract=off"]),
     ("kmeans.hip", ["-ffp-contract=off"]),

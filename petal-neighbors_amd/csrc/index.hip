@@ -157,6 +157,8 @@ struct WorkspaceBufs {
     // pn_lof_* / pn_lof_score_*: the graph store of a fit ([n][k] uint32 ids, [n][k] distances; + lrd and kdist when the
     // caller keeps neither), and the host entries' inputs and outputs
     DevBuf w_lof, w_lof_io;
+    // pn_knn_classify_* / pn_knn_regress_*: the host entries' labels or targets and their outputs
+    DevBuf w_knn_io;
     // pn_optics_* / pn_optics_dbscan_*: the O(n) arrays of a call (offsets, radii, the tournament tree), the graph store
     // (uint32 ids and distances of every core row's list), and the host entries' inputs and outputs
     DevBuf w_opt, w_opt_graph, w_opt_io;
@@ -4409,6 +4411,176 @@ extern "C" int pn_lof_score_device_f64(const pn_index *ix, const double *d_queri
     return lof_score_device<double>(ix, d_queries, nq, q_cols, q_row_stride, k, d_lrd, d_kdist, flags, d_score,
                                     (hipStream_t)stream);
 }
+
+// ---------------------------------------------------------------------------
+// k-NN classification and regression: pn_knn_{classify,regress}_{,device_,self_,self_device_}{f32,f64}.  The ordinary
+// k-NN query (new points) or the self-query (the indexed rows), chunk by chunk, and one vote or mean launch behind each
+// chunk's answer (knn_predict.hip holds the kernels and the arithmetic).  A list needs no other list's result, so nothing
+// is kept across chunks.  Here: the argument checks, the workspace and the chain.  Nothing waits for the device but the
+// host entries' final copy.
+// ---------------------------------------------------------------------------
+struct KnnPredict {
+    bool classify = false, self = false;
+    const void *values = nullptr;  // labels int64 [n] | targets double [n][width]
+    size_t width = 0;              // n_classes | n_out
+    unsigned flags = 0;
+    int64_t *pred = nullptr;       // classify: [count], required
+    double *out = nullptr;         // classify: proba [count][width], nullable | regress: out [count][width], required
+};
+constexpr size_t kKnnPredictMaxK = 1024;
+// (argument checks, before any device is touched; in the header's order)
+static int knn_predict_args(const pn_index *ix, const KnnPredict &p, const void *queries, size_t nq, size_t k, int elem_bytes) {
+    const char *values_name = p.classify ? "labels" : "targets";
+    if (p.flags & ~(unsigned)PN_KNN_WEIGHT_DISTANCE) return fail(PN_ERR_INVALID, "unknown k-NN prediction flags 0x%x", p.flags);
+    if (p.classify ? !p.pred : !p.out) return fail(PN_ERR_INVALID, "%s is NULL", p.classify ? "pred_out" : "out");
+    if (p.self) {
+        if (!p.values) return fail(PN_ERR_INVALID, "%s is NULL", values_name);
+    } else if (nq && (!queries || !p.values)) {
+        return fail(PN_ERR_INVALID, "%s is NULL", !queries ? "queries" : values_name);
+    }
+    if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
+    if (ix->elem_bytes != elem_bytes) return fail(PN_ERR_INVALID, "index element type mismatch");
+    if (p.classify) {
+        if (p.width < 1 || p.width > 0x7FFFFFFFull)
+            return fail(PN_ERR_INVALID, "n_classes must be in [1, 2^31 - 1] (got %zu)", p.width);
+    } else if (p.width < 1) {
+        return fail(PN_ERR_INVALID, "n_out must be at least 1");
+    }
+    if (p.self) {
+        if (ix->n < 2)
+            return fail(PN_ERR_INVALID, "k-NN prediction over the indexed rows needs at least 2 rows (the index holds %zu)", ix->n);
+        if (k < 1 || k > ix->n - 1) return fail(PN_ERR_INVALID, "k must be in [1, n - 1] = [1, %zu]", ix->n - 1);
+    } else if (k < 1 || k > ix->n) {
+        return fail(PN_ERR_INVALID, "k must be in [1, n] = [1, %zu]", ix->n);
+    }
+    if (k > kKnnPredictMaxK)
+        return fail(PN_ERR_UNSUPPORTED, "k = %zu is above the limit of %zu of k-NN prediction", k, kKnnPredictMaxK);
+    if (ix->n > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many rows for k-NN prediction (32-bit class and row arithmetic)");
+    return PN_OK;
+}
+// in a held workspace, on stream s; queries (unless p.self), labels or targets and the outputs in HBM; `count` lists
+template <typename T>
+static int knn_predict_enqueue(const pn_index *ix, Workspace &ws, const KnnPredict &p, const T *d_q, size_t count, size_t q_cols,
+                               size_t q_stride, size_t k, hipStream_t s) {
+    for (size_t q0 = 0; q0 < count; q0 += kSelfChunk) {
+        const size_t nqc = count - q0 < kSelfChunk ? count - q0 : kSelfChunk;
+        PNCHK(ws.w_hidx.ensure(nqc * k * sizeof(uint64_t)));
+        PNCHK(ws.w_hdist.ensure(nqc * k * sizeof(T)));
+        uint64_t *li = (uint64_t *)ws.w_hidx.p;
+        T *ld = (T *)ws.w_hdist.p;
+        if (p.self)
+            PNCHK(self_knn_chunk<T>(ix, ws, q0, nqc, k + 1, k, false, li, ld, s));
+        else
+            PNCHK(query_enqueue<T>(ix, ws, d_q + q0 * q_stride, nqc, q_cols, q_stride, k, li, ld, k, s));
+        if (p.classify)
+            HIPCHK(launch_knn_vote<T>(li, ld, nqc, (int)k, ix->index_base, ix->n, (const int64_t *)p.values, p.width, p.flags,
+                                      p.pred + q0, p.out ? p.out + q0 * p.width : nullptr, s));
+        else
+            HIPCHK(launch_knn_mean<T>(li, ld, nqc, (int)k, ix->index_base, ix->n, (const double *)p.values, p.width, p.flags,
+                                      p.out + q0 * p.width, s));
+    }
+    return PN_OK;
+}
+template <typename T>
+static int knn_predict_device(const pn_index *ix, const KnnPredict &p, const T *d_q, size_t nq, size_t q_cols, size_t q_stride,
+                              size_t k, hipStream_t s) {
+    PNCHK(knn_predict_args(ix, p, d_q, nq, k, (int)sizeof(T)));
+    const size_t count = p.self ? ix->n : nq;
+    if (count == 0) return PN_OK;
+    CallScope call(ix);
+    PNCHK(call.on_stream(s));
+    return knn_predict_enqueue<T>(ix, call.ws(), p, d_q, count, q_cols, q_stride, k, s);
+}
+template <typename T>
+static int knn_predict_host(const pn_index *ix, const KnnPredict &p, const T *q, size_t nq, size_t q_cols, ptrdiff_t q_stride,
+                            size_t k) {
+    PNCHK(knn_predict_args(ix, p, q, nq, k, (int)sizeof(T)));
+    const size_t n = ix->n, count = p.self ? n : nq;
+    if (p.classify && p.values) {  // the device entries cannot look; here a bad label is an argument error
+        const int64_t *labels = (const int64_t *)p.values;
+        for (size_t i = 0; i < n; ++i)
+            if (labels[i] < 0 || (uint64_t)labels[i] >= p.width)
+                return fail(PN_ERR_INVALID, "labels[%zu] = %lld is outside [0, n_classes) = [0, %zu)", i, (long long)labels[i],
+                            p.width);
+    }
+    if (count == 0) return PN_OK;
+    CallScope call(ix);
+    PNCHK(call.own_stream());
+    Workspace &ws = call.ws();
+    hipStream_t s = call.s();
+    if (!p.self) PNCHK(upload_rows_to<T>(q, nq, q_cols, q_stride, ws.w_hq, s));
+    const size_t values_bytes = n * (p.classify ? sizeof(int64_t) : p.width * sizeof(double));
+    const size_t pred_bytes = p.classify ? count * sizeof(int64_t) : 0;
+    const size_t out_bytes = p.out ? count * p.width * sizeof(double) : 0;
+    PNCHK(ws.w_knn_io.ensure(round_up(values_bytes, (size_t)16) + round_up(pred_bytes, (size_t)16) + out_bytes));
+    char *base = (char *)ws.w_knn_io.p;
+    KnnPredict d = p;
+    d.values = base;
+    d.pred = p.classify ? (int64_t *)(base + round_up(values_bytes, (size_t)16)) : nullptr;
+    d.out = p.out ? (double *)(base + round_up(values_bytes, (size_t)16) + round_up(pred_bytes, (size_t)16)) : nullptr;
+    HIPCHK(hipMemcpyAsync(base, p.values, values_bytes, hipMemcpyHostToDevice, s));
+    PNCHK(knn_predict_enqueue<T>(ix, ws, d, p.self ? nullptr : (const T *)ws.w_hq.p, count, q_cols, q_cols ? q_cols : 1, k, s));
+    if (p.classify) HIPCHK(hipMemcpyAsync(p.pred, d.pred, pred_bytes, hipMemcpyDeviceToHost, s));
+    if (p.out) HIPCHK(hipMemcpyAsync(p.out, d.out, out_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return PN_OK;
+}
+static KnnPredict knn_classify_call(bool self, const int64_t *labels, size_t n_classes, unsigned flags, int64_t *pred, double *proba) {
+    KnnPredict p;
+    p.classify = true, p.self = self, p.values = labels, p.width = n_classes, p.flags = flags, p.pred = pred, p.out = proba;
+    return p;
+}
+static KnnPredict knn_regress_call(bool self, const double *targets, size_t n_out, unsigned flags, double *out) {
+    KnnPredict p;
+    p.self = self, p.values = targets, p.width = n_out, p.flags = flags, p.out = out;
+    return p;
+}
+#define PN_KNN_PREDICT_ENTRIES(SFX, T)                                                                                         \
+    extern "C" int pn_knn_classify_##SFX(const pn_index *ix, const T *queries, size_t nq, size_t q_cols, ptrdiff_t q_row_stride, \
+                                         size_t k, const int64_t *labels, size_t n_classes, unsigned flags, int64_t *pred_out,  \
+                                         double *proba_out) {                                                                  \
+        return knn_predict_host<T>(ix, knn_classify_call(false, labels, n_classes, flags, pred_out, proba_out), queries, nq,    \
+                                   q_cols, q_row_stride, k);                                                                   \
+    }                                                                                                                          \
+    extern "C" int pn_knn_classify_device_##SFX(const pn_index *ix, const T *d_queries, size_t nq, size_t q_cols,                \
+                                                size_t q_row_stride, size_t k, const int64_t *d_labels, size_t n_classes,       \
+                                                unsigned flags, int64_t *d_pred, double *d_proba, void *stream) {              \
+        return knn_predict_device<T>(ix, knn_classify_call(false, d_labels, n_classes, flags, d_pred, d_proba), d_queries, nq,  \
+                                     q_cols, q_row_stride, k, (hipStream_t)stream);                                            \
+    }                                                                                                                          \
+    extern "C" int pn_knn_classify_self_##SFX(const pn_index *ix, size_t k, const int64_t *labels, size_t n_classes,             \
+                                              unsigned flags, int64_t *pred_out, double *proba_out) {                          \
+        return knn_predict_host<T>(ix, knn_classify_call(true, labels, n_classes, flags, pred_out, proba_out), nullptr, 0, 0, 0, \
+                                   k);                                                                                         \
+    }                                                                                                                          \
+    extern "C" int pn_knn_classify_self_device_##SFX(const pn_index *ix, size_t k, const int64_t *d_labels, size_t n_classes,    \
+                                                     unsigned flags, int64_t *d_pred, double *d_proba, void *stream) {         \
+        return knn_predict_device<T>(ix, knn_classify_call(true, d_labels, n_classes, flags, d_pred, d_proba), nullptr, 0, 0, 0, \
+                                     k, (hipStream_t)stream);                                                                  \
+    }                                                                                                                          \
+    extern "C" int pn_knn_regress_##SFX(const pn_index *ix, const T *queries, size_t nq, size_t q_cols, ptrdiff_t q_row_stride,  \
+                                        size_t k, const double *targets, size_t n_out, unsigned flags, double *out) {          \
+        return knn_predict_host<T>(ix, knn_regress_call(false, targets, n_out, flags, out), queries, nq, q_cols, q_row_stride,  \
+                                   k);                                                                                         \
+    }                                                                                                                          \
+    extern "C" int pn_knn_regress_device_##SFX(const pn_index *ix, const T *d_queries, size_t nq, size_t q_cols,                 \
+                                               size_t q_row_stride, size_t k, const double *d_targets, size_t n_out,           \
+                                               unsigned flags, double *d_out, void *stream) {                                  \
+        return knn_predict_device<T>(ix, knn_regress_call(false, d_targets, n_out, flags, d_out), d_queries, nq, q_cols,        \
+                                     q_row_stride, k, (hipStream_t)stream);                                                    \
+    }                                                                                                                          \
+    extern "C" int pn_knn_regress_self_##SFX(const pn_index *ix, size_t k, const double *targets, size_t n_out, unsigned flags,  \
+                                             double *out) {                                                                    \
+        return knn_predict_host<T>(ix, knn_regress_call(true, targets, n_out, flags, out), nullptr, 0, 0, 0, k);               \
+    }                                                                                                                          \
+    extern "C" int pn_knn_regress_self_device_##SFX(const pn_index *ix, size_t k, const double *d_targets, size_t n_out,         \
+                                                    unsigned flags, double *d_out, void *stream) {                             \
+        return knn_predict_device<T>(ix, knn_regress_call(true, d_targets, n_out, flags, d_out), nullptr, 0, 0, 0, k,          \
+                                     (hipStream_t)stream);                                                                     \
+    }
+PN_KNN_PREDICT_ENTRIES(f32, float)
+PN_KNN_PREDICT_ENTRIES(f64, double)
+#undef PN_KNN_PREDICT_ENTRIES
 
 // ---------------------------------------------------------------------------
 // One radius per query: pn_query_radii_{,device_,self_,self_device_}{f32,f64}.  List q is the scalar entry point's list

@@ -241,6 +241,19 @@ template <typename T>
 hipError_t launch_lof_score(const uint64_t *q_idx, const T *q_dist, size_t nq, int k, uint64_t index_base, size_t n,
                             const double *lrd, const T *kdist, double *score, hipStream_t s);
 
+// ---- knn_predict.hip: the vote and the weighted mean over the k-NN lists (pn_knn_classify_*, pn_knn_regress_*); nothing
+// in it waits for the device.  q_idx / q_dist: a chunk's k-NN answer [nq][k] (ids with the index base), 1 <= k <= 1024;
+// flags: PN_KNN_WEIGHT_DISTANCE or 0.
+// pred [nq] (-1: a poisoned list) and, where proba is not NULL, proba [nq][n_classes] (zeroed here, on s) from labels [n]
+template <typename T>
+hipError_t launch_knn_vote(const uint64_t *q_idx, const T *q_dist, size_t nq, int k, uint64_t index_base, size_t n,
+                           const int64_t *labels, size_t n_classes, unsigned flags, int64_t *pred, double *proba,
+                           hipStream_t s);
+// out [nq][n_out] from targets [n][n_out]
+template <typename T>
+hipError_t launch_knn_mean(const uint64_t *q_idx, const T *q_dist, size_t nq, int k, uint64_t index_base, size_t n,
+                           const double *targets, size_t n_out, unsigned flags, double *out, hipStream_t s);
+
 // ---- kde.hip: kernel density sums over the radius lists (pn_kde_*); nothing in it waits for the device.
 // hq [nq] <- h broadcast (n_h = 1) or copied (n_h = nq); cut [nq] <- the cutoffs.  mode 0: cut = h; 1: the smallest T >=
 // (double)h * f; 2: 0; 3: +inf; a bandwidth that is not positive is its own cutoff in every mode
