@@ -122,8 +122,9 @@ enum {
                                   fills every workgroup slot of the device, the paired
                                   kernel (one 8-wave workgroup per CU over two query tiles, its SIMD partners in
                                   anti-phase); 4 / 8 = always that kernel where it applies; 16 = the paired kernel where
-                                  it applies, else the 4-wave kernel.  Never changes a result (A/B measurements, tests
-                                  of all three kernels). */
+                                  it applies, else the 4-wave kernel; 32 = likewise the paired kernel with two row tiles
+                                  per workgroup meeting.  Never changes a result (A/B measurements, tests of all the
+                                  kernels). */
     PN_OPT_SEED_MODEL = 10,      /* bf16 tier, indexes of narrow rows (D <= 128) whose seed model was accepted at build
                                   (pn_info.seed_model): 1 (default) = k-NN calls with k <= 128 take their starting
                                   thresholds from the model (no scout launch); 0 = always scout.  Never changes a result:

@@ -67,6 +67,7 @@ typedef const __attribute__((address_space(1))) void glb_void_b;
 
 #ifdef PN_DIAG_BF_COUNT  // diagnostic build only: event counters
 __device__ unsigned long long g_bfdbg[16];  // 12.. refreshers: query visits, updates, passes, rejected reads
+__device__ unsigned long long g_bfdbg_lag[16];  // the paired kernels' lagging half (waves 4-7), same slots
 // per-wave accumulators in registers (dbg_), flushed by one atomic per counter at the end of a run: an atomic per
 // event would itself be what the barrier waits for
 #define BF_COUNT(i, v) (dbg_[i] += (unsigned long long)(v))
@@ -2246,14 +2247,63 @@ constexpr int kPairStagger = PN_DIAG_PAIR_STAGGER;  // 1: half a chain
 struct BfPairMeet {  // the lagging half's tile barrier, inside chain A: after KS / 2 steps (diagnostic builds: KS MID4 / 4),
     uint32_t ns;     // at least one -- the argument above needs an MFMA of this chain in front of the barrier
     static constexpr int at(int ks) { return ks * PN_DIAG_PAIR_MID4 / 4 > 1 ? ks * PN_DIAG_PAIR_MID4 / 4 : 1; }
+#ifdef PN_DIAG_BF_COUNT
+    unsigned long long *st;  // two stamps that do not wait (the caller settles them behind the chain): arrival, departure
+#endif
     __device__ __forceinline__ void operator()() const {
+#ifdef PN_DIAG_BF_COUNT
+        st[0] = bf_stamp_nw();
+#endif
         bf_wait_dma(ns);
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
+#ifdef PN_DIAG_BF_COUNT
+        st[1] = bf_stamp_nw();
+#endif
     }
 };
+#ifdef PN_DIAG_BF_COUNT
+#define BF_PAIR_MEET(ns) BfPairMeet{ns, tmeet_}
+#else
+#define BF_PAIR_MEET(ns) BfPairMeet{ns}
+#endif
+#ifndef PN_DIAG_PAIR_DMA_LATE
+#define PN_DIAG_PAIR_DMA_LATE 0  // diagnostic builds, 1: the second tile's pieces are issued one tile later, in that tile's gap
+#endif
 
-template <int KS, bool CI, int STAG>
+//
+// MEET (tiles per meeting; 1: the schedule above, 2: bf16_filter_kernel_meet_pair<KS, CI, 2>).  At C2 a wave takes ~0.36
+// rare-path entries per tile, so nearly every tile has one of the CU's eight waves in a detour and a meeting per tile
+// is paid at the pace of the slowest of eight.  With MEET = 2 an iteration covers the two tiles of SUPER-TILE s = tiles
+// (2s, 2s+1) of the run -- chain A, chain B of tile 2s, chain A, chain B of tile 2s+1 -- with ONE s_barrier, placed
+// where MEET = 1 places it in the first of them (leading half: between the first tile's chains; lagging half: inside
+// its chain A at BfPairMeet::at).  The ring holds 3 MEET tiles, tile t of the run in buffer t mod 6; the prologue
+// brings super-tiles 0 and 1.  The argument above holds with "tile" read as "pair of tiles":
+//  * B(s) certifies that super-tile s+1 has landed: every wave issued its pieces of both tiles behind B(s-1) (or in
+//    the prologue) and waits for them with bf_wait_dma before it arrives.  Its first readers are the last steps of
+//    chain B of tile 2s+1, behind B(s) in both roles.  `pre` and `nc` cross from tile 2s to tile 2s+1 WITHOUT a
+//    barrier: both tiles landed together, certified by B(s-1);
+//  * nobody reads super-tile s-1 any more, so its two buffers take super-tile s+2, issued behind B(s) in the wave's
+//    own gap: the last reads of super-tile s-1 are the fragment requests of chain B of tile 2s-1.  The leading half
+//    has finished chain A of tile 2s since and waits lgkmcnt(0); the lagging half has executed BfPairMeet::at >= 1
+//    steps of that chain, whose MFMAs consumed fragments requested AFTER the last request into tile 2s-1, and LDS
+//    reads of a wave return in order: it still needs no lgkmcnt(0) in mid-chain.
+// ns and bf_wait_dma: up to four survivor checks now lie between a wave's DMA issue and its next meeting, so ns can be
+// larger -- the wait's three cases stay correct for ANY ns: vector-memory operations retire in order, all ns stores
+// are younger than the DMA pieces (both tiles' pieces are issued back to back and ns restarts behind the last), and
+// "at most min(ns, 2) outstanding" therefore never leaves a piece in flight.
+// A run of odd length ends with a half super-tile: the iteration skips the second tile's chains and requests and
+// still executes its one barrier -- ceil(n / 2) barriers in both roles for every run length n, by construction (two
+// instantiations of one loop).  Cells, writers, thresholds, the order of a wave's appends and the end-of-run cut do not
+// depend on MEET: candidates, counters and answers are the same bits.
+// -DPN_DIAG_PAIR_MEET=1 (diagnostic builds) gives the two-tile kernel's entry today's schedule from this same source.
+#ifndef PN_DIAG_PAIR_MEET
+#define PN_DIAG_PAIR_MEET 2
+#endif
+constexpr int kPairMeet = PN_DIAG_PAIR_MEET;  // tiles per meeting of the two-tile kernel (Bf16Kernel::PairTwo)
+static_assert(kPairMeet == 1 || kPairMeet == 2, "PN_DIAG_PAIR_MEET");
+
+template <int KS, bool CI, int STAG, int MEET>
 __device__ __forceinline__ void bf_pair_run(const char *__restrict__ img, char *tiles, uint32_t kp, uint32_t kfin, uint2 *__restrict__ cand,
                                             uint32_t *__restrict__ ccnt, uint32_t *__restrict__ ctau,
                                             const bf16x8 (&b0)[KS], const bf16x8 (&b1)[KS], float tau0, float tau1,
@@ -2261,7 +2311,7 @@ __device__ __forceinline__ void bf_pair_run(const char *__restrict__ img, char *
     constexpr int C = 2 * KS, CP = C + 1;
     constexpr uint32_t CAP = 64u;
     constexpr int TB = kBP * CP * 16;  // bytes per tile image
-    constexpr int NBUF = 3, NW = 8;
+    constexpr int NBUF = 3 * MEET, NW = 8;
     const int jq = lane & 31, h = lane >> 5;
     BF_DBG_DECL;
     // wave w moves the consecutive pieces [w P, w P + P) of a tile (bf16_filter8_kernel)
@@ -2300,45 +2350,98 @@ __device__ __forceinline__ void bf_pair_run(const char *__restrict__ img, char *
         for (int i = 0; i < kLA; ++i) pre[i] = *reinterpret_cast<const bf16x8 *>(ar + 32 * (i < KS ? i : 0));
         if (CI) cc = bf_cinit<CP>(tiles, 0, h);
     }
-    int cur = 0;
-    for (uint32_t rt = rt0; rt < rt1; ++rt) {  // ONE s_barrier per iteration, whatever STAG
-        const int nxt = cur == NBUF - 1 ? 0 : cur + 1, prv = cur == 0 ? NBUF - 1 : cur - 1;
+    int cur = 0;  // the buffer of the tile at hand: tile t of the run sits in buffer t mod NBUF
+    auto ring = [](int b) { return b >= NBUF ? b - NBUF : b; };
+    constexpr bool LATE = MEET == 2 && PN_DIAG_PAIR_DMA_LATE != 0;
+#ifdef PN_DIAG_BF_COUNT
+    const unsigned long long trun0_ = bf_stamp();
+    unsigned long long tmeet_[2] = {0, 0};
+#endif
+    // One tile.  meets: the first tile of an iteration -- the workgroup's meeting and the wave's DMA issue lie in it.
+    auto tile = [&](uint32_t rt, auto meets) {
+        constexpr bool MT = decltype(meets)::value;
+        const int nxt = ring(cur + 1);
         const char *tb = tiles + cur * TB;
         const char *arow0 = tb + (jq * CP + h) * 16;
         const char *arow1 = arow0 + 32 * CP * 16;
         float m0, m1, p0, p1;
-        if (STAG == 2) BfPairMeet{ns}();
-        if (STAG == 1)
-            bf_chain_p<KS, CI, CP>(arow0, pre, b0, b1, cc, a00, a01, a10, a11, m0, m1, arow1, tb, 1, h, BfPairMeet{ns});
+#ifdef PN_DIAG_BF_COUNT
+        unsigned long long tc0_ = bf_stamp_nw();
+#endif
+        if (MT && STAG == 2) BF_PAIR_MEET(ns)();
+        if (MT && STAG == 1)
+            bf_chain_p<KS, CI, CP>(arow0, pre, b0, b1, cc, a00, a01, a10, a11, m0, m1, arow1, tb, 1, h, BF_PAIR_MEET(ns));
         else
             bf_chain_p<KS, CI, CP>(arow0, pre, b0, b1, cc, a00, a01, a10, a11, m0, m1, arow1, tb, 1, h);
-        if (rt == rt0) { m0 = __uint_as_float(0x7F800000u); m1 = m0; }  // nothing precedes the first tile
+#ifdef PN_DIAG_BF_COUNT
+        {  // chain A, without the meeting inside it (lagging half); the meeting itself
+            unsigned long long tc1_ = bf_stamp_nw();
+            bf_settle(tc1_);
+            bf_settle(tc0_);
+            bf_settle(tmeet_[0]);
+            bf_settle(tmeet_[1]);
+            BF_COUNT(9, tc1_ - tc0_ - (tmeet_[1] - tmeet_[0]));
+            BF_COUNT(6, tmeet_[1] - tmeet_[0]);
+            tmeet_[0] = tmeet_[1] = 0;
+        }
+#endif
+        if (MT && rt == rt0) { m0 = __uint_as_float(0x7F800000u); m1 = m0; }  // nothing precedes the first tile
         if (__any(m0 < tau0 || m1 < tau1)) {
             const uint32_t row0 = (rt - 1) * kBP + 32;
             if (__any(m0 < tau0)) bf_slow<1, false>(a10, m0, tau0, cnt0, row0, h, jq, lane, kp, ceq0, ce_blk0, ns BF_DBG_PASS);
             if (__any(m1 < tau1)) bf_slow<1, false>(a11, m1, tau1, cnt1, row0, h, jq, lane, kp, ceq1, ce_blk1, ns BF_DBG_PASS);
         }
-        if (STAG == 0) {  // the leading placement: between the tile's two chains
+        if (MT && STAG == 0) {  // the leading placement: between the tile's two chains
+#ifdef PN_DIAG_BF_COUNT
+            const unsigned long long tb0_ = bf_stamp();
+#endif
             bf_wait_dma(ns);
 #ifndef PN_DIAG_PAIR_NOLGKM
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #endif
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
+#ifdef PN_DIAG_BF_COUNT
+            BF_COUNT(6, bf_stamp() - tb0_);
+#endif
         }
-        if (rt + 2 < rt1) {
-            dma_tile(rt + 2, prv);
+        // the wave's pieces of the super-tile after next, into the buffers of the one before this: behind the meeting,
+        // in the wave's own gap (MEET = 1: tile rt + 2 into the buffer of tile rt - 1)
+        if (MT) {
+#pragma unroll
+            for (int j = 0; j < (LATE ? 1 : MEET); ++j)
+                if (rt + 2 * MEET + j < rt1) {
+                    dma_tile(rt + 2 * MEET + j, ring(cur + 2 * MEET + j));
+                    ns = 0;
+                }
+        } else if (LATE && rt + 2 * MEET < rt1) {  // (this tile is the iteration's second: its number is one higher)
+            dma_tile(rt + 2 * MEET, ring(cur + 2 * MEET));
             ns = 0;
         }
         const bool last = rt + 1 >= rt1;  // (then the requests below are never used: any valid LDS address)
         const char *ntb = last ? tb : tiles + nxt * TB;
+#ifdef PN_DIAG_BF_COUNT
+        unsigned long long tc2_ = bf_stamp_nw();
+#endif
         bf_chain_p<KS, CI, CP>(arow1, pre, b0, b1, cc, a10, a11, a00, a01, p0, p1, ntb + (jq * CP + h) * 16, ntb, 0, h);
+#ifdef PN_DIAG_BF_COUNT
+        {
+            unsigned long long tc3_ = bf_stamp_nw();
+            bf_settle(tc3_);
+            bf_settle(tc2_);
+            BF_COUNT(10, tc3_ - tc2_);
+        }
+#endif
         if (__any(p0 < tau0 || p1 < tau1)) {
             const uint32_t row0 = rt * kBP;
             if (__any(p0 < tau0)) bf_slow<1, false>(a00, p0, tau0, cnt0, row0, h, jq, lane, kp, ceq0, ce_blk0, ns BF_DBG_PASS);
             if (__any(p1 < tau1)) bf_slow<1, false>(a01, p1, tau1, cnt1, row0, h, jq, lane, kp, ceq1, ce_blk1, ns BF_DBG_PASS);
         }
         cur = nxt;
+    };
+    for (uint32_t rt = rt0; rt < rt1; rt += MEET) {  // ONE s_barrier per iteration, whatever STAG and MEET
+        tile(rt, std::true_type{});
+        if (MEET == 2 && rt + 1 < rt1) tile(rt + 1, std::false_type{});  // (a run of odd length ends with half a super-tile)
     }
     {  // drain: block 1 of the last tile
         float m0 = a10[0], m1 = a11[0];
@@ -2385,22 +2488,24 @@ __device__ __forceinline__ void bf_pair_run(const char *__restrict__ img, char *
         ccnt[cell0 + 32 + jq] = cnt1;
         ctau[cell0 + 32 + jq] = f2s(tau1);
     }
-    BF_DBG_FLUSH(lane);
+#ifdef PN_DIAG_BF_COUNT
+    BF_COUNT(7, bf_stamp() - trun0_);
+    if (lane == 0)  // per role: the leading half's sums in g_bfdbg, the lagging half's in g_bfdbg_lag
+        for (int i = 0; i < 12; ++i) atomicAdd(STAG ? &g_bfdbg_lag[i] : &g_bfdbg[i], dbg_[i]);
+#endif
 }
 
-template <int KS, bool CI>
-__global__ __launch_bounds__(512, 2) void bf16_filter_kernel_pair(const char *__restrict__ img, uint32_t n_tiles,
-                                                                  const u32x4 *__restrict__ Bq, uint32_t q_tiles,
-                                                                  uint32_t kp_keep, uint2 *__restrict__ cand,
-                                                                  uint32_t *__restrict__ ccnt,
-                                                                  uint32_t *__restrict__ ctau, size_t nq_pad,
-                                                                  const uint32_t *tau_init, BfShared sh) {
+// The body of both paired kernels (tiles: the ring of 3 MEET tile buffers in dynamic LDS)
+template <int KS, bool CI, int MEET>
+__device__ __forceinline__ void bf_pair_body(char *tiles, const char *__restrict__ img, uint32_t n_tiles,
+                                             const u32x4 *__restrict__ Bq, uint32_t q_tiles, uint32_t kp_keep,
+                                             uint2 *__restrict__ cand, uint32_t *__restrict__ ccnt,
+                                             uint32_t *__restrict__ ctau, size_t nq_pad, const uint32_t *tau_init,
+                                             const BfShared &sh) {
     const uint32_t kp = kp_keep & 0xFFFFu, keep_arg = kp_keep >> 16;
     const uint32_t kfin = keep_arg > kp ? keep_arg : kp;
     constexpr int CP = 2 * KS + 1;
     constexpr int TB = kBP * CP * 16;  // bytes per tile image
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    char *tiles = reinterpret_cast<char *>(smem_raw);  // [3][TB]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int jq = lane & 31, h = lane >> 5;
@@ -2458,14 +2563,14 @@ __global__ __launch_bounds__(512, 2) void bf16_filter_kernel_pair(const char *__
             b1[ks] = b0[ks];
         }
     }
-    // prologue, the same instructions for both halves: the run's first two tiles, one barrier (it carries the vmcnt(0))
+    // prologue, the same instructions for both halves: the run's first 2 MEET tiles, one barrier (it carries the vmcnt(0))
     {
         constexpr int P = (CP + 7) / 8;
         const int n_mine = CP - wave * P < P ? (CP - wave * P > 0 ? CP - wave * P : 0) : P;
-        // (rt0 + t < rt1, and `rt + 2 < rt1` / `last` in bf_pair_run: the guards of one- and two-tile runs.  No call
+        // (rt0 + t < rt1, and `rt + 2 MEET + j < rt1` / `last` in bf_pair_run: the guards of the shortest runs.  No call
         // reaches them -- the plan's shortest aligned run is ~9-12 tiles, tests/test_gpu_bf16_pair.py -- so they are
         // argued, not exercised: a one-tile run loads one tile, meets its one barrier and requests nothing further.)
-        for (uint32_t t = 0; t < 2u && rt0 + t < rt1; ++t) {
+        for (uint32_t t = 0; t < 2u * MEET && rt0 + t < rt1; ++t) {
             const char *ws = img + ((size_t)(rt0 + t) * (size_t)TB + (size_t)(wave * (P * 1024))) + (uint32_t)lane * 16u;
             char *wd = tiles + t * TB + wave * (P * 1024);
             if (0 < n_mine) __builtin_amdgcn_global_load_lds((glb_void_b *)ws, (lds_void_b *)wd, 16, 0, 0);
@@ -2477,11 +2582,35 @@ __global__ __launch_bounds__(512, 2) void bf16_filter_kernel_pair(const char *__
     // the two roles: one loop, two placements of its barrier; split by wave number >= 4, the SIMD partner of wave w is
     // wave w + 4 (MI355X_MICROARCH.md, "Two waves per SIMD", item 9)
     if (wave >= 4)
-        bf_pair_run<KS, CI, kPairStagger>(img, tiles, kp, kfin, cand, ccnt, ctau, b0, b1, tau0, tau1, rt0, rt1, cell0,
-                                          active, wave, lane);
+        bf_pair_run<KS, CI, kPairStagger, MEET>(img, tiles, kp, kfin, cand, ccnt, ctau, b0, b1, tau0, tau1, rt0, rt1,
+                                                cell0, active, wave, lane);
     else
-        bf_pair_run<KS, CI, 0>(img, tiles, kp, kfin, cand, ccnt, ctau, b0, b1, tau0, tau1, rt0, rt1, cell0, active, wave,
-                               lane);
+        bf_pair_run<KS, CI, 0, MEET>(img, tiles, kp, kfin, cand, ccnt, ctau, b0, b1, tau0, tau1, rt0, rt1, cell0, active,
+                                     wave, lane);
+}
+
+template <int KS, bool CI>
+__global__ __launch_bounds__(512, 2) void bf16_filter_kernel_pair(const char *__restrict__ img, uint32_t n_tiles,
+                                                                  const u32x4 *__restrict__ Bq, uint32_t q_tiles,
+                                                                  uint32_t kp_keep, uint2 *__restrict__ cand,
+                                                                  uint32_t *__restrict__ ccnt,
+                                                                  uint32_t *__restrict__ ctau, size_t nq_pad,
+                                                                  const uint32_t *tau_init, BfShared sh) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];  // [3][TB]
+    bf_pair_body<KS, CI, 1>(reinterpret_cast<char *>(smem_raw), img, n_tiles, Bq, q_tiles, kp_keep, cand, ccnt, ctau, nq_pad,
+                            tau_init, sh);
+}
+// ... and with MEET tiles per meeting (kPairMeet = 2; Bf16Kernel::PairTwo)
+template <int KS, bool CI, int MEET>
+__global__ __launch_bounds__(512, 2) void bf16_filter_kernel_meet_pair(const char *__restrict__ img, uint32_t n_tiles,
+                                                                       const u32x4 *__restrict__ Bq, uint32_t q_tiles,
+                                                                       uint32_t kp_keep, uint2 *__restrict__ cand,
+                                                                       uint32_t *__restrict__ ccnt,
+                                                                       uint32_t *__restrict__ ctau, size_t nq_pad,
+                                                                       const uint32_t *tau_init, BfShared sh) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];  // [3 MEET][TB]
+    bf_pair_body<KS, CI, MEET>(reinterpret_cast<char *>(smem_raw), img, n_tiles, Bq, q_tiles, kp_keep, cand, ccnt, ctau,
+                               nq_pad, tau_init, sh);
 }
 
 // ---------------------------------------------------------------------------
@@ -2811,6 +2940,12 @@ extern "C" int pn_debug_read_bf(unsigned long long *out, int reset) {
     if (reset && hipMemcpyToSymbol(HIP_SYMBOL(g_bfdbg), z, sizeof(z)) != hipSuccess) return 1;
     return 0;
 }
+extern "C" int pn_debug_read_bf_lag(unsigned long long *out, int reset) {
+    unsigned long long z[16] = {0};
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bfdbg_lag), sizeof(z)) != hipSuccess) return 1;
+    if (reset && hipMemcpyToSymbol(HIP_SYMBOL(g_bfdbg_lag), z, sizeof(z)) != hipSuccess) return 1;
+    return 0;
+}
 #endif
 
 // ---------------------------------------------------------------------------
@@ -3086,7 +3221,7 @@ template hipError_t launch_bf16_pack_queries<double>(const double *, const float
 // ---- launchers of the filter kernels: they run what the descriptor (Bf16Launch, pn_internal.h) names or refuse it --
 // which main-pass kernel serves a call is bf16_main_kernel's decision (bf16_launch.h), made by the plan in index.hip
 static_assert(kBQ == (int)kBf16QueryTile && kBP == (int)kBf16RowTile && kWR == (int)kBf16WideTile, "bf16_launch.h");
-// PN_DEBUG_PLAN: one line per main-pass launch of a k-NN call -- which kernel (4 / 8 / pair) and its grid
+// PN_DEBUG_PLAN: one line per main-pass launch of a k-NN call -- which kernel (4 / 8 / pair / pair2) and its grid
 static void bf_debug_kernel(const char *which, unsigned grid, unsigned block) {
     if (debug_plan()) std::fprintf(stderr, "bf16 main pass: kernel %s grid %u x %u\n", which, grid, block);
 }
@@ -3144,11 +3279,19 @@ static hipError_t launch_bf16_t(const Bf16Launch &l, hipStream_t s) {
     uint32_t *tau = static_cast<uint32_t *>(cb.tau);
     if constexpr (!RAD) {  // the kernels of the main pass alone
         if constexpr (M == 1)
-            if (l.kernel == Bf16Kernel::Pair) {
+            if (l.kernel == Bf16Kernel::Pair || l.kernel == Bf16Kernel::PairTwo) {
                 const unsigned grid = (unsigned)(((g.q_tiles + 1u) / 2u) * (n_wg / g.q_tiles));
-                bf_debug_kernel("pair", grid, 512);
-                return bf_go<bf16_filter_kernel_pair<KS, CI>>(grid, 512, sh, s, img, g.n_tiles, B, g.q_tiles, kp_keep, keys,
-                                                              cb.cnt, tau, cb.nq_pad, l.tau, a);
+                if (l.kernel == Bf16Kernel::Pair) {
+                    bf_debug_kernel("pair", grid, 512);
+                    return bf_go<bf16_filter_kernel_pair<KS, CI>>(grid, 512, sh, s, img, g.n_tiles, B, g.q_tiles, kp_keep,
+                                                                     keys, cb.cnt, tau, cb.nq_pad, l.tau, a);
+                }
+                // two tiles per meeting: a ring of 3 kPairMeet tile buffers (KS = 8: 104 448 B, KS = 9: 116 736 B of
+                // the CU's 160 KiB -- bf_go raises the kernel's dynamic-LDS limit to it); one workgroup per CU as before
+                const size_t sh2 = kPairMeet == 1 ? sh : (size_t)3 * kPairMeet * kBP * (2 * KS + 1) * 16;
+                bf_debug_kernel("pair2", grid, 512);
+                return bf_go<bf16_filter_kernel_meet_pair<KS, CI, kPairMeet>>(grid, 512, sh2, s, img, g.n_tiles, B, g.q_tiles,
+                                                                         kp_keep, keys, cb.cnt, tau, cb.nq_pad, l.tau, a);
             }
         if (l.kernel == Bf16Kernel::Eight) {
             bf_debug_kernel("8", n_all, 512);

@@ -13,8 +13,9 @@ namespace pn {
 // buffers) -- the main pass.  Radius: fixed thresholds, 256-slot buffers that overflow instead of compacting (MODE 2, RAD).
 enum class Bf16Pass { ScoutOnly, SelfScout, Seeded, Radius };
 // Four: bf16_filter_kernel (4 waves, every pass).  Eight: bf16_filter8_kernel, Pair: bf16_filter_kernel_pair (8 waves,
-// main pass of an aligned partition only).  Wide: bf16_wide_kernel (128 < D, every pass).
-enum class Bf16Kernel { Four, Eight, Pair, Wide };
+// main pass of an aligned partition only).  Wide: bf16_wide_kernel (128 < D, every pass).  PairTwo: the paired kernel
+// with two row tiles per workgroup meeting and six LDS tile buffers (bf16_filter_kernel_meet_pair<KS, CI, 2>).
+enum class Bf16Kernel { Four, Eight, Pair, Wide, PairTwo };
 
 constexpr uint32_t kBf16QueryTile = 256;  // queries per query tile (narrow and wide rows)
 constexpr uint32_t kBf16RowTile = 64;     // rows per tile, narrow rows
@@ -60,18 +61,30 @@ constexpr size_t kBf8MaxImage = (size_t)768 << 20;  // ... on corpora whose tile
 #define PN_DIAG_PAIR_MIN_RUN 200
 #endif
 constexpr uint32_t kPairMinRun = PN_DIAG_PAIR_MIN_RUN;  // the paired kernel: runs of at least this many tiles (64-slot buffers, >= 2 query tiles)
+// Two tiles per meeting: where the paired kernel is chosen AND the runs are at least this long.
+// Measured interleaved with the parent build, one device per session (profiles/r06_pair_meet_ab.log): 625-tile runs
+// -- C2 -1.6 % / -2.1 % at 200 steps (sessions 1 / 3), -2.1 % / -2.5 % at 20 steps, c5s -4.1 % -- and the 312-tile runs
+// of a 500 k-row shard of C2 -3.7 % / -3.4 % (sessions 2 / 3), every run below every run of the parent.  Only the regime measured: the
+// shortest runs measured are those 312 tiles (shorter ones keep one tile per meeting), the largest image is C2's
+// (15 625 tiles of 17 408 B = 272 MB; larger ones, up to the paired kernel's 768 MiB, keep one tile per meeting too).
+#ifndef PN_DIAG_PAIR2_MIN_RUN
+#define PN_DIAG_PAIR2_MIN_RUN 312
+#endif
+constexpr uint32_t kPairTwoMinRun = PN_DIAG_PAIR2_MIN_RUN;
+constexpr size_t kPairTwoMaxImage = (size_t)15625 * 17408;
 
 // The main-pass kernel of a narrow-row launch.  cap: slots per buffer (64 / 128 / 256); refreshers: shared thresholds
 // on; image_bytes: the corpus' tile image; wg_slots: the device's workgroup slots of the 4-wave kernel (2 per CU; 0 =
 // unknown, and the automatic choice then never takes the paired kernel); forced: PN_OPT_BF16_WAVES -- 0 = the rule
-// below, 4 / 8 = that kernel, 16 = the paired kernel, each only where it applies (elsewhere: the 4-wave kernel).
+// below, 4 / 8 = that kernel, 16 = the paired kernel, 32 = the paired kernel with two tiles per meeting, each only
+// where it applies (elsewhere: the 4-wave kernel).
 // The 8-wave kernels serve the main pass of a k-NN call (thresholds given) on an aligned partition only.
 // Where a kernel can run at all (the launcher refuses it elsewhere): the 4-wave kernel everywhere on narrow rows; the
 // paired kernel where the 8-wave kernel may run, with 64-slot buffers, no refreshers and at least two query tiles.
 inline bool bf16_kernel_applies(Bf16Kernel k, const Bf16Grid &g, int cap, Bf16Pass pass, bool refreshers) {
     if (k == Bf16Kernel::Four) return true;
     if (k == Bf16Kernel::Wide || pass != Bf16Pass::Seeded || !g.aligned) return false;
-    return k == Bf16Kernel::Eight || (cap == 64 && !refreshers && g.q_tiles >= 2);
+    return k == Bf16Kernel::Eight || (cap == 64 && !refreshers && g.q_tiles >= 2);  // (Pair and PairTwo alike)
 }
 inline Bf16Kernel bf16_main_kernel(const Bf16Grid &g, int cap, Bf16Pass pass, bool refreshers, size_t image_bytes,
                                    int wg_slots, int forced) {
@@ -82,8 +95,10 @@ inline Bf16Kernel bf16_main_kernel(const Bf16Grid &g, int cap, Bf16Pass pass, bo
     // pairing would put two waves on every SIMD of half as many CUs: not measured, and by the cycle budget a loss.)
     if (bf16_kernel_applies(Bf16Kernel::Pair, g, cap, pass, refreshers)) {
         const bool fills = wg_slots > 0 && g.n_wg >= wg_slots;
+        if (forced == 32) return Bf16Kernel::PairTwo;
         if (forced == 16 || (forced == 0 && fills && g.run_tiles >= kPairMinRun && image_bytes <= kBf8MaxImage))
-            return Bf16Kernel::Pair;
+            return forced == 0 && g.run_tiles >= kPairTwoMinRun && image_bytes <= kPairTwoMaxImage ? Bf16Kernel::PairTwo
+                                                                                                   : Bf16Kernel::Pair;
     }
     // Measured on one device (round 4, profiles/r04_waves_ab.log): at C2 (1302-tile runs) the 8-wave kernel is 7-9 %
     // SLOWER than the 4-wave kernel (2.47-2.50 vs 2.28-2.31 ms: twice the LDS fragment traffic, an 8-wave meeting per

@@ -263,7 +263,7 @@ struct pn_index {
     int filter_slots = 0;
     int mfma_structure = 0;  // 0 auto, 2 = persistent partition with LDS buffers, 3 = with HBM buffers (1: retired)
     int shared_tau = 1;      // PN_OPT_SHARED_THRESHOLDS: 0 off, 1 auto, >= 2 the rank itself
-    int bf16_waves = 0;      // PN_OPT_BF16_WAVES: 0 auto, 4 = 4-wave kernel, 8 = 8-wave kernel, 16 = paired kernel (where they apply)
+    int bf16_waves = 0;      // PN_OPT_BF16_WAVES: 0 auto, 4 = 4-wave kernel, 8 = 8-wave kernel, 16 = paired kernel, 32 = paired, two tiles per meeting (where they apply)
     // Seed model (round 4, seed_model_build): starting thresholds of a k-NN call from per-dimension moments of the corpus,
     // calibrated against the scout's own seeds at build time -- the calls it serves run WITHOUT the scout launch.
     float *d_smodel = nullptr;   // [3][ld] f32: M1_k | 4 (M2_k - M1_k^2) | 4 (M3_k - M2_k M1_k), zero padded
@@ -1031,7 +1031,8 @@ extern "C" int pn_index_set_option(pn_index *ix, int option, int64_t value) {
             ix->shared_tau = (int)value;
             return PN_OK;
         case PN_OPT_BF16_WAVES:
-            if (value != 0 && value != 4 && value != 8 && value != 16) return fail(PN_ERR_INVALID, "bad wave count (0, 4, 8 or 16)");
+            if (value != 0 && value != 4 && value != 8 && value != 16 && value != 32)
+                return fail(PN_ERR_INVALID, "bad wave count (0, 4, 8, 16 or 32)");
             ix->bf16_waves = (int)value;
             return PN_OK;
         case PN_OPT_SEED_MODEL:
@@ -1864,9 +1865,9 @@ static Bf16Plan bf16_plan(const pn_index *ix, size_t nq_pad, size_t kout, int le
                                      bf16_image_bytes(ix->n, (int)ix->dim, ix->bf16_ci), 2 * ix->n_cu, ix->bf16_waves);
     if (plan_knobs().debug)  // development aid: what a call was planned as
         fprintf(stderr, "bf16_plan: n %zu q_tiles %zu k %zu R %.0f: n_wg %d per_tile %zu split %d nseg %d kp %d cap %d aligned %d "
-                        "shared_scout %d scout_tiles %d seed_rank %d scout_max %d n_refresh %d sh_rank %d model_seed %d z %.3f\n",
+                        "shared_scout %d scout_tiles %d seed_rank %d scout_max %d n_refresh %d sh_rank %d model_seed %d z %.3f run_tiles %u\n",
                 ix->n, q_tiles, kout, R, p.grid.n_wg, per_tile, split, p.grid.nseg, p.kp, p.cap, (int)p.grid.aligned, (int)p.shared_scout,
-                p.scout_tiles, p.seed_rank, p.scout_max, p.n_refresh, p.sh_rank, (int)p.model_seed, p.model_z);
+                p.scout_tiles, p.seed_rank, p.scout_max, p.n_refresh, p.sh_rank, (int)p.model_seed, p.model_z, p.grid.run_tiles);
     return p;
 }
 // Plan of the f32 MFMA tier for one call: query_enqueue asks it whether the tier serves the call at all (ok), run_mfma

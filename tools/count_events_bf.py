@@ -17,8 +17,12 @@ if slots: t.set_option(_lib.PN_OPT_FILTER_SLOTS, slots)
 if os.environ.get('PN_SH') is not None: t.set_option(_lib.PN_OPT_SHARED_THRESHOLDS, int(os.environ['PN_SH']))
 f = L.pn_debug_read_bf; f.restype = C.c_int; f.argtypes = [C.c_void_p, C.c_int]
 out = (C.c_ulonglong * 16)()
-t.query_device(qs, k); torch.cuda.synchronize(); f(out, 1)
-t.query_device(qs, k); torch.cuda.synchronize(); f(out, 1)
+# the paired kernels keep the counters of their lagging half (waves 4-7) apart (count_events_pair.py): summed here
+g = L.pn_debug_read_bf_lag; g.restype = C.c_int; g.argtypes = [C.c_void_p, C.c_int]
+lag = (C.c_ulonglong * 16)()
+t.query_device(qs, k); torch.cuda.synchronize(); f(out, 1); g(lag, 1)
+t.query_device(qs, k); torch.cuda.synchronize(); f(out, 1); g(lag, 1)
+for i in range(16): out[i] += lag[i]
 waves = 480 * 4
 cyc = lambda i: float(out[i])   # s_memtime ticks = shader cycles (MI355X_MICROARCH.md, constants table)
 run = cyc(7) / waves

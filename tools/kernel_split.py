@@ -4,7 +4,7 @@
 usage: tools/kernel_split.py <kernel_stats.csv> <config key> [committed csv name] > profiles/rNN_<cfg>_kernel_split.json
 The scout-only launch is the instantiation with MODE = 1 (bf16_filter_kernel<KS, M, RAD, CI, 1, ...>, or the wide kernel's
 shorter launch); everything else of the dominant kernel's name is the main launch (bf16_filter_kernel<..., 2, ...>,
-bf16_filter8_kernel or bf16_filter_kernel_pair)."""
+bf16_filter8_kernel, bf16_filter_kernel_pair or bf16_filter_kernel_meet_pair)."""
 import csv, json, re, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
 cfg = sys.argv[2]
@@ -16,7 +16,7 @@ for r in rows:
     m = re.search(r"bf16_filter_kernel<(\d+), (\d+), (\w+), (\w+), (\d+)", n)
     if m:
         (scout if m.group(5) == "1" else main).append((avg, calls, n[:90]))
-    elif "bf16_filter8_kernel" in n or "bf16_filter_kernel_pair" in n:
+    elif "bf16_filter8_kernel" in n or "bf16_filter_kernel_pair" in n or "bf16_filter_kernel_meet_pair" in n:
         main.append((avg, calls, n[:90]))
     elif "bf16_wide_kernel" in n:
         other.append((avg, calls, n[:90]))
