@@ -15,11 +15,13 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 #include "../../include/petal_mi355x.h"
 #include "pn_internal.h"
 #include "csr_pieces.h"
+#include "host_io.h"
 
 using namespace pn;
 
@@ -137,7 +139,7 @@ struct WorkspaceBufs {
     DevBuf w_q, w_qnorm, w_qnrm, w_keys, w_idx, w_cnt, w_tau, w_flags, w_sel, w_misc, w2_keys, w2_idx, w2_cnt, w2_tau, w_lo;
     DevBuf w_bq, w_qn, w_qbad, w_gq, w_gqn, w_gsel, w_seed, w_lists;  // bf16 tier, second tier
     DevBuf w_hq, w_hidx, w_hdist;  // staging of the host entry points (queries up, results down)
-    DevBuf w_hrad;                 // pn_query_radii_*: the host entry points' radii, uploaded
+    DevBuf w_io;                   // the host entry points' other inputs and outputs: one buffer, carved per call (HostIo)
     DevBuf w_fparts;               // second tier, many-segment path: per-group partial results
     DevBuf w_rpos, w_rfin, w_rcx, w_rox, w_rscan;  // pn_query_radius_device_*: list positions, counts, per-segment counts / offsets, scan scratch
     DevBuf w_rkd;  // pn_query_radius_with_distance_*: the filter tier's kept rows' distances ([2][nq][kept_stride])
@@ -146,31 +148,25 @@ struct WorkspaceBufs {
     // inner offsets and scanned counts, self flags (+ the disagreement word), adjusted counts, scan scratch, and the host
     // radius entry's offsets + total
     DevBuf w_sf_idx, w_sf_dist, w_sf_off, w_sf_coff, w_sf_flag, w_sf_cnt, w_sf_scan, w_sf_hoff;
-    // pn_dbscan_*: the O(n) arrays of a call (offsets, parents, roots, ... carved from one buffer), the border rows' side
-    // lists, and the host entry's outputs
-    DevBuf w_db, w_db_side, w_db_out;
-    // pn_mst_*: the scratch of mst.hip (+ round 0's 1-NN answer), and the host entry's core distances and outputs
-    DevBuf w_mst, w_mst_io;
-    // pn_linkage_* / pn_hdbscan_*: the scratch of linkage.hip (+ the core distances and the tree edges of an HDBSCAN call),
-    // and the host entries' inputs and outputs
-    DevBuf w_hdb, w_hdb_io;
+    // pn_dbscan_*: the O(n) arrays of a call (offsets, parents, roots, ... carved from one buffer) and the border rows'
+    // side lists
+    DevBuf w_db, w_db_side;
+    DevBuf w_mst;  // pn_mst_*: the scratch of mst.hip (+ round 0's 1-NN answer)
+    // pn_linkage_* / pn_hdbscan_*: the scratch of linkage.hip (+ the core distances and the tree edges of an HDBSCAN call)
+    DevBuf w_hdb;
     // pn_lof_* / pn_lof_score_*: the graph store of a fit ([n][k] uint32 ids, [n][k] distances; + lrd and kdist when the
-    // caller keeps neither), and the host entries' inputs and outputs
-    DevBuf w_lof, w_lof_io;
-    // pn_knn_classify_* / pn_knn_regress_*: the host entries' labels or targets and their outputs
-    DevBuf w_knn_io;
-    // pn_optics_* / pn_optics_dbscan_*: the O(n) arrays of a call (offsets, radii, the tournament tree), the graph store
-    // (uint32 ids and distances of every core row's list), and the host entries' inputs and outputs
-    DevBuf w_opt, w_opt_graph, w_opt_io;
-    // pn_kde_*: the O(nq) arrays of a call (offsets, bandwidths, cutoffs; + count when the caller keeps none), and the host
-    // entries' inputs and outputs
-    DevBuf w_kde, w_kde_io;
+    // caller keeps neither)
+    DevBuf w_lof;
+    // pn_optics_* / pn_optics_dbscan_*: the O(n) arrays of a call (offsets, radii, the tournament tree) and the graph store
+    // (uint32 ids and distances of every core row's list)
+    DevBuf w_opt, w_opt_graph;
+    DevBuf w_kde;  // pn_kde_*: the O(nq) arrays of a call (offsets, bandwidths, cutoffs; + count when the caller keeps none)
     // pn_mean_shift_*: the O(active seeds) arrays of a call (offsets, two copies of positions, bandwidths and slots, the
-    // stop flags) or the merge's scratch, and the host entries' inputs and outputs
-    DevBuf w_ms, w_ms_io;
+    // stop flags) or the merge's scratch
+    DevBuf w_ms;
     // pn_kmeans_*: the packed rows (once per call), the packed centres, the O(n) arrays of an assignment (candidates,
-    // thresholds, the list of unproven rows, distances, inertia segments), the update's scratch, the host entries' staging
-    DevBuf w_km_rows, w_km_cent, w_km, w_km_upd, w_km_io;
+    // thresholds, the list of unproven rows, distances, inertia segments), the update's scratch
+    DevBuf w_km_rows, w_km_cent, w_km, w_km_upd;
     DevBuf w_pcnt;                 // shared thresholds: the segments' published fill counts [nseg][nq_pad]
 };
 static_assert(std::is_standard_layout<WorkspaceBufs>::value && sizeof(WorkspaceBufs) % sizeof(DevBuf) == 0,
@@ -844,6 +840,68 @@ private:
         lease.s = st;
         return ws_acquire(lease.ix, &lease.s, own, &lease.ws);
     }
+};
+// What a host entry point stages besides its query rows: its other inputs go up into HBM and its outputs come down, all
+// through slots of the workspace's one w_io, laid out by IoLayout (host_io.h).  The entry declares its slots -- a braced
+// list, so in the order their copies are issued -- then up(), then the enqueue on io[slot], then down().  An output slot
+// is reserved whether or not the caller wants the array back: several enqueues need it either way.
+// One buffer serves every family because (read in this file, both hold for every entry):
+//   - no *_enqueue / *_run touches w_io: they are handed pointers into it, never the workspace member;
+//   - no host entry calls another host entry inside its CallScope, so a call's slots stay its own until it returns.
+template <typename U>
+struct IoSlot {
+    size_t i;
+};
+struct HostIo {
+    explicit HostIo(const CallScope &call) : buf(call.ws().w_io), s(call.s()) {}
+    // slots; a NULL host pointer reserves the slot and copies nothing
+    template <typename U>
+    IoSlot<U> inout(const U *from, U *to, size_t count) {
+        const size_t i = lay.add(sizeof(U), count);
+        if (i < kIoSlots) src[i] = from, dst[i] = to;
+        return {i};
+    }
+    template <typename U>
+    IoSlot<U> in(const U *h, size_t count) {
+        return inout<U>(h, nullptr, count);
+    }
+    template <typename U>
+    IoSlot<U> out(U *h, size_t count) {
+        return inout<U>(nullptr, h, count);
+    }
+    // the buffer, then the inputs' copies; after it io[slot] is the slot's device array
+    int up() {
+        if (!lay.ok) return fail(PN_ERR_NOMEM, "the staged arrays of the call exceed the address space");
+        PNCHK(buf.ensure(lay.total));
+        for (size_t i = 0; i < lay.slots; ++i)
+            if (src[i] && lay.bytes[i]) HIPCHK(hipMemcpyAsync(at(i), src[i], lay.bytes[i], hipMemcpyHostToDevice, s));
+        return PN_OK;
+    }
+    template <typename U>
+    U *operator[](IoSlot<U> k) const {
+        return (U *)at(k.i);
+    }
+    // the first `count` elements of one slot, now (for an entry that reads a word back and acts on it)
+    template <typename U>
+    int fetch(IoSlot<U> k, U *h, size_t count) {
+        if (h && count) HIPCHK(hipMemcpyAsync(h, at(k.i), count * sizeof(U), hipMemcpyDeviceToHost, s));
+        return PN_OK;
+    }
+    // the outputs' copies, then the wait for the stream
+    int down() {
+        for (size_t i = 0; i < lay.slots; ++i)
+            if (dst[i] && lay.bytes[i]) HIPCHK(hipMemcpyAsync(dst[i], at(i), lay.bytes[i], hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return PN_OK;
+    }
+
+private:
+    DevBuf &buf;
+    hipStream_t s;
+    IoLayout lay;
+    const void *src[kIoSlots] = {};
+    void *dst[kIoSlots] = {};
+    char *at(size_t i) const { return (char *)buf.p + lay.off[i]; }
 };
 
 // folds a finished record into the host-side statistics and the tier plan (caller holds sh.mu)
@@ -3523,9 +3581,10 @@ static int radius_self_host(const pn_index *ix, T radius, unsigned flags, uint64
     uint32_t bad = 0;
     RadiusCall<T> c{{}, within(radius), {d_off, nullptr, nullptr, 0, d_tot}, flags};  // (the counting pass counts the rows)
     if (per_row) {
-        PNCHK(ws.w_hrad.ensure(n * sizeof(T)));
-        HIPCHK(hipMemcpyAsync(ws.w_hrad.p, radii, n * sizeof(T), hipMemcpyHostToDevice, s));
-        c.within = within_each((const T *)ws.w_hrad.p);
+        HostIo io(call);
+        const auto d_radii = io.in(radii, n);
+        PNCHK(io.up());
+        c.within = within_each((const T *)io[d_radii]);
     }
     PNCHK(radius_self_enqueue<T>(ix, ws, c, s));
     HIPCHK(hipMemcpyAsync(&total, d_tot, sizeof total, hipMemcpyDeviceToHost, s));
@@ -3697,19 +3756,12 @@ static int dbscan_host(const pn_index *ix, T eps, size_t min_samples, unsigned f
     PNCHK(dbscan_args(ix, flags, min_samples, labels, (int)sizeof(T)));
     CallScope call(ix);
     PNCHK(call.own_stream());
-    Workspace &ws = call.ws();
-    hipStream_t s = call.s();
     const size_t n = ix->n;
-    PNCHK(ws.w_db_out.ensure((n + 1) * sizeof(uint64_t) + n));
-    int64_t *d_labels = (int64_t *)ws.w_db_out.p;
-    uint64_t *d_ncl = (uint64_t *)(d_labels + n);
-    uint8_t *d_core = (uint8_t *)(d_ncl + 1);
-    PNCHK(dbscan_enqueue<T>(ix, ws, eps, min_samples, d_labels, d_core, d_ncl, s));
-    HIPCHK(hipMemcpyAsync(labels, d_labels, n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    if (core) HIPCHK(hipMemcpyAsync(core, d_core, n, hipMemcpyDeviceToHost, s));
-    if (n_clusters) HIPCHK(hipMemcpyAsync(n_clusters, d_ncl, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return PN_OK;
+    HostIo io(call);
+    const auto [d_labels, d_core, d_ncl] = std::tuple{io.out(labels, n), io.out(core, n), io.out(n_clusters, 1)};
+    PNCHK(io.up());
+    PNCHK(dbscan_enqueue<T>(ix, call.ws(), eps, min_samples, io[d_labels], io[d_core], io[d_ncl], call.s()));
+    return io.down();
 }
 extern "C" int pn_dbscan_f32(const pn_index *ix, float eps, size_t min_samples, unsigned flags, int64_t *labels,
                              uint8_t *core, uint64_t *n_clusters) {
@@ -3829,20 +3881,14 @@ static int optics_host(const pn_index *ix, size_t min_samples, T max_eps, unsign
     PNCHK(optics_args(ix, min_samples, flags, ordering, reach, (int)sizeof(T)));
     CallScope call(ix);
     PNCHK(call.own_stream());
-    Workspace &ws = call.ws();
-    hipStream_t s = call.s();
     const size_t n = ix->n;
-    PNCHK(ws.w_opt_io.ensure(2 * n * sizeof(uint64_t) + 2 * n * sizeof(T)));
-    uint64_t *d_ordering = (uint64_t *)ws.w_opt_io.p;
-    int64_t *d_pred = (int64_t *)(d_ordering + n);
-    T *d_reach = (T *)(d_pred + n), *d_core = d_reach + n;
-    PNCHK(optics_enqueue<T>(ix, ws, min_samples, max_eps, d_ordering, d_reach, d_pred, d_core, s));
-    HIPCHK(hipMemcpyAsync(ordering, d_ordering, n * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(reach, d_reach, n * sizeof(T), hipMemcpyDeviceToHost, s));
-    if (pred) HIPCHK(hipMemcpyAsync(pred, d_pred, n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    if (core) HIPCHK(hipMemcpyAsync(core, d_core, n * sizeof(T), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return PN_OK;
+    HostIo io(call);
+    const auto [d_ordering, d_reach, d_pred, d_core] =
+        std::tuple{io.out(ordering, n), io.out(reach, n), io.out(pred, n), io.out(core, n)};
+    PNCHK(io.up());
+    PNCHK(optics_enqueue<T>(ix, call.ws(), min_samples, max_eps, io[d_ordering], io[d_reach], io[d_pred], io[d_core],
+                            call.s()));
+    return io.down();
 }
 extern "C" int pn_optics_f32(const pn_index *ix, size_t min_samples, float max_eps, unsigned flags, uint64_t *ordering,
                              float *reachability, int64_t *predecessor, float *core_distances) {
@@ -3897,24 +3943,15 @@ static int optics_dbscan_host(const pn_index *ix, const uint64_t *ordering, cons
     PNCHK(optics_dbscan_args(ix, ordering, reach, core, flags, labels, (int)sizeof(T)));
     CallScope call(ix);
     PNCHK(call.own_stream());
-    Workspace &ws = call.ws();
-    hipStream_t s = call.s();
     const size_t n = ix->n;
-    PNCHK(ws.w_opt_io.ensure((2 * n + 2) * sizeof(uint64_t) + 2 * n * sizeof(T)));
-    uint64_t *d_ordering = (uint64_t *)ws.w_opt_io.p;
-    int64_t *d_labels = (int64_t *)(d_ordering + n);
-    uint64_t *d_ncl = (uint64_t *)(d_labels + n);
-    int32_t *d_err = (int32_t *)(d_ncl + 1);
-    T *d_reach = (T *)(d_ncl + 2), *d_core = d_reach + n;
-    HIPCHK(hipMemcpyAsync(d_ordering, ordering, n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_reach, reach, n * sizeof(T), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_core, core, n * sizeof(T), hipMemcpyHostToDevice, s));
-    PNCHK(optics_dbscan_enqueue<T>(ix, ws, d_ordering, d_reach, d_core, eps, d_labels, d_ncl, d_err, s));
     int32_t err = PN_OK;
-    HIPCHK(hipMemcpyAsync(&err, d_err, sizeof err, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(labels, d_labels, n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    if (n_clusters) HIPCHK(hipMemcpyAsync(n_clusters, d_ncl, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    HostIo io(call);
+    const auto [d_ordering, d_reach, d_core, d_err, d_labels, d_ncl] = std::tuple{
+        io.in(ordering, n), io.in(reach, n), io.in(core, n), io.out(&err, 1), io.out(labels, n), io.out(n_clusters, 1)};
+    PNCHK(io.up());
+    PNCHK(optics_dbscan_enqueue<T>(ix, call.ws(), io[d_ordering], io[d_reach], io[d_core], eps, io[d_labels], io[d_ncl],
+                                   io[d_err], call.s()));
+    PNCHK(io.down());
     if (err != PN_OK) return fail(PN_ERR_INVALID, "ordering is not a permutation of the rows 0 .. n - 1");
     return PN_OK;
 }
@@ -4018,24 +4055,14 @@ static int mst_host(const pn_index *ix, const T *core, unsigned flags, uint64_t 
     PNCHK(mst_args(ix, flags, src, dst, weight, (int)sizeof(T)));
     CallScope call(ix);
     PNCHK(call.own_stream());
-    Workspace &ws = call.ws();
-    hipStream_t s = call.s();
     const size_t n = ix->n, ne = n ? n - 1 : 0;
-    PNCHK(ws.w_mst_io.ensure(2 * ne * sizeof(uint64_t) + (ne + n) * sizeof(T) + 64));
-    uint64_t *d_src = (uint64_t *)ws.w_mst_io.p, *d_dst = d_src + ne;
-    T *d_weight = (T *)(d_dst + ne), *d_core = nullptr;
-    if (core && n > 1) {
-        d_core = d_weight + ne;
-        HIPCHK(hipMemcpyAsync(d_core, core, n * sizeof(T), hipMemcpyHostToDevice, s));
-    }
-    PNCHK(mst_run<T>(ix, ws, d_core, d_src, d_dst, d_weight, work_out, s));
-    if (ne) {
-        HIPCHK(hipMemcpyAsync(src, d_src, ne * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(dst, d_dst, ne * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(weight, d_weight, ne * sizeof(T), hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(hipStreamSynchronize(s));
-    return PN_OK;
+    HostIo io(call);
+    const auto [d_core, d_src, d_dst, d_weight] =
+        std::tuple{io.in(core, ne ? n : 0), io.out(src, ne), io.out(dst, ne), io.out(weight, ne)};
+    PNCHK(io.up());
+    PNCHK(mst_run<T>(ix, call.ws(), core && ne ? io[d_core] : nullptr, io[d_src], io[d_dst], io[d_weight], work_out,
+                     call.s()));
+    return io.down();
 }
 extern "C" int pn_mst_f32(const pn_index *ix, const float *core, unsigned flags, uint64_t *src_out, uint64_t *dst_out,
                           float *weight_out, uint64_t *work_out) {
@@ -4110,26 +4137,17 @@ static int linkage_host(const pn_index *ix, const uint64_t *src, const uint64_t 
     if (ix->n < 2) return PN_OK;
     CallScope call(ix);
     PNCHK(call.own_stream());
-    Workspace &ws = call.ws();
-    hipStream_t s = call.s();
     const size_t n = ix->n, ne = n - 1;
-    PNCHK(ws.w_hdb.ensure(linkage_buffer_bytes(n)));
-    PNCHK(ws.w_hdb_io.ensure(5 * ne * sizeof(uint64_t) + 2 * ne * sizeof(T) + 64));
-    uint64_t *d_src = (uint64_t *)ws.w_hdb_io.p, *d_dst = d_src + ne, *d_left = d_dst + ne, *d_right = d_left + ne,
-             *d_size = d_right + ne;
-    T *d_w = (T *)(d_size + ne), *d_wo = d_w + ne;
-    int32_t *d_err = (int32_t *)(d_wo + ne);
-    HIPCHK(hipMemcpyAsync(d_src, src, ne * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_dst, dst, ne * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_w, weight, ne * sizeof(T), hipMemcpyHostToDevice, s));
-    PNCHK(linkage_run<T>(ix, ws.w_hdb.p, d_src, d_dst, d_w, d_left, d_right, d_wo, d_size, d_err, s));
+    PNCHK(call.ws().w_hdb.ensure(linkage_buffer_bytes(n)));
     int32_t err = 0;
-    HIPCHK(hipMemcpyAsync(left, d_left, ne * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(right, d_right, ne * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(size, d_size, ne * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(weight_out, d_wo, ne * sizeof(T), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&err, d_err, sizeof err, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    HostIo io(call);
+    const auto [d_src, d_dst, d_w, d_left, d_right, d_size, d_wo, d_err] =
+        std::tuple{io.in(src, ne),    io.in(dst, ne),   io.in(weight, ne),      io.out(left, ne),
+                   io.out(right, ne), io.out(size, ne), io.out(weight_out, ne), io.out(&err, 1)};
+    PNCHK(io.up());
+    PNCHK(linkage_run<T>(ix, call.ws().w_hdb.p, io[d_src], io[d_dst], io[d_w], io[d_left], io[d_right], io[d_wo], io[d_size],
+                         io[d_err], call.s()));
+    PNCHK(io.down());
     if (err) return fail(PN_ERR_INVALID, "the edges are not a spanning tree of the %zu indexed rows", n);
     return PN_OK;
 }
@@ -4218,19 +4236,12 @@ static int hdbscan_host(const pn_index *ix, size_t min_samples, size_t min_clust
     PNCHK(hdbscan_args(ix, min_samples, min_cluster_size, flags, labels, (int)sizeof(T)));
     CallScope call(ix);
     PNCHK(call.own_stream());
-    Workspace &ws = call.ws();
-    hipStream_t s = call.s();
     const size_t n = ix->n;
-    PNCHK(ws.w_hdb_io.ensure((n + 1) * sizeof(uint64_t) + n * sizeof(T)));
-    int64_t *d_labels = (int64_t *)ws.w_hdb_io.p;
-    uint64_t *d_ncl = (uint64_t *)(d_labels + n);
-    T *d_prob = (T *)(d_ncl + 1);
-    PNCHK(hdbscan_enqueue<T>(ix, ws, min_samples, min_cluster_size, d_labels, d_prob, d_ncl, s));
-    if (n) HIPCHK(hipMemcpyAsync(labels, d_labels, n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    if (prob && n) HIPCHK(hipMemcpyAsync(prob, d_prob, n * sizeof(T), hipMemcpyDeviceToHost, s));
-    if (n_clusters) HIPCHK(hipMemcpyAsync(n_clusters, d_ncl, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return PN_OK;
+    HostIo io(call);
+    const auto [d_labels, d_prob, d_ncl] = std::tuple{io.out(labels, n), io.out(prob, n), io.out(n_clusters, 1)};
+    PNCHK(io.up());
+    PNCHK(hdbscan_enqueue<T>(ix, call.ws(), min_samples, min_cluster_size, io[d_labels], io[d_prob], io[d_ncl], call.s()));
+    return io.down();
 }
 extern "C" int pn_hdbscan_f32(const pn_index *ix, size_t min_samples, size_t min_cluster_size, unsigned flags, int64_t *labels,
                               float *probabilities, uint64_t *n_clusters) {
@@ -4319,18 +4330,12 @@ static int lof_host(const pn_index *ix, size_t k, unsigned flags, double *lof, d
     PNCHK(lof_args(ix, k, flags, lof, (int)sizeof(T)));
     CallScope call(ix);
     PNCHK(call.own_stream());
-    Workspace &ws = call.ws();
-    hipStream_t s = call.s();
     const size_t n = ix->n;
-    PNCHK(ws.w_lof_io.ensure(2 * n * sizeof(double) + n * sizeof(T)));
-    double *d_lof = (double *)ws.w_lof_io.p, *d_lrd = d_lof + n;
-    T *d_kdist = (T *)(d_lrd + n);
-    PNCHK(lof_enqueue<T>(ix, ws, k, d_lof, d_lrd, d_kdist, s));
-    HIPCHK(hipMemcpyAsync(lof, d_lof, n * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (lrd) HIPCHK(hipMemcpyAsync(lrd, d_lrd, n * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (kdist) HIPCHK(hipMemcpyAsync(kdist, d_kdist, n * sizeof(T), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return PN_OK;
+    HostIo io(call);
+    const auto [d_lof, d_lrd, d_kdist] = std::tuple{io.out(lof, n), io.out(lrd, n), io.out(kdist, n)};
+    PNCHK(io.up());
+    PNCHK(lof_enqueue<T>(ix, call.ws(), k, io[d_lof], io[d_lrd], io[d_kdist], call.s()));
+    return io.down();
 }
 extern "C" int pn_lof_f32(const pn_index *ix, size_t k, unsigned flags, double *lof, double *lrd, float *kdist) {
     return lof_host<float>(ix, k, flags, lof, lrd, kdist);
@@ -4382,15 +4387,12 @@ static int lof_score_host(const pn_index *ix, const T *q, size_t nq, size_t q_co
     hipStream_t s = call.s();
     const size_t n = ix->n;
     PNCHK(upload_rows_to<T>(q, nq, q_cols, q_stride, ws.w_hq, s));
-    PNCHK(ws.w_lof_io.ensure((n + nq) * sizeof(double) + n * sizeof(T)));
-    double *d_lrd = (double *)ws.w_lof_io.p, *d_score = d_lrd + n;
-    T *d_kdist = (T *)(d_score + nq);
-    HIPCHK(hipMemcpyAsync(d_lrd, lrd, n * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_kdist, kdist, n * sizeof(T), hipMemcpyHostToDevice, s));
-    PNCHK(lof_score_enqueue<T>(ix, ws, (const T *)ws.w_hq.p, nq, q_cols, q_cols ? q_cols : 1, k, d_lrd, d_kdist, d_score, s));
-    HIPCHK(hipMemcpyAsync(score, d_score, nq * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return PN_OK;
+    HostIo io(call);
+    const auto [d_lrd, d_kdist, d_score] = std::tuple{io.in(lrd, n), io.in(kdist, n), io.out(score, nq)};
+    PNCHK(io.up());
+    PNCHK(lof_score_enqueue<T>(ix, ws, (const T *)ws.w_hq.p, nq, q_cols, q_cols ? q_cols : 1, k, io[d_lrd], io[d_kdist],
+                               io[d_score], s));
+    return io.down();
 }
 extern "C" int pn_lof_score_f32(const pn_index *ix, const float *queries, size_t nq, size_t q_cols, ptrdiff_t q_row_stride,
                                 size_t k, const double *lrd, const float *kdist, unsigned flags, double *score_out) {
@@ -4510,21 +4512,17 @@ static int knn_predict_host(const pn_index *ix, const KnnPredict &p, const T *q,
     Workspace &ws = call.ws();
     hipStream_t s = call.s();
     if (!p.self) PNCHK(upload_rows_to<T>(q, nq, q_cols, q_stride, ws.w_hq, s));
-    const size_t values_bytes = n * (p.classify ? sizeof(int64_t) : p.width * sizeof(double));
-    const size_t pred_bytes = p.classify ? count * sizeof(int64_t) : 0;
-    const size_t out_bytes = p.out ? count * p.width * sizeof(double) : 0;
-    PNCHK(ws.w_knn_io.ensure(round_up(values_bytes, (size_t)16) + round_up(pred_bytes, (size_t)16) + out_bytes));
-    char *base = (char *)ws.w_knn_io.p;
+    HostIo io(call);
+    // (values: 8-byte words either way, int64 labels [n] or double targets [n][width])
+    const auto [d_values, d_pred, d_out] = std::tuple{io.in((const uint64_t *)p.values, p.classify ? n : n * p.width),
+                                                      io.out(p.pred, p.classify ? count : 0), io.out(p.out, p.out ? count * p.width : 0)};
+    PNCHK(io.up());
     KnnPredict d = p;
-    d.values = base;
-    d.pred = p.classify ? (int64_t *)(base + round_up(values_bytes, (size_t)16)) : nullptr;
-    d.out = p.out ? (double *)(base + round_up(values_bytes, (size_t)16) + round_up(pred_bytes, (size_t)16)) : nullptr;
-    HIPCHK(hipMemcpyAsync(base, p.values, values_bytes, hipMemcpyHostToDevice, s));
+    d.values = io[d_values];
+    d.pred = p.classify ? io[d_pred] : nullptr;
+    d.out = p.out ? io[d_out] : nullptr;
     PNCHK(knn_predict_enqueue<T>(ix, ws, d, p.self ? nullptr : (const T *)ws.w_hq.p, count, q_cols, q_cols ? q_cols : 1, k, s));
-    if (p.classify) HIPCHK(hipMemcpyAsync(p.pred, d.pred, pred_bytes, hipMemcpyDeviceToHost, s));
-    if (p.out) HIPCHK(hipMemcpyAsync(p.out, d.out, out_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return PN_OK;
+    return io.down();
 }
 static KnnPredict knn_classify_call(bool self, const int64_t *labels, size_t n_classes, unsigned flags, int64_t *pred, double *proba) {
     KnnPredict p;
@@ -4626,12 +4624,13 @@ static int radii_host(const pn_index *ix, const T *q, size_t nq, size_t q_cols, 
     Workspace &ws = call.ws();
     hipStream_t s = call.s();
     PNCHK(upload_rows_to<T>(q, nq, q_cols, q_stride, ws.w_hq, s));
-    PNCHK(ws.w_hrad.ensure(nq * sizeof(T)));
-    HIPCHK(hipMemcpyAsync(ws.w_hrad.p, radii, nq * sizeof(T), hipMemcpyHostToDevice, s));
+    HostIo io(call);
+    const auto d_radii = io.in(radii, nq);
+    PNCHK(io.up());
     PNCHK(ws.w_sf_hoff.ensure((nq + 2) * sizeof(uint64_t)));
     uint64_t *d_off = (uint64_t *)ws.w_sf_hoff.p, *d_tot = d_off + nq + 1;
     uint64_t total = 0;
-    RadiusCall<T> c{{(const T *)ws.w_hq.p, nq, q_cols, q_cols ? q_cols : 1}, within_each((const T *)ws.w_hrad.p),
+    RadiusCall<T> c{{(const T *)ws.w_hq.p, nq, q_cols, q_cols ? q_cols : 1}, within_each((const T *)io[d_radii]),
                     {d_off, nullptr, nullptr, 0, d_tot}, flags};
     c.count_queries = false;  // (pn_stats.queries is left alone, as by pn_query_radius_*)
     c.add_listed = true;      // (once, by the counting pass)
@@ -4729,6 +4728,18 @@ static int kde_args(const pn_index *ix, unsigned flags, unsigned allowed, int ke
     if (nq > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many queries in one call");
     return PN_OK;
 }
+// (kde_args for the host and the device entry alike; a self call's *nq becomes the number of rows)
+static int kde_call_args(const pn_index *ix, bool self, const void *q, size_t *nq, size_t q_cols, const void *h, size_t n_h,
+                         int kernel, double atol, unsigned flags, const void *sum, const void *count, int elem_bytes) {
+    const char *null_input = self ? (!h ? "h" : nullptr) : *nq ? (!q && q_cols ? "queries" : !h ? "h" : nullptr) : nullptr;
+    PNCHK(kde_args(ix, flags, self ? (unsigned)PN_SELF_INCLUDE : 0u, kernel, atol, sum, count, null_input, n_h,
+                   self ? n_h : *nq, elem_bytes));
+    if (self) {
+        *nq = ix->n;
+        if (n_h != 1 && n_h != *nq) return fail(PN_ERR_INVALID, "n_h must be 1 or the number of rows (%zu)", *nq);
+    }
+    return PN_OK;
+}
 // in a held workspace, on stream s; everything in HBM; nq >= 1.  self: the queries are the indexed rows (d_q is not
 // looked at, nq = n), flags = PN_SELF_INCLUDE or 0.  Blocks the host once (after the counting pass) when d_sum is given.
 template <typename T>
@@ -4784,13 +4795,7 @@ template <typename T>
 static int kde_device(const pn_index *ix, bool self, const T *d_q, size_t nq, size_t q_cols, size_t q_stride, const T *d_h,
                       size_t n_h, int kernel, double atol, unsigned flags, double *d_sum, uint64_t *d_count, T *d_cutoff,
                       hipStream_t s) {
-    const char *null_input = self ? (!d_h ? "h" : nullptr) : nq ? (!d_q && q_cols ? "queries" : !d_h ? "h" : nullptr) : nullptr;
-    PNCHK(kde_args(ix, flags, self ? (unsigned)PN_SELF_INCLUDE : 0u, kernel, atol, d_sum, d_count, null_input, n_h,
-                   self ? n_h : nq, (int)sizeof(T)));
-    if (self) {
-        nq = ix->n;
-        if (n_h != 1 && n_h != nq) return fail(PN_ERR_INVALID, "n_h must be 1 or the number of rows (%zu)", nq);
-    }
+    PNCHK(kde_call_args(ix, self, d_q, &nq, q_cols, d_h, n_h, kernel, atol, flags, d_sum, d_count, (int)sizeof(T)));
     if (nq == 0) return PN_OK;
     CallScope call(ix);
     PNCHK(call.on_stream(s));
@@ -4800,13 +4805,7 @@ static int kde_device(const pn_index *ix, bool self, const T *d_q, size_t nq, si
 template <typename T>
 static int kde_host(const pn_index *ix, bool self, const T *q, size_t nq, size_t q_cols, ptrdiff_t q_stride, const T *h,
                     size_t n_h, int kernel, double atol, unsigned flags, double *sum, uint64_t *count, T *cutoff) {
-    const char *null_input = self ? (!h ? "h" : nullptr) : nq ? (!q && q_cols ? "queries" : !h ? "h" : nullptr) : nullptr;
-    PNCHK(kde_args(ix, flags, self ? (unsigned)PN_SELF_INCLUDE : 0u, kernel, atol, sum, count, null_input, n_h,
-                   self ? n_h : nq, (int)sizeof(T)));
-    if (self) {
-        nq = ix->n;
-        if (n_h != 1 && n_h != nq) return fail(PN_ERR_INVALID, "n_h must be 1 or the number of rows (%zu)", nq);
-    }
+    PNCHK(kde_call_args(ix, self, q, &nq, q_cols, h, n_h, kernel, atol, flags, sum, count, (int)sizeof(T)));
     if (nq == 0) return PN_OK;
     if (n_h == 1 && !(h[0] > (T)0 && h[0] < (T)INFINITY))
         return fail(PN_ERR_INVALID, "the bandwidth must be finite and positive");
@@ -4815,18 +4814,13 @@ static int kde_host(const pn_index *ix, bool self, const T *q, size_t nq, size_t
     Workspace &ws = call.ws();
     hipStream_t s = call.s();
     if (!self) PNCHK(upload_rows_to<T>(q, nq, q_cols, q_stride, ws.w_hq, s));
-    PNCHK(ws.w_kde_io.ensure(nq * (sizeof(double) + sizeof(uint64_t) + sizeof(T)) + n_h * sizeof(T)));
-    double *d_sum = (double *)ws.w_kde_io.p;
-    uint64_t *d_count = (uint64_t *)(d_sum + nq);
-    T *d_cutoff = (T *)(d_count + nq), *d_h = d_cutoff + nq;
-    HIPCHK(hipMemcpyAsync(d_h, h, n_h * sizeof(T), hipMemcpyHostToDevice, s));
-    PNCHK(kde_enqueue<T>(ix, ws, self, self ? nullptr : (const T *)ws.w_hq.p, nq, q_cols, q_cols ? q_cols : 1, d_h, n_h, kernel,
-                         atol, flags, sum ? d_sum : nullptr, count ? d_count : nullptr, d_cutoff, s));
-    if (sum) HIPCHK(hipMemcpyAsync(sum, d_sum, nq * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (count) HIPCHK(hipMemcpyAsync(count, d_count, nq * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    if (cutoff) HIPCHK(hipMemcpyAsync(cutoff, d_cutoff, nq * sizeof(T), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return PN_OK;
+    HostIo io(call);
+    const auto [d_h, d_sum, d_count, d_cutoff] =
+        std::tuple{io.in(h, n_h), io.out(sum, nq), io.out(count, nq), io.out(cutoff, nq)};
+    PNCHK(io.up());
+    PNCHK(kde_enqueue<T>(ix, ws, self, self ? nullptr : (const T *)ws.w_hq.p, nq, q_cols, q_cols ? q_cols : 1, io[d_h], n_h,
+                         kernel, atol, flags, sum ? io[d_sum] : nullptr, count ? io[d_count] : nullptr, io[d_cutoff], s));
+    return io.down();
 }
 extern "C" int pn_kde_f32(const pn_index *ix, const float *queries, size_t nq, size_t q_cols, ptrdiff_t q_row_stride,
                           const float *h, size_t n_h, int kernel, double atol, unsigned flags, double *sum_out,
@@ -5019,22 +5013,14 @@ static int ms_host(const pn_index *ix, const T *seeds, size_t ns, size_t s_cols,
     hipStream_t s = call.s();
     const size_t dim = ix->dim;
     if (!rows) PNCHK(upload_rows_to<T>(seeds, ns, dim, s_stride, ws.w_hq, s));
-    const size_t m_bytes = round_up(ns * dim * sizeof(T), (size_t)8), h_bytes = round_up(n_h * sizeof(T), (size_t)8);
-    PNCHK(ws.w_ms_io.ensure(ns * (sizeof(double) + sizeof(uint64_t) + sizeof(uint32_t)) + m_bytes + h_bytes));
-    double *d_shift = (double *)ws.w_ms_io.p;
-    uint64_t *d_points = (uint64_t *)(d_shift + ns);
-    T *d_modes = (T *)(d_points + ns);
-    T *d_h = (T *)((char *)d_modes + m_bytes);
-    uint32_t *d_iters = (uint32_t *)((char *)d_h + h_bytes);
-    HIPCHK(hipMemcpyAsync(d_h, h, n_h * sizeof(T), hipMemcpyHostToDevice, s));
-    PNCHK(ms_enqueue<T>(ix, ws, rows ? (const T *)ix->d_pts : (const T *)ws.w_hq.p, ns, rows ? ix->ld : dim, d_h, n_h, tol,
-                        max_iter, d_modes, d_points, iters ? d_iters : nullptr, shift ? d_shift : nullptr, work, s));
-    HIPCHK(hipMemcpyAsync(modes, d_modes, ns * dim * sizeof(T), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(points, d_points, ns * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    if (iters) HIPCHK(hipMemcpyAsync(iters, d_iters, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    if (shift) HIPCHK(hipMemcpyAsync(shift, d_shift, ns * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return PN_OK;
+    HostIo io(call);
+    const auto [d_h, d_modes, d_points, d_iters, d_shift] =
+        std::tuple{io.in(h, n_h), io.out(modes, ns * dim), io.out(points, ns), io.out(iters, ns), io.out(shift, ns)};
+    PNCHK(io.up());
+    PNCHK(ms_enqueue<T>(ix, ws, rows ? (const T *)ix->d_pts : (const T *)ws.w_hq.p, ns, rows ? ix->ld : dim, io[d_h], n_h, tol,
+                        max_iter, io[d_modes], io[d_points], iters ? io[d_iters] : nullptr, shift ? io[d_shift] : nullptr, work,
+                        s));
+    return io.down();
 }
 // ---- merge: rank sort + 2 ceil(ns / 1024) round launches (mean_shift.hip); nothing is read back
 static int ms_merge_args(const pn_index *ix, unsigned flags, const void *centres, const void *n_centres, const void *modes,
@@ -5072,23 +5058,22 @@ static int ms_merge_host(const pn_index *ix, const T *modes, size_t ns, const ui
     PNCHK(call.own_stream());
     Workspace &ws = call.ws();
     hipStream_t s = call.s();
-    const size_t dim = ix->dim, m_bytes = round_up(ns * dim * sizeof(T), (size_t)8);
-    PNCHK(ws.w_ms_io.ensure(ns * 3 * sizeof(uint64_t) + 8 + 2 * m_bytes));
-    uint64_t *d_points = (uint64_t *)ws.w_ms_io.p, *d_cp = d_points + ns, *d_nc = d_cp + ns;
-    int64_t *d_cos = (int64_t *)(d_nc + 1);
-    T *d_modes = (T *)(d_cos + ns), *d_centres = (T *)((char *)d_modes + m_bytes);
-    HIPCHK(hipMemcpyAsync(d_modes, modes, ns * dim * sizeof(T), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_points, points, ns * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    const size_t dim = ix->dim;
+    HostIo io(call);
+    // (the count first, and only that many centres: d_nc, d_centres and d_cp are fetched below)
+    const auto [d_modes, d_points, d_nc, d_centres, d_cp, d_cos] =
+        std::tuple{io.in(modes, ns * dim),       io.in(points, ns),             io.out<uint64_t>(nullptr, 1),
+                   io.out<T>(nullptr, ns * dim), io.out<uint64_t>(nullptr, ns), io.out(centre_of_seed, ns)};
+    PNCHK(io.up());
     PNCHK(ws.w_ms.ensure(ms_merge_bytes(ns)));
-    HIPCHK(ms_merge_enqueue<T>(d_modes, ns, (int)dim, d_points, h, ws.w_ms.p, d_centres, d_cp, d_cos, d_nc, s));
-    HIPCHK(hipMemcpyAsync(n_centres, d_nc, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(ms_merge_enqueue<T>(io[d_modes], ns, (int)dim, io[d_points], h, ws.w_ms.p, io[d_centres], io[d_cp], io[d_cos],
+                               io[d_nc], s));
+    PNCHK(io.fetch(d_nc, n_centres, 1));
     HIPCHK(hipStreamSynchronize(s));
     const size_t nc = (size_t)*n_centres;
-    if (nc) HIPCHK(hipMemcpyAsync(centres, d_centres, nc * dim * sizeof(T), hipMemcpyDeviceToHost, s));
-    if (nc && centre_points) HIPCHK(hipMemcpyAsync(centre_points, d_cp, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    if (centre_of_seed) HIPCHK(hipMemcpyAsync(centre_of_seed, d_cos, ns * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return PN_OK;
+    PNCHK(io.fetch(d_centres, centres, nc * dim));
+    PNCHK(io.fetch(d_cp, centre_points, nc));
+    return io.down();
 }
 // ---- labels: one exact launch against the centres
 static int ms_labels_args(const pn_index *ix, unsigned flags, const void *labels, const void *centres, size_t nc,
@@ -5119,18 +5104,12 @@ static int ms_labels_host(const pn_index *ix, const T *centres, size_t nc, T h, 
     if (ix->n == 0) return PN_OK;
     CallScope call(ix);
     PNCHK(call.own_stream());
-    Workspace &ws = call.ws();
-    hipStream_t s = call.s();
-    const size_t c_bytes = nc * ix->dim * sizeof(T);
-    PNCHK(ws.w_ms_io.ensure(ix->n * sizeof(int64_t) + c_bytes + 8));
-    int64_t *d_labels = (int64_t *)ws.w_ms_io.p;
-    T *d_centres = (T *)(d_labels + ix->n);
-    if (nc) HIPCHK(hipMemcpyAsync(d_centres, centres, c_bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(launch_ms_labels<T>((const T *)ix->d_pts, ix->n, ix->ld, (int)ix->dim, d_centres, nc, h,
-                               (flags & PN_MS_ORPHANS) != 0, d_labels, s));
-    HIPCHK(hipMemcpyAsync(labels, d_labels, ix->n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return PN_OK;
+    HostIo io(call);
+    const auto [d_centres, d_labels] = std::tuple{io.in(centres, nc * ix->dim), io.out(labels, ix->n)};
+    PNCHK(io.up());
+    HIPCHK(launch_ms_labels<T>((const T *)ix->d_pts, ix->n, ix->ld, (int)ix->dim, io[d_centres], nc, h,
+                               (flags & PN_MS_ORPHANS) != 0, io[d_labels], call.s()));
+    return io.down();
 }
 #define PN_MS_ENTRIES(SFX, T)                                                                                                  \
     extern "C" int pn_mean_shift_##SFX(const pn_index *ix, const T *seeds, size_t ns, size_t s_cols, ptrdiff_t s_row_stride,    \
@@ -5284,22 +5263,17 @@ static int km_assign_host(const pn_index *ix, const T *centres, size_t nc, unsig
     PNCHK(call.own_stream());
     Workspace &ws = call.ws();
     hipStream_t s = call.s();
-    const size_t n = ix->n, c_bytes = round_up(nc * ix->dim * sizeof(T), (size_t)8), d_bytes = round_up(n * sizeof(T), (size_t)8);
-    PNCHK(ws.w_km_io.ensure(n * sizeof(int64_t) + 8 + d_bytes + c_bytes));
-    int64_t *d_labels = (int64_t *)ws.w_km_io.p;
-    double *d_inertia = (double *)(d_labels + n);
-    T *d_dist = (T *)(d_inertia + 1), *d_centres = (T *)((char *)d_dist + d_bytes);
-    if (nc) HIPCHK(hipMemcpyAsync(d_centres, centres, nc * ix->dim * sizeof(T), hipMemcpyHostToDevice, s));
+    const size_t n = ix->n;
+    HostIo io(call);
+    const auto [d_centres, d_labels, d_dist, d_inertia] =
+        std::tuple{io.in(centres, nc * ix->dim), io.out(labels, n), io.out(dist, n), io.out(inertia, 1)};
+    PNCHK(io.up());
     KmRowImage rows;
     const bool filter = km_use_filter(ix, nc);
     if (filter) PNCHK(km_pack_rows<T>(ix, ws, &rows, s));
-    PNCHK(km_assign_enqueue<T>(ix, ws, filter ? &rows : nullptr, d_centres, nc, d_labels, dist || inertia ? d_dist : nullptr,
-                               inertia ? d_inertia : nullptr, s));
-    HIPCHK(hipMemcpyAsync(labels, d_labels, n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    if (dist) HIPCHK(hipMemcpyAsync(dist, d_dist, n * sizeof(T), hipMemcpyDeviceToHost, s));
-    if (inertia) HIPCHK(hipMemcpyAsync(inertia, d_inertia, sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return PN_OK;
+    PNCHK(km_assign_enqueue<T>(ix, ws, filter ? &rows : nullptr, io[d_centres], nc, io[d_labels],
+                               dist || inertia ? io[d_dist] : nullptr, inertia ? io[d_inertia] : nullptr, s));
+    return io.down();
 }
 // The iterations, in a held workspace on stream s; everything in HBM, d_centres holds the initial centres on entry;
 // n, nc >= 1.  Blocks the host once per iteration.
@@ -5372,27 +5346,15 @@ static int km_host(const pn_index *ix, const T *init, size_t nc, double tol, siz
     }
     CallScope call(ix);
     PNCHK(call.own_stream());
-    Workspace &ws = call.ws();
-    hipStream_t s = call.s();
-    const size_t c_bytes = round_up(nc * dim * sizeof(T), (size_t)8), d_bytes = round_up(n * sizeof(T), (size_t)8);
-    PNCHK(ws.w_km_io.ensure(n * sizeof(int64_t) + 24 + nc * sizeof(uint64_t) + d_bytes + c_bytes));
-    int64_t *d_labels = (int64_t *)ws.w_km_io.p;
-    double *d_inertia = (double *)(d_labels + n), *d_shift2 = d_inertia + 1;
-    uint64_t *d_iters = (uint64_t *)(d_shift2 + 1), *d_counts = d_iters + 1;
-    T *d_dist = (T *)(d_counts + nc), *d_centres = (T *)((char *)d_dist + d_bytes);
-    HIPCHK(hipMemcpyAsync(d_centres, init, nc * dim * sizeof(T), hipMemcpyHostToDevice, s));
-    PNCHK(km_loop_enqueue<T>(ix, ws, nc, tol, max_iter, d_centres, d_labels, dist || inertia ? d_dist : nullptr,
-                             counts ? d_counts : nullptr, inertia ? d_inertia : nullptr, d_iters,
-                             d_shift2, s));
-    HIPCHK(hipMemcpyAsync(centres, d_centres, nc * dim * sizeof(T), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(labels, d_labels, n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    if (dist) HIPCHK(hipMemcpyAsync(dist, d_dist, n * sizeof(T), hipMemcpyDeviceToHost, s));
-    if (counts) HIPCHK(hipMemcpyAsync(counts, d_counts, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    if (inertia) HIPCHK(hipMemcpyAsync(inertia, d_inertia, sizeof(double), hipMemcpyDeviceToHost, s));
-    if (iterations) HIPCHK(hipMemcpyAsync(iterations, d_iters, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    if (shift2) HIPCHK(hipMemcpyAsync(shift2, d_shift2, sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return PN_OK;
+    HostIo io(call);
+    const auto [d_centres, d_labels, d_dist, d_counts, d_inertia, d_iters, d_shift2] =
+        std::tuple{io.inout(init, centres, nc * dim), io.out(labels, n),     io.out(dist, n),  io.out(counts, nc),
+                   io.out(inertia, 1),                io.out(iterations, 1), io.out(shift2, 1)};
+    PNCHK(io.up());
+    PNCHK(km_loop_enqueue<T>(ix, call.ws(), nc, tol, max_iter, io[d_centres], io[d_labels],
+                             dist || inertia ? io[d_dist] : nullptr, counts ? io[d_counts] : nullptr,
+                             inertia ? io[d_inertia] : nullptr, io[d_iters], io[d_shift2], call.s()));
+    return io.down();
 }
 extern "C" int pn_kmeans_bounds_f32(const pn_index *ix, const float *centres, size_t nc, double *bounds_out) {
     if (!bounds_out) return fail(PN_ERR_INVALID, "bounds_out is NULL");
@@ -5408,20 +5370,16 @@ extern "C" int pn_kmeans_bounds_f32(const pn_index *ix, const float *centres, si
     Workspace &ws = call.ws();
     hipStream_t s = call.s();
     const int dim = (int)ix->dim;
-    const size_t c_bytes = round_up(nc * ix->dim * sizeof(float), (size_t)8);
-    PNCHK(ws.w_km_io.ensure(ix->n * nc * sizeof(double) + c_bytes));
-    double *d_bounds = (double *)ws.w_km_io.p;
-    float *d_centres = (float *)(d_bounds + ix->n * nc);
-    HIPCHK(hipMemcpyAsync(d_centres, centres, nc * ix->dim * sizeof(float), hipMemcpyHostToDevice, s));
+    HostIo io(call);
+    const auto [d_centres, d_bounds] = std::tuple{io.in(centres, nc * ix->dim), io.out(bounds_out, ix->n * nc)};
+    PNCHK(io.up());
     KmRowImage rows;
     PNCHK(km_pack_rows<float>(ix, ws, &rows, s));
     PNCHK(ws.w_km_cent.ensure(km_centre_image_bytes(nc, dim)));
     const KmCentreImage ci = km_centre_image_at(ws.w_km_cent.p, nc, dim);
-    HIPCHK(launch_km_pack_centres<float>(d_centres, nc, dim, ci, s));
-    HIPCHK(launch_km_bounds(rows, ix->n, ci, nc, d_bounds, s));
-    HIPCHK(hipMemcpyAsync(bounds_out, d_bounds, ix->n * nc * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return PN_OK;
+    HIPCHK(launch_km_pack_centres<float>(io[d_centres], nc, dim, ci, s));
+    HIPCHK(launch_km_bounds(rows, ix->n, ci, nc, io[d_bounds], s));
+    return io.down();
 }
 #define PN_KM_ENTRIES(SFX, T)                                                                                                  \
     extern "C" int pn_kmeans_assign_##SFX(const pn_index *ix, const T *centres, size_t nc, unsigned flags, int64_t *labels_out, \
