@@ -346,6 +346,21 @@ extern "C" {
                                 d_counts: *mut u64, d_inertia: *mut f64, d_iterations: *mut u64, d_shift2: *mut f64,
                                 stream: *mut c_void) -> c_int;
     pub fn pn_kmeans_bounds_f32(index: *const pn_index, centres: *const f32, nc: usize, bounds_out: *mut f64) -> c_int;
+    /// silhouette values (include/petal_mi355x.h): rows (with n_rows = 0), a / b / nearest / score / n_scored / d_error nullable
+    pub fn pn_silhouette_f32(index: *const pn_index, codes: *const i64, n_clusters: usize, rows: *const u64, n_rows: usize,
+                             flags: c_uint, samples_out: *mut f64, a_out: *mut f64, b_out: *mut f64,
+                             nearest_out: *mut i64, score_out: *mut f64, n_scored_out: *mut u64) -> c_int;
+    pub fn pn_silhouette_device_f32(index: *const pn_index, d_codes: *const i64, n_clusters: usize, d_rows: *const u64,
+                                    n_rows: usize, flags: c_uint, d_samples: *mut f64, d_a: *mut f64, d_b: *mut f64,
+                                    d_nearest: *mut i64, d_score: *mut f64, d_n_scored: *mut u64, d_error: *mut i32,
+                                    stream: *mut c_void) -> c_int;
+    pub fn pn_silhouette_f64(index: *const pn_index, codes: *const i64, n_clusters: usize, rows: *const u64, n_rows: usize,
+                             flags: c_uint, samples_out: *mut f64, a_out: *mut f64, b_out: *mut f64,
+                             nearest_out: *mut i64, score_out: *mut f64, n_scored_out: *mut u64) -> c_int;
+    pub fn pn_silhouette_device_f64(index: *const pn_index, d_codes: *const i64, n_clusters: usize, d_rows: *const u64,
+                                    n_rows: usize, flags: c_uint, d_samples: *mut f64, d_a: *mut f64, d_b: *mut f64,
+                                    d_nearest: *mut i64, d_score: *mut f64, d_n_scored: *mut u64, d_error: *mut i32,
+                                    stream: *mut c_void) -> c_int;
     /// dist_out nullable (PN_RADIUS_SORTED needs it); *idx_out / *dist_out released with pn_free
     pub fn pn_query_radius_self_f32(index: *const pn_index, radius: f32, flags: c_uint, offsets: *mut u64,
                                     idx_out: *mut *mut u64, dist_out: *mut *mut f32) -> c_int;

@@ -55,6 +55,9 @@ pub trait Elem: Copy + Default + PartialOrd + 'static {
     unsafe fn dbscan(ix: *const ffi::pn_index, eps: Self, min_samples: usize, labels: *mut i64, core: *mut u8,
                      ncl: *mut u64) -> c_int;
     #[doc(hidden)]
+    unsafe fn silhouette(ix: *const ffi::pn_index, codes: *const i64, nc: usize, s: *mut f64, score: *mut f64,
+                         scored: *mut u64) -> c_int;
+    #[doc(hidden)]
     unsafe fn radius_of(ix: *const ffi::pn_index, n: u64, out: *mut Self) -> c_int;
     #[doc(hidden)]
     unsafe fn lower_bound(ix: *const ffi::pn_index, a: u64, b: u64, out: *mut Self) -> c_int;
@@ -68,7 +71,7 @@ pub trait Elem: Copy + Default + PartialOrd + 'static {
 macro_rules! impl_elem {
     ($t:ty, $create:ident, $create_cos:ident, $query:ident, $radius:ident, $radius_wd:ident, $rad_of:ident, $lb:ident,
      $eu:ident, $reu:ident, $cos:ident, $pw:ident, $pwc:ident, $self_knn:ident, $self_rad:ident, $radii:ident,
-     $self_radii:ident, $dbscan:ident) => {
+     $self_radii:ident, $dbscan:ident, $silhouette:ident) => {
         impl Elem for $t {
             unsafe fn create(p: *const Self, n: usize, d: usize, rs: isize, cs: isize, cosine: bool, out: *mut *mut ffi::pn_index) -> c_int {
                 if cosine { ffi::$create_cos(p, n, d, rs, cs, 0, out) } else { ffi::$create(p, n, d, rs, cs, 0, out) }
@@ -102,6 +105,11 @@ macro_rules! impl_elem {
                              ncl: *mut u64) -> c_int {
                 ffi::$dbscan(ix, eps, min_samples, 0, labels, core, ncl)
             }
+            unsafe fn silhouette(ix: *const ffi::pn_index, codes: *const i64, nc: usize, s: *mut f64, score: *mut f64,
+                                 scored: *mut u64) -> c_int {
+                ffi::$silhouette(ix, codes, nc, std::ptr::null(), 0, 0, s, std::ptr::null_mut(), std::ptr::null_mut(),
+                                 std::ptr::null_mut(), score, scored)
+            }
             unsafe fn radius_of(ix: *const ffi::pn_index, n: u64, out: *mut Self) -> c_int { ffi::$rad_of(ix, n, out) }
             unsafe fn lower_bound(ix: *const ffi::pn_index, a: u64, b: u64, out: *mut Self) -> c_int { ffi::$lb(ix, a, b, out) }
             unsafe fn euclid(a: *const Self, b: *const Self, n: usize, squared: bool) -> Self {
@@ -118,12 +126,12 @@ impl_elem!(f32, pn_index_create_f32, pn_index_create_cosine_f32, pn_query_f32, p
            pn_query_radius_with_distance_f32, pn_tree_radius_of_f32,
            pn_tree_node_distance_lower_bound_f32, pn_euclidean_f32, pn_reuclidean_f32, pn_cosine_f32, pn_pairwise_f32,
            pn_pairwise_cosine_f32, pn_query_self_f32, pn_query_radius_self_f32, pn_query_radii_f32,
-           pn_query_radii_self_f32, pn_dbscan_f32);
+           pn_query_radii_self_f32, pn_dbscan_f32, pn_silhouette_f32);
 impl_elem!(f64, pn_index_create_f64, pn_index_create_cosine_f64, pn_query_f64, pn_query_radius_f64,
            pn_query_radius_with_distance_f64, pn_tree_radius_of_f64,
            pn_tree_node_distance_lower_bound_f64, pn_euclidean_f64, pn_reuclidean_f64, pn_cosine_f64, pn_pairwise_f64,
            pn_pairwise_cosine_f64, pn_query_self_f64, pn_query_radius_self_f64, pn_query_radii_f64,
-           pn_query_radii_self_f64, pn_dbscan_f64);
+           pn_query_radii_self_f64, pn_dbscan_f64, pn_silhouette_f64);
 
 pub mod distance {
     use super::*;
@@ -294,6 +302,17 @@ impl<'a, A: Elem, M: Metric<A>> BallTree<'a, A, M> {
         let mut ncl = 0u64;
         ok(unsafe { A::dbscan(self.handle, eps, min_samples, labels.as_mut_ptr(), core.as_mut_ptr(), &mut ncl) });
         (labels, core.iter().map(|&c| c != 0).collect(), ncl as usize)
+    }
+    /// extension: the silhouette of a labelling of the indexed rows on the device: (value per row, their mean, the number
+    /// of rows scored).  `codes[i]` in `0 .. n_clusters` is row i's cluster, a negative code excludes the row (its value is
+    /// NaN); every distance is `pairwise`'s, every sum has the fixed shape the C header states
+    pub fn silhouette(&self, codes: &[i64], n_clusters: usize) -> (Vec<f64>, f64, usize) {
+        let n = self.points.nrows();
+        assert_eq!(codes.len(), n, "one cluster code per indexed row");
+        let mut s = vec![0f64; n];
+        let (mut score, mut scored) = (0f64, 0u64);
+        ok(unsafe { A::silhouette(self.handle, codes.as_ptr(), n_clusters, s.as_mut_ptr(), &mut score, &mut scored) });
+        (s, score, scored as usize)
     }
     /// extension: `query_radius_self` with one radius per row (`radii.len()` = the number of rows): row i's list is the
     /// scalar call's for `radii[i]`

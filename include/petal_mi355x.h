@@ -67,6 +67,7 @@ extern "C" {
  * pn_optics_{,device_}{f32,f64}, pn_optics_dbscan_{,device_}{f32,f64},
  * PN_OPT_OPTICS_PIECE; pn_kde_{,device_,self_,self_device_}{f32,f64}, PN_KDE_*, PN_OPT_KDE_PIECE;
  * pn_mean_shift_{,device_,merge_,merge_device_,labels_,labels_device_}{f32,f64}, PN_MS_*, PN_OPT_MS_PIECE;
+ * pn_silhouette_{,device_}{f32,f64};
  * pn_kmeans_{,device_}{f32,f64}, pn_kmeans_assign_{,device_}{f32,f64}, pn_kmeans_bounds_f32,
  * PN_OPT_KMEANS_FILTER. */
 #define PN_ABI_VERSION 3
@@ -1002,6 +1003,58 @@ int pn_kmeans_device_f64(const pn_index *index, const double *d_init_centres, si
  * (not finite, a squared norm of 2^100 or more).  Host pointers; 8 <= dim <= 320, else PN_ERR_UNSUPPORTED.  Tests check
  * the inequality pair by pair. */
 int pn_kmeans_bounds_f32(const pn_index *index, const float *centres, size_t nc, double *bounds_out);
+
+/* ---- silhouette values of a labelling (extension; Euclidean indexes only; T = the index's element type).  DESIGN.md 4.24.
+ * codes [n]: one cluster code per indexed row.  A code in [0, n_clusters) makes the row a MEMBER of that cluster; a
+ * negative code EXCLUDES the row (it is a member of nothing and is not scored: DBSCAN's noise); a code >= n_clusters is an
+ * error.  rows [n_rows] (NULL and 0: every indexed row, in order) selects the rows that are SCORED -- all members stay
+ * members, so m listed rows cost m x n distances and each value is the full call's, bit for bit.  Row numbers count the
+ * indexed rows from 0 (PN_OPT_INDEX_BASE affects neither an input nor an output here); a row number >= n is an error; a
+ * listed row that is excluded gets NaN, NaN, NaN, -1.
+ *   For a scored row i of cluster A:
+ *   d(i, j)    = sqrt(((0 + (x_i0 - x_j0)^2) + (x_i1 - x_j1)^2) + ...) in T, sequential and unfused: the bits of
+ *                pn_pairwise_*; then widened to double.  Everything below is IEEE double arithmetic.
+ *   a(i)       = S(i, A) / (double)(|A| - 1), the sum without j = i;  a(i) = 0 when |A| = 1
+ *   b(i)       = the smallest S(i, C) / (double)|C| over the non-empty clusters C != A; nearest(i) = that C, the lowest
+ *                cluster number among equal means
+ *   s(i)       = (b - a) / max(a, b);  s(i) = 0 when |A| = 1 or max(a, b) = 0 (scikit-learn's conventions)
+ *   score      = the mean of s over the scored rows among those listed (NaN when there is none); n_scored = their count
+ * The shape of every sum.  The members are sorted by (code, row number) into positions 0 .. M - 1, and the positions are
+ * cut into spans of L = max(8192, n / 16 rounded up, rounded up to 128) positions: at most 16 spans, L a function of n.
+ *   Q(i,C,t)   = ((0.0 + d(i, j_0)) + d(i, j_1)) + ...   over the members j != i of C at positions [128 t, 128 t + 128),
+ *                ascending position
+ *   P(i,C,s)   = ((0.0 + Q(i,C,t_0)) + Q(i,C,t_1)) + ... over the tiles t inside span s that hold members of C, ascending
+ *   S(i, C)    = (P(i,C,s_0) + P(i,C,s_1)) + ...          over the spans that hold members of C, ascending
+ *   score      = T / n_scored, T the sum of 256 partials by the halving tree (partial l += partial l + w for w = 128, 64,
+ *                ..., 1); partial l = ((0.0 + s(r_0)) + s(r_1)) + ... over the scored rows among list positions l, l + 256, ...
+ * So a value is a function of the rows' data, the codes and n -- not of the device, the number of CUs, the rows asked for
+ * or how a launch was cut -- and the host and device entries give the same bits.  No floating-point atomics.
+ * Argument errors, before any device is touched and in this order: unknown flags (none is defined); samples_out NULL; codes
+ * NULL; n_clusters < 2; rows NULL with n_rows > 0 or rows given with n_rows == 0; NULL index; wrong element type:
+ * PN_ERR_INVALID; a Cosine index: PN_ERR_UNSUPPORTED; n_clusters > 2^31 - 1 or n >= 2^32 (the sort key is code << 32 | row):
+ * PN_ERR_UNSUPPORTED; an index without rows: PN_ERR_INVALID.
+ * Errors in the data -- a code >= n_clusters, fewer than two non-empty clusters, a row number >= n: the host entries
+ * return PN_ERR_INVALID; the device entries cannot look, store PN_ERR_INVALID (else PN_OK) into d_error[0] (nullable) and
+ * leave the outputs unspecified.
+ * Device entry points: everything in HBM, written in stream order on `stream`; the call enqueues and returns, it never
+ * waits for the device (the sort, the grids and the workspace follow from n, n_rows and n_clusters).  Outputs: samples
+ * [n_rows or n] is required; a, b, nearest (same length), score, n_scored ([1]) may each be NULL.
+ * pn_stats.queries advances by the number of rows asked for.  Workspace, per handle and call: 16 N bytes (N = n rounded up
+ * to a power of two, at least 1024: the sort), two images of the rows (members and scored rows, dim rounded up to 16
+ * columns), and 40 bytes per (scored row, span).
+ * Not in this version: Cosine indexes, row-sharded handles, the O(n D) indices (Davies-Bouldin, Calinski-Harabasz). */
+int pn_silhouette_f32(const pn_index *index, const int64_t *codes, size_t n_clusters, const uint64_t *rows, size_t n_rows,
+                      unsigned flags, double *samples_out, double *a_out, double *b_out, int64_t *nearest_out,
+                      double *score_out, uint64_t *n_scored_out);
+int pn_silhouette_device_f32(const pn_index *index, const int64_t *d_codes, size_t n_clusters, const uint64_t *d_rows,
+                             size_t n_rows, unsigned flags, double *d_samples, double *d_a, double *d_b,
+                             int64_t *d_nearest, double *d_score, uint64_t *d_n_scored, int32_t *d_error, void *stream);
+int pn_silhouette_f64(const pn_index *index, const int64_t *codes, size_t n_clusters, const uint64_t *rows, size_t n_rows,
+                      unsigned flags, double *samples_out, double *a_out, double *b_out, int64_t *nearest_out,
+                      double *score_out, uint64_t *n_scored_out);
+int pn_silhouette_device_f64(const pn_index *index, const int64_t *d_codes, size_t n_clusters, const uint64_t *d_rows,
+                             size_t n_rows, unsigned flags, double *d_samples, double *d_a, double *d_b,
+                             int64_t *d_nearest, double *d_score, uint64_t *d_n_scored, int32_t *d_error, void *stream);
 
 /* ---- distance::pairwise(x, &Euclidean) (src/distance.rs:58-74): n x n
  * symmetric matrix, zero diagonal, n < 2 -> zeros. Host in, host out. */

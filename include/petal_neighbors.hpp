@@ -159,6 +159,16 @@ struct KMeans {
     double inertia = 0.0, shift2 = 0.0;
     size_t n_iter = 0;
 };
+// the answer of BallTree::silhouette: per scored row the silhouette value, the mean distance to its own cluster, the
+// smallest mean distance to another cluster and that cluster's code (an excluded row: NaN, NaN, NaN, -1); the mean of the
+// values in the library's fixed sum shape and the number of rows it is taken over (all f64, whatever the tree's A)
+template <typename A>
+struct Silhouette {
+    std::vector<double> samples, a, b;
+    std::vector<int64_t> nearest;
+    double score = 0.0;
+    size_t n_scored = 0;
+};
 // the answer of BallTree::optics: ordering[t] = the t-th row OPTICS visits (a plain row number); reachability, predecessor
 // (-1 = none) and core_distances are indexed by row, +inf where undefined
 template <typename A>
@@ -669,6 +679,29 @@ class BallTree {
         res.dist.resize(n_);
         res.counts.assign(counts.begin(), counts.begin() + k);
         res.n_iter = (size_t)iters;
+        return res;
+    }
+    // extension: silhouette values on the device (pn_silhouette_*).  codes [n]: a cluster code in [0, n_clusters) per
+    // indexed row, negative = excluded; rows [n_rows] (nullptr, 0: every row): the rows to score, all members stay members
+    Silhouette<A> silhouette(const int64_t *codes, size_t n_clusters, const uint64_t *rows = nullptr, size_t n_rows = 0) const {
+        Silhouette<A> res;
+        const size_t m = rows ? n_rows : n_;
+        res.samples.resize(m + 1);
+        res.a.resize(m + 1);
+        res.b.resize(m + 1);
+        res.nearest.resize(m + 1);
+        uint64_t scored = 0;
+        if constexpr (kF32)
+            check(pn_silhouette_f32(h_, codes, n_clusters, rows, n_rows, 0u, res.samples.data(), res.a.data(), res.b.data(),
+                                    res.nearest.data(), &res.score, &scored));
+        else
+            check(pn_silhouette_f64(h_, codes, n_clusters, rows, n_rows, 0u, res.samples.data(), res.a.data(), res.b.data(),
+                                    res.nearest.data(), &res.score, &scored));
+        res.samples.resize(m);
+        res.a.resize(m);
+        res.b.resize(m);
+        res.nearest.resize(m);
+        res.n_scored = (size_t)scored;
         return res;
     }
     // extension: OPTICS on the device (pn_optics_*): scikit-learn's OPTICS(min_samples + 1, max_eps) on this library's

@@ -123,6 +123,8 @@ PAIRED = {
     "pn_kmeans_assign_device": (_i, [_vp, _vp, _sz, _cu] + [_vp] * 4),
     "pn_kmeans": (_i, [_vp, _vp, _sz, _d, _sz, _cu] + [_vp] * 7),
     "pn_kmeans_device": (_i, [_vp, _vp, _sz, _d, _sz, _cu] + [_vp] * 8),
+    "pn_silhouette": (_i, [_vp, _vp, _sz, _vp, _sz, _cu] + [_vp] * 6),
+    "pn_silhouette_device": (_i, [_vp, _vp, _sz, _vp, _sz, _cu] + [_vp] * 8),
     "pn_optics": (_i, [_vp, _sz, _R, _cu] + [_vp] * 4),
     "pn_optics_device": (_i, [_vp, _sz, _R, _cu] + [_vp] * 5),
     "pn_optics_dbscan": (_i, [_vp] * 4 + [_R, _cu, _vp, _vp]),

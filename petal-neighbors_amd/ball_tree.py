@@ -1008,6 +1008,102 @@ class BallTree(Handle):
         check(_lib.lib().pn_kmeans_bounds_f32(self._h, c.ctypes.data if c.shape[0] else None, c.shape[0], out.ctypes.data))
         return out
 
+    # -------------------------------------------------- silhouette
+    # scikit-learn's ``silhouette_samples`` / ``silhouette_score`` on the device (``pn_silhouette_*``): every (scored row,
+    # member) distance in the fold of ``pairwise``, reduced per (row, cluster) as it is made -- O(n) results, no n x n
+    # matrix.  Every sum has one stated shape (the header), so a value depends on the data and the labels alone.
+    def _sil_rows(self, rows):
+        """None (every row), or the row numbers as a contiguous uint64 array"""
+        if rows is None:
+            return None
+        r = np.asarray(rows)
+        if r.ndim != 1 or r.shape[0] < 1 or r.dtype.kind not in "iu":
+            raise ValueError("rows must be a non-empty 1-D array of row numbers")
+        if r.shape[0] and (int(r.min()) < 0 or int(r.max()) >= self._n):
+            raise ValueError(f"rows must lie in [0, {self._n})")
+        return np.ascontiguousarray(r, dtype=np.uint64)
+
+    def _sil_codes(self, labels, ignore):
+        """``(classes, codes int64 [n])``: the labels through ``np.unique``; the label ``ignore`` becomes code -1"""
+        a = np.asarray(labels)
+        if a.ndim != 1 or a.shape[0] != self._n:
+            raise ValueError(f"labels must be 1-D with one label per indexed row ({self._n})")
+        keep = np.ones(self._n, dtype=bool) if ignore is None else a != ignore
+        classes, inv = np.unique(a[keep], return_inverse=True)
+        if len(classes) < 2:
+            raise ValueError("a silhouette needs at least two clusters")
+        codes = np.full(self._n, -1, dtype=np.int64)
+        codes[keep] = inv.reshape(-1)
+        return classes, codes
+
+    def _silhouette(self, labels, rows, ignore, full):
+        self._euclidean_only("a silhouette")
+        classes, codes = self._sil_codes(labels, ignore)
+        r = self._sil_rows(rows)
+        m = self._n if r is None else r.shape[0]
+        s = np.empty(m, dtype=np.float64)
+        a, b = (np.empty(m, dtype=np.float64) for _ in range(2)) if full else (None, None)
+        near = np.empty(m, dtype=np.int64) if full else None
+        score, scored = C.c_double(0.0), C.c_uint64(0)
+        check(self._fn("silhouette")(self._h, codes.ctypes.data, len(classes), None if r is None else r.ctypes.data,
+                                     0 if r is None else m, 0, s.ctypes.data, *(x.ctypes.data if full else None
+                                                                                 for x in (a, b, near)),
+                                     C.byref(score), C.byref(scored)))
+        return classes, s, a, b, near, float(score.value)
+
+    def silhouette_samples(self, labels, rows=None, ignore=None, full: bool = False):
+        """The silhouette value of every indexed row (float64 ``[n]``) under ``labels``, any 1-D array of one label per
+        row.  ``rows``: score these row numbers only (every row stays a member of its cluster; each value is the full
+        call's, bit for bit).  ``ignore``: a label value -- ``-1`` from ``dbscan`` -- whose rows belong to no cluster and
+        get NaN.  ``full=True`` returns ``(s, a, b, nearest)``: the mean distance to the own cluster, the smallest mean to
+        another one, and that cluster's label (ties: the smallest label)."""
+        classes, s, a, b, near, _ = self._silhouette(labels, rows, ignore, full)
+        if not full:
+            return s
+        ok = near >= 0  # (only an ignored row has no nearest cluster: it keeps the label ``ignore``)
+        out = np.empty(len(near), dtype=classes.dtype)
+        out[ok] = classes[near[ok]]
+        if not ok.all():
+            out[~ok] = ignore
+        return s, a, b, out
+
+    def silhouette_score(self, labels, rows=None, ignore=None):
+        """The mean silhouette value over the scored rows (those of ``rows`` that ``ignore`` leaves), summed in the
+        library's fixed shape: a float."""
+        return self._silhouette(labels, rows, ignore, False)[5]
+
+    def silhouette_device(self, codes, n_clusters: int, rows=None, out_samples=None, out_a=None, out_b=None,
+                          out_nearest=None, out_score=None, out_n_scored=None, out_error=None, stream=None):
+        """``silhouette_samples`` in HBM: ``codes`` a contiguous int64 CUDA tensor of n cluster codes in ``[0, n_clusters)``
+        (negative: the row is excluded), ``rows`` None or a contiguous int64 CUDA tensor of row numbers.  Returns CUDA tensors
+        ``(samples float64 [m], a [m], b [m], nearest int64 [m], score float64 [1], n_scored int64 [1], error int32 [1])``
+        written in stream order on ``stream`` (default: the current torch stream) without waiting for the device.
+        ``error[0]`` is 0, or ``PN_ERR_INVALID`` for a code >= n_clusters, fewer than two non-empty clusters or a row
+        number >= n: the other outputs are then unspecified."""
+        import torch
+        self._euclidean_only("a silhouette")
+        nc = int(n_clusters)
+        if nc < 2 or nc > 2 ** 31 - 1:
+            raise ValueError("n_clusters must be in [2, 2^31 - 1]")
+        self._per_row_device(codes, torch.int64, f"codes must be a contiguous 1-D int64 CUDA tensor of {self._n} cluster "
+                                                 "codes on the tree's device")
+        m = self._n
+        if rows is not None:
+            m = rows.numel() if isinstance(rows, torch.Tensor) else 0
+            if m < 1:
+                raise ValueError("rows must be a non-empty contiguous 1-D int64 CUDA tensor on the tree's device")
+            self._per_row_device(rows, torch.int64, "rows must be a non-empty contiguous 1-D int64 CUDA tensor on the "
+                                                    "tree's device", count=m)
+        s, a, b, near, score, scored, err = self._outs(
+            (out_samples, m, torch.float64, m), (out_a, m, torch.float64, m), (out_b, m, torch.float64, m),
+            (out_nearest, m, torch.int64, m), (out_score, 1, torch.float64, 1), (out_n_scored, 1, torch.int64, 1, True),
+            (out_error, 1, torch.int32, 1, True))
+        check(self._fn("silhouette_device")(
+            self._h, codes.data_ptr(), nc, None if rows is None else rows.data_ptr(), 0 if rows is None else m, 0,
+            s.data_ptr(), a.data_ptr(), b.data_ptr(), near.data_ptr(), score.data_ptr(), scored.data_ptr(), err.data_ptr(),
+            stream_arg(stream, self._dev)))
+        return s, a, b, near, score, scored, err
+
     # -------------------------------------------------- mean shift
     # scikit-learn's ``MeanShift`` (flat kernel) on the device (``pn_mean_shift_*``): seeds climb to the modes of the tophat
     # density, every step the mean of a radius list summed by one wave in a fixed order; only the seeds still moving are

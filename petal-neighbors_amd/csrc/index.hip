@@ -167,7 +167,8 @@ struct WorkspaceBufs {
     // pn_kmeans_*: the packed rows (once per call), the packed centres, the O(n) arrays of an assignment (candidates,
     // thresholds, the list of unproven rows, distances, inertia segments), the update's scratch
     DevBuf w_km_rows, w_km_cent, w_km, w_km_upd;
-    DevBuf w_pcnt;                 // shared thresholds: the segments' published fill counts [nseg][nq_pad]
+    DevBuf w_sil;  // pn_silhouette_*: the scratch of silhouette.hip (sort, the two images, the spans' partials)
+    DevBuf w_pcnt;                // shared thresholds: the segments' published fill counts [nseg][nq_pad]
 };
 static_assert(std::is_standard_layout<WorkspaceBufs>::value && sizeof(WorkspaceBufs) % sizeof(DevBuf) == 0,
               "WorkspaceBufs holds DevBuf members only");
@@ -5405,6 +5406,110 @@ extern "C" int pn_kmeans_bounds_f32(const pn_index *ix, const float *centres, si
 PN_KM_ENTRIES(f32, float)
 PN_KM_ENTRIES(f64, double)
 #undef PN_KM_ENTRIES
+
+// ---------------------------------------------------------------------------
+// Silhouette values: pn_silhouette_{,device_}{f32,f64} (the kernels and the shape of the sums: silhouette.hip).  Here: the
+// argument checks, the workspace and the one enqueue.  Nothing waits for the device but the host entry's final copy.
+// ---------------------------------------------------------------------------
+// (before any device is touched; the header states the order)
+static int sil_args(const pn_index *ix, const void *codes, size_t nc, const void *rows, size_t n_rows, unsigned flags,
+                    const void *samples, int elem_bytes) {
+    if (flags) return fail(PN_ERR_INVALID, "unknown silhouette flags 0x%x", flags);
+    if (!samples) return fail(PN_ERR_INVALID, "samples_out is NULL");
+    if (!codes) return fail(PN_ERR_INVALID, "codes is NULL");
+    if (nc < 2) return fail(PN_ERR_INVALID, "a silhouette needs n_clusters >= 2 (got %zu)", nc);
+    if ((rows == nullptr) != (n_rows == 0)) return fail(PN_ERR_INVALID, "rows and n_rows disagree (NULL and 0: every row)");
+    if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
+    if (ix->elem_bytes != elem_bytes) return fail(PN_ERR_INVALID, "index element type mismatch");
+    if (ix->metric != 0) return fail(PN_ERR_UNSUPPORTED, "a silhouette needs a Euclidean index");
+    if (nc > 0x7FFFFFFFull || ix->n > 0xFFFFFFFFull)
+        return fail(PN_ERR_UNSUPPORTED, "too many clusters or rows for a silhouette (the sort key is code << 32 | row)");
+    if (ix->n == 0) return fail(PN_ERR_INVALID, "a silhouette needs two non-empty clusters (the index holds no rows)");
+    return PN_OK;
+}
+struct SilOut {
+    double *samples = nullptr, *a = nullptr, *b = nullptr;
+    int64_t *nearest = nullptr;
+    double *score = nullptr;
+    uint64_t *n_scored = nullptr;
+    int32_t *err = nullptr;
+};
+// in a held workspace, on stream s; everything in HBM; m = the rows asked for (n without a list)
+template <typename T>
+static int sil_run(const pn_index *ix, Workspace &ws, const int64_t *d_codes, size_t nc, const uint64_t *d_rows, size_t m,
+                   const SilOut &o, hipStream_t s) {
+    PNCHK(ws.w_sil.ensure(sil_buffer_bytes(ix->n, m, (int)ix->dim, (int)sizeof(T))));
+    SilArgs a;
+    a.X = ix->d_pts, a.n = ix->n, a.ld = ix->ld, a.dim = (int)ix->dim;
+    a.codes = d_codes, a.n_clusters = nc, a.rows = d_rows, a.m = m, a.buf = ws.w_sil.p;
+    a.samples = o.samples, a.a = o.a, a.b = o.b, a.nearest = o.nearest, a.score = o.score, a.n_scored = o.n_scored, a.err = o.err;
+    HIPCHK(sil_enqueue<T>(a, s));
+    std::lock_guard<std::mutex> lk(ix->sh.mu);
+    ix->sh.stats.queries += m;
+    return PN_OK;
+}
+template <typename T>
+static int sil_device(const pn_index *ix, const int64_t *d_codes, size_t nc, const uint64_t *d_rows, size_t n_rows,
+                      unsigned flags, const SilOut &o, hipStream_t s) {
+    PNCHK(sil_args(ix, d_codes, nc, d_rows, n_rows, flags, o.samples, (int)sizeof(T)));
+    CallScope call(ix);
+    PNCHK(call.on_stream(s));
+    return sil_run<T>(ix, call.ws(), d_codes, nc, d_rows, d_rows ? n_rows : ix->n, o, s);
+}
+template <typename T>
+static int sil_host(const pn_index *ix, const int64_t *codes, size_t nc, const uint64_t *rows, size_t n_rows, unsigned flags,
+                    const SilOut &o) {
+    PNCHK(sil_args(ix, codes, nc, rows, n_rows, flags, o.samples, (int)sizeof(T)));
+    const size_t n = ix->n, m = rows ? n_rows : n;
+    // (the device entries cannot look; here a bad code or row number is an argument error with its place)
+    for (size_t i = 0; i < n; ++i)
+        if (codes[i] >= 0 && (uint64_t)codes[i] >= nc)
+            return fail(PN_ERR_INVALID, "codes[%zu] = %lld is not below n_clusters = %zu", i, (long long)codes[i], nc);
+    for (size_t r = 0; r < n_rows; ++r)
+        if (rows[r] >= n) return fail(PN_ERR_INVALID, "rows[%zu] = %llu is not below the %zu indexed rows", r,
+                                      (unsigned long long)rows[r], n);
+    CallScope call(ix);
+    PNCHK(call.own_stream());
+    uint64_t tail[2] = {0, 0};  // n_scored | the validation word (an int32 in its low bytes)
+    HostIo io(call);
+    const auto [d_codes, d_rows, d_s, d_a, d_b, d_near, d_score, d_tail] =
+        std::tuple{io.in(codes, n),   io.in(rows, n_rows),  io.out(o.samples, m), io.out(o.a, o.a ? m : 0),
+                   io.out(o.b, o.b ? m : 0), io.out(o.nearest, o.nearest ? m : 0), io.out(o.score, 1), io.out(tail, 2)};
+    PNCHK(io.up());
+    SilOut d;
+    d.samples = io[d_s], d.a = o.a ? io[d_a] : nullptr, d.b = o.b ? io[d_b] : nullptr;
+    d.nearest = o.nearest ? io[d_near] : nullptr, d.score = io[d_score], d.n_scored = io[d_tail];
+    d.err = (int32_t *)(io[d_tail] + 1);
+    PNCHK(sil_run<T>(ix, call.ws(), io[d_codes], nc, rows ? io[d_rows] : nullptr, m, d, call.s()));
+    PNCHK(io.down());
+    int32_t err = 0;
+    memcpy(&err, &tail[1], sizeof err);
+    if (err) return fail(PN_ERR_INVALID, "a silhouette needs at least two non-empty clusters among the codes");
+    if (o.n_scored) *o.n_scored = tail[0];
+    return PN_OK;
+}
+static SilOut sil_out(double *samples, double *a, double *b, int64_t *nearest, double *score, uint64_t *n_scored, int32_t *err) {
+    SilOut o;
+    o.samples = samples, o.a = a, o.b = b, o.nearest = nearest, o.score = score, o.n_scored = n_scored, o.err = err;
+    return o;
+}
+#define PN_SIL_ENTRIES(SFX, T)                                                                                                \
+    extern "C" int pn_silhouette_##SFX(const pn_index *ix, const int64_t *codes, size_t n_clusters, const uint64_t *rows,      \
+                                       size_t n_rows, unsigned flags, double *samples_out, double *a_out, double *b_out,      \
+                                       int64_t *nearest_out, double *score_out, uint64_t *n_scored_out) {                     \
+        return sil_host<T>(ix, codes, n_clusters, rows, n_rows, flags,                                                        \
+                           sil_out(samples_out, a_out, b_out, nearest_out, score_out, n_scored_out, nullptr));               \
+    }                                                                                                                         \
+    extern "C" int pn_silhouette_device_##SFX(const pn_index *ix, const int64_t *d_codes, size_t n_clusters,                  \
+                                              const uint64_t *d_rows, size_t n_rows, unsigned flags, double *d_samples,       \
+                                              double *d_a, double *d_b, int64_t *d_nearest, double *d_score,                  \
+                                              uint64_t *d_n_scored, int32_t *d_error, void *stream) {                         \
+        return sil_device<T>(ix, d_codes, n_clusters, d_rows, n_rows, flags,                                                  \
+                             sil_out(d_samples, d_a, d_b, d_nearest, d_score, d_n_scored, d_error), (hipStream_t)stream);    \
+    }
+PN_SIL_ENTRIES(f32, float)
+PN_SIL_ENTRIES(f64, double)
+#undef PN_SIL_ENTRIES
 
 extern "C" void pn_free(void *p) { free(p); }
 

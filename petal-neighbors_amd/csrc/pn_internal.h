@@ -376,7 +376,31 @@ template <typename T>
 hipError_t km_update_enqueue(const T *X, size_t n, size_t ld, int dim, const int64_t *labels, size_t nc, void *buf,
                              T *centres, uint64_t *counts, double tol, int last, double **stop_out, hipStream_t s);
 
-// ---- mst.hip, for mean_shift.hip and kmeans.hip: the bitonic network over (key, pair), ascending by key then pair.  N =
+// ---- silhouette.hip: silhouette values of a labelling of the indexed rows (pn_silhouette_*); nothing in it waits for the
+// device.  codes [n] int64 (negative: excluded), rows [m] (nullable: the m = n indexed rows in order); samples [m] and,
+// nullable, a / b / nearest [m], score / n_scored / err [1], all in HBM.  buf: sil_buffer_bytes() bytes, 16-byte aligned.
+// The members' sorted positions are cut into spans of sil_span_len(n) positions (the shape of the sums: the header).
+struct SilArgs {
+    const void *X = nullptr;  // the index's rows [n_pad][ld] of T
+    size_t n = 0, ld = 0;
+    int dim = 0;
+    const int64_t *codes = nullptr;
+    size_t n_clusters = 0;
+    const uint64_t *rows = nullptr;
+    size_t m = 0;
+    void *buf = nullptr;
+    double *samples = nullptr, *a = nullptr, *b = nullptr;
+    int64_t *nearest = nullptr;
+    double *score = nullptr;
+    uint64_t *n_scored = nullptr;
+    int32_t *err = nullptr;
+};
+size_t sil_span_len(size_t n);
+size_t sil_buffer_bytes(size_t n, size_t m, int dim, int elem_bytes);
+template <typename T>
+hipError_t sil_enqueue(const SilArgs &a, hipStream_t s);
+
+// ---- mst.hip, for mean_shift.hip, kmeans.hip and silhouette.hip: the bitonic network over (key, pair), ascending by key then pair.  N =
 // sort_key_pair_len(count): count padded to a power of two, at least the block one workgroup sorts in LDS; the caller pads
 // the arrays (all-ones keys sort last)
 size_t sort_key_pair_len(size_t count);
