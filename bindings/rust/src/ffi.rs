@@ -135,6 +135,19 @@ extern "C" {
                              d_weight: *mut f32, work_out: *mut u64, stream: *mut c_void) -> c_int;
     pub fn pn_mst_device_f64(index: *const pn_index, d_core: *const f64, flags: c_uint, d_src: *mut u64, d_dst: *mut u64,
                              d_weight: *mut f64, work_out: *mut u64, stream: *mut c_void) -> c_int;
+    /// Nearest foreign row: groups [n] codes, core [n] (nullable), rows [n_rows] (nullable with n_rows = 0: every row);
+    /// idx / weight [m]: per answered row the row of another group that minimises (max(d, core[i], core[j]), j) and that
+    /// weight (u64::MAX and a NaN: there is none); flags = 0.  The device entry points write in stream order
+    pub fn pn_nearest_foreign_f32(index: *const pn_index, groups: *const u32, core: *const f32, rows: *const u64,
+                                  n_rows: usize, flags: c_uint, idx_out: *mut u64, weight_out: *mut f32) -> c_int;
+    pub fn pn_nearest_foreign_f64(index: *const pn_index, groups: *const u32, core: *const f64, rows: *const u64,
+                                  n_rows: usize, flags: c_uint, idx_out: *mut u64, weight_out: *mut f64) -> c_int;
+    pub fn pn_nearest_foreign_device_f32(index: *const pn_index, d_groups: *const u32, d_core: *const f32,
+                                         d_rows: *const u64, n_rows: usize, flags: c_uint, d_idx: *mut u64,
+                                         d_weight: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn pn_nearest_foreign_device_f64(index: *const pn_index, d_groups: *const u32, d_core: *const f64,
+                                         d_rows: *const u64, n_rows: usize, flags: c_uint, d_idx: *mut u64,
+                                         d_weight: *mut f64, stream: *mut c_void) -> c_int;
     /// Single-linkage dendrogram of n - 1 sorted tree edges (as pn_mst_* writes them): left / right / weight_out / size
     /// [n - 1], node n + r = the r-th merge; flags = 0.  Edges that are no spanning tree: PN_ERR_INVALID (device entry:
     /// written to d_error, an int32 in HBM, nullable; it never waits for the device)

@@ -404,6 +404,20 @@ class BallTree {
         res.rows_scanned = (size_t)work[1];
         return res;
     }
+    // extension: every row's nearest row of another group (pn_nearest_foreign_*): for row i (each of rows[0 .. n_rows), or
+    // every row in order) the pair {row j with groups[j] != groups[i] that minimises (max(distance(i, j), core[i], core[j]),
+    // j), that weight}; groups: size() codes; core as for mst().  A row without a foreign row gets UINT64_MAX and a NaN
+    std::pair<std::vector<uint64_t>, std::vector<A>> nearest_foreign(const uint32_t *groups, const A *core = nullptr,
+                                                                     const uint64_t *rows = nullptr, size_t n_rows = 0) const {
+        const size_t m = rows ? n_rows : n_;
+        std::vector<uint64_t> idx(m);
+        std::vector<A> weight(m);
+        if constexpr (kF32)
+            check(pn_nearest_foreign_f32(h_, groups, core, rows, n_rows, 0u, idx.data(), weight.data()));
+        else
+            check(pn_nearest_foreign_f64(h_, groups, core, rows, n_rows, 0u, idx.data(), weight.data()));
+        return {std::move(idx), std::move(weight)};
+    }
     // extension: the single-linkage dendrogram (pn_linkage_*) of a spanning tree's edges in merge order -- by default
     // those of mst(core).  Edges that are no spanning tree throw
     Linkage<A> linkage(const Mst<A> &tree) const {

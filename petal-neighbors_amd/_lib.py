@@ -28,6 +28,7 @@ PN_OPT_OPTICS_PIECE = 13
 PN_OPT_KDE_PIECE = 14
 PN_OPT_MS_PIECE = 15
 PN_OPT_KMEANS_FILTER = 16
+PN_OPT_FOREIGN_FILTER = 17
 PN_KDE_GAUSSIAN, PN_KDE_TOPHAT, PN_KDE_EPANECHNIKOV, PN_KDE_EXPONENTIAL, PN_KDE_LINEAR = 0, 1, 2, 3, 4
 PN_RADIUS_SORTED = 1
 PN_SELF_INCLUDE = 2
@@ -93,6 +94,8 @@ PAIRED = {
     "pn_dbscan_device": (_i, [_vp, _R, _sz, _cu] + [_vp] * 4),
     "pn_mst": (_i, [_vp, _vp, _cu] + [_vp] * 4),
     "pn_mst_device": (_i, [_vp, _vp, _cu] + [_vp] * 5),
+    "pn_nearest_foreign": (_i, [_vp, _vp, _vp, _vp, _sz, _cu, _vp, _vp]),
+    "pn_nearest_foreign_device": (_i, [_vp, _vp, _vp, _vp, _sz, _cu, _vp, _vp, _vp]),
     "pn_linkage": (_i, [_vp] * 4 + [_cu] + [_vp] * 4),
     "pn_linkage_device": (_i, [_vp] * 4 + [_cu] + [_vp] * 6),
     "pn_hdbscan": (_i, [_vp, _sz, _sz, _cu] + [_vp] * 3),

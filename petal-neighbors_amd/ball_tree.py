@@ -329,6 +329,55 @@ class BallTree(Handle):
         _, dist = self.query_self_device(int(min_samples))
         return self.mst_device(dist[:, -1].contiguous())
 
+    # ------------------------------------------------------------ nearest foreign row
+    # For a grouping of the indexed rows, every row's nearest row of another group (``pn_nearest_foreign_*``): one Boruvka
+    # step, the nearest-enemy distance, the hypothesis margin, Tomek links, the Dunn index's numerator.  ``core`` means
+    # what it means for ``mst``; the partner minimises (weight, index), so ties are decided by the lower row.
+    def _foreign_groups(self, groups):
+        return self._per_row(groups, np.uint32, f"groups must hold one code per indexed row ({self._n})")
+
+    def nearest_foreign(self, groups, core=None, rows=None):
+        """``(idx uint64 [m], weight [m])``: for each answered row i the row j of another group (``groups[j] !=
+        groups[i]``) that minimises ``(max(d(i, j), core[i], core[j]), j)``, and that weight.  ``groups``: n codes
+        (converted to uint32); ``core``: None or n values; ``rows``: None (all rows, ascending) or row numbers, any
+        order.  A row without a foreign row gets ``idx = 2**64 - 1`` and a NaN weight."""
+        g = self._foreign_groups(groups)
+        c = None
+        if core is not None:
+            c = self._per_row(core, self.dtype, f"core must hold one value per indexed row ({self._n})")
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+        m = self._n if r is None else r.shape[0]
+        idx = np.empty(m, dtype=np.uint64)
+        weight = np.empty(m, dtype=self.dtype)
+        if m:  # (an empty list answers nothing: NULL with 0 rows would mean every row)
+            check(self._fn("nearest_foreign")(self._h, g.ctypes.data, c.ctypes.data if c is not None else None,
+                                              r.ctypes.data if r is not None else None, m if r is not None else 0, 0,
+                                              idx.ctypes.data, weight.ctypes.data))
+        return idx, weight
+
+    def nearest_foreign_device(self, groups, core=None, rows=None, out_idx=None, out_weight=None, stream=None):
+        """``nearest_foreign`` in HBM: ``groups`` an int32 CUDA tensor of n codes (read as uint32), ``core`` None or n
+        values of the tree's element type, ``rows`` None or an int64 CUDA tensor of row numbers; CUDA tensors ``(idx int64
+        [m], weight [m])`` written in stream order on ``stream`` (default: the current torch stream); a row without a
+        foreign row gets ``idx = -1``.  With the first tier the call waits for the device once per 2^18 listed rows."""
+        import torch
+        n = self._n
+        g = self._per_row_device(groups, torch.int32, f"groups must be a contiguous int32 CUDA tensor of {n} codes")
+        if core is not None:
+            core = self._per_row_device(core, self._tdt, f"core must be a contiguous CUDA tensor of {n} values of the "
+                                        "tree's element type")
+        m = n
+        if rows is not None:
+            m = int(rows.numel()) if isinstance(rows, torch.Tensor) else -1
+            rows = self._per_row_device(rows, torch.int64, "rows must be a contiguous 1-D int64 CUDA tensor", count=max(m, 0))
+        idx, weight = self._outs((out_idx, m, torch.int64, m), (out_weight, m, self._tdt, m))
+        if m:
+            check(self._fn("nearest_foreign_device")(
+                self._h, g.data_ptr(), core.data_ptr() if core is not None else None,
+                rows.data_ptr() if rows is not None else None, m if rows is not None else 0, 0, idx.data_ptr(),
+                weight.data_ptr(), stream_arg(stream, self._dev)))
+        return idx, weight
+
     # ------------------------------------------------------- dendrogram, HDBSCAN
     # The single-linkage dendrogram of sorted tree edges (``pn_linkage_*``) in SciPy's layout: the r-th edge makes node
     # n + r with children ``left[r]`` (the subtree that holds ``src[r]``) and ``right[r]``; ids below n are rows.

@@ -45,6 +45,7 @@ UNITS = [
     ("self_graph.hip", ["-ffp-contract=off"]),
     ("components.hip", []),
     ("mst.hip", []),
+    ("foreign.hip", ["-ffp-contract=off"]),
     ("linkage.hip", []),
     ("lof.hip", ["-ffp-contract=off"]),
     ("knn_predict.hip", ["-ffp-contract=off"]),
@@ -63,6 +64,7 @@ COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno
 HEADERS = [os.path.join(CSRC, "pn_internal.h"), os.path.join(CSRC, "bf16_launch.h"), os.path.join(CSRC, "csr_pieces.h"),
            os.path.join(CSRC, "csr_splice.h"),
            os.path.join(CSRC, "host_io.h"),
+           os.path.join(CSRC, "km_pack.h"),
            os.path.join(CSRC, "topk_buffer.h"),
            os.path.join(CSRC, "host_tree.h"),
            os.path.join(CSRC, "union_find.h"),

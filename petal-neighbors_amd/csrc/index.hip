@@ -152,6 +152,7 @@ struct WorkspaceBufs {
     // side lists
     DevBuf w_db, w_db_side;
     DevBuf w_mst;  // pn_mst_*: the scratch of mst.hip (+ round 0's 1-NN answer)
+    DevBuf w_foreign, w_fr_tier;  // pn_nearest_foreign_*: the scratch of foreign_enqueue; the first tier's images and lists (also pn_mst_*)
     // pn_linkage_* / pn_hdbscan_*: the scratch of linkage.hip (+ the core distances and the tree edges of an HDBSCAN call)
     DevBuf w_hdb;
     // pn_lof_* / pn_lof_score_*: the graph store of a fit ([n][k] uint32 ids, [n][k] distances; + lrd and kdist when the
@@ -274,6 +275,7 @@ struct pn_index {
     uint64_t piece[kPieceFamilies] = {};
     uint64_t mst_batch = 0;     // PN_OPT_MST_BATCH: listed rows per scan launch of pn_mst_*, 0 = 2^18
     int kmeans_filter = 0;      // PN_OPT_KMEANS_FILTER: 0 = the engine decides, 1 = the filter wherever it is eligible, 2 = never
+    int foreign_filter = 0;     // PN_OPT_FOREIGN_FILTER: the same choice for the first tier of the masked scans
     // state that queries on a shared `const pn_index *` update: internally synchronised by `mu`
     struct Shared {
         std::mutex mu;
@@ -1109,6 +1111,10 @@ extern "C" int pn_index_set_option(pn_index *ix, int option, int64_t value) {
         case PN_OPT_KMEANS_FILTER:
             if (value < 0 || value > 2) return fail(PN_ERR_INVALID, "bad k-means filter choice %lld", (long long)value);
             ix->kmeans_filter = (int)value;
+            return PN_OK;
+        case PN_OPT_FOREIGN_FILTER:
+            if (value < 0 || value > 2) return fail(PN_ERR_INVALID, "bad foreign-row filter choice %lld", (long long)value);
+            ix->foreign_filter = (int)value;
             return PN_OK;
         default: return fail(PN_ERR_INVALID, "unknown option %d", option);
     }
@@ -3985,6 +3991,41 @@ extern "C" int pn_optics_dbscan_device_f64(const pn_index *ix, const uint64_t *d
 // workspace, and round 0 of an un-cored call -- every row's nearest other row by (distance, index), which is the k = 1
 // self-query and so goes through query_enqueue and whichever tier the handle's engine selects.
 // ---------------------------------------------------------------------------
+// The first tier of the masked scans (foreign.hip): Euclidean indexes of 8 <= dim <= 160.  PN_ENGINE_AUTO (and
+// PN_ENGINE_MFMA) takes it from kFrAutoMinRows rows and kFrAutoMinDim columns on: the smallest shape measured (DESIGN.md
+// 4.25), where the forced tier takes 0.65 - 0.70 of the exact scans' time at 16 columns and 0.40 - 0.44 at 128.  Below it
+// nothing is measured and the exact scan stays: its whole work shrinks with n^2, the tier's fixed cost -- packing the rows,
+// one host wait per batch -- does not.
+constexpr size_t kFrAutoMinRows = 100000, kFrAutoMinDim = 16;
+static bool fr_use_filter(const pn_index *ix) {
+    if (ix->n < 2 || ix->metric != 0 || !foreign_filter_supported((int)ix->dim) || ix->foreign_filter == 2) return false;
+    if (ix->foreign_filter == 1) return true;
+    if (ix->engine == PN_ENGINE_EXACT) return false;
+    if (ix->engine == PN_ENGINE_BF16) return true;
+    return ix->n >= kFrAutoMinRows && ix->dim >= kFrAutoMinDim;
+}
+// the tier of a call whose scans take at most `batch` rows per launch: carved and packed, once.  *usable <- false when a
+// row is flagged (not finite, or a squared norm beyond 2^100): the bound holds for no pair of such a call, so the exact scan
+// answers all of it and the tier is not launched at all -- the host reads that one word here, once per call.
+template <typename T>
+static int fr_prepare(const pn_index *ix, Workspace &ws, size_t batch, ForeignTier *t, bool *usable, hipStream_t s) {
+    PNCHK(ws.w_fr_tier.ensure(foreign_tier_bytes(ix->n, (int)ix->dim, (int)sizeof(T), batch, ix->n_cu)));
+    foreign_tier_at(ws.w_fr_tier.p, ix->n, (int)ix->dim, (int)sizeof(T), batch, ix->n_cu, t);
+    HIPCHK(foreign_pack<T>(*t, (const T *)ix->d_pts, ix->n, ix->ld, (int)ix->dim, s));
+    unsigned long long flagged = 0;
+    HIPCHK(hipMemcpyAsync(&flagged, t->cc + 4, sizeof flagged, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *usable = flagged == 0;
+    return PN_OK;
+}
+static void fr_count(const pn_index *ix, size_t answered, const ForeignWork &w) {
+    std::lock_guard<std::mutex> lk(ix->sh.mu);
+    ix->sh.stats.queries += answered;
+    ix->sh.stats.fallback_queries += w.unproven;
+    ix->sh.stats.candidates += w.evaluated;
+    ix->sh.stats.evaluations += w.evaluated;
+}
+
 static int mst_args(const pn_index *ix, unsigned flags, const void *src, const void *dst, const void *weight, int elem_bytes) {
     if (flags) return fail(PN_ERR_INVALID, "unknown MST flags 0x%x", flags);
     if ((!src || !dst || !weight) && (!ix || ix->n > 1))
@@ -4021,6 +4062,12 @@ static int mst_run(const pn_index *ix, Workspace &ws, const T *d_core, uint64_t 
     const size_t scratch = round_up(mst_buffer_bytes(n, (int)sizeof(T), a.batch, a.n_cu), (size_t)16);
     PNCHK(ws.w_mst.ensure(scratch + (d_core ? 0 : n * (sizeof(uint64_t) + sizeof(T)))));
     a.buf = ws.w_mst.p;
+    ForeignTier tier;
+    if (fr_use_filter(ix)) {
+        bool usable = false;
+        PNCHK(fr_prepare<T>(ix, ws, std::min(a.batch, n), &tier, &usable, s));
+        if (usable) a.tier = &tier;
+    }
     if (!d_core) {
         uint64_t *nn_idx = (uint64_t *)((char *)ws.w_mst.p + scratch);
         T *nn_dist = (T *)(nn_idx + n);
@@ -4036,6 +4083,7 @@ static int mst_run(const pn_index *ix, Workspace &ws, const T *d_core, uint64_t 
     }
     int rc;
     rc = mst_enqueue<T>(a, s);
+    if (rc == PN_OK) fr_count(ix, 0, a.tier_work);
     if (rc == PN_OK && work_out) {
         work_out[0] = a.work[0];
         work_out[1] = a.work[1];
@@ -4081,6 +4129,90 @@ extern "C" int pn_mst_device_f64(const pn_index *ix, const double *d_core, unsig
                                  double *d_weight, uint64_t *work_out, void *stream) {
     return mst_device<double>(ix, d_core, flags, d_src, d_dst, d_weight, work_out, (hipStream_t)stream);
 }
+
+// ---------------------------------------------------------------------------
+// Nearest foreign row: pn_nearest_foreign_{,device_}{f32,f64} -- the listed masked scan of the MST rounds with the
+// caller's grouping in the place of the components (mst.hip, foreign_enqueue; the first tier: foreign.hip).  Here: the
+// argument checks, the workspace and the counters.
+// ---------------------------------------------------------------------------
+// (before any device is touched; the header states the order)
+static int fr_args(const pn_index *ix, const void *groups, const void *rows, size_t n_rows, unsigned flags, const void *idx,
+                   const void *weight, int elem_bytes) {
+    if (flags) return fail(PN_ERR_INVALID, "unknown nearest-foreign flags 0x%x", flags);
+    if (!rows && n_rows) return fail(PN_ERR_INVALID, "rows is NULL with n_rows = %zu (NULL and 0: every row)", n_rows);
+    if ((!idx || !weight) && (!ix || ix->n > 0) && !(rows && n_rows == 0))
+        return fail(PN_ERR_INVALID, "%s is NULL", !idx ? "idx_out" : "weight_out");
+    if (!groups && (!ix || ix->n > 0)) return fail(PN_ERR_INVALID, "groups is NULL");
+    if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
+    if (ix->elem_bytes != elem_bytes) return fail(PN_ERR_INVALID, "index element type mismatch");
+    if (ix->n > 0x7FFFFFFFull || n_rows > 0x7FFFFFFFull)
+        return fail(PN_ERR_UNSUPPORTED, "too many rows for a nearest-foreign query (32-bit row numbers)");
+    return PN_OK;
+}
+// in a held workspace, on stream s; everything in HBM; m = the rows asked for (n without a list)
+template <typename T>
+static int fr_run(const pn_index *ix, Workspace &ws, const uint32_t *d_groups, const T *d_core, const uint64_t *d_rows,
+                  size_t m, uint64_t *d_idx, T *d_weight, hipStream_t s) {
+    if (m == 0 || ix->n == 0) return PN_OK;
+    ForeignArgs a;
+    a.P = ix->d_pts, a.n = ix->n, a.ld = ix->ld, a.dim = (int)ix->dim;
+    a.cnorm = ix->metric == 1 ? ix->d_cnorm : nullptr;
+    a.d_groups = d_groups, a.d_core = d_core, a.d_rows = d_rows, a.m = m, a.index_base = ix->index_base;
+    a.batch = ix->mst_batch ? (size_t)std::min<uint64_t>(ix->mst_batch, (uint64_t)1 << 24) : kSelfChunk;
+    a.n_cu = ix->n_cu;
+    a.d_idx = d_idx, a.d_weight = d_weight;
+    PNCHK(ws.w_foreign.ensure(foreign_buffer_bytes(a.n, m, (int)sizeof(T), a.batch, a.n_cu)));
+    a.buf = ws.w_foreign.p;
+    ForeignTier tier;
+    if (m >= kFrMinLaunch && fr_use_filter(ix)) {  // (a shorter list never reaches the tier: nothing is packed for it)
+        bool usable = false;
+        PNCHK(fr_prepare<T>(ix, ws, std::min(a.batch, m), &tier, &usable, s));
+        if (usable) a.tier = &tier;
+    }
+    const int rc = foreign_enqueue<T>(a, s);
+    if (rc == PN_OK) fr_count(ix, m, a.work);
+    return rc;
+}
+template <typename T>
+static int fr_device(const pn_index *ix, const uint32_t *d_groups, const T *d_core, const uint64_t *d_rows, size_t n_rows,
+                     unsigned flags, uint64_t *d_idx, T *d_weight, hipStream_t s) {
+    PNCHK(fr_args(ix, d_groups, d_rows, n_rows, flags, d_idx, d_weight, (int)sizeof(T)));
+    CallScope call(ix);
+    PNCHK(call.on_stream(s));
+    return fr_run<T>(ix, call.ws(), d_groups, d_core, d_rows, d_rows ? n_rows : ix->n, d_idx, d_weight, s);
+}
+template <typename T>
+static int fr_host(const pn_index *ix, const uint32_t *groups, const T *core, const uint64_t *rows, size_t n_rows,
+                   unsigned flags, uint64_t *idx, T *weight) {
+    PNCHK(fr_args(ix, groups, rows, n_rows, flags, idx, weight, (int)sizeof(T)));
+    const size_t n = ix->n, m = rows ? n_rows : n;
+    for (size_t r = 0; r < n_rows; ++r)  // (the device entries cannot look; here a bad row number is an argument error)
+        if (rows[r] >= n) return fail(PN_ERR_INVALID, "rows[%zu] = %llu is not below the %zu indexed rows", r,
+                                      (unsigned long long)rows[r], n);
+    if (m == 0) return PN_OK;
+    CallScope call(ix);
+    PNCHK(call.own_stream());
+    HostIo io(call);
+    const auto [d_groups, d_core, d_rows, d_idx, d_weight] =
+        std::tuple{io.in(groups, n), io.in(core, core ? n : 0), io.in(rows, n_rows), io.out(idx, m), io.out(weight, m)};
+    PNCHK(io.up());
+    PNCHK(fr_run<T>(ix, call.ws(), io[d_groups], core ? io[d_core] : nullptr, rows ? io[d_rows] : nullptr, m, io[d_idx],
+                    io[d_weight], call.s()));
+    return io.down();
+}
+#define PN_FR_ENTRIES(SFX, T)                                                                                                 \
+    extern "C" int pn_nearest_foreign_##SFX(const pn_index *ix, const uint32_t *groups, const T *core, const uint64_t *rows, \
+                                            size_t n_rows, unsigned flags, uint64_t *idx_out, T *weight_out) {               \
+        return fr_host<T>(ix, groups, core, rows, n_rows, flags, idx_out, weight_out);                                       \
+    }                                                                                                                         \
+    extern "C" int pn_nearest_foreign_device_##SFX(const pn_index *ix, const uint32_t *d_groups, const T *d_core,            \
+                                                   const uint64_t *d_rows, size_t n_rows, unsigned flags, uint64_t *d_idx,   \
+                                                   T *d_weight, void *stream) {                                              \
+        return fr_device<T>(ix, d_groups, d_core, d_rows, n_rows, flags, d_idx, d_weight, (hipStream_t)stream);              \
+    }
+PN_FR_ENTRIES(f32, float)
+PN_FR_ENTRIES(f64, double)
+#undef PN_FR_ENTRIES
 
 // ---------------------------------------------------------------------------
 // Single-linkage dendrogram of sorted tree edges: pn_linkage_{,device_}{f32,f64}, and HDBSCAN labels:

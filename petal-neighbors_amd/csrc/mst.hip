@@ -1,6 +1,8 @@
 // mst.hip -- the exact minimum spanning tree of the indexed rows under mutual reachability (pn_mst_*): Boruvka rounds
-// under a strict edge order.  The distances come from exact_scan.hip's masked scan (mst_scan_kernel); what is here is the
-// bookkeeping between scans, the round loop and the final sort.
+// under a strict edge order.  The distances come from exact_scan.hip's masked scan (mst_scan_kernel), on Euclidean indexes
+// behind foreign.hip's bf16 first tier where the engine takes it (scan_listed_rows); what is here is the bookkeeping
+// between scans, the round loop and the final sort -- and pn_nearest_foreign_*, the same listed scan with the caller's
+// grouping in the place of the components (foreign_enqueue).
 //
 // The graph is complete over the n rows; the edge {i, j}, i < j, weighs w = max(d(i, j), core[i], core[j]), the maximum
 // taken on the library's sortable keys (NaN above +inf, -0 as +0; signed keys for Cosine, and a negative core value of a
@@ -349,13 +351,164 @@ struct Layout {
                              hipGetErrorString(e_));                                                         \
     } while (0)
 
+// ---- the listed masked scan: rows list[0 .. nlist) -> their least (key(w), j) over the rows of other components / groups,
+// into cand_key / cand_j [row].  `batch` rows per launch; the exact scan's segments are sized so that a short list still
+// fills the device.  With a tier (foreign.hip, Euclidean only) the first tier answers a batch first and the exact scan the
+// rows it could not prove: the host reads their number once per batch -- to plan that scan, and for the counters.
+template <typename T>
+struct ListedScan {
+    using K = typename KeyOf<T>::type;
+    const T *P = nullptr, *cnorm = nullptr;
+    size_t n = 0, ld = 0;
+    int dim = 0;
+    const uint32_t *comp = nullptr;
+    const K *ckey = nullptr;
+    K *cand_key = nullptr, *seg_key = nullptr;
+    uint32_t *cand_j = nullptr, *seg_j = nullptr;
+    size_t seg_entries = 0, batch = 1;
+    int n_cu = 256;
+    const ForeignTier *tier = nullptr;
+    ForeignWork *work = nullptr;
+};
+size_t scan_seg_entries(size_t n, size_t batch, int n_cu) {
+    const size_t bmax = batch < n ? batch : n, qt = (bmax + kTileQ - 1) / kTileQ, target = (size_t)8 * (size_t)n_cu;
+    return (qt > target ? qt : target) * kTileQ;
+}
+template <typename T>
+int scan_listed_rows(const ListedScan<T> &c, const uint32_t *list, size_t nlist, hipStream_t s) {
+    using K = typename KeyOf<T>::type;
+    const size_t row_tiles = (c.n + kTileP - 1) / kTileP, target = (size_t)8 * (size_t)c.n_cu;
+    const dim3 blk(256);
+    auto exact = [&](const uint32_t *rows, size_t nq) -> int {
+        const size_t qt = (nq + kTileQ - 1) / kTileQ;
+        size_t nseg = target / qt;
+        nseg = nseg < 1 ? 1 : (nseg > row_tiles ? row_tiles : nseg);
+        const size_t seg_tiles = (row_tiles + nseg - 1) / nseg;
+        nseg = (row_tiles + seg_tiles - 1) / seg_tiles;
+        if (nseg * qt * kTileQ > c.seg_entries) return set_error(PN_ERR_DEVICE, "MST scan plan exceeds its scratch (internal error)");
+        MSTCHK(launch_mst_scan<T>(c.P, c.n, c.dim, c.ld, rows, (int)nq, seg_tiles * kTileP, (int)nseg, c.comp, c.ckey, c.cnorm,
+                                  c.seg_key, c.seg_j, s));
+        hipLaunchKernelGGL((mst_reduce_kernel<K>), rows_grid(nq), blk, 0, s, rows, nq, qt * kTileQ, (int)nseg, c.seg_key,
+                           c.seg_j, c.cand_key, c.cand_j);
+        MSTCHK(hipGetLastError());
+        return PN_OK;
+    };
+    for (size_t r0 = 0; r0 < nlist; r0 += c.batch) {
+        const size_t nq = nlist - r0 < c.batch ? nlist - r0 : c.batch;
+        // (a launch of fewer rows than half a tile of the tier -- a short list, or PN_OPT_MST_BATCH cut small -- would pay
+        // the tier's host wait for a nearly empty MFMA tile: the exact scan takes it, as it did before there was a tier)
+        if (!c.tier || nq < kFrMinLaunch) {
+            const int rc = exact(list + r0, nq);
+            if (rc != PN_OK) return rc;
+            continue;
+        }
+        MSTCHK(launch_foreign_filter<T>(*c.tier, c.P, c.n, c.ld, c.dim, list + r0, nq, c.comp, c.ckey, c.cand_key, c.cand_j, s));
+        uint32_t h[2] = {0, 0};
+        MSTCHK(hipMemcpyAsync(h, c.tier->ctr, sizeof h, hipMemcpyDeviceToHost, s));
+        MSTCHK(hipStreamSynchronize(s));
+        if ((size_t)h[0] > nq) return set_error(PN_ERR_DEVICE, "the first tier listed %u of %zu rows (internal error)", h[0], nq);
+        if (c.work) {
+            c.work->unproven += h[0];
+            c.work->evaluated += h[1];
+        }
+        if (h[0]) {
+            const int rc = exact(c.tier->sel, (size_t)h[0]);
+            if (rc != PN_OK) return rc;
+        }
+    }
+    return PN_OK;
+}
+
+// ---- pn_nearest_foreign_*: the core keys, the list of the rows to answer, the answer
+template <typename T>
+__global__ __launch_bounds__(256) void fr_keys_kernel(size_t n, const T *__restrict__ core, bool signed_keys,
+                                                      typename KeyOf<T>::type *__restrict__ ckey) {
+    using K = typename KeyOf<T>::type;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) ckey[i] = core ? key_of<T>(core[i], signed_keys) : (K)0;
+}
+// (a row number at or beyond n is scanned as row 0 and answered as a row without a foreign row)
+__global__ __launch_bounds__(256) void fr_list_kernel(size_t m, size_t n, const uint64_t *__restrict__ rows,
+                                                      uint32_t *__restrict__ list) {
+    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < m) list[r] = rows ? (rows[r] < n ? (uint32_t)rows[r] : 0u) : (uint32_t)r;
+}
+template <typename T>
+__global__ __launch_bounds__(256) void fr_output_kernel(size_t m, size_t n, const uint64_t *__restrict__ rows,
+                                                        const uint32_t *__restrict__ list,
+                                                        const typename KeyOf<T>::type *__restrict__ cand_key,
+                                                        const uint32_t *__restrict__ cand_j, uint64_t base, bool signed_keys,
+                                                        uint64_t *__restrict__ idx, T *__restrict__ weight) {
+    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= m) return;
+    const uint32_t row = list[r];
+    const bool none = (rows && rows[r] >= n) || cand_j[row] == kNoRow;
+    idx[r] = none ? ~0ull : base + (uint64_t)cand_j[row];
+    weight[r] = value_of<T>(none ? KeyOf<T>::kMax : cand_key[row], signed_keys);
+}
+// ckey [n], cand_key [n], seg_key [seg_entries] | cand_j [n], list [m], seg_j [seg_entries]
+struct ForeignLayout {
+    size_t seg_entries, o_u32, total;
+    ForeignLayout(size_t n, size_t m, int elem_bytes, size_t batch, int n_cu) {
+        seg_entries = scan_seg_entries(n, batch, n_cu);
+        o_u32 = round_up((2 * n + seg_entries) * (size_t)elem_bytes, (size_t)8);
+        total = o_u32 + (n + m + seg_entries) * 4;
+    }
+};
+
 }  // namespace
+
+size_t foreign_buffer_bytes(size_t n, size_t m, int elem_bytes, size_t batch, int n_cu) {
+    return ForeignLayout(n, m, elem_bytes, batch ? batch : 1, n_cu).total;
+}
+template <typename T>
+int foreign_enqueue(ForeignArgs &a, hipStream_t s) {
+    using K = typename KeyOf<T>::type;
+    const size_t n = a.n, m = a.m;
+    a.work = ForeignWork{};
+    if (m == 0 || n == 0) return PN_OK;
+    const size_t batch = a.batch ? a.batch : 1;
+    const ForeignLayout L(n, m, (int)sizeof(T), batch, a.n_cu);
+    K *ckey = (K *)a.buf, *cand_key = ckey + n, *seg_key = cand_key + n;
+    uint32_t *cand_j = (uint32_t *)((char *)a.buf + L.o_u32), *list = cand_j + n, *seg_j = list + m;
+    const bool cosm = a.cnorm != nullptr;
+    const dim3 blk(256);
+    hipLaunchKernelGGL((fr_keys_kernel<T>), rows_grid(n), blk, 0, s, n, (const T *)a.d_core, cosm, ckey);
+    hipLaunchKernelGGL(fr_list_kernel, rows_grid(m), blk, 0, s, m, n, a.d_rows, list);
+    MSTCHK(hipGetLastError());
+    ListedScan<T> scan;
+    scan.P = (const T *)a.P;
+    scan.cnorm = (const T *)a.cnorm;
+    scan.n = n;
+    scan.ld = a.ld;
+    scan.dim = a.dim;
+    scan.comp = a.d_groups;
+    scan.ckey = ckey;
+    scan.cand_key = cand_key;
+    scan.cand_j = cand_j;
+    scan.seg_key = seg_key;
+    scan.seg_j = seg_j;
+    scan.seg_entries = L.seg_entries;
+    scan.batch = batch;
+    scan.n_cu = a.n_cu;
+    scan.tier = a.tier;
+    scan.work = &a.work;
+    const int rc = scan_listed_rows<T>(scan, list, m, s);
+    if (rc != PN_OK) return rc;
+    hipLaunchKernelGGL((fr_output_kernel<T>), rows_grid(m), blk, 0, s, m, n, a.d_rows, list, cand_key, cand_j, a.index_base,
+                       cosm, a.d_idx, (T *)a.d_weight);
+    MSTCHK(hipGetLastError());
+    return PN_OK;
+}
+template int foreign_enqueue<float>(ForeignArgs &, hipStream_t);
+template int foreign_enqueue<double>(ForeignArgs &, hipStream_t);
 
 template <typename T>
 int mst_enqueue(MstArgs &a, hipStream_t s) {
     using K = typename KeyOf<T>::type;
     const size_t n = a.n;
     a.work[0] = a.work[1] = 0;
+    a.tier_work = ForeignWork{};
     if (n < 2) return PN_OK;
     const size_t batch = a.batch ? a.batch : 1;
     const Layout L(n, (int)sizeof(T), batch, a.n_cu);
@@ -369,30 +522,29 @@ int mst_enqueue(MstArgs &a, hipStream_t s) {
     const bool cosm = a.cnorm != nullptr;
     const T *P = (const T *)a.P, *cnorm = (const T *)a.cnorm;
     const dim3 g = rows_grid(n), blk(256);
-    const size_t row_tiles = (n + kTileP - 1) / kTileP, target = (size_t)8 * (size_t)a.n_cu;
 
     MSTCHK(hipMemsetAsync(ctr, 0, 4 * sizeof(uint32_t), s));
     hipLaunchKernelGGL((mst_init_kernel<T>), g, blk, 0, s, n, (const T *)a.d_core, cosm, comp, parent, cand_j, list, ckey);
     MSTCHK(hipGetLastError());
 
-    // the listed rows list[0 .. nlist), `batch` per launch; segments sized so that a short list still fills the device
-    auto scan_listed = [&](size_t nlist) -> int {
-        for (size_t r0 = 0; r0 < nlist; r0 += batch) {
-            const size_t nq = nlist - r0 < batch ? nlist - r0 : batch;
-            const size_t qt = (nq + kTileQ - 1) / kTileQ;
-            size_t nseg = target / qt;
-            nseg = nseg < 1 ? 1 : (nseg > row_tiles ? row_tiles : nseg);
-            const size_t seg_tiles = (row_tiles + nseg - 1) / nseg;
-            nseg = (row_tiles + seg_tiles - 1) / seg_tiles;
-            if (nseg * qt * kTileQ > L.seg_entries) return set_error(PN_ERR_DEVICE, "MST scan plan exceeds its scratch (internal error)");
-            MSTCHK(launch_mst_scan<T>(P, n, a.dim, a.ld, list + r0, (int)nq, seg_tiles * kTileP, (int)nseg, comp, ckey, cnorm,
-                                      seg_key, seg_j, s));
-            hipLaunchKernelGGL((mst_reduce_kernel<K>), rows_grid(nq), blk, 0, s, list + r0, nq, qt * kTileQ, (int)nseg, seg_key,
-                               seg_j, cand_key, cand_j);
-            MSTCHK(hipGetLastError());
-        }
-        return PN_OK;
-    };
+    ListedScan<T> ls;
+    ls.P = P;
+    ls.n = n;
+    ls.ld = a.ld;
+    ls.dim = a.dim;
+    ls.cnorm = cnorm;
+    ls.comp = comp;
+    ls.ckey = ckey;
+    ls.cand_key = cand_key;
+    ls.cand_j = cand_j;
+    ls.seg_key = seg_key;
+    ls.seg_j = seg_j;
+    ls.seg_entries = L.seg_entries;
+    ls.batch = batch;
+    ls.n_cu = a.n_cu;
+    ls.tier = a.tier;
+    ls.work = &a.tier_work;
+    auto scan_listed = [&](size_t nlist) -> int { return scan_listed_rows<T>(ls, list, nlist, s); };
     auto min_keys = [&]() -> int {
         MSTCHK(hipMemsetAsync(cmin_key, 0xFF, n * sizeof(K), s));
         hipLaunchKernelGGL((mst_minkey_kernel<K>), g, blk, 0, s, n, comp, cand_j, cand_key, cmin_key);

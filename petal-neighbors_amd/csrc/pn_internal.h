@@ -169,7 +169,71 @@ hipError_t launch_mst_scan(const T *P, size_t n, int dim, size_t ldp, const uint
                            int nseg, const uint32_t *comp, const typename KeyOf<T>::type *ckey, const T *cnorm,
                            typename KeyOf<T>::type *seg_key, uint32_t *seg_j, hipStream_t s);
 
-// ---- mst.hip: Boruvka under the strict edge order (pn_mst_*): bookkeeping kernels and the round loop
+// ---- foreign.hip: the first tier of the masked scan on Euclidean indexes: a bf16 MFMA self-join of the
+// listed rows against every row, an exact re-rank of m candidates per row and a proof in key order.  Nothing in it waits
+// for the device.  The tier's state of one call, carved from one 16-byte aligned buffer (foreign_tier_bytes/_at):
+struct ForeignTier {
+    // the centred two-image packing of all n rows (km_pack.h; the fields of KmRowImage)
+    uint16_t *img = nullptr, *lo = nullptr;   // [n_img][dp] bf16 bits each, rows at and beyond n zero
+    double *xn = nullptr;                     // [n] |x - mu|^2 rounded down; NaN: the row is flagged
+    float *xh = nullptr, *xl = nullptr, *xe = nullptr;  // [n] upper bounds of |x^|, |x~| and |e_x|
+    size_t n_img = 0;                         // n rounded up to 128
+    int dp = 0;                               // dim rounded up to 16
+    float *cn = nullptr;                      // [n_img] |x - mu|^2 rounded down to f32, +inf for the padding
+    unsigned long long *cc = nullptr;         // [8]: the maxima Ce, B, Ch, Cl over the rows, then the "a row is flagged" word
+    float *mu = nullptr;                      // [dim] the corpus mean
+    double *sums = nullptr;                   // [ceil(n / 4096)][dim] column sums of blocks of rows (scratch of the mean)
+    void *seg_key = nullptr;                  // [seg_entries] keys of the segments' lists
+    uint32_t *seg_j = nullptr;                // [seg_entries] their rows
+    uint32_t *sel = nullptr;                  // [batch] the rows the tier could not prove
+    uint32_t *ctr = nullptr;                  // [4]: {unproven rows, candidates evaluated} of the last launch
+    size_t seg_entries = 0;
+    int n_cu = 256;
+};
+bool foreign_filter_supported(int dim);  // 8 <= dim <= 160
+constexpr size_t kFrMinLaunch = 64;  // a scan launch of fewer listed rows than half a tile of the tier takes the exact scan
+size_t foreign_tier_bytes(size_t n, int dim, int elem_bytes, size_t batch, int n_cu);
+void foreign_tier_at(void *buf, size_t n, int dim, int elem_bytes, size_t batch, int n_cu, ForeignTier *t);
+// mean, images, norms and maxima of the rows: once per call
+template <typename T>
+hipError_t foreign_pack(const ForeignTier &t, const T *X, size_t n, size_t ld, int dim, hipStream_t s);
+// Listed rows list[0 .. nq) (nq <= the tier's batch) against every row: a proven row's least (key(w), j) over the rows j
+// with comp[j] != comp[row] goes to cand_key / cand_j [row] (kMax / 0xFFFFFFFF: there is none); the others are listed in
+// t.sel[0 .. t.ctr[0]), any order; t.ctr[1] <- the candidates evaluated.  comp, ckey [n]: as launch_mst_scan takes them.
+template <typename T>
+hipError_t launch_foreign_filter(const ForeignTier &t, const T *X, size_t n, size_t ld, int dim, const uint32_t *list,
+                                 size_t nq, const uint32_t *comp, const typename KeyOf<T>::type *ckey,
+                                 typename KeyOf<T>::type *cand_key, uint32_t *cand_j, hipStream_t s);
+
+// ---- mst.hip: the listed masked scan behind pn_mst_* and pn_nearest_foreign_*, Boruvka under the strict edge order
+// (pn_mst_*): bookkeeping kernels and the round loop
+// what the first tier did in a call: rows it left to the exact scan, candidates it evaluated in the reference's fold
+struct ForeignWork {
+    uint64_t unproven = 0, evaluated = 0;
+};
+struct ForeignArgs {
+    const void *P = nullptr;      // the index's rows [n_pad][ld] of T
+    size_t n = 0, ld = 0;
+    int dim = 0;
+    const void *cnorm = nullptr;  // Cosine: the rows' norms (T); NULL: Euclidean
+    const uint32_t *d_groups = nullptr;  // [n]
+    const void *d_core = nullptr;        // [n] of T, nullable
+    const uint64_t *d_rows = nullptr;    // [m] row numbers, nullable: the m = n rows in order
+    size_t m = 0;
+    uint64_t index_base = 0;
+    size_t batch = 0;             // listed rows per scan launch (>= 1)
+    int n_cu = 256;
+    const ForeignTier *tier = nullptr;  // packed (foreign_pack) when the first tier is to run, else NULL
+    void *buf = nullptr;          // foreign_buffer_bytes() bytes of scratch
+    uint64_t *d_idx = nullptr;    // [m]
+    void *d_weight = nullptr;     // [m] of T
+    ForeignWork work;             // out
+};
+size_t foreign_buffer_bytes(size_t n, size_t m, int elem_bytes, size_t batch, int n_cu);
+// enqueues on s; with a tier it blocks the host once per batch (to read how many rows are left to the exact scan)
+template <typename T>
+int foreign_enqueue(ForeignArgs &a, hipStream_t s);
+
 struct MstArgs {
     const void *P = nullptr;      // the index's rows [n_pad][ld] of T
     size_t n = 0, ld = 0;
@@ -183,10 +247,12 @@ struct MstArgs {
     uint64_t index_base = 0;
     size_t batch = 0;             // listed rows per scan launch (>= 1)
     int n_cu = 256;
+    const ForeignTier *tier = nullptr;  // packed once per call when the first tier answers the listed rows first, else NULL
     void *buf = nullptr;          // mst_buffer_bytes() bytes of scratch
     uint64_t *d_src = nullptr, *d_dst = nullptr;  // [n - 1]
     void *d_weight = nullptr;     // [n - 1] of T
     uint64_t work[2] = {0, 0};    // out: rounds, rows scanned
+    ForeignWork tier_work;        // out
 };
 size_t mst_buffer_bytes(size_t n, int elem_bytes, size_t batch, int n_cu);
 // enqueues on s, blocks the host once per round; PN_OK or an error code with pn_last_error() set

@@ -5,9 +5,14 @@ with the k = 10 core distances (query_self_device(10)'s last column), interleave
   * mst_device: total ms, rounds and rows scanned (pn_mst_*'s work_out);
   * query_self_device(1) on the handle's own engine: what round 0 of the un-cored call should cost;
   * one query_self_device(1) pass on the exact engine, times the rounds: what Boruvka without the three shortcuts costs.
+--tiers measures mst_device three times instead, interleaved: with the first tier of the masked scans (foreign.hip) never
+used (PN_OPT_FOREIGN_FILTER = 2: the exact scans alone), forced (1) and as PN_ENGINE_AUTO decides (0), and records what
+the forced tier left to the exact scan (pn_stats.fallback_queries over the rows scanned).  --dim sets the row width.
 --trace also runs each configuration once in a child process under `rocprofv3 --kernel-trace --stats` and adds the summed
-duration of the masked scan kernel (mst_scan_kernel).  Appends one JSON line to profiles/mst_bench.jsonl (--out).
-usage: python tools/bench_mst.py [--reps 3] [--n 100000,1000000] [--only uniform|blobs] [--trace] [--out FILE]"""
+durations of the masked scan kernel (scan_kernel_ms: mst_scan_kernel) and of the first tier's filter kernel
+(filter_kernel_ms: fr_filter_kernel).  Appends one JSON line to profiles/mst_bench.jsonl (--out).
+usage: python tools/bench_mst.py [--reps 3] [--n 100000,1000000] [--dim 16] [--only uniform|blobs] [--cores 0,1] [--tiers]
+       [--trace] [--out FILE]"""
 import argparse
 import csv
 import glob
@@ -67,10 +72,42 @@ def blob_rows(n, dim, nb, sigma, background, seed):
     return torch.from_numpy(pts[rng.permutation(n)].astype(np.float32)).to(DEV)
 
 
+DIM = 16
+PN_OPT_FOREIGN_FILTER = 17
+
+
 def rows_of(kind, n):
     if kind == "uniform":
-        return uniform_rows(n, 16, 0x5E1F5EEE)
-    return blob_rows(n, 16, max(1, n * 12 // 12000), 0.05, 0.10, 3)
+        return uniform_rows(n, DIM, 0x5E1F5EEE)
+    return blob_rows(n, DIM, max(1, n * 12 // 12000), 0.05, 0.10, 3)
+
+
+def measure_tiers(kind, n, cored, reps):
+    x = rows_of(kind, n)
+    tree = pn.BallTree.from_device(x)
+    core = tree.query_self_device(K_CORE)[1][:, -1].contiguous() if cored else None
+    outs = dict(out_src=torch.empty(n - 1, dtype=torch.int64, device=DEV), out_dst=torch.empty(n - 1, dtype=torch.int64, device=DEV),
+                out_weight=torch.empty(n - 1, dtype=torch.float32, device=DEV))
+
+    def run(choice):
+        def f():
+            tree.set_option(PN_OPT_FOREIGN_FILTER, choice)
+            tree.mst_device(core, **outs)
+        return f
+
+    t_exact, t_forced, t_auto = interleaved([run(2), run(1), run(0)], reps)
+    tree.stats(reset=True)
+    run(1)()
+    st = tree.stats()
+    rounds, scanned = tree.last_mst_work
+    listed = scanned - (0 if cored else n)  # (round 0 of an un-cored call is the 1-NN self-query)
+    rec = {"n": n, "dim": DIM, "k_core": K_CORE if cored else 0, "rounds": rounds, "rows_scanned": scanned,
+           "mst_exact_scans_ms": [round(v, 2) for v in t_exact], "mst_forced_tier_ms": [round(v, 2) for v in t_forced],
+           "mst_auto_ms": [round(v, 2) for v in t_auto], "tier_rows": listed,
+           "tier_left_to_exact": st["fallback_queries"], "tier_left_rate": round(st["fallback_queries"] / max(listed, 1), 5),
+           "tier_candidates": st["candidates"]}
+    tree.close()
+    return rec
 
 
 def measure(kind, n, cored, reps):
@@ -101,7 +138,7 @@ def measure(kind, n, cored, reps):
     rounds, scanned = tree.last_mst_work
     med = lambda v: float(np.median(v))  # noqa: E731
     rec = {
-        "n": n, "dim": 16, "k_core": K_CORE if cored else 0, "rounds": rounds, "rows_scanned": scanned,
+        "n": n, "dim": DIM, "k_core": K_CORE if cored else 0, "rounds": rounds, "rows_scanned": scanned,
         "rows_scanned_over_n": round(scanned / n, 3),
         "mst_ms": [round(v, 2) for v in tm], "self_1nn_ms": [round(v, 2) for v in ta],
         "self_1nn_exact_engine_ms": [round(v, 2) for v in te],
@@ -114,17 +151,18 @@ def measure(kind, n, cored, reps):
 
 
 def traced_scan_ms(kind, n, cored):
-    """summed duration of mst_scan_kernel over ONE mst_device call (plus its warm-up: halved), in a fresh child process"""
+    """summed durations of mst_scan_kernel and of the first tier's fr_filter_kernel over ONE mst_device call (plus its warm-up: halved), in a fresh child process"""
     with tempfile.TemporaryDirectory() as d:
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "mst", "--", sys.executable,
-               os.path.abspath(__file__), "--child", kind, str(n), "1" if cored else "0"]
+               os.path.abspath(__file__), "--child", kind, str(n), "1" if cored else "0", str(DIM)]
         subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL)
-        total = 0.0
+        total = {"mst_scan_kernel": 0.0, "fr_filter_kernel": 0.0}
         for f in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
             for row in csv.DictReader(open(f)):
-                if "mst_scan_kernel" in row["Name"]:
-                    total += float(row["TotalDurationNs"]) / 1e6
-    return round(total / 2, 2)
+                for name in total:
+                    if name in row["Name"]:
+                        total[name] += float(row["TotalDurationNs"]) / 1e6
+    return {"scan_kernel_ms": round(total["mst_scan_kernel"] / 2, 2), "filter_kernel_ms": round(total["fr_filter_kernel"] / 2, 2)}
 
 
 def child(kind, n, cored):
@@ -138,7 +176,9 @@ def child(kind, n, cored):
 
 
 def main():
+    global DIM
     if len(sys.argv) > 1 and sys.argv[1] == "--child":
+        DIM = int(sys.argv[5]) if len(sys.argv) > 5 else 16
         child(sys.argv[2], int(sys.argv[3]), sys.argv[4] == "1")
         return
     ap = argparse.ArgumentParser()
@@ -147,8 +187,11 @@ def main():
     ap.add_argument("--only", default="")
     ap.add_argument("--cores", default="0,1", help="0: without cores, 1: with the k = 10 cores")
     ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--tiers", action="store_true")
+    ap.add_argument("--dim", type=int, default=16)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mst_bench.jsonl"))
     args = ap.parse_args()
+    DIM = args.dim
     res = {"tool": "bench_mst"}
     for kind in ("uniform", "blobs"):
         if args.only not in ("", kind):
@@ -156,10 +199,12 @@ def main():
         for n in (int(v) for v in args.n.split(",")):
             for cored in (c == "1" for c in args.cores.split(",")):
                 tag = f"{kind}_{n}_{'k10' if cored else 'plain'}"
-                res[tag] = measure(kind, n, cored, args.reps)
+                if args.tiers:
+                    tag += f"_d{DIM}_tiers"
+                res[tag] = (measure_tiers if args.tiers else measure)(kind, n, cored, args.reps)
                 torch.cuda.empty_cache()
                 if args.trace:
-                    res[tag]["scan_kernel_ms"] = traced_scan_ms(kind, n, cored)
+                    res[tag].update(traced_scan_ms(kind, n, cored))
                 print(tag, json.dumps(res[tag]), flush=True)
     line = json.dumps(res)
     print(line)
