@@ -450,7 +450,7 @@ __global__ __launch_bounds__(256) void fr_output_kernel(size_t m, size_t n, cons
 struct ForeignLayout {
     size_t seg_entries, o_u32, total;
     ForeignLayout(size_t n, size_t m, int elem_bytes, size_t batch, int n_cu) {
-        seg_entries = scan_seg_entries(n, batch, n_cu);
+        seg_entries = scan_seg_entries(m, batch, n_cu);  // (a launch takes min(batch, m) rows: a list may repeat rows, m > n)
         o_u32 = round_up((2 * n + seg_entries) * (size_t)elem_bytes, (size_t)8);
         total = o_u32 + (n + m + seg_entries) * 4;
     }
