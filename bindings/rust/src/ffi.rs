@@ -359,6 +359,15 @@ extern "C" {
                                 d_counts: *mut u64, d_inertia: *mut f64, d_iterations: *mut u64, d_shift2: *mut f64,
                                 stream: *mut c_void) -> c_int;
     pub fn pn_kmeans_bounds_f32(index: *const pn_index, centres: *const f32, nc: usize, bounds_out: *mut f64) -> c_int;
+    /// greedy k-means++ seeding (include/petal_mi355x.h): trials 0 = 2 + floor(ln nc), at most 16; rows_out / d_rows nullable
+    pub fn pn_kmeans_init_f32(index: *const pn_index, nc: usize, trials: usize, seed: u64, flags: c_uint,
+                              centres_out: *mut f32, rows_out: *mut u64) -> c_int;
+    pub fn pn_kmeans_init_device_f32(index: *const pn_index, nc: usize, trials: usize, seed: u64, flags: c_uint,
+                                     d_centres: *mut f32, d_rows: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn pn_kmeans_init_f64(index: *const pn_index, nc: usize, trials: usize, seed: u64, flags: c_uint,
+                              centres_out: *mut f64, rows_out: *mut u64) -> c_int;
+    pub fn pn_kmeans_init_device_f64(index: *const pn_index, nc: usize, trials: usize, seed: u64, flags: c_uint,
+                                     d_centres: *mut f64, d_rows: *mut u64, stream: *mut c_void) -> c_int;
     /// silhouette values (include/petal_mi355x.h): rows (with n_rows = 0), a / b / nearest / score / n_scored / d_error nullable
     pub fn pn_silhouette_f32(index: *const pn_index, codes: *const i64, n_clusters: usize, rows: *const u64, n_rows: usize,
                              flags: c_uint, samples_out: *mut f64, a_out: *mut f64, b_out: *mut f64,

@@ -69,7 +69,7 @@ extern "C" {
  * pn_mean_shift_{,device_,merge_,merge_device_,labels_,labels_device_}{f32,f64}, PN_MS_*, PN_OPT_MS_PIECE;
  * pn_silhouette_{,device_}{f32,f64}; pn_nearest_foreign_{,device_}{f32,f64}, PN_OPT_FOREIGN_FILTER;
  * pn_kmeans_{,device_}{f32,f64}, pn_kmeans_assign_{,device_}{f32,f64}, pn_kmeans_bounds_f32,
- * PN_OPT_KMEANS_FILTER. */
+ * pn_kmeans_init_{,device_}{f32,f64}, PN_OPT_KMEANS_FILTER. */
 #define PN_ABI_VERSION 3
 
 /* ---- error codes.  EMPTY / NOT_CONTIGUOUS are ArrayError (src/lib.rs:9-16). */
@@ -1050,6 +1050,55 @@ int pn_kmeans_device_f64(const pn_index *index, const double *d_init_centres, si
  * (not finite, a squared norm of 2^100 or more).  Host pointers; 8 <= dim <= 320, else PN_ERR_UNSUPPORTED.  Tests check
  * the inequality pair by pair. */
 int pn_kmeans_bounds_f32(const pn_index *index, const float *centres, size_t nc, double *bounds_out);
+
+/* ---- k-means++ seeding (extension; Euclidean indexes only; T = the index's element type).  DESIGN.md 4.26.
+ * nc of the indexed rows as initial centres for pn_kmeans_*, chosen by greedy D^2 sampling (scikit-learn's
+ * kmeans_plusplus): every round after the first picks `trials` candidate rows from the current weights and keeps the one
+ * that lowers the potential most.  The result is a function of the rows, nc, trials and seed alone -- not of the device,
+ * the launch or the engine -- and the host and device entries give the same bits.  Every operation is IEEE, unfused, and
+ * there are no floating-point atomics.
+ *   trials     = the candidates per round, 1 .. 16; 1 is classic k-means++; 0 stands for min(2 + floor(ln nc), 16).
+ *                Below, L = trials.
+ *   Draws      u_j = (mix32(seed, j) >> 8) * 2^-24 as a float, j = 0, 1, ...: the stream of pn_fill_uniform_device_f32.
+ *                u_0 chooses the first centre, row floor((double)u_0 * (double)n).  Round t = 1 .. nc - 1 uses
+ *                u_(1 + (t - 1) L + c) for its candidate c = 0 .. L - 1.
+ *   Weights    m_i = the smallest distance from row i to the centres chosen so far -- the smallest by the distance key of
+ *                pn_kmeans_assign_* (a NaN above +inf), each distance the bits of pn_euclidean_*(centre, row).  The term
+ *                of row i is w_i = (double)m_i * (double)m_i, and a NaN term counts as 0.0.  For candidate row c of a
+ *                round, w_i^c is the same term of min(m_i, d(i, c)).
+ *   TREE256    the one sum shape, over the n terms in row order.  The rows are cut into blocks of 256; a block's sum is
+ *                the halving tree t[0:128] + t[128:256], then 64 + 64, ... down to 1, with 0.0 for a missing term.  256
+ *                consecutive block sums form a group, summed by the same tree (0.0 for a missing block).  The total is
+ *                ((G_0 + G_1) + G_2) ... in group order.
+ *   A pick     with the draw u from weights of total S: r = (double)u * S.  Walk the group sums with the sequential
+ *                prefix p_g = ((G_0 + G_1) + ...) + G_g and take the first group with p_g > r; carry r - p_(g-1) (p_(-1)
+ *                = 0.0) into that group's 256 block sums and walk them the same way; carry the remainder into that
+ *                block's 256 terms and walk them the same way: the row is found.  Where rounding leaves no prefix above
+ *                the carried value at a level, the last entry of that level that is not zero is taken (its prefix before
+ *                it carried on).
+ *   A round    picks its L candidates from the weights w (total: TREE256 of w); candidate c's potential is TREE256 of
+ *                w^c; the candidate with the smallest potential wins, by a strict '<' in trial order; then m_i becomes
+ *                min(m_i, d(i, winner)).  A row already chosen has weight zero and cannot be picked again.
+ *   A total that is not > 0 when a round is to pick means that the rows hold fewer distinct points than nc: the host
+ *   entries return PN_ERR_INVALID; the device entries cannot look, and then write NaN into every centre and 2^64 - 1 into
+ *   every row number.
+ * Outputs: centres_out [nc][dim], the chosen rows in the order chosen; rows_out [nc] (nullable), their numbers, counted
+ * from PN_OPT_INDEX_BASE as every row number this library returns.  flags must be 0.
+ * Argument errors, before any device is touched and in this order: unknown flags; trials > 16; centres_out NULL; nc == 0;
+ * NULL index; wrong element type: PN_ERR_INVALID; a Cosine index; nc > n (a chosen row can be chosen again only when its
+ * weight is zero); more than 2^31 - 1 rows: PN_ERR_UNSUPPORTED.
+ * Device entry points: everything in HBM, written in stream order on `stream`.  The call enqueues 2 nc launches -- a sweep
+ * of the corpus per round, a one-workgroup pick between two sweeps -- and returns; it never waits for the device.
+ * Workspace of a call: (1 + L) sizeof T bytes per row, 8 L bytes per block of 256 rows, L padded rows, 4 bytes per centre.
+ * pn_stats is not advanced.  Not in this version: Cosine indexes, row-sharded handles, k-means|| oversampling. */
+int pn_kmeans_init_f32(const pn_index *index, size_t nc, size_t trials, uint64_t seed, unsigned flags, float *centres_out,
+                       uint64_t *rows_out);
+int pn_kmeans_init_device_f32(const pn_index *index, size_t nc, size_t trials, uint64_t seed, unsigned flags,
+                              float *d_centres, uint64_t *d_rows, void *stream);
+int pn_kmeans_init_f64(const pn_index *index, size_t nc, size_t trials, uint64_t seed, unsigned flags, double *centres_out,
+                       uint64_t *rows_out);
+int pn_kmeans_init_device_f64(const pn_index *index, size_t nc, size_t trials, uint64_t seed, unsigned flags,
+                              double *d_centres, uint64_t *d_rows, void *stream);
 
 /* ---- silhouette values of a labelling (extension; Euclidean indexes only; T = the index's element type).  DESIGN.md 4.24.
  * codes [n]: one cluster code per indexed row.  A code in [0, n_clusters) makes the row a MEMBER of that cluster; a

@@ -695,6 +695,21 @@ class BallTree {
         res.n_iter = (size_t)iters;
         return res;
     }
+    // extension: greedy k-means++ seeding on the device (pn_kmeans_init_*): k of the indexed rows as initial centres for
+    // kmeans, a function of the rows, k, trials and seed alone.  trials: candidates per round, 1 .. 16 (1: classic
+    // k-means++; 0: 2 + floor(ln k), at most 16).  The chosen rows' numbers (with the index base) go to *rows when given.
+    std::vector<A> kmeans_init(size_t k, uint64_t seed = 0, size_t trials = 0, std::vector<uint64_t> *rows = nullptr) const {
+        std::vector<A> centres(k * dim_ + 1);
+        std::vector<uint64_t> chosen(k + 1);
+        if constexpr (kF32)
+            check(pn_kmeans_init_f32(h_, k, trials, seed, 0u, centres.data(), chosen.data()));
+        else
+            check(pn_kmeans_init_f64(h_, k, trials, seed, 0u, centres.data(), chosen.data()));
+        centres.resize(k * dim_);
+        chosen.resize(k);
+        if (rows) *rows = std::move(chosen);
+        return centres;
+    }
     // extension: silhouette values on the device (pn_silhouette_*).  codes [n]: a cluster code in [0, n_clusters) per
     // indexed row, negative = excluded; rows [n_rows] (nullptr, 0: every row): the rows to score, all members stay members
     Silhouette<A> silhouette(const int64_t *codes, size_t n_clusters, const uint64_t *rows = nullptr, size_t n_rows = 0) const {

@@ -997,16 +997,56 @@ class BallTree(Handle):
             chosen.append(min(i, self._n - 1))
         return rows[np.asarray(chosen)].copy()
 
-    def kmeans(self, centres_or_k, tol: float = 1e-4, max_iter: int = 300, seed=None, abs_tol=None, full: bool = False):
+    def _kinit_args(self, k, seed, trials):
+        self._euclidean_only("k-means")
+        k, seed, trials = int(k), int(seed), 0 if trials is None else int(trials)
+        if k < 1 or k > self._n:
+            raise ValueError("k must be between 1 and the number of rows")
+        if trials < 0 or trials > 16:
+            raise ValueError("trials must be between 1 and 16 (None: 2 + floor(ln k), at most 16)")
+        if seed < 0 or seed >= 2 ** 64:
+            raise ValueError("seed must fit 64 bits")
+        return k, seed, trials
+
+    def kmeans_init(self, k: int, seed=0, trials=None):
+        """Greedy k-means++ seeding on the device (``pn_kmeans_init_*``, scikit-learn's ``kmeans_plusplus``): ``(centres
+        [k][dim], rows uint64 [k])``, ``k`` of the indexed rows in the order chosen and their numbers.  Every round draws
+        ``trials`` candidates by D^2 sampling and keeps the one that lowers the potential most (``None``: ``2 + floor(ln
+        k)``, at most 16; ``1``: classic k-means++).  Bit-contractual: a function of the rows, ``k``, ``trials`` and
+        ``seed`` alone (the header states it), on host-built and ``from_device`` trees alike."""
+        k, seed, trials = self._kinit_args(k, seed, trials)
+        centres = np.empty((k, self._dim), dtype=self.dtype)
+        rows = np.empty(k, dtype=np.uint64)
+        check(self._fn("kmeans_init")(self._h, k, trials, seed, 0, centres.ctypes.data, rows.ctypes.data))
+        return centres, rows
+
+    def kmeans_init_device(self, k: int, seed=0, trials=None, out_centres=None, out_rows=None, stream=None):
+        """``kmeans_init`` in HBM: CUDA tensors ``(centres [k][dim], rows int64 [k])`` written in stream order on ``stream``
+        (default: the current torch stream); 2 k launches are enqueued and nothing waits for the device.  Fewer distinct
+        rows than ``k``: every centre is NaN and every row number -1."""
+        import torch
+        k, seed, trials = self._kinit_args(k, seed, trials)
+        centres, rows = self._outs((out_centres, (k, self._dim), self._tdt, k * self._dim), (out_rows, k, torch.int64, k))
+        check(self._fn("kmeans_init_device")(self._h, k, trials, seed, 0, centres.data_ptr(), rows.data_ptr(),
+                                             stream_arg(stream, self._dev)))
+        return centres, rows
+
+    def kmeans(self, centres_or_k, tol: float = 1e-4, max_iter: int = 300, seed=None, abs_tol=None, full: bool = False,
+               init: str = "torch"):
         """Lloyd's k-means from the given initial centres ``[k][dim]``, or from ``kmeans_plusplus(k, seed)`` when an integer
         is given: ``(centres [k][dim], labels int64 [n], inertia)``; with ``full=True`` also ``dist [n]``, ``counts uint64
         [k]``, ``iterations`` and ``shift2``.  ``tol`` is scikit-learn's: relative to the mean variance of the columns
         (computed on the host); ``abs_tol`` gives the absolute bound on the summed squared moves itself.  A cluster that
         loses every member keeps its centre (scikit-learn relocates it): look at ``counts``.  ``last_n_iter`` holds the
-        iterations run."""
+        iterations run.  ``init="device"`` seeds an integer ``centres_or_k`` with ``kmeans_init(k, seed or 0)`` instead:
+        the whole result is then a function of the rows and the arguments."""
         self._euclidean_only("k-means")
+        if init not in ("torch", "device"):
+            raise ValueError('init must be "torch" or "device"')
         abs_tol, max_iter = self._km_tol(tol, abs_tol, max_iter)
-        if np.ndim(centres_or_k) == 0:
+        if np.ndim(centres_or_k) == 0 and init == "device":
+            init = self.kmeans_init(int(centres_or_k), seed or 0)[0]
+        elif np.ndim(centres_or_k) == 0:
             init = self.kmeans_plusplus(int(centres_or_k), seed)
         else:
             init = self._centres(centres_or_k)

@@ -169,6 +169,9 @@ struct WorkspaceBufs {
     // thresholds, the list of unproven rows, distances, inertia segments), the update's scratch
     DevBuf w_km_rows, w_km_cent, w_km, w_km_upd;
     DevBuf w_sil;  // pn_silhouette_*: the scratch of silhouette.hip (sort, the two images, the spans' partials)
+    // pn_kmeans_init_*: the scratch of kmeans_init.hip (the rows' smallest distances, the round's distances per candidate,
+    // the block and group sums, the chosen rows, the candidates' image)
+    DevBuf w_kinit;
     DevBuf w_pcnt;                // shared thresholds: the segments' published fill counts [nseg][nq_pad]
 };
 static_assert(std::is_standard_layout<WorkspaceBufs>::value && sizeof(WorkspaceBufs) % sizeof(DevBuf) == 0,
@@ -5538,6 +5541,77 @@ extern "C" int pn_kmeans_bounds_f32(const pn_index *ix, const float *centres, si
 PN_KM_ENTRIES(f32, float)
 PN_KM_ENTRIES(f64, double)
 #undef PN_KM_ENTRIES
+
+// ---------------------------------------------------------------------------
+// k-means++ seeding: pn_kmeans_init_{,device_}{f32,f64} (the kernels and the contract: kmeans_init.hip).  Here: the
+// argument checks, the workspace and the one enqueue of 2 nc launches.  Nothing waits for the device but the host entry's
+// final copy, which brings the validation word along.
+// ---------------------------------------------------------------------------
+// (before any device is touched; the header states the order)
+static int kinit_args(const pn_index *ix, size_t nc, size_t trials, unsigned flags, const void *centres, int elem_bytes) {
+    if (flags) return fail(PN_ERR_INVALID, "unknown k-means seeding flags 0x%x", flags);
+    if (trials > (size_t)kKppMaxTrials) return fail(PN_ERR_INVALID, "trials must be at most %d (got %zu)", kKppMaxTrials, trials);
+    if (!centres) return fail(PN_ERR_INVALID, "centres_out is NULL");
+    if (nc == 0) return fail(PN_ERR_INVALID, "k-means seeding needs at least one centre");
+    if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
+    if (ix->elem_bytes != elem_bytes) return fail(PN_ERR_INVALID, "index element type mismatch");
+    if (ix->metric != 0) return fail(PN_ERR_UNSUPPORTED, "k-means seeding needs a Euclidean index");
+    if (nc > ix->n) return fail(PN_ERR_UNSUPPORTED, "more centres (%zu) than indexed rows (%zu)", nc, ix->n);
+    if (ix->n > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many rows");
+    return PN_OK;
+}
+// trials == 0: scikit-learn's 2 + floor(ln nc), at most kKppMaxTrials
+static int kinit_trials(size_t nc, size_t trials) {
+    if (trials) return (int)trials;
+    const size_t t = 2 + (size_t)std::floor(std::log((double)nc));
+    return (int)(t < (size_t)kKppMaxTrials ? t : (size_t)kKppMaxTrials);
+}
+// in a held workspace, on stream s; the outputs in HBM (d_rows, d_err nullable)
+template <typename T>
+static int kinit_run(const pn_index *ix, Workspace &ws, size_t nc, size_t trials, uint64_t seed, T *d_centres, uint64_t *d_rows,
+                     int32_t *d_err, hipStream_t s) {
+    KppArgs a;
+    a.X = ix->d_pts, a.n = ix->n, a.ld = ix->ld, a.dim = (int)ix->dim;
+    a.nc = nc, a.trials = kinit_trials(nc, trials), a.seed = seed, a.index_base = ix->index_base;
+    PNCHK(ws.w_kinit.ensure(kpp_buffer_bytes(a.n, a.ld, nc, a.trials, (int)sizeof(T))));
+    a.buf = ws.w_kinit.p, a.centres = d_centres, a.rows = d_rows, a.err = d_err;
+    HIPCHK(kpp_enqueue<T>(a, s));
+    return PN_OK;
+}
+template <typename T>
+static int kinit_device(const pn_index *ix, size_t nc, size_t trials, uint64_t seed, unsigned flags, T *d_centres,
+                        uint64_t *d_rows, hipStream_t s) {
+    PNCHK(kinit_args(ix, nc, trials, flags, d_centres, (int)sizeof(T)));
+    CallScope call(ix);
+    PNCHK(call.on_stream(s));
+    return kinit_run<T>(ix, call.ws(), nc, trials, seed, d_centres, d_rows, nullptr, s);
+}
+template <typename T>
+static int kinit_host(const pn_index *ix, size_t nc, size_t trials, uint64_t seed, unsigned flags, T *centres, uint64_t *rows) {
+    PNCHK(kinit_args(ix, nc, trials, flags, centres, (int)sizeof(T)));
+    CallScope call(ix);
+    PNCHK(call.own_stream());
+    int32_t err[2] = {0, 0};
+    HostIo io(call);
+    const auto [d_centres, d_rows, d_err] = std::tuple{io.out(centres, nc * ix->dim), io.out(rows, nc), io.out(err, 2)};
+    PNCHK(io.up());
+    PNCHK(kinit_run<T>(ix, call.ws(), nc, trials, seed, io[d_centres], rows ? io[d_rows] : nullptr, io[d_err], call.s()));
+    PNCHK(io.down());
+    if (err[0]) return fail(PN_ERR_INVALID, "the index holds fewer distinct rows than the %zu centres asked for", nc);
+    return PN_OK;
+}
+#define PN_KINIT_ENTRIES(SFX, T)                                                                                              \
+    extern "C" int pn_kmeans_init_##SFX(const pn_index *ix, size_t nc, size_t trials, uint64_t seed, unsigned flags,          \
+                                        T *centres_out, uint64_t *rows_out) {                                                 \
+        return kinit_host<T>(ix, nc, trials, seed, flags, centres_out, rows_out);                                             \
+    }                                                                                                                         \
+    extern "C" int pn_kmeans_init_device_##SFX(const pn_index *ix, size_t nc, size_t trials, uint64_t seed, unsigned flags,   \
+                                               T *d_centres, uint64_t *d_rows, void *stream) {                                \
+        return kinit_device<T>(ix, nc, trials, seed, flags, d_centres, d_rows, (hipStream_t)stream);                          \
+    }
+PN_KINIT_ENTRIES(f32, float)
+PN_KINIT_ENTRIES(f64, double)
+#undef PN_KINIT_ENTRIES
 
 // ---------------------------------------------------------------------------
 // Silhouette values: pn_silhouette_{,device_}{f32,f64} (the kernels and the shape of the sums: silhouette.hip).  Here: the

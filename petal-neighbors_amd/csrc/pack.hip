@@ -39,14 +39,7 @@ template hipError_t launch_pack_rows<double>(const double *, size_t, size_t, siz
 // ---------------------------------------------------------------------------
 // counter-based generator shared (by restatement) with oracle_fill_uniform_f32
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t mix32(uint64_t seed, uint64_t ctr) {
-    uint64_t z = seed * 0x9E3779B97F4A7C15ull + ctr;
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z = z ^ (z >> 31);
-    return (uint32_t)(z >> 32);
-}
+// (mix32: pn_internal.h)
 __global__ void fill_uniform_kernel(float *__restrict__ out, uint64_t count, uint64_t seed, uint64_t first) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count;
          i += (uint64_t)gridDim.x * blockDim.x)

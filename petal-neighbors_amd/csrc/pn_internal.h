@@ -76,6 +76,17 @@ struct CandBuf {
 
 inline size_t round_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 
+// ---- the counter-based generator shared (by restatement) with oracle_fill_uniform_f32: draw j of a seed is
+// (mix32(seed, j) >> 8) * 2^-24 (pack.hip: pn_fill_uniform_device_f32; kmeans_init.hip: the draws of the seeding)
+__host__ __device__ __forceinline__ uint32_t mix32(uint64_t seed, uint64_t ctr) {
+    uint64_t z = seed * 0x9E3779B97F4A7C15ull + ctr;
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z = z ^ (z >> 31);
+    return (uint32_t)(z >> 32);
+}
+
 // ---- exact_scan.hip
 // lo_key/lo_idx (nullable, [nq_pad]): only entries strictly after (lo_key[q], lo_idx[q]) take part
 // nq_dev (nullable) / nq_off: device-driven query count -- only the first min(nq, max(*nq_dev - nq_off, 0)) queries
@@ -465,6 +476,26 @@ size_t sil_span_len(size_t n);
 size_t sil_buffer_bytes(size_t n, size_t m, int dim, int elem_bytes);
 template <typename T>
 hipError_t sil_enqueue(const SilArgs &a, hipStream_t s);
+
+// ---- kmeans_init.hip: greedy k-means++ seeding (pn_kmeans_init_*); nothing in it waits for the device.  2 nc launches: a
+// sweep per round (every row against the round's candidates) and a one-workgroup pick between them, the last of which
+// gathers the chosen rows.  buf: kpp_buffer_bytes() bytes, 16-byte aligned.  1 <= nc <= n <= 2^31 - 1, 1 <= trials <= 16.
+constexpr int kKppMaxTrials = 16;
+struct KppArgs {
+    const void *X = nullptr;  // the index's rows [n_pad][ld] of T (n_pad a multiple of kRowPad, ld of kRowAlign)
+    size_t n = 0, ld = 0;
+    int dim = 0;
+    size_t nc = 0;
+    int trials = 1;
+    uint64_t seed = 0, index_base = 0;
+    void *buf = nullptr;
+    void *centres = nullptr;   // [nc][dim] of T
+    uint64_t *rows = nullptr;  // [nc], nullable
+    int32_t *err = nullptr;    // [1], nullable: PN_OK, or PN_ERR_INVALID (fewer distinct rows than centres)
+};
+size_t kpp_buffer_bytes(size_t n, size_t ld, size_t nc, int trials, int elem_bytes);
+template <typename T>
+hipError_t kpp_enqueue(const KppArgs &a, hipStream_t s);
 
 // ---- mst.hip, for mean_shift.hip, kmeans.hip and silhouette.hip: the bitonic network over (key, pair), ascending by key then pair.  N =
 // sort_key_pair_len(count): count padded to a power of two, at least the block one workgroup sorts in LDS; the caller pads
