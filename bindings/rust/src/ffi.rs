@@ -359,6 +359,15 @@ extern "C" {
                                 d_counts: *mut u64, d_inertia: *mut f64, d_iterations: *mut u64, d_shift2: *mut f64,
                                 stream: *mut c_void) -> c_int;
     pub fn pn_kmeans_bounds_f32(index: *const pn_index, centres: *const f32, nc: usize, bounds_out: *mut f64) -> c_int;
+    /// the m nearest centres of every row (include/petal_mi355x.h): labels / dist [n][m], 1 <= m <= 8, dist nullable
+    pub fn pn_kmeans_nearest_f32(index: *const pn_index, centres: *const f32, nc: usize, m: usize, flags: c_uint,
+                                 labels_out: *mut i64, dist_out: *mut f32) -> c_int;
+    pub fn pn_kmeans_nearest_device_f32(index: *const pn_index, d_centres: *const f32, nc: usize, m: usize, flags: c_uint,
+                                        d_labels: *mut i64, d_dist: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn pn_kmeans_nearest_f64(index: *const pn_index, centres: *const f64, nc: usize, m: usize, flags: c_uint,
+                                 labels_out: *mut i64, dist_out: *mut f64) -> c_int;
+    pub fn pn_kmeans_nearest_device_f64(index: *const pn_index, d_centres: *const f64, nc: usize, m: usize, flags: c_uint,
+                                        d_labels: *mut i64, d_dist: *mut f64, stream: *mut c_void) -> c_int;
     /// greedy k-means++ seeding (include/petal_mi355x.h): trials 0 = 2 + floor(ln nc), at most 16; rows_out / d_rows nullable
     pub fn pn_kmeans_init_f32(index: *const pn_index, nc: usize, trials: usize, seed: u64, flags: c_uint,
                               centres_out: *mut f32, rows_out: *mut u64) -> c_int;

@@ -70,6 +70,7 @@ extern "C" {
  * pn_silhouette_{,device_}{f32,f64}; pn_nearest_foreign_{,device_}{f32,f64}, PN_OPT_FOREIGN_FILTER;
  * pn_kmeans_{,device_}{f32,f64}, pn_kmeans_assign_{,device_}{f32,f64}, pn_kmeans_bounds_f32,
  * pn_kmeans_init_{,device_}{f32,f64}, PN_OPT_KMEANS_FILTER. */
+/* Further additions of version 3: pn_kmeans_nearest_{,device_}{f32,f64}, PN_KMEANS_NEAREST_MAX. */
 #define PN_ABI_VERSION 3
 
 /* ---- error codes.  EMPTY / NOT_CONTIGUOUS are ArrayError (src/lib.rs:9-16). */
@@ -1050,6 +1051,40 @@ int pn_kmeans_device_f64(const pn_index *index, const double *d_init_centres, si
  * (not finite, a squared norm of 2^100 or more).  Host pointers; 8 <= dim <= 320, else PN_ERR_UNSUPPORTED.  Tests check
  * the inequality pair by pair. */
 int pn_kmeans_bounds_f32(const pn_index *index, const float *centres, size_t nc, double *bounds_out);
+
+/* ---- the m nearest centres of every indexed row (extension; Euclidean indexes only; T = the index's element type).
+ * DESIGN.md 4.27.  For multi-probe lists and spill assignment, the second-nearest centre of Hamerly / Elkan bounds and of
+ * the simplified silhouette, soft assignments over the few nearest centres, a sparse KMeans.transform.
+ *   labels_out [n][m], dist_out [n][m] (nullable): for row i, slot j holds the centre that is j-th by (distance key, centre
+ *     number), ascending -- the very order of pn_kmeans_assign_* / pn_mean_shift_labels_*: the distance is the bits of
+ *     pn_euclidean_*(centre, row), its key those bits read as an unsigned integer, a NaN distance the canonical NaN key
+ *     above +inf, and of two equal keys the lower centre number comes first.  Slots j >= nc hold label -1 and NaN.
+ *     Column 0 equals pn_kmeans_assign_*'s labels and distances bit for bit, for every input.
+ *   1 <= m <= PN_KMEANS_NEAREST_MAX = 8; flags must be 0.  PN_OPT_INDEX_BASE affects no output.
+ * Engines (results never depend on them): those of pn_kmeans_assign_*, chosen by the same rule (PN_OPT_ENGINE,
+ * PN_OPT_KMEANS_FILTER, 8 <= dim <= 320, the same line under PN_ENGINE_AUTO -- drawn for m = 1) with one more condition:
+ * nc > m.  With nc <= m there is nothing to filter and the exact kernel is the whole engine, whatever is forced.  The
+ * filter keeps the m smallest bf16 keys of a row and the (m + 1)-th as the threshold; a row is proven when no centre
+ * outside its m candidates can tie or beat the m-th of them, the others (ties between the m-th and the (m + 1)-th,
+ * rows within the filter's slack of that gap, anything not finite or with a squared norm of 2^100 or more) are listed on
+ * the device and answered by the exact kernel.  pn_stats.queries advances by n, pn_stats.fallback_queries by the rows
+ * the filter listed.
+ * Argument errors, before any device is touched and in this order: unknown flags; m == 0 or m > 8; labels NULL; centres
+ * NULL with nc > 0; NULL index; wrong element type: PN_ERR_INVALID; a Cosine index: PN_ERR_UNSUPPORTED; more than
+ * 2^31 - 1 rows or centres: PN_ERR_UNSUPPORTED.  n == 0 succeeds and writes nothing.
+ * Device entry points: everything in HBM, written in stream order on `stream`; pn_kmeans_nearest_device_* never waits.
+ * Device memory of a call (workspace of the handle): none per row on the exact path; the filter adds 4 * dp + 28 + 4 M
+ * bytes per row (M = m rounded up to 2, 4 or 8: the candidates) and 4 * dp + 4 bytes per centre rounded up to 32.
+ * Not in this version: Cosine indexes, row-sharded handles, m > 8. */
+#define PN_KMEANS_NEAREST_MAX 8
+int pn_kmeans_nearest_f32(const pn_index *index, const float *centres, size_t nc, size_t m, unsigned flags,
+                          int64_t *labels_out, float *dist_out);
+int pn_kmeans_nearest_device_f32(const pn_index *index, const float *d_centres, size_t nc, size_t m, unsigned flags,
+                                 int64_t *d_labels, float *d_dist, void *stream);
+int pn_kmeans_nearest_f64(const pn_index *index, const double *centres, size_t nc, size_t m, unsigned flags,
+                          int64_t *labels_out, double *dist_out);
+int pn_kmeans_nearest_device_f64(const pn_index *index, const double *d_centres, size_t nc, size_t m, unsigned flags,
+                                 int64_t *d_labels, double *d_dist, void *stream);
 
 /* ---- k-means++ seeding (extension; Euclidean indexes only; T = the index's element type).  DESIGN.md 4.26.
  * nc of the indexed rows as initial centres for pn_kmeans_*, chosen by greedy D^2 sampling (scikit-learn's

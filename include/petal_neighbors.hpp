@@ -673,6 +673,21 @@ class BallTree {
         res.dist.resize(n_);
         return res;
     }
+    // ... the m nearest of k centres for every indexed row (pn_kmeans_nearest_*, 1 <= m <= 8): labels and dist [n][m], slot
+    // j the centre that is j-th by (distance, centre number), -1 and NaN beyond k; column 0 is kmeans_assign's answer
+    KMeans<A> kmeans_nearest(const A *centres, size_t k, size_t m) const {
+        KMeans<A> res;
+        res.centres.assign(centres, centres + k * dim_);
+        res.labels.resize(n_ * m + 1);
+        res.dist.resize(n_ * m + 1);
+        if constexpr (kF32)
+            check(pn_kmeans_nearest_f32(h_, centres, k, m, 0u, res.labels.data(), res.dist.data()));
+        else
+            check(pn_kmeans_nearest_f64(h_, centres, k, m, 0u, res.labels.data(), res.dist.data()));
+        res.labels.resize(n_ * m);
+        res.dist.resize(n_ * m);
+        return res;
+    }
     // ... Lloyd iterations from the initial centres [k][dim] until the summed squared moves are <= tol (absolute) or
     // max_iter; a cluster without members keeps its centre
     KMeans<A> kmeans(const A *init, size_t k, double tol, size_t max_iter = 300) const {

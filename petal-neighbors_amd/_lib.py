@@ -29,6 +29,7 @@ PN_OPT_KDE_PIECE = 14
 PN_OPT_MS_PIECE = 15
 PN_OPT_KMEANS_FILTER = 16
 PN_OPT_FOREIGN_FILTER = 17
+PN_KMEANS_NEAREST_MAX = 8
 PN_KDE_GAUSSIAN, PN_KDE_TOPHAT, PN_KDE_EPANECHNIKOV, PN_KDE_EXPONENTIAL, PN_KDE_LINEAR = 0, 1, 2, 3, 4
 PN_RADIUS_SORTED = 1
 PN_SELF_INCLUDE = 2
@@ -124,6 +125,8 @@ PAIRED = {
     "pn_mean_shift_labels_device": (_i, [_vp, _vp, _sz, _R, _cu, _vp, _vp]),
     "pn_kmeans_assign": (_i, [_vp, _vp, _sz, _cu] + [_vp] * 3),
     "pn_kmeans_assign_device": (_i, [_vp, _vp, _sz, _cu] + [_vp] * 4),
+    "pn_kmeans_nearest": (_i, [_vp, _vp, _sz, _sz, _cu, _vp, _vp]),
+    "pn_kmeans_nearest_device": (_i, [_vp, _vp, _sz, _sz, _cu, _vp, _vp, _vp]),
     "pn_kmeans": (_i, [_vp, _vp, _sz, _d, _sz, _cu] + [_vp] * 7),
     "pn_kmeans_device": (_i, [_vp, _vp, _sz, _d, _sz, _cu] + [_vp] * 8),
     "pn_kmeans_init": (_i, [_vp, _sz, _sz, _u64, _cu, _vp, _vp]),

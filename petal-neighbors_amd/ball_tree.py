@@ -946,6 +946,38 @@ class BallTree(Handle):
                                                stream_arg(stream, self._dev)))
         return labels, dist, inertia
 
+    def _nearest_m(self, m):
+        m = int(m)
+        if not 1 <= m <= _lib.PN_KMEANS_NEAREST_MAX:
+            raise ValueError(f"m must be between 1 and {_lib.PN_KMEANS_NEAREST_MAX}")
+        return m
+
+    def kmeans_nearest(self, centres, m: int):
+        """The ``m`` nearest centres of every indexed row (1 <= m <= 8): ``(labels int64 [n, m], dist [n, m])``, slot j the
+        centre that is j-th by (distance, centre number); column 0 is ``kmeans_assign``'s answer.  Slots beyond the
+        number of centres hold -1 and NaN."""
+        self._euclidean_only("k-means")
+        c = self._centres(centres)
+        m = self._nearest_m(m)
+        labels = np.empty((self._n, m), dtype=np.int64)
+        dist = np.empty((self._n, m), dtype=self.dtype)
+        check(self._fn("kmeans_nearest")(self._h, c.ctypes.data if c.shape[0] else None, c.shape[0], m, 0,
+                                         labels.ctypes.data, dist.ctypes.data))
+        return labels, dist
+
+    def kmeans_nearest_device(self, centres, m: int, out_labels=None, out_dist=None, stream=None):
+        """``kmeans_nearest`` in HBM: ``centres`` a contiguous 2-D CUDA tensor; returns CUDA tensors ``(labels int64
+        [n, m], dist [n, m])``.  Never waits."""
+        import torch
+        self._euclidean_only("k-means")
+        centres, nc, ptr = self._centres_device(centres)
+        m = self._nearest_m(m)
+        labels, dist = self._outs((out_labels, (self._n, m), torch.int64, self._n * m),
+                                  (out_dist, (self._n, m), self._tdt, self._n * m))
+        check(self._fn("kmeans_nearest_device")(self._h, ptr, nc, m, 0, labels.data_ptr(), dist.data_ptr(),
+                                                stream_arg(stream, self._dev)))
+        return labels, dist
+
     def _km_tol(self, tol, abs_tol, max_iter):
         if int(max_iter) < 1:
             raise ValueError("max_iter must be at least 1")

@@ -5543,6 +5543,93 @@ PN_KM_ENTRIES(f64, double)
 #undef PN_KM_ENTRIES
 
 // ---------------------------------------------------------------------------
+// The m nearest centres of every row: pn_kmeans_nearest_{,device_}{f32,f64} (the kernels: kmeans_nearest.hip).  The chain
+// of an assignment with lists in the place of the one candidate: [pack the rows] pack the centres -> filter -> re-rank
+// and proof -> the exact kernel over the listed rows; the exact kernel alone where km_use_filter says so, and wherever
+// nc <= m: there is nothing to filter.  Nothing of it waits for the device.
+// ---------------------------------------------------------------------------
+// (before any device is touched; the header states the order)
+static int kn_args(const pn_index *ix, unsigned flags, size_t m, const void *labels, const void *centres, size_t nc,
+                   int elem_bytes) {
+    if (flags) return fail(PN_ERR_INVALID, "unknown k-means flags 0x%x", flags);
+    if (m < 1 || m > (size_t)PN_KMEANS_NEAREST_MAX)
+        return fail(PN_ERR_INVALID, "m must be between 1 and %d (got %zu)", PN_KMEANS_NEAREST_MAX, m);
+    if (!labels) return fail(PN_ERR_INVALID, "labels is NULL");
+    if (nc && !centres) return fail(PN_ERR_INVALID, "centres is NULL");
+    if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
+    if (ix->elem_bytes != elem_bytes) return fail(PN_ERR_INVALID, "index element type mismatch");
+    if (ix->metric != 0) return fail(PN_ERR_UNSUPPORTED, "k-means needs a Euclidean index");
+    if (ix->n > 0x7FFFFFFFull || nc > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many rows or centres");
+    return PN_OK;
+}
+// One call, in a held workspace on stream s; n >= 1.  d_labels, d_dist [n][m], d_dist nullable.
+template <typename T>
+static int kn_enqueue(const pn_index *ix, Workspace &ws, const T *d_centres, size_t nc, size_t m, int64_t *d_labels,
+                      T *d_dist, hipStream_t s) {
+    const size_t n = ix->n;
+    const int dim = (int)ix->dim;
+    const T *X = (const T *)ix->d_pts;
+    if (km_use_filter(ix, nc) && nc > m) {
+        KmRowImage rows;
+        PNCHK(km_pack_rows<T>(ix, ws, &rows, s));
+        // w_km: nsel (8 bytes) | cand [n][M] u32 | tau [n] f32 | sel [n] u32
+        const size_t n2 = round_up(n, (size_t)2), width = (size_t)km_nearest_width(m);
+        PNCHK(ws.w_km.ensure(8 + n2 * 4 * (width + 2)));
+        uint32_t *nsel = (uint32_t *)ws.w_km.p, *cand = nsel + 2, *sel = cand + n2 * (width + 1);
+        float *tau = (float *)(cand + n2 * width);
+        PNCHK(ws.w_km_cent.ensure(km_centre_image_bytes(nc, dim)));
+        const KmCentreImage ci = km_centre_image_at(ws.w_km_cent.p, nc, dim);
+        HIPCHK(launch_km_pack_centres<T>(d_centres, nc, dim, ci, s));
+        HIPCHK(launch_km_nearest_filter(rows, n, ci, nc, (int)m, cand, tau, s));
+        HIPCHK(hipMemsetAsync(nsel, 0, sizeof(uint32_t), s));
+        HIPCHK(launch_km_nearest_rerank<T>(X, n, ix->ld, dim, d_centres, nc, (int)m, cand, tau, rows, ci, sel, nsel, d_labels,
+                                           d_dist, s));
+        HIPCHK(launch_km_nearest_exact<T>(X, n, ix->ld, dim, d_centres, nc, (int)m, sel, nsel, d_labels, d_dist, s));
+        if (ix->d_stats) HIPCHK(launch_radii_add_listed(nsel, ix->d_stats, s));
+    } else {
+        HIPCHK(launch_km_nearest_exact<T>(X, n, ix->ld, dim, d_centres, nc, (int)m, nullptr, nullptr, d_labels, d_dist, s));
+    }
+    std::lock_guard<std::mutex> lk(ix->sh.mu);
+    ix->sh.stats.queries += n;
+    return PN_OK;
+}
+template <typename T>
+static int kn_device(const pn_index *ix, const T *d_centres, size_t nc, size_t m, unsigned flags, int64_t *d_labels, T *d_dist,
+                     hipStream_t s) {
+    PNCHK(kn_args(ix, flags, m, d_labels, d_centres, nc, (int)sizeof(T)));
+    if (ix->n == 0) return PN_OK;
+    CallScope call(ix);
+    PNCHK(call.guard());
+    PNCHK(call.on_stream(s));
+    return kn_enqueue<T>(ix, call.ws(), d_centres, nc, m, d_labels, d_dist, s);
+}
+template <typename T>
+static int kn_host(const pn_index *ix, const T *centres, size_t nc, size_t m, unsigned flags, int64_t *labels, T *dist) {
+    PNCHK(kn_args(ix, flags, m, labels, centres, nc, (int)sizeof(T)));
+    if (ix->n == 0) return PN_OK;
+    CallScope call(ix);
+    PNCHK(call.own_stream());
+    HostIo io(call);
+    const auto [d_centres, d_labels, d_dist] =
+        std::tuple{io.in(centres, nc * ix->dim), io.out(labels, ix->n * m), io.out(dist, dist ? ix->n * m : 0)};
+    PNCHK(io.up());
+    PNCHK(kn_enqueue<T>(ix, call.ws(), io[d_centres], nc, m, io[d_labels], dist ? io[d_dist] : nullptr, call.s()));
+    return io.down();
+}
+#define PN_KN_ENTRIES(SFX, T)                                                                                                 \
+    extern "C" int pn_kmeans_nearest_##SFX(const pn_index *ix, const T *centres, size_t nc, size_t m, unsigned flags,         \
+                                           int64_t *labels_out, T *dist_out) {                                                \
+        return kn_host<T>(ix, centres, nc, m, flags, labels_out, dist_out);                                                   \
+    }                                                                                                                         \
+    extern "C" int pn_kmeans_nearest_device_##SFX(const pn_index *ix, const T *d_centres, size_t nc, size_t m, unsigned flags, \
+                                                  int64_t *d_labels, T *d_dist, void *stream) {                               \
+        return kn_device<T>(ix, d_centres, nc, m, flags, d_labels, d_dist, (hipStream_t)stream);                              \
+    }
+PN_KN_ENTRIES(f32, float)
+PN_KN_ENTRIES(f64, double)
+#undef PN_KN_ENTRIES
+
+// ---------------------------------------------------------------------------
 // k-means++ seeding: pn_kmeans_init_{,device_}{f32,f64} (the kernels and the contract: kmeans_init.hip).  Here: the
 // argument checks, the workspace and the one enqueue of 2 nc launches.  Nothing waits for the device but the host entry's
 // final copy, which brings the validation word along.

@@ -453,6 +453,25 @@ template <typename T>
 hipError_t km_update_enqueue(const T *X, size_t n, size_t ld, int dim, const int64_t *labels, size_t nc, void *buf,
                              T *centres, uint64_t *counts, double tol, int last, double **stop_out, hipStream_t s);
 
+// ---- kmeans_nearest.hip: the m nearest centres of every row (pn_kmeans_nearest_*), 1 <= m <= 8, on the images and the
+// bound of kmeans.hip; nothing in it waits for the device.  The kernels carry lists of km_nearest_width(m) = 2, 4 or 8.
+int km_nearest_width(size_t m);
+// cand [n][km_nearest_width(m)] <- the centres of each row's smallest keys, ascending by key (0xFFFFFFFF: an empty slot);
+// tau [n] <- the (m + 1)-th smallest key (+inf: there is none)
+hipError_t launch_km_nearest_filter(const KmRowImage &r, size_t n, const KmCentreImage &c, size_t nc, int m, uint32_t *cand,
+                                    float *tau, hipStream_t s);
+// each row's first m candidates in the reference's fold, ordered by (key, number); proven rows get labels and dist [n][m]
+// (dist nullable), the others are listed: sel[0 .. *nsel) in any order (nsel zeroed by the caller, sel [n])
+template <typename T>
+hipError_t launch_km_nearest_rerank(const T *X, size_t n, size_t ld, int dim, const T *centres, size_t nc, int m,
+                                    const uint32_t *cand, const float *tau, const KmRowImage &r, const KmCentreImage &c,
+                                    uint32_t *sel, uint32_t *nsel, int64_t *labels, T *dist, hipStream_t s);
+// every row (sel == nullptr) or the listed rows against every centre: labels and dist [n][m] by (key, number); slots at
+// and beyond nc: -1 and NaN
+template <typename T>
+hipError_t launch_km_nearest_exact(const T *X, size_t n, size_t ld, int dim, const T *centres, size_t nc, int m,
+                                   const uint32_t *sel, const uint32_t *nsel, int64_t *labels, T *dist, hipStream_t s);
+
 // ---- silhouette.hip: silhouette values of a labelling of the indexed rows (pn_silhouette_*); nothing in it waits for the
 // device.  codes [n] int64 (negative: excluded), rows [m] (nullable: the m = n indexed rows in order); samples [m] and,
 // nullable, a / b / nearest [m], score / n_scored / err [1], all in HBM.  buf: sil_buffer_bytes() bytes, 16-byte aligned.

@@ -14,6 +14,8 @@ three MFMAs per step issue and for the 2 n nc dim FLOP of the products themselve
 reaches, which also packs the rows, re-ranks and answers the listed rows.
 --line adds the sweep the planner's line was drawn from: nc = 4 .. 128 at every shape given with nc = 64, exact against
 forced filter.
+--nearest measures pn_kmeans_nearest_device_f32 instead (measure_nearest; default shapes 10^6 x 128 with 1024 and 4096
+centres) and appends its line to profiles/kmeans_nearest_bench.jsonl.
 Appends one JSON line to profiles/kmeans_bench.jsonl (--out).
 usage: python tools/bench_kmeans.py [--reps 5] [--shapes 100000x16x64,1000000x128x64,1000000x128x1024,1000000x128x4096]"""
 import argparse
@@ -49,8 +51,8 @@ def med(v):
     return round(float(np.median(v)), 3)
 
 
-def filter_kernel_ms(run):
-    """mean device time of km_assign_filter_kernel over three calls of run(), or None where the trace has no such kernel"""
+def filter_kernel_ms(run, name="km_assign_filter_kernel"):
+    """mean device time of the kernel `name` over three calls of run(), or None where the trace has no such kernel"""
     try:
         from torch.profiler import ProfilerActivity, profile
         with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
@@ -58,7 +60,7 @@ def filter_kernel_ms(run):
                 run()
             torch.cuda.synchronize()
         for e in prof.key_averages():
-            if "km_assign_filter_kernel" in e.key and e.count:
+            if name in e.key and e.count:
                 total = getattr(e, "device_time_total", None) or getattr(e, "cuda_time_total", 0.0)
                 if total:
                     return total / e.count * 1e-3
@@ -123,14 +125,67 @@ def measure(x, tree, nc, reps, iteration=True):
     return rec
 
 
+def measure_nearest(x, tree, nc, reps):
+    """--nearest: pn_kmeans_nearest_device_f32 for m = 1, 2, 4, 8 (labels alone) under PN_ENGINE_AUTO, PN_ENGINE_EXACT and
+    with the filter forced, against torch.cdist(x, centres).topk(m, largest=False) -- the one route a caller had -- and,
+    for m = 1, pn_kmeans_assign_device_f32; the rows the forced filter listed; km_nearest_filter_kernel's own time."""
+    n, dim = x.shape
+    init = x[:: max(1, n // nc)][:nc].contiguous()
+    st = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    rec = {"n": n, "dim": dim, "nc": nc}
+    one_label = torch.empty(n, dtype=torch.int64, device=x.device)
+    for m in (1, 2, 4, 8):
+        labels = torch.empty((n, m), dtype=torch.int64, device=x.device)
+
+        def near(mode):
+            def run():
+                tree.set_option(_lib.PN_OPT_KMEANS_FILTER, 1 if mode == "forced" else 0)
+                tree.set_engine("exact" if mode == "exact" else "auto")
+                check(_lib.lib().pn_kmeans_nearest_device_f32(tree._h, init.data_ptr(), nc, m, 0, labels.data_ptr(), None, st))
+            return run
+
+        def cdist_topk():
+            torch.cdist(x, init).topk(m, largest=False)
+
+        def assign():
+            tree.set_option(_lib.PN_OPT_KMEANS_FILTER, 0)
+            tree.set_engine("auto")
+            check(_lib.lib().pn_kmeans_assign_device_f32(tree._h, init.data_ptr(), nc, 0, one_label.data_ptr(), None, None, st))
+
+        times = interleaved([near("auto"), near("exact"), near("forced"), cdist_topk] + ([assign] if m == 1 else []), reps)
+        near("exact")()
+        want = labels.clone()
+        before = tree.stats()["fallback_queries"]
+        near("forced")()
+        torch.cuda.synchronize()
+        listed = tree.stats()["fallback_queries"] - before
+        assert torch.equal(labels, want)
+        t_k = filter_kernel_ms(near("forced"), "km_nearest_filter_kernel")
+        r = {"auto_ms": med(times[0]), "exact_ms": med(times[1]), "forced_ms": med(times[2]), "cdist_topk_ms": med(times[3]),
+             "listed_rows": int(listed), "listed_rate": round(listed / n, 6),
+             "filter_kernel_ms": round(t_k, 3) if t_k else None}
+        if m == 1:
+            r["assign_auto_ms"] = med(times[4])
+        rec[f"m{m}"] = r
+    tree.set_option(_lib.PN_OPT_KMEANS_FILTER, 0)
+    tree.set_engine("auto")
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--shapes", default="100000x16x64,1000000x128x64,1000000x128x1024,1000000x128x4096")
+    ap.add_argument("--shapes", default=None)
     ap.add_argument("--line", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "kmeans_bench.jsonl"))
+    ap.add_argument("--nearest", action="store_true")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    res = {"tool": "bench_kmeans"}
+    if args.shapes is None:
+        args.shapes = ("1000000x128x1024,1000000x128x4096" if args.nearest
+                       else "100000x16x64,1000000x128x64,1000000x128x1024,1000000x128x4096")
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "kmeans_nearest_bench.jsonl" if args.nearest else "kmeans_bench.jsonl")
+    res = {"tool": "bench_kmeans --nearest" if args.nearest else "bench_kmeans"}
     cache = {}
     for i, shape in enumerate(args.shapes.split(",")):
         n, dim, nc = (int(v) for v in shape.split("x"))
@@ -140,6 +195,10 @@ def main():
             x = blob_rows(n, dim, 1024, 0.05, 0.10, 3)
             cache[(n, dim)] = (x, pn.BallTree.from_device(x))
         x, tree = cache[(n, dim)]
+        if args.nearest:
+            res[shape] = measure_nearest(x, tree, nc, args.reps)
+            print(shape, json.dumps(res[shape]), flush=True)
+            continue
         res[shape] = measure(x, tree, nc, args.reps)
         print(shape, json.dumps(res[shape]), flush=True)
         if args.line and nc == 64:
