@@ -70,7 +70,8 @@ extern "C" {
  * pn_silhouette_{,device_}{f32,f64}; pn_nearest_foreign_{,device_}{f32,f64}, PN_OPT_FOREIGN_FILTER;
  * pn_kmeans_{,device_}{f32,f64}, pn_kmeans_assign_{,device_}{f32,f64}, pn_kmeans_bounds_f32,
  * pn_kmeans_init_{,device_}{f32,f64}, PN_OPT_KMEANS_FILTER. */
-/* Further additions of version 3: pn_kmeans_nearest_{,device_}{f32,f64}, PN_KMEANS_NEAREST_MAX. */
+/* Further additions of version 3: pn_kmeans_nearest_{,device_}{f32,f64}, PN_KMEANS_NEAREST_MAX;
+ * pn_spherical_kmeans_{,device_}{f32,f64}, pn_spherical_kmeans_assign_{,device_}{f32,f64}. */
 #define PN_ABI_VERSION 3
 
 /* ---- error codes.  EMPTY / NOT_CONTIGUOUS are ArrayError (src/lib.rs:9-16). */
@@ -1025,7 +1026,7 @@ int pn_mean_shift_labels_device_f64(const pn_index *index, const double *d_centr
  * pn_kmeans_*: 16 N bytes (N = n rounded up to a power of two, at least 1024: the sort of the members' lists),
  * 8 * dim * (n / 4096 + nc) bytes of segment sums and 36 bytes per centre.
  * Not in this version: Cosine / spherical k-means, row-sharded handles, mini-batch, empty-cluster relocation, a
- * device-driven iteration loop. */
+ * device-driven iteration loop.  (Spherical k-means on Cosine indexes: pn_spherical_kmeans_* below.) */
 int pn_kmeans_assign_f32(const pn_index *index, const float *centres, size_t nc, unsigned flags, int64_t *labels_out,
                          float *dist_out, double *inertia_out);
 int pn_kmeans_assign_device_f32(const pn_index *index, const float *d_centres, size_t nc, unsigned flags,
@@ -1051,6 +1052,65 @@ int pn_kmeans_device_f64(const pn_index *index, const double *d_init_centres, si
  * (not finite, a squared norm of 2^100 or more).  Host pointers; 8 <= dim <= 320, else PN_ERR_UNSUPPORTED.  Tests check
  * the inequality pair by pair. */
 int pn_kmeans_bounds_f32(const pn_index *index, const float *centres, size_t nc, double *bounds_out);
+
+/* ---- spherical k-means (extension; Cosine indexes only; T = the index's element type).  DESIGN.md 4.28.  The arguments
+ * are those of pn_kmeans_assign_* / pn_kmeans_*, one for one.
+ *   Distance: d(i, c) = the bits of pn_cosine_*(centre, row), the reference's Cosine::distance (src/distance.rs:86-107) in
+ *     T: dot = the sequential unfused fold of the products, each norm the correctly rounded sqrt of its own sequential
+ *     fold (the rows' norms are the index's, the centres' are folded once per assignment), d = 1 - dot / (norm_c *
+ *     norm_row).  Products and the denominator commute exactly: the value is symmetric in its two arguments.  Keys: the
+ *     signed order-preserving map of all floats (a distance may lie a few ulp below zero; -0 counts as +0), NaN the
+ *     canonical key above +inf.
+ *   Assignment: labels[i] = the centre of the least (key, centre number).  Where that least key is the NaN key -- a row or
+ *     every centre without a direction (zero, not finite), nc == 0 -- the row is a member of nothing: label -1, distance
+ *     NaN, inertia term 0.0.  dist[i] = the bits above.  Centres need not be normalised.
+ *   Inertia = SUM4096 (pn_kmeans_*) over i = 0 .. n - 1 of (double)dist[i] -- the distance itself, not its square.
+ *   pn_spherical_kmeans_*: Lloyd iterations from the caller's initial centres.  Iteration t: assign; for every cluster c
+ *     with its members in ascending row index, per column S_col = SUM4096(members' (double)x[i][col] / (double)norm_i)
+ *     (norm_i the index's norm of row i in T; the division IEEE f64), Q = the sum over the columns of S_col * S_col in the
+ *     64-partial shape of pn_kmeans_*'s shift (column col to partial col mod 64), and the new centre is
+ *     (T)(S_col / sqrt(Q)).  A centre without members, or whose Q is 0 or not finite, is unchanged (visible in
+ *     counts_out).  t_c, shift2, tol, max_iter, the one more assignment to the final centres and the outputs iterations /
+ *     shift2 / counts are exactly pn_kmeans_*'s.  Moved centres have unit norm to rounding.  IEEE, unfused, no
+ *     floating-point atomics: every result is a function of the rows, the initial centres, tol and max_iter alone, and the
+ *     host and device entry points give the same bits.  pn_stats.queries advances by n per assignment.
+ * Engines (PN_OPT_ENGINE and PN_OPT_KMEANS_FILTER with their values as for pn_kmeans_*; results never depend on them).  The
+ * filter -- the bf16 MFMA bound of pn_kmeans_* over the rows and centres normalised in f64, one candidate per row evaluated
+ * exactly, a proof per row -- takes 8 <= dim <= 304; rows it cannot prove (ties, rows within the filter's slack of a
+ * bisector, rows that are not finite or whose squared norm lies outside [2^-100, 2^100]; every row of a call in which a
+ * centre is in that state) are listed on the device and answered by the exact kernel, and their number is added to
+ * pn_stats.fallback_queries.  The exact kernel alone: PN_ENGINE_EXACT, PN_OPT_KMEANS_FILTER = 2, nc = 1, dim outside the
+ * filter's range, and under PN_ENGINE_AUTO below pn_kmeans_*'s line (nc >= 64, dim >= 64, n * nc * dim >= 8e9, 16e9 where
+ * dim < 128), which is unmeasured for this family.
+ * Argument errors, before any device is touched, in pn_kmeans_*'s order; the one difference: a Euclidean index is
+ * PN_ERR_UNSUPPORTED ("needs a Cosine index").  n == 0 as for pn_kmeans_*.
+ * Device entry points as pn_kmeans_*'s: pn_spherical_kmeans_assign_device_* never waits, pn_spherical_kmeans_device_*
+ * blocks the host once per iteration to read the stop word (16 bytes).  Device memory of a call: pn_kmeans_*'s, plus
+ * sizeof T bytes per centre (the centres' norms).
+ * Not in this version: row-sharded handles, spherical k-means++ seeding on the device, mini-batch, m > 1 centres per row,
+ * the filter on rows wider than 304 columns (those take the exact kernel). */
+int pn_spherical_kmeans_assign_f32(const pn_index *index, const float *centres, size_t nc, unsigned flags,
+                                   int64_t *labels_out, float *dist_out, double *inertia_out);
+int pn_spherical_kmeans_assign_device_f32(const pn_index *index, const float *d_centres, size_t nc, unsigned flags,
+                                          int64_t *d_labels, float *d_dist, double *d_inertia, void *stream);
+int pn_spherical_kmeans_f32(const pn_index *index, const float *init_centres, size_t nc, double tol, size_t max_iter,
+                            unsigned flags, float *centres_out, int64_t *labels_out, float *dist_out, uint64_t *counts_out,
+                            double *inertia_out, uint64_t *iterations_out, double *shift2_out);
+int pn_spherical_kmeans_device_f32(const pn_index *index, const float *d_init_centres, size_t nc, double tol,
+                                   size_t max_iter, unsigned flags, float *d_centres, int64_t *d_labels, float *d_dist,
+                                   uint64_t *d_counts, double *d_inertia, uint64_t *d_iterations, double *d_shift2,
+                                   void *stream);
+int pn_spherical_kmeans_assign_f64(const pn_index *index, const double *centres, size_t nc, unsigned flags,
+                                   int64_t *labels_out, double *dist_out, double *inertia_out);
+int pn_spherical_kmeans_assign_device_f64(const pn_index *index, const double *d_centres, size_t nc, unsigned flags,
+                                          int64_t *d_labels, double *d_dist, double *d_inertia, void *stream);
+int pn_spherical_kmeans_f64(const pn_index *index, const double *init_centres, size_t nc, double tol, size_t max_iter,
+                            unsigned flags, double *centres_out, int64_t *labels_out, double *dist_out,
+                            uint64_t *counts_out, double *inertia_out, uint64_t *iterations_out, double *shift2_out);
+int pn_spherical_kmeans_device_f64(const pn_index *index, const double *d_init_centres, size_t nc, double tol,
+                                   size_t max_iter, unsigned flags, double *d_centres, int64_t *d_labels, double *d_dist,
+                                   uint64_t *d_counts, double *d_inertia, uint64_t *d_iterations, double *d_shift2,
+                                   void *stream);
 
 /* ---- the m nearest centres of every indexed row (extension; Euclidean indexes only; T = the index's element type).
  * DESIGN.md 4.27.  For multi-probe lists and spill assignment, the second-nearest centre of Hamerly / Elkan bounds and of

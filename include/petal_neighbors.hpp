@@ -710,6 +710,42 @@ class BallTree {
         res.n_iter = (size_t)iters;
         return res;
     }
+    // extension: spherical k-means on a Cosine tree (pn_spherical_kmeans_*): kmeans_assign / kmeans with Cosine::distance,
+    // the centres the normalised sums of their members' directions; the inertia sums the distances themselves, and a row
+    // without a direction has label -1 and distance NaN
+    KMeans<A> spherical_kmeans_assign(const A *centres, size_t k) const {
+        KMeans<A> res;
+        res.centres.assign(centres, centres + k * dim_);
+        res.labels.resize(n_ + 1);
+        res.dist.resize(n_ + 1);
+        if constexpr (kF32)
+            check(pn_spherical_kmeans_assign_f32(h_, centres, k, 0u, res.labels.data(), res.dist.data(), &res.inertia));
+        else
+            check(pn_spherical_kmeans_assign_f64(h_, centres, k, 0u, res.labels.data(), res.dist.data(), &res.inertia));
+        res.labels.resize(n_);
+        res.dist.resize(n_);
+        return res;
+    }
+    KMeans<A> spherical_kmeans(const A *init, size_t k, double tol, size_t max_iter = 300) const {
+        KMeans<A> res;
+        res.centres.resize(k * dim_ + 1);
+        res.labels.resize(n_ + 1);
+        res.dist.resize(n_ + 1);
+        std::vector<uint64_t> counts(k + 1);
+        uint64_t iters = 0;
+        if constexpr (kF32)
+            check(pn_spherical_kmeans_f32(h_, init, k, tol, max_iter, 0u, res.centres.data(), res.labels.data(),
+                                          res.dist.data(), counts.data(), &res.inertia, &iters, &res.shift2));
+        else
+            check(pn_spherical_kmeans_f64(h_, init, k, tol, max_iter, 0u, res.centres.data(), res.labels.data(),
+                                          res.dist.data(), counts.data(), &res.inertia, &iters, &res.shift2));
+        res.centres.resize(k * dim_);
+        res.labels.resize(n_);
+        res.dist.resize(n_);
+        res.counts.assign(counts.begin(), counts.begin() + k);
+        res.n_iter = (size_t)iters;
+        return res;
+    }
     // extension: greedy k-means++ seeding on the device (pn_kmeans_init_*): k of the indexed rows as initial centres for
     // kmeans, a function of the rows, k, trials and seed alone.  trials: candidates per round, 1 .. 16 (1: classic
     // k-means++; 0: 2 + floor(ln k), at most 16).  The chosen rows' numbers (with the index base) go to *rows when given.

@@ -129,6 +129,10 @@ PAIRED = {
     "pn_kmeans_nearest_device": (_i, [_vp, _vp, _sz, _sz, _cu, _vp, _vp, _vp]),
     "pn_kmeans": (_i, [_vp, _vp, _sz, _d, _sz, _cu] + [_vp] * 7),
     "pn_kmeans_device": (_i, [_vp, _vp, _sz, _d, _sz, _cu] + [_vp] * 8),
+    "pn_spherical_kmeans_assign": (_i, [_vp, _vp, _sz, _cu] + [_vp] * 3),
+    "pn_spherical_kmeans_assign_device": (_i, [_vp, _vp, _sz, _cu] + [_vp] * 4),
+    "pn_spherical_kmeans": (_i, [_vp, _vp, _sz, _d, _sz, _cu] + [_vp] * 7),
+    "pn_spherical_kmeans_device": (_i, [_vp, _vp, _sz, _d, _sz, _cu] + [_vp] * 8),
     "pn_kmeans_init": (_i, [_vp, _sz, _sz, _u64, _cu, _vp, _vp]),
     "pn_kmeans_init_device": (_i, [_vp, _sz, _sz, _u64, _cu, _vp, _vp, _vp]),
     "pn_silhouette": (_i, [_vp, _vp, _sz, _vp, _sz, _cu] + [_vp] * 6),

@@ -925,24 +925,30 @@ class BallTree(Handle):
         ``(labels int64 [n], dist [n], inertia)`` with ``dist`` the distance to that centre and ``inertia`` the sum of
         the squared distances in the library's fixed shape (a float)."""
         self._euclidean_only("k-means")
+        return self._km_assign("kmeans", centres)
+
+    def _km_assign(self, fam, centres):
         c = self._centres(centres)
         labels = np.empty(self._n, dtype=np.int64)
         dist = np.empty(self._n, dtype=self.dtype)
         inertia = C.c_double(0.0)
-        check(self._fn("kmeans_assign")(self._h, c.ctypes.data if c.shape[0] else None, c.shape[0], 0, labels.ctypes.data,
+        check(self._fn(fam + "_assign")(self._h, c.ctypes.data if c.shape[0] else None, c.shape[0], 0, labels.ctypes.data,
                                         dist.ctypes.data, C.byref(inertia)))
         return labels, dist, float(inertia.value)
 
     def kmeans_assign_device(self, centres, out_labels=None, out_dist=None, out_inertia=None, stream=None):
         """``kmeans_assign`` in HBM: ``centres`` a contiguous 2-D CUDA tensor; returns CUDA tensors ``(labels int64 [n],
         dist [n], inertia float64 [1])``.  Never waits."""
-        import torch
         self._euclidean_only("k-means")
+        return self._km_assign_device("kmeans", centres, out_labels, out_dist, out_inertia, stream)
+
+    def _km_assign_device(self, fam, centres, out_labels, out_dist, out_inertia, stream):
+        import torch
         centres, nc, ptr = self._centres_device(centres)
         labels, dist, inertia = self._outs((out_labels, self._n, torch.int64, self._n),
                                            (out_dist, self._n, self._tdt, self._n),
                                            (out_inertia, 1, torch.float64, 1, True))
-        check(self._fn("kmeans_assign_device")(self._h, ptr, nc, 0, labels.data_ptr(), dist.data_ptr(), inertia.data_ptr(),
+        check(self._fn(fam + "_assign_device")(self._h, ptr, nc, 0, labels.data_ptr(), dist.data_ptr(), inertia.data_ptr(),
                                                stream_arg(stream, self._dev)))
         return labels, dist, inertia
 
@@ -1082,6 +1088,9 @@ class BallTree(Handle):
             init = self.kmeans_plusplus(int(centres_or_k), seed)
         else:
             init = self._centres(centres_or_k)
+        return self._km_loop("kmeans", init, abs_tol, max_iter, full)
+
+    def _km_loop(self, fam, init, abs_tol, max_iter, full):
         k = init.shape[0]
         if k < 1:
             raise ValueError("k-means needs at least one centre")
@@ -1091,7 +1100,7 @@ class BallTree(Handle):
         dist = np.empty(self._n, dtype=self.dtype)
         counts = np.zeros(k, dtype=np.uint64)
         inertia, shift2, iters = C.c_double(0.0), C.c_double(0.0), C.c_uint64(0)
-        check(self._fn("kmeans")(
+        check(self._fn(fam)(
             self._h, init.ctypes.data, k, abs_tol, max_iter, 0, centres.ctypes.data, labels.ctypes.data, dist.ctypes.data,
             counts.ctypes.data, C.byref(inertia), C.byref(iters), C.byref(shift2)))
         self.last_n_iter = int(iters.value)
@@ -1103,8 +1112,11 @@ class BallTree(Handle):
         """``kmeans`` in HBM from initial centres given as a contiguous 2-D CUDA tensor, with the absolute tolerance:
         CUDA tensors ``(centres, labels int64 [n], dist [n], counts int64 [k], inertia float64 [1], iterations int64 [1],
         shift2 float64 [1])``.  The call waits for the device once per iteration and cannot be captured into a graph."""
-        import torch
         self._euclidean_only("k-means")
+        return self._km_loop_device("kmeans", centres, abs_tol, max_iter, stream)
+
+    def _km_loop_device(self, fam, centres, abs_tol, max_iter, stream):
+        import torch
         centres, k, _ = self._centres_device(centres)
         abs_tol, max_iter = self._km_tol(0.0, abs_tol, max_iter)
         if k < 1:
@@ -1117,7 +1129,7 @@ class BallTree(Handle):
         inertia = torch.zeros(1, dtype=torch.float64, device=dev)
         iters = torch.zeros(1, dtype=torch.int64, device=dev)
         shift2 = torch.zeros(1, dtype=torch.float64, device=dev)
-        check(self._fn("kmeans_device")(
+        check(self._fn(fam + "_device")(
             self._h, centres.data_ptr(), k, abs_tol, max_iter, 0, out_c.data_ptr(), labels.data_ptr(), dist.data_ptr(),
             counts.data_ptr(), inertia.data_ptr(), iters.data_ptr(), shift2.data_ptr(), stream_arg(stream, dev)))
         return out_c, labels, dist, counts, inertia, iters, shift2
@@ -1128,6 +1140,56 @@ class BallTree(Handle):
         out = np.zeros((self._n, c.shape[0]), dtype=np.float64)
         check(_lib.lib().pn_kmeans_bounds_f32(self._h, c.ctypes.data if c.shape[0] else None, c.shape[0], out.ctypes.data))
         return out
+
+    # -------------------------------------------------- spherical k-means
+    # k-means on a Cosine tree (``pn_spherical_kmeans_*``): rows go to the centre of the least ``Cosine::distance`` behind a
+    # bf16 MFMA filter over the normalised rows, the centres become the normalised sums of their members' directions.  The
+    # argument layer, the outputs and the fixed shapes of the sums are those of ``kmeans``; the inertia is the sum of the
+    # distances themselves (not squared), and a row or centre without a direction (zero, not finite) is a member of
+    # nothing: label -1, distance NaN.
+    def _cosine_only(self, what):
+        if not isinstance(self.metric, Cosine):
+            raise ValueError(f"{what} needs a Cosine tree")
+
+    def spherical_kmeans_assign(self, centres):
+        """The centre of the least Cosine distance of every indexed row by (distance, centre number): ``(labels int64 [n],
+        dist [n], inertia)``, ``inertia`` the sum of the distances in the library's fixed shape.  Centres need not be
+        normalised."""
+        self._cosine_only("spherical k-means")
+        return self._km_assign("spherical_kmeans", centres)
+
+    def spherical_kmeans_assign_device(self, centres, out_labels=None, out_dist=None, out_inertia=None, stream=None):
+        """``spherical_kmeans_assign`` in HBM: ``centres`` a contiguous 2-D CUDA tensor; returns CUDA tensors ``(labels
+        int64 [n], dist [n], inertia float64 [1])``.  Never waits."""
+        self._cosine_only("spherical k-means")
+        return self._km_assign_device("spherical_kmeans", centres, out_labels, out_dist, out_inertia, stream)
+
+    def spherical_kmeans(self, centres_or_k, tol: float = 1e-4, max_iter: int = 300, seed=None, full: bool = False):
+        """Spherical k-means from the given initial centres ``[k][dim]``: ``(centres [k][dim], labels int64 [n], inertia)``;
+        with ``full=True`` also ``dist [n]``, ``counts uint64 [k]``, ``iterations`` and ``shift2``.  An integer ``k`` seeds
+        with ``k`` distinct rows drawn by ``np.random.default_rng(seed).choice(n, k, replace=False)`` (the rows must be on
+        the host).  ``tol`` is the ABSOLUTE bound on the summed squared moves of the centres, which have unit norm once
+        moved.  A cluster without members, or whose members' directions cancel, keeps its centre: look at ``counts``."""
+        self._cosine_only("spherical k-means")
+        abs_tol, max_iter = self._km_tol(0.0, tol, max_iter)
+        if np.ndim(centres_or_k) == 0:
+            k = int(centres_or_k)
+            if k < 1 or k > self._n:
+                raise ValueError("k must be between 1 and the number of rows")
+            if self.points is None:
+                raise ValueError("seeding with k needs the rows on the host")
+            rows = np.random.default_rng(seed).choice(self._n, k, replace=False)
+            init = np.ascontiguousarray(self.points)[rows].copy()
+        else:
+            init = self._centres(centres_or_k)
+        return self._km_loop("spherical_kmeans", init, abs_tol, max_iter, full)
+
+    def spherical_kmeans_device(self, centres, abs_tol, max_iter: int = 300, stream=None):
+        """``spherical_kmeans`` in HBM from initial centres given as a contiguous 2-D CUDA tensor: CUDA tensors ``(centres,
+        labels int64 [n], dist [n], counts int64 [k], inertia float64 [1], iterations int64 [1], shift2 float64 [1])``.
+        The call waits for the device once per iteration and cannot be captured into a graph."""
+        self._cosine_only("spherical k-means")
+        return self._km_loop_device("spherical_kmeans", centres, abs_tol, max_iter, stream)
 
     # -------------------------------------------------- silhouette
     # scikit-learn's ``silhouette_samples`` / ``silhouette_score`` on the device (``pn_silhouette_*``): every (scored row,

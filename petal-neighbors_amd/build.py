@@ -54,6 +54,7 @@ UNITS = [
     ("kmeans.hip", ["-ffp-contract=off"]),
     ("kmeans_init.hip", ["-ffp-contract=off"]),
     ("kmeans_nearest.hip", ["-ffp-contract=off"]),
+    ("spherical_kmeans.hip", ["-ffp-contract=off"]),
     ("optics.hip", ["-ffp-contract=off"]),
     ("radii_tau.hip", ["-ffp-contract=off"]),
     # (its fold is written as scalar f32 operations and stays so: the packed f32 forms are kept out of this unit)

@@ -5302,8 +5302,10 @@ PN_MS_ENTRIES(f64, double)
 // launches), and on narrow rows the filter gains too little per centre to make it up (the line)
 constexpr size_t kKmAutoMinCentres = 64, kKmAutoMinDim = 64, kKmAutoWideDim = 128;
 constexpr double kKmAutoMinWork = 8e9, kKmAutoMinWorkNarrow = 16e9;
-static bool km_use_filter(const pn_index *ix, size_t nc) {
-    if (nc < 2 || ix->n == 0 || !km_filter_supported((int)ix->dim) || ix->kmeans_filter == 2) return false;
+// (sph: pn_spherical_kmeans_* -- the same rule over its own filter's range; its line is unmeasured)
+static bool km_use_filter(const pn_index *ix, size_t nc, bool sph = false) {
+    const bool supported = sph ? skm_filter_supported((int)ix->dim) : km_filter_supported((int)ix->dim);
+    if (nc < 2 || ix->n == 0 || !supported || ix->kmeans_filter == 2) return false;
     if (ix->kmeans_filter == 1) return true;
     if (ix->engine == PN_ENGINE_EXACT) return false;
     if (ix->engine == PN_ENGINE_BF16) return true;
@@ -5312,7 +5314,7 @@ static bool km_use_filter(const pn_index *ix, size_t nc) {
 }
 // (before any device is touched; the header states the order)
 static int km_args(const pn_index *ix, bool loop, unsigned flags, double tol, size_t max_iter, const void *labels,
-                   const void *centres_out, const void *centres, size_t nc, int elem_bytes) {
+                   const void *centres_out, const void *centres, size_t nc, int elem_bytes, bool sph = false) {
     if (flags) return fail(PN_ERR_INVALID, "unknown k-means flags 0x%x", flags);
     if (loop && !(tol >= 0.0)) return fail(PN_ERR_INVALID, "tol must be >= 0");
     if (loop && max_iter == 0) return fail(PN_ERR_INVALID, "max_iter must be at least 1");
@@ -5322,39 +5324,61 @@ static int km_args(const pn_index *ix, bool loop, unsigned flags, double tol, si
     if (loop && nc == 0) return fail(PN_ERR_INVALID, "k-means needs at least one centre");
     if (!ix) return fail(PN_ERR_INVALID, "index is NULL");
     if (ix->elem_bytes != elem_bytes) return fail(PN_ERR_INVALID, "index element type mismatch");
-    if (ix->metric != 0) return fail(PN_ERR_UNSUPPORTED, "k-means needs a Euclidean index");
+    if (sph && ix->metric != 1) return fail(PN_ERR_UNSUPPORTED, "spherical k-means needs a Cosine index");
+    if (!sph && ix->metric != 0) return fail(PN_ERR_UNSUPPORTED, "k-means needs a Euclidean index");
     if (ix->n > 0x7FFFFFFFull || nc > 0x7FFFFFFFull) return fail(PN_ERR_UNSUPPORTED, "too many rows or centres");
     return PN_OK;
 }
-// the rows' image of a call (filter path only)
-template <typename T>
+// the rows' image of a call (filter path only); SPH: the rows normalised
+template <typename T, bool SPH = false>
 static int km_pack_rows(const pn_index *ix, Workspace &ws, KmRowImage *rows, hipStream_t s) {
     PNCHK(ws.w_km_rows.ensure(km_row_image_bytes(ix->n, (int)ix->dim)));
     *rows = km_row_image_at(ws.w_km_rows.p, ix->n, (int)ix->dim);
-    HIPCHK(launch_km_pack_rows<T>((const T *)ix->d_pts, ix->n, ix->ld, (int)ix->dim, *rows, s));
+    if constexpr (SPH)
+        HIPCHK(launch_skm_pack_rows<T>((const T *)ix->d_pts, ix->n, ix->ld, (int)ix->dim, *rows, s));
+    else
+        HIPCHK(launch_km_pack_rows<T>((const T *)ix->d_pts, ix->n, ix->ld, (int)ix->dim, *rows, s));
     return PN_OK;
 }
 // One assignment, in a held workspace on stream s; n >= 1.  rows: the packed rows when the filter is used, else nullptr.
 // d_dist nullable unless d_inertia is given.
-template <typename T>
+template <typename T, bool SPH = false>
 static int km_assign_enqueue(const pn_index *ix, Workspace &ws, const KmRowImage *rows, const T *d_centres, size_t nc,
                              int64_t *d_labels, T *d_dist, double *d_inertia, hipStream_t s) {
     const size_t n = ix->n;
     const int dim = (int)ix->dim;
     const T *X = (const T *)ix->d_pts;
     // w_km: nsel (8 bytes) | [inertia without the caller's distances: dist [n] T] | [inertia: its segments] | [filter:
-    // cand [n] u32 | tau [n] f32 | sel [n] u32]
+    // cand [n] u32 | tau [n] f32 | sel [n] u32] | [SPH: the centres' norms [nc] T]
     const size_t n2 = round_up(n, (size_t)2);
     const bool filter = rows && nc;
     const size_t dist_bytes = d_inertia && !d_dist ? n2 * sizeof(T) : 0, seg_bytes = d_inertia ? km_inertia_bytes(n) : 0;
-    PNCHK(ws.w_km.ensure(8 + dist_bytes + seg_bytes + (filter ? n2 * 12 : 0)));
+    const size_t filter_bytes = filter ? n2 * 12 : 0;
+    PNCHK(ws.w_km.ensure(8 + dist_bytes + seg_bytes + filter_bytes + (SPH ? nc * sizeof(T) : 0)));
     uint32_t *nsel = (uint32_t *)ws.w_km.p;
     T *own_dist = (T *)(nsel + 2);
     void *seg = (void *)((char *)own_dist + dist_bytes);
     uint32_t *cand = (uint32_t *)((char *)seg + seg_bytes), *sel = cand + 2 * n2;
     float *tau = (float *)(cand + n2);
     if (d_inertia && !d_dist) d_dist = own_dist;
-    if (filter) {
+    if constexpr (SPH) {
+        // Cosine::distance: the centres' norms are folded once per assignment, the rows' are the index's
+        T *cnorm = (T *)((char *)cand + filter_bytes);
+        const T *rnorm = (const T *)ix->d_cnorm;
+        HIPCHK(launch_cosine_norms<T>(d_centres, nc, dim, (size_t)dim, cnorm, s));
+        if (filter) {
+            PNCHK(ws.w_km_cent.ensure(km_centre_image_bytes(nc, dim)));
+            const KmCentreImage ci = km_centre_image_at(ws.w_km_cent.p, nc, dim);
+            HIPCHK(launch_skm_pack_centres<T>(d_centres, nc, dim, ci, s));
+            HIPCHK(launch_skm_filter(*rows, n, ci, nc, cand, tau, s));
+            HIPCHK(launch_skm_rerank<T>(X, n, ix->ld, dim, rnorm, d_centres, cnorm, nc, cand, tau, *rows, ci, sel, nsel,
+                                        d_labels, d_dist, s));
+            HIPCHK(launch_skm_exact<T>(X, n, ix->ld, dim, rnorm, d_centres, cnorm, nc, sel, nsel, d_labels, d_dist, s));
+            if (ix->d_stats) HIPCHK(launch_radii_add_listed(nsel, ix->d_stats, s));
+        } else {
+            HIPCHK(launch_skm_exact<T>(X, n, ix->ld, dim, rnorm, d_centres, cnorm, nc, nullptr, nullptr, d_labels, d_dist, s));
+        }
+    } else if (filter) {
         PNCHK(ws.w_km_cent.ensure(km_centre_image_bytes(nc, dim)));
         const KmCentreImage ci = km_centre_image_at(ws.w_km_cent.p, nc, dim);
         HIPCHK(launch_km_pack_centres<T>(d_centres, nc, dim, ci, s));
@@ -5366,15 +5390,15 @@ static int km_assign_enqueue(const pn_index *ix, Workspace &ws, const KmRowImage
     } else {
         HIPCHK(launch_km_exact<T>(X, n, ix->ld, dim, d_centres, nc, nullptr, nullptr, d_labels, d_dist, s));
     }
-    if (d_inertia) HIPCHK(launch_km_inertia<T>(d_labels, d_dist, n, seg, d_inertia, s));
+    if (d_inertia) HIPCHK(launch_km_inertia<T>(d_labels, d_dist, n, seg, d_inertia, s, !SPH));
     std::lock_guard<std::mutex> lk(ix->sh.mu);
     ix->sh.stats.queries += n;
     return PN_OK;
 }
-template <typename T>
+template <typename T, bool SPH = false>
 static int km_assign_device(const pn_index *ix, const T *d_centres, size_t nc, unsigned flags, int64_t *d_labels, T *d_dist,
                             double *d_inertia, hipStream_t s) {
-    PNCHK(km_args(ix, false, flags, 0.0, 1, d_labels, nullptr, d_centres, nc, (int)sizeof(T)));
+    PNCHK(km_args(ix, false, flags, 0.0, 1, d_labels, nullptr, d_centres, nc, (int)sizeof(T), SPH));
     CallScope call(ix);
     PNCHK(call.guard());
     if (ix->n == 0) {
@@ -5383,14 +5407,14 @@ static int km_assign_device(const pn_index *ix, const T *d_centres, size_t nc, u
     }
     PNCHK(call.on_stream(s));
     KmRowImage rows;
-    const bool filter = km_use_filter(ix, nc);
-    if (filter) PNCHK(km_pack_rows<T>(ix, call.ws(), &rows, s));
-    return km_assign_enqueue<T>(ix, call.ws(), filter ? &rows : nullptr, d_centres, nc, d_labels, d_dist, d_inertia, s);
+    const bool filter = km_use_filter(ix, nc, SPH);
+    if (filter) PNCHK((km_pack_rows<T, SPH>(ix, call.ws(), &rows, s)));
+    return km_assign_enqueue<T, SPH>(ix, call.ws(), filter ? &rows : nullptr, d_centres, nc, d_labels, d_dist, d_inertia, s);
 }
-template <typename T>
+template <typename T, bool SPH = false>
 static int km_assign_host(const pn_index *ix, const T *centres, size_t nc, unsigned flags, int64_t *labels, T *dist,
                           double *inertia) {
-    PNCHK(km_args(ix, false, flags, 0.0, 1, labels, nullptr, centres, nc, (int)sizeof(T)));
+    PNCHK(km_args(ix, false, flags, 0.0, 1, labels, nullptr, centres, nc, (int)sizeof(T), SPH));
     if (ix->n == 0) {
         if (inertia) *inertia = 0.0;
         return PN_OK;
@@ -5405,24 +5429,33 @@ static int km_assign_host(const pn_index *ix, const T *centres, size_t nc, unsig
         std::tuple{io.in(centres, nc * ix->dim), io.out(labels, n), io.out(dist, n), io.out(inertia, 1)};
     PNCHK(io.up());
     KmRowImage rows;
-    const bool filter = km_use_filter(ix, nc);
-    if (filter) PNCHK(km_pack_rows<T>(ix, ws, &rows, s));
-    PNCHK(km_assign_enqueue<T>(ix, ws, filter ? &rows : nullptr, io[d_centres], nc, io[d_labels],
-                               dist || inertia ? io[d_dist] : nullptr, inertia ? io[d_inertia] : nullptr, s));
+    const bool filter = km_use_filter(ix, nc, SPH);
+    if (filter) PNCHK((km_pack_rows<T, SPH>(ix, ws, &rows, s)));
+    PNCHK((km_assign_enqueue<T, SPH>(ix, ws, filter ? &rows : nullptr, io[d_centres], nc, io[d_labels],
+                                     dist || inertia ? io[d_dist] : nullptr, inertia ? io[d_inertia] : nullptr, s)));
     return io.down();
 }
 // The iterations, in a held workspace on stream s; everything in HBM, d_centres holds the initial centres on entry;
 // n, nc >= 1.  Blocks the host once per iteration.
-template <typename T>
+template <typename T, bool SPH = false>
 static int km_loop_enqueue(const pn_index *ix, Workspace &ws, size_t nc, double tol, size_t max_iter, T *d_centres,
                            int64_t *d_labels, T *d_dist, uint64_t *d_counts, double *d_inertia, uint64_t *d_iterations,
                            double *d_shift2, hipStream_t s) {
     const size_t n = ix->n;
     const int dim = (int)ix->dim;
     KmRowImage rows;
-    const bool filter = km_use_filter(ix, nc);
-    if (filter) PNCHK(km_pack_rows<T>(ix, ws, &rows, s));
+    const bool filter = km_use_filter(ix, nc, SPH);
+    if (filter) PNCHK((km_pack_rows<T, SPH>(ix, ws, &rows, s)));
     PNCHK(ws.w_km_upd.ensure(km_update_bytes(n, nc, dim)));
+    // one update of the centres (or, without them, the counts): the mean, or SPH the normalised sum of the directions
+    auto update = [&](T *centres, uint64_t *counts, double tl, int last, double **stop_out) {
+        if constexpr (SPH)
+            return skm_update_enqueue<T>((const T *)ix->d_pts, n, ix->ld, dim, (const T *)ix->d_cnorm, d_labels, nc,
+                                         ws.w_km_upd.p, centres, counts, tl, last, stop_out, s);
+        else
+            return km_update_enqueue<T>((const T *)ix->d_pts, n, ix->ld, dim, d_labels, nc, ws.w_km_upd.p, centres, counts, tl,
+                                        last, stop_out, s);
+    };
     struct {
         double shift2;
         unsigned long long stop;
@@ -5430,28 +5463,25 @@ static int km_loop_enqueue(const pn_index *ix, Workspace &ws, size_t nc, double 
     uint64_t iterations = 0;
     double *d_stop = nullptr;
     for (size_t t = 1;; ++t) {
-        PNCHK(km_assign_enqueue<T>(ix, ws, filter ? &rows : nullptr, d_centres, nc, d_labels, (T *)nullptr, nullptr, s));
-        HIPCHK(km_update_enqueue<T>((const T *)ix->d_pts, n, ix->ld, dim, d_labels, nc, ws.w_km_upd.p, d_centres, nullptr, tol,
-                                    t >= max_iter, &d_stop, s));
+        PNCHK((km_assign_enqueue<T, SPH>(ix, ws, filter ? &rows : nullptr, d_centres, nc, d_labels, (T *)nullptr, nullptr, s)));
+        HIPCHK(update(d_centres, nullptr, tol, t >= max_iter, &d_stop));
         HIPCHK(hipMemcpyAsync(&h_stop, d_stop, sizeof h_stop, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         iterations = t;
         if (h_stop.stop || t >= max_iter) break;
     }
-    PNCHK(km_assign_enqueue<T>(ix, ws, filter ? &rows : nullptr, d_centres, nc, d_labels, d_dist, d_inertia, s));
-    if (d_counts)
-        HIPCHK(km_update_enqueue<T>((const T *)ix->d_pts, n, ix->ld, dim, d_labels, nc, ws.w_km_upd.p, (T *)nullptr, d_counts,
-                                    0.0, 1, nullptr, s));
+    PNCHK((km_assign_enqueue<T, SPH>(ix, ws, filter ? &rows : nullptr, d_centres, nc, d_labels, d_dist, d_inertia, s)));
+    if (d_counts) HIPCHK(update((T *)nullptr, d_counts, 0.0, 1, nullptr));
     if (d_shift2) HIPCHK(hipMemcpyAsync(d_shift2, d_stop, sizeof(double), hipMemcpyDeviceToDevice, s));
     if (d_iterations) HIPCHK(hipMemcpyAsync(d_iterations, &iterations, sizeof(uint64_t), hipMemcpyHostToDevice, s));
     if (d_iterations) HIPCHK(hipStreamSynchronize(s));  // (the source is this frame's)
     return PN_OK;
 }
-template <typename T>
+template <typename T, bool SPH = false>
 static int km_device(const pn_index *ix, const T *d_init, size_t nc, double tol, size_t max_iter, unsigned flags, T *d_centres,
                      int64_t *d_labels, T *d_dist, uint64_t *d_counts, double *d_inertia, uint64_t *d_iterations,
                      double *d_shift2, hipStream_t s) {
-    PNCHK(km_args(ix, true, flags, tol, max_iter, d_labels, d_centres, d_init, nc, (int)sizeof(T)));
+    PNCHK(km_args(ix, true, flags, tol, max_iter, d_labels, d_centres, d_init, nc, (int)sizeof(T), SPH));
     CallScope call(ix);
     PNCHK(call.guard());
     if (d_centres != d_init)
@@ -5464,13 +5494,13 @@ static int km_device(const pn_index *ix, const T *d_init, size_t nc, double tol,
         return PN_OK;
     }
     PNCHK(call.on_stream(s));
-    return km_loop_enqueue<T>(ix, call.ws(), nc, tol, max_iter, d_centres, d_labels, d_dist, d_counts, d_inertia, d_iterations,
-                              d_shift2, s);
+    return km_loop_enqueue<T, SPH>(ix, call.ws(), nc, tol, max_iter, d_centres, d_labels, d_dist, d_counts, d_inertia,
+                                   d_iterations, d_shift2, s);
 }
-template <typename T>
+template <typename T, bool SPH = false>
 static int km_host(const pn_index *ix, const T *init, size_t nc, double tol, size_t max_iter, unsigned flags, T *centres,
                    int64_t *labels, T *dist, uint64_t *counts, double *inertia, uint64_t *iterations, double *shift2) {
-    PNCHK(km_args(ix, true, flags, tol, max_iter, labels, centres, init, nc, (int)sizeof(T)));
+    PNCHK(km_args(ix, true, flags, tol, max_iter, labels, centres, init, nc, (int)sizeof(T), SPH));
     const size_t n = ix->n, dim = ix->dim;
     if (n == 0) {
         if (centres != init) memmove(centres, init, nc * dim * sizeof(T));
@@ -5487,9 +5517,9 @@ static int km_host(const pn_index *ix, const T *init, size_t nc, double tol, siz
         std::tuple{io.inout(init, centres, nc * dim), io.out(labels, n),     io.out(dist, n),  io.out(counts, nc),
                    io.out(inertia, 1),                io.out(iterations, 1), io.out(shift2, 1)};
     PNCHK(io.up());
-    PNCHK(km_loop_enqueue<T>(ix, call.ws(), nc, tol, max_iter, io[d_centres], io[d_labels],
-                             dist || inertia ? io[d_dist] : nullptr, counts ? io[d_counts] : nullptr,
-                             inertia ? io[d_inertia] : nullptr, io[d_iters], io[d_shift2], call.s()));
+    PNCHK((km_loop_enqueue<T, SPH>(ix, call.ws(), nc, tol, max_iter, io[d_centres], io[d_labels],
+                                   dist || inertia ? io[d_dist] : nullptr, counts ? io[d_counts] : nullptr,
+                                   inertia ? io[d_inertia] : nullptr, io[d_iters], io[d_shift2], call.s())));
     return io.down();
 }
 extern "C" int pn_kmeans_bounds_f32(const pn_index *ix, const float *centres, size_t nc, double *bounds_out) {
@@ -5541,6 +5571,37 @@ extern "C" int pn_kmeans_bounds_f32(const pn_index *ix, const float *centres, si
 PN_KM_ENTRIES(f32, float)
 PN_KM_ENTRIES(f64, double)
 #undef PN_KM_ENTRIES
+
+// Spherical k-means on Cosine indexes: pn_spherical_kmeans_assign_{,device_}*, pn_spherical_kmeans_{,device_}* (the kernels,
+// the bound and the update: spherical_kmeans.hip).  The host side is that of pn_kmeans_* above with SPH set:
+// the same chain of an assignment over the normalised images, the centres' norms folded first, the same loop and stop
+// word, the same workspace; the filter takes 8 <= dim <= 304.
+#define PN_SKM_ENTRIES(SFX, T)                                                                                                 \
+    extern "C" int pn_spherical_kmeans_assign_##SFX(const pn_index *ix, const T *centres, size_t nc, unsigned flags,            \
+                                                    int64_t *labels_out, T *dist_out, double *inertia_out) {                    \
+        return km_assign_host<T, true>(ix, centres, nc, flags, labels_out, dist_out, inertia_out);                              \
+    }                                                                                                                          \
+    extern "C" int pn_spherical_kmeans_assign_device_##SFX(const pn_index *ix, const T *d_centres, size_t nc, unsigned flags,   \
+                                                           int64_t *d_labels, T *d_dist, double *d_inertia, void *stream) {     \
+        return km_assign_device<T, true>(ix, d_centres, nc, flags, d_labels, d_dist, d_inertia, (hipStream_t)stream);           \
+    }                                                                                                                          \
+    extern "C" int pn_spherical_kmeans_##SFX(const pn_index *ix, const T *init_centres, size_t nc, double tol, size_t max_iter, \
+                                             unsigned flags, T *centres_out, int64_t *labels_out, T *dist_out,                  \
+                                             uint64_t *counts_out, double *inertia_out, uint64_t *iterations_out,               \
+                                             double *shift2_out) {                                                              \
+        return km_host<T, true>(ix, init_centres, nc, tol, max_iter, flags, centres_out, labels_out, dist_out, counts_out,      \
+                                inertia_out, iterations_out, shift2_out);                                                       \
+    }                                                                                                                          \
+    extern "C" int pn_spherical_kmeans_device_##SFX(const pn_index *ix, const T *d_init_centres, size_t nc, double tol,         \
+                                                    size_t max_iter, unsigned flags, T *d_centres, int64_t *d_labels,           \
+                                                    T *d_dist, uint64_t *d_counts, double *d_inertia, uint64_t *d_iterations,   \
+                                                    double *d_shift2, void *stream) {                                           \
+        return km_device<T, true>(ix, d_init_centres, nc, tol, max_iter, flags, d_centres, d_labels, d_dist, d_counts,          \
+                                  d_inertia, d_iterations, d_shift2, (hipStream_t)stream);                                      \
+    }
+PN_SKM_ENTRIES(f32, float)
+PN_SKM_ENTRIES(f64, double)
+#undef PN_SKM_ENTRIES
 
 // ---------------------------------------------------------------------------
 // The m nearest centres of every row: pn_kmeans_nearest_{,device_}{f32,f64} (the kernels: kmeans_nearest.hip).  The chain

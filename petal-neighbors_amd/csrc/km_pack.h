@@ -37,7 +37,11 @@ __device__ __forceinline__ double km_wave_sum(double v) {
 // cn (nullable) [n_img]: |x|^2 rounded down to f32 (+inf for the padding and for flagged rows); cc (nullable): cc[0..3] <-
 // the maxima Ce, B, Ch, Cl of |e|, |x|, |x^|, |x~| over the rows (as the bits of non-negative doubles, by integer max),
 // cc[4] <- nonzero when a row is flagged.  The centres of k-means: !ROWS with cn and cc.
-template <typename T, bool ROWS>
+// NORM (spherical_kmeans.hip): the normalising front of Cosine indexes.  The row that is packed is
+// x / |x| in f64 as cos_normalize_rows_kernel (bf16_filter.hip) forms it -- ss = the sum of the squares, every element
+// times 1 / sqrt(ss) -- and a row whose ss is not inside [2^-100, 2^100] (zero, not finite) is flagged.  Every packed
+// vector then has norm 1 to rounding.  Without NORM nothing of this is compiled: the other instantiations keep their bits.
+template <typename T, bool ROWS, bool NORM = false>
 __global__ __launch_bounds__(256) void km_pack_kernel(const T *__restrict__ X, size_t n, size_t n_img, size_t ld, int dim,
                                                       int dp, uint16_t *__restrict__ img, uint16_t *__restrict__ lo,
                                                       double *__restrict__ xn, float *__restrict__ xh,
@@ -49,11 +53,24 @@ __global__ __launch_bounds__(256) void km_pack_kernel(const T *__restrict__ X, s
     if (r >= n_img) return;  // (the whole wave)
     double s2 = 0.0, h2 = 0.0, l2 = 0.0, e2 = 0.0;
     bool bad = false;
+    double inv = 1.0;
+    if constexpr (NORM) {
+        double ss = 0.0;
+        if (r < n)
+            for (int k = lane; k < dim; k += 64) {
+                const double v = (double)X[r * ld + k];
+                ss = ss + v * v;
+            }
+        ss = km_wave_sum(ss);  // (the butterfly of commutative additions: the same bits on every lane)
+        if (r < n && !(ss >= 7.888609052210118e-31 && ss <= 1.2676506002282294e30)) bad = true;  // 2^-100 .. 2^100, NaN
+        inv = bad ? 0.0 : 1.0 / sqrt(ss);
+    }
     for (int k = lane; k < dp; k += 64) {
         uint16_t hb = 0, lb = 0;
-        if (r < n && k < dim) {
+        if (r < n && k < dim && !(NORM && bad)) {
             double x = (double)X[r * ld + k];
             if (mu) x = x - (double)mu[k];
+            if constexpr (NORM) x = x * inv;
             if (!(fabs(x) < 1.0e30)) {  // (NaN, inf, or beyond what a squared norm below 2^100 allows)
                 bad = true;
             } else {

@@ -336,7 +336,8 @@ __global__ __launch_bounds__(256) void km_none_kernel(size_t n, int64_t *__restr
 
 // ---- SUM4096 of the squared distances: one wave per segment of 4096 rows, then one thread over the segments
 constexpr int kKmSeg = 4096;
-template <typename T>
+// SQUARED: the term of a member is d * d (k-means); else d itself (spherical k-means)
+template <typename T, bool SQUARED>
 __global__ __launch_bounds__(64) void km_inertia_seg_kernel(const int64_t *__restrict__ labels, const T *__restrict__ dist,
                                                             size_t n, double *__restrict__ seg) {
 #pragma clang fp contract(off)
@@ -347,7 +348,7 @@ __global__ __launch_bounds__(64) void km_inertia_seg_kernel(const int64_t *__res
     double P = 0.0;
     for (size_t j = lane; j < len; j += 64) {
         const double d = (double)dist[beg + j];
-        const double t = labels[beg + j] < 0 ? 0.0 : d * d;
+        const double t = labels[beg + j] < 0 ? 0.0 : SQUARED ? d * d : d;
         P = P + t;
     }
     s_p[lane] = P;
@@ -645,10 +646,14 @@ hipError_t launch_km_exact(const T *X, size_t n, size_t ld, int dim, const T *ce
 
 size_t km_inertia_bytes(size_t n) { return ((n + kKmSeg - 1) / kKmSeg + 1) * sizeof(double); }
 template <typename T>
-hipError_t launch_km_inertia(const int64_t *labels, const T *dist, size_t n, void *buf, double *out, hipStream_t s) {
+hipError_t launch_km_inertia(const int64_t *labels, const T *dist, size_t n, void *buf, double *out, hipStream_t s,
+                             bool squared) {
     const size_t nseg = (n + kKmSeg - 1) / kKmSeg;
     double *seg = (double *)buf;
-    if (nseg) hipLaunchKernelGGL((km_inertia_seg_kernel<T>), dim3((unsigned)nseg), dim3(64), 0, s, labels, dist, n, seg);
+    if (nseg && squared)
+        hipLaunchKernelGGL((km_inertia_seg_kernel<T, true>), dim3((unsigned)nseg), dim3(64), 0, s, labels, dist, n, seg);
+    else if (nseg)
+        hipLaunchKernelGGL((km_inertia_seg_kernel<T, false>), dim3((unsigned)nseg), dim3(64), 0, s, labels, dist, n, seg);
     hipLaunchKernelGGL(km_fold_segments_kernel, dim3(1), dim3(64), 0, s, seg, nseg, out);
     return hipGetLastError();
 }
@@ -662,24 +667,39 @@ size_t km_update_bytes(size_t n, size_t nc, int dim) {
 }
 // labels [n] -> the members' lists, the counts (nullable) and, with centres != nullptr, one update of the centres in
 // place; stop_out (device, 16 bytes): {shift2, the stop word}
-template <typename T>
-hipError_t km_update_enqueue(const T *X, size_t n, size_t ld, int dim, const int64_t *labels, size_t nc, void *buf,
-                             T *centres, uint64_t *counts, double tol, int last, double **stop_out, hipStream_t s) {
+// the front half of an update, shared with spherical_kmeans.hip: the sort, the offsets, the counts and, with segments,
+// the (cluster, segment) enumeration; m <- where the parts of buf are
+hipError_t km_members_enqueue(const int64_t *labels, size_t n, size_t nc, int dim, void *buf, bool segments,
+                              uint64_t *counts, KmMembers *m, hipStream_t s) {
     const size_t N = sort_key_pair_len(n);
     uint64_t *key = (uint64_t *)buf;
     unsigned long long *pair = (unsigned long long *)(key + N);
     uint64_t *off = (uint64_t *)(pair + N), *seg_off = off + nc + 1, *scan = seg_off + nc + 1;
     double *tc = (double *)(scan + nc / 4096 + 2), *stop = tc + nc, *segsum = stop + 2;
     uint32_t *nseg = (uint32_t *)(segsum + km_max_segments(n, nc) * (size_t)dim);
-    if (stop_out) *stop_out = stop;
+    *m = KmMembers{key, off, seg_off, tc, stop, segsum, km_max_segments(n, nc)};
     hipLaunchKernelGGL(km_member_keys_kernel, km_grid(N), dim3(256), 0, s, labels, n, N, key, pair);
     hipError_t e = launch_sort_key_pair_u64(key, pair, N, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(km_offsets_kernel, km_grid(nc + 1), dim3(256), 0, s, key, N, nc, off);
-    hipLaunchKernelGGL(km_counts_kernel, km_grid(nc), dim3(256), 0, s, off, nc, centres ? nseg : (uint32_t *)nullptr, counts);
-    if (!centres) return hipGetLastError();
-    e = launch_exclusive_scan_u32(nseg, nc, seg_off, scan, nullptr, s);
+    hipLaunchKernelGGL(km_counts_kernel, km_grid(nc), dim3(256), 0, s, off, nc, segments ? nseg : (uint32_t *)nullptr, counts);
+    if (!segments) return hipGetLastError();
+    return launch_exclusive_scan_u32(nseg, nc, seg_off, scan, nullptr, s);
+}
+hipError_t launch_km_stop(const double *tc, size_t nc, double tol, int last, double *stop, hipStream_t s) {
+    hipLaunchKernelGGL(km_stop_kernel, dim3(1), dim3(64), 0, s, tc, nc, tol, last, stop);
+    return hipGetLastError();
+}
+template <typename T>
+hipError_t km_update_enqueue(const T *X, size_t n, size_t ld, int dim, const int64_t *labels, size_t nc, void *buf,
+                             T *centres, uint64_t *counts, double tol, int last, double **stop_out, hipStream_t s) {
+    KmMembers m;
+    const hipError_t e = km_members_enqueue(labels, n, nc, dim, buf, centres != nullptr, counts, &m, s);
     if (e != hipSuccess) return e;
+    const uint64_t *key = m.key, *off = m.off, *seg_off = m.seg_off;
+    double *tc = m.tc, *stop = m.stop, *segsum = m.segsum;
+    if (stop_out) *stop_out = stop;
+    if (!centres) return hipGetLastError();
     const dim3 grid((unsigned)km_max_segments(n, nc));
     if (ld % 16 == 0)
         hipLaunchKernelGGL((km_segment_sums_kernel<T, 16>), grid, dim3(64), 0, s, key, off, seg_off, nc, X, ld, dim, segsum);
@@ -698,7 +718,7 @@ hipError_t km_update_enqueue(const T *X, size_t n, size_t ld, int dim, const int
                                             uint32_t *, int64_t *, T *, hipStream_t);                                        \
     template hipError_t launch_km_exact<T>(const T *, size_t, size_t, int, const T *, size_t, const uint32_t *,              \
                                            const uint32_t *, int64_t *, T *, hipStream_t);                                   \
-    template hipError_t launch_km_inertia<T>(const int64_t *, const T *, size_t, void *, double *, hipStream_t);             \
+    template hipError_t launch_km_inertia<T>(const int64_t *, const T *, size_t, void *, double *, hipStream_t, bool);       \
     template hipError_t km_update_enqueue<T>(const T *, size_t, size_t, int, const int64_t *, size_t, void *, T *,           \
                                              uint64_t *, double, int, double **, hipStream_t);
 PN_KM_INSTANTIATE(float)

@@ -441,10 +441,12 @@ hipError_t launch_km_rerank(const T *X, size_t n, size_t ld, int dim, const T *c
 template <typename T>
 hipError_t launch_km_exact(const T *X, size_t n, size_t ld, int dim, const T *centres, size_t nc, const uint32_t *sel,
                            const uint32_t *nsel, int64_t *labels, T *dist, hipStream_t s);
-// *out <- SUM4096 of (double)dist[i]^2 (0 where labels[i] < 0); buf: km_inertia_bytes(n)
+// *out <- SUM4096 of (double)dist[i]^2 (0 where labels[i] < 0), of (double)dist[i] itself without `squared`; buf:
+// km_inertia_bytes(n)
 size_t km_inertia_bytes(size_t n);
 template <typename T>
-hipError_t launch_km_inertia(const int64_t *labels, const T *dist, size_t n, void *buf, double *out, hipStream_t s);
+hipError_t launch_km_inertia(const int64_t *labels, const T *dist, size_t n, void *buf, double *out, hipStream_t s,
+                             bool squared = true);
 // The members' lists of labels [n] (one sort), counts [nc] (nullable) and, with centres != nullptr, one update of the
 // centres [nc][dim] in place; *stop_out <- where the 16 bytes {shift2, stop word = shift2 <= tol || last} will be (in
 // buf: km_update_bytes(n, nc, dim), 8-byte aligned).  n, nc >= 1.
@@ -452,6 +454,44 @@ size_t km_update_bytes(size_t n, size_t nc, int dim);
 template <typename T>
 hipError_t km_update_enqueue(const T *X, size_t n, size_t ld, int dim, const int64_t *labels, size_t nc, void *buf,
                              T *centres, uint64_t *counts, double tol, int last, double **stop_out, hipStream_t s);
+// its front half (the sort of the members' lists, the offsets, counts and, with `segments`, the enumeration of the
+// (cluster, segment of 4096 members) pairs) and its stop kernel, for the update of spherical_kmeans.hip
+struct KmMembers {
+    uint64_t *key, *off, *seg_off;  // sorted (label << 32 | row) [N]; first position per cluster [nc + 1]; first segment
+    double *tc, *stop, *segsum;     // squared move per centre [nc]; {shift2, stop word}; [max_segments][dim]
+    size_t max_segments;
+};
+hipError_t km_members_enqueue(const int64_t *labels, size_t n, size_t nc, int dim, void *buf, bool segments,
+                              uint64_t *counts, KmMembers *m, hipStream_t s);
+hipError_t launch_km_stop(const double *tc, size_t nc, double tol, int last, double *stop, hipStream_t s);
+
+// ---- spherical_kmeans.hip: spherical k-means on Cosine indexes (pn_spherical_kmeans_*); nothing in it
+// waits for the device.  The images and the bound are kmeans.hip's over the rows and centres NORMALISED in f64; the
+// filter takes 8 <= dim <= 304 (skm_filter_supported).
+bool skm_filter_supported(int dim);
+template <typename T>
+hipError_t launch_skm_pack_rows(const T *X, size_t n, size_t ld, int dim, const KmRowImage &r, hipStream_t s);
+template <typename T>
+hipError_t launch_skm_pack_centres(const T *centres, size_t nc, int dim, const KmCentreImage &c, hipStream_t s);
+// cand [n] <- the centre of each row's smallest key, tau [n] <- the second smallest key
+hipError_t launch_skm_filter(const KmRowImage &r, size_t n, const KmCentreImage &c, size_t nc, uint32_t *cand, float *tau,
+                             hipStream_t s);
+// the candidates' Cosine::distance in the reference's arithmetic (rnorm [n], cnorm [nc]: the norms' folds in T); proven
+// rows get their label and distance (dist nullable), the others are listed: sel[0 .. *nsel) (nsel: 8 bytes, zeroed here)
+template <typename T>
+hipError_t launch_skm_rerank(const T *X, size_t n, size_t ld, int dim, const T *rnorm, const T *centres, const T *cnorm,
+                             size_t nc, const uint32_t *cand, const float *tau, const KmRowImage &r, const KmCentreImage &c,
+                             uint32_t *sel, uint32_t *nsel, int64_t *labels, T *dist, hipStream_t s);
+// every row (sel == nullptr) or the listed rows against every centre by (signed key, centre number); a NaN key, and
+// nc == 0: label -1, distance NaN
+template <typename T>
+hipError_t launch_skm_exact(const T *X, size_t n, size_t ld, int dim, const T *rnorm, const T *centres, const T *cnorm,
+                            size_t nc, const uint32_t *sel, const uint32_t *nsel, int64_t *labels, T *dist, hipStream_t s);
+// km_update_enqueue with the spherical mean: the term of a member is x / rnorm in f64, the new centre S / sqrt(Q)
+template <typename T>
+hipError_t skm_update_enqueue(const T *X, size_t n, size_t ld, int dim, const T *rnorm, const int64_t *labels, size_t nc,
+                              void *buf, T *centres, uint64_t *counts, double tol, int last, double **stop_out,
+                              hipStream_t s);
 
 // ---- kmeans_nearest.hip: the m nearest centres of every row (pn_kmeans_nearest_*), 1 <= m <= 8, on the images and the
 // bound of kmeans.hip; nothing in it waits for the device.  The kernels carry lists of km_nearest_width(m) = 2, 4 or 8.
