@@ -68,6 +68,7 @@ HEADERS = [os.path.join(CSRC, "pn_internal.h"), os.path.join(CSRC, "bf16_launch.
            os.path.join(CSRC, "csr_splice.h"),
            os.path.join(CSRC, "host_io.h"),
            os.path.join(CSRC, "km_pack.h"),
+           os.path.join(CSRC, "km_filter.h"),
            os.path.join(CSRC, "topk_buffer.h"),
            os.path.join(CSRC, "host_tree.h"),
            os.path.join(CSRC, "union_find.h"),

@@ -46,15 +46,11 @@
 // the one fused multiply-add of the bound is written as such.
 #include "../../include/petal_mi355x.h"
 #include "pn_internal.h"
-#include "km_pack.h"
+#include "km_filter.h"  // the packing and E(x), the MFMA chain, the gathered row tile, the fold's sqrt and key
 
 namespace pn {
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // M = 3 candidates per row: with it the measured MST calls (10^5 and 10^6 rows of 16 columns, 10^5 of 128, uniform and
 // blobs, with and without cores) leave 0 to 0.47 % of their listed rows to the exact scan, at three folds
@@ -117,9 +113,6 @@ __global__ void fr_mean_kernel(const double *__restrict__ sums, size_t nblk, siz
     const float m = (float)(s / (double)n);
     mu[k] = fabsf(m) < 1.0e30f ? m : 0.0f;  // (NaN, inf: the rows are flagged by the packing anyway)
 }
-__global__ void fr_zero_kernel(unsigned long long *p, int words) {
-    if ((int)threadIdx.x < words) p[threadIdx.x] = 0ull;
-}
 
 // a32 <= xn - E in f32 (NaN for a flagged row: nothing of it is kept, and the re-rank lists it)
 __device__ __forceinline__ float fr_row_offset(double xn, double xh, double xl, double xe,
@@ -164,17 +157,7 @@ __global__ __launch_bounds__(256) void fr_filter_kernel(
     const size_t st_end = st_begin + seg_stages < n_stages ? st_begin + seg_stages : n_stages;
 
     // ---- the listed rows' images, gathered through the list (positions at and beyond nq: zeros)
-    for (int q = t; q < kFrRows * chunks; q += 256) {
-        const int rr = q / chunks, ch = q - rr * chunks;
-        u32x4 vh = {0u, 0u, 0u, 0u}, vl = {0u, 0u, 0u, 0u};
-        if (pos0 + (size_t)rr < (size_t)nq) {
-            const size_t src = (size_t)list[pos0 + rr] * (size_t)dp + (size_t)ch * 8;
-            vh = *(const u32x4 *)(img + src);
-            vl = *(const u32x4 *)(lo + src);
-        }
-        *(u32x4 *)(btile + (size_t)rr * pitch + ch * 8) = vh;
-        *(u32x4 *)(btile_lo + (size_t)rr * pitch + ch * 8) = vl;
-    }
+    km_gather_row_tile<256>(btile, btile_lo, img, lo, list, pos0, (size_t)nq, kFrRows, dp, t);
     // ---- this lane's row
     const size_t my_pos = pos0 + (size_t)(w * 32 + r);
     const bool mine = my_pos < (size_t)nq;
@@ -241,23 +224,10 @@ __global__ __launch_bounds__(256) void fr_filter_kernel(
     const uint16_t *brow_lo = btile_lo + (size_t)(w * 32 + r) * pitch + h * 8;
     auto chain = [&](size_t stage, int v) {
         const uint16_t *a0 = abuf + (size_t)(stage & 1) * 2 * srows * pitch + (size_t)(v * 32 + r) * pitch + h * 8;
-        const uint16_t *a1 = a0 + (size_t)srows * pitch;
-        f32x16 acc;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
-        for (int ks = 0; ks < ksteps; ++ks) {
-            const bf16x8 a = *(const bf16x8 *)(a0 + ks * 16);
-            const bf16x8 al = *(const bf16x8 *)(a1 + ks * 16);
-            const bf16x8 b = *(const bf16x8 *)(brow + ks * 16);
-            const bf16x8 bl = *(const bf16x8 *)(brow_lo + ks * 16);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bl, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, b, acc, 0, 0, 0);
-        }
-        return acc;
+        return km_mfma_chain(a0, a0 + (size_t)srows * pitch, brow, brow_lo, ksteps);
     };
-    // registers 4 g .. 4 g + 3 of the accumulator are the tile's rows 8 g + 4 h + 0 .. 3 (the C layout of the instruction):
-    // a lane meets its partners in ascending j, so a strict '<' on the key keeps the smaller j among equal keys
+    // registers 4 g .. 4 g + 3 of the accumulator are the tile's rows 8 g + 4 h + 0 .. 3 (km_mfma_chain): a lane meets its
+    // partners in ascending j, so a strict '<' on the key keeps the smaller j among equal keys
     auto scan = [&](const f32x16 &acc, size_t stage, int v) {
         const FrMeta<K> m = meta_at((int)(stage % 3));
         const size_t j0 = stage * (size_t)srows + (size_t)(v * 32);
@@ -320,17 +290,6 @@ __global__ __launch_bounds__(256) void fr_filter_kernel(
     }
 }
 
-template <typename T> __device__ __forceinline__ typename KeyOf<T>::type fr_dist_key(T d);
-template <> __device__ __forceinline__ uint32_t fr_dist_key<float>(float d) {
-    return d != d ? KeyOf<float>::kNaN : __float_as_uint(d);
-}
-template <> __device__ __forceinline__ uint64_t fr_dist_key<double>(double d) {
-    return d != d ? KeyOf<double>::kNaN : (uint64_t)__double_as_longlong(d);
-}
-template <typename T> __device__ __forceinline__ T fr_sqrt(T x);
-template <> __device__ __forceinline__ float fr_sqrt<float>(float x) { return sqrtf(x); }  // correctly rounded (build flags)
-template <> __device__ __forceinline__ double fr_sqrt<double>(double x) { return sqrt(x); }
-
 // ---- merge of the segments' lists, re-rank and proof: one thread per listed row.  ctr[0]: the rows listed for the exact
 // scan (sel[slot]), ctr[1]: the candidates evaluated.
 template <typename T>
@@ -385,7 +344,7 @@ __global__ __launch_bounds__(64) void fr_rerank_kernel(const T *__restrict__ X, 
                     const T sq = diff * diff;
                     sum = sum + sq;
                 }
-                K kk = fr_dist_key<T>(fr_sqrt<T>(sum));
+                K kk = km_dist_key<T>(km_sqrt<T>(sum));
                 const K cj = ckey[j];
                 kk = kk > ci ? kk : ci;
                 kk = kk > cj ? kk : cj;
@@ -473,7 +432,7 @@ template <typename T>
 hipError_t foreign_pack(const ForeignTier &t, const T *X, size_t n, size_t ld, int dim, hipStream_t s) {
     // (kernels, not memsets: the words are cleared in stream order whatever the caller's stream is captured into)
     const size_t nblk = fr_sum_blocks(n);
-    hipLaunchKernelGGL(fr_zero_kernel, dim3(1), dim3(64), 0, s, t.cc, 8);
+    km_zero_words(t.cc, 8, s);
     hipLaunchKernelGGL((fr_colsum_kernel<T>), dim3((unsigned)nblk), dim3(256), 0, s, X, n, ld, dim, t.sums);
     hipLaunchKernelGGL(fr_mean_kernel, dim3((unsigned)((dim + 63) / 64)), dim3(64), 0, s, t.sums, nblk, n, dim, t.mu);
     hipLaunchKernelGGL((km_pack_kernel<T, true>), dim3((unsigned)((t.n_img + 3) / 4)), dim3(256), 0, s, X, n, t.n_img, ld, dim,
@@ -499,7 +458,7 @@ hipError_t launch_foreign_filter(const ForeignTier &t, const T *X, size_t n, siz
     }
     const double u = sizeof(T) == 4 ? 5.9604644775390625e-08 : 1.1102230246251565e-16;
     const float shrink = (float)(1.0 - (double)(dim + 4) * u - 1.0e-6);
-    hipLaunchKernelGGL(fr_zero_kernel, dim3(1), dim3(64), 0, s, (unsigned long long *)t.ctr, 2);
+    km_zero_words(t.ctr, 2, s);
     hipLaunchKernelGGL((fr_filter_kernel<K>), dim3((unsigned)p.qt, (unsigned)p.nseg), dim3(256), lds, s, t.img, t.lo, t.cn, n,
                        t.dp, list, (int)nq, p.n_stages, p.seg_stages, comp, ckey, t.xn, t.xh, t.xl, t.xe, t.cc, shrink,
                        (K *)t.seg_key, t.seg_j, nq_pad);

@@ -5334,10 +5334,7 @@ template <typename T, bool SPH = false>
 static int km_pack_rows(const pn_index *ix, Workspace &ws, KmRowImage *rows, hipStream_t s) {
     PNCHK(ws.w_km_rows.ensure(km_row_image_bytes(ix->n, (int)ix->dim)));
     *rows = km_row_image_at(ws.w_km_rows.p, ix->n, (int)ix->dim);
-    if constexpr (SPH)
-        HIPCHK(launch_skm_pack_rows<T>((const T *)ix->d_pts, ix->n, ix->ld, (int)ix->dim, *rows, s));
-    else
-        HIPCHK(launch_km_pack_rows<T>((const T *)ix->d_pts, ix->n, ix->ld, (int)ix->dim, *rows, s));
+    HIPCHK((launch_km_pack_rows<T, SPH>((const T *)ix->d_pts, ix->n, ix->ld, (int)ix->dim, *rows, s)));
     return PN_OK;
 }
 // One assignment, in a held workspace on stream s; n >= 1.  rows: the packed rows when the filter is used, else nullptr.
@@ -5361,34 +5358,24 @@ static int km_assign_enqueue(const pn_index *ix, Workspace &ws, const KmRowImage
     uint32_t *cand = (uint32_t *)((char *)seg + seg_bytes), *sel = cand + 2 * n2;
     float *tau = (float *)(cand + n2);
     if (d_inertia && !d_dist) d_dist = own_dist;
+    KmNorms<T> norms;
     if constexpr (SPH) {
         // Cosine::distance: the centres' norms are folded once per assignment, the rows' are the index's
         T *cnorm = (T *)((char *)cand + filter_bytes);
-        const T *rnorm = (const T *)ix->d_cnorm;
         HIPCHK(launch_cosine_norms<T>(d_centres, nc, dim, (size_t)dim, cnorm, s));
-        if (filter) {
-            PNCHK(ws.w_km_cent.ensure(km_centre_image_bytes(nc, dim)));
-            const KmCentreImage ci = km_centre_image_at(ws.w_km_cent.p, nc, dim);
-            HIPCHK(launch_skm_pack_centres<T>(d_centres, nc, dim, ci, s));
-            HIPCHK(launch_skm_filter(*rows, n, ci, nc, cand, tau, s));
-            HIPCHK(launch_skm_rerank<T>(X, n, ix->ld, dim, rnorm, d_centres, cnorm, nc, cand, tau, *rows, ci, sel, nsel,
-                                        d_labels, d_dist, s));
-            HIPCHK(launch_skm_exact<T>(X, n, ix->ld, dim, rnorm, d_centres, cnorm, nc, sel, nsel, d_labels, d_dist, s));
-            if (ix->d_stats) HIPCHK(launch_radii_add_listed(nsel, ix->d_stats, s));
-        } else {
-            HIPCHK(launch_skm_exact<T>(X, n, ix->ld, dim, rnorm, d_centres, cnorm, nc, nullptr, nullptr, d_labels, d_dist, s));
-        }
-    } else if (filter) {
+        norms = KmNorms<T>{(const T *)ix->d_cnorm, cnorm};
+    }
+    if (filter) {
         PNCHK(ws.w_km_cent.ensure(km_centre_image_bytes(nc, dim)));
         const KmCentreImage ci = km_centre_image_at(ws.w_km_cent.p, nc, dim);
-        HIPCHK(launch_km_pack_centres<T>(d_centres, nc, dim, ci, s));
-        HIPCHK(launch_km_filter(*rows, n, ci, nc, cand, tau, s));
-        HIPCHK(hipMemsetAsync(nsel, 0, sizeof(uint32_t), s));
-        HIPCHK(launch_km_rerank<T>(X, n, ix->ld, dim, d_centres, nc, cand, tau, *rows, ci, sel, nsel, d_labels, d_dist, s));
-        HIPCHK(launch_km_exact<T>(X, n, ix->ld, dim, d_centres, nc, sel, nsel, d_labels, d_dist, s));
+        HIPCHK((launch_km_pack_centres<T, SPH>(d_centres, nc, dim, ci, s)));
+        HIPCHK(launch_km_filter<SPH>(*rows, n, ci, nc, cand, tau, s));
+        HIPCHK((launch_km_rerank<T, SPH>(X, n, ix->ld, dim, norms, d_centres, nc, cand, tau, *rows, ci, sel, nsel, d_labels,
+                                         d_dist, s)));
+        HIPCHK((launch_km_exact<T, SPH>(X, n, ix->ld, dim, norms, d_centres, nc, sel, nsel, d_labels, d_dist, s)));
         if (ix->d_stats) HIPCHK(launch_radii_add_listed(nsel, ix->d_stats, s));
     } else {
-        HIPCHK(launch_km_exact<T>(X, n, ix->ld, dim, d_centres, nc, nullptr, nullptr, d_labels, d_dist, s));
+        HIPCHK((launch_km_exact<T, SPH>(X, n, ix->ld, dim, norms, d_centres, nc, nullptr, nullptr, d_labels, d_dist, s)));
     }
     if (d_inertia) HIPCHK(launch_km_inertia<T>(d_labels, d_dist, n, seg, d_inertia, s, !SPH));
     std::lock_guard<std::mutex> lk(ix->sh.mu);
@@ -5449,12 +5436,8 @@ static int km_loop_enqueue(const pn_index *ix, Workspace &ws, size_t nc, double 
     PNCHK(ws.w_km_upd.ensure(km_update_bytes(n, nc, dim)));
     // one update of the centres (or, without them, the counts): the mean, or SPH the normalised sum of the directions
     auto update = [&](T *centres, uint64_t *counts, double tl, int last, double **stop_out) {
-        if constexpr (SPH)
-            return skm_update_enqueue<T>((const T *)ix->d_pts, n, ix->ld, dim, (const T *)ix->d_cnorm, d_labels, nc,
-                                         ws.w_km_upd.p, centres, counts, tl, last, stop_out, s);
-        else
-            return km_update_enqueue<T>((const T *)ix->d_pts, n, ix->ld, dim, d_labels, nc, ws.w_km_upd.p, centres, counts, tl,
-                                        last, stop_out, s);
+        return km_update_enqueue<T, SPH>((const T *)ix->d_pts, n, ix->ld, dim, SPH ? (const T *)ix->d_cnorm : nullptr, d_labels,
+                                         nc, ws.w_km_upd.p, centres, counts, tl, last, stop_out, s);
     };
     struct {
         double shift2;
@@ -5642,7 +5625,6 @@ static int kn_enqueue(const pn_index *ix, Workspace &ws, const T *d_centres, siz
         const KmCentreImage ci = km_centre_image_at(ws.w_km_cent.p, nc, dim);
         HIPCHK(launch_km_pack_centres<T>(d_centres, nc, dim, ci, s));
         HIPCHK(launch_km_nearest_filter(rows, n, ci, nc, (int)m, cand, tau, s));
-        HIPCHK(hipMemsetAsync(nsel, 0, sizeof(uint32_t), s));
         HIPCHK(launch_km_nearest_rerank<T>(X, n, ix->ld, dim, d_centres, nc, (int)m, cand, tau, rows, ci, sel, nsel, d_labels,
                                            d_dist, s));
         HIPCHK(launch_km_nearest_exact<T>(X, n, ix->ld, dim, d_centres, nc, (int)m, sel, nsel, d_labels, d_dist, s));

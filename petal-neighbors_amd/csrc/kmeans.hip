@@ -32,35 +32,11 @@
 // This translation unit is compiled with -ffp-contract=off: every operation outside the MFMA is plain IEEE, unfused.
 #include "../../include/petal_mi355x.h"
 #include "pn_internal.h"
-#include "km_pack.h"  // the packing kernel, the constants of the bound and E(x) (shared with foreign.hip)
+#include "km_filter.h"  // the packing and E(x), the MFMA chain, the proof, the kernels and launchers shared with the Cosine twin
 
 namespace pn {
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kKmLabelRows = 64, kKmLabelPitch = 65;
-
-__device__ __forceinline__ void km_lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-template <typename T>
-__device__ __forceinline__ T km_sqrt(T x);
-template <>
-__device__ __forceinline__ float km_sqrt<float>(float x) { return sqrtf(x); }  // correctly rounded (build flags)
-template <>
-__device__ __forceinline__ double km_sqrt<double>(double x) { return sqrt(x); }
-
-template <typename T>
-__device__ __forceinline__ typename KeyOf<T>::type km_key(T d) {
-    using K = typename KeyOf<T>::type;
-    if constexpr (sizeof(T) == 4)
-        return d != d ? KeyOf<T>::kNaN : (K)__float_as_uint(d);
-    else
-        return d != d ? KeyOf<T>::kNaN : (K)__double_as_longlong(d);
-}
 
 // ---- the filter.  A workgroup of WAVES waves takes 32 WAVES rows, a wave 32 of them: the rows' two bf16 images lie in LDS
 // ([2][rows][dp + 8], the 16 bytes of padding spread the rows over the banks) and are the B operands of
@@ -90,13 +66,7 @@ __global__ __launch_bounds__(64 * WAVES) void km_assign_filter_kernel(const uint
     uint16_t *tile = (uint16_t *)km_smem, *tile_lo = tile + (size_t)kRows * pitch;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, r = lane & 31, h = lane >> 5;
     const size_t row0 = (size_t)blockIdx.x * kRows;  // (the images have whole tiles of 128 rows: rows beyond n are zeros)
-    const int chunks = dp >> 3;                      // 16-byte chunks per row
-    for (int q = t; q < kRows * chunks; q += 64 * WAVES) {
-        const int rr = q / chunks, ch = q - rr * chunks;
-        const size_t src = (row0 + (size_t)rr) * (size_t)dp + (size_t)ch * 8;
-        *(u32x4 *)(tile + (size_t)rr * pitch + ch * 8) = *(const u32x4 *)(ximg + src);
-        *(u32x4 *)(tile_lo + (size_t)rr * pitch + ch * 8) = *(const u32x4 *)(xlo + src);
-    }
+    km_load_row_tile<64 * WAVES>(tile, tile_lo, ximg, xlo, row0, kRows, dp, t);
     __syncthreads();
     const uint16_t *brow = tile + (size_t)(w * 32 + r) * pitch + h * 8;
     const uint16_t *brow_lo = tile_lo + (size_t)(w * 32 + r) * pitch + h * 8;
@@ -113,22 +83,9 @@ __global__ __launch_bounds__(64 * WAVES) void km_assign_filter_kernel(const uint
     }
     for (size_t ct = 0; ct < nc_pad; ct += kKmCentreTile) {
         const size_t aoff = (ct + (size_t)r) * (size_t)dp + h * 8;
-        const uint16_t *arow = cimg + aoff, *arow_lo = clo + aoff;
-        f32x16 acc;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
-        for (int ks = 0; ks < ksteps; ++ks) {
-            const bf16x8 a = *(const bf16x8 *)(arow + ks * 16);
-            const bf16x8 al = *(const bf16x8 *)(arow_lo + ks * 16);
-            const bf16x8 b = *(const bf16x8 *)(brow + ks * 16);
-            const bf16x8 bl = *(const bf16x8 *)(brow_lo + ks * 16);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bl, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, b, acc, 0, 0, 0);
-        }
+        const f32x16 acc = km_mfma_chain(cimg + aoff, clo + aoff, brow, brow_lo, ksteps);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            // registers 4 g .. 4 g + 3 are the centres ct + 8 g + 4 h + 0 .. 3 (the C layout of the instruction)
             const size_t cb = ct + (size_t)(8 * g + 4 * h);
             const float4 cn4 = *(const float4 *)(cn + cb);
             const float cnv[4] = {cn4.x, cn4.y, cn4.z, cn4.w};
@@ -136,11 +93,8 @@ __global__ __launch_bounds__(64 * WAVES) void km_assign_filter_kernel(const uint
             for (int j = 0; j < 4; ++j) {
                 const float key = cnv[j] - 2.0f * acc[4 * g + j];
                 if (BOUNDS) {
-                    if (my_row < n && cb + j < nc) {
-                        // (pushed down by the roundings of its own evaluation, as the proof's tau' is)
-                        const double lb = (xnr + (double)key) - slack;
-                        bounds[my_row * nc + cb + j] = lb - (xnr + fabs((double)key) + slack) * 1.7763568394002505e-15;
-                    }
+                    // (the proof's tau' with this pair's key in the place of tau)
+                    if (my_row < n && cb + j < nc) bounds[my_row * nc + cb + j] = km_tau_floor(xnr, (double)key, slack);
                 } else if (key < k2) {
                     if (key < k1) {
                         k2 = k1;
@@ -173,169 +127,31 @@ __global__ __launch_bounds__(64 * WAVES) void km_assign_filter_kernel(const uint
     }
 }
 
-// ---- staging of a wave's 64 rows, transposed, in LDS (ms_labels_kernel says why); sel: the listed rows
+// ---- the Euclidean metric of km_filter.h's kernels: the fold of ms_labels_kernel, (c - x)^2 summed in column order and
+// the correctly rounded sqrt; keys are the bits of the distance.  A row is PROVEN by km_euclid_proven.  m = 1 candidate:
+// a row without a second centre (tau = +inf) is proven by its candidate alone.
 template <typename T>
-__device__ __forceinline__ void km_stage_rows(const T *__restrict__ X, size_t ld, int dim, const uint32_t *__restrict__ sel,
-                                              size_t first, int rows, int lane, T *__restrict__ tile) {
-    for (int r = 0; r < rows; ++r) {
-        const size_t i = sel ? (size_t)sel[first + r] : first + (size_t)r;
-        for (int k = lane; k < dim; k += kKmLabelRows) tile[k * kKmLabelPitch + r] = X[i * ld + k];
-    }
-    __syncthreads();
-}
-
-// ---- the exact kernel: the fold of ms_labels_kernel with a distance output and an optional row list.  sel / nsel
-// (nullable together): thread j of the launch answers row sel[j], j < *nsel (the grid is sized for n).
-template <typename T, bool STAGED>
-__global__ __launch_bounds__(kKmLabelRows) void km_exact_kernel(const T *__restrict__ X, size_t n, size_t ld, int dim,
-                                                                const T *__restrict__ centres, size_t nc,
-                                                                const uint32_t *__restrict__ sel,
-                                                                const uint32_t *__restrict__ nsel,
-                                                                int64_t *__restrict__ labels, T *__restrict__ dist) {
-#pragma clang fp contract(off)
+struct KmMetric<T, false> {
     using K = typename KeyOf<T>::type;
-    extern __shared__ __align__(16) unsigned char km_smem[];
-    T *tile = (T *)km_smem;
-    const int lane = threadIdx.x;
-    const size_t count = sel ? (size_t)*nsel : n;
-    const size_t first = (size_t)blockIdx.x * kKmLabelRows, j = first + lane;
-    if (first >= count) return;  // (the whole workgroup)
-    if (STAGED) {
-        const int rows = count - first < (size_t)kKmLabelRows ? (int)(count - first) : kKmLabelRows;
-        km_stage_rows<T>(X, ld, dim, sel, first, rows, lane, tile);
+    static constexpr K kNoKey = KeyOf<T>::kMax;
+    static __device__ __forceinline__ T no_dist() { return (T)0; }
+    static __device__ __forceinline__ T term(T c, T x) {
+        const T diff = c - x;
+        return diff * diff;
     }
-    if (j >= count) return;
-    const size_t i = sel ? (size_t)sel[j] : j;
-    const T *row = X + i * ld;
-    K best = KeyOf<T>::kMax;
-    int64_t lab = -1;
-    T best_d = (T)0;
-    for (size_t c = 0; c < nc; c += 4) {
-        const T *cp[4];
-        T sum[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            cp[u] = centres + (c + u < nc ? c + u : nc - 1) * (size_t)dim;  // (past the end: the last centre again, not used)
-            sum[u] = (T)0;
-        }
-        for (int k = 0; k < dim; ++k) {
-            const T x = STAGED ? tile[k * kKmLabelPitch + lane] : row[k];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const T diff = cp[u][k] - x;
-                const T sq = diff * diff;
-                sum[u] = sum[u] + sq;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const T d = km_sqrt<T>(sum[u]);
-            const K key = km_key<T>(d);
-            if (c + u < nc && key < best) {
-                best = key;
-                lab = (int64_t)(c + u);
-                best_d = d;
-            }
-        }
+    static __device__ __forceinline__ T row_norm(const KmNorms<T> &, size_t) { return (T)0; }
+    static __device__ __forceinline__ T finish(T sum, const KmNorms<T> &, size_t, T) { return km_sqrt<T>(sum); }
+    static __device__ __forceinline__ K key(T d) { return km_dist_key<T>(d); }
+    static __device__ __forceinline__ bool admits(const float *, size_t) { return true; }
+    template <typename TauFloor>
+    static __device__ __forceinline__ bool proven(T d, float tau, int dim, TauFloor tau_floor) {
+        return km_euclid_proven<T>(key(d), tau, dim, tau_floor);
     }
-    labels[i] = lab;
-    if (dist) dist[i] = best_d;
-}
-
-// the proof's right-hand side: everything at or below it may still round to d (key kk, finite) and tie (select.hip)
-template <typename T> __device__ __forceinline__ double km_proof_rhs(typename KeyOf<T>::type kk);
-template <> __device__ __forceinline__ double km_proof_rhs<float>(uint32_t kk) {
-    const double dk = (double)__uint_as_float(kk), dn = (double)__uint_as_float(kk + 1);  // succ(d): the next float up
-    const double mid = 0.5 * (dk + dn);
-    return mid * mid * (1.0 + 4.5e-16);
-}
-template <> __device__ __forceinline__ double km_proof_rhs<double>(uint64_t kk) {
-    const double dn = __longlong_as_double((long long)(kk + 1));
-    return dn * dn * (1.0 + 4.440892098500626e-16);
-}
-
-// ---- re-rank and proof: one thread per row, the wave's rows staged as above.  The candidate's distance in the
-// reference's fold; proven rows are answered here, the others are listed: slot = atomicAdd(nsel), sel[slot] = row.
-template <typename T, bool STAGED>
-__global__ __launch_bounds__(kKmLabelRows) void km_rerank_kernel(const T *__restrict__ X, size_t n, size_t ld, int dim,
-                                                                 const T *__restrict__ centres, size_t nc,
-                                                                 const uint32_t *__restrict__ cand,
-                                                                 const float *__restrict__ tau,
-                                                                 const double *__restrict__ xn,
-                                                                 const float *__restrict__ xh,
-                                                                 const float *__restrict__ xl,
-                                                                 const float *__restrict__ xe,
-                                                                 const unsigned long long *__restrict__ cc,
-                                                                 uint32_t *__restrict__ sel, uint32_t *__restrict__ nsel,
-                                                                 int64_t *__restrict__ labels, T *__restrict__ dist) {
-#pragma clang fp contract(off)
-    using K = typename KeyOf<T>::type;
-    extern __shared__ __align__(16) unsigned char km_smem[];
-    T *tile = (T *)km_smem;
-    const int lane = threadIdx.x;
-    const size_t first = (size_t)blockIdx.x * kKmLabelRows, i = first + lane;
-    if (STAGED) {
-        const int rows = n - first < (size_t)kKmLabelRows ? (int)(n - first) : kKmLabelRows;
-        km_stage_rows<T>(X, ld, dim, nullptr, first, rows, lane, tile);
-    }
-    if (i >= n) return;
-    const uint32_t c = cand[i];
-    const double xnr = xn[i];
-    bool ok = cc[4] == 0 && xnr == xnr && (size_t)c < nc;
-    T d = (T)0;
-    if (ok) {
-        const T *cp = centres + (size_t)c * (size_t)dim;
-        const T *row = X + i * ld;
-        T sum = (T)0;
-        for (int k = 0; k < dim; ++k) {
-            const T x = STAGED ? tile[k * kKmLabelPitch + lane] : row[k];
-            const T diff = cp[k] - x;
-            const T sq = diff * diff;
-            sum = sum + sq;
-        }
-        d = km_sqrt<T>(sum);
-        const K kk = km_key<T>(d);
-        constexpr K kInf = sizeof(T) == 4 ? (K)0x7F800000u : (K)0x7FF0000000000000ull;
-        const float tv = tau[i];
-        if (kk >= kInf || tv != tv) {
-            ok = false;  // an infinite or NaN distance: the exact kernel orders it
-        } else if (tv < __uint_as_float(0x7F800000u)) {
-            const double slack = km_row_slack((double)xh[i], (double)xl[i], (double)xe[i], cc);
-            // tau' = xn + tau - E, pushed down by the roundings of its own evaluation
-            double lb = (xnr + (double)tv) - slack;
-            lb = lb - (xnr + fabs((double)tv) + slack) * 1.7763568394002505e-15;  // 2^-49
-            if constexpr (sizeof(T) == 4)
-                lb = lb * (1.0 - (double)(dim + 4) * 5.9604644775390625e-08) - 1e-37;
-            else
-                lb = lb * (1.0 - (double)(dim + 4) * 1.1102230246251565e-16) * (1.0 - 8.881784197001252e-16) - 1e-300;
-            ok = lb > km_proof_rhs<T>(kk);
-        }  // (tau = +inf: no other centre exists)
-    }
-    if (ok) {
-        labels[i] = (int64_t)c;
-        if (dist) dist[i] = d;
-    } else {
-        const uint32_t slot = atomicAdd(nsel, 1u);
-        sel[slot] = (uint32_t)i;  // (slot < n: every row is listed at most once)
-    }
-}
-
-// nc == 0: every label -1, every distance NaN
-template <typename T>
-__global__ __launch_bounds__(256) void km_none_kernel(size_t n, int64_t *__restrict__ labels, T *__restrict__ dist) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    labels[i] = -1;
-    if (dist) {
-        if constexpr (sizeof(T) == 4)
-            dist[i] = __uint_as_float(0x7FC00000u);
-        else
-            dist[i] = __longlong_as_double(0x7FF8000000000000ll);
-    }
-}
+    // One wave per centre: the segments in order, the division, the move; tc[c] <- the sum of the squared moves
+    static void launch_move(const KmMembers &m, size_t nc, int dim, T *centres, hipStream_t s);
+};
 
 // ---- SUM4096 of the squared distances: one wave per segment of 4096 rows, then one thread over the segments
-constexpr int kKmSeg = 4096;
 // SQUARED: the term of a member is d * d (k-means); else d itself (spherical k-means)
 template <typename T, bool SQUARED>
 __global__ __launch_bounds__(64) void km_inertia_seg_kernel(const int64_t *__restrict__ labels, const T *__restrict__ dist,
@@ -404,60 +220,6 @@ __global__ __launch_bounds__(256) void km_counts_kernel(const uint64_t *__restri
     const uint64_t m = off[c + 1] - off[c];
     if (nseg) nseg[c] = (uint32_t)((m + kKmSeg - 1) / kKmSeg);
     if (counts) counts[c] = m;
-}
-// One wave per (cluster, segment): workgroup b is segment b of the enumeration seg_off (the exclusive scan of nseg);
-// the grid is sized for the most segments a call can have and the surplus exits.  Lane l strides the segment's members
-// by 64 and reads COLS consecutive columns of each row; the 64 partials of a column are transposed through LDS and lane c
-// folds column c's in lane order (ms_step_kernel).  segsum [segments][dim].
-template <typename T, int COLS>
-__global__ __launch_bounds__(64) void km_segment_sums_kernel(const uint64_t *__restrict__ key,
-                                                             const uint64_t *__restrict__ off,
-                                                             const uint64_t *__restrict__ seg_off, size_t nc,
-                                                             const T *__restrict__ X, size_t ld, int dim,
-                                                             double *__restrict__ segsum) {
-#pragma clang fp contract(off)
-    __shared__ double s_part[COLS][65];
-    const int lane = threadIdx.x;
-    const uint64_t b = blockIdx.x;
-    if (b >= seg_off[nc]) return;
-    // the cluster: the last c with seg_off[c] <= b (clusters without members have no segment and are skipped by the search)
-    size_t lo = 0, hi = nc;
-    while (hi - lo > 1) {
-        const size_t mid = lo + (hi - lo) / 2;
-        if (seg_off[mid] <= b)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    const size_t c = lo;
-    const uint64_t s = b - seg_off[c];
-    const uint64_t beg = off[c] + s * kKmSeg, rest = off[c + 1] - beg;
-    const uint64_t len = rest < (uint64_t)kKmSeg ? rest : (uint64_t)kKmSeg;
-    for (int c0 = 0; c0 < dim; c0 += COLS) {
-        double P[COLS];
-#pragma unroll
-        for (int k = 0; k < COLS; ++k) P[k] = 0.0;
-        for (uint64_t j = lane; j < len; j += 64) {
-            // (c0 + COLS <= ld: the row's padding is read, and never used)
-            const T *__restrict__ row = X + (size_t)(uint32_t)key[beg + j] * ld + c0;
-            T v[COLS];
-#pragma unroll
-            for (int k = 0; k < COLS; ++k) v[k] = row[k];
-#pragma unroll
-            for (int k = 0; k < COLS; ++k) P[k] = P[k] + (double)v[k];
-        }
-#pragma unroll
-        for (int k = 0; k < COLS; ++k) s_part[k][lane] = P[k];
-        km_lds_fence();
-        const int col = c0 + lane;
-        if (lane < COLS && col < dim) {
-            double S = s_part[lane][0];
-#pragma unroll 9
-            for (int l = 1; l < 64; ++l) S = S + s_part[lane][l];
-            segsum[b * (uint64_t)dim + col] = S;
-        }
-        km_lds_fence();
-    }
 }
 // One wave per centre: the segments in order, the division, the move; tc[c] <- the sum of the squared moves in the
 // 64-partial shape (column col to partial col mod 64).  A centre without members is unchanged.
@@ -558,25 +320,6 @@ KmCentreImage km_centre_image_at(void *buf, size_t nc, int dim) {
     return c;
 }
 
-template <typename T>
-hipError_t launch_km_pack_rows(const T *X, size_t n, size_t ld, int dim, const KmRowImage &r, hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL((km_pack_kernel<T, true>), dim3((unsigned)((r.n_img + 3) / 4)), dim3(256), 0, s, X, n, r.n_img, ld,
-                       dim, r.dp, r.img, r.lo, r.xn, r.xh, r.xl, r.xe, (float *)nullptr, (unsigned long long *)nullptr,
-                       (const float *)nullptr);
-    return hipGetLastError();
-}
-template <typename T>
-hipError_t launch_km_pack_centres(const T *centres, size_t nc, int dim, const KmCentreImage &c, hipStream_t s) {
-    const int dp = (dim + 15) / 16 * 16;
-    hipError_t e = hipMemsetAsync(c.cc, 0, 8 * sizeof(unsigned long long), s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((km_pack_kernel<T, false>), dim3((unsigned)((c.nc_pad + 3) / 4)), dim3(256), 0, s, centres, nc,
-                       c.nc_pad, (size_t)dim, dim, dp, c.img, c.lo, (double *)nullptr, (float *)nullptr, (float *)nullptr,
-                       (float *)nullptr, c.cn, c.cc, (const float *)nullptr);
-    return hipGetLastError();
-}
-
 // the two instantiations of a launch: four waves per workgroup up to dp = 256, two beyond
 template <bool BOUNDS>
 static hipError_t km_filter_launch(const KmRowImage &r, size_t n, const KmCentreImage &c, size_t nc, uint32_t *cand,
@@ -602,46 +345,14 @@ static hipError_t km_filter_launch(const KmRowImage &r, size_t n, const KmCentre
                            c.cn, nc, c.nc_pad, cand, tau, r.xn, r.xh, r.xl, r.xe, c.cc, bounds);
     return hipGetLastError();
 }
-hipError_t launch_km_filter(const KmRowImage &r, size_t n, const KmCentreImage &c, size_t nc, uint32_t *cand, float *tau,
-                            hipStream_t s) {
+template <>
+hipError_t launch_km_filter<false>(const KmRowImage &r, size_t n, const KmCentreImage &c, size_t nc, uint32_t *cand,
+                                   float *tau, hipStream_t s) {
     return km_filter_launch<false>(r, n, c, nc, cand, tau, nullptr, s);
 }
 hipError_t launch_km_bounds(const KmRowImage &r, size_t n, const KmCentreImage &c, size_t nc, double *bounds,
                             hipStream_t s) {
     return km_filter_launch<true>(r, n, c, nc, nullptr, nullptr, bounds, s);
-}
-
-template <typename T>
-hipError_t launch_km_rerank(const T *X, size_t n, size_t ld, int dim, const T *centres, size_t nc, const uint32_t *cand,
-                            const float *tau, const KmRowImage &r, const KmCentreImage &c, uint32_t *sel, uint32_t *nsel,
-                            int64_t *labels, T *dist, hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    const dim3 grid((unsigned)((n + kKmLabelRows - 1) / kKmLabelRows)), blk(kKmLabelRows);
-    const size_t tile = (size_t)dim * kKmLabelPitch * sizeof(T);
-    if (tile <= 64 * 1024)
-        hipLaunchKernelGGL((km_rerank_kernel<T, true>), grid, blk, tile, s, X, n, ld, dim, centres, nc, cand, tau, r.xn, r.xh,
-                           r.xl, r.xe, c.cc, sel, nsel, labels, dist);
-    else
-        hipLaunchKernelGGL((km_rerank_kernel<T, false>), grid, blk, 0, s, X, n, ld, dim, centres, nc, cand, tau, r.xn, r.xh,
-                           r.xl, r.xe, c.cc, sel, nsel, labels, dist);
-    return hipGetLastError();
-}
-
-template <typename T>
-hipError_t launch_km_exact(const T *X, size_t n, size_t ld, int dim, const T *centres, size_t nc, const uint32_t *sel,
-                           const uint32_t *nsel, int64_t *labels, T *dist, hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    if (nc == 0) {
-        hipLaunchKernelGGL((km_none_kernel<T>), km_grid(n), dim3(256), 0, s, n, labels, dist);
-        return hipGetLastError();
-    }
-    const dim3 grid((unsigned)((n + kKmLabelRows - 1) / kKmLabelRows)), blk(kKmLabelRows);
-    const size_t tile = (size_t)dim * kKmLabelPitch * sizeof(T);
-    if (tile <= 64 * 1024)
-        hipLaunchKernelGGL((km_exact_kernel<T, true>), grid, blk, tile, s, X, n, ld, dim, centres, nc, sel, nsel, labels, dist);
-    else  // (rows too long for LDS: read in place)
-        hipLaunchKernelGGL((km_exact_kernel<T, false>), grid, blk, 0, s, X, n, ld, dim, centres, nc, sel, nsel, labels, dist);
-    return hipGetLastError();
 }
 
 size_t km_inertia_bytes(size_t n) { return ((n + kKmSeg - 1) / kKmSeg + 1) * sizeof(double); }
@@ -665,8 +376,6 @@ size_t km_update_bytes(size_t n, size_t nc, int dim) {
     return (2 * sort_key_pair_len(n) + 3 * nc + 2 + (nc / 4096 + 2) + 2 + km_max_segments(n, nc) * (size_t)dim) * 8 +
            round_up(nc, (size_t)2) * 4;
 }
-// labels [n] -> the members' lists, the counts (nullable) and, with centres != nullptr, one update of the centres in
-// place; stop_out (device, 16 bytes): {shift2, the stop word}
 // the front half of an update, shared with spherical_kmeans.hip: the sort, the offsets, the counts and, with segments,
 // the (cluster, segment) enumeration; m <- where the parts of buf are
 hipError_t km_members_enqueue(const int64_t *labels, size_t n, size_t nc, int dim, void *buf, bool segments,
@@ -691,38 +400,14 @@ hipError_t launch_km_stop(const double *tc, size_t nc, double tol, int last, dou
     return hipGetLastError();
 }
 template <typename T>
-hipError_t km_update_enqueue(const T *X, size_t n, size_t ld, int dim, const int64_t *labels, size_t nc, void *buf,
-                             T *centres, uint64_t *counts, double tol, int last, double **stop_out, hipStream_t s) {
-    KmMembers m;
-    const hipError_t e = km_members_enqueue(labels, n, nc, dim, buf, centres != nullptr, counts, &m, s);
-    if (e != hipSuccess) return e;
-    const uint64_t *key = m.key, *off = m.off, *seg_off = m.seg_off;
-    double *tc = m.tc, *stop = m.stop, *segsum = m.segsum;
-    if (stop_out) *stop_out = stop;
-    if (!centres) return hipGetLastError();
-    const dim3 grid((unsigned)km_max_segments(n, nc));
-    if (ld % 16 == 0)
-        hipLaunchKernelGGL((km_segment_sums_kernel<T, 16>), grid, dim3(64), 0, s, key, off, seg_off, nc, X, ld, dim, segsum);
-    else
-        hipLaunchKernelGGL((km_segment_sums_kernel<T, 8>), grid, dim3(64), 0, s, key, off, seg_off, nc, X, ld, dim, segsum);
-    hipLaunchKernelGGL((km_move_kernel<T>), dim3((unsigned)nc), dim3(64), 0, s, off, seg_off, segsum, dim, centres, tc);
-    hipLaunchKernelGGL(km_stop_kernel, dim3(1), dim3(64), 0, s, tc, nc, tol, last, stop);
-    return hipGetLastError();
+void KmMetric<T, false>::launch_move(const KmMembers &m, size_t nc, int dim, T *centres, hipStream_t s) {
+    hipLaunchKernelGGL((km_move_kernel<T>), dim3((unsigned)nc), dim3(64), 0, s, m.off, m.seg_off, m.segsum, dim, centres, m.tc);
 }
 
-#define PN_KM_INSTANTIATE(T)                                                                                                 \
-    template hipError_t launch_km_pack_rows<T>(const T *, size_t, size_t, int, const KmRowImage &, hipStream_t);             \
-    template hipError_t launch_km_pack_centres<T>(const T *, size_t, int, const KmCentreImage &, hipStream_t);               \
-    template hipError_t launch_km_rerank<T>(const T *, size_t, size_t, int, const T *, size_t, const uint32_t *,             \
-                                            const float *, const KmRowImage &, const KmCentreImage &, uint32_t *,            \
-                                            uint32_t *, int64_t *, T *, hipStream_t);                                        \
-    template hipError_t launch_km_exact<T>(const T *, size_t, size_t, int, const T *, size_t, const uint32_t *,              \
-                                           const uint32_t *, int64_t *, T *, hipStream_t);                                   \
-    template hipError_t launch_km_inertia<T>(const int64_t *, const T *, size_t, void *, double *, hipStream_t, bool);       \
-    template hipError_t km_update_enqueue<T>(const T *, size_t, size_t, int, const int64_t *, size_t, void *, T *,           \
-                                             uint64_t *, double, int, double **, hipStream_t);
-PN_KM_INSTANTIATE(float)
-PN_KM_INSTANTIATE(double)
+PN_KM_INSTANTIATE(float, false)
+PN_KM_INSTANTIATE(double, false)
 #undef PN_KM_INSTANTIATE
+template hipError_t launch_km_inertia<float>(const int64_t *, const float *, size_t, void *, double *, hipStream_t, bool);
+template hipError_t launch_km_inertia<double>(const int64_t *, const double *, size_t, void *, double *, hipStream_t, bool);
 
 }  // namespace pn

@@ -22,36 +22,16 @@
 // This translation unit is compiled with -ffp-contract=off: every operation outside the MFMA is plain IEEE, unfused.
 #include "../../include/petal_mi355x.h"
 #include "pn_internal.h"
-#include "km_pack.h"  // km_row_slack and the constants of the bound
+#include "km_filter.h"  // the MFMA chain, the row tile, the fold's helpers and the proof
 
 namespace pn {
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kKnRows = 64, kKnPitch = 65;  // the re-rank's and the exact kernel's rows per workgroup, transposed in LDS
 constexpr int kKnCentreTile = 32, kKnMaxDp = 320, kKnFourWaveDp = 240;
 constexpr size_t kKnLdsMax = 160 * 1024;
 constexpr uint32_t kKnNone = 0xFFFFFFFFu;
 
-template <typename T>
-__device__ __forceinline__ T kn_sqrt(T x);
-template <>
-__device__ __forceinline__ float kn_sqrt<float>(float x) { return sqrtf(x); }  // correctly rounded (build flags)
-template <>
-__device__ __forceinline__ double kn_sqrt<double>(double x) { return sqrt(x); }
-
-template <typename T>
-__device__ __forceinline__ typename KeyOf<T>::type kn_key(T d) {
-    using K = typename KeyOf<T>::type;
-    if constexpr (sizeof(T) == 4)
-        return d != d ? KeyOf<T>::kNaN : (K)__float_as_uint(d);
-    else
-        return d != d ? KeyOf<T>::kNaN : (K)__double_as_longlong(d);
-}
 // the distance of a key (a NaN comes back as the canonical one)
 __device__ __forceinline__ float kn_dist(uint32_t k) { return __uint_as_float(k); }
 __device__ __forceinline__ double kn_dist(uint64_t k) { return __longlong_as_double((long long)k); }
@@ -98,12 +78,7 @@ __global__ __launch_bounds__(64 * WAVES) void km_nearest_filter_kernel(const uin
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, r = lane & 31, h = lane >> 5;
     const size_t row0 = (size_t)blockIdx.x * kRows;  // (the images have whole tiles of 128 rows: rows beyond n are zeros)
     const int chunks = dp >> 3, half = 32 * chunks, total = 64 * chunks;
-    for (int q = t; q < kRows * chunks; q += kThreads) {
-        const int rr = q / chunks, ch = q - rr * chunks;
-        const size_t src = (row0 + (size_t)rr) * (size_t)dp + (size_t)ch * 8;
-        *(u32x4 *)(tile + (size_t)rr * pitch + ch * 8) = *(const u32x4 *)(ximg + src);
-        *(u32x4 *)(tile_lo + (size_t)rr * pitch + ch * 8) = *(const u32x4 *)(xlo + src);
-    }
+    km_load_row_tile<kThreads>(tile, tile_lo, ximg, xlo, row0, kRows, dp, t);
     // this thread's chunks of a centre tile: chunk q of the 64 image rows [hi 0 .. 31 | lo 0 .. 31] lies at q * 8 of the
     // packed tile (whole rows, contiguous) and at (q + q / chunks) * 8 of a buffer (the pitch)
     int dst[kPre];
@@ -147,22 +122,9 @@ __global__ __launch_bounds__(64 * WAVES) void km_nearest_filter_kernel(const uin
         const bool more = ct + kKnCentreTile < nc_pad;
         if (more) fetch(ct + kKnCentreTile);
         const uint16_t *arow = cbuf + (size_t)cur * cbuf_len + (size_t)r * pitch + h * 8;
-        const uint16_t *arow_lo = arow + (size_t)32 * pitch;
-        f32x16 acc;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
-        for (int ks = 0; ks < ksteps; ++ks) {
-            const bf16x8 a = *(const bf16x8 *)(arow + ks * 16);
-            const bf16x8 al = *(const bf16x8 *)(arow_lo + ks * 16);
-            const bf16x8 b = *(const bf16x8 *)(brow + ks * 16);
-            const bf16x8 bl = *(const bf16x8 *)(brow_lo + ks * 16);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bl, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, b, acc, 0, 0, 0);
-        }
+        const f32x16 acc = km_mfma_chain(arow, arow + (size_t)32 * pitch, brow, brow_lo, ksteps);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            // registers 4 g .. 4 g + 3 are the centres ct + 8 g + 4 h + 0 .. 3 (the C layout of the instruction)
             const size_t cb = ct + (size_t)(8 * g + 4 * h);
             const float4 cn4 = *(const float4 *)(cn + cb);
             const float cnv[4] = {cn4.x, cn4.y, cn4.z, cn4.w};
@@ -202,17 +164,6 @@ __global__ __launch_bounds__(64 * WAVES) void km_nearest_filter_kernel(const uin
     }
 }
 
-// ---- staging of a wave's 64 rows, transposed, in LDS (ms_labels_kernel says why); sel: the listed rows
-template <typename T>
-__device__ __forceinline__ void kn_stage_rows(const T *__restrict__ X, size_t ld, int dim, const uint32_t *__restrict__ sel,
-                                              size_t first, int rows, int lane, T *__restrict__ tile) {
-    for (int r = 0; r < rows; ++r) {
-        const size_t i = sel ? (size_t)sel[first + r] : first + (size_t)r;
-        for (int k = lane; k < dim; k += kKnRows) tile[k * kKnPitch + r] = X[i * ld + k];
-    }
-    __syncthreads();
-}
-
 // slot j of a row's answer; id 0xFFFFFFFF: there is no such centre (label -1, NaN)
 template <typename T>
 __device__ __forceinline__ void kn_write(int64_t *__restrict__ labels, T *__restrict__ dist, size_t at, uint32_t id,
@@ -226,7 +177,7 @@ __device__ __forceinline__ void kn_write(int64_t *__restrict__ labels, T *__rest
 // launch answers row sel[j], j < *nsel (the grid is sized for n).  labels / dist [n][m], m <= M; slots at and beyond nc:
 // -1 and NaN (nc == 0: every slot).
 template <typename T, int M>
-__global__ __launch_bounds__(kKnRows) void km_nearest_exact_kernel(const T *__restrict__ X, size_t n, size_t ld, int dim,
+__global__ __launch_bounds__(kKmLabelRows) void km_nearest_exact_kernel(const T *__restrict__ X, size_t n, size_t ld, int dim,
                                                                    const T *__restrict__ centres, size_t nc, int m,
                                                                    int staged, const uint32_t *__restrict__ sel,
                                                                    const uint32_t *__restrict__ nsel,
@@ -237,11 +188,11 @@ __global__ __launch_bounds__(kKnRows) void km_nearest_exact_kernel(const T *__re
     T *tile = (T *)kn_smem;
     const int lane = threadIdx.x;
     const size_t count = sel ? (size_t)*nsel : n;
-    const size_t first = (size_t)blockIdx.x * kKnRows, j = first + lane;
+    const size_t first = (size_t)blockIdx.x * kKmLabelRows, j = first + lane;
     if (first >= count) return;  // (the whole workgroup)
     if (staged) {
-        const int rows = count - first < (size_t)kKnRows ? (int)(count - first) : kKnRows;
-        kn_stage_rows<T>(X, ld, dim, sel, first, rows, lane, tile);
+        const int rows = count - first < (size_t)kKmLabelRows ? (int)(count - first) : kKmLabelRows;
+        km_stage_rows<T>(X, ld, dim, sel, first, rows, lane, tile);
     }
     if (j >= count) return;
     const size_t i = sel ? (size_t)sel[j] : j;
@@ -264,7 +215,7 @@ __global__ __launch_bounds__(kKnRows) void km_nearest_exact_kernel(const T *__re
         // (one loop per source of the row, chosen outside it)
         auto fold = [&](auto in_lds) {
             for (int k = 0; k < dim; ++k) {
-                const T x = decltype(in_lds)::value ? tile[k * kKnPitch + lane] : row[k];
+                const T x = decltype(in_lds)::value ? tile[k * kKmLabelPitch + lane] : row[k];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const T diff = cp[u][k] - x;
@@ -279,7 +230,7 @@ __global__ __launch_bounds__(kKnRows) void km_nearest_exact_kernel(const T *__re
             fold(std::false_type{});
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const K kk = kn_key<T>(kn_sqrt<T>(sum[u]));
+            const K kk = km_dist_key<T>(km_sqrt<T>(sum[u]));
             if (c + u < nc && kk < key[M - 1]) kn_insert<K, M, M>(key, id, kk, (uint32_t)(c + u));
         }
     }
@@ -288,24 +239,12 @@ __global__ __launch_bounds__(kKnRows) void km_nearest_exact_kernel(const T *__re
         if (s < m) kn_write<T>(labels, dist, i * (size_t)m + s, id[s], key[s]);
 }
 
-// the proof's right-hand side: everything at or below it may still round to d (key kk, finite) and tie (select.hip)
-template <typename T> __device__ __forceinline__ double kn_proof_rhs(typename KeyOf<T>::type kk);
-template <> __device__ __forceinline__ double kn_proof_rhs<float>(uint32_t kk) {
-    const double dk = (double)__uint_as_float(kk), dn = (double)__uint_as_float(kk + 1);  // succ(d): the next float up
-    const double mid = 0.5 * (dk + dn);
-    return mid * mid * (1.0 + 4.5e-16);
-}
-template <> __device__ __forceinline__ double kn_proof_rhs<double>(uint64_t kk) {
-    const double dn = __longlong_as_double((long long)(kk + 1));
-    return dn * dn * (1.0 + 4.440892098500626e-16);
-}
-
 // ---- re-rank and proof: one thread per row, the wave's rows staged as above.  The row's m candidates in the
 // reference's fold, all at once (slots m .. M - 1 fold the first candidate again and are not used), sorted by (key,
 // number) in an odd-even network; proven rows are answered here, the others are listed: slot = atomicAdd(nsel),
 // sel[slot] = row.  Never proven: a flagged row or call, an empty slot among the m, an infinite or NaN d_m.
 template <typename T, int M>
-__global__ __launch_bounds__(kKnRows) void km_nearest_rerank_kernel(const T *__restrict__ X, size_t n, size_t ld, int dim,
+__global__ __launch_bounds__(kKmLabelRows) void km_nearest_rerank_kernel(const T *__restrict__ X, size_t n, size_t ld, int dim,
                                                                     const T *__restrict__ centres, size_t nc, int m,
                                                                     int staged, const uint32_t *__restrict__ cand,
                                                                     const float *__restrict__ tau,
@@ -321,10 +260,10 @@ __global__ __launch_bounds__(kKnRows) void km_nearest_rerank_kernel(const T *__r
     extern __shared__ __align__(16) unsigned char kn_smem[];
     T *tile = (T *)kn_smem;
     const int lane = threadIdx.x;
-    const size_t first = (size_t)blockIdx.x * kKnRows, i = first + lane;
+    const size_t first = (size_t)blockIdx.x * kKmLabelRows, i = first + lane;
     if (staged) {
-        const int rows = n - first < (size_t)kKnRows ? (int)(n - first) : kKnRows;
-        kn_stage_rows<T>(X, ld, dim, nullptr, first, rows, lane, tile);
+        const int rows = n - first < (size_t)kKmLabelRows ? (int)(n - first) : kKmLabelRows;
+        km_stage_rows<T>(X, ld, dim, nullptr, first, rows, lane, tile);
     }
     if (i >= n) return;
     const double xnr = xn[i];
@@ -347,7 +286,7 @@ __global__ __launch_bounds__(kKnRows) void km_nearest_rerank_kernel(const T *__r
         }
         auto fold = [&](auto in_lds) {
             for (int k = 0; k < dim; ++k) {
-                const T x = decltype(in_lds)::value ? tile[k * kKnPitch + lane] : row[k];
+                const T x = decltype(in_lds)::value ? tile[k * kKmLabelPitch + lane] : row[k];
 #pragma unroll
                 for (int s = 0; s < M; ++s) {
                     const T diff = cp[s][k] - x;
@@ -361,7 +300,7 @@ __global__ __launch_bounds__(kKnRows) void km_nearest_rerank_kernel(const T *__r
         else
             fold(std::false_type{});
 #pragma unroll
-        for (int s = 0; s < M; ++s) key[s] = s < m ? kn_key<T>(kn_sqrt<T>(sum[s])) : KeyOf<T>::kMax;
+        for (int s = 0; s < M; ++s) key[s] = s < m ? km_dist_key<T>(km_sqrt<T>(sum[s])) : KeyOf<T>::kMax;
         // (the slots beyond m: the largest key and the largest number, so they stay behind)
 #pragma unroll
         for (int round = 0; round < M; ++round) {
@@ -380,21 +319,10 @@ __global__ __launch_bounds__(kKnRows) void km_nearest_rerank_kernel(const T *__r
 #pragma unroll
         for (int s = 1; s < M; ++s)
             if (s == m - 1) kk = key[s];
-        constexpr K kInf = sizeof(T) == 4 ? (K)0x7F800000u : (K)0x7FF0000000000000ull;
         const float tv = tau[i];
-        if (kk >= kInf || tv != tv) {
-            ok = false;  // an infinite or NaN distance: the exact kernel orders it
-        } else if (tv < __uint_as_float(0x7F800000u)) {
-            const double slack = km_row_slack((double)xh[i], (double)xl[i], (double)xe[i], cc);
-            // tau' = xn + tau - E, pushed down by the roundings of its own evaluation
-            double lb = (xnr + (double)tv) - slack;
-            lb = lb - (xnr + fabs((double)tv) + slack) * 1.7763568394002505e-15;  // 2^-49
-            if constexpr (sizeof(T) == 4)
-                lb = lb * (1.0 - (double)(dim + 4) * 5.9604644775390625e-08) - 1e-37;
-            else
-                lb = lb * (1.0 - (double)(dim + 4) * 1.1102230246251565e-16) * (1.0 - 8.881784197001252e-16) - 1e-300;
-            ok = lb > kn_proof_rhs<T>(kk);
-        }  // (tau = +inf: no other centre exists)
+        ok = km_euclid_proven<T>(kk, tv, dim, [&] {
+            return km_tau_floor(xnr, (double)tv, km_row_slack((double)xh[i], (double)xl[i], (double)xe[i], cc));
+        });
         if (ok) {
 #pragma unroll
             for (int s = 0; s < M; ++s)
@@ -466,10 +394,11 @@ hipError_t launch_km_nearest_rerank(const T *X, size_t n, size_t ld, int dim, co
                                     const uint32_t *cand, const float *tau, const KmRowImage &r, const KmCentreImage &c,
                                     uint32_t *sel, uint32_t *nsel, int64_t *labels, T *dist, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    const dim3 grid((unsigned)((n + kKnRows - 1) / kKnRows)), blk(kKnRows);
-    const size_t bytes = (size_t)dim * kKnPitch * sizeof(T);
+    const dim3 grid((unsigned)((n + kKmLabelRows - 1) / kKmLabelRows)), blk(kKmLabelRows);
+    const size_t bytes = km_stage_bytes(dim, sizeof(T));
     const int staged = bytes <= 64 * 1024;  // (rows too long for LDS: read in place)
     const size_t lds = staged ? bytes : 0;
+    km_zero_words(nsel, 1, s);
 #define PN_KN_RERANK(M)                                                                                                      \
     hipLaunchKernelGGL((km_nearest_rerank_kernel<T, M>), grid, blk, lds, s, X, n, ld, dim, centres, nc, m, staged, cand, tau, \
                        r.xn, r.xh, r.xl, r.xe, c.cc, sel, nsel, labels, dist)
@@ -486,8 +415,8 @@ template <typename T>
 hipError_t launch_km_nearest_exact(const T *X, size_t n, size_t ld, int dim, const T *centres, size_t nc, int m,
                                    const uint32_t *sel, const uint32_t *nsel, int64_t *labels, T *dist, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    const dim3 grid((unsigned)((n + kKnRows - 1) / kKnRows)), blk(kKnRows);
-    const size_t bytes = (size_t)dim * kKnPitch * sizeof(T);
+    const dim3 grid((unsigned)((n + kKmLabelRows - 1) / kKmLabelRows)), blk(kKmLabelRows);
+    const size_t bytes = km_stage_bytes(dim, sizeof(T));
     const int staged = bytes <= 64 * 1024;
     const size_t lds = staged ? bytes : 0;
 #define PN_KN_EXACT(M)                                                                                                     \

@@ -421,26 +421,39 @@ size_t km_row_image_bytes(size_t n, int dim);
 size_t km_centre_image_bytes(size_t nc, int dim);
 KmRowImage km_row_image_at(void *buf, size_t n, int dim);
 KmCentreImage km_centre_image_at(void *buf, size_t nc, int dim);
+// The launchers of an assignment are one family over the metric: SPH = false Euclidean (instantiated in kmeans.hip), SPH =
+// true Cosine over the rows and centres NORMALISED in f64 (spherical_kmeans.hip).  Their definitions are
+// in km_filter.h.  KmNorms: the norms' folds in T that Cosine::distance divides by (rnorm [n]: the index's, cnorm [nc]);
+// not read for Euclid.
 template <typename T>
+struct KmNorms {
+    const T *rnorm = nullptr, *cnorm = nullptr;
+};
+template <typename T, bool SPH = false>
 hipError_t launch_km_pack_rows(const T *X, size_t n, size_t ld, int dim, const KmRowImage &r, hipStream_t s);
-template <typename T>
+template <typename T, bool SPH = false>
 hipError_t launch_km_pack_centres(const T *centres, size_t nc, int dim, const KmCentreImage &c, hipStream_t s);
 // cand [n] <- the centre of each row's smallest key, tau [n] <- the second smallest key (+inf: there is none)
+template <bool SPH>
 hipError_t launch_km_filter(const KmRowImage &r, size_t n, const KmCentreImage &c, size_t nc, uint32_t *cand, float *tau,
                             hipStream_t s);
+template <>
+hipError_t launch_km_filter<false>(const KmRowImage &, size_t, const KmCentreImage &, size_t, uint32_t *, float *, hipStream_t);
+template <>
+hipError_t launch_km_filter<true>(const KmRowImage &, size_t, const KmCentreImage &, size_t, uint32_t *, float *, hipStream_t);
 // diagnostic: bounds[i * nc + c] <- L(x_i, c)
 hipError_t launch_km_bounds(const KmRowImage &r, size_t n, const KmCentreImage &c, size_t nc, double *bounds, hipStream_t s);
-// the candidates in the reference's fold; proven rows get their label and distance (dist nullable), the others are listed:
-// sel[0 .. *nsel) in any order (nsel zeroed by the caller, sel [n])
-template <typename T>
-hipError_t launch_km_rerank(const T *X, size_t n, size_t ld, int dim, const T *centres, size_t nc, const uint32_t *cand,
-                            const float *tau, const KmRowImage &r, const KmCentreImage &c, uint32_t *sel, uint32_t *nsel,
-                            int64_t *labels, T *dist, hipStream_t s);
-// every row (sel == nullptr) or the listed rows against every centre: launch_ms_labels' answer, and the distance
-// (nullable); nc == 0: labels -1, distances NaN
-template <typename T>
-hipError_t launch_km_exact(const T *X, size_t n, size_t ld, int dim, const T *centres, size_t nc, const uint32_t *sel,
-                           const uint32_t *nsel, int64_t *labels, T *dist, hipStream_t s);
+// the candidates in the reference's arithmetic; proven rows get their label and distance (dist nullable), the others are
+// listed: sel[0 .. *nsel) in any order (sel [n]; nsel: 8 bytes, zeroed here)
+template <typename T, bool SPH>
+hipError_t launch_km_rerank(const T *X, size_t n, size_t ld, int dim, const KmNorms<T> &norms, const T *centres, size_t nc,
+                            const uint32_t *cand, const float *tau, const KmRowImage &r, const KmCentreImage &c,
+                            uint32_t *sel, uint32_t *nsel, int64_t *labels, T *dist, hipStream_t s);
+// every row (sel == nullptr) or the listed rows against every centre by (key, centre number): launch_ms_labels' answer for
+// Euclid, and the distance (nullable); a row whose every key is the NaN key (Cosine), and nc == 0: label -1, distance NaN
+template <typename T, bool SPH>
+hipError_t launch_km_exact(const T *X, size_t n, size_t ld, int dim, const KmNorms<T> &norms, const T *centres, size_t nc,
+                           const uint32_t *sel, const uint32_t *nsel, int64_t *labels, T *dist, hipStream_t s);
 // *out <- SUM4096 of (double)dist[i]^2 (0 where labels[i] < 0), of (double)dist[i] itself without `squared`; buf:
 // km_inertia_bytes(n)
 size_t km_inertia_bytes(size_t n);
@@ -451,9 +464,10 @@ hipError_t launch_km_inertia(const int64_t *labels, const T *dist, size_t n, voi
 // centres [nc][dim] in place; *stop_out <- where the 16 bytes {shift2, stop word = shift2 <= tol || last} will be (in
 // buf: km_update_bytes(n, nc, dim), 8-byte aligned).  n, nc >= 1.
 size_t km_update_bytes(size_t n, size_t nc, int dim);
-template <typename T>
-hipError_t km_update_enqueue(const T *X, size_t n, size_t ld, int dim, const int64_t *labels, size_t nc, void *buf,
-                             T *centres, uint64_t *counts, double tol, int last, double **stop_out, hipStream_t s);
+// SPH: the spherical mean -- the term of a member is x / rnorm in f64, the new centre S / sqrt(Q); else rnorm is not read.
+template <typename T, bool SPH>
+hipError_t km_update_enqueue(const T *X, size_t n, size_t ld, int dim, const T *rnorm, const int64_t *labels, size_t nc,
+                             void *buf, T *centres, uint64_t *counts, double tol, int last, double **stop_out, hipStream_t s);
 // its front half (the sort of the members' lists, the offsets, counts and, with `segments`, the enumeration of the
 // (cluster, segment of 4096 members) pairs) and its stop kernel, for the update of spherical_kmeans.hip
 struct KmMembers {
@@ -469,29 +483,6 @@ hipError_t launch_km_stop(const double *tc, size_t nc, double tol, int last, dou
 // waits for the device.  The images and the bound are kmeans.hip's over the rows and centres NORMALISED in f64; the
 // filter takes 8 <= dim <= 304 (skm_filter_supported).
 bool skm_filter_supported(int dim);
-template <typename T>
-hipError_t launch_skm_pack_rows(const T *X, size_t n, size_t ld, int dim, const KmRowImage &r, hipStream_t s);
-template <typename T>
-hipError_t launch_skm_pack_centres(const T *centres, size_t nc, int dim, const KmCentreImage &c, hipStream_t s);
-// cand [n] <- the centre of each row's smallest key, tau [n] <- the second smallest key
-hipError_t launch_skm_filter(const KmRowImage &r, size_t n, const KmCentreImage &c, size_t nc, uint32_t *cand, float *tau,
-                             hipStream_t s);
-// the candidates' Cosine::distance in the reference's arithmetic (rnorm [n], cnorm [nc]: the norms' folds in T); proven
-// rows get their label and distance (dist nullable), the others are listed: sel[0 .. *nsel) (nsel: 8 bytes, zeroed here)
-template <typename T>
-hipError_t launch_skm_rerank(const T *X, size_t n, size_t ld, int dim, const T *rnorm, const T *centres, const T *cnorm,
-                             size_t nc, const uint32_t *cand, const float *tau, const KmRowImage &r, const KmCentreImage &c,
-                             uint32_t *sel, uint32_t *nsel, int64_t *labels, T *dist, hipStream_t s);
-// every row (sel == nullptr) or the listed rows against every centre by (signed key, centre number); a NaN key, and
-// nc == 0: label -1, distance NaN
-template <typename T>
-hipError_t launch_skm_exact(const T *X, size_t n, size_t ld, int dim, const T *rnorm, const T *centres, const T *cnorm,
-                            size_t nc, const uint32_t *sel, const uint32_t *nsel, int64_t *labels, T *dist, hipStream_t s);
-// km_update_enqueue with the spherical mean: the term of a member is x / rnorm in f64, the new centre S / sqrt(Q)
-template <typename T>
-hipError_t skm_update_enqueue(const T *X, size_t n, size_t ld, int dim, const T *rnorm, const int64_t *labels, size_t nc,
-                              void *buf, T *centres, uint64_t *counts, double tol, int last, double **stop_out,
-                              hipStream_t s);
 
 // ---- kmeans_nearest.hip: the m nearest centres of every row (pn_kmeans_nearest_*), 1 <= m <= 8, on the images and the
 // bound of kmeans.hip; nothing in it waits for the device.  The kernels carry lists of km_nearest_width(m) = 2, 4 or 8.
@@ -501,7 +492,7 @@ int km_nearest_width(size_t m);
 hipError_t launch_km_nearest_filter(const KmRowImage &r, size_t n, const KmCentreImage &c, size_t nc, int m, uint32_t *cand,
                                     float *tau, hipStream_t s);
 // each row's first m candidates in the reference's fold, ordered by (key, number); proven rows get labels and dist [n][m]
-// (dist nullable), the others are listed: sel[0 .. *nsel) in any order (nsel zeroed by the caller, sel [n])
+// (dist nullable), the others are listed: sel[0 .. *nsel) in any order (sel [n]; nsel: 8 bytes, zeroed here)
 template <typename T>
 hipError_t launch_km_nearest_rerank(const T *X, size_t n, size_t ld, int dim, const T *centres, size_t nc, int m,
                                     const uint32_t *cand, const float *tau, const KmRowImage &r, const KmCentreImage &c,

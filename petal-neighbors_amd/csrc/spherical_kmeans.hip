@@ -37,27 +37,14 @@
 // This translation unit is compiled with -ffp-contract=off: every operation outside the MFMA is plain IEEE, unfused.
 #include "../../include/petal_mi355x.h"
 #include "pn_internal.h"
-#include "km_pack.h"
+#include "km_filter.h"  // the chain, the row tile, the proof's tau', the kernels and launchers shared with kmeans.hip
 
 namespace pn {
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kSkmMaxDp = 304, kSkmWideDp = 192;  // four waves up to kSkmWideDp padded columns, two beyond
-constexpr int kSkmLabelRows = 64, kSkmLabelPitch = 65;
-constexpr int kSkmSeg = 4096;
-
 __host__ __device__ inline int skm_sub(int dp) { return dp <= 48 ? 4 : dp <= 96 ? 2 : 1; }  // 32-centre tiles per stage
-
-__device__ __forceinline__ void skm_lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-template <typename T> __device__ __forceinline__ T skm_nan();
-template <> __device__ __forceinline__ float skm_nan<float>() { return __uint_as_float(0x7FC00000u); }
-template <> __device__ __forceinline__ double skm_nan<double>() { return __longlong_as_double(0x7FF8000000000000ll); }
 
 // the order-preserving map of ALL floats (select.hip, sel_key_signed): -0 as +0, NaN above +inf
 template <typename T> struct SkmKey;
@@ -78,10 +65,6 @@ template <> struct SkmKey<double> {
     }
 };
 
-__global__ void skm_zero_kernel(unsigned long long *p, int words) {
-    if ((int)threadIdx.x < words) p[threadIdx.x] = 0ull;
-}
-
 // ---- the filter.  grid: the row tiles; PF = the 16-byte chunks a thread carries from HBM to LDS per stage, at most
 template <int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void skm_filter_kernel(const uint16_t *__restrict__ ximg,
@@ -100,13 +83,7 @@ __global__ __launch_bounds__(64 * WAVES) void skm_filter_kernel(const uint16_t *
     const size_t row0 = (size_t)blockIdx.x * kRows;  // (the images have whole tiles of 128 rows: rows beyond n are zeros)
     const size_t n_stages = (nc_pad + (size_t)srows - 1) / (size_t)srows;
 
-    // ---- the workgroup's rows
-    for (int q = t; q < kRows * chunks; q += kThreads) {
-        const int rr = q / chunks, ch = q - rr * chunks;
-        const size_t src = (row0 + (size_t)rr) * (size_t)dp + (size_t)ch * 8;
-        *(u32x4 *)(btile + (size_t)rr * pitch + ch * 8) = *(const u32x4 *)(ximg + src);
-        *(u32x4 *)(btile_lo + (size_t)rr * pitch + ch * 8) = *(const u32x4 *)(xlo + src);
-    }
+    km_load_row_tile<kThreads>(btile, btile_lo, ximg, xlo, row0, kRows, dp, t);
 
     // ---- the stream of the centres.  Stage s lies in data buffer s & 1 and meta buffer s % 3.
     const int per_img = srows * chunks, total = 2 * per_img;  // 16-byte chunks of a stage: total <= PF kThreads
@@ -142,23 +119,9 @@ __global__ __launch_bounds__(64 * WAVES) void skm_filter_kernel(const uint16_t *
     const uint16_t *brow_lo = btile_lo + (size_t)(w * 32 + r) * pitch + h * 8;
     auto chain = [&](size_t stage, int v) {
         const uint16_t *a0 = abuf + (size_t)(stage & 1) * 2 * srows * pitch + (size_t)(v * 32 + r) * pitch + h * 8;
-        const uint16_t *a1 = a0 + (size_t)srows * pitch;
-        f32x16 acc;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
-        for (int ks = 0; ks < ksteps; ++ks) {
-            const bf16x8 a = *(const bf16x8 *)(a0 + ks * 16);
-            const bf16x8 al = *(const bf16x8 *)(a1 + ks * 16);
-            const bf16x8 b = *(const bf16x8 *)(brow + ks * 16);
-            const bf16x8 bl = *(const bf16x8 *)(brow_lo + ks * 16);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bl, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, b, acc, 0, 0, 0);
-        }
-        return acc;
+        return km_mfma_chain(a0, a0 + (size_t)srows * pitch, brow, brow_lo, ksteps);
     };
-    // registers 4 g .. 4 g + 3 of the accumulator are the tile's centres 8 g + 4 h + 0 .. 3 (the C layout of the
-    // instruction); the padding's cn is +inf, so its keys never pass the strict '<'
+    // (the padding's cn is +inf, so its keys never pass the strict '<')
     const float inf = __uint_as_float(0x7F800000u);
     float k1 = inf, k2 = inf;
     uint32_t c1 = 0xFFFFFFFFu;
@@ -227,202 +190,37 @@ __global__ __launch_bounds__(64 * WAVES) void skm_filter_kernel(const uint16_t *
     }
 }
 
-// ---- staging of a wave's 64 rows, transposed, in LDS (kmeans.hip, km_stage_rows); sel: the listed rows
+// ---- the Cosine metric of km_filter.h's kernels: Cosine::distance as the header of this file states it -- the unfused
+// fold of x_k c_k, 1 - dot / (norm_c * norm_row) -- on the signed keys; a row whose least key is the NaN key is a member of
+// nothing (label -1, distance NaN).  A row without a finite runner-up is listed.  PROVEN: every other centre's reference
+// distance is at least (tau' - eps1) / 2 - E' (cos_proof_lb's constants, select.hip), pushed down by the roundings of its
+// own evaluation, and that is strictly above the candidate's d.
 template <typename T>
-__device__ __forceinline__ void skm_stage_rows(const T *__restrict__ X, size_t ld, int dim, const uint32_t *__restrict__ sel,
-                                               size_t first, int rows, int lane, T *__restrict__ tile) {
-    for (int r = 0; r < rows; ++r) {
-        const size_t i = sel ? (size_t)sel[first + r] : first + (size_t)r;
-        for (int k = lane; k < dim; k += kSkmLabelRows) tile[k * kSkmLabelPitch + r] = X[i * ld + k];
-    }
-    __syncthreads();
-}
-
-// ---- the exact kernel: Cosine::distance of every centre for thread j's row (sel / nsel as in km_exact_kernel), the
-// least (signed key, centre number); a row whose least key is the NaN key is a member of nothing
-template <typename T, bool STAGED>
-__global__ __launch_bounds__(kSkmLabelRows) void skm_exact_kernel(const T *__restrict__ X, size_t n, size_t ld, int dim,
-                                                                  const T *__restrict__ rnorm,
-                                                                  const T *__restrict__ centres,
-                                                                  const T *__restrict__ cnorm, size_t nc,
-                                                                  const uint32_t *__restrict__ sel,
-                                                                  const uint32_t *__restrict__ nsel,
-                                                                  int64_t *__restrict__ labels, T *__restrict__ dist) {
-#pragma clang fp contract(off)
+struct KmMetric<T, true> {
     using K = typename KeyOf<T>::type;
-    extern __shared__ __align__(16) unsigned char skm_smem[];
-    T *tile = (T *)skm_smem;
-    const int lane = threadIdx.x;
-    const size_t count = sel ? (size_t)*nsel : n;
-    const size_t first = (size_t)blockIdx.x * kSkmLabelRows, j = first + lane;
-    if (first >= count) return;  // (the whole workgroup)
-    if (STAGED) {
-        const int rows = count - first < (size_t)kSkmLabelRows ? (int)(count - first) : kSkmLabelRows;
-        skm_stage_rows<T>(X, ld, dim, sel, first, rows, lane, tile);
+    static constexpr K kNoKey = SkmKey<T>::kNaN;  // (only keys below the NaN key make a member)
+    static __device__ __forceinline__ T no_dist() { return km_nan<T>(); }
+    static __device__ __forceinline__ T term(T c, T x) { return c * x; }
+    static __device__ __forceinline__ T row_norm(const KmNorms<T> &norms, size_t i) { return norms.rnorm[i]; }
+    static __device__ __forceinline__ T finish(T dot, const KmNorms<T> &norms, size_t c, T rn) {
+        const T den = norms.cnorm[(uint32_t)c] * rn;  // (nc < 2^31: a 32-bit index keeps the exact kernel's scalars in registers)
+        return (T)1 - dot / den;
     }
-    if (j >= count) return;
-    const size_t i = sel ? (size_t)sel[j] : j;
-    const T *row = X + i * ld;
-    const T rn = rnorm[i];
-    K best = SkmKey<T>::kNaN;  // (only keys below the NaN key make a member)
-    int64_t lab = -1;
-    T best_d = skm_nan<T>();
-    for (size_t c = 0; c < nc; c += 4) {
-        const T *cp[4];
-        T dot[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            cp[u] = centres + (c + u < nc ? c + u : nc - 1) * (size_t)dim;  // (past the end: the last centre again, not used)
-            dot[u] = (T)0;
-        }
-        for (int k = 0; k < dim; ++k) {
-            const T x = STAGED ? tile[k * kSkmLabelPitch + lane] : row[k];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const T pr = cp[u][k] * x;
-                dot[u] = dot[u] + pr;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const T den = cnorm[c + u < nc ? c + u : nc - 1] * rn;
-            const T d = (T)1 - dot[u] / den;
-            const K key = SkmKey<T>::of(d);
-            if (c + u < nc && key < best) {
-                best = key;
-                lab = (int64_t)(c + u);
-                best_d = d;
-            }
-        }
+    static __device__ __forceinline__ K key(T d) { return SkmKey<T>::of(d); }
+    static __device__ __forceinline__ bool admits(const float *tau, size_t i) { return tau[i] < __uint_as_float(0x7F800000u); }
+    template <typename TauFloor>
+    static __device__ __forceinline__ bool proven(T d, float, int dim, TauFloor tau_floor) {
+        if (key(d) >= SkmKey<T>::kInf) return false;  // an infinite or NaN distance: the exact kernel orders it
+        const double u = sizeof(T) == 4 ? 5.9604644775390625e-08 : 1.1102230246251565e-16;
+        double lb = tau_floor();
+        const double eps1 = (4.5 * (double)dim + 45.0) * 1.1102230246251565e-16;
+        const double e = (2.0 * (double)dim + 16.0) * u;
+        lb = 0.5 * (lb - eps1) - e - (fabs(lb) + 1.0) * 1.0e-15;
+        return lb > (double)d;
     }
-    labels[i] = lab;
-    if (dist) dist[i] = best_d;
-}
+    static void launch_move(const KmMembers &m, size_t nc, int dim, T *centres, hipStream_t s);
+};
 
-// ---- re-rank and proof: one thread per row, the wave's rows staged as above.  The candidate's distance in the
-// reference's arithmetic; proven rows are answered here, the others are listed: slot = atomicAdd(nsel), sel[slot] = row.
-template <typename T, bool STAGED>
-__global__ __launch_bounds__(kSkmLabelRows) void skm_rerank_kernel(const T *__restrict__ X, size_t n, size_t ld, int dim,
-                                                                   const T *__restrict__ rnorm,
-                                                                   const T *__restrict__ centres,
-                                                                   const T *__restrict__ cnorm, size_t nc,
-                                                                   const uint32_t *__restrict__ cand,
-                                                                   const float *__restrict__ tau,
-                                                                   const double *__restrict__ xn,
-                                                                   const float *__restrict__ xh,
-                                                                   const float *__restrict__ xl,
-                                                                   const float *__restrict__ xe,
-                                                                   const unsigned long long *__restrict__ cc,
-                                                                   uint32_t *__restrict__ sel, uint32_t *__restrict__ nsel,
-                                                                   int64_t *__restrict__ labels, T *__restrict__ dist) {
-#pragma clang fp contract(off)
-    using K = typename KeyOf<T>::type;
-    extern __shared__ __align__(16) unsigned char skm_smem[];
-    T *tile = (T *)skm_smem;
-    const int lane = threadIdx.x;
-    const size_t first = (size_t)blockIdx.x * kSkmLabelRows, i = first + lane;
-    if (STAGED) {
-        const int rows = n - first < (size_t)kSkmLabelRows ? (int)(n - first) : kSkmLabelRows;
-        skm_stage_rows<T>(X, ld, dim, nullptr, first, rows, lane, tile);
-    }
-    if (i >= n) return;
-    const uint32_t c = cand[i];
-    const double xnr = xn[i];
-    const float tv = tau[i];
-    // (a flagged centre, a flagged row, no candidate, no finite runner-up: the exact kernel)
-    bool ok = cc[4] == 0 && xnr == xnr && (size_t)c < nc && tv < __uint_as_float(0x7F800000u);
-    T d = (T)0;
-    if (ok) {
-        const T *cp = centres + (size_t)c * (size_t)dim;
-        const T *row = X + i * ld;
-        T dot = (T)0;
-        for (int k = 0; k < dim; ++k) {
-            const T x = STAGED ? tile[k * kSkmLabelPitch + lane] : row[k];
-            const T pr = cp[k] * x;
-            dot = dot + pr;
-        }
-        const T den = cnorm[c] * rnorm[i];
-        d = (T)1 - dot / den;
-        const K kk = SkmKey<T>::of(d);
-        if (kk >= SkmKey<T>::kInf) {
-            ok = false;  // an infinite or NaN distance: the exact kernel orders it
-        } else {
-            const double u = sizeof(T) == 4 ? 5.9604644775390625e-08 : 1.1102230246251565e-16;
-            const double slack = km_row_slack((double)xh[i], (double)xl[i], (double)xe[i], cc);
-            // tau' = xn + tau - E, pushed down by the roundings of its own evaluation
-            double lb = (xnr + (double)tv) - slack;
-            lb = lb - (xnr + fabs((double)tv) + slack) * 1.7763568394002505e-15;  // 2^-49
-            // (tau' - eps1) / 2 - E' - guard: cos_proof_lb's constants (select.hip)
-            const double eps1 = (4.5 * (double)dim + 45.0) * 1.1102230246251565e-16;
-            const double e = (2.0 * (double)dim + 16.0) * u;
-            lb = 0.5 * (lb - eps1) - e - (fabs(lb) + 1.0) * 1.0e-15;
-            ok = lb > (double)d;
-        }
-    }
-    if (ok) {
-        labels[i] = (int64_t)c;
-        if (dist) dist[i] = d;
-    } else {
-        const uint32_t slot = atomicAdd(nsel, 1u);
-        sel[slot] = (uint32_t)i;  // (slot < n: every row is listed at most once)
-    }
-}
-
-// ---- the update.  km_segment_sums_kernel (kmeans.hip) with the member's term x / |x|: (double)x[i][col] / (double)rnorm[i]
-template <typename T, int COLS>
-__global__ __launch_bounds__(64) void skm_segment_sums_kernel(const uint64_t *__restrict__ key,
-                                                              const uint64_t *__restrict__ off,
-                                                              const uint64_t *__restrict__ seg_off, size_t nc,
-                                                              const T *__restrict__ X, size_t ld, int dim,
-                                                              const T *__restrict__ rnorm, double *__restrict__ segsum) {
-#pragma clang fp contract(off)
-    __shared__ double s_part[COLS][65];
-    const int lane = threadIdx.x;
-    const uint64_t b = blockIdx.x;
-    if (b >= seg_off[nc]) return;
-    size_t lo = 0, hi = nc;  // the cluster: the last c with seg_off[c] <= b
-    while (hi - lo > 1) {
-        const size_t mid = lo + (hi - lo) / 2;
-        if (seg_off[mid] <= b)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    const size_t c = lo;
-    const uint64_t s = b - seg_off[c];
-    const uint64_t beg = off[c] + s * kSkmSeg, rest = off[c + 1] - beg;
-    const uint64_t len = rest < (uint64_t)kSkmSeg ? rest : (uint64_t)kSkmSeg;
-    for (int c0 = 0; c0 < dim; c0 += COLS) {
-        double P[COLS];
-#pragma unroll
-        for (int k = 0; k < COLS; ++k) P[k] = 0.0;
-        for (uint64_t j = lane; j < len; j += 64) {
-            // (c0 + COLS <= ld: the row's padding is read, and never used)
-            const size_t i = (size_t)(uint32_t)key[beg + j];
-            const T *__restrict__ row = X + i * ld + c0;
-            const double rn = (double)rnorm[i];
-            T v[COLS];
-#pragma unroll
-            for (int k = 0; k < COLS; ++k) v[k] = row[k];
-#pragma unroll
-            for (int k = 0; k < COLS; ++k) {
-                const double q = (double)v[k] / rn;
-                P[k] = P[k] + q;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < COLS; ++k) s_part[k][lane] = P[k];
-        skm_lds_fence();
-        const int col = c0 + lane;
-        if (lane < COLS && col < dim) {
-            double S = s_part[lane][0];
-#pragma unroll 9
-            for (int l = 1; l < 64; ++l) S = S + s_part[lane][l];
-            segsum[b * (uint64_t)dim + col] = S;
-        }
-        skm_lds_fence();
-    }
-}
 // One wave per centre: S_col = the segments in order; Q = the sum of S_col^2 in the 64-partial shape; the new centre
 // (T)(S_col / sqrt(Q)); tc[c] <- the sum of the squared moves in the same shape.  A centre without members, or whose Q is
 // 0 or not finite, is unchanged.
@@ -480,26 +278,9 @@ __global__ __launch_bounds__(64) void skm_move_kernel(const uint64_t *__restrict
 
 bool skm_filter_supported(int dim) { return dim >= 8 && (dim + 15) / 16 * 16 <= kSkmMaxDp; }
 
-template <typename T>
-hipError_t launch_skm_pack_rows(const T *X, size_t n, size_t ld, int dim, const KmRowImage &r, hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL((km_pack_kernel<T, true, true>), dim3((unsigned)((r.n_img + 3) / 4)), dim3(256), 0, s, X, n, r.n_img, ld,
-                       dim, r.dp, r.img, r.lo, r.xn, r.xh, r.xl, r.xe, (float *)nullptr, (unsigned long long *)nullptr,
-                       (const float *)nullptr);
-    return hipGetLastError();
-}
-template <typename T>
-hipError_t launch_skm_pack_centres(const T *centres, size_t nc, int dim, const KmCentreImage &c, hipStream_t s) {
-    const int dp = (dim + 15) / 16 * 16;
-    hipLaunchKernelGGL(skm_zero_kernel, dim3(1), dim3(64), 0, s, c.cc, 8);
-    hipLaunchKernelGGL((km_pack_kernel<T, false, true>), dim3((unsigned)((c.nc_pad + 3) / 4)), dim3(256), 0, s, centres, nc,
-                       c.nc_pad, (size_t)dim, dim, dp, c.img, c.lo, (double *)nullptr, (float *)nullptr, (float *)nullptr,
-                       (float *)nullptr, c.cn, c.cc, (const float *)nullptr);
-    return hipGetLastError();
-}
-
-hipError_t launch_skm_filter(const KmRowImage &r, size_t n, const KmCentreImage &c, size_t nc, uint32_t *cand, float *tau,
-                             hipStream_t s) {
+template <>
+hipError_t launch_km_filter<true>(const KmRowImage &r, size_t n, const KmCentreImage &c, size_t nc, uint32_t *cand,
+                                  float *tau, hipStream_t s) {
     if (n == 0 || nc == 0) return hipSuccess;
     if (r.dp > kSkmMaxDp) return hipErrorInvalidValue;
     static LdsAttrOnce once4, once2;
@@ -522,69 +303,12 @@ hipError_t launch_skm_filter(const KmRowImage &r, size_t n, const KmCentreImage 
 }
 
 template <typename T>
-hipError_t launch_skm_rerank(const T *X, size_t n, size_t ld, int dim, const T *rnorm, const T *centres, const T *cnorm,
-                             size_t nc, const uint32_t *cand, const float *tau, const KmRowImage &r, const KmCentreImage &c,
-                             uint32_t *sel, uint32_t *nsel, int64_t *labels, T *dist, hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    const dim3 grid((unsigned)((n + kSkmLabelRows - 1) / kSkmLabelRows)), blk(kSkmLabelRows);
-    const size_t tile = (size_t)dim * kSkmLabelPitch * sizeof(T);
-    hipLaunchKernelGGL(skm_zero_kernel, dim3(1), dim3(64), 0, s, (unsigned long long *)nsel, 1);
-    if (tile <= 64 * 1024)
-        hipLaunchKernelGGL((skm_rerank_kernel<T, true>), grid, blk, tile, s, X, n, ld, dim, rnorm, centres, cnorm, nc, cand, tau,
-                           r.xn, r.xh, r.xl, r.xe, c.cc, sel, nsel, labels, dist);
-    else
-        hipLaunchKernelGGL((skm_rerank_kernel<T, false>), grid, blk, 0, s, X, n, ld, dim, rnorm, centres, cnorm, nc, cand, tau,
-                           r.xn, r.xh, r.xl, r.xe, c.cc, sel, nsel, labels, dist);
-    return hipGetLastError();
-}
-
-template <typename T>
-hipError_t launch_skm_exact(const T *X, size_t n, size_t ld, int dim, const T *rnorm, const T *centres, const T *cnorm,
-                            size_t nc, const uint32_t *sel, const uint32_t *nsel, int64_t *labels, T *dist, hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    const dim3 grid((unsigned)((n + kSkmLabelRows - 1) / kSkmLabelRows)), blk(kSkmLabelRows);
-    const size_t tile = (size_t)dim * kSkmLabelPitch * sizeof(T);
-    if (tile <= 64 * 1024)
-        hipLaunchKernelGGL((skm_exact_kernel<T, true>), grid, blk, tile, s, X, n, ld, dim, rnorm, centres, cnorm, nc, sel, nsel,
-                           labels, dist);
-    else  // (rows too long for LDS: read in place)
-        hipLaunchKernelGGL((skm_exact_kernel<T, false>), grid, blk, 0, s, X, n, ld, dim, rnorm, centres, cnorm, nc, sel, nsel,
-                           labels, dist);
-    return hipGetLastError();
-}
-
-template <typename T>
-hipError_t skm_update_enqueue(const T *X, size_t n, size_t ld, int dim, const T *rnorm, const int64_t *labels, size_t nc,
-                              void *buf, T *centres, uint64_t *counts, double tol, int last, double **stop_out,
-                              hipStream_t s) {
-    KmMembers m;
-    const hipError_t e = km_members_enqueue(labels, n, nc, dim, buf, centres != nullptr, counts, &m, s);
-    if (e != hipSuccess) return e;
-    if (stop_out) *stop_out = m.stop;
-    if (!centres) return hipGetLastError();
-    const dim3 grid((unsigned)m.max_segments);
-    if (ld % 16 == 0)
-        hipLaunchKernelGGL((skm_segment_sums_kernel<T, 16>), grid, dim3(64), 0, s, m.key, m.off, m.seg_off, nc, X, ld, dim, rnorm,
-                           m.segsum);
-    else
-        hipLaunchKernelGGL((skm_segment_sums_kernel<T, 8>), grid, dim3(64), 0, s, m.key, m.off, m.seg_off, nc, X, ld, dim, rnorm,
-                           m.segsum);
+void KmMetric<T, true>::launch_move(const KmMembers &m, size_t nc, int dim, T *centres, hipStream_t s) {
     hipLaunchKernelGGL((skm_move_kernel<T>), dim3((unsigned)nc), dim3(64), 0, s, m.off, m.seg_off, m.segsum, dim, centres, m.tc);
-    return launch_km_stop(m.tc, nc, tol, last, m.stop, s);
 }
 
-#define PN_SKM_INSTANTIATE(T)                                                                                              \
-    template hipError_t launch_skm_pack_rows<T>(const T *, size_t, size_t, int, const KmRowImage &, hipStream_t);          \
-    template hipError_t launch_skm_pack_centres<T>(const T *, size_t, int, const KmCentreImage &, hipStream_t);            \
-    template hipError_t launch_skm_rerank<T>(const T *, size_t, size_t, int, const T *, const T *, const T *, size_t,      \
-                                             const uint32_t *, const float *, const KmRowImage &, const KmCentreImage &,   \
-                                             uint32_t *, uint32_t *, int64_t *, T *, hipStream_t);                         \
-    template hipError_t launch_skm_exact<T>(const T *, size_t, size_t, int, const T *, const T *, const T *, size_t,       \
-                                            const uint32_t *, const uint32_t *, int64_t *, T *, hipStream_t);              \
-    template hipError_t skm_update_enqueue<T>(const T *, size_t, size_t, int, const T *, const int64_t *, size_t, void *,  \
-                                              T *, uint64_t *, double, int, double **, hipStream_t);
-PN_SKM_INSTANTIATE(float)
-PN_SKM_INSTANTIATE(double)
-#undef PN_SKM_INSTANTIATE
+PN_KM_INSTANTIATE(float, true)
+PN_KM_INSTANTIATE(double, true)
+#undef PN_KM_INSTANTIATE
 
 }  // namespace pn
