@@ -152,9 +152,11 @@ enum {
                                   eligible (8 <= dim <= 320), on any handle; 2 = never.  Other values: PN_ERR_INVALID.
                                   Never changes a result (it lets tests force the filter at small n). */
     PN_OPT_FOREIGN_FILTER = 17   /* pn_nearest_foreign_*, the rounds of pn_mst_* (and what is built on them): 0 (default) =
-                                  PN_OPT_ENGINE decides; 1 = the bf16 first tier wherever it is eligible (a Euclidean index,
-                                  8 <= dim <= 160), on any handle; 2 = never.  Other values: PN_ERR_INVALID.  Never changes
-                                  a result (it lets tests force the tier at small n). */
+                                  PN_OPT_ENGINE decides; 1 = the Euclidean bf16 first tier wherever it is eligible (a Euclidean
+                                  index, 8 <= dim <= 160), on any handle -- a Cosine handle keeps the exact scan; 2 = never;
+                                  3 = the first tier of the handle's metric wherever one is eligible (8 <= dim <= 160): on a
+                                  Euclidean handle what 1 is, on a Cosine handle the Cosine tier.  Other values:
+                                  PN_ERR_INVALID.  Never changes a result (it lets tests force the tier at small n). */
 };
 
 /* kernels of pn_kde_* (scikit-learn's names; its sixth, `cosine`, is left out: the name collides with the Cosine metric
@@ -470,7 +472,7 @@ int pn_dbscan_device_f64(const pn_index *index, double eps, size_t min_samples, 
  * handed to a scan summed over the rounds (a round answered by the k-NN pipeline counts n).  Without cores round 0 is
  * pn_query_self_device_*(k = 1) on the handle's engine; every other round is an exact masked scan of the rows whose cached
  * candidate has joined their own component.  Device memory beyond a 2^18-query batch's workspace: about
- * 100 bytes per row (f64: 130).  On a Euclidean index of 8 <= dim <= 160 the listed rows of a scan go through the bf16 first
+ * 100 bytes per row (f64: 130).  On an index of 8 <= dim <= 160 the listed rows of a scan go through the bf16 first
  * tier of pn_nearest_foreign_* (below) first where the engine says so -- PN_ENGINE_BF16, PN_ENGINE_AUTO from 10^5 rows of at
  * least 16 columns on, PN_OPT_FOREIGN_FILTER on any handle; the rows are packed once per call (4 dim + 24 more bytes per
  * row), the edges, their order and work_out do not change, and pn_stats counts the tier's work as it does there.
@@ -497,17 +499,20 @@ int pn_mst_device_f64(const pn_index *index, const double *d_core, unsigned flag
  * n_rows = 0: all n rows, ascending; not NULL with n_rows = 0: an empty list -- nothing is written, the outputs may be NULL.  Output r answers row i = rows[r] (or r): idx_out[r] = the row j with groups[j] !=
  * groups[i] that minimises (key(w(i, j)), j), PN_OPT_INDEX_BASE added; weight_out[r] = w(i, j), written as the value of its
  * key (-0 as +0, any NaN as the canonical quiet NaN).  A row without a foreign row (every row is of its group) gets idx =
- * UINT64_MAX and the value of the greatest key as its weight (all bits set: a NaN).  The answer depends on the data alone,
+ * UINT64_MAX and the value of the greatest key as its weight (all bits set, on a Cosine index all but the sign bit: a NaN).  The answer depends on the data alone,
  * not on the engine, PN_OPT_FOREIGN_FILTER or PN_OPT_MST_BATCH (the most rows one scan launch takes, as for pn_mst_*).
  * flags must be 0.  Argument errors, before any device is touched and in this order: flags != 0; rows == NULL with n_rows
  * != 0; a NULL output with n > 0 and rows to answer; groups == NULL with n > 0; NULL index; wrong element type: PN_ERR_INVALID;
  * more than 2^31 - 1 indexed or listed rows: PN_ERR_UNSUPPORTED.  The host entry points then reject a row number >= n
  * (PN_ERR_INVALID); the device entry points cannot look: such a row is answered like a row without a foreign row.
- * Engines.  Cosine indexes, dim < 8 or > 160, PN_ENGINE_EXACT: the exact masked scan (mst_scan_kernel).  Otherwise --
- * PN_ENGINE_BF16, PN_ENGINE_AUTO from 10^5 rows of at least 16 columns on, PN_OPT_FOREIGN_FILTER = 1 anywhere -- a bf16 MFMA
+ * Engines.  dim < 8 or > 160, PN_ENGINE_EXACT: the exact masked scan (mst_scan_kernel).  Otherwise -- PN_ENGINE_BF16,
+ * PN_ENGINE_AUTO from 10^5 rows of at least 16 columns on,
+ * PN_OPT_FOREIGN_FILTER = 3 anywhere, = 1 anywhere on a Euclidean index -- a bf16 MFMA
  * first tier looks at every pair first: a proven lower bound of every pair's key, the 3 smallest per row re-ranked in the
- * reference's fold, the row proven in key order or handed to the exact scan; a call with a row that is not
- * finite or whose squared distance to the corpus mean exceeds 2^100 goes to the exact scan as a whole.  A scan launch of fewer
+ * reference's fold, the row proven in key order or handed to the exact scan (Cosine indexes, over the
+ * normalised rows and on the signed keys: 4.29); a call with a row that is not
+ * finite or whose squared distance to the corpus mean exceeds 2^100 (Cosine: whose squared norm lies outside [2^-100,
+ * 2^100] -- a zero row) goes to the exact scan as a whole.  A scan launch of fewer
  * than 64 listed rows (a short list, or PN_OPT_MST_BATCH cut small) takes the exact scan too.  pn_stats: queries
  * += the rows answered, fallback_queries += the rows the first tier left to the exact scan, candidates and evaluations +=
  * the candidates it evaluated (the mean is summed in a fixed shape: the counters depend on the data alone).  Device memory: 16 bytes per indexed row and 4 per listed row (f64: 24 and 4), and with the
@@ -515,7 +520,7 @@ int pn_mst_device_f64(const pn_index *index, const double *d_core, unsigned flag
  * Device entry points: everything in HBM, written in stream order on `stream`; with the first tier the call BLOCKS THE HOST
  * ONCE PER BATCH of 2^18 listed rows (to read how many rows are left to the exact scan) and is then not capturable into a
  * graph; without it nothing waits.
- * Not in this version: row-sharded handles (pn_sharded_*), a first tier for Cosine indexes. */
+ * Not in this version: row-sharded handles (pn_sharded_*). */
 int pn_nearest_foreign_f32(const pn_index *index, const uint32_t *groups, const float *core, const uint64_t *rows,
                            size_t n_rows, unsigned flags, uint64_t *idx_out, float *weight_out);
 int pn_nearest_foreign_f64(const pn_index *index, const uint32_t *groups, const double *core, const uint64_t *rows,

@@ -1,5 +1,5 @@
-// foreign.hip -- the first tier of the masked nearest-foreign-row scan on Euclidean indexes (pn_nearest_foreign_*, the
-// rounds of pn_mst_*).  For every listed row i the exact scan (exact_scan.hip, mst_scan_kernel) wants the
+// foreign.hip -- the first tier of the masked nearest-foreign-row scan (pn_nearest_foreign_*, the rounds of pn_mst_*): on
+// Euclidean indexes and, below under "Cosine", on Cosine indexes.  For every listed row i the exact scan (exact_scan.hip, mst_scan_kernel) wants the
 // least (key(w(i, j)), j) over the rows j of another group, w = max(d(i, j), core[i], core[j]) on the sortable keys, and
 // pays 3 VALU operations per coordinate of every pair for it.  Here the matrix cores look at every pair first.
 //
@@ -28,6 +28,32 @@
 // proven -- or any row of a call in which some row is not finite or has a squared norm beyond 2^100 -- is listed for the
 // exact scan, which answers it alone: results never depend on this tier.
 //
+// Cosine (COS instantiations; the candidates, tau, the proof in key order and the fallback are the ones above).  The rows
+// are packed NORMALISED and not translated -- a translation changes angles -- by km_pack.h's NORM front: x- = x / |x| in
+// f64, two bf16 images; no mean is summed.  Over the packed unit vectors the same chain and the same slack give
+//   L(i, j) = xn(i) + fl32(cn(j) - 2 S(i, j)) - E(i) <= |x-_i - x-_j|^2,
+// and every packed vector has norm 1 to rounding, so E(i) is about 2.9e-4 for every row (spherical_kmeans.hip).  With
+// DESIGN.md 4.8's two inequalities (select.hip, cos_proof_lb; D = dim, u = 2^-24 | 2^-53 by the index's type)
+//   | |x-_i - x-_j|^2 - 2 d* | <= eps1 = (4.5 D + 45) 2^-53,      | d_ref - d* | <= E' = (2 D + 16) u
+// the distance the reference computes obeys d_ref(i, j) >= (L - eps1) / 2 - E'.  The kernel evaluates, per accumulator
+// element and in f32, with a32 <= xn(i) - E(i) (fr_row_offset) and key = fl32(cn(j) - 2 S), so a32 + key <= L exactly,
+//   t = fl32(a32 + key),      l = fmaf(t, 0.5, -c),      c >= eps1 / 2 + E' + 2^-21      (c folded on the host, rounded up)
+// one add and one fused multiply-add, no square root.  The allowance 2^-21: |x^| <= 1 + 2^-8 and |x~| <= 2^-8 bound |S| by
+// 1.02, cn <= 1 and -0.01 < a32 <= 1 give |a32 + key| < 4.1 and |t / 2 - c| < 2.1, so both results lie below 8 in magnitude,
+// where a float's half ulp is at most 2^-22: t <= (a32 + key) + 2^-22, l <= (t / 2 - c) + 2^-22, together
+//   l <= (a32 + key) / 2 - c + 2^-23 + 2^-22 < (L - eps1) / 2 - E' <= d_ref(i, j).
+// l may be negative: its key is the signed order-preserving map of exact_scan.hip (dist_key_signed) -- of l for an f32
+// index, of (double)l for an f64 one, an exact and hence monotone conversion.  l is never -0 (c > 0: a fused result is
+// zero only when t / 2 = c exactly, and round-to-nearest makes that +0) and, for an unflagged call, never NaN.  So
+//   lifted(i, j) = max(key(l), ckey[i], ckey[j]) <= key(w(i, j))
+// as above.  Without cores ckey is (K)0 everywhere (mst.hip, fr_keys_kernel), which is the least key of the signed map too
+// -- the key of the negative NaN of all bits set, below every number -- so the maximum leaves key(l) as it is.  The padding's
+// cn is +inf and its core key kMax: never kept.  The re-rank evaluates a candidate by the reference's Cosine::distance
+// in T -- the sequential unfused dot, 1 - dot / (norm_i * norm_j) with the index's own row norms, the expression and the
+// operands of mst_scan_kernel, so both paths deliver the same bits -- on the signed keys.  A call with a flagged row (not
+// finite, or a squared norm outside [2^-100, 2^100]: a zero row) goes to the exact scan as a whole, as above: such a row
+// is a partner of every other row and its reference distance need not be NaN.
+//
 // Layout of the filter.  A workgroup of 4 waves holds 128 listed rows, gathered through the list: their two images lie in
 // LDS ([2][128][dp + 8]) and are the B operands of v_mfma_f32_32x32x16_bf16; wave w owns rows 32 w .. 32 w + 31, the ROW on
 // the lane (lane & 31), 16 partners in the lane's accumulator.  Every row of the index streams past as the A operand in
@@ -39,7 +65,7 @@
 // 160 keeps it at 30 MFMAs (the allowance g = 2^-13 is checked up to 65, pn_bf16_selftest) and the LDS at 130,560 bytes.
 // The stream is cut into segments (grid.y) so that a short list still fills the device; the segments' lists are merged by
 // the re-rank kernel.  Keys are integers and every reduction is a minimum of (key, j); the corpus mean is summed in a
-// fixed shape (blocks of 4096 rows in row order, the blocks in order): no floating-point atomics anywhere, so the images,
+// fixed shape (blocks of 4096 rows in row order, the blocks in order; Euclidean only): no floating-point atomics anywhere, so the images,
 // the lists and the counters of pn_stats depend on the data alone.
 //
 // This translation unit is compiled with -ffp-contract=off: every operation outside the MFMA is plain IEEE, unfused, and
@@ -70,6 +96,24 @@ template <typename K> __device__ __forceinline__ K fr_key_of_f32(float l);  // k
 template <> __device__ __forceinline__ uint32_t fr_key_of_f32<uint32_t>(float l) { return __float_as_uint(l); }
 template <> __device__ __forceinline__ uint64_t fr_key_of_f32<uint64_t>(float l) {
     return (uint64_t)__double_as_longlong((double)l);
+}
+// Cosine: the signed key (exact_scan.hip, dist_key_signed) of a float l that is neither -0 nor NaN, and of a distance in T
+template <typename K> __device__ __forceinline__ K fr_signed_key_of_f32(float l);
+template <> __device__ __forceinline__ uint32_t fr_signed_key_of_f32<uint32_t>(float l) {
+    const uint32_t b = __float_as_uint(l);
+    return b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u);  // (negative: every bit; else: the sign bit)
+}
+template <> __device__ __forceinline__ uint64_t fr_signed_key_of_f32<uint64_t>(float l) {
+    const uint64_t b = (uint64_t)__double_as_longlong((double)l);
+    return b ^ ((uint64_t)((int64_t)b >> 63) | 0x8000000000000000ull);
+}
+__device__ __forceinline__ uint32_t fr_signed_key(float d) {
+    return d != d ? 0xFFC00000u : fr_signed_key_of_f32<uint32_t>(d == 0.0f ? 0.0f : d);
+}
+__device__ __forceinline__ uint64_t fr_signed_key(double d) {
+    if (d != d) return 0xFFF8000000000000ull;
+    const uint64_t b = (uint64_t)__double_as_longlong(d == 0.0 ? 0.0 : d);
+    return b ^ ((uint64_t)((int64_t)b >> 63) | 0x8000000000000000ull);
 }
 template <typename K>
 __device__ __forceinline__ bool fr_before(K ka, uint32_t ja, K kb, uint32_t jb) {
@@ -130,12 +174,13 @@ struct FrMeta {  // a stage's rows: |x - mu|^2 rounded down (+inf: padding), gro
 };
 
 // grid (listed-row tiles, segments), 256 threads.  seg_key / seg_j [seg][nq_pad][kFrM1]
-template <typename K>
+// fc: the constant of the bound folded on the host -- `shrink` (Euclidean), -c (COS); the metric enters in scan() alone
+template <typename K, bool COS>
 __global__ __launch_bounds__(256) void fr_filter_kernel(
     const uint16_t *__restrict__ img, const uint16_t *__restrict__ lo, const float *__restrict__ cn, size_t n, int dp,
     const uint32_t *__restrict__ list, int nq, size_t n_stages, size_t seg_stages, const uint32_t *__restrict__ comp,
     const K *__restrict__ ckey, const double *__restrict__ xn, const float *__restrict__ xh, const float *__restrict__ xl,
-    const float *__restrict__ xe, const unsigned long long *__restrict__ cc, float shrink, K *__restrict__ seg_key,
+    const float *__restrict__ xe, const unsigned long long *__restrict__ cc, float fc, K *__restrict__ seg_key,
     uint32_t *__restrict__ seg_j, size_t nq_pad) {
     constexpr K KMAX = ~(K)0;
     extern __shared__ __align__(16) unsigned char fr_smem[];
@@ -237,9 +282,14 @@ __global__ __launch_bounds__(256) void fr_filter_kernel(
             for (int jj = 0; jj < 4; ++jj) {
                 const int a = v * 32 + 8 * g + 4 * h + jj;
                 const float key = m.cn[a] - 2.0f * acc[4 * g + jj];
-                const float lp = __builtin_fmaf(a32 + key, shrink, -1.0e-36f);
-                const float l = lp > 1.0e-30f ? __builtin_amdgcn_sqrtf(lp) * 0.99999952f : 0.0f;
-                K lifted = fr_key_of_f32<K>(l);
+                K lifted;
+                if constexpr (COS) {
+                    lifted = fr_signed_key_of_f32<K>(__builtin_fmaf(a32 + key, 0.5f, fc));
+                } else {
+                    const float lp = __builtin_fmaf(a32 + key, fc, -1.0e-36f);
+                    const float l = lp > 1.0e-30f ? __builtin_amdgcn_sqrtf(lp) * 0.99999952f : 0.0f;
+                    lifted = fr_key_of_f32<K>(l);
+                }
                 const K cj = m.ck[a];
                 lifted = lifted > ck_i ? lifted : ck_i;
                 lifted = lifted > cj ? lifted : cj;
@@ -291,8 +341,9 @@ __global__ __launch_bounds__(256) void fr_filter_kernel(
 }
 
 // ---- merge of the segments' lists, re-rank and proof: one thread per listed row.  ctr[0]: the rows listed for the exact
-// scan (sel[slot]), ctr[1]: the candidates evaluated.
-template <typename T>
+// scan (sel[slot]), ctr[1]: the candidates evaluated.  COS: the edge is Cosine::distance with the index's row norms
+// cnorm [n] on the signed keys (mst_scan_kernel's expression: the same bits); else cnorm is not read.
+template <typename T, bool COS>
 __global__ __launch_bounds__(64) void fr_rerank_kernel(const T *__restrict__ X, size_t ld, int dim,
                                                        const uint32_t *__restrict__ list, size_t nq, size_t nq_pad, int nseg,
                                                        const typename KeyOf<T>::type *__restrict__ seg_key,
@@ -302,7 +353,7 @@ __global__ __launch_bounds__(64) void fr_rerank_kernel(const T *__restrict__ X, 
                                                        const unsigned long long *__restrict__ cc,
                                                        typename KeyOf<T>::type *__restrict__ cand_key,
                                                        uint32_t *__restrict__ cand_j, uint32_t *__restrict__ sel,
-                                                       uint32_t *__restrict__ ctr) {
+                                                       uint32_t *__restrict__ ctr, const T *__restrict__ cnorm) {
 #pragma clang fp contract(off)
     using K = typename KeyOf<T>::type;
     constexpr K KMAX = KeyOf<T>::kMax;
@@ -333,18 +384,30 @@ __global__ __launch_bounds__(64) void fr_rerank_kernel(const T *__restrict__ X, 
         if (ok) {
             const T *xi = X + i * ld;
             const K ci = ckey[i];
+            T ni = (T)0;
+            if constexpr (COS) ni = cnorm[i];
 #pragma unroll
             for (int e = 0; e < kFrM; ++e) {
                 const uint32_t j = lj[e];
                 if (j == kFrNoRow) break;
                 const T *xj = X + (size_t)j * ld;
                 T sum = (T)0;
-                for (int k = 0; k < dim; ++k) {
-                    const T diff = xi[k] - xj[k];
-                    const T sq = diff * diff;
-                    sum = sum + sq;
+                K kk;
+                if constexpr (COS) {
+                    for (int k = 0; k < dim; ++k) {
+                        const T pr = xi[k] * xj[k];
+                        sum = sum + pr;
+                    }
+                    const T den = ni * cnorm[j];
+                    kk = fr_signed_key((T)1 - sum / den);
+                } else {
+                    for (int k = 0; k < dim; ++k) {
+                        const T diff = xi[k] - xj[k];
+                        const T sq = diff * diff;
+                        sum = sum + sq;
+                    }
+                    kk = km_dist_key<T>(km_sqrt<T>(sum));
                 }
-                K kk = km_dist_key<T>(km_sqrt<T>(sum));
                 const K cj = ckey[j];
                 kk = kk > ci ? kk : ci;
                 kk = kk > cj ? kk : cj;
@@ -429,10 +492,15 @@ void foreign_tier_at(void *buf, size_t n, int dim, int elem_bytes, size_t batch,
 }
 
 template <typename T>
-hipError_t foreign_pack(const ForeignTier &t, const T *X, size_t n, size_t ld, int dim, hipStream_t s) {
+hipError_t foreign_pack(const ForeignTier &t, const T *X, size_t n, size_t ld, int dim, bool cosine, hipStream_t s) {
     // (kernels, not memsets: the words are cleared in stream order whatever the caller's stream is captured into)
     const size_t nblk = fr_sum_blocks(n);
     km_zero_words(t.cc, 8, s);
+    if (cosine) {  // normalised, not translated: no mean (t.mu and t.sums stay unused)
+        hipLaunchKernelGGL((km_pack_kernel<T, true, true>), dim3((unsigned)((t.n_img + 3) / 4)), dim3(256), 0, s, X, n, t.n_img,
+                           ld, dim, t.dp, t.img, t.lo, t.xn, t.xh, t.xl, t.xe, t.cn, t.cc, (const float *)nullptr);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL((fr_colsum_kernel<T>), dim3((unsigned)nblk), dim3(256), 0, s, X, n, ld, dim, t.sums);
     hipLaunchKernelGGL(fr_mean_kernel, dim3((unsigned)((dim + 63) / 64)), dim3(64), 0, s, t.sums, nblk, n, dim, t.mu);
     hipLaunchKernelGGL((km_pack_kernel<T, true>), dim3((unsigned)((t.n_img + 3) / 4)), dim3(256), 0, s, X, n, t.n_img, ld, dim,
@@ -442,7 +510,7 @@ hipError_t foreign_pack(const ForeignTier &t, const T *X, size_t n, size_t ld, i
 
 template <typename T>
 hipError_t launch_foreign_filter(const ForeignTier &t, const T *X, size_t n, size_t ld, int dim, const uint32_t *list,
-                                 size_t nq, const uint32_t *comp, const typename KeyOf<T>::type *ckey,
+                                 size_t nq, const uint32_t *comp, const typename KeyOf<T>::type *ckey, const T *cnorm,
                                  typename KeyOf<T>::type *cand_key, uint32_t *cand_j, hipStream_t s) {
     using K = typename KeyOf<T>::type;
     if (nq == 0) return hipSuccess;
@@ -451,27 +519,36 @@ hipError_t launch_foreign_filter(const ForeignTier &t, const T *X, size_t n, siz
     if (p.nseg * nq_pad * kFrM1 > t.seg_entries) return hipErrorInvalidValue;
     const int sub = fr_sub(t.dp), srows = 32 * sub, pitch = t.dp + 8;
     const size_t lds = ((size_t)2 * kFrRows + (size_t)4 * srows) * pitch * 2 + (size_t)3 * srows * (8 + sizeof(K));
-    static LdsAttrOnce once;
-    if (lds > 64 * 1024) {
-        const hipError_t e = once.ensure((const void *)fr_filter_kernel<K>, kFrMaxLds);
-        if (e != hipSuccess) return e;
-    }
     const double u = sizeof(T) == 4 ? 5.9604644775390625e-08 : 1.1102230246251565e-16;
-    const float shrink = (float)(1.0 - (double)(dim + 4) * u - 1.0e-6);
     km_zero_words(t.ctr, 2, s);
-    hipLaunchKernelGGL((fr_filter_kernel<K>), dim3((unsigned)p.qt, (unsigned)p.nseg), dim3(256), lds, s, t.img, t.lo, t.cn, n,
-                       t.dp, list, (int)nq, p.n_stages, p.seg_stages, comp, ckey, t.xn, t.xh, t.xl, t.xe, t.cc, shrink,
-                       (K *)t.seg_key, t.seg_j, nq_pad);
-    hipLaunchKernelGGL((fr_rerank_kernel<T>), dim3((unsigned)((nq + 63) / 64)), dim3(64), 0, s, X, ld, dim, list, nq, nq_pad,
-                       (int)p.nseg, (const K *)t.seg_key, t.seg_j, ckey, t.xn, t.cc, cand_key, cand_j, t.sel, t.ctr);
-    return hipGetLastError();
+    auto run = [&](auto cos, float fc) -> hipError_t {  // (one instantiation, and one LDS attribute, per metric)
+        constexpr bool COS = decltype(cos)::value;
+        static LdsAttrOnce once;
+        if (lds > 64 * 1024) {
+            const hipError_t e = once.ensure((const void *)fr_filter_kernel<K, COS>, kFrMaxLds);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL((fr_filter_kernel<K, COS>), dim3((unsigned)p.qt, (unsigned)p.nseg), dim3(256), lds, s, t.img, t.lo,
+                           t.cn, n, t.dp, list, (int)nq, p.n_stages, p.seg_stages, comp, ckey, t.xn, t.xh, t.xl, t.xe, t.cc, fc,
+                           (K *)t.seg_key, t.seg_j, nq_pad);
+        hipLaunchKernelGGL((fr_rerank_kernel<T, COS>), dim3((unsigned)((nq + 63) / 64)), dim3(64), 0, s, X, ld, dim, list, nq,
+                           nq_pad, (int)p.nseg, (const K *)t.seg_key, t.seg_j, ckey, t.xn, t.cc, cand_key, cand_j, t.sel, t.ctr,
+                           cnorm);
+        return hipGetLastError();
+    };
+    if (cnorm) {  // -c of the header: c >= eps1 / 2 + E' + 2^-21, and the conversion to float rounds it up
+        const double c = 0.5 * (4.5 * (double)dim + 45.0) * 1.1102230246251565e-16 + (2.0 * (double)dim + 16.0) * u +
+                         4.76837158203125e-07;
+        return run(std::true_type{}, -(float)(c * (1.0 + 2.4e-7)));
+    }
+    return run(std::false_type{}, (float)(1.0 - (double)(dim + 4) * u - 1.0e-6));
 }
 
 #define PN_FR_INSTANTIATE(T)                                                                                          \
-    template hipError_t foreign_pack<T>(const ForeignTier &, const T *, size_t, size_t, int, hipStream_t);            \
+    template hipError_t foreign_pack<T>(const ForeignTier &, const T *, size_t, size_t, int, bool, hipStream_t);      \
     template hipError_t launch_foreign_filter<T>(const ForeignTier &, const T *, size_t, size_t, int, const uint32_t *, \
-                                                 size_t, const uint32_t *, const KeyOf<T>::type *, KeyOf<T>::type *,   \
-                                                 uint32_t *, hipStream_t);
+                                                 size_t, const uint32_t *, const KeyOf<T>::type *, const T *,          \
+                                                 KeyOf<T>::type *, uint32_t *, hipStream_t);
 PN_FR_INSTANTIATE(float)
 PN_FR_INSTANTIATE(double)
 #undef PN_FR_INSTANTIATE

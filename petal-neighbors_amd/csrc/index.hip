@@ -1116,7 +1116,7 @@ extern "C" int pn_index_set_option(pn_index *ix, int option, int64_t value) {
             ix->kmeans_filter = (int)value;
             return PN_OK;
         case PN_OPT_FOREIGN_FILTER:
-            if (value < 0 || value > 2) return fail(PN_ERR_INVALID, "bad foreign-row filter choice %lld", (long long)value);
+            if (value < 0 || value > 3) return fail(PN_ERR_INVALID, "bad foreign-row filter choice %lld", (long long)value);
             ix->foreign_filter = (int)value;
             return PN_OK;
         default: return fail(PN_ERR_INVALID, "unknown option %d", option);
@@ -3994,27 +3994,30 @@ extern "C" int pn_optics_dbscan_device_f64(const pn_index *ix, const uint64_t *d
 // workspace, and round 0 of an un-cored call -- every row's nearest other row by (distance, index), which is the k = 1
 // self-query and so goes through query_enqueue and whichever tier the handle's engine selects.
 // ---------------------------------------------------------------------------
-// The first tier of the masked scans (foreign.hip): Euclidean indexes of 8 <= dim <= 160.  PN_ENGINE_AUTO (and
+// The first tier of the masked scans (foreign.hip): indexes of 8 <= dim <= 160.  Euclidean: PN_ENGINE_AUTO (and
 // PN_ENGINE_MFMA) takes it from kFrAutoMinRows rows and kFrAutoMinDim columns on: the smallest shape measured (DESIGN.md
 // 4.25), where the forced tier takes 0.65 - 0.70 of the exact scans' time at 16 columns and 0.40 - 0.44 at 128.  Below it
 // nothing is measured and the exact scan stays: its whole work shrinks with n^2, the tier's fixed cost -- packing the rows,
 // one host wait per batch -- does not.
 constexpr size_t kFrAutoMinRows = 100000, kFrAutoMinDim = 16;
+// Cosine indexes: the same line.  It is the smallest shape measured there too, and the forced tier takes
+// 0.67 - 0.78 of the exact scans' time at 16 columns and 0.48 - 0.67 at 128, the repeats within 1 %.
 static bool fr_use_filter(const pn_index *ix) {
-    if (ix->n < 2 || ix->metric != 0 || !foreign_filter_supported((int)ix->dim) || ix->foreign_filter == 2) return false;
-    if (ix->foreign_filter == 1) return true;
+    if (ix->n < 2 || !foreign_filter_supported((int)ix->dim) || ix->foreign_filter == 2) return false;
+    if (ix->foreign_filter == 3) return true;
+    if (ix->foreign_filter == 1) return ix->metric == 0;  // (1 names the Euclidean tier: a Cosine handle keeps the exact scan)
     if (ix->engine == PN_ENGINE_EXACT) return false;
     if (ix->engine == PN_ENGINE_BF16) return true;
     return ix->n >= kFrAutoMinRows && ix->dim >= kFrAutoMinDim;
 }
 // the tier of a call whose scans take at most `batch` rows per launch: carved and packed, once.  *usable <- false when a
-// row is flagged (not finite, or a squared norm beyond 2^100): the bound holds for no pair of such a call, so the exact scan
+// row is flagged (not finite, or a squared norm beyond 2^100; Cosine: outside [2^-100, 2^100]): the bound holds for no pair of such a call, so the exact scan
 // answers all of it and the tier is not launched at all -- the host reads that one word here, once per call.
 template <typename T>
 static int fr_prepare(const pn_index *ix, Workspace &ws, size_t batch, ForeignTier *t, bool *usable, hipStream_t s) {
     PNCHK(ws.w_fr_tier.ensure(foreign_tier_bytes(ix->n, (int)ix->dim, (int)sizeof(T), batch, ix->n_cu)));
     foreign_tier_at(ws.w_fr_tier.p, ix->n, (int)ix->dim, (int)sizeof(T), batch, ix->n_cu, t);
-    HIPCHK(foreign_pack<T>(*t, (const T *)ix->d_pts, ix->n, ix->ld, (int)ix->dim, s));
+    HIPCHK(foreign_pack<T>(*t, (const T *)ix->d_pts, ix->n, ix->ld, (int)ix->dim, ix->metric == 1, s));
     unsigned long long flagged = 0;
     HIPCHK(hipMemcpyAsync(&flagged, t->cc + 4, sizeof flagged, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));

@@ -353,7 +353,7 @@ struct Layout {
 
 // ---- the listed masked scan: rows list[0 .. nlist) -> their least (key(w), j) over the rows of other components / groups,
 // into cand_key / cand_j [row].  `batch` rows per launch; the exact scan's segments are sized so that a short list still
-// fills the device.  With a tier (foreign.hip, Euclidean only) the first tier answers a batch first and the exact scan the
+// fills the device.  With a tier (foreign.hip) the first tier answers a batch first and the exact scan the
 // rows it could not prove: the host reads their number once per batch -- to plan that scan, and for the counters.
 template <typename T>
 struct ListedScan {
@@ -402,7 +402,8 @@ int scan_listed_rows(const ListedScan<T> &c, const uint32_t *list, size_t nlist,
             if (rc != PN_OK) return rc;
             continue;
         }
-        MSTCHK(launch_foreign_filter<T>(*c.tier, c.P, c.n, c.ld, c.dim, list + r0, nq, c.comp, c.ckey, c.cand_key, c.cand_j, s));
+        MSTCHK(launch_foreign_filter<T>(*c.tier, c.P, c.n, c.ld, c.dim, list + r0, nq, c.comp, c.ckey, c.cnorm, c.cand_key,
+                                        c.cand_j, s));
         uint32_t h[2] = {0, 0};
         MSTCHK(hipMemcpyAsync(h, c.tier->ctr, sizeof h, hipMemcpyDeviceToHost, s));
         MSTCHK(hipStreamSynchronize(s));
@@ -425,7 +426,7 @@ __global__ __launch_bounds__(256) void fr_keys_kernel(size_t n, const T *__restr
                                                       typename KeyOf<T>::type *__restrict__ ckey) {
     using K = typename KeyOf<T>::type;
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) ckey[i] = core ? key_of<T>(core[i], signed_keys) : (K)0;
+    if (i < n) ckey[i] = core ? key_of<T>(core[i], signed_keys) : (K)0;  // (no cores: the least key of either map, w = d)
 }
 // (a row number at or beyond n is scanned as row 0 and answered as a row without a foreign row)
 __global__ __launch_bounds__(256) void fr_list_kernel(size_t m, size_t n, const uint64_t *__restrict__ rows,

@@ -180,9 +180,10 @@ hipError_t launch_mst_scan(const T *P, size_t n, int dim, size_t ldp, const uint
                            int nseg, const uint32_t *comp, const typename KeyOf<T>::type *ckey, const T *cnorm,
                            typename KeyOf<T>::type *seg_key, uint32_t *seg_j, hipStream_t s);
 
-// ---- foreign.hip: the first tier of the masked scan on Euclidean indexes: a bf16 MFMA self-join of the
-// listed rows against every row, an exact re-rank of m candidates per row and a proof in key order.  Nothing in it waits
-// for the device.  The tier's state of one call, carved from one 16-byte aligned buffer (foreign_tier_bytes/_at):
+// ---- foreign.hip: the first tier of the masked scan on Euclidean and Cosine (4.29) indexes: a bf16 MFMA
+// self-join of the listed rows against every row, an exact re-rank of m candidates per row and a proof in key order.
+// Nothing in it waits for the device.  Cosine: the rows are packed normalised and not centred -- xn and cn are those of
+// x / |x|, mu and sums stay unused.  The tier's state of one call, carved from one 16-byte aligned buffer (foreign_tier_bytes/_at):
 struct ForeignTier {
     // the centred two-image packing of all n rows (km_pack.h; the fields of KmRowImage)
     uint16_t *img = nullptr, *lo = nullptr;   // [n_img][dp] bf16 bits each, rows at and beyond n zero
@@ -205,15 +206,16 @@ bool foreign_filter_supported(int dim);  // 8 <= dim <= 160
 constexpr size_t kFrMinLaunch = 64;  // a scan launch of fewer listed rows than half a tile of the tier takes the exact scan
 size_t foreign_tier_bytes(size_t n, int dim, int elem_bytes, size_t batch, int n_cu);
 void foreign_tier_at(void *buf, size_t n, int dim, int elem_bytes, size_t batch, int n_cu, ForeignTier *t);
-// mean, images, norms and maxima of the rows: once per call
+// mean (Euclidean), images, norms and maxima of the rows: once per call.  cosine: a Cosine index
 template <typename T>
-hipError_t foreign_pack(const ForeignTier &t, const T *X, size_t n, size_t ld, int dim, hipStream_t s);
+hipError_t foreign_pack(const ForeignTier &t, const T *X, size_t n, size_t ld, int dim, bool cosine, hipStream_t s);
 // Listed rows list[0 .. nq) (nq <= the tier's batch) against every row: a proven row's least (key(w), j) over the rows j
 // with comp[j] != comp[row] goes to cand_key / cand_j [row] (kMax / 0xFFFFFFFF: there is none); the others are listed in
-// t.sel[0 .. t.ctr[0]), any order; t.ctr[1] <- the candidates evaluated.  comp, ckey [n]: as launch_mst_scan takes them.
+// t.sel[0 .. t.ctr[0]), any order; t.ctr[1] <- the candidates evaluated.  comp, ckey [n], cnorm (NULL: Euclidean; t is
+// packed for the same metric): as launch_mst_scan takes them.
 template <typename T>
 hipError_t launch_foreign_filter(const ForeignTier &t, const T *X, size_t n, size_t ld, int dim, const uint32_t *list,
-                                 size_t nq, const uint32_t *comp, const typename KeyOf<T>::type *ckey,
+                                 size_t nq, const uint32_t *comp, const typename KeyOf<T>::type *ckey, const T *cnorm,
                                  typename KeyOf<T>::type *cand_key, uint32_t *cand_j, hipStream_t s);
 
 // ---- mst.hip: the listed masked scan behind pn_mst_* and pn_nearest_foreign_*, Boruvka under the strict edge order

@@ -8,11 +8,13 @@ with the k = 10 core distances (query_self_device(10)'s last column), interleave
 --tiers measures mst_device three times instead, interleaved: with the first tier of the masked scans (foreign.hip) never
 used (PN_OPT_FOREIGN_FILTER = 2: the exact scans alone), forced (1) and as PN_ENGINE_AUTO decides (0), and records what
 the forced tier left to the exact scan (pn_stats.fallback_queries over the rows scanned).  --dim sets the row width.
+--metric cosine builds BallTree.new(x, Cosine()) over the same rows (the uniform ones shifted by -0.5, so that angles
+spread) and forces the tier with PN_OPT_FOREIGN_FILTER = 3; "exact" is then the only path such an index had before.
 --trace also runs each configuration once in a child process under `rocprofv3 --kernel-trace --stats` and adds the summed
 durations of the masked scan kernel (scan_kernel_ms: mst_scan_kernel) and of the first tier's filter kernel
 (filter_kernel_ms: fr_filter_kernel).  Appends one JSON line to profiles/mst_bench.jsonl (--out).
 usage: python tools/bench_mst.py [--reps 3] [--n 100000,1000000] [--dim 16] [--only uniform|blobs] [--cores 0,1] [--tiers]
-       [--trace] [--out FILE]"""
+       [--metric euclidean|cosine] [--trace] [--out FILE]"""
 import argparse
 import csv
 import glob
@@ -73,18 +75,24 @@ def blob_rows(n, dim, nb, sigma, background, seed):
 
 
 DIM = 16
+COSINE = False
 PN_OPT_FOREIGN_FILTER = 17
 
 
 def rows_of(kind, n):
     if kind == "uniform":
-        return uniform_rows(n, DIM, 0x5E1F5EEE)
+        x = uniform_rows(n, DIM, 0x5E1F5EEE)
+        return x - 0.5 if COSINE else x
     return blob_rows(n, DIM, max(1, n * 12 // 12000), 0.05, 0.10, 3)
+
+
+def tree_of(x):
+    return pn.BallTree.new(x.cpu().numpy(), pn.distance.Cosine()) if COSINE else pn.BallTree.from_device(x)
 
 
 def measure_tiers(kind, n, cored, reps):
     x = rows_of(kind, n)
-    tree = pn.BallTree.from_device(x)
+    tree = tree_of(x)
     core = tree.query_self_device(K_CORE)[1][:, -1].contiguous() if cored else None
     outs = dict(out_src=torch.empty(n - 1, dtype=torch.int64, device=DEV), out_dst=torch.empty(n - 1, dtype=torch.int64, device=DEV),
                 out_weight=torch.empty(n - 1, dtype=torch.float32, device=DEV))
@@ -95,14 +103,15 @@ def measure_tiers(kind, n, cored, reps):
             tree.mst_device(core, **outs)
         return f
 
-    t_exact, t_forced, t_auto = interleaved([run(2), run(1), run(0)], reps)
+    forced = 3 if COSINE else 1
+    t_exact, t_forced, t_auto = interleaved([run(2), run(forced), run(0)], reps)
     tree.stats(reset=True)
-    run(1)()
+    run(forced)()
     st = tree.stats()
     rounds, scanned = tree.last_mst_work
     listed = scanned - (0 if cored else n)  # (round 0 of an un-cored call is the 1-NN self-query)
-    rec = {"n": n, "dim": DIM, "k_core": K_CORE if cored else 0, "rounds": rounds, "rows_scanned": scanned,
-           "mst_exact_scans_ms": [round(v, 2) for v in t_exact], "mst_forced_tier_ms": [round(v, 2) for v in t_forced],
+    rec = {"n": n, "dim": DIM, "metric": "cosine" if COSINE else "euclidean", "k_core": K_CORE if cored else 0,
+           "rounds": rounds, "rows_scanned": scanned, "mst_exact_scans_ms": [round(v, 2) for v in t_exact], "mst_forced_tier_ms": [round(v, 2) for v in t_forced],
            "mst_auto_ms": [round(v, 2) for v in t_auto], "tier_rows": listed,
            "tier_left_to_exact": st["fallback_queries"], "tier_left_rate": round(st["fallback_queries"] / max(listed, 1), 5),
            "tier_candidates": st["candidates"]}
@@ -112,7 +121,7 @@ def measure_tiers(kind, n, cored, reps):
 
 def measure(kind, n, cored, reps):
     x = rows_of(kind, n)
-    tree = pn.BallTree.from_device(x)
+    tree = tree_of(x)
     core = None
     if cored:
         core = tree.query_self_device(K_CORE)[1][:, -1].contiguous()
@@ -154,7 +163,7 @@ def traced_scan_ms(kind, n, cored):
     """summed durations of mst_scan_kernel and of the first tier's fr_filter_kernel over ONE mst_device call (plus its warm-up: halved), in a fresh child process"""
     with tempfile.TemporaryDirectory() as d:
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "mst", "--", sys.executable,
-               os.path.abspath(__file__), "--child", kind, str(n), "1" if cored else "0", str(DIM)]
+               os.path.abspath(__file__), "--child", kind, str(n), "1" if cored else "0", str(DIM), "1" if COSINE else "0"]
         subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL)
         total = {"mst_scan_kernel": 0.0, "fr_filter_kernel": 0.0}
         for f in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
@@ -167,7 +176,7 @@ def traced_scan_ms(kind, n, cored):
 
 def child(kind, n, cored):
     x = rows_of(kind, n)
-    tree = pn.BallTree.from_device(x)
+    tree = tree_of(x)
     core = tree.query_self_device(K_CORE)[1][:, -1].contiguous() if cored else None
     for _ in range(2):
         tree.mst_device(core)
@@ -176,9 +185,10 @@ def child(kind, n, cored):
 
 
 def main():
-    global DIM
+    global DIM, COSINE
     if len(sys.argv) > 1 and sys.argv[1] == "--child":
         DIM = int(sys.argv[5]) if len(sys.argv) > 5 else 16
+        COSINE = len(sys.argv) > 6 and sys.argv[6] == "1"
         child(sys.argv[2], int(sys.argv[3]), sys.argv[4] == "1")
         return
     ap = argparse.ArgumentParser()
@@ -189,9 +199,10 @@ def main():
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--tiers", action="store_true")
     ap.add_argument("--dim", type=int, default=16)
+    ap.add_argument("--metric", default="euclidean", choices=["euclidean", "cosine"])
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mst_bench.jsonl"))
     args = ap.parse_args()
-    DIM = args.dim
+    DIM, COSINE = args.dim, args.metric == "cosine"
     res = {"tool": "bench_mst"}
     for kind in ("uniform", "blobs"):
         if args.only not in ("", kind):
@@ -200,7 +211,7 @@ def main():
             for cored in (c == "1" for c in args.cores.split(",")):
                 tag = f"{kind}_{n}_{'k10' if cored else 'plain'}"
                 if args.tiers:
-                    tag += f"_d{DIM}_tiers"
+                    tag += f"_d{DIM}_tiers" + ("_cosine" if COSINE else "")
                 res[tag] = (measure_tiers if args.tiers else measure)(kind, n, cored, args.reps)
                 torch.cuda.empty_cache()
                 if args.trace:
